@@ -34,7 +34,7 @@ int td_abi_version(void);
  * to_q/k/v, to_out, ff, proj_mlp, proj_out [ext diffusers 0.31.0 transformer_flux.py], Qwen2-VL
  * q/k/v/o/gate/up/down [ext vLLM fork].  K % 64 == 0, N % 8 == 0; bias/gate/res may be NULL; res may
  * alias y.  Rounding points follow the reference's bf16 pipeline: Linear output, activation, gate
- * multiply and residual add each round to bf16. */
+ * multiply and residual add each round to bf16.  act = TD_ACT_ID_* (other codes: TD_ERR_INVALID). */
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
                    void* stream);
@@ -301,7 +301,7 @@ int td_layernorm_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows
                       const void* w, const void* b, void* stream);
 /* out[r,:] = a[r,:] + b[r % b_rows,:]  (token + position embeddings, bias rows). */
 int td_add_rows_bf16(const void* a, const void* b, void* out, int rows, int D, int b_rows, void* stream);
-/* out[m,j] = act(gu[m,j]) * gu[m,I+j]  (T5 gated-GELU / SwiGLU); act = TD_ACT_ID_*. */
+/* out[m,j] = act(gu[m,j]) * gu[m,I+j]  (T5 gated-GELU / SwiGLU); act = any TD_ACT_ID_* (other codes: TD_ERR_INVALID). */
 int td_glu_mul_bf16(const void* gate_up, void* out, int rows, int I, int act, void* stream);
 /* td_attention_bf16 with an additive fp32 score bias [Hq,Sq,Skv] (T5 relative position bias), batch 1. */
 int td_attention_bias_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo,

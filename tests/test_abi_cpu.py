@@ -85,3 +85,23 @@ def test_oversize_element_counts_are_refused_not_truncated():
         msg = lib.td_last_error()
         assert rc == 2, (what, rc, msg)
         assert b"2^32" in msg or b"32-bit index" in msg, (what, msg)
+
+
+def test_unknown_activation_codes_are_refused_without_a_gpu():
+    """Activation codes outside 0 .. 4 (TD_ACT_NONE .. TD_ACT_QUICK_GELU) are an argument error on every entry that takes one -- the
+    tile GEMM and the skinny-M weight stream (both behind td_gemm_launch) and td_glu_mul -- before any HIP call."""
+    lib = ctypes.CDLL(LIB)
+    lib.td_last_error.restype = ctypes.c_char_p
+    one = ctypes.c_void_p(256)                          # never dereferenced
+    i64 = ctypes.c_int64
+    for code in (5, -1, 1000):
+        for M in (1, 17, 300):                          # dot-product stream, matrix-core stream, tile kernels
+            rc = lib.td_linear_bf16(one, i64(128), one, None, one, i64(64), M, 64, 128, code, None, None, i64(0), None)
+            assert rc == 2 and b"activation" in lib.td_last_error(), (code, M, lib.td_last_error())
+            rc = lib.td_linear_split_bf16(one, i64(128), one, None, one, i64(32), 0, one, i64(32), code, M, 64, 128, 32, None)
+            assert rc == 2 and b"activation" in lib.td_last_error(), (code, M, lib.td_last_error())
+        rc = lib.td_linear_grouped2_bf16(one, 300, one, None, None, None, one, None, 0, None, None, None, None, None,
+                                         i64(128), i64(64), i64(0), 64, 128, code, 0, None)
+        assert rc == 2 and b"activation" in lib.td_last_error(), (code, lib.td_last_error())
+        rc = lib.td_glu_mul_bf16(one, one, 4, 64, code, None)
+        assert rc == 2 and b"activation" in lib.td_last_error(), (code, lib.td_last_error())

@@ -275,3 +275,116 @@ def test_running_maximum_forms_never_miss_a_score(hip, form):
     o = out.float()
     assert torch.isfinite(o).all()
     assert float(o.min()) >= -1e-3 and float(o.max()) <= 1.0 + 2.0 ** -7      # values lie in [0, 1): so does every probability-weighted mean of them
+
+
+# ---- causal attention against a KV cache: decode (Sq = 1) and cached prefill (1 < Sq < Skv) ------------------------------
+
+def _ref64(q, k, v, Hq, Hkv):
+    """float64 causal attention of the last Sq positions against Skv keys (query i sees keys j <= i + Skv - Sq)."""
+    B, Sq, _ = q.shape
+    Skv = k.shape[1]
+    qh = q.double().reshape(B, Sq, Hq, 128).transpose(1, 2)
+    kh = k.double().reshape(B, Skv, Hkv, 128).transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
+    vh = v.double().reshape(B, Skv, Hkv, 128).transpose(1, 2).repeat_interleave(Hq // Hkv, dim=1)
+    s = qh @ kh.transpose(-1, -2) / math.sqrt(128)
+    i = torch.arange(Sq)[:, None] + (Skv - Sq)
+    s = s.masked_fill(torch.arange(Skv)[None, :] > i, float("-inf"))
+    o = torch.softmax(s, dim=-1) @ vh
+    return o.transpose(1, 2).reshape(B, Sq, Hq * 128)
+
+
+def _cache(B, Skv, Hkv, g, vmode, dom, q):
+    """k, v [B, max_len, Hkv*128] views into one cache-shaped buffer (k | v | pad columns, max_len > Skv rows, the rows past Skv
+    filled with large values that must not be read).  vmode: 'randn', 'big' (|v| up to 1e3) or 'offset' (a common offset of 500).
+    dom: None or the key index made dominant for every q head of its kv head."""
+    max_len, ld = Skv + 7, 2 * Hkv * 128 + 64
+    buf = torch.randn(B, max_len, ld, generator=g)
+    Hq = q.shape[2] // 128
+    if vmode == "big":
+        buf[:, :, Hkv * 128:2 * Hkv * 128] *= 330.0
+        buf[:, :, Hkv * 128:2 * Hkv * 128].clamp_(-1000.0, 1000.0)
+    elif vmode == "offset":
+        buf[:, :, Hkv * 128:2 * Hkv * 128] += 500.0
+    if dom is not None:
+        qg = q.float().reshape(B, Hq, 128).reshape(B, Hkv, Hq // Hkv, 128).sum(dim=2)      # [B, Hkv, 128]
+        buf[:, dom, :Hkv * 128] = 3.0 * qg.reshape(B, Hkv * 128)
+    buf[:, Skv:, :] = 1e4                 # rows past the sequence: would dominate every score / value if read
+    buf = buf.bfloat16()
+    return buf, buf[:, :Skv, :Hkv * 128], buf[:, :Skv, Hkv * 128:2 * Hkv * 128]
+
+
+# (Hq, Hkv, Skv, batch, dominant key, v mode): every value of every axis at least once; the long caches with small batches
+DECODE_CASES = [
+    (12, 2, 1, 70, None, "randn"), (28, 4, 2, 3, "last_key", "big"), (4, 4, 15, 3, "first", "offset"), (7, 1, 16, 70, "last_slot", "randn"),
+    (12, 2, 17, 3, "last_key", "big"), (28, 4, 63, 1, "first", "randn"), (7, 1, 64, 3, "last_slot", "offset"), (4, 4, 65, 70, "last_key", "randn"),
+    (12, 2, 300, 70, None, "big"), (28, 4, 300, 70, "last_slot", "randn"), (28, 4, 1025, 3, "last_key", "offset"), (7, 1, 8192, 1, "first", "big"),
+    (12, 2, 8192, 1, "last_slot", "randn"),
+]
+
+
+@pytest.mark.parametrize("Hq,Hkv,Skv,B,dom,vmode", DECODE_CASES)
+def test_decode_against_cache(hip, request, Hq, Hkv, Skv, B, dom, vmode):
+    """Sq = 1, causal through hip.attention: td_attention_bf16 routes it to the decode kernel (csrc/attention_decode.hip: 16 key slots
+    over 4 waves, fp32 softmax and accumulation) under 'auto', to the tile kernel under the other variants.  k / v are read from a
+    cache-shaped buffer (batch stride max_len x ld with max_len > Skv).  Every forced q-head group that divides Hq / Hkv runs, and the
+    automatic choice; a second launch must give identical bits.
+
+    Bound under 'auto' (P stays fp32): |err| <= 1 bf16 ulp of the reference + 2^-12 max |v| of the kv head (the fp32 softmax
+    weights carry ~1e-6 relative error, which the value offset / magnitude scales).  Under variants 1 / 2 the tile kernel rounds P
+    to bf16: the module's 2^-7 of the output scale."""
+    variant = request.node.callspec.params["all_variants"]
+    g = torch.Generator().manual_seed(Skv * 131 + B * 7 + Hq)
+    q = torch.randn(B, 1, Hq * 128, generator=g).bfloat16()
+    qbuf = torch.zeros(B, 1, Hq * 128 + 64, dtype=torch.bfloat16)
+    qbuf[:, :, :Hq * 128] = q
+    pos = {None: None, "first": 0, "last_slot": min(15, Skv - 1), "last_key": Skv - 1}[dom]
+    buf, k, v = _cache(B, Skv, Hkv, g, vmode, pos, q)
+    ref = _ref64(q, k, v, Hq, Hkv)
+    dbuf = buf.cuda()
+    dk, dv = dbuf[:, :Skv, :Hkv * 128], dbuf[:, :Skv, Hkv * 128:2 * Hkv * 128]
+    dq = qbuf.cuda()[:, :, :Hq * 128]
+    groups = [0] + [gg for gg in (1, 2, 3, 4, 6, 7) if (Hq // Hkv) % gg == 0] if variant == 0 else [0]
+    vmax = v.double().abs().reshape(B, 1, Skv, Hkv, 128).amax(dim=(2, 4))                                # [B, 1, Hkv]
+    vmax = vmax.repeat_interleave(Hq // Hkv * 128, dim=2)                                               # [B, 1, Hq*128]
+    worst = 0.0
+    for grp in groups:
+        prev = hip.lib().td_attention_decode_set_group(grp)
+        try:
+            outs = []
+            for _ in range(2):
+                out = torch.full((B, 1, Hq * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+                hip.attention(dq, dk, dv, out, Hq, Hkv, causal=True)
+                outs.append(out)
+            torch.cuda.synchronize()
+        finally:
+            hip.lib().td_attention_decode_set_group(prev)
+        assert torch.equal(outs[0], outs[1]), f"group {grp}: a repeated launch gave different bits"
+        got = outs[0].double().cpu()
+        assert torch.isfinite(got).all()
+        if variant == 0:
+            a = ref.abs().clamp_min(2.0 ** -126)
+            tol = torch.exp2(torch.floor(torch.log2(a)) - 7) + 2.0 ** -12 * vmax
+            r = ((got - ref).abs() / tol).max().item()
+            worst = max(worst, r)
+            assert r <= 1.0, f"group {grp}: max error {r:.3g} x the bound"
+        else:
+            worst = max(worst, ((got - ref).abs().max() / ref.abs().max()).item() / 2.0 ** -7)
+            _check(outs[0], ref)
+    print(f"decode variant {variant} Hq={Hq} Hkv={Hkv} Skv={Skv} B={B}: max error {worst:.3f} x the bound")
+
+
+@pytest.mark.parametrize("Sq,Skv", [(2, 300), (17, 64), (256, 1029), (300, 4096)])
+def test_cached_prefill_causal_gqa(hip, Sq, Skv):
+    """1 < Sq < Skv, causal, GQA: a prefill chunk against a longer cache (query i sees keys j <= i + Skv - Sq), batch 2, k / v from a
+    cache-shaped buffer.  float64 masked softmax reference; the module's tolerance (2^-7 of the output scale)."""
+    B, Hq, Hkv = 2, 12, 2
+    g = torch.Generator().manual_seed(Sq * 13 + Skv)
+    q = torch.randn(B, Sq, Hq * 128, generator=g).bfloat16()
+    buf, k, v = _cache(B, Skv, Hkv, g, "randn", None, q[:, :1])
+    ref = _ref64(q, k, v, Hq, Hkv)
+    dbuf = buf.cuda()
+    out = torch.full((B, Sq, Hq * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention(q.cuda(), dbuf[:, :Skv, :Hkv * 128], dbuf[:, :Skv, Hkv * 128:2 * Hkv * 128], out, Hq, Hkv, causal=True)
+    torch.cuda.synchronize()
+    print(f"cached prefill Sq={Sq} Skv={Skv}: max error {((out.double().cpu() - ref).abs().max() / ref.abs().max()).item() / 2.0 ** -7:.3f} x the bound")
+    _check(out, ref)

@@ -473,7 +473,9 @@ int td_mrope_table_launch(const int* pos, int n, const int* sections, float thet
 
 // ---------------------------------------------------------------------------------------------
 // Row normalisation for any D % 8 == 0 (CLIP 768, EVA 1408, Qwen-ViT 1280 ...): LayerNorm with affine weight and
-// bias, or RMSNorm.  One wave per row, two sweeps over the (L2-resident) row.  y = bf16(n * w + b), fp32 statistics.
+// bias, or RMSNorm.  One wave per row, fp32 statistics.  LayerNorm sweeps the (L2-resident) row three times: the sum, then
+// the squares of x - mean (a one-pass E[x^2] - mean^2 loses the spread of rows whose mean is large next to it to fp32
+// cancellation: rstd off by several bf16 ulps at mean / std of a few hundred), then the output.  y = bf16(n * w + b).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void td_norm_rows_generic_kernel(const bf16_t* x, int ldx, bf16_t* y, int ldy, int rows, int D, int rms,
                                                                    float eps, const bf16_t* w, const bf16_t* b) {
@@ -481,17 +483,28 @@ __global__ __launch_bounds__(256) void td_norm_rows_generic_kernel(const bf16_t*
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const bf16_t* xr = x + (size_t)row * ldx;
-  float s = 0.f, q = 0.f;
+  float mean = 0.f;
+  if (!rms) {
+    float s = 0.f;
+    for (int c = lane * 8; c < D; c += 512) {
+      float v[8];
+      unpack8(*(const u32x4_t*)(xr + c), v);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s += v[i];
+    }
+    mean = wave_sum(s) / D;
+  }
+  float q = 0.f;
   for (int c = lane * 8; c < D; c += 512) {
     float v[8];
     unpack8(*(const u32x4_t*)(xr + c), v);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { s += v[i]; q += v[i] * v[i]; }
+    for (int i = 0; i < 8; ++i) {
+      const float d = v[i] - mean;
+      q += d * d;
+    }
   }
-  s = wave_sum(s); q = wave_sum(q);
-  const float mean = rms ? 0.f : s / D;
-  const float var = rms ? q / D : fmaxf(q / D - mean * mean, 0.f);
-  const float rstd = rsqrtf(var + eps);
+  const float rstd = rsqrtf(wave_sum(q) / D + eps);
   bf16_t* yr = y + (size_t)row * ldy;
   for (int c = lane * 8; c < D; c += 512) {
     float v[8], wv[8], bv[8];
@@ -541,7 +554,17 @@ int td_add_rows_launch(const bf16_t* a, const bf16_t* b, bf16_t* out, int rows, 
   return 0;
 }
 
-// gated unit: out[m, j] = bf16(bf16(act(g[m,j])) * u[m,j]), g | u = the two halves of gu[m, 2I]; act: TdAct code
+// gated unit: out[m, j] = bf16(bf16(act(g[m,j])) * u[m,j]), g | u = the two halves of gu[m, 2I]; act: any TdAct code
+__device__ __forceinline__ float glu_act(int act, float x) {
+  switch (act) {
+    case TD_ACT_GELU_TANH: return gelu_tanh_f(x);
+    case TD_ACT_GELU_ERF: return gelu_erf_f(x);
+    case TD_ACT_SILU: return silu_f(x);
+    case TD_ACT_QUICK_GELU: return quick_gelu_f(x);
+    default: return x;      // TD_ACT_NONE (the launcher refuses unknown codes)
+  }
+}
+
 __global__ void td_glu_mul_kernel(const bf16_t* gu, bf16_t* out, int rows, int I, int act) {
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int per_row = I / 8;
@@ -552,14 +575,14 @@ __global__ void td_glu_mul_kernel(const bf16_t* gu, bf16_t* out, int rows, int I
   unpack8(*(const u32x4_t*)(gu + (size_t)m * 2 * I + I + c * 8), u);
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const float a = act == TD_ACT_GELU_TANH ? gelu_tanh_f(g[i]) : act == TD_ACT_GELU_ERF ? gelu_erf_f(g[i]) : silu_f(g[i]);
-    g[i] = rbf(a) * u[i];
+    g[i] = rbf(glu_act(act, g[i])) * u[i];
   }
   *(u32x4_t*)(out + (size_t)m * I + c * 8) = pack8(g);
 }
 
 int td_glu_mul_launch(const bf16_t* gu, bf16_t* out, int rows, int I, int act, hipStream_t stream) {
   TD_CHECK_ARG(rows > 0 && I % 8 == 0, "td_glu_mul: bad shape");
+  TD_CHECK_ARG(td_act_valid(act), "td_glu_mul: unknown activation code %d (0 .. 4: TD_ACT_NONE .. TD_ACT_QUICK_GELU)", act);
   const long long n = (long long)rows * (I / 8);
   TD_GRID_1D(nblk, n, 256, "td_glu_mul");
   hipLaunchKernelGGL(td_glu_mul_kernel, dim3(nblk), dim3(256), 0, stream, gu, out, rows, I, act);

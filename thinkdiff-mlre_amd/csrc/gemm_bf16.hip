@@ -64,7 +64,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 // `act` and `mode` are block-uniform run-time values: ONE body, with scalar branches around the optional stages of a row.
 // (One instantiation per activation, selected by a switch in front, made the compiler hoist the shared `acc + bias` of all
 // WM rows above the switch: 128 extra live values and a spilling kernel.)
-template <int WM, int WN, bool Q8 = false>   // mode 0: bias(+act); 1: bias, gate, (+res); 2: bias, res
+template <int WM, int WN, bool Q8 = false>   // mode 0: bias(+act); 1: bias(+act), gate, (+res); 2: bias(+act), res
 __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg, bool second,
                                          const int act, const int mode) {
   constexpr int NV = 4 * WN;
@@ -152,7 +152,7 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
 #pragma unroll
           for (int c = 0; c < NV; ++c) v[c] = apply_act<TD_ACT_SILU>(v[c]);
           break;
-        default:
+        case TD_ACT_QUICK_GELU:
 #pragma unroll
           for (int c = 0; c < NV; ++c) v[c] = apply_act<TD_ACT_QUICK_GELU>(v[c]);
           break;
@@ -617,12 +617,11 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
         }
     }
   }
-  // (an activation followed by a gate / residual does not occur on this path: act wins)
   if (p.out_f32) {
     epilogue_f32<WM, WN>(p, pv, acc, mbeg, nbeg);
     return;
   }
-  const int mode = act != TD_ACT_NONE ? 0 : (pv.gate ? 1 : (pv.res ? 2 : 0));
+  const int mode = pv.gate ? 1 : (pv.res ? 2 : 0);      // after the activation, if any: bias -> act -> gate -> residual
   epilogue<WM, WN, I8 && WN == 4>(p, pv, acc, mbeg, nbeg, second, act, mode);
 }
 
@@ -922,6 +921,7 @@ int td_gemm_config_id(int M, int N, int K) {
 
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "td_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
+  TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemm: unknown activation code act=%d act2=%d (0 .. 4: TD_ACT_NONE .. TD_ACT_QUICK_GELU)", p.act, p.act2);
   const int esz = (p.fp8 || p.i8) ? 1 : 2;
   TD_CHECK_ARG(!(p.fp8 && p.i8), "td_gemm: fp8 and int8 operands are exclusive");
   TD_CHECK_ARG(p.K % (128 / esz) == 0, "td_gemm: K=%d must be a multiple of %d", p.K, 128 / esz);

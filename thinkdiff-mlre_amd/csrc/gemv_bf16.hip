@@ -36,7 +36,7 @@ __device__ __forceinline__ float act_rt(int act, float x) {
     case TD_ACT_GELU_ERF: return gelu_erf_f(x);
     case TD_ACT_SILU: return silu_f(x);
     case TD_ACT_QUICK_GELU: return quick_gelu_f(x);
-    default: return x;
+    default: return x;      // TD_ACT_NONE (td_gemm_launch refuses unknown codes)
   }
 }
 
@@ -123,10 +123,8 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
   const int act = second ? p.act2 : p.act;
   if (p.bias) v += bf2f(p.bias[n]);
   if (act != TD_ACT_NONE) v = act_rt(act, rbf(v));
-  else {
-    if (p.gate) v = rbf(v) * bf2f(p.gate[n]);
-    if (p.res) v = rbf(v) + bf2f(p.res[(size_t)m * p.ldr + n]);
-  }
+  if (p.gate) v = rbf(v) * bf2f(p.gate[n]);
+  if (p.res) v = rbf(v) + bf2f(p.res[(size_t)m * p.ldr + n]);
   if (second) p.C2[(size_t)m * p.ldc2 + (n - p.n_split)] = f2bf(v);
   else p.C[(size_t)m * p.ldc + n] = f2bf(v);
 }
@@ -288,10 +286,8 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
       float y = v[i];
       if (p.bias) y += bf2f(p.bias[n + i]);
       if (act != TD_ACT_NONE) y = act_rt(act, rbf(y));
-      else {
-        if (p.gate) y = rbf(y) * bf2f(p.gate[n + i]);
-        if (p.res) y = rbf(y) + bf2f(p.res[(size_t)m * p.ldr + n + i]);
-      }
+      if (p.gate) y = rbf(y) * bf2f(p.gate[n + i]);
+      if (p.res) y = rbf(y) + bf2f(p.res[(size_t)m * p.ldr + n + i]);
       v[i] = y;
     }
     const u32x2_t o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
@@ -421,6 +417,7 @@ bool td_gemv_mfma_ok(const TdGemmParams& p) {
 
 
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
+  TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemv: unknown activation code act=%d act2=%d", p.act, p.act2);
   TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % 8 == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");
   TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W) % 16 == 0, "td_gemv: operands must be 16-byte aligned");
   if (p.glu_I) {

@@ -4,6 +4,8 @@
 #include "td_common.h"
 
 enum TdAct { TD_ACT_NONE = 0, TD_ACT_GELU_TANH = 1, TD_ACT_GELU_ERF = 2, TD_ACT_SILU = 3, TD_ACT_QUICK_GELU = 4 };
+// every launcher that takes an activation code refuses one outside this range (no route has a fallback for it)
+inline bool td_act_valid(int act) { return act >= TD_ACT_NONE && act <= TD_ACT_QUICK_GELU; }
 
 struct TdGemmParams {
   const bf16_t* A = nullptr;     // [M, lda]  activations, K-contiguous
