@@ -352,6 +352,42 @@ int td_vae_decode(td_vae* f, const void* packed_latents, int h, int w, float sca
 /* The image size td_vae_decode writes for an h x w latent (2x per block but the last: 8h x 8w for the FLUX.1 VAE) and the channel count of
  * a packed latent row (4 x latent_channels); out pointers may be NULL.  (The torch.ops layer sizes and checks its tensors with it.) */
 int td_vae_output_shape(const td_vae* f, int h, int w, int* H, int* W, int* packed_channels);
+/* ---- FLUX VAE encoder (AutoencoderKL.encode) and the image-to-image boundaries -----------------------------------------
+ * A handle of its own (td_vae_enc), configured by the same TdVaeConfig as the decoder (out_channels = the image's 3 channels,
+ * latent_channels = 16 -> 32 moment channels: double_z, no quant_conv).  Parameters use the diffusers names
+ * ("encoder.down_blocks.1.downsamplers.0.conv.weight", ...), conv weights in torch [Cout,Cin,3,3] layout. */
+typedef struct td_vae_enc td_vae_enc;
+#define TD_IMAGE_U8_HWC 0   /* uint8 [H, W, 3] (what PIL gives) */
+#define TD_IMAGE_F32_CHW 1  /* float32 [3, H, W] in [0, 1] */
+/* Encoder for images of up to max_image_h x max_image_w pixels; every workspace is allocated here ([ext] diffusers 0.31.0
+ * vae.py Encoder: conv_in, DownEncoderBlock2D x num_blocks, UNetMidBlock2D with attention, GroupNorm + SiLU, conv_out). */
+int td_vae_enc_create(const TdVaeConfig* cfg, int max_image_h, int max_image_w, td_vae_enc** out);
+void td_vae_enc_destroy(td_vae_enc* f);
+int td_vae_enc_num_params(const td_vae_enc* f);
+int td_vae_enc_param_info(const td_vae_enc* f, int idx, char* name_buf, int buf_len, int64_t* count);
+int td_vae_enc_load_param(td_vae_enc* f, const char* name, const void* src, int64_t count, void* stream);
+/* seeded synthetic encoder, the weight scheme of td_vae_init_random */
+int td_vae_enc_init_random(td_vae_enc* f, uint64_t seed, float std, void* stream);
+/* `VaeImageProcessor.preprocess(image).to(bf16)` + `vae.encode(x)` up to the posterior's parameters ([ext] autoencoder_kl.py
+ * AutoencoderKL._encode): image (device; format TD_IMAGE_*) -> moments_nhwc bf16 [(H/8)(W/8), 2 x latent_channels] = mean | logvar
+ * per latent pixel (H/2^(num_blocks-1) for other depths).  H, W multiples of 16 within the capacity, the mid block's pixel count
+ * a multiple of 64; refused before any launch otherwise.  No allocation. */
+int td_vae_encode(td_vae_enc* f, const void* image, int image_format, int H, int W, void* moments_nhwc, void* stream);
+/* The moments td_vae_encode writes for an H x W image: h x w latent pixels (H / 2^(num_blocks-1): H/8 for the FLUX.1 VAE) of
+ * 2 x latent_channels; out pointers may be NULL.  (The torch.ops layer sizes its output with it.) */
+int td_vae_enc_output_shape(const td_vae_enc* f, int H, int W, int* h, int* w, int* moment_channels);
+/* moments [h*w, 2C] bf16 (td_vae_encode's output) -> packed FLUX latents [(h/2)(w/2), 4C] bf16, fusing, with the bf16 rounding
+ * points of the torch statements: DiagonalGaussianDistribution.sample(eps) (eps NULL: .mode()), FluxImg2ImgPipeline._encode_vae_image
+ * ((z - shift_factor) * scaling_factor), FlowMatchEulerDiscreteScheduler.scale_noise (sigma rounded to bf16; noise NULL: no noising)
+ * and _pack_latents.  eps / noise: bf16 NCHW [C, h, w] drawn by the caller.  h, w even. */
+int td_vae_latents_from_moments(const void* moments, const void* eps, const void* noise, float sigma, float scaling_factor,
+                                float shift_factor, int C, int h, int w, void* packed_out, void* stream);
+/* VaeImageProcessor.preprocess + .to(bf16) alone: out bf16 [H*W, Cpad] NHWC = RNE(2 x - 1) with x = float32(u8) / 255 or the
+ * float32 [0,1] value; channels 3 .. Cpad-1 zero.  Cpad % 8 == 0. */
+int td_vae_image_to_nhwc_bf16(const void* image, int image_format, int H, int W, void* out, int Cpad, void* stream);
+/* Downsample2D(use_conv=True, padding=0): F.pad(x, (0,1,0,1)) then a 3x3 conv, stride 2, no padding, as an implicit GEMM:
+ *   y[(Hin/2)(Win/2), Cout] = conv3x3_s2(x[Hin*Win, Cin]) + bias;   Hin, Win even, Cin % 64 == 0, w packed as for td_conv3x3_nhwc_bf16. */
+int td_conv3x3_s2_nhwc_bf16(const void* x, const void* w, const void* bias, void* y, int Hin, int Win, int Cin, int Cout, void* stream);
 /* GroupNorm (+ optional SiLU) over an NHWC image x[P,C]; workspace: td_groupnorm_workspace_floats() floats. */
 int td_groupnorm_nhwc_bf16(const void* x, void* y, int P, int C, int groups, float eps, const void* gamma,
                            const void* beta, int silu, float* workspace, void* stream);

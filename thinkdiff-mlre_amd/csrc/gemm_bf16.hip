@@ -265,7 +265,7 @@ __device__ __forceinline__ void epilogue_f32(const TdGemmParams& pp, const ProbV
 // become floats (x a_scale[m] x w_scale[n]) in front of the common epilogue.  Round 3: 8-bit operands whose quantisation noise is
 // ~4x below e4m3's on Gaussian-like operands (uniform step max/127 against a 3-bit mantissa).
 // One output tile: rows [m0, m0 + 32 WM) of problem `second_prob`, columns [n0, n0 + 64 WN).  Called once per workgroup.
-template <int WM, int WN, bool CONV, bool FP8, bool I8>
+template <int WM, int WN, int CONV, bool FP8, bool I8>
 __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0) {
   constexpr int BM = 32 * WM, BN = 64 * WN;
   constexpr int A_BYTES = BM * ROW_BYTES, W_BYTES = BN * ROW_BYTES;
@@ -297,7 +297,9 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
   if (m0 >= pv.M) return;      // (a sub-tile of a split tail tile that lies wholly below the problem's last row; workgroup-uniform)
 
   // ---- buffer descriptors (wave-uniform; OOB rows read as zero) -----------------------------
-  const unsigned bytesA = CONV ? (unsigned)((long long)(p.conv_H >> p.conv_up) * (p.conv_W >> p.conv_up) * p.conv_Cin * 2)
+  // (the stride-2 form reads a 2H x 2W input: its whole extent, or valid taps of the lower half would read as zero)
+  const unsigned bytesA = CONV == 2 ? (unsigned)(4ll * p.conv_H * p.conv_W * p.conv_Cin * 2)
+                        : CONV ? (unsigned)((long long)(p.conv_H >> p.conv_up) * (p.conv_W >> p.conv_up) * p.conv_Cin * 2)
                                 : (unsigned)(((long long)(pv.M - 1) * p.lda + p.K) * ESZ);
   const unsigned bytesW = (unsigned)((((long long)p.N - 1) * p.ldw + p.K) * ESZ);
   __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Aptr, 0, bytesA, 0x00020000);
@@ -336,7 +338,9 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
   // Implicit-GEMM 3x3 convolution (CONV): A is an NHWC image [Hin*Win, Cin]; k-tile kt covers tap kt / (Cin/64)
   // and input channels 64*(kt % (Cin/64)).  A row (= output pixel) reads input pixel (y+dy, x+dx) -- or its
   // nearest-neighbour parent when the conv follows a 2x upsample -- and taps outside the image are sent past the
-  // descriptor range, so the zero padding costs nothing.
+  // descriptor range, so the zero padding costs nothing.  CONV == 2 is Downsample2D's stride-2 conv after F.pad(x, (0,1,0,1)):
+  // conv_H x conv_W is the OUTPUT extent, the input is 2 conv_H x 2 conv_W, output pixel (y, x) reads (2y+ky, 2x+kx), and
+  // the only invalid taps are the right / bottom pad (no negative taps).
   int cy[SA], cx[SA];
   if constexpr (CONV) {
 #pragma unroll
@@ -351,6 +355,13 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
   auto conv_voff = [&](int s, int kt) -> unsigned {
     const int cpt = p.conv_Cin >> 6;
     const int tap = kt / cpt, c0 = (kt - tap * cpt) << 6;
+    if constexpr (CONV == 2) {
+      const int ky = tap * 11 >> 5, kx = tap - ky * 3;
+      const int yy = 2 * cy[s] + ky, xx = 2 * cx[s] + kx, win = 2 * p.conv_W;
+      const bool ok = (unsigned)yy < (unsigned)(2 * p.conv_H) && (unsigned)xx < (unsigned)win;
+      const unsigned off = ((unsigned)(yy * win + xx) * (unsigned)p.conv_Cin + (unsigned)c0) * 2u + schunk;
+      return ok ? off : 0xFFFFFF00u;
+    }
     const int dy = (tap * 11 >> 5) - 1, dx = tap - (tap * 11 >> 5) * 3 - 1;
     const int yy = cy[s] + dy, xx = cx[s] + dx;
     const bool ok = (unsigned)yy < (unsigned)p.conv_H && (unsigned)xx < (unsigned)p.conv_W;
@@ -638,7 +649,7 @@ __device__ __forceinline__ int xcd_contiguous(const int bid, const int nwg) {
 // behind the full rounds -- into TAIL sub-tiles of 32 WM / TAIL rows each: workgroups [tail_first_wg, grid) take one sub-tile, so the
 // last round costs 1 / TAIL of a tile time (x the smaller tile's lower efficiency) instead of a whole one.  No split along K, no
 // fix-up pass: every output element is still produced by one workgroup with the full contraction, bit-identical to the unsplit launch.
-template <int WM, int WN, bool CONV = false, bool FP8 = false, bool I8 = false, int TAIL = 1>
+template <int WM, int WN, int CONV = 0, bool FP8 = false, bool I8 = false, int TAIL = 1>
 __global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)  // body uses gfx950-only types (__amdgpu_buffer_rsrc_t): the host pass only needs the stub
   static_assert(TAIL == 1 || (WM % TAIL == 0 && !CONV), "tail sub-tiles cut the m extent of the tile");
@@ -719,7 +730,7 @@ int tail_split(long long tiles, int cus) {
   return pick;
 }
 
-template <int WM, int WN, bool CONV = false, bool FP8 = false, bool I8 = false, int TAIL = 1>
+template <int WM, int WN, int CONV = 0, bool FP8 = false, bool I8 = false, int TAIL = 1>
 int launch_cfg(const TdGemmParams& p0, hipStream_t stream) {
   constexpr int BM = 32 * WM, BN = 64 * WN;
   constexpr int LDS = (2 * BM + 3 * BN) * ROW_BYTES;
@@ -946,6 +957,11 @@ int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
     TD_CHECK_ARG(p.conv_Cin % 64 == 0 && p.K == 9 * p.conv_Cin && p.M == p.conv_H * p.conv_W && p.g_M == 0 && !p.C2,
                  "td_gemm(conv): need Cin %% 64 == 0, K == 9 Cin, M == H W (got Cin=%d K=%d M=%d H=%d W=%d)", p.conv_Cin, p.K, p.M, p.conv_H, p.conv_W);
     TD_CHECK_ARG(p.conv_up == 0 || (p.conv_H % 2 == 0 && p.conv_W % 2 == 0), "td_gemm(conv): upsampled output dims must be even");
+    if (p.conv_s2) {
+      TD_CHECK_ARG(p.conv_up == 0 && p.res == nullptr, "td_gemm(conv): the stride-2 form has no upsample and no residual");
+      TD_CHECK_ARG(4ll * p.M * p.conv_Cin * 2 < LIM, "td_gemm(conv): stride-2 input exceeds the 4 GiB buffer-descriptor range");
+      return p.N <= 64 ? launch_cfg<8, 1, 2>(p, stream) : p.N <= 128 ? launch_cfg<8, 2, 2>(p, stream) : launch_cfg<8, 4, 2>(p, stream);
+    }
     // output-channel tile: 64, 128 (the 128-channel 1024^2 / 512^2 layers of the VAE: a 256-wide tile would be half empty) or 256
     return p.N <= 64 ? launch_cfg<8, 1, true>(p, stream) : p.N <= 128 ? launch_cfg<8, 2, true>(p, stream) : launch_cfg<8, 4, true>(p, stream);
   }

@@ -43,6 +43,9 @@ struct TdGemmParams {
   // implicit-GEMM 3x3 convolution over an NHWC image (conv_H > 0): A = input [Hin*Win, Cin], W = [N, 9*Cin]
   // (k = tap*Cin + c, tap = ky*3+kx), M = conv_H*conv_W output pixels; conv_up = 1 fuses a nearest 2x upsample
   int conv_H = 0, conv_W = 0, conv_Cin = 0, conv_up = 0;
+  // conv_s2 = 1: Downsample2D(padding=0)'s pad (0,1,0,1) + stride-2 3x3 conv instead; conv_H x conv_W is then the output extent
+  // and the input is [2 conv_H * 2 conv_W, Cin] (a kernel form of its own: the stride-1 instantiations are untouched)
+  int conv_s2 = 0;
   // fp8 operands (fp8 = 1): A and W hold OCP e4m3 bytes (lda, K in elements = bytes); y = acc * a_scale[m] * w_scale[n]
   // gated MLP in one pass (skinny-M kernels only, glu_I > 0): W = [gate rows | up rows] (2 * glu_I x K), N = glu_I outputs,
   // C[m, n] = bf16(bf16(silu(bf16(x.gate_n))) * bf16(x.up_n)) -- Linear, SiLU and the product each round, as the separate kernels do

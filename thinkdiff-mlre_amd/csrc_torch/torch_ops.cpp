@@ -242,6 +242,38 @@ at::Tensor vae_decode_u8(int64_t engine, const at::Tensor& packed, int64_t h, in
   ok(td_vae_decode((td_vae*)(uintptr_t)engine, packed.data_ptr(), (int)h, (int)w, (float)scaling_factor, (float)shift_factor, img.data_ptr(), nullptr, stream_of(packed)));
   return img;
 }
+// VaeImageProcessor.preprocess + AutoencoderKL.encode up to the posterior's parameters: image uint8 [H, W, 3] or float32 [3, H, W] in [0, 1]
+// -> moments [(H/8)(W/8), 2 x latent_channels] bf16 (mean | logvar, NHWC) on a td_vae_enc* engine
+at::Tensor vae_encode_moments(int64_t engine, const at::Tensor& image, int64_t H, int64_t W) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null VAE encoder handle");
+  TORCH_CHECK(image.is_cuda() && image.is_contiguous(), "thinkdiff_hip::vae_encode_moments: image must be a contiguous GPU tensor");
+  const bool u8 = image.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || image.scalar_type() == at::kFloat, "thinkdiff_hip::vae_encode_moments: image must be uint8 [H, W, 3] or float32 [3, H, W], got ", image.scalar_type());
+  TORCH_CHECK(u8 ? image.sizes() == at::IntArrayRef({H, W, 3}) : image.sizes() == at::IntArrayRef({3, H, W}),
+              "thinkdiff_hip::vae_encode_moments: image must be ", u8 ? "uint8 [H, W, 3]" : "float32 [3, H, W]", " with H = ", H, ", W = ", W, ", got ", image.sizes());
+  int h = 0, w = 0, mc = 0;
+  ok(td_vae_enc_output_shape((const td_vae_enc*)(uintptr_t)engine, (int)H, (int)W, &h, &w, &mc));
+  DeviceGuard guard(image.device());
+  at::Tensor mom = at::empty({(int64_t)h * w, mc}, image.options().dtype(at::kBFloat16));
+  ok(td_vae_encode((td_vae_enc*)(uintptr_t)engine, image.data_ptr(), u8 ? TD_IMAGE_U8_HWC : TD_IMAGE_F32_CHW, (int)H, (int)W, mom.data_ptr(), stream_of(image)));
+  return mom;
+}
+// posterior sample / mode + shift / scale + scale_noise + _pack_latents: moments [h*w, 2C] -> packed latents [(h/2)(w/2), 4C]
+at::Tensor vae_latents_from_moments(const at::Tensor& moments, const c10::optional<at::Tensor>& eps, const c10::optional<at::Tensor>& noise, double sigma,
+                                    double scaling_factor, double shift_factor, int64_t h, int64_t w) {
+  check_rows(moments, "moments");
+  TORCH_CHECK(h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0, "thinkdiff_hip::vae_latents_from_moments: even latent height and width");
+  TORCH_CHECK(moments.dim() == 2 && moments.is_contiguous() && moments.size(0) == h * w && moments.size(1) % 2 == 0,
+              "thinkdiff_hip::vae_latents_from_moments: moments must be contiguous [h*w = ", h * w, ", 2C] bf16, got ", moments.sizes());
+  const int64_t C = moments.size(1) / 2;
+  check_vec(eps, "eps", moments, C * h * w);
+  check_vec(noise, "noise", moments, C * h * w);
+  DeviceGuard guard(moments.device());
+  at::Tensor out = at::empty({(h / 2) * (w / 2), 4 * C}, moments.options());
+  ok(td_vae_latents_from_moments(moments.data_ptr(), P(eps), P(noise), (float)sigma, (float)scaling_factor, (float)shift_factor, (int)C, (int)h, (int)w,
+                                 out.data_ptr(), stream_of(moments)));
+  return out;
+}
 // the joint attention with QK^T and P.V on the e4m3 MFMA (td_attention_fp8): q, k, v [S, >= H*128] bf16 views
 at::Tensor attention_fp8(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t H, double scale) {
   check_rows(q, "q"); check_rows(k, "k"); check_rows(v, "v"); same_device(k, "k", q); same_device(v, "v", q);
@@ -273,6 +305,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_denoise_multi_(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()");
   m.def("vae_decode_u8(int engine, Tensor packed, int h, int w, float scaling_factor, float shift_factor) -> Tensor");
   m.def("attention_fp8(Tensor q, Tensor k, Tensor v, int H, float scale) -> Tensor");
+  m.def("vae_encode_moments(int engine, Tensor image, int H, int W) -> Tensor");
+  m.def("vae_latents_from_moments(Tensor moments, Tensor? eps, Tensor? noise, float sigma, float scaling_factor, float shift_factor, int h, int w) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -291,4 +325,6 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_denoise_multi_", &flux_denoise_multi_);
   m.impl("vae_decode_u8", &vae_decode_u8);
   m.impl("attention_fp8", &attention_fp8);
+  m.impl("vae_encode_moments", &vae_encode_moments);
+  m.impl("vae_latents_from_moments", &vae_latents_from_moments);
 }

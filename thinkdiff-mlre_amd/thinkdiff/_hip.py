@@ -98,6 +98,16 @@ def _declare(L):
         "td_vae_decode": [vp, vp, i32, i32, f32, f32, vp, vp, vp],
         "td_conv3x3_nhwc_bf16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
         "td_conv3x3_pack_weight": [vp, vp, i32, i32, i32, i32, vp],
+        "td_conv3x3_s2_nhwc_bf16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "td_vae_enc_create": [vp, i32, i32, vp],
+        "td_vae_enc_num_params": [vp],
+        "td_vae_enc_param_info": [vp, i32, ctypes.c_char_p, i32, vp],
+        "td_vae_enc_load_param": [vp, ctypes.c_char_p, vp, i64, vp],
+        "td_vae_enc_init_random": [vp, ctypes.c_uint64, f32, vp],
+        "td_vae_enc_output_shape": [vp, i32, i32, vp, vp, vp],
+        "td_vae_encode": [vp, vp, i32, i32, i32, vp, vp],
+        "td_vae_latents_from_moments": [vp, vp, vp, f32, f32, f32, i32, i32, i32, vp, vp],
+        "td_vae_image_to_nhwc_bf16": [vp, i32, i32, i32, vp, i32, vp],
         "td_linear_f32out_bf16": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
         "td_groupnorm_nhwc_bf16": [vp, vp, i32, i32, i32, f32, vp, vp, i32, vp, vp],
         "td_groupnorm_workspace_floats": [],
@@ -141,6 +151,8 @@ def _declare(L):
     L.td_flux_destroy.restype = None
     L.td_vae_destroy.argtypes = [vp]
     L.td_vae_destroy.restype = None
+    L.td_vae_enc_destroy.argtypes = [vp]
+    L.td_vae_enc_destroy.restype = None
     L.td_qwen2_destroy.argtypes = [vp]
     L.td_qwen2_destroy.restype = None
     L.td_flux_param_elems.argtypes = [vp]
@@ -390,6 +402,26 @@ def conv3x3_nhwc(x, w_packed, bias, H, W, Cout, res=None, upsample2x=False):
     y = torch.empty(H * W, Cout, dtype=torch.bfloat16, device=x.device)
     check(lib().td_conv3x3_nhwc_bf16(ptr(x), ptr(w_packed), ptr(bias), ptr(res), ptr(y), H, W, Cin, Cout, int(upsample2x), stream_ptr()))
     return y
+
+
+def conv3x3_s2_nhwc(x, w_packed, bias, Hin, Win, Cout):
+    """Downsample2D's conv: x [Hin*Win, Cin] bf16 NHWC, pad (0,1,0,1), 3x3 stride 2 -> [(Hin/2)(Win/2), Cout]"""
+    Cin = x.shape[1]
+    y = torch.empty((Hin // 2) * (Win // 2), Cout, dtype=torch.bfloat16, device=x.device)
+    check(lib().td_conv3x3_s2_nhwc_bf16(ptr(x), ptr(w_packed), ptr(bias), ptr(y), Hin, Win, Cin, Cout, stream_ptr()))
+    return y
+
+
+IMAGE_U8_HWC, IMAGE_F32_CHW = 0, 1      # TD_IMAGE_* (include/thinkdiff_hip.h)
+
+
+def vae_image_to_nhwc(image, Cpad=64):
+    """VaeImageProcessor.preprocess + .to(bf16): uint8 [H, W, 3] or float32 [3, H, W] in [0,1] -> bf16 [H*W, Cpad] (channels >= 3 zero)"""
+    u8 = image.dtype == torch.uint8
+    H, W = (image.shape[0], image.shape[1]) if u8 else (image.shape[1], image.shape[2])
+    out = torch.empty(H * W, Cpad, dtype=torch.bfloat16, device=image.device)
+    check(lib().td_vae_image_to_nhwc_bf16(ptr(image.contiguous()), IMAGE_U8_HWC if u8 else IMAGE_F32_CHW, H, W, ptr(out), Cpad, stream_ptr()))
+    return out
 
 
 def conv3x3_pack_weight(w_oihw, Cout_pad=None, Cin_pad=None):

@@ -194,6 +194,13 @@ class FluxPipelineRewritePrompt:
         t_eff = [effective_scalar(float(s) * self.scheduler.num_train_timesteps, tr.dtype) for s in sig[:-1]]
         g_eff = float((torch.tensor([guidance_scale], dtype=torch.float32).to(tr.dtype) * 1000).float()) \
             if tr.config.guidance_embeds else 0.0
+        xs = self._denoise_groups(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff)
+        return self._finish(xs, h, w, output_type, return_dict)
+
+    def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff):
+        """The denoise loop over `sig` (any sigma list ending in 0: the full schedule or a truncated one) for the first B packed latents
+        of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents."""
+        tr = self.transformer
         n_prompts = prompt_embeds.shape[0]
         # `images_in_flight` independent images advance together, each on its own stream and engine context (shared
         # weights): the grids of one step are 1.6 - 3.2 rounds of the 256 CUs, and a second image fills those tails.
@@ -220,6 +227,11 @@ class FluxPipelineRewritePrompt:
             for k in range(len(group)):
                 main.wait_stream(self._streams[k])
             xs.extend(lat_g)
+        return xs
+
+    def _finish(self, xs, h: int, w: int, output_type: str, return_dict: bool):
+        """Denoised packed latents -> the pipeline's output (diffusers' `output_type` / `return_dict`)."""
+        tr = self.transformer
         outs = []
         for x in xs:
             if output_type == "latent":      # diffusers: packed latents, no unpack

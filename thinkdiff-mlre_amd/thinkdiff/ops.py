@@ -23,6 +23,8 @@ flux_forward_ / flux_denoise_ / flux_denoise_multi_   FluxTransformer2DModel.for
                            extents the prepared context expects (td_flux_prepared_shape)
 vae_decode_u8              AutoencoderKL.decode + VaeImageProcessor.postprocess on a td_vae* engine
 attention_fp8              the joint attention with QK^T / P.V on the e4m3 MFMA
+vae_encode_moments         VaeImageProcessor.preprocess + AutoencoderKL.encode (posterior parameters) on a td_vae_enc* engine
+vae_latents_from_moments   posterior sample / mode, the img2img pipeline's shift / scale, scale_noise and _pack_latents, fused
 """
 import os
 
@@ -49,6 +51,8 @@ SCHEMAS = {
     "flux_denoise_multi_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()",
     "vae_decode_u8": "(int engine, Tensor packed, int h, int w, float scaling_factor, float shift_factor) -> Tensor",
     "attention_fp8": "(Tensor q, Tensor k, Tensor v, int H, float scale) -> Tensor",
+    "vae_encode_moments": "(int engine, Tensor image, int H, int W) -> Tensor",
+    "vae_latents_from_moments": "(Tensor moments, Tensor? eps, Tensor? noise, float sigma, float scaling_factor, float shift_factor, int h, int w) -> Tensor",
 }
 
 _loaded = False
