@@ -160,6 +160,23 @@ int td_timestep_sincos(const float* t, int n, void* out, void* stream);
 /* FlowMatchEulerDiscreteScheduler.step on bf16 latents: x = bf16(float(x) + dt*float(v)), product and sum each rounded
  * to fp32 as torch's `sample + dt * model_output` does (no fused multiply-add). */
 int td_euler_step_bf16(void* x, const void* v, float dt, int64_t n, void* stream);
+/* FluxInpaintPipeline's step: scheduler.step, scale_noise of the image latents to the next sigma, and the mask blend, fused, in
+ * place on x; every op a bf16 torch op ([ext] pipeline_flux_inpaint.py, scheduling_flow_match_euler_discrete.py):
+ *   a  = bf16(float(x) + float(bf16(bf16(dt) * float(v))))                          (td_euler_step_bf16's arithmetic)
+ *   s  = bf16(sigma_next)
+ *   p  = noise ? bf16(bf16(s * noise) + bf16(bf16(1 - s) * image_latents)) : image_latents
+ *   x  = bf16(bf16(bf16(1 - mask) * p) + bf16(mask * a))
+ * All operands bf16 [n], 16-byte aligned; n % 8 == 0; noise may be NULL (the loop's last step). */
+int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents, const void* noise, const void* mask, float dt,
+                              float sigma_next, int64_t n, void* stream);
+#define TD_INPAINT_MASK_U8_HW 0   /* uint8 [H, W] (PIL mode "L") */
+#define TD_INPAINT_MASK_F32_HW 1  /* float32 [H, W] in [0, 1] */
+/* FluxInpaintPipeline's mask latents from a height x width mask (format TD_INPAINT_MASK_*):
+ *   m = binarize(mask)          (uint8: u8 / 255 >= 0.5, i.e. u8 >= 128; float32: v >= 0.5)
+ *   m = F.interpolate(m, (H/8, W/8), nearest)      (the exact factor 8: latent pixel (y, x) takes m[8y, 8x])
+ *   packed_out = _pack_latents(m.repeat(1, C, 1, 1))   -> bf16 [(H/16)(W/16), 4C] of 0 / 1
+ * H, W multiples of 16; C even; packed_out 16-byte aligned. */
+int td_flux_inpaint_mask(const void* mask, int format, int H, int W, int C, void* packed_out, void* stream);
 /* FluxPipeline._pack_latents (unpack=0: [C,H,W] -> [(H/2)(W/2),4C]) / _unpack_latents (unpack=1, with
  * out = bf16(bf16(in / div) + add), i.e. the `latents / scaling_factor + shift_factor` on bf16 tensors that precedes
  * vae.decode in [ext] pipeline_flux.py, with torch's CPU scalar rules: fp32 divisor, addend cast to bf16, quotient and sum
@@ -217,6 +234,9 @@ int td_flux_load_param(td_flux* f, const char* name, const void* src, int64_t co
 int td_flux_fork(td_flux* parent, td_flux** out);
 /* td_flux_denoise for `count` contexts (a parent and its forks), advanced step by step, context k on streams[k]. */
 int td_flux_denoise_multi(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n, void* const* streams);
+/* td_flux_denoise_multi with the inpainting step of td_flux_denoise_inpaint: image_latents[k], noise[k], mask[k] blend context k. */
+int td_flux_denoise_multi_inpaint(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n,
+                                  const void* const* image_latents, const void* const* noise, const void* const* mask, void* const* streams);
 
 /* Operand precision of the block GEMMs.  TD_PRECISION_FP8_E4M3 quantises every double-/single-stream Linear weight per
  * output channel from the parameters as loaded NOW (call after loading; call again after reloading) and runs those GEMMs on
@@ -270,6 +290,12 @@ int td_flux_trace_begin(td_flux* f, int max_launches);
 int td_flux_trace_end(td_flux* f, void* stream, int64_t* counts, double* ms, double* flops);
 /* n Euler steps in place; sigmas: n+1 host floats */
 int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void* stream);
+/* FluxInpaintPipeline's loop: n steps in place, each the transformer then td_flux_inpaint_step_bf16 with
+ *   dt = sigmas[i+1] - sigmas[i],  sigma_next = sigmas[i+1],  noise used for i < n-1 (the last step blends the clean image_latents).
+ * image_latents (the packed clean latents z), noise (the packed start noise) and mask (td_flux_inpaint_mask's output): bf16
+ * [S_img, in_channels], 16-byte aligned, none NULL, none overlapping the latents. */
+int td_flux_denoise_inpaint(td_flux* f, void* latents, const float* sigmas, int n, const void* image_latents, const void* noise,
+                            const void* mask, void* stream);
 
 /* ---- fp8 operand path (BASELINE config 5 "fp8 MFMA FLUX path") -------------------------------
  * Operands are OCP e4m3 bytes with one fp32 dequantisation scale per row: weights per output channel (quantised once at

@@ -187,6 +187,14 @@ int td_timestep_sincos(const float* t, int n, void* out, void* stream) {
 int td_euler_step_bf16(void* x, const void* v, float dt, int64_t n, void* stream) {
   return td_euler_step_launch((bf16_t*)x, (const bf16_t*)v, dt, n, (hipStream_t)stream);
 }
+int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents, const void* noise, const void* mask, float dt,
+                              float sigma_next, int64_t n, void* stream) {
+  return td_flux_inpaint_step_launch((bf16_t*)x, (const bf16_t*)v, (const bf16_t*)image_latents, (const bf16_t*)noise, (const bf16_t*)mask, dt,
+                                     sigma_next, n, (hipStream_t)stream);
+}
+int td_flux_inpaint_mask(const void* mask, int format, int H, int W, int C, void* packed_out, void* stream) {
+  return td_flux_inpaint_mask_launch(mask, format, H, W, C, (bf16_t*)packed_out, (hipStream_t)stream);
+}
 int td_flux_pack_latents(const void* src, void* dst, int C, int H, int W, int unpack, float div, float add, void* stream) {
   return td_flux_pack_launch((const bf16_t*)src, (bf16_t*)dst, C, H, W, unpack, div, add, (hipStream_t)stream);
 }

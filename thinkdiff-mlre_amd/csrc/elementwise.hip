@@ -4,6 +4,7 @@
 #include "td_common.h"
 #include "td_kernels.h"
 #include "qk_rope_math.h"
+#include "../../include/thinkdiff_hip.h"
 
 namespace {
 
@@ -327,16 +328,101 @@ int td_temb_combine_silu_launch(const bf16_t* te, const bf16_t* ge, const bf16_t
 // `(sigma_next - sigma)` is a 0-dim fp32 tensor and `model_output` a bf16 tensor, so torch's type promotion makes the PRODUCT a bf16
 // op: the scalar is cast to bf16, the product is rounded to bf16, and only the sum with the fp32 sample is fp32.  Three roundings:
 //   x = bf16(float(x) + float(bf16(float(bf16(dt)) * float(v))))
+// euler8 leaves the sum in fp32; the caller rounds it (pack8 or rbf).
+__device__ __forceinline__ void euler8(float (&a)[8], const float (&b)[8], float dt) {
+  const float dtb = rbf(dt);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = a[i] + rbf(dtb * b[i]);   // rbf() between the product and the sum: nothing to contract into an fma
+}
+
 __global__ void td_euler_step_kernel(bf16_t* x, const bf16_t* v, float dt, int n8) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n8) return;
   float a[8], b[8];
   unpack8(((const u32x4_t*)x)[idx], a);
   unpack8(((const u32x4_t*)v)[idx], b);
-  const float dtb = rbf(dt);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) a[i] = a[i] + rbf(dtb * b[i]);   // rbf() between the product and the sum: nothing to contract into an fma
+  euler8(a, b, dt);
   ((u32x4_t*)x)[idx] = pack8(a);
+}
+
+// FluxInpaintPipeline's loop body after the transformer [ext pipeline_flux_inpaint.py]: the scheduler step, then
+//   init_latents_proper = scale_noise(image_latents, [t_next], noise)   (the last step: image_latents itself)
+//   latents = (1 - init_mask) * init_latents_proper + init_mask * latents
+// on bf16 tensors, every op rounded to bf16 (s = bf16(sigma_next): scale_noise casts the sigmas to the latents' dtype):
+//   a  = bf16(float(x) + float(bf16(bf16(dt) * float(v))))
+//   p  = noise ? bf16(bf16(s * noise) + bf16(bf16(1 - s) * z)) : z
+//   x' = bf16(bf16(bf16(1 - m) * p) + bf16(m * a))
+// Five bf16 streams in, one out, 16 B per lane; in place on x.
+__global__ void td_flux_inpaint_step_kernel(bf16_t* x, const bf16_t* v, const bf16_t* z, const bf16_t* noise, const bf16_t* mask,
+                                            float dt, float sigma_next, int n8) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n8) return;
+  float a[8], b[8], p[8], m[8];
+  unpack8(((const u32x4_t*)x)[idx], a);
+  unpack8(((const u32x4_t*)v)[idx], b);
+  unpack8(((const u32x4_t*)z)[idx], p);
+  unpack8(((const u32x4_t*)mask)[idx], m);
+  euler8(a, b, dt);
+  if (noise) {
+    float e[8];
+    unpack8(((const u32x4_t*)noise)[idx], e);
+    const float s = rbf(sigma_next), oms = rbf(1.0f - s);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = rbf(rbf(s * e[i]) + rbf(oms * p[i]));
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = rbf(rbf(1.0f - m[i]) * p[i]) + rbf(m[i] * rbf(a[i]));
+  ((u32x4_t*)x)[idx] = pack8(a);
+}
+
+int td_flux_inpaint_step_launch(bf16_t* x, const bf16_t* v, const bf16_t* z, const bf16_t* noise, const bf16_t* mask, float dt,
+                                float sigma_next, long long n, hipStream_t stream) {
+  TD_CHECK_ARG(x && v && z && mask, "td_flux_inpaint_step: null argument (x, v, image_latents and mask are required)");
+  TD_CHECK_ARG(n > 0 && n % 8 == 0, "td_flux_inpaint_step: n=%lld must be a positive multiple of 8", n);
+  TD_CHECK_ARG(((uintptr_t)x | (uintptr_t)v | (uintptr_t)z | (uintptr_t)noise | (uintptr_t)mask) % 16 == 0,
+               "td_flux_inpaint_step: every buffer must be 16-byte aligned");
+  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)n * sizeof(bf16_t);
+  for (const bf16_t* o : {z, noise, mask})
+    TD_CHECK_ARG(!o || (uintptr_t)o >= x1 || (uintptr_t)o + (uintptr_t)n * sizeof(bf16_t) <= x0,
+                 "td_flux_inpaint_step: image_latents, noise and mask must not overlap x (updated in place)");
+  TD_GRID_1D_I32(nblk, n / 8, 256, "td_flux_inpaint_step");
+  hipLaunchKernelGGL(td_flux_inpaint_step_kernel, dim3(nblk), dim3(256), 0, stream, x, v, z, noise, mask, dt, sigma_next, (int)(n / 8));
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
+// FluxInpaintPipeline's mask path after the host's resize / grayscale [ext image_processor.py, pipeline_flux_inpaint.py]:
+//   binarize (u8: float32(u8) / 255 >= 0.5, i.e. u8 >= 128; f32: v >= 0.5) -> F.interpolate(nearest) to (H/8, W/8), which at the exact
+//   factor 8 takes mask pixel (8y, 8x) for latent pixel (y, x) -> .repeat(1, C, 1, 1) -> _pack_latents (td_vae_latents_kernel's mapping:
+//   row (y/2)(w/2) + x/2, column 4c + 2(y&1) + (x&1)).
+// One thread per 8 output columns (two channels x the four pixels of a token): 16-byte stores.
+__global__ void td_flux_inpaint_mask_kernel(const void* src, int fmt, int H, int W, int C, bf16_t* out) {
+  const int chunks = C >> 1, w2 = W >> 4;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (H >> 4) * w2 * chunks) return;
+  const int tok = idx / chunks;
+  const int ty = tok / w2, tx = tok - ty * w2;
+  float q[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {      // k = 2 dy + dx: latent pixel (2ty + dy, 2tx + dx)
+    const size_t pix = (size_t)(16 * ty + 8 * (k >> 1)) * W + 16 * tx + 8 * (k & 1);
+    const bool on = fmt == TD_INPAINT_MASK_U8_HW ? ((const unsigned char*)src)[pix] >= 128 : ((const float*)src)[pix] >= 0.5f;
+    q[k] = on ? 1.0f : 0.0f;
+  }
+  const unsigned lo = pack_bf2(q[0], q[1]), hi = pack_bf2(q[2], q[3]);
+  *(u32x4_t*)(out + (size_t)idx * 8) = u32x4_t{lo, hi, lo, hi};
+}
+
+int td_flux_inpaint_mask_launch(const void* mask, int fmt, int H, int W, int C, bf16_t* out, hipStream_t stream) {
+  TD_CHECK_ARG(mask && out, "td_flux_inpaint_mask: null argument");
+  TD_CHECK_ARG(fmt == TD_INPAINT_MASK_U8_HW || fmt == TD_INPAINT_MASK_F32_HW, "td_flux_inpaint_mask: unknown mask format %d", fmt);
+  TD_CHECK_ARG(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "td_flux_inpaint_mask: H=%d, W=%d must be positive multiples of 16", H, W);
+  TD_CHECK_ARG(C > 0 && C % 2 == 0, "td_flux_inpaint_mask: C=%d must be a positive multiple of 2 (4C columns in 8-column chunks)", C);
+  TD_CHECK_ARG(((uintptr_t)out) % 16 == 0, "td_flux_inpaint_mask: packed_out must be 16-byte aligned");
+  TD_GRID_1D_I32(nblk, (long long)(H / 16) * (W / 16) * (C / 2), 256, "td_flux_inpaint_mask");
+  hipLaunchKernelGGL(td_flux_inpaint_mask_kernel, dim3(nblk), dim3(256), 0, stream, mask, fmt, H, W, C, out);
+  TD_CHECK_LAUNCH();
+  return 0;
 }
 
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream) {

@@ -1181,24 +1181,60 @@ int td_flux_trace_end(td_flux* f, void* stream, int64_t* counts, double* ms, dou
   return TD_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The blend operands of one image in FluxInpaintPipeline's loop (td_flux_denoise_inpaint); a null InpaintBlend is the plain Euler step.
+struct InpaintBlend {
+  const void* z;       // packed clean image latents
+  const void* noise;   // packed start noise
+  const void* mask;    // packed 0 / 1 mask (td_flux_inpaint_mask)
+};
+
+bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + nb && y < x + na;
+}
+
+// blend k's buffers: present, 16-byte aligned, and clear of every latents buffer the loop writes
+int check_blend(const char* fn, td_flux* const* fs, void* const* latents, int count, int k, const InpaintBlend& b) {
+  TD_CHECK_ARG(b.z && b.noise && b.mask, "%s: image %d: image_latents, noise and mask are required", fn, k);
+  const size_t bytes = (size_t)fs[k]->S_img * fs[k]->cfg.in_channels * sizeof(bf16_t);
+  const void* bufs[3] = {b.z, b.noise, b.mask};
+  static const char* names[3] = {"image_latents", "noise", "mask"};
+  for (int j = 0; j < 3; ++j) {
+    TD_CHECK_ARG((uintptr_t)bufs[j] % 16 == 0, "%s: image %d: %s must be 16-byte aligned", fn, k, names[j]);
+    for (int l = 0; l < count; ++l)
+      TD_CHECK_ARG(!overlaps(bufs[j], bytes, latents[l], (size_t)fs[l]->S_img * fs[l]->cfg.in_channels * sizeof(bf16_t)),
+                   "%s: image %d: %s overlaps the latents of image %d (the loop writes them in place)", fn, k, names[j], l);
+  }
+  return TD_OK;
+}
+
+// the scheduler step of loop step i (of n) after the forward wrote f->vout: Euler, or Euler + scale_noise + mask blend
+int scheduler_step(td_flux* f, void* latents, const float* sigmas, int i, int n, const InpaintBlend* b, void* stream) {
+  const long long count = (long long)f->S_img * f->cfg.in_channels;
+  if (!b) return td_euler_step_launch((bf16_t*)latents, f->vout, sigmas[i + 1] - sigmas[i], count, (hipStream_t)stream);
+  return td_flux_inpaint_step_launch((bf16_t*)latents, f->vout, (const bf16_t*)b->z, i < n - 1 ? (const bf16_t*)b->noise : nullptr,
+                                     (const bf16_t*)b->mask, sigmas[i + 1] - sigmas[i], sigmas[i + 1], count, (hipStream_t)stream);
+}
+
 // The FluxPipeline.__call__ loop: for i: v = transformer(x, t_i); x = bf16(float(x) + (sigma_{i+1}-sigma_i) float(v)).
-// latents [S_img, in_channels] bf16, updated in place; sigmas: n+1 host floats.
-int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void* stream) {
-  TD_CHECK_ARG(f && latents && sigmas, "td_flux_denoise: null argument");
-  TD_CHECK_ARG(n > 0 && n <= f->n_steps, "td_flux_denoise: n=%d exceeds the %d prepared timesteps", n, f->n_steps);
+// latents [S_img, in_channels] bf16, updated in place; sigmas: n+1 host floats.  blend: FluxInpaintPipeline's step instead.
+int denoise_loop(td_flux* f, void* latents, const float* sigmas, int n, const InpaintBlend* blend, void* stream) {
   for (int i = 0; i < n; ++i) {
     TD_TRY(td_flux_forward(f, latents, i, f->vout, stream));
-    TD_TRY(td_euler_step_launch((bf16_t*)latents, f->vout, sigmas[i + 1] - sigmas[i], (long long)f->S_img * f->cfg.in_channels, (hipStream_t)stream));
+    TD_TRY(scheduler_step(f, latents, sigmas, i, n, blend, stream));
   }
   return TD_OK;
 }
 
 // Several independent images in flight: contexts fs[k] (a parent and its forks) advance step by step, each on its own
 // stream, so the tail of one image's kernels (grids of 1.6 - 3.2 rounds of the 256 CUs) is filled by the other's.
-int td_flux_denoise_multi(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n, void* const* streams) {
-  TD_CHECK_ARG(fs && latents && sigmas && streams && count > 0, "td_flux_denoise_multi: null argument");
-  for (int k = 0; k < count; ++k)
-    TD_CHECK_ARG(fs[k] && latents[k] && n > 0 && n <= fs[k]->n_steps, "td_flux_denoise_multi: context %d is not prepared for %d steps", k, n);
+// blends: NULL, or one InpaintBlend per context.
+int denoise_multi_loop(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n, const InpaintBlend* blends,
+                       void* const* streams) {
   // With several images in flight the attention of each runs as a plain grid (one workgroup per item): its second, 59 %-empty
   // round is exactly what the other images' kernels fill, while the persistent form holds every CU for its whole duration
   // and shuts them out (measured, 3 in flight: 0.698 images/s persistent vs 0.71 plain; one image alone: 0.678 vs 0.655).
@@ -1210,11 +1246,50 @@ int td_flux_denoise_multi(td_flux* const* fs, void* const* latents, int count, c
     for (int k = 0; k < count && rc == TD_OK; ++k) {
       td_flux* f = fs[k];
       rc = td_flux_forward(f, latents[k], i, f->vout, streams[k]);
-      if (rc == TD_OK)
-        rc = td_euler_step_launch((bf16_t*)latents[k], f->vout, sigmas[i + 1] - sigmas[i], (long long)f->S_img * f->cfg.in_channels, (hipStream_t)streams[k]);
+      if (rc == TD_OK) rc = scheduler_step(f, latents[k], sigmas, i, n, blends ? &blends[k] : nullptr, streams[k]);
     }
   for (int k = 0; k < count; ++k) { fs[k]->attn_variant = 0; fs[k]->shared_chip = false; }
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void* stream) {
+  TD_CHECK_ARG(f && latents && sigmas, "td_flux_denoise: null argument");
+  TD_CHECK_ARG(n > 0 && n <= f->n_steps, "td_flux_denoise: n=%d exceeds the %d prepared timesteps", n, f->n_steps);
+  return denoise_loop(f, latents, sigmas, n, nullptr, stream);
+}
+
+int td_flux_denoise_inpaint(td_flux* f, void* latents, const float* sigmas, int n, const void* image_latents, const void* noise,
+                            const void* mask, void* stream) {
+  TD_CHECK_ARG(f && latents && sigmas, "td_flux_denoise_inpaint: null argument");
+  TD_CHECK_ARG(n > 0 && n <= f->n_steps, "td_flux_denoise_inpaint: n=%d exceeds the %d prepared timesteps", n, f->n_steps);
+  const InpaintBlend b{image_latents, noise, mask};
+  void* const lat[1] = {latents};
+  TD_TRY(check_blend("td_flux_denoise_inpaint", &f, lat, 1, 0, b));
+  return denoise_loop(f, latents, sigmas, n, &b, stream);
+}
+
+int td_flux_denoise_multi(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n, void* const* streams) {
+  TD_CHECK_ARG(fs && latents && sigmas && streams && count > 0, "td_flux_denoise_multi: null argument");
+  for (int k = 0; k < count; ++k)
+    TD_CHECK_ARG(fs[k] && latents[k] && n > 0 && n <= fs[k]->n_steps, "td_flux_denoise_multi: context %d is not prepared for %d steps", k, n);
+  return denoise_multi_loop(fs, latents, count, sigmas, n, nullptr, streams);
+}
+
+int td_flux_denoise_multi_inpaint(td_flux* const* fs, void* const* latents, int count, const float* sigmas, int n,
+                                  const void* const* image_latents, const void* const* noise, const void* const* mask, void* const* streams) {
+  TD_CHECK_ARG(fs && latents && sigmas && streams && image_latents && noise && mask && count > 0, "td_flux_denoise_multi_inpaint: null argument");
+  for (int k = 0; k < count; ++k)
+    TD_CHECK_ARG(fs[k] && latents[k] && n > 0 && n <= fs[k]->n_steps, "td_flux_denoise_multi_inpaint: context %d is not prepared for %d steps", k, n);
+  std::vector<InpaintBlend> blends(count);
+  for (int k = 0; k < count; ++k) {
+    blends[k] = InpaintBlend{image_latents[k], noise[k], mask[k]};
+    TD_TRY(check_blend("td_flux_denoise_multi_inpaint", fs, latents, count, k, blends[k]));
+  }
+  return denoise_multi_loop(fs, latents, count, sigmas, n, blends.data(), streams);
 }
 
 }  // extern "C"

@@ -139,6 +139,33 @@ at::Tensor& euler_step_(at::Tensor& x, const at::Tensor& v, double dt) {
   return x;
 }
 
+// FluxInpaintPipeline's step in place: Euler step, scale_noise of the image latents to bf16(sigma_next) (noise None: the clean latents) and
+// the mask blend, every op a bf16 torch op (td_flux_inpaint_step_bf16)
+at::Tensor& flux_inpaint_step_(at::Tensor& x, const at::Tensor& v, const at::Tensor& image_latents, const c10::optional<at::Tensor>& noise,
+                               const at::Tensor& mask, double dt, double sigma_next) {
+  check_rows(x, "x");
+  TORCH_CHECK(x.is_contiguous(), "thinkdiff_hip::flux_inpaint_step_: x must be contiguous");
+  check_vec(v, "v", x, x.numel()); check_vec(image_latents, "image_latents", x, x.numel());
+  check_vec(noise, "noise", x, x.numel()); check_vec(mask, "mask", x, x.numel());
+  DeviceGuard guard(x.device());
+  ok(td_flux_inpaint_step_bf16(x.data_ptr(), v.data_ptr(), image_latents.data_ptr(), P(noise), mask.data_ptr(), (float)dt, (float)sigma_next,
+                               x.numel(), stream_of(x)));
+  return x;
+}
+
+// binarize + F.interpolate(nearest) to (H/8, W/8) + repeat over C channels + _pack_latents: uint8 or float32 [H, W] -> bf16 [(H/16)(W/16), 4C]
+at::Tensor flux_inpaint_mask(const at::Tensor& mask, int64_t C) {
+  TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() && mask.dim() == 2, "thinkdiff_hip::flux_inpaint_mask: mask must be a contiguous GPU tensor [H, W]");
+  const bool u8 = mask.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || mask.scalar_type() == at::kFloat, "thinkdiff_hip::flux_inpaint_mask: mask must be uint8 or float32, got ", mask.scalar_type());
+  const int64_t H = mask.size(0), W = mask.size(1);
+  TORCH_CHECK(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0 && C > 0, "thinkdiff_hip::flux_inpaint_mask: H, W must be positive multiples of 16, got ", mask.sizes());
+  DeviceGuard guard(mask.device());
+  at::Tensor out = at::empty({(H / 16) * (W / 16), 4 * C}, mask.options().dtype(at::kBFloat16));
+  ok(td_flux_inpaint_mask(mask.data_ptr(), u8 ? TD_INPAINT_MASK_U8_HW : TD_INPAINT_MASK_F32_HW, (int)H, (int)W, (int)C, out.data_ptr(), stream_of(mask)));
+  return out;
+}
+
 at::Tensor flux_pack_latents(const at::Tensor& latents) {            // [C,H,W] -> [(H/2)(W/2), 4C]
   check_rows(latents, "latents");
   TORCH_CHECK(latents.dim() == 3 && latents.is_contiguous(), "thinkdiff_hip::flux_pack_latents: contiguous [C,H,W]");
@@ -228,6 +255,42 @@ void flux_denoise_multi_(at::ArrayRef<int64_t> engines, at::TensorList latents, 
   DeviceGuard guard(latents[0].device());
   ok(td_flux_denoise_multi(fs.data(), ls.data(), (int)fs.size(), sg.data(), (int)sg.size() - 1, ss.data()));
 }
+// FluxInpaintPipeline's loop in place: flux_denoise_ with the inpainting step (flux_inpaint_step_) after every forward; image_latents, noise
+// and mask are [S_img, in_channels] like the latents and must not overlap them
+at::Tensor& flux_denoise_inpaint_(int64_t engine, at::Tensor& latents, at::ArrayRef<double> sigmas, const at::Tensor& image_latents,
+                                  const at::Tensor& noise, const at::Tensor& mask) {
+  td_flux* f = flux_of(engine);
+  check_latents(f, latents, "latents");
+  check_latents(f, image_latents, "image_latents"); check_latents(f, noise, "noise"); check_latents(f, mask, "mask");
+  same_device(image_latents, "image_latents", latents); same_device(noise, "noise", latents); same_device(mask, "mask", latents);
+  TORCH_CHECK(sigmas.size() >= 2, "thinkdiff_hip::flux_denoise_inpaint_: sigmas needs n + 1 >= 2 entries");
+  std::vector<float> sg(sigmas.begin(), sigmas.end());
+  DeviceGuard guard(latents.device());
+  ok(td_flux_denoise_inpaint(f, latents.data_ptr(), sg.data(), (int)sg.size() - 1, image_latents.data_ptr(), noise.data_ptr(), mask.data_ptr(),
+                             stream_of(latents)));
+  return latents;
+}
+// the same for several prepared contexts at once, context k on streams[k], blended with image_latents[k], noise[k], mask[k]
+void flux_denoise_multi_inpaint_(at::ArrayRef<int64_t> engines, at::TensorList latents, at::ArrayRef<double> sigmas, at::TensorList image_latents,
+                                 at::TensorList noise, at::TensorList mask, at::ArrayRef<int64_t> streams) {
+  const size_t n = engines.size();
+  TORCH_CHECK(n > 0 && latents.size() == n && streams.size() == n && image_latents.size() == n && noise.size() == n && mask.size() == n,
+              "thinkdiff_hip::flux_denoise_multi_inpaint_: one latent tensor, blend triple and stream per engine");
+  TORCH_CHECK(sigmas.size() >= 2, "thinkdiff_hip::flux_denoise_multi_inpaint_: sigmas needs n + 1 >= 2 entries");
+  std::vector<td_flux*> fs; std::vector<void*> ls, ss; std::vector<const void*> zs, ns, ms;
+  for (size_t k = 0; k < n; ++k) {
+    fs.push_back(flux_of(engines[k]));
+    check_latents(fs.back(), latents[k], "latents[k]"); same_device(latents[k], "latents[k]", latents[0]);
+    check_latents(fs.back(), image_latents[k], "image_latents[k]"); same_device(image_latents[k], "image_latents[k]", latents[0]);
+    check_latents(fs.back(), noise[k], "noise[k]"); same_device(noise[k], "noise[k]", latents[0]);
+    check_latents(fs.back(), mask[k], "mask[k]"); same_device(mask[k], "mask[k]", latents[0]);
+    ls.push_back(latents[k].data_ptr()); ss.push_back((void*)(uintptr_t)streams[k]);
+    zs.push_back(image_latents[k].data_ptr()); ns.push_back(noise[k].data_ptr()); ms.push_back(mask[k].data_ptr());
+  }
+  std::vector<float> sg(sigmas.begin(), sigmas.end());
+  DeviceGuard guard(latents[0].device());
+  ok(td_flux_denoise_multi_inpaint(fs.data(), ls.data(), (int)n, sg.data(), (int)sg.size() - 1, zs.data(), ns.data(), ms.data(), ss.data()));
+}
 // AutoencoderKL.decode + VaeImageProcessor.postprocess: packed latents [(h/2)(w/2), 4C] -> uint8 [H, W, 3] (8h x 8w for the FLUX.1 VAE)
 at::Tensor vae_decode_u8(int64_t engine, const at::Tensor& packed, int64_t h, int64_t w, double scaling_factor, double shift_factor) {
   TORCH_CHECK(engine != 0, "thinkdiff_hip: null VAE engine handle");
@@ -307,6 +370,10 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("attention_fp8(Tensor q, Tensor k, Tensor v, int H, float scale) -> Tensor");
   m.def("vae_encode_moments(int engine, Tensor image, int H, int W) -> Tensor");
   m.def("vae_latents_from_moments(Tensor moments, Tensor? eps, Tensor? noise, float sigma, float scaling_factor, float shift_factor, int h, int w) -> Tensor");
+  m.def("flux_inpaint_step_(Tensor(a!) x, Tensor v, Tensor image_latents, Tensor? noise, Tensor mask, float dt, float sigma_next) -> Tensor(a!)");
+  m.def("flux_inpaint_mask(Tensor mask, int C) -> Tensor");
+  m.def("flux_denoise_inpaint_(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)");
+  m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -327,4 +394,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("attention_fp8", &attention_fp8);
   m.impl("vae_encode_moments", &vae_encode_moments);
   m.impl("vae_latents_from_moments", &vae_latents_from_moments);
+  m.impl("flux_inpaint_step_", &flux_inpaint_step_);
+  m.impl("flux_inpaint_mask", &flux_inpaint_mask);
+  m.impl("flux_denoise_inpaint_", &flux_denoise_inpaint_);
+  m.impl("flux_denoise_multi_inpaint_", &flux_denoise_multi_inpaint_);
 }

@@ -49,6 +49,8 @@ def _declare(L):
         "td_flux_rope_table": [vp, i32, vp, ctypes.c_double, vp, vp, vp],
         "td_timestep_sincos": [vp, i32, vp, vp],
         "td_euler_step_bf16": [vp, vp, f32, i64, vp],
+        "td_flux_inpaint_step_bf16": [vp, vp, vp, vp, vp, f32, f32, i64, vp],
+        "td_flux_inpaint_mask": [vp, i32, i32, i32, i32, vp, vp],
         "td_flux_pack_latents": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
         "td_cls_avgpool2_bf16": [vp, vp, i32, i32, vp],
         "td_fill_normal_bf16": [vp, i64, ctypes.c_uint64, f32, f32, vp],
@@ -67,10 +69,12 @@ def _declare(L):
         "td_vae_output_shape": [vp, i32, i32, vp, vp, vp],
         "td_flux_fork": [vp, vp],
         "td_flux_denoise_multi": [vp, vp, i32, vp, i32, vp],
+        "td_flux_denoise_multi_inpaint": [vp, vp, i32, vp, i32, vp, vp, vp, vp],
         "td_flux_set_condition": [vp, vp, i32, vp, vp, vp, i32, vp],
         "td_flux_set_timesteps": [vp, vp, i32, f32, vp],
         "td_flux_forward": [vp, vp, i32, vp, vp],
         "td_flux_denoise": [vp, vp, vp, i32, vp],
+        "td_flux_denoise_inpaint": [vp, vp, vp, i32, vp, vp, vp, vp],
         "td_flux_trace_begin": [vp, i32],
         "td_flux_trace_end": [vp, vp, vp, vp, vp],
         "td_attention_set_variant": [i32],

@@ -3,6 +3,7 @@ from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import BlipVisionT5DecoderForConditionalGeneration, build_vision_projector
 from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
+from .flux_inpaint import FluxInpaintPipelineRewritePrompt
 from .flux_prompt import FluxPipelineRewritePrompt
 from .flux_transformer import FluxTransformer2DModel, FluxTransformerConfig
 from .mllama_vllm_t5_embed_decoder_2 import MllamaVllmT5EmbedDecoderForConditionalGeneration_5
@@ -10,4 +11,5 @@ from .mllama_vllm_generate_1 import MllamaVllmGenerate_1
 from .qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
 
 __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration", "build_vision_projector",
-           "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxTransformer2DModel", "FluxTransformerConfig"]
+           "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
+           "FluxTransformer2DModel", "FluxTransformerConfig"]

@@ -197,9 +197,12 @@ class FluxPipelineRewritePrompt:
         xs = self._denoise_groups(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff)
         return self._finish(xs, h, w, output_type, return_dict)
 
-    def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff):
+    def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff,
+                        inpaint=None):
         """The denoise loop over `sig` (any sigma list ending in 0: the full schedule or a truncated one) for the first B packed latents
-        of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents."""
+        of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents.
+        inpaint: None, or per sample b an (image_latents, noise, mask) triple of [S, 64] tensors made on the current stream (the
+        inpainting loop, FluxTransformer2DModel.denoise)."""
         tr = self.transformer
         n_prompts = prompt_embeds.shape[0]
         # `images_in_flight` independent images advance together, each on its own stream and engine context (shared
@@ -219,11 +222,12 @@ class FluxPipelineRewritePrompt:
                     ctxs[k].set_condition(prompt_embeds[pb], pooled_prompt_embeds[min(pb, pooled_prompt_embeds.shape[0] - 1)], img_ids, text_ids)
                     ctxs[k].set_timesteps(t_eff, g_eff)
                     lat_g.append(lat[b].contiguous())
+            blend_g = None if inpaint is None else [inpaint[b] for b in group]
             if len(group) == 1:
                 with torch.cuda.stream(self._streams[0]):
-                    ctxs[0].denoise(lat_g[0], sig)
+                    ctxs[0].denoise(lat_g[0], sig, None if blend_g is None else blend_g[0])
             else:
-                type(tr).denoise_multi(ctxs[:len(group)], lat_g, sig, self._streams[:len(group)])
+                type(tr).denoise_multi(ctxs[:len(group)], lat_g, sig, self._streams[:len(group)], blend_g)
             for k in range(len(group)):
                 main.wait_stream(self._streams[k])
             xs.extend(lat_g)

@@ -86,9 +86,15 @@ class FluxTransformer2DModel:
         return child
 
     @staticmethod
-    def denoise_multi(contexts, latents, sigmas: Sequence[float], streams):
-        """td_flux_denoise for several prepared contexts at once, context k on streams[k] (torch.cuda.Stream)."""
-        _OPS.flux_denoise_multi_([int(m._h.value) for m in contexts], list(latents), [float(s) for s in sigmas], [int(st.cuda_stream) for st in streams])
+    def denoise_multi(contexts, latents, sigmas: Sequence[float], streams, inpaint=None):
+        """td_flux_denoise for several prepared contexts at once, context k on streams[k] (torch.cuda.Stream).  inpaint: None, or one
+        (image_latents, noise, mask) triple per context -- the inpainting step of `denoise` for each."""
+        engines, sg, ss = [int(m._h.value) for m in contexts], [float(s) for s in sigmas], [int(st.cuda_stream) for st in streams]
+        if inpaint is None:
+            _OPS.flux_denoise_multi_(engines, list(latents), sg, ss)
+        else:
+            z, noise, mask = (list(t) for t in zip(*inpaint))
+            _OPS.flux_denoise_multi_inpaint_(engines, list(latents), sg, z, noise, mask, ss)
         return latents
 
     # ---- parameters ---------------------------------------------------------------------------------
@@ -193,10 +199,15 @@ class FluxTransformer2DModel:
             out = torch.empty_like(latents)
         return _OPS.flux_forward_(int(self._h.value), latents, int(step), out)
 
-    def denoise(self, latents, sigmas: Sequence[float]):
-        """In-place Euler flow-matching loop over the prepared timesteps (len(sigmas) == n_steps + 1)."""
+    def denoise(self, latents, sigmas: Sequence[float], inpaint=None):
+        """In-place Euler flow-matching loop over the prepared timesteps (len(sigmas) == n_steps + 1).  inpaint: an (image_latents,
+        noise, mask) triple of [S_img, in_channels] bf16 tensors -- FluxInpaintPipeline's loop: after every step the latents are blended
+        with the image latents re-noised to the next sigma under the mask (flux_inpaint_step_)."""
         assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.in_channels)
-        return _OPS.flux_denoise_(int(self._h.value), latents, [float(s) for s in sigmas])
+        if inpaint is None:
+            return _OPS.flux_denoise_(int(self._h.value), latents, [float(s) for s in sigmas])
+        z, noise, mask = inpaint
+        return _OPS.flux_denoise_inpaint_(int(self._h.value), latents, [float(s) for s in sigmas], z, noise, mask)
 
     # ---- per-launch HIP-event trace (bench.py roofline leg) ------------------------------------------
     TRACE_CATEGORIES = ("gemm_256x256", "gemm_other", "attention", "layernorm_modulate", "qk_rmsnorm_rope", "gemm_288x192")

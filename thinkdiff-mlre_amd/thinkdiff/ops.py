@@ -25,6 +25,9 @@ vae_decode_u8              AutoencoderKL.decode + VaeImageProcessor.postprocess 
 attention_fp8              the joint attention with QK^T / P.V on the e4m3 MFMA
 vae_encode_moments         VaeImageProcessor.preprocess + AutoencoderKL.encode (posterior parameters) on a td_vae_enc* engine
 vae_latents_from_moments   posterior sample / mode, the img2img pipeline's shift / scale, scale_noise and _pack_latents, fused
+flux_inpaint_step_         FluxInpaintPipeline's step: scheduler.step + scale_noise of the image latents + mask blend, fused, in place
+flux_inpaint_mask          the inpainting mask's binarize, F.interpolate(nearest) to the latent size, repeat and _pack_latents, fused
+flux_denoise_inpaint_ / flux_denoise_multi_inpaint_   the inpainting denoise loop (flux_denoise_ / flux_denoise_multi_ with that step)
 """
 import os
 
@@ -53,6 +56,10 @@ SCHEMAS = {
     "attention_fp8": "(Tensor q, Tensor k, Tensor v, int H, float scale) -> Tensor",
     "vae_encode_moments": "(int engine, Tensor image, int H, int W) -> Tensor",
     "vae_latents_from_moments": "(Tensor moments, Tensor? eps, Tensor? noise, float sigma, float scaling_factor, float shift_factor, int h, int w) -> Tensor",
+    "flux_inpaint_step_": "(Tensor(a!) x, Tensor v, Tensor image_latents, Tensor? noise, Tensor mask, float dt, float sigma_next) -> Tensor(a!)",
+    "flux_inpaint_mask": "(Tensor mask, int C) -> Tensor",
+    "flux_denoise_inpaint_": "(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)",
+    "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
 }
 
 _loaded = False
