@@ -177,6 +177,17 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
  *   packed_out = _pack_latents(m.repeat(1, C, 1, 1))   -> bf16 [(H/16)(W/16), 4C] of 0 / 1
  * H, W multiples of 16; C even; packed_out 16-byte aligned. */
 int td_flux_inpaint_mask(const void* mask, int format, int H, int W, int C, void* packed_out, void* stream);
+/* FLUX.1 Fill's channel condition of one image, in one pass ([ext] diffusers >= 0.32 pipeline_flux_fill.py prepare_mask_latents):
+ * cond_out bf16 [S, 4C + 256], S = (H/16)(W/16), h = H/8, w = W/8:
+ *   columns 0 .. 4C-1:       _pack_latents((latent_dist.sample(eps) - shift) * scaling) of the MASKED image's moments [h*w, 2C]
+ *                            (td_vae_encode_masked) -- td_vae_latents_from_moments with noise = NULL, its arithmetic and rounding points;
+ *                            eps bf16 [C, h, w], NULL = .mode()
+ *   columns 4C .. 4C+255:    the binarized mask (td_flux_inpaint_mask's rule) at FULL resolution, unshuffled, not sampled:
+ *                            mask[H, W].view(h, 8, w, 8).permute(1, 3, 0, 2).reshape(64, h, w) -> _pack_latents, i.e. column
+ *                            4C + (py*8 + px)*4 + dy*2 + dx of token (Y, X) = m[8(2Y + dy) + py, 8(2X + dx) + px] as bf16 0 / 1.
+ * H, W multiples of 16; C even; cond_out 16-byte aligned. */
+int td_flux_fill_condition(const void* moments, const void* eps, const void* mask, int mask_format, int H, int W, float scaling_factor,
+                           float shift_factor, int C, void* cond_out, void* stream);
 /* FluxPipeline._pack_latents (unpack=0: [C,H,W] -> [(H/2)(W/2),4C]) / _unpack_latents (unpack=1, with
  * out = bf16(bf16(in / div) + add), i.e. the `latents / scaling_factor + shift_factor` on bf16 tensors that precedes
  * vae.decode in [ext] pipeline_flux.py, with torch's CPU scalar rules: fp32 divisor, addend cast to bf16, quotient and sum
@@ -219,6 +230,10 @@ typedef struct TdFluxConfig {
   int mlp_ratio;          /* 4   */
   int axes_dims[3];       /* 16,56,56 */
   float rope_theta;       /* 10000 */
+  int out_channels;       /* 0 = in_channels (FLUX.1-dev: 64).  FLUX.1 Fill 64 of 384, FLUX.1 Canny / Depth 64 of 128: the checkpoints whose
+                           * x_embedder reads the latents and a per-image condition concatenated along the channel axis, in_channels =
+                           * out_channels + C_cond, while proj_out, the velocity and the latents the scheduler steps keep out_channels.
+                           * Both multiples of 64.  Last field: a caller that zero-fills the struct keeps the unconditioned model. */
 } TdFluxConfig;
 
 int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_tokens, int max_steps, td_flux** out);
@@ -278,9 +293,23 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
  * guidance*1000 after the pipeline's dtype casts); precomputes temb and every adaLN modulation */
 int td_flux_set_timesteps(td_flux* f, const float* t_eff, int n, float g_eff, void* stream);
 /* The extents a prepared context expects: image / text tokens of the last td_flux_set_condition (0 before it), latent channels, prepared
- * timesteps.  Any out pointer may be NULL.  (The torch.ops layer checks tensor extents against it before handing pointers over.) */
+ * timesteps.  Any out pointer may be NULL.  (The torch.ops layer checks tensor extents against it before handing pointers over.)
+ * `in_channels` is the width of the LATENTS and of the velocity (TdFluxConfig::out_channels; on an unconditioned engine that is also
+ * x_embedder's width -- td_flux_input_shape reports the two apart). */
 int td_flux_prepared_shape(const td_flux* f, int* img_tokens, int* txt_tokens, int* in_channels, int* n_steps);
-/* velocity[S_img,in_channels] = transformer(latents[S_img,in_channels]; prepared step) */
+/* What x_embedder reads: its width (TdFluxConfig::in_channels), the channel condition's share of it (in_channels - out_channels, 0 on an
+ * unconditioned engine) and whether this context holds a valid channel condition.  Any out pointer may be NULL. */
+int td_flux_input_shape(const td_flux* f, int* in_channels, int* cond_channels, int* cond_valid);
+/* The per-image channel condition of a conditioned engine (C_cond = in_channels - out_channels > 0): cond bf16 [S_img, C_cond], S_img of the
+ * last td_flux_set_condition, 16-byte aligned; copied into this context's x_embedder staging rows at columns out_channels .. in_channels - 1
+ * (forks own theirs), where every later forward of the image finds it.  Replaces the `torch.cat([latents, masked_image_latents], dim=2)` /
+ * `torch.cat([latents, control_image], dim=2)` that [ext] diffusers >= 0.32 FluxFillPipeline / FluxControlPipeline.__call__ make in front of
+ * every transformer call.  td_flux_set_condition with another S_img invalidates it; a forward without a valid one is TD_ERR_INVALID (never
+ * a run on zeros); on an unconditioned engine the call itself is TD_ERR_INVALID.  Forgets the 8-bit modes' per-token history like
+ * td_flux_set_condition (another image). */
+int td_flux_set_channel_condition(td_flux* f, const void* cond, void* stream);
+/* velocity[S_img,out_channels] = transformer(latents[S_img,out_channels]; prepared step).  On a conditioned engine the latents are gathered
+ * beside the channel condition and x_embedder runs as ONE Linear over in_channels, as on torch.cat([latents, cond]). */
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream);
 /* Per-launch HIP-event trace of the engine's kernels (events recorded on the launch stream).
  * categories: 0 GEMM 256x256 tile (td_gemm_bf16_nt_kernel<8,4>), 1 small GEMM tiles, 2 attention,
@@ -293,7 +322,7 @@ int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void*
 /* FluxInpaintPipeline's loop: n steps in place, each the transformer then td_flux_inpaint_step_bf16 with
  *   dt = sigmas[i+1] - sigmas[i],  sigma_next = sigmas[i+1],  noise used for i < n-1 (the last step blends the clean image_latents).
  * image_latents (the packed clean latents z), noise (the packed start noise) and mask (td_flux_inpaint_mask's output): bf16
- * [S_img, in_channels], 16-byte aligned, none NULL, none overlapping the latents. */
+ * [S_img, out_channels] (the latents' width), 16-byte aligned, none NULL, none overlapping the latents. */
 int td_flux_denoise_inpaint(td_flux* f, void* latents, const float* sigmas, int n, const void* image_latents, const void* noise,
                             const void* mask, void* stream);
 
@@ -399,6 +428,12 @@ int td_vae_enc_init_random(td_vae_enc* f, uint64_t seed, float std, void* stream
  * per latent pixel (H/2^(num_blocks-1) for other depths).  H, W multiples of 16 within the capacity, the mid block's pixel count
  * a multiple of 64; refused before any launch otherwise.  No allocation. */
 int td_vae_encode(td_vae_enc* f, const void* image, int image_format, int H, int W, void* moments_nhwc, void* stream);
+/* td_vae_encode of `masked_image = image * (1 - mask)` ([ext] diffusers >= 0.32 FluxFillPipeline.__call__; the product is taken in fp32
+ * on the preprocessed image and rounded to bf16 by prepare_mask_latents' `.to(dtype)`): the image-in kernel writes bf16(2x - 1) where the
+ * binarized mask is 0 and a zero where it is 1 (the zero keeps the sign of 2x - 1, as the fp32 product does).  mask: [H, W] at full pixel
+ * resolution, format TD_INPAINT_MASK_* and td_flux_inpaint_mask's binarization (uint8 >= 128, float32 >= 0.5).  Then the encoder as it is. */
+int td_vae_encode_masked(td_vae_enc* f, const void* image, int image_format, const void* mask, int mask_format, int H, int W,
+                         void* moments_nhwc, void* stream);
 /* The moments td_vae_encode writes for an H x W image: h x w latent pixels (H / 2^(num_blocks-1): H/8 for the FLUX.1 VAE) of
  * 2 x latent_channels; out pointers may be NULL.  (The torch.ops layer sizes its output with it.) */
 int td_vae_enc_output_shape(const td_vae_enc* f, int H, int W, int* h, int* w, int* moment_channels);
@@ -411,6 +446,9 @@ int td_vae_latents_from_moments(const void* moments, const void* eps, const void
 /* VaeImageProcessor.preprocess + .to(bf16) alone: out bf16 [H*W, Cpad] NHWC = RNE(2 x - 1) with x = float32(u8) / 255 or the
  * float32 [0,1] value; channels 3 .. Cpad-1 zero.  Cpad % 8 == 0. */
 int td_vae_image_to_nhwc_bf16(const void* image, int image_format, int H, int W, void* out, int Cpad, void* stream);
+/* ... of image * (1 - binarize(mask)): the first stage of td_vae_encode_masked alone. */
+int td_vae_image_to_nhwc_masked_bf16(const void* image, int image_format, const void* mask, int mask_format, int H, int W, void* out, int Cpad,
+                                     void* stream);
 /* Downsample2D(use_conv=True, padding=0): F.pad(x, (0,1,0,1)) then a 3x3 conv, stride 2, no padding, as an implicit GEMM:
  *   y[(Hin/2)(Win/2), Cout] = conv3x3_s2(x[Hin*Win, Cin]) + bias;   Hin, Win even, Cin % 64 == 0, w packed as for td_conv3x3_nhwc_bf16. */
 int td_conv3x3_s2_nhwc_bf16(const void* x, const void* w, const void* bias, void* y, int Hin, int Win, int Cin, int Cout, void* stream);

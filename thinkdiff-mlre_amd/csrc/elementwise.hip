@@ -425,6 +425,27 @@ int td_flux_inpaint_mask_launch(const void* mask, int fmt, int H, int W, int C, 
   return 0;
 }
 
+// dst[r, 0 .. cols) = src[r, 0 .. cols) between two row-major bf16 matrices of different row strides: the channel-conditioned FLUX engine's
+// x_embedder operand xin = cat(latents, cond) along the channel axis -- the latents go to its first columns at the head of every forward,
+// the condition to the rest once per image (td_flux_set_channel_condition) -- [ext] diffusers >= 0.32 FluxFillPipeline / FluxControlPipeline
+// `torch.cat([latents, masked_image_latents | control_image], dim=2)`.  One lane per 8 columns: 16-byte loads and (strided) stores.
+__global__ void td_copy_cols_kernel(const bf16_t* src, int lds, bf16_t* dst, int ldd, int rows, int chunks) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * chunks) return;
+  const int r = idx / chunks, c = idx - r * chunks;
+  *(u32x4_t*)(dst + (size_t)r * ldd + c * 8) = *(const u32x4_t*)(src + (size_t)r * lds + c * 8);
+}
+
+int td_copy_cols_launch(const bf16_t* src, int lds, bf16_t* dst, int ldd, int rows, int cols, hipStream_t stream) {
+  TD_CHECK_ARG(src && dst && rows > 0 && cols > 0, "td_copy_cols: empty problem");
+  TD_CHECK_ARG(cols % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && cols <= lds && cols <= ldd, "td_copy_cols: cols=%d, lds=%d, ldd=%d must be multiples of 8, cols within both", cols, lds, ldd);
+  TD_CHECK_ARG(((uintptr_t)src | (uintptr_t)dst) % 16 == 0, "td_copy_cols: both buffers must be 16-byte aligned");
+  TD_GRID_1D_I32(nblk, (long long)rows * (cols / 8), 256, "td_copy_cols");
+  hipLaunchKernelGGL(td_copy_cols_kernel, dim3(nblk), dim3(256), 0, stream, src, lds, dst, ldd, rows, cols / 8);
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream) {
   TD_CHECK_ARG(n > 0 && n % 8 == 0, "td_euler_step: n=%lld must be a positive multiple of 8", n);
   TD_GRID_1D_I32(nblk, n / 8, 256, "td_euler_step");

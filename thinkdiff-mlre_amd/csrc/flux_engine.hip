@@ -135,6 +135,12 @@ struct td_flux {
   // state
   int T = 0, S_img = 0, n_steps = 0;
   bool cond_set = false;
+  // channel conditioning (FLUX.1 Fill / Canny / Depth): x_embedder reads Cin = Cout + Ccond columns, everything from proj_out on has Cout.
+  // xin [max_img, Cin] is the per-context operand of x_embedder: the latents are gathered into its first Cout columns at the head of every
+  // forward, td_flux_set_channel_condition writes the rest once per image.  Ccond == 0: no xin, the forward reads the caller's latents.
+  int Cin = 0, Cout = 0, Ccond = 0;
+  bf16_t* xin = nullptr;
+  bool ccond_set = false;
   // optional per-launch HIP-event trace (bench.py roofline leg)
   bool tracing = false;
   std::vector<hipEvent_t> ev_pool;
@@ -313,7 +319,8 @@ int alloc_workspace(td_flux* f) {
   std::vector<Req> reqs = {
       {(void**)&f->h, S * D * 2}, {(void**)&f->xn, S * D * 2}, {(void**)&f->qkv, S * 3 * D * 2},
       {(void**)&f->attn, S * D * 2}, {(void**)&f->mlp, S * M * 2}, {(void**)&f->cat, S * (D + M) * 2},
-      {(void**)&f->ctx, (int64_t)max_txt_tokens * D * 2}, {(void**)&f->vout, (int64_t)max_img_tokens * cfg->in_channels * 2},
+      {(void**)&f->ctx, (int64_t)max_txt_tokens * D * 2}, {(void**)&f->vout, (int64_t)max_img_tokens * f->Cout * 2},
+      {(void**)&f->xin, f->Ccond > 0 ? (int64_t)max_img_tokens * f->Cin * 2 : 0},
       {(void**)&f->tproj, n * 256 * 2}, {(void**)&f->tmid, n * D * 2}, {(void**)&f->te, n * D * 2},
       {(void**)&f->gproj, 256 * 2}, {(void**)&f->gmid, (int64_t)D * 2}, {(void**)&f->ge, (int64_t)D * 2},
       {(void**)&f->pmid, (int64_t)D * 2}, {(void**)&f->pe, (int64_t)D * 2},
@@ -342,7 +349,7 @@ int alloc_workspace(td_flux* f) {
   (void)hipDeviceSynchronize();   // the handle may be used from any stream next; a null-stream memset is not ordered with non-blocking streams
   int64_t o = 0;
   for (auto& r : reqs) {
-    *r.p = f->ws + o;
+    *r.p = r.bytes ? f->ws + o : nullptr;
     o += (r.bytes + 255) & ~int64_t(255);
   }
   return TD_OK;
@@ -359,8 +366,15 @@ int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_toke
   TD_CHECK_ARG(cfg->in_channels % 64 == 0 && cfg->joint_dim % 64 == 0 && cfg->pooled_dim % 64 == 0, "td_flux_create: input widths must be multiples of 64");
   TD_CHECK_ARG((cfg->num_heads * 128) % 512 == 0, "td_flux_create: inner dim must be a multiple of 512");
   TD_CHECK_ARG(max_img_tokens > 0 && max_txt_tokens > 0 && max_steps > 0, "td_flux_create: capacities must be positive");
+  const int c_out = cfg->out_channels ? cfg->out_channels : cfg->in_channels;
+  TD_CHECK_ARG(cfg->in_channels > 0 && c_out > 0 && c_out % 64 == 0, "td_flux_create: in_channels=%d, out_channels=%d must be positive multiples of 64",
+               cfg->in_channels, c_out);
+  TD_CHECK_ARG(c_out <= cfg->in_channels, "td_flux_create: out_channels=%d exceeds in_channels=%d (in_channels = out_channels + the channel condition's width)",
+               c_out, cfg->in_channels);
   td_flux* f = new td_flux();
   f->cfg = *cfg;
+  f->cfg.out_channels = c_out;
+  f->Cin = cfg->in_channels; f->Cout = c_out; f->Ccond = cfg->in_channels - c_out;
   const int D = f->D = cfg->num_heads * cfg->head_dim;
   const int M = f->M = cfg->mlp_ratio * D;
   const int L = cfg->num_layers, Ls = cfg->num_single_layers;
@@ -380,7 +394,7 @@ int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_toke
   ap.take(&f->p1_w, (int64_t)D * cfg->pooled_dim); ap.take(&f->p1_b, D);
   ap.take(&f->p2_w, (int64_t)D * D); ap.take(&f->p2_b, D);
   ap.take(&f->mod_w, (int64_t)f->NMOD * D); ap.take(&f->mod_b, f->NMOD);
-  ap.take(&f->proj_w, (int64_t)cfg->in_channels * D); ap.take(&f->proj_b, cfg->in_channels);
+  ap.take(&f->proj_w, (int64_t)f->Cout * D); ap.take(&f->proj_b, f->Cout);
   for (auto& w : f->dbl) {
     ap.take(&w.qkv_img_w, (int64_t)3 * D * D); ap.take(&w.qkv_img_b, 3 * D);
     ap.take(&w.qkv_ctx_w, (int64_t)3 * D * D); ap.take(&w.qkv_ctx_b, 3 * D);
@@ -452,7 +466,7 @@ int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_toke
     add_slot(f, p + "attn.norm_k.weight", w.norm_k, 128);
   }
   add_linear(f, "norm_out.linear", f->mod_w, f->mod_b, (int64_t)L * 12 * D + (int64_t)Ls * 3 * D, 2 * D, D);
-  add_linear(f, "proj_out", f->proj_w, f->proj_b, 0, cfg->in_channels, D);
+  add_linear(f, "proj_out", f->proj_w, f->proj_b, 0, f->Cout, D);
 
   if (int rc = alloc_workspace(f)) {
     (void)hipFree(f->arena);
@@ -485,7 +499,7 @@ int td_flux_fork(td_flux* src, td_flux** out) {
   f->parent = root;
   f->ws = nullptr;
   f->ev_pool.clear(); f->trace.clear(); f->tracing = false;
-  f->T = f->S_img = f->n_steps = 0; f->cond_set = false;
+  f->T = f->S_img = f->n_steps = 0; f->cond_set = false; f->ccond_set = false;
   if (int rc = alloc_workspace(f)) { delete f; return rc; }
   *out = f;
   return TD_OK;
@@ -861,6 +875,7 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
                "td_flux_set_condition: T=%d / S_img=%d exceed capacity (%d / %d)", T, S_img, f->max_txt, f->max_img);
   hipStream_t s = (hipStream_t)stream;
   const int D = f->D;
+  if (S_img != f->S_img) f->ccond_set = false;      // the channel condition was written for another token count
   f->T = T; f->S_img = S_img;
   TD_TRY(gemm(f, s, (const bf16_t*)prompt_embeds, f->cfg.joint_dim, f->ctx_w, f->ctx_b, f->ctx, D, T, D, f->cfg.joint_dim));
   TD_TRY(gemm(f, s, (const bf16_t*)pooled, f->cfg.pooled_dim, f->p1_w, f->p1_b, f->pmid, D, 1, D, f->cfg.pooled_dim, TD_ACT_SILU));
@@ -872,6 +887,19 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
   f->cond_set = true;
   f->n_steps = 0;
   f->hs_step = f->href_step = -1;      // another image: the previous one's maxima / reference points say nothing about it
+  return TD_OK;
+}
+
+// The channel condition of one image (conditioned engines): cond [S_img, Ccond] -> xin[:, Cout .. Cin), where every forward's x_embedder
+// GEMM reads it beside the gathered latents.
+int td_flux_set_channel_condition(td_flux* f, const void* cond, void* stream) {
+  TD_CHECK_ARG(f && cond, "td_flux_set_channel_condition: null argument");
+  TD_CHECK_ARG(f->Ccond > 0, "td_flux_set_channel_condition: this engine takes no channel condition (in_channels = out_channels = %d)", f->Cout);
+  TD_CHECK_ARG(f->cond_set, "td_flux_set_channel_condition: call td_flux_set_condition first (it fixes the image token count)");
+  TD_CHECK_ARG((uintptr_t)cond % 16 == 0, "td_flux_set_channel_condition: cond must be 16-byte aligned");
+  TD_TRY(td_copy_cols_launch((const bf16_t*)cond, f->Ccond, f->xin + f->Cout, f->Cin, f->S_img, f->Ccond, (hipStream_t)stream));
+  f->ccond_set = true;
+  f->hs_step = f->href_step = -1;      // another image, as in td_flux_set_condition: the previous one's per-token history says nothing about it
   return TD_OK;
 }
 
@@ -915,23 +943,33 @@ int td_flux_set_timesteps(td_flux* f, const float* t_eff, int n, float g_eff, vo
   return TD_OK;
 }
 
-// One transformer evaluation: velocity[S_img, in_channels] = FluxTransformer2DModel(latents; step).
+// One transformer evaluation: velocity[S_img, out_channels] = FluxTransformer2DModel(latents; step).
 // What the prepared context expects of its callers' buffers (the torch.ops layer validates tensor extents against it).
 int td_flux_prepared_shape(const td_flux* f, int* img_tokens, int* txt_tokens, int* in_channels, int* n_steps) {
   TD_CHECK_ARG(f, "td_flux_prepared_shape: null context");
   if (img_tokens) *img_tokens = f->cond_set ? f->S_img : 0;
   if (txt_tokens) *txt_tokens = f->cond_set ? f->T : 0;
-  if (in_channels) *in_channels = f->cfg.in_channels;
+  if (in_channels) *in_channels = f->Cout;      // the latents' and the velocity's width (== x_embedder's on an unconditioned engine)
   if (n_steps) *n_steps = f->n_steps;
+  return TD_OK;
+}
+
+int td_flux_input_shape(const td_flux* f, int* in_channels, int* cond_channels, int* cond_valid) {
+  TD_CHECK_ARG(f, "td_flux_input_shape: null context");
+  if (in_channels) *in_channels = f->Cin;
+  if (cond_channels) *cond_channels = f->Ccond;
+  if (cond_valid) *cond_valid = f->Ccond > 0 && f->cond_set && f->ccond_set;
   return TD_OK;
 }
 
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream) {
   TD_CHECK_ARG(f && latents && velocity, "td_flux_forward: null argument");
   TD_CHECK_ARG(f->cond_set && step >= 0 && step < f->n_steps, "td_flux_forward: step %d outside the %d prepared timesteps", step, f ? f->n_steps : 0);
+  TD_CHECK_ARG(f->Ccond == 0 || f->ccond_set, "td_flux_forward: this engine reads a %d-channel condition beside the %d latent channels and none is set for "
+               "the %d image tokens (td_flux_set_channel_condition after td_flux_set_condition)", f->Ccond, f->Cout, f->S_img);
   hipStream_t s = (hipStream_t)stream;
   const int D = f->D, M = f->M, T = f->T, S = f->T + f->S_img, Si = f->S_img;
-  const int H = f->cfg.num_heads, C = f->cfg.in_channels;
+  const int H = f->cfg.num_heads, C = f->Cout;
   const int L = f->cfg.num_layers, Ls = f->cfg.num_single_layers;
   const bf16_t* mod = f->mods + (size_t)step * f->NMOD;
   bf16_t* h = f->h;
@@ -939,7 +977,13 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
   const float scale = 0.08838834764831845f;  // 128^-0.5
 
   TD_CHECK_HIP(hipMemcpyAsync(h, f->ctx, (size_t)T * D * 2, hipMemcpyDeviceToDevice, s));
-  TD_TRY(gemm(f, s, (const bf16_t*)latents, C, f->x_w, f->x_b, h_img, D, Si, D, C));
+  if (f->Ccond > 0) {      // Linear(cat(latents, cond)): the latents join the condition in xin, then ONE GEMM over K = Cin (one fp32 sum, one rounding)
+    TD_CHECK_ARG((uintptr_t)latents % 16 == 0, "td_flux_forward: latents must be 16-byte aligned");
+    TD_TRY(td_copy_cols_launch((const bf16_t*)latents, C, f->xin, f->Cin, Si, C, s));
+    TD_TRY(gemm(f, s, f->xin, f->Cin, f->x_w, f->x_b, h_img, D, Si, D, f->Cin));
+  } else {
+    TD_TRY(gemm(f, s, (const bf16_t*)latents, C, f->x_w, f->x_b, h_img, D, Si, D, C));
+  }
 
   TdNormParams np;
   np.x = h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = S; np.D = D; np.eps = 1e-6f; np.split = T;
@@ -1200,13 +1244,13 @@ bool overlaps(const void* a, size_t na, const void* b, size_t nb) {
 // blend k's buffers: present, 16-byte aligned, and clear of every latents buffer the loop writes
 int check_blend(const char* fn, td_flux* const* fs, void* const* latents, int count, int k, const InpaintBlend& b) {
   TD_CHECK_ARG(b.z && b.noise && b.mask, "%s: image %d: image_latents, noise and mask are required", fn, k);
-  const size_t bytes = (size_t)fs[k]->S_img * fs[k]->cfg.in_channels * sizeof(bf16_t);
+  const size_t bytes = (size_t)fs[k]->S_img * fs[k]->Cout * sizeof(bf16_t);
   const void* bufs[3] = {b.z, b.noise, b.mask};
   static const char* names[3] = {"image_latents", "noise", "mask"};
   for (int j = 0; j < 3; ++j) {
     TD_CHECK_ARG((uintptr_t)bufs[j] % 16 == 0, "%s: image %d: %s must be 16-byte aligned", fn, k, names[j]);
     for (int l = 0; l < count; ++l)
-      TD_CHECK_ARG(!overlaps(bufs[j], bytes, latents[l], (size_t)fs[l]->S_img * fs[l]->cfg.in_channels * sizeof(bf16_t)),
+      TD_CHECK_ARG(!overlaps(bufs[j], bytes, latents[l], (size_t)fs[l]->S_img * fs[l]->Cout * sizeof(bf16_t)),
                    "%s: image %d: %s overlaps the latents of image %d (the loop writes them in place)", fn, k, names[j], l);
   }
   return TD_OK;
@@ -1214,14 +1258,14 @@ int check_blend(const char* fn, td_flux* const* fs, void* const* latents, int co
 
 // the scheduler step of loop step i (of n) after the forward wrote f->vout: Euler, or Euler + scale_noise + mask blend
 int scheduler_step(td_flux* f, void* latents, const float* sigmas, int i, int n, const InpaintBlend* b, void* stream) {
-  const long long count = (long long)f->S_img * f->cfg.in_channels;
+  const long long count = (long long)f->S_img * f->Cout;
   if (!b) return td_euler_step_launch((bf16_t*)latents, f->vout, sigmas[i + 1] - sigmas[i], count, (hipStream_t)stream);
   return td_flux_inpaint_step_launch((bf16_t*)latents, f->vout, (const bf16_t*)b->z, i < n - 1 ? (const bf16_t*)b->noise : nullptr,
                                      (const bf16_t*)b->mask, sigmas[i + 1] - sigmas[i], sigmas[i + 1], count, (hipStream_t)stream);
 }
 
 // The FluxPipeline.__call__ loop: for i: v = transformer(x, t_i); x = bf16(float(x) + (sigma_{i+1}-sigma_i) float(v)).
-// latents [S_img, in_channels] bf16, updated in place; sigmas: n+1 host floats.  blend: FluxInpaintPipeline's step instead.
+// latents [S_img, out_channels] bf16, updated in place; sigmas: n+1 host floats.  blend: FluxInpaintPipeline's step instead.
 int denoise_loop(td_flux* f, void* latents, const float* sigmas, int n, const InpaintBlend* blend, void* stream) {
   for (int i = 0; i < n; ++i) {
     TD_TRY(td_flux_forward(f, latents, i, f->vout, stream));

@@ -44,7 +44,11 @@ namespace {
 // uint8 HWC: x = float32(u8) / 255 (pil_to_numpy), 2x - 1 (normalize), RNE to bf16; float32 CHW in [0,1]: 2x - 1, RNE to bf16.
 // Every step is one IEEE fp32 operation (explicit _rn intrinsics: no contraction into an fma), as numpy / torch compute it.
 // One thread per (pixel, 8-channel chunk): 16-byte stores.
-__global__ void td_vae_image_in_kernel(const void* src, int fmt, int H, int W, bf16_t* out, int Cpad) {
+// MASKED (FLUX.1 Fill, [ext] diffusers >= 0.32 pipeline_flux_fill.py `masked_image = image * (1 - mask)` on the fp32 preprocessed image, then
+// `.to(bf16)`): the value is multiplied by 1 - m in fp32 before the rounding, m = the binarized mask pixel (u8 >= 128, f32 >= 0.5; [H, W] at
+// full resolution).  With m in {0, 1} that is the unmasked value or a zero carrying its sign.
+template <bool MASKED>
+__global__ void td_vae_image_in_kernel(const void* src, int fmt, int H, int W, bf16_t* out, int Cpad, const void* mask, int mfmt) {
   const int chunks = Cpad >> 3;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= H * W * chunks) return;
@@ -58,18 +62,27 @@ __global__ void td_vae_image_in_kernel(const void* src, int fmt, int H, int W, b
                                              : ((const float*)src)[(size_t)c * H * W + pix];
       v[c] = __fsub_rn(__fmul_rn(2.0f, x), 1.0f);
     }
+    if (MASKED) {
+      const bool on = mfmt == TD_INPAINT_MASK_U8_HW ? ((const unsigned char*)mask)[pix] >= 128 : ((const float*)mask)[pix] >= 0.5f;
+      const float keep = __fsub_rn(1.0f, on ? 1.0f : 0.0f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v[c] = __fmul_rn(v[c], keep);
+    }
     o[0] = pack_bf2(v[0], v[1]);
     o[1] = pack_bf2(v[2], 0.f);
   }
   *(u32x4_t*)(out + (size_t)pix * Cpad + ch * 8) = o;
 }
 
-int image_in_launch(const void* src, int fmt, int H, int W, bf16_t* out, int Cpad, hipStream_t s) {
+// mask == NULL: the plain image; else the masked image (mfmt = TD_INPAINT_MASK_*)
+int image_in_launch(const void* src, int fmt, int H, int W, bf16_t* out, int Cpad, hipStream_t s, const void* mask = nullptr, int mfmt = 0) {
   TD_CHECK_ARG(src && out && H > 0 && W > 0 && Cpad >= 8 && Cpad % 8 == 0, "td_vae_image_to_nhwc: bad arguments");
+  TD_CHECK_ARG(!mask || mfmt == TD_INPAINT_MASK_U8_HW || mfmt == TD_INPAINT_MASK_F32_HW, "td_vae_image_to_nhwc: unknown mask format %d", mfmt);
   TD_CHECK_ARG(fmt == TD_IMAGE_U8_HWC || fmt == TD_IMAGE_F32_CHW, "td_vae_image_to_nhwc: unknown image format %d", fmt);
   TD_CHECK_ARG(((uintptr_t)out) % 16 == 0, "td_vae_image_to_nhwc: out must be 16-byte aligned");
   TD_GRID_1D_I32(nblk, (long long)H * W * (Cpad / 8), 256, "td_vae_image_to_nhwc");
-  hipLaunchKernelGGL(td_vae_image_in_kernel, dim3(nblk), dim3(256), 0, s, src, fmt, H, W, out, Cpad);
+  if (mask) hipLaunchKernelGGL(td_vae_image_in_kernel<true>, dim3(nblk), dim3(256), 0, s, src, fmt, H, W, out, Cpad, mask, mfmt);
+  else hipLaunchKernelGGL(td_vae_image_in_kernel<false>, dim3(nblk), dim3(256), 0, s, src, fmt, H, W, out, Cpad, (const void*)nullptr, 0);
   TD_CHECK_LAUNCH();
   return 0;
 }
@@ -81,11 +94,10 @@ int image_in_launch(const void* src, int fmt, int H, int W, bf16_t* out, int Cpa
 //   scale_noise:                  x = sigma * noise + (1 - sigma) * z   with sigma = bf16(sigma)            (noise NULL: x = z)
 //   _pack_latents:                row (y/2)(w/2) + x/2, column 4c + 2(y&1) + (x&1)
 // eps / noise are NCHW [C, h, w] bf16 (what torch.randn(..., dtype=bf16) draws for one image).
-__global__ void td_vae_latents_kernel(const bf16_t* mom, const bf16_t* eps, const bf16_t* noise, float sigma, float scaling, float shift,
-                                      int C, int h, int w, bf16_t* out) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= h * w * C) return;
-  const int col = idx % (4 * C), tok = idx / (4 * C);
+// latent_value: column `col` of packed token `tok` (shared by td_vae_latents_kernel and td_flux_fill_condition_kernel, as euler8 is shared by the
+// two step kernels); the result is a bf16 value held in fp32.
+__device__ __forceinline__ float latent_value(const bf16_t* mom, const bf16_t* eps, const bf16_t* noise, float sigma, float scaling, float shift,
+                                              int C, int h, int w, int tok, int col) {
   const int c = col >> 2, y = (tok / (w >> 1)) * 2 + ((col >> 1) & 1), x = (tok % (w >> 1)) * 2 + (col & 1);
   const int pix = y * w + x;
   float z = bf2f(mom[(size_t)pix * 2 * C + c]);
@@ -99,7 +111,47 @@ __global__ void td_vae_latents_kernel(const bf16_t* mom, const bf16_t* eps, cons
     const float s = rbf(sigma);
     z = rbf(__fadd_rn(rbf(__fmul_rn(s, bf2f(noise[(size_t)c * h * w + pix]))), rbf(__fmul_rn(rbf(__fsub_rn(1.0f, s)), z))));
   }
-  out[idx] = f2bf(z);
+  return z;
+}
+
+__global__ void td_vae_latents_kernel(const bf16_t* mom, const bf16_t* eps, const bf16_t* noise, float sigma, float scaling, float shift,
+                                      int C, int h, int w, bf16_t* out) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= h * w * C) return;
+  out[idx] = f2bf(latent_value(mom, eps, noise, sigma, scaling, shift, C, h, w, idx / (4 * C), idx % (4 * C)));
+}
+
+// ---- FLUX.1 Fill's channel condition of one image: [S, 4C + 256] = packed masked-image latents | unshuffled mask ------------------
+// [ext] diffusers >= 0.32 pipeline_flux_fill.py prepare_mask_latents:
+//   masked_image_latents = _pack_latents((vae.encode(masked_image).latent_dist.sample(generator) - shift) * scaling)
+//   mask = mask[:, 0].view(B, h, 8, w, 8).permute(0, 2, 4, 1, 3).reshape(B, 64, h, w);  mask = _pack_latents(mask)
+//   masked_image_latents = torch.cat((masked_image_latents, mask), dim=-1)
+// The first 4C columns are latent_value with noise = NULL.  Mask column (py*8 + px)*4 + dy*2 + dx of token (Y, X) is the binarized mask
+// pixel (8(2Y + dy) + py, 8(2X + dx) + px): every pixel of the 16 x 16 patch of a token lands in exactly one of its 256 columns.
+// One lane per 8 output columns (16-byte stores): latent chunk j = channels 2j, 2j+1; mask chunk k = (py, px) in {(k >> 2, 2 (k & 3)), +1 in px},
+// whose two mask pixels per (dy, dx) are neighbours in the row.
+__global__ void td_flux_fill_condition_kernel(const bf16_t* mom, const bf16_t* eps, const void* mask, int mfmt, int H, int W, float scaling,
+                                              float shift, int C, bf16_t* out) {
+  const int h = H >> 3, w = W >> 3, lat_chunks = C >> 1, chunks = lat_chunks + 32;
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (h >> 1) * (w >> 1) * chunks) return;
+  const int tok = idx / chunks, ch = idx - tok * chunks;
+  float v[8];
+  if (ch < lat_chunks) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = latent_value(mom, eps, nullptr, 0.f, scaling, shift, C, h, w, tok, ch * 8 + i);
+  } else {
+    const int k = ch - lat_chunks, py = k >> 2, px = 2 * (k & 3);
+    const int Y = tok / (w >> 1), X = tok - Y * (w >> 1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {      // i = (px & 1) * 4 + dy * 2 + dx
+      const size_t pix = (size_t)(8 * (2 * Y + ((i >> 1) & 1)) + py) * W + 8 * (2 * X + (i & 1)) + px + (i >> 2);
+      const bool on = mfmt == TD_INPAINT_MASK_U8_HW ? ((const unsigned char*)mask)[pix] >= 128 : ((const float*)mask)[pix] >= 0.5f;
+      v[i] = on ? 1.0f : 0.0f;
+    }
+  }
+  *(u32x4_t*)(out + (size_t)tok * (4 * C + 256) + ch * 8) =
+      u32x4_t{pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])};
 }
 
 int conv3_s2(hipStream_t s, const bf16_t* x, const bf16_t* w, const bf16_t* b, bf16_t* y, int Hout, int Wout, int cin, int cout) {
@@ -120,6 +172,26 @@ int td_conv3x3_s2_nhwc_bf16(const void* x, const void* w, const void* bias, void
 
 int td_vae_image_to_nhwc_bf16(const void* image, int image_format, int H, int W, void* out, int Cpad, void* stream) {
   return image_in_launch(image, image_format, H, W, (bf16_t*)out, Cpad, (hipStream_t)stream);
+}
+
+int td_vae_image_to_nhwc_masked_bf16(const void* image, int image_format, const void* mask, int mask_format, int H, int W, void* out, int Cpad,
+                                     void* stream) {
+  TD_CHECK_ARG(mask, "td_vae_image_to_nhwc_masked: null mask");
+  return image_in_launch(image, image_format, H, W, (bf16_t*)out, Cpad, (hipStream_t)stream, mask, mask_format);
+}
+
+int td_flux_fill_condition(const void* moments, const void* eps, const void* mask, int mask_format, int H, int W, float scaling_factor,
+                           float shift_factor, int C, void* cond_out, void* stream) {
+  TD_CHECK_ARG(moments && mask && cond_out, "td_flux_fill_condition: null argument (moments, mask and cond_out are required)");
+  TD_CHECK_ARG(mask_format == TD_INPAINT_MASK_U8_HW || mask_format == TD_INPAINT_MASK_F32_HW, "td_flux_fill_condition: unknown mask format %d", mask_format);
+  TD_CHECK_ARG(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "td_flux_fill_condition: H=%d, W=%d must be positive multiples of 16", H, W);
+  TD_CHECK_ARG(C > 0 && C % 2 == 0, "td_flux_fill_condition: C=%d must be a positive multiple of 2 (4C columns in 8-column chunks)", C);
+  TD_CHECK_ARG(((uintptr_t)cond_out) % 16 == 0, "td_flux_fill_condition: cond_out must be 16-byte aligned");
+  TD_GRID_1D_I32(nblk, (long long)(H / 16) * (W / 16) * (C / 2 + 32), 256, "td_flux_fill_condition");
+  hipLaunchKernelGGL(td_flux_fill_condition_kernel, dim3(nblk), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)moments, (const bf16_t*)eps,
+                     mask, mask_format, H, W, scaling_factor, shift_factor, C, (bf16_t*)cond_out);
+  TD_CHECK_LAUNCH();
+  return TD_OK;
 }
 
 int td_vae_latents_from_moments(const void* moments, const void* eps, const void* noise, float sigma, float scaling_factor,
@@ -252,7 +324,23 @@ int td_vae_enc_output_shape(const td_vae_enc* f, int H, int W, int* h, int* w, i
   return TD_OK;
 }
 
+static int vae_encode(td_vae_enc* f, const void* image, int image_format, const void* mask, int mask_format, int H, int W, void* moments_nhwc,
+                      void* stream);
+
 int td_vae_encode(td_vae_enc* f, const void* image, int image_format, int H, int W, void* moments_nhwc, void* stream) {
+  return vae_encode(f, image, image_format, nullptr, 0, H, W, moments_nhwc, stream);
+}
+
+int td_vae_encode_masked(td_vae_enc* f, const void* image, int image_format, const void* mask, int mask_format, int H, int W,
+                         void* moments_nhwc, void* stream) {
+  TD_CHECK_ARG(mask, "td_vae_encode_masked: null mask");
+  TD_CHECK_ARG(mask_format == TD_INPAINT_MASK_U8_HW || mask_format == TD_INPAINT_MASK_F32_HW, "td_vae_encode_masked: unknown mask format %d", mask_format);
+  return vae_encode(f, image, image_format, mask, mask_format, H, W, moments_nhwc, stream);
+}
+
+// mask == NULL: td_vae_encode; else td_vae_encode_masked (only the image-in stage differs)
+static int vae_encode(td_vae_enc* f, const void* image, int image_format, const void* mask, int mask_format, int H, int W, void* moments_nhwc,
+                      void* stream) {
   TD_CHECK_ARG(f && image && moments_nhwc, "td_vae_encode: null argument");
   TD_CHECK_ARG(image_format == TD_IMAGE_U8_HWC || image_format == TD_IMAGE_F32_CHW, "td_vae_encode: unknown image format %d", image_format);
   TD_CHECK_ARG(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "td_vae_encode: image %dx%d: height and width must be positive multiples of 16", H, W);
@@ -263,7 +351,7 @@ int td_vae_encode(td_vae_enc* f, const void* image, int image_format, int H, int
   TD_CHECK_ARG(((uintptr_t)moments_nhwc) % 16 == 0, "td_vae_encode: moments must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
 
-  TDV_TRY(image_in_launch(image, image_format, H, W, f->T1, f->in_pad, s));
+  TDV_TRY(image_in_launch(image, image_format, H, W, f->T1, f->in_pad, s, mask, mask_format));
   TDV_TRY(conv3(s, f->T1, f->cin_w, f->cin_b, nullptr, f->X, H, W, f->in_pad, f->cfg.block_out_channels[0], 0));
   // ---- down blocks ----------------------------------------------------------------------------------------
   for (int b = 0; b < nb; ++b) {

@@ -223,6 +223,21 @@ void check_latents(td_flux* f, const at::Tensor& x, const char* name) {
   TORCH_CHECK(si > 0 && n > 0, "thinkdiff_hip: the FLUX context has no condition / timesteps prepared");
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous() && x.size(0) == si && x.size(1) == c, "thinkdiff_hip: ", name, " must be contiguous [", si, ", ", c, "] bf16, got ", x.sizes());
 }
+// the channel condition of a conditioned engine (FLUX.1 Fill / Canny / Depth): cond [S_img, in_channels - out_channels] bf16, copied beside
+// the latents' columns of this context's x_embedder operand (td_flux_set_channel_condition)
+void flux_set_channel_condition(int64_t engine, const at::Tensor& cond) {
+  td_flux* f = flux_of(engine);
+  int si = 0, cin = 0, cc = 0;
+  ok(td_flux_prepared_shape(f, &si, nullptr, nullptr, nullptr));
+  ok(td_flux_input_shape(f, &cin, &cc, nullptr));
+  TORCH_CHECK(cc > 0, "thinkdiff_hip::flux_set_channel_condition: this engine takes no channel condition (x_embedder reads the ", cin, " latent channels only)");
+  TORCH_CHECK(si > 0, "thinkdiff_hip::flux_set_channel_condition: the FLUX context has no condition prepared (set_condition fixes the token count)");
+  check_rows(cond, "cond");
+  TORCH_CHECK(cond.dim() == 2 && cond.is_contiguous() && cond.size(0) == si && cond.size(1) == cc,
+              "thinkdiff_hip::flux_set_channel_condition: cond must be contiguous [", si, ", ", cc, "] bf16, got ", cond.sizes());
+  DeviceGuard guard(cond.device());
+  ok(td_flux_set_channel_condition(f, cond.data_ptr(), stream_of(cond)));
+}
 // velocity = FluxTransformer2DModel.forward(latents) at prepared step `step`
 at::Tensor& flux_forward_(int64_t engine, const at::Tensor& latents, int64_t step, at::Tensor& velocity) {
   td_flux* f = flux_of(engine);
@@ -256,7 +271,7 @@ void flux_denoise_multi_(at::ArrayRef<int64_t> engines, at::TensorList latents, 
   ok(td_flux_denoise_multi(fs.data(), ls.data(), (int)fs.size(), sg.data(), (int)sg.size() - 1, ss.data()));
 }
 // FluxInpaintPipeline's loop in place: flux_denoise_ with the inpainting step (flux_inpaint_step_) after every forward; image_latents, noise
-// and mask are [S_img, in_channels] like the latents and must not overlap them
+// and mask are [S_img, out_channels] like the latents and must not overlap them
 at::Tensor& flux_denoise_inpaint_(int64_t engine, at::Tensor& latents, at::ArrayRef<double> sigmas, const at::Tensor& image_latents,
                                   const at::Tensor& noise, const at::Tensor& mask) {
   td_flux* f = flux_of(engine);
@@ -321,6 +336,50 @@ at::Tensor vae_encode_moments(int64_t engine, const at::Tensor& image, int64_t H
   ok(td_vae_encode((td_vae_enc*)(uintptr_t)engine, image.data_ptr(), u8 ? TD_IMAGE_U8_HWC : TD_IMAGE_F32_CHW, (int)H, (int)W, mom.data_ptr(), stream_of(image)));
   return mom;
 }
+// a [H, W] mask for the FLUX.1 Fill kernels: uint8 or float32, contiguous, on `like`'s device; returns its TD_INPAINT_MASK_* format
+int fill_mask_format(const at::Tensor& mask, const at::Tensor& like, int64_t H, int64_t W, const char* op) {
+  TORCH_CHECK(mask.is_cuda() && mask.is_contiguous() && mask.dim() == 2 && mask.size(0) == H && mask.size(1) == W,
+              "thinkdiff_hip::", op, ": mask must be a contiguous GPU tensor [H = ", H, ", W = ", W, "], got ", mask.sizes());
+  same_device(mask, "mask", like);
+  const bool u8 = mask.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || mask.scalar_type() == at::kFloat, "thinkdiff_hip::", op, ": mask must be uint8 or float32, got ", mask.scalar_type());
+  return u8 ? TD_INPAINT_MASK_U8_HW : TD_INPAINT_MASK_F32_HW;
+}
+// vae_encode_moments of image * (1 - binarize(mask)) (FLUX.1 Fill's masked image): mask uint8 or float32 [H, W] at full resolution
+at::Tensor vae_encode_moments_masked(int64_t engine, const at::Tensor& image, const at::Tensor& mask, int64_t H, int64_t W) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null VAE encoder handle");
+  TORCH_CHECK(image.is_cuda() && image.is_contiguous(), "thinkdiff_hip::vae_encode_moments_masked: image must be a contiguous GPU tensor");
+  const bool u8 = image.scalar_type() == at::kByte;
+  TORCH_CHECK(u8 || image.scalar_type() == at::kFloat, "thinkdiff_hip::vae_encode_moments_masked: image must be uint8 [H, W, 3] or float32 [3, H, W], got ", image.scalar_type());
+  TORCH_CHECK(u8 ? image.sizes() == at::IntArrayRef({H, W, 3}) : image.sizes() == at::IntArrayRef({3, H, W}),
+              "thinkdiff_hip::vae_encode_moments_masked: image must be ", u8 ? "uint8 [H, W, 3]" : "float32 [3, H, W]", " with H = ", H, ", W = ", W, ", got ", image.sizes());
+  const int mfmt = fill_mask_format(mask, image, H, W, "vae_encode_moments_masked");
+  int h = 0, w = 0, mc = 0;
+  ok(td_vae_enc_output_shape((const td_vae_enc*)(uintptr_t)engine, (int)H, (int)W, &h, &w, &mc));
+  DeviceGuard guard(image.device());
+  at::Tensor mom = at::empty({(int64_t)h * w, mc}, image.options().dtype(at::kBFloat16));
+  ok(td_vae_encode_masked((td_vae_enc*)(uintptr_t)engine, image.data_ptr(), u8 ? TD_IMAGE_U8_HWC : TD_IMAGE_F32_CHW, mask.data_ptr(), mfmt, (int)H, (int)W,
+                          mom.data_ptr(), stream_of(image)));
+  return mom;
+}
+// FLUX.1 Fill's channel condition of one image: packed (sample(moments, eps) - shift) * scaling | the unshuffled binarized mask ->
+// [(H/16)(W/16), 4C + 256] bf16 (td_flux_fill_condition); moments [(H/8)(W/8), 2C] of the masked image
+at::Tensor flux_fill_condition(const at::Tensor& moments, const c10::optional<at::Tensor>& eps, const at::Tensor& mask, double scaling_factor,
+                               double shift_factor, int64_t H, int64_t W) {
+  check_rows(moments, "moments");
+  TORCH_CHECK(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "thinkdiff_hip::flux_fill_condition: H, W must be positive multiples of 16, got ", H, " x ", W);
+  const int64_t h = H / 8, w = W / 8;
+  TORCH_CHECK(moments.dim() == 2 && moments.is_contiguous() && moments.size(0) == h * w && moments.size(1) % 4 == 0 && moments.size(1) > 0,
+              "thinkdiff_hip::flux_fill_condition: moments must be contiguous [(H/8)(W/8) = ", h * w, ", 2C] bf16 with C even, got ", moments.sizes());
+  const int64_t C = moments.size(1) / 2;
+  check_vec(eps, "eps", moments, C * h * w);
+  const int mfmt = fill_mask_format(mask, moments, H, W, "flux_fill_condition");
+  DeviceGuard guard(moments.device());
+  at::Tensor out = at::empty({(h / 2) * (w / 2), 4 * C + 256}, moments.options());
+  ok(td_flux_fill_condition(moments.data_ptr(), P(eps), mask.data_ptr(), mfmt, (int)H, (int)W, (float)scaling_factor, (float)shift_factor, (int)C,
+                            out.data_ptr(), stream_of(moments)));
+  return out;
+}
 // posterior sample / mode + shift / scale + scale_noise + _pack_latents: moments [h*w, 2C] -> packed latents [(h/2)(w/2), 4C]
 at::Tensor vae_latents_from_moments(const at::Tensor& moments, const c10::optional<at::Tensor>& eps, const c10::optional<at::Tensor>& noise, double sigma,
                                     double scaling_factor, double shift_factor, int64_t h, int64_t w) {
@@ -373,6 +432,9 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_inpaint_step_(Tensor(a!) x, Tensor v, Tensor image_latents, Tensor? noise, Tensor mask, float dt, float sigma_next) -> Tensor(a!)");
   m.def("flux_inpaint_mask(Tensor mask, int C) -> Tensor");
   m.def("flux_denoise_inpaint_(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)");
+  m.def("flux_set_channel_condition(int engine, Tensor cond) -> ()");
+  m.def("vae_encode_moments_masked(int engine, Tensor image, Tensor mask, int H, int W) -> Tensor");
+  m.def("flux_fill_condition(Tensor moments, Tensor? eps, Tensor mask, float scaling_factor, float shift_factor, int H, int W) -> Tensor");
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
 }
 
@@ -398,4 +460,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_inpaint_mask", &flux_inpaint_mask);
   m.impl("flux_denoise_inpaint_", &flux_denoise_inpaint_);
   m.impl("flux_denoise_multi_inpaint_", &flux_denoise_multi_inpaint_);
+  m.impl("flux_set_channel_condition", &flux_set_channel_condition);
+  m.impl("vae_encode_moments_masked", &vae_encode_moments_masked);
+  m.impl("flux_fill_condition", &flux_fill_condition);
 }

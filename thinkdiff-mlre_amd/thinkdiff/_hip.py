@@ -66,6 +66,11 @@ def _declare(L):
         "td_flux_set_smoothing": [vp, i32],
         "td_flux_set_attention": [vp, i32],
         "td_flux_prepared_shape": [vp, vp, vp, vp, vp],
+        "td_flux_input_shape": [vp, vp, vp, vp],
+        "td_flux_set_channel_condition": [vp, vp, vp],
+        "td_flux_fill_condition": [vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp],
+        "td_vae_encode_masked": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
+        "td_vae_image_to_nhwc_masked_bf16": [vp, i32, vp, i32, i32, i32, vp, i32, vp],
         "td_vae_output_shape": [vp, i32, i32, vp, vp, vp],
         "td_flux_fork": [vp, vp],
         "td_flux_denoise_multi": [vp, vp, i32, vp, i32, vp],
@@ -289,7 +294,7 @@ class TdFluxConfig(ctypes.Structure):
     _fields_ = [("in_channels", ctypes.c_int), ("num_layers", ctypes.c_int), ("num_single_layers", ctypes.c_int),
                 ("num_heads", ctypes.c_int), ("head_dim", ctypes.c_int), ("joint_dim", ctypes.c_int),
                 ("pooled_dim", ctypes.c_int), ("guidance_embeds", ctypes.c_int), ("mlp_ratio", ctypes.c_int),
-                ("axes_dims", ctypes.c_int * 3), ("rope_theta", ctypes.c_float)]
+                ("axes_dims", ctypes.c_int * 3), ("rope_theta", ctypes.c_float), ("out_channels", ctypes.c_int)]
 
 
 def norm_rows(x, out=None, rms=False, eps=1e-6, w=None, split=0, shiftA=None, scaleA=None, shiftB=None, scaleB=None):
@@ -419,12 +424,22 @@ def conv3x3_s2_nhwc(x, w_packed, bias, Hin, Win, Cout):
 IMAGE_U8_HWC, IMAGE_F32_CHW = 0, 1      # TD_IMAGE_* (include/thinkdiff_hip.h)
 
 
-def vae_image_to_nhwc(image, Cpad=64):
-    """VaeImageProcessor.preprocess + .to(bf16): uint8 [H, W, 3] or float32 [3, H, W] in [0,1] -> bf16 [H*W, Cpad] (channels >= 3 zero)"""
+MASK_U8_HW, MASK_F32_HW = 0, 1          # TD_INPAINT_MASK_* (include/thinkdiff_hip.h)
+
+
+def vae_image_to_nhwc(image, Cpad=64, mask=None):
+    """VaeImageProcessor.preprocess + .to(bf16): uint8 [H, W, 3] or float32 [3, H, W] in [0,1] -> bf16 [H*W, Cpad] (channels >= 3 zero).
+    mask (uint8 or float32 [H, W]): FLUX.1 Fill's masked image, image * (1 - binarize(mask)) in fp32 before the cast."""
     u8 = image.dtype == torch.uint8
     H, W = (image.shape[0], image.shape[1]) if u8 else (image.shape[1], image.shape[2])
     out = torch.empty(H * W, Cpad, dtype=torch.bfloat16, device=image.device)
-    check(lib().td_vae_image_to_nhwc_bf16(ptr(image.contiguous()), IMAGE_U8_HWC if u8 else IMAGE_F32_CHW, H, W, ptr(out), Cpad, stream_ptr()))
+    fmt = IMAGE_U8_HWC if u8 else IMAGE_F32_CHW
+    if mask is None:
+        check(lib().td_vae_image_to_nhwc_bf16(ptr(image.contiguous()), fmt, H, W, ptr(out), Cpad, stream_ptr()))
+    else:
+        assert mask.shape == (H, W) and mask.dtype in (torch.uint8, torch.float32) and mask.is_contiguous()
+        mfmt = MASK_U8_HW if mask.dtype == torch.uint8 else MASK_F32_HW
+        check(lib().td_vae_image_to_nhwc_masked_bf16(ptr(image.contiguous()), fmt, ptr(mask), mfmt, H, W, ptr(out), Cpad, stream_ptr()))
     return out
 
 

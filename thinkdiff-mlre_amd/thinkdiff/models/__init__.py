@@ -2,6 +2,8 @@
 from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import BlipVisionT5DecoderForConditionalGeneration, build_vision_projector
+from .flux_control import FluxControlPipelineRewritePrompt
+from .flux_fill import FluxFillPipelineRewritePrompt
 from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
 from .flux_inpaint import FluxInpaintPipelineRewritePrompt
 from .flux_prompt import FluxPipelineRewritePrompt
@@ -12,4 +14,5 @@ from .qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
 
 __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration", "build_vision_projector",
            "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
+           "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt",
            "FluxTransformer2DModel", "FluxTransformerConfig"]

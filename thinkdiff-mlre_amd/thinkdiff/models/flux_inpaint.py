@@ -29,9 +29,9 @@ num_images_per_prompt, latents h = H/8, w = W/8, C = 16, S = (H/16)(W/16); H and
       x' = bf16(bf16(bf16(1 - m) * p) + bf16(m * a))
 - Output: `_finish` as in the other pipelines; no overlay (that needs `padding_mask_crop`).
 
-Refused, not approximated: `padding_mask_crop` (crop region, resize_mode="fill", apply_overlay), FLUX.1 Fill (the 384-channel
-transformer that reads the masked-image latents), resizing tensor masks, `callback_on_step_end`, custom `sigmas` and lists of
-generators.
+Refused, not approximated: `padding_mask_crop` (crop region, resize_mode="fill", apply_overlay), resizing tensor masks,
+`callback_on_step_end`, custom `sigmas` and lists of generators.  FLUX.1 Fill (the 384-channel transformer that reads the
+masked-image latents) is a pipeline of its own: `FluxFillPipelineRewritePrompt` (flux_fill.py).
 """
 from typing import List, Optional
 

@@ -42,6 +42,12 @@ class FlowMatchEulerSchedule:
         return np.concatenate([s.astype(np.float32), np.zeros(1, dtype=np.float32)])
 
 
+def latent_channels(config) -> int:
+    """Width of the packed latents of a transformer config: `out_channels` where the config has one (channel-conditioned checkpoints read
+    more than they write), else `in_channels`."""
+    return int(getattr(config, "out_channels", None) or config.in_channels)
+
+
 class FluxPipelineRewritePrompt:
     vae_scale_factor = 16          # [ext] FluxPipeline.__init__ (0.31.0): 2 ** len(vae.block_out_channels)
     vae_scaling_factor = 0.3611    # [ext] FLUX.1-dev vae/config.json
@@ -158,7 +164,7 @@ class FluxPipelineRewritePrompt:
     def prepare_latents(self, batch: int, height: int, width: int, generator=None, latents=None):
         """Returns packed latents [B, (h/2)(w/2), 64] bf16 and the latent (h, w).  `latents`, if given, is
         already packed (as in diffusers)."""
-        c = self.transformer.config.in_channels // 4
+        c = latent_channels(self.transformer.config) // 4
         h = 2 * (int(height) // self.vae_scale_factor)
         w = 2 * (int(width) // self.vae_scale_factor)
         dev = self._execution_device
@@ -198,11 +204,12 @@ class FluxPipelineRewritePrompt:
         return self._finish(xs, h, w, output_type, return_dict)
 
     def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff,
-                        inpaint=None):
+                        inpaint=None, channel_cond=None):
         """The denoise loop over `sig` (any sigma list ending in 0: the full schedule or a truncated one) for the first B packed latents
         of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents.
         inpaint: None, or per sample b an (image_latents, noise, mask) triple of [S, 64] tensors made on the current stream (the
-        inpainting loop, FluxTransformer2DModel.denoise)."""
+        inpainting loop, FluxTransformer2DModel.denoise).  channel_cond: None, or per sample b the [S, in_channels - out_channels] condition
+        of a channel-conditioned transformer, set on the context that carries sample b next to its prompt (FLUX.1 Fill / Control)."""
         tr = self.transformer
         n_prompts = prompt_embeds.shape[0]
         # `images_in_flight` independent images advance together, each on its own stream and engine context (shared
@@ -220,6 +227,8 @@ class FluxPipelineRewritePrompt:
                 st.wait_stream(main)
                 with torch.cuda.stream(st):
                     ctxs[k].set_condition(prompt_embeds[pb], pooled_prompt_embeds[min(pb, pooled_prompt_embeds.shape[0] - 1)], img_ids, text_ids)
+                    if channel_cond is not None:
+                        ctxs[k].set_channel_condition(channel_cond[b])
                     ctxs[k].set_timesteps(t_eff, g_eff)
                     lat_g.append(lat[b].contiguous())
             blend_g = None if inpaint is None else [inpaint[b] for b in group]
@@ -241,7 +250,7 @@ class FluxPipelineRewritePrompt:
             if output_type == "latent":      # diffusers: packed latents, no unpack
                 outs.append(x)
             elif output_type == "vae_input":  # _unpack_latents + (z / scaling_factor + shift_factor), no decode
-                outs.append(_OPS.flux_unpack_latents(x, tr.config.in_channels // 4, h, w,
+                outs.append(_OPS.flux_unpack_latents(x, latent_channels(tr.config) // 4, h, w,
                                                      self.vae_scaling_factor, self.vae_shift_factor))
             elif self.vae is None:
                 raise _hip.ThinkDiffHipError("no VAE loaded: call with output_type='latent' (packed latents) or "

@@ -34,10 +34,29 @@ class FluxTransformerConfig:
     pooled_projection_dim: int = 768
     guidance_embeds: bool = True
     axes_dims_rope: Sequence[int] = (16, 56, 56)
+    # [ext] diffusers >= 0.32: null / absent = in_channels.  FLUX.1 Fill (in 384, out 64) and FLUX.1 Canny / Depth (in 128, out 64) read a
+    # per-image condition of in_channels - out_channels columns concatenated to the latents (FluxTransformer2DModel.set_channel_condition).
+    out_channels: Optional[int] = None
 
     @property
     def inner_dim(self):
         return self.attention_head_dim * self.num_attention_heads
+
+    @property
+    def latent_channels(self) -> int:
+        """Width of the packed latents and of the velocity (proj_out's)."""
+        return self.out_channels or self.in_channels
+
+    @property
+    def cond_channels(self) -> int:
+        """Width of the channel condition x_embedder reads beside the latents (0: an unconditioned model)."""
+        return self.in_channels - self.latent_channels
+
+    def to_hip(self) -> "_hip.TdFluxConfig":
+        """The engine's `struct TdFluxConfig` (out_channels None -> 0, the struct's spelling of "= in_channels")."""
+        return _hip.TdFluxConfig(self.in_channels, self.num_layers, self.num_single_layers, self.num_attention_heads,
+                                 self.attention_head_dim, self.joint_attention_dim, self.pooled_projection_dim,
+                                 int(self.guidance_embeds), 4, (ctypes.c_int * 3)(*self.axes_dims_rope), 10000.0, int(self.out_channels or 0))
 
 
 def effective_scalar(value: float, dtype: torch.dtype) -> float:
@@ -59,9 +78,7 @@ class FluxTransformer2DModel:
         if self.device.type != "cuda":
             raise _hip.ThinkDiffHipError("FluxTransformer2DModel runs on the MI355X HIP engine only (device='cuda')")
         self._L = _hip.lib()
-        cc = _hip.TdFluxConfig(c.in_channels, c.num_layers, c.num_single_layers, c.num_attention_heads,
-                               c.attention_head_dim, c.joint_attention_dim, c.pooled_projection_dim,
-                               int(c.guidance_embeds), 4, (ctypes.c_int * 3)(*c.axes_dims_rope), 10000.0)
+        cc = c.to_hip()
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _hip.check(self._L.td_flux_create(ctypes.byref(cc), max_img_tokens, max_txt_tokens, max_steps, ctypes.byref(h)))
@@ -125,6 +142,12 @@ class FluxTransformer2DModel:
             torch.cuda.current_stream().synchronize()  # `d` may be a temporary
         return missing, unexpected
 
+    @staticmethod
+    def config_from_json(raw: dict) -> FluxTransformerConfig:
+        """transformer/config.json -> FluxTransformerConfig: known keys only; `out_channels` absent or null = in_channels."""
+        fields = {f.name for f in dataclasses.fields(FluxTransformerConfig)}
+        return FluxTransformerConfig(**{k: v for k, v in raw.items() if k in fields})
+
     @classmethod
     def from_pretrained(cls, path: str, subfolder: str = "transformer", **kw):
         """Local directories only (there is no hub access): <path>/<subfolder>/{config.json,*.safetensors}."""
@@ -132,8 +155,7 @@ class FluxTransformer2DModel:
         root = os.path.join(path, subfolder) if os.path.isdir(os.path.join(path, subfolder)) else path
         with open(os.path.join(root, "config.json")) as fh:
             raw = json.load(fh)
-        fields = {f.name for f in dataclasses.fields(FluxTransformerConfig)}
-        model = cls(FluxTransformerConfig(**{k: v for k, v in raw.items() if k in fields}), **kw)
+        model = cls(cls.config_from_json(raw), **kw)
         seen = set()
         for fn in sorted(glob.glob(os.path.join(root, "*.safetensors"))):
             with safe_open(fn, framework="pt") as fh:
@@ -188,22 +210,34 @@ class FluxTransformer2DModel:
         self._n_img = ii.shape[0]
         torch.cuda.current_stream().synchronize()
 
+    def set_channel_condition(self, cond):
+        """The per-image condition of a channel-conditioned model, cond [S_img, in_channels - out_channels] bf16 (FLUX.1 Fill: packed
+        masked-image latents | unshuffled mask; FLUX.1 Canny / Depth: the packed control-image latents): what diffusers concatenates to
+        the latents in front of every transformer call.  After set_condition, once per image; this context's own (forks hold theirs)."""
+        c = self.config
+        if c.cond_channels == 0:
+            raise _hip.ThinkDiffHipError(f"this transformer takes no channel condition (in_channels = out_channels = {c.in_channels})")
+        assert cond.dim() == 2 and cond.shape[1] == c.cond_channels, f"cond must be [S_img, {c.cond_channels}], got {tuple(cond.shape)}"
+        d = cond.to(self.device, torch.bfloat16).contiguous()
+        _OPS.flux_set_channel_condition(int(self._h.value), d)
+        torch.cuda.current_stream().synchronize()      # `d` may be a temporary
+
     def set_timesteps(self, t_eff: Sequence[float], g_eff: float = 0.0):
         arr = (ctypes.c_float * len(t_eff))(*[float(t) for t in t_eff])
         _hip.check(self._L.td_flux_set_timesteps(self._h, ctypes.cast(arr, ctypes.c_void_p), len(t_eff), float(g_eff), _hip.stream_ptr()))
         self._n_steps = len(t_eff)
 
     def forward_step(self, latents, step: int, out=None):
-        assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.in_channels)
+        assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.latent_channels)
         if out is None:
             out = torch.empty_like(latents)
         return _OPS.flux_forward_(int(self._h.value), latents, int(step), out)
 
     def denoise(self, latents, sigmas: Sequence[float], inpaint=None):
         """In-place Euler flow-matching loop over the prepared timesteps (len(sigmas) == n_steps + 1).  inpaint: an (image_latents,
-        noise, mask) triple of [S_img, in_channels] bf16 tensors -- FluxInpaintPipeline's loop: after every step the latents are blended
+        noise, mask) triple of [S_img, out_channels] bf16 tensors -- FluxInpaintPipeline's loop: after every step the latents are blended
         with the image latents re-noised to the next sigma under the mask (flux_inpaint_step_)."""
-        assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.in_channels)
+        assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.latent_channels)
         if inpaint is None:
             return _OPS.flux_denoise_(int(self._h.value), latents, [float(s) for s in sigmas])
         z, noise, mask = inpaint
@@ -226,11 +260,19 @@ class FluxTransformer2DModel:
     # ---- diffusers-style call -------------------------------------------------------------------------
     def forward(self, hidden_states, encoder_hidden_states, pooled_projections, timestep, img_ids, txt_ids=None,
                 guidance=None, return_dict: bool = False, **_ignored):
-        """[ext] FluxTransformer2DModel.forward semantics; batch is looped (conditions differ per sample)."""
+        """[ext] FluxTransformer2DModel.forward semantics; batch is looped (conditions differ per sample).  A channel-conditioned model
+        takes what diffusers passes it, hidden_states [B, S, in_channels] = cat(latents, condition), and splits it itself."""
         B = hidden_states.shape[0]
         outs = []
+        c_lat, c_cond = self.config.latent_channels, self.config.cond_channels
+        if hidden_states.shape[-1] != self.config.in_channels:
+            raise ValueError(f"hidden_states has {hidden_states.shape[-1]} channels, the transformer's in_channels is {self.config.in_channels}")
+        cond_all = hidden_states[..., c_lat:] if c_cond else None
+        hidden_states = hidden_states[..., :c_lat]
         for b in range(B):
             self.set_condition(encoder_hidden_states[b], pooled_projections[b], img_ids, txt_ids)
+            if c_cond:
+                self.set_channel_condition(cond_all[b])
             t = float(timestep[b] if timestep.dim() else timestep)
             g = float(guidance[b] if guidance.dim() else guidance) if guidance is not None else 0.0
             # timestep arrives as t/1000 in the latents dtype; the transformer multiplies by 1000 in that dtype

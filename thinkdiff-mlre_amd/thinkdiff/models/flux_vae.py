@@ -6,7 +6,7 @@ import glob
 import json
 import os
 from types import SimpleNamespace
-from typing import Dict, Sequence
+from typing import Dict, Optional, Sequence
 
 import torch
 
@@ -186,16 +186,20 @@ class AutoencoderKLEncoder:
         return self
 
     @torch.no_grad()
-    def encode_moments(self, image: torch.Tensor) -> torch.Tensor:
+    def encode_moments(self, image: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One image -> the posterior's parameters [h*w, 2C] bf16 (NHWC rows: mean | logvar), h = H / 8 for the FLUX.1 VAE.
         image: uint8 [H, W, 3] (PIL layout, 0..255) or float [3, H, W] in [0, 1]; `VaeImageProcessor.preprocess`'s 2x - 1 and the
-        bf16 cast happen on the GPU.  H, W: multiples of 16 within the capacity given at construction."""
+        bf16 cast happen on the GPU.  H, W: multiples of 16 within the capacity given at construction.
+        mask (uint8 or float32 [H, W]): encode FLUX.1 Fill's masked image instead, image * (1 - binarize(mask)) taken in fp32 before the
+        bf16 cast, inside the same image-in kernel (td_vae_encode_masked)."""
         if image.dtype == torch.uint8:
             H, W = int(image.shape[0]), int(image.shape[1])
         else:
             image = image.float()
             H, W = int(image.shape[1]), int(image.shape[2])
         x = image.to(self.device).contiguous()
+        if mask is not None:
+            return _OPS.vae_encode_moments_masked(int(self._h.value), x, mask.to(self.device).contiguous(), H, W)
         h, w, mc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _hip.check(self._L.td_vae_enc_output_shape(self._h, H, W, ctypes.byref(h), ctypes.byref(w), ctypes.byref(mc)))
         mom = torch.empty(h.value * w.value, mc.value, dtype=torch.bfloat16, device=self.device)
