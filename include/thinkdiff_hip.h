@@ -169,6 +169,12 @@ int td_euler_step_bf16(void* x, const void* v, float dt, int64_t n, void* stream
  * All operands bf16 [n], 16-byte aligned; n % 8 == 0; noise may be NULL (the loop's last step). */
 int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents, const void* noise, const void* mask, float dt,
                               float sigma_next, int64_t n, void* stream);
+/* FluxKontextPipeline's step under true classifier-free guidance, fused, in place on x ([ext] diffusers >= 0.34 pipeline_flux_kontext.py
+ *   `noise_pred = neg_noise_pred + true_cfg_scale * (noise_pred - neg_noise_pred)`, then scheduler.step), every op a bf16 torch op;
+ * `scale` is a Python float there, which eager torch keeps in fp32 as the operand of the bf16 multiply (it is not rounded to bf16 first):
+ *   d = bf16(v_pos - v_neg);  m = bf16(scale * float(d));  v = bf16(v_neg + m);  x = bf16(float(x) + float(bf16(bf16(dt) * float(v))))
+ * All operands bf16 [n], 16-byte aligned, n % 8 == 0, v_pos / v_neg not overlapping x. */
+int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream);
 #define TD_INPAINT_MASK_U8_HW 0   /* uint8 [H, W] (PIL mode "L") */
 #define TD_INPAINT_MASK_F32_HW 1  /* float32 [H, W] in [0, 1] */
 /* FluxInpaintPipeline's mask latents from a height x width mask (format TD_INPAINT_MASK_*):
@@ -236,6 +242,7 @@ typedef struct TdFluxConfig {
                            * Both multiples of 64.  Last field: a caller that zero-fills the struct keeps the unconditioned model. */
 } TdFluxConfig;
 
+/* max_img_tokens bounds the IMAGE STREAM of a forward: the latents' tokens plus the reference tokens of td_flux_set_reference_tokens, if any. */
 int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_tokens, int max_steps, td_flux** out);
 void td_flux_destroy(td_flux* f);
 int64_t td_flux_param_elems(const td_flux* f);
@@ -286,7 +293,8 @@ enum { TD_FP8_QKV = 1, TD_FP8_OUT = 2, TD_FP8_FF1 = 4, TD_FP8_FF2 = 8,      /* d
 int td_flux_set_fp8_gemms(td_flux* f, unsigned mask);
 int td_flux_init_random(td_flux* f, uint64_t seed, float std, void* stream);
 /* per prompt: prompt_embeds bf16 [T,joint_dim], pooled bf16 [pooled_dim], ids fp32 device [n,3]
- * (txt_ids NULL = zeros, thinkdiff/models/flux_prompt.py:119) */
+ * (txt_ids NULL = zeros, thinkdiff/models/flux_prompt.py:119).  Always voids the context's reference tokens (it rebuilds the RoPE table for
+ * T + S_img rows): set them again after it, for every image; a forward without them is the plain model. */
 int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const void* pooled, const float* txt_ids,
                           const float* img_ids, int S_img, void* stream);
 /* per schedule: t_eff (host, n floats) / g_eff = the values fed to the sinusoids (timestep*1000,
@@ -308,6 +316,17 @@ int td_flux_input_shape(const td_flux* f, int* in_channels, int* cond_channels, 
  * a run on zeros); on an unconditioned engine the call itself is TD_ERR_INVALID.  Forgets the 8-bit modes' per-token history like
  * td_flux_set_condition (another image). */
 int td_flux_set_channel_condition(td_flux* f, const void* cond, void* stream);
+/* FLUX.1 Kontext's reference tokens of one image: ref_latents bf16 [S_ref, out_channels] (packed, already shifted / scaled, 16-byte aligned),
+ * ref_ids device fp32 [S_ref, 3].  After td_flux_set_condition, once per image, this context's own (forks hold theirs).  From then on every
+ * forward of the context runs its blocks over [text | latents | reference] -- T + S_img + S_ref rows, the reference rows with the RoPE
+ * of ref_ids -- while the final AdaLayerNorm, proj_out, the velocity and every step kernel keep the S_img latent rows.  Replaces, in
+ * [ext] diffusers >= 0.34 FluxKontextPipeline.__call__, `latent_model_input = torch.cat([latents, image_latents], dim=1)`,
+ * `latent_ids = torch.cat([latent_ids, image_ids], dim=0)` and `noise_pred = noise_pred[:, : latents.size(1)]` of every step.
+ * S_ref == 0 (null pointers allowed) clears.  TD_ERR_INVALID: no condition set; S_img + S_ref > max_img_tokens; a channel-conditioned
+ * engine; misaligned pointers.  Forgets the 8-bit modes' per-token history like td_flux_set_condition (another image). */
+int td_flux_set_reference_tokens(td_flux* f, const void* ref_latents, int S_ref, const float* ref_ids, void* stream);
+/* The reference tokens this context holds (0: none, or no condition set). */
+int td_flux_reference_tokens(const td_flux* f, int* S_ref);
 /* velocity[S_img,out_channels] = transformer(latents[S_img,out_channels]; prepared step).  On a conditioned engine the latents are gathered
  * beside the channel condition and x_embedder runs as ONE Linear over in_channels, as on torch.cat([latents, cond]). */
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream);
@@ -319,6 +338,12 @@ int td_flux_trace_begin(td_flux* f, int max_launches);
 int td_flux_trace_end(td_flux* f, void* stream, int64_t* counts, double* ms, double* flops);
 /* n Euler steps in place; sigmas: n+1 host floats */
 int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void* stream);
+/* FluxKontextPipeline's loop under true classifier-free guidance ([ext] diffusers >= 0.34 pipeline_flux_kontext.py, `do_true_cfg`): n steps
+ * in place, each the transformer on `pos` and on `neg` (two prepared contexts -- in practice a context and its fork: shared weights, own
+ * conditioning, own 8-bit history), then td_flux_cfg_step_bf16 with dt = sigmas[i+1] - sigmas[i].  ONE stream.  Reference tokens, if any, are
+ * set on both contexts by the caller.  TD_ERR_INVALID: contexts whose S_img, S_ref, out_channels or prepared step count differ; pos == neg;
+ * latents overlapping either context's velocity buffer. */
+int td_flux_denoise_cfg(td_flux* pos, td_flux* neg, void* latents, const float* sigmas, int n, float scale, void* stream);
 /* FluxInpaintPipeline's loop: n steps in place, each the transformer then td_flux_inpaint_step_bf16 with
  *   dt = sigmas[i+1] - sigmas[i],  sigma_next = sigmas[i+1],  noise used for i < n-1 (the last step blends the clean image_latents).
  * image_latents (the packed clean latents z), noise (the packed start noise) and mask (td_flux_inpaint_mask's output): bf16
@@ -400,8 +425,9 @@ int td_vae_param_info(const td_vae* f, int idx, char* name_buf, int buf_len, int
 int td_vae_load_param(td_vae* f, const char* name, const void* src, int64_t count, void* stream);
 /* seeded synthetic decoder; std <= 0: 1 / sqrt(fan_in) weights (images with contrast), else that std for every weight and bias */
 int td_vae_init_random(td_vae* f, uint64_t seed, float std, void* stream);
-/* packed latents bf16 [(h/2)(w/2), 4*latent_channels] (h, w = latent size, h*w % 64 == 0) -> image_u8 [8h,8w,3]
- * uint8 and/or image_chw bf16 [3,8h,8w] (= vae.decode output); either may be NULL. */
+/* packed latents bf16 [(h/2)(w/2), 4*latent_channels] (h, w = latent size, both even, within the capacity) -> image_u8 [8h,8w,3]
+ * uint8 and/or image_chw bf16 [3,8h,8w] (= vae.decode output); either may be NULL.  The mid-block attention pads its key axis to the next
+ * multiple of 64 with exact zeros, so any even h, w is served; with h*w % 64 == 0 there is no pad. */
 int td_vae_decode(td_vae* f, const void* packed_latents, int h, int w, float scaling_factor, float shift_factor,
                   void* image_u8, void* image_chw, void* stream);
 /* The image size td_vae_decode writes for an h x w latent (2x per block but the last: 8h x 8w for the FLUX.1 VAE) and the channel count of
@@ -425,8 +451,9 @@ int td_vae_enc_load_param(td_vae_enc* f, const char* name, const void* src, int6
 int td_vae_enc_init_random(td_vae_enc* f, uint64_t seed, float std, void* stream);
 /* `VaeImageProcessor.preprocess(image).to(bf16)` + `vae.encode(x)` up to the posterior's parameters ([ext] autoencoder_kl.py
  * AutoencoderKL._encode): image (device; format TD_IMAGE_*) -> moments_nhwc bf16 [(H/8)(W/8), 2 x latent_channels] = mean | logvar
- * per latent pixel (H/2^(num_blocks-1) for other depths).  H, W multiples of 16 within the capacity, the mid block's pixel count
- * a multiple of 64; refused before any launch otherwise.  No allocation. */
+ * per latent pixel (H/2^(num_blocks-1) for other depths).  H, W multiples of 16 within the capacity; refused before any launch
+ * otherwise.  (The mid-block attention pads its key axis to the next multiple of 64 with exact zeros: any such size is served, and a mid-block
+ * pixel count that is a multiple of 64 runs unpadded.)  No allocation. */
 int td_vae_encode(td_vae_enc* f, const void* image, int image_format, int H, int W, void* moments_nhwc, void* stream);
 /* td_vae_encode of `masked_image = image * (1 - mask)` ([ext] diffusers >= 0.32 FluxFillPipeline.__call__; the product is taken in fp32
  * on the preprocessed image and rounded to bf16 by prepare_mask_latents' `.to(dtype)`): the image-in kernel writes bf16(2x - 1) where the
@@ -457,7 +484,11 @@ int td_groupnorm_nhwc_bf16(const void* x, void* y, int P, int C, int groups, flo
                            const void* beta, int silu, float* workspace, void* stream);
 int td_groupnorm_workspace_floats(void);
 /* p[rows,cols] (bf16) = softmax(scale * s[rows,cols]) (fp32 in). */
+/* (s 16-byte, p 8-byte aligned, neither NULL: the kernel's vector accesses need it; refused with TD_ERR_INVALID otherwise) */
 int td_softmax_rows_f32_bf16(const float* s, void* p, int rows, int cols, float scale, void* stream);
+/* ... with rows `ld` elements apart in both matrices (ld >= cols, ld % 4 == 0): softmax over the first `cols` columns of each row, the pad
+ * columns [cols, ld) of s never read and those of p written as exact zeros (the VAE mid-block attention's key-axis pad). */
+int td_softmax_rows_strided_f32_bf16(const float* s, void* p, int rows, int cols, int ld, float scale, void* stream);
 
 /* ---- Qwen2-VL text decoder: hidden states at `model.norm` + KV-cached decoding -------------------------
  * Replaces the vLLM fork's model runner behind `self.mllama.generate(inputs, sampling_params)` with

@@ -192,6 +192,9 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
   return td_flux_inpaint_step_launch((bf16_t*)x, (const bf16_t*)v, (const bf16_t*)image_latents, (const bf16_t*)noise, (const bf16_t*)mask, dt,
                                      sigma_next, n, (hipStream_t)stream);
 }
+int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream) {
+  return td_flux_cfg_step_launch((bf16_t*)x, (const bf16_t*)v_pos, (const bf16_t*)v_neg, scale, dt, n, (hipStream_t)stream);
+}
 int td_flux_inpaint_mask(const void* mask, int format, int H, int W, int C, void* packed_out, void* stream) {
   return td_flux_inpaint_mask_launch(mask, format, H, W, C, (bf16_t*)packed_out, (hipStream_t)stream);
 }
@@ -243,7 +246,10 @@ int td_groupnorm_nhwc_bf16(const void* x, void* y, int P, int C, int groups, flo
 }
 int td_groupnorm_workspace_floats(void) { return 1024 * 64 * 2 + 256; }
 int td_softmax_rows_f32_bf16(const float* s, void* p, int rows, int cols, float scale, void* stream) {
-  return td_softmax_rows_launch(s, (bf16_t*)p, rows, cols, scale, (hipStream_t)stream);
+  return td_softmax_rows_launch(s, (bf16_t*)p, rows, cols, cols, scale, (hipStream_t)stream);
+}
+int td_softmax_rows_strided_f32_bf16(const float* s, void* p, int rows, int cols, int ld, float scale, void* stream) {
+  return td_softmax_rows_launch(s, (bf16_t*)p, rows, cols, ld, scale, (hipStream_t)stream);
 }
 
 int td_layernorm_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows, int D, int rms, float eps,

@@ -345,6 +345,39 @@ __global__ void td_euler_step_kernel(bf16_t* x, const bf16_t* v, float dt, int n
   ((u32x4_t*)x)[idx] = pack8(a);
 }
 
+// FluxKontextPipeline's loop body with true classifier-free guidance [ext diffusers >= 0.34 pipeline_flux_kontext.py]:
+//   noise_pred = neg_noise_pred + true_cfg_scale * (noise_pred - neg_noise_pred);  latents = scheduler.step(noise_pred, t, latents)
+// on bf16 tensors with `true_cfg_scale` a Python float.  Eager torch keeps a Python scalar as an fp32 operand of the bf16 op (it is NOT
+// rounded to bf16 first: with s = 3.7 the two forms differ in 16 % of the products), and rounds the result of each of the three ops:
+//   d = bf16(p - n);  m = bf16(s * float(d));  v = bf16(n + m);  x = euler(x, v, dt)
+// Three bf16 streams in, one out, 16 B per lane; in place on x.
+__global__ void td_flux_cfg_step_kernel(bf16_t* x, const bf16_t* vp, const bf16_t* vn, float scale, float dt, int n8) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n8) return;
+  float a[8], p[8], q[8];
+  unpack8(((const u32x4_t*)x)[idx], a);
+  unpack8(((const u32x4_t*)vp)[idx], p);
+  unpack8(((const u32x4_t*)vn)[idx], q);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) p[i] = rbf(q[i] + rbf(scale * rbf(p[i] - q[i])));
+  euler8(a, p, dt);
+  ((u32x4_t*)x)[idx] = pack8(a);
+}
+
+int td_flux_cfg_step_launch(bf16_t* x, const bf16_t* v_pos, const bf16_t* v_neg, float scale, float dt, long long n, hipStream_t stream) {
+  TD_CHECK_ARG(x && v_pos && v_neg, "td_flux_cfg_step: null argument");
+  TD_CHECK_ARG(n > 0 && n % 8 == 0, "td_flux_cfg_step: n=%lld must be a positive multiple of 8", n);
+  TD_CHECK_ARG(((uintptr_t)x | (uintptr_t)v_pos | (uintptr_t)v_neg) % 16 == 0, "td_flux_cfg_step: every buffer must be 16-byte aligned");
+  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + (uintptr_t)n * sizeof(bf16_t);
+  for (const bf16_t* o : {v_pos, v_neg})
+    TD_CHECK_ARG((uintptr_t)o >= x1 || (uintptr_t)o + (uintptr_t)n * sizeof(bf16_t) <= x0,
+                 "td_flux_cfg_step: v_pos and v_neg must not overlap x (updated in place)");
+  TD_GRID_1D_I32(nblk, n / 8, 256, "td_flux_cfg_step");
+  hipLaunchKernelGGL(td_flux_cfg_step_kernel, dim3(nblk), dim3(256), 0, stream, x, v_pos, v_neg, scale, dt, (int)(n / 8));
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
 // FluxInpaintPipeline's loop body after the transformer [ext pipeline_flux_inpaint.py]: the scheduler step, then
 //   init_latents_proper = scale_noise(image_latents, [t_next], noise)   (the last step: image_latents itself)
 //   latents = (1 - init_mask) * init_latents_proper + init_mask * latents

@@ -141,6 +141,12 @@ struct td_flux {
   int Cin = 0, Cout = 0, Ccond = 0;
   bf16_t* xin = nullptr;
   bool ccond_set = false;
+  // reference tokens (FLUX.1 Kontext): S_ref rows that join the image stream behind the S_img latent rows in every forward, constant over the
+  // schedule, never stepped or returned.  xref [max_img, Cout] is the per-context operand of x_embedder while S_ref > 0: rows S_img ..
+  // S_img + S_ref are written once per image (td_flux_set_reference_tokens), the head rows take the caller's latents by one device-to-device
+  // copy per forward.  The blocks then run over T + S_img + S_ref rows; the final norm, proj_out, the velocity and every step kernel keep S_img.
+  int S_ref = 0;
+  bf16_t* xref = nullptr;
   // optional per-launch HIP-event trace (bench.py roofline leg)
   bool tracing = false;
   std::vector<hipEvent_t> ev_pool;
@@ -321,6 +327,7 @@ int alloc_workspace(td_flux* f) {
       {(void**)&f->attn, S * D * 2}, {(void**)&f->mlp, S * M * 2}, {(void**)&f->cat, S * (D + M) * 2},
       {(void**)&f->ctx, (int64_t)max_txt_tokens * D * 2}, {(void**)&f->vout, (int64_t)max_img_tokens * f->Cout * 2},
       {(void**)&f->xin, f->Ccond > 0 ? (int64_t)max_img_tokens * f->Cin * 2 : 0},
+      {(void**)&f->xref, f->Ccond == 0 ? (int64_t)max_img_tokens * f->Cout * 2 : 0},
       {(void**)&f->tproj, n * 256 * 2}, {(void**)&f->tmid, n * D * 2}, {(void**)&f->te, n * D * 2},
       {(void**)&f->gproj, 256 * 2}, {(void**)&f->gmid, (int64_t)D * 2}, {(void**)&f->ge, (int64_t)D * 2},
       {(void**)&f->pmid, (int64_t)D * 2}, {(void**)&f->pe, (int64_t)D * 2},
@@ -499,7 +506,7 @@ int td_flux_fork(td_flux* src, td_flux** out) {
   f->parent = root;
   f->ws = nullptr;
   f->ev_pool.clear(); f->trace.clear(); f->tracing = false;
-  f->T = f->S_img = f->n_steps = 0; f->cond_set = false; f->ccond_set = false;
+  f->T = f->S_img = f->n_steps = 0; f->cond_set = false; f->ccond_set = false; f->S_ref = 0;
   if (int rc = alloc_workspace(f)) { delete f; return rc; }
   *out = f;
   return TD_OK;
@@ -877,6 +884,7 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
   const int D = f->D;
   if (S_img != f->S_img) f->ccond_set = false;      // the channel condition was written for another token count
   f->T = T; f->S_img = S_img;
+  f->S_ref = 0;      // the tables below hold T + S_img rows: reference tokens are set again after the condition, for every image
   TD_TRY(gemm(f, s, (const bf16_t*)prompt_embeds, f->cfg.joint_dim, f->ctx_w, f->ctx_b, f->ctx, D, T, D, f->cfg.joint_dim));
   TD_TRY(gemm(f, s, (const bf16_t*)pooled, f->cfg.pooled_dim, f->p1_w, f->p1_b, f->pmid, D, 1, D, f->cfg.pooled_dim, TD_ACT_SILU));
   TD_TRY(gemm(f, s, f->pmid, D, f->p2_w, f->p2_b, f->pe, D, 1, D, D));
@@ -900,6 +908,40 @@ int td_flux_set_channel_condition(td_flux* f, const void* cond, void* stream) {
   TD_TRY(td_copy_cols_launch((const bf16_t*)cond, f->Ccond, f->xin + f->Cout, f->Cin, f->S_img, f->Ccond, (hipStream_t)stream));
   f->ccond_set = true;
   f->hs_step = f->href_step = -1;      // another image, as in td_flux_set_condition: the previous one's per-token history says nothing about it
+  return TD_OK;
+}
+
+// The reference tokens of one image (FLUX.1 Kontext): [ext] diffusers >= 0.34 FluxKontextPipeline.__call__
+//   latent_model_input = torch.cat([latents, image_latents], dim=1);  latent_ids = torch.cat([latent_ids, image_ids], dim=0)
+// ref_latents [S_ref, Cout] -> xref rows S_img ..; ref_ids [S_ref, 3] -> rows T + S_img .. of the id / RoPE tables (td_flux_rope_table's arithmetic).
+int td_flux_set_reference_tokens(td_flux* f, const void* ref_latents, int S_ref, const float* ref_ids, void* stream) {
+  TD_CHECK_ARG(f, "td_flux_set_reference_tokens: null context");
+  TD_CHECK_ARG(S_ref >= 0, "td_flux_set_reference_tokens: S_ref=%d is negative", S_ref);
+  TD_CHECK_ARG(f->Ccond == 0, "td_flux_set_reference_tokens: this engine is channel-conditioned (in_channels=%d, out_channels=%d); reference tokens "
+               "belong to the unconditioned FLUX.1 Kontext transformer", f->Cin, f->Cout);
+  TD_CHECK_ARG(f->cond_set, "td_flux_set_reference_tokens: call td_flux_set_condition first (it fixes the text and image token counts; S_ref=%d)", S_ref);
+  if (S_ref == 0) {
+    f->S_ref = 0;
+    f->hs_step = f->href_step = -1;
+    return TD_OK;
+  }
+  TD_CHECK_ARG(ref_latents && ref_ids, "td_flux_set_reference_tokens: null ref_latents / ref_ids with S_ref=%d", S_ref);
+  TD_CHECK_ARG((long long)f->S_img + S_ref <= f->max_img, "td_flux_set_reference_tokens: S_img=%d + S_ref=%d exceed the image-stream capacity %d "
+               "(max_img_tokens of td_flux_create)", f->S_img, S_ref, f->max_img);
+  TD_CHECK_ARG((uintptr_t)ref_latents % 16 == 0 && (uintptr_t)ref_ids % 4 == 0, "td_flux_set_reference_tokens: ref_latents must be 16-byte, ref_ids 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t row0 = (size_t)f->T + f->S_img;
+  TD_CHECK_HIP(hipMemcpyAsync(f->xref + (size_t)f->S_img * f->Cout, ref_latents, (size_t)S_ref * f->Cout * 2, hipMemcpyDeviceToDevice, s));
+  TD_CHECK_HIP(hipMemcpyAsync(f->ids + row0 * 3, ref_ids, (size_t)S_ref * 12, hipMemcpyDeviceToDevice, s));
+  TD_TRY(td_flux_rope_table_launch(f->ids + row0 * 3, S_ref, f->cfg.axes_dims, (double)f->cfg.rope_theta, f->cosT + row0 * 128, f->sinT + row0 * 128, s));
+  f->S_ref = S_ref;
+  f->hs_step = f->href_step = -1;      // another image, as in td_flux_set_condition: the previous one's per-token history says nothing about it
+  return TD_OK;
+}
+
+int td_flux_reference_tokens(const td_flux* f, int* S_ref) {
+  TD_CHECK_ARG(f && S_ref, "td_flux_reference_tokens: null argument");
+  *S_ref = f->cond_set ? f->S_ref : 0;
   return TD_OK;
 }
 
@@ -968,7 +1010,8 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
   TD_CHECK_ARG(f->Ccond == 0 || f->ccond_set, "td_flux_forward: this engine reads a %d-channel condition beside the %d latent channels and none is set for "
                "the %d image tokens (td_flux_set_channel_condition after td_flux_set_condition)", f->Ccond, f->Cout, f->S_img);
   hipStream_t s = (hipStream_t)stream;
-  const int D = f->D, M = f->M, T = f->T, S = f->T + f->S_img, Si = f->S_img;
+  // Si: rows of the image stream the blocks run over (latents, then the reference tokens if any); So: the rows that are a velocity
+  const int D = f->D, M = f->M, T = f->T, So = f->S_img, Si = f->S_img + f->S_ref, S = f->T + Si;
   const int H = f->cfg.num_heads, C = f->Cout;
   const int L = f->cfg.num_layers, Ls = f->cfg.num_single_layers;
   const bf16_t* mod = f->mods + (size_t)step * f->NMOD;
@@ -981,6 +1024,9 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
     TD_CHECK_ARG((uintptr_t)latents % 16 == 0, "td_flux_forward: latents must be 16-byte aligned");
     TD_TRY(td_copy_cols_launch((const bf16_t*)latents, C, f->xin, f->Cin, Si, C, s));
     TD_TRY(gemm(f, s, f->xin, f->Cin, f->x_w, f->x_b, h_img, D, Si, D, f->Cin));
+  } else if (f->S_ref > 0) {      // Linear(cat([latents, ref], dim=0)): the latents join the reference rows in xref, then ONE GEMM over all rows
+    TD_CHECK_HIP(hipMemcpyAsync(f->xref, latents, (size_t)So * C * 2, hipMemcpyDeviceToDevice, s));
+    TD_TRY(gemm(f, s, f->xref, C, f->x_w, f->x_b, h_img, D, Si, D, C));
   } else {
     TD_TRY(gemm(f, s, (const bf16_t*)latents, C, f->x_w, f->x_b, h_img, D, Si, D, C));
   }
@@ -1181,15 +1227,15 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
     }
   }
 
-  // AdaLayerNormContinuous: chunk order (scale, shift); image rows only
+  // AdaLayerNormContinuous: chunk order (scale, shift); the latents' image rows only (reference tokens have no velocity)
   const bf16_t* mf = mod + (size_t)L * 12 * D + (size_t)Ls * 3 * D;
   TdNormParams nf = np;
   nf.q = nullptr;   // the final projection stays bf16
   nf.smoothA = nf.smoothB = nullptr; nf.extA = nf.extB = nullptr; nf.ext_n = 0;
-  nf.x = h_img; nf.y = f->xn; nf.rows = Si; nf.split = 0;
+  nf.x = h_img; nf.y = f->xn; nf.rows = So; nf.split = 0;
   nf.scaleA = nf.scaleB = mf; nf.shiftA = nf.shiftB = mf + D;
   TD_TRY(norm_rows(f, s, nf));
-  TD_TRY(gemm(f, s, f->xn, D, f->proj_w, f->proj_b, (bf16_t*)velocity, C, Si, C, D));
+  TD_TRY(gemm(f, s, f->xn, D, f->proj_w, f->proj_b, (bf16_t*)velocity, C, So, C, D));
   if (calib) TD_TRY(finish_smoothing(wroot, s));      // (synchronises s; bumps the history epoch)
   if (hist_mode) { f->hs_step = step; f->hs_T = T; f->hs_S = S; f->hs_epoch = root->hist_epoch; } else f->hs_step = -1;
   if (href_on) { f->href_cur ^= 1; f->href_step = step; f->href_T = T; f->href_S = S; f->href_epoch = root->hist_epoch; } else f->href_step = -1;
@@ -1304,6 +1350,29 @@ int td_flux_denoise(td_flux* f, void* latents, const float* sigmas, int n, void*
   TD_CHECK_ARG(f && latents && sigmas, "td_flux_denoise: null argument");
   TD_CHECK_ARG(n > 0 && n <= f->n_steps, "td_flux_denoise: n=%d exceeds the %d prepared timesteps", n, f->n_steps);
   return denoise_loop(f, latents, sigmas, n, nullptr, stream);
+}
+
+// FluxKontextPipeline's loop with true classifier-free guidance: per step the transformer under the positive and under the negative
+// conditioning (two contexts, ONE stream), then td_flux_cfg_step_bf16.
+int td_flux_denoise_cfg(td_flux* pos, td_flux* neg, void* latents, const float* sigmas, int n, float scale, void* stream) {
+  TD_CHECK_ARG(pos && neg && latents && sigmas, "td_flux_denoise_cfg: null argument");
+  TD_CHECK_ARG(pos != neg, "td_flux_denoise_cfg: the positive and the negative context are the same object (fork one from the other)");
+  TD_CHECK_ARG(pos->cond_set && neg->cond_set, "td_flux_denoise_cfg: both contexts need td_flux_set_condition");
+  TD_CHECK_ARG(pos->S_img == neg->S_img && pos->Cout == neg->Cout, "td_flux_denoise_cfg: the contexts disagree on the latents: S_img %d / %d, out_channels %d / %d",
+               pos->S_img, neg->S_img, pos->Cout, neg->Cout);
+  TD_CHECK_ARG(pos->S_ref == neg->S_ref, "td_flux_denoise_cfg: the contexts hold %d / %d reference tokens (set the image's reference tokens on both, or on neither)",
+               pos->S_ref, neg->S_ref);
+  TD_CHECK_ARG(pos->n_steps == neg->n_steps, "td_flux_denoise_cfg: the contexts are prepared for %d / %d timesteps", pos->n_steps, neg->n_steps);
+  TD_CHECK_ARG(n > 0 && n <= pos->n_steps, "td_flux_denoise_cfg: n=%d exceeds the %d prepared timesteps", n, pos->n_steps);
+  const long long count = (long long)pos->S_img * pos->Cout;
+  TD_CHECK_ARG(!overlaps(latents, (size_t)count * 2, pos->vout, (size_t)count * 2) && !overlaps(latents, (size_t)count * 2, neg->vout, (size_t)count * 2),
+               "td_flux_denoise_cfg: latents overlap a context's velocity buffer");
+  for (int i = 0; i < n; ++i) {
+    TD_TRY(td_flux_forward(pos, latents, i, pos->vout, stream));
+    TD_TRY(td_flux_forward(neg, latents, i, neg->vout, stream));
+    TD_TRY(td_flux_cfg_step_launch((bf16_t*)latents, pos->vout, neg->vout, scale, sigmas[i + 1] - sigmas[i], count, (hipStream_t)stream));
+  }
+  return TD_OK;
 }
 
 int td_flux_denoise_inpaint(td_flux* f, void* latents, const float* sigmas, int n, const void* image_latents, const void* noise,

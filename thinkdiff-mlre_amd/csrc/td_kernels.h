@@ -204,6 +204,7 @@ int td_flux_rope_table_launch(const float* ids, int S, const int* axes, double t
 int td_timestep_sincos_launch(const float* t, int n, bf16_t* out, hipStream_t stream);
 int td_temb_combine_silu_launch(const bf16_t* te, const bf16_t* ge, const bf16_t* pe, int n, int D, bf16_t* temb, bf16_t* silu_out, hipStream_t stream);
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream);
+int td_flux_cfg_step_launch(bf16_t* x, const bf16_t* v_pos, const bf16_t* v_neg, float scale, float dt, long long n, hipStream_t stream);
 int td_copy_cols_launch(const bf16_t* src, int lds, bf16_t* dst, int ldd, int rows, int cols, hipStream_t stream);
 int td_flux_inpaint_step_launch(bf16_t* x, const bf16_t* v, const bf16_t* z, const bf16_t* noise, const bf16_t* mask, float dt,
                                 float sigma_next, long long n, hipStream_t stream);
@@ -218,7 +219,7 @@ int td_mrope_table_launch(const int* pos, int n, const int* sections, float thet
 // VAE decoder kernels (vae_kernels.hip); groupnorm workspace: 1024*64*2 + 256 floats
 int td_groupnorm_nhwc_launch(const bf16_t* x, bf16_t* y, int P, int C, int G, float eps, const bf16_t* gamma, const bf16_t* beta,
                              int silu, float* workspace, hipStream_t stream);
-int td_softmax_rows_launch(const float* s, bf16_t* p, int rows, int cols, float scale, hipStream_t stream);
+int td_softmax_rows_launch(const float* s, bf16_t* p, int rows, int cols, int ld, float scale, hipStream_t stream);   // ld: row stride of s and p (>= cols)
 int td_conv_pack_launch(const bf16_t* w, bf16_t* out, int Cout, int Cin, int Cout_pad, int Cin_pad, hipStream_t stream);
 int td_latents_to_nhwc_launch(const bf16_t* packed, bf16_t* out, int C, int h, int w, int Cpad, float div, float add, hipStream_t stream);
 int td_image_finalize_launch(const bf16_t* x, int P, int Cpad, unsigned char* u8, bf16_t* chw, hipStream_t stream);

@@ -117,21 +117,31 @@ int resnet(F* f, hipStream_t s, const Resnet& r, int H, int W) {
 // x (in X, [P0, c]) -> X + to_out(attention(gn(x))), using T1, T2, Q, K, VT, S, P.  ONE head of width c: scores are produced in fp32
 // row chunks of f->chunk_rows by the GEMM (fp32 output), softmaxed by a row kernel and multiplied with V^T by the GEMM again; to_v's
 // bias is added after the product (softmax rows sum to 1).
+// The P . V^T product contracts over the keys and the GEMM's K must be a multiple of 64: the KEY axis of S / P / V^T is padded to
+// Pk = pad64(P0).  The pad rows of gn(x) are zeroed in every call (T1 is a scratch buffer other stages write), so V^T's pad columns are exact
+// zeros (to_v runs without its bias here): that is the memset correctness rests on.  K's pad rows are zeroed only to keep uninitialised memory
+// out of the score GEMM -- the score columns they produce are never read; the softmax normalises over the P0 real columns and writes
+// zeros into P's pad columns, and 0 x 0 adds nothing to the fp32 accumulator.  With P0 % 64 == 0 there is no pad: the launches, their extents and every bit are those of the unpadded form.
 template <class F>
 int mid_attention(F* f, hipStream_t s, const MidAttn& a, int P0, int c) {
+  const int Pk = pad64(P0);
   TDV_TRY(gn(f, s, f->X, f->T1, P0, c, a.gn_w, a.gn_b, 0));
+  if (Pk != P0) {
+    TD_CHECK_HIP(hipMemsetAsync(f->T1 + (size_t)P0 * c, 0, (size_t)(Pk - P0) * c * sizeof(bf16_t), s));
+    TD_CHECK_HIP(hipMemsetAsync(f->K + (size_t)P0 * c, 0, (size_t)(Pk - P0) * c * sizeof(bf16_t), s));
+  }
   TDV_TRY(lin(s, f->T1, c, a.q_w, a.q_b, f->Q, c, P0, c, c));
   TDV_TRY(lin(s, f->T1, c, a.k_w, a.k_b, f->K, c, P0, c, c));
-  TDV_TRY(lin(s, a.v_w, c, f->T1, nullptr, f->VT, P0, c, P0, c));      // V^T [c, P0] = Wv . xn^T (bias added after PV)
+  TDV_TRY(lin(s, a.v_w, c, f->T1, nullptr, f->VT, Pk, c, Pk, c));      // V^T [c, Pk] = Wv . xn^T (bias added after PV)
   const float scale = 1.0f / sqrtf((float)c);
   for (int r0 = 0; r0 < P0; r0 += f->chunk_rows) {
     const int rows = std::min(f->chunk_rows, P0 - r0);
     TdGemmParams g;   // scores (fp32) = Q_chunk . K^T
-    g.A = f->Q + (size_t)r0 * c; g.lda = c; g.W = f->K; g.C = (bf16_t*)f->S; g.ldc = P0; g.M = rows; g.N = P0; g.K = c; g.out_f32 = 1;
-    g.cfg = P0 <= 64 ? 1 : (rows <= 32 ? 2 : 0);
+    g.A = f->Q + (size_t)r0 * c; g.lda = c; g.W = f->K; g.C = (bf16_t*)f->S; g.ldc = Pk; g.M = rows; g.N = Pk; g.K = c; g.out_f32 = 1;
+    g.cfg = Pk <= 64 ? 1 : (rows <= 32 ? 2 : 0);
     TDV_TRY(td_gemm_launch(g, s));
-    TDV_TRY(td_softmax_rows_launch(f->S, f->P, rows, P0, scale, s));
-    TDV_TRY(lin(s, f->P, P0, f->VT, a.v_b, f->T2 + (size_t)r0 * c, c, rows, c, P0));   // + b_v: softmax rows sum to 1
+    TDV_TRY(td_softmax_rows_launch(f->S, f->P, rows, P0, Pk, scale, s));
+    TDV_TRY(lin(s, f->P, Pk, f->VT, a.v_b, f->T2 + (size_t)r0 * c, c, rows, c, Pk));   // + b_v: softmax rows sum to 1
   }
   TDV_TRY(lin(s, f->T2, c, a.o_w, a.o_b, f->X, c, P0, c, c, f->X));   // to_out + residual
   return 0;

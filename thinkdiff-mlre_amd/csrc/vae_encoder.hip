@@ -274,12 +274,14 @@ int td_vae_enc_create(const TdVaeConfig* cfg, int max_image_h, int max_image_w, 
     prev = co;
   }
   const int64_t pm = px;   // mid-block pixels at capacity
+  const int64_t pk = (pm + 63) & ~int64_t(63);   // ... and its key axis, padded to the GEMM's k-tile (mid_attention)
+  maxX = std::max(maxX, pk * cmid);              // T1 carries the pad rows of gn(x)
   f->chunk_rows = (int)std::min<int64_t>(2048, pm);
   struct Req { void** p; int64_t bytes; };
   std::vector<Req> reqs = {
       {(void**)&f->X, maxX * 2}, {(void**)&f->T1, maxX * 2}, {(void**)&f->T2, maxT2 * 2}, {(void**)&f->T3, maxT2 * 2},
-      {(void**)&f->Q, pm * cmid * 2}, {(void**)&f->K, pm * cmid * 2}, {(void**)&f->VT, pm * cmid * 2},
-      {(void**)&f->S, (int64_t)f->chunk_rows * pm * 4}, {(void**)&f->P, (int64_t)f->chunk_rows * pm * 2},
+      {(void**)&f->Q, pm * cmid * 2}, {(void**)&f->K, pk * cmid * 2}, {(void**)&f->VT, pk * cmid * 2},
+      {(void**)&f->S, (int64_t)f->chunk_rows * pk * 4}, {(void**)&f->P, (int64_t)f->chunk_rows * pk * 2},
       {(void**)&f->gn, (int64_t)(1024 * 64 * 2 + 256) * 4},
   };
   int64_t total = 0;
@@ -346,8 +348,6 @@ static int vae_encode(td_vae_enc* f, const void* image, int image_format, const 
   TD_CHECK_ARG(H > 0 && W > 0 && H % 16 == 0 && W % 16 == 0, "td_vae_encode: image %dx%d: height and width must be positive multiples of 16", H, W);
   TD_CHECK_ARG((long long)H * W <= f->max_pixels, "td_vae_encode: image %dx%d exceeds the %d-pixel capacity given at create", H, W, f->max_pixels);
   const int nb = f->nb, cmid = f->cmid;
-  const int hm = H >> (nb - 1), wm = W >> (nb - 1);
-  TD_CHECK_ARG((hm * wm) % 64 == 0, "td_vae_encode: the mid block's pixel count %d (image %dx%d) must be a multiple of 64", hm * wm, H, W);
   TD_CHECK_ARG(((uintptr_t)moments_nhwc) % 16 == 0, "td_vae_encode: moments must be 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
 

@@ -114,13 +114,15 @@ int td_vae_create(const TdVaeConfig* cfg, int max_latent_h, int max_latent_w, td
     if (b != nb - 1) { px *= 4; maxX = std::max(maxX, px * co); }
     prev = co;
   }
+  const int64_t pk = ((int64_t)f->max_lat_pixels + 63) & ~int64_t(63);   // the mid-block attention's key axis, padded to the GEMM's k-tile
+  maxX = std::max(maxX, pk * cmid);                                      // T1 carries the pad rows of gn(x)
   f->chunk_rows = std::min(2048, f->max_lat_pixels);
   struct Req { void** p; int64_t bytes; };
   std::vector<Req> reqs = {
       {(void**)&f->X, maxX * 2}, {(void**)&f->T1, maxX * 2}, {(void**)&f->T2, maxT2 * 2}, {(void**)&f->T3, maxT2 * 2},
-      {(void**)&f->Q, (int64_t)f->max_lat_pixels * cmid * 2}, {(void**)&f->K, (int64_t)f->max_lat_pixels * cmid * 2},
-      {(void**)&f->VT, (int64_t)f->max_lat_pixels * cmid * 2},
-      {(void**)&f->S, (int64_t)f->chunk_rows * f->max_lat_pixels * 4}, {(void**)&f->P, (int64_t)f->chunk_rows * f->max_lat_pixels * 2},
+      {(void**)&f->Q, (int64_t)f->max_lat_pixels * cmid * 2}, {(void**)&f->K, pk * cmid * 2},
+      {(void**)&f->VT, pk * cmid * 2},
+      {(void**)&f->S, (int64_t)f->chunk_rows * pk * 4}, {(void**)&f->P, (int64_t)f->chunk_rows * pk * 2},
       {(void**)&f->gn, (int64_t)(1024 * 64 * 2 + 256) * 4},
   };
   int64_t total = 0;
@@ -172,7 +174,6 @@ int td_vae_output_shape(const td_vae* f, int h, int w, int* H, int* W, int* pack
 int td_vae_decode(td_vae* f, const void* packed_latents, int h, int w, float scaling_factor, float shift_factor,
                   void* image_u8, void* image_chw, void* stream) {
   TD_CHECK_ARG(f && packed_latents && (image_u8 || image_chw), "td_vae_decode: null argument");
-  TD_CHECK_ARG((h * w) % 64 == 0, "td_vae_decode: latent pixel count %d must be a multiple of 64", h * w);
   TD_CHECK_ARG(h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && h * w <= f->max_lat_pixels, "td_vae_decode: latent %dx%d exceeds the %d-pixel capacity", h, w, f->max_lat_pixels);
   hipStream_t s = (hipStream_t)stream;
   const int cmid = f->cmid, nb = f->nb;

@@ -128,11 +128,13 @@ int td_groupnorm_nhwc_launch(const bf16_t* x, bf16_t* y, int P, int C, int G, fl
   return 0;
 }
 
-// ---- fp32 row softmax -> bf16:  p[r, :] = softmax(scale * s[r, :]),  one workgroup per row ---------------
-__global__ __launch_bounds__(256) void td_softmax_rows_kernel(const float* s, bf16_t* p, int cols, float scale) {
+// ---- fp32 row softmax -> bf16:  p[r, :cols] = softmax(scale * s[r, :cols]),  one workgroup per row --------
+// Rows of both matrices lie `ld` elements apart; the pad columns [cols, ld) of s are never read and those of p are written as exact zeros
+// (the VAE mid-block attention pads its key axis to the GEMM's k-tile: a zero probability adds nothing to the P.V^T accumulator).
+__global__ __launch_bounds__(256) void td_softmax_rows_kernel(const float* s, bf16_t* p, int cols, int ld, float scale) {
   __shared__ float red[8];
-  const float* sr = s + (size_t)blockIdx.x * cols;
-  bf16_t* pr = p + (size_t)blockIdx.x * cols;
+  const float* sr = s + (size_t)blockIdx.x * ld;
+  bf16_t* pr = p + (size_t)blockIdx.x * ld;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float mx = -INFINITY;
   for (int c = threadIdx.x * 4; c < cols; c += 1024) {
@@ -162,12 +164,16 @@ __global__ __launch_bounds__(256) void td_softmax_rows_kernel(const float* s, bf
     o[1] = pack_bf2(__builtin_amdgcn_exp2f((v[2] - mx) * k) * inv, __builtin_amdgcn_exp2f((v[3] - mx) * k) * inv);
     *(u32x2_t*)(pr + c) = o;
   }
+  for (int c = cols + threadIdx.x * 4; c < ld; c += 1024) *(u32x2_t*)(pr + c) = u32x2_t{0u, 0u};
 }
 
-int td_softmax_rows_launch(const float* s, bf16_t* p, int rows, int cols, float scale, hipStream_t stream) {
+int td_softmax_rows_launch(const float* s, bf16_t* p, int rows, int cols, int ld, float scale, hipStream_t stream) {
+  TD_CHECK_ARG(s && p, "td_softmax_rows: null argument");
   TD_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0, "td_softmax_rows: cols=%d must be a positive multiple of 4", cols);
+  TD_CHECK_ARG(ld >= cols && ld % 4 == 0, "td_softmax_rows: row stride %d must be a multiple of 4 and at least cols=%d", ld, cols);
+  TD_CHECK_ARG((uintptr_t)s % 16 == 0 && (uintptr_t)p % 8 == 0, "td_softmax_rows: s must be 16-byte and p 8-byte aligned");
   TD_GRID_1D(nblk, (long long)rows * 256, 256, "td_softmax_rows");
-  hipLaunchKernelGGL(td_softmax_rows_kernel, dim3(nblk), dim3(256), 0, stream, s, p, cols, scale);
+  hipLaunchKernelGGL(td_softmax_rows_kernel, dim3(nblk), dim3(256), 0, stream, s, p, cols, ld, scale);
   TD_CHECK_LAUNCH();
   return 0;
 }

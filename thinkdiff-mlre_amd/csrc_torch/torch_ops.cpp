@@ -139,6 +139,17 @@ at::Tensor& euler_step_(at::Tensor& x, const at::Tensor& v, double dt) {
   return x;
 }
 
+// FluxKontextPipeline's step under true classifier-free guidance, in place: v = v_neg + scale * (v_pos - v_neg) as three bf16 torch ops with
+// the Python float `scale` kept in fp32, then the Euler step (td_flux_cfg_step_bf16)
+at::Tensor& flux_cfg_step_(at::Tensor& x, const at::Tensor& v_pos, const at::Tensor& v_neg, double scale, double dt) {
+  check_rows(x, "x");
+  TORCH_CHECK(x.is_contiguous(), "thinkdiff_hip::flux_cfg_step_: x must be contiguous");
+  check_vec(v_pos, "v_pos", x, x.numel()); check_vec(v_neg, "v_neg", x, x.numel());
+  DeviceGuard guard(x.device());
+  ok(td_flux_cfg_step_bf16(x.data_ptr(), v_pos.data_ptr(), v_neg.data_ptr(), (float)scale, (float)dt, x.numel(), stream_of(x)));
+  return x;
+}
+
 // FluxInpaintPipeline's step in place: Euler step, scale_noise of the image latents to bf16(sigma_next) (noise None: the clean latents) and
 // the mask blend, every op a bf16 torch op (td_flux_inpaint_step_bf16)
 at::Tensor& flux_inpaint_step_(at::Tensor& x, const at::Tensor& v, const at::Tensor& image_latents, const c10::optional<at::Tensor>& noise,
@@ -238,6 +249,22 @@ void flux_set_channel_condition(int64_t engine, const at::Tensor& cond) {
   DeviceGuard guard(cond.device());
   ok(td_flux_set_channel_condition(f, cond.data_ptr(), stream_of(cond)));
 }
+// FLUX.1 Kontext's reference tokens of one image: ref_latents [S_ref, out_channels] bf16, ref_ids [S_ref, 3] fp32; they join this context's
+// image stream behind the latents in every forward (td_flux_set_reference_tokens).  S_ref == 0 clears.
+void flux_set_reference_tokens(int64_t engine, const at::Tensor& ref_latents, const at::Tensor& ref_ids) {
+  td_flux* f = flux_of(engine);
+  int si = 0, c = 0;
+  ok(td_flux_prepared_shape(f, &si, nullptr, &c, nullptr));
+  TORCH_CHECK(si > 0, "thinkdiff_hip::flux_set_reference_tokens: the FLUX context has no condition prepared (set_condition fixes the token counts)");
+  check_rows(ref_latents, "ref_latents"); check_rows(ref_ids, "ref_ids", at::kFloat); same_device(ref_ids, "ref_ids", ref_latents);
+  TORCH_CHECK(ref_latents.dim() == 2 && ref_latents.is_contiguous() && ref_latents.size(1) == c,
+              "thinkdiff_hip::flux_set_reference_tokens: ref_latents must be contiguous [S_ref, ", c, "] bf16, got ", ref_latents.sizes());
+  const int64_t sr = ref_latents.size(0);
+  TORCH_CHECK(ref_ids.dim() == 2 && ref_ids.is_contiguous() && ref_ids.size(0) == sr && ref_ids.size(1) == 3,
+              "thinkdiff_hip::flux_set_reference_tokens: ref_ids must be contiguous [", sr, ", 3] fp32, got ", ref_ids.sizes());
+  DeviceGuard guard(ref_latents.device());
+  ok(td_flux_set_reference_tokens(f, sr ? ref_latents.data_ptr() : nullptr, (int)sr, sr ? (const float*)ref_ids.data_ptr() : nullptr, stream_of(ref_latents)));
+}
 // velocity = FluxTransformer2DModel.forward(latents) at prepared step `step`
 at::Tensor& flux_forward_(int64_t engine, const at::Tensor& latents, int64_t step, at::Tensor& velocity) {
   td_flux* f = flux_of(engine);
@@ -254,6 +281,17 @@ at::Tensor& flux_denoise_(int64_t engine, at::Tensor& latents, at::ArrayRef<doub
   std::vector<float> sg(sigmas.begin(), sigmas.end());
   DeviceGuard guard(latents.device());
   ok(td_flux_denoise(f, latents.data_ptr(), sg.data(), (int)sg.size() - 1, stream_of(latents)));
+  return latents;
+}
+// FluxKontextPipeline's loop under true classifier-free guidance, in place: per step the transformer on both contexts, then flux_cfg_step_
+at::Tensor& flux_denoise_cfg_(int64_t engine_pos, int64_t engine_neg, at::Tensor& latents, at::ArrayRef<double> sigmas, double scale) {
+  td_flux* fp = flux_of(engine_pos);
+  td_flux* fn = flux_of(engine_neg);
+  check_latents(fp, latents, "latents (positive context)"); check_latents(fn, latents, "latents (negative context)");
+  TORCH_CHECK(sigmas.size() >= 2, "thinkdiff_hip::flux_denoise_cfg_: sigmas needs n + 1 >= 2 entries");
+  std::vector<float> sg(sigmas.begin(), sigmas.end());
+  DeviceGuard guard(latents.device());
+  ok(td_flux_denoise_cfg(fp, fn, latents.data_ptr(), sg.data(), (int)sg.size() - 1, (float)scale, stream_of(latents)));
   return latents;
 }
 // the same for several prepared contexts (a parent and its forks) at once, context k on streams[k] (hipStream_t values)
@@ -433,6 +471,9 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_inpaint_mask(Tensor mask, int C) -> Tensor");
   m.def("flux_denoise_inpaint_(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)");
   m.def("flux_set_channel_condition(int engine, Tensor cond) -> ()");
+  m.def("flux_set_reference_tokens(int engine, Tensor ref_latents, Tensor ref_ids) -> ()");
+  m.def("flux_cfg_step_(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)");
+  m.def("flux_denoise_cfg_(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)");
   m.def("vae_encode_moments_masked(int engine, Tensor image, Tensor mask, int H, int W) -> Tensor");
   m.def("flux_fill_condition(Tensor moments, Tensor? eps, Tensor mask, float scaling_factor, float shift_factor, int H, int W) -> Tensor");
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
@@ -461,6 +502,9 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_denoise_inpaint_", &flux_denoise_inpaint_);
   m.impl("flux_denoise_multi_inpaint_", &flux_denoise_multi_inpaint_);
   m.impl("flux_set_channel_condition", &flux_set_channel_condition);
+  m.impl("flux_set_reference_tokens", &flux_set_reference_tokens);
+  m.impl("flux_cfg_step_", &flux_cfg_step_);
+  m.impl("flux_denoise_cfg_", &flux_denoise_cfg_);
   m.impl("vae_encode_moments_masked", &vae_encode_moments_masked);
   m.impl("flux_fill_condition", &flux_fill_condition);
 }

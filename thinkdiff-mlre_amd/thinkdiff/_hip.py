@@ -50,6 +50,7 @@ def _declare(L):
         "td_timestep_sincos": [vp, i32, vp, vp],
         "td_euler_step_bf16": [vp, vp, f32, i64, vp],
         "td_flux_inpaint_step_bf16": [vp, vp, vp, vp, vp, f32, f32, i64, vp],
+        "td_flux_cfg_step_bf16": [vp, vp, vp, f32, f32, i64, vp],
         "td_flux_inpaint_mask": [vp, i32, i32, i32, i32, vp, vp],
         "td_flux_pack_latents": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
         "td_cls_avgpool2_bf16": [vp, vp, i32, i32, vp],
@@ -68,6 +69,9 @@ def _declare(L):
         "td_flux_prepared_shape": [vp, vp, vp, vp, vp],
         "td_flux_input_shape": [vp, vp, vp, vp],
         "td_flux_set_channel_condition": [vp, vp, vp],
+        "td_flux_set_reference_tokens": [vp, vp, i32, vp, vp],
+        "td_flux_reference_tokens": [vp, vp],
+        "td_flux_denoise_cfg": [vp, vp, vp, vp, i32, f32, vp],
         "td_flux_fill_condition": [vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp],
         "td_vae_encode_masked": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
         "td_vae_image_to_nhwc_masked_bf16": [vp, i32, vp, i32, i32, i32, vp, i32, vp],
@@ -121,6 +125,7 @@ def _declare(L):
         "td_groupnorm_nhwc_bf16": [vp, vp, i32, i32, i32, f32, vp, vp, i32, vp, vp],
         "td_groupnorm_workspace_floats": [],
         "td_softmax_rows_f32_bf16": [vp, vp, i32, i32, f32, vp],
+        "td_softmax_rows_strided_f32_bf16": [vp, vp, i32, i32, i32, f32, vp],
         "td_qwen2_create": [vp, i32, vp],
         "td_qwen2_num_params": [vp],
         "td_qwen2_param_info": [vp, i32, ctypes.c_char_p, i32, vp],

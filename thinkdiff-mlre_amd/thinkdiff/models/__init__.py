@@ -6,6 +6,7 @@ from .flux_control import FluxControlPipelineRewritePrompt
 from .flux_fill import FluxFillPipelineRewritePrompt
 from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
 from .flux_inpaint import FluxInpaintPipelineRewritePrompt
+from .flux_kontext import FluxKontextPipelineRewritePrompt
 from .flux_prompt import FluxPipelineRewritePrompt
 from .flux_transformer import FluxTransformer2DModel, FluxTransformerConfig
 from .mllama_vllm_t5_embed_decoder_2 import MllamaVllmT5EmbedDecoderForConditionalGeneration_5
@@ -14,5 +15,5 @@ from .qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
 
 __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration", "build_vision_projector",
            "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
-           "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt",
+           "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt", "FluxKontextPipelineRewritePrompt",
            "FluxTransformer2DModel", "FluxTransformerConfig"]

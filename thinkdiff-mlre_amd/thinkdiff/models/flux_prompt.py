@@ -204,14 +204,38 @@ class FluxPipelineRewritePrompt:
         return self._finish(xs, h, w, output_type, return_dict)
 
     def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff,
-                        inpaint=None, channel_cond=None):
+                        inpaint=None, channel_cond=None, reference=None, cfg=None):
         """The denoise loop over `sig` (any sigma list ending in 0: the full schedule or a truncated one) for the first B packed latents
         of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents.
         inpaint: None, or per sample b an (image_latents, noise, mask) triple of [S, 64] tensors made on the current stream (the
         inpainting loop, FluxTransformer2DModel.denoise).  channel_cond: None, or per sample b the [S, in_channels - out_channels] condition
-        of a channel-conditioned transformer, set on the context that carries sample b next to its prompt (FLUX.1 Fill / Control)."""
+        of a channel-conditioned transformer, set on the context that carries sample b next to its prompt (FLUX.1 Fill / Control).
+        reference: None, or per sample b the (ref_latents [S_ref, 64], ref_ids [S_ref, 3]) reference tokens of FLUX.1 Kontext, set on the
+        context that carries sample b right after its prompt (an entry may be None: no reference for that sample).
+        cfg: None, or (negative_prompt_embeds, negative_pooled_prompt_embeds, negative_text_ids, true_cfg_scale): true classifier-free
+        guidance -- one (positive, negative) context pair on one stream, samples one after another (FluxTransformer2DModel.denoise_cfg)."""
         tr = self.transformer
         n_prompts = prompt_embeds.shape[0]
+        if cfg is not None:
+            if inpaint is not None or channel_cond is not None:
+                raise NotImplementedError("true classifier-free guidance is built for the plain and the reference-token loop only")
+            neg_embeds, neg_pooled, neg_ids, scale = cfg
+            pos, neg = self._contexts(2)
+            main, st, xs = torch.cuda.current_stream(), self._streams[0], []
+            for b in range(B):
+                pb = min(b // num_images_per_prompt, n_prompts - 1)
+                st.wait_stream(main)
+                with torch.cuda.stream(st):
+                    for ctx, e, p, ids in ((pos, prompt_embeds, pooled_prompt_embeds, text_ids), (neg, neg_embeds, neg_pooled, neg_ids)):
+                        ctx.set_condition(e[min(pb, e.shape[0] - 1)], p[min(pb, p.shape[0] - 1)], img_ids, ids)
+                        if reference is not None and reference[b] is not None:
+                            ctx.set_reference_tokens(*reference[b])
+                        ctx.set_timesteps(t_eff, g_eff)
+                    x = lat[b].contiguous()
+                    pos.denoise_cfg(neg, x, sig, scale)
+                main.wait_stream(st)
+                xs.append(x)
+            return xs
         # `images_in_flight` independent images advance together, each on its own stream and engine context (shared
         # weights): the grids of one step are 1.6 - 3.2 rounds of the 256 CUs, and a second image fills those tails.
         G = max(1, min(int(self.images_in_flight), B))
@@ -229,6 +253,8 @@ class FluxPipelineRewritePrompt:
                     ctxs[k].set_condition(prompt_embeds[pb], pooled_prompt_embeds[min(pb, pooled_prompt_embeds.shape[0] - 1)], img_ids, text_ids)
                     if channel_cond is not None:
                         ctxs[k].set_channel_condition(channel_cond[b])
+                    if reference is not None and reference[b] is not None:
+                        ctxs[k].set_reference_tokens(*reference[b])
                     ctxs[k].set_timesteps(t_eff, g_eff)
                     lat_g.append(lat[b].contiguous())
             blend_g = None if inpaint is None else [inpaint[b] for b in group]

@@ -222,6 +222,23 @@ class FluxTransformer2DModel:
         _OPS.flux_set_channel_condition(int(self._h.value), d)
         torch.cuda.current_stream().synchronize()      # `d` may be a temporary
 
+    def set_reference_tokens(self, ref_latents, ref_ids=None):
+        """FLUX.1 Kontext's reference tokens of one image: ref_latents [S_ref, out_channels] bf16 (packed, shifted / scaled image latents),
+        ref_ids [S_ref, 3] (first coordinate 1).  From now on every forward of this context runs over [text | latents | reference] and
+        returns the velocity of the latents' rows only -- what diffusers' FluxKontextPipeline does with a torch.cat and a slice per step.
+        After set_condition (which always voids them), once per image; this context's own (forks hold theirs).  None clears."""
+        c = self.config
+        if ref_latents is None:
+            ref_latents = torch.empty(0, c.latent_channels, dtype=torch.bfloat16, device=self.device)
+            ref_ids = torch.empty(0, 3, dtype=torch.float32, device=self.device)
+        if ref_ids is None:
+            raise ValueError("set_reference_tokens: ref_ids [S_ref, 3] are required with ref_latents (only set_reference_tokens(None) clears)")
+        assert ref_latents.dim() == 2 and ref_latents.shape[1] == c.latent_channels, f"ref_latents must be [S_ref, {c.latent_channels}], got {tuple(ref_latents.shape)}"
+        d = ref_latents.to(self.device, torch.bfloat16).contiguous()
+        ii = ref_ids.to(self.device, torch.float32).contiguous()
+        _OPS.flux_set_reference_tokens(int(self._h.value), d, ii)
+        torch.cuda.current_stream().synchronize()      # `d` / `ii` may be temporaries
+
     def set_timesteps(self, t_eff: Sequence[float], g_eff: float = 0.0):
         arr = (ctypes.c_float * len(t_eff))(*[float(t) for t in t_eff])
         _hip.check(self._L.td_flux_set_timesteps(self._h, ctypes.cast(arr, ctypes.c_void_p), len(t_eff), float(g_eff), _hip.stream_ptr()))
@@ -242,6 +259,13 @@ class FluxTransformer2DModel:
             return _OPS.flux_denoise_(int(self._h.value), latents, [float(s) for s in sigmas])
         z, noise, mask = inpaint
         return _OPS.flux_denoise_inpaint_(int(self._h.value), latents, [float(s) for s in sigmas], z, noise, mask)
+
+    def denoise_cfg(self, neg_context, latents, sigmas: Sequence[float], scale: float):
+        """FluxKontextPipeline's loop under true classifier-free guidance, in place: per step the transformer on this (positive) context
+        and on `neg_context` (a fork prepared with the negative prompt and the same schedule), then flux_cfg_step_ --
+        v = v_neg + scale * (v_pos - v_neg) and the Euler step, fused.  One stream."""
+        assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.latent_channels)
+        return _OPS.flux_denoise_cfg_(int(self._h.value), int(neg_context._h.value), latents, [float(s) for s in sigmas], float(scale))
 
     # ---- per-launch HIP-event trace (bench.py roofline leg) ------------------------------------------
     TRACE_CATEGORIES = ("gemm_256x256", "gemm_other", "attention", "layernorm_modulate", "qk_rmsnorm_rope", "gemm_288x192")

@@ -134,6 +134,7 @@ class AutoencoderKLEncoder:
         with torch.cuda.device(self.device):
             _hip.check(self._L.td_vae_enc_create(ctypes.byref(cc), max_image_size[0], max_image_size[1], ctypes.byref(h)))
         self._h = h
+        self.max_image_size = (int(max_image_size[0]), int(max_image_size[1]))      # capacity: H * W <= their product
         self.downscale = 2 ** (len(c.block_out_channels) - 1)
 
     def __del__(self):

@@ -28,6 +28,9 @@ vae_latents_from_moments   posterior sample / mode, the img2img pipeline's shift
 flux_inpaint_step_         FluxInpaintPipeline's step: scheduler.step + scale_noise of the image latents + mask blend, fused, in place
 flux_inpaint_mask          the inpainting mask's binarize, F.interpolate(nearest) to the latent size, repeat and _pack_latents, fused
 flux_denoise_inpaint_ / flux_denoise_multi_inpaint_   the inpainting denoise loop (flux_denoise_ / flux_denoise_multi_ with that step)
+flux_set_reference_tokens  FluxKontextPipeline's per-step torch.cat of the reference-image latents / ids behind the latents, once per image
+flux_cfg_step_             true classifier-free guidance (neg + scale * (pos - neg)) + scheduler.step, fused, in place
+flux_denoise_cfg_          the denoise loop under true CFG: both conditionings per step on two prepared contexts, then flux_cfg_step_
 """
 import os
 
@@ -59,6 +62,9 @@ SCHEMAS = {
     "flux_inpaint_step_": "(Tensor(a!) x, Tensor v, Tensor image_latents, Tensor? noise, Tensor mask, float dt, float sigma_next) -> Tensor(a!)",
     "flux_inpaint_mask": "(Tensor mask, int C) -> Tensor",
     "flux_denoise_inpaint_": "(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)",
+    "flux_set_reference_tokens": "(int engine, Tensor ref_latents, Tensor ref_ids) -> ()",
+    "flux_cfg_step_": "(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)",
+    "flux_denoise_cfg_": "(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)",
     "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
 }
 
