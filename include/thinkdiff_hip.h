@@ -16,6 +16,7 @@
  */
 #ifndef THINKDIFF_HIP_H
 #define THINKDIFF_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -248,7 +249,8 @@ void td_flux_destroy(td_flux* f);
 int64_t td_flux_param_elems(const td_flux* f);
 int td_flux_num_params(const td_flux* f);
 int td_flux_param_info(const td_flux* f, int idx, char* name_buf, int buf_len, int64_t* count);
-/* copy one parameter (device bf16, `count` elements) into the engine's fused weight arena */
+/* copy one parameter (device bf16, `count` elements) into the engine's fused weight arena.  TD_ERR_INVALID while the parameter holds a LoRA
+ * base copy (td_flux_lora_load): clear the adapters first.  td_flux_init_random likewise. */
 int td_flux_load_param(td_flux* f, const char* name, const void* src, int64_t count, void* stream);
 /* A second context over the same weights (own workspace, conditioning, timestep schedule): independent images in flight on
  * separate streams fill the tails of each other's kernels (a 1024^2 step's grids are 1.6 - 3.2 rounds of the 256 CUs).
@@ -350,6 +352,57 @@ int td_flux_denoise_cfg(td_flux* pos, td_flux* neg, void* latents, const float* 
  * [S_img, out_channels] (the latents' width), 16-byte aligned, none NULL, none overlapping the latents. */
 int td_flux_denoise_inpaint(td_flux* f, void* latents, const float* sigmas, int n, const void* image_latents, const void* noise,
                             const void* mask, void* stream);
+
+/* ---- LoRA adapters: low-rank weight merge --------------------------------------------------------------------------
+ * On this engine an adapter is always MERGED: W_eff = W + sum_i weight_i * (alpha_i / rank_i) * B_i A_i, recomputed from an untouched copy of
+ * the base weight with one rounding whenever the adapters or their weights change.  The forward afterwards is the code that exists (same kernels,
+ * same launch count; the 8-bit modes quantise W_eff), and the merge is a pure function of (base, active adapters, weights): switching adapters
+ * never drifts, unloading gives back the base bits.  Replaces [ext] peft LoraLayer.forward / merge / unmerge as [ext] diffusers
+ * FluxLoraLoaderMixin drives them (load_lora_weights, set_adapters, fuse_lora / unfuse_lora, delete_adapters, unload_lora_weights).
+ * The reference drivers load no LoRA: this belongs to the FLUX.1 pipelines' own surface. */
+#define TD_LORA_MAX_ADAPTERS 8   /* active adapters on ONE parameter (one td_lora_merge_bf16 call) */
+/* The kernel's operand form of one (lora_A.weight [rank, K], lora_B.weight [N, rank]) pair: A transposed [K, r_pad] then B [N, r_pad], the rank
+ * zero-padded to r_pad = 16 ceil(rank / 16) (one k-step of the bf16 matrix instruction), so that every fragment is one 16-byte read.  Made once
+ * per adapter, not per merge.  td_lora_packed_bytes: its size (0 for rank < 1 or empty extents). */
+size_t td_lora_packed_bytes(int rank, int N, int K);
+int td_lora_pack_bf16(const void* A, const void* B, int rank, int N, int K, void* packed, void* stream);
+/* w_out[n, k] = RNE_bf16( float(w_base[n, k]) + sum_i scales[i] * sum_r B_i[n, r] A_i[r, k] ): peft's `weight + scaling * (B @ A)` for up to
+ * TD_LORA_MAX_ADAPTERS pairs at once.  w_base, w_out bf16 [N, K] contiguous, 16-byte aligned, w_out may BE w_base (in place); packed[i] from
+ * td_lora_pack_bf16 with the same N, K; any rank >= 1; K % 64 == 0, N % 8 == 0.  Inner products on v_mfma_f32_32x32x16_bf16 with fp32
+ * accumulation; scales[i] multiplies the fp32 sum of adapter i; the base joins in fp32; one rounding.  Pairs with scale 0 are skipped, and with
+ * none left w_out receives the base bits.  TD_ERR_INVALID before any launch for anything else. */
+int td_lora_merge_bf16(const void* w_base, void* w_out, int N, int K, int n_adapters, const void* const* packed, const int* ranks,
+                       const float* scales, void* stream);
+/* The parameter AS THE FORWARD SEES IT NOW (the effective weight: base + merged adapters) -> dst (device bf16, `count` elements): the inverse of
+ * td_flux_load_param; what `transformer.state_dict()[name]` is after fuse_lora. */
+int td_flux_read_param(td_flux* f, const char* name, void* dst, int64_t count, void* stream);
+/* [N, K] of a Linear's `.weight` parameter, [count, 1] of a 1-D one (biases, norm scales).  The engine takes N, K of an adapter pair from here:
+ * a C caller of td_flux_lora_load vouches that A holds rank x K and B N x rank elements (the torch.ops layer checks its tensors against it). */
+int td_flux_param_shape(const td_flux* f, const char* name, int64_t* rows, int64_t* cols);
+/* Attach one low-rank pair of adapter `adapter` to the `.weight` of one Linear (`param` = its diffusers state-dict name, e.g.
+ * "transformer_blocks.3.attn.to_k.weight"): A = lora_A.weight [rank, K], B = lora_B.weight [N, rank], device bf16, 16-byte aligned;
+ * scale = lora_alpha / rank.  Replaces peft's inject_adapter + set_peft_model_state_dict for that module.  Copies the pair into engine-owned
+ * device memory in the kernel's operand form; the first pair on a parameter also takes the BASE COPY of it.  Allocates (like
+ * td_flux_set_precision: not capturable).  Changes no weight yet: a new adapter is inactive until td_flux_lora_set_adapters names it.
+ * TD_ERR_INVALID, naming the offender: a fork; an unknown, 1-D or non-`.weight` parameter; rank < 1; a non-finite scale; misaligned pointers;
+ * a second pair for the same (adapter, parameter). */
+int td_flux_lora_load(td_flux* f, const char* adapter, const char* param, const void* A, const void* B, int rank, float scale, void* stream);
+/* diffusers' set_adapters(names, weights): the n named adapters become the active set with these weights, every other adapter inactive, and EVERY
+ * parameter any loaded adapter touches is recomputed from its base copy with scales weights[i] * scale (one td_lora_merge_bf16 launch each);
+ * n == 0: all inactive, base bits.  In an 8-bit precision the block weights are then quantised again from the merged ones (td_flux_set_precision's
+ * pass) and the int8 history / smoothing calibration is forgotten as after td_flux_load_param.  Bumps the weight epoch: a context whose
+ * td_flux_set_condition / td_flux_set_timesteps ran before it refuses td_flux_forward / td_flux_denoise* until both ran again (they precompute
+ * the embedders and every adaLN modulation FROM weights).  The caller keeps merges off streams that run forwards on these weights.
+ * TD_ERR_INVALID: a fork; an unknown or repeated adapter name; a non-finite weight; more than TD_LORA_MAX_ADAPTERS active on one parameter
+ * (nothing is changed then). */
+int td_flux_lora_set_adapters(td_flux* f, const char* const* names, const float* weights, int n, void* stream);
+/* diffusers' delete_adapters(name) / unload_lora_weights(): drop one / all adapters and recompute what they touched; a parameter no adapter
+ * touches any more gets its base bits back and its base copy is freed.  Synchronises the stream (memory is released).  Weight epoch as above. */
+int td_flux_lora_delete(td_flux* f, const char* adapter, void* stream);
+int td_flux_lora_clear(td_flux* f, void* stream);
+/* Bookkeeping: loaded adapters, parameters holding a base copy, device bytes held (operands + base copies; with every Linear of FLUX.1-dev
+ * targeted the base copies are one more weight arena).  Any out pointer may be NULL. */
+int td_flux_lora_info(const td_flux* f, int* n_adapters, int* n_params_touched, int64_t* bytes_held);
 
 /* ---- fp8 operand path (BASELINE config 5 "fp8 MFMA FLUX path") -------------------------------
  * Operands are OCP e4m3 bytes with one fp32 dequantisation scale per row: weights per output channel (quantised once at

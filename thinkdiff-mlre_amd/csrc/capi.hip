@@ -16,7 +16,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 2; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX)
+int td_abi_version(void) { return 3; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,

@@ -36,6 +36,28 @@ struct Slot {
   std::string name;
   bf16_t* ptr;
   int64_t count;
+  int64_t rows, cols;      // [N, K] of a Linear's weight; [count, 1] of a 1-D parameter
+};
+
+// LoRA adapters (td_flux_lora_*; parent context).  An adapter is a set of low-rank pairs, each on one Linear weight slot, kept in the merge kernel's
+// operand form (csrc/lora.hip).  Every slot any pair touches holds a BASE COPY of the parameter as it was before the first pair arrived: the
+// effective weight in the arena is always recomputed from it, never updated incrementally.
+struct LoraPair {
+  int slot;
+  int rank;
+  float scale;             // lora_alpha / rank
+  bf16_t* packed;          // At [K, r_pad] | Bp [N, r_pad]
+  int64_t bytes;
+};
+struct LoraAdapter {
+  std::string name;
+  std::vector<LoraPair> pairs;
+  bool active = false;
+  float weight = 0.f;
+};
+struct LoraState {
+  std::vector<LoraAdapter> adapters;
+  std::unordered_map<int, bf16_t*> base;      // slot -> base copy
 };
 
 struct DoubleW {
@@ -132,6 +154,12 @@ struct td_flux {
   // a forked context (td_flux_fork) shares the parent's weights (bf16 arena, fp8 arena, precision) and owns its
   // workspace, conditioning and schedule: several images in flight on separate streams fill each other's kernel tails
   td_flux* parent = nullptr;
+  // LoRA registry (parent only; a fork's copy of the pointer is never used) and the weight epoch: td_flux_lora_set_adapters / delete / clear bump
+  // it on the parent, td_flux_set_condition / td_flux_set_timesteps record it on their context (both precompute values from weights), and a
+  // forward refuses a context prepared under an older one.
+  LoraState* lora = nullptr;
+  int weight_epoch = 0;
+  int cond_epoch = 0, sched_epoch = 0;
   // state
   int T = 0, S_img = 0, n_steps = 0;
   bool cond_set = false;
@@ -167,12 +195,13 @@ struct ArenaPlan {
 
 void add_slot(td_flux* f, const std::string& name, bf16_t* ptr, int64_t count) {
   f->index[name] = (int)f->slots.size();
-  f->slots.push_back({name, ptr, count});
+  f->slots.push_back({name, ptr, count, count, 1});
 }
 
 // registers "<name>.weight" / "<name>.bias" of a Linear living at rows [row0, row0+out) of a fused matrix
 void add_linear(td_flux* f, const std::string& name, bf16_t* w, bf16_t* b, int64_t row0, int64_t out, int64_t in) {
   add_slot(f, name + ".weight", w + row0 * in, out * in);
+  f->slots.back().rows = out; f->slots.back().cols = in;
   add_slot(f, name + ".bias", b + row0, out);
 }
 
@@ -488,6 +517,11 @@ void td_flux_destroy(td_flux* f) {
   if (!f) return;
   for (hipEvent_t ev : f->ev_pool) (void)hipEventDestroy(ev);
   if (!f->parent) {
+    if (f->lora) {
+      for (auto& a : f->lora->adapters) for (auto& p : a.pairs) (void)hipFree(p.packed);
+      for (auto& b : f->lora->base) (void)hipFree(b.second);
+      delete f->lora;
+    }
     (void)hipFree(f->arena);
     if (f->arena8) (void)hipFree(f->arena8);
     if (f->sm_ax) (void)hipFree(f->sm_ax);      // one allocation: ax | aw | s | inv | inv16
@@ -575,6 +609,11 @@ int td_flux_load_param(td_flux* f, const char* name, const void* src, int64_t co
   TD_CHECK_ARG(it != f->index.end(), "td_flux_load_param: unknown parameter '%s'", name);
   const Slot& s = f->slots[it->second];
   TD_CHECK_ARG(s.count == count, "td_flux_load_param: '%s' expects %lld elements, got %lld", name, (long long)s.count, (long long)count);
+  {
+    const LoraState* ls = (f->parent ? f->parent : f)->lora;
+    TD_CHECK_ARG(!ls || !ls->base.count(it->second), "td_flux_load_param: '%s' carries LoRA adapters (its base copy would go stale): clear the adapters first "
+                 "(td_flux_lora_clear)", name);
+  }
   TD_CHECK_HIP(hipMemcpyAsync(s.ptr, src, (size_t)count * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return TD_OK;
 }
@@ -823,6 +862,205 @@ int td_flux_set_precision(td_flux* f, int precision, void* stream) {
 
 }  // extern "C"
 
+// ---- LoRA adapter registry ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+int lora_find(const LoraState* ls, const char* name) {
+  if (ls) for (size_t i = 0; i < ls->adapters.size(); ++i) if (ls->adapters[i].name == name) return (int)i;
+  return -1;
+}
+
+// the pairs that act on `slot` under the current active set, in adapter order; false: more than one merge launch takes
+bool lora_active_on(const LoraState* ls, int slot, std::vector<const void*>* packed, std::vector<int>* ranks, std::vector<float>* scales) {
+  int n = 0;
+  for (const LoraAdapter& a : ls->adapters) {
+    if (!a.active || a.weight == 0.f) continue;
+    for (const LoraPair& p : a.pairs) {
+      if (p.slot != slot) continue;
+      if (++n > TD_LORA_MAX_ADAPTERS) return false;
+      if (packed) { packed->push_back(p.packed); ranks->push_back(p.rank); scales->push_back(a.weight * p.scale); }
+    }
+  }
+  return true;
+}
+
+// Recompute the arena's copy of every slot in `slots` from its base copy, free the base copies no pair needs any more, then everything a weight
+// change entails: weight epoch, 8-bit history / smoothing calibration, the 8-bit weights themselves.
+int lora_remerge(td_flux* f, const std::vector<int>& slots, hipStream_t s) {
+  LoraState* ls = f->lora;
+  for (int slot : slots)
+    TD_CHECK_ARG(lora_active_on(ls, slot, nullptr, nullptr, nullptr), "td_flux_lora: more than %d active adapters on '%s'", TD_LORA_MAX_ADAPTERS,
+                 f->slots[slot].name.c_str());
+  auto touched = [&](int slot) {
+    for (const LoraAdapter& a : ls->adapters) for (const LoraPair& p : a.pairs) if (p.slot == slot) return true;
+    return false;
+  };
+  bool orphans = false;
+  for (int slot : slots) {
+    auto it = ls->base.find(slot);
+    if (it == ls->base.end()) continue;
+    const Slot& sl = f->slots[slot];
+    std::vector<const void*> packed; std::vector<int> ranks; std::vector<float> scales;
+    lora_active_on(ls, slot, &packed, &ranks, &scales);
+    TD_TRY(td_lora_merge_bf16(it->second, sl.ptr, (int)sl.rows, (int)sl.cols, (int)packed.size(), packed.data(), ranks.data(), scales.data(), s));
+    orphans |= !touched(slot);
+  }
+  if (orphans) {      // base copies no pair needs any more: their bits are back in the arena once the stream has drained
+    TD_CHECK_HIP(hipStreamSynchronize(s));
+    for (int slot : slots) {
+      auto it = ls->base.find(slot);
+      if (it != ls->base.end() && !touched(slot)) { (void)hipFree(it->second); ls->base.erase(it); }
+    }
+  }
+  ++f->weight_epoch;
+  ++f->hist_epoch;
+  f->smooth_ready = false;
+  if (f->precision != TD_PRECISION_BF16) TD_TRY(td_flux_set_precision(f, f->precision, s));      // the 8-bit weights again, from the merged ones
+  return TD_OK;
+}
+
+std::vector<int> lora_all_slots(const LoraState* ls) {
+  std::vector<int> v;
+  for (const auto& b : ls->base) v.push_back(b.first);
+  std::sort(v.begin(), v.end());
+  return v;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_flux_read_param(td_flux* f, const char* name, void* dst, int64_t count, void* stream) {
+  TD_CHECK_ARG(f && name && dst, "td_flux_read_param: null argument");
+  auto it = f->index.find(name);
+  TD_CHECK_ARG(it != f->index.end(), "td_flux_read_param: unknown parameter '%s'", name);
+  const Slot& s = f->slots[it->second];
+  TD_CHECK_ARG(s.count == count, "td_flux_read_param: '%s' holds %lld elements, the destination %lld", name, (long long)s.count, (long long)count);
+  TD_CHECK_HIP(hipMemcpyAsync(dst, s.ptr, (size_t)count * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TD_OK;
+}
+
+int td_flux_param_shape(const td_flux* f, const char* name, int64_t* rows, int64_t* cols) {
+  TD_CHECK_ARG(f && name, "td_flux_param_shape: null argument");
+  auto it = f->index.find(name);
+  TD_CHECK_ARG(it != f->index.end(), "td_flux_param_shape: unknown parameter '%s'", name);
+  if (rows) *rows = f->slots[it->second].rows;
+  if (cols) *cols = f->slots[it->second].cols;
+  return TD_OK;
+}
+
+int td_flux_lora_load(td_flux* f, const char* adapter, const char* param, const void* A, const void* B, int rank, float scale, void* stream) {
+  TD_CHECK_ARG(f && adapter && param && A && B, "td_flux_lora_load: null argument");
+  TD_CHECK_ARG(!f->parent, "td_flux_lora_load: '%s': adapters belong to the parent context (forks see its weights)", param);
+  TD_CHECK_ARG(adapter[0], "td_flux_lora_load: empty adapter name");
+  auto it = f->index.find(param);
+  TD_CHECK_ARG(it != f->index.end(), "td_flux_lora_load: unknown parameter '%s'", param);
+  const int slot = it->second;
+  const Slot& sl = f->slots[slot];
+  const size_t pl = strlen(param);
+  TD_CHECK_ARG(sl.cols > 1 && pl > 7 && strcmp(param + pl - 7, ".weight") == 0, "td_flux_lora_load: '%s' is not the weight of a Linear (%lld elements, 1-D): "
+               "bias and norm-scale deltas are not built", param, (long long)sl.count);
+  TD_CHECK_ARG(rank >= 1, "td_flux_lora_load: '%s': rank=%d must be at least 1", param, rank);
+  TD_CHECK_ARG(std::isfinite(scale), "td_flux_lora_load: '%s': scale is not finite", param);
+  TD_CHECK_ARG((uintptr_t)A % 16 == 0 && (uintptr_t)B % 16 == 0, "td_flux_lora_load: '%s': A and B must be 16-byte aligned", param);
+  TD_CHECK_ARG(sl.cols % 64 == 0 && sl.rows % 8 == 0 && sl.rows < (1ll << 31) && sl.cols < (1ll << 31), "td_flux_lora_load: '%s' is [%lld, %lld]: the merge "
+               "needs rows %% 8 == 0 and columns %% 64 == 0", param, (long long)sl.rows, (long long)sl.cols);
+  if (!f->lora) f->lora = new LoraState();
+  LoraState* ls = f->lora;
+  int ai = lora_find(ls, adapter);
+  if (ai >= 0)
+    for (const LoraPair& p : ls->adapters[ai].pairs)
+      TD_CHECK_ARG(p.slot != slot, "td_flux_lora_load: adapter '%s' already holds a pair for '%s'", adapter, param);
+  hipStream_t s = (hipStream_t)stream;
+  LoraPair p;
+  p.slot = slot; p.rank = rank; p.scale = scale;
+  p.bytes = (int64_t)td_lora_packed_bytes(rank, (int)sl.rows, (int)sl.cols);
+  hipError_t e = hipMalloc((void**)&p.packed, (size_t)p.bytes);
+  if (e != hipSuccess) { td_set_error("td_flux_lora_load: '%s': hipMalloc of %lld operand bytes failed: %s", param, (long long)p.bytes, hipGetErrorString(e)); return TD_ERR_HIP; }
+  if (int rc = td_lora_pack_bf16(A, B, rank, (int)sl.rows, (int)sl.cols, p.packed, s)) { (void)hipFree(p.packed); return rc; }
+  if (!ls->base.count(slot)) {
+    bf16_t* base = nullptr;
+    e = hipMalloc((void**)&base, (size_t)sl.count * 2);
+    if (e == hipSuccess) e = hipMemcpyAsync(base, sl.ptr, (size_t)sl.count * 2, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) {
+      td_set_error("td_flux_lora_load: '%s': base copy of %lld bytes failed: %s", param, (long long)sl.count * 2, hipGetErrorString(e));
+      (void)hipStreamSynchronize(s);
+      (void)hipFree(p.packed); if (base) (void)hipFree(base);
+      return TD_ERR_HIP;
+    }
+    ls->base[slot] = base;
+  }
+  if (ai < 0) { ls->adapters.emplace_back(); ls->adapters.back().name = adapter; ai = (int)ls->adapters.size() - 1; }
+  ls->adapters[ai].pairs.push_back(p);
+  return TD_OK;
+}
+
+int td_flux_lora_set_adapters(td_flux* f, const char* const* names, const float* weights, int n, void* stream) {
+  TD_CHECK_ARG(f && n >= 0 && (n == 0 || (names && weights)), "td_flux_lora_set_adapters: null argument");
+  TD_CHECK_ARG(!f->parent, "td_flux_lora_set_adapters: adapters belong to the parent context (forks see its weights)");
+  LoraState* ls = f->lora;
+  std::vector<int> idx(n);
+  for (int i = 0; i < n; ++i) {
+    TD_CHECK_ARG(names[i], "td_flux_lora_set_adapters: name %d is null", i);
+    idx[i] = lora_find(ls, names[i]);
+    TD_CHECK_ARG(idx[i] >= 0, "td_flux_lora_set_adapters: unknown adapter '%s'", names[i]);
+    TD_CHECK_ARG(std::isfinite(weights[i]), "td_flux_lora_set_adapters: the weight of adapter '%s' is not finite", names[i]);
+    for (int j = 0; j < i; ++j) TD_CHECK_ARG(idx[j] != idx[i], "td_flux_lora_set_adapters: adapter '%s' is named twice", names[i]);
+  }
+  if (!ls) return TD_OK;      // nothing loaded, nothing named
+  std::vector<std::pair<bool, float>> before;
+  for (LoraAdapter& a : ls->adapters) { before.emplace_back(a.active, a.weight); a.active = false; a.weight = 0.f; }
+  for (int i = 0; i < n; ++i) { ls->adapters[idx[i]].active = true; ls->adapters[idx[i]].weight = weights[i]; }
+  const std::vector<int> slots = lora_all_slots(ls);
+  for (int slot : slots)
+    if (!lora_active_on(ls, slot, nullptr, nullptr, nullptr)) {      // refused: nothing changes
+      for (size_t i = 0; i < before.size(); ++i) { ls->adapters[i].active = before[i].first; ls->adapters[i].weight = before[i].second; }
+      td_set_error("td_flux_lora_set_adapters: more than %d active adapters on '%s'", TD_LORA_MAX_ADAPTERS, f->slots[slot].name.c_str());
+      return TD_ERR_INVALID;
+    }
+  return lora_remerge(f, slots, (hipStream_t)stream);
+}
+
+int td_flux_lora_delete(td_flux* f, const char* adapter, void* stream) {
+  TD_CHECK_ARG(f && adapter, "td_flux_lora_delete: null argument");
+  TD_CHECK_ARG(!f->parent, "td_flux_lora_delete: adapters belong to the parent context (forks see its weights)");
+  const int ai = lora_find(f->lora, adapter);
+  TD_CHECK_ARG(ai >= 0, "td_flux_lora_delete: unknown adapter '%s'", adapter);
+  LoraState* ls = f->lora;
+  TD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));      // its operands may still be read by a merge in flight
+  std::vector<int> slots;
+  for (LoraPair& p : ls->adapters[ai].pairs) { slots.push_back(p.slot); (void)hipFree(p.packed); }
+  ls->adapters.erase(ls->adapters.begin() + ai);
+  return lora_remerge(f, slots, (hipStream_t)stream);
+}
+
+int td_flux_lora_clear(td_flux* f, void* stream) {
+  TD_CHECK_ARG(f, "td_flux_lora_clear: null handle");
+  TD_CHECK_ARG(!f->parent, "td_flux_lora_clear: adapters belong to the parent context (forks see its weights)");
+  LoraState* ls = f->lora;
+  if (!ls || (ls->adapters.empty() && ls->base.empty())) return TD_OK;
+  TD_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+  for (LoraAdapter& a : ls->adapters) for (LoraPair& p : a.pairs) (void)hipFree(p.packed);
+  ls->adapters.clear();
+  return lora_remerge(f, lora_all_slots(ls), (hipStream_t)stream);
+}
+
+int td_flux_lora_info(const td_flux* f, int* n_adapters, int* n_params_touched, int64_t* bytes_held) {
+  TD_CHECK_ARG(f, "td_flux_lora_info: null handle");
+  const LoraState* ls = (f->parent ? f->parent : f)->lora;
+  int64_t bytes = 0;
+  if (ls) {
+    for (const LoraAdapter& a : ls->adapters) for (const LoraPair& p : a.pairs) bytes += p.bytes;
+    for (const auto& b : ls->base) bytes += f->slots[b.first].count * 2;
+  }
+  if (n_adapters) *n_adapters = ls ? (int)ls->adapters.size() : 0;
+  if (n_params_touched) *n_params_touched = ls ? (int)ls->base.size() : 0;
+  if (bytes_held) *bytes_held = bytes;
+  return TD_OK;
+}
+
+}  // extern "C"
+
 struct FloatPack { static constexpr int N = 128; float v[N]; };
 __global__ void td_set_floats_kernel(float* dst, FloatPack vals, int n) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
@@ -863,6 +1101,11 @@ int td_fill_normal_bf16(void* dst, int64_t n, uint64_t seed, float std, float me
 
 int td_flux_init_random(td_flux* f, uint64_t seed, float std, void* stream) {
   TD_CHECK_ARG(f, "td_flux_init_random: null handle");
+  {
+    const LoraState* ls = (f->parent ? f->parent : f)->lora;
+    TD_CHECK_ARG(!ls || ls->base.empty(), "td_flux_init_random: %d parameters carry LoRA adapters (their base copies would go stale): clear the adapters first "
+                 "(td_flux_lora_clear)", ls ? (int)ls->base.size() : 0);
+  }
   (f->parent ? f->parent : f)->bounds_dirty = true;
   ++(f->parent ? f->parent : f)->hist_epoch;
   (f->parent ? f->parent : f)->smooth_ready = false;
@@ -893,6 +1136,7 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
   TD_CHECK_HIP(hipMemcpyAsync(f->ids + (size_t)T * 3, img_ids, (size_t)S_img * 12, hipMemcpyDeviceToDevice, s));
   TD_TRY(td_flux_rope_table_launch(f->ids, T + S_img, f->cfg.axes_dims, (double)f->cfg.rope_theta, f->cosT, f->sinT, s));
   f->cond_set = true;
+  f->cond_epoch = (f->parent ? f->parent : f)->weight_epoch;
   f->n_steps = 0;
   f->hs_step = f->href_step = -1;      // another image: the previous one's maxima / reference points say nothing about it
   return TD_OK;
@@ -981,6 +1225,7 @@ int td_flux_set_timesteps(td_flux* f, const float* t_eff, int n, float g_eff, vo
   TD_TRY(td_temb_combine_silu_launch(f->te, f->cfg.guidance_embeds ? f->ge : nullptr, f->pe, n, D, f->temb, f->st, s));
   TD_TRY(gemm_big_n(f, s, f->st, D, f->mod_w, f->mod_b, f->mods, f->NMOD, n, f->NMOD, D));
   f->n_steps = n;
+  f->sched_epoch = (f->parent ? f->parent : f)->weight_epoch;
   f->hs_step = f->href_step = -1;      // another schedule: "the previous step" of the old one is not this one's
   return TD_OK;
 }
@@ -1007,6 +1252,11 @@ int td_flux_input_shape(const td_flux* f, int* in_channels, int* cond_channels, 
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream) {
   TD_CHECK_ARG(f && latents && velocity, "td_flux_forward: null argument");
   TD_CHECK_ARG(f->cond_set && step >= 0 && step < f->n_steps, "td_flux_forward: step %d outside the %d prepared timesteps", step, f ? f->n_steps : 0);
+  {
+    const int we = (f->parent ? f->parent : f)->weight_epoch;
+    TD_CHECK_ARG(f->cond_epoch == we && f->sched_epoch == we, "td_flux_forward: weights changed since td_flux_set_condition / td_flux_set_timesteps (LoRA adapters "
+                 "were set, deleted or cleared; both precompute values from weights): call them again on this context");
+  }
   TD_CHECK_ARG(f->Ccond == 0 || f->ccond_set, "td_flux_forward: this engine reads a %d-channel condition beside the %d latent channels and none is set for "
                "the %d image tokens (td_flux_set_channel_condition after td_flux_set_condition)", f->Ccond, f->Cout, f->S_img);
   hipStream_t s = (hipStream_t)stream;

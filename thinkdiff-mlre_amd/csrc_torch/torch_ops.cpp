@@ -447,6 +447,103 @@ at::Tensor attention_fp8(const at::Tensor& q, const at::Tensor& k, const at::Ten
   return out;
 }
 
+// ---- LoRA adapters --------------------------------------------------------------------------------------------------------------------------
+// peft's `weight + scaling * (lora_B.weight @ lora_A.weight)` for several pairs at once, one rounding (td_lora_merge_bf16): w [N, K], A[i] [r_i, K],
+// B[i] [N, r_i] bf16 contiguous -> a new [N, K] tensor.  The kernel's operand form of every pair is made here, per call (the engine makes it once).
+at::Tensor lora_merge(const at::Tensor& w, at::TensorList A, at::TensorList B, at::ArrayRef<double> scales) {
+  check_rows(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous(), "thinkdiff_hip::lora_merge: w must be contiguous [N, K]");
+  TORCH_CHECK(A.size() == B.size() && A.size() == scales.size(), "thinkdiff_hip::lora_merge: ", A.size(), " A, ", B.size(), " B, ", scales.size(), " scales");
+  TORCH_CHECK(A.size() <= TD_LORA_MAX_ADAPTERS, "thinkdiff_hip::lora_merge: ", A.size(), " adapters, one call takes at most ", TD_LORA_MAX_ADAPTERS);
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N < (1ll << 31) && K < (1ll << 31), "thinkdiff_hip::lora_merge: w is too large");
+  DeviceGuard guard(w.device());
+  std::vector<at::Tensor> packed;
+  std::vector<const void*> ptrs;
+  std::vector<int> ranks;
+  std::vector<float> sc;
+  for (size_t i = 0; i < A.size(); ++i) {
+    TORCH_CHECK(A[i].dim() == 2 && B[i].dim() == 2 && A[i].size(0) >= 1, "thinkdiff_hip::lora_merge: pair ", i, ": A [r, K], B [N, r] with r >= 1");
+    const int64_t r = A[i].size(0);
+    TORCH_CHECK(A[i].size(1) == K && B[i].size(0) == N && B[i].size(1) == r, "thinkdiff_hip::lora_merge: pair ", i, ": A ", A[i].sizes(), " / B ", B[i].sizes(),
+                " do not fit w ", w.sizes());
+    check_vec(A[i], "A", w, r * K); check_vec(B[i], "B", w, N * r);
+    const size_t bytes = td_lora_packed_bytes((int)r, (int)N, (int)K);
+    packed.push_back(at::empty({(int64_t)bytes}, w.options().dtype(at::kByte)));
+    ok(td_lora_pack_bf16(A[i].data_ptr(), B[i].data_ptr(), (int)r, (int)N, (int)K, packed.back().data_ptr(), stream_of(w)));
+    ptrs.push_back(packed.back().data_ptr()); ranks.push_back((int)r); sc.push_back((float)scales[i]);
+  }
+  at::Tensor out = at::empty_like(w);
+  ok(td_lora_merge_bf16(w.data_ptr(), out.data_ptr(), (int)N, (int)K, (int)ptrs.size(), ptrs.data(), ranks.data(), sc.data(), stream_of(w)));
+  return out;
+}
+// the same, into w itself (td_lora_merge_bf16 with w_out == w_base)
+at::Tensor& lora_merge_(at::Tensor& w, at::TensorList A, at::TensorList B, at::ArrayRef<double> scales) {
+  check_rows(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous(), "thinkdiff_hip::lora_merge_: w must be contiguous [N, K]");
+  TORCH_CHECK(A.size() == B.size() && A.size() == scales.size(), "thinkdiff_hip::lora_merge_: ", A.size(), " A, ", B.size(), " B, ", scales.size(), " scales");
+  TORCH_CHECK(A.size() <= TD_LORA_MAX_ADAPTERS, "thinkdiff_hip::lora_merge_: ", A.size(), " adapters, one call takes at most ", TD_LORA_MAX_ADAPTERS);
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N < (1ll << 31) && K < (1ll << 31), "thinkdiff_hip::lora_merge_: w is too large");
+  DeviceGuard guard(w.device());
+  std::vector<at::Tensor> packed;
+  std::vector<const void*> ptrs;
+  std::vector<int> ranks;
+  std::vector<float> sc;
+  for (size_t i = 0; i < A.size(); ++i) {
+    TORCH_CHECK(A[i].dim() == 2 && B[i].dim() == 2 && A[i].size(0) >= 1, "thinkdiff_hip::lora_merge_: pair ", i, ": A [r, K], B [N, r] with r >= 1");
+    const int64_t r = A[i].size(0);
+    TORCH_CHECK(A[i].size(1) == K && B[i].size(0) == N && B[i].size(1) == r, "thinkdiff_hip::lora_merge_: pair ", i, ": A ", A[i].sizes(), " / B ", B[i].sizes(),
+                " do not fit w ", w.sizes());
+    check_vec(A[i], "A", w, r * K); check_vec(B[i], "B", w, N * r);
+    packed.push_back(at::empty({(int64_t)td_lora_packed_bytes((int)r, (int)N, (int)K)}, w.options().dtype(at::kByte)));
+    ok(td_lora_pack_bf16(A[i].data_ptr(), B[i].data_ptr(), (int)r, (int)N, (int)K, packed.back().data_ptr(), stream_of(w)));
+    ptrs.push_back(packed.back().data_ptr()); ranks.push_back((int)r); sc.push_back((float)scales[i]);
+  }
+  ok(td_lora_merge_bf16(w.data_ptr(), w.data_ptr(), (int)N, (int)K, (int)ptrs.size(), ptrs.data(), ranks.data(), sc.data(), stream_of(w)));
+  return w;
+}
+// attach one pair to a Linear of the engine (td_flux_lora_load): A [r, K], B [N, r] against the [N, K] td_flux_param_shape reports
+void flux_lora_load(int64_t engine, std::string adapter, std::string param, const at::Tensor& A, const at::Tensor& B, double scale) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  td_flux* f = (td_flux*)(uintptr_t)engine;
+  int64_t N = 0, K = 0;
+  ok(td_flux_param_shape(f, param.c_str(), &N, &K));
+  check_rows(A, "A"); check_rows(B, "B"); same_device(B, "B", A);
+  TORCH_CHECK(K > 1, "thinkdiff_hip::flux_lora_load: '", param, "' is not the weight of a Linear (", N, " elements, 1-D): bias and norm-scale deltas are not built");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.size(0) >= 1 && A.size(1) == K && B.size(0) == N && B.size(1) == A.size(0),
+              "thinkdiff_hip::flux_lora_load: '", param, "' is [", N, ", ", K, "]: lora_A must be [r, ", K, "] and lora_B [", N, ", r], got ", A.sizes(), " / ", B.sizes());
+  check_vec(A, "A", A, A.size(0) * K); check_vec(B, "B", A, N * A.size(0));
+  DeviceGuard guard(A.device());
+  ok(td_flux_lora_load(f, adapter.c_str(), param.c_str(), A.data_ptr(), B.data_ptr(), (int)A.size(0), (float)scale, stream_of(A)));
+}
+// The three ops below carry no tensor argument for the dispatcher to pick a backend from, so they are registered for every backend; they touch only
+// the engine (device memory it owns, on the current HIP device and stream) and compute nothing themselves.
+void* current_stream() { return (void*)c10::hip::getCurrentHIPStream().stream(); }
+at::Tensor flux_read_param(int64_t engine, std::string name) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  td_flux* f = (td_flux*)(uintptr_t)engine;
+  int64_t rows = 0, cols = 0;
+  ok(td_flux_param_shape(f, name.c_str(), &rows, &cols));
+  at::Tensor out = cols > 1 ? at::empty({rows, cols}, at::TensorOptions().dtype(at::kBFloat16).device(at::kCUDA))
+                            : at::empty({rows}, at::TensorOptions().dtype(at::kBFloat16).device(at::kCUDA));
+  ok(td_flux_read_param(f, name.c_str(), out.data_ptr(), out.numel(), current_stream()));
+  return out;
+}
+void flux_lora_set_adapters(int64_t engine, std::vector<std::string> names, at::ArrayRef<double> weights) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  TORCH_CHECK(names.size() == weights.size(), "thinkdiff_hip::flux_lora_set_adapters: ", names.size(), " names, ", weights.size(), " weights");
+  std::vector<const char*> np;
+  std::vector<float> wf;
+  for (size_t i = 0; i < names.size(); ++i) { np.push_back(names[i].c_str()); wf.push_back((float)weights[i]); }
+  ok(td_flux_lora_set_adapters((td_flux*)(uintptr_t)engine, np.data(), wf.data(), (int)np.size(), current_stream()));
+}
+void flux_lora_delete(int64_t engine, std::string adapter) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  if (adapter.empty()) ok(td_flux_lora_clear((td_flux*)(uintptr_t)engine, current_stream()));
+  else ok(td_flux_lora_delete((td_flux*)(uintptr_t)engine, adapter.c_str(), current_stream()));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(thinkdiff_hip, m) {
@@ -477,6 +574,12 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("vae_encode_moments_masked(int engine, Tensor image, Tensor mask, int H, int W) -> Tensor");
   m.def("flux_fill_condition(Tensor moments, Tensor? eps, Tensor mask, float scaling_factor, float shift_factor, int H, int W) -> Tensor");
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
+  m.def("lora_merge(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor");
+  m.def("lora_merge_(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)");
+  m.def("flux_read_param(int engine, str name) -> Tensor");
+  m.def("flux_lora_load(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()");
+  m.def("flux_lora_set_adapters(int engine, str[] names, float[] weights) -> ()");
+  m.def("flux_lora_delete(int engine, str adapter) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -507,4 +610,13 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_denoise_cfg_", &flux_denoise_cfg_);
   m.impl("vae_encode_moments_masked", &vae_encode_moments_masked);
   m.impl("flux_fill_condition", &flux_fill_condition);
+  m.impl("lora_merge", &lora_merge);
+  m.impl("lora_merge_", &lora_merge_);
+  m.impl("flux_lora_load", &flux_lora_load);
+}
+
+TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {
+  m.impl("flux_read_param", &flux_read_param);
+  m.impl("flux_lora_set_adapters", &flux_lora_set_adapters);
+  m.impl("flux_lora_delete", &flux_lora_delete);
 }

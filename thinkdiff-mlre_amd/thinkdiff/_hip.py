@@ -76,6 +76,15 @@ def _declare(L):
         "td_vae_encode_masked": [vp, vp, i32, vp, i32, i32, i32, vp, vp],
         "td_vae_image_to_nhwc_masked_bf16": [vp, i32, vp, i32, i32, i32, vp, i32, vp],
         "td_vae_output_shape": [vp, i32, i32, vp, vp, vp],
+        "td_lora_pack_bf16": [vp, vp, i32, i32, i32, vp, vp],
+        "td_lora_merge_bf16": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
+        "td_flux_read_param": [vp, ctypes.c_char_p, vp, i64, vp],
+        "td_flux_param_shape": [vp, ctypes.c_char_p, vp, vp],
+        "td_flux_lora_load": [vp, ctypes.c_char_p, ctypes.c_char_p, vp, vp, i32, f32, vp],
+        "td_flux_lora_set_adapters": [vp, vp, vp, i32, vp],
+        "td_flux_lora_delete": [vp, ctypes.c_char_p, vp],
+        "td_flux_lora_clear": [vp, vp],
+        "td_flux_lora_info": [vp, vp, vp, vp],
         "td_flux_fork": [vp, vp],
         "td_flux_denoise_multi": [vp, vp, i32, vp, i32, vp],
         "td_flux_denoise_multi_inpaint": [vp, vp, i32, vp, i32, vp, vp, vp, vp],
@@ -171,6 +180,8 @@ def _declare(L):
     L.td_qwen2_destroy.restype = None
     L.td_flux_param_elems.argtypes = [vp]
     L.td_flux_param_elems.restype = ctypes.c_int64
+    L.td_lora_packed_bytes.argtypes = [i32, i32, i32]
+    L.td_lora_packed_bytes.restype = ctypes.c_size_t
     return sig
 
 

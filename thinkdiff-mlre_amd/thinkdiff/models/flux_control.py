@@ -21,7 +21,9 @@ B = prompts x num_images_per_prompt, h = H/8, w = W/8, C = 16, S = (H/16)(W/16);
   as in the other pipelines.
 
 Refused, not approximated (NotImplementedError): `callback_on_step_end`, custom `sigmas`, lists of generators,
-`joint_attention_kwargs` (LoRA scale -- FLUX.1 Canny / Depth LoRA checkpoints are not loaded; the full 128-channel ones are).  The
+`joint_attention_kwargs` (the per-call LoRA scale: adapters loaded with `load_lora_weights` are merged into the weights, so set their
+weights with `set_adapters(names, weights)`; the FLUX.1 Canny / Depth *LoRA* checkpoints, which widen `x_embedder`, are refused by the
+loader -- the full 128-channel ones load).  The
 ControlNet side network is a different model and is not this pipeline.  A transformer with other channel counts is refused with
 both numbers named.
 """

@@ -28,7 +28,8 @@ check.  B = prompts x num_images_per_prompt, h = H/8, w = W/8, C = 16, S = (H/16
   with the input.  Output: `_finish` as in the other pipelines.
 
 Refused, not approximated (NotImplementedError): `callback_on_step_end`, custom `sigmas`, lists of generators,
-`joint_attention_kwargs` (LoRA scale).  A transformer with other channel counts is refused with both numbers named.
+`joint_attention_kwargs` (the per-call LoRA scale: adapters loaded with `load_lora_weights` are merged into the weights, so set their
+weights with `set_adapters(names, weights)` before the call).  A transformer with other channel counts is refused with both numbers named.
 """
 from typing import Optional
 

@@ -97,6 +97,7 @@ class FluxImg2ImgPipelineRewritePrompt(FluxPipelineRewritePrompt):
                  width: Optional[int] = None, num_inference_steps: int = 28, guidance_scale: float = 7.0,
                  num_images_per_prompt: int = 1, generator=None, latents=None, prompt_embeds=None, pooled_prompt_embeds=None,
                  output_type: str = "pil", return_dict: bool = True, max_sequence_length: int = 512, **_ignored):
+        self._refuse_call_scale(_ignored)      # (a per-call LoRA scale while adapters are loaded: set_adapters(names, weights) instead)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         t_start = get_timesteps(num_inference_steps, strength)

@@ -90,6 +90,7 @@ class FluxInpaintPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
                  width: Optional[int] = None, padding_mask_crop: Optional[int] = None, strength: float = 0.6, num_inference_steps: int = 28,
                  guidance_scale: float = 7.0, num_images_per_prompt: int = 1, generator=None, latents=None, prompt_embeds=None,
                  pooled_prompt_embeds=None, output_type: str = "pil", return_dict: bool = True, max_sequence_length: int = 512, **kw):
+        self._refuse_call_scale(kw)      # (a per-call LoRA scale while adapters are loaded: set_adapters(names, weights) instead)
         if padding_mask_crop is not None:
             raise NotImplementedError("padding_mask_crop (crop region, resize_mode='fill', apply_overlay) is not supported")
         for name in ("callback_on_step_end", "sigmas"):

@@ -41,7 +41,7 @@ S_ref = (H_r/16)(W_r/16) reference tokens of the H_r x W_r reference image.
 - Output: `_finish` as in the other pipelines.
 
 Refused, not approximated (NotImplementedError, before any device call): `callback_on_step_end`, custom `sigmas`, lists of
-generators, `joint_attention_kwargs`, the IP-adapter arguments, a list of reference images per sample.  A keyword that is neither in the
+generators, `joint_attention_kwargs` (a LoRA's weight is set with `set_adapters(names, weights)`), the IP-adapter arguments, a list of reference images per sample.  A keyword that is neither in the
 call surface nor one of those is a TypeError (a misspelt `negative_prompt` must not run the plain loop silently).  A transformer that is not
 64 / 64 is refused with both numbers named; an image stream S + S_ref beyond the transformer's `max_img_tokens` is refused with the
 numbers and the constructor argument to raise (the default 4096 holds a 1024 x 1024 output alone; with a 1024 x 1024 reference

@@ -106,6 +106,63 @@ class FluxPipelineRewritePrompt:
         vae = AutoencoderKLDecoder().init_random(seed + 1) if with_vae else None
         return cls(transformer=FluxTransformer2DModel(config, **kw).init_random(seed), vae=vae)
 
+    # ---- LoRA ([ext] diffusers FluxLoraLoaderMixin) ------------------------------------------------------
+    # On this engine adapters are ALWAYS merged into the transformer's weights, recomputed from an untouched base copy whenever the set or
+    # its weights change (FluxTransformer2DModel.load_lora_adapter / set_adapters; include/thinkdiff_hip.h td_flux_lora_*): the denoise loop
+    # is the same code at the same rate, in every precision, and forked contexts need nothing (they share the weights).  The per-call
+    # `joint_attention_kwargs={"scale": s}` is not built: use set_adapters(names, weights).
+    def load_lora_weights(self, path_or_dict, weight_name: Optional[str] = None, adapter_name: Optional[str] = None, alpha=None, **_ignored):
+        """A local .safetensors file, a directory (+ weight_name, default pytorch_lora_weights.safetensors) or a state dict in the diffusers /
+        peft format (thinkdiff.models.flux_lora); no hub.  Transformer adapters only.  The adapter becomes active at weight 1.0 beside those
+        already active; alpha= overrides the file's alphas (a number or a dict per module)."""
+        if adapter_name is None:
+            have, i = set(self.transformer.list_adapters()), 0
+            while f"default_{i}" in have:
+                i += 1
+            adapter_name = f"default_{i}"
+        self._fuse_scale = None      # a new active set: fuse_lora's factor belongs to the old one
+        self.transformer.load_lora_adapter(path_or_dict, adapter_name=adapter_name, alpha=alpha, weight_name=weight_name)
+        return adapter_name
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self._fuse_scale = None
+        self.transformer.set_adapters(adapter_names, adapter_weights)
+
+    def get_active_adapters(self) -> List[str]:
+        return list(self.transformer.active_adapters())
+
+    def get_list_adapters(self):
+        return {"transformer": self.transformer.list_adapters()}
+
+    def delete_adapters(self, adapter_names):
+        self.transformer.delete_adapters(adapter_names)
+
+    def unload_lora_weights(self):
+        self._fuse_scale = None
+        self.transformer.unload_lora()
+
+    def fuse_lora(self, lora_scale: float = 1.0, **_ignored):
+        """Adapters are merged at all times here; fuse_lora(s) multiplies the active adapters' weights by s until unfuse_lora()."""
+        if getattr(self, "_fuse_scale", None) is not None:
+            raise ValueError("fuse_lora: already fused (unfuse_lora first)")
+        active = self.transformer.active_adapters()
+        self._fuse_scale = (float(lora_scale), dict(active))
+        if active and float(lora_scale) != 1.0:
+            self.transformer.set_adapters(list(active), [w * float(lora_scale) for w in active.values()])
+
+    def unfuse_lora(self, **_ignored):
+        """Restores the weights the active adapters had before fuse_lora (the merge is recomputed from the base copy: nothing drifts)."""
+        fused, self._fuse_scale = getattr(self, "_fuse_scale", None), None
+        if fused is not None and fused[1] and fused[0] != 1.0:
+            self.transformer.set_adapters(list(fused[1]), list(fused[1].values()))
+
+    def _refuse_call_scale(self, kwargs):
+        """The text-to-image / img2img / inpaint calls swallow unknown keywords; with adapters loaded a per-call LoRA scale must not vanish."""
+        jak = kwargs.get("joint_attention_kwargs")
+        if jak and "scale" in jak and self.transformer is not None and self.transformer.list_adapters():
+            raise NotImplementedError("joint_attention_kwargs={'scale': ...} (a per-call LoRA scale) is not built: adapters are merged into the "
+                                      "weights; use set_adapters(names, weights) before the call")
+
     def to(self, *_a, **_k):
         return self  # the engine lives on the GPU it was created on
 
@@ -181,6 +238,7 @@ class FluxPipelineRewritePrompt:
                  num_inference_steps: int = 28, guidance_scale: float = 3.5, num_images_per_prompt: int = 1,
                  generator=None, latents=None, prompt_embeds=None, pooled_prompt_embeds=None,
                  output_type: str = "pil", return_dict: bool = True, max_sequence_length: int = 512, **_ignored):
+        self._refuse_call_scale(_ignored)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         if prompt is None and prompt_embeds is None:

@@ -167,6 +167,126 @@ class FluxTransformer2DModel:
             raise KeyError(f"checkpoint at {root} lacks {len(missing)} tensors, e.g. {missing[:3]}")
         return model
 
+    # ---- LoRA adapters (td_flux_lora_*: always merged, recomputed from a base copy) ----------------------
+    def linear_shapes(self) -> Dict[str, tuple]:
+        """{`<module>.weight`: (out_features, in_features)} of every Linear (the parameters an adapter may target)."""
+        out = {}
+        rows, cols = ctypes.c_int64(), ctypes.c_int64()
+        for name in self.param_table():
+            _hip.check(self._L.td_flux_param_shape(self._h, name.encode(), ctypes.byref(rows), ctypes.byref(cols)))
+            if name.endswith(".weight") and cols.value > 1:
+                out[name] = (rows.value, cols.value)
+        return out
+
+    def read_param(self, name: str) -> torch.Tensor:
+        """The parameter as the forward sees it now (base + merged adapters): a new device tensor, [N, K] for a Linear's weight."""
+        with torch.cuda.device(self.device):
+            return _OPS.flux_read_param(int(self._root()._h.value), name)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """Effective weights under the diffusers names (what `transformer.state_dict()` is after diffusers' fuse_lora)."""
+        return {name: self.read_param(name) for name in self.param_table()}
+
+    def _root(self) -> "FluxTransformer2DModel":
+        return getattr(self, "_parent", None) or self
+
+    def _lora_state(self) -> dict:
+        r = self._root()
+        if not hasattr(r, "_lora_active"):
+            r._lora_loaded, r._lora_active = [], {}      # names in load order; {name: weight} of the active set
+        return r.__dict__
+
+    def _apply_adapters(self):
+        st = self._lora_state()
+        names = [n for n in st["_lora_loaded"] if n in st["_lora_active"]]
+        with torch.cuda.device(self.device):
+            _OPS.flux_lora_set_adapters(int(self._root()._h.value), names, [float(st["_lora_active"][n]) for n in names])
+        # (in an 8-bit mode the engine has quantised the merged weights again under the precision settings it holds)
+
+    def load_lora_adapter(self, sd_or_path, adapter_name: str = "default", alpha=None, weight_name: Optional[str] = None):
+        """diffusers' `transformer.load_lora_adapter`: parse (thinkdiff.models.flux_lora), copy every pair into the engine, then activate the
+        adapter at weight 1.0 together with those already active.  sd_or_path: a state dict, a local .safetensors file, or a directory
+        (+ weight_name)."""
+        from . import flux_lora
+        if getattr(self, "_parent", None) is not None:
+            raise _hip.ThinkDiffHipError("load_lora_adapter: adapters belong to the parent transformer (forks share its weights)")
+        st = self._lora_state()
+        if adapter_name in st["_lora_loaded"]:
+            raise ValueError(f"adapter {adapter_name!r} is already loaded (delete_adapters first, or pick another adapter_name)")
+        metadata = None
+        if not isinstance(sd_or_path, dict):
+            sd_or_path, metadata = flux_lora.read_lora_file(str(sd_or_path), weight_name)
+        pairs = flux_lora.parse_lora_state_dict(sd_or_path, metadata, alpha, self.linear_shapes())
+        h = int(self._h.value)
+        try:
+            with torch.cuda.device(self.device):
+                for name, (A, B, scale) in pairs.items():
+                    a = A.to(self.device, torch.bfloat16).contiguous()
+                    b = B.to(self.device, torch.bfloat16).contiguous()
+                    _OPS.flux_lora_load(h, adapter_name, name, a, b, float(scale))
+                torch.cuda.current_stream().synchronize()      # `a` / `b` may be temporaries
+        except Exception:
+            try:
+                _OPS.flux_lora_delete(h, adapter_name)      # no half-loaded adapter stays behind
+            except RuntimeError:
+                pass
+            raise
+        st["_lora_loaded"].append(adapter_name)
+        st["_lora_active"][adapter_name] = 1.0
+        self._apply_adapters()
+        return sorted(pairs)
+
+    def set_adapters(self, names, weights=None):
+        """diffusers' set_adapters: the active set and its weights (default 1.0 each); every touched parameter is recomputed from its base."""
+        st = self._lora_state()
+        names = [names] if isinstance(names, str) else list(names)
+        if weights is None:
+            weights = [1.0] * len(names)
+        elif isinstance(weights, (int, float)):
+            weights = [float(weights)] * len(names)
+        weights = list(weights)
+        if len(weights) != len(names):
+            raise ValueError(f"set_adapters: {len(names)} adapter names, {len(weights)} weights")
+        for n in names:
+            if n not in st["_lora_loaded"]:
+                raise ValueError(f"set_adapters: unknown adapter {n!r} (loaded: {st['_lora_loaded']})")
+        for w in weights:
+            if not isinstance(w, (int, float)):
+                raise ValueError("set_adapters: per-block weight dicts are not built; one number per adapter")
+        st["_lora_active"] = {n: float(w) for n, w in zip(names, weights)}
+        self._apply_adapters()
+
+    def delete_adapters(self, names):
+        st = self._lora_state()
+        names = [names] if isinstance(names, str) else list(names)
+        for n in names:
+            if n not in st["_lora_loaded"]:
+                raise ValueError(f"delete_adapters: unknown adapter {n!r} (loaded: {st['_lora_loaded']})")
+        with torch.cuda.device(self.device):
+            for n in names:
+                _OPS.flux_lora_delete(int(self._root()._h.value), n)
+                st["_lora_loaded"].remove(n)
+                st["_lora_active"].pop(n, None)
+
+    def unload_lora(self):
+        """diffusers' unload_lora_weights: drop every adapter; each parameter gets its base bits back."""
+        st = self._lora_state()
+        with torch.cuda.device(self.device):
+            _OPS.flux_lora_delete(int(self._root()._h.value), "")
+        st["_lora_loaded"], st["_lora_active"] = [], {}
+
+    def active_adapters(self) -> Dict[str, float]:
+        st = self._lora_state()
+        return {n: st["_lora_active"][n] for n in st["_lora_loaded"] if n in st["_lora_active"]}
+
+    def list_adapters(self):
+        return list(self._lora_state()["_lora_loaded"])
+
+    def lora_info(self) -> Dict[str, int]:
+        n, p, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _hip.check(self._L.td_flux_lora_info(self._h, ctypes.byref(n), ctypes.byref(p), ctypes.byref(b)))
+        return {"adapters": n.value, "params_touched": p.value, "bytes_held": b.value}
+
     def init_random(self, seed: int = 0, std: float = 0.02):
         """Synthetic full-shape checkpoint generated on the device (throughput runs)."""
         _hip.check(self._L.td_flux_init_random(self._h, seed, std, _hip.stream_ptr()))

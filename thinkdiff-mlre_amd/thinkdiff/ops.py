@@ -31,6 +31,10 @@ flux_denoise_inpaint_ / flux_denoise_multi_inpaint_   the inpainting denoise loo
 flux_set_reference_tokens  FluxKontextPipeline's per-step torch.cat of the reference-image latents / ids behind the latents, once per image
 flux_cfg_step_             true classifier-free guidance (neg + scale * (pos - neg)) + scheduler.step, fused, in place
 flux_denoise_cfg_          the denoise loop under true CFG: both conditionings per step on two prepared contexts, then flux_cfg_step_
+lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up to 8 pairs at once, fp32 accumulation, one rounding
+flux_lora_load / flux_lora_set_adapters / flux_lora_delete / flux_read_param   diffusers' load_lora_weights / set_adapters / delete_adapters
+                           (empty name: unload_lora_weights) on the engine's merged weights, and the effective parameter read back; the last
+                           three take no tensor, so they alone are registered for every backend (they only reach the engine handle)
 """
 import os
 
@@ -66,6 +70,12 @@ SCHEMAS = {
     "flux_cfg_step_": "(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)",
     "flux_denoise_cfg_": "(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)",
     "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
+    "lora_merge": "(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor",
+    "lora_merge_": "(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)",
+    "flux_read_param": "(int engine, str name) -> Tensor",
+    "flux_lora_load": "(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()",
+    "flux_lora_set_adapters": "(int engine, str[] names, float[] weights) -> ()",
+    "flux_lora_delete": "(int engine, str adapter) -> ()",
 }
 
 _loaded = False
