@@ -149,7 +149,7 @@ def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-6) -> torch.Tenso
     return y * w
 
 
-# fp8 operand mode (BASELINE config 5; restates csrc/flux_engine.hip td_flux_set_precision): every Linear inside the
+# fp8 operand mode (BASELINE config 5; restates csrc/flux_model.hip td_flux_set_precision): every Linear inside the
 # double-/single-stream blocks except the adaLN modulation linears takes OCP e4m3 operands -- weights quantised per output
 # channel, activations per token, both with scale = max|.| / 448 -- accumulates exactly, dequantises, adds the bias and
 # rounds once to the working dtype.  Off by default: the reference itself has no fp8 path.
