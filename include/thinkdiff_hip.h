@@ -176,6 +176,13 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
  *   d = bf16(v_pos - v_neg);  m = bf16(scale * float(d));  v = bf16(v_neg + m);  x = bf16(float(x) + float(bf16(bf16(dt) * float(v))))
  * All operands bf16 [n], 16-byte aligned, n % 8 == 0, v_pos / v_neg not overlapping x. */
 int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream);
+/* FLUX ControlNet residual injection, in place on h ([ext] diffusers >= 0.30 controlnet_flux.py `sample * conditioning_scale`, transformer_flux.py
+ * `hidden_states = hidden_states + controlnet_block_samples[...]`), every op a bf16 torch op; `scale` is a Python float there, an fp32 operand of the
+ * bf16 multiply as in td_flux_cfg_step_bf16:
+ *   h[m, j] = bf16(float(h[m, j]) + float(bf16(scale * float(r[m, j]))))        m < rows, j < D
+ * h, r bf16 with row strides ldh, ldr >= D (elements; columns beyond D are untouched); D % 8 == 0, strides multiples of 8, both pointers 16-byte
+ * aligned, r not overlapping h. */
+int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream);
 #define TD_INPAINT_MASK_U8_HW 0   /* uint8 [H, W] (PIL mode "L") */
 #define TD_INPAINT_MASK_F32_HW 1  /* float32 [H, W] in [0, 1] */
 /* FluxInpaintPipeline's mask latents from a height x width mask (format TD_INPAINT_MASK_*):
@@ -332,6 +339,40 @@ int td_flux_reference_tokens(const td_flux* f, int* S_ref);
 /* velocity[S_img,out_channels] = transformer(latents[S_img,out_channels]; prepared step).  On a conditioned engine the latents are gathered
  * beside the channel condition and x_embedder runs as ONE Linear over in_channels, as on torch.cat([latents, cond]). */
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream);
+/* ---- FLUX ControlNet (td_abi_version() >= 4): a side network of the same double- / single-stream blocks with its own weights
+ * ([ext] diffusers >= 0.30 FluxControlNetModel: InstantX FLUX.1-dev-Controlnet-Canny / -Union, Shakker Union-Pro).  TdFluxConfig describes it as it
+ * describes a transformer (num_layers = n_d >= 1, num_single_layers = n_s >= 0, guidance_embeds as the checkpoint has it, out_channels 0); the
+ * struct itself is unchanged, the kind and num_mode travel as arguments.  Parameters: the transformer's without norm_out / proj_out, plus
+ * controlnet_x_embedder, controlnet_blocks.{i}, controlnet_single_blocks.{i} (weight + bias) and, with num_mode > 0 ("union" checkpoints),
+ * controlnet_mode_embedder.weight [num_mode, D].  The handle is a td_flux: parameters, td_flux_fork, td_flux_set_condition, td_flux_set_timesteps
+ * and td_flux_destroy are the transformer's.  It runs in bf16 only: td_flux_set_precision / td_flux_set_attention to an 8-bit mode and
+ * td_flux_lora_load are TD_ERR_INVALID on it (the main transformer may be in any mode); td_flux_forward on it is TD_ERR_INVALID. */
+int td_flux_controlnet_create(const TdFluxConfig* cfg, int num_mode, int max_img_tokens, int max_txt_tokens, int max_steps, td_flux** out);
+/* Union models: the control mode, before td_flux_set_condition -- which then prepends controlnet_mode_embedder[mode] to the embedded prompt and
+ * duplicates the first txt id (T + 1 text rows; td_flux_prepared_shape reports them) and is TD_ERR_INVALID with none set.  -1 clears.  Per context. */
+int td_flux_controlnet_set_mode(td_flux* cn, int mode);
+/* The control image of one image: control_latents bf16 [S_img, in_channels] (VAE latents, shifted / scaled, packed), 16-byte aligned, after
+ * td_flux_set_condition.  Computes E = controlnet_x_embedder(control_latents) once; every forward adds it to x_embedder(latents) (each Linear's
+ * output rounds to bf16, then the sum).  td_flux_set_condition with another S_img invalidates it. */
+int td_flux_controlnet_set_condition(td_flux* cn, const void* control_latents, void* stream);
+/* One ControlNet evaluation at a prepared step: behind block i the i-th output Linear writes controlnet_blocks[i](image stream) /
+ * controlnet_single_blocks[i](image rows) into the context's sample arena, UNSCALED. */
+int td_flux_controlnet_forward(td_flux* cn, const void* latents, int step, void* stream);
+/* The sample arena of the last forward: sample k (double-block samples first, n_double + n_single in all) is bf16 [rows, width] contiguous at
+ * base + k * stride_elems.  Any out pointer may be NULL. */
+int td_flux_controlnet_samples(const td_flux* cn, void** base, int* n_double, int* n_single, int64_t* stride_elems, int* rows, int* width);
+/* Copy sample k of the last forward into dst, bf16 [rows, width] contiguous (stream-ordered). */
+int td_flux_controlnet_read_sample(const td_flux* cn, int k, void* dst, void* stream);
+/* Attach ONE ControlNet context to a main context (NULL detaches); a ControlNet context serves one main context at a time (forks pair up: one
+ * ControlNet fork per main context).  From then on td_flux_forward -- and with it every td_flux_denoise* loop -- at a step whose scale is not 0
+ * first runs the ControlNet on the same latents, step and stream, then adds   bf16(scale * sample[i / ceil(n_blocks / n_samples)])   to the image
+ * rows behind double block i, and likewise behind single block i (td_flux_residual_inject_bf16; trailing samples the index never reaches are
+ * unused; n_s = 0: no single-block injection).  A step with scale 0, and a context with nothing attached, issue the plain forward's launches.
+ * Forward-time TD_ERR_INVALID: inner width, heads or latent width differ; the ControlNet context is prepared for another S_img or step count, or
+ * holds no control condition; reference tokens are set; the main engine is channel-conditioned.  Attaching resets the scales to 1.0. */
+int td_flux_attach_controlnet(td_flux* f, td_flux* cn);
+/* conditioning scale per prepared step (n host floats; steps beyond n keep 1.0): controlnet_conditioning_scale x controlnet_keep[i]. */
+int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n);
 /* Per-launch HIP-event trace of the engine's kernels (events recorded on the launch stream).
  * categories: 0 GEMM 256x256 tile (td_gemm_bf16_nt_kernel<8,4>), 1 small GEMM tiles, 2 attention,
  * 3 LayerNorm+modulate, 4 QK-RMSNorm+RoPE, 5 GEMM 288x192 tile (<9,3>).  trace_end synchronises and

@@ -16,7 +16,8 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 3; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param
+int td_abi_version(void) { return 4; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+                                            // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -191,6 +192,10 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
                               float sigma_next, int64_t n, void* stream) {
   return td_flux_inpaint_step_launch((bf16_t*)x, (const bf16_t*)v, (const bf16_t*)image_latents, (const bf16_t*)noise, (const bf16_t*)mask, dt,
                                      sigma_next, n, (hipStream_t)stream);
+}
+int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream) {
+  TD_CHECK_ARG(ldh >= 0 && ldh < (1ll << 31) && ldr >= 0 && ldr < (1ll << 31), "td_flux_residual_inject: ldh=%lld / ldr=%lld outside the 32-bit range", (long long)ldh, (long long)ldr);
+  return td_flux_residual_inject_launch((bf16_t*)h, (int)ldh, (const bf16_t*)r, (int)ldr, rows, D, scale, (hipStream_t)stream);
 }
 int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream) {
   return td_flux_cfg_step_launch((bf16_t*)x, (const bf16_t*)v_pos, (const bf16_t*)v_neg, scale, dt, n, (hipStream_t)stream);

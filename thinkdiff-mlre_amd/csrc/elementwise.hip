@@ -479,6 +479,41 @@ int td_copy_cols_launch(const bf16_t* src, int lds, bf16_t* dst, int ldd, int ro
   return 0;
 }
 
+// FLUX ControlNet residual injection [ext diffusers >= 0.30 controlnet_flux.py, transformer_flux.py]:
+//   sample = controlnet_block(block_sample) * conditioning_scale          (side network, once per block output)
+//   hidden_states = hidden_states + sample                                (main transformer, behind every block)
+// on bf16 tensors with `conditioning_scale` a Python float: as in td_flux_cfg_step_kernel the scalar stays an fp32 operand of the bf16
+// multiply, the product rounds to bf16, then the sum rounds:
+//   h[m, j] = bf16(float(h[m, j]) + float(bf16(scale * float(r[m, j]))))
+// Two bf16 streams in, one out, 16 B per lane; in place on h; rows of D columns at strides ldh / ldr (the image rows of the joint buffer).
+__global__ void td_flux_residual_inject_kernel(bf16_t* h, int ldh, const bf16_t* r, int ldr, int rows, int chunks, float scale) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * chunks) return;
+  const int m = idx / chunks, c = idx - m * chunks;
+  bf16_t* hp = h + (size_t)m * ldh + c * 8;
+  float a[8], b[8];
+  unpack8(*(const u32x4_t*)hp, a);
+  unpack8(*(const u32x4_t*)(r + (size_t)m * ldr + c * 8), b);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = a[i] + rbf(scale * b[i]);   // rbf() between the product and the sum: nothing to contract into an fma
+  *(u32x4_t*)hp = pack8(a);
+}
+
+int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr, int rows, int D, float scale, hipStream_t stream) {
+  TD_CHECK_ARG(h && r, "td_flux_residual_inject: null argument");
+  TD_CHECK_ARG(rows > 0 && D > 0 && D % 8 == 0, "td_flux_residual_inject: rows=%d, D=%d: D must be a positive multiple of 8, rows positive", rows, D);
+  TD_CHECK_ARG(ldh % 8 == 0 && ldr % 8 == 0 && ldh >= D && ldr >= D, "td_flux_residual_inject: ldh=%d, ldr=%d must be multiples of 8 and at least D=%d", ldh, ldr, D);
+  TD_CHECK_ARG(((uintptr_t)h | (uintptr_t)r) % 16 == 0, "td_flux_residual_inject: both buffers must be 16-byte aligned");
+  // the extents the rows span: (rows - 1) strides and one row
+  const uintptr_t h0 = (uintptr_t)h, h1 = h0 + ((uintptr_t)(rows - 1) * ldh + D) * sizeof(bf16_t);
+  const uintptr_t r0 = (uintptr_t)r, r1 = r0 + ((uintptr_t)(rows - 1) * ldr + D) * sizeof(bf16_t);
+  TD_CHECK_ARG(r0 >= h1 || r1 <= h0, "td_flux_residual_inject: r must not overlap h (updated in place)");
+  TD_GRID_1D_I32(nblk, (long long)rows * (D / 8), 256, "td_flux_residual_inject");
+  hipLaunchKernelGGL(td_flux_residual_inject_kernel, dim3(nblk), dim3(256), 0, stream, h, ldh, r, ldr, rows, D / 8, scale);
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream) {
   TD_CHECK_ARG(n > 0 && n % 8 == 0, "td_euler_step: n=%lld must be a positive multiple of 8", n);
   TD_GRID_1D_I32(nblk, n / 8, 256, "td_euler_step");

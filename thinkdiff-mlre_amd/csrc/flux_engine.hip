@@ -24,7 +24,11 @@
 // Files: csrc/flux_model.h holds the two structures -- FluxModel (weights, numeric configuration, LoRA registry; shared) and td_flux (one
 // image's context: workspace, conditioning, schedule, history, trace).  csrc/flux_model.hip holds everything that touches only the model;
 // this file holds everything that runs on a context: create / fork / destroy, conditioning, schedule, the forward, the denoise loops, the trace.
+// A ControlNet side network (td_flux_controlnet_*) is a second KIND of model run by the same block loop (run_blocks): its contexts keep block
+// samples, and a main context with one attached adds them behind its own blocks (td_flux_attach_controlnet, td_flux_residual_inject_bf16).
+#include <cmath>
 #include <cstring>
+#include <functional>
 
 #include "flux_model.h"
 
@@ -79,10 +83,12 @@ struct Epilogue {
   int act = TD_ACT_NONE;
   const bf16_t *gate = nullptr, *gate_ctx = nullptr;      // per output channel; a pair launch: of the image / of the text stream
   bool residual = false;                                  // y += c (in place)
+  const bf16_t* res = nullptr; int ldr = 0;               // y += res (another buffer; same rounding points: the Linear's output rounds, then the sum)
   bf16_t* c2 = nullptr; int ldc2 = 0, act2 = TD_ACT_NONE, n_split = 0;      // output columns >= n_split go to c2 under act2
   const Q8Out* q8 = nullptr;                              // 8-bit form only
   static Epilogue to(bf16_t* c, int ldc, int act = TD_ACT_NONE) { Epilogue o; o.c = c; o.ldc = ldc; o.act = act; return o; }
   Epilogue& gated_residual(const bf16_t* g, const bf16_t* g_ctx = nullptr) { gate = g; gate_ctx = g_ctx; residual = true; return *this; }
+  Epilogue& plus(const bf16_t* r, int ld) { res = r; ldr = ld; return *this; }
   Epilogue& split(int n, bf16_t* c2_, int ldc2_, int act2_) { n_split = n; c2 = c2_; ldc2 = ldc2_; act2 = act2_; return *this; }
   Epilogue& int8_out(const Q8Out* q) { q8 = q; return *this; }
 };
@@ -94,6 +100,7 @@ int linear(td_flux* f, hipStream_t s, const FluxLinear& l, const Rows& a, int ro
   p.M = rows; p.N = l.N; p.bias = l.b;
   p.C = o.c; p.ldc = o.ldc; p.act = o.act; p.gate = o.gate;
   if (o.residual) { p.res = o.c; p.ldr = o.ldc; }
+  else if (o.res) { p.res = o.res; p.ldr = o.ldr; }
   p.C2 = o.c2; p.ldc2 = o.ldc2; p.act2 = o.act2; p.n_split = o.n_split;
   if (flux_mask8(m) & l.cls) {
     p.fp8 = m->precision == TD_PRECISION_FP8_E4M3; p.i8 = m->precision == TD_PRECISION_INT8;
@@ -197,7 +204,7 @@ int alloc_workspace(td_flux* f) {
   const FluxModel* m = f->m;
   const TdFluxConfig* cfg = &m->cfg;
   const int64_t D = m->D, M = m->M;
-  const int max_img_tokens = m->max_img, max_txt_tokens = m->max_txt;
+  const int max_img_tokens = m->max_img, max_txt_tokens = m->max_txt + (m->num_mode > 0 ? 1 : 0);      // (a union ControlNet prepends its mode row)
   const int64_t S = (int64_t)max_img_tokens + max_txt_tokens;
   const int64_t n = m->max_steps;
   struct Req { void** p; int64_t bytes; };
@@ -207,6 +214,8 @@ int alloc_workspace(td_flux* f) {
       {(void**)&f->ctx, (int64_t)max_txt_tokens * D * 2}, {(void**)&f->vout, (int64_t)max_img_tokens * m->Cout * 2},
       {(void**)&f->xin, m->Ccond > 0 ? (int64_t)max_img_tokens * m->Cin * 2 : 0},
       {(void**)&f->xref, m->Ccond == 0 ? (int64_t)max_img_tokens * m->Cout * 2 : 0},
+      {(void**)&f->cn_E, m->controlnet ? (int64_t)max_img_tokens * D * 2 : 0},
+      {(void**)&f->cn_samples, m->controlnet ? (int64_t)(cfg->num_layers + cfg->num_single_layers) * max_img_tokens * D * 2 : 0},
       {(void**)&f->tproj, n * 256 * 2}, {(void**)&f->tmid, n * D * 2}, {(void**)&f->te, n * D * 2},
       {(void**)&f->gproj, 256 * 2}, {(void**)&f->gmid, (int64_t)D * 2}, {(void**)&f->ge, (int64_t)D * 2},
       {(void**)&f->pmid, (int64_t)D * 2}, {(void**)&f->pe, (int64_t)D * 2},
@@ -261,7 +270,19 @@ extern "C" {
 int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_tokens, int max_steps, td_flux** out) {
   TD_CHECK_ARG(cfg && out, "td_flux_create: null argument");
   FluxModel* m = nullptr;
-  TD_TRY(flux_model_create(cfg, max_img_tokens, max_txt_tokens, max_steps, &m));
+  TD_TRY(flux_model_create(cfg, 0, 0, max_img_tokens, max_txt_tokens, max_steps, &m));
+  const int rc = new_context(m, true, out);
+  if (rc != TD_OK) flux_model_destroy(m);
+  return rc;
+}
+
+// A ControlNet side network ([ext] diffusers FluxControlNetModel): a second, shallower model of the same blocks with its own weights.  Its
+// contexts are prepared like any (td_flux_set_condition / td_flux_set_timesteps, td_flux_fork), take the control image's latents through
+// td_flux_controlnet_set_condition, and serve ONE main context each through td_flux_attach_controlnet.
+int td_flux_controlnet_create(const TdFluxConfig* cfg, int num_mode, int max_img_tokens, int max_txt_tokens, int max_steps, td_flux** out) {
+  TD_CHECK_ARG(cfg && out, "td_flux_controlnet_create: null argument");
+  FluxModel* m = nullptr;
+  TD_TRY(flux_model_create(cfg, 1, num_mode, max_img_tokens, max_txt_tokens, max_steps, &m));
   const int rc = new_context(m, true, out);
   if (rc != TD_OK) flux_model_destroy(m);
   return rc;
@@ -271,6 +292,8 @@ int td_flux_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_toke
 void td_flux_destroy(td_flux* f) {
   if (!f) return;
   for (hipEvent_t ev : f->ev_pool) (void)hipEventDestroy(ev);
+  if (f->cn) f->cn->cn_owner = nullptr;            // either end of an attachment may go first
+  if (f->cn_owner) f->cn_owner->cn = nullptr;
   if (f->root) flux_model_destroy(f->m);
   (void)hipFree(f->ws);
   delete f;
@@ -293,14 +316,26 @@ int td_flux_set_condition(td_flux* f, const void* prompt_embeds, int T, const vo
                "td_flux_set_condition: T=%d / S_img=%d exceed capacity (%d / %d)", T, S_img, m->max_txt, m->max_img);
   hipStream_t s = (hipStream_t)stream;
   const int D = m->D;
-  if (S_img != f->S_img) f->ccond_set = false;      // the channel condition was written for another token count
-  f->T = T; f->S_img = S_img;
+  // A union ControlNet ([ext] controlnet_flux.py): encoder_hidden_states = cat([controlnet_mode_embedder(mode), context_embedder(enc)]) and
+  // txt_ids = cat([txt_ids[:1], txt_ids]) -- its text stream has one row more than the caller's.
+  const int mode_rows = m->num_mode > 0 ? 1 : 0;
+  TD_CHECK_ARG(!mode_rows || f->cn_mode_id >= 0, "td_flux_set_condition: this ControlNet is a union model (num_mode=%d) and no control mode is set "
+               "(td_flux_controlnet_set_mode before the condition)", m->num_mode);
+  if (S_img != f->S_img) f->ccond_set = f->cn_cond_set = false;      // the channel / control condition was written for another token count
+  f->S_img = S_img;
   f->S_ref = 0;      // the tables below hold T + S_img rows: reference tokens are set again after the condition, for every image
-  TD_TRY(linear(f, s, m->ctx_emb, bf16_rows(prompt_embeds, m->cfg.joint_dim), T, Epilogue::to(f->ctx, D)));
+  if (mode_rows) TD_CHECK_HIP(hipMemcpyAsync(f->ctx, m->cn_mode + (size_t)f->cn_mode_id * D, (size_t)D * 2, hipMemcpyDeviceToDevice, s));
+  TD_TRY(linear(f, s, m->ctx_emb, bf16_rows(prompt_embeds, m->cfg.joint_dim), T, Epilogue::to(f->ctx + (size_t)mode_rows * D, D)));
   TD_TRY(linear(f, s, m->p1, bf16_rows(pooled, m->cfg.pooled_dim), 1, Epilogue::to(f->pmid, D, TD_ACT_SILU)));
   TD_TRY(linear(f, s, m->p2, bf16_rows(f->pmid, D), 1, Epilogue::to(f->pe, D)));
-  if (txt_ids) TD_CHECK_HIP(hipMemcpyAsync(f->ids, txt_ids, (size_t)T * 12, hipMemcpyDeviceToDevice, s));
-  else TD_CHECK_HIP(hipMemsetAsync(f->ids, 0, (size_t)T * 12, s));
+  if (txt_ids) {
+    if (mode_rows) TD_CHECK_HIP(hipMemcpyAsync(f->ids, txt_ids, 12, hipMemcpyDeviceToDevice, s));
+    TD_CHECK_HIP(hipMemcpyAsync(f->ids + (size_t)mode_rows * 3, txt_ids, (size_t)T * 12, hipMemcpyDeviceToDevice, s));
+  } else {
+    TD_CHECK_HIP(hipMemsetAsync(f->ids, 0, (size_t)(T + mode_rows) * 12, s));
+  }
+  T += mode_rows;
+  f->T = T;
   TD_CHECK_HIP(hipMemcpyAsync(f->ids + (size_t)T * 3, img_ids, (size_t)S_img * 12, hipMemcpyDeviceToDevice, s));
   TD_TRY(td_flux_rope_table_launch(f->ids, T + S_img, m->cfg.axes_dims, (double)m->cfg.rope_theta, f->cosT, f->sinT, s));
   f->cond_set = true;
@@ -331,6 +366,7 @@ int td_flux_set_reference_tokens(td_flux* f, const void* ref_latents, int S_ref,
   TD_CHECK_ARG(f, "td_flux_set_reference_tokens: null context");
   const FluxModel* m = f->m;
   TD_CHECK_ARG(S_ref >= 0, "td_flux_set_reference_tokens: S_ref=%d is negative", S_ref);
+  TD_CHECK_ARG(!m->controlnet, "td_flux_set_reference_tokens: S_ref=%d on a ControlNet context: a ControlNet together with reference tokens is not built", S_ref);
   TD_CHECK_ARG(m->Ccond == 0, "td_flux_set_reference_tokens: this engine is channel-conditioned (in_channels=%d, out_channels=%d); reference tokens "
                "belong to the unconditioned FLUX.1 Kontext transformer", m->Cin, m->Cout);
   TD_CHECK_ARG(f->cond_set, "td_flux_set_reference_tokens: call td_flux_set_condition first (it fixes the text and image token counts; S_ref=%d)", S_ref);
@@ -416,16 +452,25 @@ int td_flux_input_shape(const td_flux* f, int* in_channels, int* cond_channels, 
   return TD_OK;
 }
 
-// One transformer evaluation: velocity[S_img, out_channels] = FluxTransformer2DModel(latents; step).
-int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream) {
-  TD_CHECK_ARG(f && latents && velocity, "td_flux_forward: null argument");
-  TD_CHECK_ARG(f->cond_set && step >= 0 && step < f->n_steps, "td_flux_forward: step %d outside the %d prepared timesteps", step, f ? f->n_steps : 0);
+// What every forward asks of its context, whichever model kind it runs
+static int check_prepared(const char* fn, const td_flux* f, int step) {
+  TD_CHECK_ARG(f->cond_set && step >= 0 && step < f->n_steps, "%s: step %d outside the %d prepared timesteps", fn, step, f->n_steps);
+  const FluxModel* m = f->m;
+  TD_CHECK_ARG(f->cond_epoch == m->weight_epoch && f->sched_epoch == m->weight_epoch, "%s: weights changed since td_flux_set_condition / "
+               "td_flux_set_timesteps (LoRA adapters were set, deleted or cleared; both precompute values from weights): call them again on this context", fn);
+  TD_CHECK_ARG(m->Ccond == 0 || f->ccond_set, "%s: this engine reads a %d-channel condition beside the %d latent channels and none is set for "
+               "the %d image tokens (td_flux_set_channel_condition after td_flux_set_condition)", fn, m->Ccond, m->Cout, f->S_img);
+  return TD_OK;
+}
+
+// Called behind every block of the loop below -- (false, i): double block i, (true, i): single block i -- with the block's output in f->h.
+using BlockHook = std::function<int(bool single, int i)>;
+
+// The embedders and the block loop of BOTH model kinds on a prepared context (check_prepared), then -- velocity != null: the transformer -- the final
+// AdaLayerNorm and proj_out.  A ControlNet context adds E = controlnet_x_embedder(cond) in x_embedder's epilogue and stops behind the last block;
+// what it keeps of each block is its hook's business, as is what an attached ControlNet adds to the main transformer's stream.
+static int run_blocks(td_flux* f, const void* latents, int step, void* velocity, const BlockHook* hook, hipStream_t s) {
   FluxModel* const m = f->m;
-  TD_CHECK_ARG(f->cond_epoch == m->weight_epoch && f->sched_epoch == m->weight_epoch, "td_flux_forward: weights changed since td_flux_set_condition / "
-               "td_flux_set_timesteps (LoRA adapters were set, deleted or cleared; both precompute values from weights): call them again on this context");
-  TD_CHECK_ARG(m->Ccond == 0 || f->ccond_set, "td_flux_forward: this engine reads a %d-channel condition beside the %d latent channels and none is set for "
-               "the %d image tokens (td_flux_set_channel_condition after td_flux_set_condition)", m->Ccond, m->Cout, f->S_img);
-  hipStream_t s = (hipStream_t)stream;
   const Switches sw = Switches::read();
   // Si: rows of the image stream the blocks run over (latents, then the reference tokens if any); So: the rows that are a velocity
   const int D = m->D, M = m->M, T = f->T, So = f->S_img, Si = f->S_img + f->S_ref, S = f->T + Si;
@@ -448,7 +493,10 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
     TD_CHECK_HIP(hipMemcpyAsync(f->xref, latents, (size_t)So * C * 2, hipMemcpyDeviceToDevice, s));
     x_in = f->xref;
   }
-  TD_TRY(linear(f, s, m->x_emb, bf16_rows(x_in, m->Cin), Si, Epilogue::to(h_img, D)));
+  if (m->controlnet)      // h = x_embedder(hidden) + controlnet_x_embedder(cond): each Linear rounds, then the sum (E: td_flux_controlnet_set_condition)
+    TD_TRY(linear(f, s, m->x_emb, bf16_rows(x_in, m->Cin), Si, Epilogue::to(h_img, D).plus(f->cn_E, D)));
+  else
+    TD_TRY(linear(f, s, m->x_emb, bf16_rows(x_in, m->Cin), Si, Epilogue::to(h_img, D)));
 
   TdNormParams np;
   np.x = h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = S; np.D = D; np.eps = 1e-6f; np.split = T;
@@ -558,6 +606,7 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
     }
     const Rows mo{f->mlp, M, f->aq, M, ff_hist ? hm.scale : f->as_};
     TD_TRY(linear2(f, s, lin[FF2_IMG], lin[FF2_CTX], mo, T, Si, Epilogue::to(h, D).gated_residual(mi + 5 * D, mc + 5 * D)));
+    if (hook) TD_TRY((*hook)(false, i));
   }
 
   // ---- single-stream blocks -------------------------------------------------------------------------------------------------------
@@ -589,20 +638,159 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
       TD_TRY(quant_act(f, s, f->cat, D + M, all, hist_mode ? hc.amax : nullptr, sm_on ? m->sm_inv + w2.sm : nullptr));
     const Rows co{f->cat, D + M, f->aq, D + M, sg_hist ? hc.scale : f->as_};
     TD_TRY(linear(f, s, w2, co, S, Epilogue::to(h, D).gated_residual(ms + 2 * D)));
+    if (hook) TD_TRY((*hook)(true, i));
   }
 
   // ---- AdaLayerNormContinuous (chunk order: scale, shift) and proj_out, on the latents' image rows only (reference tokens have no velocity)
-  const bf16_t* mf = mod + (size_t)L * 12 * D + (size_t)Ls * 3 * D;
-  TdNormParams nf = np;
-  nf.q = nullptr;   // the final projection stays bf16
-  nf.smoothA = nf.smoothB = nullptr; nf.extA = nf.extB = nullptr; nf.ext_n = 0;
-  nf.x = h_img; nf.y = f->xn; nf.rows = So; nf.split = 0;
-  nf.scaleA = nf.scaleB = mf; nf.shiftA = nf.shiftB = mf + D;
-  TD_TRY(norm_rows(f, s, nf));
-  TD_TRY(linear(f, s, m->proj, bf16_rows(f->xn, D), So, Epilogue::to((bf16_t*)velocity, C)));
+  if (velocity) {
+    const bf16_t* mf = mod + (size_t)L * 12 * D + (size_t)Ls * 3 * D;
+    TdNormParams nf = np;
+    nf.q = nullptr;   // the final projection stays bf16
+    nf.smoothA = nf.smoothB = nullptr; nf.extA = nf.extB = nullptr; nf.ext_n = 0;
+    nf.x = h_img; nf.y = f->xn; nf.rows = So; nf.split = 0;
+    nf.scaleA = nf.scaleB = mf; nf.shiftA = nf.shiftB = mf + D;
+    TD_TRY(norm_rows(f, s, nf));
+    TD_TRY(linear(f, s, m->proj, bf16_rows(f->xn, D), So, Epilogue::to((bf16_t*)velocity, C)));
+  }
   if (calib) TD_TRY(flux_finish_smoothing(m, s));      // (synchronises s; bumps the history epoch)
   if (hist_mode) { f->hs_step = step; f->hs_T = T; f->hs_S = S; f->hs_epoch = m->hist_epoch; } else f->hs_step = -1;
   if (href_on) { f->href_cur ^= 1; f->href_step = step; f->href_T = T; f->href_S = S; f->href_epoch = m->hist_epoch; } else f->href_step = -1;
+  return TD_OK;
+}
+
+// sample k of a ControlNet context's arena (double-block samples first)
+static bf16_t* cn_sample(const td_flux* cn, int k) { return cn->cn_samples + (size_t)k * cn->m->max_img * cn->m->D; }
+
+// One ControlNet evaluation on its own context: behind block i the i-th output Linear runs from the image rows into the sample arena, UNSCALED
+// (controlnet_blocks[i](block_sample[i]), controlnet_single_blocks[i](single_sample[i])); the conditioning scale meets them where they are injected.
+static int controlnet_forward(const char* fn, td_flux* cn, const void* latents, int step, hipStream_t s) {
+  TD_TRY(check_prepared(fn, cn, step));
+  TD_CHECK_ARG(cn->cn_cond_set, "%s: the ControlNet context holds no control condition for its %d image tokens (td_flux_controlnet_set_condition after "
+               "td_flux_set_condition)", fn, cn->S_img);
+  const FluxModel* m = cn->m;
+  const int D = m->D, L = m->cfg.num_layers;
+  const bf16_t* h_img = cn->h + (size_t)cn->T * D;
+  const BlockHook keep = [&](bool single, int i) {
+    const FluxLinear& l = single ? m->cn_sgl[i] : m->cn_dbl[i];
+    return linear(cn, s, l, bf16_rows(h_img, D), cn->S_img, Epilogue::to(cn_sample(cn, single ? L + i : i), D));
+  };
+  return run_blocks(cn, latents, step, nullptr, &keep, s);
+}
+
+int td_flux_controlnet_forward(td_flux* cn, const void* latents, int step, void* stream) {
+  TD_CHECK_ARG(cn && latents, "td_flux_controlnet_forward: null argument");
+  TD_CHECK_ARG(cn->m->controlnet, "td_flux_controlnet_forward: not a ControlNet context (td_flux_controlnet_create makes one)");
+  return controlnet_forward("td_flux_controlnet_forward", cn, latents, step, (hipStream_t)stream);
+}
+
+// One transformer evaluation: velocity[S_img, out_channels] = FluxTransformer2DModel(latents; step).  With a ControlNet context attached and a
+// non-zero conditioning scale at this step ([ext] diffusers FluxControlNetPipeline's loop body): first the ControlNet on the same latents, step
+// and stream, then the blocks with   hidden = hidden + bf16(scale * sample[i / ceil(n_blocks / n_samples)])   behind each, image rows only.
+// With nothing attached, or scale 0 (h + 0 is h), exactly the launches of the plain forward.
+int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream) {
+  TD_CHECK_ARG(f && latents && velocity, "td_flux_forward: null argument");
+  FluxModel* const m = f->m;
+  TD_CHECK_ARG(!m->controlnet, "td_flux_forward: a ControlNet context has no velocity (td_flux_controlnet_forward runs it; td_flux_attach_controlnet makes a "
+               "main context run it)");
+  TD_TRY(check_prepared("td_flux_forward", f, step));
+  hipStream_t s = (hipStream_t)stream;
+  td_flux* const cn = f->cn;
+  const float sc = cn ? ((size_t)step < f->cn_scales.size() ? f->cn_scales[step] : 1.0f) : 0.0f;
+  if (!cn || sc == 0.0f) return run_blocks(f, latents, step, velocity, nullptr, s);
+  const FluxModel* c = cn->m;
+  TD_CHECK_ARG(c->D == m->D && c->cfg.num_heads == m->cfg.num_heads, "td_flux_forward: the attached ControlNet has inner width %d (%d heads), the transformer %d (%d heads)",
+               c->D, c->cfg.num_heads, m->D, m->cfg.num_heads);
+  TD_CHECK_ARG(m->Ccond == 0, "td_flux_forward: a ControlNet is attached to a channel-conditioned transformer (in_channels=%d, out_channels=%d): that pairing "
+               "is not built", m->Cin, m->Cout);
+  TD_CHECK_ARG(c->Cin == m->Cout, "td_flux_forward: the attached ControlNet reads %d latent channels, the transformer steps %d", c->Cin, m->Cout);
+  TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: a ControlNet is attached and the context holds %d reference tokens: a ControlNet together with reference tokens "
+               "is not built", f->S_ref);
+  TD_CHECK_ARG(cn->cond_set && cn->S_img == f->S_img, "td_flux_forward: the attached ControlNet context is prepared for %d image tokens, this context for %d "
+               "(td_flux_set_condition on both, per image)", cn->cond_set ? cn->S_img : 0, f->S_img);
+  TD_CHECK_ARG(cn->n_steps == f->n_steps, "td_flux_forward: the attached ControlNet context is prepared for %d timesteps, this context for %d", cn->n_steps, f->n_steps);
+  cn->attn_variant = f->attn_variant; cn->shared_chip = f->shared_chip;      // images in flight: the side network's kernels follow its image's
+  TD_TRY(controlnet_forward("td_flux_forward(attached ControlNet)", cn, latents, step, s));
+  const int D = m->D, L = m->cfg.num_layers, Ls = m->cfg.num_single_layers, nd = c->cfg.num_layers, ns = c->cfg.num_single_layers;
+  const int per_d = (L + nd - 1) / nd, per_s = ns > 0 ? (Ls + ns - 1) / ns : 0;      // ceil(L / n_d), ceil(Ls / n_s): trailing samples may stay unused
+  bf16_t* h_img = f->h + (size_t)f->T * D;
+  const BlockHook inject = [&](bool single, int i) {
+    if (single && ns == 0) return (int)TD_OK;
+    TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
+    return td_flux_residual_inject_launch(h_img, D, cn_sample(cn, single ? nd + i / per_s : i / per_d), D, f->S_img, D, sc, s);
+  };
+  return run_blocks(f, latents, step, velocity, &inject, s);
+}
+
+// The control mode of a union ControlNet (row of controlnet_mode_embedder the next td_flux_set_condition prepends); -1 clears.
+int td_flux_controlnet_set_mode(td_flux* cn, int mode) {
+  TD_CHECK_ARG(cn, "td_flux_controlnet_set_mode: null context");
+  TD_CHECK_ARG(cn->m->controlnet, "td_flux_controlnet_set_mode: not a ControlNet context");
+  TD_CHECK_ARG(mode == -1 || cn->m->num_mode > 0, "td_flux_controlnet_set_mode: mode %d on a ControlNet without a mode embedder (num_mode = 0)", mode);
+  TD_CHECK_ARG(mode >= -1 && mode < cn->m->num_mode, "td_flux_controlnet_set_mode: mode %d outside the %d rows of controlnet_mode_embedder", mode, cn->m->num_mode);
+  if (mode != cn->cn_mode_id) cn->cond_set = false;      // the text stream's first row is another: the condition must be set again
+  cn->cn_mode_id = mode;
+  return TD_OK;
+}
+
+// The control image of one image: control_latents bf16 [S_img, in_channels] (packed, shifted / scaled) -> E = controlnet_x_embedder(cond), once;
+// every forward of the context then adds E in x_embedder's epilogue.
+int td_flux_controlnet_set_condition(td_flux* cn, const void* control_latents, void* stream) {
+  TD_CHECK_ARG(cn && control_latents, "td_flux_controlnet_set_condition: null argument");
+  const FluxModel* m = cn->m;
+  TD_CHECK_ARG(m->controlnet, "td_flux_controlnet_set_condition: not a ControlNet context");
+  TD_CHECK_ARG(cn->cond_set, "td_flux_controlnet_set_condition: call td_flux_set_condition first (it fixes the image token count)");
+  TD_CHECK_ARG((uintptr_t)control_latents % 16 == 0, "td_flux_controlnet_set_condition: control_latents must be 16-byte aligned");
+  TD_TRY(linear(cn, (hipStream_t)stream, m->cn_x_emb, bf16_rows(control_latents, m->Cin), cn->S_img, Epilogue::to(cn->cn_E, m->D)));
+  cn->cn_cond_set = true;
+  return TD_OK;
+}
+
+int td_flux_controlnet_samples(const td_flux* cn, void** base, int* n_double, int* n_single, int64_t* stride_elems, int* rows, int* width) {
+  TD_CHECK_ARG(cn, "td_flux_controlnet_samples: null context");
+  TD_CHECK_ARG(cn->m->controlnet, "td_flux_controlnet_samples: not a ControlNet context");
+  if (base) *base = cn->cn_samples;
+  if (n_double) *n_double = cn->m->cfg.num_layers;
+  if (n_single) *n_single = cn->m->cfg.num_single_layers;
+  if (stride_elems) *stride_elems = (int64_t)cn->m->max_img * cn->m->D;
+  if (rows) *rows = cn->cond_set ? cn->S_img : 0;
+  if (width) *width = cn->m->D;
+  return TD_OK;
+}
+
+// sample k of the last forward -> dst bf16 [rows, width] contiguous (one device-to-device copy on `stream`)
+int td_flux_controlnet_read_sample(const td_flux* cn, int k, void* dst, void* stream) {
+  TD_CHECK_ARG(cn && dst, "td_flux_controlnet_read_sample: null argument");
+  TD_CHECK_ARG(cn->m->controlnet && cn->cond_set, "td_flux_controlnet_read_sample: a prepared ControlNet context is required");
+  const int n = cn->m->cfg.num_layers + cn->m->cfg.num_single_layers;
+  TD_CHECK_ARG(k >= 0 && k < n, "td_flux_controlnet_read_sample: sample %d outside the %d the model produces", k, n);
+  TD_CHECK_HIP(hipMemcpyAsync(dst, cn_sample(cn, k), (size_t)cn->S_img * cn->m->D * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TD_OK;
+}
+
+// One ControlNet context per main context, one main context per ControlNet context; cn == NULL detaches.  The scales return to 1.0.
+int td_flux_attach_controlnet(td_flux* f, td_flux* cn) {
+  TD_CHECK_ARG(f, "td_flux_attach_controlnet: null context");
+  TD_CHECK_ARG(!f->m->controlnet, "td_flux_attach_controlnet: the first argument is a ControlNet context (attach a ControlNet TO a transformer context)");
+  if (cn) {
+    TD_CHECK_ARG(cn->m->controlnet, "td_flux_attach_controlnet: the second argument is not a ControlNet context (td_flux_controlnet_create makes one)");
+    TD_CHECK_ARG(!cn->cn_owner || cn->cn_owner == f, "td_flux_attach_controlnet: this ControlNet context already serves another main context (one at a time: "
+                 "fork the ControlNet, one fork per main context)");
+  }
+  if (f->cn) f->cn->cn_owner = nullptr;
+  f->cn = cn;
+  if (cn) cn->cn_owner = f;
+  f->cn_scales.clear();
+  return TD_OK;
+}
+
+// conditioning scale of every prepared step (host floats; diffusers: controlnet_conditioning_scale x controlnet_keep[i]); steps beyond n keep 1.0
+int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n) {
+  TD_CHECK_ARG(f && n >= 0 && (n == 0 || scales), "td_flux_set_controlnet_scales: null argument");
+  TD_CHECK_ARG(!f->m->controlnet, "td_flux_set_controlnet_scales: the scales belong to the main context the ControlNet is attached to");
+  TD_CHECK_ARG(f->cn, "td_flux_set_controlnet_scales: no ControlNet is attached (td_flux_attach_controlnet)");
+  TD_CHECK_ARG(n <= f->m->max_steps, "td_flux_set_controlnet_scales: n=%d exceeds the %d steps of capacity", n, f->m->max_steps);
+  for (int i = 0; i < n; ++i) TD_CHECK_ARG(std::isfinite(scales[i]), "td_flux_set_controlnet_scales: scale %d is not finite", i);
+  f->cn_scales.assign(scales, scales + n);
   return TD_OK;
 }
 

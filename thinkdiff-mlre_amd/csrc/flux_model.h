@@ -88,6 +88,14 @@ struct FluxModel {
   std::vector<Slot> slots;
   std::unordered_map<std::string, int> index;
   FluxLinear x_emb, ctx_emb, t1, t2, g1, g2, p1, p2, mod, proj;
+  // A ControlNet side network (td_flux_controlnet_create; [ext] diffusers FluxControlNetModel): the same embedders and blocks, no final norm and
+  // no proj_out (NMOD without the final-norm share), and its own always-bf16 Linears -- controlnet_x_embedder [D, Cin], one output Linear [D, D]
+  // behind every double / single block -- plus the mode embedding [num_mode, D] of the "union" checkpoints (num_mode == 0: none).
+  bool controlnet = false;
+  int num_mode = 0;
+  FluxLinear cn_x_emb;
+  std::vector<FluxLinear> cn_dbl, cn_sgl;
+  bf16_t* cn_mode = nullptr;
   std::vector<DoubleBlock> dbl;
   std::vector<SingleBlock> sgl;
   std::vector<FluxLinear*> linears;      // every block Linear, in block order
@@ -133,7 +141,8 @@ inline unsigned flux_mask8(const FluxModel* m) { return (m->precision != TD_PREC
 inline int flux_k8(const FluxModel* m, const FluxLinear& l) { return l.K + (l.ext >= 0 && flux_smoothed(m) ? SM_EXT : 0); }
 
 // csrc/flux_model.hip.  flux_model_create validates the configuration (td_flux_create's argument errors) and allocates arena + parameter table.
-int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_tokens, int max_steps, FluxModel** out);
+// controlnet: the side-network kind (num_mode: rows of its mode embedding, 0 = none); 0, 0: the transformer.
+int flux_model_create(const TdFluxConfig* cfg, int controlnet, int num_mode, int max_img_tokens, int max_txt_tokens, int max_steps, FluxModel** out);
 void flux_model_destroy(FluxModel* m);
 int flux_refresh_score_bounds(FluxModel* m);
 int flux_finish_smoothing(FluxModel* m, hipStream_t s);      // end of the calibration forward on stream s
@@ -182,6 +191,16 @@ struct td_flux {
   // The blocks then run over T + S_img + S_ref rows; the final norm, proj_out, the velocity and every step kernel keep S_img.
   int S_ref = 0;
   bf16_t* xref = nullptr;
+  // ---- ControlNet.  On a ControlNet context (m->controlnet): the control mode (-1: none), E = controlnet_x_embedder(control latents) of the
+  // image [max_img, D] -- the residual of every forward's x_embedder epilogue -- and the arena of UNSCALED samples the last forward left,
+  // [n_d + n_s][max_img, D] (sample k at cn_samples + k * max_img * D).  cn_owner: the main context it is attached to (one at a time).
+  int cn_mode_id = -1;
+  bf16_t *cn_E = nullptr, *cn_samples = nullptr;
+  bool cn_cond_set = false;
+  td_flux* cn_owner = nullptr;
+  // On a main context: the attached ControlNet context and the conditioning scale of every prepared step (host floats; missing entries are 1.0)
+  td_flux* cn = nullptr;
+  std::vector<float> cn_scales;
   // optional per-launch HIP-event trace (bench.py roofline leg)
   bool tracing = false;
   std::vector<hipEvent_t> ev_pool;

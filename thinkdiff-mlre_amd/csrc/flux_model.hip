@@ -33,7 +33,8 @@ void add_linear(FluxModel* m, const std::string& name, const FluxLinear& l, int6
 
 }  // namespace
 
-int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_tokens, int max_steps, FluxModel** out) {
+int flux_model_create(const TdFluxConfig* cfg, int controlnet, int num_mode, int max_img_tokens, int max_txt_tokens, int max_steps, FluxModel** out) {
+  const char* const fn = controlnet ? "td_flux_controlnet_create" : "td_flux_create";
   TD_CHECK_ARG(cfg->head_dim == 128, "td_flux_create: head_dim must be 128");
   TD_CHECK_ARG(cfg->axes_dims[0] + cfg->axes_dims[1] + cfg->axes_dims[2] == 128, "td_flux_create: rope axes must sum to 128");
   TD_CHECK_ARG(cfg->in_channels % 64 == 0 && cfg->joint_dim % 64 == 0 && cfg->pooled_dim % 64 == 0, "td_flux_create: input widths must be multiples of 64");
@@ -44,14 +45,22 @@ int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_t
                cfg->in_channels, c_out);
   TD_CHECK_ARG(c_out <= cfg->in_channels, "td_flux_create: out_channels=%d exceeds in_channels=%d (in_channels = out_channels + the channel condition's width)",
                c_out, cfg->in_channels);
+  TD_CHECK_ARG(cfg->num_layers >= (controlnet ? 1 : 0) && cfg->num_single_layers >= 0, "%s: num_layers=%d, num_single_layers=%d", fn, cfg->num_layers, cfg->num_single_layers);
+  if (controlnet) {
+    TD_CHECK_ARG(c_out == cfg->in_channels, "td_flux_controlnet_create: in_channels=%d, out_channels=%d: a ControlNet reads the latents alone (its condition enters "
+                 "through controlnet_x_embedder, not through the channel axis)", cfg->in_channels, c_out);
+    TD_CHECK_ARG(num_mode >= 0 && num_mode <= 65536, "td_flux_controlnet_create: num_mode=%d", num_mode);
+  }
   FluxModel* m = new FluxModel();
   m->cfg = *cfg;
+  m->controlnet = controlnet != 0;
+  m->num_mode = controlnet ? num_mode : 0;
   m->cfg.out_channels = c_out;
   m->Cin = cfg->in_channels; m->Cout = c_out; m->Ccond = cfg->in_channels - c_out;
   const int D = m->D = cfg->num_heads * cfg->head_dim;
   const int M = m->M = cfg->mlp_ratio * D;
   const int L = cfg->num_layers, Ls = cfg->num_single_layers;
-  m->NMOD = L * 12 * D + Ls * 3 * D + 2 * D;
+  m->NMOD = L * 12 * D + Ls * 3 * D + (controlnet ? 0 : 2 * D);      // (a ControlNet has no norm_out)
   m->max_img = max_img_tokens; m->max_txt = max_txt_tokens; m->max_steps = max_steps;
   m->dbl.resize(L);
   m->sgl.resize(Ls);
@@ -62,6 +71,12 @@ int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_t
   shape(m->t1, D, 256); shape(m->t2, D, D); shape(m->g1, D, 256); shape(m->g2, D, D);
   shape(m->p1, D, cfg->pooled_dim); shape(m->p2, D, D);
   shape(m->mod, m->NMOD, D); shape(m->proj, m->Cout, D);
+  if (controlnet) {      // its own Linears: plain shapes, cls = 0 (always bf16), outside m->linears (never quantised, never smoothed)
+    shape(m->cn_x_emb, D, m->Cin);
+    m->cn_dbl.resize(L); m->cn_sgl.resize(Ls);
+    for (FluxLinear& l : m->cn_dbl) shape(l, D, D);
+    for (FluxLinear& l : m->cn_sgl) shape(l, D, D);
+  }
   // smoothed: its input channels take the next K slots of the smoothing vectors; ln_fed: it reads a LayerNorm output and takes the next replication table
   auto block_linear = [&](FluxLinear& l, int N, int K, unsigned cls, bool smoothed, bool ln_fed, int sm_fixed = 0) {
     shape(l, N, K);
@@ -94,10 +109,16 @@ int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_t
     ap.take(b.lin[SINGLE_IN]); ap.take(b.lin[SINGLE_OUT]);
     ap.take(&b.norm_q, 128); ap.take(&b.norm_k, 128);
   }
+  if (controlnet) {      // behind everything the transformer has: the shared part keeps the transformer's offsets
+    ap.take(m->cn_x_emb);
+    for (FluxLinear& l : m->cn_dbl) ap.take(l);
+    for (FluxLinear& l : m->cn_sgl) ap.take(l);
+    if (m->num_mode > 0) ap.take(&m->cn_mode, (int64_t)m->num_mode * D);
+  }
   m->arena_elems = ap.off;
   hipError_t e = hipMalloc((void**)&m->arena, (size_t)ap.off * sizeof(bf16_t));
   if (e != hipSuccess) {
-    td_set_error("td_flux_create: hipMalloc of %.2f GiB weight arena failed: %s", ap.off * 2.0 / (1 << 30), hipGetErrorString(e));
+    td_set_error("%s: hipMalloc of %.2f GiB weight arena failed: %s", fn, ap.off * 2.0 / (1 << 30), hipGetErrorString(e));
     delete m;
     return TD_ERR_HIP;
   }
@@ -148,8 +169,18 @@ int flux_model_create(const TdFluxConfig* cfg, int max_img_tokens, int max_txt_t
     add_slot(m, p + "attn.norm_q.weight", b.norm_q, 128);
     add_slot(m, p + "attn.norm_k.weight", b.norm_k, 128);
   }
-  add_linear(m, "norm_out.linear", m->mod, (int64_t)L * 12 * D + (int64_t)Ls * 3 * D, 2 * D);
-  add_linear(m, "proj_out", m->proj, 0, m->Cout);
+  if (!controlnet) {
+    add_linear(m, "norm_out.linear", m->mod, (int64_t)L * 12 * D + (int64_t)Ls * 3 * D, 2 * D);
+    add_linear(m, "proj_out", m->proj, 0, m->Cout);
+  } else {
+    add_linear(m, "controlnet_x_embedder", m->cn_x_emb, 0, D);
+    for (int i = 0; i < L; ++i) add_linear(m, "controlnet_blocks." + std::to_string(i), m->cn_dbl[i], 0, D);
+    for (int i = 0; i < Ls; ++i) add_linear(m, "controlnet_single_blocks." + std::to_string(i), m->cn_sgl[i], 0, D);
+    if (m->num_mode > 0) {
+      add_slot(m, "controlnet_mode_embedder.weight", m->cn_mode, (int64_t)m->num_mode * D);
+      m->slots.back().rows = m->num_mode; m->slots.back().cols = D;
+    }
+  }
   *out = m;
   return TD_OK;
 }
@@ -544,6 +575,7 @@ int td_flux_set_smoothing(td_flux* f, int mode) {
 // attention is otherwise a quarter of the image.
 int td_flux_set_attention(td_flux* f, int mode) {
   TD_CHECK_ARG(f && f->root && (mode == TD_ATTENTION_BF16 || mode == TD_ATTENTION_FP8), "td_flux_set_attention: parent context, TD_ATTENTION_BF16 or TD_ATTENTION_FP8");
+  TD_CHECK_ARG(!f->m->controlnet || mode == TD_ATTENTION_BF16, "td_flux_set_attention: mode %d on a ControlNet model: the side network runs in bf16 only", mode);
   f->m->attn_mode = mode;
   ++f->m->hist_epoch;
   return TD_OK;
@@ -552,6 +584,8 @@ int td_flux_set_attention(td_flux* f, int mode) {
 int td_flux_set_precision(td_flux* f, int precision, void* stream) {
   TD_CHECK_ARG(f && (precision == TD_PRECISION_BF16 || precision == TD_PRECISION_FP8_E4M3 || precision == TD_PRECISION_INT8), "td_flux_set_precision: unknown precision %d", precision);
   TD_CHECK_ARG(f->root, "td_flux_set_precision: set the precision on the parent context (forks follow it)");
+  TD_CHECK_ARG(!f->m->controlnet || precision == TD_PRECISION_BF16, "td_flux_set_precision: precision %d on a ControlNet model: the side network runs in bf16 only "
+               "(the main transformer may be in any mode)", precision);
   return set_precision(f->m, precision, (hipStream_t)stream);
 }
 
@@ -559,6 +593,7 @@ int td_flux_lora_load(td_flux* f, const char* adapter, const char* param, const 
   TD_CHECK_ARG(f && adapter && param && A && B, "td_flux_lora_load: null argument");
   TD_CHECK_ARG(f->root, "td_flux_lora_load: '%s': adapters belong to the parent context (forks see its weights)", param);
   TD_CHECK_ARG(adapter[0], "td_flux_lora_load: empty adapter name");
+  TD_CHECK_ARG(!f->m->controlnet, "td_flux_lora_load: '%s' on a ControlNet model: adapters on the side network are not built (the main transformer takes them)", param);
   FluxModel* m = f->m;
   auto it = m->index.find(param);
   TD_CHECK_ARG(it != m->index.end(), "td_flux_lora_load: unknown parameter '%s'", param);

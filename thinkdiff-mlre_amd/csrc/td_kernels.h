@@ -205,6 +205,7 @@ int td_timestep_sincos_launch(const float* t, int n, bf16_t* out, hipStream_t st
 int td_temb_combine_silu_launch(const bf16_t* te, const bf16_t* ge, const bf16_t* pe, int n, int D, bf16_t* temb, bf16_t* silu_out, hipStream_t stream);
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream);
 int td_flux_cfg_step_launch(bf16_t* x, const bf16_t* v_pos, const bf16_t* v_neg, float scale, float dt, long long n, hipStream_t stream);
+int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr, int rows, int D, float scale, hipStream_t stream);
 int td_copy_cols_launch(const bf16_t* src, int lds, bf16_t* dst, int ldd, int rows, int cols, hipStream_t stream);
 int td_flux_inpaint_step_launch(bf16_t* x, const bf16_t* v, const bf16_t* z, const bf16_t* noise, const bf16_t* mask, float dt,
                                 float sigma_next, long long n, hipStream_t stream);

@@ -150,6 +150,17 @@ at::Tensor& flux_cfg_step_(at::Tensor& x, const at::Tensor& v_pos, const at::Ten
   return x;
 }
 
+// FLUX ControlNet residual injection in place: h[:, :D] += bf16(scale * r[:, :D]) with D = r's width, the Python float `scale` kept in fp32
+// (td_flux_residual_inject_bf16).  h and r are 2-D views with innermost stride 1: row strides may exceed the width, columns of h beyond D stay.
+at::Tensor& flux_residual_inject_(at::Tensor& h, const at::Tensor& r, double scale) {
+  check_rows(h, "h"); check_rows(r, "r"); same_device(r, "r", h);
+  TORCH_CHECK(h.dim() == 2 && r.dim() == 2 && r.size(0) == h.size(0) && r.size(1) <= h.size(1) && h.size(0) > 0 && r.size(1) > 0,
+              "thinkdiff_hip::flux_residual_inject_: h [rows, >= D], r [rows, D] with the same row count");
+  DeviceGuard guard(h.device());
+  ok(td_flux_residual_inject_bf16(h.data_ptr(), h.stride(0), r.data_ptr(), r.stride(0), (int)h.size(0), (int)r.size(1), (float)scale, stream_of(h)));
+  return h;
+}
+
 // FluxInpaintPipeline's step in place: Euler step, scale_noise of the image latents to bf16(sigma_next) (noise None: the clean latents) and
 // the mask blend, every op a bf16 torch op (td_flux_inpaint_step_bf16)
 at::Tensor& flux_inpaint_step_(at::Tensor& x, const at::Tensor& v, const at::Tensor& image_latents, const c10::optional<at::Tensor>& noise,
@@ -570,6 +581,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_set_channel_condition(int engine, Tensor cond) -> ()");
   m.def("flux_set_reference_tokens(int engine, Tensor ref_latents, Tensor ref_ids) -> ()");
   m.def("flux_cfg_step_(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)");
+  m.def("flux_residual_inject_(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)");
   m.def("flux_denoise_cfg_(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)");
   m.def("vae_encode_moments_masked(int engine, Tensor image, Tensor mask, int H, int W) -> Tensor");
   m.def("flux_fill_condition(Tensor moments, Tensor? eps, Tensor mask, float scaling_factor, float shift_factor, int H, int W) -> Tensor");
@@ -607,6 +619,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_set_channel_condition", &flux_set_channel_condition);
   m.impl("flux_set_reference_tokens", &flux_set_reference_tokens);
   m.impl("flux_cfg_step_", &flux_cfg_step_);
+  m.impl("flux_residual_inject_", &flux_residual_inject_);
   m.impl("flux_denoise_cfg_", &flux_denoise_cfg_);
   m.impl("vae_encode_moments_masked", &vae_encode_moments_masked);
   m.impl("flux_fill_condition", &flux_fill_condition);

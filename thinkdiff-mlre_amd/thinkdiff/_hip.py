@@ -51,6 +51,15 @@ def _declare(L):
         "td_euler_step_bf16": [vp, vp, f32, i64, vp],
         "td_flux_inpaint_step_bf16": [vp, vp, vp, vp, vp, f32, f32, i64, vp],
         "td_flux_cfg_step_bf16": [vp, vp, vp, f32, f32, i64, vp],
+        "td_flux_residual_inject_bf16": [vp, i64, vp, i64, i32, i32, f32, vp],
+        "td_flux_controlnet_create": [vp, i32, i32, i32, i32, vp],
+        "td_flux_controlnet_set_mode": [vp, i32],
+        "td_flux_controlnet_set_condition": [vp, vp, vp],
+        "td_flux_controlnet_forward": [vp, vp, i32, vp],
+        "td_flux_controlnet_samples": [vp, vp, vp, vp, vp, vp, vp],
+        "td_flux_controlnet_read_sample": [vp, i32, vp, vp],
+        "td_flux_attach_controlnet": [vp, vp],
+        "td_flux_set_controlnet_scales": [vp, vp, i32],
         "td_flux_inpaint_mask": [vp, i32, i32, i32, i32, vp, vp],
         "td_flux_pack_latents": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
         "td_cls_avgpool2_bf16": [vp, vp, i32, i32, vp],

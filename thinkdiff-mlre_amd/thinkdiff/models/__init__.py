@@ -3,6 +3,7 @@ from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import BlipVisionT5DecoderForConditionalGeneration, build_vision_projector
 from .flux_control import FluxControlPipelineRewritePrompt
+from .flux_controlnet import FluxControlNetConfig, FluxControlNetModel, FluxControlNetPipelineRewritePrompt
 from .flux_fill import FluxFillPipelineRewritePrompt
 from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
 from .flux_inpaint import FluxInpaintPipelineRewritePrompt
@@ -16,4 +17,5 @@ from .qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
 __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration", "build_vision_projector",
            "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
            "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt", "FluxKontextPipelineRewritePrompt",
+           "FluxControlNetPipelineRewritePrompt", "FluxControlNetModel", "FluxControlNetConfig",
            "FluxTransformer2DModel", "FluxTransformerConfig"]

@@ -24,7 +24,7 @@ Refused, not approximated (NotImplementedError): `callback_on_step_end`, custom 
 `joint_attention_kwargs` (the per-call LoRA scale: adapters loaded with `load_lora_weights` are merged into the weights, so set their
 weights with `set_adapters(names, weights)`; the FLUX.1 Canny / Depth *LoRA* checkpoints, which widen `x_embedder`, are refused by the
 loader -- the full 128-channel ones load).  The
-ControlNet side network is a different model and is not this pipeline.  A transformer with other channel counts is refused with
+ControlNet side network is a different model with its own pipeline (flux_controlnet.py), not this one.  A transformer with other channel counts is refused with
 both numbers named.
 """
 from typing import Optional

@@ -387,6 +387,21 @@ class FluxTransformer2DModel:
         assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.latent_channels)
         return _OPS.flux_denoise_cfg_(int(self._h.value), int(neg_context._h.value), latents, [float(s) for s in sigmas], float(scale))
 
+    # ---- ControlNet (thinkdiff.models.flux_controlnet) ------------------------------------------------------
+    def attach_controlnet(self, controlnet):
+        """Attach one `FluxControlNetModel` context to THIS context (None detaches): every forward / denoise step whose scale is not 0
+        then runs the ControlNet first and adds its scaled samples behind the blocks (td_flux_attach_controlnet).  One ControlNet context
+        serves one transformer context at a time (fork both: one pair per image in flight).  The scales return to 1.0."""
+        _hip.check(self._L.td_flux_attach_controlnet(self._h, controlnet._h if controlnet is not None else None))
+        self._controlnet = controlnet      # (keeps the attached context alive)
+        return self
+
+    def set_controlnet_scales(self, scales: Sequence[float]):
+        """The conditioning scale of every prepared step: `controlnet_conditioning_scale * controlnet_keep[i]` (0: the plain step)."""
+        arr = (ctypes.c_float * max(1, len(scales)))(*[float(v) for v in scales])
+        _hip.check(self._L.td_flux_set_controlnet_scales(self._h, ctypes.cast(arr, ctypes.c_void_p), len(scales)))
+        return self
+
     # ---- per-launch HIP-event trace (bench.py roofline leg) ------------------------------------------
     TRACE_CATEGORIES = ("gemm_256x256", "gemm_other", "attention", "layernorm_modulate", "qk_rmsnorm_rope", "gemm_288x192")
 

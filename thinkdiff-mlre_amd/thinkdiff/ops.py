@@ -31,6 +31,7 @@ flux_denoise_inpaint_ / flux_denoise_multi_inpaint_   the inpainting denoise loo
 flux_set_reference_tokens  FluxKontextPipeline's per-step torch.cat of the reference-image latents / ids behind the latents, once per image
 flux_cfg_step_             true classifier-free guidance (neg + scale * (pos - neg)) + scheduler.step, fused, in place
 flux_denoise_cfg_          the denoise loop under true CFG: both conditionings per step on two prepared contexts, then flux_cfg_step_
+flux_residual_inject_      FluxTransformer2DModel's `hidden_states + controlnet_block_samples[..]` with the ControlNet's `* conditioning_scale`, fused, in place
 lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up to 8 pairs at once, fp32 accumulation, one rounding
 flux_lora_load / flux_lora_set_adapters / flux_lora_delete / flux_read_param   diffusers' load_lora_weights / set_adapters / delete_adapters
                            (empty name: unload_lora_weights) on the engine's merged weights, and the effective parameter read back; the last
@@ -68,6 +69,7 @@ SCHEMAS = {
     "flux_denoise_inpaint_": "(int engine, Tensor(a!) latents, float[] sigmas, Tensor image_latents, Tensor noise, Tensor mask) -> Tensor(a!)",
     "flux_set_reference_tokens": "(int engine, Tensor ref_latents, Tensor ref_ids) -> ()",
     "flux_cfg_step_": "(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)",
+    "flux_residual_inject_": "(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)",
     "flux_denoise_cfg_": "(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)",
     "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
     "lora_merge": "(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor",
