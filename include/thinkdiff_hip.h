@@ -183,6 +183,23 @@ int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float s
  * h, r bf16 with row strides ldh, ldr >= D (elements; columns beyond D are untouched); D % 8 == 0, strides multiples of 8, both pointers 16-byte
  * aligned, r not overlapping h. */
 int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream);
+/* FLUX IP-Adapter cross-attention (td_abi_version() >= 5; [ext] diffusers >= 0.32 FluxIPAdapterJointAttnProcessor2_0, restated from the published
+ * source, parity unpinned): the image rows' query against the n_keys image-prompt tokens of one adapter, the scaled result written or added to o.
+ *   qn[m, h, :] = norm_w ? bf16(bf16(q[m, h, :] * rstd) * norm_w)  :  q[m, h, :]       rstd = rsqrt(mean(q[m, h, :]^2) + eps) in fp32 (qk_norm8 of
+ *                 csrc/qk_rope_math.h with td_qk_norm_rope_bf16's summation tree: the bits that kernel rounds before it rotates)
+ *   s[m, h, j]  = sum_d qn[m, h, d] k[j, h*128 + d]                  fp32 accumulation of bf16 products (v_mfma_f32_16x16x32_bf16), j < n_keys
+ *   p[m, h, j]  = bf16(exp2((s - max_j s) * 128^-0.5 * log2(e)))     the TRUE row maximum over all n_keys (k is not normalised: no score bound)
+ *   a[m, h, d]  = bf16((sum_j p[m, h, j] v[j, h*128 + d]) / (sum_j p[m, h, j]))      fp32 accumulation; the row sum is over the rounded p
+ *   t           = bf16(out_scale * float(a))                         `scale` is a Python float in diffusers: an fp32 operand of a bf16 multiply
+ *   o[m, h*128 + d] = accumulate ? bf16(float(o[m, h*128 + d]) + float(t)) : t
+ * q bf16 [rows, ldq] with head h at column h*128 (the FLUX engine passes the image rows of its [S, 3D] projection buffer, ldq = 3D); k, v bf16
+ * [n_keys, ldkv]; o bf16 [rows, ldo]; norm_w bf16 [128] or NULL.  rows >= 1, 1 <= H <= 65535, 1 <= n_keys <= TD_IP_MAX_KEYS; strides multiples of 8
+ * and >= H*128; all pointers 16-byte aligned.  Keys are scored in tiles of 32: the kernel zero-fills the padding in LDS and masks its scores, and
+ * reads nothing outside [n_keys, ldkv].  Columns of o beyond H*128 and rows beyond `rows` are untouched.  Anything else: TD_ERR_INVALID before any
+ * launch, the offender named.  Capturable (no allocation, no synchronisation). */
+#define TD_IP_MAX_KEYS 256       /* two images of a 128-token adapter */
+int td_ip_attention_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo, int rows, int H, int n_keys,
+                         const void* norm_w, float eps, float out_scale, int accumulate, void* stream);
 #define TD_INPAINT_MASK_U8_HW 0   /* uint8 [H, W] (PIL mode "L") */
 #define TD_INPAINT_MASK_F32_HW 1  /* float32 [H, W] in [0, 1] */
 /* FluxInpaintPipeline's mask latents from a height x width mask (format TD_INPAINT_MASK_*):
@@ -373,6 +390,46 @@ int td_flux_controlnet_read_sample(const td_flux* cn, int k, void* dst, void* st
 int td_flux_attach_controlnet(td_flux* f, td_flux* cn);
 /* conditioning scale per prepared step (n host floats; steps beyond n keep 1.0): controlnet_conditioning_scale x controlnet_keep[i]. */
 int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n);
+/* ---- FLUX IP-Adapter (td_abi_version() >= 5): image-prompt conditioning of the double-stream blocks ([ext] diffusers >= 0.32 FluxIPAdapterMixin,
+ * embeddings.ImageProjection, attention_processor.FluxIPAdapterJointAttnProcessor2_0, transformer_flux.FluxTransformerBlock.forward; restated from
+ * the published sources, parity unpinned).  Up to TD_IP_MAX_ADAPTERS adapters in numbered slots.  Per adapter, J = joint_dim, D = heads x 128:
+ *   tokens = LayerNorm_J(Linear(embeds [n_img, E] -> [n_img, num_tokens J]).reshape(n_img num_tokens, J))     eps 1e-5, affine; once per image
+ *   K_i = to_k_ip_i(tokens), V_i = to_v_ip_i(tokens)      Linear(J -> D, bias), double block i; once per image, not per step
+ * and in double block i, for the adapters in slot order:   ip = 0;  ip += scale_a[i] * SDPA(norm_q(to_q(norm_hidden)), K_i^a, V_i^a)   -- the image
+ * stream's query BEFORE RoPE, every op a bf16 torch op (td_ip_attention_bf16 spells the roundings) -- then, behind `hidden + gate_mlp * ff`,
+ *   hidden = bf16(float(hidden) + float(ip))      (td_flux_residual_inject_bf16 at scale 1.0, which is exact).
+ * ip is neither projected by to_out nor gated; the text stream and the single-stream blocks are untouched.  The adapter's weights stay bf16 in every
+ * precision mode, to_q runs in whatever mode the model is in, and nothing of it joins the int8 smoothing calibration or the history scales.
+ *
+ * Model level -- parent context only (forks share the model, as with LoRA); TD_ERR_INVALID on a fork and on a ControlNet.
+ * td_flux_ip_adapter_add: claims the first free slot for an adapter of num_tokens tokens per image over embeddings of width embed_dim (% 8 == 0)
+ * and allocates its weights (not capturable, like td_flux_lora_load).  Parameter names of td_flux_ip_adapter_load_param (device bf16, `count`
+ * elements, torch Linear layout): image_proj.proj.weight [num_tokens J, E], image_proj.proj.bias, image_proj.norm.weight [J], image_proj.norm.bias,
+ * ip_adapter.{i}.to_k_ip.weight [D, J], ip_adapter.{i}.to_k_ip.bias [D], ip_adapter.{i}.to_v_ip.weight, ip_adapter.{i}.to_v_ip.bias, i < num_layers.
+ * td_flux_ip_adapter_remove frees a slot (-1: all).  td_flux_set_ip_adapter_scale: n == 1 (all blocks) or n == num_layers finite host floats;
+ * default 1.0; a block whose scale is 0 contributes nothing and launches nothing. */
+#define TD_IP_MAX_ADAPTERS 4
+int td_flux_ip_adapter_add(td_flux* f, int num_tokens, int embed_dim, int* slot);
+int td_flux_ip_adapter_load_param(td_flux* f, int slot, const char* name, const void* data, int64_t count, void* stream);
+int td_flux_ip_adapter_remove(td_flux* f, int slot);
+int td_flux_set_ip_adapter_scale(td_flux* f, int slot, const float* per_block, int n);
+/* Slot facts (any out pointer may be NULL): used, num_tokens, embed_dim; and on THIS context whether embeds are set and for how many keys. */
+int td_flux_ip_adapter_info(const td_flux* f, int slot, int* used, int* num_tokens, int* embed_dim, int* embeds_set, int* n_keys);
+/* Per context (forks hold their own image prompt): embeds bf16 [n_img, E] contiguous, 16-byte aligned; NULL clears the slot for this context.
+ * Runs the projection (the engine's GEMM, td_layernorm_bf16) and the 2 x num_layers K / V Linears into this context's arena
+ * [L][K | V][keys_pad][D], n_keys = n_img x num_tokens, rows up to the multiple of 32 zero.  Allocates at first use and when a later call needs more
+ * (hipMalloc / hipFree: NOT capturable, like td_flux_lora_load).  TD_ERR_INVALID: a free slot, a parameter of the slot not loaded yet (named),
+ * n_img x num_tokens > TD_IP_MAX_KEYS (both numbers in the message), a ControlNet context.
+ * Forward-time TD_ERR_INVALID of a context with embeds set (td_flux_forward and every td_flux_denoise* loop): the slot's weights changed or the slot
+ * was removed since (td_flux_ip_adapter_load_param / _remove: set the embeds again, or clear them); reference tokens are set (the image rows would
+ * include the reference rows); a ControlNet is attached.  A context with no embeds set, or with every scale 0, issues the plain forward's launches
+ * and gives its bits; one active slot adds two launches per double block (td_ip_attention_bf16, td_flux_residual_inject_bf16), each further one. */
+int td_flux_set_ip_image_embeds(td_flux* f, int slot, const void* embeds, int n_img, void* stream);
+/* Tests: copy this context's image-prompt tokens (block < 0: bf16 [n_keys, J]) or double block `block`'s K (which = 0) / V (1) (bf16 [n_keys, D])
+ * of a slot into dst, contiguous, stream-ordered. */
+int td_flux_ip_read(const td_flux* f, int slot, int block, int which, void* dst, void* stream);
+/* The widths of those rows: J = joint_dim (tokens) and D = heads x 128 (K / V). */
+int td_flux_ip_widths(const td_flux* f, int* joint_dim, int* inner_dim);
 /* Per-launch HIP-event trace of the engine's kernels (events recorded on the launch stream).
  * categories: 0 GEMM 256x256 tile (td_gemm_bf16_nt_kernel<8,4>), 1 small GEMM tiles, 2 attention,
  * 3 LayerNorm+modulate, 4 QK-RMSNorm+RoPE, 5 GEMM 288x192 tile (<9,3>).  trace_end synchronises and

@@ -26,6 +26,8 @@
 // this file holds everything that runs on a context: create / fork / destroy, conditioning, schedule, the forward, the denoise loops, the trace.
 // A ControlNet side network (td_flux_controlnet_*) is a second KIND of model run by the same block loop (run_blocks): its contexts keep block
 // samples, and a main context with one attached adds them behind its own blocks (td_flux_attach_controlnet, td_flux_residual_inject_bf16).
+// IP-Adapter slots (td_flux_ip_adapter_*: the model's; td_flux_set_ip_image_embeds: a context's image prompt -> tokens and every double block's
+// K / V, once per image) add, inside a double block, td_ip_attention of the image rows' un-rotated query and one add behind the FF.
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -295,6 +297,8 @@ void td_flux_destroy(td_flux* f) {
   if (f->cn) f->cn->cn_owner = nullptr;            // either end of an attachment may go first
   if (f->cn_owner) f->cn_owner->cn = nullptr;
   if (f->root) flux_model_destroy(f->m);
+  for (td_flux::IpCtx& c : f->ip) if (c.buf) (void)hipFree(c.buf);
+  if (f->ip_out) (void)hipFree(f->ip_out);
   (void)hipFree(f->ws);
   delete f;
 }
@@ -558,6 +562,10 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
     return td_col_amax_launch(x + (size_t)sp.r0 * ld, ld, sp.rows, K, m->sm_ax + slot, s);
   };
 
+  // IP-Adapter: the slots whose image prompt this context holds (td_flux_forward vouched for them: current weights, no reference tokens, no ControlNet)
+  int ip_slots[TD_IP_MAX_ADAPTERS], n_ip = 0;
+  for (int a = 0; a < TD_IP_MAX_ADAPTERS; ++a) if (f->ip[a].set && m->ip[a].used) ip_slots[n_ip++] = a;
+
   // ---- double-stream blocks -------------------------------------------------------------------------------------------------------
   for (int i = 0; i < L; ++i) {
     const DoubleBlock& b = m->dbl[i];
@@ -569,6 +577,19 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
     TD_TRY(norm_for(lin[QKV_CTX], lin[QKV_IMG]));
     if (calib) { TD_TRY(cal(f->xn, D, txt, D, lin[QKV_CTX].sm)); TD_TRY(cal(f->xn, D, img, D, lin[QKV_IMG].sm)); }
     TD_TRY(linear2(f, s, lin[QKV_IMG], lin[QKV_CTX], ln, T, Si, Epilogue::to(f->qkv, 3 * D)));
+    // IP-Adapter: ip = sum_a scale_a[i] * SDPA(norm_q(q_img), K_i^a, V_i^a) from the RAW image-row q -- here, because td_qk_norm_rope below
+    // normalises AND rotates q in place (the bf16 attention mode; the e4m3 mode keeps the raw q, the position is the same in both)
+    bool ip_blk = false;
+    for (int j = 0; j < n_ip; ++j) {
+      const td_flux::IpCtx& c = f->ip[ip_slots[j]];
+      const float sc = m->ip[ip_slots[j]].scale[i];
+      if (sc == 0.0f) continue;
+      const bf16_t* Ki = c.kv + (size_t)(2 * i) * c.keys_pad * D;
+      TraceScope ts(f, s, TD_TRACE_ATTN, 4.0 * Si * (double)c.n_keys * H * 128.0);
+      TD_TRY(td_ip_attention_launch(f->qkv + (size_t)T * 3 * D, 3 * D, Ki, Ki + (size_t)c.keys_pad * D, D, f->ip_out, D, Si, H, c.n_keys, b.norm_q, 1e-6f,
+                                    sc, ip_blk ? 1 : 0, s));
+      ip_blk = true;
+    }
     // QK-RMSNorm + RoPE -> joint attention
     rp.wqA = b.norm_added_q; rp.wkA = b.norm_added_k; rp.wqB = b.norm_q; rp.wkB = b.norm_k;
     if (!rope_in_pack) TD_TRY(qk_rope(f, s, rp));
@@ -606,6 +627,10 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
     }
     const Rows mo{f->mlp, M, f->aq, M, ff_hist ? hm.scale : f->as_};
     TD_TRY(linear2(f, s, lin[FF2_IMG], lin[FF2_CTX], mo, T, Si, Epilogue::to(h, D).gated_residual(mi + 5 * D, mc + 5 * D)));
+    if (ip_blk) {      // hidden = hidden + ip: one bf16 add behind the gated FF residual (scale 1.0: bf16(1.0 x ip) is ip)
+      TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
+      TD_TRY(td_flux_residual_inject_launch(h_img, D, f->ip_out, D, Si, D, 1.0f, s));
+    }
     if (hook) TD_TRY((*hook)(false, i));
   }
 
@@ -693,6 +718,14 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
   TD_CHECK_ARG(!m->controlnet, "td_flux_forward: a ControlNet context has no velocity (td_flux_controlnet_forward runs it; td_flux_attach_controlnet makes a "
                "main context run it)");
   TD_TRY(check_prepared("td_flux_forward", f, step));
+  for (int a = 0; a < TD_IP_MAX_ADAPTERS; ++a) {
+    if (!f->ip[a].set) continue;
+    TD_CHECK_ARG(m->ip[a].used && f->ip[a].epoch == m->ip[a].epoch, "td_flux_forward: the weights of IP-Adapter slot %d changed since td_flux_set_ip_image_embeds on this "
+                 "context (td_flux_ip_adapter_load_param / _remove; its K / V are values of the old ones): set the image embeds again, or clear them", a);
+    TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: IP-Adapter slot %d holds an image prompt and the context %d reference tokens (the image rows would include "
+                 "the reference rows): that pairing is not built", a, f->S_ref);
+    TD_CHECK_ARG(!f->cn, "td_flux_forward: IP-Adapter slot %d holds an image prompt and a ControlNet is attached: that pairing is not built", a);
+  }
   hipStream_t s = (hipStream_t)stream;
   td_flux* const cn = f->cn;
   const float sc = cn ? ((size_t)step < f->cn_scales.size() ? f->cn_scales[step] : 1.0f) : 0.0f;
@@ -791,6 +824,89 @@ int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n) {
   TD_CHECK_ARG(n <= f->m->max_steps, "td_flux_set_controlnet_scales: n=%d exceeds the %d steps of capacity", n, f->m->max_steps);
   for (int i = 0; i < n; ++i) TD_CHECK_ARG(std::isfinite(scales[i]), "td_flux_set_controlnet_scales: scale %d is not finite", i);
   f->cn_scales.assign(scales, scales + n);
+  return TD_OK;
+}
+
+// The image prompt of one image for IP-Adapter slot `slot` on THIS context (include/thinkdiff_hip.h spells the arithmetic): the projection and the
+// 2 L K / V Linears, once; every forward of the context then reads the arena.  NULL clears.
+int td_flux_set_ip_image_embeds(td_flux* f, int slot, const void* embeds, int n_img, void* stream) {
+  TD_CHECK_ARG(f, "td_flux_set_ip_image_embeds: null context");
+  TD_CHECK_ARG(slot >= 0 && slot < TD_IP_MAX_ADAPTERS, "td_flux_set_ip_image_embeds: slot %d outside 0 .. %d", slot, TD_IP_MAX_ADAPTERS - 1);
+  td_flux::IpCtx& c = f->ip[slot];
+  if (!embeds) { c.set = false; return TD_OK; }
+  FluxModel* const m = f->m;
+  TD_CHECK_ARG(!m->controlnet, "td_flux_set_ip_image_embeds: a ControlNet context takes no image prompt");
+  const IpAdapter& a = m->ip[slot];
+  TD_CHECK_ARG(a.used, "td_flux_set_ip_image_embeds: slot %d holds no adapter (td_flux_ip_adapter_add)", slot);
+  for (const auto& kv : a.params)
+    TD_CHECK_ARG(kv.second.loaded, "td_flux_set_ip_image_embeds: parameter '%s' of slot %d is not loaded (td_flux_ip_adapter_load_param)", kv.first.c_str(), slot);
+  TD_CHECK_ARG(n_img >= 1, "td_flux_set_ip_image_embeds: n_img=%d", n_img);
+  TD_CHECK_ARG((long long)n_img * a.num_tokens <= TD_IP_MAX_KEYS, "td_flux_set_ip_image_embeds: %d images x %d tokens = %lld keys exceed TD_IP_MAX_KEYS = %d", n_img,
+               a.num_tokens, (long long)n_img * a.num_tokens, TD_IP_MAX_KEYS);
+  TD_CHECK_ARG((uintptr_t)embeds % 16 == 0, "td_flux_set_ip_image_embeds: embeds must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t J = m->cfg.joint_dim, D = m->D, L = m->cfg.num_layers;
+  const int n_keys = n_img * a.num_tokens, keys_pad = (n_keys + 31) & ~31;
+  auto up = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+  const int64_t b_stage = up((int64_t)n_img * a.E_pad * 2), b_proj = up((int64_t)n_keys * J * 2), b_kv = up(L * 2 * keys_pad * D * 2);
+  const int64_t need = b_stage + 2 * b_proj + b_kv;
+  c.set = false;
+  if (need > c.bytes) {      // first use, or more keys than before (hipFree waits for the device: nobody reads the old arena any more)
+    if (c.buf) (void)hipFree(c.buf);
+    c.buf = nullptr; c.bytes = 0;
+    hipError_t e = hipMalloc((void**)&c.buf, (size_t)need);
+    if (e != hipSuccess) {
+      td_set_error("td_flux_set_ip_image_embeds: hipMalloc of %.1f MiB for slot %d failed: %s", need / double(1 << 20), slot, hipGetErrorString(e));
+      return TD_ERR_HIP;
+    }
+    c.bytes = need;
+  }
+  if (!f->ip_out) {
+    hipError_t e = hipMalloc((void**)&f->ip_out, (size_t)m->max_img * D * 2);
+    if (e != hipSuccess) {
+      td_set_error("td_flux_set_ip_image_embeds: hipMalloc of the %d x %lld output buffer failed: %s", m->max_img, (long long)D, hipGetErrorString(e));
+      return TD_ERR_HIP;
+    }
+  }
+  c.stage = (bf16_t*)c.buf; c.projd = (bf16_t*)(c.buf + b_stage); c.tokens = (bf16_t*)(c.buf + b_stage + b_proj); c.kv = (bf16_t*)(c.buf + b_stage + 2 * b_proj);
+  c.n_img = n_img; c.n_keys = n_keys; c.keys_pad = keys_pad;
+  // embeds -> rows of E_pad (zeros behind E), then tokens = LayerNorm_J(proj(embeds).reshape(n_keys, J))
+  TD_CHECK_HIP(hipMemsetAsync(c.stage, 0, (size_t)b_stage, s));
+  TD_CHECK_HIP(hipMemcpy2DAsync(c.stage, (size_t)a.E_pad * 2, embeds, (size_t)a.E * 2, (size_t)a.E * 2, (size_t)n_img, hipMemcpyDeviceToDevice, s));
+  auto par = [&](const std::string& name) { return a.params.at(name).ptr; };
+  FluxLinear proj;
+  proj.w = par("image_proj.proj.weight"); proj.b = par("image_proj.proj.bias"); proj.N = (int)(a.num_tokens * J); proj.K = a.E_pad;
+  TD_TRY(linear(f, s, proj, bf16_rows(c.stage, a.E_pad), n_img, Epilogue::to(c.projd, proj.N)));
+  TD_TRY(td_norm_rows_generic_launch(c.projd, (int)J, c.tokens, (int)J, n_keys, (int)J, 0, 1e-5f, par("image_proj.norm.weight"), par("image_proj.norm.bias"), s));
+  TD_CHECK_HIP(hipMemsetAsync(c.kv, 0, (size_t)b_kv, s));
+  for (int i = 0; i < L; ++i)
+    for (int w = 0; w < 2; ++w) {
+      const std::string base = "ip_adapter." + std::to_string(i) + (w ? ".to_v_ip" : ".to_k_ip");
+      FluxLinear l;
+      l.w = par(base + ".weight"); l.b = par(base + ".bias"); l.N = (int)D; l.K = (int)J;
+      TD_TRY(linear(f, s, l, bf16_rows(c.tokens, (int)J), n_keys, Epilogue::to(c.kv + (size_t)(2 * i + w) * keys_pad * D, (int)D)));
+    }
+  c.epoch = a.epoch;
+  c.set = true;
+  return TD_OK;
+}
+
+int td_flux_ip_read(const td_flux* f, int slot, int block, int which, void* dst, void* stream) {
+  TD_CHECK_ARG(f && dst && slot >= 0 && slot < TD_IP_MAX_ADAPTERS, "td_flux_ip_read: null argument or slot %d outside 0 .. %d", slot, TD_IP_MAX_ADAPTERS - 1);
+  const td_flux::IpCtx& c = f->ip[slot];
+  TD_CHECK_ARG(c.set, "td_flux_ip_read: slot %d holds no image prompt on this context", slot);
+  const FluxModel* m = f->m;
+  TD_CHECK_ARG(block < m->cfg.num_layers && (which == 0 || which == 1), "td_flux_ip_read: block %d of %d, which=%d (0 = K, 1 = V)", block, m->cfg.num_layers, which);
+  const bf16_t* src = block < 0 ? c.tokens : c.kv + (size_t)(2 * block + which) * c.keys_pad * m->D;
+  const size_t width = block < 0 ? (size_t)m->cfg.joint_dim : (size_t)m->D;
+  TD_CHECK_HIP(hipMemcpyAsync(dst, src, (size_t)c.n_keys * width * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TD_OK;
+}
+
+int td_flux_ip_widths(const td_flux* f, int* joint_dim, int* inner_dim) {
+  TD_CHECK_ARG(f, "td_flux_ip_widths: null context");
+  if (joint_dim) *joint_dim = f->m->cfg.joint_dim;
+  if (inner_dim) *inner_dim = f->m->D;
   return TD_OK;
 }
 

@@ -43,6 +43,27 @@ struct LoraState {
   std::unordered_map<int, bf16_t*> base;      // slot -> base copy
 };
 
+// IP-Adapter (td_flux_ip_adapter_*; root context; [ext] diffusers FluxIPAdapterMixin, restated).  One slot = one adapter: the image projection
+// (Linear E -> num_tokens x J, LayerNorm over J) and, per double block, to_k_ip / to_v_ip (Linear J -> D, bias).  All of it stays bf16 in every
+// precision mode, in ONE allocation of its own (adapters come and go; the fused weight arena does not move).  proj.weight is held with its rows
+// zero-padded to E_pad = a multiple of the GEMM's k-tile (the padding adds exact zeros).
+struct IpParam {
+  bf16_t* ptr;
+  int64_t count;           // elements the caller supplies: rows x cols
+  int rows, cols, ld;      // ld: row stride in the allocation (cols, or E_pad for proj.weight)
+  bool loaded;
+};
+struct IpAdapter {
+  bool used = false;
+  int num_tokens = 0, E = 0, E_pad = 0;
+  bf16_t* w = nullptr;
+  std::unordered_map<std::string, IpParam> params;
+  std::vector<float> scale;      // per double block (td_flux_set_ip_adapter_scale; default 1.0)
+  // td_flux_ip_adapter_add / _load_param / _remove give the slot a new epoch (from FluxModel::ip_epoch); td_flux_set_ip_image_embeds records it on
+  // its context -- the K / V it computed are values of these weights -- and a forward refuses a context whose record is older.
+  int epoch = 0;
+};
+
 // 8-bit modes (td_flux_set_precision): e4m3 / int8 copy of a block weight [rows, K] + one dequantisation scale per output channel
 struct Fp8Mat {
   uint8_t* q = nullptr;
@@ -124,6 +145,8 @@ struct FluxModel {
   float *sm_s = nullptr, *sm_inv = nullptr;         // s, 1 / s
   bf16_t* sm_inv16 = nullptr;                       // 1 / s as bf16 (the LayerNorm and GEMM epilogue kernels read it beside their bf16 operands)
   LoraState* lora = nullptr;
+  IpAdapter ip[TD_IP_MAX_ADAPTERS];
+  int ip_epoch = 0;
   // td_flux_lora_set_adapters / delete / clear bump the weight epoch; td_flux_set_condition / td_flux_set_timesteps record it on their context
   // (both precompute values from weights), and a forward refuses a context prepared under an older one.
   int weight_epoch = 0;
@@ -201,6 +224,19 @@ struct td_flux {
   // On a main context: the attached ControlNet context and the conditioning scale of every prepared step (host floats; missing entries are 1.0)
   td_flux* cn = nullptr;
   std::vector<float> cn_scales;
+  // ---- IP-Adapter: per slot the image-prompt tokens of THIS image and every double block's K / V of them (td_flux_set_ip_image_embeds; one
+  // allocation per slot, made at first use and grown when a later call needs more): staging [n_img, E_pad] | projection [n_img, num_tokens J] |
+  // tokens [n_keys, J] | kv [L][K, V][keys_pad][D] (rows n_keys .. keys_pad zero).  ip_out [max_img, D]: the sum over the active slots of one
+  // block, written by td_ip_attention before the block's RoPE and added to the image rows behind its FF (first use as well).
+  struct IpCtx {
+    bool set = false;
+    int n_img = 0, n_keys = 0, keys_pad = 0, epoch = -1;
+    char* buf = nullptr;
+    int64_t bytes = 0;
+    bf16_t *stage = nullptr, *projd = nullptr, *tokens = nullptr, *kv = nullptr;
+  };
+  IpCtx ip[TD_IP_MAX_ADAPTERS];
+  bf16_t* ip_out = nullptr;
   // optional per-launch HIP-event trace (bench.py roofline leg)
   bool tracing = false;
   std::vector<hipEvent_t> ev_pool;

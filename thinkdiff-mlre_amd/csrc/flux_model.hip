@@ -191,6 +191,7 @@ void flux_model_destroy(FluxModel* m) {
     for (auto& b : m->lora->base) (void)hipFree(b.second);
     delete m->lora;
   }
+  for (IpAdapter& a : m->ip) if (a.w) (void)hipFree(a.w);
   (void)hipFree(m->arena);
   if (m->arena8) (void)hipFree(m->arena8);
   if (m->sm_ax) (void)hipFree(m->sm_ax);      // one allocation: ax | aw | s | inv | inv16
@@ -698,6 +699,111 @@ int td_flux_lora_info(const td_flux* f, int* n_adapters, int* n_params_touched, 
   if (n_adapters) *n_adapters = ls ? (int)ls->adapters.size() : 0;
   if (n_params_touched) *n_params_touched = ls ? (int)ls->base.size() : 0;
   if (bytes_held) *bytes_held = bytes;
+  return TD_OK;
+}
+
+// ---- IP-Adapter slots (the model's half; td_flux_set_ip_image_embeds and the block loop's half are in csrc/flux_engine.hip) ------------------------
+static int ip_slot_arg(const char* fn, const td_flux* f, int slot) {
+  TD_CHECK_ARG(f, "%s: null handle", fn);
+  TD_CHECK_ARG(f->root, "%s: adapters belong to the parent context (forks share its model)", fn);
+  TD_CHECK_ARG(!f->m->controlnet, "%s: a ControlNet takes no IP-Adapter", fn);
+  TD_CHECK_ARG(slot >= 0 && slot < TD_IP_MAX_ADAPTERS, "%s: slot %d outside 0 .. %d", fn, slot, TD_IP_MAX_ADAPTERS - 1);
+  return TD_OK;
+}
+
+static void ip_free_slot(FluxModel* m, int slot) {
+  IpAdapter& a = m->ip[slot];
+  if (a.w) (void)hipFree(a.w);
+  a = IpAdapter();
+  a.epoch = ++m->ip_epoch;      // contexts that hold K / V of the old weights are stale
+}
+
+int td_flux_ip_adapter_add(td_flux* f, int num_tokens, int embed_dim, int* slot_out) {
+  TD_TRY(ip_slot_arg("td_flux_ip_adapter_add", f, 0));
+  TD_CHECK_ARG(slot_out, "td_flux_ip_adapter_add: null slot pointer");
+  TD_CHECK_ARG(num_tokens >= 1 && num_tokens <= TD_IP_MAX_KEYS, "td_flux_ip_adapter_add: num_tokens=%d outside 1 .. %d (TD_IP_MAX_KEYS)", num_tokens, TD_IP_MAX_KEYS);
+  TD_CHECK_ARG(embed_dim >= 8 && embed_dim % 8 == 0 && embed_dim <= 65536, "td_flux_ip_adapter_add: embed_dim=%d must be a multiple of 8 in 8 .. 65536", embed_dim);
+  FluxModel* m = f->m;
+  int slot = -1;
+  for (int i = 0; i < TD_IP_MAX_ADAPTERS && slot < 0; ++i) if (!m->ip[i].used) slot = i;
+  TD_CHECK_ARG(slot >= 0, "td_flux_ip_adapter_add: all %d slots are taken (td_flux_ip_adapter_remove frees one)", TD_IP_MAX_ADAPTERS);
+  IpAdapter a;
+  a.num_tokens = num_tokens; a.E = embed_dim; a.E_pad = (embed_dim + 63) & ~63;
+  const int64_t J = m->cfg.joint_dim, D = m->D, L = m->cfg.num_layers, NJ = (int64_t)num_tokens * J;
+  const int64_t total = NJ * a.E_pad + NJ + 2 * J + L * 2 * (D * J + D);
+  hipError_t e = hipMalloc((void**)&a.w, (size_t)total * 2);
+  if (e != hipSuccess) {
+    td_set_error("td_flux_ip_adapter_add: hipMalloc of %.2f GiB of adapter weights failed: %s", total * 2 / double(1 << 30), hipGetErrorString(e));
+    return TD_ERR_HIP;
+  }
+  TD_CHECK_HIP(hipMemset(a.w, 0, (size_t)total * 2));      // (the padding columns of proj.weight stay zero)
+  bf16_t* p = a.w;
+  auto put = [&](const std::string& name, int64_t rows, int64_t cols, int64_t ld) {
+    a.params[name] = IpParam{p, rows * cols, (int)rows, (int)cols, (int)ld, false};
+    p += rows * ld;
+  };
+  put("image_proj.proj.weight", NJ, a.E, a.E_pad);
+  put("image_proj.proj.bias", 1, NJ, NJ);
+  put("image_proj.norm.weight", 1, J, J);
+  put("image_proj.norm.bias", 1, J, J);
+  for (int i = 0; i < L; ++i)
+    for (const char* kv : {"to_k_ip", "to_v_ip"}) {
+      const std::string base = "ip_adapter." + std::to_string(i) + "." + kv;
+      put(base + ".weight", D, J, J);
+      put(base + ".bias", 1, D, D);
+    }
+  a.scale.assign((size_t)L, 1.0f);
+  a.used = true;
+  a.epoch = ++m->ip_epoch;
+  m->ip[slot] = std::move(a);
+  *slot_out = slot;
+  return TD_OK;
+}
+
+int td_flux_ip_adapter_load_param(td_flux* f, int slot, const char* name, const void* data, int64_t count, void* stream) {
+  TD_TRY(ip_slot_arg("td_flux_ip_adapter_load_param", f, slot));
+  TD_CHECK_ARG(name && data, "td_flux_ip_adapter_load_param: null argument");
+  IpAdapter& a = f->m->ip[slot];
+  TD_CHECK_ARG(a.used, "td_flux_ip_adapter_load_param: '%s': slot %d holds no adapter (td_flux_ip_adapter_add)", name, slot);
+  auto it = a.params.find(name);
+  TD_CHECK_ARG(it != a.params.end(), "td_flux_ip_adapter_load_param: unknown parameter '%s' (slot %d: %d tokens, %d double blocks)", name, slot, a.num_tokens,
+               f->m->cfg.num_layers);
+  IpParam& q = it->second;
+  TD_CHECK_ARG(q.count == count, "td_flux_ip_adapter_load_param: '%s' expects %lld elements ([%d, %d]), got %lld", name, (long long)q.count, q.rows, q.cols, (long long)count);
+  TD_CHECK_HIP(hipMemcpy2DAsync(q.ptr, (size_t)q.ld * 2, data, (size_t)q.cols * 2, (size_t)q.cols * 2, (size_t)q.rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  q.loaded = true;
+  a.epoch = ++f->m->ip_epoch;
+  return TD_OK;
+}
+
+int td_flux_ip_adapter_remove(td_flux* f, int slot) {
+  TD_TRY(ip_slot_arg("td_flux_ip_adapter_remove", f, slot < 0 ? 0 : slot));
+  TD_CHECK_ARG(slot >= -1, "td_flux_ip_adapter_remove: slot %d (-1 removes all)", slot);
+  TD_CHECK_HIP(hipDeviceSynchronize());      // a context may still be computing K / V from these weights
+  for (int i = 0; i < TD_IP_MAX_ADAPTERS; ++i)
+    if ((slot < 0 || slot == i) && f->m->ip[i].used) ip_free_slot(f->m, i);
+  return TD_OK;
+}
+
+int td_flux_set_ip_adapter_scale(td_flux* f, int slot, const float* per_block, int n) {
+  TD_TRY(ip_slot_arg("td_flux_set_ip_adapter_scale", f, slot));
+  IpAdapter& a = f->m->ip[slot];
+  const int L = f->m->cfg.num_layers;
+  TD_CHECK_ARG(a.used, "td_flux_set_ip_adapter_scale: slot %d holds no adapter", slot);
+  TD_CHECK_ARG(per_block && (n == 1 || n == L), "td_flux_set_ip_adapter_scale: %d scales given; one for all blocks or one per double block (%d)", n, L);
+  for (int i = 0; i < n; ++i) TD_CHECK_ARG(std::isfinite(per_block[i]), "td_flux_set_ip_adapter_scale: scale %d is not finite", i);
+  for (int i = 0; i < L; ++i) a.scale[i] = per_block[n == 1 ? 0 : i];
+  return TD_OK;
+}
+
+int td_flux_ip_adapter_info(const td_flux* f, int slot, int* used, int* num_tokens, int* embed_dim, int* embeds_set, int* n_keys) {
+  TD_CHECK_ARG(f && slot >= 0 && slot < TD_IP_MAX_ADAPTERS, "td_flux_ip_adapter_info: null handle or slot %d outside 0 .. %d", slot, TD_IP_MAX_ADAPTERS - 1);
+  const IpAdapter& a = f->m->ip[slot];
+  if (used) *used = a.used;
+  if (num_tokens) *num_tokens = a.num_tokens;
+  if (embed_dim) *embed_dim = a.E;
+  if (embeds_set) *embeds_set = f->ip[slot].set;
+  if (n_keys) *n_keys = f->ip[slot].set ? f->ip[slot].n_keys : 0;
   return TD_OK;
 }
 

@@ -161,6 +161,57 @@ at::Tensor& flux_residual_inject_(at::Tensor& h, const at::Tensor& r, double sca
   return h;
 }
 
+// FLUX IP-Adapter cross-attention (td_ip_attention_bf16): q [rows, >= H*128] (raw projection rows when norm_w is given: the per-head QK-RMSNorm is
+// fused), k / v [n_keys, >= H*128] with equal strides, 1 <= n_keys <= TD_IP_MAX_KEYS -> bf16(out_scale * softmax(qn k^T / sqrt(128)) v) [rows, H*128]
+void check_ip(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t H, const c10::optional<at::Tensor>& norm_w) {
+  check_rows(q, "q"); check_rows(k, "k"); check_rows(v, "v"); same_device(k, "k", q); same_device(v, "v", q);
+  TORCH_CHECK(q.dim() == 2 && k.dim() == 2 && v.dim() == 2 && k.sizes() == v.sizes() && k.strides() == v.strides(), "thinkdiff_hip::", op,
+              ": q [rows, cols], k / v [n_keys, cols] with equal shapes and strides");
+  TORCH_CHECK(H > 0 && q.size(1) >= H * 128 && k.size(1) >= H * 128, "thinkdiff_hip::", op, ": q and k / v need >= H*128 = ", H * 128, " columns (got ", q.size(1), ", ",
+              k.size(1), ")");
+  TORCH_CHECK(q.size(0) >= 1 && q.size(0) < (1ll << 31), "thinkdiff_hip::", op, ": q needs 1 .. 2^31 - 1 rows");
+  check_vec(norm_w, "norm_w", q, 128);
+}
+at::Tensor ip_attention(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t H, const c10::optional<at::Tensor>& norm_w, double eps, double out_scale) {
+  check_ip("ip_attention", q, k, v, H, norm_w);
+  DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({q.size(0), H * 128}, q.options());
+  ok(td_ip_attention_bf16(q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0), o.data_ptr(), o.stride(0), (int)q.size(0), (int)H, (int)k.size(0),
+                          P(norm_w), (float)eps, (float)out_scale, 0, stream_of(q)));
+  return o;
+}
+// the same into o [rows, >= H*128] (columns beyond H*128 stay); accumulate: o = bf16(o + term), the sum over several adapters
+at::Tensor& ip_attention_(at::Tensor& o, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t H, const c10::optional<at::Tensor>& norm_w, double eps,
+                          double out_scale, bool accumulate) {
+  check_ip("ip_attention_", q, k, v, H, norm_w);
+  check_rows(o, "o"); same_device(o, "o", q);
+  TORCH_CHECK(o.dim() == 2 && o.size(0) == q.size(0) && o.size(1) >= H * 128, "thinkdiff_hip::ip_attention_: o must be [rows, >= H*128]");
+  DeviceGuard guard(q.device());
+  ok(td_ip_attention_bf16(q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0), o.data_ptr(), o.stride(0), (int)q.size(0), (int)H, (int)k.size(0),
+                          P(norm_w), (float)eps, (float)out_scale, accumulate ? 1 : 0, stream_of(q)));
+  return o;
+}
+// one parameter of an IP-Adapter slot (td_flux_ip_adapter_load_param; the engine checks the name and the element count)
+void flux_ip_adapter_load_param(int64_t engine, int64_t slot, std::string name, const at::Tensor& data) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  check_rows(data, "data");
+  TORCH_CHECK(data.is_contiguous(), "thinkdiff_hip::flux_ip_adapter_load_param: '", name, "' must be contiguous");
+  DeviceGuard guard(data.device());
+  ok(td_flux_ip_adapter_load_param((td_flux*)(uintptr_t)engine, (int)slot, name.c_str(), data.data_ptr(), data.numel(), stream_of(data)));
+}
+// the image prompt of one image on this context (td_flux_set_ip_image_embeds): embeds [n_img, E] against the slot's embed_dim
+void flux_set_ip_image_embeds(int64_t engine, int64_t slot, const at::Tensor& embeds) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  td_flux* f = (td_flux*)(uintptr_t)engine;
+  int used = 0, E = 0;
+  ok(td_flux_ip_adapter_info(f, (int)slot, &used, nullptr, &E, nullptr, nullptr));
+  check_rows(embeds, "embeds");
+  TORCH_CHECK(!used || (embeds.dim() == 2 && embeds.is_contiguous() && embeds.size(1) == E && embeds.size(0) >= 1), "thinkdiff_hip::flux_set_ip_image_embeds: slot ", slot,
+              " takes contiguous embeds [n_img, ", E, "], got ", embeds.sizes());
+  DeviceGuard guard(embeds.device());
+  ok(td_flux_set_ip_image_embeds(f, (int)slot, embeds.data_ptr(), embeds.dim() == 2 ? (int)embeds.size(0) : 0, stream_of(embeds)));
+}
+
 // FluxInpaintPipeline's step in place: Euler step, scale_noise of the image latents to bf16(sigma_next) (noise None: the clean latents) and
 // the mask blend, every op a bf16 torch op (td_flux_inpaint_step_bf16)
 at::Tensor& flux_inpaint_step_(at::Tensor& x, const at::Tensor& v, const at::Tensor& image_latents, const c10::optional<at::Tensor>& noise,
@@ -541,6 +592,17 @@ at::Tensor flux_read_param(int64_t engine, std::string name) {
   ok(td_flux_read_param(f, name.c_str(), out.data_ptr(), out.numel(), current_stream()));
   return out;
 }
+// tests: a context's image-prompt tokens (block < 0) or double block `block`'s K (which 0) / V (1) of an IP-Adapter slot, as a new tensor
+at::Tensor flux_ip_read(int64_t engine, int64_t slot, int64_t block, int64_t which) {
+  TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
+  td_flux* f = (td_flux*)(uintptr_t)engine;
+  int set = 0, n_keys = 0, D = 0, J = 0;
+  ok(td_flux_ip_adapter_info(f, (int)slot, nullptr, nullptr, nullptr, &set, &n_keys));
+  ok(td_flux_ip_widths(f, &J, &D));
+  at::Tensor out = at::empty({n_keys, block < 0 ? J : D}, at::TensorOptions().dtype(at::kBFloat16).device(at::kCUDA));
+  ok(td_flux_ip_read(f, (int)slot, (int)block, (int)which, out.data_ptr(), current_stream()));
+  return out;
+}
 void flux_lora_set_adapters(int64_t engine, std::vector<std::string> names, at::ArrayRef<double> weights) {
   TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
   TORCH_CHECK(names.size() == weights.size(), "thinkdiff_hip::flux_lora_set_adapters: ", names.size(), " names, ", weights.size(), " weights");
@@ -588,6 +650,11 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
   m.def("lora_merge(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor");
   m.def("lora_merge_(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)");
+  m.def("ip_attention(Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale) -> Tensor");
+  m.def("ip_attention_(Tensor(a!) o, Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale, bool accumulate) -> Tensor(a!)");
+  m.def("flux_ip_adapter_load_param(int engine, int slot, str name, Tensor data) -> ()");
+  m.def("flux_set_ip_image_embeds(int engine, int slot, Tensor embeds) -> ()");
+  m.def("flux_ip_read(int engine, int slot, int block, int which) -> Tensor");
   m.def("flux_read_param(int engine, str name) -> Tensor");
   m.def("flux_lora_load(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()");
   m.def("flux_lora_set_adapters(int engine, str[] names, float[] weights) -> ()");
@@ -626,10 +693,15 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("lora_merge", &lora_merge);
   m.impl("lora_merge_", &lora_merge_);
   m.impl("flux_lora_load", &flux_lora_load);
+  m.impl("ip_attention", &ip_attention);
+  m.impl("ip_attention_", &ip_attention_);
+  m.impl("flux_ip_adapter_load_param", &flux_ip_adapter_load_param);
+  m.impl("flux_set_ip_image_embeds", &flux_set_ip_image_embeds);
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {
   m.impl("flux_read_param", &flux_read_param);
+  m.impl("flux_ip_read", &flux_ip_read);
   m.impl("flux_lora_set_adapters", &flux_lora_set_adapters);
   m.impl("flux_lora_delete", &flux_lora_delete);
 }

@@ -94,6 +94,15 @@ def _declare(L):
         "td_flux_lora_delete": [vp, ctypes.c_char_p, vp],
         "td_flux_lora_clear": [vp, vp],
         "td_flux_lora_info": [vp, vp, vp, vp],
+        "td_ip_attention_bf16": [vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, vp, f32, f32, i32, vp],
+        "td_flux_ip_adapter_add": [vp, i32, i32, vp],
+        "td_flux_ip_adapter_load_param": [vp, i32, ctypes.c_char_p, vp, i64, vp],
+        "td_flux_ip_adapter_remove": [vp, i32],
+        "td_flux_set_ip_adapter_scale": [vp, i32, vp, i32],
+        "td_flux_ip_adapter_info": [vp, i32, vp, vp, vp, vp, vp],
+        "td_flux_set_ip_image_embeds": [vp, i32, vp, i32, vp],
+        "td_flux_ip_read": [vp, i32, i32, i32, vp, vp],
+        "td_flux_ip_widths": [vp, vp, vp],
         "td_flux_fork": [vp, vp],
         "td_flux_denoise_multi": [vp, vp, i32, vp, i32, vp],
         "td_flux_denoise_multi_inpaint": [vp, vp, i32, vp, i32, vp, vp, vp, vp],

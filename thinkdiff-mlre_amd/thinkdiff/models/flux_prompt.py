@@ -163,6 +163,61 @@ class FluxPipelineRewritePrompt:
             raise NotImplementedError("joint_attention_kwargs={'scale': ...} (a per-call LoRA scale) is not built: adapters are merged into the "
                                       "weights; use set_adapters(names, weights) before the call")
 
+    # ---- IP-Adapter ([ext] diffusers FluxIPAdapterMixin; thinkdiff.models.flux_ip_adapter holds the specification) ----------------------
+    def load_ip_adapter(self, path_or_dict, weight_name: Optional[str] = None, image_encoder=None, feature_extractor=None, **_ignored):
+        """One adapter from a local .safetensors file, a directory + weight_name, or a state dict (diffusers or XLabs keys); no hub.  Call again
+        for a further adapter (up to 4).  image_encoder: an optional torch module whose output has `.image_embeds` (with feature_extractor, if the
+        images are not tensors yet) -- it serves `ip_adapter_image`; there is no HIP image encoder, `ip_adapter_image_embeds` needs none."""
+        idx = self.transformer.load_ip_adapter(path_or_dict, weight_name=weight_name)
+        if image_encoder is not None:
+            self.image_encoder, self.feature_extractor = image_encoder, feature_extractor
+        return idx
+
+    def set_ip_adapter_scale(self, scale):
+        self.transformer.set_ip_adapter_scale(scale)
+
+    def unload_ip_adapter(self):
+        for ctx in self._ctx_pool[1:]:
+            ctx.set_ip_image_embeds(None)
+        self.transformer.unload_ip_adapter()
+        self.image_encoder = self.feature_extractor = None
+
+    def encode_image(self, image):
+        """`ip_adapter_image` of one adapter (an image, a tensor [n_img, 3, h, w] or a list of images) -> embeds [n_img, E] through the
+        caller-supplied image encoder; once per call."""
+        enc = getattr(self, "image_encoder", None)
+        if enc is None:
+            raise ValueError("ip_adapter_image needs an image encoder (load_ip_adapter(..., image_encoder=...)); without one pass ip_adapter_image_embeds")
+        if not isinstance(image, torch.Tensor):
+            fe = getattr(self, "feature_extractor", None)
+            if fe is None:
+                raise ValueError("ip_adapter_image: images that are not tensors need a feature_extractor (load_ip_adapter(..., feature_extractor=...))")
+            image = fe(images=image, return_tensors="pt").pixel_values
+        if image.dim() == 3:
+            image = image[None]
+        p = next(iter(enc.parameters()), None) if hasattr(enc, "parameters") else None
+        if p is not None:
+            image = image.to(device=p.device, dtype=p.dtype)
+        return enc(image).image_embeds
+
+    def _ip_call_embeds(self, batch, ip_adapter_image, ip_adapter_image_embeds, negative_ip_adapter_image, negative_ip_adapter_image_embeds):
+        """The IP arguments of a call -> None, or per adapter a [1 or batch, n_img, E] tensor."""
+        from . import flux_ip_adapter as ipa
+        if negative_ip_adapter_image is not None or negative_ip_adapter_image_embeds is not None:
+            raise NotImplementedError("negative_ip_adapter_image / negative_ip_adapter_image_embeds: a negative image prompt needs true classifier-free "
+                                      "guidance, which only FluxKontextPipeline runs here")
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            return None
+        loaded = self.transformer.ip_adapters()
+        if not loaded:
+            raise ValueError("ip_adapter_image / ip_adapter_image_embeds were passed and no IP-Adapter is loaded (load_ip_adapter first)")
+        if ip_adapter_image_embeds is None:
+            images = ip_adapter_image if isinstance(ip_adapter_image, list) and len(loaded) > 1 else [ip_adapter_image]
+            if len(images) != len(loaded):
+                raise ValueError(f"ip_adapter_image: {len(images)} entries for {len(loaded)} loaded adapters (one entry per adapter)")
+            ip_adapter_image_embeds = [self.encode_image(im) for im in images]
+        return ipa.normalize_image_embeds(ip_adapter_image_embeds, len(loaded), batch, [a["embed_dim"] for a in loaded])
+
     def to(self, *_a, **_k):
         return self  # the engine lives on the GPU it was created on
 
@@ -237,7 +292,8 @@ class FluxPipelineRewritePrompt:
     def __call__(self, prompt=None, prompt_2=None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 28, guidance_scale: float = 3.5, num_images_per_prompt: int = 1,
                  generator=None, latents=None, prompt_embeds=None, pooled_prompt_embeds=None,
-                 output_type: str = "pil", return_dict: bool = True, max_sequence_length: int = 512, **_ignored):
+                 output_type: str = "pil", return_dict: bool = True, max_sequence_length: int = 512, ip_adapter_image=None,
+                 ip_adapter_image_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None, **_ignored):
         self._refuse_call_scale(_ignored)
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
@@ -251,6 +307,9 @@ class FluxPipelineRewritePrompt:
         # The reference's encode_prompt does not tile supplied embeds (flux_prompt.py:83-86), so sample b
         # is conditioned on prompt b // num_images_per_prompt.
         B = prompt_embeds.shape[0] * num_images_per_prompt
+        # [ext] FluxIPAdapterMixin: the image prompt of sample b is entry b // num_images_per_prompt of every adapter's embeds
+        ip_embeds = self._ip_call_embeds(prompt_embeds.shape[0], ip_adapter_image, ip_adapter_image_embeds, negative_ip_adapter_image,
+                                         negative_ip_adapter_image_embeds)
         lat, h, w = self.prepare_latents(B, height, width, generator, latents)
         S_img = lat.shape[1]
         img_ids = self._prepare_latent_image_ids(h // 2, w // 2, lat.device)
@@ -258,11 +317,12 @@ class FluxPipelineRewritePrompt:
         t_eff = [effective_scalar(float(s) * self.scheduler.num_train_timesteps, tr.dtype) for s in sig[:-1]]
         g_eff = float((torch.tensor([guidance_scale], dtype=torch.float32).to(tr.dtype) * 1000).float()) \
             if tr.config.guidance_embeds else 0.0
-        xs = self._denoise_groups(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff)
+        xs = self._denoise_groups(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff,
+                                  ip_embeds=ip_embeds)
         return self._finish(xs, h, w, output_type, return_dict)
 
     def _denoise_groups(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff,
-                        inpaint=None, channel_cond=None, reference=None, cfg=None):
+                        inpaint=None, channel_cond=None, reference=None, cfg=None, ip_embeds=None):
         """The denoise loop over `sig` (any sigma list ending in 0: the full schedule or a truncated one) for the first B packed latents
         of `lat` [B, S, 64]; sample b is conditioned on prompt b // num_images_per_prompt.  Returns the B denoised latents.
         inpaint: None, or per sample b an (image_latents, noise, mask) triple of [S, 64] tensors made on the current stream (the
@@ -271,9 +331,14 @@ class FluxPipelineRewritePrompt:
         reference: None, or per sample b the (ref_latents [S_ref, 64], ref_ids [S_ref, 3]) reference tokens of FLUX.1 Kontext, set on the
         context that carries sample b right after its prompt (an entry may be None: no reference for that sample).
         cfg: None, or (negative_prompt_embeds, negative_pooled_prompt_embeds, negative_text_ids, true_cfg_scale): true classifier-free
-        guidance -- one (positive, negative) context pair on one stream, samples one after another (FluxTransformer2DModel.denoise_cfg)."""
+        guidance -- one (positive, negative) context pair on one stream, samples one after another (FluxTransformer2DModel.denoise_cfg).
+        ip_embeds: None, or per loaded IP-Adapter a [1 or n_prompts, n_img, E] tensor: the image prompt of sample b, set on the context that
+        carries it next to its prompt.  With adapters loaded and no image prompt the contexts' image prompts are cleared (the plain model)."""
         tr = self.transformer
         n_prompts = prompt_embeds.shape[0]
+        has_ip = bool(tr.ip_adapters())
+        if ip_embeds is not None and cfg is not None:
+            raise NotImplementedError("an image prompt under true classifier-free guidance is not built")
         if cfg is not None:
             if inpaint is not None or channel_cond is not None:
                 raise NotImplementedError("true classifier-free guidance is built for the plain and the reference-token loop only")
@@ -286,6 +351,8 @@ class FluxPipelineRewritePrompt:
                 with torch.cuda.stream(st):
                     for ctx, e, p, ids in ((pos, prompt_embeds, pooled_prompt_embeds, text_ids), (neg, neg_embeds, neg_pooled, neg_ids)):
                         ctx.set_condition(e[min(pb, e.shape[0] - 1)], p[min(pb, p.shape[0] - 1)], img_ids, ids)
+                        if has_ip:
+                            ctx.set_ip_image_embeds(None)
                         if reference is not None and reference[b] is not None:
                             ctx.set_reference_tokens(*reference[b])
                         ctx.set_timesteps(t_eff, g_eff)
@@ -309,6 +376,8 @@ class FluxPipelineRewritePrompt:
                 st.wait_stream(main)
                 with torch.cuda.stream(st):
                     ctxs[k].set_condition(prompt_embeds[pb], pooled_prompt_embeds[min(pb, pooled_prompt_embeds.shape[0] - 1)], img_ids, text_ids)
+                    if has_ip:
+                        ctxs[k].set_ip_image_embeds(None if ip_embeds is None else [e[min(pb, e.shape[0] - 1)] for e in ip_embeds])
                     if channel_cond is not None:
                         ctxs[k].set_channel_condition(channel_cond[b])
                     if reference is not None and reference[b] is not None:

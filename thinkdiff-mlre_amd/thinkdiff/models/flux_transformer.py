@@ -402,6 +402,92 @@ class FluxTransformer2DModel:
         _hip.check(self._L.td_flux_set_controlnet_scales(self._h, ctypes.cast(arr, ctypes.c_void_p), len(scales)))
         return self
 
+    # ---- IP-Adapter (thinkdiff.models.flux_ip_adapter; td_flux_ip_adapter_*) ------------------------------------
+    def ip_adapters(self) -> list:
+        """The loaded adapters in load order: dicts of slot, num_tokens, embed_dim (the root's; forks share them)."""
+        r = self._root()
+        if not hasattr(r, "_ip_loaded"):
+            r._ip_loaded = []
+        return r._ip_loaded
+
+    def load_ip_adapter(self, sd_or_path, weight_name: Optional[str] = None) -> int:
+        """diffusers' `_load_ip_adapter_weights` for one adapter: a state dict (diffusers or XLabs keys), a local .safetensors file, or a
+        directory + weight_name.  Adapters stack: the n-th call is adapter n of `set_ip_adapter_scale` / `set_ip_image_embeds`.  Its weights stay
+        bf16 in every precision mode; scale 1.0 until set.  Returns the adapter's index."""
+        from . import flux_ip_adapter as ipa
+        if getattr(self, "_parent", None) is not None:
+            raise _hip.ThinkDiffHipError("load_ip_adapter: adapters belong to the parent transformer (forks share its model)")
+        c = self.config
+        flat, num_tokens, embed_dim = ipa.load_ip_adapter_state_dict(sd_or_path, weight_name, num_layers=c.num_layers, joint_dim=c.joint_attention_dim,
+                                                                     inner_dim=c.num_attention_heads * c.attention_head_dim)
+        loaded = self.ip_adapters()
+        if len(loaded) >= ipa.TD_IP_MAX_ADAPTERS:
+            raise ValueError(f"load_ip_adapter: {ipa.TD_IP_MAX_ADAPTERS} adapters are loaded already (unload_ip_adapter first)")
+        if num_tokens > ipa.TD_IP_MAX_KEYS:
+            raise ValueError(f"load_ip_adapter: {num_tokens} tokens per image exceed the kernel's {ipa.TD_IP_MAX_KEYS} keys")
+        slot = ctypes.c_int(-1)
+        with torch.cuda.device(self.device):
+            _hip.check(self._L.td_flux_ip_adapter_add(self._h, num_tokens, embed_dim, ctypes.byref(slot)))
+            try:
+                for name, t in flat.items():
+                    d = t.to(self.device, torch.bfloat16).contiguous()
+                    _OPS.flux_ip_adapter_load_param(int(self._h.value), slot.value, name, d)
+                torch.cuda.current_stream().synchronize()      # `d` may be a temporary
+            except Exception:
+                self._L.td_flux_ip_adapter_remove(self._h, slot.value)      # no half-loaded adapter stays behind
+                raise
+        loaded.append(dict(slot=slot.value, num_tokens=num_tokens, embed_dim=embed_dim))
+        return len(loaded) - 1
+
+    def unload_ip_adapter(self):
+        """diffusers' unload_ip_adapter: drop every adapter and this context's image prompts (forks: clear theirs with set_ip_image_embeds(None);
+        a fork that still holds one refuses its forward and says so)."""
+        if getattr(self, "_parent", None) is not None:
+            raise _hip.ThinkDiffHipError("unload_ip_adapter: adapters belong to the parent transformer (forks share its model)")
+        self.set_ip_image_embeds(None)
+        _hip.check(self._L.td_flux_ip_adapter_remove(self._h, -1))
+        self.ip_adapters().clear()
+
+    def set_ip_adapter_scale(self, scale):
+        """A float (all adapters, all double blocks) or a list with one entry per adapter, each a float or `num_layers` per-block floats."""
+        from . import flux_ip_adapter as ipa
+        loaded = self.ip_adapters()
+        if not loaded:
+            raise ValueError("set_ip_adapter_scale: no IP-Adapter is loaded (load_ip_adapter)")
+        per = ipa.expand_scales(scale, len(loaded), self.config.num_layers)
+        root = self._root()
+        for a, s in zip(loaded, per):
+            arr = (ctypes.c_float * len(s))(*s)
+            _hip.check(self._L.td_flux_set_ip_adapter_scale(root._h, a["slot"], ctypes.cast(arr, ctypes.c_void_p), len(s)))
+
+    def set_ip_image_embeds(self, embeds):
+        """The image prompt of THIS context's image (forks hold their own): None clears; else one [n_img, E] tensor per adapter (a bare tensor with
+        one adapter loaded).  Computes the image-prompt tokens and every double block's K / V once (td_flux_set_ip_image_embeds)."""
+        loaded = self.ip_adapters()
+        h = int(self._h.value)
+        if embeds is None:
+            for slot in range(4):
+                _hip.check(self._L.td_flux_set_ip_image_embeds(self._h, slot, None, 0, None))
+            return
+        if not loaded:
+            raise ValueError("set_ip_image_embeds: no IP-Adapter is loaded (load_ip_adapter)")
+        if isinstance(embeds, torch.Tensor):
+            embeds = [embeds]
+        if len(embeds) != len(loaded):
+            raise ValueError(f"set_ip_image_embeds: {len(embeds)} entries for {len(loaded)} loaded adapters")
+        with torch.cuda.device(self.device):
+            for a, e in zip(loaded, embeds):
+                if e.dim() != 2 or e.shape[1] != a["embed_dim"]:
+                    raise ValueError(f"set_ip_image_embeds: adapter {a['slot']} takes [n_img, {a['embed_dim']}], got {tuple(e.shape)}")
+                d = e.to(self.device, torch.bfloat16).contiguous()
+                _OPS.flux_set_ip_image_embeds(h, a["slot"], d)
+            torch.cuda.current_stream().synchronize()      # `d` may be a temporary
+
+    def read_ip(self, adapter: int, block: int = -1, which: int = 0) -> torch.Tensor:
+        """Tests: this context's image-prompt tokens of adapter `adapter` (block < 0), or double block `block`'s K (which 0) / V (1)."""
+        with torch.cuda.device(self.device):
+            return _OPS.flux_ip_read(int(self._h.value), self.ip_adapters()[adapter]["slot"], int(block), int(which))
+
     # ---- per-launch HIP-event trace (bench.py roofline leg) ------------------------------------------
     TRACE_CATEGORIES = ("gemm_256x256", "gemm_other", "attention", "layernorm_modulate", "qk_rmsnorm_rope", "gemm_288x192")
 

@@ -36,6 +36,10 @@ lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up 
 flux_lora_load / flux_lora_set_adapters / flux_lora_delete / flux_read_param   diffusers' load_lora_weights / set_adapters / delete_adapters
                            (empty name: unload_lora_weights) on the engine's merged weights, and the effective parameter read back; the last
                            three take no tensor, so they alone are registered for every backend (they only reach the engine handle)
+ip_attention / ip_attention_   FluxIPAdapterJointAttnProcessor2_0's image-prompt branch: the fused QK-RMSNorm of the un-rotated query, SDPA against
+                           the adapter's few keys (true row maximum, masked padding) and `scale *`, written or accumulated
+flux_ip_adapter_load_param / flux_set_ip_image_embeds / flux_ip_read   diffusers' load_ip_adapter weights and `ip_adapter_image_embeds` of one
+                           image on an engine context (projection + every block's to_k_ip / to_v_ip, once), and the tokens / K / V read back
 """
 import os
 
@@ -78,6 +82,11 @@ SCHEMAS = {
     "flux_lora_load": "(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()",
     "flux_lora_set_adapters": "(int engine, str[] names, float[] weights) -> ()",
     "flux_lora_delete": "(int engine, str adapter) -> ()",
+    "ip_attention": "(Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale) -> Tensor",
+    "ip_attention_": "(Tensor(a!) o, Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale, bool accumulate) -> Tensor(a!)",
+    "flux_ip_adapter_load_param": "(int engine, int slot, str name, Tensor data) -> ()",
+    "flux_set_ip_image_embeds": "(int engine, int slot, Tensor embeds) -> ()",
+    "flux_ip_read": "(int engine, int slot, int block, int which) -> Tensor",
 }
 
 _loaded = False
