@@ -149,7 +149,10 @@ int td_norm_rows_bf16(const void* x, int64_t ldx, void* y, int64_t ldy, int rows
 
 /* In-place per-head RMSNorm(q), RMSNorm(k) (weights may be NULL = no norm) + rotary embedding on a
  * fused projection buffer.  rotate_half=0: FLUX interleaved pairs ([ext] diffusers apply_rotary_emb);
- * rotate_half=1: Qwen2 half-split.  cos/sin: fp32 [rows,128]. */
+ * rotate_half=1: Qwen2 half-split (element i with i +- 64), y = bf16(x*cos + rotate_half(x)*sin) as one fp32 expression;
+ * rotate_half=2: the same rotation with every op of the bf16 torch graph rounding, y = bf16(bf16(x*cos) + bf16(rotate_half(x)*sin))
+ * (what the Qwen2-VL engine runs: bit-identical to transformers' apply_multimodal_rotary_pos_emb on bf16 tensors).
+ * Any other rotate_half: TD_ERR_INVALID, nothing launched.  cos/sin: fp32 [rows,128]. */
 int td_qk_norm_rope_bf16(void* qkv, int64_t ld, int rows, int Hq, int Hk, int q_col, int k_col,
                          const float* cos, const float* sin, int split, const void* wqA, const void* wkA,
                          const void* wqB, const void* wkB, float eps, int rotate_half, void* stream);
@@ -722,8 +725,14 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
 int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, void* stream);
 
 /* Qwen2 building blocks */
+/* out bf16[n,D] = table[ids[i],:] (table bf16 [vocab,D], ids device int32[n], D % 8 == 0).  An id outside [0, vocab) is CLAMPED, not
+ * refused: id < 0 reads row 0, id >= vocab reads row vocab - 1 (the kernel never reads outside the table; a caller that wants an
+ * error for a bad id checks on the host). */
 int td_embed_gather_bf16(const int* ids, const void* table, void* out, int n, int D, int vocab, void* stream);
 int td_silu_mul_bf16(const void* gate_up, void* out, int rows, int I, void* stream);
+/* M-RoPE tables: pos3n device int32 [3,n] (temporal, height, width), sections3 HOST ints summing to 64; cos/sin fp32 [n,128], column j and
+ * 64 + j = cosf/sinf(float(pos[axis(j)]) * inv_freq_j), inv_freq_j = 1.0f / fp32(theta^(2j/128)) with the power correctly rounded (the
+ * arithmetic of Qwen2VLRotaryEmbedding in fp32), axis(j) = the section j falls in; round_bf16: values rounded to bf16. */
 int td_mrope_table(const int* pos3n, int n, const int* sections3, float theta, int round_bf16, float* cos, float* sin, void* stream);
 /* Temperature / top-p (nucleus) sampling, one token per row of bf16 logits [rows, ld], in ONE launch and without a sort:
  *   p = softmax(logits / temperature); keep the most likely tokens while the mass in front of a token is < top_p; renormalise;

@@ -2,6 +2,12 @@
 
 Tolerance: P is rounded to bf16 before the PV product (as in flash-style kernels the reference's
 SDPA dispatches to) and the output is bf16: |err| <= 2^-7 of the output scale.
+
+The score-bias tests (td_attention_bias_bf16, at the end) keep that bar against a float64 softmax(q.k^T scale + bias [+ causal mask]) . v:
+the bias joins the fp32 scores before the softmax (as bias / scale in the kernel's unscaled domain, fp32: ~2^-24 relative, nothing
+next to the bf16 rounding of P), so the error model is the one above.  What makes them decisive is the INPUT: a bias that is independent
+per (head, row, key) and as large as the q.k scores, checked on the CPU to move the reference by >= 10x the tolerance under every
+indexing mistake tried (test_attention_bias_dense).
 """
 import math
 
@@ -388,3 +394,189 @@ def test_cached_prefill_causal_gqa(hip, Sq, Skv):
     torch.cuda.synchronize()
     print(f"cached prefill Sq={Sq} Skv={Skv}: max error {((out.double().cpu() - ref).abs().max() / ref.abs().max()).item() / 2.0 ** -7:.3f} x the bound")
     _check(out, ref)
+
+
+# ---- score-bias attention (td_attention_bias_bf16: the BIAS instantiations of the tile kernel) ---------------------------
+
+def _ref64_bias(q, k, v, Hq, Hkv, scale, causal, bias):
+    """float64 softmax(q.k^T * scale + bias [+ causal mask, query i sees keys j <= i + Skv - Sq]) . v of 2-D operands
+    q [Sq, Hq*128], k / v [Skv, Hkv*128], bias [Hq, Sq, Skv] -> [Sq, Hq*128]."""
+    Sq, Skv = q.shape[0], k.shape[0]
+    qh = q.double().reshape(Sq, Hq, 128).transpose(0, 1)
+    kh = k.double().reshape(Skv, Hkv, 128).transpose(0, 1).repeat_interleave(Hq // Hkv, dim=0)
+    vh = v.double().reshape(Skv, Hkv, 128).transpose(0, 1).repeat_interleave(Hq // Hkv, dim=0)
+    s = qh @ kh.transpose(-1, -2) * scale + bias.double()
+    if causal:
+        i = torch.arange(Sq)[:, None] + (Skv - Sq)
+        s = s.masked_fill(torch.arange(Skv)[None, :] > i, float("-inf"))
+    o = torch.softmax(s, dim=-1) @ vh
+    return o.transpose(0, 1).reshape(Sq, Hq * 128)
+
+
+def _check_bias(got, ref, what):
+    """The module's bar (_check: |err| <= 2^-7 max|ref|), with the figure and the worst element printed first."""
+    g = got.double().cpu()
+    err = (g - ref).abs()
+    i = int(torch.argmax(err))
+    r, c = divmod(i, ref.shape[1])
+    print(f"{what}: max error {float(err.max() / ref.abs().max()) / 2.0 ** -7:.3f} x the bound (row {r} col {c}: got {float(g[r, c]):.6g} "
+          f"ref {float(ref[r, c]):.6g})")
+    _check(got, ref)
+
+
+SCALE_D = 128 ** -0.5
+# (Sq, Skv, Hq, Hkv, scale, causal): the smallest shapes that reach every branch of the BIAS tile body (64-key tile, 32 query rows per
+# wave, 256 per workgroup, one float4 of bias per 4 keys): a 36-key last tile (the `kbase + 4 <= Skv` guard splits an 8-key group);
+# GQA + inv_scale + Sq % 32 != 0 (the qrow clamp); a second query workgroup of 44 rows; causal with bias, offset 0 and 64; Sq = 1
+# (with a bias this must stay on the tile kernel, not the decode kernel)
+BIAS_CASES = [(100, 100, 3, 3, 1.0, False), (45, 132, 4, 2, SCALE_D, False), (300, 68, 2, 2, SCALE_D, False),
+              (76, 76, 2, 2, 1.0, True), (40, 104, 2, 1, SCALE_D, True), (1, 68, 2, 2, SCALE_D, True)]
+_bias_cache = {}
+
+
+def _bias_case(Sq, Skv, Hq, Hkv, scale, causal):
+    """Operands, fp64 reference and the CPU mutation margins of one dense case (computed once, shared by the kernel variants).
+    bias: fp32 randn of std 2, independent per (head, row, key) -- not Toeplitz, so a read that is a key, a row or a head off
+    changes it completely; for scale = 1 q and k are scaled by 0.3 so that q.k (std ~1) and the bias both matter."""
+    key = (Sq, Skv, Hq, Hkv, scale, causal)
+    if key not in _bias_cache:
+        g = torch.Generator().manual_seed(Sq * 1009 + Skv * 31 + Hq)
+        amp = 0.3 if scale == 1.0 else 1.0
+        q = (torch.randn(Sq, Hq * 128, generator=g) * amp).bfloat16()
+        k = (torch.randn(Skv, Hkv * 128, generator=g) * amp).bfloat16()
+        v = torch.randn(Skv, Hkv * 128, generator=g).bfloat16()
+        bias = torch.randn(Hq, Sq, Skv, generator=g) * 2.0
+        ref = _ref64_bias(q, k, v, Hq, Hkv, scale, causal, bias)
+        mutants = {"rolled by one key": torch.roll(bias, 1, dims=2), "rolled by four keys": torch.roll(bias, 4, dims=2)}
+        if Sq > 1:
+            mutants["rolled by one row"] = torch.roll(bias, 1, dims=1)
+        if Hq > 1:
+            mutants["rolled by one head"] = torch.roll(bias, 1, dims=0)
+        if Skv % 64:
+            z = bias.clone()
+            z[:, :, Skv // 64 * 64:] = 0.0
+            mutants["zeroed on the ragged last tile"] = z
+        if scale != 1.0:
+            mutants["bias * scale"] = bias * scale
+        margins = {name: float((_ref64_bias(q, k, v, Hq, Hkv, scale, causal, b) - ref).abs().max() / ref.abs().max()) / 2.0 ** -7
+                   for name, b in mutants.items()}
+        _bias_cache[key] = (q, k, v, bias, ref, margins)
+    return _bias_cache[key]
+
+
+@pytest.mark.parametrize("Sq,Skv,Hq,Hkv,scale,causal", BIAS_CASES)
+def test_attention_bias_dense(hip, Sq, Skv, Hq, Hkv, scale, causal):
+    """td_attention_bias_bf16 with a dense random bias against float64.  First a condition on the INPUTS: the fp64 reference recomputed
+    with each plausible indexing mistake (bias a key, four keys, a row or a head off, dropped on the ragged last tile, multiplied by
+    scale instead of added as it is) lies >= 10x the tolerance from the true one, so the kernel cannot pass with any of them.
+    Measured margins (fp64, CPU; x the 2^-7 tolerance), smallest mutant of each case: 100x100 131; 45x132 58; 300x68 94; 76x76 causal 83;
+    40x104 causal 83; 1x68 causal 44 (the smallest is always the bias dropped on the ragged last tile; the rolls and bias * scale lie
+    at 115 - 300).  Kernel on MI355X, max error x the bound, the same under all three variants: 0.30, 0.31, 0.36, 0.24, 0.40, 0.43."""
+    q, k, v, bias, ref, margins = _bias_case(Sq, Skv, Hq, Hkv, scale, causal)
+    for name, m in margins.items():
+        print(f"bias {Sq}x{Skv} Hq={Hq} causal={causal}: mutant '{name}' lies {m:.1f} x the tolerance from the reference")
+        assert m >= 10.0, f"inputs too weak: mutant '{name}' only {m:.2f} x the tolerance away"
+    out = torch.full((Sq, Hq * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention_bias(q.cuda(), k.cuda(), v.cuda(), out, Hq, Hkv, scale, causal, bias.cuda())
+    torch.cuda.synchronize()
+    _check_bias(out, ref, f"bias attention {Sq}x{Skv} Hq={Hq} Hkv={Hkv} scale={scale:.4f} causal={causal}")
+
+
+@pytest.mark.parametrize("scale", [1.0, SCALE_D])
+def test_attention_bias_carrying_a_mask(hip, scale):
+    """A bias that carries a mask, as T5 and the vision towers use it: -1e4 on ALL keys of the first tile for rows >= 10 (the first tile
+    sets the reference point of the row's exponentials at about -1e4 / scale; the next tile must move it by that much and wipe
+    what the first one accumulated) and on a random 30 % of the other keys, on top of the random bias.  Sq = Skv = 132.
+    Measured on MI355X: max error 0.33 (scale 1) and 0.42 (scale 128^-0.5) x the bound."""
+    S, H = 132, 2
+    g = torch.Generator().manual_seed(132)
+    amp = 0.3 if scale == 1.0 else 1.0
+    q = (torch.randn(S, H * 128, generator=g) * amp).bfloat16()
+    k = (torch.randn(S, H * 128, generator=g) * amp).bfloat16()
+    v = torch.randn(S, H * 128, generator=g).bfloat16()
+    bias = torch.randn(H, S, S, generator=g) * 2.0
+    block = torch.zeros(H, S, S, dtype=torch.bool)
+    block[:, 10:, :64] = True
+    masked = block | ((torch.rand(H, S, S, generator=g) < 0.3) & ~block)
+    assert (~masked).any(dim=2).all()
+    bias = bias + masked.float() * -1e4
+    ref = _ref64_bias(q, k, v, H, H, scale, False, bias)
+    out = torch.full((S, H * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention_bias(q.cuda(), k.cuda(), v.cuda(), out, H, H, scale, False, bias.cuda())
+    torch.cuda.synchronize()
+    assert torch.isfinite(out.float()).all()
+    _check_bias(out, ref, f"bias attention with a -1e4 mask, scale={scale:.4f}")
+
+
+def test_attention_bias_late_spike(hip):
+    """+40 at one key of the third tile for a few rows (Skv = 200): the online softmax must move its reference point because of the
+    BIAS (q.k * scale stays within a few units), and those rows become that key's value row.  Measured on MI355X: 0.34 x the bound."""
+    Sq, Skv, H, key = 70, 200, 2, 150
+    rows = [3, 40, 69]
+    g = torch.Generator().manual_seed(200)
+    q = torch.randn(Sq, H * 128, generator=g).bfloat16()
+    k = torch.randn(Skv, H * 128, generator=g).bfloat16()
+    v = torch.randn(Skv, H * 128, generator=g).bfloat16()
+    bias = torch.randn(H, Sq, Skv, generator=g) * 2.0
+    bias[:, rows, key] += 40.0
+    assert float((q.double().view(Sq, H, 128).transpose(0, 1) @ k.double().view(Skv, H, 128).transpose(0, 1).transpose(1, 2)).abs().max()) * SCALE_D < 8.0
+    ref = _ref64_bias(q, k, v, H, H, SCALE_D, False, bias)
+    assert (ref[rows] - v[key].double()).abs().max() < 1e-6          # the spike owns those rows: only the bias can have done that
+    out = torch.full((Sq, H * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention_bias(q.cuda(), k.cuda(), v.cuda(), out, H, H, SCALE_D, False, bias.cuda())
+    torch.cuda.synchronize()
+    _check_bias(out, ref, "bias attention with a +40 spike in the third tile")
+
+
+@pytest.mark.parametrize("causal", [False, True])
+def test_attention_zero_bias_is_the_plain_kernel(hip, causal):
+    """An all-zero bias on a shape with fewer (query tile, head) items than CUs (so td_attention_bf16 takes the tile kernel too, not
+    stream-K): bit-identical to hip.attention on the same operands -- st + 0 * inv_scale is exact, so any difference means the BIAS
+    and the plain instantiations of the tile kernel have diverged."""
+    S, H = 300, 2
+    g = torch.Generator().manual_seed(300 + causal)
+    qkv = torch.randn(S, 3 * H * 128, generator=g).bfloat16().cuda()
+    q, k, v = qkv[:, :H * 128], qkv[:, H * 128:2 * H * 128], qkv[:, 2 * H * 128:]
+    plain = torch.full((1, S, H * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention(q[None], k[None], v[None], plain, H, H, scale=SCALE_D, causal=causal)
+    out = torch.full((S, H * 128), 5.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention_bias(q, k, v, out, H, H, SCALE_D, causal, torch.zeros(H, S, S, dtype=torch.float32, device="cuda"))
+    torch.cuda.synchronize()
+    assert torch.equal(out, plain[0])
+
+
+@pytest.mark.parametrize("pad", [64, 4])
+def test_attention_bias_strided_operands(hip, pad):
+    """q, k, v as column slices of ONE fused [S, (Hq + 2 Hkv) * 128 + 64] buffer (the T5 layout), out into a wider buffer pre-filled with
+    a sentinel: the pad columns of out stay untouched.  pad = 4: rows of out are 8- but not 16-byte aligned (the narrow store form).
+    Measured on MI355X: max error 0.33 (pad 64) and 0.38 (pad 4) x the bound."""
+    S, Hq, Hkv = 100, 4, 2
+    g = torch.Generator().manual_seed(7 + pad)
+    W = (Hq + 2 * Hkv) * 128
+    buf = torch.randn(S, W + 64, generator=g).bfloat16()
+    bias = torch.randn(Hq, S, S, generator=g) * 2.0
+    sl = lambda t: (t[:, :Hq * 128], t[:, Hq * 128:(Hq + Hkv) * 128], t[:, (Hq + Hkv) * 128:W])
+    ref = _ref64_bias(*sl(buf), Hq, Hkv, SCALE_D, False, bias)
+    wide = torch.full((S, Hq * 128 + pad), -7.0, dtype=torch.bfloat16, device="cuda")
+    hip.attention_bias(*sl(buf.cuda()), wide[:, :Hq * 128], Hq, Hkv, SCALE_D, False, bias.cuda())
+    torch.cuda.synchronize()
+    _check_bias(wide[:, :Hq * 128], ref, f"bias attention, strided operands, out pad {pad}")
+    assert (wide[:, Hq * 128:].float() == -7.0).all(), "pad columns of out written"
+
+
+def test_attention_bias_refusals(hip):
+    """Skv % 4 != 0 (the float4 bias loads would straddle rows) and a bias pointer that is not 16-byte aligned: TD_ERR_INVALID before
+    any launch, out unchanged."""
+    H = 2
+    for Sq, Skv, shift in [(16, 70, 0), (16, 68, 1)]:
+        q = torch.randn(Sq, H * 128).bfloat16().cuda()
+        k = torch.randn(Skv, H * 128).bfloat16().cuda()
+        v = torch.randn(Skv, H * 128).bfloat16().cuda()
+        flat = torch.zeros(H * Sq * Skv + 4, dtype=torch.float32, device="cuda")
+        bias = flat[shift:shift + H * Sq * Skv].view(H, Sq, Skv)
+        assert bias.data_ptr() % 16 == 4 * shift
+        out = torch.full((Sq, H * 128), -7.0, dtype=torch.bfloat16, device="cuda")
+        with pytest.raises(hip.ThinkDiffHipError, match="error 2"):
+            hip.attention_bias(q, k, v, out, H, H, SCALE_D, False, bias)
+        torch.cuda.synchronize()
+        assert (out.float() == -7.0).all()

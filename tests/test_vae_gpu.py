@@ -4,6 +4,27 @@ against the CPU oracle (oracle/vae_ref.py: F.conv2d / F.group_norm / SDPA in bf1
 Tolerances: conv / groupnorm single ops <= 2^-6 of the output scale (bf16 output, fp32 accumulate, different
 summation order); the tiny 2-block decoder end to end: relative RMSE <= 3e-2 vs the bf16 oracle and uint8 pixels
 within 1e-2 RMSE on the [0,1] scale (the north-star pixel bar).
+
+td_groupnorm_nhwc_bf16 against float64 (test_groupnorm_vs_float64): reference = float64 GroupNorm of the bf16 input, t = bf16((x - mean)
+rstd gamma + beta), then y = bf16(silu(t)) in float64 when silu is set -- the kernel's two rounding points.  Per-element tolerance:
+  tol_t = ulp(|t| + S) + S,      tol_y = ulp(|y| + d) + d,  d = |silu'(t)| tol_t      (ulp(r) = one bf16 ulp of r)
+One ulp at each of the two rounding points, taken at the largest magnitude the rounded value can have (the reference's plus what
+reaches it from upstream): next to a power of two the kernel's value may lie in the binade above the reference's, where the ulp is
+twice as large -- e.g. t one ulp lower takes silu(t) from -0.031188 to -0.031417, which round to -0.0311279 and -0.0314941, three
+ulps of the reference apart but one ulp of the upper binade plus silu' ulp(t).
+  S = (L + 8) 2^-24 rstd |gamma| (mean|x| + 1.5 |x - mean| E[x^2] / var)
+S is what the fp32 statistics may cost, derived as tests/test_norms_gpu.py derives its term.  td_gn_partial_kernel adds every value
+into fp32 chains of length at most L = ceil(ppb / ppp) + 8 + ppp nj (the thread's pixels, its 8-channel sum, then ppp nj sub-sums in
+the block's fixed-order sum; ppb pixels per block, ppp = 256 / (C/8) pixels per pass, nj = max(cpg / 8, 1)); the block partials are
+added in double.  Worst-case rounding of such a sum is L 2^-24 of the sum of magnitudes: the mean is off by <= L 2^-24 mean|x|, which
+moves t by that times rstd |gamma|.  The variance is ONE-PASS, var = E[x^2] - mean^2: E[x^2] is off by L 2^-24 E[x^2] and mean^2 by
+2 |mean| L 2^-24 mean|x| <= 2 L 2^-24 E[x^2], so var is off by 3 L 2^-24 E[x^2] -- RELATIVE to var that is the cancellation factor
+E[x^2] / var -- and rstd by half of it, which moves t by 1.5 L 2^-24 (E[x^2] / var) |x - mean| rstd |gamma|.  The factor stays in the
+formula so that it is visible what the one-pass form is being allowed: ~1 for centred data, 1e4 at mean / std = 100.  The + 8 covers
+the fp32 casts of mean and rstd and the fp32 output expression.  Measured on MI355X, max error x the bound: 0 (the four shapes of <= 128 pixels with <= 64 channels: every bit right) to 0.999 without SiLU -- an element
+whose rounding flipped -- and to 0.81 with it.
+
+DC-offset inputs (test_groupnorm_dc_offset_groups) take their bar from the reference's own arithmetic instead: see the test.
 """
 import pytest
 import torch
@@ -53,6 +74,123 @@ def test_groupnorm_silu_nhwc(hip, P, C, silu):
     y = hip.groupnorm_nhwc(x.cuda(), ga.cuda(), be.cuda(), 32, 1e-6, silu)
     torch.cuda.synchronize()
     _close(y, ref[0].t(), 2.0 ** -6)
+
+
+def _ulp(r):
+    a = r.abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 7)
+
+
+def _gn_chain(P, C, G):
+    """Longest fp32 addition chain of td_gn_partial_kernel for this shape (the launcher's block split restated)."""
+    nblocks = min(1024, (P + 63) // 64)
+    ppb = -(-P // nblocks)
+    ppp = 256 // (C // 8)
+    nj = max(C // G // 8, 1)
+    return -(-ppb // ppp) + 8 + ppp * nj
+
+
+def _gn_stats64(x, G):
+    """float64 per-element mean, biased variance and E[x^2] of x [P, C] over (all pixels, the channels of the group)."""
+    P, C = x.shape
+    xg = x.double().reshape(P, G, C // G)
+    mean = xg.mean(dim=(0, 2), keepdim=True)
+    var = ((xg - mean) ** 2).mean(dim=(0, 2), keepdim=True)
+    ex2 = (xg * xg).mean(dim=(0, 2), keepdim=True)
+    absx = xg.abs().mean(dim=(0, 2), keepdim=True)
+    full = lambda t: t.expand(P, G, C // G).reshape(P, C)
+    return full(mean), full(var), full(ex2), full(absx)
+
+
+def _gn_ref(x, ga, be, G, eps, silu):
+    """float64 reference and its per-element tolerance (derivation: module docstring)."""
+    P, C = x.shape
+    mean, var, ex2, absx = _gn_stats64(x, G)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    xd, gd = x.double(), ga.double()[None, :]
+    t = ((xd - mean) * rstd * gd + be.double()[None, :]).bfloat16().double()
+    S = (_gn_chain(P, C, G) + 8) * 2.0 ** -24 * rstd * gd.abs() * (absx + 1.5 * (xd - mean).abs() * ex2 / (var + eps))
+    tol = _ulp(t.abs() + S) + S
+    if not silu:
+        return t, tol
+    sg = torch.sigmoid(t)
+    y = (t * sg).bfloat16().double()
+    d = (sg * (1.0 + t * (1.0 - sg))).abs() * tol
+    return y, _ulp(y.abs() + d) + d
+
+
+def _gn_check(got, ref, tol, what):
+    got = got.double().cpu()
+    assert torch.isfinite(got).all(), what
+    err = (got - ref).abs()
+    bad = err > tol
+    print(f"{what}: max error {float((err / tol).max()):.3f} x the bound")
+    if bad.any():
+        i = int(torch.argmax(err / tol))
+        r, c = divmod(i, ref.shape[1])
+        raise AssertionError(f"{what}: {int(bad.sum())} / {bad.numel()} elements beyond the bound; worst pixel {r} channel {c}: got "
+                             f"{float(got[r, c]):.6g} ref {float(ref[r, c]):.6g} ({float(err[r, c] / tol[r, c]):.3g} x the bound)")
+
+
+def _gn_affine(C, g):
+    """gamma and beta with a visible spread (a channel-index error shows)."""
+    return (1.0 + 0.5 * torch.randn(C, generator=g)).bfloat16(), (0.7 * torch.randn(C, generator=g)).bfloat16()
+
+
+# (P, C, G): a single pixel; cpg = 1 / 2 (two blocks) / 4: the sub-group path of a thread's 8 channels; cpg = 8, 16, 64: the nj path, the last
+# with tpp = 256 threads per pixel and one pixel per pass; cpg = 24 with tpp = 24 not dividing 256 (16 idle threads); G = 64 and G = 1;
+# 70000 pixels: the 1024-block cap, 69 pixels per block, the last 9 blocks empty
+GN_SHAPES = [(1, 64, 32), (63, 32, 32), (65, 64, 32), (1000, 128, 32), (257, 256, 32), (300, 512, 32), (64, 2048, 32), (100, 192, 8),
+             (128, 64, 64), (500, 64, 1), (70000, 64, 32)]
+
+
+@pytest.mark.parametrize("silu", [False, True])
+@pytest.mark.parametrize("P,C,G", GN_SHAPES)
+def test_groupnorm_vs_float64(hip, P, C, G, silu):
+    """Every index path of the statistics kernel against float64, every group with its own mean (+-3) and spread (0.5 .. 2.5)."""
+    g = torch.Generator().manual_seed(P * 31 + C + G)
+    gm = (torch.rand(G, generator=g) * 6.0 - 3.0).repeat_interleave(C // G)
+    gs = (0.5 + 2.0 * torch.rand(G, generator=g)).repeat_interleave(C // G)
+    x = (torch.randn(P, C, generator=g) * gs[None, :] + gm[None, :]).bfloat16()
+    ga, be = _gn_affine(C, g)
+    ref, tol = _gn_ref(x, ga, be, G, 1e-6, silu)
+    y = hip.groupnorm_nhwc(x.cuda(), ga.cuda(), be.cuda(), G, 1e-6, silu)
+    torch.cuda.synchronize()
+    _gn_check(y, ref, tol, f"groupnorm P={P} C={C} G={G} silu={silu}")
+
+
+# (mean, std) of the groups, in turn: mean / std from 32 to 100 (beyond ~256 the spread is no longer representable in bf16)
+GN_DC = [(16.0, 0.5), (50.0, 1.0), (100.0, 2.0), (200.0, 2.0), (-200.0, 4.0)]
+
+
+@pytest.mark.parametrize("P,C", [(4096, 128), (16384, 512)])
+def test_groupnorm_dc_offset_groups(hip, P, C):
+    """Groups whose mean is large next to their spread, where the one-pass variance E[x^2] - mean^2 over fp32 partial sums is at risk
+    (the generic LayerNorm kernel is guarded against the same in tests/test_norms_gpu.py).  The bar is the reference's own arithmetic:
+    F.group_norm of the same input in fp32 on the CPU, rounded to bf16.  Both implementations are measured against float64 GroupNorm
+    rounded to bf16, in bf16 ulps of that reference over the elements with |ref| > 0.1; the kernel's worst error may exceed the fp32
+    implementation's by at most ONE ulp (two valid fp32 statistics can flip one rounding).
+    Measured on MI355X: (4096, 128): kernel 1.00 ulp, fp32 F.group_norm 1.00 ulp; (16384, 512): kernel 1.00 ulp, fp32 F.group_norm 1.00 ulp
+    -- the one-pass form loses nothing at these offsets, so td_gn_partial_kernel stays as it is."""
+    G = 32
+    g = torch.Generator().manual_seed(P + C)
+    gm = torch.tensor([GN_DC[i % len(GN_DC)][0] for i in range(G)]).repeat_interleave(C // G)
+    gs = torch.tensor([GN_DC[i % len(GN_DC)][1] for i in range(G)]).repeat_interleave(C // G)
+    x = (torch.randn(P, C, generator=g) * gs[None, :] + gm[None, :]).bfloat16()
+    ga, be = _gn_affine(C, g)
+    mean, var, _, _ = _gn_stats64(x, G)
+    ref = ((x.double() - mean) / torch.sqrt(var + 1e-6) * ga.double()[None, :] + be.double()[None, :]).bfloat16().double()
+    cpu = F.group_norm(x.float().t()[None], G, ga.float(), be.float(), eps=1e-6)[0].t().bfloat16().double()
+    y = hip.groupnorm_nhwc(x.cuda(), ga.cuda(), be.cuda(), G, 1e-6, False)
+    torch.cuda.synchronize()
+    got = y.double().cpu()
+    assert torch.isfinite(got).all()
+    sel = ref.abs() > 0.1
+    u = _ulp(ref)
+    e_kernel = float(((got - ref).abs() / u)[sel].max())
+    e_cpu = float(((cpu - ref).abs() / u)[sel].max())
+    print(f"groupnorm DC-offset groups P={P} C={C}: worst error {e_kernel:.2f} bf16 ulp (kernel), {e_cpu:.2f} bf16 ulp (fp32 F.group_norm on the CPU)")
+    assert e_kernel <= e_cpu + 1.0, f"kernel {e_kernel:.2f} ulp vs fp32 reference arithmetic {e_cpu:.2f} ulp"
 
 
 def _tiny_vae(seed):

@@ -243,6 +243,7 @@ __global__ __launch_bounds__(256) void td_qk_norm_rope_kernel(const TdQkRopePara
 int td_qk_norm_rope_launch(const TdQkRopeParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.rows > 0 && p.Hq > 0 && p.Hk >= 0, "td_qk_norm_rope: empty problem");
   TD_CHECK_ARG(p.ld % 8 == 0 && p.q_col % 8 == 0 && p.k_col % 8 == 0, "td_qk_norm_rope: columns must be 16-byte aligned");
+  TD_CHECK_ARG(p.rotate_half >= 0 && p.rotate_half <= 2, "td_qk_norm_rope: rotate_half=%d is not a rotation mode (0, 1 or 2)", p.rotate_half);
   TD_GRID_1D(nblk, (long long)p.rows * 256, 256, "td_qk_norm_rope");
   hipLaunchKernelGGL(td_qk_norm_rope_kernel, dim3(nblk), dim3(256), 0, stream, p);
   TD_CHECK_LAUNCH();
@@ -630,7 +631,10 @@ __global__ void td_mrope_table_kernel(const int* pos, int n, int s0, int s1, flo
   if (idx >= n * 64) return;
   const int t = idx / 64, j = idx % 64;
   const int axis = j < s0 ? 0 : (j < s0 + s1 ? 1 : 2);
-  const float inv_freq = 1.0f / powf(theta, (float)(2 * j) / 128.0f);
+  // theta^(2j/128) CORRECTLY rounded to fp32 (through double), then one fp32 division, as a 1-ulp host pow gives it in all but a stray
+  // column: device powf is good to 1 - 2 ulps, not correctly rounded, and at positions beyond ~10^4 one fp32 ulp of the angle is already
+  // several bf16 ulps of a small cosine -- the tables then differ from the reference's own fp32 evaluation (tests/test_qwen2_kernels_gpu.py)
+  const float inv_freq = 1.0f / (float)pow((double)theta, (double)(2 * j) / 128.0);
   const float ang = (float)pos[axis * n + t] * inv_freq;
   float c = cosf(ang), s = sinf(ang);
   if (round_bf16) { c = rbf(c); s = rbf(s); }

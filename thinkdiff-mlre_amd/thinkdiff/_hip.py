@@ -359,6 +359,29 @@ def flux_rope_table(ids, axes_dims=(16, 56, 56), theta=10000.0):
     return cos, sin
 
 
+def mrope_table(pos, sections=(16, 24, 24), theta=1e6, round_bf16=True):
+    """td_mrope_table: pos int32 [3, n] (temporal, height, width) -> cos, sin fp32 [n, 128]."""
+    assert pos.dtype == torch.int32 and pos.dim() == 2 and pos.shape[0] == 3 and pos.is_contiguous()
+    n = pos.shape[1]
+    cos = torch.empty(n, 128, dtype=torch.float32, device=pos.device)
+    sin = torch.empty_like(cos)
+    sec = (ctypes.c_int * 3)(*sections)
+    check(lib().td_mrope_table(ptr(pos), n, ctypes.cast(sec, ctypes.c_void_p), float(theta), int(round_bf16), ptr(cos), ptr(sin), stream_ptr()))
+    return cos, sin
+
+
+def embed_gather(ids, table, out=None):
+    """td_embed_gather_bf16: out[i, :] = table[ids[i], :]; ids int32 [n] on the device, table bf16 [vocab, D].  Ids outside [0, vocab) are clamped."""
+    assert ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous()
+    assert table.dtype == torch.bfloat16 and table.dim() == 2 and table.is_contiguous()
+    n, (vocab, D) = ids.numel(), table.shape
+    if out is None:
+        out = torch.empty(n, D, dtype=torch.bfloat16, device=table.device)
+    assert out.shape == (n, D) and out.is_contiguous() and out.dtype == torch.bfloat16
+    check(lib().td_embed_gather_bf16(ptr(ids), ptr(table), ptr(out), n, D, vocab, stream_ptr()))
+    return out
+
+
 def timestep_sincos(t):
     assert t.dtype == torch.float32 and t.is_contiguous()
     out = torch.empty(t.numel(), 256, dtype=torch.bfloat16, device=t.device)
@@ -524,6 +547,21 @@ def attention_padded(qkv, H, scale, causal=False, bias=None, out=None):
     assert out.shape == (S, W) and out.is_contiguous()
     check(lib().td_attention_bias_bf16(ptr(qkv), _rows(qkv), ptr(qkv[:, W:]), ptr(qkv[:, 2 * W:]), _rows(qkv), ptr(out), W,
                                        S, S, H, H, float(scale), int(causal), ptr(bias), stream_ptr()))
+    return out
+
+
+def attention_bias(q, k, v, out, Hq, Hkv, scale, causal, bias):
+    """td_attention_bias_bf16 on separate operand views: q [Sq, >= Hq*128], k, v [Skv, >= Hkv*128] (one row stride for both), out
+    [Sq, >= Hq*128], each with its own row stride; bias fp32 [Hq, Sq, Skv] (16-byte aligned, Skv % 4 == 0) or None.
+    softmax(q.k^T * scale + bias [+ causal mask: query i sees keys j <= i + Skv - Sq]) . v -> out."""
+    for t in (q, k, v, out):
+        assert t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    Sq, Skv = q.shape[0], k.shape[0]
+    assert k.stride() == v.stride() and v.shape[0] == Skv and out.shape[0] == Sq
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.shape == (Hq, Sq, Skv) and bias.is_contiguous()
+    check(lib().td_attention_bias_bf16(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(out), out.stride(0),
+                                       Sq, Skv, Hq, Hkv, float(scale), int(causal), ptr(bias), stream_ptr()))
     return out
 
 
