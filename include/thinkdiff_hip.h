@@ -186,6 +186,18 @@ int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float s
  * h, r bf16 with row strides ldh, ldr >= D (elements; columns beyond D are untouched); D % 8 == 0, strides multiples of 8, both pointers 16-byte
  * aligned, r not overlapping h. */
 int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream);
+/* First-block cache kernels (td_abi_version() >= 6; what the engine's cache runs, td_flux_set_block_cache below).  bf16 rows of D columns (D % 8 == 0)
+ * at row strides that are multiples of 8 and at least D, every pointer 16-byte aligned.
+ * td_block_cache_head_bf16:   r[m, j] = bf16(float(h1[m, j]) - float(h0[m, j]))
+ *                             sums[0] = sum |float(r) - float(r_prev)|,   sums[1] = sum |float(r_prev)|      over all rows x D elements, fp64 (device)
+ * r_prev NULL = no previous residual: r is written, sums[0] = sums[1] = 0.  r overlaps none of the inputs.  The sums are taken without atomics in one
+ * combination order fixed by (rows, D) -- fp32 per thread over at most a few dozen terms, fp64 above -- so the same inputs give the same bits on every
+ * run, whatever else the device runs.  ws: TD_BLOCK_CACHE_WS_BYTES of device scratch, not shared by launches that may run concurrently.
+ * td_block_cache_tail_bf16:   out[m, j] = bf16(float(a[m, j]) - float(b[m, j]));  out may be a or b (same stride): in place. */
+#define TD_BLOCK_CACHE_WS_BYTES 65536
+int td_block_cache_head_bf16(const void* h1, int64_t ld1, const void* h0, int64_t ld0, const void* r_prev, int64_t ldp, void* r, int64_t ldr, int rows, int D,
+                             double* sums, void* ws, void* stream);
+int td_block_cache_tail_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int rows, int D, void* stream);
 /* FLUX IP-Adapter cross-attention (td_abi_version() >= 5; [ext] diffusers >= 0.32 FluxIPAdapterJointAttnProcessor2_0, restated from the published
  * source, parity unpinned): the image rows' query against the n_keys image-prompt tokens of one adapter, the scaled result written or added to o.
  *   qn[m, h, :] = norm_w ? bf16(bf16(q[m, h, :] * rstd) * norm_w)  :  q[m, h, :]       rstd = rsqrt(mean(q[m, h, :]^2) + eps) in fp32 (qk_norm8 of
@@ -433,6 +445,31 @@ int td_flux_set_ip_image_embeds(td_flux* f, int slot, const void* embeds, int n_
 int td_flux_ip_read(const td_flux* f, int slot, int block, int which, void* dst, void* stream);
 /* The widths of those rows: J = joint_dim (tokens) and D = heads x 128 (K / V). */
 int td_flux_ip_widths(const td_flux* f, int* joint_dim, int* inner_dim);
+/* ---- First-block cache (td_abi_version() >= 6; [ext] diffusers >= 0.33 hooks/first_block_cache.py `FirstBlockCacheConfig`, restated from the
+ * published source, parity unpinned): skip the transformer on forwards whose first block's output barely moved.  With the cache on, every
+ * td_flux_forward -- and with it every td_flux_denoise* loop -- runs the embedders and double block 0 as always (an IP-Adapter's add included), then
+ *   r      = bf16(float(h1) - float(h0))                       h0 / h1: the S_img + S_ref image rows before / behind the block
+ *   metric = sum |r - r_prev| / sum |r_prev|                   r_prev: r of the last COMPUTED forward; sums as td_block_cache_head_bf16 takes them, the
+ *                                                              ratio in double on the host (diffusers rounds both means and the ratio to bf16)
+ * and is COMPUTED -- r_prev <- r, the remaining blocks run, tail = bf16(float(h_final) - float(h1)) is kept for the S_img latent rows -- when there
+ * is no r_prev, when the mode's rule says so (mode 1: metric > threshold; mode 2: the schedule's entry for this forward, counted from the last reset,
+ * 1 beyond its end), or when an int8 smoothing calibration is pending; otherwise SKIPPED: h = bf16(float(h1) + float(tail)) on the latent rows
+ * (td_flux_residual_inject_bf16 at scale 1.0), then the final norm and proj_out as always.  A skipped forward leaves the context's 8-bit history as an
+ * out-of-order step does: the next forward starts its history scales and softmax references afresh.  The decision needs the sums on the host: one
+ * 16-byte copy and one synchronisation of the forward's stream per forward -- only with the cache on; mode 0 issues exactly the plain launches.
+ * State (r_prev, tail, the log) is per context and reset by: every td_flux_denoise* loop at its start, a change of the token layout (T, S_img, S_ref),
+ * of the model's weights (LoRA) or of these settings, and td_flux_block_cache_reset.  It is allocated at a context's first forward under the cache
+ * (hipMalloc: not capturable).
+ * Settings are the model's -- parent context only, forks follow.  td_flux_set_block_cache: mode 0 off, 1 threshold (>= 0; 0 = always compute).
+ * td_flux_set_block_cache_schedule: mode 2, compute[i] != 0 = forward i is computed; compute[0] must be 1; the metric is still taken and logged.
+ * TD_ERR_INVALID: a fork; a ControlNet model; a forward with the cache on and a ControlNet attached (its samples are added behind every block: that
+ * pairing is not built); a negative or NaN threshold; a mode other than 0 / 1; a schedule that is empty or starts with 0; a model without a double block.
+ * td_flux_block_cache_stats: the log since the last reset -- *n forwards, and for the first min(cap, *n) of them the metric (+inf where there was no
+ * r_prev) and whether the forward was computed.  metric / computed may be NULL with cap 0. */
+int td_flux_set_block_cache(td_flux* f, int mode, float threshold);
+int td_flux_set_block_cache_schedule(td_flux* f, const unsigned char* compute, int n);
+int td_flux_block_cache_reset(td_flux* f);
+int td_flux_block_cache_stats(const td_flux* f, int cap, float* metric, unsigned char* computed, int* n);
 /* Per-launch HIP-event trace of the engine's kernels (events recorded on the launch stream).
  * categories: 0 GEMM 256x256 tile (td_gemm_bf16_nt_kernel<8,4>), 1 small GEMM tiles, 2 attention,
  * 3 LayerNorm+modulate, 4 QK-RMSNorm+RoPE, 5 GEMM 288x192 tile (<9,3>).  trace_end synchronises and

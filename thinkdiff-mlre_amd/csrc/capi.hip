@@ -1,6 +1,7 @@
 // extern "C" surface of libthinkdiff_hip.so (declared in include/thinkdiff_hip.h).
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 #include "td_kernels.h"
 #include "../../include/thinkdiff_hip.h"
 
@@ -16,9 +17,10 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 5; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 6; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
+                                            // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -197,6 +199,18 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
 int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream) {
   TD_CHECK_ARG(ldh >= 0 && ldh < (1ll << 31) && ldr >= 0 && ldr < (1ll << 31), "td_flux_residual_inject: ldh=%lld / ldr=%lld outside the 32-bit range", (long long)ldh, (long long)ldr);
   return td_flux_residual_inject_launch((bf16_t*)h, (int)ldh, (const bf16_t*)r, (int)ldr, rows, D, scale, (hipStream_t)stream);
+}
+
+int td_block_cache_head_bf16(const void* h1, int64_t ld1, const void* h0, int64_t ld0, const void* r_prev, int64_t ldp, void* r, int64_t ldr, int rows, int D,
+                             double* sums, void* ws, void* stream) {
+  for (int64_t ld : {ld1, ld0, ldp, ldr}) TD_CHECK_ARG(ld >= 0 && ld < (1ll << 31), "td_block_cache_head: leading dimension %lld outside the 32-bit range", (long long)ld);
+  return td_block_cache_head_launch((const bf16_t*)h1, (int)ld1, (const bf16_t*)h0, (int)ld0, (const bf16_t*)r_prev, (int)ldp, (bf16_t*)r, (int)ldr, rows, D, sums,
+                                    (double*)ws, (hipStream_t)stream);
+}
+
+int td_block_cache_tail_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int rows, int D, void* stream) {
+  for (int64_t ld : {lda, ldb, ldo}) TD_CHECK_ARG(ld >= 0 && ld < (1ll << 31), "td_block_cache_tail: leading dimension %lld outside the 32-bit range", (long long)ld);
+  return td_block_cache_tail_launch((const bf16_t*)a, (int)lda, (const bf16_t*)b, (int)ldb, (bf16_t*)out, (int)ldo, rows, D, (hipStream_t)stream);
 }
 int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream) {
   return td_flux_cfg_step_launch((bf16_t*)x, (const bf16_t*)v_pos, (const bf16_t*)v_neg, scale, dt, n, (hipStream_t)stream);

@@ -28,6 +28,8 @@
 // samples, and a main context with one attached adds them behind its own blocks (td_flux_attach_controlnet, td_flux_residual_inject_bf16).
 // IP-Adapter slots (td_flux_ip_adapter_*: the model's; td_flux_set_ip_image_embeds: a context's image prompt -> tokens and every double block's
 // K / V, once per image) add, inside a double block, td_ip_attention of the image rows' un-rotated query and one add behind the FF.
+// The first-block cache (td_flux_set_block_cache*; kernels in csrc/block_cache.hip) decides behind double block 0 whether the forward runs its
+// remaining blocks or adds the tail the last computed forward left -- the one place the forward waits for the device.
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -260,6 +262,79 @@ int new_context(FluxModel* m, bool root, td_flux** out) {
   return TD_OK;
 }
 
+constexpr size_t BC_LOG_MAX = 1 << 16;      // forwards the log keeps between two resets (a denoise loop resets it; bare forwards may go on for ever)
+
+void block_cache_reset(td_flux* f) {
+  f->bc_has_prev = false;
+  f->bc_count = 0;
+  f->bc_metric.clear();
+  f->bc_computed.clear();
+}
+
+// The state a forward under the cache needs: buffers (first use), and values that belong to this token layout, these weights and these settings.
+int block_cache_prepare(td_flux* f) {
+  const FluxModel* m = f->m;
+  if (!f->bc_buf) {
+    const size_t rows = (size_t)m->max_img * m->D * sizeof(bf16_t);
+    hipError_t e = hipMalloc((void**)&f->bc_buf, 3 * rows + TD_BLOCK_CACHE_WS_BYTES + 256);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&f->bc_host, 16);
+    if (e != hipSuccess) {
+      td_set_error("td_flux_forward: allocating the first-block cache state (3 x %d x %d bf16) failed: %s", m->max_img, m->D, hipGetErrorString(e));
+      if (f->bc_buf) (void)hipFree(f->bc_buf);
+      f->bc_buf = nullptr;
+      return TD_ERR_HIP;
+    }
+    f->bc_r[0] = (bf16_t*)f->bc_buf; f->bc_r[1] = (bf16_t*)(f->bc_buf + rows); f->bc_tail = (bf16_t*)(f->bc_buf + 2 * rows);
+    f->bc_ws = (double*)(f->bc_buf + 3 * rows); f->bc_sums = (double*)(f->bc_buf + 3 * rows + TD_BLOCK_CACHE_WS_BYTES);
+  }
+  if (f->bc_T != f->T || f->bc_S_img != f->S_img || f->bc_S_ref != f->S_ref || f->bc_wepoch != m->weight_epoch || f->bc_cepoch != m->bc_epoch) block_cache_reset(f);
+  f->bc_T = f->T; f->bc_S_img = f->S_img; f->bc_S_ref = f->S_ref; f->bc_wepoch = m->weight_epoch; f->bc_cepoch = m->bc_epoch;
+  return TD_OK;
+}
+
+// Behind double block 0 (h0: the image rows before it, in f->cat): this forward's residual and metric, then the decision -- the forward's one wait
+// for the device.  *skip = false: r_prev is this forward's residual and bc_tail holds h1's latent rows for block_cache_keep_tail.
+int block_cache_decide(td_flux* f, hipStream_t s, bool must_compute, bool* skip) {
+  const FluxModel* m = f->m;
+  const int D = m->D, Si = f->S_img + f->S_ref;
+  const bf16_t* h1 = f->h + (size_t)f->T * D;
+  {
+    TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
+    TD_TRY(td_block_cache_head_launch(h1, D, f->cat, D, f->bc_has_prev ? f->bc_r[f->bc_cur] : nullptr, D, f->bc_r[f->bc_cur ^ 1], D, Si, D, f->bc_sums, f->bc_ws, s));
+  }
+  TD_CHECK_HIP(hipMemcpyAsync(f->bc_host, f->bc_sums, 16, hipMemcpyDeviceToHost, s));
+  TD_CHECK_HIP(hipStreamSynchronize(s));
+  // mean |r - r_prev| / mean |r_prev| over the same element count: the ratio of the sums.  A zero denominator is "no basis to skip on".
+  const double num = f->bc_host[0], den = f->bc_host[1];
+  const float metric = f->bc_has_prev && den > 0.0 ? (float)(num / den) : INFINITY;
+  bool compute = must_compute || !f->bc_has_prev || !(den > 0.0);
+  if (!compute) {
+    if (m->bc_mode == 2) compute = (size_t)f->bc_count >= m->bc_schedule.size() || m->bc_schedule[f->bc_count] != 0;
+    else compute = metric > m->bc_threshold;
+  }
+  ++f->bc_count;
+  if (f->bc_metric.size() < BC_LOG_MAX) { f->bc_metric.push_back(metric); f->bc_computed.push_back(compute ? 1 : 0); }
+  *skip = !compute;
+  if (compute) {
+    f->bc_cur ^= 1;
+    f->bc_has_prev = false;      // until block_cache_keep_tail has the tail that belongs to this residual
+    TD_CHECK_HIP(hipMemcpyAsync(f->bc_tail, h1, (size_t)f->S_img * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+  } else {
+    TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
+    TD_TRY(td_flux_residual_inject_launch(f->h + (size_t)f->T * D, D, f->bc_tail, D, f->S_img, D, 1.0f, s));
+  }
+  return TD_OK;
+}
+
+// Behind the last block of a computed forward: tail = bf16(float(h_final) - float(h1)), in place over the h1 rows
+int block_cache_keep_tail(td_flux* f, hipStream_t s) {
+  const int D = f->m->D;
+  TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
+  TD_TRY(td_block_cache_tail_launch(f->h + (size_t)f->T * D, D, f->bc_tail, D, f->bc_tail, D, f->S_img, D, s));
+  f->bc_has_prev = true;
+  return TD_OK;
+}
+
 }  // namespace
 
 struct FloatPack { static constexpr int N = 128; float v[N]; };
@@ -299,6 +374,8 @@ void td_flux_destroy(td_flux* f) {
   if (f->root) flux_model_destroy(f->m);
   for (td_flux::IpCtx& c : f->ip) if (c.buf) (void)hipFree(c.buf);
   if (f->ip_out) (void)hipFree(f->ip_out);
+  if (f->bc_buf) (void)hipFree(f->bc_buf);
+  if (f->bc_host) (void)hipHostFree(f->bc_host);
   (void)hipFree(f->ws);
   delete f;
 }
@@ -501,6 +578,10 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
     TD_TRY(linear(f, s, m->x_emb, bf16_rows(x_in, m->Cin), Si, Epilogue::to(h_img, D).plus(f->cn_E, D)));
   else
     TD_TRY(linear(f, s, m->x_emb, bf16_rows(x_in, m->Cin), Si, Epilogue::to(h_img, D)));
+  // first-block cache: h0 = the image rows before double block 0 (td_flux_forward prepared the state and refused what the cache does not pair with)
+  const bool bc_on = m->bc_mode != 0 && velocity;
+  bool bc_skip = false;
+  if (bc_on) TD_CHECK_HIP(hipMemcpyAsync(f->cat, h_img, (size_t)Si * D * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
 
   TdNormParams np;
   np.x = h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = S; np.D = D; np.eps = 1e-6f; np.split = T;
@@ -632,10 +713,14 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
       TD_TRY(td_flux_residual_inject_launch(h_img, D, f->ip_out, D, Si, D, 1.0f, s));
     }
     if (hook) TD_TRY((*hook)(false, i));
+    if (bc_on && i == 0) {      // (a pending calibration must see every block)
+      TD_TRY(block_cache_decide(f, s, calib, &bc_skip));
+      if (bc_skip) break;
+    }
   }
 
   // ---- single-stream blocks -------------------------------------------------------------------------------------------------------
-  for (int i = 0; i < Ls; ++i) {
+  for (int i = 0; i < Ls && !bc_skip; ++i) {
     const SingleBlock& b = m->sgl[i];
     const FluxLinear &w1 = b.lin[SINGLE_IN], &w2 = b.lin[SINGLE_OUT];
     const bf16_t* ms = mod + (size_t)L * 12 * D + (size_t)i * 3 * D;  // shift, scale, gate
@@ -667,6 +752,7 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
   }
 
   // ---- AdaLayerNormContinuous (chunk order: scale, shift) and proj_out, on the latents' image rows only (reference tokens have no velocity)
+  if (bc_on && !bc_skip) TD_TRY(block_cache_keep_tail(f, s));
   if (velocity) {
     const bf16_t* mf = mod + (size_t)L * 12 * D + (size_t)Ls * 3 * D;
     TdNormParams nf = np;
@@ -680,6 +766,7 @@ static int run_blocks(td_flux* f, const void* latents, int step, void* velocity,
   if (calib) TD_TRY(flux_finish_smoothing(m, s));      // (synchronises s; bumps the history epoch)
   if (hist_mode) { f->hs_step = step; f->hs_T = T; f->hs_S = S; f->hs_epoch = m->hist_epoch; } else f->hs_step = -1;
   if (href_on) { f->href_cur ^= 1; f->href_step = step; f->href_T = T; f->href_S = S; f->href_epoch = m->hist_epoch; } else f->href_step = -1;
+  if (bc_skip) f->hs_step = f->href_step = -1;      // only block 0 left maxima / reference points: the next forward starts afresh, as after an out-of-order step
   return TD_OK;
 }
 
@@ -725,6 +812,12 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
     TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: IP-Adapter slot %d holds an image prompt and the context %d reference tokens (the image rows would include "
                  "the reference rows): that pairing is not built", a, f->S_ref);
     TD_CHECK_ARG(!f->cn, "td_flux_forward: IP-Adapter slot %d holds an image prompt and a ControlNet is attached: that pairing is not built", a);
+  }
+  if (m->bc_mode != 0) {
+    TD_CHECK_ARG(!f->cn, "td_flux_forward: the first-block cache is on (mode %d) and a ControlNet is attached (its samples are added behind every block, "
+                 "a skipped forward runs one): that pairing is not built", m->bc_mode);
+    TD_CHECK_ARG(m->cfg.num_layers > 0, "td_flux_forward: the first-block cache is on (mode %d) and the model has no double-stream block to decide behind", m->bc_mode);
+    TD_TRY(block_cache_prepare(f));
   }
   hipStream_t s = (hipStream_t)stream;
   td_flux* const cn = f->cn;
@@ -910,6 +1003,52 @@ int td_flux_ip_widths(const td_flux* f, int* joint_dim, int* inner_dim) {
   return TD_OK;
 }
 
+// First-block cache, the model's settings (include/thinkdiff_hip.h spells the semantics).  Every change voids every context's state (bc_epoch).
+static int block_cache_model(const char* fn, td_flux* f, int mode) {
+  TD_CHECK_ARG(f, "%s: null context", fn);
+  TD_CHECK_ARG(f->root, "%s: mode %d asked of a fork: the cache settings are the model's (call it on the parent context; forks follow)", fn, mode);
+  TD_CHECK_ARG(!f->m->controlnet, "%s: mode %d asked of a ControlNet model: it has no velocity to cache, and a transformer with a ControlNet attached refuses "
+               "the cache as well", fn, mode);
+  return TD_OK;
+}
+
+int td_flux_set_block_cache(td_flux* f, int mode, float threshold) {
+  TD_TRY(block_cache_model("td_flux_set_block_cache", f, mode));
+  TD_CHECK_ARG(mode == 0 || mode == 1, "td_flux_set_block_cache: mode %d (0 = off, 1 = threshold; td_flux_set_block_cache_schedule sets mode 2)", mode);
+  TD_CHECK_ARG(mode == 0 || threshold >= 0.0f, "td_flux_set_block_cache: threshold %g must be a number >= 0 (0 = always compute)", (double)threshold);
+  FluxModel* m = f->m;
+  m->bc_mode = mode;
+  m->bc_threshold = mode ? threshold : 0.f;
+  m->bc_schedule.clear();
+  ++m->bc_epoch;
+  return TD_OK;
+}
+
+int td_flux_set_block_cache_schedule(td_flux* f, const unsigned char* compute, int n) {
+  TD_TRY(block_cache_model("td_flux_set_block_cache_schedule", f, 2));
+  TD_CHECK_ARG(compute && n > 0, "td_flux_set_block_cache_schedule: an empty schedule (n=%d)", n);
+  TD_CHECK_ARG(compute[0] != 0, "td_flux_set_block_cache_schedule: the schedule of %d forwards starts with a skip: the first forward has nothing to reuse", n);
+  FluxModel* m = f->m;
+  m->bc_mode = 2;
+  m->bc_threshold = 0.f;
+  m->bc_schedule.assign(compute, compute + n);
+  ++m->bc_epoch;
+  return TD_OK;
+}
+
+int td_flux_block_cache_reset(td_flux* f) {
+  TD_CHECK_ARG(f, "td_flux_block_cache_reset: null context");
+  block_cache_reset(f);
+  return TD_OK;
+}
+
+int td_flux_block_cache_stats(const td_flux* f, int cap, float* metric, unsigned char* computed, int* n) {
+  TD_CHECK_ARG(f && n && cap >= 0 && (cap == 0 || (metric && computed)), "td_flux_block_cache_stats: null argument (cap=%d)", cap);
+  *n = (int)f->bc_metric.size();
+  for (int i = 0; i < cap && i < *n; ++i) { metric[i] = f->bc_metric[i]; computed[i] = f->bc_computed[i]; }
+  return TD_OK;
+}
+
 // Per-launch HIP-event trace.  begin: arm (events are created once); end: synchronise the stream and
 // return, per category, launch count / summed milliseconds / summed algorithmic FLOPs.
 int td_flux_trace_begin(td_flux* f, int max_launches) {
@@ -981,6 +1120,7 @@ int scheduler_step(td_flux* f, void* latents, const float* sigmas, int i, int n,
 // The FluxPipeline.__call__ loop: for i: v = transformer(x, t_i); x = bf16(float(x) + (sigma_{i+1}-sigma_i) float(v)).
 // latents [S_img, out_channels] bf16, updated in place; sigmas: n+1 host floats.  blend: FluxInpaintPipeline's step instead.
 int denoise_loop(td_flux* f, void* latents, const float* sigmas, int n, const InpaintBlend* blend, void* stream) {
+  block_cache_reset(f);      // (diffusers resets its cache state per pipeline call)
   for (int i = 0; i < n; ++i) {
     TD_TRY(td_flux_forward(f, latents, i, f->vout, stream));
     TD_TRY(scheduler_step(f, latents, sigmas, i, n, blend, stream));
@@ -998,7 +1138,7 @@ int denoise_multi_loop(td_flux* const* fs, void* const* latents, int count, cons
   // and shuts them out (measured, 3 in flight: 0.698 images/s persistent vs 0.71 plain; one image alone: 0.678 vs 0.655).
   static const char* force = getenv("TD_FLUX_INFLIGHT_ATTN");      // experiments only: 0 / 1 forces the attention form used with images in flight
   const int multi_variant = force ? atoi(force) : 1;
-  for (int k = 0; k < count; ++k) { fs[k]->attn_variant = count > 1 ? multi_variant : 0; fs[k]->shared_chip = count > 1; }
+  for (int k = 0; k < count; ++k) { fs[k]->attn_variant = count > 1 ? multi_variant : 0; fs[k]->shared_chip = count > 1; block_cache_reset(fs[k]); }
   int rc = TD_OK;
   for (int i = 0; i < n && rc == TD_OK; ++i)
     for (int k = 0; k < count && rc == TD_OK; ++k) {
@@ -1035,6 +1175,8 @@ int td_flux_denoise_cfg(td_flux* pos, td_flux* neg, void* latents, const float* 
   const long long count = (long long)pos->S_img * pos->m->Cout;
   TD_CHECK_ARG(!overlaps(latents, (size_t)count * 2, pos->vout, (size_t)count * 2) && !overlaps(latents, (size_t)count * 2, neg->vout, (size_t)count * 2),
                "td_flux_denoise_cfg: latents overlap a context's velocity buffer");
+  block_cache_reset(pos);      // two contexts, two cache states: diffusers' separate cond / uncond cache contexts
+  block_cache_reset(neg);
   for (int i = 0; i < n; ++i) {
     TD_TRY(td_flux_forward(pos, latents, i, pos->vout, stream));
     TD_TRY(td_flux_forward(neg, latents, i, neg->vout, stream));

@@ -153,6 +153,12 @@ struct FluxModel {
   // Every setter that changes weights, precision, Linear classes, scale mode or attention mode bumps the history epoch: a context trusts its
   // per-step history (td_flux::href, hs_*) only when it was recorded in the current one.
   int hist_epoch = 0;
+  // First-block cache (td_flux_set_block_cache / _schedule; include/thinkdiff_hip.h spells the semantics): 0 off, 1 threshold, 2 fixed schedule.
+  // The settings are the model's -- forks follow their parent -- and every change bumps bc_epoch, which voids every context's cache state.
+  int bc_mode = 0;
+  float bc_threshold = 0.f;
+  std::vector<unsigned char> bc_schedule;
+  int bc_epoch = 0;
 };
 
 // int8 smoothing: the first forward after a change calibrates -- it runs on the bf16 path and collects channel maxima
@@ -237,6 +243,20 @@ struct td_flux {
   };
   IpCtx ip[TD_IP_MAX_ADAPTERS];
   bf16_t* ip_out = nullptr;
+  // ---- First-block cache state of THIS image (the settings are the model's).  One allocation, made at the first forward under the cache:
+  // bc_r[2] [max_img, D] -- bc_r[bc_cur] is r_prev, the residual of the last computed forward, the other one receives this forward's -- and bc_tail
+  // [max_img, D]: h1's latent rows during a computed forward, then (in place) what the remaining blocks added to them; bc_ws / bc_sums: the head
+  // kernel's partial sums and its two fp64 results, which bc_host (16 pinned bytes) receives before the decision.  h0 needs no buffer of its own: it
+  // waits in f->cat, which no double block touches.
+  char* bc_buf = nullptr;
+  bf16_t *bc_r[2] = {nullptr, nullptr}, *bc_tail = nullptr;
+  double *bc_ws = nullptr, *bc_sums = nullptr, *bc_host = nullptr;
+  int bc_cur = 0;
+  bool bc_has_prev = false;                 // bc_r[bc_cur] and bc_tail hold a computed forward's values for the layout / epochs below
+  int bc_T = 0, bc_S_img = 0, bc_S_ref = 0, bc_wepoch = -1, bc_cepoch = -1;
+  int bc_count = 0;                         // forwards since the last reset (the schedule's index)
+  std::vector<float> bc_metric;             // the log since the last reset (td_flux_block_cache_stats), at most BC_LOG_MAX entries
+  std::vector<unsigned char> bc_computed;
   // optional per-launch HIP-event trace (bench.py roofline leg)
   bool tracing = false;
   std::vector<hipEvent_t> ev_pool;

@@ -206,6 +206,10 @@ int td_temb_combine_silu_launch(const bf16_t* te, const bf16_t* ge, const bf16_t
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream);
 int td_flux_cfg_step_launch(bf16_t* x, const bf16_t* v_pos, const bf16_t* v_neg, float scale, float dt, long long n, hipStream_t stream);
 int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr, int rows, int D, float scale, hipStream_t stream);
+// csrc/block_cache.hip: the first-block cache's residual + deterministic metric sums, and its tail difference (td_block_cache_*_bf16 document both)
+int td_block_cache_head_launch(const bf16_t* h1, int ld1, const bf16_t* h0, int ld0, const bf16_t* r_prev, int ldp, bf16_t* r, int ldr, int rows, int D,
+                               double* sums, double* ws, hipStream_t stream);
+int td_block_cache_tail_launch(const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* out, int ldo, int rows, int D, hipStream_t stream);
 // csrc/ip_attention.hip: FLUX IP-Adapter cross-attention (td_ip_attention_bf16 documents the arithmetic); validates its arguments
 int td_ip_attention_launch(const bf16_t* q, int ldq, const bf16_t* k, const bf16_t* v, int ldkv, bf16_t* o, int ldo, int rows, int H, int n_keys,
                            const bf16_t* norm_w, float eps, float out_scale, int accumulate, hipStream_t stream);

@@ -14,6 +14,8 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <tuple>
+
 #include "../../include/thinkdiff_hip.h"
 
 namespace {
@@ -159,6 +161,34 @@ at::Tensor& flux_residual_inject_(at::Tensor& h, const at::Tensor& r, double sca
   DeviceGuard guard(h.device());
   ok(td_flux_residual_inject_bf16(h.data_ptr(), h.stride(0), r.data_ptr(), r.stride(0), (int)h.size(0), (int)r.size(1), (float)scale, stream_of(h)));
   return h;
+}
+
+// First-block cache, the residual and its metric sums (td_block_cache_head_bf16): h1, h0 [rows, D] and the optional r_prev, 2-D views with innermost
+// stride 1 -> (r = bf16(h1 - h0) [rows, D], sums fp64 [2] = sum |r - r_prev|, sum |r_prev|; both 0 without r_prev).  Deterministic: no atomics.
+std::tuple<at::Tensor, at::Tensor> block_cache_head(const at::Tensor& h1, const at::Tensor& h0, const c10::optional<at::Tensor>& r_prev) {
+  check_rows(h1, "h1"); check_rows(h0, "h0"); same_device(h0, "h0", h1);
+  TORCH_CHECK(h1.dim() == 2 && h0.dim() == 2 && h0.sizes() == h1.sizes() && h1.size(0) > 0 && h1.size(1) > 0, "thinkdiff_hip::block_cache_head: h1, h0 [rows, D] of one shape");
+  const bool prev = r_prev.has_value() && r_prev->defined();
+  if (prev) {
+    check_rows(*r_prev, "r_prev"); same_device(*r_prev, "r_prev", h1);
+    TORCH_CHECK(r_prev->dim() == 2 && r_prev->sizes() == h1.sizes(), "thinkdiff_hip::block_cache_head: r_prev must have h1's shape");
+  }
+  DeviceGuard guard(h1.device());
+  at::Tensor r = at::empty({h1.size(0), h1.size(1)}, h1.options());
+  at::Tensor sums = at::empty({2}, h1.options().dtype(at::kDouble));
+  at::Tensor ws = at::empty({TD_BLOCK_CACHE_WS_BYTES / 8}, h1.options().dtype(at::kDouble));
+  ok(td_block_cache_head_bf16(h1.data_ptr(), h1.stride(0), h0.data_ptr(), h0.stride(0), prev ? r_prev->data_ptr() : nullptr, prev ? r_prev->stride(0) : 0, r.data_ptr(),
+                              r.stride(0), (int)h1.size(0), (int)h1.size(1), (double*)sums.data_ptr(), ws.data_ptr(), stream_of(h1)));
+  return {r, sums};
+}
+// ... and its tail (td_block_cache_tail_bf16): bf16(a - b) for 2-D views a, b [rows, D] with innermost stride 1
+at::Tensor block_cache_tail(const at::Tensor& a, const at::Tensor& b) {
+  check_rows(a, "a"); check_rows(b, "b"); same_device(b, "b", a);
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.sizes() == b.sizes() && a.size(0) > 0 && a.size(1) > 0, "thinkdiff_hip::block_cache_tail: a, b [rows, D] of one shape");
+  DeviceGuard guard(a.device());
+  at::Tensor out = at::empty({a.size(0), a.size(1)}, a.options());
+  ok(td_block_cache_tail_bf16(a.data_ptr(), a.stride(0), b.data_ptr(), b.stride(0), out.data_ptr(), out.stride(0), (int)a.size(0), (int)a.size(1), stream_of(a)));
+  return out;
 }
 
 // FLUX IP-Adapter cross-attention (td_ip_attention_bf16): q [rows, >= H*128] (raw projection rows when norm_w is given: the per-head QK-RMSNorm is
@@ -644,6 +674,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_set_reference_tokens(int engine, Tensor ref_latents, Tensor ref_ids) -> ()");
   m.def("flux_cfg_step_(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)");
   m.def("flux_residual_inject_(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)");
+  m.def("block_cache_head(Tensor h1, Tensor h0, Tensor? r_prev) -> (Tensor, Tensor)");
+  m.def("block_cache_tail(Tensor a, Tensor b) -> Tensor");
   m.def("flux_denoise_cfg_(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)");
   m.def("vae_encode_moments_masked(int engine, Tensor image, Tensor mask, int H, int W) -> Tensor");
   m.def("flux_fill_condition(Tensor moments, Tensor? eps, Tensor mask, float scaling_factor, float shift_factor, int H, int W) -> Tensor");
@@ -687,6 +719,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_set_reference_tokens", &flux_set_reference_tokens);
   m.impl("flux_cfg_step_", &flux_cfg_step_);
   m.impl("flux_residual_inject_", &flux_residual_inject_);
+  m.impl("block_cache_head", &block_cache_head);
+  m.impl("block_cache_tail", &block_cache_tail);
   m.impl("flux_denoise_cfg_", &flux_denoise_cfg_);
   m.impl("vae_encode_moments_masked", &vae_encode_moments_masked);
   m.impl("flux_fill_condition", &flux_fill_condition);

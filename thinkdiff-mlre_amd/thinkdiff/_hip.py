@@ -52,6 +52,12 @@ def _declare(L):
         "td_flux_inpaint_step_bf16": [vp, vp, vp, vp, vp, f32, f32, i64, vp],
         "td_flux_cfg_step_bf16": [vp, vp, vp, f32, f32, i64, vp],
         "td_flux_residual_inject_bf16": [vp, i64, vp, i64, i32, i32, f32, vp],
+        "td_block_cache_head_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp],
+        "td_block_cache_tail_bf16": [vp, i64, vp, i64, vp, i64, i32, i32, vp],
+        "td_flux_set_block_cache": [vp, i32, f32],
+        "td_flux_set_block_cache_schedule": [vp, vp, i32],
+        "td_flux_block_cache_reset": [vp],
+        "td_flux_block_cache_stats": [vp, i32, vp, vp, vp],
         "td_flux_controlnet_create": [vp, i32, i32, i32, i32, vp],
         "td_flux_controlnet_set_mode": [vp, i32],
         "td_flux_controlnet_set_condition": [vp, vp, vp],

@@ -45,7 +45,8 @@ Refused, not approximated, each naming what was asked: `conditioning_embedding_c
 form) and with it `controlnet_blocks_repeat`; lists of ControlNets (`FluxMultiControlNetModel`) and per-ControlNet lists of scales,
 starts or ends; everything flux_control.py refuses (`callback_on_step_end`, custom `sigmas`, lists of generators,
 `joint_attention_kwargs`); a ControlNet together with reference tokens, or on a channel-conditioned transformer; 8-bit precision setters
-and LoRA ON THE CONTROLNET MODEL (the main transformer may be in any mode, and may carry adapters).
+and LoRA ON THE CONTROLNET MODEL (the main transformer may be in any mode, and may carry adapters); a transformer whose first-block cache
+is enabled (`ValueError`; the engine refuses the same pairing at the forward).
 """
 import ctypes
 import dataclasses
@@ -238,6 +239,9 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
             raise ValueError(f"control_guidance_start = {start} exceeds control_guidance_end = {end}")
         if start < 0.0 or end > 1.0:
             raise ValueError(f"control_guidance_start = {start} / control_guidance_end = {end} outside [0, 1]")
+        if getattr(tr, "is_cache_enabled", False):
+            raise ValueError(f"{name}: the transformer's first-block cache is enabled and a ControlNet adds its samples behind every block (a skipped step "
+                             "runs one block): that pairing is not built; call pipe.transformer.disable_cache() first")
         c_lat = 64
         if tr.config.cond_channels:
             raise NotImplementedError(f"a ControlNet on a channel-conditioned transformer (in_channels = {tr.config.in_channels}, out_channels = "

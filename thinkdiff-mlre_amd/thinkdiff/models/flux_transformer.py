@@ -59,6 +59,26 @@ class FluxTransformerConfig:
                                  int(self.guidance_embeds), 4, (ctypes.c_int * 3)(*self.axes_dims_rope), 10000.0, int(self.out_channels or 0))
 
 
+@dataclasses.dataclass
+class FirstBlockCacheConfig:
+    """[ext] diffusers >= 0.33 `FirstBlockCacheConfig`: a denoise step whose first transformer block moved its output by no more than
+    `threshold` (relative mean absolute change of the block's residual against the last computed step's) reuses what the remaining blocks
+    added at that step instead of running them.  0 = always compute; diffusers suggests 0.05 - 0.2 for FLUX."""
+    threshold: float = 0.05
+
+    def __post_init__(self):
+        t = self.threshold
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not t >= 0:      # (NaN fails the comparison)
+            raise ValueError(f"FirstBlockCacheConfig: threshold = {t!r} must be a number >= 0")
+        self.threshold = float(t)
+
+
+def apply_first_block_cache(transformer: "FluxTransformer2DModel", config: Optional[FirstBlockCacheConfig] = None) -> "FluxTransformer2DModel":
+    """[ext] diffusers `apply_first_block_cache(module, config)`: the same as `transformer.enable_cache(config)`."""
+    transformer.enable_cache(config or FirstBlockCacheConfig())
+    return transformer
+
+
 def effective_scalar(value: float, dtype: torch.dtype) -> float:
     """What the sinusoidal embedding finally sees for `timestep`/`guidance` in the reference pipeline:
     cast to the latents dtype, /1000 in the pipeline, *1000 in the transformer, all in `dtype`
@@ -386,6 +406,61 @@ class FluxTransformer2DModel:
         v = v_neg + scale * (v_pos - v_neg) and the Euler step, fused.  One stream."""
         assert latents.dtype == torch.bfloat16 and latents.is_contiguous() and latents.shape == (self._n_img, self.config.latent_channels)
         return _OPS.flux_denoise_cfg_(int(self._h.value), int(neg_context._h.value), latents, [float(s) for s in sigmas], float(scale))
+
+    # ---- first-block cache (td_flux_set_block_cache*; the names of diffusers' CacheMixin) ---------------------------
+    def _cache_root(self, what: str) -> "FluxTransformer2DModel":
+        if getattr(self, "_parent", None) is not None:
+            raise _hip.ThinkDiffHipError(f"{what}: the cache settings belong to the parent transformer (forks follow it)")
+        return self
+
+    def enable_cache(self, config: Optional[FirstBlockCacheConfig] = None):
+        """Skip the blocks behind the first on denoise steps where its residual changed by no more than `config.threshold` (FirstBlockCacheConfig).
+        The setting is the model's: every pipeline built on this transformer honours it, forks included; each context (image in flight, CFG
+        branch) keeps its own state, reset at the start of every denoise loop.  Costs one host synchronisation per forward while enabled."""
+        config = config or FirstBlockCacheConfig()
+        if not isinstance(config, FirstBlockCacheConfig):
+            raise ValueError(f"enable_cache: config is a {type(config).__name__}; only FirstBlockCacheConfig is built (no TeaCache, FasterCache or "
+                             "PyramidAttentionBroadcast)")
+        r = self._cache_root("enable_cache")
+        _hip.check(self._L.td_flux_set_block_cache(r._h, 1, float(config.threshold)))
+        r._cache_config, r._cache_schedule = config, None
+        return self
+
+    def set_cache_schedule(self, compute: Sequence):
+        """A fixed schedule instead of the threshold: forward i of every denoise loop (counted from the state's last reset) runs all blocks where
+        compute[i] is true and reuses the last computed forward's tail where it is false; forwards beyond the list are computed.  compute[0]
+        must be true.  The metric is still taken and logged (cache_stats)."""
+        r = self._cache_root("set_cache_schedule")
+        flags = bytes(1 if c else 0 for c in compute)
+        _hip.check(self._L.td_flux_set_block_cache_schedule(r._h, flags, len(flags)))
+        r._cache_config, r._cache_schedule = None, [bool(c) for c in compute]
+        return self
+
+    def disable_cache(self):
+        r = self._cache_root("disable_cache")
+        _hip.check(self._L.td_flux_set_block_cache(r._h, 0, 0.0))
+        r._cache_config = r._cache_schedule = None
+        return self
+
+    @property
+    def is_cache_enabled(self) -> bool:
+        r = self._root()
+        return getattr(r, "_cache_config", None) is not None or getattr(r, "_cache_schedule", None) is not None
+
+    def reset_cache(self):
+        """Forget THIS context's cache state and log (every denoise loop does so at its start)."""
+        _hip.check(self._L.td_flux_block_cache_reset(self._h))
+
+    def cache_stats(self):
+        """(metrics, computed) of THIS context's forwards since its state was last reset: the first-block metric of each (inf where there was no
+        previous residual) and whether all blocks ran."""
+        n = ctypes.c_int()
+        _hip.check(self._L.td_flux_block_cache_stats(self._h, 0, None, None, ctypes.byref(n)))
+        cap = max(1, n.value)
+        met, comp = (ctypes.c_float * cap)(), (ctypes.c_ubyte * cap)()
+        _hip.check(self._L.td_flux_block_cache_stats(self._h, cap, ctypes.cast(met, ctypes.c_void_p), ctypes.cast(comp, ctypes.c_void_p), ctypes.byref(n)))
+        k = min(cap, n.value)
+        return [float(met[i]) for i in range(k)], [bool(comp[i]) for i in range(k)]
 
     # ---- ControlNet (thinkdiff.models.flux_controlnet) ------------------------------------------------------
     def attach_controlnet(self, controlnet):

@@ -32,6 +32,8 @@ flux_set_reference_tokens  FluxKontextPipeline's per-step torch.cat of the refer
 flux_cfg_step_             true classifier-free guidance (neg + scale * (pos - neg)) + scheduler.step, fused, in place
 flux_denoise_cfg_          the denoise loop under true CFG: both conditionings per step on two prepared contexts, then flux_cfg_step_
 flux_residual_inject_      FluxTransformer2DModel's `hidden_states + controlnet_block_samples[..]` with the ControlNet's `* conditioning_scale`, fused, in place
+block_cache_head / block_cache_tail   diffusers' First Block Cache arithmetic: the first block's residual with the two sums of its
+                           `(r - r_prev).abs().mean() / r_prev.abs().mean()` test taken deterministically (no atomics), and the tail difference
 lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up to 8 pairs at once, fp32 accumulation, one rounding
 flux_lora_load / flux_lora_set_adapters / flux_lora_delete / flux_read_param   diffusers' load_lora_weights / set_adapters / delete_adapters
                            (empty name: unload_lora_weights) on the engine's merged weights, and the effective parameter read back; the last
@@ -74,6 +76,8 @@ SCHEMAS = {
     "flux_set_reference_tokens": "(int engine, Tensor ref_latents, Tensor ref_ids) -> ()",
     "flux_cfg_step_": "(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)",
     "flux_residual_inject_": "(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)",
+    "block_cache_head": "(Tensor h1, Tensor h0, Tensor? r_prev) -> (Tensor, Tensor)",
+    "block_cache_tail": "(Tensor a, Tensor b) -> Tensor",
     "flux_denoise_cfg_": "(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)",
     "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
     "lora_merge": "(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor",

@@ -389,6 +389,39 @@ def bench_norm():
           f"8-bit out {bq*1e3:.1f} us", flush=True)
 
 
+def bench_blockcache():
+    """The first-block cache's two kernels at the 1024^2 shape (4096 image rows of a [4608, 3072] joint buffer; and 8192 rows: Kontext) against
+    hipMemcpyAsync (torch's device-to-device copy_) of the SAME byte count in the same process, rotating over operand sets larger than the caches.
+    head: reads h1, h0, r_prev, writes r (4 x rows x D x 2 bytes) + the partial-sum finish launch; tail: reads a, b, writes out (3 x)."""
+    import thinkdiff.ops  # noqa: F401
+    ops = torch.ops.thinkdiff_hip
+    D = 3072
+    for rows in (4096, 8192):
+        n_sets = 6
+        sets = [[torch.randn(rows + 512, D, device="cuda").bfloat16()[512:] for _ in range(3)] for _ in range(n_sets)]
+        st = {"i": 0}
+        def head():
+            st["i"] = (st["i"] + 1) % n_sets
+            ops.block_cache_head(*sets[st["i"]])
+        def tail():
+            st["i"] = (st["i"] + 1) % n_sets
+            ops.block_cache_tail(sets[st["i"]][0], sets[st["i"]][1])
+        def copy_of(n_bufs):      # n_bufs x rows x D x 2 bytes moved: half read, half written
+            elems = n_bufs * rows * D // 2
+            src = [torch.randn(elems, device="cuda").bfloat16() for _ in range(n_sets)]
+            dst = torch.empty(elems, device="cuda", dtype=torch.bfloat16)
+            def f():
+                st["i"] = (st["i"] + 1) % n_sets
+                dst.copy_(src[st["i"]])
+            return min(timeit(f, iters=50, warmup=5) for _ in range(3))
+        t_head = min(timeit(head, iters=50, warmup=5) for _ in range(3))
+        t_tail = min(timeit(tail, iters=50, warmup=5) for _ in range(3))
+        c_head, c_tail = copy_of(4), copy_of(3)
+        bh, bt = 4 * rows * D * 2, 3 * rows * D * 2
+        print(f"block cache rows={rows} D={D}: head {t_head*1e3:.1f} us ({bh/1e6:.0f} MB, {bh/t_head/1e9:.2f} TB/s) vs copy of the same bytes {c_head*1e3:.1f} us "
+              f"= {t_head/c_head:.2f}x;  tail {t_tail*1e3:.1f} us ({bt/1e6:.0f} MB, {bt/t_tail/1e9:.2f} TB/s) vs copy {c_tail*1e3:.1f} us = {t_tail/c_tail:.2f}x", flush=True)
+
+
 def bench_gemmref():
     """External yardstick for the block GEMMs (measurement only; never in the product): torch.nn.functional.linear (= hipBLASLt on
     this image) against td_linear on the six FLUX.1-dev block shapes at the joint sequence length, random operands, same box, same
