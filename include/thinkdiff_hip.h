@@ -565,6 +565,75 @@ int td_norm_rows_quant_fp8(const void* x, int64_t ldx, void* q, int64_t ldq, flo
                            const void* w, int split, const void* shiftA, const void* scaleA, const void* shiftB, const void* scaleB,
                            void* stream);
 
+/* ---- int8 policy building blocks (td_abi_version() >= 7) -----------------------------------------------------------------------------------
+ * The launch forms of the 8-bit policy that only the FLUX engine used to reach (int8 block Linears, history scales, per-channel smoothing with
+ * replicated outlier channels, int8 attention output), one thin entry each, so that every kernel of the policy can be compared with its exact integer
+ * statement (tests/test_int8_policy_gpu.py).  The reference graph has none of this (it runs bf16): it belongs to BASELINE config 5's 8-bit MFMA path.
+ * The quantisation arithmetic, everywhere below, in fp32 and in this order:
+ *     s = amax * (1.0f / 127)   (448 for e4m3; 1.0f where amax == 0)      inv = 1.0f / s      q = clamp(rint(v * inv), -127, 127)   (half to even)
+ * Every entry refuses NULL required pointers, misaligned rows and extents that do not fit with TD_ERR_INVALID before any HIP call. */
+
+/* td_norm_rows_bf16 whose output row y leaves quantised, with smoothing and replicated channels (all of td_norm_rows_bf16's arguments first):
+ *   v[j]       = float(y[j]) * float(smooth[j])         smooth = smoothA for rows < split, smoothB for the others (bf16 [D]; NULL = none): a product
+ *                                                       of two bf16 values, exact in fp32
+ *   q_scale[r] = s(max_j |v[j]|),   q[r, j] = q(v[j])   j < D;   int8 != 0: symmetric int8, else OCP e4m3 under max / 448 (td_norm_rows_quant_fp8)
+ *   q[r, D + e] = ext[e] >= 0 ? q[r, ext[e]] : 0        e < ext_n; ext = extA / extB by the same row split (device int32 [ext_n], entries < D);
+ *                                                       int8 form only, both tables or none, ext_n even
+ * q rows are ldq bytes apart, ldq % 8 == 0, ldq >= D + ext_n; bytes beyond D + ext_n are untouched. */
+int td_norm_rows_quant8(const void* x, int64_t ldx, void* q, int64_t ldq, float* q_scale, int rows, int D, int rms, float eps,
+                        const void* w, int split, const void* shiftA, const void* scaleA, const void* shiftB, const void* scaleB,
+                        int int8, const void* smoothA, const void* smoothB, const int* extA, const int* extB, int ext_n, void* stream);
+/* td_quant_rows_int8 (int8 != 0) / td_quant_rows_fp8 with per-column factors and the row maxima:
+ *   v[r, j] = float(x[r, j]) * col_mul[j]  (fp32 [K], 16-byte aligned; NULL = none),   scale[r] = s(max_j |v[r, j]|),   q[r, j] = q(v[r, j]),
+ *   amax_out[r] = the float bits of max_j |v[r, j]|  (NULL = not wanted).   K % 8 == 0; ldx (elements) and ldq (bytes) multiples of 8, >= K. */
+int td_quant_rows8(const void* x, int64_t ldx, void* q, int64_t ldq, float* scale, int rows, int K, int int8, const float* col_mul, uint32_t* amax_out, void* stream);
+/* amax[j] = max(amax[j], max_r |x[r, j]|) on float bits (all values >= 0: unsigned order is float order), j < K, r < rows; a column of zeros leaves
+ * its accumulator as it was.  x bf16 [rows, ldx], K % 8 == 0. */
+int td_col_amax_bf16(const void* x, int64_t ldx, int rows, int K, uint32_t* amax, void* stream);
+/* SmoothQuant's balance at alpha = 1/2 rounded to a power of two, from two arrays of maxima (float bits, as td_col_amax_bf16 leaves them):
+ *   s[i] = 2^clamp(rint(0.5 * (log2 amax_x[i] - log2 amax_w[i])), -8, 8)   (1 where either maximum is 0),   inv[i] = 1 / s[i],   inv_bf16[i] = bf16(inv[i]) */
+int td_smooth_factors(const uint32_t* amax_x, const uint32_t* amax_w, int n, float* s, float* inv, void* inv_bf16, void* stream);
+/* History scales: scale[i] = float(amax[i]) * margin * (1.0f / 127) in fp32, left to right (1.0f where amax[i] == 0), inv[i] = 1.0f / scale[i], and
+ * amax[i] = 0 for the step being started.  margin >= 1 (the engine: 1.25). */
+int td_q8_scales_from_amax(uint32_t* amax, float* scale, float* inv, int64_t n, float margin, void* stream);
+/* q[r, K + e] = ext[e] >= 0 ? q[r, ext[e]] : 0   for e < ext_n, r < rows: the replicated input channels of an int8 weight whose rows are ld >= K + ext_n
+ * bytes apart (ext: device int32 [ext_n], entries < K).  The K original bytes and the bytes beyond K + ext_n are untouched. */
+int td_ext_cols_int8(void* q, int64_t ld, int rows, int K, const int* ext, int ext_n, void* stream);
+/* td_linear_int8 whose activated result leaves as int8 under per-row scales fixed IN ADVANCE (the engine: last step's maxima x 1.25):
+ *   t = bf16(acc * x_scale[m] * w_scale[n] + bias[n])        acc: the exact int32 contraction; the dequantisation in fp32
+ *   a = bf16(act(t))                                          (act = TD_ACT_ID_NONE: a = t)
+ *   v = float(a) * float(q8_smooth[n])                        bf16 [N] indexed by the ABSOLUTE output column (NULL = none): 1 / s of the next Linear
+ *   q8[m, n] = clamp(rint(v * q8_inv[m]), -127, 127),    q8_amax[m] = max(q8_amax[m], max_n |v|)  on float bits
+ * One problem of such a launch: */
+typedef struct TdLinearQ8Problem {
+  const void* xq; const float* x_scale;      /* int8 [M, ldx], fp32 [M] */
+  const void* wq; const float* w_scale;      /* int8 [N, K] contiguous, fp32 [N] */
+  const void* bias;                          /* bf16 [N] or NULL */
+  void* q8;                                  /* int8 out [M, ldq8] (the int8 columns only, from column 0) */
+  const float* q8_inv; uint32_t* q8_amax;    /* fp32 [M], float bits [M] */
+  const void* q8_smooth;                     /* bf16 [N] or NULL */
+  int M;
+} TdLinearQ8Problem;
+/* K % 128 == 0, N % 16 == 0, ldx and ldq8 multiples of 16, 16-byte aligned operands; tile_cfg 0 (256x256), 2 (32x256) or -1 (automatic; a shape for
+ * which that picks the 288x192 tile is refused: it has no int8 output).  No bf16 output is written.  Bytes beyond N of a q8 row are untouched. */
+int td_linear_int8_q8(const TdLinearQ8Problem* a, int64_t ldx, int64_t ldq8, int N, int K, int act, int tile_cfg, void* stream);
+/* The split-output form (td_linear_split_bf16 on int8 operands): columns [0, n_split) -> y0 bf16 under act0 as td_linear_int8 writes them, columns
+ * [n_split, N) -> a->q8[m, n - n_split] as int8 under act1, with q8_smooth still indexed by the absolute column n.  n_split % 256 == 0. */
+int td_linear_split_int8_q8(const TdLinearQ8Problem* a, int64_t ldx, int64_t ldq8, void* y0, int64_t ldy0, int act0, int act1, int N, int K, int n_split, int tile_cfg,
+                            void* stream);
+/* Two problems in one launch (td_linear_grouped2_bf16 on int8 operands: same N, K, strides, activation; own rows, weights, scales, smoothing). */
+int td_linear_grouped2_int8_q8(const TdLinearQ8Problem* a0, const TdLinearQ8Problem* a1, int64_t ldx, int64_t ldq8, int N, int K, int act, int tile_cfg, void* stream);
+/* The joint attention (one batch entry, Hq == Hkv = H, head_dim 128) whose output leaves as int8: with o = the bf16 output td_attention_bf16 (plain
+ * form, q_prescaled = 0) or td_attention_joint_prescaled_bf16 (q_prescaled != 0, score_bound as there; `scale` is then unused) writes for the same operands,
+ *   q8[s, h*128 + d] = clamp(rint(float(o[s, h*128 + d]) * q8_inv[s]), -127, 127),    q8_amax[s] = max(q8_amax[s], max over all heads |o[s, :]|).
+ * q8 rows are ldq8 bytes apart (% 8 == 0, >= H*128): the FLUX single-stream block passes its [attn | mlp] row, whose bytes beyond H*128 stay untouched.
+ * causal / bias exist so that the call shape is td_attention_bias_bf16's: a non-zero causal or a non-NULL bias is TD_ERR_INVALID. */
+int td_attention_q8(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* q8, int64_t ldq8, const float* q8_inv, uint32_t* q8_amax,
+                    int Sq, int Skv, int H, float scale, int causal, const float* bias, int q_prescaled, float score_bound, void* stream);
+/* The same over td_attention_fp8's output (same operands, workspace and arithmetic up to the store). */
+int td_attention_fp8_q8(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* q8, int64_t ldq8, const float* q8_inv, uint32_t* q8_amax,
+                        int Sq, int Skv, int H, float scale, void* workspace, void* stream);
+
 /* ---- building blocks of the text encoders (T5-XXL, CLIP-L) feeding encode_prompt
  * (thinkdiff/models/flux_prompt.py:88-104 -> [ext] FluxPipeline._get_t5_prompt_embeds / _get_clip_prompt_embeds) ---- */
 /* y = norm(x) for any D % 8 == 0: rms = 0 nn.LayerNorm(w, b, eps), rms = 1 T5LayerNorm(w). */

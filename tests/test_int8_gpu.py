@@ -1,7 +1,8 @@
 """int8 operand path (TD_PRECISION_INT8, round 3): the quantiser bit-exact against its torch statement, the int8 GEMM against the
 exact integer contraction of the very same quantised operands (int32 accumulation is exact, so only the dequantisation and the
 bf16 output rounding remain), the end-to-end quantisation error against the bf16 GEMM, and the FLUX engine in int8 mode against
-the oracle's int8 switch."""
+the oracle's int8 switch.  Kernel-level coverage of the policy's quantising kernels (norm -> int8 with smoothing and replicated channels, int8 GEMM and
+attention epilogues under history scales, the smoothing helpers), byte for byte: tests/test_int8_policy_gpu.py."""
 import pytest
 import torch
 

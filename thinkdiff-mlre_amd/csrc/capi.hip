@@ -17,10 +17,12 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 6; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 7; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
+                                            // 7: int8 policy building blocks (td_norm_rows_quant8, td_quant_rows8, td_col_amax_bf16, td_smooth_factors,
+                                            //    td_q8_scales_from_amax, td_ext_cols_int8, td_linear*_int8_q8, td_attention_q8, td_attention_fp8_q8)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -348,6 +350,180 @@ int td_norm_rows_quant_fp8(const void* x, int64_t ldx, void* q, int64_t ldq, flo
   if (p.scaleA && !p.scaleB) { p.scaleB = p.scaleA; p.shiftB = p.shiftA; }
   TD_CHECK_ARG(q && q_scale, "td_norm_rows_quant_fp8: null output");
   return td_norm_rows_launch(p, (hipStream_t)stream);
+}
+
+// ---- int8 policy building blocks (td_abi_version() >= 7): the launch forms only the FLUX engine used to reach, one thin entry each.  Every entry
+// checks its pointers, alignments and extents itself, before the launcher makes its first HIP call (several launchers ask for the device first).
+namespace {
+inline bool al(const void* p, unsigned a) { return ((uintptr_t)p) % a == 0; }
+inline bool ld32(int64_t ld) { return ld >= 0 && ld < (1ll << 31); }
+}  // namespace
+
+int td_norm_rows_quant8(const void* x, int64_t ldx, void* q, int64_t ldq, float* q_scale, int rows, int D, int rms, float eps,
+                        const void* w, int split, const void* shiftA, const void* scaleA, const void* shiftB, const void* scaleB,
+                        int int8, const void* smoothA, const void* smoothB, const int* extA, const int* extB, int ext_n, void* stream) {
+  TD_CHECK_ARG(x && q && q_scale, "td_norm_rows_quant8: x, q and q_scale are required");
+  TD_CHECK_ARG(rows > 0 && D > 0 && D % 512 == 0 && D <= 4096, "td_norm_rows_quant8: rows=%d, D=%d (a multiple of 512, at most 4096)", rows, D);
+  TD_CHECK_ARG(ld32(ldx) && ld32(ldq) && ldx % 8 == 0 && ldx >= D && ldq % 8 == 0, "td_norm_rows_quant8: ldx=%lld / ldq=%lld must be multiples of 8, ldx >= D",
+               (long long)ldx, (long long)ldq);
+  TD_CHECK_ARG(al(x, 16) && al(w, 16) && al(shiftA, 16) && al(scaleA, 16) && al(shiftB, 16) && al(scaleB, 16) && al(smoothA, 16) && al(smoothB, 16),
+               "td_norm_rows_quant8: x, w, the modulation rows and the smoothing factors must be 16-byte aligned");
+  TD_CHECK_ARG(al(q, 8) && al(q_scale, 4), "td_norm_rows_quant8: misaligned rows: q must be 8-byte aligned, q_scale 4-byte");
+  TD_CHECK_ARG((scaleA == nullptr) == (shiftA == nullptr) && (scaleB == nullptr) == (shiftB == nullptr) && (scaleA || !scaleB),
+               "td_norm_rows_quant8: shift and scale come together (B without A is not a form)");
+  TD_CHECK_ARG(ext_n >= 0 && (extA == nullptr) == (extB == nullptr) && (extA != nullptr) == (ext_n > 0), "td_norm_rows_quant8: replicated channels need both tables and ext_n > 0 (ext_n=%d)", ext_n);
+  if (ext_n > 0) {
+    TD_CHECK_ARG(int8 != 0, "td_norm_rows_quant8: replicated channels (ext tables) exist for the int8 form only");
+    TD_CHECK_ARG(ext_n % 2 == 0 && al(extA, 4) && al(extB, 4), "td_norm_rows_quant8: ext_n=%d must be even, the tables 4-byte aligned", ext_n);
+  }
+  TD_CHECK_ARG(ldq >= (int64_t)D + ext_n, "td_norm_rows_quant8: ldq=%lld is less than D + ext_n = %d bytes", (long long)ldq, D + ext_n);
+  TdNormParams p;
+  p.x = (const bf16_t*)x; p.ldx = (int)ldx; p.q = (uint8_t*)q; p.ldq = (int)ldq; p.q_scale = q_scale; p.q_int8 = int8 ? 1 : 0; p.rows = rows; p.D = D;
+  p.rms = rms; p.eps = eps; p.w = (const bf16_t*)w; p.split = split;
+  p.shiftA = (const bf16_t*)shiftA; p.scaleA = (const bf16_t*)scaleA;
+  p.shiftB = (const bf16_t*)shiftB; p.scaleB = (const bf16_t*)scaleB;
+  if (p.scaleA && !p.scaleB) { p.scaleB = p.scaleA; p.shiftB = p.shiftA; }
+  p.smoothA = (const bf16_t*)smoothA; p.smoothB = (const bf16_t*)smoothB;
+  p.extA = extA; p.extB = extB; p.ext_n = ext_n;
+  return td_norm_rows_launch(p, (hipStream_t)stream);
+}
+
+int td_quant_rows8(const void* x, int64_t ldx, void* q, int64_t ldq, float* scale, int rows, int K, int int8, const float* col_mul, uint32_t* amax_out, void* stream) {
+  TD_CHECK_ARG(x && q && scale, "td_quant_rows8: x, q and scale are required");
+  TD_CHECK_ARG(rows > 0 && K > 0 && K % 8 == 0, "td_quant_rows8: rows=%d, K=%d (a multiple of 8)", rows, K);
+  TD_CHECK_ARG(ld32(ldx) && ld32(ldq) && ldx % 8 == 0 && ldq % 8 == 0 && ldx >= K && ldq >= K, "td_quant_rows8: ldx=%lld / ldq=%lld must be multiples of 8 and at least K",
+               (long long)ldx, (long long)ldq);
+  TD_CHECK_ARG(al(x, 16) && al(q, 8) && al(scale, 4) && al(amax_out, 4) && al(col_mul, 16), "td_quant_rows8: misaligned rows: x and col_mul 16-byte, q 8-byte, scale and amax_out 4-byte");
+  return td_quant_rows_fp8_launch((const bf16_t*)x, (int)ldx, (uint8_t*)q, (int)ldq, scale, rows, K, (hipStream_t)stream, int8 ? 1 : 0, amax_out, col_mul);
+}
+
+int td_col_amax_bf16(const void* x, int64_t ldx, int rows, int K, uint32_t* amax, void* stream) {
+  TD_CHECK_ARG(x && amax, "td_col_amax_bf16: x and amax are required");
+  TD_CHECK_ARG(rows > 0 && K > 0 && K % 8 == 0 && ld32(ldx) && ldx % 8 == 0 && ldx >= K, "td_col_amax_bf16: rows=%d, K=%d, ldx=%lld (K and ldx multiples of 8, ldx >= K)", rows, K, (long long)ldx);
+  TD_CHECK_ARG(al(x, 16) && al(amax, 4), "td_col_amax_bf16: misaligned rows: x must be 16-byte aligned, amax 4-byte");
+  return td_col_amax_launch((const bf16_t*)x, (int)ldx, rows, K, amax, (hipStream_t)stream);
+}
+
+int td_smooth_factors(const uint32_t* amax_x, const uint32_t* amax_w, int n, float* s, float* inv, void* inv_bf16, void* stream) {
+  TD_CHECK_ARG(amax_x && amax_w && s && inv && inv_bf16, "td_smooth_factors: both maxima and all three outputs are required");
+  TD_CHECK_ARG(n > 0 && al(amax_x, 4) && al(amax_w, 4) && al(s, 4) && al(inv, 4) && al(inv_bf16, 2), "td_smooth_factors: n=%d must be positive, the arrays aligned to their element", n);
+  return td_smooth_factors_launch(amax_x, amax_w, n, s, inv, (bf16_t*)inv_bf16, (hipStream_t)stream);
+}
+
+int td_q8_scales_from_amax(uint32_t* amax, float* scale, float* inv, int64_t n, float margin, void* stream) {
+  TD_CHECK_ARG(amax && scale && inv, "td_q8_scales_from_amax: amax, scale and inv are required");
+  TD_CHECK_ARG(n > 0 && al(amax, 4) && al(scale, 4) && al(inv, 4), "td_q8_scales_from_amax: n=%lld must be positive, the arrays 4-byte aligned", (long long)n);
+  TD_CHECK_ARG(margin >= 1.0f, "td_q8_scales_from_amax: margin=%g below 1 would clip values the last step has seen", (double)margin);      // (false for NaN too)
+  return td_q8_scales_from_amax_launch(amax, scale, inv, (long long)n, margin, (hipStream_t)stream);
+}
+
+int td_ext_cols_int8(void* q, int64_t ld, int rows, int K, const int* ext, int ext_n, void* stream) {
+  TD_CHECK_ARG(q && ext && al(ext, 4), "td_ext_cols_int8: q and a 4-byte aligned ext table are required");
+  TD_CHECK_ARG(rows > 0 && K > 0 && ext_n > 0 && ld32(ld) && ld >= (int64_t)K + ext_n, "td_ext_cols_int8: rows=%d, K=%d, ext_n=%d, ld=%lld (ld >= K + ext_n)", rows, K, ext_n, (long long)ld);
+  return td_ext_cols_launch((uint8_t*)q, (int)ld, rows, K, ext, ext_n, (hipStream_t)stream);
+}
+
+namespace {
+// what the three int8-output Linear entries share: one problem's operands and its int8 output of n_q8 columns
+int q8_linear_check(const char* me, const TdLinearQ8Problem& a, int64_t ldx, int64_t ldq8, int N, int K, int n_q8, int act, int tile_cfg) {
+  TD_CHECK_ARG(a.xq && a.x_scale && a.wq && a.w_scale, "%s: the int8 operands and their scales are required", me);
+  TD_CHECK_ARG(a.q8, "%s: the int8 output q8 is required", me);
+  TD_CHECK_ARG(a.q8_inv && a.q8_amax, "%s: the int8 output needs its per-row inverse scales (q8_inv) and its maxima accumulators (q8_amax)", me);
+  TD_CHECK_ARG(a.M > 0 && N > 0 && K > 0 && K % 128 == 0, "%s: M=%d, N=%d, K=%d (K a multiple of 128)", me, a.M, N, K);
+  TD_CHECK_ARG(n_q8 > 0 && n_q8 % 16 == 0 && N % 16 == 0, "%s: the int8 output is written 16 columns at a time: N=%d and its %d int8 columns must be multiples of 16", me, N, n_q8);
+  TD_CHECK_ARG(ld32(ldx) && ld32(ldq8) && ldx % 16 == 0 && ldx >= K && ldq8 % 16 == 0 && ldq8 >= n_q8,
+               "%s: ldx=%lld (>= K) and ldq8=%lld (>= the int8 columns) must be multiples of 16", me, (long long)ldx, (long long)ldq8);
+  TD_CHECK_ARG(al(a.xq, 16) && al(a.wq, 16) && al(a.q8, 16) && al(a.bias, 16) && al(a.q8_smooth, 16) && al(a.x_scale, 4) && al(a.w_scale, 16) && al(a.q8_inv, 4) && al(a.q8_amax, 4),
+               "%s: misaligned rows: xq, wq, q8, bias, q8_smooth and w_scale must be 16-byte aligned, the per-row arrays 4-byte", me);
+  TD_CHECK_ARG(td_act_valid(act), "%s: unknown activation code %d", me, act);
+  TD_CHECK_ARG(tile_cfg == -1 || tile_cfg == 0 || tile_cfg == 2, "%s: tile_cfg=%d: the int8 output exists on the 256-column tiles 0 (256x256) and 2 (32x256); -1 = automatic", me, tile_cfg);
+  return 0;
+}
+void q8_linear_fill(TdGemmParams& p, const TdLinearQ8Problem& a, int64_t ldx, int64_t ldq8, int N, int K, int tile_cfg) {
+  p.i8 = 1; p.A = (const bf16_t*)a.xq; p.lda = (int)ldx; p.a_scale = a.x_scale; p.W = (const bf16_t*)a.wq; p.w_scale = a.w_scale; p.bias = (const bf16_t*)a.bias;
+  p.M = a.M; p.N = N; p.K = K; p.cfg = tile_cfg;
+  p.q8 = (uint8_t*)a.q8; p.ldq8 = (int)ldq8; p.q8_inv = a.q8_inv; p.q8_amax = a.q8_amax; p.q8_smooth = (const bf16_t*)a.q8_smooth;
+}
+}  // namespace
+
+int td_linear_int8_q8(const TdLinearQ8Problem* a, int64_t ldx, int64_t ldq8, int N, int K, int act, int tile_cfg, void* stream) {
+  TD_CHECK_ARG(a, "td_linear_int8_q8: null problem");
+  if (int rc = q8_linear_check("td_linear_int8_q8", *a, ldx, ldq8, N, K, N, act, tile_cfg)) return rc;
+  TdGemmParams p;
+  q8_linear_fill(p, *a, ldx, ldq8, N, K, tile_cfg);
+  p.act = act; p.ldc = N;      // (no bf16 output in this form: C stays null and is never stored to)
+  return td_gemm_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_split_int8_q8(const TdLinearQ8Problem* a, int64_t ldx, int64_t ldq8, void* y0, int64_t ldy0, int act0, int act1, int N, int K, int n_split, int tile_cfg,
+                            void* stream) {
+  TD_CHECK_ARG(a, "td_linear_split_int8_q8: null problem");
+  TD_CHECK_ARG(n_split > 0 && n_split < N && n_split % 256 == 0, "td_linear_split_int8_q8: n_split=%d must be a multiple of the 256-column tile inside (0, N=%d)", n_split, N);
+  if (int rc = q8_linear_check("td_linear_split_int8_q8", *a, ldx, ldq8, N, K, N - n_split, act1, tile_cfg)) return rc;
+  TD_CHECK_ARG(y0 && al(y0, 16) && ld32(ldy0) && ldy0 % 8 == 0 && ldy0 >= n_split, "td_linear_split_int8_q8: y0 must be 16-byte aligned with ldy0=%lld a multiple of 8, >= n_split", (long long)ldy0);
+  TD_CHECK_ARG(td_act_valid(act0), "td_linear_split_int8_q8: unknown activation code %d", act0);
+  TdGemmParams p;
+  q8_linear_fill(p, *a, ldx, ldq8, N, K, tile_cfg);
+  p.C = (bf16_t*)y0; p.ldc = (int)ldy0; p.act = act0; p.act2 = act1; p.n_split = n_split;
+  // The kernel tells a split launch by a non-null C2, so one must be given; the int8 rows stand in and nothing is ever stored through it as bf16.
+  // That rests on two things in gemm_bf16.hip: the Q8 epilogue returns after its int8 store, before the bf16 one, for every tile of the second
+  // output; and plan_split_k() gives 1 part whenever i8 or q8 is set, so the split-K reduce kernel, which does store through C2, is never launched.
+  p.C2 = (bf16_t*)a->q8; p.ldc2 = 0;
+  return td_gemm_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_grouped2_int8_q8(const TdLinearQ8Problem* a0, const TdLinearQ8Problem* a1, int64_t ldx, int64_t ldq8, int N, int K, int act, int tile_cfg, void* stream) {
+  TD_CHECK_ARG(a0 && a1, "td_linear_grouped2_int8_q8: two problems are required");
+  if (int rc = q8_linear_check("td_linear_grouped2_int8_q8 (problem 0)", *a0, ldx, ldq8, N, K, N, act, tile_cfg)) return rc;
+  if (int rc = q8_linear_check("td_linear_grouped2_int8_q8 (problem 1)", *a1, ldx, ldq8, N, K, N, act, tile_cfg)) return rc;
+  TdGemmParams p;
+  q8_linear_fill(p, *a0, ldx, ldq8, N, K, tile_cfg);
+  p.act = act; p.ldc = N;
+  p.g_A = (const bf16_t*)a1->xq; p.g_a_scale = a1->x_scale; p.g_W = (const bf16_t*)a1->wq; p.g_w_scale = a1->w_scale; p.g_bias = (const bf16_t*)a1->bias; p.g_M = a1->M;
+  p.g_q8 = (uint8_t*)a1->q8; p.g_q8_inv = a1->q8_inv; p.g_q8_amax = a1->q8_amax; p.g_q8_smooth = (const bf16_t*)a1->q8_smooth;
+  // (no bf16 output in either problem: C and g_C stay null, which the launcher accepts of a q8 launch)
+  return td_gemm_launch(p, (hipStream_t)stream);
+}
+
+namespace {
+int attn_q8_check(const char* me, const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* q8, int64_t ldq8, const float* q8_inv,
+                  const uint32_t* q8_amax, int Sq, int Skv, int H) {
+  TD_CHECK_ARG(q && k && v, "%s: q, k and v are required", me);
+  TD_CHECK_ARG(q8, "%s: the int8 output q8 is required", me);
+  TD_CHECK_ARG(q8_inv && q8_amax, "%s: the int8 output needs its per-row inverse scales (q8_inv) and its maxima accumulators (q8_amax)", me);
+  TD_CHECK_ARG(Sq > 0 && Skv > 0 && H > 0 && H <= 65535, "%s: Sq=%d, Skv=%d, H=%d", me, Sq, Skv, H);
+  TD_CHECK_ARG(ld32(ldq) && ld32(ldkv) && ld32(ldq8) && ldq % 8 == 0 && ldkv % 8 == 0 && ldq8 % 8 == 0 && ldq >= (int64_t)H * 128 && ldkv >= (int64_t)H * 128 && ldq8 >= (int64_t)H * 128,
+               "%s: ldq=%lld, ldkv=%lld, ldq8=%lld must be multiples of 8 and at least H x 128", me, (long long)ldq, (long long)ldkv, (long long)ldq8);
+  TD_CHECK_ARG(al(q, 16) && al(k, 16) && al(v, 16) && al(q8, 8) && al(q8_inv, 4) && al(q8_amax, 4), "%s: misaligned rows: q, k, v must be 16-byte aligned, q8 8-byte, the per-row arrays 4-byte", me);
+  return 0;
+}
+}  // namespace
+
+int td_attention_q8(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* q8, int64_t ldq8, const float* q8_inv, uint32_t* q8_amax,
+                    int Sq, int Skv, int H, float scale, int causal, const float* bias, int q_prescaled, float score_bound, void* stream) {
+  TD_CHECK_ARG(!causal && !bias, "td_attention_q8: the int8 output form exists for the joint attention only (no causal mask, no score bias)");
+  if (int rc = attn_q8_check("td_attention_q8", q, ldq, k, v, ldkv, q8, ldq8, q8_inv, q8_amax, Sq, Skv, H)) return rc;
+  TD_CHECK_ARG(score_bound >= 0.f && score_bound <= 48.f && (score_bound == 0.f || q_prescaled), "td_attention_q8: a score bound goes with pre-scaled q and lies in (0, 48] octaves (0 = none)");
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v;
+  p.batch = 1; p.Sq = Sq; p.Skv = Skv; p.Hq = H; p.Hkv = H; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldq8; p.scale = q_prescaled ? 1.0f : scale; p.variant = g_attn_variant & 0xff;
+  p.q_prescaled = q_prescaled ? 1 : 0; p.score_bound = score_bound;
+  p.q8 = (uint8_t*)q8; p.ldq8 = (int)ldq8; p.q8_inv = q8_inv; p.q8_amax = q8_amax;
+  return td_attn_launch(p, (hipStream_t)stream);
+}
+
+int td_attention_fp8_q8(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* q8, int64_t ldq8, const float* q8_inv, uint32_t* q8_amax,
+                        int Sq, int Skv, int H, float scale, void* workspace, void* stream) {
+  if (int rc = attn_q8_check("td_attention_fp8_q8", q, ldq, k, v, ldkv, q8, ldq8, q8_inv, q8_amax, Sq, Skv, H)) return rc;
+  TD_CHECK_ARG(workspace && al(workspace, 16), "td_attention_fp8_q8: a 16-byte aligned workspace of td_attention_fp8_workspace_bytes(Sq, Skv, H) bytes is required");
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v;
+  p.batch = 1; p.Sq = Sq; p.Skv = Skv; p.Hq = H; p.Hkv = H; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldq8; p.scale = scale; p.f8_ws = workspace;
+  p.variant = ((g_attn_variant & 1) ? 0x1000 : 0) | ((g_attn_variant & 2) ? 0x2000 : 0);      // as td_attention_fp8 (without its timing probes)
+  p.q8 = (uint8_t*)q8; p.ldq8 = (int)ldq8; p.q8_inv = q8_inv; p.q8_amax = q8_amax;
+  return td_attn_fp8_launch(p, (hipStream_t)stream);
 }
 
 int td_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int vocab, float temperature, float top_p,

@@ -950,7 +950,7 @@ int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
   if (p.res) TD_CHECK_ARG(p.ldr % 4 == 0, "td_gemm: ldr must be a multiple of 4");
   if (p.C2) TD_CHECK_ARG(p.ldc2 % 8 == 0 && p.n_split % 8 == 0 && p.n_split < p.N, "td_gemm: bad split-output arguments");
   if (p.g_M > 0) {
-    TD_CHECK_ARG(p.g_A && p.g_W && p.g_C && !p.C2, "td_gemm: grouped launch needs A/W/C of the second problem and no split output");
+    TD_CHECK_ARG(p.g_A && p.g_W && (p.g_C || (p.q8 && p.g_q8)) && !p.C2, "td_gemm: grouped launch needs A/W/C of the second problem and no split output");      // (int8 outputs q8 / g_q8: no bf16 output, C and g_C may be null)
     TD_CHECK_ARG(((uintptr_t)p.g_A | (uintptr_t)p.g_W | (uintptr_t)p.g_C) % 16 == 0, "td_gemm: grouped pointers must be 16-byte aligned");
   }
   if (p.conv_H > 0) {

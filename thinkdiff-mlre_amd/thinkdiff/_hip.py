@@ -126,6 +126,17 @@ def _declare(L):
         "td_quant_rows_int8": [vp, i64, vp, i64, vp, i32, i32, vp],
         "td_linear_int8": [vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, i32, vp],
         "td_norm_rows_quant_fp8": [vp, i64, vp, i64, vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
+        "td_norm_rows_quant8": [vp, i64, vp, i64, vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp],
+        "td_quant_rows8": [vp, i64, vp, i64, vp, i32, i32, i32, vp, vp, vp],
+        "td_col_amax_bf16": [vp, i64, i32, i32, vp, vp],
+        "td_smooth_factors": [vp, vp, i32, vp, vp, vp, vp],
+        "td_q8_scales_from_amax": [vp, vp, vp, i64, f32, vp],
+        "td_ext_cols_int8": [vp, i64, i32, i32, vp, i32, vp],
+        "td_linear_int8_q8": [vp, i64, i64, i32, i32, i32, i32, vp],
+        "td_linear_split_int8_q8": [vp, i64, i64, vp, i64, i32, i32, i32, i32, i32, i32, vp],
+        "td_linear_grouped2_int8_q8": [vp, vp, i64, i64, i32, i32, i32, i32, vp],
+        "td_attention_q8": [vp, i64, vp, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp, i32, f32, vp],
+        "td_attention_fp8_q8": [vp, i64, vp, vp, i64, vp, i64, vp, vp, i32, i32, i32, f32, vp, vp],
         "td_layernorm_bf16": [vp, i64, vp, i64, i32, i32, i32, f32, vp, vp, vp],
         "td_add_rows_bf16": [vp, vp, vp, i32, i32, i32, vp],
         "td_glu_mul_bf16": [vp, vp, i32, i32, i32, vp],
@@ -206,6 +217,8 @@ def _declare(L):
     L.td_flux_param_elems.restype = ctypes.c_int64
     L.td_lora_packed_bytes.argtypes = [i32, i32, i32]
     L.td_lora_packed_bytes.restype = ctypes.c_size_t
+    L.td_attention_fp8_workspace_bytes.argtypes = [i32, i32, i32]
+    L.td_attention_fp8_workspace_bytes.restype = ctypes.c_size_t
     return sig
 
 
@@ -302,7 +315,6 @@ def attention_fp8(q, k, v, out, H, scale=None, workspace=None):
     if scale is None:
         scale = 128 ** -0.5
     L = lib()
-    L.td_attention_fp8_workspace_bytes.restype = ctypes.c_size_t
     nbytes = int(L.td_attention_fp8_workspace_bytes(Sq, Skv, H))
     ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=q.device)
     assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_contiguous()
@@ -320,7 +332,6 @@ def attention_fp8_qk_rope(qkv, out, H, cos, sin, split=0, wqA=None, wkA=None, wq
     if scale is None:
         scale = 128 ** -0.5
     L = lib()
-    L.td_attention_fp8_workspace_bytes.restype = ctypes.c_size_t
     nbytes = int(L.td_attention_fp8_workspace_bytes(S, S, H))
     ws = workspace if workspace is not None else torch.empty(nbytes, dtype=torch.uint8, device=qkv.device)
     assert ws.dtype == torch.uint8 and ws.numel() >= nbytes and ws.is_contiguous()
@@ -680,6 +691,125 @@ def norm_rows_quant_fp8(x, rms=False, eps=1e-6, w=None, split=0, shiftA=None, sc
     check(lib().td_norm_rows_quant_fp8(ptr(x), _rows(x), ptr(q), D, ptr(s), R, D, int(rms), float(eps), ptr(w), split,
                                        ptr(shiftA), ptr(scaleA), ptr(shiftB), ptr(scaleB), stream_ptr()))
     return q, s
+
+
+# ---- int8 policy building blocks (include/thinkdiff_hip.h, same heading): thin wrappers; maxima travel as int32 tensors holding float bits ------
+def _bytes2d(t):
+    assert t.dim() == 2 and t.stride(1) == 1 and t.dtype in (torch.int8, torch.uint8), (t.shape, t.stride(), t.dtype)
+    return t.stride(0)
+
+
+def norm_rows_quant8(x, int8=True, q=None, rms=False, eps=1e-6, w=None, split=0, shiftA=None, scaleA=None, shiftB=None, scaleB=None,
+                     smoothA=None, smoothB=None, extA=None, extB=None):
+    """td_norm_rows_quant8: (q [rows, >= D + ext_n] int8 / e4m3 bytes, fp32 scale [rows]); q may be a caller's wider (pre-filled) buffer."""
+    R, D = x.shape
+    ext_n = 0 if extA is None else extA.numel()
+    if q is None:
+        q = torch.empty(R, D + ext_n, dtype=torch.int8 if int8 else torch.uint8, device=x.device)
+    s = torch.empty(R, dtype=torch.float32, device=x.device)
+    check(lib().td_norm_rows_quant8(ptr(x), _rows(x), ptr(q), _bytes2d(q), ptr(s), R, D, int(rms), float(eps), ptr(w), split,
+                                    ptr(shiftA), ptr(scaleA), ptr(shiftB), ptr(scaleB), int(int8), ptr(smoothA), ptr(smoothB), ptr(extA), ptr(extB), ext_n, stream_ptr()))
+    return q, s
+
+
+def quant_rows8(x, int8=True, col_mul=None, want_amax=False, q=None):
+    """td_quant_rows8: (q, fp32 scale [R], int32 float-bits row maxima [R] or None)."""
+    R, K = x.shape
+    if q is None:
+        q = torch.empty(R, K, dtype=torch.int8 if int8 else torch.uint8, device=x.device)
+    s = torch.empty(R, dtype=torch.float32, device=x.device)
+    amax = torch.empty(R, dtype=torch.int32, device=x.device) if want_amax else None
+    check(lib().td_quant_rows8(ptr(x), _rows(x), ptr(q), _bytes2d(q), ptr(s), R, K, int(int8), ptr(col_mul), ptr(amax), stream_ptr()))
+    return q, s, amax
+
+
+def col_amax(x, amax, rows=None):
+    """td_col_amax_bf16 in place on amax (int32 float bits [K]) over the first `rows` rows of x."""
+    R, K = x.shape
+    assert amax.dtype == torch.int32 and amax.numel() == K and amax.is_contiguous()
+    check(lib().td_col_amax_bf16(ptr(x), _rows(x), R if rows is None else rows, K, ptr(amax), stream_ptr()))
+    return amax
+
+
+def smooth_factors(amax_x, amax_w):
+    """td_smooth_factors: (s fp32, 1 / s fp32, 1 / s bf16) from two int32 float-bits arrays."""
+    n = amax_x.numel()
+    assert amax_x.dtype == amax_w.dtype == torch.int32 and amax_w.numel() == n
+    s = torch.empty(n, dtype=torch.float32, device=amax_x.device)
+    inv = torch.empty_like(s)
+    inv16 = torch.empty(n, dtype=torch.bfloat16, device=amax_x.device)
+    check(lib().td_smooth_factors(ptr(amax_x), ptr(amax_w), n, ptr(s), ptr(inv), ptr(inv16), stream_ptr()))
+    return s, inv, inv16
+
+
+def q8_scales_from_amax(amax, margin):
+    """td_q8_scales_from_amax: (scale, inv) fp32; amax (int32 float bits) is cleared in place."""
+    n = amax.numel()
+    assert amax.dtype == torch.int32 and amax.is_contiguous()
+    scale = torch.empty(n, dtype=torch.float32, device=amax.device)
+    inv = torch.empty_like(scale)
+    check(lib().td_q8_scales_from_amax(ptr(amax), ptr(scale), ptr(inv), n, float(margin), stream_ptr()))
+    return scale, inv
+
+
+def ext_cols_int8(q, K, ext):
+    """td_ext_cols_int8 in place on q int8 [rows, >= K + ext_n]; ext int32 [ext_n] on the device."""
+    assert ext.dtype == torch.int32 and ext.is_contiguous()
+    check(lib().td_ext_cols_int8(ptr(q), _bytes2d(q), q.shape[0], K, ptr(ext), ext.numel(), stream_ptr()))
+    return q
+
+
+class TdLinearQ8Problem(ctypes.Structure):
+    """Mirror of `struct TdLinearQ8Problem` (include/thinkdiff_hip.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("xq", "x_scale", "wq", "w_scale", "bias", "q8", "q8_inv", "q8_amax", "q8_smooth")] + [("M", ctypes.c_int)]
+
+
+def q8_problem(xq, xs, wq, ws, bias, q8, q8_inv, q8_amax, q8_smooth=None):
+    """One problem of an int8-output Linear: xq int8 [M, K], wq int8 [N, K], q8 int8 [M, >= int8 columns], q8_amax int32 float bits [M]."""
+    assert xq.dtype == torch.int8 and wq.dtype == torch.int8 and wq.is_contiguous() and wq.shape[1] == xq.shape[1] and q8_amax.dtype == torch.int32
+    dp = lambda t: None if t is None else t.data_ptr()
+    pr = TdLinearQ8Problem(dp(xq), dp(xs), dp(wq), dp(ws), dp(bias), dp(q8), dp(q8_inv), dp(q8_amax), dp(q8_smooth), xq.shape[0])
+    pr._keep = (xq, xs, wq, ws, bias, q8, q8_inv, q8_amax, q8_smooth)
+    return pr
+
+
+def linear_int8_q8(pr, N, K, ldx, ldq8, act=ACT_NONE, tile_cfg=0):
+    check(lib().td_linear_int8_q8(ctypes.byref(pr), ldx, ldq8, N, K, act, tile_cfg, stream_ptr()))
+
+
+def linear_split_int8_q8(pr, N, K, ldx, ldq8, y0, act0, act1, n_split, tile_cfg=0):
+    check(lib().td_linear_split_int8_q8(ctypes.byref(pr), ldx, ldq8, ptr(y0), _rows(y0), act0, act1, N, K, n_split, tile_cfg, stream_ptr()))
+    return y0
+
+
+def linear_grouped2_int8_q8(pr0, pr1, N, K, ldx, ldq8, act=ACT_NONE, tile_cfg=0):
+    check(lib().td_linear_grouped2_int8_q8(ctypes.byref(pr0), ctypes.byref(pr1), ldx, ldq8, N, K, act, tile_cfg, stream_ptr()))
+
+
+def attention_q8(q, k, v, q8, q8_inv, q8_amax, H, scale=None, q_prescaled=False, score_bound=0.0):
+    """td_attention_q8: q, k, v bf16 [S, >= H*128] views, q8 int8 [Sq, >= H*128] (written in place), q8_amax int32 float bits [Sq] (max-accumulated)."""
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert k.stride() == v.stride() and q8_amax.dtype == torch.int32 and q8_inv.dtype == torch.float32
+    if scale is None:
+        scale = 128 ** -0.5
+    check(lib().td_attention_q8(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(q8), _bytes2d(q8), ptr(q8_inv), ptr(q8_amax), q.shape[0], k.shape[0], H,
+                                float(scale), 0, None, int(q_prescaled), float(score_bound), stream_ptr()))
+    return q8
+
+
+def attention_fp8_q8(q, k, v, q8, q8_inv, q8_amax, H, scale=None):
+    """td_attention_fp8_q8: as attention_q8 over the e4m3 joint attention."""
+    for t in (q, k, v):
+        assert t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert k.stride() == v.stride() and q8_amax.dtype == torch.int32 and q8_inv.dtype == torch.float32
+    if scale is None:
+        scale = 128 ** -0.5
+    L = lib()
+    ws = torch.empty(int(L.td_attention_fp8_workspace_bytes(q.shape[0], k.shape[0], H)), dtype=torch.uint8, device=q.device)
+    check(L.td_attention_fp8_q8(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(q8), _bytes2d(q8), ptr(q8_inv), ptr(q8_amax), q.shape[0], k.shape[0], H,
+                                float(scale), ptr(ws), stream_ptr()))
+    return q8
 
 
 def sample_top_p(logits, temperature, top_p, seed, offset, out=None):
