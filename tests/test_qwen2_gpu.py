@@ -435,6 +435,39 @@ def test_packed_prefill_equals_padded_and_single(hip):
         assert o["token_ids"] == ref["token_ids"]
 
 
+@pytest.mark.parametrize("Hq,Hkv", [(7, 1), (3, 1)])
+def test_prefill_forms_agree_when_q_width_is_no_multiple_of_256(hip, Hq, Hkv):
+    """Hq * 128 = 896 / 384 columns of q: the fused q | k | v Linear cannot split its output at a tile boundary, so the prefill runs q and k | v as
+    two Linears (the tiny config of the other prefill tests has 512 columns and never does).  Packed, right-padded and one-request-at-a-time prefill
+    give the same prompt states, and -- through two teacher-forced decode steps -- the same cache."""
+    from thinkdiff.models.qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
+    tc = Qwen2VLTextConfig(hidden_size=512, num_hidden_layers=2, num_attention_heads=Hq, num_key_value_heads=Hkv, intermediate_size=1024, vocab_size=1024)
+    g = torch.Generator().manual_seed(5)
+    lens = [1, 9, 33, 64, 70]
+    reqs = [{"prompt_token_ids": torch.randint(0, 1024, (n,), generator=g).tolist()} for n in lens]
+    forced = [torch.randint(0, 1024, (2,), generator=g).tolist() for _ in lens]
+    sp = SamplingParams(max_tokens=2, min_tokens=2, ignore_eos=True)
+    outs = {}
+    for mode in ("single", "padded", "packed"):
+        e = Qwen2VLTextEngine(tc, max_model_len=128, n_slots=len(lens), prefill_rows=512).init_random(3)
+        if mode == "single":
+            e.set_slots(1)
+            res = [e.generate(r["prompt_token_ids"], sp, forced_output_ids=f) for r, f in zip(reqs, forced)]
+            res = [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()} for o in res]
+        else:
+            e.packed_prefill = mode == "packed"
+            res = e.generate_batch([dict(r) for r in reqs], sp, forced_output_ids=forced)
+        torch.cuda.synchronize()
+        outs[mode] = res
+    for a, b, c, n in zip(outs["single"], outs["padded"], outs["packed"], lens):
+        for o in (a, b, c):
+            assert o["prompt_hidden_states"].shape == (n, 512) and o["hidden_states"].shape == (2, 512)
+            assert torch.isfinite(o["prompt_hidden_states"].float()).all() and torch.isfinite(o["hidden_states"].float()).all()
+        assert _rel(c["prompt_hidden_states"], a["prompt_hidden_states"]) < 5e-3 and _rel(c["hidden_states"], a["hidden_states"]) < 5e-3
+        assert _rel(c["prompt_hidden_states"], b["prompt_hidden_states"]) < 5e-3 and _rel(c["hidden_states"], b["hidden_states"]) < 5e-3
+        assert _rel(b["prompt_hidden_states"], a["prompt_hidden_states"]) < 5e-3 and _rel(b["hidden_states"], a["hidden_states"]) < 5e-3
+
+
 def test_packed_prefill_from_token_ids_through_the_c_abi(hip):
     """td_qwen2_prefill_packed with token ids instead of embeddings (the form a C caller uses), one and several prompts, logits of the last tokens: against
     td_qwen2_forward_slot per prompt -- bit-equal (same kernels per row: the packed form only changes which rows share a launch)."""

@@ -9,12 +9,6 @@
 #include "td_kernels.h"
 #include "../../include/thinkdiff_hip.h"
 
-#define TD_TRY(expr)          \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
-
 struct Slot {
   std::string name;
   bf16_t* ptr;

@@ -9,9 +9,14 @@
 //   Attn: q/k/v Linear with bias, M-RoPE (rotate_half, 3 position streams merged by mrope_section),
 //   causal GQA softmax(q k^T / sqrt(128)) v, o_proj without bias.
 //
-// Layout: one fused [q | k | v] projection per layer whose k|v columns are written STRAIGHT into the
-// layer's KV cache rows (dual-output GEMM epilogue), so prefill and decode share one code path:
-// `td_qwen2_forward(tokens at positions [pos0, pos0+n))` attends over cache rows [0, pos0+n).
+// Layout: one fused [q | k | v] projection per layer (dual-output GEMM epilogue: q to scratch, k | v to their own rows) and a KV
+// cache of n_slots sequences x slot_len rows per layer.  Two layer loops:
+//   prefill_pass -- many rows at once, in three forms that differ only in where a layer's k|v rows are written, what carries them
+//     to the cache and what the attention reads (PrefillForm): one sequence at positions [pos0, pos0 + n) written straight into its
+//     cache rows (td_qwen2_forward_slot), a right-padded batch (td_qwen2_prefill_batch_at), prompts back to back
+//     (td_qwen2_prefill_packed_slots);
+//   decode_step -- one new token for each of up to 256 sequences, with a launch list of its own (weight-stream or split-K Linears,
+//     rotary embedding and cache write inside the attention launch), captured into a graph per batch size and replayed.
 // Parameters are addressed by their Hugging Face names (model.layers.N.self_attn.q_proj.weight, ...).
 #include <algorithm>
 #include <cstdio>
@@ -90,12 +95,6 @@ struct IntPack { int v[3 * MAX_BATCH]; };      // (3 KB of kernel arguments: len
 __global__ void td_set_ints_kernel(int* dst, IntPack vals, int n) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = vals.v[threadIdx.x];
 }
-// dst_base[off[b] + c] = src[b, c]: the k|v rows of a decode step go to their sequences' cache rows
-__global__ void td_scatter_rows_kernel(const bf16_t* src, bf16_t* dst_base, const int* off, int W) {
-  const int b = blockIdx.y;
-  const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 8;
-  if (c < W) *(u32x4_t*)(dst_base + (size_t)off[b] + c) = *(const u32x4_t*)(src + (size_t)b * W + c);
-}
 
 // row b*L + t of src -> cache row (b * slot_len + t): the k|v rows of a batched prefill go to their sequences' slots
 __global__ void td_kv_rows_to_slots_kernel(const bf16_t* src, bf16_t* dst_base, int L, int slot_len, int W) {
@@ -150,11 +149,119 @@ __global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, 
   }
 }
 
-#define TDQ_TRY(expr)         \
-  do {                        \
-    int _rc = (expr);         \
-    if (_rc != 0) return _rc; \
-  } while (0)
+// The launch arguments of one Linear, y[M, N] = x[M, K] W[N, K]^T (+ bias) (+ y itself with `residual`: the h += ... of both sub-blocks).
+// Returned, not launched: the call sites with a second output or a K split decorate it first.
+TdGemmParams linear(const bf16_t* x, int ldx, const bf16_t* W, const bf16_t* bias, bf16_t* y, int ldy, int M, int N, int K, bool residual = false) {
+  TdGemmParams g;
+  g.A = x; g.lda = ldx; g.W = W; g.bias = bias; g.C = y; g.ldc = ldy; g.M = M; g.N = N; g.K = K;
+  if (residual) { g.res = y; g.ldr = ldy; }
+  return g;
+}
+
+// logits[M, vocab] = lm_head(rows[M, hidden]), rows = model.norm outputs
+int lm_head(td_qwen2* f, const bf16_t* rows, int M, void* logits, hipStream_t s) {
+  return td_gemm_launch(linear(rows, f->D, f->lm_w, nullptr, (bf16_t*)logits, f->cfg.vocab, M, f->cfg.vocab, f->D), s);
+}
+
+// two rows on one slot would write the same cache row: refused, not left to corrupt a sequence
+int check_distinct_slots(const char* fn, const char* unit, const int* slots, int B) {
+  int sorted[MAX_BATCH];
+  std::copy(slots, slots + B, sorted);
+  std::sort(sorted, sorted + B);
+  const int* dup = std::adjacent_find(sorted, sorted + B);
+  TD_CHECK_ARG(dup == sorted + B, "%s: cache slot %d is named by more than one %s", fn, *dup, unit);
+  return TD_OK;
+}
+
+// k|v rows of one layer: in its cache from element `off` on, or (off < 0) in the engine's kvtmp
+struct KvRows {
+  long long off;
+  bf16_t* of(const td_qwen2* f, const QLayer& l) const { return off < 0 ? f->kvtmp : l.kv + off; }
+};
+constexpr KvRows KV_TMP{-1};
+
+// What tells the three prefills apart (everything else of prefill_pass is common to them).
+struct PrefillForm {
+  int n = 0;                   // rows of the pass
+  KvRows kv_new = KV_TMP;      // where the q | k | v projection writes a layer's new k|v rows (RoPE rotates the k half there)
+  // what carries them to the cache behind RoPE: nothing (they are cache rows), or one of
+  const int* to_rows = nullptr;                // row r -> cache row to_rows[r] (device ints)
+  long long to_slots = -1; int slots_L = 0;    // row b * slots_L + t -> row t of the b-th slot from cache element to_slots on
+  TdAttnParams attn;           // the layer's attention, all but K / V, which are the k and the v half of `attn_kv`
+  KvRows attn_kv = KV_TMP;
+};
+
+// Runs form.n rows through the decoder: embed (or take inputs_embeds), M-RoPE table, every layer, model.norm -- left in f->xn and copied to
+// hidden_out if given.  The caller has checked its arguments; which rows feed lm_head is its business too.
+int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, const void* inputs_embeds, const int* position_ids, void* hidden_out, hipStream_t s) {
+  const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv, n = form.n;
+  const int QW = Hq * 128, KVW = 2 * Hkv * 128;
+
+  if (inputs_embeds) TD_CHECK_HIP(hipMemcpyAsync(f->h, inputs_embeds, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
+  else TD_TRY(td_embed_gather_launch(token_ids, f->embed_w, f->h, n, D, f->cfg.vocab, s));
+  // transformers casts the fp32 cos/sin tables to the model dtype before use
+  TD_TRY(td_mrope_table_launch(position_ids, n, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
+
+  TdNormParams np;
+  np.x = f->h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = n; np.D = D; np.rms = 1; np.eps = f->cfg.rms_eps;
+  TdQkRopeParams rq;   // q heads in the q buffer
+  rq.qkv = f->q; rq.ld = QW; rq.rows = n; rq.Hq = Hq; rq.Hk = 0; rq.q_col = 0; rq.k_col = 0;
+  rq.cos = f->cosT; rq.sin = f->sinT; rq.rotate_half = 2;
+  TdQkRopeParams rk = rq;  // k heads in the k|v rows just written
+  rk.ld = KVW; rk.Hq = Hkv;
+  TdAttnParams ap = form.attn;
+
+  for (const QLayer& l : f->layers) {
+    bf16_t* kv_new = form.kv_new.of(f, l);
+    np.w = l.ln1_w;
+    TD_TRY(td_norm_rows_launch(np, s));
+    {  // fused q | k | v projection: q -> scratch, k | v -> kv_new
+      TdGemmParams g = linear(f->xn, D, l.qkv_w, l.qkv_b, f->q, QW, n, QW + KVW, D);
+      g.C2 = kv_new; g.ldc2 = KVW; g.n_split = QW;
+      if (QW % 256 == 0) {
+        // the column split needs a tile width that divides 256: every config but the 288x192 one
+        g.cfg = n <= 32 ? -1 : (td_gemm_config_id(n, QW + KVW, D) == 1 ? 1 : 0);
+        TD_TRY(td_gemm_launch(g, s));
+      } else {
+        TdGemmParams a = g; a.C2 = nullptr; a.N = QW;
+        TD_TRY(td_gemm_launch(a, s));
+        TdGemmParams b = a; b.W = l.qkv_w + (size_t)QW * D; b.bias = l.qkv_b + QW; b.N = KVW; b.C = kv_new; b.ldc = KVW;
+        TD_TRY(td_gemm_launch(b, s));
+      }
+    }
+    TD_TRY(td_qk_norm_rope_launch(rq, s));
+    rk.qkv = kv_new; TD_TRY(td_qk_norm_rope_launch(rk, s));
+    if (form.to_rows)
+      hipLaunchKernelGGL(td_kv_rows_to_rows_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv, form.to_rows, KVW);
+    else if (form.to_slots >= 0)
+      hipLaunchKernelGGL(td_kv_rows_to_slots_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv + form.to_slots, form.slots_L, f->slot_len, KVW);
+    ap.K = form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
+    TD_TRY(td_attn_launch(ap, s));
+    // h += o_proj(attn)
+    TD_TRY(td_gemm_launch(linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), s));
+    np.w = l.ln2_w;
+    TD_TRY(td_norm_rows_launch(np, s));
+    // gate | up, SwiGLU, down (+ residual)
+    TD_TRY(td_gemm_launch(linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, n, 2 * I, D), s));
+    TD_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
+    TD_TRY(td_gemm_launch(linear(f->act, I, l.down_w, nullptr, f->h, D, n, D, I, true), s));
+  }
+  // model.norm -> captured embedding
+  np.w = f->norm_w;
+  TD_TRY(td_norm_rows_launch(np, s));
+  if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
+  return TD_OK;
+}
+
+// The part of a layer's attention descriptor every prefill form shares: q and the output in the engine's buffers, causal, 128-wide heads.
+TdAttnParams prefill_attn(const td_qwen2* f, int batch, int Sq, int Skv, int causal_offset) {
+  const int QW = f->Hq * 128;
+  TdAttnParams ap;
+  ap.Q = f->q; ap.ldq = QW; ap.ldkv = 2 * f->Hkv * 128; ap.O = f->attn; ap.ldo = QW;
+  ap.batch = batch; ap.Sq = Sq; ap.Skv = Skv; ap.Hq = f->Hq; ap.Hkv = f->Hkv; ap.scale = 0.08838834764831845f;
+  ap.causal = 1; ap.causal_offset = causal_offset;
+  return ap;
+}
 
 }  // namespace
 
@@ -291,14 +398,13 @@ int td_qwen2_load_param(td_qwen2* f, const char* name, const void* src, int64_t 
 
 int td_qwen2_init_random(td_qwen2* f, uint64_t seed, float std, void* stream) {
   TD_CHECK_ARG(f, "td_qwen2_init_random: null handle");
-  TDQ_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
+  TD_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
   for (const QSlot& s : f->slots)
     if (s.name.find("layernorm.weight") != std::string::npos || s.name == "model.norm.weight")
-      TDQ_TRY(td_fill_normal_bf16(s.ptr, s.count, seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(s.ptr - f->arena + 1)), 0.05f, 1.0f, stream));
+      TD_TRY(td_fill_normal_bf16(s.ptr, s.count, seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(s.ptr - f->arena + 1)), 0.05f, 1.0f, stream));
   return TD_OK;
 }
 
-// Runs n new tokens at cache positions [pos0, pos0 + n) through the decoder.
 // out[i,:] = embed_tokens[ids[i],:] -- the host builds `inputs_embeds` from this, replacing the image-placeholder
 // rows with the vision tower's merged tokens ([ext] Qwen2VLModel.forward masked_scatter).
 int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, void* stream) {
@@ -306,6 +412,7 @@ int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, v
   return td_embed_gather_launch(token_ids, f->embed_w, (bf16_t*)out, n, f->D, f->cfg.vocab, (hipStream_t)stream);
 }
 
+// Runs n new tokens at cache positions [pos0, pos0 + n) of sequence `slot` through the decoder.
 //   token_ids  : device int32 [n], or NULL when inputs_embeds is given
 //   inputs_embeds : device bf16 [n, hidden] (token embeddings with the image-token rows replaced by the
 //                vision tower's output), or NULL
@@ -319,81 +426,18 @@ int td_qwen2_forward_slot(td_qwen2* f, int slot, const int* token_ids, const voi
   TD_CHECK_ARG(slot >= 0 && slot < f->n_slots, "td_qwen2_forward: slot %d outside the %d configured sequences", slot, f->n_slots);
   TD_CHECK_ARG(n > 0 && pos0 >= 0 && pos0 + n <= f->slot_len, "td_qwen2_forward: positions [%d, %d) exceed the cache capacity %d", pos0, pos0 + n, f->slot_len);
   hipStream_t s = (hipStream_t)stream;
-  const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv;
-  const int QW = Hq * 128, KVW = 2 * Hkv * 128;
-
-  if (inputs_embeds) TD_CHECK_HIP(hipMemcpyAsync(f->h, inputs_embeds, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
-  else TDQ_TRY(td_embed_gather_launch(token_ids, f->embed_w, f->h, n, D, f->cfg.vocab, s));
-  // transformers casts the fp32 cos/sin tables to the model dtype before use
-  TDQ_TRY(td_mrope_table_launch(position_ids, n, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
-
-  TdNormParams np;
-  np.x = f->h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = n; np.D = D; np.rms = 1; np.eps = f->cfg.rms_eps;
-  TdQkRopeParams rq;   // q heads in the q buffer
-  rq.qkv = f->q; rq.ld = QW; rq.rows = n; rq.Hq = Hq; rq.Hk = 0; rq.q_col = 0; rq.k_col = 0;
-  rq.cos = f->cosT; rq.sin = f->sinT; rq.rotate_half = 2;
-  TdQkRopeParams rk = rq;  // k heads in the cache rows just written
-  rk.ld = KVW; rk.Hq = Hkv;
-
-  for (int i = 0; i < f->cfg.num_layers; ++i) {
-    const QLayer& l = f->layers[i];
-    bf16_t* kv_seq = l.kv + (size_t)slot * f->slot_len * KVW;   // this sequence's cache rows
-    bf16_t* kv_new = kv_seq + (size_t)pos0 * KVW;
-    np.w = l.ln1_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {  // fused q | k | v projection: q -> scratch, k | v -> this layer's cache rows
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.qkv_w; g.bias = l.qkv_b; g.M = n; g.N = QW + KVW; g.K = D;
-      g.C = f->q; g.ldc = QW; g.C2 = kv_new; g.ldc2 = KVW; g.n_split = QW;
-      if (QW % 256 == 0) {
-        // the column split needs a tile width that divides 256: every config but the 288x192 one
-        g.cfg = n <= 32 ? -1 : (td_gemm_config_id(n, QW + KVW, D) == 1 ? 1 : 0);
-        TDQ_TRY(td_gemm_launch(g, s));
-      } else {
-        TdGemmParams a = g; a.C2 = nullptr; a.N = QW;
-        TDQ_TRY(td_gemm_launch(a, s));
-        TdGemmParams b = g; b.C2 = nullptr; b.W = l.qkv_w + (size_t)QW * D; b.bias = l.qkv_b + QW; b.N = KVW; b.C = kv_new; b.ldc = KVW;
-        TDQ_TRY(td_gemm_launch(b, s));
-      }
-    }
-    rq.qkv = f->q; TDQ_TRY(td_qk_norm_rope_launch(rq, s));
-    rk.qkv = kv_new; TDQ_TRY(td_qk_norm_rope_launch(rk, s));
-    TdAttnParams ap;
-    ap.Q = f->q; ap.ldq = QW; ap.K = kv_seq; ap.V = kv_seq + Hkv * 128; ap.ldkv = KVW; ap.O = f->attn; ap.ldo = QW;
-    ap.batch = 1; ap.Sq = n; ap.Skv = pos0 + n; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f;
-    ap.causal = 1; ap.causal_offset = pos0;
-    TDQ_TRY(td_attn_launch(ap, s));
-    {  // h += o_proj(attn)
-      TdGemmParams g;
-      g.A = f->attn; g.lda = QW; g.W = l.o_w; g.C = f->h; g.ldc = D; g.res = f->h; g.ldr = D; g.M = n; g.N = D; g.K = QW;
-      TDQ_TRY(td_gemm_launch(g, s));
-    }
-    np.w = l.ln2_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {  // gate | up, SwiGLU, down (+ residual)
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.gu_w; g.C = f->gu; g.ldc = 2 * I; g.M = n; g.N = 2 * I; g.K = D;
-      TDQ_TRY(td_gemm_launch(g, s));
-      TDQ_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
-      TdGemmParams d;
-      d.A = f->act; d.lda = I; d.W = l.down_w; d.C = f->h; d.ldc = D; d.res = f->h; d.ldr = D; d.M = n; d.N = D; d.K = I;
-      TDQ_TRY(td_gemm_launch(d, s));
-    }
-  }
-  // model.norm -> captured embedding
-  np.w = f->norm_w; np.y = f->xn;
-  TDQ_TRY(td_norm_rows_launch(np, s));
-  if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
-  if (logits_last) {
-    TdGemmParams g;
-    g.A = f->xn + (size_t)(n - 1) * D; g.lda = D; g.W = f->lm_w; g.C = (bf16_t*)logits_last; g.ldc = f->cfg.vocab;
-    g.M = 1; g.N = f->cfg.vocab; g.K = D;
-    TDQ_TRY(td_gemm_launch(g, s));
-  }
+  const long long KVW = 2 * f->Hkv * 128, seq = (long long)slot * f->slot_len * KVW;   // this sequence's cache rows
+  PrefillForm form;
+  form.n = n;
+  form.kv_new = KvRows{seq + pos0 * KVW};      // k | v -> straight into the layer's cache rows
+  form.attn = prefill_attn(f, 1, n, pos0 + n, pos0);
+  form.attn_kv = KvRows{seq};
+  TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
+  if (logits_last) TD_TRY(lm_head(f, f->xn + (size_t)(n - 1) * f->D, 1, logits_last, s));
   return TD_OK;
 }
 
-// ---- batched KV-cached decode (the precompute job: many short sequences against one pass over the weights) --------------
+// ... of the first (or only) sequence
 int td_qwen2_forward(td_qwen2* f, const int* token_ids, const void* inputs_embeds, const int* position_ids, int n,
                      int pos0, void* hidden_out, void* logits_last, void* stream) {
   return td_qwen2_forward_slot(f, 0, token_ids, inputs_embeds, position_ids, n, pos0, hidden_out, logits_last, stream);
@@ -433,6 +477,7 @@ int td_qwen2_move_slot(td_qwen2* f, int src, int dst, int len, void* stream) {
 
 }  // extern "C"
 
+// ---- batched KV-cached decode (the precompute job: many short sequences against one pass over the weights) --------------
 namespace {
 // The launches of one decode step for the sequences in slots 0 .. B-1: ids from tok_buf / pos_buf, lengths and cache rows from ibuf, the final
 // hidden states left in xn and the logits in logits_buf.  Captured into a graph by td_qwen2_decode_batch (nothing here may depend on a host value
@@ -450,8 +495,8 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
   const int stream_batch = env_stream_batch > 0 ? (env_stream_batch < 16 ? 16 : env_stream_batch) : (D >= 3072 ? 32 : STREAM_BATCH);
   const bool wide = B > stream_batch;
 
-  TDQ_TRY(td_embed_gather_launch(f->tok_buf, f->embed_w, f->h, B, D, f->cfg.vocab, s));
-  TDQ_TRY(td_mrope_table_launch(f->pos_buf, B, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
+  TD_TRY(td_embed_gather_launch(f->tok_buf, f->embed_w, f->h, B, D, f->cfg.vocab, s));
+  TD_TRY(td_mrope_table_launch(f->pos_buf, B, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
   TdNormParams np;
   np.x = f->h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = B; np.D = D; np.rms = 1; np.eps = f->cfg.rms_eps;
   for (int i = 0; i < f->cfg.num_layers; ++i) {
@@ -459,70 +504,59 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     // (wide steps: the reduction launch of the Linear in front normalises the rows it finishes -- TdGemmParams::sk_norm_w -- so only layer 0 has a norm launch)
     if (!wide || i == 0) {
       np.w = l.ln1_w;
-      TDQ_TRY(td_norm_rows_launch(np, s));
+      TD_TRY(td_norm_rows_launch(np, s));
     }
     {
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.qkv_w; g.bias = l.qkv_b; g.M = B; g.N = QW + KVW; g.K = D;
-      g.C = f->q; g.ldc = QW; g.C2 = f->kvtmp; g.ldc2 = KVW; g.n_split = QW;
+      TdGemmParams g = linear(f->xn, D, l.qkv_w, l.qkv_b, f->q, QW, B, QW + KVW, D);
+      g.C2 = f->kvtmp; g.ldc2 = KVW; g.n_split = QW;
       if (wide) { g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES; }      // (tile width and parts by the wide planner: n_split = Hq 128 fits its 64- / 128-column tiles)
-      TDQ_TRY(td_gemm_launch(g, s));
+      TD_TRY(td_gemm_launch(g, s));
     }
     // rotary embedding of the new q / k rows and the cache write ride inside the attention launch (TdAttnParams::dec_kv_new);
-    // td_qwen2_set_fused_rope(f, 0) / TD_QWEN2_NO_FUSED_ROPE: the separate launch (A/B and the bit-identity test)
-    static const bool env_unfused = getenv("TD_QWEN2_NO_FUSED_ROPE") != nullptr;
-    const bool fused_rope = f->fused_rope && !env_unfused;
-    if (!fused_rope) hipLaunchKernelGGL(td_decode_rope_scatter_kernel, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, l.kv, row_off, f->cosT, f->sinT, Hq, Hkv);
+    // td_qwen2_set_fused_rope(f, 0): the separate launch (A/B and the bit-identity test)
+    if (!f->fused_rope) hipLaunchKernelGGL(td_decode_rope_scatter_kernel, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, l.kv, row_off, f->cosT, f->sinT, Hq, Hkv);
     TdAttnParams ap;
-    if (fused_rope) { ap.dec_kv_new = f->kvtmp; ap.dec_cos = f->cosT; ap.dec_sin = f->sinT; ap.dec_row_off = row_off; }
+    if (f->fused_rope) { ap.dec_kv_new = f->kvtmp; ap.dec_cos = f->cosT; ap.dec_sin = f->sinT; ap.dec_row_off = row_off; }
     ap.Q = f->q; ap.ldq = QW; ap.q_bstride = QW; ap.K = l.kv; ap.V = l.kv + Hkv * 128; ap.ldkv = KVW;
     ap.kv_bstride = (long long)f->slot_len * KVW; ap.O = f->attn; ap.ldo = QW; ap.o_bstride = QW;
     ap.batch = B; ap.Sq = 1; ap.Skv = max_len; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f;
     ap.causal = 1; ap.causal_offset = max_len - 1; ap.kv_lens = kv_lens; ap.dec_slots = slot_ids;
-    TDQ_TRY(td_attn_launch(ap, s));
+    TD_TRY(td_attn_launch(ap, s));
     {
-      TdGemmParams g;
-      g.A = f->attn; g.lda = QW; g.W = l.o_w; g.C = f->h; g.ldc = D; g.res = f->h; g.ldr = D; g.M = B; g.N = D; g.K = QW;
+      TdGemmParams g = linear(f->attn, QW, l.o_w, nullptr, f->h, D, B, D, QW, true);
       if (wide) {
         g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
         g.sk_norm_w = l.ln2_w; g.sk_norm_out = f->xn; g.sk_norm_ld = D; g.sk_norm_eps = f->cfg.rms_eps;
       }
-      TDQ_TRY(td_gemm_launch(g, s));
+      TD_TRY(td_gemm_launch(g, s));
     }
     if (!wide) {
       np.w = l.ln2_w;
-      TDQ_TRY(td_norm_rows_launch(np, s));
+      TD_TRY(td_norm_rows_launch(np, s));
     }
-    {
-      TdGemmParams g;
-      if (!wide) {
-        g.A = f->xn; g.lda = D; g.W = l.gu_w; g.C = f->act; g.ldc = I; g.M = B; g.N = I; g.K = D; g.glu_I = I;   // gate | up, SiLU and product in one pass
-        TDQ_TRY(td_gemm_launch(g, s));
-      } else {      // the prefill's form: gate | up as one Linear, SiLU and product in a pass of their own (the same rounding points)
-        g.A = f->xn; g.lda = D; g.W = l.gu_w; g.C = f->gu; g.ldc = 2 * I; g.M = B; g.N = 2 * I; g.K = D;
-        g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
-        TDQ_TRY(td_gemm_launch(g, s));
-        TDQ_TRY(td_silu_mul_launch(f->gu, f->act, B, I, s));
-      }
-      TdGemmParams d;
-      d.A = f->act; d.lda = I; d.W = l.down_w; d.C = f->h; d.ldc = D; d.res = f->h; d.ldr = D; d.M = B; d.N = D; d.K = I;
-      if (wide) {
-        d.split_k = -1; d.sk_ws = f->sk_ws; d.sk_ws_bytes = SK_WS_BYTES;
-        d.sk_norm_w = i + 1 < f->cfg.num_layers ? f->layers[i + 1].ln1_w : f->norm_w;      // the next layer's input norm, or model.norm
-        d.sk_norm_out = f->xn; d.sk_norm_ld = D; d.sk_norm_eps = f->cfg.rms_eps;
-      }
-      TDQ_TRY(td_gemm_launch(d, s));
+    if (!wide) {
+      TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->act, I, B, I, D);
+      g.glu_I = I;   // gate | up, SiLU and product in one pass
+      TD_TRY(td_gemm_launch(g, s));
+    } else {      // the prefill's form: gate | up as one Linear, SiLU and product in a pass of their own (the same rounding points)
+      TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, B, 2 * I, D);
+      g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
+      TD_TRY(td_gemm_launch(g, s));
+      TD_TRY(td_silu_mul_launch(f->gu, f->act, B, I, s));
     }
+    TdGemmParams d = linear(f->act, I, l.down_w, nullptr, f->h, D, B, D, I, true);
+    if (wide) {
+      d.split_k = -1; d.sk_ws = f->sk_ws; d.sk_ws_bytes = SK_WS_BYTES;
+      d.sk_norm_w = i + 1 < f->cfg.num_layers ? f->layers[i + 1].ln1_w : f->norm_w;      // the next layer's input norm, or model.norm
+      d.sk_norm_out = f->xn; d.sk_norm_ld = D; d.sk_norm_eps = f->cfg.rms_eps;
+    }
+    TD_TRY(td_gemm_launch(d, s));
   }
   if (!wide) {
     np.w = f->norm_w; np.y = f->xn;
-    TDQ_TRY(td_norm_rows_launch(np, s));
+    TD_TRY(td_norm_rows_launch(np, s));
   }
-  if (want_logits) {
-    TdGemmParams g;
-    g.A = f->xn; g.lda = D; g.W = f->lm_w; g.C = f->logits_buf; g.ldc = f->cfg.vocab; g.M = B; g.N = f->cfg.vocab; g.K = D;
-    TDQ_TRY(td_gemm_launch(g, s));
-  }
+  if (want_logits) TD_TRY(lm_head(f, f->xn, B, f->logits_buf, s));
   TD_CHECK_LAUNCH();
   return TD_OK;
 }
@@ -548,12 +582,7 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
   const int D = f->D;
   IntPack ip;
   int max_len = 0;
-  if (slots) {      // two rows on one slot would write the same cache row: refused, not left to corrupt a sequence
-    int sorted[MAX_BATCH];
-    std::copy(slots, slots + B, sorted);
-    std::sort(sorted, sorted + B);
-    TD_CHECK_ARG(std::adjacent_find(sorted, sorted + B) == sorted + B, "td_qwen2_decode_batch: cache slot %d is named by more than one row", *std::adjacent_find(sorted, sorted + B));
-  }
+  if (slots) TD_TRY(check_distinct_slots("td_qwen2_decode_batch", "row", slots, B));
   for (int b = 0; b < B; ++b) {
     const int slot = slots ? slots[b] : b;
     TD_CHECK_ARG(slot >= 0 && slot < f->n_slots, "td_qwen2_decode_batch: sequence %d names cache slot %d of %d", b, slot, f->n_slots);
@@ -575,7 +604,7 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
   if (it != f->step_graphs.end()) {
     TD_CHECK_HIP(hipGraphLaunch(it->second, s));
   } else if (no_graph || !f->graphs_ok || f->step_calls[key]++ == 0) {
-    TDQ_TRY(decode_step(f, B, max_len, want_logits, s));
+    TD_TRY(decode_step(f, B, max_len, want_logits, s));
   } else {
     // capture on the engine's own stream (the caller's may be the legacy default stream, which cannot capture), after everything the caller
     // queued so far: nothing runs during a capture, but the eager fallback below must see the ids copied above
@@ -596,7 +625,7 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
     } else {
       (void)hipGetLastError();
       f->graphs_ok = false;      // this runtime cannot capture the step: stay on the eager path for good
-      TDQ_TRY(decode_step(f, B, max_len, want_logits, s));
+      TD_TRY(decode_step(f, B, max_len, want_logits, s));
     }
   }
   if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)B * D * 2, hipMemcpyDeviceToDevice, s));
@@ -621,76 +650,23 @@ int td_qwen2_prefill_batch_at(td_qwen2* f, int slot0, int B, int L, const int* t
                "td_qwen2_prefill_batch: slots [%d, %d) x L=%d exceed the handle (slots %d x %d tokens, workspace %d rows)", slot0, slot0 + B, L, f->n_slots, f->slot_len, f->ws_rows);
   for (int b = 0; b < B; ++b) TD_CHECK_ARG(lens[b] >= 1 && lens[b] <= L, "td_qwen2_prefill_batch: sequence %d has %d of %d tokens", b, lens[b], L);
   hipStream_t s = (hipStream_t)stream;
-  const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv;
-  const int QW = Hq * 128, KVW = 2 * Hkv * 128, n = B * L;
-  if (inputs_embeds) TD_CHECK_HIP(hipMemcpyAsync(f->h, inputs_embeds, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
-  else TDQ_TRY(td_embed_gather_launch(token_ids, f->embed_w, f->h, n, D, f->cfg.vocab, s));
-  TDQ_TRY(td_mrope_table_launch(position_ids, n, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
-  TdNormParams np;
-  np.x = f->h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = n; np.D = D; np.rms = 1; np.eps = f->cfg.rms_eps;
-  TdQkRopeParams rq;
-  rq.qkv = f->q; rq.ld = QW; rq.rows = n; rq.Hq = Hq; rq.Hk = 0; rq.q_col = 0; rq.k_col = 0;
-  rq.cos = f->cosT; rq.sin = f->sinT; rq.rotate_half = 2;
-  TdQkRopeParams rk = rq;
-  rk.qkv = f->kvtmp; rk.ld = KVW; rk.Hq = Hkv;
-  for (int i = 0; i < f->cfg.num_layers; ++i) {
-    const QLayer& l = f->layers[i];
-    np.w = l.ln1_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.qkv_w; g.bias = l.qkv_b; g.M = n; g.N = QW + KVW; g.K = D;
-      g.C = f->q; g.ldc = QW; g.C2 = f->kvtmp; g.ldc2 = KVW; g.n_split = QW;
-      if (QW % 256 == 0) {
-        g.cfg = n <= 32 ? -1 : (td_gemm_config_id(n, QW + KVW, D) == 1 ? 1 : 0);
-        TDQ_TRY(td_gemm_launch(g, s));
-      } else {
-        TdGemmParams a = g; a.C2 = nullptr; a.N = QW;
-        TDQ_TRY(td_gemm_launch(a, s));
-        TdGemmParams b2 = g; b2.C2 = nullptr; b2.W = l.qkv_w + (size_t)QW * D; b2.bias = l.qkv_b + QW; b2.N = KVW; b2.C = f->kvtmp; b2.ldc = KVW;
-        TDQ_TRY(td_gemm_launch(b2, s));
-      }
-    }
-    TDQ_TRY(td_qk_norm_rope_launch(rq, s));
-    TDQ_TRY(td_qk_norm_rope_launch(rk, s));
-    bf16_t* kv0 = l.kv + (size_t)slot0 * f->slot_len * KVW;      // first slot of this call
-    hipLaunchKernelGGL(td_kv_rows_to_slots_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, f->kvtmp, kv0, L, f->slot_len, KVW);
-    TdAttnParams ap;
-    ap.Q = f->q; ap.ldq = QW; ap.q_bstride = (long long)L * QW; ap.K = kv0; ap.V = kv0 + Hkv * 128; ap.ldkv = KVW;
-    ap.kv_bstride = (long long)f->slot_len * KVW; ap.O = f->attn; ap.ldo = QW; ap.o_bstride = (long long)L * QW;
-    ap.batch = B; ap.Sq = L; ap.Skv = L; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f; ap.causal = 1; ap.causal_offset = 0;
-    TDQ_TRY(td_attn_launch(ap, s));
-    {
-      TdGemmParams g;
-      g.A = f->attn; g.lda = QW; g.W = l.o_w; g.C = f->h; g.ldc = D; g.res = f->h; g.ldr = D; g.M = n; g.N = D; g.K = QW;
-      TDQ_TRY(td_gemm_launch(g, s));
-    }
-    np.w = l.ln2_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.gu_w; g.C = f->gu; g.ldc = 2 * I; g.M = n; g.N = 2 * I; g.K = D;
-      TDQ_TRY(td_gemm_launch(g, s));
-      TDQ_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
-      TdGemmParams d;
-      d.A = f->act; d.lda = I; d.W = l.down_w; d.C = f->h; d.ldc = D; d.res = f->h; d.ldr = D; d.M = n; d.N = D; d.K = I;
-      TDQ_TRY(td_gemm_launch(d, s));
-    }
-  }
-  np.w = f->norm_w; np.y = f->xn;
-  TDQ_TRY(td_norm_rows_launch(np, s));
-  if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
+  const int D = f->D, QW = f->Hq * 128;
+  const long long KVW = 2 * f->Hkv * 128, kv0 = (long long)slot0 * f->slot_len * KVW;      // first slot of this call
+  PrefillForm form;
+  form.n = B * L;
+  form.to_slots = kv0; form.slots_L = L;
+  form.attn = prefill_attn(f, B, L, L, 0);
+  form.attn.q_bstride = form.attn.o_bstride = (long long)L * QW; form.attn.kv_bstride = f->slot_len * KVW;
+  form.attn_kv = KvRows{kv0};
+  TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     for (int b = 0; b < B; ++b)
       TD_CHECK_HIP(hipMemcpyAsync(f->lastrows + (size_t)b * D, f->xn + ((size_t)b * L + lens[b] - 1) * D, (size_t)D * 2, hipMemcpyDeviceToDevice, s));
-    TdGemmParams g;
-    g.A = f->lastrows; g.lda = D; g.W = f->lm_w; g.C = (bf16_t*)logits_last; g.ldc = f->cfg.vocab; g.M = B; g.N = f->cfg.vocab; g.K = D;
-    TDQ_TRY(td_gemm_launch(g, s));
+    TD_TRY(lm_head(f, f->lastrows, B, logits_last, s));
   }
   TD_CHECK_LAUNCH();
   return TD_OK;
 }
-
 
 // Packed prefill: the B prompts lie back to back (row offsets = the running sum of lens; no padding rows), sequence b goes to cache slot slot0 + b.
 // What vLLM's scheduler does with the reference's request batches (max_num_batched_tokens rows per pass); against the padded form it saves the
@@ -710,12 +686,7 @@ int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const in
   TD_CHECK_ARG(f && slots && position_ids && lens && (token_ids || inputs_embeds), "td_qwen2_prefill_packed: null argument");
   TD_CHECK_ARG(B >= 1 && B <= MAX_BATCH, "td_qwen2_prefill_packed: %d sequences (1 .. %d)", B, MAX_BATCH);
   for (int b = 0; b < B; ++b) TD_CHECK_ARG(slots[b] >= 0 && slots[b] < f->n_slots, "td_qwen2_prefill_packed: sequence %d names cache slot %d of %d", b, slots[b], f->n_slots);
-  {
-    int sorted[MAX_BATCH];
-    std::copy(slots, slots + B, sorted);
-    std::sort(sorted, sorted + B);
-    TD_CHECK_ARG(std::adjacent_find(sorted, sorted + B) == sorted + B, "td_qwen2_prefill_packed: cache slot %d is named by more than one sequence", *std::adjacent_find(sorted, sorted + B));
-  }
+  TD_TRY(check_distinct_slots("td_qwen2_prefill_packed", "sequence", slots, B));
   long long total = 0;
   int L = 0;
   for (int b = 0; b < B; ++b) {
@@ -725,8 +696,7 @@ int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const in
   }
   TD_CHECK_ARG(total <= f->ws_rows, "td_qwen2_prefill_packed: %lld packed rows exceed the %d workspace rows", total, f->ws_rows);
   hipStream_t s = (hipStream_t)stream;
-  const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv;
-  const int QW = Hq * 128, KVW = 2 * Hkv * 128, n = (int)total;
+  const int D = f->D, n = (int)total;
   // segment starts (device, for the attention and the last-row gather) and the cache row of every packed row
   IntPack ip;
   int* seg_starts = f->ibuf + 3 * MAX_BATCH;      // [B + 1] behind the decode step's lengths, rows and slots
@@ -742,67 +712,15 @@ int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const in
   hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, seg_starts, ip, B + 1);
   TD_CHECK_LAUNCH();
   TD_CHECK_HIP(hipMemcpyAsync(f->row_map, f->row_map_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
-  if (inputs_embeds) TD_CHECK_HIP(hipMemcpyAsync(f->h, inputs_embeds, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
-  else TDQ_TRY(td_embed_gather_launch(token_ids, f->embed_w, f->h, n, D, f->cfg.vocab, s));
-  TDQ_TRY(td_mrope_table_launch(position_ids, n, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
-  TdNormParams np;
-  np.x = f->h; np.ldx = D; np.y = f->xn; np.ldy = D; np.rows = n; np.D = D; np.rms = 1; np.eps = f->cfg.rms_eps;
-  TdQkRopeParams rq;
-  rq.qkv = f->q; rq.ld = QW; rq.rows = n; rq.Hq = Hq; rq.Hk = 0; rq.q_col = 0; rq.k_col = 0;
-  rq.cos = f->cosT; rq.sin = f->sinT; rq.rotate_half = 2;
-  TdQkRopeParams rk = rq;
-  rk.qkv = f->kvtmp; rk.ld = KVW; rk.Hq = Hkv;
-  for (int i = 0; i < f->cfg.num_layers; ++i) {
-    const QLayer& l = f->layers[i];
-    np.w = l.ln1_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.qkv_w; g.bias = l.qkv_b; g.M = n; g.N = QW + KVW; g.K = D;
-      g.C = f->q; g.ldc = QW; g.C2 = f->kvtmp; g.ldc2 = KVW; g.n_split = QW;
-      if (QW % 256 == 0) {
-        g.cfg = n <= 32 ? -1 : (td_gemm_config_id(n, QW + KVW, D) == 1 ? 1 : 0);
-        TDQ_TRY(td_gemm_launch(g, s));
-      } else {
-        TdGemmParams a = g; a.C2 = nullptr; a.N = QW;
-        TDQ_TRY(td_gemm_launch(a, s));
-        TdGemmParams b2 = g; b2.C2 = nullptr; b2.W = l.qkv_w + (size_t)QW * D; b2.bias = l.qkv_b + QW; b2.N = KVW; b2.C = f->kvtmp; b2.ldc = KVW;
-        TDQ_TRY(td_gemm_launch(b2, s));
-      }
-    }
-    TDQ_TRY(td_qk_norm_rope_launch(rq, s));
-    TDQ_TRY(td_qk_norm_rope_launch(rk, s));
-    hipLaunchKernelGGL(td_kv_rows_to_rows_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, f->kvtmp, l.kv, f->row_map, KVW);
-    TdAttnParams ap;      // causal attention inside each packed prompt, straight from the projection rows (a prefill starts at position 0)
-    ap.Q = f->q; ap.ldq = QW; ap.K = f->kvtmp; ap.V = f->kvtmp + Hkv * 128; ap.ldkv = KVW; ap.O = f->attn; ap.ldo = QW;
-    ap.batch = B; ap.Sq = L; ap.Skv = L; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f; ap.causal = 1; ap.causal_offset = 0;
-    ap.seg_starts = seg_starts;
-    TDQ_TRY(td_attn_launch(ap, s));
-    {
-      TdGemmParams g;
-      g.A = f->attn; g.lda = QW; g.W = l.o_w; g.C = f->h; g.ldc = D; g.res = f->h; g.ldr = D; g.M = n; g.N = D; g.K = QW;
-      TDQ_TRY(td_gemm_launch(g, s));
-    }
-    np.w = l.ln2_w;
-    TDQ_TRY(td_norm_rows_launch(np, s));
-    {
-      TdGemmParams g;
-      g.A = f->xn; g.lda = D; g.W = l.gu_w; g.C = f->gu; g.ldc = 2 * I; g.M = n; g.N = 2 * I; g.K = D;
-      TDQ_TRY(td_gemm_launch(g, s));
-      TDQ_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
-      TdGemmParams d;
-      d.A = f->act; d.lda = I; d.W = l.down_w; d.C = f->h; d.ldc = D; d.res = f->h; d.ldr = D; d.M = n; d.N = D; d.K = I;
-      TDQ_TRY(td_gemm_launch(d, s));
-    }
-  }
-  np.w = f->norm_w; np.y = f->xn;
-  TDQ_TRY(td_norm_rows_launch(np, s));
-  if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)n * D * 2, hipMemcpyDeviceToDevice, s));
+  PrefillForm form;
+  form.n = n;
+  form.to_rows = f->row_map;
+  form.attn = prefill_attn(f, B, L, L, 0);      // causal attention inside each packed prompt, straight from the projection rows (a prefill starts at position 0)
+  form.attn.seg_starts = seg_starts;
+  TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     hipLaunchKernelGGL(td_gather_last_rows_kernel, dim3((D / 8 + 255) / 256, B), dim3(256), 0, s, f->xn, f->lastrows, seg_starts, D);
-    TdGemmParams g;
-    g.A = f->lastrows; g.lda = D; g.W = f->lm_w; g.C = (bf16_t*)logits_last; g.ldc = f->cfg.vocab; g.M = B; g.N = f->cfg.vocab; g.K = D;
-    TDQ_TRY(td_gemm_launch(g, s));
+    TD_TRY(lm_head(f, f->lastrows, B, logits_last, s));
   }
   TD_CHECK_LAUNCH();
   return TD_OK;

@@ -86,6 +86,12 @@ void td_set_error(const char* fmt, ...);
     }                                                                             \
   } while (0)
 #define TD_CHECK_LAUNCH() TD_CHECK_HIP(hipGetLastError())
+// pass on the status of a call that has already recorded its error
+#define TD_TRY(expr)          \
+  do {                        \
+    int _rc = (expr);         \
+    if (_rc != 0) return _rc; \
+  } while (0)
 
 // ---- launch geometry -------------------------------------------------------
 // A dispatch packet carries the grid as 32-bit WORK-ITEM counts: blocks x threads-per-block must stay below 2^32, and a larger
