@@ -198,6 +198,22 @@ int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ld
 int td_block_cache_head_bf16(const void* h1, int64_t ld1, const void* h0, int64_t ld0, const void* r_prev, int64_t ldp, void* r, int64_t ldr, int rows, int D,
                              double* sums, void* ws, void* stream);
 int td_block_cache_tail_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int rows, int D, void* stream);
+/* FLUX.1 Redux prompt composition (td_abi_version() >= 8; [ext] diffusers FluxPriorReduxPipeline.__call__, restated from the published source, parity
+ * unpinned): B [text | image] prompt streams, each under its own scale, summed into ONE stream of T + S rows -- the pipeline's
+ *   prompt_embeds = cat([text, image_embeds], dim=1);  prompt_embeds *= scale[:, None, None];  prompt_embeds = sum(prompt_embeds, dim=0)
+ * on bf16 tensors, without the concatenated intermediate.  out [T + S, ldo] bf16:
+ *   out[r, :D]     = bf16( sum_{b = 0 .. B-1} float( bf16( s_b * text[b, r, :] ) ) )          r < T
+ *   out[T + r, :D] = bf16( sum_{b = 0 .. B-1} float( bf16( s_b * image[b, r, :] ) ) )         r < S
+ * Rounding: s_b = scales[b] rounded to bf16 (on the host, by this entry); each product rounded to bf16; the sum in fp32 in index order b = 0, 1, ..,
+ * starting from the b = 0 term, rounded once (B = 1 with scale 1 returns the inputs' bits).  Source rows are contiguous (D elements apart), batch
+ * entries text_bstride / image_bstride elements apart.  text NULL = zero rows: +0.0 is written, nothing read.  text_bstride 0 = one text stream shared
+ * by every b, still added B times, each under its scale (one string prompt with several images).  Columns D .. ldo-1 of out are not written.  T == 0 or
+ * S == 0 is allowed, not both (the pooled vector: T = 1, S = 0, D = 768).  scales: B floats in HOST memory, read before the launch; they travel in
+ * the kernel's argument segment.  out overlaps neither input.
+ * TD_ERR_INVALID, nothing launched: D % 8 != 0; B < 1 or B > 16; T < 0, S < 0, T + S == 0; ldo < D or ldo % 8 != 0; image NULL with S > 0; scales NULL;
+ * out NULL; a batch stride negative or not a multiple of 8; a pointer not 16-byte aligned; (T + S) x D > INT32_MAX elements (32-bit index). */
+int td_redux_compose_bf16(const void* text, int64_t text_bstride, int T, const void* image, int64_t image_bstride, int S,
+                          const float* scales /* host, B floats */, int B, int D, void* out, int64_t ldo, void* stream);
 /* FLUX IP-Adapter cross-attention (td_abi_version() >= 5; [ext] diffusers >= 0.32 FluxIPAdapterJointAttnProcessor2_0, restated from the published
  * source, parity unpinned): the image rows' query against the n_keys image-prompt tokens of one adapter, the scaled result written or added to o.
  *   qn[m, h, :] = norm_w ? bf16(bf16(q[m, h, :] * rstd) * norm_w)  :  q[m, h, :]       rstd = rsqrt(mean(q[m, h, :]^2) + eps) in fp32 (qk_norm8 of
@@ -654,7 +670,8 @@ int td_attention_bias_bf16(const void* q, int64_t ldq, const void* k, const void
 int td_rope_half_bf16(void* x, int64_t ldx, int S, int H, int head_stride, int hd, const float* cos_t, const float* sin_t, void* stream);
 /* cos/sin fp32 [S, hd/2] of the 2-D vision rotary from pos int32 [S,2] = (row, column) of each patch (device). */
 int td_vision_rope_table(const int* pos, int S, int hd, float theta, float* cos_t, float* sin_t, void* stream);
-/* Conv2d(kernel = stride = p) operand: pix [C,H,W] (fp32 if src_f32 else bf16) -> out [(H/p)(W/p), Kpad] bf16, zero padded. */
+/* Conv2d(kernel = stride = p) operand: pix [C,H,W] (fp32 if src_f32 else bf16) -> out [(H/p)(W/p), Kpad] bf16, zero padded.  H / p and W / p round
+ * down: the trailing H % p rows and W % p columns are dropped, as the convolution drops them (SigLIP so400m: 384 = 27 x 14 + 6). */
 int td_patchify_bf16(const void* pix, int src_f32, int C, int H, int W, int p, void* out, int Kpad, void* stream);
 /* Qwen2-VL image preprocessing after the resize ([ext] transformers Qwen2VLImageProcessor rescale / normalize / patchify, which
  * vLLM runs on the host for thinkdiff/models/mllama_vllm_generate_1.py:543-583): img uint8 [H,W,3] (device) -> out bf16

@@ -17,12 +17,13 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 7; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 8; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
                                             // 7: int8 policy building blocks (td_norm_rows_quant8, td_quant_rows8, td_col_amax_bf16, td_smooth_factors,
                                             //    td_q8_scales_from_amax, td_ext_cols_int8, td_linear*_int8_q8, td_attention_q8, td_attention_fp8_q8)
+                                            // 8: FLUX.1 Redux (td_abi_version() >= 8: td_redux_compose_bf16)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -213,6 +214,11 @@ int td_block_cache_head_bf16(const void* h1, int64_t ld1, const void* h0, int64_
 int td_block_cache_tail_bf16(const void* a, int64_t lda, const void* b, int64_t ldb, void* out, int64_t ldo, int rows, int D, void* stream) {
   for (int64_t ld : {lda, ldb, ldo}) TD_CHECK_ARG(ld >= 0 && ld < (1ll << 31), "td_block_cache_tail: leading dimension %lld outside the 32-bit range", (long long)ld);
   return td_block_cache_tail_launch((const bf16_t*)a, (int)lda, (const bf16_t*)b, (int)ldb, (bf16_t*)out, (int)ldo, rows, D, (hipStream_t)stream);
+}
+int td_redux_compose_bf16(const void* text, int64_t text_bstride, int T, const void* image, int64_t image_bstride, int S, const float* scales, int B, int D,
+                          void* out, int64_t ldo, void* stream) {
+  return td_redux_compose_launch((const bf16_t*)text, (long long)text_bstride, T, (const bf16_t*)image, (long long)image_bstride, S, scales, B, D, (bf16_t*)out,
+                                 (long long)ldo, (hipStream_t)stream);
 }
 int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float scale, float dt, int64_t n, void* stream) {
   return td_flux_cfg_step_launch((bf16_t*)x, (const bf16_t*)v_pos, (const bf16_t*)v_neg, scale, dt, n, (hipStream_t)stream);

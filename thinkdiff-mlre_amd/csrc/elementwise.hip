@@ -815,7 +815,8 @@ __global__ void td_patchify_kernel(const void* pix, int src_f32, int C, int H, i
 }
 
 int td_patchify_launch(const void* pix, int src_f32, int C, int H, int W, int p, bf16_t* out, int Kpad, hipStream_t stream) {
-  TD_CHECK_ARG(C > 0 && p > 0 && H % p == 0 && W % p == 0 && Kpad >= C * p * p, "td_patchify: image %dx%d is not a multiple of the patch %d, or Kpad too small", H, W, p);
+  // H % p trailing rows and W % p trailing columns are dropped, as Conv2d(kernel = stride = p, no padding) drops them (SigLIP: 384 = 27 x 14 + 6)
+  TD_CHECK_ARG(C > 0 && p > 0 && H >= p && W >= p && Kpad >= C * p * p, "td_patchify: image %dx%d is smaller than the patch %d, or Kpad=%d too small", H, W, p, Kpad);
   TD_GRID_1D(nblk, (long long)(H / p) * (W / p) * 256, 256, "td_patchify");
   hipLaunchKernelGGL(td_patchify_kernel, dim3(nblk), dim3(256), 0, stream, pix, src_f32, C, H, W, p, out, Kpad);
   TD_CHECK_LAUNCH();

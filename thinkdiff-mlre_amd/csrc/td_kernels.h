@@ -210,6 +210,9 @@ int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr,
 int td_block_cache_head_launch(const bf16_t* h1, int ld1, const bf16_t* h0, int ld0, const bf16_t* r_prev, int ldp, bf16_t* r, int ldr, int rows, int D,
                                double* sums, double* ws, hipStream_t stream);
 int td_block_cache_tail_launch(const bf16_t* a, int lda, const bf16_t* b, int ldb, bf16_t* out, int ldo, int rows, int D, hipStream_t stream);
+// csrc/redux.hip: FLUX.1 Redux, B scaled [text | image] prompt streams summed into one (td_redux_compose_bf16 documents the rounding); validates its arguments
+int td_redux_compose_launch(const bf16_t* text, long long text_bstride, int T, const bf16_t* image, long long image_bstride, int S, const float* scales,
+                            int B, int D, bf16_t* out, long long ldo, hipStream_t stream);
 // csrc/ip_attention.hip: FLUX IP-Adapter cross-attention (td_ip_attention_bf16 documents the arithmetic); validates its arguments
 int td_ip_attention_launch(const bf16_t* q, int ldq, const bf16_t* k, const bf16_t* v, int ldkv, bf16_t* o, int ldo, int rows, int H, int n_keys,
                            const bf16_t* norm_w, float eps, float out_scale, int accumulate, hipStream_t stream);

@@ -191,6 +191,34 @@ at::Tensor block_cache_tail(const at::Tensor& a, const at::Tensor& b) {
   return out;
 }
 
+// FLUX.1 Redux prompt composition (td_redux_compose_bf16): text [1 or B, T, D] or None (text_rows rows of +0.0), image [B, S, D] or None (S = 0), both
+// contiguous, scales B floats (rounded to bf16 by the entry) -> [T + S, D] = sum over b of bf16(s_b * [text[b] | image[b]]), fp32 sum in index order
+at::Tensor redux_compose(const c10::optional<at::Tensor>& text, const c10::optional<at::Tensor>& image, at::ArrayRef<double> scales, int64_t text_rows) {
+  const bool has_t = text.has_value() && text->defined(), has_i = image.has_value() && image->defined();
+  TORCH_CHECK(has_t || has_i, "thinkdiff_hip::redux_compose: text and image are both None");
+  const at::Tensor& ref = has_i ? *image : *text;
+  const int64_t B = (int64_t)scales.size();
+  TORCH_CHECK(B >= 1 && B <= 16, "thinkdiff_hip::redux_compose: ", B, " scales, 1 .. 16 streams are supported");
+  check_rows(ref, has_i ? "image" : "text");
+  TORCH_CHECK(ref.dim() == 3 && ref.is_contiguous(), "thinkdiff_hip::redux_compose: text / image must be contiguous [batch, rows, D]");
+  const int64_t D = ref.size(2);
+  if (has_t && has_i) {
+    check_rows(*text, "text"); same_device(*text, "text", ref);
+    TORCH_CHECK(text->dim() == 3 && text->is_contiguous() && text->size(2) == D, "thinkdiff_hip::redux_compose: text must be contiguous [1 or B, T, ", D, "]");
+  }
+  TORCH_CHECK(!has_i || image->size(0) == B, "thinkdiff_hip::redux_compose: image has batch ", has_i ? image->size(0) : 0, ", ", B, " scales were given");
+  TORCH_CHECK(!has_t || text->size(0) == 1 || text->size(0) == B, "thinkdiff_hip::redux_compose: text has batch ", has_t ? text->size(0) : 0, ", expected 1 or ", B);
+  const int64_t T = has_t ? text->size(1) : text_rows, S = has_i ? image->size(1) : 0;
+  TORCH_CHECK(T >= 0 && T + S > 0 && T + S < (1ll << 31), "thinkdiff_hip::redux_compose: T = ", T, ", S = ", S, ": T + S must be 1 .. 2^31 - 1");
+  float sc[16];
+  for (int64_t b = 0; b < B; ++b) sc[b] = (float)scales[b];
+  DeviceGuard guard(ref.device());
+  at::Tensor out = at::empty({T + S, D}, ref.options());
+  ok(td_redux_compose_bf16(has_t ? text->data_ptr() : nullptr, has_t && text->size(0) > 1 ? text->stride(0) : 0, (int)T, has_i ? image->data_ptr() : nullptr,
+                           has_i ? image->stride(0) : 0, (int)S, sc, (int)B, (int)D, out.data_ptr(), out.stride(0), stream_of(ref)));
+  return out;
+}
+
 // FLUX IP-Adapter cross-attention (td_ip_attention_bf16): q [rows, >= H*128] (raw projection rows when norm_w is given: the per-head QK-RMSNorm is
 // fused), k / v [n_keys, >= H*128] with equal strides, 1 <= n_keys <= TD_IP_MAX_KEYS -> bf16(out_scale * softmax(qn k^T / sqrt(128)) v) [rows, H*128]
 void check_ip(const char* op, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t H, const c10::optional<at::Tensor>& norm_w) {
@@ -682,6 +710,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
   m.def("lora_merge(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor");
   m.def("lora_merge_(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)");
+  m.def("redux_compose(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor");
   m.def("ip_attention(Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale) -> Tensor");
   m.def("ip_attention_(Tensor(a!) o, Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale, bool accumulate) -> Tensor(a!)");
   m.def("flux_ip_adapter_load_param(int engine, int slot, str name, Tensor data) -> ()");
@@ -727,6 +756,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("lora_merge", &lora_merge);
   m.impl("lora_merge_", &lora_merge_);
   m.impl("flux_lora_load", &flux_lora_load);
+  m.impl("redux_compose", &redux_compose);
   m.impl("ip_attention", &ip_attention);
   m.impl("ip_attention_", &ip_attention_);
   m.impl("flux_ip_adapter_load_param", &flux_ip_adapter_load_param);

@@ -54,6 +54,7 @@ def _declare(L):
         "td_flux_residual_inject_bf16": [vp, i64, vp, i64, i32, i32, f32, vp],
         "td_block_cache_head_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp, vp, vp],
         "td_block_cache_tail_bf16": [vp, i64, vp, i64, vp, i64, i32, i32, vp],
+        "td_redux_compose_bf16": [vp, i64, i32, vp, i64, i32, ctypes.POINTER(f32), i32, i32, vp, i64, vp],
         "td_flux_set_block_cache": [vp, i32, f32],
         "td_flux_set_block_cache_schedule": [vp, vp, i32],
         "td_flux_block_cache_reset": [vp],
@@ -820,6 +821,36 @@ def sample_top_p(logits, temperature, top_p, seed, offset, out=None):
         out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     check(lib().td_sample_top_p_bf16(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), float(top_p),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, ptr(out), stream_ptr()))
+    return out
+
+
+def redux_compose(text, image, scales, T=None, D=None, device=None, out=None):
+    """FLUX.1 Redux (td_redux_compose_bf16): out[T + S, D] = sum over b of bf16(bf16(scales[b]) * [text[b] | image[b]]), fp32 sum in index order,
+    one rounding.  text [1 or B, T, D] or None (T rows of +0.0, `T=` gives the count), image [B, S, D] or None (S = 0); both contiguous bf16.
+    A text of batch 1 with B > 1 is shared by every stream and still added B times.  With neither, `D=` and `device=` size the zero rows.
+    `out` may be a 2-D view whose row stride exceeds D."""
+    scales = [float(s) for s in scales]
+    B = len(scales)
+    ref = image if image is not None else text
+    if ref is not None:
+        D, device = ref.shape[-1], ref.device
+    elif D is None or device is None or not T:
+        raise ThinkDiffHipError("redux_compose: without text and image, T=, D= and device= must size the zero rows")
+    for name, t in (("text", text), ("image", image)):
+        if t is not None and not (t.dim() == 3 and t.dtype == torch.bfloat16 and t.is_contiguous() and t.shape[2] == D and t.device == device):
+            raise ThinkDiffHipError(f"redux_compose: {name} must be a contiguous bf16 [batch, rows, {D}] tensor on {device}, got {tuple(t.shape)} {t.dtype}")
+    if image is not None and image.shape[0] != B:
+        raise ThinkDiffHipError(f"redux_compose: image has batch {image.shape[0]}, {B} scales were given")
+    if text is not None and text.shape[0] not in (1, B):
+        raise ThinkDiffHipError(f"redux_compose: text has batch {text.shape[0]}, expected 1 or {B}")
+    T = text.shape[1] if text is not None else int(T or 0)
+    S = image.shape[1] if image is not None else 0
+    if out is None:
+        out = torch.empty((T + S, D), dtype=torch.bfloat16, device=device)
+    assert out.shape[0] == T + S and out.shape[1] >= D and out.is_cuda
+    tbs = text.stride(0) if text is not None and text.shape[0] > 1 else 0
+    ibs = image.stride(0) if image is not None else 0
+    check(lib().td_redux_compose_bf16(ptr(text), tbs, T, ptr(image), ibs, S, (ctypes.c_float * B)(*scales), B, D, ptr(out), _rows(out), stream_ptr()))
     return out
 
 

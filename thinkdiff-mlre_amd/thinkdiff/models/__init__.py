@@ -9,6 +9,7 @@ from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
 from .flux_inpaint import FluxInpaintPipelineRewritePrompt
 from .flux_kontext import FluxKontextPipelineRewritePrompt
 from .flux_prompt import FluxPipelineRewritePrompt
+from .flux_redux import FluxPriorReduxPipelineRewritePrompt, ReduxImageEncoder
 from .flux_transformer import FirstBlockCacheConfig, FluxTransformer2DModel, FluxTransformerConfig, apply_first_block_cache
 from .mllama_vllm_t5_embed_decoder_2 import MllamaVllmT5EmbedDecoderForConditionalGeneration_5
 from .mllama_vllm_generate_1 import MllamaVllmGenerate_1
@@ -18,4 +19,5 @@ __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration
            "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
            "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt", "FluxKontextPipelineRewritePrompt",
            "FluxControlNetPipelineRewritePrompt", "FluxControlNetModel", "FluxControlNetConfig",
-           "FluxTransformer2DModel", "FluxTransformerConfig", "FirstBlockCacheConfig", "apply_first_block_cache"]
+           "FluxTransformer2DModel", "FluxTransformerConfig", "FirstBlockCacheConfig", "apply_first_block_cache",
+           "FluxPriorReduxPipelineRewritePrompt", "ReduxImageEncoder"]

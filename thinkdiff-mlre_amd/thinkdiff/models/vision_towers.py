@@ -6,10 +6,13 @@
 * `HipQwen2VisionTransformer` -- the Qwen2-VL ViT (32 blocks, D 1280, 16 heads x 80, 2-D rotary, full attention per
   image, 2x2 patch merger) that vLLM runs inside `self.mllama.generate` (mllama_vllm_t5_embed_decoder_2.py:1083-1089);
   oracle = transformers `Qwen2VisionTransformerPretrainedModel`.
+* `HipSiglipVisionModel` -- the SigLIP so400m ViT as transformers `SiglipVisionModel` (27 layers, D 1152, 16 heads x 72, MLP 4304, 14x14 patches of a
+  384^2 image -> 729 tokens, no class token): the image encoder of FLUX.1 Redux (thinkdiff/models/flux_redux.py), which reads `last_hidden_state`.
 
 Heads of width 88 / 80 are zero-padded to the attention kernel's 128 columns inside the fused projection weights
 (built once at load): q.k is unchanged by zero columns and the padded value columns meet zero rows of the output
-projection.  GEMM K must be a multiple of 64, so the patch operands (588 / 1176 wide) are zero-padded to 640 / 1216.
+projection.  GEMM K must be a multiple of 64, so the patch operands (588 / 1176 wide) are zero-padded to 640 / 1216; SigLIP's MLP width (4304) is padded the
+same way to 4352 (zero fc1 rows and bias give gelu(0) = 0 against zero fc2 columns).
 """
 from typing import Dict, Sequence
 
@@ -107,6 +110,110 @@ class HipBlip2VisionModel(_Base):
         hs = torch.stack(outs)
         pooled = torch.stack([_hip.layernorm(o[:1].contiguous(), self.post_w, self.post_b, self.eps)[0] for o in outs])
         return _EncoderOutput((hs, pooled))
+
+
+def siglip_padded_weights(sd: Dict[str, torch.Tensor], num_heads: int) -> dict:
+    """The operands `HipSiglipVisionModel` runs on, built from a transformers SigLIP vision state dict (with or without the `vision_model.`
+    prefix; `head.*` ignored) in the dtype and on the device of its tensors -- plain tensor surgery, so it is checkable on the host in fp32:
+      patch_w [D, round64(3 p p)], pos [n_patches, D];  per layer  qkv_w [3 H 128, Dk] / qkv_b (q | k | v, every head zero-padded to 128 columns),
+      o_w [D, H 128], fc1_w [Ip, Dk] / fc1_b [Ip], fc2_w [D, Ip]     with Dk = round64(D), Ip = round64(intermediate): zero padding throughout."""
+    pre = "vision_model." if "vision_model.embeddings.patch_embedding.weight" in sd else ""
+    if pre + "embeddings.patch_embedding.weight" not in sd:
+        raise KeyError("embeddings.patch_embedding.weight not found in the state dict (with or without the vision_model. prefix)")
+    g = lambda k: sd[pre + k]
+    w = g("embeddings.patch_embedding.weight")
+    D, H = w.shape[0], num_heads
+    hd = D // H
+    if hd * H != D or hd > HP:
+        raise ValueError(f"SigLIP width {D} does not split into {H} heads of at most {HP} columns")
+
+    def vec(b):      # _pad_heads_vec in b's own dtype (that one always answers in bf16)
+        o = torch.zeros(H * HP, dtype=b.dtype, device=b.device)
+        o.view(H, HP)[:, :hd] = b.view(H, hd)
+        return o
+
+    out = dict(D=D, H=H, hd=hd, patch=w.shape[-1], patch_w=_pad_k(w.reshape(D, -1)).contiguous(), patch_b=g("embeddings.patch_embedding.bias"),
+               pos=g("embeddings.position_embedding.weight").contiguous(), post_w=g("post_layernorm.weight"), post_b=g("post_layernorm.bias"), layers=[])
+    i = 0
+    while f"{pre}encoder.layers.{i}.self_attn.q_proj.weight" in sd:
+        p = f"encoder.layers.{i}."
+        fc1_w, fc1_b, fc2_w = g(p + "mlp.fc1.weight"), g(p + "mlp.fc1.bias"), g(p + "mlp.fc2.weight")
+        Ip = _round64(fc1_w.shape[0])
+        fc1_wp = torch.zeros(Ip, _round64(D), dtype=fc1_w.dtype, device=fc1_w.device)
+        fc1_wp[:fc1_w.shape[0], :D] = fc1_w
+        fc1_bp = torch.zeros(Ip, dtype=fc1_b.dtype, device=fc1_b.device)
+        fc1_bp[:fc1_b.shape[0]] = fc1_b
+        out["layers"].append(dict(
+            ln1w=g(p + "layer_norm1.weight"), ln1b=g(p + "layer_norm1.bias"),
+            qkv_w=_pad_k(torch.cat([_pad_heads_rows(g(p + f"self_attn.{n}_proj.weight"), H, hd) for n in "qkv"])).contiguous(),
+            qkv_b=torch.cat([vec(g(p + f"self_attn.{n}_proj.bias")) for n in "qkv"]).contiguous(),
+            o_w=_pad_heads_cols(g(p + "self_attn.out_proj.weight"), H, hd).contiguous(), o_b=g(p + "self_attn.out_proj.bias"),
+            ln2w=g(p + "layer_norm2.weight"), ln2b=g(p + "layer_norm2.bias"),
+            fc1_w=fc1_wp, fc1_b=fc1_bp, fc2_w=_pad_k(fc2_w).contiguous(), fc2_b=g(p + "mlp.fc2.bias")))
+        i += 1
+    return out
+
+
+class HipSiglipVisionModel(_Base):
+    """transformers `SiglipVisionModel` up to `last_hidden_state` (no class token, learned position table, LayerNorm with affine, gelu_pytorch_tanh
+    MLP, attention scale head_dim^-0.5, post_layernorm).  The pooling head (`head.*`) is not built: FLUX.1 Redux reads the hidden states."""
+
+    def __init__(self, sd: Dict[str, torch.Tensor], num_heads: int = 16, eps: float = 1e-6, device="cuda"):
+        super().__init__(device)
+        sd = {k: self._dev(v) for k, v in sd.items() if ".head." not in "." + k}
+        P = siglip_padded_weights(sd, num_heads)
+        self.D, self.H, self.hd, self.p, self.eps = P["D"], P["H"], P["hd"], P["patch"], eps
+        self.Dk = _round64(self.D)
+        self.patch_w, self.patch_b, self.pos = P["patch_w"], P["patch_b"], P["pos"]
+        self.layers, self.post_w, self.post_b = P["layers"], P["post_w"], P["post_b"]
+
+    @classmethod
+    def from_random(cls, hidden=1152, num_layers=27, num_heads=16, intermediate=4304, image_size=384, patch_size=14, seed=0, device="cuda"):
+        """Synthetic so400m-shaped tower (defaults = google/siglip-so400m-patch14-384 vision_config: 729 tokens) drawn on the device."""
+        shapes = {"embeddings.patch_embedding.weight": (hidden, 3, patch_size, patch_size), "embeddings.patch_embedding.bias": (hidden,),
+                  "embeddings.position_embedding.weight": ((image_size // patch_size) ** 2, hidden),
+                  "post_layernorm.weight": (hidden,), "post_layernorm.bias": (hidden,)}
+        for i in range(num_layers):
+            p = f"encoder.layers.{i}."
+            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+                shapes.update({p + f"self_attn.{n}.weight": (hidden, hidden), p + f"self_attn.{n}.bias": (hidden,)})
+            shapes.update({p + "layer_norm1.weight": (hidden,), p + "layer_norm1.bias": (hidden,), p + "layer_norm2.weight": (hidden,),
+                           p + "layer_norm2.bias": (hidden,), p + "mlp.fc1.weight": (intermediate, hidden), p + "mlp.fc1.bias": (intermediate,),
+                           p + "mlp.fc2.weight": (hidden, intermediate), p + "mlp.fc2.bias": (hidden,)})
+        return cls(_random_sd(shapes, seed, torch.device(device)), num_heads, device=device)
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: str = "image_encoder", device="cuda"):
+        cfg, sd = _read_dir(path, subfolder)
+        cfg = cfg.get("vision_config", cfg)
+        if cfg.get("hidden_act", "gelu_pytorch_tanh") != "gelu_pytorch_tanh":
+            raise _hip.ThinkDiffHipError(f"SigLIP hidden_act {cfg['hidden_act']!r}: only gelu_pytorch_tanh is implemented")
+        return cls(sd, cfg.get("num_attention_heads", 16), cfg.get("layer_norm_eps", 1e-6), device)
+
+    @torch.no_grad()
+    def __call__(self, pixel_values: torch.Tensor, **_kw):
+        """pixel_values [B,3,H,W] (fp32 or bf16, already resized and normalised) -> last_hidden_state [B, (H/p)(W/p), D] after post_layernorm;
+        `pooler_output` is None."""
+        outs = []
+        for img in pixel_values:
+            img = img.to(self.device)
+            img = img.contiguous() if img.dtype in (torch.float32, torch.bfloat16) else img.float().contiguous()
+            patches = _hip.patchify(img, self.p, self.patch_w.shape[1])
+            n = patches.shape[0]
+            if n != self.pos.shape[0]:
+                raise _hip.ThinkDiffHipError(f"image gives {n} patches; position table holds {self.pos.shape[0]} (interpolation is not implemented)")
+            h = _hip.add_rows(_hip.linear(patches, self.patch_w, self.patch_b), self.pos)
+            # GEMM K is a multiple of 64: a width that is not (tests) is normalised into the leading columns of a zeroed operand
+            x = torch.zeros(n, self.Dk, dtype=torch.bfloat16, device=self.device) if self.Dk != self.D else None
+            xv = x[:, :self.D] if x is not None else None
+            for L in self.layers:
+                y = _hip.layernorm(h, L["ln1w"], L["ln1b"], self.eps, out=xv)
+                a = _hip.attention_padded(_hip.linear(y if x is None else x, L["qkv_w"], L["qkv_b"]), self.H, self.hd ** -0.5)
+                h = _hip.linear(a, L["o_w"], L["o_b"], res=h)
+                y = _hip.layernorm(h, L["ln2w"], L["ln2b"], self.eps, out=xv)
+                h = _hip.linear(_hip.linear(y if x is None else x, L["fc1_w"], L["fc1_b"], act=_hip.ACT_GELU_TANH), L["fc2_w"], L["fc2_b"], res=h)
+            outs.append(_hip.layernorm(h, self.post_w, self.post_b, self.eps))
+        return _EncoderOutput((torch.stack(outs), None))
 
 
 def vision_position_ids(grid_thw: Sequence[Sequence[int]], merge: int = 2) -> torch.Tensor:

@@ -42,6 +42,8 @@ ip_attention / ip_attention_   FluxIPAdapterJointAttnProcessor2_0's image-prompt
                            the adapter's few keys (true row maximum, masked padding) and `scale *`, written or accumulated
 flux_ip_adapter_load_param / flux_set_ip_image_embeds / flux_ip_read   diffusers' load_ip_adapter weights and `ip_adapter_image_embeds` of one
                            image on an engine context (projection + every block's to_k_ip / to_v_ip, once), and the tokens / K / V read back
+redux_compose              FluxPriorReduxPipeline's `cat([text, image_embeds], 1) * scale[:, None, None]` and `sum(dim=0)` over the images of one call, fused:
+                           bf16 products, fp32 sum in index order, one rounding
 """
 import os
 
@@ -91,6 +93,7 @@ SCHEMAS = {
     "flux_ip_adapter_load_param": "(int engine, int slot, str name, Tensor data) -> ()",
     "flux_set_ip_image_embeds": "(int engine, int slot, Tensor embeds) -> ()",
     "flux_ip_read": "(int engine, int slot, int block, int which) -> Tensor",
+    "redux_compose": "(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor",
 }
 
 _loaded = False
