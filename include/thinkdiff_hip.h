@@ -71,6 +71,18 @@ int td_linear_grouped2_bf16(const void* x0, int M0, const void* w0, const void* 
                             int64_t ldx, int64_t ldy, int64_t ldr, int N, int K, int act, int tile_cfg,
                             void* stream);
 
+/* Test entry of the 256x256 tile's persistent walk (td_abi_version() >= 9).  With several images in flight (td_flux_denoise_multi), a bf16 launch of
+ * that tile with more tiles than CUs runs as one workgroup per CU, each walking tiles b, b + G, b + 2G, .. of the launch's tile order and storing
+ * half of every tile's output from inside the next tile's main loop.  The environment variable TD_GEMM_DRAIN, read per launch, forces the
+ * one-tile-per-workgroup launch (0) or the walk (1) everywhere.  Both forms give the same bits.
+ * This entry is td_linear_grouped2_bf16 (x1 NULL: one problem) or, with y_split != NULL (one problem only), td_linear_split_bf16, always on the
+ * 256x256 tile, with a bound on the number of walking workgroups: max_workgroups > 0 launches min(tiles, CUs, max_workgroups) of them, so that a
+ * small problem walks several tiles per workgroup (max_workgroups >= tiles: the one-tile-per-workgroup launch); 0 = no bound. */
+int td_linear_drain_bf16(const void* x0, int M0, const void* w0, const void* bias0, const void* gate0, const void* res0, void* y0,
+                         const void* x1, int M1, const void* w1, const void* bias1, const void* gate1, const void* res1, void* y1,
+                         int64_t ldx, int64_t ldy, int64_t ldr, int N, int K, int act,
+                         void* y_split, int64_t ld_split, int act_split, int n_split, int max_workgroups, void* stream);
+
 /* 3x3 convolution, stride 1, zero padding 1, over an NHWC bf16 image as an implicit GEMM (no im2col buffer):
  *   y[H*W, Cout] = conv3x3(x[Hin*Win, Cin]) + bias (+ res[H*W, Cout]);   upsample2x != 0 fuses the nearest 2x
  * upsample that precedes the conv in Upsample2D (then Hin = H/2, Win = W/2), else Hin = H, Win = W.

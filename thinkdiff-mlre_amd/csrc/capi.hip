@@ -17,13 +17,14 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 8; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 9; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
                                             // 7: int8 policy building blocks (td_norm_rows_quant8, td_quant_rows8, td_col_amax_bf16, td_smooth_factors,
                                             //    td_q8_scales_from_amax, td_ext_cols_int8, td_linear*_int8_q8, td_attention_q8, td_attention_fp8_q8)
                                             // 8: FLUX.1 Redux (td_abi_version() >= 8: td_redux_compose_bf16)
+                                            // 9: td_linear_drain_bf16 (test entry of the 256x256 tile's persistent walk)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -71,6 +72,22 @@ int td_linear_grouped2_bf16(const void* x0, int M0, const void* w0, const void* 
   p.g_A = (const bf16_t*)x1; p.g_W = (const bf16_t*)w1; p.g_bias = (const bf16_t*)bias1; p.g_gate = (const bf16_t*)gate1;
   p.g_res = (const bf16_t*)res1; p.g_C = (bf16_t*)y1; p.g_M = M1;
   p.lda = (int)ldx; p.ldc = (int)ldy; p.ldr = (int)ldr; p.N = N; p.K = K; p.act = act; p.cfg = tile_cfg;
+  return td_gemm_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_drain_bf16(const void* x0, int M0, const void* w0, const void* bias0, const void* gate0, const void* res0, void* y0,
+                         const void* x1, int M1, const void* w1, const void* bias1, const void* gate1, const void* res1, void* y1,
+                         int64_t ldx, int64_t ldy, int64_t ldr, int N, int K, int act,
+                         void* y_split, int64_t ld_split, int act_split, int n_split, int max_workgroups, void* stream) {
+  TD_CHECK_ARG(max_workgroups >= 0, "td_linear_drain_bf16: max_workgroups=%d must not be negative", max_workgroups);
+  TdGemmParams p;
+  p.A = (const bf16_t*)x0; p.W = (const bf16_t*)w0; p.bias = (const bf16_t*)bias0; p.gate = (const bf16_t*)gate0;
+  p.res = (const bf16_t*)res0; p.C = (bf16_t*)y0; p.M = M0;
+  p.g_A = (const bf16_t*)x1; p.g_W = (const bf16_t*)w1; p.g_bias = (const bf16_t*)bias1; p.g_gate = (const bf16_t*)gate1;
+  p.g_res = (const bf16_t*)res1; p.g_C = (bf16_t*)y1; p.g_M = x1 ? M1 : 0;
+  p.lda = (int)ldx; p.ldc = (int)ldy; p.ldr = (int)ldr; p.N = N; p.K = K; p.act = act;
+  p.C2 = (bf16_t*)y_split; p.ldc2 = (int)ld_split; p.act2 = y_split ? act_split : TD_ACT_NONE; p.n_split = y_split ? n_split : 0;
+  p.cfg = 0; p.drain_cap = max_workgroups;
   return td_gemm_launch(p, (hipStream_t)stream);
 }
 

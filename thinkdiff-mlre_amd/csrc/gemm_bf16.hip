@@ -57,6 +57,16 @@ struct ProbView {
 
 constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;   // beyond any descriptor range (operands are < 4 GiB - 64 KiB, checked on the host)
 
+// What a tile of the persistent walk (td_gemm_bf16_drain_kernel) leaves to the NEXT tile's main loop: the packed bf16 output of its last ND
+// m-tiles -- bias, activation, gate and residual already applied -- and where they go.  Row d, 16-byte chunk c is stored at cb[c] + d * step of
+// the descriptor (C, bytes); a chunk past N carries a cb so far up that no row of it lands inside any descriptor (see the epilogue).
+template <int ND>
+struct DrainState {
+  u32x4_t v[ND][2];
+  unsigned cb[2], step;
+  const void* C; unsigned bytes;
+};
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, p ? bytes : 0u, 0x00020000);
 }
@@ -64,9 +74,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
 // `act` and `mode` are block-uniform run-time values: ONE body, with scalar branches around the optional stages of a row.
 // (One instantiation per activation, selected by a switch in front, made the compiler hoist the shared `acc + bias` of all
 // WM rows above the switch: 128 extra live values and a spilling kernel.)
-template <int WM, int WN, bool Q8 = false>   // mode 0: bias(+act); 1: bias(+act), gate, (+res); 2: bias(+act), res
+// ND > 0 (persistent walk): the last ND m-tiles are packed into *ds instead of being stored; the others are stored here, i.e. ahead of them.
+template <int WM, int WN, bool Q8 = false, int ND = 0, class DS = void>   // mode 0: bias(+act); 1: bias(+act), gate, (+res); 2: bias(+act), res
 __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg, bool second,
-                                         const int act, const int mode) {
+                                         const int act, const int mode, DS* ds = nullptr) {
   constexpr int NV = 4 * WN;
   constexpr int CH = (NV % 8 == 0) ? 8 : 4;          // columns per access: 16-byte accesses when the lane's span allows
   constexpr int NCH = NV / CH;
@@ -88,6 +99,12 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
   const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.bias, (unsigned)pp.N * 2u);
   // (the int8 output form has no gate: its slot of per-column registers carries the smoothing factors instead)
   const bool q8_sm = q8_here && p.q8_smooth != nullptr;
+  if constexpr (ND > 0) {
+    static_assert(NCH == 2 && !Q8, "deferred rows: two 16-byte chunks per lane and row");
+    ds->C = Cout;
+    ds->bytes = (unsigned)(((long long)(p.M - 1) * ldo + ncols_out) * 2);
+    ds->step = 32u * (unsigned)ldo;
+  }
   const __amdgpu_buffer_rsrc_t rsG = make_rsrc(q8_here ? p.q8_smooth : p.gate, (unsigned)pp.N * 2u);
 
   // per-column operands of the lane's NV columns (a null bias / gate reads as zeros; mode 1 always has a gate)
@@ -99,6 +116,11 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
     const bool inr = nbeg + c * CH + CH <= pp.N;
     cok[c] = inr;
     coff[c] = (unsigned)(ncol + c * CH) * 2u;
+    if constexpr (ND > 0) {
+      // rows of the tile run at most 288 past M, and (M + 288) rows fit under 4 GiB - 64 KiB (td_gemm_launch): ND - 1 steps of 16 rows below
+      // OOB_OFFSET is still above the descriptor's extent, and the offsets of a dropped chunk do not wrap
+      ds->cb[c] = inr ? (unsigned)(mbeg + (WM - ND) * 16) * (unsigned)ldo * 2u + coff[c] : OOB_OFFSET - (unsigned)(ND - 1) * ds->step;
+    }
     if constexpr (CH == 8) {
       const u32x4_t b = __builtin_amdgcn_raw_buffer_load_b128(rsB, (unsigned)(nbeg + c * CH) * 2u, 0, 0);
 #pragma unroll
@@ -195,6 +217,8 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
     {
       if (mode != 0 && use_res) {            // block-uniform
         round_all();
+        // (res may alias the output.  In the persistent walk the previous tile's deferred stores may still be in flight here: they go to
+        // that tile's rows and columns, these loads read this tile's, so there is nothing to order)
         const unsigned roff = (unsigned)m * (unsigned)pp.ldr * 2u + (unsigned)nbeg * 2u;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
@@ -216,6 +240,9 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
         u32x4_t o;
         o[0] = pack_bf2(v[c * 8], v[c * 8 + 1]); o[1] = pack_bf2(v[c * 8 + 2], v[c * 8 + 3]);
         o[2] = pack_bf2(v[c * 8 + 4], v[c * 8 + 5]); o[3] = pack_bf2(v[c * 8 + 6], v[c * 8 + 7]);
+        if constexpr (ND > 0) {
+          if (i >= WM - ND) { ds->v[i - (WM - ND)][c] = o; continue; }
+        }
         __builtin_amdgcn_raw_buffer_store_b128(o, rsC, cok[c] ? ooff + coff[c] : OOB_OFFSET, 0, 0);   // (a sum with OOB_OFFSET would wrap)
       } else {
         u32x2_t o;
@@ -687,6 +714,241 @@ __global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmPar
 #endif
 }
 
+// ---- Persistent walk of the 256x256 tile with deferred stores (bf16 operands and output, no conv, no tail split, no K split) ---------------
+// One launch of the block Linears is 3-6 rounds of the CUs, and 13-15 % of it lies outside the k-loop (profiles/r4_gemm_probe.log): at the end of
+// a round every CU stores 128 KiB at once, a wave's vector-memory operations retire in order, and so the next tile's first counted wait sits
+// behind that burst -- whether the next tile is a new workgroup or not (profiles/r4_gemm_persistent_ab.md).  Here a workgroup walks tiles
+// b, b + G, b + 2G, ... of the SAME logical order (G workgroups = CUs), and a tile's epilogue keeps the packed output of its last ND m-tiles in
+// registers: they are stored two per k-tile (one m-tile's row) from inside the next tile's first ND k-tiles, in (k-step, m-tile) slots that
+// carry no DMA, and the counted waits of those k-tiles leave them in flight -- a store then has a whole k-tile of MFMAs to be acknowledged
+// under.  What a short k-loop (K = 64 ND and below) or the ragged loop cannot take is stored behind it, and the last tile's rows behind the walk.
+// Every output element is still one workgroup's whole contraction in the same k order through the same epilogue: bit-identical.
+template <int ND>
+__device__ __forceinline__ void drain_row(const DrainState<ND>& ds, const int d) {
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc(ds.C, ds.bytes);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) __builtin_amdgcn_raw_buffer_store_b128(ds.v[d][c], rs, ds.cb[c] + (unsigned)d * ds.step, 0, 0);
+}
+
+// One tile of the walk: gemm_tile<8, 4> for bf16 operands without its conv / 8-bit / split-K forms, plus the stores `ds` holds when `pending`.
+template <int ND>
+__device__ __forceinline__ void gemm_tile_drain(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0, DrainState<ND>& ds,
+                                                bool& pending) {
+  constexpr int WM = 8, WN = 4;
+  constexpr int BM = 32 * WM, BN = 64 * WN;
+  constexpr int A_BYTES = BM * ROW_BYTES, W_BYTES = BN * ROW_BYTES;
+  constexpr int SA = BM / 64, SW = BN / 64, NS = SA + SW;      // staging instructions per wave and k-tile
+  constexpr int NV = 4 * WN;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wr = wid >> 2, wc = wid & 3;
+
+  ProbView pv;
+  pv.bias = second_prob ? p.g_bias : p.bias;
+  pv.gate = second_prob ? p.g_gate : p.gate;
+  pv.res = second_prob ? p.g_res : p.res;
+  pv.C = second_prob ? p.g_C : p.C;
+  pv.M = second_prob ? p.g_M : p.M;
+  pv.q8 = nullptr; pv.q8_inv = nullptr; pv.q8_amax = nullptr; pv.q8_smooth = nullptr;
+  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(second_prob ? p.g_A : p.A, (unsigned)(((long long)(pv.M - 1) * p.lda + p.K) * 2));
+  const __amdgpu_buffer_rsrc_t rsW = make_rsrc(second_prob ? p.g_W : p.W, (unsigned)((((long long)p.N - 1) * p.ldw + p.K) * 2));
+
+  // staging offsets, LDS layout and fragment offsets: gemm_tile's
+  const int srow = lane >> 3;
+  const int schunk = ((lane & 7) ^ srow) << 4;
+  unsigned voffS[NS];
+  int ldsS[NS];
+#pragma unroll
+  for (int s = 0; s < SA; ++s) {
+    const int g = wid + 8 * s;
+    voffS[s] = (unsigned)(m0 + g * 8 + srow) * (unsigned)p.lda * 2u + schunk;
+    ldsS[s] = g * 1024;
+  }
+#pragma unroll
+  for (int s = 0; s < SW; ++s) {
+    const int g = wid + 8 * s;
+    const int rho = g * 8 + srow;
+    const int wcol = rho / (16 * WN);
+    const int rem = rho - wcol * (16 * WN);
+    const int j = rem >> 4, i16 = rem & 15;
+    const int n = n0 + wcol * (16 * WN) + (i16 >> 2) * NV + j * 4 + (i16 & 3);
+    voffS[SA + s] = (unsigned)n * (unsigned)p.ldw * 2u + schunk;
+    ldsS[SA + s] = g * 1024;
+  }
+  constexpr int W_REGION = 2 * A_BYTES;
+  auto stage_one = [&](int s, int abuf, int wbuf, int kt) {
+    if (s < SA) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (TD_LDS void*)(smem + abuf * A_BYTES + ldsS[s]), 16, voffS[s], kt * (BK * 2), 0, 0);
+    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (TD_LDS void*)(smem + W_REGION + wbuf * W_BYTES + ldsS[s]), 16, voffS[s], kt * (BK * 2), 0, 0);
+  };
+  const int frow = lane & 15;
+  const int foff0 = frow * ROW_BYTES + ((((lane >> 4)) ^ (lane & 7)) << 4);
+  const int aoff = (wr * 16 * WM) * ROW_BYTES;
+  const int woff = (wc * 16 * WN) * ROW_BYTES;
+
+  f32x4_t acc[WN][WM];
+#pragma unroll
+  for (int j = 0; j < WN; ++j)
+#pragma unroll
+    for (int i = 0; i < WM; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int nt = p.probe == 2 ? 1 : p.K / BK;
+#pragma unroll
+  for (int s = 0; s < NS; ++s) stage_one(s, 0, 0, 0);
+#pragma unroll
+  for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
+  int wcur = 0;
+  int done = 0;      // deferred rows issued inside this tile's k-loop (workgroup-uniform)
+  if (pv.M - m0 <= p.ragged_rows) {
+    // gemm_tile's ragged loop (at most 64 rows exist): nothing is matrix-bound here, the deferred rows are stored behind it
+    const int mt_valid = wr == 0 ? (pv.M - m0 + 15) >> 4 : 0;
+    for (int t = 0; t < nt; ++t) {
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
+      __builtin_amdgcn_s_barrier();
+      const char* wb = smem + W_REGION + wcur * W_BYTES + woff;
+      const char* ab = smem + (t & 1) * A_BYTES + aoff;
+      const int kt_a = min(t + 1, nt - 1), kt_w = min(t + 2, nt - 1);
+      const int abuf_next = (t + 1) & 1;
+      const int wbuf_next = wcur == 0 ? 2 : wcur - 1;
+      wcur = wcur == 2 ? 0 : wcur + 1;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) stage_one(s, abuf_next, wbuf_next, s < SA ? kt_a : kt_w);
+      if (mt_valid > 0) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+          const int fo = foff0 ^ (ks << 6);
+          bf16x8_t wf[WN];
+#pragma unroll
+          for (int j = 0; j < WN; ++j) wf[j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + fo);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (i < mt_valid) {
+              const bf16x8_t af = *(const bf16x8_t*)(ab + i * 16 * ROW_BYTES + fo);
+#pragma unroll
+              for (int j = 0; j < WN; ++j) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af, acc[j][i], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+  } else {
+    // gemm_tile's main loop.  drow >= 0: this k-tile also stores deferred row drow, one chunk each in slots 9 and 13 (k-step 1: the DMAs ride on
+    // k-step 0).  after_stores: the previous k-tile issued two stores behind its W DMAs, so the counted wait leaves two more operations in flight.
+    // Both are literals at every call, and the body is inlined at each.
+    auto ktile = [&](const int t, const int drow, const bool after_stores) __attribute__((always_inline)) {
+      if (after_stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW + 2) : "memory");
+      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
+      __builtin_amdgcn_s_barrier();
+      const char* wb = smem + W_REGION + wcur * W_BYTES + woff;
+      const char* ab = smem + (t & 1) * A_BYTES + aoff;
+      const int kt_a = min(t + 1, nt - 1);
+      const int kt_w = min(t + 2, nt - 1);
+      const int abuf_next = (t + 1) & 1;
+      const int wbuf_next = wcur == 0 ? 2 : wcur - 1;
+      wcur = wcur == 2 ? 0 : wcur + 1;
+      bf16x8_t wf[2][WN], af[2];
+#pragma unroll
+      for (int j = 0; j < WN; ++j) wf[0][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + foff0);
+      af[0] = *(const bf16x8_t*)(ab + foff0);
+      __builtin_amdgcn_sched_group_barrier(0x100, WN + 1, 0);
+      constexpr int MASK_VMEM = 0x010, MASK_VMEM_WRITE = 0x040, MASK_DS_READ = 0x100, MASK_MFMA = 0x008;
+      const __amdgpu_buffer_rsrc_t rsD = make_rsrc(ds.C, ds.bytes);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const int fo = foff0 ^ (ks << 6);
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+          const int it = ks * WM + i;
+          const int cur = it & 1;
+          if (it < NS) stage_one(it, abuf_next, wbuf_next, it < SA ? kt_a : kt_w);
+          const bool st = drow >= 0 && (it == 9 || it == 13);
+          if (st) __builtin_amdgcn_raw_buffer_store_b128(ds.v[drow][it == 13], rsD, ds.cb[it == 13] + (unsigned)drow * ds.step, 0, 0);
+          if (i + 1 < WM) af[cur ^ 1] = *(const bf16x8_t*)(ab + (i + 1) * 16 * ROW_BYTES + fo);
+          else if (ks == 0) af[cur ^ 1] = *(const bf16x8_t*)(ab + (fo ^ 64));
+          bool rd_w = false;
+          if (ks == 0) {
+#pragma unroll
+            for (int j = 0; j < WN; ++j)
+              if (WM - 1 - j == i) { wf[1][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + (fo ^ 64)); rd_w = true; }
+          }
+#pragma unroll
+          for (int j = 0; j < WN; ++j) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][j], af[cur], acc[j][i], 0, 0, 0);
+          if (it < NS) __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 1, 0);
+          if (st) __builtin_amdgcn_sched_group_barrier(MASK_VMEM_WRITE, 1, 0);
+          if (i + 1 < WM || ks == 0) {
+            if (rd_w) __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 2, 0);
+            else __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 1, 0);
+          }
+          __builtin_amdgcn_sched_group_barrier(MASK_MFMA, WN, 0);
+        }
+      }
+    };
+    int t = 0;
+    if (pending) {
+#pragma unroll
+      for (int d = 0; d <= ND; ++d) {      // (the k-tile behind the last stores: the wider wait once more)
+        if (t < nt) {
+          ktile(t, d < ND ? d : -1, d > 0);
+          ++t;
+          if (d < ND) done = d + 1;
+        }
+      }
+    }
+    for (; t < nt; ++t) ktile(t, -1, false);
+  }
+  // every wave has read its last fragments before anybody's next DMA may land on them (the next tile's prologue, or nothing)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  if (pending) {
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+      if (d >= done) drain_row(ds, d);
+  }
+  pending = false;
+  if (p.probe == 1) return;
+  // epilogue.  Lanes whose columns lie past N stay in (the walk goes on): their loads are range-checked, their chunks are dropped.
+  const int nbeg = n0 + wc * 16 * WN + (lane >> 4) * NV;
+  const bool second = (p.C2 != nullptr) && (n0 >= p.n_split);
+  const int act = second ? p.act2 : p.act;
+  const int mbeg = m0 + wr * 16 * WM + frow;
+  const int mode = pv.gate ? 1 : (pv.res ? 2 : 0);
+  epilogue<WM, WN, false, ND>(p, pv, acc, mbeg, nbeg, second, act, mode, &ds);
+  pending = true;
+}
+
+constexpr int TD_DRAIN_ROWS = 4;      // m-tiles (of 8) whose stores a tile leaves to the next: see DESIGN 4
+
+template <int ND>
+__global__ __launch_bounds__(512, 1) void td_gemm_bf16_drain_kernel(const TdGemmParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int total = p.tiles_m * p.tiles_n;
+  DrainState<ND> ds = {};
+  bool pending = false;
+  // virtual workgroup ids b, b + G, ...: with G a multiple of 8 they are all on this workgroup's XCD, so every tile runs where the
+  // one-tile-per-workgroup launch would have put it, in the same order
+  for (int v = (int)blockIdx.x; v < total; v += (int)gridDim.x) {
+    const int t = xcd_contiguous(v, total);
+    constexpr int GROUP_M = 4;
+    const int per_group = GROUP_M * p.tiles_n;
+    const int gid = t / per_group;
+    const int first_m = gid * GROUP_M;
+    const int gsize = min(p.tiles_m - first_m, GROUP_M);
+    const int in_g = t - gid * per_group;
+    int tm = first_m + in_g % gsize;
+    const int tn = in_g / gsize;
+    const bool second_prob = tm >= p.tiles_m0;
+    if (second_prob) tm -= p.tiles_m0;
+    gemm_tile_drain<ND>(p, smem, second_prob, tm * 256, tn * 256, ds, pending);
+  }
+  if (pending) {
+#pragma unroll
+    for (int d = 0; d < ND; ++d) drain_row(ds, d);
+  }
+#endif
+}
+
 namespace {
 
 // How many CUs the device has (the round size of a one-workgroup-per-CU grid); cached per device.
@@ -762,6 +1024,30 @@ int launch_cfg(const TdGemmParams& p0, hipStream_t stream) {
     attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
   }
   if (p.ldw == 0) p.ldw = p.K;
+  if constexpr (TAIL == 1 && WM == 8 && WN == 4 && !CONV && !FP8 && !I8) {
+    // More tiles than CUs, bf16 in and out: one persistent workgroup per CU walks the tiles and drains each tile's stores under the next one's
+    // main loop (td_gemm_bf16_drain_kernel).  Taken where it measured a gain (profiles/gemm_drain_ab.log, same process, alternated three times):
+    // with several images in flight (the caller's shared-chip hint) 0.6112 against 0.5948 images/s, every run of one arm above every run of the
+    // other; a lone image LOSES 0.2 % with it (0.5868 against 0.5882) and a lone cold launch gains nothing (profiles/gemm_drain_probe.log), so
+    // without the hint the launch stays one tile per workgroup.  TD_GEMM_DRAIN=0 / 1 forces either form (A/B switch, read per launch so one
+    // process can time both); drain_cap bounds the workgroups and asks for the walk (tests: a small problem walks several tiles per workgroup).
+    const char* dr = getenv("TD_GEMM_DRAIN");
+    const bool walk = dr ? atoi(dr) != 0 : (p.no_tail != 0 || p.drain_cap > 0);
+    if (p.k_parts == 1 && !p.out_f32 && walk) {
+      int wgs = std::min(grid, cu_count());
+      if (p.drain_cap > 0) wgs = std::min(wgs, p.drain_cap);
+      if (wgs < grid) {
+        static std::atomic<unsigned long long> drain_attr_done{0ull};
+        if (!((drain_attr_done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
+          TD_CHECK_HIP(hipFuncSetAttribute((const void*)td_gemm_bf16_drain_kernel<TD_DRAIN_ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+          drain_attr_done.fetch_or(1ull << (dev & 63), std::memory_order_release);
+        }
+        hipLaunchKernelGGL((td_gemm_bf16_drain_kernel<TD_DRAIN_ROWS>), dim3(wgs), dim3(512), LDS, stream, p);
+        TD_CHECK_LAUNCH();
+        return 0;
+      }
+    }
+  }
   hipLaunchKernelGGL((td_gemm_bf16_nt_kernel<WM, WN, CONV, FP8, I8, TAIL>), dim3(grid, p.k_parts > 1 ? p.k_parts : 1), dim3(512), LDS, stream, p);
   TD_CHECK_LAUNCH();
   return 0;

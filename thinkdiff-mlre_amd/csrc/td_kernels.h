@@ -69,6 +69,7 @@ struct TdGemmParams {
   int tail_first_wg = 0;                       // filled by the launcher (tail-split launches): workgroups from here on take a sub-tile of the last tiles
   int no_tail = 0;                             // caller's hint: other kernels share the chip (several images in flight) -- an empty last round gets filled anyway, do not split it
   int probe = 0;                               // filled by the launcher from TD_GEMM_PROBE (timing experiments, results WRONG): 1 = no epilogue, 2 = no k-loop
+  int drain_cap = 0;                           // 256x256 bf16 tile: at most this many persistent workgroups walk the tiles (0: one per CU); see td_gemm_bf16_drain_kernel
 };
 
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream);

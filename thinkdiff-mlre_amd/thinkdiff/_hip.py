@@ -44,6 +44,7 @@ def _declare(L):
         "td_linear_split_bf16": [vp, i64, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
         "td_linear_splitk_bf16": [vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, vp, vp, i64, f32, vp],
         "td_linear_grouped2_bf16": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, i32, vp],
+        "td_linear_drain_bf16": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, i32, i32, i32, vp],
         "td_norm_rows_bf16": [vp, i64, vp, i64, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
         "td_qk_norm_rope_bf16": [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, i32, vp],
         "td_flux_rope_table": [vp, i32, vp, ctypes.c_double, vp, vp, vp],
@@ -464,6 +465,21 @@ def linear_grouped2(x0, w0, b0, y0, x1, w1, b1, y1, act=ACT_NONE, gate0=None, re
                                         ptr(x1), M1, ptr(w1), ptr(b1), ptr(gate1), ptr(res1), ptr(y1),
                                         _rows(x0), _rows(y0), ldr, N, K, act, tile_cfg, stream_ptr()))
     return y0, y1
+
+
+def linear_drain(x0, w0, b0, y0, x1=None, w1=None, b1=None, y1=None, act=ACT_NONE, gate0=None, res0=None, gate1=None, res1=None,
+                 y_split=None, act_split=ACT_NONE, n_split=0, max_workgroups=0):
+    """td_linear_drain_bf16: linear_grouped2 (or, with y_split, the split-output Linear) on the 256x256 tile with at most max_workgroups
+    walking workgroups (0: no bound)."""
+    M0, K = x0.shape
+    N = w0.shape[0]
+    M1 = 0 if x1 is None else x1.shape[0]
+    ldr = _rows(res0) if res0 is not None else 0
+    check(lib().td_linear_drain_bf16(ptr(x0), M0, ptr(w0), ptr(b0), ptr(gate0), ptr(res0), ptr(y0),
+                                     ptr(x1), M1, ptr(w1), ptr(b1), ptr(gate1), ptr(res1), ptr(y1),
+                                     _rows(x0), _rows(y0), ldr, N, K, act,
+                                     ptr(y_split), _rows(y_split) if y_split is not None else 0, act_split, n_split, max_workgroups, stream_ptr()))
+    return y0
 
 
 class TdQwen2Config(ctypes.Structure):

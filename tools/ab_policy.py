@@ -1,5 +1,6 @@
 """Same-box, same-process A/B of an environment switch on whole images: config 5's shape (T = 258), 2 images in flight, a policy of
 tests/test_flux_full_depth_gpu.py::POLICIES; the switch (e.g. TD_GEMM_NO_TAIL=1) is read per launch, so both arms share weights, clocks and thermals.
+The "on" arm sets ENVVAR to $TD_AB_VALUE (default 1), the "off" arm unsets it (TD_AB_VALUE=0 with TD_GEMM_DRAIN: "on" is the one-tile launch).
 usage: python tools/ab_policy.py POLICY ENVVAR [rounds=3] [images in flight=2]"""
 import os
 import sys
@@ -45,4 +46,4 @@ for _ in range(rounds):
         torch.cuda.synchronize()
         res[arm].append(4 / (time.perf_counter() - t0))
 os.environ.pop(var, None)
-print(f"{policy} ({G} in flight): {var} unset " + " ".join(f"{v:.4f}" for v in res["off"]) + f" images/s | {var}=1 " + " ".join(f"{v:.4f}" for v in res["on"]), flush=True)
+print(f"{policy} ({G} in flight): {var} unset " + " ".join(f"{v:.4f}" for v in res["off"]) + f" images/s | {var}={os.environ.get('TD_AB_VALUE', '1')} " + " ".join(f"{v:.4f}" for v in res["on"]), flush=True)

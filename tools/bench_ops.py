@@ -119,7 +119,8 @@ def bench_gemmfp8():
 
 def bench_gemmprobe():
     """Where a block GEMM's time goes: the whole launch, the k-loop alone (TD_GEMM_PROBE=1: no epilogue) and the prologue + epilogue alone
-    (TD_GEMM_PROBE=2: one k-tile), bf16 and int8, GELU epilogue, cold weights, tail split off and on."""
+    (TD_GEMM_PROBE=2: one k-tile), bf16 and int8, GELU epilogue, cold weights, tail split off and on; with the tail split off, the bf16 launch both
+    as one tile per workgroup (TD_GEMM_DRAIN=0) and as the persistent walk with deferred stores (the int8 kernels have no such form)."""
     for name, M, N, K in [("ff1", 4289, 12288, 3072), ("qkv", 4289, 9216, 3072), ("single_in", 4289, 21504, 3072), ("ff1 T=258", 4354, 12288, 3072)]:
         x = torch.randn(M, K, device="cuda").bfloat16()
         npool = max(2, int(0.8e9 // (N * K * 2)))
@@ -136,11 +137,15 @@ def bench_gemmprobe():
             st["i"] = (st["i"] + 1) % npool
             wq, ws = ipool[st["i"]]
             _hip.linear_int8(xi, xis, wq, ws, b, act=_hip.ACT_GELU_TANH, out=y, tile_cfg=0)
-        for tail in ("off", "on"):
+        for tail, drain in (("off", "off"), ("off", "on"), ("on", "off")):
             if tail == "off":
                 os.environ.pop("TD_GEMM_TAIL", None)
             else:
                 os.environ["TD_GEMM_TAIL"] = "auto"
+            if drain == "off":
+                os.environ["TD_GEMM_DRAIN"] = "0"
+            else:
+                os.environ["TD_GEMM_DRAIN"] = "1"
             row = []
             for kind, f in (("bf16", f_bf16), ("int8", f_int8)):
                 t = {}
@@ -149,7 +154,8 @@ def bench_gemmprobe():
                     t[probe] = min(timeit(f, iters=10, warmup=2) for _ in range(3))
                 os.environ.pop("TD_GEMM_PROBE")
                 row.append(f"{kind}: whole {t['0']*1e3:6.1f} us  k-loop only {t['1']*1e3:6.1f}  1 k-tile + epilogue {t['2']*1e3:6.1f}")
-            print(f"{name:10s} M={M} N={N} K={K} tail split {tail:3s} | " + " | ".join(row), flush=True)
+            print(f"{name:10s} M={M} N={N} K={K} tail split {tail:3s} drain {drain:3s} | " + " | ".join(row), flush=True)
+        os.environ.pop("TD_GEMM_DRAIN", None)
         del pool, ipool
 
 
