@@ -198,6 +198,17 @@ int td_flux_cfg_step_bf16(void* x, const void* v_pos, const void* v_neg, float s
  * h, r bf16 with row strides ldh, ldr >= D (elements; columns beyond D are untouched); D % 8 == 0, strides multiples of 8, both pointers 16-byte
  * aligned, r not overlapping h. */
 int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream);
+/* The same for n ControlNets at once (td_abi_version() >= 10; [ext] diffusers controlnet_flux.py FluxMultiControlNetModel.forward: the scaled samples
+ * of the nets are summed in bf16 first, in list order, then the sum is added to hidden_states):
+ *   s_k = bf16(scales[k] * float(r[k][m, j]));   acc = s_0;   acc = bf16(float(acc) + float(s_k))  for k = 1 .. n-1 (left fold, one rounding per add)
+ *   h[m, j] = bf16(float(h[m, j]) + float(acc))                                  m < rows, j < D
+ * -- not what n calls of td_flux_residual_inject_bf16 give, and one pass over h instead of n.  r, ldr, scales: HOST arrays of n entries
+ * (1 <= n <= TD_MAX_CONTROLNETS), read during the call and passed to the kernel by value (no device-side table: capturable).  Checked before the
+ * launch, TD_ERR_INVALID naming k: every r[k] non-null, 16-byte aligned, ldr[k] a multiple of 8 and >= D, not overlapping h; every scales[k] finite
+ * (a NaN or infinite scale is refused, as td_flux_set_controlnet_scales refuses it).  n == 1 gives td_flux_residual_inject_bf16's bits. */
+#define TD_MAX_CONTROLNETS 4
+int td_flux_residual_inject_multi_bf16(void* h, int64_t ldh, const void* const* r, const int64_t* ldr, const float* scales, int n, int rows, int D,
+                                       void* stream);
 /* First-block cache kernels (td_abi_version() >= 6; what the engine's cache runs, td_flux_set_block_cache below).  bf16 rows of D columns (D % 8 == 0)
  * at row strides that are multiples of 8 and at least D, every pointer 16-byte aligned.
  * td_block_cache_head_bf16:   r[m, j] = bf16(float(h1[m, j]) - float(h0[m, j]))
@@ -433,6 +444,23 @@ int td_flux_controlnet_read_sample(const td_flux* cn, int k, void* dst, void* st
 int td_flux_attach_controlnet(td_flux* f, td_flux* cn);
 /* conditioning scale per prepared step (n host floats; steps beyond n keep 1.0): controlnet_conditioning_scale x controlnet_keep[i]. */
 int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n);
+/* ---- Several ControlNets on one main context (td_abi_version() >= 10; [ext] diffusers FluxMultiControlNetModel, restated from the published
+ * controlnet_flux.py / pipeline_flux_controlnet.py, parity unpinned).  td_flux_attach_controlnets attaches cns[0 .. n) in list order, 0 <= n <=
+ * TD_MAX_CONTROLNETS; n = 0 detaches all.  td_flux_attach_controlnet(f, cn) is its n = 1 form, cn == NULL its n = 0 form.  Every context obeys the
+ * one-main-context rule above; the same context listed twice is TD_ERR_INVALID (two appearances of one MODEL are two forks).  Attaching resets
+ * every net's scale table to 1.0; a refused call changes nothing.
+ * td_flux_forward at a step: the nets whose scale at the step is not 0 are the ACTIVE ones.  Each passes the forward-time checks above (messages
+ * name k), then they run one after another on the same latents, step and stream, and behind each block ONE td_flux_residual_inject_multi_bf16
+ * launch over the active nets in list order adds   bf16(h + fold_k bf16(scale_k * sample_k[idx_k]))   to the image rows.
+ * Deviations from diffusers, both deliberate: (1) every net uses ITS OWN index rule idx_k = i / ceil(n_blocks / n_samples_k) (diffusers zips the
+ * nets' sample lists and silently truncates when the counts differ; with equal counts the two agree), and a net with n_s = 0 takes no part in the
+ * single-block sums; (2) a net whose scale at the step is 0 is not run and is left out of the fold (diffusers adds bf16(0 * x): at most the sign of
+ * a zero differs).  A step at which every scale is 0, and a context with nothing attached, issue exactly the plain forward's launches. */
+int td_flux_attach_controlnets(td_flux* f, td_flux* const* cns, int n);
+/* Net k's conditioning scale per prepared step (as td_flux_set_controlnet_scales, which is k = 0); k outside the attached count is TD_ERR_INVALID. */
+int td_flux_set_controlnet_scales_at(td_flux* f, int k, const float* scales, int n);
+/* The attached count (0 .. TD_MAX_CONTROLNETS). */
+int td_flux_attached_controlnets(const td_flux* f, int* n);
 /* ---- FLUX IP-Adapter (td_abi_version() >= 5): image-prompt conditioning of the double-stream blocks ([ext] diffusers >= 0.32 FluxIPAdapterMixin,
  * embeddings.ImageProjection, attention_processor.FluxIPAdapterJointAttnProcessor2_0, transformer_flux.FluxTransformerBlock.forward; restated from
  * the published sources, parity unpinned).  Up to TD_IP_MAX_ADAPTERS adapters in numbered slots.  Per adapter, J = joint_dim, D = heads x 128:

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 9; }      // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 10; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -25,6 +25,8 @@ int td_abi_version(void) { return 9; }      // 2: TdFluxConfig::out_channels app
                                             //    td_q8_scales_from_amax, td_ext_cols_int8, td_linear*_int8_q8, td_attention_q8, td_attention_fp8_q8)
                                             // 8: FLUX.1 Redux (td_abi_version() >= 8: td_redux_compose_bf16)
                                             // 9: td_linear_drain_bf16 (test entry of the 256x256 tile's persistent walk)
+                                            // 10: several ControlNets per context (td_flux_attach_controlnets, td_flux_set_controlnet_scales_at,
+                                            //     td_flux_attached_controlnets, td_flux_residual_inject_multi_bf16)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -219,6 +221,19 @@ int td_flux_inpaint_step_bf16(void* x, const void* v, const void* image_latents,
 int td_flux_residual_inject_bf16(void* h, int64_t ldh, const void* r, int64_t ldr, int rows, int D, float scale, void* stream) {
   TD_CHECK_ARG(ldh >= 0 && ldh < (1ll << 31) && ldr >= 0 && ldr < (1ll << 31), "td_flux_residual_inject: ldh=%lld / ldr=%lld outside the 32-bit range", (long long)ldh, (long long)ldr);
   return td_flux_residual_inject_launch((bf16_t*)h, (int)ldh, (const bf16_t*)r, (int)ldr, rows, D, scale, (hipStream_t)stream);
+}
+
+int td_flux_residual_inject_multi_bf16(void* h, int64_t ldh, const void* const* r, const int64_t* ldr, const float* scales, int n, int rows, int D,
+                                       void* stream) {
+  TD_CHECK_ARG(h && r && ldr && scales, "td_flux_residual_inject_multi: null argument");
+  TD_CHECK_ARG(n >= 1 && n <= TD_MAX_CONTROLNETS, "td_flux_residual_inject_multi: n=%d outside 1 .. %d", n, TD_MAX_CONTROLNETS);
+  TD_CHECK_ARG(ldh >= 0 && ldh < (1ll << 31), "td_flux_residual_inject_multi: ldh=%lld outside the 32-bit range", (long long)ldh);
+  int ld[TD_MAX_CONTROLNETS];
+  for (int k = 0; k < n; ++k) {
+    TD_CHECK_ARG(ldr[k] >= 0 && ldr[k] < (1ll << 31), "td_flux_residual_inject_multi: ldr[%d]=%lld outside the 32-bit range", k, (long long)ldr[k]);
+    ld[k] = (int)ldr[k];
+  }
+  return td_flux_residual_inject_multi_launch((bf16_t*)h, (int)ldh, (const bf16_t* const*)r, ld, scales, n, rows, D, (hipStream_t)stream);
 }
 
 int td_block_cache_head_bf16(const void* h1, int64_t ld1, const void* h0, int64_t ld0, const void* r_prev, int64_t ldp, void* r, int64_t ldr, int rows, int D,

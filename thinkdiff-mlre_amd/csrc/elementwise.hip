@@ -515,6 +515,72 @@ int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr,
   return 0;
 }
 
+// Several ControlNets on one transformer [ext diffusers controlnet_flux.py FluxMultiControlNetModel.forward, transformer_flux.py]: the scaled
+// samples of the nets are summed in bf16 FIRST, in list order, one rounding per add, and the sum meets the hidden state once:
+//   s_k = bf16(scale_k * float(r_k[m, j]));   acc = s_0;   acc = bf16(float(acc) + float(s_k))  for k = 1 .. N-1
+//   h[m, j] = bf16(float(h[m, j]) + float(acc))
+// which is NOT what N launches of the kernel above give (bf16(bf16(h + s_0) + s_1)), and reads and writes h once instead of N times.  The
+// pointers, strides and scales travel BY VALUE in the kernel arguments (no device-side table: capturable, nothing to keep alive); N is a
+// template argument so that every index into them is a constant (they stay in SGPRs).  N + 1 bf16 streams in, one out, 16 B per lane; rbf()
+// stands behind every product and every partial sum, so there is no a + b * c for the compiler to contract.  N == 1 is the kernel above.
+struct TdInjectMultiArgs {
+  const bf16_t* r[TD_MAX_CONTROLNETS];
+  int ldr[TD_MAX_CONTROLNETS];
+  float scale[TD_MAX_CONTROLNETS];
+};
+
+template <int N>
+__global__ void td_flux_residual_inject_multi_kernel(bf16_t* h, int ldh, TdInjectMultiArgs p, int rows, int chunks) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * chunks) return;
+  const int m = idx / chunks, c = idx - m * chunks;
+  bf16_t* hp = h + (size_t)m * ldh + c * 8;
+  float a[8], acc[8], b[8];
+  unpack8(*(const u32x4_t*)hp, a);
+  unpack8(*(const u32x4_t*)(p.r[0] + (size_t)m * p.ldr[0] + c * 8), b);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = rbf(p.scale[0] * b[i]);
+#pragma unroll
+  for (int k = 1; k < N; ++k) {
+    unpack8(*(const u32x4_t*)(p.r[k] + (size_t)m * p.ldr[k] + c * 8), b);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = rbf(acc[i] + rbf(p.scale[k] * b[i]));
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) a[i] = a[i] + acc[i];
+  *(u32x4_t*)hp = pack8(a);
+}
+
+int td_flux_residual_inject_multi_launch(bf16_t* h, int ldh, const bf16_t* const* r, const int* ldr, const float* scales, int n, int rows, int D,
+                                         hipStream_t stream) {
+  TD_CHECK_ARG(h && r && ldr && scales, "td_flux_residual_inject_multi: null argument");
+  TD_CHECK_ARG(n >= 1 && n <= TD_MAX_CONTROLNETS, "td_flux_residual_inject_multi: n=%d outside 1 .. %d", n, TD_MAX_CONTROLNETS);
+  TD_CHECK_ARG(rows > 0 && D > 0 && D % 8 == 0, "td_flux_residual_inject_multi: rows=%d, D=%d: D must be a positive multiple of 8, rows positive", rows, D);
+  TD_CHECK_ARG(ldh % 8 == 0 && ldh >= D, "td_flux_residual_inject_multi: ldh=%d must be a multiple of 8 and at least D=%d", ldh, D);
+  TD_CHECK_ARG((uintptr_t)h % 16 == 0, "td_flux_residual_inject_multi: h must be 16-byte aligned");
+  const uintptr_t h0 = (uintptr_t)h, h1 = h0 + ((uintptr_t)(rows - 1) * ldh + D) * sizeof(bf16_t);
+  TdInjectMultiArgs p = {};
+  for (int k = 0; k < n; ++k) {
+    TD_CHECK_ARG(r[k], "td_flux_residual_inject_multi: r[%d] is null", k);
+    TD_CHECK_ARG(ldr[k] % 8 == 0 && ldr[k] >= D, "td_flux_residual_inject_multi: ldr[%d]=%d must be a multiple of 8 and at least D=%d", k, ldr[k], D);
+    TD_CHECK_ARG((uintptr_t)r[k] % 16 == 0, "td_flux_residual_inject_multi: r[%d] must be 16-byte aligned", k);
+    TD_CHECK_ARG(std::isfinite(scales[k]), "td_flux_residual_inject_multi: scales[%d] is not finite", k);
+    const uintptr_t r0 = (uintptr_t)r[k], r1 = r0 + ((uintptr_t)(rows - 1) * ldr[k] + D) * sizeof(bf16_t);
+    TD_CHECK_ARG(r0 >= h1 || r1 <= h0, "td_flux_residual_inject_multi: r[%d] must not overlap h (updated in place)", k);
+    p.r[k] = r[k]; p.ldr[k] = ldr[k]; p.scale[k] = scales[k];
+  }
+  TD_GRID_1D_I32(nblk, (long long)rows * (D / 8), 256, "td_flux_residual_inject_multi");
+  const dim3 grid(nblk), block(256);
+  switch (n) {
+    case 1: hipLaunchKernelGGL(td_flux_residual_inject_multi_kernel<1>, grid, block, 0, stream, h, ldh, p, rows, D / 8); break;
+    case 2: hipLaunchKernelGGL(td_flux_residual_inject_multi_kernel<2>, grid, block, 0, stream, h, ldh, p, rows, D / 8); break;
+    case 3: hipLaunchKernelGGL(td_flux_residual_inject_multi_kernel<3>, grid, block, 0, stream, h, ldh, p, rows, D / 8); break;
+    default: hipLaunchKernelGGL(td_flux_residual_inject_multi_kernel<4>, grid, block, 0, stream, h, ldh, p, rows, D / 8); break;
+  }
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream) {
   TD_CHECK_ARG(n > 0 && n % 8 == 0, "td_euler_step: n=%lld must be a positive multiple of 8", n);
   TD_GRID_1D_I32(nblk, n / 8, 256, "td_euler_step");

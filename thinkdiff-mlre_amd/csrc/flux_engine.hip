@@ -25,7 +25,8 @@
 // image's context: workspace, conditioning, schedule, history, trace).  csrc/flux_model.hip holds everything that touches only the model;
 // this file holds everything that runs on a context: create / fork / destroy, conditioning, schedule, the forward, the denoise loops, the trace.
 // A ControlNet side network (td_flux_controlnet_*) is a second KIND of model run by the same block loop (run_blocks): its contexts keep block
-// samples, and a main context with one attached adds them behind its own blocks (td_flux_attach_controlnet, td_flux_residual_inject_bf16).
+// samples, and a main context with one attached adds them behind its own blocks (td_flux_attach_controlnet, td_flux_residual_inject_bf16); with up
+// to TD_MAX_CONTROLNETS attached it adds their bf16 sum, one launch per block (td_flux_attach_controlnets, td_flux_residual_inject_multi_bf16).
 // IP-Adapter slots (td_flux_ip_adapter_*: the model's; td_flux_set_ip_image_embeds: a context's image prompt -> tokens and every double block's
 // K / V, once per image) add, inside a double block, td_ip_attention of the image rows' un-rotated query and one add behind the FF.
 // The first-block cache (td_flux_set_block_cache*; kernels in csrc/block_cache.hip) decides behind double block 0 whether the forward runs its
@@ -365,12 +366,23 @@ int td_flux_controlnet_create(const TdFluxConfig* cfg, int num_mode, int max_img
   return rc;
 }
 
+// Take ControlNet context `cn` out of main context `o`'s list: the nets behind it move up with their scale tables.
+static void detach_one(td_flux* o, td_flux* cn) {
+  int k = 0;
+  while (k < o->n_cn && o->cns[k] != cn) ++k;
+  if (k == o->n_cn) return;
+  for (; k + 1 < o->n_cn; ++k) { o->cns[k] = o->cns[k + 1]; o->cn_scales[k].swap(o->cn_scales[k + 1]); }
+  o->cns[--o->n_cn] = nullptr;
+  o->cn_scales[o->n_cn].clear();
+  cn->cn_owner = nullptr;
+}
+
 // The root context frees the model: it must outlive its forks.
 void td_flux_destroy(td_flux* f) {
   if (!f) return;
   for (hipEvent_t ev : f->ev_pool) (void)hipEventDestroy(ev);
-  if (f->cn) f->cn->cn_owner = nullptr;            // either end of an attachment may go first
-  if (f->cn_owner) f->cn_owner->cn = nullptr;
+  for (int k = 0; k < f->n_cn; ++k) f->cns[k]->cn_owner = nullptr;      // either end of an attachment may go first
+  if (f->cn_owner) detach_one(f->cn_owner, f);
   if (f->root) flux_model_destroy(f->m);
   for (td_flux::IpCtx& c : f->ip) if (c.buf) (void)hipFree(c.buf);
   if (f->ip_out) (void)hipFree(f->ip_out);
@@ -798,7 +810,9 @@ int td_flux_controlnet_forward(td_flux* cn, const void* latents, int step, void*
 // One transformer evaluation: velocity[S_img, out_channels] = FluxTransformer2DModel(latents; step).  With a ControlNet context attached and a
 // non-zero conditioning scale at this step ([ext] diffusers FluxControlNetPipeline's loop body): first the ControlNet on the same latents, step
 // and stream, then the blocks with   hidden = hidden + bf16(scale * sample[i / ceil(n_blocks / n_samples)])   behind each, image rows only.
-// With nothing attached, or scale 0 (h + 0 is h), exactly the launches of the plain forward.
+// With several attached (td_flux_attach_controlnets) the nets whose scale is not 0 run one after another and ONE launch behind each block adds the
+// bf16 left fold of their scaled samples (td_flux_residual_inject_multi_bf16).  With nothing attached, or every scale 0 (h + 0 is h), exactly the
+// launches of the plain forward.
 int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, void* stream) {
   TD_CHECK_ARG(f && latents && velocity, "td_flux_forward: null argument");
   FluxModel* const m = f->m;
@@ -811,38 +825,62 @@ int td_flux_forward(td_flux* f, const void* latents, int step, void* velocity, v
                  "context (td_flux_ip_adapter_load_param / _remove; its K / V are values of the old ones): set the image embeds again, or clear them", a);
     TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: IP-Adapter slot %d holds an image prompt and the context %d reference tokens (the image rows would include "
                  "the reference rows): that pairing is not built", a, f->S_ref);
-    TD_CHECK_ARG(!f->cn, "td_flux_forward: IP-Adapter slot %d holds an image prompt and a ControlNet is attached: that pairing is not built", a);
+    TD_CHECK_ARG(f->n_cn == 0, "td_flux_forward: IP-Adapter slot %d holds an image prompt and a ControlNet is attached: that pairing is not built", a);
   }
   if (m->bc_mode != 0) {
-    TD_CHECK_ARG(!f->cn, "td_flux_forward: the first-block cache is on (mode %d) and a ControlNet is attached (its samples are added behind every block, "
+    TD_CHECK_ARG(f->n_cn == 0, "td_flux_forward: the first-block cache is on (mode %d) and a ControlNet is attached (its samples are added behind every block, "
                  "a skipped forward runs one): that pairing is not built", m->bc_mode);
     TD_CHECK_ARG(m->cfg.num_layers > 0, "td_flux_forward: the first-block cache is on (mode %d) and the model has no double-stream block to decide behind", m->bc_mode);
     TD_TRY(block_cache_prepare(f));
   }
   hipStream_t s = (hipStream_t)stream;
-  td_flux* const cn = f->cn;
-  const float sc = cn ? ((size_t)step < f->cn_scales.size() ? f->cn_scales[step] : 1.0f) : 0.0f;
-  if (!cn || sc == 0.0f) return run_blocks(f, latents, step, velocity, nullptr, s);
-  const FluxModel* c = cn->m;
-  TD_CHECK_ARG(c->D == m->D && c->cfg.num_heads == m->cfg.num_heads, "td_flux_forward: the attached ControlNet has inner width %d (%d heads), the transformer %d (%d heads)",
-               c->D, c->cfg.num_heads, m->D, m->cfg.num_heads);
-  TD_CHECK_ARG(m->Ccond == 0, "td_flux_forward: a ControlNet is attached to a channel-conditioned transformer (in_channels=%d, out_channels=%d): that pairing "
-               "is not built", m->Cin, m->Cout);
-  TD_CHECK_ARG(c->Cin == m->Cout, "td_flux_forward: the attached ControlNet reads %d latent channels, the transformer steps %d", c->Cin, m->Cout);
-  TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: a ControlNet is attached and the context holds %d reference tokens: a ControlNet together with reference tokens "
-               "is not built", f->S_ref);
-  TD_CHECK_ARG(cn->cond_set && cn->S_img == f->S_img, "td_flux_forward: the attached ControlNet context is prepared for %d image tokens, this context for %d "
-               "(td_flux_set_condition on both, per image)", cn->cond_set ? cn->S_img : 0, f->S_img);
-  TD_CHECK_ARG(cn->n_steps == f->n_steps, "td_flux_forward: the attached ControlNet context is prepared for %d timesteps, this context for %d", cn->n_steps, f->n_steps);
-  cn->attn_variant = f->attn_variant; cn->shared_chip = f->shared_chip;      // images in flight: the side network's kernels follow its image's
-  TD_TRY(controlnet_forward("td_flux_forward(attached ControlNet)", cn, latents, step, s));
-  const int D = m->D, L = m->cfg.num_layers, Ls = m->cfg.num_single_layers, nd = c->cfg.num_layers, ns = c->cfg.num_single_layers;
-  const int per_d = (L + nd - 1) / nd, per_s = ns > 0 ? (Ls + ns - 1) / ns : 0;      // ceil(L / n_d), ceil(Ls / n_s): trailing samples may stay unused
+  // the nets that take part in this step, in list order: scale != 0 (a net at scale 0 is neither run nor folded)
+  td_flux* act[TD_MAX_CONTROLNETS];
+  float sc[TD_MAX_CONTROLNETS];
+  int idx[TD_MAX_CONTROLNETS], n_act = 0;
+  for (int k = 0; k < f->n_cn; ++k) {
+    const float v = (size_t)step < f->cn_scales[k].size() ? f->cn_scales[k][step] : 1.0f;
+    if (v == 0.0f) continue;
+    td_flux* const cn = f->cns[k];
+    const FluxModel* c = cn->m;
+    TD_CHECK_ARG(c->D == m->D && c->cfg.num_heads == m->cfg.num_heads, "td_flux_forward: the attached ControlNet %d has inner width %d (%d heads), the transformer "
+                 "%d (%d heads)", k, c->D, c->cfg.num_heads, m->D, m->cfg.num_heads);
+    TD_CHECK_ARG(m->Ccond == 0, "td_flux_forward: a ControlNet (%d) is attached to a channel-conditioned transformer (in_channels=%d, out_channels=%d): that pairing "
+                 "is not built", k, m->Cin, m->Cout);
+    TD_CHECK_ARG(c->Cin == m->Cout, "td_flux_forward: the attached ControlNet %d reads %d latent channels, the transformer steps %d", k, c->Cin, m->Cout);
+    TD_CHECK_ARG(f->S_ref == 0, "td_flux_forward: a ControlNet (%d) is attached and the context holds %d reference tokens: a ControlNet together with reference "
+                 "tokens is not built", k, f->S_ref);
+    TD_CHECK_ARG(cn->cond_set && cn->S_img == f->S_img, "td_flux_forward: the attached ControlNet context %d is prepared for %d image tokens, this context for %d "
+                 "(td_flux_set_condition on both, per image)", k, cn->cond_set ? cn->S_img : 0, f->S_img);
+    TD_CHECK_ARG(cn->n_steps == f->n_steps, "td_flux_forward: the attached ControlNet context %d is prepared for %d timesteps, this context for %d", k, cn->n_steps,
+                 f->n_steps);
+    act[n_act] = cn; sc[n_act] = v; idx[n_act++] = k;
+  }
+  if (n_act == 0) return run_blocks(f, latents, step, velocity, nullptr, s);
+  for (int a = 0; a < n_act; ++a) {      // one after another on the same latents, step and stream; each into its own arena
+    char fn[64];
+    snprintf(fn, sizeof(fn), "td_flux_forward(attached ControlNet %d)", idx[a]);
+    act[a]->attn_variant = f->attn_variant; act[a]->shared_chip = f->shared_chip;      // images in flight: the side network's kernels follow its image's
+    TD_TRY(controlnet_forward(fn, act[a], latents, step, s));
+  }
+  // behind block i: net a's sample i / ceil(n_blocks / n_samples_a) -- every net by ITS OWN counts; trailing samples may stay unused, and a net
+  // without single blocks takes no part behind the single blocks.  One launch over the nets that take part (one net: the single-net kernel).
+  const int D = m->D, L = m->cfg.num_layers, Ls = m->cfg.num_single_layers;
   bf16_t* h_img = f->h + (size_t)f->T * D;
   const BlockHook inject = [&](bool single, int i) {
-    if (single && ns == 0) return (int)TD_OK;
+    const bf16_t* r[TD_MAX_CONTROLNETS];
+    int ld[TD_MAX_CONTROLNETS], n = 0;
+    float w[TD_MAX_CONTROLNETS];
+    for (int a = 0; a < n_act; ++a) {
+      const int nd = act[a]->m->cfg.num_layers, ns = act[a]->m->cfg.num_single_layers;
+      if (single && ns == 0) continue;
+      const int per = single ? (Ls + ns - 1) / ns : (L + nd - 1) / nd;
+      r[n] = cn_sample(act[a], single ? nd + i / per : i / per); ld[n] = D; w[n++] = sc[a];
+    }
+    if (n == 0) return (int)TD_OK;
     TraceScope ts(f, s, TD_TRACE_NORM, 0.0);
-    return td_flux_residual_inject_launch(h_img, D, cn_sample(cn, single ? nd + i / per_s : i / per_d), D, f->S_img, D, sc, s);
+    if (n == 1) return td_flux_residual_inject_launch(h_img, D, r[0], D, f->S_img, D, w[0], s);
+    return td_flux_residual_inject_multi_launch(h_img, D, r, ld, w, n, f->S_img, D, s);
   };
   return run_blocks(f, latents, step, velocity, &inject, s);
 }
@@ -893,31 +931,60 @@ int td_flux_controlnet_read_sample(const td_flux* cn, int k, void* dst, void* st
   return TD_OK;
 }
 
-// One ControlNet context per main context, one main context per ControlNet context; cn == NULL detaches.  The scales return to 1.0.
-int td_flux_attach_controlnet(td_flux* f, td_flux* cn) {
-  TD_CHECK_ARG(f, "td_flux_attach_controlnet: null context");
-  TD_CHECK_ARG(!f->m->controlnet, "td_flux_attach_controlnet: the first argument is a ControlNet context (attach a ControlNet TO a transformer context)");
-  if (cn) {
-    TD_CHECK_ARG(cn->m->controlnet, "td_flux_attach_controlnet: the second argument is not a ControlNet context (td_flux_controlnet_create makes one)");
-    TD_CHECK_ARG(!cn->cn_owner || cn->cn_owner == f, "td_flux_attach_controlnet: this ControlNet context already serves another main context (one at a time: "
-                 "fork the ControlNet, one fork per main context)");
+// ControlNet contexts cns[0 .. n) onto main context f, in list order; n = 0 detaches all.  One main context per ControlNet context.  Every scale
+// table returns to 1.0.  Nothing changes when a check fails.
+static int attach_controlnets(const char* fn, td_flux* f, td_flux* const* cns, int n) {
+  TD_CHECK_ARG(f, "%s: null context", fn);
+  TD_CHECK_ARG(n >= 0 && n <= TD_MAX_CONTROLNETS, "%s: n=%d ControlNets outside 0 .. %d", fn, n, TD_MAX_CONTROLNETS);
+  TD_CHECK_ARG(n == 0 || cns, "%s: null list of %d ControlNet contexts", fn, n);
+  for (int k = 0; k < n; ++k) {      // (the list itself first: no context is looked into before the list is sound)
+    TD_CHECK_ARG(cns[k], "%s: ControlNet context %d of %d is null", fn, k, n);
+    for (int j = 0; j < k; ++j)
+      TD_CHECK_ARG(cns[j] != cns[k], "%s: entries %d and %d are the same ControlNet context (each holds ONE mode, condition and sample arena: list a "
+                   "fork of it instead)", fn, j, k);
   }
-  if (f->cn) f->cn->cn_owner = nullptr;
-  f->cn = cn;
-  if (cn) cn->cn_owner = f;
-  f->cn_scales.clear();
+  TD_CHECK_ARG(!f->m->controlnet, "%s: the first argument is a ControlNet context (attach a ControlNet TO a transformer context)", fn);
+  for (int k = 0; k < n; ++k) {
+    td_flux* const cn = cns[k];
+    TD_CHECK_ARG(cn->m->controlnet, "%s: the second argument is not a ControlNet context (entry %d; td_flux_controlnet_create makes one)", fn, k);
+    TD_CHECK_ARG(!cn->cn_owner || cn->cn_owner == f, "%s: this ControlNet context (entry %d) already serves another main context (one at a time: "
+                 "fork the ControlNet, one fork per main context)", fn, k);
+  }
+  for (int k = 0; k < f->n_cn; ++k) { f->cns[k]->cn_owner = nullptr; f->cns[k] = nullptr; }
+  for (int k = 0; k < TD_MAX_CONTROLNETS; ++k) f->cn_scales[k].clear();
+  for (int k = 0; k < n; ++k) { f->cns[k] = cns[k]; cns[k]->cn_owner = f; }
+  f->n_cn = n;
   return TD_OK;
 }
 
-// conditioning scale of every prepared step (host floats; diffusers: controlnet_conditioning_scale x controlnet_keep[i]); steps beyond n keep 1.0
-int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n) {
-  TD_CHECK_ARG(f && n >= 0 && (n == 0 || scales), "td_flux_set_controlnet_scales: null argument");
-  TD_CHECK_ARG(!f->m->controlnet, "td_flux_set_controlnet_scales: the scales belong to the main context the ControlNet is attached to");
-  TD_CHECK_ARG(f->cn, "td_flux_set_controlnet_scales: no ControlNet is attached (td_flux_attach_controlnet)");
-  TD_CHECK_ARG(n <= f->m->max_steps, "td_flux_set_controlnet_scales: n=%d exceeds the %d steps of capacity", n, f->m->max_steps);
-  for (int i = 0; i < n; ++i) TD_CHECK_ARG(std::isfinite(scales[i]), "td_flux_set_controlnet_scales: scale %d is not finite", i);
-  f->cn_scales.assign(scales, scales + n);
+int td_flux_attach_controlnets(td_flux* f, td_flux* const* cns, int n) { return attach_controlnets("td_flux_attach_controlnets", f, cns, n); }
+
+// the n = 1 form; cn == NULL: the n = 0 form
+int td_flux_attach_controlnet(td_flux* f, td_flux* cn) { return attach_controlnets("td_flux_attach_controlnet", f, &cn, cn ? 1 : 0); }
+
+int td_flux_attached_controlnets(const td_flux* f, int* n) {
+  TD_CHECK_ARG(f && n, "td_flux_attached_controlnets: null argument");
+  *n = f->n_cn;
   return TD_OK;
+}
+
+// net k's conditioning scale of every prepared step (host floats; diffusers: controlnet_conditioning_scale[k] x controlnet_keep[i][k]); steps beyond n keep 1.0
+static int set_controlnet_scales(const char* fn, td_flux* f, int k, const float* scales, int n) {
+  TD_CHECK_ARG(f && n >= 0 && (n == 0 || scales), "%s: null argument", fn);
+  TD_CHECK_ARG(k >= 0 && k < TD_MAX_CONTROLNETS, "%s: ControlNet %d outside 0 .. %d", fn, k, TD_MAX_CONTROLNETS - 1);
+  TD_CHECK_ARG(!f->m->controlnet, "%s: the scales belong to the main context the ControlNet is attached to", fn);
+  TD_CHECK_ARG(f->n_cn > 0, "%s: no ControlNet is attached (td_flux_attach_controlnet)", fn);
+  TD_CHECK_ARG(k < f->n_cn, "%s: ControlNet %d outside the %d attached", fn, k, f->n_cn);
+  TD_CHECK_ARG(n <= f->m->max_steps, "%s: n=%d exceeds the %d steps of capacity", fn, n, f->m->max_steps);
+  for (int i = 0; i < n; ++i) TD_CHECK_ARG(std::isfinite(scales[i]), "%s: scale %d is not finite", fn, i);
+  f->cn_scales[k].assign(scales, scales + n);
+  return TD_OK;
+}
+
+int td_flux_set_controlnet_scales(td_flux* f, const float* scales, int n) { return set_controlnet_scales("td_flux_set_controlnet_scales", f, 0, scales, n); }
+
+int td_flux_set_controlnet_scales_at(td_flux* f, int k, const float* scales, int n) {
+  return set_controlnet_scales("td_flux_set_controlnet_scales_at", f, k, scales, n);
 }
 
 // The image prompt of one image for IP-Adapter slot `slot` on THIS context (include/thinkdiff_hip.h spells the arithmetic): the projection and the

@@ -221,9 +221,11 @@ struct td_flux {
   bf16_t *cn_E = nullptr, *cn_samples = nullptr;
   bool cn_cond_set = false;
   td_flux* cn_owner = nullptr;
-  // On a main context: the attached ControlNet context and the conditioning scale of every prepared step (host floats; missing entries are 1.0)
-  td_flux* cn = nullptr;
-  std::vector<float> cn_scales;
+  // On a main context: the attached ControlNet contexts cns[0 .. n_cn) in list order (td_flux_attach_controlnets) and, per net, the conditioning
+  // scale of every prepared step (host floats; missing entries are 1.0)
+  td_flux* cns[TD_MAX_CONTROLNETS] = {};
+  int n_cn = 0;
+  std::vector<float> cn_scales[TD_MAX_CONTROLNETS];
   // ---- IP-Adapter: per slot the image-prompt tokens of THIS image and every double block's K / V of them (td_flux_set_ip_image_embeds; one
   // allocation per slot, made at first use and grown when a later call needs more): staging [n_img, E_pad] | projection [n_img, num_tokens J] |
   // tokens [n_keys, J] | kv [L][K, V][keys_pad][D] (rows n_keys .. keys_pad zero).  ip_out [max_img, D]: the sum over the active slots of one

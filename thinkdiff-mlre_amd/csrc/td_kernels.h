@@ -207,6 +207,10 @@ int td_temb_combine_silu_launch(const bf16_t* te, const bf16_t* ge, const bf16_t
 int td_euler_step_launch(bf16_t* x, const bf16_t* v, float dt, long long n, hipStream_t stream);
 int td_flux_cfg_step_launch(bf16_t* x, const bf16_t* v_pos, const bf16_t* v_neg, float scale, float dt, long long n, hipStream_t stream);
 int td_flux_residual_inject_launch(bf16_t* h, int ldh, const bf16_t* r, int ldr, int rows, int D, float scale, hipStream_t stream);
+// n in 1 .. TD_MAX_CONTROLNETS samples folded in bf16, then added to h once (td_flux_residual_inject_multi_bf16 documents the rounding); r, ldr and
+// scales are HOST arrays of n entries, passed on to the kernel by value
+int td_flux_residual_inject_multi_launch(bf16_t* h, int ldh, const bf16_t* const* r, const int* ldr, const float* scales, int n, int rows, int D,
+                                         hipStream_t stream);
 // csrc/block_cache.hip: the first-block cache's residual + deterministic metric sums, and its tail difference (td_block_cache_*_bf16 document both)
 int td_block_cache_head_launch(const bf16_t* h1, int ld1, const bf16_t* h0, int ld0, const bf16_t* r_prev, int ldp, bf16_t* r, int ldr, int rows, int D,
                                double* sums, double* ws, hipStream_t stream);

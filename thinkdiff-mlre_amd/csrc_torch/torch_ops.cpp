@@ -163,6 +163,26 @@ at::Tensor& flux_residual_inject_(at::Tensor& h, const at::Tensor& r, double sca
   return h;
 }
 
+// The same for several ControlNets: h[:, :D] += fold_k bf16(scales[k] * r[k][:, :D]), the fold a bf16 left fold in list order, one launch
+// (td_flux_residual_inject_multi_bf16).  1 .. 4 tensors of one width D, each a 2-D view with innermost stride 1 and its own row stride.
+at::Tensor& flux_residual_inject_multi_(at::Tensor& h, at::TensorList r, at::ArrayRef<double> scales) {
+  check_rows(h, "h");
+  TORCH_CHECK(r.size() >= 1 && r.size() <= TD_MAX_CONTROLNETS && r.size() == scales.size(),
+              "thinkdiff_hip::flux_residual_inject_multi_: 1 .. ", TD_MAX_CONTROLNETS, " tensors and as many scales, got ", r.size(), " and ", scales.size());
+  const void* ptr[TD_MAX_CONTROLNETS];
+  int64_t ld[TD_MAX_CONTROLNETS];
+  float sc[TD_MAX_CONTROLNETS];
+  for (size_t k = 0; k < r.size(); ++k) {
+    check_rows(r[k], "r[k]"); same_device(r[k], "r[k]", h);
+    TORCH_CHECK(h.dim() == 2 && r[k].dim() == 2 && r[k].size(0) == h.size(0) && r[k].size(1) <= h.size(1) && h.size(0) > 0 && r[k].size(1) > 0 &&
+                r[k].size(1) == r[0].size(1), "thinkdiff_hip::flux_residual_inject_multi_: h [rows, >= D], every r[k] [rows, D] with the same row count and width");
+    ptr[k] = r[k].data_ptr(); ld[k] = r[k].stride(0); sc[k] = (float)scales[k];
+  }
+  DeviceGuard guard(h.device());
+  ok(td_flux_residual_inject_multi_bf16(h.data_ptr(), h.stride(0), ptr, ld, sc, (int)r.size(), (int)h.size(0), (int)r[0].size(1), stream_of(h)));
+  return h;
+}
+
 // First-block cache, the residual and its metric sums (td_block_cache_head_bf16): h1, h0 [rows, D] and the optional r_prev, 2-D views with innermost
 // stride 1 -> (r = bf16(h1 - h0) [rows, D], sums fp64 [2] = sum |r - r_prev|, sum |r_prev|; both 0 without r_prev).  Deterministic: no atomics.
 std::tuple<at::Tensor, at::Tensor> block_cache_head(const at::Tensor& h1, const at::Tensor& h0, const c10::optional<at::Tensor>& r_prev) {
@@ -702,6 +722,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_set_reference_tokens(int engine, Tensor ref_latents, Tensor ref_ids) -> ()");
   m.def("flux_cfg_step_(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)");
   m.def("flux_residual_inject_(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)");
+  m.def("flux_residual_inject_multi_(Tensor(a!) h, Tensor[] r, float[] scales) -> Tensor(a!)");
   m.def("block_cache_head(Tensor h1, Tensor h0, Tensor? r_prev) -> (Tensor, Tensor)");
   m.def("block_cache_tail(Tensor a, Tensor b) -> Tensor");
   m.def("flux_denoise_cfg_(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)");
@@ -748,6 +769,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_set_reference_tokens", &flux_set_reference_tokens);
   m.impl("flux_cfg_step_", &flux_cfg_step_);
   m.impl("flux_residual_inject_", &flux_residual_inject_);
+  m.impl("flux_residual_inject_multi_", &flux_residual_inject_multi_);
   m.impl("block_cache_head", &block_cache_head);
   m.impl("block_cache_tail", &block_cache_tail);
   m.impl("flux_denoise_cfg_", &flux_denoise_cfg_);

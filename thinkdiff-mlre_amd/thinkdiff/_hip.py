@@ -68,6 +68,10 @@ def _declare(L):
         "td_flux_controlnet_read_sample": [vp, i32, vp, vp],
         "td_flux_attach_controlnet": [vp, vp],
         "td_flux_set_controlnet_scales": [vp, vp, i32],
+        "td_flux_attach_controlnets": [vp, vp, i32],
+        "td_flux_set_controlnet_scales_at": [vp, i32, vp, i32],
+        "td_flux_attached_controlnets": [vp, vp],
+        "td_flux_residual_inject_multi_bf16": [vp, i64, vp, vp, vp, i32, i32, i32, vp],
         "td_flux_inpaint_mask": [vp, i32, i32, i32, i32, vp, vp],
         "td_flux_pack_latents": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
         "td_cls_avgpool2_bf16": [vp, vp, i32, i32, vp],

@@ -3,7 +3,7 @@ from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import BlipVisionT5DecoderForConditionalGeneration, build_vision_projector
 from .flux_control import FluxControlPipelineRewritePrompt
-from .flux_controlnet import FluxControlNetConfig, FluxControlNetModel, FluxControlNetPipelineRewritePrompt
+from .flux_controlnet import FluxControlNetConfig, FluxControlNetModel, FluxControlNetPipelineRewritePrompt, FluxMultiControlNetModel
 from .flux_fill import FluxFillPipelineRewritePrompt
 from .flux_img2img import FluxImg2ImgPipelineRewritePrompt
 from .flux_inpaint import FluxInpaintPipelineRewritePrompt
@@ -18,6 +18,6 @@ from .qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
 __all__ = ["registry", "BaseModel", "BlipVisionT5DecoderForConditionalGeneration", "build_vision_projector",
            "FluxPipelineRewritePrompt", "FluxImg2ImgPipelineRewritePrompt", "FluxInpaintPipelineRewritePrompt",
            "FluxFillPipelineRewritePrompt", "FluxControlPipelineRewritePrompt", "FluxKontextPipelineRewritePrompt",
-           "FluxControlNetPipelineRewritePrompt", "FluxControlNetModel", "FluxControlNetConfig",
+           "FluxControlNetPipelineRewritePrompt", "FluxControlNetModel", "FluxControlNetConfig", "FluxMultiControlNetModel",
            "FluxTransformer2DModel", "FluxTransformerConfig", "FirstBlockCacheConfig", "apply_first_block_cache",
            "FluxPriorReduxPipelineRewritePrompt", "ReduxImageEncoder"]

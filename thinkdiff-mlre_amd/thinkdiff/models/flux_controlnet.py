@@ -41,9 +41,29 @@ Notation: D = heads x 128; the main transformer has L double and Ls single block
   call whose scales are all 0 is the plain text-to-image loop on the same latents.
 - Images in flight advance through the existing `denoise_multi`: one (transformer fork, ControlNet fork) pair per image.
 
+`FluxMultiControlNetModel(nets)` ([ext] controlnet_flux.py `FluxMultiControlNetModel.forward`, pipeline_flux_controlnet.py), 1 to 4 nets, as
+`controlnet=` of the pipeline
+- `control_image` is a list of K entries, each whatever the single-net pipeline takes; `control_mode` a list of K (None for a net without a
+  mode embedder); `controlnet_conditioning_scale`, `control_guidance_start`, `control_guidance_end` each one number for all nets or a list
+  of K.  Net k's table is `scale_k * keep_k[i]` (`controlnet_scale_tables`).  The generator gives the control images their eps net by net in
+  list order, then the noise.
+- At one step, for the nets k = 0 .. K-1 in list order with scale c_k (a Python float: an fp32 operand of the bf16 multiply):
+      s_k[i] = bf16(c_k * sample_k[i]);   acc[i] = s_0[i];   acc[i] = bf16(float(acc[i]) + float(s_k[i]))  for k = 1 .. K-1
+      hidden = bf16(float(hidden) + float(acc[idx]))          (image rows, behind double block i / single block i)
+  a left fold with one rounding per add, THEN the add to the hidden state -- one kernel launch per block
+  (td_flux_residual_inject_multi_bf16), not K launches of the single-net kernel, which would compute bf16(bf16(h + a) + b).
+- **Deviation 1, per-net sample index**: each net uses its own rule `idx_k = i // ceil(n_blocks / n_samples_k)`; diffusers zips the nets'
+  sample lists and silently truncates when the counts differ (with equal counts the two agree).  A net without single blocks takes no
+  part in the single-block sums.
+- **Deviation 2, inactive nets are left out**: a net whose scale at the step is 0 is not run and is left out of the fold; diffusers runs it
+  and adds `bf16(0 * x)`, which can differ only in the sign of a zero.  A step at which every net's scale is 0 is the plain step.
+- The same `FluxControlNetModel` may appear more than once (a union checkpoint under two modes, two control images): each appearance
+  runs on its own fork; with images in flight every transformer context is paired with K ControlNet forks.
+
 Refused, not approximated, each naming what was asked: `conditioning_embedding_channels` / `input_hint_block` (the XLabs pixel-hint
-form) and with it `controlnet_blocks_repeat`; lists of ControlNets (`FluxMultiControlNetModel`) and per-ControlNet lists of scales,
-starts or ends; everything flux_control.py refuses (`callback_on_step_end`, custom `sigmas`, lists of generators,
+form) and with it `controlnet_blocks_repeat`; a raw Python list as `controlnet=` and per-ControlNet lists given with a single
+`FluxControlNetModel` (both point at `FluxMultiControlNetModel([...])`); more than 4 nets, lists of the wrong length, a union net without
+its mode; everything flux_control.py refuses (`callback_on_step_end`, custom `sigmas`, lists of generators,
 `joint_attention_kwargs`); a ControlNet together with reference tokens, or on a channel-conditioned transformer; 8-bit precision setters
 and LoRA ON THE CONTROLNET MODEL (the main transformer may be in any mode, and may carry adapters); a transformer whose first-block cache
 is enabled (`ValueError`; the engine refuses the same pairing at the forward).
@@ -187,26 +207,81 @@ class FluxControlNetModel(FluxTransformer2DModel):
         return outs[:c.num_layers], outs[c.num_layers:]
 
 
+MAX_CONTROLNETS = 4      # TD_MAX_CONTROLNETS of include/thinkdiff_hip.h
+
+
+class FluxMultiControlNetModel:
+    """[ext] diffusers `FluxMultiControlNetModel(nets)`: 1 to 4 `FluxControlNetModel`s whose scaled samples are summed, in list order, before
+    they meet the transformer's hidden state.  It owns no weights and no engine context: it is the list, and the only way to the multi
+    form of `FluxControlNetPipelineRewritePrompt`.  The same model may appear more than once (one union checkpoint under two modes):
+    every appearance runs on its own fork."""
+
+    def __init__(self, nets):
+        if isinstance(nets, FluxControlNetModel):
+            nets = [nets]
+        nets = list(nets)
+        if not 1 <= len(nets) <= MAX_CONTROLNETS:
+            raise ValueError(f"FluxMultiControlNetModel takes 1 to {MAX_CONTROLNETS} ControlNets, got {len(nets)}")
+        for k, m in enumerate(nets):
+            if not isinstance(m, FluxControlNetModel):
+                raise ValueError(f"FluxMultiControlNetModel: entry {k} is a {type(m).__name__}, not a FluxControlNetModel")
+        self.nets = nets
+
+    def __len__(self):
+        return len(self.nets)
+
+    def __iter__(self):
+        return iter(self.nets)
+
+    def __getitem__(self, k):
+        return self.nets[k]
+
+
+_USE_MULTI = "that form goes with controlnet=FluxMultiControlNetModel([...]); with one FluxControlNetModel"
+
+
 def _one_number(name: str, v) -> float:
     if isinstance(v, (list, tuple)):
-        raise NotImplementedError(f"{name} = {v!r}: per-ControlNet lists belong to FluxMultiControlNetModel, which is not built; pass one number")
+        raise NotImplementedError(f"{name} = {v!r}: per-ControlNet lists: {_USE_MULTI} pass one number")
     return float(v)
 
 
+def _per_net(name: str, v, K: int) -> list:
+    """One entry per ControlNet: a list / tuple of exactly K, or one value for all of them."""
+    if isinstance(v, (list, tuple)):
+        if len(v) != K:
+            raise ValueError(f"{name} has {len(v)} entries for {K} ControlNets: pass one per ControlNet, in the order of FluxMultiControlNetModel([...])"
+                             + ("" if name in ("control_image", "control_mode") else ", or one number for all"))
+        return list(v)
+    return [v] * K
+
+
+def controlnet_scale_tables(n: int, K: int, conditioning_scale=1.0, start=0.0, end=1.0) -> List[List[float]]:
+    """[ext] pipeline_flux_controlnet.py with a FluxMultiControlNetModel: net k's table is `scale_k * keep_k[i]`,
+    `keep_k[i] = 1.0 - float(i / n < start_k or (i + 1) / n > end_k)`; each argument one number for all nets or a list of K."""
+    sc, st, en = (_per_net(nm, v, K) for nm, v in (("controlnet_conditioning_scale", conditioning_scale), ("control_guidance_start", start),
+                                                   ("control_guidance_end", end)))
+    return [[float(sc[k]) * kp for kp in controlnet_keep(n, float(st[k]), float(en[k]))] for k in range(K)]
+
+
 class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
-    def __init__(self, *args, controlnet: Optional[FluxControlNetModel] = None, **kw):
+    def __init__(self, *args, controlnet=None, **kw):
         super().__init__(*args, **kw)
         if isinstance(controlnet, (list, tuple)):
-            raise NotImplementedError(f"controlnet is a list of {len(controlnet)} ControlNets: FluxMultiControlNetModel is not built; pass one FluxControlNetModel")
+            raise NotImplementedError(f"controlnet is a list of {len(controlnet)} ControlNets: a raw list is not taken, wrap it as FluxMultiControlNetModel([...])")
         self.controlnet = controlnet
-        self._cn_pool = []
+        self._cn_pool, self._cn_pool_key = [], None
 
     def _controlnet_contexts(self, n: int):
-        """The ControlNet plus n - 1 forks (created once): one per transformer context of `_contexts`."""
-        if not self._cn_pool or self._cn_pool[0] is not self.controlnet:
-            self._cn_pool = [self.controlnet]
+        """n rows, one per transformer context of `_contexts`, each holding one ControlNet context per net of the list (created once).
+        Row 0 holds the models themselves -- except a model's second appearance in the list, which is a fork like every entry of the
+        later rows: one context holds one mode, one control condition and one sample arena."""
+        nets = list(self.controlnet.nets) if isinstance(self.controlnet, FluxMultiControlNetModel) else [self.controlnet]
+        key = tuple(id(m) for m in nets)
+        if self._cn_pool_key != key:
+            self._cn_pool, self._cn_pool_key = [[m if all(m is not o for o in nets[:k]) else m.fork() for k, m in enumerate(nets)]], key
         while len(self._cn_pool) < n:
-            self._cn_pool.append(self.controlnet.fork())
+            self._cn_pool.append([m.fork() for m in nets])
         return self._cn_pool[:n]
 
     @torch.no_grad()
@@ -219,26 +294,47 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
         refuse_unsupported(name, generator, kw)
         tr, cn = self.transformer, self.controlnet
         if isinstance(cn, (list, tuple)):
-            raise NotImplementedError(f"controlnet is a list of {len(cn)} ControlNets: FluxMultiControlNetModel is not built; pass one FluxControlNetModel")
-        if not isinstance(cn, FluxControlNetModel):
-            raise ValueError(f"{name} needs controlnet= a FluxControlNetModel, got {type(cn).__name__}")
-        scale = _one_number("controlnet_conditioning_scale", controlnet_conditioning_scale)
-        start = _one_number("control_guidance_start", control_guidance_start)
-        end = _one_number("control_guidance_end", control_guidance_end)
-        if isinstance(control_mode, (list, tuple)):
-            raise NotImplementedError(f"control_mode = {control_mode!r}: per-ControlNet lists belong to FluxMultiControlNetModel, which is not built")
-        if isinstance(control_image, (list, tuple)) and control_image and isinstance(control_image[0], (list, tuple)):
-            raise NotImplementedError("control_image is a list of lists (one per ControlNet): FluxMultiControlNetModel is not built")
-        if cn.union and control_mode is None:
-            raise ValueError(f"this ControlNet is a union model (num_mode = {cn.config.num_mode}): control_mode is required")
-        if not cn.union and control_mode is not None:
-            raise ValueError(f"control_mode = {control_mode} on a ControlNet without a mode embedder (num_mode is not set)")
-        if cn.union and not 0 <= int(control_mode) < cn.config.num_mode:
-            raise ValueError(f"control_mode = {control_mode} outside the {cn.config.num_mode} modes of this ControlNet")
-        if start > end:
-            raise ValueError(f"control_guidance_start = {start} exceeds control_guidance_end = {end}")
-        if start < 0.0 or end > 1.0:
-            raise ValueError(f"control_guidance_start = {start} / control_guidance_end = {end} outside [0, 1]")
+            raise NotImplementedError(f"controlnet is a list of {len(cn)} ControlNets: a raw list is not taken, wrap it as FluxMultiControlNetModel([...])")
+        multi = isinstance(cn, FluxMultiControlNetModel)
+        if not multi and not isinstance(cn, FluxControlNetModel):
+            raise ValueError(f"{name} needs controlnet= a FluxControlNetModel or a FluxMultiControlNetModel, got {type(cn).__name__}")
+        if multi:
+            nets = list(cn.nets)
+            K = len(nets)
+            if K > MAX_CONTROLNETS:
+                raise ValueError(f"{K} ControlNets: FluxMultiControlNetModel takes 1 to {MAX_CONTROLNETS}")
+            if control_image is not None and not isinstance(control_image, (list, tuple)):
+                raise ValueError(f"control_image must be a list of {K} entries, one per ControlNet of FluxMultiControlNetModel([...]), got {type(control_image).__name__}")
+            images = _per_net("control_image", control_image, K) if control_image is not None else None
+            if control_mode is not None and not isinstance(control_mode, (list, tuple)):
+                raise ValueError(f"control_mode = {control_mode!r} must be a list of {K} entries, one per ControlNet (None for a net without a mode embedder)")
+            modes = _per_net("control_mode", control_mode, K)
+            scale_l = [float(v) for v in _per_net("controlnet_conditioning_scale", controlnet_conditioning_scale, K)]
+            start_l = [float(v) for v in _per_net("control_guidance_start", control_guidance_start, K)]
+            end_l = [float(v) for v in _per_net("control_guidance_end", control_guidance_end, K)]
+        else:
+            nets, K = [cn], 1
+            scale_l = [_one_number("controlnet_conditioning_scale", controlnet_conditioning_scale)]
+            start_l = [_one_number("control_guidance_start", control_guidance_start)]
+            end_l = [_one_number("control_guidance_end", control_guidance_end)]
+            if isinstance(control_mode, (list, tuple)):
+                raise NotImplementedError(f"control_mode = {control_mode!r}: per-ControlNet lists: {_USE_MULTI} pass one mode")
+            if isinstance(control_image, (list, tuple)) and control_image and isinstance(control_image[0], (list, tuple)):
+                raise NotImplementedError(f"control_image is a list of lists (one per ControlNet): {_USE_MULTI} pass its images alone")
+            images, modes = ([control_image] if control_image is not None else None), [control_mode]
+        for k, m in enumerate(nets):
+            tag = f"ControlNet {k} of {K}: " if multi else ""
+            mode, start, end = modes[k], start_l[k], end_l[k]
+            if m.union and mode is None:
+                raise ValueError(f"{tag}this ControlNet is a union model (num_mode = {m.config.num_mode}): control_mode is required")
+            if not m.union and mode is not None:
+                raise ValueError(f"{tag}control_mode = {mode} on a ControlNet without a mode embedder (num_mode is not set)")
+            if m.union and not 0 <= int(mode) < m.config.num_mode:
+                raise ValueError(f"{tag}control_mode = {mode} outside the {m.config.num_mode} modes of this ControlNet")
+            if start > end:
+                raise ValueError(f"{tag}control_guidance_start = {start} exceeds control_guidance_end = {end}")
+            if start < 0.0 or end > 1.0:
+                raise ValueError(f"{tag}control_guidance_start = {start} / control_guidance_end = {end} outside [0, 1]")
         if getattr(tr, "is_cache_enabled", False):
             raise ValueError(f"{name}: the transformer's first-block cache is enabled and a ControlNet adds its samples behind every block (a skipped step "
                              "runs one block): that pairing is not built; call pipe.transformer.disable_cache() first")
@@ -246,65 +342,79 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
         if tr.config.cond_channels:
             raise NotImplementedError(f"a ControlNet on a channel-conditioned transformer (in_channels = {tr.config.in_channels}, out_channels = "
                                       f"{tr.config.latent_channels}) is not built")
-        if (tr.config.in_channels, cn.config.in_channels) != (c_lat, c_lat) or tr.config.inner_dim != cn.config.inner_dim:
-            raise ValueError(f"{name}: transformer (in_channels = {tr.config.in_channels}, inner width {tr.config.inner_dim}) and ControlNet (in_channels = "
-                             f"{cn.config.in_channels}, inner width {cn.config.inner_dim}) must agree, with {c_lat} latent channels")
+        for k, m in enumerate(nets):
+            if (tr.config.in_channels, m.config.in_channels) != (c_lat, c_lat) or tr.config.inner_dim != m.config.inner_dim:
+                raise ValueError(f"{name}: transformer (in_channels = {tr.config.in_channels}, inner width {tr.config.inner_dim}) and ControlNet"
+                                 f"{f' {k}' if multi else ''} (in_channels = {m.config.in_channels}, inner width {m.config.inner_dim}) must agree, with "
+                                 f"{c_lat} latent channels")
         height = int(height or self.default_sample_size * self.vae_scale_factor)
         width = int(width or self.default_sample_size * self.vae_scale_factor)
         if height % 16 or width % 16:
             raise ValueError(f"height and width must be multiples of 16, got {height} x {width}")
         if prompt is None and prompt_embeds is None:
             raise ValueError("Provide either `prompt` or `prompt_embeds`.")
-        if control_image is None:
+        if images is None:
             raise ValueError("Provide `control_image`.")
         c, h, w = c_lat // 4, height // 8, width // 8
         S_img = (h // 2) * (w // 2)
-        as_latents = isinstance(control_image, torch.Tensor) and control_image.dim() == 4 and control_image.shape[1] == c
-        if as_latents:
-            if tuple(control_image.shape[2:]) != (h, w):
-                raise ValueError(f"a {c}-channel control_image is taken as latents and must be [B, {c}, h, w] with (h, w) = {(h, w)}, "
-                                 f"got {tuple(control_image.shape)}")
-            n_ctrl = control_image.shape[0]
-        else:
-            imgs = self._image_list(control_image, height, width)
-            n_ctrl = len(imgs)
+        as_latents, imgs, n_ctrl = [], [], []
+        for k, ci in enumerate(images):
+            tag = f"control_image[{k}]: " if multi else ""
+            lat_k = isinstance(ci, torch.Tensor) and ci.dim() == 4 and ci.shape[1] == c
+            if lat_k:
+                if tuple(ci.shape[2:]) != (h, w):
+                    raise ValueError(f"{tag}a {c}-channel control_image is taken as latents and must be [B, {c}, h, w] with (h, w) = {(h, w)}, "
+                                     f"got {tuple(ci.shape)}")
+                imgs.append(None)
+                n_ctrl.append(ci.shape[0])
+            else:
+                if ci is None:
+                    raise ValueError(f"{tag}Provide `control_image`.")
+                imgs.append(self._image_list(ci, height, width))
+                n_ctrl.append(len(imgs[-1]))
+            as_latents.append(lat_k)
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
             num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length)
         B = prompt_embeds.shape[0] * num_images_per_prompt
-        if B % n_ctrl:
-            raise ValueError(f"cannot duplicate {n_ctrl} control images to the batch of {B} (prompts x num_images_per_prompt)")
+        for k in range(K):
+            if B % n_ctrl[k]:
+                raise ValueError(f"cannot duplicate {n_ctrl[k]} control images{f' of ControlNet {k}' if multi else ''} to the batch of {B} "
+                                 "(prompts x num_images_per_prompt)")
         if latents is not None and tuple(latents.shape) != (B, S_img, c_lat):
             raise ValueError(f"latents must be packed [B, S, {c_lat}] = {(B, S_img, c_lat)}, got {tuple(latents.shape)}")
-        if not as_latents and self.vae_encoder is None:
+        if not all(as_latents) and self.vae_encoder is None:
             raise _hip.ThinkDiffHipError("no VAE encoder loaded: build the pipeline with vae_encoder= (or from_pipe / from_pretrained)")
         dev = self._execution_device
-        # generator order: the control image's eps, then the noise
-        if as_latents:
-            ctrl = [_OPS.flux_pack_latents(control_image[i].to(dev, torch.bfloat16).contiguous()) for i in range(n_ctrl)]
-        else:
-            enc = self.vae_encoder
-            moments = [enc.encode_moments(im) for im in imgs]
-            eps = torch.randn((n_ctrl, c, h, w), generator=generator, device=dev, dtype=torch.bfloat16)
-            dist = DiagonalGaussianDistribution(moments, h, w)
-            ctrl = [dist.packed_latents(i, eps[i], None, 0.0, self.vae_scaling_factor, self.vae_shift_factor) for i in range(n_ctrl)]
+        # generator order: the control images' eps, net by net in list order, then the noise
+        ctrl = []
+        for k in range(K):
+            if as_latents[k]:
+                ctrl.append([_OPS.flux_pack_latents(images[k][i].to(dev, torch.bfloat16).contiguous()) for i in range(n_ctrl[k])])
+            else:
+                enc = self.vae_encoder
+                moments = [enc.encode_moments(im) for im in imgs[k]]
+                eps = torch.randn((n_ctrl[k], c, h, w), generator=generator, device=dev, dtype=torch.bfloat16)
+                dist = DiagonalGaussianDistribution(moments, h, w)
+                ctrl.append([dist.packed_latents(i, eps[i], None, 0.0, self.vae_scaling_factor, self.vae_shift_factor) for i in range(n_ctrl[k])])
         lat, _, _ = self.prepare_latents(B, height, width, generator, latents)
         sig = self.scheduler.sigmas(num_inference_steps, S_img)
         img_ids = self._prepare_latent_image_ids(h // 2, w // 2, lat.device)
         t_eff = [effective_scalar(float(s) * self.scheduler.num_train_timesteps, tr.dtype) for s in sig[:-1]]
         g_bf = float((torch.tensor([guidance_scale], dtype=torch.float32).to(tr.dtype) * 1000).float())
         g_eff = g_bf if tr.config.guidance_embeds else 0.0
-        scales = [scale * k for k in controlnet_keep(num_inference_steps, start, end)]
+        scales = controlnet_scale_tables(num_inference_steps, K, scale_l, start_l, end_l)
         control = None
-        if any(s != 0.0 for s in scales):      # all zero: every step is the plain step -- the text-to-image loop
-            control = dict(model=cn, conds=[ctrl[b % n_ctrl] for b in range(B)], scales=scales, mode=control_mode,
-                           g_eff=g_bf if cn.config.guidance_embeds else 0.0)
+        if any(s != 0.0 for tab in scales for s in tab):      # all zero: every step is the plain step -- the text-to-image loop
+            control = dict(conds=[[ctrl[k][b % n_ctrl[k]] for k in range(K)] for b in range(B)], scales=scales, modes=modes,
+                           g_eff=[g_bf if m.config.guidance_embeds else 0.0 for m in nets])
         xs = self._denoise_controlled(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff, control)
         return self._finish(xs, h, w, output_type, return_dict)
 
     def _denoise_controlled(self, lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff, control):
-        """`_denoise_groups` with one ControlNet context attached to every transformer context for the duration of the loop: the
-        ControlNet context gets the sample's prompt, pooled embeds, ids, control mode, control latents and the same schedule."""
+        """`_denoise_groups` with the ControlNet contexts of one row of `_controlnet_contexts` attached to every transformer context for the
+        duration of the loop: each ControlNet context gets the sample's prompt, pooled embeds, ids, ITS control mode and control latents and the
+        same schedule; the main context gets one scale table per net."""
         if control is None:
             return self._denoise_groups(lat, B, num_images_per_prompt, prompt_embeds, pooled_prompt_embeds, text_ids, img_ids, sig, t_eff, g_eff)
         G = max(1, min(int(self.images_in_flight), B))
@@ -315,7 +425,7 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
         xs = []
         try:
             for k in range(G):
-                ctxs[k].attach_controlnet(cns[k])
+                ctxs[k].attach_controlnets(cns[k])
             for b0 in range(0, B, G):
                 group = list(range(b0, min(b0 + G, B)))
                 lat_g = []
@@ -327,10 +437,11 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
                         pe, po = prompt_embeds[pb], pooled_prompt_embeds[min(pb, pooled_prompt_embeds.shape[0] - 1)]
                         ctxs[k].set_condition(pe, po, img_ids, text_ids)
                         ctxs[k].set_timesteps(t_eff, g_eff)
-                        ctxs[k].set_controlnet_scales(control["scales"])
-                        cns[k].set_condition(pe, po, img_ids, text_ids, control_mode=control["mode"])
-                        cns[k].set_control_condition(control["conds"][b])
-                        cns[k].set_timesteps(t_eff, control["g_eff"])
+                        for j, cnj in enumerate(cns[k]):
+                            ctxs[k].set_controlnet_scales(control["scales"][j], net=j)
+                            cnj.set_condition(pe, po, img_ids, text_ids, control_mode=control["modes"][j])
+                            cnj.set_control_condition(control["conds"][b][j])
+                            cnj.set_timesteps(t_eff, control["g_eff"][j])
                         lat_g.append(lat[b].contiguous())
                 if len(group) == 1:
                     with torch.cuda.stream(self._streams[0]):
@@ -342,5 +453,5 @@ class FluxControlNetPipelineRewritePrompt(FluxImg2ImgPipelineRewritePrompt):
                 xs.extend(lat_g)
         finally:
             for k in range(G):      # the transformer's contexts are shared with the other pipelines: leave them plain
-                ctxs[k].attach_controlnet(None)
+                ctxs[k].attach_controlnets([])
         return xs

@@ -471,10 +471,29 @@ class FluxTransformer2DModel:
         self._controlnet = controlnet      # (keeps the attached context alive)
         return self
 
-    def set_controlnet_scales(self, scales: Sequence[float]):
-        """The conditioning scale of every prepared step: `controlnet_conditioning_scale * controlnet_keep[i]` (0: the plain step)."""
+    def attach_controlnets(self, controlnets):
+        """Attach 0 .. 4 `FluxControlNetModel` contexts to THIS context, in list order (empty: detach all): at every step the nets whose
+        scale is not 0 run one after another and the bf16 left fold of their scaled samples is added behind each block, one launch
+        (td_flux_attach_controlnets).  The same context may not appear twice -- list forks of it.  Every scale table returns to 1.0."""
+        cns = list(controlnets)
+        arr = (ctypes.c_void_p * max(1, len(cns)))(*[c._h.value for c in cns])
+        _hip.check(self._L.td_flux_attach_controlnets(self._h, ctypes.cast(arr, ctypes.c_void_p), len(cns)))
+        self._controlnet = cns or None      # (keeps the attached contexts alive)
+        return self
+
+    def attached_controlnets(self) -> int:
+        n = ctypes.c_int()
+        _hip.check(self._L.td_flux_attached_controlnets(self._h, ctypes.byref(n)))
+        return n.value
+
+    def set_controlnet_scales(self, scales: Sequence[float], net: Optional[int] = None):
+        """The conditioning scale of every prepared step: `controlnet_conditioning_scale * controlnet_keep[i]` (0: the plain step);
+        `net`: which of the attached ControlNets (td_flux_set_controlnet_scales_at; None: the first)."""
         arr = (ctypes.c_float * max(1, len(scales)))(*[float(v) for v in scales])
-        _hip.check(self._L.td_flux_set_controlnet_scales(self._h, ctypes.cast(arr, ctypes.c_void_p), len(scales)))
+        if net is None:
+            _hip.check(self._L.td_flux_set_controlnet_scales(self._h, ctypes.cast(arr, ctypes.c_void_p), len(scales)))
+        else:
+            _hip.check(self._L.td_flux_set_controlnet_scales_at(self._h, int(net), ctypes.cast(arr, ctypes.c_void_p), len(scales)))
         return self
 
     # ---- IP-Adapter (thinkdiff.models.flux_ip_adapter; td_flux_ip_adapter_*) ------------------------------------

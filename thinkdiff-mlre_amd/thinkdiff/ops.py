@@ -32,6 +32,7 @@ flux_set_reference_tokens  FluxKontextPipeline's per-step torch.cat of the refer
 flux_cfg_step_             true classifier-free guidance (neg + scale * (pos - neg)) + scheduler.step, fused, in place
 flux_denoise_cfg_          the denoise loop under true CFG: both conditionings per step on two prepared contexts, then flux_cfg_step_
 flux_residual_inject_      FluxTransformer2DModel's `hidden_states + controlnet_block_samples[..]` with the ControlNet's `* conditioning_scale`, fused, in place
+flux_residual_inject_multi_   the same under FluxMultiControlNetModel: the scaled samples of 1 .. 4 ControlNets summed in bf16 in list order, then added, one launch
 block_cache_head / block_cache_tail   diffusers' First Block Cache arithmetic: the first block's residual with the two sums of its
                            `(r - r_prev).abs().mean() / r_prev.abs().mean()` test taken deterministically (no atomics), and the tail difference
 lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up to 8 pairs at once, fp32 accumulation, one rounding
@@ -78,6 +79,7 @@ SCHEMAS = {
     "flux_set_reference_tokens": "(int engine, Tensor ref_latents, Tensor ref_ids) -> ()",
     "flux_cfg_step_": "(Tensor(a!) x, Tensor v_pos, Tensor v_neg, float scale, float dt) -> Tensor(a!)",
     "flux_residual_inject_": "(Tensor(a!) h, Tensor r, float scale) -> Tensor(a!)",
+    "flux_residual_inject_multi_": "(Tensor(a!) h, Tensor[] r, float[] scales) -> Tensor(a!)",
     "block_cache_head": "(Tensor h1, Tensor h0, Tensor? r_prev) -> (Tensor, Tensor)",
     "block_cache_tail": "(Tensor a, Tensor b) -> Tensor",
     "flux_denoise_cfg_": "(int engine_pos, int engine_neg, Tensor(a!) latents, float[] sigmas, float scale) -> Tensor(a!)",
