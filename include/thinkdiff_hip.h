@@ -718,6 +718,28 @@ int td_patchify_bf16(const void* pix, int src_f32, int C, int H, int W, int p, v
  * [(H/patch)(W/patch), Kpad] in the processor's merge-window row order, columns (c, t, py, px); lut fp32 [3,256] = the
  * processor's own rescale + normalize of every pixel value per channel (device). */
 int td_qwen2_patchify_u8(const void* img_hwc, int H, int W, const float* lut, int patch, int merge, int temporal, void* out, int Kpad, void* stream);
+/* ---- PIL-exact image resize ([ext] Pillow src/libImaging/Resample.c, the `Image.resize` every image processor upstream of the towers calls) ----
+ * One axis' coefficient table, made on the HOST (no HIP call, no allocation: it runs on a machine without a GPU).  filter takes Pillow's own integer
+ * codes, so a processor's `resample` passes straight through: 1 = LANCZOS (support 3), 2 = BILINEAR (support 1), 3 = BICUBIC (a = -0.5, support 2);
+ * 0 (NEAREST), 4 (BOX), 5 (HAMMING) and anything else are TD_ERR_INVALID.  Arithmetic, in double, is Pillow's precompute_coeffs +
+ * normalize_coeffs_8bpc: scale = in / out, fs = max(scale, 1), support = filter_support * fs, ksize = ceil(support) * 2 + 1; per output xx:
+ * center = (xx + 0.5) * scale, xmin = max((int)(center - support + 0.5), 0), count = min((int)(center + support + 0.5), in) - xmin,
+ * w[x] = filter((x + xmin - center + 0.5) * (1 / fs)), summed in index order and each divided by the sum, then (int)(+-0.5 + w * 2^22) with the sign
+ * of w.  lanczos' sinc is sin(pi x) / (pi x) with libm's sin, which is why the table is not made in a kernel.
+ * Fills bounds[out_size][2] = (xmin, count), kk[out_size][ksize] (rows zero past count) and *ksize; with bounds == kk == NULL only *ksize (query). */
+int td_resize_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int* ksize);
+/* src uint8 [in_h, in_w, in_c] -> dst uint8 [out_h, out_w, out_c] (device, contiguous) in Pillow's order: horizontal pass into tmp (uint8
+ * [in_h, out_w, out_c], device), then vertical pass; each pass accumulates pixel * weight in int32 from 1 << 21 and writes clip8(acc >> 22).  A pass
+ * whose size does not change is skipped (its table may be NULL); with both unchanged the call is a copy or the channel conversion alone; tmp is needed
+ * only when both run.  h_* / v_* are the DEVICE copies of td_resize_coeffs' output for (in_w, out_w) / (in_h, out_h); the caller orders their upload
+ * before this call on `stream`.  Channel forms, fixed by what Pillow's convert("RGB") does (the conversion happens in the first pass that runs):
+ * 3 -> 3 RGB, 1 -> 1 "L", 1 -> 3 "L" replicated, 4 -> 3 "RGBA" with alpha dropped; every other pair is TD_ERR_INVALID.  No allocation, no
+ * synchronisation; every refusal (non-positive sizes, bad channel pair, missing table or tmp, element counts past 2^31) comes before any launch. */
+int td_image_resize_u8(const void* src_hwc, int in_h, int in_w, int in_c, void* dst_hwc, int out_h, int out_w, int out_c, const int32_t* h_bounds, const int32_t* h_kk,
+                       int h_ksize, const int32_t* v_bounds, const int32_t* v_kk, int v_ksize, void* tmp, void* stream);
+/* out fp32 [C, H, W] = lut[c][img[y, x, c]] for img uint8 [H, W, C], lut fp32 [C, 256] (device): a processor's rescale + normalize of every pixel value
+ * per channel, computed by the processor's own arithmetic on the host, so the result is the host path's bit for bit.  1 <= C <= 4. */
+int td_image_lut_chw_f32(const void* img_hwc, int H, int W, int C, const float* lut, float* out, void* stream);
 /* out[r, :K] = bf16(src[r, :K]); out[r, K:Kpad] = 0. */
 int td_cast_pad_rows_bf16(const void* src, int src_f32, int rows, int K, void* out, int Kpad, void* stream);
 

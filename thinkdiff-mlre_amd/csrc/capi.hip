@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 10; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 11; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -27,6 +27,7 @@ int td_abi_version(void) { return 10; }     // 2: TdFluxConfig::out_channels app
                                             // 9: td_linear_drain_bf16 (test entry of the 256x256 tile's persistent walk)
                                             // 10: several ControlNets per context (td_flux_attach_controlnets, td_flux_set_controlnet_scales_at,
                                             //     td_flux_attached_controlnets, td_flux_residual_inject_multi_bf16)
+                                            // 11: PIL-exact image resize (td_resize_coeffs, td_image_resize_u8, td_image_lut_chw_f32)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -340,6 +341,20 @@ int td_vision_rope_table(const int* pos, int S, int hd, float theta, float* cos_
 }
 int td_qwen2_patchify_u8(const void* img_hwc, int H, int W, const float* lut, int patch, int merge, int temporal, void* out, int Kpad, void* stream) {
   return td_qwen2_patchify_u8_launch((const unsigned char*)img_hwc, H, W, lut, patch, merge, temporal, (bf16_t*)out, Kpad, (hipStream_t)stream);
+}
+
+int td_resize_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* kk, int* ksize) {
+  return td_resize_coeffs_host(in_size, out_size, filter, bounds, kk, ksize);
+}
+
+int td_image_resize_u8(const void* src_hwc, int in_h, int in_w, int in_c, void* dst_hwc, int out_h, int out_w, int out_c, const int32_t* h_bounds, const int32_t* h_kk,
+                       int h_ksize, const int32_t* v_bounds, const int32_t* v_kk, int v_ksize, void* tmp, void* stream) {
+  return td_image_resize_u8_launch((const unsigned char*)src_hwc, in_h, in_w, in_c, (unsigned char*)dst_hwc, out_h, out_w, out_c, h_bounds, h_kk, h_ksize, v_bounds, v_kk,
+                                   v_ksize, (unsigned char*)tmp, (hipStream_t)stream);
+}
+
+int td_image_lut_chw_f32(const void* img_hwc, int H, int W, int C, const float* lut, float* out, void* stream) {
+  return td_image_lut_chw_f32_launch((const unsigned char*)img_hwc, H, W, C, lut, out, (hipStream_t)stream);
 }
 
 int td_patchify_bf16(const void* pix, int src_f32, int C, int H, int W, int p, void* out, int Kpad, void* stream) {

@@ -251,6 +251,14 @@ int td_patchify_launch(const void* pix, int src_f32, int C, int H, int W, int p,
 int td_qwen2_patchify_u8_launch(const unsigned char* img, int H, int W, const float* lut, int p, int m, int T, bf16_t* out, int Kpad, hipStream_t stream);
 int td_cast_pad_rows_launch(const void* src, int src_f32, int rows, int K, bf16_t* out, int Kpad, hipStream_t stream);
 
+// csrc/image_resize.hip: PIL-exact separable resize of uint8 HWC images.  td_resize_coeffs_host fills one axis' table on the host (no HIP call, no
+// allocation); the launch runs Pillow's horizontal then vertical pass (a pass whose size does not change is skipped) and validates its arguments.
+int td_resize_coeffs_host(int in_size, int out_size, int filter, int* bounds, int* kk, int* ksize_out);
+int td_image_resize_u8_launch(const unsigned char* src, int in_h, int in_w, int in_c, unsigned char* dst, int out_h, int out_w, int out_c, const int* h_bounds,
+                              const int* h_kk, int h_ksize, const int* v_bounds, const int* v_kk, int v_ksize, unsigned char* tmp, hipStream_t stream);
+// out fp32 [C, H, W] = lut[c][img[y, x, c]] for img uint8 [H, W, C]: an image processor's rescale + normalize as its own 256-entry table per channel
+int td_image_lut_chw_f32_launch(const unsigned char* img, int H, int W, int C, const float* lut, float* out, hipStream_t stream);
+
 // temperature / top-p sampling over bf16 logits rows (sampler.hip): one workgroup per row, token ids to out_ids[rows]
 int td_sample_top_p_launch(const bf16_t* logits, long long ld, int rows, int vocab, float temperature, float top_p,
                            unsigned long long seed, unsigned long long offset, int* out_ids, hipStream_t stream);

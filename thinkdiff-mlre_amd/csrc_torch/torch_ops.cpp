@@ -348,6 +348,41 @@ at::Tensor cls_avgpool2(const at::Tensor& tokens) {                  // [1+G*G, 
   return out;
 }
 
+// PIL's Image.resize on the device (td_resize_coeffs + td_image_resize_u8): img uint8 [H, W, C] contiguous -> uint8 [out_h, out_w, out_channels or C], the bytes
+// Pillow gives for `resample` 1 (LANCZOS), 2 (BILINEAR) or 3 (BICUBIC); C -> out_channels is 3 -> 3, 1 -> 1, 1 -> 3 or 4 -> 3 (Pillow's convert("RGB")).  The
+// coefficient tables are made on the host per call and uploaded on the current stream ahead of the launch, so no device copy is shared between streams.
+at::Tensor image_resize_u8(const at::Tensor& img, int64_t out_h, int64_t out_w, int64_t resample, c10::optional<int64_t> out_channels) {
+  TORCH_CHECK(img.is_cuda() && img.scalar_type() == at::kByte && img.dim() == 3 && img.is_contiguous(),
+              "thinkdiff_hip::image_resize_u8: img must be a contiguous uint8 GPU tensor [H, W, C], got ", img.sizes(), " ", img.scalar_type());
+  const int64_t in_h = img.size(0), in_w = img.size(1), in_c = img.size(2), out_c = out_channels.value_or(in_c);
+  TORCH_CHECK(in_h > 0 && in_w > 0 && in_h < (1ll << 31) && in_w < (1ll << 31) && out_h > 0 && out_w > 0 && out_h < (1ll << 31) && out_w < (1ll << 31),
+              "thinkdiff_hip::image_resize_u8: sizes ", in_h, "x", in_w, " -> ", out_h, "x", out_w, " must be 1 .. 2^31 - 1");
+  TORCH_CHECK(in_c >= 1 && in_c <= 4 && out_c >= 1 && out_c <= 4, "thinkdiff_hip::image_resize_u8: channels ", in_c, " -> ", out_c, " are not built");
+  const bool horiz = out_w != in_w, vert = out_h != in_h;
+  int kh = 0, kv = 0;
+  if (horiz) ok(td_resize_coeffs((int)in_w, (int)out_w, (int)resample, nullptr, nullptr, &kh));
+  if (vert) ok(td_resize_coeffs((int)in_h, (int)out_h, (int)resample, nullptr, nullptr, &kv));
+  // one host buffer [h_bounds | h_kk | v_bounds | v_kk], one upload
+  const int64_t o_hk = horiz ? 2 * out_w : 0, o_vb = o_hk + (horiz ? out_w * kh : 0), o_vk = o_vb + (vert ? 2 * out_h : 0), total = o_vk + (vert ? out_h * kv : 0);
+  DeviceGuard guard(img.device());
+  at::Tensor tab_dev;
+  const int32_t* t = nullptr;
+  if (total > 0) {
+    at::Tensor tab = at::empty({total}, at::TensorOptions().dtype(at::kInt));
+    int32_t* h = tab.data_ptr<int32_t>();
+    if (horiz) ok(td_resize_coeffs((int)in_w, (int)out_w, (int)resample, h, h + o_hk, &kh));
+    if (vert) ok(td_resize_coeffs((int)in_h, (int)out_h, (int)resample, h + o_vb, h + o_vk, &kv));
+    tab_dev = tab.to(img.device());
+    t = tab_dev.data_ptr<int32_t>();
+  }
+  at::Tensor out = at::empty({out_h, out_w, out_c}, img.options());
+  at::Tensor tmp;
+  if (horiz && vert) tmp = at::empty({in_h, out_w, out_c}, img.options());
+  ok(td_image_resize_u8(img.data_ptr(), (int)in_h, (int)in_w, (int)in_c, out.data_ptr(), (int)out_h, (int)out_w, (int)out_c, horiz ? t : nullptr, horiz ? t + o_hk : nullptr, kh,
+                        vert ? t + o_vb : nullptr, vert ? t + o_vk : nullptr, kv, tmp.defined() ? tmp.data_ptr() : nullptr, stream_of(img)));
+  return out;
+}
+
 // one token per row of bf16 logits: temperature / top-p, drawn from (seed, offset, row); temperature <= 0: greedy
 at::Tensor sample_top_p(const at::Tensor& logits, double temperature, double top_p, int64_t seed, int64_t offset) {
   check_rows(logits, "logits");
@@ -732,6 +767,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("lora_merge(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor");
   m.def("lora_merge_(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)");
   m.def("redux_compose(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor");
+  m.def("image_resize_u8(Tensor img, int out_h, int out_w, int resample, int? out_channels) -> Tensor");
   m.def("ip_attention(Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale) -> Tensor");
   m.def("ip_attention_(Tensor(a!) o, Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale, bool accumulate) -> Tensor(a!)");
   m.def("flux_ip_adapter_load_param(int engine, int slot, str name, Tensor data) -> ()");
@@ -779,6 +815,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("lora_merge_", &lora_merge_);
   m.impl("flux_lora_load", &flux_lora_load);
   m.impl("redux_compose", &redux_compose);
+  m.impl("image_resize_u8", &image_resize_u8);
   m.impl("ip_attention", &ip_attention);
   m.impl("ip_attention_", &ip_attention_);
   m.impl("flux_ip_adapter_load_param", &flux_ip_adapter_load_param);

@@ -6,6 +6,7 @@ import of any op raises, so a GPU run can never silently take an eager/CPU path.
 """
 import ctypes
 import os
+import threading
 
 import torch
 
@@ -153,6 +154,9 @@ def _declare(L):
         "td_patchify_bf16": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
         "td_qwen2_patchify_u8": [vp, i32, i32, vp, i32, i32, i32, vp, i32, vp],
         "td_cast_pad_rows_bf16": [vp, i32, i32, i32, vp, i32, vp],
+        "td_resize_coeffs": [i32, i32, i32, vp, vp, vp],
+        "td_image_resize_u8": [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp],
+        "td_image_lut_chw_f32": [vp, i32, i32, i32, vp, vp, vp],
         "td_vae_create": [vp, i32, i32, vp],
         "td_vae_num_params": [vp],
         "td_vae_param_info": [vp, i32, ctypes.c_char_p, i32, vp],
@@ -634,6 +638,86 @@ def qwen2_patchify_u8(img, lut, patch, merge, temporal, Kpad, out=None):
         out = torch.empty(S, Kpad, dtype=torch.bfloat16, device=img.device)
     assert out.shape == (S, Kpad) and out.is_contiguous() and out.dtype == torch.bfloat16
     check(lib().td_qwen2_patchify_u8(ptr(img), H, W, ptr(lut), int(patch), int(merge), int(temporal), ptr(out), int(Kpad), stream_ptr()))
+    return out
+
+
+_resize_tables = {}                      # (in_size, out_size, filter) -> (numpy int32 [2 out + out ksize] = bounds | kk, ksize, the same memory as a torch tensor)
+_resize_tables_lock = threading.Lock()   # the request builder's helper thread and the main thread both resize
+
+
+def _resize_table(in_size, out_size, resample):
+    import numpy as np
+    key = (int(in_size), int(out_size), int(resample))
+    with _resize_tables_lock:
+        hit = _resize_tables.get(key)
+    if hit is not None:
+        return hit
+    L = lib()
+    ks = ctypes.c_int(0)
+    check(L.td_resize_coeffs(key[0], key[1], key[2], None, None, ctypes.byref(ks)))
+    tab = np.empty(2 * key[1] + key[1] * ks.value, dtype=np.int32)
+    base = tab.ctypes.data
+    check(L.td_resize_coeffs(key[0], key[1], key[2], ctypes.c_void_p(base), ctypes.c_void_p(base + 8 * key[1]), ctypes.byref(ks)))
+    host = torch.from_numpy(tab)
+    tab.setflags(write=False)
+    hit = (tab, ks.value, host)
+    with _resize_tables_lock:
+        if len(_resize_tables) >= 512:       # a dataset of arbitrary sizes must not grow the cache without bound
+            _resize_tables.clear()
+        hit = _resize_tables.setdefault(key, hit)
+    return hit
+
+
+def resize_coeffs(in_size, out_size, resample):
+    """One axis' Pillow coefficient table (td_resize_coeffs, host only): (numpy int32 [2 * out_size + out_size * ksize] = bounds | kk, ksize),
+    cached by (in_size, out_size, resample) under a lock; the array is shared between callers and read-only."""
+    return _resize_table(in_size, out_size, resample)[:2]
+
+
+def image_resize_u8(img, out_h, out_w, resample, out_channels=None, out=None):
+    """PIL's Image.resize on the device: img uint8 [H, W, C] (or [H, W] = one channel), cuda, contiguous -> uint8 [out_h, out_w, out_channels or C],
+    Pillow's bytes for resample 1 (LANCZOS), 2 (BILINEAR), 3 (BICUBIC).  C -> out_channels: 3 -> 3, 1 -> 1, 1 -> 3 ("L" replicated), 4 -> 3 ("RGBA"
+    with alpha dropped), as convert("RGB") before the resize.  The host tables are cached; their device copy is made per call on the current stream
+    ahead of the launch, so nothing on the device is shared between streams."""
+    if img.dim() == 2:
+        img = img[:, :, None]
+    assert img.dim() == 3 and img.dtype == torch.uint8 and img.is_contiguous(), (img.shape, img.dtype)
+    in_h, in_w, in_c = img.shape
+    out_h, out_w = int(out_h), int(out_w)
+    out_c = in_c if out_channels is None else int(out_channels)
+    if out is None:
+        out = torch.empty(max(out_h, 0), max(out_w, 0), out_c, dtype=torch.uint8, device=img.device)
+    assert out.shape == (out_h, out_w, out_c) and out.dtype == torch.uint8 and out.is_contiguous() and out.device == img.device
+    horiz, vert = out_w != in_w, out_h != in_h
+    parts, kh, kv = [], 0, 0
+    if horiz:
+        _, kh, th = _resize_table(in_w, out_w, resample)
+        parts.append(th)
+    if vert:
+        _, kv, tv = _resize_table(in_h, out_h, resample)
+        parts.append(tv)
+    hb = hk = vb = vk = None
+    if parts:
+        dev_tab = (parts[0] if len(parts) == 1 else torch.cat(parts)).to(img.device)      # one upload for both axes
+        base, o = dev_tab.data_ptr(), 0
+        if horiz:
+            hb, hk, o = ctypes.c_void_p(base), ctypes.c_void_p(base + 8 * out_w), 4 * th.numel()
+        if vert:
+            vb, vk = ctypes.c_void_p(base + o), ctypes.c_void_p(base + o + 8 * out_h)
+    tmp = torch.empty(in_h * out_w * out_c, dtype=torch.uint8, device=img.device) if horiz and vert else None
+    check(lib().td_image_resize_u8(ptr(img), in_h, in_w, in_c, ptr(out), out_h, out_w, out_c, hb, hk, kh, vb, vk, kv, ptr(tmp), stream_ptr()))
+    return out
+
+
+def image_lut_chw_f32(img, lut, out=None):
+    """img uint8 [H, W, C] (cuda, contiguous), lut fp32 [C, 256] (cuda) -> fp32 [C, H, W] = lut[c][img[y, x, c]]: a processor's rescale + normalize as
+    its own table of the 256 pixel values per channel (td_image_lut_chw_f32)."""
+    H, W, C = img.shape
+    assert img.dtype == torch.uint8 and img.is_contiguous() and lut.dtype == torch.float32 and lut.shape == (C, 256) and lut.is_contiguous()
+    if out is None:
+        out = torch.empty(C, H, W, dtype=torch.float32, device=img.device)
+    assert out.shape == (C, H, W) and out.dtype == torch.float32 and out.is_contiguous()
+    check(lib().td_image_lut_chw_f32(ptr(img), H, W, C, ptr(lut), ptr(out), stream_ptr()))
     return out
 
 

@@ -88,19 +88,42 @@ class ReduxImageEncoder(_Base):
 
 class ReduxDefaultImageProcessor:
     """What transformers' PIL SigLIP processor does under the released `feature_extractor/preprocessor_config.json`, for a checkpoint directory
-    without one: convert to RGB, resize to size x size bicubic (PIL), x 1/255 (in fp64, rounded to fp32), (x - 0.5) / 0.5 in fp32."""
+    without one: convert to RGB, resize to size x size bicubic (PIL), x 1/255 (in fp64, rounded to fp32), (x - 0.5) / 0.5 in fp32.
 
-    def __init__(self, size: int = 384, image_mean: float = 0.5, image_std: float = 0.5):
+    `device=`: the same values computed on that device -- the image's bytes go up in their own mode ("L", "RGB", "RGBA"), the RGB conversion and the
+    resize run as td_image_resize_u8 (Pillow's bytes) and the two arithmetic steps as a lookup in the table of their results for the 256 pixel
+    values (td_image_lut_chw_f32); `pixel_values` then lives on the device.  Without it nothing changes."""
+
+    def __init__(self, size: int = 384, image_mean: float = 0.5, image_std: float = 0.5, device=None):
         self.size, self.image_mean, self.image_std = int(size), float(image_mean), float(image_std)
+        self.device = torch.device(device) if device is not None else None
+        self._lut = None
+
+    def _normalize(self, a):
+        import numpy as np
+        a = (a.astype(np.float64) * (1 / 255)).astype(np.float32)
+        return (a - np.float32(self.image_mean)) / np.float32(self.image_std)
+
+    def _device_lut(self):
+        import numpy as np
+        if self._lut is None:      # the host path's own arithmetic on every pixel value; one row per channel
+            row = self._normalize(np.arange(256, dtype=np.uint8))
+            self._lut = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(row, (3, 256)))).to(self.device)
+        return self._lut
 
     def preprocess(self, images, **_kw):
         import numpy as np
         from PIL import Image
         out = []
         for im in ([images] if isinstance(images, Image.Image) else list(images)):
+            if self.device is not None:
+                im = im if im.mode in ("L", "RGB", "RGBA") else im.convert("RGB")
+                a = torch.from_numpy(np.ascontiguousarray(np.asarray(im, dtype=np.uint8))).to(self.device)
+                a = _hip.image_resize_u8(a, self.size, self.size, int(Image.BICUBIC), out_channels=3)
+                out.append(_hip.image_lut_chw_f32(a, self._device_lut()))
+                continue
             a = np.asarray(im.convert("RGB").resize((self.size, self.size), resample=Image.BICUBIC))
-            a = (a.astype(np.float64) * (1 / 255)).astype(np.float32)
-            a = (a - np.float32(self.image_mean)) / np.float32(self.image_std)
+            a = self._normalize(a)
             out.append(torch.from_numpy(np.ascontiguousarray(a.transpose(2, 0, 1))))
         return type("BatchFeature", (), {"pixel_values": torch.stack(out)})()
 

@@ -30,15 +30,34 @@ class SyntheticVisionTower:
 
 
 class SyntheticImageProcessor:
-    """Blip2Processor stand-in: resize to 224 (bicubic), rescale, CLIP mean/std -> {'pixel_values': [1,3,224,224]}."""
+    """Blip2Processor stand-in: resize to 224 (bicubic), rescale, CLIP mean/std -> {'pixel_values': [1,3,224,224]}.
+
+    `device=`: the same values computed on that device (td_image_resize_u8 for the RGB conversion + resize, td_image_lut_chw_f32 with the table of
+    this class's own rescale / normalize results for the 256 pixel values per channel); `pixel_values` then lives there.  Without it nothing changes."""
     mean, std = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+
+    def __init__(self, device=None):
+        self.device = torch.device(device) if device is not None else None
+        self._lut = None
+
+    def _normalize(self, arr):
+        """uint8 [H, W, 3] -> fp32 [3, H, W]: rescale, CLIP mean / std"""
+        arr = arr.astype("float32") / 255.0
+        return (torch.from_numpy(arr).permute(2, 0, 1) - torch.tensor(self.mean)[:, None, None]) / torch.tensor(self.std)[:, None, None]
 
     def __call__(self, image, text=None, return_tensors="pt"):
         import numpy as np
         from PIL import Image
-        arr = np.asarray(image.convert("RGB").resize((224, 224), Image.BICUBIC), dtype=np.float32) / 255.0
-        t = (torch.from_numpy(arr).permute(2, 0, 1) - torch.tensor(self.mean)[:, None, None]) / torch.tensor(self.std)[:, None, None]
-        return {"pixel_values": t[None]}
+        if self.device is not None:
+            from .. import _hip
+            if self._lut is None:
+                ramp = np.ascontiguousarray(np.broadcast_to(np.arange(256, dtype=np.uint8)[:, None, None], (256, 1, 3)))
+                self._lut = self._normalize(ramp)[:, :, 0].contiguous().to(self.device)          # [3, 256]
+            image = image if image.mode in ("L", "RGB", "RGBA") else image.convert("RGB")
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(image, dtype=np.uint8))).to(self.device)
+            a = _hip.image_resize_u8(a, 224, 224, int(Image.BICUBIC), out_channels=3)
+            return {"pixel_values": _hip.image_lut_chw_f32(a, self._lut)[None]}
+        return {"pixel_values": self._normalize(np.asarray(image.convert("RGB").resize((224, 224), Image.BICUBIC)))[None]}
 
 
 class SyntheticTextEncoders:

@@ -729,8 +729,10 @@ class QwenChatFrontend:
 
     def _device_preprocess_plan(self):
         """Settings of the image processor when its pipeline is the PIL one of transformers (convert to RGB, smart_resize +
-        PIL resize, rescale, normalize, patchify) -- then only the resize stays on the host and the rest runs as one HIP launch per
-        image (td_qwen2_patchify_u8).  None for any other processor: it is called as is."""
+        PIL resize, rescale, normalize, patchify) -- then the whole of it runs on the device: the resize with the RGB conversion of
+        "L" / "RGBA" folded in (td_image_resize_u8, Pillow's bytes) and the rest as one more launch per image
+        (td_qwen2_patchify_u8).  A `resample` other than LANCZOS / BILINEAR / BICUBIC keeps the resize on the host in PIL.
+        None for any other processor: it is called as is."""
         ip = self.image_processor
         plan = getattr(self, "_dev_pre_plan", None)
         if plan is not None and plan[0] is ip:
@@ -755,7 +757,8 @@ class QwenChatFrontend:
 
     def _preprocess_on_device(self, images):
         """PIL images -> {"pixel_values": bf16 [S, Kpad] on the device, "image_grid_thw": [[1, gh, gw], ...]} or None (caller falls back
-        to the processor).  Host: RGB conversion + the processor's smart_resize / PIL resize (threads); device: the rest."""
+        to the processor).  Host: the image's bytes as a uint8 array in its own mode ("L", "RGB", "RGBA"; any other mode through
+        convert("RGB")) and smart_resize's arithmetic; device: RGB conversion + resize, then rescale / normalize / patchify."""
         plan = self._device_preprocess_plan()
         from PIL import Image
         if plan is None or not images or not all(isinstance(im, Image.Image) for im in images):
@@ -764,15 +767,25 @@ class QwenChatFrontend:
             return None
         import numpy as np
         f = plan["patch"] * plan["merge"]
+        device_resize = plan["resample"] in (1, 2, 3)       # Pillow's LANCZOS, BILINEAR, BICUBIC: the filters td_resize_coeffs builds
+
+        def target(h, w):
+            if plan["do_resize"]:
+                return smart_resize(h, w, factor=f, min_pixels=plan["min_pixels"], max_pixels=plan["max_pixels"])
+            if h % f or w % f:
+                raise ValueError(f"image {w}x{h} is not a multiple of {f} and the processor does not resize")
+            return h, w
 
         def prep(im):
+            if device_resize:
+                im = im if im.mode in ("L", "RGB", "RGBA") else im.convert("RGB")
+                a = np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+                return a[:, :, None] if a.ndim == 2 else a
             im = im.convert("RGB") if im.mode != "RGB" else im
             w, h = im.size
-            if plan["do_resize"]:
-                h2, w2 = smart_resize(h, w, factor=f, min_pixels=plan["min_pixels"], max_pixels=plan["max_pixels"])
+            h2, w2 = target(h, w)
+            if (h2, w2) != (h, w):
                 im = im.resize((w2, h2), resample=plan["resample"])
-            elif h % f or w % f:
-                raise ValueError(f"image {w}x{h} is not a multiple of {f} and the processor does not resize")
             return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
 
         if len(images) > 2:
@@ -782,14 +795,18 @@ class QwenChatFrontend:
         else:
             arrs = [prep(im) for im in images]
         p = plan["patch"]
-        grid = [[1, a.shape[0] // p, a.shape[1] // p] for a in arrs]
+        sizes = [target(a.shape[0], a.shape[1]) if device_resize else a.shape[:2] for a in arrs]
+        grid = [[1, h // p, w // p] for h, w in sizes]
         Kpad = self.visual.padded_patch_dim
         dev = self.visual.device
         out = torch.empty(sum(g[1] * g[2] for g in grid), Kpad, dtype=torch.bfloat16, device=dev)
         r0 = 0
-        for a, g in zip(arrs, grid):
+        for a, g, (h2, w2) in zip(arrs, grid, sizes):
             n = g[1] * g[2]
-            _hip.qwen2_patchify_u8(torch.from_numpy(a).to(dev), plan["lut"], p, plan["merge"], plan["temporal"], Kpad, out=out[r0:r0 + n])
+            img = torch.from_numpy(a).to(dev)
+            if a.shape != (h2, w2, 3):
+                img = _hip.image_resize_u8(img, h2, w2, plan["resample"], out_channels=3)
+            _hip.qwen2_patchify_u8(img, plan["lut"], p, plan["merge"], plan["temporal"], Kpad, out=out[r0:r0 + n])
             r0 += n
         return {"pixel_values": out, "image_grid_thw": grid}
 

@@ -45,6 +45,8 @@ flux_ip_adapter_load_param / flux_set_ip_image_embeds / flux_ip_read   diffusers
                            image on an engine context (projection + every block's to_k_ip / to_v_ip, once), and the tokens / K / V read back
 redux_compose              FluxPriorReduxPipeline's `cat([text, image_embeds], 1) * scale[:, None, None]` and `sum(dim=0)` over the images of one call, fused:
                            bf16 products, fp32 sum in index order, one rounding
+image_resize_u8            PIL's `Image.resize` (LANCZOS / BILINEAR / BICUBIC, with `convert("RGB")` of "L" / "RGBA" folded in) on a uint8 HWC image: Pillow's
+                           fixed-point horizontal and vertical passes as two kernels over host-made coefficient tables, the same bytes
 """
 import os
 
@@ -96,6 +98,7 @@ SCHEMAS = {
     "flux_set_ip_image_embeds": "(int engine, int slot, Tensor embeds) -> ()",
     "flux_ip_read": "(int engine, int slot, int block, int which) -> Tensor",
     "redux_compose": "(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor",
+    "image_resize_u8": "(Tensor img, int out_h, int out_w, int resample, int? out_channels) -> Tensor",
 }
 
 _loaded = False
