@@ -909,6 +909,59 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
 /* out bf16[n,hidden] = embed_tokens[token_ids] (device int32[n]): the host splices vision tokens into this to form inputs_embeds. */
 int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, void* stream);
 
+/* ---- 8-bit weight stream (td_abi_version() >= 12): weight-only quantisation of the decoder's Linears -----------------------------------------
+ * Format (fixed): OCP e4m3 bytes with ONE POWER-OF-TWO scale per output row of a Linear weight W[N, K]:
+ *   amax_n = max_k |W[n, k]|;  e_n = the smallest integer with amax_n 2^-e_n <= 448, clamped to [-40, 40] (0 for an all-zero row);
+ *   q[n, k] = e4m3_rne(W[n, k] 2^-e_n) (the product is exact in fp32: one rounding);  W^[n, k] = q[n, k] 2^e_n.
+ * W^ is a bf16 value exactly (4 significant bits, exponent inside bf16's range), so the quantised model is an ordinary bf16 model with weights W^,
+ * and the stream kernels reproduce those bf16 values from the bytes inside the conversion instruction: the products of a dot product are the
+ * ones the bf16 kernels form on W^, only the order of the fp32 sum may differ.  Activations, KV cache, norms and attention stay bf16. */
+/* w bf16 [N, ldw] -> q bytes [N, K] (row stride K), scale fp32 [N] = 2^e_n, and w_hat bf16 [N, ldw] = W^ (NULL: not written; may alias w).
+ * K % 8 == 0, ldw % 8 == 0, ldw >= K; w / w_hat 16-byte, q 8-byte, scale 4-byte aligned.  TD_ERR_INVALID before any HIP call otherwise.
+ * A row whose exponent is clamped at +40 (amax > 448 x 2^40) saturates at +-448 x 2^40. */
+int td_quant_weight_rows_e4m3(const void* w, int64_t ldw, void* q, float* scale, void* w_hat, int N, int K, void* stream);
+/* y[M, N] = epilogue(x[M, K] . W^[N, K]^T) with W^ given as (wq, w_scale) in the format above: td_linear_bf16's epilogue and rounding points (bias,
+ * act, gate, res).  M <= 64 ONLY (the weight-stream kernels; more rows read W^ as bf16 through td_linear_bf16).  N % 4 == 0 and K % 16 == 0; more than
+ * 16 rows (and 5 .. 16 rows on the matrix core) need K % 128 == 0, N % 16 == 0, ldy % 4 == 0.  x and wq 16-byte aligned, ldx % 8 == 0.  M > 64, a NULL
+ * x / wq / w_scale / y, misaligned operands or a K the kernels do not take: TD_ERR_INVALID with a message, before any HIP call. */
+int td_linear_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream);
+/* ... with td_linear_split_bf16's two outputs (columns < n_split -> y0 with act0, the rest -> y1 with act1; n_split % 4 == 0) */
+int td_linear_split_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, const void* bias, void* y0, int64_t ldy0, int act0,
+                            void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream);
+/* Gated MLP front in one pass, the decode step's form: w = [gate rows | up rows] ([2 I, K]), y[m, n] = bf16(bf16(silu(bf16(x . gate_n))) * bf16(x . up_n)),
+ * n < I -- Linear, SiLU and product each round, as td_linear_bf16 + td_silu_mul_bf16 do.  M <= 64, I % 8 == 0, ldy % 4 == 0; bf16: K % 8 == 0
+ * (more than 16 rows: K % 64 == 0); w8: K % 16 == 0 (more than 16 rows: K % 128 == 0).  TD_ERR_INVALID before any HIP call otherwise. */
+int td_linear_glu_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int M, int I, int K, void* stream);
+int td_linear_glu_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, void* y, int64_t ldy, int M, int I, int K, void* stream);
+
+enum { TD_QWEN2_WEIGHTS_BF16 = 0, TD_QWEN2_WEIGHTS_E4M3 = 1 };
+/* Called after the parameters are loaded.  mode = TD_QWEN2_WEIGHTS_E4M3 (anything else: TD_ERR_INVALID): builds the 8-bit copy and the row scales of every
+ * layer's q|k|v, o, gate|up and down weights and of lm_head (4 x layers + 1 Linears) and OVERWRITES the bf16 weights with W^; with tied embeddings the
+ * embedding table IS the lm_head weight and becomes W^ too.  From then on the weight stream is on: every Linear launch of up to 64 rows that the
+ * weight-stream kernels take (the decode step of 1 .. 64 sequences, lm_head, prefills of up to 64 rows) reads the 8-bit copy; launches of more rows
+ * (prefill, packed prefill, the 65 .. 256-sequence decode step) read W^ as bf16 and do not depend on the switch at all.  Memory GROWS by half the
+ * Linear weights (the copy sits beside the bf16 arena: this buys time, not memory).  Drops the captured decode graphs.  May be called again
+ * (idempotent: quantising W^ gives W^) and MUST be called again after td_qwen2_load_param / td_qwen2_init_random on a quantised handle: until then
+ * every forward, prefill and decode entry, and td_qwen2_embed_tokens (with tied embeddings its table is a quantised weight; it refuses on an
+ * untied model too, one rule for the handle), returns TD_ERR_INVALID naming this function -- never a run on a half-quantised model.
+ * Allocates on the first call (not capturable). */
+int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream);
+/* A/B switch and test handle on a quantised handle: on (default after quantising) = launches of up to 64 rows read the 8-bit copy, off = the same
+ * launches read bf16 W^.  The model is the same either way.  Two exceptions to "the same launches", both in the decode step: with hidden >= 3072 a
+ * step of 33 .. 64 sequences runs on the weight-stream kernels with the stream on and on the tile / split-K kernels with it off (the bf16
+ * cross-over of that width is 32 sequences; on half the bytes the stream stays ahead through 64), and with hidden < 3072 a step of exactly 2
+ * sequences reads bf16 W^ even with the stream on (measured slower on the bytes, on the 2B shape only).  Drops the captured decode graphs.
+ * Returns the previous setting (0 / 1); TD_ERR_INVALID on a NULL or unquantised handle. */
+int td_qwen2_set_weight_stream(td_qwen2* f, int on);
+/* mode (TD_QWEN2_WEIGHTS_*), whether the stream is on, bytes of the 8-bit copy (weight bytes + row scales), number of quantised Linears; any output
+ * may be NULL */
+int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* bytes_8bit, int* n_linears);
+/* How many Linear launches the handle has enqueued so far that read the 8-bit copy (a captured decode step counts once, when it is captured;
+ * its replays launch nothing from the host and do not count).  The test handle that tells "the 8-bit kernels ran" from "the bf16 kernels ran on
+ * W^", which the outputs alone cannot (the model is the same).  -1 on a NULL handle. */
+int64_t td_qwen2_weight_stream_launches(const td_qwen2* f);
+
 /* Qwen2 building blocks */
 /* out bf16[n,D] = table[ids[i],:] (table bf16 [vocab,D], ids device int32[n], D % 8 == 0).  An id outside [0, vocab) is CLAMPED, not
  * refused: id < 0 reads row 0, id >= vocab reads row vocab - 1 (the kernel never reads outside the table; a caller that wants an

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 11; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 12; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -28,6 +28,8 @@ int td_abi_version(void) { return 11; }     // 2: TdFluxConfig::out_channels app
                                             // 10: several ControlNets per context (td_flux_attach_controlnets, td_flux_set_controlnet_scales_at,
                                             //     td_flux_attached_controlnets, td_flux_residual_inject_multi_bf16)
                                             // 11: PIL-exact image resize (td_resize_coeffs, td_image_resize_u8, td_image_lut_chw_f32)
+                                            // 12: 8-bit weight stream (td_quant_weight_rows_e4m3, td_linear*_w8_bf16, td_linear_glu_bf16,
+                                            //     td_qwen2_quantize_weights, td_qwen2_set_weight_stream, td_qwen2_weight_info, td_qwen2_weight_stream_launches)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -577,6 +579,58 @@ int td_attention_fp8_q8(const void* q, int64_t ldq, const void* k, const void* v
   p.variant = ((g_attn_variant & 1) ? 0x1000 : 0) | ((g_attn_variant & 2) ? 0x2000 : 0);      // as td_attention_fp8 (without its timing probes)
   p.q8 = (uint8_t*)q8; p.ldq8 = (int)ldq8; p.q8_inv = q8_inv; p.q8_amax = q8_amax;
   return td_attn_fp8_launch(p, (hipStream_t)stream);
+}
+
+// ---- 8-bit weight stream (td_abi_version() >= 12): every entry checks its arguments itself, before the launcher makes its first HIP call
+int td_quant_weight_rows_e4m3(const void* w, int64_t ldw, void* q, float* scale, void* w_hat, int N, int K, void* stream) {
+  return td_quant_weight_rows_launch((const bf16_t*)w, (long long)ldw, (uint8_t*)q, scale, (bf16_t*)w_hat, N, K, (hipStream_t)stream);
+}
+
+namespace {
+int w8_linear_check(const char* me, const void* x, int64_t ldx, const void* wq, const float* w_scale, const void* y, int64_t ldy, int M, int N, int K) {
+  TD_CHECK_ARG(x && wq && w_scale && y, "%s: x, the 8-bit weights wq, their row scales w_scale and the output are required", me);
+  TD_CHECK_ARG(M >= 1 && M <= 64, "%s: M=%d: the 8-bit weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", me, M);
+  TD_CHECK_ARG(N > 0 && K > 0 && ld32(ldx) && ld32(ldy), "%s: N=%d, K=%d, ldx=%lld, ldy=%lld", me, N, K, (long long)ldx, (long long)ldy);
+  return 0;
+}
+}  // namespace
+
+int td_linear_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream) {
+  if (int rc = w8_linear_check("td_linear_w8_bf16", x, ldx, wq, w_scale, y, ldy, M, N, K)) return rc;
+  TD_CHECK_ARG(ld32(ldr) && (!res || ldr >= N), "td_linear_w8_bf16: ldr=%lld must cover the N=%d columns of the residual", (long long)ldr, N);
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W8 = (const uint8_t*)wq; p.w8_scale = w_scale; p.bias = (const bf16_t*)bias;
+  p.C = (bf16_t*)y; p.ldc = (int)ldy; p.gate = (const bf16_t*)gate; p.res = (const bf16_t*)res; p.ldr = (int)ldr;
+  p.M = M; p.N = N; p.K = K; p.act = act;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_split_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, const void* bias, void* y0, int64_t ldy0, int act0,
+                            void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream) {
+  if (int rc = w8_linear_check("td_linear_split_w8_bf16", x, ldx, wq, w_scale, y0, ldy0, M, N, K)) return rc;
+  TD_CHECK_ARG(y1 && ld32(ldy1), "td_linear_split_w8_bf16: the second output y1 is required");
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W8 = (const uint8_t*)wq; p.w8_scale = w_scale; p.bias = (const bf16_t*)bias;
+  p.C = (bf16_t*)y0; p.ldc = (int)ldy0; p.act = act0; p.C2 = (bf16_t*)y1; p.ldc2 = (int)ldy1; p.act2 = act1; p.n_split = n_split;
+  p.M = M; p.N = N; p.K = K;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_glu_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int M, int I, int K, void* stream) {
+  TD_CHECK_ARG(x && w && y, "td_linear_glu_bf16: x, w and y are required");
+  TD_CHECK_ARG(M >= 1 && M <= 64 && I > 0 && K > 0 && ld32(ldx) && ld32(ldy) && ldx >= K && ldy >= I, "td_linear_glu_bf16: M=%d (1 .. 64), I=%d, K=%d, ldx=%lld, ldy=%lld", M, I, K,
+               (long long)ldx, (long long)ldy);
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W = (const bf16_t*)w; p.C = (bf16_t*)y; p.ldc = (int)ldy; p.M = M; p.N = I; p.K = K; p.glu_I = I;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_glu_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, void* y, int64_t ldy, int M, int I, int K, void* stream) {
+  if (int rc = w8_linear_check("td_linear_glu_w8_bf16", x, ldx, wq, w_scale, y, ldy, M, I, K)) return rc;
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W8 = (const uint8_t*)wq; p.w8_scale = w_scale; p.C = (bf16_t*)y; p.ldc = (int)ldy; p.M = M; p.N = I; p.K = K; p.glu_I = I;
+  return td_gemv_launch(p, (hipStream_t)stream);
 }
 
 int td_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int vocab, float temperature, float top_p,

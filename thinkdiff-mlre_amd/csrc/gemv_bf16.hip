@@ -40,21 +40,44 @@ __device__ __forceinline__ float act_rt(int act, float x) {
   }
 }
 
+// 8-bit weights (TdGemmParams::W8): 16 e4m3 bytes of a row -> 8 bf16 pairs, the row's power-of-two scale applied INSIDE the conversion
+// (v_cvt_scalef32_pk_bf16_fp8: exact, the result has 4 significant bits), so v_dot2c sees the operands it sees on the bf16 path
+__device__ __forceinline__ void cvt16(const u32x4_t& w, float scale, u32x4_t& lo, u32x4_t& hi) {
+  unsigned o[8];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned uw = w[q];
+    o[2 * q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(uw, scale, false));
+    o[2 * q + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(uw, scale, true));
+  }
+  lo = u32x4_t{o[0], o[1], o[2], o[3]};
+  hi = u32x4_t{o[4], o[5], o[6], o[7]};
+}
+
 constexpr int R = 4;          // weight rows (output columns) per workgroup
 constexpr int THREADS = 256;
 
-template <int MR>
+// W8: the weight rows are e4m3 bytes (p.W8, p.w8_scale); a 16-byte chunk then holds 16 weights and meets two chunks of x.  Everything behind the
+// accumulators is shared with the bf16 form.
+template <int MR, bool W8 = false>
 __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParams p) {
   __shared__ float red[THREADS / 64][R][MR];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int n0 = blockIdx.x * R;
-  const int nchunk = p.K >> 3;
+  const int nchunk = W8 ? p.K >> 4 : p.K >> 3;
   const u32x4_t* wp[R];
+  float wsc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     // gated mode: rows 0,1 = gate rows 2b, 2b+1; rows 2,3 = the matching up rows (glu_I further down the matrix)
     const int row = p.glu_I ? (blockIdx.x * 2 + (r & 1) + (r >> 1) * p.glu_I) : min(n0 + r, p.N - 1);
-    wp[r] = (const u32x4_t*)(p.W + (size_t)row * p.K);
+    if constexpr (W8) {
+      wp[r] = (const u32x4_t*)(p.W8 + (size_t)row * p.K);
+      wsc[r] = p.w8_scale[row];
+    } else {
+      wp[r] = (const u32x4_t*)(p.W + (size_t)row * p.K);
+      wsc[r] = 1.f;
+    }
   }
   const u32x4_t* xp[MR];
 #pragma unroll
@@ -74,22 +97,46 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
       w0[r] = __builtin_nontemporal_load(wp[r] + c);
       w1[r] = __builtin_nontemporal_load(wp[r] + c + THREADS);
     }
+    if constexpr (W8) {
+      u32x4_t a0[R], b0[R], a1[R], b1[R];
 #pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const u32x4_t x0 = xp[m][c], x1 = xp[m][c + THREADS];
+      for (int r = 0; r < R; ++r) { cvt16(w0[r], wsc[r], a0[r], b0[r]); cvt16(w1[r], wsc[r], a1[r], b1[r]); }
 #pragma unroll
-      for (int r = 0; r < R; ++r) acc[r][m] = dot8(w1[r], x1, dot8(w0[r], x0, acc[r][m]));
+      for (int m = 0; m < MR; ++m) {
+        const u32x4_t x0 = xp[m][2 * c], x1 = xp[m][2 * c + 1], x2 = xp[m][2 * (c + THREADS)], x3 = xp[m][2 * (c + THREADS) + 1];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][m] = dot8(b1[r], x3, dot8(a1[r], x2, dot8(b0[r], x1, dot8(a0[r], x0, acc[r][m]))));
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const u32x4_t x0 = xp[m][c], x1 = xp[m][c + THREADS];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][m] = dot8(w1[r], x1, dot8(w0[r], x0, acc[r][m]));
+      }
     }
   }
   if (c < nchunk) {
     u32x4_t w0[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) w0[r] = __builtin_nontemporal_load(wp[r] + c);
+    if constexpr (W8) {
+      u32x4_t a0[R], b0[R];
 #pragma unroll
-    for (int m = 0; m < MR; ++m) {
-      const u32x4_t x0 = xp[m][c];
+      for (int r = 0; r < R; ++r) cvt16(w0[r], wsc[r], a0[r], b0[r]);
 #pragma unroll
-      for (int r = 0; r < R; ++r) acc[r][m] = dot8(w0[r], x0, acc[r][m]);
+      for (int m = 0; m < MR; ++m) {
+        const u32x4_t x0 = xp[m][2 * c], x1 = xp[m][2 * c + 1];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][m] = dot8(b0[r], x1, dot8(a0[r], x0, acc[r][m]));
+      }
+    } else {
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const u32x4_t x0 = xp[m][c];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][m] = dot8(w0[r], x0, acc[r][m]);
+      }
     }
   }
 
@@ -154,7 +201,12 @@ constexpr size_t SPLITK_PART_BYTES = (size_t)SPLITK_MAX_WGS * 4 * 8 * 1024;   //
 template <int MB> constexpr int gemv_xb() { return MB > 2 ? 2 : MB; }     // activation blocks passing through the slab together
 template <int MB, int NR> constexpr int gemv_lds_bytes() { return MW * (2 * NR + 2 * gemv_xb<MB>()) * 1024; }
 
-template <int MB, int NR, bool DEEP>
+// W8 (TdGemmParams::W8): the weight rows are e4m3 bytes.  A whole 128-byte line of a row is then 128 weights, so a step covers 128 elements of K: the same
+// two weight loads per block as a bf16 step (8 rows x one line each), twice the activation loads, and the loop body below runs its two 64-element halves
+// in turn.  The weight lines go through the slab AS BYTES (same writes, same XOR placement of the 16-byte chunks); a lane reads the 8 bytes of its operand
+// fragment back (ds_read_b64) and converts them with its row's scale (4 x v_cvt_scalef32_pk_bf16_fp8 per fragment) into the very bf16 fragment the bf16
+// form would have read.  Accumulators, reduction, split-K hand-off and epilogue are shared.
+template <int MB, int NR, bool DEEP, bool W8 = false>
 __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParams p, char* ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int XB = gemv_xb<MB>();
@@ -176,12 +228,14 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   // LDS pass (a workgroup streams only 16 rows x K, its lifetime is a handful of memory round trips); otherwise hipcc threads
   // the loads between the steps at low register count, which keeps several workgroups per CU for short K.
   const unsigned w_rows = p.glu_I ? 2u * (unsigned)p.glu_I : (unsigned)p.N;
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (unsigned)((size_t)w_rows * p.K * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = W8 ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W8, 0, (unsigned)((size_t)w_rows * p.K), 0x00020000)
+                                        : __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (unsigned)((size_t)w_rows * p.K * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (unsigned)((((size_t)p.M - 1) * p.lda + p.K) * 2), 0x00020000);
   constexpr unsigned OOB = 0xFFFFFF00u;
   const int lrow = lane >> 3;                                  // row of the 8-row half this lane fetches
   const int lchunk = (lane & 7) ^ (lrow & 7);                  // ... and which 16-byte chunk of the row's 128-byte line
   unsigned woff[NR][2], xoff[MB][2];
+  float wsc[NR];                                               // W8: scale of the weight row this lane holds in operand layout (row r of the block)
 #pragma unroll
   for (int nr = 0; nr < NR; ++nr) {
     const int bid = min((int)blockIdx.x * NR + nr, nblk - 1);
@@ -189,8 +243,10 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
     for (int h = 0; h < 2; ++h) {
       // gated mode: rows 0-7 = gate rows 8b..8b+7, rows 8-15 = the matching up rows
       const int wr_ = p.glu_I ? (bid * 8 + lrow + h * p.glu_I) : bid * 16 + 8 * h + lrow;
-      woff[nr][h] = (unsigned)(((size_t)wr_ * p.K + 8 * lchunk) * 2);
+      woff[nr][h] = W8 ? (unsigned)((size_t)wr_ * p.K + 16 * lchunk) : (unsigned)(((size_t)wr_ * p.K + 8 * lchunk) * 2);
     }
+    if constexpr (W8) wsc[nr] = p.w8_scale[p.glu_I ? (bid * 8 + (r & 7) + (r >> 3) * p.glu_I) : bid * 16 + r];
+    else wsc[nr] = 1.f;
   }
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -201,29 +257,40 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   const char* rd_ptr[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) rd_ptr[h] = slab + r * 128 + (((4 * h + g) ^ (r & 7)) << 4);   // + block * 2048
-  const int nk_all = p.K >> 6;                  // 64-element steps
+  // W8: bytes of the 8 fragment bytes of (half j of the step, h): k = 64 j + 32 h + 8 g .. + 7 = chunk 4 j + 2 h + g / 2 of the row's line, its half g % 2
+  const char* rd8_ptr[2][2];
+  if constexpr (W8) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) rd8_ptr[j][h] = slab + r * 128 + (((4 * j + 2 * h + (g >> 1)) ^ (r & 7)) << 4) + 8 * (g & 1);
+  }
+  constexpr int KH = W8 ? 2 : 1;                // 64-element halves of a step
+  const int nk_all = W8 ? p.K >> 7 : p.K >> 6;  // steps (64 elements; W8: 128)
   const int s_beg = (int)((long long)nk_all * ky / KS), nk = (int)((long long)nk_all * (ky + 1) / KS);   // this workgroup's steps
   f32x4_t acc[NR][MB];
 #pragma unroll
   for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc[nr][mb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  constexpr int SF = DEEP ? 32 / (2 * NR + 2 * MB) : (MB * NR == 1 ? 2 : 1);    // k-steps per wave and iteration
+  constexpr int SF = DEEP ? (32 / (2 * NR + 2 * KH * MB) > 0 ? 32 / (2 * NR + 2 * KH * MB) : 1) : (MB * NR == 1 ? 2 : 1);    // k-steps per wave and iteration
   for (int s = s_beg + wid; s < nk; s += SF * MW) {
-    u32x4_t w[SF][NR][2], x[SF][MB][2];
+    u32x4_t w[SF][NR][2], x[SF][KH][MB][2];
 #pragma unroll
     for (int f = 0; f < SF; ++f) {
       const int st = s + f * MW;
       const bool ok = st < nk;
-      const unsigned k0 = (unsigned)st * 128u;
+      const unsigned k0 = (unsigned)st * 128u;      // a step is one 128-byte line of every weight row in both forms
 #pragma unroll
       for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
         for (int h = 0; h < 2; ++h) w[f][nr][h] = __builtin_amdgcn_raw_buffer_load_b128(rsW, ok ? woff[nr][h] + k0 : OOB, 0, 0);
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
+      for (int j = 0; j < KH; ++j)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) x[f][mb][h] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? xoff[mb][h] + k0 : OOB, 0, 0);
+        for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) x[f][j][mb][h] = __builtin_amdgcn_raw_buffer_load_b128(rsX, ok ? xoff[mb][h] + KH * k0 + 128u * j : OOB, 0, 0);
     }
     if (DEEP) __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise threads the loads between the steps and keeps 4-6 of them in flight
 #pragma unroll
@@ -233,6 +300,8 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
       for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
         for (int h = 0; h < 2; ++h) wr_ptr[(2 * nr + h) * 64] = w[f][nr][h];
+#pragma unroll
+      for (int kh = 0; kh < KH; ++kh) {
       bf16x8_t wf[NR][2];
 #pragma unroll
       for (int m0 = 0; m0 < MB; m0 += XB) {       // XB activation blocks at a time through the slab
@@ -240,13 +309,25 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
         for (int j = 0; j < XB; ++j)
 #pragma unroll
           for (int h = 0; h < 2; ++h)
-            if (m0 + j < MB) wr_ptr[(2 * (NR + j) + h) * 64] = x[f][m0 + j < MB ? m0 + j : 0][h];
+            if (m0 + j < MB) wr_ptr[(2 * (NR + j) + h) * 64] = x[f][kh][m0 + j < MB ? m0 + j : 0][h];
         bf16x8_t xf[XB][2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           if (m0 == 0) {
 #pragma unroll
-            for (int nr = 0; nr < NR; ++nr) wf[nr][h] = *(const bf16x8_t*)(rd_ptr[h] + nr * 2048);
+            for (int nr = 0; nr < NR; ++nr) {
+              if constexpr (W8) {
+                const u32x2_t b = *(const u32x2_t*)(rd8_ptr[kh][h] + nr * 2048);
+                const unsigned b0 = b[0], b1 = b[1];
+                const u32x4_t o = {__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b0, wsc[nr], false)),
+                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b0, wsc[nr], true)),
+                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b1, wsc[nr], false)),
+                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b1, wsc[nr], true))};
+                wf[nr][h] = __builtin_bit_cast(bf16x8_t, o);
+              } else {
+                wf[nr][h] = *(const bf16x8_t*)(rd_ptr[h] + nr * 2048);
+              }
+            }
           }
 #pragma unroll
           for (int j = 0; j < XB; ++j) xf[j][h] = *(const bf16x8_t*)(rd_ptr[h] + (NR + j) * 2048);
@@ -259,6 +340,7 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
             for (int j = 0; j < XB; ++j)
               if (m0 + j < MB) acc[nr][m0 + j < MB ? m0 + j : 0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nr][h], xf[j][h], acc[nr][m0 + j < MB ? m0 + j : 0], 0, 0, 0);
       }
+     }
     }
   }
   __syncthreads();          // every wave is done with its slab before the reduction reuses the space
@@ -364,7 +446,7 @@ int splitk_workspace(hipStream_t stream, char** out) {
   return 0;
 }
 
-template <int MB, int NR, bool DEEP>
+template <int MB, int NR, bool DEEP, bool W8>
 int launch_one(const TdGemmParams& p, dim3 grid, char* ws, hipStream_t stream) {
   constexpr int lds = gemv_lds_bytes<MB, NR>();
   if (lds + 64 >= 64 * 1024) {  // dynamic + the static ticket word reach the default 64 KiB limit: raise it once per device
@@ -372,43 +454,93 @@ int launch_one(const TdGemmParams& p, dim3 grid, char* ws, hipStream_t stream) {
     int dev = 0;
     TD_CHECK_HIP(hipGetDevice(&dev));
     if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-      TD_CHECK_HIP(hipFuncSetAttribute((const void*)td_gemv_mfma_kernel<MB, NR, DEEP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      TD_CHECK_HIP(hipFuncSetAttribute((const void*)td_gemv_mfma_kernel<MB, NR, DEEP, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       done.fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL((td_gemv_mfma_kernel<MB, NR, DEEP>), grid, dim3(MW * 64), lds, stream, p, ws);
+  hipLaunchKernelGGL((td_gemv_mfma_kernel<MB, NR, DEEP, W8>), grid, dim3(MW * 64), lds, stream, p, ws);
   return 0;
 }
 
-template <int MB>
+template <int MB, bool W8>
 int launch_mfma(const TdGemmParams& p, hipStream_t stream) {
   const int nblk = p.glu_I ? p.glu_I / 8 : p.N / 16;
+  const int steps = W8 ? p.K >> 7 : p.K >> 6;      // k-steps of the kernel (64 elements; W8: 128, one line of weight bytes)
   // two weight blocks per workgroup halve the x re-reads from L2; only where the grid still oversubscribes the chip
   if (MB > 1 && nblk >= 1024) {
     const dim3 grid((nblk + 1) / 2);
-    return (p.K >> 6) >= 4 * MW ? launch_one<MB, 2, true>(p, grid, nullptr, stream) : launch_one<MB, 2, false>(p, grid, nullptr, stream);
+    return steps >= 4 * MW ? launch_one<MB, 2, true, W8>(p, grid, nullptr, stream) : launch_one<MB, 2, false, W8>(p, grid, nullptr, stream);
   }
-  // few block columns: split K over workgroups too, as long as every wave of a workgroup keeps at least one 64-element step
+  // few block columns: split K over workgroups too, as long as every wave of a workgroup keeps at least one step
   int ks = 1;
-  if (nblk < SPLITK_MAX_WGS / 2) ks = std::max(1, std::min({8, SPLITK_MAX_WGS / nblk, (p.K >> 6) / MW}));
+  if (nblk < SPLITK_MAX_WGS / 2) ks = std::max(1, std::min({8, SPLITK_MAX_WGS / nblk, steps / MW}));
   char* ws = nullptr;
   if (ks > 1) {
     if (int rc = splitk_workspace(stream, &ws)) return rc;
   }
   const dim3 grid(nblk, ks);
-  return (p.K >> 6) / ks >= 4 * MW ? launch_one<MB, 1, true>(p, grid, ws, stream) : launch_one<MB, 1, false>(p, grid, ws, stream);
+  return steps / ks >= 4 * MW ? launch_one<MB, 1, true, W8>(p, grid, ws, stream) : launch_one<MB, 1, false, W8>(p, grid, ws, stream);
 }
 
+template <bool W8>
 int launch_mfma_rows(const TdGemmParams& p, hipStream_t stream) {
-  if (p.M <= 16) return launch_mfma<1>(p, stream);
-  if (p.M <= 32) return launch_mfma<2>(p, stream);
-  if (p.M <= 48) return launch_mfma<3>(p, stream);
-  return launch_mfma<4>(p, stream);
+  if (p.M <= 16) return launch_mfma<1, W8>(p, stream);
+  if (p.M <= 32) return launch_mfma<2, W8>(p, stream);
+  if (p.M <= 48) return launch_mfma<3, W8>(p, stream);
+  return launch_mfma<4, W8>(p, stream);
+}
+
+// the dot-product form's launch for M <= 16 rows
+template <bool W8>
+void launch_dot(const TdGemmParams& p, dim3 grid, hipStream_t stream) {
+  const dim3 block(THREADS);
+  if (p.M == 1) hipLaunchKernelGGL((td_gemv_bf16_kernel<1, W8>), grid, block, 0, stream, p);
+  else if (p.M == 2) hipLaunchKernelGGL((td_gemv_bf16_kernel<2, W8>), grid, block, 0, stream, p);
+  else if (p.M <= 4) hipLaunchKernelGGL((td_gemv_bf16_kernel<4, W8>), grid, block, 0, stream, p);
+  else if (p.M <= 8) hipLaunchKernelGGL((td_gemv_bf16_kernel<8, W8>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((td_gemv_bf16_kernel<16, W8>), grid, block, 0, stream, p);
+}
+
+// td_gemv_launch for TdGemmParams::W8: the routing of the bf16 form with the 8-bit kernels' own extents (a chunk is 16 weights, an MFMA step 128)
+bool w8_mfma_ok(const TdGemmParams& p) {
+  const long long w_rows = p.glu_I ? 2ll * p.glu_I : p.N;
+  if (w_rows * p.K >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
+  if (p.glu_I) return p.K % 128 == 0;
+  return p.K % 128 == 0 && p.N % 16 == 0 && p.ldc % 4 == 0 && p.lda % 8 == 0 && (!p.C2 || (p.ldc2 % 4 == 0 && p.n_split % 4 == 0));
+}
+
+int gemv_w8_launch(const TdGemmParams& p, hipStream_t stream) {
+  TD_CHECK_ARG(p.W8 && p.w8_scale && p.A && p.C, "td_gemv(w8): x, the 8-bit weights, their row scales and the output are required");
+  TD_CHECK_ARG(p.M >= 1 && p.M <= 64, "td_gemv(w8): M=%d: the 8-bit weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", p.M);
+  TD_CHECK_ARG(p.N > 0 && p.N % R == 0 && p.K > 0 && p.K % 16 == 0, "td_gemv(w8): N=%d must be a multiple of 4 and K=%d a multiple of 16 (one 16-byte chunk of weight bytes)", p.N, p.K);
+  TD_CHECK_ARG(p.lda >= p.K && p.lda % 8 == 0 && p.ldc >= (p.C2 ? p.n_split : p.N), "td_gemv(w8): bad leading dimensions lda=%d ldc=%d", p.lda, p.ldc);
+  TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W8) % 16 == 0 && (uintptr_t)p.w8_scale % 4 == 0 && (uintptr_t)p.C % 8 == 0 && (uintptr_t)p.C2 % 8 == 0,
+               "td_gemv(w8): misaligned operands: x and the weight bytes must be 16-byte aligned, the outputs 8-byte, the scales 4-byte");
+  if (p.C2) TD_CHECK_ARG(p.n_split > 0 && p.n_split < p.N && p.n_split % 4 == 0 && p.ldc2 >= p.N - p.n_split, "td_gemv(w8): bad split-output arguments");
+  if (p.glu_I) {
+    TD_CHECK_ARG(p.N == p.glu_I && p.glu_I % 8 == 0 && !p.bias && !p.gate && !p.res && !p.C2 && p.act == TD_ACT_NONE && p.ldc % 4 == 0,
+                 "td_gemv(w8, glu): N must equal glu_I (multiple of 8), no bias / gate / residual / split");
+  }
+  const bool mfma = w8_mfma_ok(p);
+  TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(w8): more than 16 rows need the matrix-core form (K=%d %% 128, N=%d %% 16, ldc %% 4 == 0, operands under 4 GiB)", p.K, p.N);
+  if (p.M > 4 && mfma) {
+    if (int rc = launch_mfma_rows<true>(p, stream)) return rc;
+  } else {
+    launch_dot<true>(p, dim3(p.glu_I ? p.glu_I / 2 : p.N / R), stream);
+  }
+  TD_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace
 
 // shapes the matrix-core weight stream takes (td_gemm_launch asks before routing 16 < M <= 64 here)
+bool td_gemv_w8_ok(const TdGemmParams& p) {
+  if (p.M < 1 || p.M > 64 || p.N % R != 0 || p.K % 16 != 0 || p.lda % 8 != 0) return false;
+  if (p.glu_I && (p.N != p.glu_I || p.glu_I % 8 != 0 || p.ldc % 4 != 0)) return false;
+  return p.M <= 16 || w8_mfma_ok(p);
+}
+
 bool td_gemv_mfma_ok(const TdGemmParams& p) {
   const long long w_rows = p.glu_I ? 2ll * p.glu_I : p.N;          // operands sit behind 32-bit buffer descriptors
   if (w_rows * p.K * 2 >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
@@ -418,6 +550,7 @@ bool td_gemv_mfma_ok(const TdGemmParams& p) {
 
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemv: unknown activation code act=%d act2=%d", p.act, p.act2);
+  if (p.W8) return gemv_w8_launch(p, stream);
   TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % 8 == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");
   TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W) % 16 == 0, "td_gemv: operands must be 16-byte aligned");
   if (p.glu_I) {
@@ -426,27 +559,18 @@ int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
     const bool mfma = p.K % 64 == 0 && 2ll * p.glu_I * p.K * 2 < 0xFFFFFF00ll && ((long long)(p.M - 1) * p.lda + p.K) * 2 < 0xFFFFFF00ll;
     TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(glu): more than 16 rows need K %% 64 == 0 and operands under 4 GiB");
     if (p.M > 4 && mfma) {
-      if (int rc = launch_mfma_rows(p, stream)) return rc;
-    } else if (p.M == 1) hipLaunchKernelGGL(td_gemv_bf16_kernel<1>, dim3(p.glu_I / 2), dim3(THREADS), 0, stream, p);
-    else if (p.M == 2) hipLaunchKernelGGL(td_gemv_bf16_kernel<2>, dim3(p.glu_I / 2), dim3(THREADS), 0, stream, p);
-    else if (p.M <= 4) hipLaunchKernelGGL(td_gemv_bf16_kernel<4>, dim3(p.glu_I / 2), dim3(THREADS), 0, stream, p);
-    else if (p.M <= 8) hipLaunchKernelGGL(td_gemv_bf16_kernel<8>, dim3(p.glu_I / 2), dim3(THREADS), 0, stream, p);
-    else hipLaunchKernelGGL(td_gemv_bf16_kernel<16>, dim3(p.glu_I / 2), dim3(THREADS), 0, stream, p);
+      if (int rc = launch_mfma_rows<false>(p, stream)) return rc;
+    } else launch_dot<false>(p, dim3(p.glu_I / 2), stream);
     TD_CHECK_LAUNCH();
     return 0;
   }
   if (p.M > 4 && td_gemv_mfma_ok(p)) {
-    if (int rc = launch_mfma_rows(p, stream)) return rc;
+    if (int rc = launch_mfma_rows<false>(p, stream)) return rc;
     TD_CHECK_LAUNCH();
     return 0;
   }
   TD_CHECK_ARG(p.M <= 16, "td_gemv: more than 16 rows need the matrix-core form (K %% 64, N %% 16, ldc %% 4 == 0)");
-  const dim3 grid(p.N / R), block(THREADS);
-  if (p.M == 1) hipLaunchKernelGGL(td_gemv_bf16_kernel<1>, grid, block, 0, stream, p);
-  else if (p.M == 2) hipLaunchKernelGGL(td_gemv_bf16_kernel<2>, grid, block, 0, stream, p);
-  else if (p.M <= 4) hipLaunchKernelGGL(td_gemv_bf16_kernel<4>, grid, block, 0, stream, p);
-  else if (p.M <= 8) hipLaunchKernelGGL(td_gemv_bf16_kernel<8>, grid, block, 0, stream, p);
-  else hipLaunchKernelGGL(td_gemv_bf16_kernel<16>, grid, block, 0, stream, p);
+  launch_dot<false>(p, dim3(p.N / R), stream);
   TD_CHECK_LAUNCH();
   return 0;
 }

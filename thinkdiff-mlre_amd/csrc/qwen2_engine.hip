@@ -32,7 +32,11 @@ namespace {
 
 struct QSlot { std::string name; bf16_t* ptr; int64_t count; };
 
+// the 8-bit copy of one Linear weight (td_qwen2_quantize_weights): e4m3 bytes [N, K] and the row scales 2^e_n; null on an unquantised handle
+struct W8Ref { uint8_t* q = nullptr; float* s = nullptr; };
+
 struct QLayer {
+  W8Ref qkv_8, o_8, gu_8, down_8;
   bf16_t *qkv_w, *qkv_b;   // [(Hq + 2 Hkv) * 128, D]
   bf16_t* o_w;             // [D, Hq * 128]
   bf16_t* gu_w;            // [2 I, D] = gate_proj | up_proj
@@ -74,6 +78,15 @@ struct td_qwen2 {
   bf16_t* logits_buf = nullptr;                 // [MAX_BATCH, vocab]
   int* row_map = nullptr;                       // [ws_rows] packed prefill: cache row of every packed prompt row
   std::vector<int> row_map_host;                // ... its host image (kept alive across the asynchronous upload)
+  // 8-bit weight stream (td_qwen2_quantize_weights): the e4m3 copy of every Linear weight beside the bf16 arena, which then holds the dequantised values
+  int w_mode = TD_QWEN2_WEIGHTS_BF16;
+  bool w8_on = false;                           // launches of up to 64 rows read the 8-bit copy (td_qwen2_set_weight_stream)
+  bool w8_stale = false;                        // parameters were loaded after quantising: every run is refused until td_qwen2_quantize_weights is called again
+  char* w8_arena = nullptr;
+  int64_t w8_bytes = 0;
+  int w8_linears = 0;
+  long long w8_launches = 0;                    // Linear launches enqueued (or captured) so far that read the 8-bit copy (td_qwen2_weight_stream_launches)
+  W8Ref lm_8;
   float* sk_ws = nullptr;                       // partial sums of the decode step's split-K Linears (65-256 sequences): the engine's own buffer, so a captured step allocates nothing
 };
 
@@ -89,6 +102,7 @@ void q_add(td_qwen2* f, const std::string& name, bf16_t* p, int64_t n) {
 // kernels the prefill uses, with K split over workgroups where the output is narrow (td_gemm_launch's split_k form).
 constexpr int MAX_BATCH = 256;
 constexpr int STREAM_BATCH = 64;
+constexpr int STREAM_ROWS_MAX = 64;            // rows the weight-stream kernels take (td_gemv_launch)
 constexpr int64_t SK_WS_BYTES = 32ll << 20;
 
 struct IntPack { int v[3 * MAX_BATCH]; };      // (3 KB of kernel arguments: lengths | cache rows | cache slots of a decode step)
@@ -158,10 +172,25 @@ TdGemmParams linear(const bf16_t* x, int ldx, const bf16_t* W, const bf16_t* bia
   return g;
 }
 
-// logits[M, vocab] = lm_head(rows[M, hidden]), rows = model.norm outputs
-int lm_head(td_qwen2* f, const bf16_t* rows, int M, void* logits, hipStream_t s) {
-  return td_gemm_launch(linear(rows, f->D, f->lm_w, nullptr, (bf16_t*)logits, f->cfg.vocab, M, f->cfg.vocab, f->D), s);
+// Launches a Linear of the decoder.  With the weight stream on, a launch of up to 64 rows that would reach the skinny-M kernels anyway (no tile override,
+// no K split) and has a shape their 8-bit forms take reads the e4m3 copy `w8` instead of the bf16 weight; everything else reads the bf16 arena, which
+// holds the same (dequantised) values -- the model does not depend on the route.
+int run_linear(td_qwen2* f, TdGemmParams g, const W8Ref& w8, hipStream_t s, bool allow8 = true) {
+  if (allow8 && f->w8_on && w8.q && g.M <= STREAM_ROWS_MAX && g.cfg < 0 && g.split_k == 0 && td_gemv_w8_ok(g)) {
+    g.W8 = w8.q; g.w8_scale = w8.s;
+    ++f->w8_launches;
+  }
+  return td_gemm_launch(g, s);
 }
+
+// logits[M, vocab] = lm_head(rows[M, hidden]), rows = model.norm outputs
+int lm_head(td_qwen2* f, const bf16_t* rows, int M, void* logits, hipStream_t s, bool allow8 = true) {
+  return run_linear(f, linear(rows, f->D, f->lm_w, nullptr, (bf16_t*)logits, f->cfg.vocab, M, f->cfg.vocab, f->D), f->lm_8, s, allow8);
+}
+
+// every entry that runs the model: a handle whose parameters changed after quantising is refused, never run half-quantised
+#define TD_QWEN2_FRESH(f, fn) \
+  TD_CHECK_ARG(!(f)->w8_stale, "%s: parameters were loaded after the weights were quantised; call td_qwen2_quantize_weights again first", fn)
 
 // two rows on one slot would write the same cache row: refused, not left to corrupt a sequence
 int check_distinct_slots(const char* fn, const char* unit, const int* slots, int B) {
@@ -221,7 +250,7 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
       if (QW % 256 == 0) {
         // the column split needs a tile width that divides 256: every config but the 288x192 one
         g.cfg = n <= 32 ? -1 : (td_gemm_config_id(n, QW + KVW, D) == 1 ? 1 : 0);
-        TD_TRY(td_gemm_launch(g, s));
+        TD_TRY(run_linear(f, g, l.qkv_8, s));
       } else {
         TdGemmParams a = g; a.C2 = nullptr; a.N = QW;
         TD_TRY(td_gemm_launch(a, s));
@@ -238,13 +267,13 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
     ap.K = form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
     TD_TRY(td_attn_launch(ap, s));
     // h += o_proj(attn)
-    TD_TRY(td_gemm_launch(linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), s));
+    TD_TRY(run_linear(f, linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), l.o_8, s));
     np.w = l.ln2_w;
     TD_TRY(td_norm_rows_launch(np, s));
     // gate | up, SwiGLU, down (+ residual)
-    TD_TRY(td_gemm_launch(linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, n, 2 * I, D), s));
+    TD_TRY(run_linear(f, linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, n, 2 * I, D), l.gu_8, s));
     TD_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
-    TD_TRY(td_gemm_launch(linear(f->act, I, l.down_w, nullptr, f->h, D, n, D, I, true), s));
+    TD_TRY(run_linear(f, linear(f->act, I, l.down_w, nullptr, f->h, D, n, D, I, true), l.down_8, s));
   }
   // model.norm -> captured embedding
   np.w = f->norm_w;
@@ -371,7 +400,68 @@ void td_qwen2_destroy(td_qwen2* f) {
   if (f->capture_stream) (void)hipStreamDestroy(f->capture_stream);
   (void)hipFree(f->arena);
   (void)hipFree(f->ws);
+  if (f->w8_arena) (void)hipFree(f->w8_arena);
   delete f;
+}
+
+int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream) {
+  TD_CHECK_ARG(f, "td_qwen2_quantize_weights: null handle");
+  TD_CHECK_ARG(mode == TD_QWEN2_WEIGHTS_E4M3, "td_qwen2_quantize_weights: unknown mode %d (TD_QWEN2_WEIGHTS_E4M3 = %d is the one served)", mode, TD_QWEN2_WEIGHTS_E4M3);
+  const int D = f->D, I = f->I, QW = f->Hq * 128, NQKV = (f->Hq + 2 * f->Hkv) * 128;
+  struct Lin { bf16_t* w; W8Ref* ref; int N, K; };
+  std::vector<Lin> lins;
+  for (QLayer& l : f->layers) {
+    lins.push_back({l.qkv_w, &l.qkv_8, NQKV, D});
+    lins.push_back({l.o_w, &l.o_8, D, QW});
+    lins.push_back({l.gu_w, &l.gu_8, 2 * I, D});
+    lins.push_back({l.down_w, &l.down_8, D, I});
+  }
+  lins.push_back({f->lm_w, &f->lm_8, f->cfg.vocab, D});      // (tied embeddings: this is the embedding table)
+  if (!f->w8_arena) {
+    int64_t total = 0;
+    for (const Lin& x : lins) total += (((int64_t)x.N * x.K + 255) & ~int64_t(255)) + (((int64_t)x.N * 4 + 255) & ~int64_t(255));
+    hipError_t e = hipMalloc((void**)&f->w8_arena, (size_t)total);
+    if (e != hipSuccess) {
+      f->w8_arena = nullptr;
+      td_set_error("td_qwen2_quantize_weights: hipMalloc of %.2f GiB for the 8-bit copy failed: %s", total / double(1 << 30), hipGetErrorString(e));
+      return TD_ERR_HIP;
+    }
+    int64_t o = 0;
+    for (const Lin& x : lins) {
+      x.ref->q = (uint8_t*)(f->w8_arena + o); o += ((int64_t)x.N * x.K + 255) & ~int64_t(255);
+      x.ref->s = (float*)(f->w8_arena + o); o += ((int64_t)x.N * 4 + 255) & ~int64_t(255);
+    }
+    f->w8_bytes = 0;
+    for (const Lin& x : lins) f->w8_bytes += (int64_t)x.N * x.K + (int64_t)x.N * 4;      // (reported without the padding between the pieces)
+    f->w8_linears = (int)lins.size();
+  }
+  drop_step_graphs(f);      // the captured steps carry the bf16 launch list
+  f->w8_stale = true;       // (a failing launch below must not leave a half-quantised handle runnable)
+  f->w_mode = mode;
+  for (const Lin& x : lins) TD_TRY(td_quant_weight_rows_launch(x.w, x.K, x.ref->q, x.ref->s, x.w, x.N, x.K, (hipStream_t)stream));
+  f->w8_stale = false;
+  f->w8_on = true;
+  return TD_OK;
+}
+
+int td_qwen2_set_weight_stream(td_qwen2* f, int on) {
+  TD_CHECK_ARG(f, "td_qwen2_set_weight_stream: null handle");
+  TD_CHECK_ARG(f->w_mode != TD_QWEN2_WEIGHTS_BF16, "td_qwen2_set_weight_stream: the handle is not quantised (td_qwen2_quantize_weights first)");
+  const int prev = f->w8_on ? 1 : 0;
+  f->w8_on = on != 0;
+  drop_step_graphs(f);      // the captured steps carry the old launch list
+  return prev;
+}
+
+int64_t td_qwen2_weight_stream_launches(const td_qwen2* f) { return f ? (int64_t)f->w8_launches : -1; }
+
+int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* bytes_8bit, int* n_linears) {
+  TD_CHECK_ARG(f, "td_qwen2_weight_info: null handle");
+  if (mode) *mode = f->w_mode;
+  if (stream_on) *stream_on = f->w8_on ? 1 : 0;
+  if (bytes_8bit) *bytes_8bit = f->w8_bytes;
+  if (n_linears) *n_linears = f->w8_linears;
+  return TD_OK;
 }
 
 int td_qwen2_num_params(const td_qwen2* f) { return f ? (int)f->slots.size() : 0; }
@@ -393,11 +483,13 @@ int td_qwen2_load_param(td_qwen2* f, const char* name, const void* src, int64_t 
   const QSlot& s = f->slots[it->second];
   TD_CHECK_ARG(s.count == count, "td_qwen2_load_param: '%s' expects %lld elements, got %lld", name, (long long)s.count, (long long)count);
   TD_CHECK_HIP(hipMemcpyAsync(s.ptr, src, (size_t)count * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (f->w_mode != TD_QWEN2_WEIGHTS_BF16) f->w8_stale = true;      // the 8-bit copy no longer matches: td_qwen2_quantize_weights again
   return TD_OK;
 }
 
 int td_qwen2_init_random(td_qwen2* f, uint64_t seed, float std, void* stream) {
   TD_CHECK_ARG(f, "td_qwen2_init_random: null handle");
+  if (f->w_mode != TD_QWEN2_WEIGHTS_BF16) f->w8_stale = true;
   TD_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
   for (const QSlot& s : f->slots)
     if (s.name.find("layernorm.weight") != std::string::npos || s.name == "model.norm.weight")
@@ -409,6 +501,7 @@ int td_qwen2_init_random(td_qwen2* f, uint64_t seed, float std, void* stream) {
 // rows with the vision tower's merged tokens ([ext] Qwen2VLModel.forward masked_scatter).
 int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, void* stream) {
   TD_CHECK_ARG(f && token_ids && out && n > 0, "td_qwen2_embed_tokens: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_embed_tokens");      // (with tied embeddings the table is a quantised weight; untied handles are refused too: one rule)
   return td_embed_gather_launch(token_ids, f->embed_w, (bf16_t*)out, n, f->D, f->cfg.vocab, (hipStream_t)stream);
 }
 
@@ -423,6 +516,7 @@ int td_qwen2_embed_tokens(td_qwen2* f, const int* token_ids, void* out, int n, v
 int td_qwen2_forward_slot(td_qwen2* f, int slot, const int* token_ids, const void* inputs_embeds, const int* position_ids, int n,
                           int pos0, void* hidden_out, void* logits_last, void* stream) {
   TD_CHECK_ARG(f && position_ids && (token_ids || inputs_embeds), "td_qwen2_forward: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_forward");
   TD_CHECK_ARG(slot >= 0 && slot < f->n_slots, "td_qwen2_forward: slot %d outside the %d configured sequences", slot, f->n_slots);
   TD_CHECK_ARG(n > 0 && pos0 >= 0 && pos0 + n <= f->slot_len, "td_qwen2_forward: positions [%d, %d) exceed the cache capacity %d", pos0, pos0 + n, f->slot_len);
   hipStream_t s = (hipStream_t)stream;
@@ -493,7 +587,13 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
   // 18 % ahead on the tiles at 64 (5.44 vs 6.63 ms).  TD_QWEN2_STREAM_BATCH (>= 16): A/B.
   static const int env_stream_batch = getenv("TD_QWEN2_STREAM_BATCH") ? atoi(getenv("TD_QWEN2_STREAM_BATCH")) : 0;
   const int stream_batch = env_stream_batch > 0 ? (env_stream_batch < 16 ? 16 : env_stream_batch) : (D >= 3072 ? 32 : STREAM_BATCH);
-  const bool wide = B > stream_batch;
+  // With the 8-bit stream on, a step of up to 64 sequences moves half the bytes, so it stays on the stream kernels on both shapes
+  // (tools/bench_qwen2_w8.py measures every batch bucket against the bf16 routing of the same handle)
+  const bool wide = B > (f->w8_on ? STREAM_BATCH : stream_batch);
+  // ... every bucket but one: two sequences measured 3 % SLOWER on the bytes than on bf16 W^ (1.503 vs 1.461 ms per step, profiles/qwen2_w8_bench.json),
+  // so that step reads bf16 W^ -- the same model, no cost in numerics.  Measured on the 2B shape (hidden 1536) ONLY; the rule is drawn at the width
+  // that already separates the two measured shapes (hidden < 3072), other narrow widths have not been timed
+  const bool a8 = !(B == 2 && D < 3072);
 
   TD_TRY(td_embed_gather_launch(f->tok_buf, f->embed_w, f->h, B, D, f->cfg.vocab, s));
   TD_TRY(td_mrope_table_launch(f->pos_buf, B, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));
@@ -510,7 +610,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
       TdGemmParams g = linear(f->xn, D, l.qkv_w, l.qkv_b, f->q, QW, B, QW + KVW, D);
       g.C2 = f->kvtmp; g.ldc2 = KVW; g.n_split = QW;
       if (wide) { g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES; }      // (tile width and parts by the wide planner: n_split = Hq 128 fits its 64- / 128-column tiles)
-      TD_TRY(td_gemm_launch(g, s));
+      TD_TRY(run_linear(f, g, l.qkv_8, s, a8));
     }
     // rotary embedding of the new q / k rows and the cache write ride inside the attention launch (TdAttnParams::dec_kv_new);
     // td_qwen2_set_fused_rope(f, 0): the separate launch (A/B and the bit-identity test)
@@ -528,7 +628,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
         g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
         g.sk_norm_w = l.ln2_w; g.sk_norm_out = f->xn; g.sk_norm_ld = D; g.sk_norm_eps = f->cfg.rms_eps;
       }
-      TD_TRY(td_gemm_launch(g, s));
+      TD_TRY(run_linear(f, g, l.o_8, s, a8));
     }
     if (!wide) {
       np.w = l.ln2_w;
@@ -537,7 +637,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     if (!wide) {
       TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->act, I, B, I, D);
       g.glu_I = I;   // gate | up, SiLU and product in one pass
-      TD_TRY(td_gemm_launch(g, s));
+      TD_TRY(run_linear(f, g, l.gu_8, s, a8));
     } else {      // the prefill's form: gate | up as one Linear, SiLU and product in a pass of their own (the same rounding points)
       TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, B, 2 * I, D);
       g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
@@ -550,13 +650,13 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
       d.sk_norm_w = i + 1 < f->cfg.num_layers ? f->layers[i + 1].ln1_w : f->norm_w;      // the next layer's input norm, or model.norm
       d.sk_norm_out = f->xn; d.sk_norm_ld = D; d.sk_norm_eps = f->cfg.rms_eps;
     }
-    TD_TRY(td_gemm_launch(d, s));
+    TD_TRY(run_linear(f, d, l.down_8, s, a8));
   }
   if (!wide) {
     np.w = f->norm_w; np.y = f->xn;
     TD_TRY(td_norm_rows_launch(np, s));
   }
-  if (want_logits) TD_TRY(lm_head(f, f->xn, B, f->logits_buf, s));
+  if (want_logits) TD_TRY(lm_head(f, f->xn, B, f->logits_buf, s, a8));
   TD_CHECK_LAUNCH();
   return TD_OK;
 }
@@ -577,6 +677,7 @@ int td_qwen2_decode_batch(td_qwen2* f, int B, const int* token_ids, const int* p
 int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int* token_ids, const int* position_ids, const int* cache_pos,
                                 void* hidden_out, void* logits, void* stream) {
   TD_CHECK_ARG(f && token_ids && position_ids && cache_pos, "td_qwen2_decode_batch: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_decode_batch");
   TD_CHECK_ARG(B >= 1 && B <= MAX_BATCH && B <= f->n_slots && B <= f->ws_rows, "td_qwen2_decode_batch: batch %d exceeds min(%d, %d slots, %d workspace rows)", B, MAX_BATCH, f->n_slots, f->ws_rows);
   hipStream_t s = (hipStream_t)stream;
   const int D = f->D;
@@ -646,6 +747,7 @@ int td_qwen2_prefill_batch(td_qwen2* f, int B, int L, const int* token_ids, cons
 int td_qwen2_prefill_batch_at(td_qwen2* f, int slot0, int B, int L, const int* token_ids, const void* inputs_embeds, const int* position_ids,
                               const int* lens, void* hidden_out, void* logits_last, void* stream) {
   TD_CHECK_ARG(f && position_ids && lens && (token_ids || inputs_embeds), "td_qwen2_prefill_batch: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_prefill_batch");
   TD_CHECK_ARG(slot0 >= 0 && B >= 1 && B <= MAX_BATCH && slot0 + B <= f->n_slots && L >= 1 && L <= f->slot_len && (long long)B * L <= f->ws_rows,
                "td_qwen2_prefill_batch: slots [%d, %d) x L=%d exceed the handle (slots %d x %d tokens, workspace %d rows)", slot0, slot0 + B, L, f->n_slots, f->slot_len, f->ws_rows);
   for (int b = 0; b < B; ++b) TD_CHECK_ARG(lens[b] >= 1 && lens[b] <= L, "td_qwen2_prefill_batch: sequence %d has %d of %d tokens", b, lens[b], L);
@@ -684,6 +786,7 @@ int td_qwen2_prefill_packed(td_qwen2* f, int slot0, int B, const int* token_ids,
 int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const int* token_ids, const void* inputs_embeds, const int* position_ids,
                                   const int* lens, void* hidden_out, void* logits_last, void* stream) {
   TD_CHECK_ARG(f && slots && position_ids && lens && (token_ids || inputs_embeds), "td_qwen2_prefill_packed: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_prefill_packed");
   TD_CHECK_ARG(B >= 1 && B <= MAX_BATCH, "td_qwen2_prefill_packed: %d sequences (1 .. %d)", B, MAX_BATCH);
   for (int b = 0; b < B; ++b) TD_CHECK_ARG(slots[b] >= 0 && slots[b] < f->n_slots, "td_qwen2_prefill_packed: sequence %d names cache slot %d of %d", b, slots[b], f->n_slots);
   TD_TRY(check_distinct_slots("td_qwen2_prefill_packed", "sequence", slots, B));

@@ -51,6 +51,10 @@ struct TdGemmParams {
   // C[m, n] = bf16(bf16(silu(bf16(x.gate_n))) * bf16(x.up_n)) -- Linear, SiLU and the product each round, as the separate kernels do
   int glu_I = 0;
   int fp8 = 0;
+  // 8-bit weight stream (skinny-M kernels only, M <= 64; W is then unused): W8 = OCP e4m3 bytes [N, K] (gated form: [2 glu_I, K]), w8_scale[n] = 2^e_n,
+  // the format td_quant_weight_rows_launch writes.  The kernels convert with the row's scale inside the conversion, so the dot products / MFMAs see
+  // the bf16 values q * 2^e exactly -- the operands the bf16 kernels see when W holds the dequantised weights; only the fp32 summation order may differ.
+  const uint8_t* W8 = nullptr; const float* w8_scale = nullptr;
   // int8 operands (i8 = 1): A and W hold symmetric int8 (lda, K in elements = bytes), v_mfma_i32_16x16x64_i8, exact int32 accumulation;
   // y = float(acc) * a_scale[m] * w_scale[n] -- the same scale arrays and the same 2x-bf16 MFMA rate as the fp8 form
   int i8 = 0;
@@ -76,6 +80,10 @@ int td_gemm_launch(const TdGemmParams& p, hipStream_t stream);
 // weight-streaming form for M <= 8 (td_gemm_launch routes to it; csrc/gemv_bf16.hip)
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream);
 bool td_gemv_mfma_ok(const TdGemmParams& p);   // shapes the matrix-core weight stream takes for 16 < M <= 64
+bool td_gemv_w8_ok(const TdGemmParams& p);     // shapes the 8-bit weight stream takes (p.W8 need not be set yet): what td_gemv_launch would accept with W8
+// Weight-only e4m3 quantisation with one power-of-two scale per row (csrc/quant_weight.hip): q[n, k] = e4m3_rne(w[n, k] 2^-e_n), scale[n] = 2^e_n, e_n the
+// smallest integer with max_k |w[n, k]| 2^-e_n <= 448 (clamped to [-40, 40]; 0 for a zero row); w_hat (may be null, may alias w) = q 2^e_n as bf16, exactly
+int td_quant_weight_rows_launch(const bf16_t* w, long long ldw, uint8_t* q, float* scale, bf16_t* w_hat, int N, int K, hipStream_t stream);
 // 0: 256x256 (td_gemm_bf16_nt_kernel<8,4>), 1: 256x64, 2: 32x256, 3: 288x192 (<9,3>)
 int td_gemm_config_id(int M, int N, int K);
 

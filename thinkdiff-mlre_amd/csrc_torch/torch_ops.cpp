@@ -61,6 +61,37 @@ at::Tensor linear(const at::Tensor& x, const at::Tensor& w, const c10::optional<
   return y;
 }
 
+// Weight-only e4m3 quantisation with one power-of-two scale per row (td_quant_weight_rows_e4m3): w [N,K] -> (q uint8 [N,K], scale fp32 [N], w_hat bf16 [N,K])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quant_weight_rows_e4m3(const at::Tensor& w) {
+  check_rows(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous(), "thinkdiff_hip::quant_weight_rows_e4m3: w [N,K] contiguous");
+  DeviceGuard guard(w.device());
+  at::Tensor q = at::empty({w.size(0), w.size(1)}, w.options().dtype(at::kByte));
+  at::Tensor scale = at::empty({w.size(0)}, w.options().dtype(at::kFloat));
+  at::Tensor w_hat = at::empty_like(w);
+  ok(td_quant_weight_rows_e4m3(w.data_ptr(), w.stride(0), q.data_ptr(), (float*)scale.data_ptr(), w_hat.data_ptr(), (int)w.size(0), (int)w.size(1), stream_of(w)));
+  return std::make_tuple(q, scale, w_hat);
+}
+
+// linear with the weight given as e4m3 bytes + row scales (the 8-bit weight stream, M <= 64)
+at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& w_scale, const c10::optional<at::Tensor>& bias, int64_t act,
+                     const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& res) {
+  check_rows(x, "x"); check_rows(wq, "wq", at::kByte); same_device(wq, "wq", x);
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 2 && wq.is_contiguous() && wq.size(1) == x.size(1), "thinkdiff_hip::linear_w8: x [M,K], wq uint8 [N,K] contiguous");
+  check_vec(w_scale, "w_scale", x, wq.size(0), at::kFloat);
+  check_vec(bias, "bias", x, wq.size(0)); check_vec(gate, "gate", x, wq.size(0));
+  if (res.has_value() && res->defined()) {
+    check_rows(*res, "res"); same_device(*res, "res", x);
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == x.size(0) && res->size(1) == wq.size(0), "thinkdiff_hip::linear_w8: res must be [M,N]");
+  }
+  DeviceGuard guard(x.device());
+  at::Tensor y = at::empty({x.size(0), wq.size(0)}, x.options());
+  const int64_t ldr = res.has_value() && res->defined() ? res->stride(0) : 0;
+  ok(td_linear_w8_bf16(x.data_ptr(), x.stride(0), wq.data_ptr(), (const float*)w_scale.data_ptr(), P(bias), y.data_ptr(), y.stride(0), (int)x.size(0),
+                       (int)wq.size(0), (int)x.size(1), (int)act, P(gate), P(res), ldr, stream_of(x)));
+  return y;
+}
+
 // ThinkDiff aligner mm_projector "mlp2x_gelu_t5_norm": T5LayerNorm(Linear2(GELU_erf(Linear0(x))))
 at::Tensor aligner_mlp2x(const at::Tensor& x, const at::Tensor& w0, const at::Tensor& b0, const at::Tensor& w2, const at::Tensor& b2,
                          const at::Tensor& norm_w, double eps, bool fp32_norm) {
@@ -777,6 +808,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_lora_load(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()");
   m.def("flux_lora_set_adapters(int engine, str[] names, float[] weights) -> ()");
   m.def("flux_lora_delete(int engine, str adapter) -> ()");
+  m.def("quant_weight_rows_e4m3(Tensor w) -> (Tensor, Tensor, Tensor)");
+  m.def("linear_w8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -820,6 +853,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("ip_attention_", &ip_attention_);
   m.impl("flux_ip_adapter_load_param", &flux_ip_adapter_load_param);
   m.impl("flux_set_ip_image_embeds", &flux_set_ip_image_embeds);
+  m.impl("quant_weight_rows_e4m3", &quant_weight_rows_e4m3);
+  m.impl("linear_w8", &linear_w8);
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {

@@ -200,6 +200,14 @@ def _declare(L):
         "td_qwen2_move_slot": [vp, i32, i32, i32, vp],
         "td_qwen2_decode_batch": [vp, i32, vp, vp, vp, vp, vp, vp],
         "td_qwen2_decode_batch_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
+        "td_qwen2_quantize_weights": [vp, i32, vp],
+        "td_qwen2_set_weight_stream": [vp, i32],
+        "td_qwen2_weight_info": [vp, vp, vp, vp, vp],
+        "td_quant_weight_rows_e4m3": [vp, i64, vp, vp, vp, i32, i32, vp],
+        "td_linear_w8_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp],
+        "td_linear_split_w8_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
+        "td_linear_glu_bf16": [vp, i64, vp, vp, i64, i32, i32, i32, vp],
+        "td_linear_glu_w8_bf16": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
         "td_embed_gather_bf16": [vp, vp, vp, i32, i32, i32, vp],
         "td_silu_mul_bf16": [vp, vp, i32, i32, vp],
         "td_mrope_table": [vp, i32, vp, f32, i32, vp, vp, vp],
@@ -223,6 +231,8 @@ def _declare(L):
     L.td_vae_enc_destroy.restype = None
     L.td_qwen2_destroy.argtypes = [vp]
     L.td_qwen2_destroy.restype = None
+    L.td_qwen2_weight_stream_launches.argtypes = [vp]
+    L.td_qwen2_weight_stream_launches.restype = ctypes.c_int64
     L.td_flux_param_elems.argtypes = [vp]
     L.td_flux_param_elems.restype = ctypes.c_int64
     L.td_lora_packed_bytes.argtypes = [i32, i32, i32]
@@ -263,6 +273,67 @@ def linear(x, w, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
         out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
     check(lib().td_linear_bf16(ptr(x), _rows(x), ptr(w), ptr(bias), ptr(out), _rows(out), M, N, K, act,
                                ptr(gate), ptr(res), _rows(res) if res is not None else 0, stream_ptr()))
+    return out
+
+
+QWEN2_WEIGHTS_BF16, QWEN2_WEIGHTS_E4M3 = 0, 1
+
+
+def quant_weight_rows_e4m3(w, want_w_hat=True, inplace=False):
+    """Weight-only e4m3 quantisation with one power-of-two scale per row (td_quant_weight_rows_e4m3): w bf16 [N, K] (row stride may exceed K) ->
+    (q uint8 [N, K], scale fp32 [N] = 2^e_n, w_hat bf16 = q 2^e_n exactly, or None).  inplace: w_hat is written over w."""
+    N, K = w.shape
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    scale = torch.empty((N,), dtype=torch.float32, device=w.device)
+    w_hat = w if inplace else (torch.empty_like(w) if want_w_hat else None)
+    if w_hat is not None:
+        assert w_hat.stride(0) == w.stride(0)
+    check(lib().td_quant_weight_rows_e4m3(ptr(w), _rows(w), ptr(q), ptr(scale), ptr(w_hat), N, K, stream_ptr()))
+    return q, scale, w_hat
+
+
+def _w8(x, wq, w_scale):
+    M, K = x.shape
+    assert wq.dtype == torch.uint8 and wq.dim() == 2 and wq.is_contiguous() and wq.shape[1] == K, (wq.shape, wq.dtype, K)
+    assert w_scale.dtype == torch.float32 and w_scale.is_contiguous() and w_scale.numel() == wq.shape[0]
+    return M, wq.shape[0], K
+
+
+def linear_w8(x, wq, w_scale, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
+    """linear() with the weight as e4m3 bytes + row scales (the 8-bit weight stream; M <= 64)."""
+    M, N, K = _w8(x, wq, w_scale)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_w8_bf16(ptr(x), _rows(x), ptr(wq), ptr(w_scale), ptr(bias), ptr(out), _rows(out), M, N, K, act,
+                                  ptr(gate), ptr(res), _rows(res) if res is not None else 0, stream_ptr()))
+    return out
+
+
+def linear_split_w8(x, wq, w_scale, bias, out0, act0, out1, act1, n_split):
+    M, N, K = _w8(x, wq, w_scale)
+    check(lib().td_linear_split_w8_bf16(ptr(x), _rows(x), ptr(wq), ptr(w_scale), ptr(bias), ptr(out0), _rows(out0), act0,
+                                        ptr(out1), _rows(out1), act1, M, N, K, n_split, stream_ptr()))
+    return out0, out1
+
+
+def linear_glu(x, w, out=None):
+    """out[m, n] = bf16(bf16(silu(bf16(x . w[n]))) * bf16(x . w[I + n])) for w = [gate rows | up rows] ([2 I, K]); M <= 64 (td_linear_glu_bf16)."""
+    M, K = x.shape
+    assert w.dim() == 2 and w.is_contiguous() and w.shape[1] == K and w.shape[0] % 2 == 0
+    inter = w.shape[0] // 2
+    if out is None:
+        out = torch.empty((M, inter), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_glu_bf16(ptr(x), _rows(x), ptr(w), ptr(out), _rows(out), M, inter, K, stream_ptr()))
+    return out
+
+
+def linear_glu_w8(x, wq, w_scale, out=None):
+    """linear_glu() with the weight as e4m3 bytes + row scales."""
+    M, N2, K = _w8(x, wq, w_scale)
+    assert N2 % 2 == 0
+    if out is None:
+        out = torch.empty((M, N2 // 2), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_glu_w8_bf16(ptr(x), _rows(x), ptr(wq), ptr(w_scale), ptr(out), _rows(out), M, N2 // 2, K, stream_ptr()))
     return out
 
 

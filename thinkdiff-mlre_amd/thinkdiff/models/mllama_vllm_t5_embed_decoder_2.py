@@ -39,9 +39,12 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
                                       mm_hidden_size=(text_config or Qwen2VLTextConfig()).hidden_size, hidden_size=hidden_size)
         self._device = torch.device(device)
         # vLLM decodes up to `max_num_seqs` requests together; the engine advances up to 256 per decode step
+        quantization = Qwen2VLTextEngine.check_quantization(vc.get("quantization"))      # (before the engine allocates anything)
         self.decode_batch = max(1, min(Qwen2VLTextEngine.MAX_BATCH, int(vc.get("max_num_seqs", 1))))
         self.mllama = Qwen2VLTextEngine(text_config, max_model_len=vc.get("max_model_len", 8192), device=device, n_slots=self.decode_batch,
                                         prefill_rows=min(int(vc.get("max_num_batched_tokens", 16384)), 16384) if self.decode_batch > 1 else None)
+        # vLLM's `quantization="fp8"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
+        self.mllama.weight_quantization = quantization
         self.mllama_sampling_params = SamplingParams(
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),
             min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True))

@@ -65,6 +65,9 @@ class Qwen2VLTextEngine:
             self.prefill_rows = max(int(prefill_rows or 0), max_model_len)
             _hip.check(self._L.td_qwen2_create_ex(ctypes.byref(cc), max_model_len, int(n_slots), self.prefill_rows, ctypes.byref(h)))
         self._h = h
+        # set by the models from vllm_config["quantization"]: every load below then ends with quantize_weights (None: the bf16 engine, untouched)
+        self.weight_quantization: Optional[str] = None
+        self._defer_quantize = False
         self.n_slots, self.slot_len = int(n_slots), max_model_len
         self.max_model_len = max_model_len
 
@@ -91,7 +94,13 @@ class Qwen2VLTextEngine:
                 d = t.to(device=self.device, dtype=torch.bfloat16).contiguous()
                 _hip.check(self._L.td_qwen2_load_param(self._h, name.encode(), _hip.ptr(d), d.numel(), _hip.stream_ptr()))
                 torch.cuda.current_stream().synchronize()
+        self._requantize()
         return missing
+
+    def _requantize(self):
+        # a quantised engine whose parameters changed refuses to run until it is quantised again: do it here rather than leave the handle stale
+        if self.weight_quantization and not self._defer_quantize:
+            self.quantize_weights(self.weight_quantization)
 
     def load_pretrained(self, path: str):
         """Text-decoder tensors of a LOCAL Hugging Face Qwen2-VL checkpoint directory (*.safetensors; `visual.*` skipped)."""
@@ -102,24 +111,68 @@ class Qwen2VLTextEngine:
         if not files:
             raise FileNotFoundError(f"no *.safetensors under {path}")
         seen = set()
-        for fn in files:
-            with safe_open(fn, framework="pt") as fh:
-                sd = {}
-                for k in fh.keys():
-                    if "visual." in k:
-                        continue
-                    name = k.replace("model.language_model.", "model.")     # newer exports nest the decoder
-                    sd[name] = fh.get_tensor(k)
-                seen.update(sd)
-                self.load_state_dict(sd, strict=False)
+        self._defer_quantize = True      # (one quantisation behind the last shard, not one per shard)
+        try:
+            for fn in files:
+                with safe_open(fn, framework="pt") as fh:
+                    sd = {}
+                    for k in fh.keys():
+                        if "visual." in k:
+                            continue
+                        name = k.replace("model.language_model.", "model.")     # newer exports nest the decoder
+                        sd[name] = fh.get_tensor(k)
+                    seen.update(sd)
+                    self.load_state_dict(sd, strict=False)
+        finally:
+            self._defer_quantize = False
         missing = [k for k in self.param_table() if k not in seen and not (k == "lm_head.weight" and self.config.tie_word_embeddings)]
         if missing:
             raise KeyError(f"checkpoint at {path} lacks {len(missing)} decoder tensors, e.g. {missing[:3]}")
+        self._requantize()
         return self
 
     def init_random(self, seed: int = 0, std: float = 0.02):
         _hip.check(self._L.td_qwen2_init_random(self._h, seed, std, _hip.stream_ptr()))
+        self._requantize()
         return self
+
+    # ---- 8-bit weight stream --------------------------------------------------------------------------------
+    WEIGHT_QUANTIZATIONS = {"fp8": _hip.QWEN2_WEIGHTS_E4M3}
+
+    @classmethod
+    def check_quantization(cls, value):
+        """vllm_config["quantization"] as the models take it: None (bf16) or "fp8"; anything else is an error, never ignored."""
+        if value is not None and value not in cls.WEIGHT_QUANTIZATIONS:
+            raise ValueError(f"vllm_config quantization={value!r} is not served by the HIP engine: only 'fp8' (weight-only e4m3), or None for bf16")
+        return value
+
+    def quantize_weights(self, quantization: str = "fp8"):
+        """Weight-only fp8 of every decoder Linear and lm_head (vLLM's `quantization="fp8"`): e4m3 bytes with one power-of-two scale per output row
+        beside the bf16 weights, which are OVERWRITTEN with the dequantised values (exactly representable; with tied embeddings the embedding table too).
+        Decode steps of up to 64 sequences then stream the bytes; prefill and wider steps run the same model in bf16.  Call after the weights
+        are loaded, and again after any later load_state_dict / init_random (runs are refused until then)."""
+        if quantization not in Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS:
+            raise ValueError(f"Qwen2VLTextEngine.quantize_weights: quantization={quantization!r} is not served (only 'fp8')")
+        _hip.check(self._L.td_qwen2_quantize_weights(self._h, Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS[quantization], _hip.stream_ptr()))
+        return self
+
+    def set_weight_stream(self, on: bool) -> bool:
+        """A/B switch of a quantised engine: launches of up to 64 rows read the 8-bit copy (default) or the dequantised bf16 weights -- the same
+        model either way.  Returns the previous setting."""
+        rc = self._L.td_qwen2_set_weight_stream(self._h, 1 if on else 0)
+        if rc not in (0, 1):
+            _hip.check(rc)
+        return bool(rc)
+
+    def weight_stream_launches(self) -> int:
+        """Linear launches enqueued so far that read the 8-bit copy (a captured decode step counts when captured, not per replay)."""
+        return int(self._L.td_qwen2_weight_stream_launches(self._h))
+
+    def weight_info(self) -> dict:
+        mode, on, nbytes, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
+        _hip.check(self._L.td_qwen2_weight_info(self._h, ctypes.byref(mode), ctypes.byref(on), ctypes.byref(nbytes), ctypes.byref(n)))
+        return {"mode": {v: k for k, v in self.WEIGHT_QUANTIZATIONS.items()}.get(mode.value, "bf16"), "stream_on": bool(on.value),
+                "bytes_8bit": int(nbytes.value), "n_linears": int(n.value)}
 
     # ---- one decoder pass over n new tokens ---------------------------------------------------------------
     def set_slots(self, n_slots: int):

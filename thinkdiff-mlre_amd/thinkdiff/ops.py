@@ -47,6 +47,8 @@ redux_compose              FluxPriorReduxPipeline's `cat([text, image_embeds], 1
                            bf16 products, fp32 sum in index order, one rounding
 image_resize_u8            PIL's `Image.resize` (LANCZOS / BILINEAR / BICUBIC, with `convert("RGB")` of "L" / "RGBA" folded in) on a uint8 HWC image: Pillow's
                            fixed-point horizontal and vertical passes as two kernels over host-made coefficient tables, the same bytes
+quant_weight_rows_e4m3 / linear_w8   weight-only fp8 of an nn.Linear (vLLM's `quantization="fp8"` on the LVLM): e4m3 bytes with one power-of-two scale per
+                           output row (bytes, scales and the dequantised bf16 weight, which is exact), and the Linear of up to 64 rows that streams the bytes
 """
 import os
 
@@ -99,6 +101,8 @@ SCHEMAS = {
     "flux_ip_read": "(int engine, int slot, int block, int which) -> Tensor",
     "redux_compose": "(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor",
     "image_resize_u8": "(Tensor img, int out_h, int out_w, int resample, int? out_channels) -> Tensor",
+    "quant_weight_rows_e4m3": "(Tensor w) -> (Tensor, Tensor, Tensor)",
+    "linear_w8": "(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor",
 }
 
 _loaded = False
