@@ -962,6 +962,46 @@ int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* 
  * W^", which the outputs alone cannot (the model is the same).  -1 on a NULL handle. */
 int64_t td_qwen2_weight_stream_launches(const td_qwen2* f);
 
+/* ---- e4m3 KV cache (td_abi_version() >= 13; vLLM's `kv_cache_dtype="fp8"`) --------------------------------------------------------------------
+ * Format (fixed): the weight format above applied to every 128-wide head vector x of a cache row (one token of one sequence, one layer; the rotated
+ * k | v row of 2 Hkv head vectors):
+ *   amax = max_d |x_d|;  e = the smallest integer with amax 2^-e <= 448, clamped to [-40, 40] (0 for an all-zero vector);
+ *   q_d = e4m3_rne(x_d 2^-e) (OCP e4m3, saturating at +-448; the product is exact in fp32: one rounding);  x^_d = q_d 2^e.
+ * Per layer a BYTES plane [max_tokens, 2 Hkv 128] u8 (k heads then v heads, the column order of the bf16 row) and a SCALE plane fp32 [max_tokens, 2 Hkv]
+ * holding 2^e (column h = k head h, column Hkv + h = v head h): KVW + 8 Hkv bytes per row against 2 KVW (KVW = 2 Hkv 128), a ratio of 0.516.
+ * x^ is a bf16 value exactly, so a handle in this mode is an ordinary bf16 engine whose cache holds K^ | V^, and EVERY consumer sees those values:
+ * the decode step, the prefill's own attention (the rows are rounded before it runs) and a continued td_qwen2_forward.  A result never depends on whether
+ * a key came from registers, the staging rows or the cache.  The scales are powers of two, so the kernels fold them inside the conversion instructions
+ * (v_cvt_scalef32_pk_bf16_fp8 for k into v_dot2c, v_cvt_scalef32_pk_f32_fp8 for v): exact, the arithmetic from there on is that of the bf16 kernel.
+ * DEVIATION from vLLM: vLLM stores e4m3 under ONE per-tensor scale (1.0 without calibration).  Here every (token, kv head, k or v) has its own scale, 3 %
+ * of the bytes, which removes the saturation and underflow risk of an uncalibrated scale on Qwen2's large rotated keys.
+ * The tile (prefill) attention does not read this format: prefills attend over bf16 staging rows that hold the same values. */
+enum { TD_QWEN2_KV_BF16 = 0, TD_QWEN2_KV_E4M3 = 1 };
+/* td_qwen2_create_ex with the cache format; fixed at creation because it sizes the allocation (TD_QWEN2_KV_E4M3: the bf16 cache is not allocated).
+ * td_qwen2_create_ex equals kv_mode = TD_QWEN2_KV_BF16.  Any other mode: TD_ERR_INVALID before anything is allocated.  Independent of
+ * td_qwen2_quantize_weights.  td_qwen2_init_random draws the same weights for the same seed in both modes. */
+int td_qwen2_create_kv(const TdQwen2Config* cfg, int slot_len, int n_slots, int ws_rows, int kv_mode, td_qwen2** out);
+/* mode (TD_QWEN2_KV_*), bytes of one cache row of one layer, bytes of the whole handle's cache (rows x layers); any output may be NULL */
+int td_qwen2_kv_info(const td_qwen2* f, int* kv_mode, int64_t* bytes_per_row, int64_t* cache_bytes);
+/* rows [row0, row0 + n) of sequence `slot` in layer `layer` -> out_bf16 [n, 2 Hkv 128] (device, 16-byte aligned): dequantised (exact); bf16 mode: a copy */
+int td_qwen2_read_kv(td_qwen2* f, int layer, int slot, int row0, int n, void* out_bf16, void* stream);
+/* kv bf16 [rows, ld] with `heads` 128-wide head vectors per row -> bytes at q[dst, h 128 ..] (ldq BYTES per row) and 2^e at scale[dst, h] (lds floats per
+ * row), dst = dst_rows[r] (device int32[rows]) or r when NULL; kv_hat (NULL, or bf16 [rows, ld]; may alias kv) receives x^ at row r.  ld % 8 == 0,
+ * ldq % 8 == 0, both >= heads x 128, lds >= heads; kv / kv_hat 16-byte, q 8-byte, scale / dst_rows 4-byte aligned.  A NULL kv / q / scale, rows or
+ * heads <= 0, a bad stride or a misaligned pointer: TD_ERR_INVALID with a message, before any HIP call.  Rows named by nobody are not touched. */
+int td_kv_quant_rows_e4m3(const void* kv, int64_t ld, void* q, int64_t ldq, float* scale, int64_t lds, void* kv_hat,
+                          int rows, int heads, const int* dst_rows, void* stream);
+/* ... and back: out[r, h 128 + d] = q[r, h 128 + d] scale[r, h] as bf16 (exact).  The same rules. */
+int td_kv_dequant_rows_e4m3(const void* q, int64_t ldq, const float* scale, int64_t lds, void* out, int64_t ld, int rows, int heads, void* stream);
+/* Decode attention (one query token per sequence, td_attention_bf16 with Sq = 1 and causal) over an e4m3 cache: q [batch][1, Hq 128] bf16 (q_bstride
+ * elements apart), k8 / v8 [batch][Skv, ldkv] bytes (ldkv and kv_bstride in BYTES; head h at byte h 128), k_scale / v_scale [batch][Skv, lds] fp32 (head h at
+ * column h; s_bstride floats apart), o as q.  Sequence b attends keys [0, kv_lens[b]) (device int32[batch]), or all Skv when NULL.
+ * td_attention_decode_set_group governs this form too.  ldkv % 8 == 0, kv_bstride % 8 == 0, q / o 16-byte, k8 / v8 8-byte, scales 4-byte aligned; a NULL
+ * operand, a bad stride or a misaligned pointer: TD_ERR_INVALID with a message, before any HIP call. */
+int td_attention_decode_kv8(const void* q, int64_t ldq, int64_t q_bstride, const void* k8, const void* v8, int64_t ldkv, int64_t kv_bstride,
+                            const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int64_t o_bstride,
+                            int batch, int Skv, const int* kv_lens, int Hq, int Hkv, float scale, void* stream);
+
 /* Qwen2 building blocks */
 /* out bf16[n,D] = table[ids[i],:] (table bf16 [vocab,D], ids device int32[n], D % 8 == 0).  An id outside [0, vocab) is CLAMPED, not
  * refused: id < 0 reads row 0, id >= vocab reads row vocab - 1 (the kernel never reads outside the table; a caller that wants an

@@ -7,10 +7,21 @@
 // online-softmax state and output slice in registers, and the 16 slots are merged at the end (shuffles inside a wave, LDS
 // across waves).  fp32 scores / softmax / accumulation; q.k through v_dot2c_f32_bf16.
 // Semantics = td_attn_launch with Sq = 1, causal, kv_lens (keys [0, kv_lens[b]) of sequence b are visible).
+//
+// e4m3 KV cache (td_attn_decode_kernel<G, true>, TdAttnParams::K8; include/thinkdiff_hip.h "e4m3 KV cache"): every 128-wide head vector of a cache row is
+// 128 OCP e4m3 bytes under ONE POWER-OF-TWO scale, x^ = q 2^e with e the smallest integer that brings the vector's largest magnitude to <= 448 (the weight
+// format of csrc/quant_weight.hip per head vector; csrc/kv8_math.h).  x^ is a bf16 value exactly, so the 8-bit form is this kernel on a cache that holds
+// K^ | V^: a lane fetches 8 bytes of the 128-byte line and the line's scale, and the scale goes INTO the conversion (v_cvt_scalef32_pk_bf16_fp8 for k,
+// v_cvt_scalef32_pk_f32_fp8 for v), never onto a rounded value.  Deviation from vLLM's kv_cache_dtype="fp8": one scale per (token, kv head, k or v) instead of
+// one per tensor.  Below the kernel: td_kv_quant_rows_kernel / td_kv_dequant_rows_kernel, which move bf16 k | v rows into and out of that format (prefill
+// scatter, staging of a continued forward, td_qwen2_read_kv).
 #include <atomic>
+
+#include <type_traits>
 
 #include "td_common.h"
 #include "td_kernels.h"
+#include "kv8_math.h"
 
 namespace {
 
@@ -37,8 +48,17 @@ __device__ __forceinline__ float row_sum16(float s) {
   return s;
 }
 
-template <int G>
+// What a lane fetches of one key: its 16 B of the bf16 k and v head rows, or -- e4m3 cache -- its 8 B of each 128-byte line and the line's two scales.
+struct KeyRaw16 { u32x4_t k, v; };
+struct KeyRaw8 { u32x2_t k, v; float ks, vs; };
+
+// KV8: the cache holds e4m3 bytes with one power-of-two scale per (row, kv head, k or v) (TdAttnParams::K8).  A head row is one 128-byte line plus one
+// scale; k goes through v_cvt_scalef32_pk_bf16_fp8 with its scale into the bf16 pairs v_dot2c takes, v through v_cvt_scalef32_pk_f32_fp8 into the fp32
+// values the accumulation takes -- both exact, so from there on the arithmetic is that of the bf16 form on the dequantised cache, instruction for instruction.
+// A template parameter: the key loop has no branch on the format.
+template <int G, bool KV8>
 __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams p) {
+  using KeyRaw = std::conditional_t<KV8, KeyRaw8, KeyRaw16>;
   __shared__ float sm_m[4][G], sm_l[4][G];
   __shared__ float sm_o[4][G][128];
   // one workgroup per (q-head group of G, sequence); G = 1 launches one per q head: K/V of a kv head are then read by each of
@@ -50,8 +70,12 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
   const int slot = wid * 4 + (lane >> 4);        // key slot 0..15
   const int len = p.kv_lens ? p.kv_lens[b] : p.Skv;
   const int cslot = p.dec_slots ? p.dec_slots[b] : b;      // the cache slot of sequence b
-  const bf16_t* Kb = p.K + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j;
-  const bf16_t* Vb = p.V + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j;
+  const bf16_t* Kb = KV8 ? nullptr : p.K + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j;
+  const bf16_t* Vb = KV8 ? nullptr : p.V + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j;
+  const uint8_t* Kb8 = KV8 ? p.K8 + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j : nullptr;      // (ldkv / kv_bstride in bytes)
+  const uint8_t* Vb8 = KV8 ? p.V8 + (size_t)cslot * p.kv_bstride + (size_t)kvh * 128 + 8 * j : nullptr;
+  const float* Ksb = KV8 ? p.k_scale + (size_t)cslot * p.s_bstride + kvh : nullptr;
+  const float* Vsb = KV8 ? p.v_scale + (size_t)cslot * p.s_bstride + kvh : nullptr;
   const bf16_t* Qb = p.Q + (size_t)b * p.q_bstride + (size_t)qg * G * 128 + 8 * j;
   u32x4_t q[G];
 #pragma unroll
@@ -86,7 +110,21 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
     const int KVW = p.Hkv * 2 * 128;
     knew = rope(*(const u32x4_t*)(p.dec_kv_new + (size_t)b * KVW + (size_t)kvh * 128 + 8 * j));
     vnew = *(const u32x4_t*)(p.dec_kv_new + (size_t)b * KVW + (size_t)(p.Hkv + kvh) * 128 + 8 * j);
-    if ((qg * G) % p.q_per_kv == 0 && tid < 16) {      // one 16-lane row of the kv head's first workgroup writes the new cache row
+    if constexpr (KV8) {
+      // the new key and value are rounded through the format BEFORE use (row maximum over the 16 lanes by DPP, exponent, bytes, x^ back into the registers
+      // one_key reads): this launch sees the values every later launch will read from the cache
+      float ks, vs;
+      const u32x2_t kb = kv8_round_row(knew, ks), vb = kv8_round_row(vnew, vs);
+      if ((qg * G) % p.q_per_kv == 0 && tid < 16) {      // one 16-lane row of the kv head's first workgroup writes the new line and its scales
+        const size_t row = (size_t)p.dec_row_off[b];
+        *(u32x2_t*)((uint8_t*)p.K8 + row * p.ldkv + (size_t)kvh * 128 + 8 * j) = kb;
+        *(u32x2_t*)((uint8_t*)p.V8 + row * p.ldkv + (size_t)kvh * 128 + 8 * j) = vb;
+        if (j == 0) {
+          ((float*)p.k_scale)[row * p.lds + kvh] = ks;
+          ((float*)p.v_scale)[row * p.lds + kvh] = vs;
+        }
+      }
+    } else if ((qg * G) % p.q_per_kv == 0 && tid < 16) {      // one 16-lane row of the kv head's first workgroup writes the new cache row
       bf16_t* dst = (bf16_t*)p.K + (size_t)p.dec_row_off[b] * p.ldkv;      // (a ROW index: 256 sequences x 8192 rows x 1024 elements pass 2^31)
       *(u32x4_t*)(dst + (size_t)kvh * 128 + 8 * j) = knew;
       *(u32x4_t*)(dst + (size_t)(p.Hkv + kvh) * 128 + 8 * j) = vnew;
@@ -102,10 +140,7 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
   }
   const float sc = p.scale * 1.4426950408889634f;   // softmax in base 2
   // one key of this slot: scores of the G query heads against it, online softmax, value accumulation
-  auto one_key = [&](const u32x4_t& kk, const u32x4_t& vv) {
-    float vf[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { vf[2 * i] = bf_lo(vv[i]); vf[2 * i + 1] = bf_hi(vv[i]); }
+  auto one_key_f = [&](const u32x4_t& kk, const float (&vf)[8]) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       float s = row_sum16(dot8q(kk, q[g])) * sc;
@@ -117,6 +152,31 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
       for (int i = 0; i < 8; ++i) o[g][i] = o[g][i] * corr + pe * vf[i];
     }
   };
+  auto one_key = [&](const u32x4_t& kk, const u32x4_t& vv) {
+    float vf[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { vf[2 * i] = bf_lo(vv[i]); vf[2 * i + 1] = bf_hi(vv[i]); }
+    one_key_f(kk, vf);
+  };
+  auto fetch = [&](int key) -> KeyRaw {
+    if constexpr (KV8) {
+      return KeyRaw8{*(const u32x2_t*)(Kb8 + (size_t)key * p.ldkv), *(const u32x2_t*)(Vb8 + (size_t)key * p.ldkv), Ksb[(size_t)key * p.lds], Vsb[(size_t)key * p.lds]};
+    } else {
+      return KeyRaw16{*(const u32x4_t*)(Kb + (size_t)key * p.ldkv), *(const u32x4_t*)(Vb + (size_t)key * p.ldkv)};
+    }
+  };
+  auto use = [&](const KeyRaw& r) {
+    if constexpr (KV8) {
+      typedef __attribute__((ext_vector_type(2))) float f32x2_t;
+      const unsigned v0 = r.v[0], v1 = r.v[1];
+      const f32x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v0, r.vs, false), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v0, r.vs, true);
+      const f32x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v1, r.vs, false), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v1, r.vs, true);
+      const float vf[8] = {a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+      one_key_f(kv8_to_bf16(r.k, r.ks), vf);
+    } else {
+      one_key(r.k, r.v);
+    }
+  };
   // The loop is a chain of dependent HBM / L2 round trips (one key row per slot and trip: ~0.6 us each, 19 trips for 300 keys = the 12 us the
   // kernel took per layer at one sequence): four keys per slot are fetched before the first is used, so a trip's latency covers four keys.
   // The keys of a slot are still visited in increasing order, so the arithmetic -- and the result -- is unchanged.
@@ -125,47 +185,43 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
   constexpr int UN = G >= 6 ? 2 : 4;      // (6 / 7 heads per workgroup: two keys per buffer keep the kernel inside 256 registers, i.e. two waves per SIMD)
   int key = slot;
   if constexpr (G == 1) {      // one head per workgroup (small batches: the grid is heads x sequences): a trip is all fetch, nothing to overlap it with
-    for (; key + 16 * (UN - 1) < len_cache; key += 16 * UN) {
-      u32x4_t kk[UN], vv[UN];
+    if constexpr (KV8) {       // half the bytes per key leave room for eight keys per trip (6 registers a key against 8): half as many dependent round trips on a long cache
+      for (; key + 16 * 7 < len_cache; key += 16 * 8) {
+        KeyRaw r[8];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) {
-        kk[u] = *(const u32x4_t*)(Kb + (size_t)(key + 16 * u) * p.ldkv);
-        vv[u] = *(const u32x4_t*)(Vb + (size_t)(key + 16 * u) * p.ldkv);
+        for (int u = 0; u < 8; ++u) r[u] = fetch(key + 16 * u);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) use(r[u]);
       }
+    }
+    for (; key + 16 * (UN - 1) < len_cache; key += 16 * UN) {
+      KeyRaw r[UN];
 #pragma unroll
-      for (int u = 0; u < UN; ++u) one_key(kk[u], vv[u]);
+      for (int u = 0; u < UN; ++u) r[u] = fetch(key + 16 * u);
+#pragma unroll
+      for (int u = 0; u < UN; ++u) use(r[u]);
     }
   } else if (key + 16 * (UN - 1) < len_cache) {
-    u32x4_t kk[UN], vv[UN];
+    KeyRaw r[UN];
 #pragma unroll
-    for (int u = 0; u < UN; ++u) {
-      kk[u] = *(const u32x4_t*)(Kb + (size_t)(key + 16 * u) * p.ldkv);
-      vv[u] = *(const u32x4_t*)(Vb + (size_t)(key + 16 * u) * p.ldkv);
-    }
+    for (int u = 0; u < UN; ++u) r[u] = fetch(key + 16 * u);
     for (;;) {
       const int nkey = key + 16 * UN;
       const bool more = nkey + 16 * (UN - 1) < len_cache;
-      u32x4_t kn[UN], vn[UN];
+      KeyRaw rn[UN];
       if (more) {
 #pragma unroll
-        for (int u = 0; u < UN; ++u) {
-          kn[u] = *(const u32x4_t*)(Kb + (size_t)(nkey + 16 * u) * p.ldkv);
-          vn[u] = *(const u32x4_t*)(Vb + (size_t)(nkey + 16 * u) * p.ldkv);
-        }
+        for (int u = 0; u < UN; ++u) rn[u] = fetch(nkey + 16 * u);
       }
 #pragma unroll
-      for (int u = 0; u < UN; ++u) one_key(kk[u], vv[u]);
+      for (int u = 0; u < UN; ++u) use(r[u]);
       key = nkey;
       if (!more) break;
 #pragma unroll
-      for (int u = 0; u < UN; ++u) { kk[u] = kn[u]; vv[u] = vn[u]; }
+      for (int u = 0; u < UN; ++u) r[u] = rn[u];
     }
   }
-  for (; key < len_cache; key += 16) {
-    const u32x4_t kk = *(const u32x4_t*)(Kb + (size_t)key * p.ldkv);
-    const u32x4_t vv = *(const u32x4_t*)(Vb + (size_t)key * p.ldkv);
-    one_key(kk, vv);
-  }
+  for (; key < len_cache; key += 16) use(fetch(key));
   if (fused && key == len - 1) one_key(knew, vnew);      // the slot that owns key len - 1 in the strided order: same arithmetic order as reading it from the cache
   // merge the 4 key slots of this wave (lanes 16 / 32 apart hold the same d-chunk), then the 4 waves through LDS
 #pragma unroll
@@ -217,6 +273,13 @@ int td_attn_decode_launch(const TdAttnParams& p, hipStream_t stream) {
   q.q_per_kv = p.Hq / p.Hkv;
   if (p.dec_kv_new) TD_CHECK_ARG(p.kv_lens && p.dec_cos && p.dec_sin && p.dec_row_off && ((uintptr_t)p.dec_kv_new | (uintptr_t)p.dec_cos | (uintptr_t)p.dec_sin) % 16 == 0,
                                  "td_attn_decode: the fused rotary / cache-write form needs kv_lens, both table rows and the cache row offsets");
+  const bool kv8 = p.K8 != nullptr;
+  if (kv8) {
+    TD_CHECK_ARG(p.V8 && p.k_scale && p.v_scale && p.Q && p.O, "td_attn_decode: the e4m3 cache form needs both byte planes and both scale planes");
+    TD_CHECK_ARG(p.ldkv % 8 == 0 && p.kv_bstride % 8 == 0 && ((uintptr_t)p.K8 | (uintptr_t)p.V8) % 8 == 0 && ((uintptr_t)p.k_scale | (uintptr_t)p.v_scale) % 4 == 0 &&
+                 ((uintptr_t)p.Q | (uintptr_t)p.O) % 16 == 0 && p.q_bstride % 8 == 0 && p.lds > 0,
+                 "td_attn_decode: e4m3 cache lines must be 8-byte aligned (ldkv %% 8 == 0 bytes), scales 4-byte, q and o 16-byte");
+  } else
   TD_CHECK_ARG(p.ldkv % 8 == 0 && ((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V | (uintptr_t)p.O) % 16 == 0 && p.q_bstride % 8 == 0 && p.kv_bstride % 8 == 0,
                "td_attn_decode: operands must be 16-byte aligned");
   // G q heads of one kv head per workgroup read its K/V once instead of G times (from L2); taken when the grid still gives
@@ -233,14 +296,81 @@ int td_attn_decode_launch(const TdAttnParams& p, hipStream_t stream) {
   for (int g : {7, 6, 4, 3, 2})
     if (q.q_per_kv % g == 0 && (forced ? g == forced : (long long)(p.Hq / g) * p.batch >= cus)) { G = g; break; }
   const dim3 grid(p.Hq / G, p.batch);
+#define TD_DEC_LAUNCH(g)                                                                                        \
+  do {                                                                                                          \
+    if (kv8) hipLaunchKernelGGL((td_attn_decode_kernel<g, true>), grid, dim3(256), 0, stream, q);               \
+    else hipLaunchKernelGGL((td_attn_decode_kernel<g, false>), grid, dim3(256), 0, stream, q);                  \
+  } while (0)
   switch (G) {
-    case 7: hipLaunchKernelGGL(td_attn_decode_kernel<7>, grid, dim3(256), 0, stream, q); break;
-    case 6: hipLaunchKernelGGL(td_attn_decode_kernel<6>, grid, dim3(256), 0, stream, q); break;
-    case 4: hipLaunchKernelGGL(td_attn_decode_kernel<4>, grid, dim3(256), 0, stream, q); break;
-    case 3: hipLaunchKernelGGL(td_attn_decode_kernel<3>, grid, dim3(256), 0, stream, q); break;
-    case 2: hipLaunchKernelGGL(td_attn_decode_kernel<2>, grid, dim3(256), 0, stream, q); break;
-    default: hipLaunchKernelGGL(td_attn_decode_kernel<1>, grid, dim3(256), 0, stream, q);
+    case 7: TD_DEC_LAUNCH(7); break;
+    case 6: TD_DEC_LAUNCH(6); break;
+    case 4: TD_DEC_LAUNCH(4); break;
+    case 3: TD_DEC_LAUNCH(3); break;
+    case 2: TD_DEC_LAUNCH(2); break;
+    default: TD_DEC_LAUNCH(1);
   }
+#undef TD_DEC_LAUNCH
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the rows of an e4m3 KV cache: bf16 k | v rows -> bytes + scales, and back ------------------------------------------------------------------
+namespace {
+
+// 16 lanes per head vector (lane j: elements 8j .. 8j+7), 16 vectors per workgroup.  A vector past the end is clamped to the last one and stores
+// nothing, so every DPP row is fully active.  kv_hat may alias kv: a row of lanes reads its vector before it writes it, and nobody else touches it.
+__global__ __launch_bounds__(256) void td_kv_quant_rows_kernel(const bf16_t* kv, long long ld, uint8_t* q, long long ldq, float* scale, long long lds,
+                                                               bf16_t* kv_hat, long long total, int heads, const int* dst_rows) {
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool live = unit < total;
+  const long long u = live ? unit : total - 1;
+  const long long r = u / heads;
+  const int h = (int)(u - r * heads), j = threadIdx.x & 15;
+  u32x4_t x = *(const u32x4_t*)(kv + (size_t)r * ld + (size_t)h * 128 + 8 * j);
+  float s;
+  const u32x2_t b = kv8_round_row(x, s);
+  if (!live) return;
+  const size_t dr = dst_rows ? (size_t)dst_rows[r] : (size_t)r;
+  *(u32x2_t*)(q + dr * ldq + (size_t)h * 128 + 8 * j) = b;
+  if (j == 0) scale[dr * lds + h] = s;
+  if (kv_hat) *(u32x4_t*)(kv_hat + (size_t)r * ld + (size_t)h * 128 + 8 * j) = x;
+}
+
+__global__ __launch_bounds__(256) void td_kv_dequant_rows_kernel(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld,
+                                                                 long long total, int heads) {
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (unit >= total) return;
+  const long long r = unit / heads;
+  const int h = (int)(unit - r * heads), j = threadIdx.x & 15;
+  const u32x2_t b = *(const u32x2_t*)(q + (size_t)r * ldq + (size_t)h * 128 + 8 * j);
+  *(u32x4_t*)(out + (size_t)r * ld + (size_t)h * 128 + 8 * j) = kv8_to_bf16(b, scale[(size_t)r * lds + h]);
+}
+
+}  // namespace
+
+int td_kv_quant_rows_launch(const bf16_t* kv, long long ld, uint8_t* q, long long ldq, float* scale, long long lds, bf16_t* kv_hat, int rows, int heads,
+                            const int* dst_rows, hipStream_t stream) {
+  TD_CHECK_ARG(kv && q && scale, "td_kv_quant_rows_e4m3: kv, q and scale are required");
+  TD_CHECK_ARG(heads > 0 && rows > 0, "td_kv_quant_rows_e4m3: rows=%d, heads=%d must be positive", rows, heads);
+  TD_CHECK_ARG(ld >= (long long)heads * 128 && ld % 8 == 0 && ldq >= (long long)heads * 128 && ldq % 8 == 0 && lds >= heads,
+               "td_kv_quant_rows_e4m3: ld=%lld, ldq=%lld must be multiples of 8 and at least heads x 128 = %lld, lds=%lld at least heads", ld, ldq, (long long)heads * 128, lds);
+  TD_CHECK_ARG((uintptr_t)kv % 16 == 0 && (uintptr_t)kv_hat % 16 == 0 && (uintptr_t)q % 8 == 0 && (uintptr_t)scale % 4 == 0 && (uintptr_t)dst_rows % 4 == 0,
+               "td_kv_quant_rows_e4m3: misaligned rows: kv and kv_hat must be 16-byte aligned, q 8-byte, scale and dst_rows 4-byte");
+  const long long total = (long long)rows * heads;
+  hipLaunchKernelGGL(td_kv_quant_rows_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, kv, ld, q, ldq, scale, lds, kv_hat, total, heads, dst_rows);
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
+int td_kv_dequant_rows_launch(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld, int rows, int heads, hipStream_t stream) {
+  TD_CHECK_ARG(q && scale && out, "td_kv_dequant_rows_e4m3: q, scale and out are required");
+  TD_CHECK_ARG(heads > 0 && rows > 0, "td_kv_dequant_rows_e4m3: rows=%d, heads=%d must be positive", rows, heads);
+  TD_CHECK_ARG(ld >= (long long)heads * 128 && ld % 8 == 0 && ldq >= (long long)heads * 128 && ldq % 8 == 0 && lds >= heads,
+               "td_kv_dequant_rows_e4m3: ld=%lld, ldq=%lld must be multiples of 8 and at least heads x 128 = %lld, lds=%lld at least heads", ld, ldq, (long long)heads * 128, lds);
+  TD_CHECK_ARG((uintptr_t)out % 16 == 0 && (uintptr_t)q % 8 == 0 && (uintptr_t)scale % 4 == 0,
+               "td_kv_dequant_rows_e4m3: misaligned rows: out must be 16-byte aligned, q 8-byte, scale 4-byte");
+  const long long total = (long long)rows * heads;
+  hipLaunchKernelGGL(td_kv_dequant_rows_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, q, ldq, scale, lds, out, ld, total, heads);
   TD_CHECK_LAUNCH();
   return 0;
 }

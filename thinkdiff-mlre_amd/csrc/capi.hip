@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 12; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 13; }     // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -30,6 +30,8 @@ int td_abi_version(void) { return 12; }     // 2: TdFluxConfig::out_channels app
                                             // 11: PIL-exact image resize (td_resize_coeffs, td_image_resize_u8, td_image_lut_chw_f32)
                                             // 12: 8-bit weight stream (td_quant_weight_rows_e4m3, td_linear*_w8_bf16, td_linear_glu_bf16,
                                             //     td_qwen2_quantize_weights, td_qwen2_set_weight_stream, td_qwen2_weight_info, td_qwen2_weight_stream_launches)
+                                            // 13: e4m3 KV cache (td_qwen2_create_kv, td_qwen2_kv_info, td_qwen2_read_kv, td_kv_quant_rows_e4m3,
+                                            //     td_kv_dequant_rows_e4m3, td_attention_decode_kv8)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -631,6 +633,36 @@ int td_linear_glu_w8_bf16(const void* x, int64_t ldx, const void* wq, const floa
   TdGemmParams p;
   p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W8 = (const uint8_t*)wq; p.w8_scale = w_scale; p.C = (bf16_t*)y; p.ldc = (int)ldy; p.M = M; p.N = I; p.K = K; p.glu_I = I;
   return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+// ---- e4m3 KV cache (td_abi_version() >= 13): as above, every refusal comes before the first HIP call
+int td_kv_quant_rows_e4m3(const void* kv, int64_t ld, void* q, int64_t ldq, float* scale, int64_t lds, void* kv_hat, int rows, int heads, const int* dst_rows, void* stream) {
+  return td_kv_quant_rows_launch((const bf16_t*)kv, (long long)ld, (uint8_t*)q, (long long)ldq, scale, (long long)lds, (bf16_t*)kv_hat, rows, heads, dst_rows, (hipStream_t)stream);
+}
+
+int td_kv_dequant_rows_e4m3(const void* q, int64_t ldq, const float* scale, int64_t lds, void* out, int64_t ld, int rows, int heads, void* stream) {
+  return td_kv_dequant_rows_launch((const uint8_t*)q, (long long)ldq, scale, (long long)lds, (bf16_t*)out, (long long)ld, rows, heads, (hipStream_t)stream);
+}
+
+int td_attention_decode_kv8(const void* q, int64_t ldq, int64_t q_bstride, const void* k8, const void* v8, int64_t ldkv, int64_t kv_bstride,
+                            const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int64_t o_bstride,
+                            int batch, int Skv, const int* kv_lens, int Hq, int Hkv, float scale, void* stream) {
+  TD_CHECK_ARG(q && k8 && v8 && k_scale && v_scale && o, "td_attention_decode_kv8: q, both byte planes (k8, v8), both scale planes (k_scale, v_scale) and o are required");
+  TD_CHECK_ARG(batch > 0 && Skv > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "td_attention_decode_kv8: batch=%d, Skv=%d, Hq=%d, Hkv=%d (Hq a multiple of Hkv)", batch, Skv, Hq, Hkv);
+  TD_CHECK_ARG(ld32(ldq) && ld32(ldkv) && ld32(ldo) && ld32(lds) && ldq % 8 == 0 && ldo % 8 == 0 && q_bstride % 8 == 0 && o_bstride % 8 == 0 && ldq >= (int64_t)Hq * 128 && ldo >= (int64_t)Hq * 128,
+               "td_attention_decode_kv8: ldq=%lld, ldo=%lld must be multiples of 8 and at least Hq x 128", (long long)ldq, (long long)ldo);
+  TD_CHECK_ARG(ldkv % 8 == 0 && kv_bstride % 8 == 0 && ldkv >= (int64_t)Hkv * 128, "td_attention_decode_kv8: ldkv=%lld, kv_bstride=%lld (bytes) must be multiples of 8, ldkv at least Hkv x 128",
+               (long long)ldkv, (long long)kv_bstride);
+  TD_CHECK_ARG(lds >= Hkv && s_bstride >= 0 && kv_bstride >= 0, "td_attention_decode_kv8: lds=%lld must cover the Hkv=%d scales of a row", (long long)lds, Hkv);
+  TD_CHECK_ARG(al(q, 16) && al(o, 16) && al(k8, 8) && al(v8, 8) && al(k_scale, 4) && al(v_scale, 4) && al(kv_lens, 4),
+               "td_attention_decode_kv8: misaligned operands: q and o must be 16-byte aligned, k8 and v8 8-byte, the scale planes and kv_lens 4-byte");
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.O = (bf16_t*)o; p.K8 = (const uint8_t*)k8; p.V8 = (const uint8_t*)v8; p.k_scale = k_scale; p.v_scale = v_scale;
+  p.batch = batch; p.Sq = 1; p.Skv = Skv; p.Hq = Hq; p.Hkv = Hkv; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo; p.lds = (int)lds;
+  p.q_bstride = q_bstride; p.kv_bstride = kv_bstride; p.o_bstride = o_bstride; p.s_bstride = s_bstride;
+  p.scale = scale; p.causal = 1; p.causal_offset = Skv - 1; p.kv_lens = kv_lens;
+  return td_attn_launch(p, (hipStream_t)stream);
 }
 
 int td_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int vocab, float temperature, float top_p,

@@ -434,10 +434,10 @@ void weights_changed(FluxModel* m) {
 // Grid-stride: a launch carries at most 2^32 - 1 work-items (the dispatch packet's grid size is 32 bits and a larger product is
 // truncated WITHOUT an error) -- the 11.9 B-parameter FLUX arena needs 5.95 G pairs.  The one-thread-per-pair form filled only
 // the first 3.3 G elements of it (embedders + modulation matrix) and left every block weight at the allocator's zeros.
-__global__ void td_fill_normal_kernel(bf16_t* dst, long long n, unsigned long long seed, float std, float mean) {
+__global__ void td_fill_normal_kernel(bf16_t* dst, long long n, unsigned long long seed, float std, float mean, long long pair0) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long pair = (long long)blockIdx.x * blockDim.x + threadIdx.x; 2 * pair < n; pair += stride) {
-    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(pair + 1);
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(pair0 + pair + 1);      // (pair0: dst is a piece of a larger fill)
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z = z ^ (z >> 31);
@@ -449,6 +449,15 @@ __global__ void td_fill_normal_kernel(bf16_t* dst, long long n, unsigned long lo
     dst[2 * pair] = f2bf(mean + std * r * c);
     if (2 * pair + 1 < n) dst[2 * pair + 1] = f2bf(mean + std * r * s);
   }
+}
+
+int td_fill_normal_from_launch(bf16_t* dst, long long n, unsigned long long seed, float std, float mean, long long pair0, hipStream_t stream) {
+  TD_CHECK_ARG(dst && n > 0 && pair0 >= 0, "td_fill_normal_bf16: empty buffer");
+  const long long pairs = (n + 1) / 2;
+  const long long blocks = (pairs + 255) / 256;
+  hipLaunchKernelGGL(td_fill_normal_kernel, dim3((unsigned)(blocks < (1ll << 20) ? blocks : (1ll << 20))), dim3(256), 0, stream, dst, n, seed, std, mean, pair0);
+  TD_CHECK_LAUNCH();
+  return TD_OK;
 }
 
 extern "C" {
@@ -501,13 +510,7 @@ int td_flux_param_shape(const td_flux* f, const char* name, int64_t* rows, int64
 }
 
 int td_fill_normal_bf16(void* dst, int64_t n, uint64_t seed, float std, float mean, void* stream) {
-  TD_CHECK_ARG(dst && n > 0, "td_fill_normal_bf16: empty buffer");
-  const long long pairs = (n + 1) / 2;
-  const long long blocks = (pairs + 255) / 256;
-  hipLaunchKernelGGL(td_fill_normal_kernel, dim3((unsigned)(blocks < (1ll << 20) ? blocks : (1ll << 20))), dim3(256), 0, (hipStream_t)stream,
-                     (bf16_t*)dst, (long long)n, (unsigned long long)seed, std, mean);
-  TD_CHECK_LAUNCH();
-  return TD_OK;
+  return td_fill_normal_from_launch((bf16_t*)dst, (long long)n, (unsigned long long)seed, std, mean, 0, (hipStream_t)stream);
 }
 
 int td_flux_init_random(td_flux* f, uint64_t seed, float std, void* stream) {

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "td_kernels.h"
+#include "kv8_math.h"
 #include "../../include/thinkdiff_hip.h"
 
 namespace {
@@ -42,7 +43,9 @@ struct QLayer {
   bf16_t* gu_w;            // [2 I, D] = gate_proj | up_proj
   bf16_t* down_w;          // [D, I]
   bf16_t *ln1_w, *ln2_w;   // [D]
-  bf16_t* kv;              // cache [max_tokens, 2 * Hkv * 128]
+  bf16_t* kv = nullptr;    // cache [max_tokens, 2 * Hkv * 128]; null on a handle with the e4m3 cache, which owns the two planes below instead
+  uint8_t* kv8 = nullptr;  // e4m3 bytes [max_tokens, 2 * Hkv * 128], k heads then v heads
+  float* kvs = nullptr;    // scales 2^e [max_tokens, 2 * Hkv]: column h = k head h, column Hkv + h = v head h
 };
 
 }  // namespace
@@ -87,6 +90,17 @@ struct td_qwen2 {
   int w8_linears = 0;
   long long w8_launches = 0;                    // Linear launches enqueued (or captured) so far that read the 8-bit copy (td_qwen2_weight_stream_launches)
   W8Ref lm_8;
+  // e4m3 KV cache (td_qwen2_create_kv): fixed at creation, it sizes the allocation.  The parameter arena then lacks the cache rows; `segs` maps its pieces
+  // (arena offset, offset in the bf16-mode layout, elements) so that td_qwen2_init_random draws the weights a bf16-mode handle draws from the same seed
+  int kv_mode = TD_QWEN2_KV_BF16;
+  char* kv8_arena = nullptr;
+  struct Seg { int64_t off, voff, n; };
+  std::vector<Seg> segs;
+  int64_t voff_of(const bf16_t* p) const {
+    const int64_t o = p - arena;
+    for (const Seg& g : segs) if (o >= g.off && o < g.off + g.n) return g.voff + (o - g.off);
+    return o;
+  }
   float* sk_ws = nullptr;                       // partial sums of the decode step's split-K Linears (65-256 sequences): the engine's own buffer, so a captured step allocates nothing
 };
 
@@ -133,7 +147,10 @@ __global__ void td_gather_last_rows_kernel(const bf16_t* src, bf16_t* dst, const
 
 // Decode step, one launch for: M-RoPE on the new q rows (in place), M-RoPE on the new k rows, k|v rows -> their sequences' cache
 // rows.  Rotation = rotate_half with every op rounding to bf16 (td_qk_norm_rope_kernel rotate_half == 2: q*cos, rot*sin, sum).
-__global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, const bf16_t* kv, bf16_t* cache, const int* row_off,
+// KV8: the rotated k and the v head vectors go through the e4m3 format (kv8_round_row: what the fused form does in the attention launch) and their
+// bytes and scales are stored in cache8 / scales instead of the bf16 row.
+template <bool KV8>
+__global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, const bf16_t* kv, bf16_t* cache, uint8_t* cache8, float* scales, const int* row_off,
                                                                      const float* cosT, const float* sinT, int Hq, int Hkv) {
   const int b = blockIdx.x;
   const int l16 = threadIdx.x & 15, unit0 = threadIdx.x >> 4;
@@ -141,7 +158,7 @@ __global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, 
   float cs[8], sn[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) { cs[i] = cosT[(size_t)b * 128 + l16 * 8 + i]; sn[i] = sinT[(size_t)b * 128 + l16 * 8 + i]; }
-  bf16_t* dst = cache + (size_t)row_off[b] * KVW;      // (row index of the sequence's new cache row)
+  bf16_t* dst = KV8 ? nullptr : cache + (size_t)row_off[b] * KVW;      // (row index of the sequence's new cache row)
   for (int u = unit0; u < Hq + 2 * Hkv; u += 16) {
     const bool is_q = u < Hq, is_v = u >= Hq + Hkv;
     const bf16_t* src = is_q ? q + (size_t)b * QW + u * 128 + l16 * 8 : kv + (size_t)b * KVW + (u - Hq) * 128 + l16 * 8;
@@ -158,8 +175,19 @@ __global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, 
       }
       raw = u32x4_t{pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
     }
-    bf16_t* out = is_q ? q + (size_t)b * QW + u * 128 + l16 * 8 : dst + (u - Hq) * 128 + l16 * 8;
-    *(u32x4_t*)out = raw;
+    if constexpr (KV8) {
+      if (is_q) {
+        *(u32x4_t*)(q + (size_t)b * QW + u * 128 + l16 * 8) = raw;
+      } else {      // (u is the same in all 16 lanes of a row, so the row is fully active here)
+        float sc;
+        const u32x2_t bytes = kv8_round_row(raw, sc);
+        *(u32x2_t*)(cache8 + (size_t)row_off[b] * KVW + (u - Hq) * 128 + l16 * 8) = bytes;
+        if (l16 == 0) scales[(size_t)row_off[b] * (2 * Hkv) + (u - Hq)] = sc;
+      }
+    } else {
+      bf16_t* out = is_q ? q + (size_t)b * QW + u * 128 + l16 * 8 : dst + (u - Hq) * 128 + l16 * 8;
+      *(u32x4_t*)out = raw;
+    }
   }
 }
 
@@ -218,6 +246,10 @@ struct PrefillForm {
   long long to_slots = -1; int slots_L = 0;    // row b * slots_L + t -> row t of the b-th slot from cache element to_slots on
   TdAttnParams attn;           // the layer's attention, all but K / V, which are the k and the v half of `attn_kv`
   KvRows attn_kv = KV_TMP;
+  // e4m3 cache: the new k | v rows always go to kvtmp, from row q8_tmp_row0 on; behind RoPE td_kv_quant_rows_launch writes their bytes and scales to cache row
+  // to_rows[r], or (to_rows null) q8_cache_row0 + q8_tmp_row0 + r, and puts x^ back into kvtmp, which the attention reads (attn_kv = KV_TMP).  A continuation
+  // (q8_tmp_row0 > 0) first dequantises cache rows [q8_cache_row0, q8_cache_row0 + q8_tmp_row0) into kvtmp rows [0, q8_tmp_row0): exact, x^ is a bf16 value.
+  int q8_tmp_row0 = 0; long long q8_cache_row0 = 0;
 };
 
 // Runs form.n rows through the decoder: embed (or take inputs_embeds), M-RoPE table, every layer, model.norm -- left in f->xn and copied to
@@ -239,9 +271,13 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
   TdQkRopeParams rk = rq;  // k heads in the k|v rows just written
   rk.ld = KVW; rk.Hq = Hkv;
   TdAttnParams ap = form.attn;
+  const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
 
   for (const QLayer& l : f->layers) {
-    bf16_t* kv_new = form.kv_new.of(f, l);
+    bf16_t* kv_new = kv8 ? f->kvtmp + (size_t)form.q8_tmp_row0 * KVW : form.kv_new.of(f, l);
+    if (kv8 && form.q8_tmp_row0 > 0)
+      TD_TRY(td_kv_dequant_rows_launch(l.kv8 + (size_t)form.q8_cache_row0 * KVW, KVW, l.kvs + (size_t)form.q8_cache_row0 * 2 * Hkv, 2 * Hkv, f->kvtmp, KVW,
+                                       form.q8_tmp_row0, 2 * Hkv, s));
     np.w = l.ln1_w;
     TD_TRY(td_norm_rows_launch(np, s));
     {  // fused q | k | v projection: q -> scratch, k | v -> kv_new
@@ -260,11 +296,14 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
     }
     TD_TRY(td_qk_norm_rope_launch(rq, s));
     rk.qkv = kv_new; TD_TRY(td_qk_norm_rope_launch(rk, s));
-    if (form.to_rows)
+    if (kv8) {      // the quantising scatter runs BEFORE the attention, which then reads K^ | V^: no result depends on where a key came from
+      const long long r0 = form.to_rows ? 0 : form.q8_cache_row0 + form.q8_tmp_row0;
+      TD_TRY(td_kv_quant_rows_launch(kv_new, KVW, l.kv8 + (size_t)r0 * KVW, KVW, l.kvs + (size_t)r0 * 2 * Hkv, 2 * Hkv, kv_new, n, 2 * Hkv, form.to_rows, s));
+    } else if (form.to_rows)
       hipLaunchKernelGGL(td_kv_rows_to_rows_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv, form.to_rows, KVW);
     else if (form.to_slots >= 0)
       hipLaunchKernelGGL(td_kv_rows_to_slots_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv + form.to_slots, form.slots_L, f->slot_len, KVW);
-    ap.K = form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
+    ap.K = kv8 ? f->kvtmp : form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
     TD_TRY(td_attn_launch(ap, s));
     // h += o_proj(attn)
     TD_TRY(run_linear(f, linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), l.o_8, s));
@@ -298,6 +337,15 @@ extern "C" {
 
 // KV cache of n_slots sequences x slot_len rows per layer; activation workspace for slot_len rows (the longest prefill)
 int td_qwen2_create_ex(const TdQwen2Config* cfg, int slot_len, int n_slots, int ws_rows, td_qwen2** out) {
+  return td_qwen2_create_kv(cfg, slot_len, n_slots, ws_rows, TD_QWEN2_KV_BF16, out);
+}
+
+// ... with the KV cache in the given format: TD_QWEN2_KV_BF16 (td_qwen2_create_ex) or TD_QWEN2_KV_E4M3, in which every layer owns a byte plane and a scale
+// plane instead of its bf16 rows (KVW + 8 Hkv bytes per row against 2 KVW)
+int td_qwen2_create_kv(const TdQwen2Config* cfg, int slot_len, int n_slots, int ws_rows, int kv_mode, td_qwen2** out) {
+  TD_CHECK_ARG(kv_mode == TD_QWEN2_KV_BF16 || kv_mode == TD_QWEN2_KV_E4M3, "td_qwen2_create_kv: unknown kv mode %d (TD_QWEN2_KV_BF16 = %d, TD_QWEN2_KV_E4M3 = %d)", kv_mode,
+               TD_QWEN2_KV_BF16, TD_QWEN2_KV_E4M3);
+  const bool kv8 = kv_mode == TD_QWEN2_KV_E4M3;
   TD_CHECK_ARG(cfg && out && slot_len > 0 && n_slots > 0 && (long long)slot_len * n_slots < (1ll << 30), "td_qwen2_create: bad arguments");
   if (ws_rows < slot_len) ws_rows = slot_len;
   const int max_tokens = slot_len * n_slots;
@@ -315,11 +363,16 @@ int td_qwen2_create_ex(const TdQwen2Config* cfg, int slot_len, int n_slots, int 
   f->slot_len = slot_len;
   f->n_slots = n_slots;
   f->ws_rows = ws_rows;
+  f->kv_mode = kv_mode;
   f->layers.resize(cfg->num_layers);
 
-  int64_t off = 0;
+  int64_t off = 0, voff = 0;      // offset in this arena; offset in the arena of a bf16-mode handle (which holds the cache rows too)
   std::vector<std::pair<bf16_t**, int64_t>> fix;
-  auto take = [&](bf16_t** p, int64_t n) { fix.emplace_back(p, off); off += (n + 127) & ~int64_t(127); };
+  auto take = [&](bf16_t** p, int64_t n) {
+    const int64_t padded = (n + 127) & ~int64_t(127);
+    if (p) { fix.emplace_back(p, off); f->segs.push_back({off, voff, padded}); off += padded; }
+    voff += padded;
+  };
   take(&f->embed_w, (int64_t)cfg->vocab * D);
   take(&f->norm_w, D);
   if (!cfg->tie_embeddings) take(&f->lm_w, (int64_t)cfg->vocab * D);
@@ -329,7 +382,7 @@ int td_qwen2_create_ex(const TdQwen2Config* cfg, int slot_len, int n_slots, int 
     take(&l.gu_w, (int64_t)2 * I * D);
     take(&l.down_w, (int64_t)D * I);
     take(&l.ln1_w, D); take(&l.ln2_w, D);
-    take(&l.kv, (int64_t)max_tokens * 2 * Hkv * 128);
+    take(kv8 ? nullptr : &l.kv, (int64_t)max_tokens * 2 * Hkv * 128);
   }
   f->arena_elems = off;
   hipError_t e = hipMalloc((void**)&f->arena, (size_t)off * 2);
@@ -340,6 +393,30 @@ int td_qwen2_create_ex(const TdQwen2Config* cfg, int slot_len, int n_slots, int 
   }
   for (auto& fx : fix) *fx.first = f->arena + fx.second;
   if (cfg->tie_embeddings) f->lm_w = f->embed_w;
+  if (kv8) {
+    const int64_t plane = ((int64_t)max_tokens * 2 * Hkv * 128 + 255) & ~int64_t(255), splane = ((int64_t)max_tokens * 2 * Hkv * 4 + 255) & ~int64_t(255);
+    const int64_t bytes = (plane + splane) * cfg->num_layers;
+    e = hipMalloc((void**)&f->kv8_arena, (size_t)bytes);
+    if (e != hipSuccess) {
+      td_set_error("td_qwen2_create_kv: hipMalloc of %.2f GiB for the e4m3 cache failed: %s", bytes / double(1 << 30), hipGetErrorString(e));
+      (void)hipFree(f->arena);
+      delete f;
+      return TD_ERR_HIP;
+    }
+    e = hipMemset(f->kv8_arena, 0, (size_t)bytes);      // (ordered with every stream by the synchronise below)
+    if (e != hipSuccess) {
+      td_set_error("td_qwen2_create_kv: hipMemset of the e4m3 cache failed: %s", hipGetErrorString(e));
+      (void)hipFree(f->kv8_arena);
+      (void)hipFree(f->arena);
+      delete f;
+      return TD_ERR_HIP;
+    }
+    int64_t o = 0;
+    for (auto& l : f->layers) {
+      l.kv8 = (uint8_t*)(f->kv8_arena + o); o += plane;
+      l.kvs = (float*)(f->kv8_arena + o); o += splane;
+    }
+  }
 
   q_add(f, "model.embed_tokens.weight", f->embed_w, (int64_t)cfg->vocab * D);
   q_add(f, "model.norm.weight", f->norm_w, D);
@@ -377,6 +454,7 @@ int td_qwen2_create_ex(const TdQwen2Config* cfg, int slot_len, int n_slots, int 
   if (e != hipSuccess) {
     td_set_error("td_qwen2_create: hipMalloc of %.2f GiB workspace failed: %s", total / double(1 << 30), hipGetErrorString(e));
     (void)hipFree(f->arena);
+    if (f->kv8_arena) (void)hipFree(f->kv8_arena);
     delete f;
     return TD_ERR_HIP;
   }
@@ -401,7 +479,32 @@ void td_qwen2_destroy(td_qwen2* f) {
   (void)hipFree(f->arena);
   (void)hipFree(f->ws);
   if (f->w8_arena) (void)hipFree(f->w8_arena);
+  if (f->kv8_arena) (void)hipFree(f->kv8_arena);
   delete f;
+}
+
+int td_qwen2_kv_info(const td_qwen2* f, int* kv_mode, int64_t* bytes_per_row, int64_t* cache_bytes) {
+  TD_CHECK_ARG(f, "td_qwen2_kv_info: null handle");
+  const int64_t KVW = (int64_t)2 * f->Hkv * 128;
+  const int64_t row = f->kv_mode == TD_QWEN2_KV_E4M3 ? KVW + 8 * f->Hkv : 2 * KVW;      // bytes + 2 Hkv fp32 scales | bf16
+  if (kv_mode) *kv_mode = f->kv_mode;
+  if (bytes_per_row) *bytes_per_row = row;
+  if (cache_bytes) *cache_bytes = row * f->max_tokens * f->cfg.num_layers;
+  return TD_OK;
+}
+
+// rows [row0, row0 + n) of sequence `slot` in layer `layer` as bf16 [n, 2 Hkv 128]: a copy, or -- e4m3 cache -- the dequantised values q 2^e (exact)
+int td_qwen2_read_kv(td_qwen2* f, int layer, int slot, int row0, int n, void* out_bf16, void* stream) {
+  TD_CHECK_ARG(f && out_bf16, "td_qwen2_read_kv: null argument");
+  TD_CHECK_ARG(layer >= 0 && layer < f->cfg.num_layers && slot >= 0 && slot < f->n_slots, "td_qwen2_read_kv: layer %d of %d, slot %d of %d", layer, f->cfg.num_layers, slot, f->n_slots);
+  TD_CHECK_ARG(row0 >= 0 && n > 0 && (long long)row0 + n <= f->slot_len, "td_qwen2_read_kv: rows [%d, %lld) exceed the slot capacity %d", row0, (long long)row0 + n, f->slot_len);
+  TD_CHECK_ARG((uintptr_t)out_bf16 % 16 == 0, "td_qwen2_read_kv: the output must be 16-byte aligned");
+  const QLayer& l = f->layers[layer];
+  const size_t KVW = (size_t)2 * f->Hkv * 128, r = (size_t)slot * f->slot_len + row0;
+  if (f->kv_mode == TD_QWEN2_KV_E4M3)
+    return td_kv_dequant_rows_launch(l.kv8 + r * KVW, (long long)KVW, l.kvs + r * 2 * f->Hkv, 2 * f->Hkv, (bf16_t*)out_bf16, (long long)KVW, n, 2 * f->Hkv, (hipStream_t)stream);
+  TD_CHECK_HIP(hipMemcpyAsync(out_bf16, l.kv + r * KVW, (size_t)n * KVW * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return TD_OK;
 }
 
 int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream) {
@@ -490,10 +593,14 @@ int td_qwen2_load_param(td_qwen2* f, const char* name, const void* src, int64_t 
 int td_qwen2_init_random(td_qwen2* f, uint64_t seed, float std, void* stream) {
   TD_CHECK_ARG(f, "td_qwen2_init_random: null handle");
   if (f->w_mode != TD_QWEN2_WEIGHTS_BF16) f->w8_stale = true;
-  TD_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
+  if (f->kv_mode == TD_QWEN2_KV_BF16) {
+    TD_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
+  } else {      // the arena lacks the cache rows: every piece draws what it draws at its place in a bf16-mode handle (pieces start on even offsets)
+    for (const td_qwen2::Seg& g : f->segs) TD_TRY(td_fill_normal_from_launch(f->arena + g.off, g.n, seed, std, 0.f, g.voff / 2, (hipStream_t)stream));
+  }
   for (const QSlot& s : f->slots)
     if (s.name.find("layernorm.weight") != std::string::npos || s.name == "model.norm.weight")
-      TD_TRY(td_fill_normal_bf16(s.ptr, s.count, seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(s.ptr - f->arena + 1)), 0.05f, 1.0f, stream));
+      TD_TRY(td_fill_normal_bf16(s.ptr, s.count, seed ^ (0x9E3779B97F4A7C15ull * (uint64_t)(f->voff_of(s.ptr) + 1)), 0.05f, 1.0f, stream));
   return TD_OK;
 }
 
@@ -523,9 +630,14 @@ int td_qwen2_forward_slot(td_qwen2* f, int slot, const int* token_ids, const voi
   const long long KVW = 2 * f->Hkv * 128, seq = (long long)slot * f->slot_len * KVW;   // this sequence's cache rows
   PrefillForm form;
   form.n = n;
-  form.kv_new = KvRows{seq + pos0 * KVW};      // k | v -> straight into the layer's cache rows
   form.attn = prefill_attn(f, 1, n, pos0 + n, pos0);
-  form.attn_kv = KvRows{seq};
+  if (f->kv_mode == TD_QWEN2_KV_E4M3) {
+    // staging: the slot's rows [0, pos0) are dequantised into kvtmp, the new rows join them there, the bf16 attention runs over kvtmp (ws_rows >= slot_len rows)
+    form.q8_tmp_row0 = pos0; form.q8_cache_row0 = (long long)slot * f->slot_len;
+  } else {
+    form.kv_new = KvRows{seq + pos0 * KVW};      // k | v -> straight into the layer's cache rows
+    form.attn_kv = KvRows{seq};
+  }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) TD_TRY(lm_head(f, f->xn + (size_t)(n - 1) * f->D, 1, logits_last, s));
   return TD_OK;
@@ -563,6 +675,14 @@ int td_qwen2_move_slot(td_qwen2* f, int src, int dst, int len, void* stream) {
   TD_CHECK_ARG(f && src >= 0 && src < f->n_slots && dst >= 0 && dst < f->n_slots && len >= 0 && len <= f->slot_len, "td_qwen2_move_slot: bad arguments");
   if (src == dst || len == 0) return TD_OK;
   const size_t KVW = (size_t)2 * f->Hkv * 128;
+  if (f->kv_mode == TD_QWEN2_KV_E4M3) {      // both planes
+    const size_t SW = (size_t)2 * f->Hkv;
+    for (const QLayer& l : f->layers) {
+      TD_CHECK_HIP(hipMemcpyAsync(l.kv8 + (size_t)dst * f->slot_len * KVW, l.kv8 + (size_t)src * f->slot_len * KVW, (size_t)len * KVW, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+      TD_CHECK_HIP(hipMemcpyAsync(l.kvs + (size_t)dst * f->slot_len * SW, l.kvs + (size_t)src * f->slot_len * SW, (size_t)len * SW * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
+    return TD_OK;
+  }
   for (const QLayer& l : f->layers)
     TD_CHECK_HIP(hipMemcpyAsync(l.kv + (size_t)dst * f->slot_len * KVW, l.kv + (size_t)src * f->slot_len * KVW, (size_t)len * KVW * 2,
                                 hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -614,13 +734,22 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     }
     // rotary embedding of the new q / k rows and the cache write ride inside the attention launch (TdAttnParams::dec_kv_new);
     // td_qwen2_set_fused_rope(f, 0): the separate launch (A/B and the bit-identity test)
-    if (!f->fused_rope) hipLaunchKernelGGL(td_decode_rope_scatter_kernel, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, l.kv, row_off, f->cosT, f->sinT, Hq, Hkv);
+    const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
+    if (!f->fused_rope) {
+      if (kv8) hipLaunchKernelGGL(td_decode_rope_scatter_kernel<true>, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, (bf16_t*)nullptr, l.kv8, l.kvs, row_off, f->cosT, f->sinT, Hq, Hkv);
+      else hipLaunchKernelGGL(td_decode_rope_scatter_kernel<false>, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, l.kv, (uint8_t*)nullptr, (float*)nullptr, row_off, f->cosT, f->sinT, Hq, Hkv);
+    }
     TdAttnParams ap;
     if (f->fused_rope) { ap.dec_kv_new = f->kvtmp; ap.dec_cos = f->cosT; ap.dec_sin = f->sinT; ap.dec_row_off = row_off; }
-    ap.Q = f->q; ap.ldq = QW; ap.q_bstride = QW; ap.K = l.kv; ap.V = l.kv + Hkv * 128; ap.ldkv = KVW;
+    ap.Q = f->q; ap.ldq = QW; ap.q_bstride = QW; ap.ldkv = KVW;
     ap.kv_bstride = (long long)f->slot_len * KVW; ap.O = f->attn; ap.ldo = QW; ap.o_bstride = QW;
     ap.batch = B; ap.Sq = 1; ap.Skv = max_len; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f;
     ap.causal = 1; ap.causal_offset = max_len - 1; ap.kv_lens = kv_lens; ap.dec_slots = slot_ids;
+    if (!kv8) {
+      ap.K = l.kv; ap.V = l.kv + Hkv * 128;
+    } else {      // the same launch, its descriptor carrying bytes + scales (ldkv / kv_bstride then count bytes)
+      ap.K8 = l.kv8; ap.V8 = l.kv8 + Hkv * 128; ap.k_scale = l.kvs; ap.v_scale = l.kvs + Hkv; ap.lds = 2 * Hkv; ap.s_bstride = (long long)f->slot_len * 2 * Hkv;
+    }
     TD_TRY(td_attn_launch(ap, s));
     {
       TdGemmParams g = linear(f->attn, QW, l.o_w, nullptr, f->h, D, B, D, QW, true);
@@ -756,10 +885,20 @@ int td_qwen2_prefill_batch_at(td_qwen2* f, int slot0, int B, int L, const int* t
   const long long KVW = 2 * f->Hkv * 128, kv0 = (long long)slot0 * f->slot_len * KVW;      // first slot of this call
   PrefillForm form;
   form.n = B * L;
-  form.to_slots = kv0; form.slots_L = L;
   form.attn = prefill_attn(f, B, L, L, 0);
-  form.attn.q_bstride = form.attn.o_bstride = (long long)L * QW; form.attn.kv_bstride = f->slot_len * KVW;
-  form.attn_kv = KvRows{kv0};
+  form.attn.q_bstride = form.attn.o_bstride = (long long)L * QW;
+  if (f->kv_mode == TD_QWEN2_KV_E4M3) {      // the attention reads the rounded rows in kvtmp; the quantising scatter takes the cache row of every row
+    f->row_map_host.resize((size_t)B * L);
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t < L; ++t) f->row_map_host[(size_t)b * L + t] = (slot0 + b) * f->slot_len + t;
+    TD_CHECK_HIP(hipMemcpyAsync(f->row_map, f->row_map_host.data(), (size_t)B * L * 4, hipMemcpyHostToDevice, s));
+    form.to_rows = f->row_map;
+    form.attn.kv_bstride = L * KVW;
+  } else {
+    form.to_slots = kv0; form.slots_L = L;
+    form.attn.kv_bstride = f->slot_len * KVW;
+    form.attn_kv = KvRows{kv0};
+  }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     for (int b = 0; b < B; ++b)

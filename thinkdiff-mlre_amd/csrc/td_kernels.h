@@ -115,6 +115,13 @@ struct TdAttnParams {
   // decode kernel only: sequence b's cache is slot dec_slots[b] (K / V + dec_slots[b] kv_bstride) instead of slot b -- the sequences of a step need not
   // sit in the first slots, so a finished sequence frees its slot without anybody's cache rows being moved (continuous batching); q / o stay row b
   const int* dec_slots = nullptr;
+  // decode kernel only: an e4m3 KV cache (K8 != null; K / V are then unused).  K8 / V8 [batch][Skv, ldkv] hold OCP e4m3 BYTES -- ldkv and kv_bstride count
+  // bytes in this form -- and k_scale / v_scale [batch][Skv, lds] the power-of-two scale 2^e of every (row, kv head) (s_bstride floats between sequences):
+  // the format td_kv_quant_rows_launch writes.  The kernel converts with the scale inside the conversion, so q.k and p.v see the bf16 values q 2^e exactly:
+  // the arithmetic of the bf16 form on a cache that holds the dequantised rows.  With dec_kv_new, the new key and value are rounded through the format before
+  // use and the first workgroup of each kv head writes their bytes and scales.
+  const uint8_t* K8 = nullptr; const uint8_t* V8 = nullptr; const float* k_scale = nullptr; const float* v_scale = nullptr;
+  int lds = 0; long long s_bstride = 0;
   // optional packed segments (device int[batch + 1], non-causal): segment b = rows [seg_starts[b], seg_starts[b+1]) of q/k/v/o; Sq = Skv = the longest
   const int* seg_starts = nullptr;
   // optional hand-off workspace of the persistent (stream-K) joint-attention kernel: td_attn_streamk_ws_bytes() bytes, zeroed
@@ -157,6 +164,18 @@ int td_attn_fp8_launch(const TdAttnParams& p, hipStream_t stream);
 int td_attn_launch(const TdAttnParams& p, hipStream_t stream);
 // Sq = 1 (KV-cached decode) form, csrc/attention_decode.hip; td_attn_launch routes to it
 int td_attn_decode_launch(const TdAttnParams& p, hipStream_t stream);
+// e4m3 KV-cache rows (csrc/attention_decode.hip; the format of TdAttnParams::K8): every 128-wide head vector x of the `rows` bf16 rows kv [rows, ld]
+// (`heads` vectors per row) becomes 128 bytes q = e4m3_rne(x 2^-e) at q[dst, h 128 ..] and one scale 2^e at scale[dst, h], e the smallest integer with
+// max|x| 2^-e <= 448 (clamped to [-40, 40]; 0 for a zero vector), dst = dst_rows[r] (device ints) or r.  kv_hat (may be null, may alias kv; row stride ld):
+// x^ = q 2^e as bf16, exactly, at row r.  ldq in bytes, lds in floats.
+int td_kv_quant_rows_launch(const bf16_t* kv, long long ld, uint8_t* q, long long ldq, float* scale, long long lds, bf16_t* kv_hat, int rows, int heads,
+                            const int* dst_rows, hipStream_t stream);
+// ... and back: out[r, h 128 + d] = q[r, h 128 + d] scale[r, h] as bf16 (exact)
+int td_kv_dequant_rows_launch(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld, int rows, int heads, hipStream_t stream);
+// csrc/flux_model.hip: td_fill_normal_bf16 whose element i draws what element 2 pair0 + i of a fill from pair 0 draws (a piece of a larger buffer).
+// It exists for ONE caller: td_qwen2_init_random on a handle with the e4m3 cache, whose arena lacks the cache rows (td_qwen2::segs), so that the same seed
+// gives the weights of a bf16-cache handle -- what tools/bench_qwen2_kv8.py's two-handle comparison needs.  Every other fill passes pair0 = 0.
+int td_fill_normal_from_launch(bf16_t* dst, long long n, unsigned long long seed, float std, float mean, long long pair0, hipStream_t stream);
 
 struct TdNormParams {
   const bf16_t* x = nullptr; int ldx = 0;

@@ -73,6 +73,52 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> quant_weight_rows_e4m3(const at::
   return std::make_tuple(q, scale, w_hat);
 }
 
+// e4m3 KV-cache rows (td_kv_quant_rows_e4m3): kv bf16 [rows, >= heads 128] -> (q uint8 [rows, heads 128], scale fp32 [rows, heads] = 2^e, kv_hat bf16 [rows, heads 128])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> kv_quant_rows_e4m3(const at::Tensor& kv, int64_t heads) {
+  check_rows(kv, "kv");
+  TORCH_CHECK(kv.dim() == 2 && heads > 0 && kv.size(1) == heads * 128 && kv.size(0) > 0, "thinkdiff_hip::kv_quant_rows_e4m3: kv [rows, heads x 128]");
+  DeviceGuard guard(kv.device());
+  at::Tensor q = at::empty({kv.size(0), heads * 128}, kv.options().dtype(at::kByte));
+  at::Tensor scale = at::empty({kv.size(0), heads}, kv.options().dtype(at::kFloat));
+  at::Tensor kv_hat = at::empty_strided(kv.sizes(), kv.strides(), kv.options());
+  ok(td_kv_quant_rows_e4m3(kv.data_ptr(), kv.stride(0), q.data_ptr(), q.stride(0), (float*)scale.data_ptr(), scale.stride(0), kv_hat.data_ptr(), (int)kv.size(0),
+                           (int)heads, nullptr, stream_of(kv)));
+  return std::make_tuple(q, scale, kv_hat);
+}
+
+// ... and back (td_kv_dequant_rows_e4m3): q uint8 [rows, heads 128], scale fp32 [rows, heads] -> bf16 [rows, heads 128]
+at::Tensor kv_dequant_rows_e4m3(const at::Tensor& q, const at::Tensor& scale) {
+  check_rows(q, "q", at::kByte); check_rows(scale, "scale", at::kFloat); same_device(scale, "scale", q);
+  TORCH_CHECK(q.dim() == 2 && scale.dim() == 2 && q.size(0) > 0 && q.size(0) == scale.size(0) && scale.size(1) > 0 && q.size(1) == scale.size(1) * 128,
+              "thinkdiff_hip::kv_dequant_rows_e4m3: q [rows, heads x 128], scale [rows, heads]");
+  DeviceGuard guard(q.device());
+  at::Tensor out = at::empty({q.size(0), q.size(1)}, q.options().dtype(at::kBFloat16));
+  ok(td_kv_dequant_rows_e4m3(q.data_ptr(), q.stride(0), (const float*)scale.data_ptr(), scale.stride(0), out.data_ptr(), out.stride(0), (int)q.size(0), (int)scale.size(1),
+                             stream_of(q)));
+  return out;
+}
+
+// Decode attention over an e4m3 cache (td_attention_decode_kv8): q bf16 [B, Hq 128]; k8 / v8 uint8 [B, Skv, >= Hkv 128] and k_scale / v_scale fp32 [B, Skv, >= Hkv]
+// (views of the two planes; k and v share their strides); kv_lens int32 [B] or None -> bf16 [B, Hq 128]
+at::Tensor attention_decode_kv8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& k_scale, const at::Tensor& v_scale,
+                                const c10::optional<at::Tensor>& kv_lens, int64_t Hq, int64_t Hkv, double scale) {
+  check_rows(q, "q"); check_rows(k8, "k8", at::kByte); check_rows(v8, "v8", at::kByte); check_rows(k_scale, "k_scale", at::kFloat); check_rows(v_scale, "v_scale", at::kFloat);
+  same_device(k8, "k8", q); same_device(v8, "v8", q); same_device(k_scale, "k_scale", q); same_device(v_scale, "v_scale", q);
+  TORCH_CHECK(q.dim() == 2 && k8.dim() == 3 && v8.dim() == 3 && k_scale.dim() == 3 && v_scale.dim() == 3 && Hq > 0 && Hkv > 0 && q.size(1) == Hq * 128,
+              "thinkdiff_hip::attention_decode_kv8: q [B, Hq x 128], k8 / v8 [B, Skv, Hkv x 128], k_scale / v_scale [B, Skv, Hkv]");
+  const int64_t B = q.size(0), Skv = k8.size(1);
+  TORCH_CHECK(k8.size(0) == B && v8.sizes() == k8.sizes() && v8.strides() == k8.strides() && k8.size(2) >= Hkv * 128 && k_scale.size(0) == B && k_scale.size(1) == Skv &&
+              k_scale.size(2) >= Hkv && v_scale.sizes() == k_scale.sizes() && v_scale.strides() == k_scale.strides(),
+              "thinkdiff_hip::attention_decode_kv8: the k and v planes must share shape and strides, with Skv rows per sequence");
+  if (kv_lens.has_value() && kv_lens->defined()) check_vec(*kv_lens, "kv_lens", q, B, at::kInt);
+  DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({B, Hq * 128}, q.options());
+  ok(td_attention_decode_kv8(q.data_ptr(), q.stride(0), q.stride(0), k8.data_ptr(), v8.data_ptr(), k8.stride(1), k8.stride(0), (const float*)k_scale.data_ptr(),
+                             (const float*)v_scale.data_ptr(), k_scale.stride(1), k_scale.stride(0), o.data_ptr(), o.stride(0), o.stride(0), (int)B, (int)Skv,
+                             (const int*)P(kv_lens), (int)Hq, (int)Hkv, (float)scale, stream_of(q)));
+  return o;
+}
+
 // linear with the weight given as e4m3 bytes + row scales (the 8-bit weight stream, M <= 64)
 at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& w_scale, const c10::optional<at::Tensor>& bias, int64_t act,
                      const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& res) {
@@ -809,6 +855,9 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_lora_set_adapters(int engine, str[] names, float[] weights) -> ()");
   m.def("flux_lora_delete(int engine, str adapter) -> ()");
   m.def("quant_weight_rows_e4m3(Tensor w) -> (Tensor, Tensor, Tensor)");
+  m.def("kv_quant_rows_e4m3(Tensor kv, int heads) -> (Tensor, Tensor, Tensor)");
+  m.def("kv_dequant_rows_e4m3(Tensor q, Tensor scale) -> Tensor");
+  m.def("attention_decode_kv8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor");
   m.def("linear_w8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
 }
 
@@ -854,6 +903,9 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_ip_adapter_load_param", &flux_ip_adapter_load_param);
   m.impl("flux_set_ip_image_embeds", &flux_set_ip_image_embeds);
   m.impl("quant_weight_rows_e4m3", &quant_weight_rows_e4m3);
+  m.impl("kv_quant_rows_e4m3", &kv_quant_rows_e4m3);
+  m.impl("kv_dequant_rows_e4m3", &kv_dequant_rows_e4m3);
+  m.impl("attention_decode_kv8", &attention_decode_kv8);
   m.impl("linear_w8", &linear_w8);
 }
 

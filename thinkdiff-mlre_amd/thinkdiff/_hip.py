@@ -203,6 +203,12 @@ def _declare(L):
         "td_qwen2_quantize_weights": [vp, i32, vp],
         "td_qwen2_set_weight_stream": [vp, i32],
         "td_qwen2_weight_info": [vp, vp, vp, vp, vp],
+        "td_qwen2_create_kv": [vp, i32, i32, i32, i32, vp],
+        "td_qwen2_kv_info": [vp, vp, vp, vp],
+        "td_qwen2_read_kv": [vp, i32, i32, i32, i32, vp, vp],
+        "td_kv_quant_rows_e4m3": [vp, i64, vp, i64, vp, i64, vp, i32, i32, vp, vp],
+        "td_kv_dequant_rows_e4m3": [vp, i64, vp, i64, vp, i64, i32, i32, vp],
+        "td_attention_decode_kv8": [vp, i64, i64, vp, vp, i64, i64, vp, vp, i64, i64, vp, i64, i64, i32, i32, vp, i32, i32, f32, vp],
         "td_quant_weight_rows_e4m3": [vp, i64, vp, vp, vp, i32, i32, vp],
         "td_linear_w8_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp],
         "td_linear_split_w8_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
@@ -290,6 +296,61 @@ def quant_weight_rows_e4m3(w, want_w_hat=True, inplace=False):
         assert w_hat.stride(0) == w.stride(0)
     check(lib().td_quant_weight_rows_e4m3(ptr(w), _rows(w), ptr(q), ptr(scale), ptr(w_hat), N, K, stream_ptr()))
     return q, scale, w_hat
+
+
+QWEN2_KV_BF16, QWEN2_KV_E4M3 = 0, 1
+
+
+def kv_quant_rows_e4m3(kv, heads, q=None, scale=None, dst_rows=None, want_kv_hat=True, inplace=False):
+    """The e4m3 KV-cache format on bf16 rows (td_kv_quant_rows_e4m3): kv [rows, >= heads * 128] -> (q uint8, scale fp32 = 2^e, kv_hat bf16 = q 2^e
+    exactly, or None).  q [R, >= heads * 128] / scale [R, >= heads] may be given (views of larger planes) with dst_rows int32 [rows]: row r is then written at
+    row dst_rows[r] and no other row is touched.  inplace: kv_hat is written over kv."""
+    rows = kv.shape[0]
+    assert kv.dim() == 2 and kv.dtype == torch.bfloat16 and kv.stride(1) == 1
+    if q is None:
+        assert dst_rows is None
+        q = torch.empty((rows, heads * 128), dtype=torch.uint8, device=kv.device)
+        scale = torch.empty((rows, heads), dtype=torch.float32, device=kv.device)
+    assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and q.dim() == 2 and scale.dim() == 2 and q.stride(1) == 1 and scale.stride(1) == 1
+    if dst_rows is not None:
+        assert dst_rows.dtype == torch.int32 and dst_rows.is_contiguous() and dst_rows.numel() == rows
+    kv_hat = kv if inplace else (torch.empty_strided(kv.shape, kv.stride(), dtype=kv.dtype, device=kv.device) if want_kv_hat else None)
+    check(lib().td_kv_quant_rows_e4m3(ptr(kv), kv.stride(0), ptr(q), q.stride(0), ptr(scale), scale.stride(0), ptr(kv_hat), rows, int(heads),
+                                      ptr(dst_rows), stream_ptr()))
+    return q, scale, kv_hat
+
+
+def kv_dequant_rows_e4m3(q, scale, out=None):
+    """bytes [rows, >= heads * 128] + scales [rows, heads] -> bf16 [rows, heads * 128] = q 2^e (td_kv_dequant_rows_e4m3)."""
+    assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and q.dim() == 2 and scale.dim() == 2 and q.stride(1) == 1 and scale.stride(1) == 1
+    rows, heads = scale.shape
+    if out is None:
+        out = torch.empty((rows, heads * 128), dtype=torch.bfloat16, device=q.device)
+    assert out.dtype == torch.bfloat16 and out.stride(1) == 1
+    check(lib().td_kv_dequant_rows_e4m3(ptr(q), q.stride(0), ptr(scale), scale.stride(0), ptr(out), out.stride(0), rows, heads, stream_ptr()))
+    return out
+
+
+def attention_decode_kv8(q, k8, v8, k_scale, v_scale, Hq, Hkv, kv_lens=None, scale=None, out=None):
+    """Decode attention over an e4m3 cache (td_attention_decode_kv8): q bf16 [B, >= Hq*128]; k8, v8 uint8 [B, Skv, >= Hkv*128] and k_scale, v_scale fp32
+    [B, Skv, >= Hkv] (views into the byte / scale planes; k and v share their strides); kv_lens int32 [B] or None -> out bf16 [B, Hq*128]."""
+    B, Skv = k8.shape[0], k8.shape[1]
+    assert q.dim() == 2 and q.dtype == torch.bfloat16 and q.stride(1) == 1 and q.shape[0] == B
+    for t in (k8, v8):
+        assert t.dim() == 3 and t.dtype == torch.uint8 and t.stride(2) == 1
+    for t in (k_scale, v_scale):
+        assert t.dim() == 3 and t.dtype == torch.float32 and t.stride(2) == 1 and t.shape[:2] == (B, Skv)
+    assert k8.stride() == v8.stride() and k_scale.stride() == v_scale.stride()
+    if kv_lens is not None:
+        assert kv_lens.dtype == torch.int32 and kv_lens.is_contiguous() and kv_lens.numel() == B
+    if out is None:
+        out = torch.empty((B, Hq * 128), dtype=torch.bfloat16, device=q.device)
+    if scale is None:
+        scale = 128 ** -0.5
+    check(lib().td_attention_decode_kv8(ptr(q), q.stride(0), q.stride(0), ptr(k8), ptr(v8), k8.stride(1), k8.stride(0), ptr(k_scale), ptr(v_scale),
+                                        k_scale.stride(1), k_scale.stride(0), ptr(out), out.stride(0), out.stride(0), B, Skv, ptr(kv_lens), Hq, Hkv,
+                                        float(scale), stream_ptr()))
+    return out
 
 
 def _w8(x, wq, w_scale):

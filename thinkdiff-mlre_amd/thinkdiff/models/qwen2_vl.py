@@ -47,8 +47,23 @@ class SamplingParams:
 class Qwen2VLTextEngine:
     dtype = torch.bfloat16
 
+    # vLLM's `kv_cache_dtype` values the engine serves: "auto" (the model dtype, bf16) and the two spellings of OCP e4m3
+    KV_CACHE_DTYPES = {"auto": _hip.QWEN2_KV_BF16, "fp8": _hip.QWEN2_KV_E4M3, "fp8_e4m3": _hip.QWEN2_KV_E4M3}
+
+    @classmethod
+    def check_kv_cache_dtype(cls, value):
+        """vllm_config["kv_cache_dtype"] as the models take it: "auto" / None (bf16), "fp8" or "fp8_e4m3" (the e4m3 cache); anything else -- "fp8_e5m2"
+        included -- is an error naming the value, never ignored.  Returns "auto" or "fp8"."""
+        if value is None:
+            return "auto"
+        if not isinstance(value, str) or value not in cls.KV_CACHE_DTYPES:
+            raise ValueError(f"vllm_config kv_cache_dtype={value!r} is not served by the HIP engine: only 'fp8' / 'fp8_e4m3' (e4m3 bytes with a power-of-two "
+                             "scale per token and kv head), or 'auto' / None for bf16")
+        return "auto" if cls.KV_CACHE_DTYPES[value] == _hip.QWEN2_KV_BF16 else "fp8"
+
     def __init__(self, config: Optional[Qwen2VLTextConfig] = None, max_model_len: int = 8192, device="cuda", n_slots: int = 1,
-                 prefill_rows: Optional[int] = None, **kw):
+                 prefill_rows: Optional[int] = None, kv_cache_dtype: Optional[str] = "auto", **kw):
+        self.kv_cache_dtype = self.check_kv_cache_dtype(kv_cache_dtype)      # (before anything is allocated)
         self.config = config or Qwen2VLTextConfig(**kw)
         c = self.config
         self.device = torch.device(device)
@@ -63,7 +78,8 @@ class Qwen2VLTextEngine:
             # n_slots sequences of max_model_len tokens each (batched decode); n_slots = 1 is the single-request engine
             # prefill_rows: activation-workspace rows = the capacity (sum of padded prompt lengths) of one batched prefill
             self.prefill_rows = max(int(prefill_rows or 0), max_model_len)
-            _hip.check(self._L.td_qwen2_create_ex(ctypes.byref(cc), max_model_len, int(n_slots), self.prefill_rows, ctypes.byref(h)))
+            _hip.check(self._L.td_qwen2_create_kv(ctypes.byref(cc), max_model_len, int(n_slots), self.prefill_rows,
+                                                  self.KV_CACHE_DTYPES[self.kv_cache_dtype], ctypes.byref(h)))
         self._h = h
         # set by the models from vllm_config["quantization"]: every load below then ends with quantize_weights (None: the bf16 engine, untouched)
         self.weight_quantization: Optional[str] = None
@@ -173,6 +189,20 @@ class Qwen2VLTextEngine:
         _hip.check(self._L.td_qwen2_weight_info(self._h, ctypes.byref(mode), ctypes.byref(on), ctypes.byref(nbytes), ctypes.byref(n)))
         return {"mode": {v: k for k, v in self.WEIGHT_QUANTIZATIONS.items()}.get(mode.value, "bf16"), "stream_on": bool(on.value),
                 "bytes_8bit": int(nbytes.value), "n_linears": int(n.value)}
+
+    # ---- e4m3 KV cache ----------------------------------------------------------------------------------------
+    def kv_cache_info(self) -> dict:
+        """{"dtype": "auto" | "fp8", "bytes_per_row": bytes of one cache row of one layer, "cache_bytes": bytes of the whole handle's cache}."""
+        mode, row, total = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(self._L.td_qwen2_kv_info(self._h, ctypes.byref(mode), ctypes.byref(row), ctypes.byref(total)))
+        return {"dtype": "fp8" if mode.value == _hip.QWEN2_KV_E4M3 else "auto", "bytes_per_row": int(row.value), "cache_bytes": int(total.value)}
+
+    def read_kv(self, layer: int, slot: int, row0: int, n: int) -> torch.Tensor:
+        """Cache rows [row0, row0 + n) of sequence `slot` in layer `layer` as bf16 [n, 2 Hkv 128] (rotated k heads | v heads): the values every
+        consumer sees -- on an e4m3 cache the dequantised bytes, which is exact."""
+        out = torch.empty(int(n), 2 * self.config.num_key_value_heads * 128, dtype=torch.bfloat16, device=self.device)
+        _hip.check(self._L.td_qwen2_read_kv(self._h, int(layer), int(slot), int(row0), int(n), _hip.ptr(out), _hip.stream_ptr()))
+        return out
 
     # ---- one decoder pass over n new tokens ---------------------------------------------------------------
     def set_slots(self, n_slots: int):
