@@ -237,18 +237,29 @@ def test_decode_attention_groups_q_heads_of_a_kv_head(hip, Hq, Hkv, G):
     assert _rel(outs[G][0], outs[1][0]) < 2e-3 and _rel(outs[G][1], outs[1][1]) < 2e-3
 
 
-@pytest.mark.parametrize("Hq,Hkv,G", [(12, 2, 1), (12, 2, 3), (6, 2, 3), (28, 4, 7), (4, 4, 1)])
-def test_decode_fused_rope_and_cache_write_bit_identical(hip, Hq, Hkv, G):
+LENS_FUSED = [1, 2, 15, 16, 17, 31, 63, 64, 65, 100, 130]
+LENS_FUSED_SHORT = [1, 2, 15, 16, 17, 31, 47]
+# (Hq, Hkv, G, cache format, layers, lengths).  The first five are the bf16 cache at full size.  The rest are the smallest shapes that reach the forms no other
+# test runs -- td_attn_decode_kernel<G, e4m3 cache> for G = 2, 3, 4, 6, 7 with the fused rope (the engine tests of the e4m3 cache step at G = 1), and
+# G = 4 without it in either format (no decode-attention case has 4 q heads per kv head): one layer, two kv heads, a few dozen cached rows.
+FUSED_CASES = [(12, 2, 1, "auto", 2, LENS_FUSED), (12, 2, 3, "auto", 2, LENS_FUSED), (6, 2, 3, "auto", 2, LENS_FUSED), (28, 4, 7, "auto", 2, LENS_FUSED),
+               (4, 4, 1, "auto", 2, LENS_FUSED), (8, 2, 4, "auto", 1, LENS_FUSED_SHORT), (4, 2, 2, "fp8", 1, LENS_FUSED_SHORT), (6, 2, 3, "fp8", 1, LENS_FUSED_SHORT),
+               (8, 2, 4, "fp8", 1, LENS_FUSED_SHORT), (12, 2, 6, "fp8", 1, LENS_FUSED_SHORT), (14, 2, 7, "fp8", 1, LENS_FUSED_SHORT)]
+
+
+@pytest.mark.parametrize("Hq,Hkv,G,kv,layers,lens", FUSED_CASES,
+                         ids=[f"{c[0]}-{c[1]}-{c[2]}" + ("" if c[3] == "auto" and c[4] == 2 else f"-{c[3]}-short") for c in FUSED_CASES])
+def test_decode_fused_rope_and_cache_write_bit_identical(hip, Hq, Hkv, G, kv, layers, lens):
     """td_qwen2_set_fused_rope: the decode attention rotates its own q heads and the new key, attends the new key / value from registers and
     writes them to the cache.  Hidden states, logits AND the cache (seen through three further steps) must be bit-identical to the form with
     the separate rope + scatter launch, for one head per workgroup and for grouped q heads, sequence lengths that put the new key in every
-    key slot of the 16-slot order, and three distinct M-RoPE streams."""
+    key slot of the 16-slot order, and three distinct M-RoPE streams; in both cache formats (kv = "fp8": the e4m3 cache, where both forms round
+    the new key and value through the format)."""
     from thinkdiff.models.qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine
-    tc = Qwen2VLTextConfig(hidden_size=512, num_hidden_layers=2, num_attention_heads=Hq, num_key_value_heads=Hkv, intermediate_size=1024, vocab_size=1024)
-    lens = [1, 2, 15, 16, 17, 31, 63, 64, 65, 100, 130]
+    tc = Qwen2VLTextConfig(hidden_size=512, num_hidden_layers=layers, num_attention_heads=Hq, num_key_value_heads=Hkv, intermediate_size=1024, vocab_size=1024)
     outs = {}
     for fused in (False, True):
-        e = Qwen2VLTextEngine(tc, max_model_len=len(lens) * 160, n_slots=len(lens)).init_random(5)
+        e = Qwen2VLTextEngine(tc, max_model_len=len(lens) * 160, n_slots=len(lens), kv_cache_dtype=kv).init_random(5)
         assert e.set_fused_rope(fused) is True        # the default is the fused form
         g = torch.Generator().manual_seed(9)
         for b, n in enumerate(lens):

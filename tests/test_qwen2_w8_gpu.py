@@ -221,12 +221,13 @@ def test_linear_w8_split_output(hip, M, N, K, n_split):
         _check(torch.cat([y0, y1], dim=1), ref, tol, f"{what} split output")
 
 
-@pytest.mark.parametrize("M,inter,K", [(2, 64, 1536), (8, 40, 48), (17, 64, 1024), (64, 8192, 512), (33, 2048, 4096), (64, 8192, 4096)])
+@pytest.mark.parametrize("M,inter,K", [(2, 64, 1536), (8, 40, 48), (17, 64, 1024), (64, 8192, 512), (33, 2048, 4096), (64, 8192, 4096), (5, 64, 2048)])
 def test_linear_w8_glu(hip, M, inter, K):
     """out = bf16(bf16(silu(bf16(g))) * bf16(u)), g / u = x . gate / up rows.  M = 2, 8: dot form; then the matrix-core kernel gated (blocks = inter / 8):
-    17 x 64: <2, 1, shallow>; 64 x 8192 x 512: <4, 2, shallow>; 33 x 2048 x 4096: <3, 1, DEEP>; 64 x 8192 x 4096: <4, 2, DEEP>.  Not every
+    17 x 64: <2, 1, shallow>; 64 x 8192 x 512: <4, 2, shallow>; 33 x 2048 x 4096: <3, 1, DEEP>; 64 x 8192 x 4096: <4, 2, DEEP>; 5 x 64 x 2048: <1, 1, shallow>
+    with K split over 2 workgroups (one activation block, and the ticket hand-off's finisher running the gated epilogue).  Not every
     <MB, NR, DEEP> is run gated: the gated mode changes which weight rows and scales a block addresses and the epilogue, none of which depends on
-    MB or DEEP beyond what these four cover (both NR, both depths, an odd and a full MB); the loop forms themselves are all run plain above.
+    MB or DEEP beyond what these five cover (both NR, both depths, one, an odd and a full MB); the loop forms themselves are all run plain above.
     Bound, carried through the chain: dg = sum bound + ulp(g); silu has slope <= 1.1 and is evaluated in fp32 with v_exp / v_rcp (<= 2^-20 relative,
     generous): ds = 1.1 dg + 2^-20 |s| + ulp(s); du = sum bound + ulp(u); product: |s| du + |u| ds + ds du; plus the output's ulp."""
     x, q, s, wh = _rand_problem(M, 2 * inter, K, seed=M + inter)

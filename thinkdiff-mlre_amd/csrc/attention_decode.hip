@@ -9,10 +9,9 @@
 // Semantics = td_attn_launch with Sq = 1, causal, kv_lens (keys [0, kv_lens[b]) of sequence b are visible).
 //
 // e4m3 KV cache (td_attn_decode_kernel<G, true>, TdAttnParams::K8; include/thinkdiff_hip.h "e4m3 KV cache"): every 128-wide head vector of a cache row is
-// 128 OCP e4m3 bytes under ONE POWER-OF-TWO scale, x^ = q 2^e with e the smallest integer that brings the vector's largest magnitude to <= 448 (the weight
-// format of csrc/quant_weight.hip per head vector; csrc/kv8_math.h).  x^ is a bf16 value exactly, so the 8-bit form is this kernel on a cache that holds
-// K^ | V^: a lane fetches 8 bytes of the 128-byte line and the line's scale, and the scale goes INTO the conversion (v_cvt_scalef32_pk_bf16_fp8 for k,
-// v_cvt_scalef32_pk_f32_fp8 for v), never onto a rounded value.  Deviation from vLLM's kv_cache_dtype="fp8": one scale per (token, kv head, k or v) instead of
+// 128 bytes in the e4m3 power-of-two format of csrc/e4m3_pow2.h, one scale per head vector.  x^ is a bf16 value exactly, so the 8-bit form is this kernel
+// on a cache that holds K^ | V^: a lane fetches 8 bytes of the 128-byte line and the line's scale, and the scale goes INTO the conversion (to bf16 for k,
+// to fp32 for v), never onto a rounded value.  Deviation from vLLM's kv_cache_dtype="fp8": one scale per (token, kv head, k or v) instead of
 // one per tensor.  Below the kernel: td_kv_quant_rows_kernel / td_kv_dequant_rows_kernel, which move bf16 k | v rows into and out of that format (prefill
 // scatter, staging of a continued forward, td_qwen2_read_kv).
 #include <atomic>
@@ -21,40 +20,18 @@
 
 #include "td_common.h"
 #include "td_kernels.h"
-#include "kv8_math.h"
+#include "e4m3_pow2.h"
+#include "qk_rope_math.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-__device__ __forceinline__ float dot8q(const u32x4_t& a, const u32x4_t& b) {
-  float acc = 0.f;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned ua = a[q], ub = b[q];   // copy out first: bit_cast on a vector-element lvalue reads element 0 (hipcc 7.2)
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, ua), __builtin_bit_cast(bf16x2_t, ub), acc, false);
-  }
-  return acc;
-}
-
-// Sum over the 16 lanes of a DPP row, every lane ending with the total: four rotate-and-add VALU instructions (row_ror 8, 4, 2, 1).  The
-// `__shfl_xor(s, off, 16)` butterfly this replaces compiles to ds_bpermute -- four DEPENDENT trips through the LDS crossbar per score, ~230 per
-// workgroup at 300 keys and three query heads: that chain, not the K/V stream, was most of the kernel's 23 us at 64 sequences (round 4).
-__device__ __forceinline__ float row_sum16(float s) {
-  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x128, 0xf, 0xf, false));
-  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x124, 0xf, 0xf, false));
-  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x122, 0xf, 0xf, false));
-  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x121, 0xf, 0xf, false));
-  return s;
-}
 
 // What a lane fetches of one key: its 16 B of the bf16 k and v head rows, or -- e4m3 cache -- its 8 B of each 128-byte line and the line's two scales.
 struct KeyRaw16 { u32x4_t k, v; };
 struct KeyRaw8 { u32x2_t k, v; float ks, vs; };
 
 // KV8: the cache holds e4m3 bytes with one power-of-two scale per (row, kv head, k or v) (TdAttnParams::K8).  A head row is one 128-byte line plus one
-// scale; k goes through v_cvt_scalef32_pk_bf16_fp8 with its scale into the bf16 pairs v_dot2c takes, v through v_cvt_scalef32_pk_f32_fp8 into the fp32
-// values the accumulation takes -- both exact, so from there on the arithmetic is that of the bf16 form on the dequantised cache, instruction for instruction.
+// scale; k is converted with its scale into the bf16 pairs v_dot2c takes (e4m3p2_to_bf16), v into the fp32 values the accumulation takes
+// (e4m3p2_to_f32) -- both exact, so from there on the arithmetic is that of the bf16 form on the dequantised cache, instruction for instruction.
 // A template parameter: the key loop has no branch on the format.
 template <int G, bool KV8>
 __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams p) {
@@ -93,16 +70,13 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
       for (int i = 0; i < 4; ++i) { cs[i] = c0[i]; cs[4 + i] = c1[i]; sn[i] = s0[i]; sn[4 + i] = s1[i]; }
     }
     auto rope = [&](const u32x4_t raw) -> u32x4_t {
-      float x[8], y[8];
+      float x[8], other[8], y[8];
       unsigned r4[4] = {raw[0], raw[1], raw[2], raw[3]};
 #pragma unroll
       for (int i = 0; i < 4; ++i) { x[2 * i] = bf_lo(r4[i]); x[2 * i + 1] = bf_hi(r4[i]); }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float other = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x[i]), 0x128, 0xf, 0xf, false));      // lane j ^ 8 of the row
-        const float rot = (j < 8) ? -other : other;
-        y[i] = rbf(x[i] * cs[i]) + rbf(rot * sn[i]);
-      }
+      for (int i = 0; i < 8; ++i) other[i] = row16_xor8(x[i]);
+      qk_rope_half8_rbf(x, other, j < 8, cs, sn, y);
       return u32x4_t{pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
     };
 #pragma unroll
@@ -143,7 +117,7 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
   auto one_key_f = [&](const u32x4_t& kk, const float (&vf)[8]) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
-      float s = row_sum16(dot8q(kk, q[g])) * sc;
+      float s = row16_sum(dot8(kk, q[g], 0.f)) * sc;
       const float mn = fmaxf(m[g], s);
       const float corr = __builtin_amdgcn_exp2f(m[g] - mn), pe = __builtin_amdgcn_exp2f(s - mn);
       m[g] = mn;
@@ -167,12 +141,9 @@ __global__ __launch_bounds__(256) void td_attn_decode_kernel(const TdAttnParams 
   };
   auto use = [&](const KeyRaw& r) {
     if constexpr (KV8) {
-      typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-      const unsigned v0 = r.v[0], v1 = r.v[1];
-      const f32x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v0, r.vs, false), b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v0, r.vs, true);
-      const f32x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v1, r.vs, false), d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(v1, r.vs, true);
-      const float vf[8] = {a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
-      one_key_f(kv8_to_bf16(r.k, r.ks), vf);
+      float vf[8];
+      e4m3p2_to_f32(r.v, r.vs, vf);
+      one_key_f(e4m3p2_to_bf16(r.k, r.ks), vf);
     } else {
       one_key(r.k, r.v);
     }
@@ -343,7 +314,7 @@ __global__ __launch_bounds__(256) void td_kv_dequant_rows_kernel(const uint8_t* 
   const long long r = unit / heads;
   const int h = (int)(unit - r * heads), j = threadIdx.x & 15;
   const u32x2_t b = *(const u32x2_t*)(q + (size_t)r * ldq + (size_t)h * 128 + 8 * j);
-  *(u32x4_t*)(out + (size_t)r * ld + (size_t)h * 128 + 8 * j) = kv8_to_bf16(b, scale[(size_t)r * lds + h]);
+  *(u32x4_t*)(out + (size_t)r * ld + (size_t)h * 128 + 8 * j) = e4m3p2_to_bf16(b, scale[(size_t)r * lds + h]);
 }
 
 }  // namespace

@@ -221,13 +221,14 @@ __global__ __launch_bounds__(256) void td_qk_norm_rope_kernel(const TdQkRopePara
     }
     float y[8];
     if (p.rotate_half) {
-      // partner element i+64 (or i-64) lives 8 lanes away
+      // partner element i+64 (or i-64) lives 8 lanes away.  The mode is decided per element, on the one-element form of qk_rope_half8_rbf: with one branch
+      // around two 8-wide blocks hipcc packs the products into v_pk_mul_f32, and the copies that feeds cost 18 registers (58 -> 76, 8 -> 6 waves per SIMD).
+      // (`rot` is the select the helper makes itself; the compiler merges the two.)
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const float other = __shfl_xor(x[i], 8, 16);
         const float rot = (l16 < 8) ? -other : other;
-        // rotate_half == 2: every torch op of the bf16 graph rounds (q*cos, rotate_half(q)*sin, their sum)
-        y[i] = p.rotate_half == 2 ? rbf(x[i] * cs[i]) + rbf(rot * sn[i]) : x[i] * cs[i] + rot * sn[i];
+        y[i] = p.rotate_half == 2 ? qk_rope_half_rbf(x[i], other, l16 < 8, cs[i], sn[i]) : x[i] * cs[i] + rot * sn[i];
       }
     } else {
       qk_rope_pairs8(x, cs, sn, y);

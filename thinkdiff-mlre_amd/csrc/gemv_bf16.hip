@@ -15,20 +15,9 @@
 
 #include "td_common.h"
 #include "td_kernels.h"
+#include "e4m3_pow2.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-__device__ __forceinline__ float dot8(const u32x4_t& a, const u32x4_t& b, float acc) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    // copy the elements out first: __builtin_bit_cast applied directly to a vector-element lvalue reads element 0 (hipcc 7.2)
-    const unsigned ua = a[q], ub = b[q];
-    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, ua), __builtin_bit_cast(bf16x2_t, ub), acc, false);
-  }
-  return acc;
-}
 
 __device__ __forceinline__ float act_rt(int act, float x) {
   switch (act) {
@@ -40,18 +29,11 @@ __device__ __forceinline__ float act_rt(int act, float x) {
   }
 }
 
-// 8-bit weights (TdGemmParams::W8): 16 e4m3 bytes of a row -> 8 bf16 pairs, the row's power-of-two scale applied INSIDE the conversion
-// (v_cvt_scalef32_pk_bf16_fp8: exact, the result has 4 significant bits), so v_dot2c sees the operands it sees on the bf16 path
+// 8-bit weights (TdGemmParams::W8, the format of csrc/e4m3_pow2.h): 16 bytes of a row -> 8 bf16 pairs with the row's scale, so v_dot2c sees the
+// operands it sees on the bf16 path
 __device__ __forceinline__ void cvt16(const u32x4_t& w, float scale, u32x4_t& lo, u32x4_t& hi) {
-  unsigned o[8];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const unsigned uw = w[q];
-    o[2 * q] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(uw, scale, false));
-    o[2 * q + 1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(uw, scale, true));
-  }
-  lo = u32x4_t{o[0], o[1], o[2], o[3]};
-  hi = u32x4_t{o[4], o[5], o[6], o[7]};
+  lo = e4m3p2_to_bf16(u32x2_t{w[0], w[1]}, scale);
+  hi = e4m3p2_to_bf16(u32x2_t{w[2], w[3]}, scale);
 }
 
 constexpr int R = 4;          // weight rows (output columns) per workgroup
@@ -204,7 +186,7 @@ template <int MB, int NR> constexpr int gemv_lds_bytes() { return MW * (2 * NR +
 // W8 (TdGemmParams::W8): the weight rows are e4m3 bytes.  A whole 128-byte line of a row is then 128 weights, so a step covers 128 elements of K: the same
 // two weight loads per block as a bf16 step (8 rows x one line each), twice the activation loads, and the loop body below runs its two 64-element halves
 // in turn.  The weight lines go through the slab AS BYTES (same writes, same XOR placement of the 16-byte chunks); a lane reads the 8 bytes of its operand
-// fragment back (ds_read_b64) and converts them with its row's scale (4 x v_cvt_scalef32_pk_bf16_fp8 per fragment) into the very bf16 fragment the bf16
+// fragment back (ds_read_b64) and converts them with its row's scale (e4m3p2_to_bf16) into the very bf16 fragment the bf16
 // form would have read.  Accumulators, reduction, split-K hand-off and epilogue are shared.
 template <int MB, int NR, bool DEEP, bool W8 = false>
 __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParams p, char* ws) {
@@ -317,13 +299,7 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
               if constexpr (W8) {
-                const u32x2_t b = *(const u32x2_t*)(rd8_ptr[kh][h] + nr * 2048);
-                const unsigned b0 = b[0], b1 = b[1];
-                const u32x4_t o = {__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b0, wsc[nr], false)),
-                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b0, wsc[nr], true)),
-                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b1, wsc[nr], false)),
-                                   __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(b1, wsc[nr], true))};
-                wf[nr][h] = __builtin_bit_cast(bf16x8_t, o);
+                wf[nr][h] = __builtin_bit_cast(bf16x8_t, e4m3p2_to_bf16(*(const u32x2_t*)(rd8_ptr[kh][h] + nr * 2048), wsc[nr]));
               } else {
                 wf[nr][h] = *(const bf16x8_t*)(rd_ptr[h] + nr * 2048);
               }
@@ -501,14 +477,36 @@ void launch_dot(const TdGemmParams& p, dim3 grid, hipStream_t stream) {
   else hipLaunchKernelGGL((td_gemv_bf16_kernel<16, W8>), grid, block, 0, stream, p);
 }
 
-// td_gemv_launch for TdGemmParams::W8: the routing of the bf16 form with the 8-bit kernels' own extents (a chunk is 16 weights, an MFMA step 128)
-bool w8_mfma_ok(const TdGemmParams& p) {
+// The two weight forms of the stream kernels, as far as the host's shape rules go
+struct WeightForm { int chunk, step, bytes; };      // weights per 16-byte chunk (dot form), per MFMA k-step, and bytes per weight
+constexpr WeightForm FORM_BF16{8, 64, 2}, FORM_W8{16, 128, 1};
+
+// Shapes the matrix-core form takes.  Its operands sit behind 32-bit buffer descriptors, a k-step is whole, and the epilogue stores 4 columns (8 bytes) at
+// a time.  `gated_checked`: the caller has already put a gated problem (glu_I) through the gated argument check (N == glu_I, a multiple of 8, ldc % 4, lda % 8,
+// no split), which is all a gated launch needs -- its blocks are 8 gate + 8 up rows, so N % 16 is NOT asked.  td_gemv_mfma_ok asks it all the same.
+bool mfma_ok(const TdGemmParams& p, WeightForm f, bool gated_checked) {
   const long long w_rows = p.glu_I ? 2ll * p.glu_I : p.N;
-  if (w_rows * p.K >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
-  if (p.glu_I) return p.K % 128 == 0;
-  return p.K % 128 == 0 && p.N % 16 == 0 && p.ldc % 4 == 0 && p.lda % 8 == 0 && (!p.C2 || (p.ldc2 % 4 == 0 && p.n_split % 4 == 0));
+  if (w_rows * p.K * f.bytes >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
+  if (p.K % f.step != 0) return false;
+  if (p.glu_I && gated_checked) return true;
+  return p.N % 16 == 0 && p.ldc % 4 == 0 && p.lda % 8 == 0 && (!p.C2 || (p.ldc2 % 4 == 0 && p.n_split % 4 == 0));
 }
 
+// The routing tail of both forms: more than 4 rows and a shape the matrix core takes -> MFMA form, else the dot form (the caller has refused more than
+// 16 rows without the MFMA form, in its own words)
+template <bool W8>
+int route(const TdGemmParams& p, bool mfma, hipStream_t stream) {
+  if (p.M > 4 && mfma) {
+    if (int rc = launch_mfma_rows<W8>(p, stream)) return rc;
+  } else {
+    launch_dot<W8>(p, dim3(p.glu_I ? p.glu_I / 2 : p.N / R), stream);
+  }
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
+// td_gemv_launch for TdGemmParams::W8.  It checks the leading dimensions and the alignment of every pointer itself (the bf16 entry below checks lda and
+// the alignment of x and W only): the C ABI's 8-bit entries come straight here
 int gemv_w8_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.W8 && p.w8_scale && p.A && p.C, "td_gemv(w8): x, the 8-bit weights, their row scales and the output are required");
   TD_CHECK_ARG(p.M >= 1 && p.M <= 64, "td_gemv(w8): M=%d: the 8-bit weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", p.M);
@@ -521,56 +519,34 @@ int gemv_w8_launch(const TdGemmParams& p, hipStream_t stream) {
     TD_CHECK_ARG(p.N == p.glu_I && p.glu_I % 8 == 0 && !p.bias && !p.gate && !p.res && !p.C2 && p.act == TD_ACT_NONE && p.ldc % 4 == 0,
                  "td_gemv(w8, glu): N must equal glu_I (multiple of 8), no bias / gate / residual / split");
   }
-  const bool mfma = w8_mfma_ok(p);
+  const bool mfma = mfma_ok(p, FORM_W8, true);
   TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(w8): more than 16 rows need the matrix-core form (K=%d %% 128, N=%d %% 16, ldc %% 4 == 0, operands under 4 GiB)", p.K, p.N);
-  if (p.M > 4 && mfma) {
-    if (int rc = launch_mfma_rows<true>(p, stream)) return rc;
-  } else {
-    launch_dot<true>(p, dim3(p.glu_I ? p.glu_I / 2 : p.N / R), stream);
-  }
-  TD_CHECK_LAUNCH();
-  return 0;
+  return route<true>(p, mfma, stream);
 }
 
 }  // namespace
 
-// shapes the matrix-core weight stream takes (td_gemm_launch asks before routing 16 < M <= 64 here)
+// shapes the 8-bit weight stream takes (csrc/qwen2_engine.hip asks before it routes a Linear to its e4m3 copy)
 bool td_gemv_w8_ok(const TdGemmParams& p) {
-  if (p.M < 1 || p.M > 64 || p.N % R != 0 || p.K % 16 != 0 || p.lda % 8 != 0) return false;
+  if (p.M < 1 || p.M > 64 || p.N % R != 0 || p.K % FORM_W8.chunk != 0 || p.lda % 8 != 0) return false;
   if (p.glu_I && (p.N != p.glu_I || p.glu_I % 8 != 0 || p.ldc % 4 != 0)) return false;
-  return p.M <= 16 || w8_mfma_ok(p);
+  return p.M <= 16 || mfma_ok(p, FORM_W8, true);
 }
 
-bool td_gemv_mfma_ok(const TdGemmParams& p) {
-  const long long w_rows = p.glu_I ? 2ll * p.glu_I : p.N;          // operands sit behind 32-bit buffer descriptors
-  if (w_rows * p.K * 2 >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
-  return p.K % 64 == 0 && p.N % 16 == 0 && p.ldc % 4 == 0 && p.lda % 8 == 0 && (!p.C2 || (p.ldc2 % 4 == 0 && p.n_split % 4 == 0));
-}
-
+// shapes the matrix-core weight stream takes (td_gemm_launch asks before routing 16 < M <= 64 here)
+bool td_gemv_mfma_ok(const TdGemmParams& p) { return mfma_ok(p, FORM_BF16, false); }
 
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemv: unknown activation code act=%d act2=%d", p.act, p.act2);
   if (p.W8) return gemv_w8_launch(p, stream);
-  TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % 8 == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");
+  TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % FORM_BF16.chunk == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");
   TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W) % 16 == 0, "td_gemv: operands must be 16-byte aligned");
   if (p.glu_I) {
     TD_CHECK_ARG(p.N == p.glu_I && p.glu_I % 8 == 0 && !p.bias && !p.gate && !p.res && !p.C2 && p.act == TD_ACT_NONE && p.ldc % 4 == 0,
                  "td_gemv(glu): N must equal glu_I (multiple of 8), no bias / gate / residual / split");
-    const bool mfma = p.K % 64 == 0 && 2ll * p.glu_I * p.K * 2 < 0xFFFFFF00ll && ((long long)(p.M - 1) * p.lda + p.K) * 2 < 0xFFFFFF00ll;
-    TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(glu): more than 16 rows need K %% 64 == 0 and operands under 4 GiB");
-    if (p.M > 4 && mfma) {
-      if (int rc = launch_mfma_rows<false>(p, stream)) return rc;
-    } else launch_dot<false>(p, dim3(p.glu_I / 2), stream);
-    TD_CHECK_LAUNCH();
-    return 0;
   }
-  if (p.M > 4 && td_gemv_mfma_ok(p)) {
-    if (int rc = launch_mfma_rows<false>(p, stream)) return rc;
-    TD_CHECK_LAUNCH();
-    return 0;
-  }
-  TD_CHECK_ARG(p.M <= 16, "td_gemv: more than 16 rows need the matrix-core form (K %% 64, N %% 16, ldc %% 4 == 0)");
-  launch_dot<false>(p, dim3(p.N / R), stream);
-  TD_CHECK_LAUNCH();
-  return 0;
+  const bool mfma = mfma_ok(p, FORM_BF16, true);
+  if (p.glu_I) TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(glu): more than 16 rows need K %% 64 == 0 and operands under 4 GiB");
+  else TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv: more than 16 rows need the matrix-core form (K %% 64, N %% 16, ldc %% 4 == 0)");
+  return route<false>(p, mfma, stream);
 }

@@ -30,3 +30,16 @@ __device__ __forceinline__ void qk_rope_pairs8(const float (&x)[8], const float 
     y[i + 1] = __builtin_fmaf(x[i + 1], cs[i + 1], p1);
   }
 }
+// rotate_half (Qwen2: element d pairs with d +- 64) with EVERY torch op of the bf16 graph rounding: q*cos, rotate_half(q)*sin, their sum (the sum is
+// rounded by the caller's pack to bf16).  x = an element of this lane, other = the element of the lane that holds d +- 64 (lane j ^ 8 of the 16-lane head row;
+// how it is fetched is the caller's business), lower = this lane holds d < 64, whose partner enters negated.  Shared by td_qk_norm_rope_kernel
+// (rotate_half == 2), td_decode_rope_scatter_kernel and the decode attention's fused form, which must agree to the bit.
+__device__ __forceinline__ float qk_rope_half_rbf(float x, float other, bool lower, float cs, float sn) {
+  const float rot = lower ? -other : other;
+  return rbf(x * cs) + rbf(rot * sn);
+}
+// ... of a lane's 8 elements
+__device__ __forceinline__ void qk_rope_half8_rbf(const float (&x)[8], const float (&other)[8], bool lower, const float (&cs)[8], const float (&sn)[8], float (&y)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) y[i] = qk_rope_half_rbf(x[i], other[i], lower, cs[i], sn[i]);
+}

@@ -26,7 +26,8 @@
 #include <vector>
 
 #include "td_kernels.h"
-#include "kv8_math.h"
+#include "e4m3_pow2.h"
+#include "qk_rope_math.h"
 #include "../../include/thinkdiff_hip.h"
 
 namespace {
@@ -146,7 +147,7 @@ __global__ void td_gather_last_rows_kernel(const bf16_t* src, bf16_t* dst, const
 }
 
 // Decode step, one launch for: M-RoPE on the new q rows (in place), M-RoPE on the new k rows, k|v rows -> their sequences' cache
-// rows.  Rotation = rotate_half with every op rounding to bf16 (td_qk_norm_rope_kernel rotate_half == 2: q*cos, rot*sin, sum).
+// rows.  Rotation = rotate_half with every op rounding to bf16 (qk_rope_half8_rbf: what td_qk_norm_rope_kernel does with rotate_half == 2).
 // KV8: the rotated k and the v head vectors go through the e4m3 format (kv8_round_row: what the fused form does in the attention launch) and their
 // bytes and scales are stored in cache8 / scales instead of the bf16 row.
 template <bool KV8>
@@ -164,15 +165,12 @@ __global__ __launch_bounds__(256) void td_decode_rope_scatter_kernel(bf16_t* q, 
     const bf16_t* src = is_q ? q + (size_t)b * QW + u * 128 + l16 * 8 : kv + (size_t)b * KVW + (u - Hq) * 128 + l16 * 8;
     u32x4_t raw = *(const u32x4_t*)src;
     if (!is_v) {
-      float x[8], y[8];
+      float x[8], other[8], y[8];
 #pragma unroll
       for (int i = 0; i < 4; ++i) { x[2 * i] = bf_lo(raw[i]); x[2 * i + 1] = bf_hi(raw[i]); }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float other = __shfl_xor(x[i], 8, 16);
-        const float rot = (l16 < 8) ? -other : other;
-        y[i] = rbf(x[i] * cs[i]) + rbf(rot * sn[i]);
-      }
+      for (int i = 0; i < 8; ++i) other[i] = __shfl_xor(x[i], 8, 16);
+      qk_rope_half8_rbf(x, other, l16 < 8, cs, sn, y);
       raw = u32x4_t{pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]), pack_bf2(y[4], y[5]), pack_bf2(y[6], y[7])};
     }
     if constexpr (KV8) {

@@ -12,6 +12,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4_t;    // 16x16 accumulat
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;  // 32x32 accumulator
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;  // operand of v_dot2c_f32_bf16, result of v_cvt_scalef32_pk_bf16_fp8
 
 #define TD_LDS __attribute__((address_space(3)))
 
@@ -38,6 +39,16 @@ __device__ __forceinline__ float as_f32(unsigned u) { return __builtin_bit_cast(
 __device__ __forceinline__ float rbf(float f) { return bf2f(f2bf(f)); }
 __device__ __forceinline__ float bf_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+// acc + the dot product of 8 bf16 values a side (four packed pairs each): four v_dot2c_f32_bf16 in a chain, element 0 to 3
+__device__ __forceinline__ float dot8(const u32x4_t& a, const u32x4_t& b, float acc) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    // copy the elements out first: __builtin_bit_cast applied directly to a vector-element lvalue reads element 0 (hipcc 7.2)
+    const unsigned ua = a[q], ub = b[q];
+    acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, ua), __builtin_bit_cast(bf16x2_t, ub), acc, false);
+  }
+  return acc;
+}
 
 // ---- activations (fp32 math) -------------------------------------------
 // Written on v_exp_f32 / v_rcp_f32 directly: a plain `/` compiles to the ~12-instruction IEEE division sequence, which made the
@@ -66,6 +77,32 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ---- 16-lane DPP rows (lanes 16 r .. 16 r + 15 of a wave) ------------------
+// ALL 16 LANES OF THE ROW MUST BE ACTIVE: a DPP read of an inactive lane returns 0 (old = 0, bound_ctrl off), silently.
+// The value lane j ^ 8 of the row holds: one rotate by 8.
+__device__ __forceinline__ float row16_xor8(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
+}
+// Sum over the 16 lanes of a row, every lane ending with the total: four rotate-and-add VALU instructions (row_ror 8, 4, 2, 1).  The
+// `__shfl_xor(s, off, 16)` butterfly this replaces compiles to ds_bpermute -- four DEPENDENT trips through the LDS crossbar per score, ~230 per
+// workgroup at 300 keys and three query heads in the decode attention: that chain, not the K/V stream, was most of the kernel's 23 us at 64
+// sequences (round 4).
+__device__ __forceinline__ float row16_sum(float s) {
+  s += row16_xor8(s);
+  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x124, 0xf, 0xf, false));
+  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x122, 0xf, 0xf, false));
+  s += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x121, 0xf, 0xf, false));
+  return s;
+}
+// Maximum over the 16 lanes of a row, every lane ending with it (the same four rotations)
+__device__ __forceinline__ float row16_max(float s) {
+  s = fmaxf(s, row16_xor8(s));
+  s = fmaxf(s, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x124, 0xf, 0xf, false)));
+  s = fmaxf(s, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x122, 0xf, 0xf, false)));
+  s = fmaxf(s, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s), 0x121, 0xf, 0xf, false)));
+  return s;
 }
 
 // ---- error plumbing shared by the C-ABI translation units ---------------

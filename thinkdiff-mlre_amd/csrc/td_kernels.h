@@ -81,8 +81,8 @@ int td_gemm_launch(const TdGemmParams& p, hipStream_t stream);
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream);
 bool td_gemv_mfma_ok(const TdGemmParams& p);   // shapes the matrix-core weight stream takes for 16 < M <= 64
 bool td_gemv_w8_ok(const TdGemmParams& p);     // shapes the 8-bit weight stream takes (p.W8 need not be set yet): what td_gemv_launch would accept with W8
-// Weight-only e4m3 quantisation with one power-of-two scale per row (csrc/quant_weight.hip): q[n, k] = e4m3_rne(w[n, k] 2^-e_n), scale[n] = 2^e_n, e_n the
-// smallest integer with max_k |w[n, k]| 2^-e_n <= 448 (clamped to [-40, 40]; 0 for a zero row); w_hat (may be null, may alias w) = q 2^e_n as bf16, exactly
+// Weight-only e4m3 quantisation with one power-of-two scale per row (csrc/quant_weight.hip; the format: csrc/e4m3_pow2.h): q = the row's bytes,
+// scale[n] = 2^e_n; w_hat (may be null, may alias w) = q 2^e_n as bf16, exactly
 int td_quant_weight_rows_launch(const bf16_t* w, long long ldw, uint8_t* q, float* scale, bf16_t* w_hat, int N, int K, hipStream_t stream);
 // 0: 256x256 (td_gemm_bf16_nt_kernel<8,4>), 1: 256x64, 2: 32x256, 3: 288x192 (<9,3>)
 int td_gemm_config_id(int M, int N, int K);
@@ -164,10 +164,9 @@ int td_attn_fp8_launch(const TdAttnParams& p, hipStream_t stream);
 int td_attn_launch(const TdAttnParams& p, hipStream_t stream);
 // Sq = 1 (KV-cached decode) form, csrc/attention_decode.hip; td_attn_launch routes to it
 int td_attn_decode_launch(const TdAttnParams& p, hipStream_t stream);
-// e4m3 KV-cache rows (csrc/attention_decode.hip; the format of TdAttnParams::K8): every 128-wide head vector x of the `rows` bf16 rows kv [rows, ld]
-// (`heads` vectors per row) becomes 128 bytes q = e4m3_rne(x 2^-e) at q[dst, h 128 ..] and one scale 2^e at scale[dst, h], e the smallest integer with
-// max|x| 2^-e <= 448 (clamped to [-40, 40]; 0 for a zero vector), dst = dst_rows[r] (device ints) or r.  kv_hat (may be null, may alias kv; row stride ld):
-// x^ = q 2^e as bf16, exactly, at row r.  ldq in bytes, lds in floats.
+// e4m3 KV-cache rows (csrc/attention_decode.hip; the layout of TdAttnParams::K8, the format of csrc/e4m3_pow2.h): every 128-wide head vector x of the
+// `rows` bf16 rows kv [rows, ld] (`heads` vectors per row) becomes its 128 bytes at q[dst, h 128 ..] and its scale 2^e at scale[dst, h],
+// dst = dst_rows[r] (device ints) or r.  kv_hat (may be null, may alias kv; row stride ld): x^ = q 2^e as bf16, exactly, at row r.  ldq in bytes, lds in floats.
 int td_kv_quant_rows_launch(const bf16_t* kv, long long ld, uint8_t* q, long long ldq, float* scale, long long lds, bf16_t* kv_hat, int rows, int heads,
                             const int* dst_rows, hipStream_t stream);
 // ... and back: out[r, h 128 + d] = q[r, h 128 + d] scale[r, h] as bf16 (exact)
