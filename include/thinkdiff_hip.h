@@ -1021,6 +1021,52 @@ int td_mrope_table(const int* pos3n, int n, const int* sections3, float theta, i
 int td_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int vocab, float temperature, float top_p,
                          uint64_t seed, uint64_t offset, int32_t* out_ids, void* stream);
 
+/* ---- per-request sampler (td_abi_version() >= 14): top-k, top-p, min-p and the three penalties, every value per row ----
+ * The rest of what a caller sets on vllm.SamplingParams per prompt ([ext] vLLM sampler: apply_penalties, _apply_top_k_top_p, _apply_min_p), in ONE
+ * launch without a sort.  For a row with bf16 logits x[0..vocab), prompt token set P and generated-token counts c[t] (both from the row's slot):
+ *   z[t] = float(x[t]);  for t in P or c[t] > 0:  z[t] = z[t] > 0 ? z[t] / repetition_penalty : z[t] * repetition_penalty;
+ *          z[t] -= frequency_penalty * c[t];  z[t] -= presence_penalty * (c[t] > 0)            (fp32, never rounded back to bf16)
+ *   temperature <= 0: the first index holding max z.  Otherwise p = softmax(z / temperature) and the kept set is the intersection of
+ *     top-k   the k most likely tokens (off when top_k <= 0 or top_k >= vocab),
+ *     top-p   of the top-k set: a token is kept iff the mass in front of it is < top_p x (top-k mass)  (td_sample_top_p_bf16's rule),
+ *     min-p   z[t] >= max z + temperature x ln(min_p), i.e. p[t] >= min_p x max p (off when min_p <= 0);
+ *   renormalise, draw one token.  Ties at a boundary resolve in index order of the kernel's walk (any tied token, the count the rule gives).
+ * The draw is td_sample_top_p_bf16's function of (seed, offset, stream) with `stream` in the place of its row number: rows with one seed and
+ * offset, stream = row, slot = -1 and every filter off return td_sample_top_p_bf16's ids bit for bit.
+ * Out-of-range per-row values never fault: top_p <= 0 keeps the top token only, top_p > 1 or NaN is 1; min_p > 1 is 1; repetition_penalty <= 0 or
+ * non-finite is 1; a non-finite presence / frequency penalty is 0; slot outside [0, n_slots) is "no history".  Degenerate rows as
+ * td_sample_top_p_bf16, after the penalties: a +inf value wins (first index), a row of -inf / NaN yields id 0, one finite value is always taken. */
+typedef struct TdSampleRow {
+  float temperature, top_p, min_p, repetition_penalty, presence_penalty, frequency_penalty;
+  int top_k;
+  int slot;        /* history slot of the td_sampler, -1: no history */
+  int stream;      /* the draw's third key (td_sample_top_p_bf16's row number) */
+  uint64_t seed;
+} TdSampleRow;
+size_t td_sample_row_size(void);      /* sizeof(TdSampleRow), for bindings that restate the struct */
+
+/* Token history of n_slots sequences over one vocabulary: per slot a prompt-presence bitmap, a bitmap of the tokens with history (prompt or
+ * generated) and a uint16 count per vocabulary entry, exact to 65 535 and saturating there: n_slots x vocab x 2.25 bytes of device memory
+ * (87.6 MB at 256 x 152 064), allocated here and zeroed.  n_slots 1..65535, vocab % 8 == 0. */
+typedef struct td_sampler td_sampler;
+int td_sampler_create(int n_slots, int vocab, td_sampler** out);
+void td_sampler_destroy(td_sampler* s);
+/* Clear a slot and mark prompt_ids_dev[0..n_prompt) (device int32; ids outside [0, vocab) are ignored; n_prompt 0 with a NULL pointer just clears). */
+int td_sampler_reset_slot(td_sampler* s, int slot, const int* prompt_ids_dev, int n_prompt, void* stream);
+/* Tests and debugging: counts as int32 [vocab], the prompt set as uint8 [vocab] (0 / 1); set_counts replaces the counts (clamped to 0..65535) and
+ * rebuilds the slot's history bitmap from them and the prompt bitmap. */
+int td_sampler_read_counts(const td_sampler* s, int slot, int32_t* out_dev, void* stream);
+int td_sampler_read_prompt_mask(const td_sampler* s, int slot, uint8_t* out_dev, void* stream);
+int td_sampler_set_counts(td_sampler* s, int slot, const int32_t* counts_dev, void* stream);
+/* One token per row -> out_ids[rows].  params_dev: rows TdSampleRow structs, offsets_dev: rows int64 (the draw's second key, per row), both in
+ * device memory.  s may be NULL iff every row has slot == -1 (the caller's promise: the kernel reads no history when s is NULL).
+ * update_state = 1: the thread that writes out_ids[row] also adds 1 to the slot's count of that token (saturating) and marks it in the history
+ * bitmap; the slots named by one launch must then be distinct (not checked: two rows on one slot race on its counts).  update_state = 0: the
+ * state is only read and rows may share a slot.  TD_ERR_INVALID before any HIP call: a NULL logits / params / offsets / out_ids; vocab % 8,
+ * ld % 8 or logits not 16-byte aligned; rows outside 1..65535; vocab != the state's; update_state with s == NULL. */
+int td_sample_rows_bf16(const td_sampler* s, const void* logits, int64_t ld, int rows, int vocab, const TdSampleRow* params_dev,
+                        const int64_t* offsets_dev, int update_state, int32_t* out_ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

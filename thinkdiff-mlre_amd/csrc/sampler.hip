@@ -19,12 +19,11 @@
 // offset, row) triple always yields the same token.  HBM/L2-bound, ~4 reads of the row per token.
 #include "td_common.h"
 #include "td_kernels.h"
+#include "sampler_common.h"
 
 namespace {
 
-constexpr int NT = 1024;            // threads per workgroup
-constexpr int NW = NT / 64;         // waves
-typedef unsigned long long u64;
+using namespace td_sampler_detail;
 
 // larger logit <-> larger key; NaN sorts below everything
 __device__ __forceinline__ unsigned key16(unsigned b) {
@@ -40,37 +39,6 @@ __device__ __forceinline__ u64 mass_of(unsigned k, float xmax, float c) {
   const float e = __builtin_amdgcn_exp2f((unkey16(k) - xmax) * c);
   return (u64)(e * 1099511627776.0f);
 }
-__device__ __forceinline__ u64 splitmix64(u64 z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// exclusive prefix sum of one value per thread over the workgroup (thread order); total in *tot.  `scratch`: NW + 1 slots.
-template <typename T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T* scratch, T* tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
-  if (lane == 63) scratch[w] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T run = 0;
-    for (int i = 0; i < NW; ++i) { const T t = scratch[i]; scratch[i] = run; run += t; }
-    scratch[NW] = run;
-  }
-  __syncthreads();
-  const T base = scratch[w];
-  *tot = scratch[NW];
-  __syncthreads();
-  return base + inc - v;
-}
-
 // Among 256 bins (mass in bins[], thread t < 256 owns bin t): the bin b, scanning from the top, in which the running mass first
 // reaches `target` given `base` mass already in front of bin 255.  Writes {b, mass in front of b} for the one bin that matches.
 __device__ __forceinline__ void find_crossing(const u64* bins, u64 base, u64 target, u64* scratch, int* out_bin, u64* out_above) {
@@ -239,7 +207,7 @@ __global__ __launch_bounds__(NT) void td_sample_top_p_kernel(const bf16_t* __res
   const u64 my_mass = my_gt + (u64)tie_room * m_tau;
   u64 mass_total;
   const u64 m_off = block_exclusive_scan<u64>(my_mass, scr64, &mass_total);
-  const u64 rnd = splitmix64(splitmix64(seed ^ (0xD1B54A32D192ED03ull * (offset + 1ull))) ^ (0x9E3779B97F4A7C15ull * ((u64)row + 1ull)));
+  const u64 rnd = draw_bits(seed, offset, (u64)row);
   const u64 r = __umul64hi(rnd, kept);                       // uniform in [0, kept); mass_total == kept by construction
   if (tid == 0) out[row] = 0;                              // always defined; the owner of r overwrites it below
   __syncthreads();

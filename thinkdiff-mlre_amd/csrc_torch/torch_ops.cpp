@@ -472,6 +472,26 @@ at::Tensor sample_top_p(const at::Tensor& logits, double temperature, double top
   return out;
 }
 
+// one token per row, every row under its own TdSampleRow (params: uint8 [rows, sizeof(TdSampleRow)] on the device, offsets: int64 [rows]); state: a
+// td_sampler handle as an int (thinkdiff._hip.Sampler.handle) or None when no row names a history slot
+at::Tensor sample_rows(const at::Tensor& logits, const at::Tensor& params, const at::Tensor& offsets, c10::optional<int64_t> state, bool update_state) {
+  check_rows(logits, "logits");
+  at::Tensor x = logits.dim() == 1 ? logits.unsqueeze(0) : logits;
+  TORCH_CHECK(x.dim() == 2, "thinkdiff_hip::sample_rows: logits [rows, vocab]");
+  const int64_t rows = x.size(0);
+  TORCH_CHECK(params.is_cuda() && params.device() == x.device() && params.scalar_type() == at::kByte && params.is_contiguous() &&
+              params.numel() == rows * (int64_t)td_sample_row_size(),
+              "thinkdiff_hip::sample_rows: params must be a contiguous uint8 tensor of ", rows, " x ", td_sample_row_size(), " bytes on the logits' device");
+  TORCH_CHECK(offsets.is_cuda() && offsets.device() == x.device() && offsets.scalar_type() == at::kLong && offsets.is_contiguous() && offsets.numel() == rows,
+              "thinkdiff_hip::sample_rows: offsets must be a contiguous int64 tensor of ", rows, " entries on the logits' device");
+  DeviceGuard guard(x.device());
+  at::Tensor out = at::empty({rows}, x.options().dtype(at::kInt));
+  const td_sampler* s = state.has_value() && *state != 0 ? reinterpret_cast<const td_sampler*>(*state) : nullptr;
+  ok(td_sample_rows_bf16(s, x.data_ptr(), x.stride(0), (int)rows, (int)x.size(1), (const TdSampleRow*)params.data_ptr(), (const int64_t*)offsets.data_ptr(),
+                         update_state ? 1 : 0, (int32_t*)out.data_ptr(), stream_of(x)));
+  return out;
+}
+
 // ---- the engines: the denoise loop itself goes through the dispatcher ----------------------------------------------------------------
 // An engine is a stateful C++ object behind the C ABI (weights, workspaces, prepared conditioning); the ops take its handle as an int (the
 // td_flux* / td_vae* value, as thinkdiff.models.* hold it) and check every tensor against what the prepared context expects.
@@ -820,6 +840,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_unpack_latents(Tensor packed, int C, int H, int W, float div, float add) -> Tensor");
   m.def("cls_avgpool2(Tensor tokens) -> Tensor");
   m.def("sample_top_p(Tensor logits, float temperature, float top_p, int seed, int offset) -> Tensor");
+  m.def("sample_rows(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state) -> Tensor");
   m.def("flux_forward_(int engine, Tensor latents, int step, Tensor(a!) velocity) -> Tensor(a!)");
   m.def("flux_denoise_(int engine, Tensor(a!) latents, float[] sigmas) -> Tensor(a!)");
   m.def("flux_denoise_multi_(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()");
@@ -872,6 +893,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_unpack_latents", &flux_unpack_latents);
   m.impl("cls_avgpool2", &cls_avgpool2);
   m.impl("sample_top_p", &sample_top_p);
+  m.impl("sample_rows", &sample_rows);
   m.impl("flux_forward_", &flux_forward_);
   m.impl("flux_denoise_", &flux_denoise_);
   m.impl("flux_denoise_multi_", &flux_denoise_multi_);

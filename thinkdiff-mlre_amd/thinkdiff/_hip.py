@@ -222,6 +222,12 @@ def _declare(L):
         "td_attention_joint_prescaled_bf16": [vp, i64, vp, vp, i64, vp, i64, i32, i32, f32, vp],
         "td_attention_fp8_qk_rope": [vp, i64, i32, i32, i32, vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, f32, vp, vp],
         "td_sample_top_p_bf16": [vp, i64, i32, i32, f32, f32, ctypes.c_uint64, ctypes.c_uint64, vp, vp],
+        "td_sampler_create": [i32, i32, vp],
+        "td_sampler_reset_slot": [vp, i32, vp, i32, vp],
+        "td_sampler_read_counts": [vp, i32, vp, vp],
+        "td_sampler_read_prompt_mask": [vp, i32, vp, vp],
+        "td_sampler_set_counts": [vp, i32, vp, vp],
+        "td_sample_rows_bf16": [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("TD_HIP_LIB") and not hasattr(L, name):
@@ -237,6 +243,11 @@ def _declare(L):
     L.td_vae_enc_destroy.restype = None
     L.td_qwen2_destroy.argtypes = [vp]
     L.td_qwen2_destroy.restype = None
+    if hasattr(L, "td_sampler_destroy"):
+        L.td_sampler_destroy.argtypes = [vp]
+        L.td_sampler_destroy.restype = None
+        L.td_sample_row_size.argtypes = []
+        L.td_sample_row_size.restype = ctypes.c_size_t
     L.td_qwen2_weight_stream_launches.argtypes = [vp]
     L.td_qwen2_weight_stream_launches.restype = ctypes.c_int64
     L.td_flux_param_elems.argtypes = [vp]
@@ -1057,6 +1068,107 @@ def sample_top_p(logits, temperature, top_p, seed, offset, out=None):
         out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
     check(lib().td_sample_top_p_bf16(ptr(x), x.stride(0), x.shape[0], x.shape[1], float(temperature), float(top_p),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, ptr(out), stream_ptr()))
+    return out
+
+
+class TdSampleRow(ctypes.Structure):
+    """One row's settings for td_sample_rows_bf16 (include/thinkdiff_hip.h; sizeof checked against td_sample_row_size() in tests)."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float), ("min_p", ctypes.c_float), ("repetition_penalty", ctypes.c_float),
+                ("presence_penalty", ctypes.c_float), ("frequency_penalty", ctypes.c_float), ("top_k", ctypes.c_int), ("slot", ctypes.c_int),
+                ("stream", ctypes.c_int), ("seed", ctypes.c_uint64)]
+
+
+SAMPLE_ROW_DEFAULTS = dict(temperature=1.0, top_p=1.0, min_p=0.0, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, top_k=-1,
+                           slot=-1, stream=0, seed=0)
+
+
+def pack_sample_rows(rows):
+    """A list of dicts (keys of SAMPLE_ROW_DEFAULTS; missing keys take the default) -> CPU uint8 tensor [len(rows), sizeof(TdSampleRow)], the packed
+    params operand of sample_rows / torch.ops.thinkdiff_hip.sample_rows."""
+    arr = (TdSampleRow * len(rows))()
+    for a, r in zip(arr, rows):
+        unknown = set(r) - set(SAMPLE_ROW_DEFAULTS)
+        if unknown:
+            raise ThinkDiffHipError(f"pack_sample_rows: unknown field(s) {sorted(unknown)}")
+        for k, d in SAMPLE_ROW_DEFAULTS.items():
+            v = r.get(k, d)
+            setattr(a, k, (int(v) & 0xFFFFFFFFFFFFFFFF) if k == "seed" else (float(v) if isinstance(d, float) else int(v)))
+    return torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).view(len(rows), ctypes.sizeof(TdSampleRow))
+
+
+class Sampler:
+    """td_sampler: the token history of n_slots sequences (prompt bitmap + uint16 generated-token counts per vocabulary entry, n_slots x vocab x
+    2.25 bytes on the device) that the penalties of sample_rows read."""
+
+    def __init__(self, n_slots, vocab, device=None):
+        self.n_slots, self.vocab = int(n_slots), int(vocab)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        h = ctypes.c_void_p()
+        self._destroy = lib().td_sampler_destroy      # (held here: __del__ may run while the interpreter tears the module down)
+        with torch.cuda.device(self.device):
+            check(lib().td_sampler_create(self.n_slots, self.vocab, ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        return int(self._h.value or 0)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._destroy(h)
+
+    __del__ = close
+
+    def reset_slot(self, slot, prompt_ids=None):
+        """Clear the slot's history and mark `prompt_ids` (a sequence or an int32 device tensor; ids outside the vocabulary are ignored)."""
+        ids = None
+        if prompt_ids is not None and len(prompt_ids):
+            ids = prompt_ids if torch.is_tensor(prompt_ids) else torch.tensor(list(prompt_ids), dtype=torch.int32)
+            ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        check(lib().td_sampler_reset_slot(self._h, int(slot), ptr(ids), 0 if ids is None else ids.numel(), stream_ptr()))
+
+    def read_counts(self, slot):
+        out = torch.empty(self.vocab, dtype=torch.int32, device=self.device)
+        check(lib().td_sampler_read_counts(self._h, int(slot), ptr(out), stream_ptr()))
+        return out
+
+    def read_prompt_mask(self, slot):
+        out = torch.empty(self.vocab, dtype=torch.uint8, device=self.device)
+        check(lib().td_sampler_read_prompt_mask(self._h, int(slot), ptr(out), stream_ptr()))
+        return out
+
+    def set_counts(self, slot, counts):
+        c = counts.to(device=self.device, dtype=torch.int32).contiguous()
+        assert c.numel() == self.vocab
+        check(lib().td_sampler_set_counts(self._h, int(slot), ptr(c), stream_ptr()))
+
+
+def sampler_create(n_slots, vocab, device=None):
+    return Sampler(n_slots, vocab, device)
+
+
+def sample_rows(logits, params, offsets, sampler=None, update_state=False, out=None):
+    """td_sample_rows_bf16: logits bf16 [rows, vocab] -> int32 [rows] ids, each row under its own settings.  params: the packed uint8
+    [rows, sizeof(TdSampleRow)] tensor (pack_sample_rows) or a list of dicts; offsets: int64 [rows] tensor, a list, or one int for every row.
+    Host-side operands are uploaded here; device tensors are used as they are (no host synchronisation)."""
+    x = logits if logits.dim() == 2 else logits[None]
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1
+    rows = x.shape[0]
+    if not torch.is_tensor(params):
+        params = pack_sample_rows(params)
+    params = params.to(x.device).contiguous()
+    if params.dtype != torch.uint8 or params.numel() != rows * ctypes.sizeof(TdSampleRow):
+        raise ThinkDiffHipError(f"sample_rows: params must hold {rows} packed TdSampleRow structs ({rows * ctypes.sizeof(TdSampleRow)} bytes), got {params.numel()}")
+    if not torch.is_tensor(offsets):
+        offsets = torch.tensor([int(offsets)] * rows if isinstance(offsets, int) else [int(o) for o in offsets], dtype=torch.int64)
+    offsets = offsets.to(device=x.device, dtype=torch.int64).contiguous()
+    if offsets.numel() != rows:
+        raise ThinkDiffHipError(f"sample_rows: {offsets.numel()} offsets for {rows} rows")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int32, device=x.device)
+    h = None if sampler is None else (sampler._h if isinstance(sampler, Sampler) else ctypes.c_void_p(int(sampler)))
+    check(lib().td_sample_rows_bf16(h, ptr(x), x.stride(0), rows, x.shape[1], ptr(params), ptr(offsets), int(bool(update_state)), ptr(out), stream_ptr()))
     return out
 
 

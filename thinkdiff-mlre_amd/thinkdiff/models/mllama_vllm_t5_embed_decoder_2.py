@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import HipVisionProjector
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, sampler_fields_from_vllm_config
 
 SYSTEM_PROMPT = "You are a helpful assistant."   # reference :1048
 NUM_SYSTEM_TOKENS = 14                            # reference :1107-1109 ("input_no_system" drops the first 14)
@@ -49,7 +49,8 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         self.mllama.weight_quantization = quantization
         self.mllama_sampling_params = SamplingParams(
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),
-            min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True))
+            min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True),
+            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed: the per-request sampler (td_sample_rows_bf16)
         self.mm_projector = HipVisionProjector(self.config.mm_hidden_size, hidden_size, mm_projector_type, device=device, fp32_norm=True)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, processor
         self.visual, self.image_token_id = visual, image_token_id

@@ -9,6 +9,7 @@ Image inputs: `vision_towers.HipQwen2VisionTransformer` produces the merged visi
 """
 import ctypes
 import dataclasses
+import numbers
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -35,13 +36,117 @@ class Qwen2VLTextConfig:
 
 @dataclasses.dataclass
 class SamplingParams:
-    """The fields of vllm.SamplingParams the reference sets (mllama_vllm_t5_embed_decoder_2.py:817-823)."""
+    """The fields of vllm.SamplingParams the reference sets (mllama_vllm_t5_embed_decoder_2.py:817-823), and the ones a user sets next: top_k, min_p,
+    the three penalties and a per-request seed, under vLLM's names, defaults and ranges.  With every one of those at its default the engine samples
+    with td_sample_top_p_bf16 as before; any other value routes the call through the per-request sampler (td_sample_rows_bf16)."""
     temperature: float = 0.6
     top_p: float = 0.9
     max_tokens: int = 128
     min_tokens: int = 128
     ignore_eos: bool = True
     stop_token_ids: Optional[List[int]] = None
+    top_k: int = -1
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    seed: Optional[int] = None
+
+    def validate(self) -> "SamplingParams":
+        """vLLM's ranges; a ValueError names the field and the value."""
+        def bad(field, why):
+            raise ValueError(f"SamplingParams.{field}={getattr(self, field)!r}: {why}")
+        if not (isinstance(self.top_k, numbers.Integral) and not isinstance(self.top_k, bool) and self.top_k >= -1):
+            bad("top_k", "must be -1 or 0 (off) or an integer >= 1")
+        for f in ("min_p", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "temperature"):
+            v = getattr(self, f)
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or v in (float("inf"), float("-inf")):
+                bad(f, "must be a finite number")
+        if not 0.0 <= self.min_p <= 1.0:
+            bad("min_p", "must be in [0, 1]")
+        if not 0.0 < self.top_p <= 1.0:
+            bad("top_p", "must be in (0, 1]")
+        if not self.repetition_penalty > 0.0:
+            bad("repetition_penalty", "must be > 0")
+        for f in ("presence_penalty", "frequency_penalty"):
+            if not -2.0 <= getattr(self, f) <= 2.0:
+                bad(f, "must be in [-2, 2]")
+        if self.temperature < 0.0:
+            bad("temperature", "must be >= 0")
+        if self.seed is not None and (isinstance(self.seed, bool) or not isinstance(self.seed, numbers.Integral)):
+            bad("seed", "must be an integer or None")
+        if not (isinstance(self.max_tokens, numbers.Integral) and self.max_tokens >= 0):
+            bad("max_tokens", "must be an integer >= 0")
+        if not (isinstance(self.min_tokens, numbers.Integral) and self.min_tokens >= 0):
+            bad("min_tokens", "must be an integer >= 0")
+        return self
+
+    @property
+    def has_penalty(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def per_request(self) -> bool:
+        """True when a field td_sample_top_p_bf16 does not serve is set."""
+        return self.top_k > 0 or self.min_p > 0.0 or self.has_penalty or self.seed is not None
+
+
+SAMPLER_CONFIG_KEYS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "seed")
+
+
+def sampler_fields_from_vllm_config(vc) -> dict:
+    """The per-request sampler fields a vllm_config sets, under SamplingParams' names; absent keys (and None) keep the defaults."""
+    return {k: vc[k] for k in SAMPLER_CONFIG_KEYS if vc.get(k) is not None}
+
+
+def _sampling_list(sampling, n, what):
+    """`sampling` of a generate call -> (one validated SamplingParams per request, rows): rows False = the single-params call whose new fields are
+    all at their defaults (td_sample_top_p_bf16, as before); n None: the request count is not known yet (chunks pulled lazily)."""
+    if isinstance(sampling, SamplingParams):
+        sampling.validate()
+        return None, sampling.per_request
+    sps = list(sampling)
+    if n is not None and len(sps) != n:
+        raise ValueError(f"{what}: {len(sps)} SamplingParams for {n} request(s): pass one SamplingParams, or exactly one per request")
+    for sp in sps:
+        if not isinstance(sp, SamplingParams):
+            raise ValueError(f"{what}: sampling must be a SamplingParams or a sequence of them, got {type(sp).__name__}")
+        sp.validate()
+    return sps, True
+
+
+class _RowSampling:
+    """The per-request sampler path of one generate call (td_sample_rows_bf16): a device table of TdSampleRow structs in live-row order, rewritten only
+    when the live set changes, and the offsets uploaded per step.  A request with its own seed draws from (seed, its generated-token count, 0), so
+    its tokens do not depend on which rows share the step; the others draw from (the call's key, the step, live row) as the single-params path does.
+    History (the engine's td_sampler, created on first use) is kept only for requests with a penalty; every other row names slot -1."""
+
+    def __init__(self, engine, key):
+        self.engine, self.key = engine, int(key)
+        self.table, self.seeded, self.state = None, [], None
+
+    def admit(self, slot, sp, prompt_ids):
+        if sp.has_penalty:
+            self.engine._sampler_state().reset_slot(int(slot), [int(t) for t in prompt_ids])
+
+    def set_live(self, rows):
+        """rows: (SamplingParams, cache slot) per live row."""
+        recs, self.seeded, any_hist = [], [], False
+        for r, (sp, slot) in enumerate(rows):
+            hist = sp.has_penalty
+            any_hist |= hist
+            self.seeded.append(sp.seed is not None)
+            recs.append(dict(temperature=sp.temperature, top_p=sp.top_p, min_p=sp.min_p, repetition_penalty=sp.repetition_penalty,
+                             presence_penalty=sp.presence_penalty, frequency_penalty=sp.frequency_penalty, top_k=sp.top_k,
+                             slot=int(slot) if hist else -1, stream=0 if sp.seed is not None else r,
+                             seed=sp.seed if sp.seed is not None else self.key))
+        self.table = _hip.pack_sample_rows(recs).to(self.engine.device)
+        self.state = self.engine._sampler_state().handle if any_hist else None
+
+    def sample(self, logits, step, ngen):
+        """logits [n, vocab] of the live rows; step: the call's decode step; ngen[i]: tokens live row i has generated."""
+        offs = torch.tensor([int(ngen[i]) if s else int(step) for i, s in enumerate(self.seeded)], dtype=torch.int64).to(self.engine.device)
+        return _OPS.sample_rows(logits, self.table, offs, self.state, self.state is not None)
 
 
 class Qwen2VLTextEngine:
@@ -91,6 +196,19 @@ class Qwen2VLTextEngine:
         h, self._h = getattr(self, "_h", None), None
         if h:
             self._L.td_qwen2_destroy(h)
+        st, self._sampler = getattr(self, "_sampler", None), None
+        if st is not None:
+            st.close()
+
+    def _sampler_state(self):
+        """The token history behind the penalties (td_sampler, one slot per cache slot), created the first time a request with a penalty arrives:
+        n_slots x vocab x 2.25 bytes of device memory (87.6 MB at 256 x 152 064)."""
+        st = getattr(self, "_sampler", None)
+        if st is None or st.n_slots != max(1, getattr(self, "n_slots", 1)):
+            if st is not None:
+                st.close()
+            st = self._sampler = _hip.Sampler(max(1, getattr(self, "n_slots", 1)), self.config.vocab_size, self.device)
+        return st
 
     # ---- parameters (Hugging Face names) -----------------------------------------------------------------
     def param_table(self) -> Dict[str, int]:
@@ -308,6 +426,9 @@ class Qwen2VLTextEngine:
 
         Sampling is temperature / top-p on the device.  `forced_output_ids` teacher-forces the continuation
         (the reference samples at T=0.6, so parity of the hidden states is checked on forced ids)."""
+        sps, by_rows = _sampling_list(sampling, 1, "generate")
+        if sps is not None:
+            sampling = sps[0]
         n_p = len(prompt_token_ids)
         pos = self.text_position_ids(n_p) if position_ids is None else position_ids
         next_pos = int(pos.max()) + 1      # M-RoPE: generation continues one past the largest prompt position
@@ -317,6 +438,11 @@ class Qwen2VLTextEngine:
         stops = set(sampling.stop_token_ids or [])
         can_stop = forced_output_ids is None and (bool(stops) or ((not sampling.ignore_eos) and eos_token_id is not None))
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
+        rows = None
+        if by_rows and forced_output_ids is None:      # (teacher-forced decoding does not sample and keeps no history)
+            rows = _RowSampling(self, key)
+            rows.admit(0, sampling, prompt_token_ids)
+            rows.set_live([(sampling, 0)])
         if forced_output_ids is not None:
             forced_dev = torch.tensor(list(forced_output_ids), dtype=torch.int32).to(self.device)
         for step in range(sampling.max_tokens):
@@ -324,6 +450,8 @@ class Qwen2VLTextEngine:
                 if step >= len(forced_output_ids):
                     break
                 nxt = forced_dev[step:step + 1]
+            elif rows is not None:
+                nxt = rows.sample(logits if logits.dim() == 2 else logits[None], step, [step])
             else:
                 nxt = _OPS.sample_top_p(logits, float(sampling.temperature), float(sampling.top_p), int(key), int(step))     # device int32 [1], no host round trip
             out_tok.append(nxt)
@@ -358,6 +486,9 @@ class Qwen2VLTextEngine:
         reference's precompute job).  requests: dicts with "prompt_token_ids" and optional "position_ids" / "inputs_embeds".
         Returns one generate()-style dict per request, in order."""
         B = len(requests)
+        sps, by_rows = _sampling_list(sampling, B, "generate_batch")
+        if sps is None:
+            sps = [sampling] * B
         if B > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
             raise _hip.ThinkDiffHipError(f"generate_batch: {B} requests exceed min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
         res = [{"prompt_hidden_states": None, "hidden_states": [], "token_ids": []} for _ in range(B)]
@@ -429,14 +560,25 @@ class Qwen2VLTextEngine:
         owner = list(range(B))                      # live row -> request index
         slots = list(range(B))                      # live row -> cache slot (a finished sequence just leaves the lists: no cache rows move)
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
-        stops = set(sampling.stop_token_ids or [])
+        stops = [set(sp.stop_token_ids or []) for sp in sps]      # per request, like max_tokens / min_tokens / ignore_eos below
+        rows_s = None
+        if by_rows and forced_output_ids is None:
+            rows_s = _RowSampling(self, key)
+            for b in range(B):
+                rows_s.admit(b, sps[b], requests[b]["prompt_token_ids"])
+            live_changed = True
         step = 0
         # per step: the hidden rows stay ONE device tensor and the slot -> request map is remembered; the rows are handed to their requests by a
         # single gather after the loop (256 sequences x 256 steps of per-row tensor views and list appends were ~0.5 ms of host time per step,
         # during which the GPU idled: 15 % of a 3.3 ms step)
         step_hid, step_owner, step_toks = [], [], []
-        eos_on = (not sampling.ignore_eos) and eos_token_id is not None
-        while owner and step < sampling.max_tokens:
+        eos_on = [(not sp.ignore_eos) and eos_token_id is not None for sp in sps]
+        owner = [b for b in owner if sps[b].max_tokens > 0]
+        if len(owner) < B:
+            slots = list(owner)
+            cache_len, next_pos = [cache_len[b] for b in owner], [next_pos[b] for b in owner]
+            logits = logits[owner]
+        while owner:
             n = len(owner)
             if forced_output_ids is not None:
                 live = [i for i in range(n) if step < len(forced_output_ids[owner[i]])]
@@ -448,6 +590,11 @@ class Qwen2VLTextEngine:
                         break
                     n = len(owner)
                 toks = [int(forced_output_ids[owner[i]][step]) for i in range(n)]
+            elif rows_s is not None:
+                if live_changed:
+                    rows_s.set_live([(sps[o], sl) for o, sl in zip(owner, slots)])
+                    live_changed = False
+                toks = rows_s.sample(logits[:n], step, [step] * n).tolist()      # (every sequence of a batch starts at step 0)
             else:
                 # one launch for all live rows (td_sample_top_p_bf16); the ids come to the host once per step for the bookkeeping below
                 toks = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(step)).tolist()
@@ -456,18 +603,20 @@ class Qwen2VLTextEngine:
             step_hid.append(hid)
             step_owner.append(list(owner))
             step_toks.append(toks)
-            may_stop = forced_output_ids is None and step + 1 >= sampling.min_tokens
             keep = []
             for i in range(n):
                 cache_len[i] += 1
                 next_pos[i] += 1
-                stop = may_stop and ((eos_on and toks[i] == eos_token_id) or toks[i] in stops)
+                o = owner[i]
+                may_stop = forced_output_ids is None and step + 1 >= sps[o].min_tokens
+                stop = step + 1 >= sps[o].max_tokens or (may_stop and ((eos_on[o] and toks[i] == eos_token_id) or toks[i] in stops[o]))
                 if not stop and cache_len[i] < self.slot_len:
                     keep.append(i)
             if len(keep) < n:
                 owner, slots = [owner[i] for i in keep], [slots[i] for i in keep]
                 cache_len, next_pos = [cache_len[i] for i in keep], [next_pos[i] for i in keep]
                 logits = logits[keep]
+                live_changed = True
             step += 1
         rows = [[] for _ in range(B)]
         base = 0
@@ -507,6 +656,10 @@ class Qwen2VLTextEngine:
         admit_min = max(1, max_live // 8) if admit_min is None else max(1, int(admit_min))
         if isinstance(request_chunks, (list, tuple)) and (not request_chunks or isinstance(request_chunks[0], dict)):
             request_chunks = [list(request_chunks)]
+            n_known = len(request_chunks[0])
+        else:
+            n_known = None      # chunks pulled lazily: a per-request list is checked against each chunk as it arrives
+        sps_all, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
         chunk_it = iter(request_chunks)
         D, V = self.config.hidden_size, self.config.vocab_size
         requests, res, waiting = [], [], deque()
@@ -523,6 +676,8 @@ class Qwen2VLTextEngine:
                 n = len(r["prompt_token_ids"])
                 if n < 1 or n > min(self.slot_len, self.prefill_rows):
                     raise _hip.ThinkDiffHipError(f"generate_continuous: a prompt of {n} tokens does not fit a slot ({self.slot_len}) / a prefill pass ({self.prefill_rows})")
+                if sps_all is not None and len(requests) >= len(sps_all):
+                    raise ValueError(f"generate_continuous: {len(sps_all)} SamplingParams for more than {len(sps_all)} requests: pass one SamplingParams, or exactly one per request")
                 waiting.append(len(requests))
                 requests.append(r)
                 res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
@@ -535,16 +690,27 @@ class Qwen2VLTextEngine:
         free_slots = list(range(max_live - 1, -1, -1))      # (a stack: the lowest free slot is taken first)
         logits = torch.empty(max_live, V, dtype=torch.bfloat16, device=self.device)      # row i = the next-token logits of live row i
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
-        stops = np.array(sorted(set(sampling.stop_token_ids or [])), dtype=np.int64)
-        eos_on = (not sampling.ignore_eos) and eos_token_id is not None
-        can_stop = forced_output_ids is None and (stops.size > 0 or eos_on)
+
+        def sp_of(i):       # the SamplingParams of request i
+            return sampling if sps_all is None else sps_all[i]
+
+        if sps_all is None:
+            stops = np.array(sorted(set(sampling.stop_token_ids or [])), dtype=np.int64)
+            eos_on = (not sampling.ignore_eos) and eos_token_id is not None
+            can_stop = forced_output_ids is None and (stops.size > 0 or eos_on)
+        else:               # the stop rules per request (mint: the live rows' min_tokens)
+            stop_sets = [set(sp.stop_token_ids or []) for sp in sps_all]
+            can_stop = forced_output_ids is None
+            mint = np.zeros(max_live, dtype=np.int32)
+        rows_s = _RowSampling(self, key) if by_rows and forced_output_ids is None else None
+        live_changed = True
         step_hid, step_owner, step_toks = [], [], []
         gstep = 0
-        slot_len, min_tok = self.slot_len, sampling.min_tokens
+        slot_len, min_tok = self.slot_len, (sampling.min_tokens if sps_all is None else None)
         vp = ctypes.c_void_p
 
         def budget(i):      # tokens request i may still produce
-            return len(forced_output_ids[i]) if forced_output_ids is not None else sampling.max_tokens
+            return len(forced_output_ids[i]) if forced_output_ids is not None else sp_of(i).max_tokens
 
         while True:
             free = max_live - n
@@ -596,6 +762,12 @@ class Qwen2VLTextEngine:
                     clen[n:n + k] = lens
                     ngen[n:n + k] = 0
                     lim[n:n + k] = [budget(i) for i in new]
+                    if sps_all is not None:
+                        mint[n:n + k] = [sps_all[i].min_tokens for i in new]
+                    if rows_s is not None:      # a request admitted into a slot starts that slot's history over
+                        for i, sl in zip(new, new_slots):
+                            rows_s.admit(sl, sp_of(i), requests[i]["prompt_token_ids"])
+                    live_changed = True
                     n += k
                     continue      # (more may fit in another pass before the next decode step)
             if n == 0:
@@ -607,7 +779,13 @@ class Qwen2VLTextEngine:
                 toks = np.array([forced_output_ids[own[i]][ngen[i]] for i in range(n)], dtype=np.int32)
                 tok_dev = torch.from_numpy(toks).to(self.device)
             else:
-                tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(gstep))
+                if rows_s is not None:
+                    if live_changed:
+                        rows_s.set_live([(sp_of(int(own[i])), int(slt[i])) for i in range(n)])
+                        live_changed = False
+                    tok_dev = rows_s.sample(logits[:n], gstep, ngen[:n])
+                else:
+                    tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(gstep))
                 toks = tok_dev.cpu().numpy()      # (the host sees the ids once per step, for the stop rules below)
             pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(npos[:n], (3, n)))).to(self.device)
             hid = torch.empty(n, D, dtype=torch.bfloat16, device=self.device)
@@ -619,17 +797,22 @@ class Qwen2VLTextEngine:
             npos[:n] += 1
             ngen[:n] += 1
             done = (ngen[:n] >= lim[:n]) | (clen[:n] >= slot_len)
-            if can_stop:
+            if can_stop and sps_all is None:
                 hit = np.isin(toks, stops) if stops.size else np.zeros(n, dtype=bool)
                 if eos_on:
                     hit |= toks == eos_token_id
                 done |= hit & (ngen[:n] >= min_tok)
+            elif can_stop:
+                hit = np.array([int(toks[i]) in stop_sets[own[i]] or (eos_token_id is not None and not sps_all[own[i]].ignore_eos and int(toks[i]) == eos_token_id)
+                                for i in range(n)], dtype=bool)
+                done |= hit & (ngen[:n] >= mint[:n])
             if done.any():
                 keep = np.nonzero(~done)[0]
                 free_slots.extend(sorted((int(x) for x in slt[:n][done]), reverse=True))
                 k = keep.size
-                for arr in (own, slt, clen, npos, ngen, lim):
+                for arr in (own, slt, clen, npos, ngen, lim) + (() if sps_all is None else (mint,)):
                     arr[:k] = arr[:n][keep]
+                live_changed = True
                 if k:
                     logits[:k] = logits[:n].index_select(0, torch.from_numpy(keep).to(self.device))
                 n = k

@@ -18,6 +18,7 @@ norm_rows                  LayerNorm / RMSNorm rows (+ adaLN modulation)
 qk_norm_rope_              per-head QK-RMSNorm + rotary embedding, in place
 euler_step_                FlowMatchEulerDiscreteScheduler.step, in place
 flux_pack_latents / flux_unpack_latents, cls_avgpool2, sample_top_p
+sample_rows                per-request sampler: penalties, top-k, top-p, min-p per row (`state` = a thinkdiff._hip.Sampler handle or None)
 flux_forward_ / flux_denoise_ / flux_denoise_multi_   FluxTransformer2DModel.forward and the pipeline's denoising loop, on a prepared engine
                            (`engine` = the td_flux* handle thinkdiff.models.flux_transformer holds); tensors are checked against the
                            extents the prepared context expects (td_flux_prepared_shape)
@@ -72,6 +73,7 @@ SCHEMAS = {
     "flux_unpack_latents": "(Tensor packed, int C, int H, int W, float div, float add) -> Tensor",
     "cls_avgpool2": "(Tensor tokens) -> Tensor",
     "sample_top_p": "(Tensor logits, float temperature, float top_p, int seed, int offset) -> Tensor",
+    "sample_rows": "(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state) -> Tensor",
     "flux_forward_": "(int engine, Tensor latents, int step, Tensor(a!) velocity) -> Tensor(a!)",
     "flux_denoise_": "(int engine, Tensor(a!) latents, float[] sigmas) -> Tensor(a!)",
     "flux_denoise_multi_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()",
