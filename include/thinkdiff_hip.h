@@ -1067,6 +1067,63 @@ int td_sampler_set_counts(td_sampler* s, int slot, const int32_t* counts_dev, vo
 int td_sample_rows_bf16(const td_sampler* s, const void* logits, int64_t ld, int rows, int vocab, const TdSampleRow* params_dev,
                         const int64_t* offsets_dev, int update_state, int32_t* out_ids, void* stream);
 
+/* ---- logit edits in the sampler's launch (td_abi_version() >= 15): logit_bias, allowed_token_ids, bad words and the min_tokens stop mask of
+ * vllm.SamplingParams ([ext] vLLM V1 sampler: allowed ids, then bad words, then min-tokens and logit bias, then penalties), as one per-row edit
+ * of the logits in front of the penalties.  For a row with bf16 logits x, an edit slot (banned set B, bias b) and the history above:
+ *   z[t] = -inf                   if t in B              (a banned token stays banned whatever its bias)
+ *   z[t] = float(x[t]) + b[t]     if t has a bias        (fp32, never rounded back to bf16; NaN -> -inf, so a -inf logit with a +inf bias is -inf)
+ *   z[t] = float(x[t])            otherwise              (NaN -> -inf, as above)
+ * then the penalties of td_sample_rows_bf16 on z (the repetition sign test sees the biased value), then temperature, top-k, top-p, min-p and the
+ * draw, unchanged.  A row whose every token is banned is a row of -inf: id 0, never a fault.
+ * State: n_slots edit slots over one vocabulary; per slot a ban bitmap and a bias bitmap (one byte of each per 8 tokens, read beside the logits;
+ * the kernel reads both rather than their OR, so that an edited chunk costs no second, dependent read) and a table of at most TD_MAX_LOGIT_BIAS
+ * (token, fp32 value) pairs sorted by token, which a workgroup stages in LDS and searches for biased tokens only:
+ * n_slots x (2 x vocab / 8 + 8 x TD_MAX_LOGIT_BIAS + 4) bytes of device memory, 11.8 MB at 256 x 152 064, allocated here and zeroed.
+ * Every setter is stream-ordered, makes no allocation and no host synchronisation, and refuses a NULL state or a slot outside [0, n_slots) with
+ * TD_ERR_INVALID before any HIP call. */
+#define TD_MAX_LOGIT_BIAS 1024
+typedef struct td_logit_edits td_logit_edits;
+int td_logit_edits_create(int n_slots, int vocab, td_logit_edits** out);      /* n_slots 1..65535, vocab % 8 == 0 */
+void td_logit_edits_destroy(td_logit_edits* e);
+/* Clear the slot's bans and biases. */
+int td_logit_edits_reset_slot(td_logit_edits* e, int slot, void* stream);
+/* Replace the slot's bias table.  ids / values are HOST arrays of n entries, read before the call returns (the library sorts them and hands them to
+ * the device in the launches' arguments).  Refused before any HIP call: n > TD_MAX_LOGIT_BIAS, an id given twice, an id outside [0, vocab).
+ * A NaN value counts as 0; +-inf is honoured.  n = 0 clears the table. */
+int td_logit_edits_set_bias(td_logit_edits* e, int slot, const int32_t* ids, const float* values, int n, void* stream);
+/* Set (on != 0) or clear the ban on ids_dev[0..n) (DEVICE int32; ids outside the vocabulary are ignored).  Clearing a ban restores the token's
+ * bias if it has one. */
+int td_logit_edits_ban(td_logit_edits* e, int slot, const int32_t* ids_dev, int n, int on, void* stream);
+/* Ban every token except ids_dev[0..n) (DEVICE int32; ids outside the vocabulary are ignored; replaces the slot's bans, keeps its biases). */
+int td_logit_edits_allow_only(td_logit_edits* e, int slot, const int32_t* ids_dev, int n, void* stream);
+/* Tests and debugging: the banned set as uint8 [vocab] (0 / 1) and the biases as fp32 [vocab] (0 where none), device memory; either may be NULL. */
+int td_logit_edits_read(const td_logit_edits* e, int slot, uint8_t* banned_u8_out_dev, float* bias_f32_out_dev, void* stream);
+/* td_sample_rows_bf16 with the edits of slot edit_slots_dev[row] applied to row `row` (device int32 [rows]; -1 or any value outside [0, n_slots):
+ * no edits for that row).  The launch only reads the edit state, so rows may share an edit slot.  e == NULL: the call IS td_sample_rows_bf16
+ * (edit_slots_dev is not read); a row without edits returns td_sample_rows_bf16's id bit for bit.  TD_ERR_INVALID before any HIP call: what
+ * td_sample_rows_bf16 refuses, a NULL edit_slots_dev with e set, vocab != the edit state's. */
+int td_sample_rows_edit_bf16(const td_sampler* s, const td_logit_edits* e, const int32_t* edit_slots_dev, const void* logits, int64_t ld, int rows,
+                             int vocab, const TdSampleRow* params_dev, const int64_t* offsets_dev, int update_state, int32_t* out_ids, void* stream);
+
+/* ---- logprobs of rows of bf16 logits (td_abi_version() >= 15; csrc/logprobs_rows.hip), one workgroup per row, no sort ----
+ * Takes the RAW logits, before edits, penalties and temperature (vLLM V1's default logprobs mode, `raw_logprobs`).  Per row:
+ *   m = max x,  lse = m + ln(sum exp(x - m)),  lp[t] = float(x[t]) - lse
+ * with the sum taken over 2^-40 fixed-point masses in 64-bit integers, so it does not depend on the order of accumulation: one row gives the same
+ * bits at any row index and row count.
+ *   ids_dev[rows]     the sampled or forced token of each row;
+ *   n_top_dev[rows]   < 0: the row is skipped and its outputs are left untouched; 0: the chosen token only; up to top_cap (larger: top_cap);
+ *   lp_sampled[rows]  fp32, the chosen token's logprob;       rank[rows]  int32, the number of t with x[t] >= x[id] (vLLM's batched_count_greater_than);
+ *   top_ids / top_lp  [rows, top_cap] int32 / fp32: the n_top largest logits in descending value, then ascending index (ties go to the lower index),
+ *                     found with the 16-bit radix select of td_sample_top_p_bf16; unused columns hold id -1 and lp -inf.
+ * Degenerate rows never fault and no output is ever NaN -- where torch.log_softmax returns NaN, this does not: a NaN logit counts as -inf; a row
+ * with no finite value and no +inf gives lp -inf for every token and rank = vocab; in a row holding +inf those tokens get lp 0 and every other
+ * token -inf; an id outside [0, vocab) gives lp -inf and rank 0.
+ * vocab % 8 == 0, ld % 8 == 0, ld >= vocab, rows 1..65535, 0 <= top_cap <= TD_MAX_LOGPROBS (top_ids / top_lp may be NULL iff top_cap == 0), logits
+ * 16-byte aligned; TD_ERR_INVALID before any HIP call otherwise. */
+#define TD_MAX_LOGPROBS 20
+int td_logprobs_rows_bf16(const void* logits, int64_t ld, int rows, int vocab, const int32_t* ids_dev, const int32_t* n_top_dev, int top_cap,
+                          float* lp_sampled, int32_t* rank, int32_t* top_ids, float* top_lp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

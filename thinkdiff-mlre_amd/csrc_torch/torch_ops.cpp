@@ -14,6 +14,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <limits>
 #include <tuple>
 
 #include "../../include/thinkdiff_hip.h"
@@ -492,6 +493,56 @@ at::Tensor sample_rows(const at::Tensor& logits, const at::Tensor& params, const
   return out;
 }
 
+// sample_rows with the logit edits of slot edit_slots[row] applied to each row (edits: a td_logit_edits handle as an int, thinkdiff._hip.LogitEdits.handle;
+// edit_slots: int32 [rows] on the logits' device, -1 = none).  edits None: sample_rows.
+at::Tensor sample_rows_edit(const at::Tensor& logits, const at::Tensor& params, const at::Tensor& offsets, c10::optional<int64_t> state, bool update_state,
+                            c10::optional<int64_t> edits, const c10::optional<at::Tensor>& edit_slots) {
+  const td_logit_edits* e = edits.has_value() && *edits != 0 ? reinterpret_cast<const td_logit_edits*>(*edits) : nullptr;
+  if (!e) return sample_rows(logits, params, offsets, state, update_state);
+  check_rows(logits, "logits");
+  at::Tensor x = logits.dim() == 1 ? logits.unsqueeze(0) : logits;
+  TORCH_CHECK(x.dim() == 2, "thinkdiff_hip::sample_rows_edit: logits [rows, vocab]");
+  const int64_t rows = x.size(0);
+  TORCH_CHECK(params.is_cuda() && params.device() == x.device() && params.scalar_type() == at::kByte && params.is_contiguous() &&
+              params.numel() == rows * (int64_t)td_sample_row_size(),
+              "thinkdiff_hip::sample_rows_edit: params must be a contiguous uint8 tensor of ", rows, " x ", td_sample_row_size(), " bytes on the logits' device");
+  TORCH_CHECK(offsets.is_cuda() && offsets.device() == x.device() && offsets.scalar_type() == at::kLong && offsets.is_contiguous() && offsets.numel() == rows,
+              "thinkdiff_hip::sample_rows_edit: offsets must be a contiguous int64 tensor of ", rows, " entries on the logits' device");
+  TORCH_CHECK(edit_slots.has_value() && edit_slots->is_cuda() && edit_slots->device() == x.device() && edit_slots->scalar_type() == at::kInt &&
+              edit_slots->is_contiguous() && edit_slots->numel() == rows,
+              "thinkdiff_hip::sample_rows_edit: edit_slots must be a contiguous int32 tensor of ", rows, " entries on the logits' device");
+  DeviceGuard guard(x.device());
+  at::Tensor out = at::empty({rows}, x.options().dtype(at::kInt));
+  const td_sampler* s = state.has_value() && *state != 0 ? reinterpret_cast<const td_sampler*>(*state) : nullptr;
+  ok(td_sample_rows_edit_bf16(s, e, (const int32_t*)edit_slots->data_ptr(), x.data_ptr(), x.stride(0), (int)rows, (int)x.size(1),
+                              (const TdSampleRow*)params.data_ptr(), (const int64_t*)offsets.data_ptr(), update_state ? 1 : 0, (int32_t*)out.data_ptr(),
+                              stream_of(x)));
+  return out;
+}
+
+// raw-logit logprobs per row: (lp_sampled fp32 [rows], rank int32 [rows], top_ids int32 [rows, top_cap], top_lp fp32 [rows, top_cap]); ids / n_top: int32
+// [rows] on the logits' device.  Rows with n_top < 0 are skipped by the kernel: their outputs are pre-filled here (lp -inf, rank 0, ids -1).
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> logprobs_rows(const at::Tensor& logits, const at::Tensor& ids, const at::Tensor& n_top, int64_t top_cap) {
+  check_rows(logits, "logits");
+  at::Tensor x = logits.dim() == 1 ? logits.unsqueeze(0) : logits;
+  TORCH_CHECK(x.dim() == 2, "thinkdiff_hip::logprobs_rows: logits [rows, vocab]");
+  const int64_t rows = x.size(0);
+  TORCH_CHECK(top_cap >= 0 && top_cap <= TD_MAX_LOGPROBS, "thinkdiff_hip::logprobs_rows: top_cap must be in 0..", TD_MAX_LOGPROBS, ", got ", top_cap);
+  for (const at::Tensor* t : {&ids, &n_top})
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device() && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == rows,
+                "thinkdiff_hip::logprobs_rows: ids and n_top must be contiguous int32 tensors of ", rows, " entries on the logits' device");
+  DeviceGuard guard(x.device());
+  const auto inf = std::numeric_limits<float>::infinity();
+  at::Tensor lp = at::full({rows}, -inf, x.options().dtype(at::kFloat));
+  at::Tensor rank = at::zeros({rows}, x.options().dtype(at::kInt));
+  at::Tensor top_ids = at::full({rows, top_cap}, -1, x.options().dtype(at::kInt));
+  at::Tensor top_lp = at::full({rows, top_cap}, -inf, x.options().dtype(at::kFloat));
+  ok(td_logprobs_rows_bf16(x.data_ptr(), x.stride(0), (int)rows, (int)x.size(1), (const int32_t*)ids.data_ptr(), (const int32_t*)n_top.data_ptr(), (int)top_cap,
+                           (float*)lp.data_ptr(), (int32_t*)rank.data_ptr(), top_cap ? (int32_t*)top_ids.data_ptr() : nullptr,
+                           top_cap ? (float*)top_lp.data_ptr() : nullptr, stream_of(x)));
+  return std::make_tuple(lp, rank, top_ids, top_lp);
+}
+
 // ---- the engines: the denoise loop itself goes through the dispatcher ----------------------------------------------------------------
 // An engine is a stateful C++ object behind the C ABI (weights, workspaces, prepared conditioning); the ops take its handle as an int (the
 // td_flux* / td_vae* value, as thinkdiff.models.* hold it) and check every tensor against what the prepared context expects.
@@ -841,6 +892,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("cls_avgpool2(Tensor tokens) -> Tensor");
   m.def("sample_top_p(Tensor logits, float temperature, float top_p, int seed, int offset) -> Tensor");
   m.def("sample_rows(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state) -> Tensor");
+  m.def("sample_rows_edit(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state, int? edits, Tensor? edit_slots) -> Tensor");
+  m.def("logprobs_rows(Tensor logits, Tensor ids, Tensor n_top, int top_cap) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("flux_forward_(int engine, Tensor latents, int step, Tensor(a!) velocity) -> Tensor(a!)");
   m.def("flux_denoise_(int engine, Tensor(a!) latents, float[] sigmas) -> Tensor(a!)");
   m.def("flux_denoise_multi_(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()");
@@ -894,6 +947,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("cls_avgpool2", &cls_avgpool2);
   m.impl("sample_top_p", &sample_top_p);
   m.impl("sample_rows", &sample_rows);
+  m.impl("sample_rows_edit", &sample_rows_edit);
+  m.impl("logprobs_rows", &logprobs_rows);
   m.impl("flux_forward_", &flux_forward_);
   m.impl("flux_denoise_", &flux_denoise_);
   m.impl("flux_denoise_multi_", &flux_denoise_multi_);

@@ -228,6 +228,14 @@ def _declare(L):
         "td_sampler_read_prompt_mask": [vp, i32, vp, vp],
         "td_sampler_set_counts": [vp, i32, vp, vp],
         "td_sample_rows_bf16": [vp, vp, i64, i32, i32, vp, vp, i32, vp, vp],
+        "td_logit_edits_create": [i32, i32, vp],
+        "td_logit_edits_reset_slot": [vp, i32, vp],
+        "td_logit_edits_set_bias": [vp, i32, vp, vp, i32, vp],
+        "td_logit_edits_ban": [vp, i32, vp, i32, i32, vp],
+        "td_logit_edits_allow_only": [vp, i32, vp, i32, vp],
+        "td_logit_edits_read": [vp, i32, vp, vp, vp],
+        "td_sample_rows_edit_bf16": [vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, vp, vp],
+        "td_logprobs_rows_bf16": [vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("TD_HIP_LIB") and not hasattr(L, name):
@@ -248,6 +256,9 @@ def _declare(L):
         L.td_sampler_destroy.restype = None
         L.td_sample_row_size.argtypes = []
         L.td_sample_row_size.restype = ctypes.c_size_t
+    if hasattr(L, "td_logit_edits_destroy"):
+        L.td_logit_edits_destroy.argtypes = [vp]
+        L.td_logit_edits_destroy.restype = None
     L.td_qwen2_weight_stream_launches.argtypes = [vp]
     L.td_qwen2_weight_stream_launches.restype = ctypes.c_int64
     L.td_flux_param_elems.argtypes = [vp]
@@ -1170,6 +1181,129 @@ def sample_rows(logits, params, offsets, sampler=None, update_state=False, out=N
     h = None if sampler is None else (sampler._h if isinstance(sampler, Sampler) else ctypes.c_void_p(int(sampler)))
     check(lib().td_sample_rows_bf16(h, ptr(x), x.stride(0), rows, x.shape[1], ptr(params), ptr(offsets), int(bool(update_state)), ptr(out), stream_ptr()))
     return out
+
+
+MAX_LOGIT_BIAS = 1024      # TD_MAX_LOGIT_BIAS
+MAX_LOGPROBS = 20          # TD_MAX_LOGPROBS
+
+
+class LogitEdits:
+    """td_logit_edits: n_slots edit slots over one vocabulary (per slot a ban bitmap, a bias bitmap and a sorted table of at most 1024
+    (token, fp32 bias) pairs; n_slots x (2 x vocab / 8 + 8196) bytes on the device, 11.8 MB at 256 x 152 064) that sample_rows_edit applies to the
+    logits in front of the penalties.  Every setter is stream-ordered and does not synchronise."""
+
+    def __init__(self, n_slots, vocab, device=None):
+        self.n_slots, self.vocab = int(n_slots), int(vocab)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        h = ctypes.c_void_p()
+        self._destroy = lib().td_logit_edits_destroy      # (held here: __del__ may run while the interpreter tears the module down)
+        with torch.cuda.device(self.device):
+            check(lib().td_logit_edits_create(self.n_slots, self.vocab, ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        return int(self._h.value or 0)
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._destroy(h)
+
+    __del__ = close
+
+    def _ids(self, ids):
+        t = ids if torch.is_tensor(ids) else torch.tensor([int(i) for i in ids], dtype=torch.int32)
+        return t.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def reset_slot(self, slot):
+        """Clear the slot's bans and biases."""
+        check(lib().td_logit_edits_reset_slot(self._h, int(slot), stream_ptr()))
+
+    def set_bias(self, slot, bias):
+        """Replace the slot's bias table: `bias` is a dict token -> value or a sequence of (token, value) pairs, at most 1024, host side (the library
+        sorts them; a duplicate id or an id outside the vocabulary is refused; NaN counts as 0, +-inf is honoured)."""
+        items = list(bias.items()) if hasattr(bias, "items") else [tuple(p) for p in bias]
+        n = len(items)
+        ids = (ctypes.c_int32 * max(n, 1))(*[int(t) for t, _ in items])
+        vals = (ctypes.c_float * max(n, 1))(*[float(v) for _, v in items])
+        check(lib().td_logit_edits_set_bias(self._h, int(slot), ctypes.cast(ids, ctypes.c_void_p), ctypes.cast(vals, ctypes.c_void_p), n, stream_ptr()))
+
+    def ban(self, slot, ids, on=True):
+        """Set (or, on=False, clear) the ban on `ids` (a sequence or an int32 device tensor; ids outside the vocabulary are ignored)."""
+        t = self._ids(ids)
+        check(lib().td_logit_edits_ban(self._h, int(slot), ptr(t) if t.numel() else None, t.numel(), int(bool(on)), stream_ptr()))
+
+    def allow_only(self, slot, ids):
+        """Ban every token except `ids` (replaces the slot's bans, keeps its biases)."""
+        t = self._ids(ids)
+        check(lib().td_logit_edits_allow_only(self._h, int(slot), ptr(t) if t.numel() else None, t.numel(), stream_ptr()))
+
+    def read(self, slot):
+        """-> (banned uint8 [vocab], bias fp32 [vocab]) on the device (tests and debugging)."""
+        banned = torch.empty(self.vocab, dtype=torch.uint8, device=self.device)
+        bias = torch.empty(self.vocab, dtype=torch.float32, device=self.device)
+        check(lib().td_logit_edits_read(self._h, int(slot), ptr(banned), ptr(bias), stream_ptr()))
+        return banned, bias
+
+
+def logit_edits_create(n_slots, vocab, device=None):
+    return LogitEdits(n_slots, vocab, device)
+
+
+def sample_rows_edit(logits, params, offsets, sampler=None, update_state=False, edits=None, edit_slots=None, out=None):
+    """td_sample_rows_edit_bf16: sample_rows with the edits of slot edit_slots[row] (an int32 [rows] tensor, a list, or one int for every row; -1 = no
+    edits) applied to each row's logits in front of the penalties.  edits None: sample_rows."""
+    if edits is None:
+        return sample_rows(logits, params, offsets, sampler, update_state, out)
+    x = logits if logits.dim() == 2 else logits[None]
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1
+    rows = x.shape[0]
+    if not torch.is_tensor(params):
+        params = pack_sample_rows(params)
+    params = params.to(x.device).contiguous()
+    if params.dtype != torch.uint8 or params.numel() != rows * ctypes.sizeof(TdSampleRow):
+        raise ThinkDiffHipError(f"sample_rows_edit: params must hold {rows} packed TdSampleRow structs ({rows * ctypes.sizeof(TdSampleRow)} bytes), got {params.numel()}")
+    if not torch.is_tensor(offsets):
+        offsets = torch.tensor([int(offsets)] * rows if isinstance(offsets, int) else [int(o) for o in offsets], dtype=torch.int64)
+    offsets = offsets.to(device=x.device, dtype=torch.int64).contiguous()
+    if edit_slots is None:
+        edit_slots = -1
+    if not torch.is_tensor(edit_slots):
+        edit_slots = torch.tensor([int(edit_slots)] * rows if isinstance(edit_slots, int) else [int(s) for s in edit_slots], dtype=torch.int32)
+    edit_slots = edit_slots.to(device=x.device, dtype=torch.int32).contiguous()
+    if offsets.numel() != rows or edit_slots.numel() != rows:
+        raise ThinkDiffHipError(f"sample_rows_edit: {offsets.numel()} offsets and {edit_slots.numel()} edit slots for {rows} rows")
+    if out is None:
+        out = torch.empty(rows, dtype=torch.int32, device=x.device)
+    h = None if sampler is None else (sampler._h if isinstance(sampler, Sampler) else ctypes.c_void_p(int(sampler)))
+    eh = edits._h if isinstance(edits, LogitEdits) else ctypes.c_void_p(int(edits))
+    check(lib().td_sample_rows_edit_bf16(h, eh, ptr(edit_slots), ptr(x), x.stride(0), rows, x.shape[1], ptr(params), ptr(offsets), int(bool(update_state)),
+                                         ptr(out), stream_ptr()))
+    return out
+
+
+def logprobs_rows(logits, ids, n_top, top_cap=MAX_LOGPROBS, out=None):
+    """td_logprobs_rows_bf16 on RAW logits bf16 [rows, vocab]: ids int32 [rows] (the chosen tokens), n_top int32 [rows] (a tensor, a list or one int;
+    -1 skips a row) -> (lp_sampled fp32 [rows], rank int32 [rows], top_ids int32 [rows, top_cap], top_lp fp32 [rows, top_cap]).  `out`: that tuple of
+    tensors to write into (skipped rows leave theirs untouched); otherwise fresh ones, pre-filled with lp -inf, rank 0 and id -1."""
+    x = logits if logits.dim() == 2 else logits[None]
+    assert x.dtype == torch.bfloat16 and x.stride(1) == 1
+    rows, top_cap = x.shape[0], int(top_cap)
+    ids = (ids if torch.is_tensor(ids) else torch.tensor([int(i) for i in ids], dtype=torch.int32)).to(device=x.device, dtype=torch.int32).contiguous()
+    if not torch.is_tensor(n_top):
+        n_top = torch.tensor([int(n_top)] * rows if isinstance(n_top, int) else [int(v) for v in n_top], dtype=torch.int32)
+    n_top = n_top.to(device=x.device, dtype=torch.int32).contiguous()
+    if ids.numel() != rows or n_top.numel() != rows:
+        raise ThinkDiffHipError(f"logprobs_rows: {ids.numel()} ids and {n_top.numel()} n_top for {rows} rows")
+    if out is None:
+        out = (torch.full((rows,), float("-inf"), dtype=torch.float32, device=x.device), torch.zeros(rows, dtype=torch.int32, device=x.device),
+               torch.full((rows, max(top_cap, 0)), -1, dtype=torch.int32, device=x.device),
+               torch.full((rows, max(top_cap, 0)), float("-inf"), dtype=torch.float32, device=x.device))
+    lp, rank, top_ids, top_lp = out
+    check(lib().td_logprobs_rows_bf16(ptr(x), x.stride(0), rows, x.shape[1], ptr(ids), ptr(n_top), top_cap, ptr(lp), ptr(rank),
+                                      ptr(top_ids) if top_cap > 0 else None, ptr(top_lp) if top_cap > 0 else None, stream_ptr()))
+    return lp, rank, top_ids, top_lp
 
 
 def redux_compose(text, image, scales, T=None, D=None, device=None, out=None):

@@ -47,7 +47,7 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 256),
             min_tokens=vc.get("min_tokens", 1), ignore_eos=vc.get("ignore_eos", False),
             stop_token_ids=list(vc["stop_token_ids"]) if vc.get("stop_token_ids") else None,      # (a vllm.SamplingParams field; the reference's config leaves it unset)
-            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed: the per-request sampler (td_sample_rows_bf16)
+            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs
         self.mllama_tokenizer, self.mllama_processor = tokenizer, None
         self.visual, self.image_processor, self.image_token_id = None, None, 151655
         self.request_builder = request_builder

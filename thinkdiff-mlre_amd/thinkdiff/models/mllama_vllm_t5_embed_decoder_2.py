@@ -50,7 +50,7 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         self.mllama_sampling_params = SamplingParams(
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),
             min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True),
-            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed: the per-request sampler (td_sample_rows_bf16)
+            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs
         self.mm_projector = HipVisionProjector(self.config.mm_hidden_size, hidden_size, mm_projector_type, device=device, fp32_norm=True)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, processor
         self.visual, self.image_token_id = visual, image_token_id

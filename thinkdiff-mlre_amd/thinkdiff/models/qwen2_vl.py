@@ -7,6 +7,7 @@ and the generated tokens' hidden states at `embedding_layer_name="model.norm"` p
 Image inputs: `vision_towers.HipQwen2VisionTransformer` produces the merged vision tokens; `expand_image_placeholders`,
 `embed_tokens` and `mrope_position_ids` below do what vLLM's input processor and `get_rope_index` do around the decoder.
 """
+import collections
 import ctypes
 import dataclasses
 import numbers
@@ -51,11 +52,46 @@ class SamplingParams:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     seed: Optional[int] = None
+    # logit edits (td_sample_rows_edit_bf16: applied in front of the penalties, in vLLM's order) and logprobs (td_logprobs_rows_bf16, raw logits)
+    logit_bias: Optional[Dict[int, float]] = None
+    allowed_token_ids: Optional[List[int]] = None
+    bad_words_token_ids: Optional[List[List[int]]] = None      # vLLM's bad words, already tokenised (string `bad_words` need a tokenizer: not served)
+    mask_stop_below_min_tokens: bool = False      # True: vLLM's min_tokens rule (EOS and the stop ids cannot be sampled before min_tokens); False: they are sampled and only do not stop
+    logprobs: Optional[int] = None
 
     def validate(self) -> "SamplingParams":
         """vLLM's ranges; a ValueError names the field and the value."""
         def bad(field, why):
             raise ValueError(f"SamplingParams.{field}={getattr(self, field)!r}: {why}")
+
+        def token(t):
+            return isinstance(t, numbers.Integral) and not isinstance(t, bool) and t >= 0
+        if self.logit_bias is not None:
+            if not hasattr(self.logit_bias, "items"):
+                bad("logit_bias", "must be a dict token id -> bias, or None")
+            if len(self.logit_bias) > _hip.MAX_LOGIT_BIAS:
+                bad("logit_bias", f"holds {len(self.logit_bias)} entries, at most {_hip.MAX_LOGIT_BIAS} are served")
+            for t, v in self.logit_bias.items():
+                if not token(t):
+                    bad("logit_bias", f"token id {t!r} must be an integer >= 0")
+                if isinstance(v, bool) or not isinstance(v, numbers.Real) or v != v or v in (float("inf"), float("-inf")):
+                    bad("logit_bias", f"the bias of token {t} must be a finite number, got {v!r}")
+        if self.allowed_token_ids is not None:
+            if isinstance(self.allowed_token_ids, (str, bytes)) or not hasattr(self.allowed_token_ids, "__len__") or len(self.allowed_token_ids) == 0:
+                bad("allowed_token_ids", "must be a non-empty list of token ids, or None")
+            if not all(token(t) for t in self.allowed_token_ids):
+                bad("allowed_token_ids", "every token id must be an integer >= 0")
+        if self.bad_words_token_ids is not None:
+            if isinstance(self.bad_words_token_ids, (str, bytes)) or not hasattr(self.bad_words_token_ids, "__len__"):
+                bad("bad_words_token_ids", "must be a list of token-id lists, or None")
+            for w in self.bad_words_token_ids:
+                if isinstance(w, (str, bytes)) or not hasattr(w, "__len__") or len(w) == 0 or not all(token(t) for t in w):
+                    bad("bad_words_token_ids", f"every word must be a non-empty list of token ids >= 0, got {w!r}")
+        if not isinstance(self.mask_stop_below_min_tokens, bool):
+            bad("mask_stop_below_min_tokens", "must be True or False")
+        if self.logprobs is not None and not (isinstance(self.logprobs, numbers.Integral) and not isinstance(self.logprobs, bool)
+                                              and 0 <= self.logprobs <= _hip.MAX_LOGPROBS):
+            bad("logprobs", f"must be None or an integer in [0, {_hip.MAX_LOGPROBS}]")
         if not (isinstance(self.top_k, numbers.Integral) and not isinstance(self.top_k, bool) and self.top_k >= -1):
             bad("top_k", "must be -1 or 0 (off) or an integer >= 1")
         for f in ("min_p", "top_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "temperature"):
@@ -88,15 +124,101 @@ class SamplingParams:
     @property
     def per_request(self) -> bool:
         """True when a field td_sample_top_p_bf16 does not serve is set."""
-        return self.top_k > 0 or self.min_p > 0.0 or self.has_penalty or self.seed is not None
+        return self.top_k > 0 or self.min_p > 0.0 or self.has_penalty or self.seed is not None or self.has_edit
+
+    @property
+    def has_edit(self) -> bool:
+        """True when the request edits its logits (td_sample_rows_edit_bf16): a bias, an allowed set, bad words, or the min_tokens stop mask with
+        something to mask (an EOS id is only known to the generate call: `not ignore_eos` counts as "maybe")."""
+        return bool(self.logit_bias) or self.allowed_token_ids is not None or bool(self.bad_words_token_ids) or \
+            (self.mask_stop_below_min_tokens and self.min_tokens > 0 and (bool(self.stop_token_ids) or not self.ignore_eos))
 
 
 SAMPLER_CONFIG_KEYS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "seed")
+LOGIT_EDIT_CONFIG_KEYS = ("logit_bias", "allowed_token_ids", "bad_words_token_ids", "mask_stop_below_min_tokens", "logprobs")
+# vllm.SamplingParams keys the engine does not serve: a vllm_config that sets one is refused, never ignored
+UNSERVED_CONFIG_KEYS = {"prompt_logprobs": "prompt_logprobs is not served by the HIP engine (logprobs of generated or forced tokens are: `logprobs`)",
+                        "bad_words": "string bad_words need a tokenizer, which the engine does not hold: pass the words as token ids in bad_words_token_ids"}
 
 
 def sampler_fields_from_vllm_config(vc) -> dict:
-    """The per-request sampler fields a vllm_config sets, under SamplingParams' names; absent keys (and None) keep the defaults."""
-    return {k: vc[k] for k in SAMPLER_CONFIG_KEYS if vc.get(k) is not None}
+    """The per-request sampler, logit-edit and logprobs fields a vllm_config sets, under SamplingParams' names; absent keys (and None) keep the
+    defaults.  A key of UNSERVED_CONFIG_KEYS that is set raises a ValueError saying what to use instead."""
+    for k, why in UNSERVED_CONFIG_KEYS.items():
+        if vc.get(k) is not None:
+            raise ValueError(f"vllm_config {k}={vc[k]!r}: {why}")
+    return {k: vc[k] for k in SAMPLER_CONFIG_KEYS + LOGIT_EDIT_CONFIG_KEYS if vc.get(k) is not None}
+
+
+Logprob = collections.namedtuple("Logprob", ["logprob", "rank"])      # vLLM's Logprob, without the decoded text
+
+
+class LogitEditPlan:
+    """Which token ids one request bans at which step: vLLM's allowed_token_ids, bad-words and min-tokens rules as set differences, pure Python, no
+    device calls (tests/test_logit_edits_cpu.py checks it against a brute-force restatement).
+
+      allowed     allowed_token_ids, or None: everything outside is banned for good (td_logit_edits_allow_only at admission);
+      fixed       tokens banned for good: the one-token bad words;
+      stops       EOS (unless ignore_eos) and the stop_token_ids, banned while fewer than min_tokens tokens exist (mask_stop_below_min_tokens);
+      words       bad words of two or more tokens: the last token is banned at a step iff the request's OUTPUT ends with the word's prefix.
+    start() gives the admission-time calls, advance(token) the bans to set and to clear before the next step.  A token is never un-banned while
+    another rule still bans it: `fixed` and the complement of `allowed` are never cleared, and the per-step set is kept as one set.  Only a plan with
+    `words` needs the sampled token on the host (needs_tokens): every other rule depends on the token COUNT alone, so such requests keep the
+    "no host round trip" property of the decode loop."""
+
+    def __init__(self, sp: "SamplingParams", vocab: int, eos_token_id: Optional[int] = None):
+        def inside(field, t):
+            if int(t) >= vocab:
+                raise ValueError(f"SamplingParams.{field}: token id {int(t)} is outside the vocabulary of {vocab} tokens")
+            return int(t)
+        self.bias = {inside("logit_bias", t): float(v) for t, v in (sp.logit_bias or {}).items()}
+        self.allowed = None if sp.allowed_token_ids is None else sorted({inside("allowed_token_ids", t) for t in sp.allowed_token_ids})
+        words = [[inside("bad_words_token_ids", t) for t in w] for w in (sp.bad_words_token_ids or [])]
+        self.fixed = {w[0] for w in words if len(w) == 1}
+        self.words = [w for w in words if len(w) > 1]
+        self.min_tokens = int(sp.min_tokens)
+        self.stops = set()
+        if sp.mask_stop_below_min_tokens and self.min_tokens > 0:
+            self.stops = {int(t) for t in (sp.stop_token_ids or []) if 0 <= int(t) < vocab}
+            if not sp.ignore_eos and eos_token_id is not None and 0 <= int(eos_token_id) < vocab:
+                self.stops.add(int(eos_token_id))
+        self.needs_tokens = bool(self.words)
+        self.per_step = bool(self.words) or bool(self.stops)
+        self._allowed_set = None if self.allowed is None else set(self.allowed)
+        self.output: List[int] = []
+        self.ngen = 0
+        self.current = set()      # what the per-step rules ban now, tokens banned for good left out
+        if self.allowed is not None and not (self._allowed_set - self.fixed - self.stops):
+            raise ValueError(f"SamplingParams.allowed_token_ids={sp.allowed_token_ids!r}: every allowed token is banned by bad_words_token_ids or the "
+                             "min_tokens stop mask, nothing could be sampled")
+
+    def _for_good(self, t):
+        return t in self.fixed or (self._allowed_set is not None and t not in self._allowed_set)
+
+    def _wanted(self):
+        want = set(self.stops) if self.ngen < self.min_tokens else set()
+        for w in self.words:
+            k = len(w) - 1
+            if k <= len(self.output) and self.output[len(self.output) - k:] == w[:-1]:
+                want.add(w[-1])
+        return {t for t in want if not self._for_good(t)}
+
+    def start(self):
+        """-> (allowed ids or None, ids to ban) for a freshly reset slot, before the first token."""
+        self.output, self.ngen = [], 0
+        self.current = self._wanted()
+        return self.allowed, sorted(self.fixed | self.current)
+
+    def advance(self, token=None):
+        """One more token exists (`token`: its id, needed iff needs_tokens) -> (ids to ban, ids to un-ban) before the next step."""
+        self.ngen += 1
+        if self.needs_tokens:
+            self.output.append(int(token))
+            del self.output[:-max(len(w) for w in self.words)]      # (only the longest prefix can matter)
+        want = self._wanted()
+        on, off = sorted(want - self.current), sorted(self.current - want)
+        self.current = want
+        return on, off
 
 
 def _sampling_list(sampling, n, what):
@@ -119,19 +241,40 @@ class _RowSampling:
     """The per-request sampler path of one generate call (td_sample_rows_bf16): a device table of TdSampleRow structs in live-row order, rewritten only
     when the live set changes, and the offsets uploaded per step.  A request with its own seed draws from (seed, its generated-token count, 0), so
     its tokens do not depend on which rows share the step; the others draw from (the call's key, the step, live row) as the single-params path does.
-    History (the engine's td_sampler, created on first use) is kept only for requests with a penalty; every other row names slot -1."""
+    History (the engine's td_sampler, created on first use) is kept only for requests with a penalty; every other row names slot -1.
+    Logit edits (the engine's td_logit_edits, created on first use, one slot per cache slot): a request with an edit (SamplingParams.has_edit) has
+    its slot reset and filled at admission from its LogitEditPlan, names that slot in the per-row edit-slot table, and has the plan's per-step ban
+    changes applied after every token (advance).  A step none of whose live rows has an edit calls sample_rows exactly as before.  Only a request
+    with a bad word of two or more tokens needs its sampled token on the host every step; everything else depends on token counts alone."""
 
-    def __init__(self, engine, key):
-        self.engine, self.key = engine, int(key)
+    def __init__(self, engine, key, eos_token_id=None):
+        self.engine, self.key, self.eos = engine, int(key), eos_token_id
         self.table, self.seeded, self.state = None, [], None
+        self.plans, self.edit_slots, self.live_plans = {}, None, []
 
     def admit(self, slot, sp, prompt_ids):
         if sp.has_penalty:
             self.engine._sampler_state().reset_slot(int(slot), [int(t) for t in prompt_ids])
+        self.plans.pop(int(slot), None)
+        if sp.has_edit:
+            plan = LogitEditPlan(sp, self.engine.config.vocab_size, self.eos)      # (raises ValueError for an id outside the vocabulary, before any device call)
+            ed = self.engine._logit_edits()
+            ed.reset_slot(int(slot))      # a reused slot starts clean
+            allowed, ban = plan.start()
+            if allowed is not None:
+                ed.allow_only(int(slot), allowed)
+            if ban:
+                ed.ban(int(slot), ban, True)
+            if plan.bias:
+                ed.set_bias(int(slot), plan.bias)
+            self.plans[int(slot)] = plan
 
     def set_live(self, rows):
         """rows: (SamplingParams, cache slot) per live row."""
         recs, self.seeded, any_hist = [], [], False
+        es = [int(slot) if int(slot) in self.plans and sp.has_edit else -1 for sp, slot in rows]
+        self.live_plans = [(i, s, self.plans[s]) for i, s in enumerate(es) if s >= 0 and self.plans[s].per_step]
+        self.edit_slots = torch.tensor(es, dtype=torch.int32).to(self.engine.device) if any(s >= 0 for s in es) else None
         for r, (sp, slot) in enumerate(rows):
             hist = sp.has_penalty
             any_hist |= hist
@@ -146,7 +289,68 @@ class _RowSampling:
     def sample(self, logits, step, ngen):
         """logits [n, vocab] of the live rows; step: the call's decode step; ngen[i]: tokens live row i has generated."""
         offs = torch.tensor([int(ngen[i]) if s else int(step) for i, s in enumerate(self.seeded)], dtype=torch.int64).to(self.engine.device)
-        return _OPS.sample_rows(logits, self.table, offs, self.state, self.state is not None)
+        if self.edit_slots is None:
+            return _OPS.sample_rows(logits, self.table, offs, self.state, self.state is not None)
+        return _OPS.sample_rows_edit(logits, self.table, offs, self.state, self.state is not None, self.engine._logit_edits().handle, self.edit_slots)
+
+    def advance(self, toks):
+        """After a step: toks[i] is live row i's new token (a device tensor, a list or an array; read on the host only for the rows whose plan has a
+        bad word of several tokens).  Applies each plan's ban changes to its edit slot before the next step's launch."""
+        if not self.live_plans:
+            return
+        ed = self.engine._logit_edits()
+        for i, slot, plan in self.live_plans:
+            on, off = plan.advance(int(toks[i]) if plan.needs_tokens else None)
+            if off:
+                ed.ban(slot, off, False)
+            if on:
+                ed.ban(slot, on, True)
+
+
+class _LogprobLog:
+    """The logprobs of one generate call (td_logprobs_rows_bf16 on the RAW logits of every step, one launch per step for the rows that asked): the
+    results stay on the device and are read once at the end.  add(): logits [n, vocab], the n chosen (sampled or forced) tokens as a device int32
+    tensor, and the request each row belongs to; finish(): res[i]["logprobs"] = per generated token a dict token_id -> Logprob(logprob, rank) holding
+    the chosen token and the top `logprobs` ones (ranks 1, 2, .. in the kernel's order), res[i]["cumulative_logprob"] = the sum over the chosen
+    tokens -- for the requests that asked, nobody else's dict changes."""
+
+    def __init__(self, engine, want):
+        """want: SamplingParams.logprobs per request (None: not asked), a list, or one int for every request."""
+        self.engine = engine
+        self.want = (lambda i, v=int(want): v) if isinstance(want, numbers.Integral) else (lambda i, w=list(want): w[i])
+        self.cap = int(want) if isinstance(want, numbers.Integral) else max([0] + [int(v) for v in want if v is not None])
+        self.steps = []
+
+    @staticmethod
+    def wanted(sps):
+        return any(sp.logprobs is not None for sp in sps)
+
+    def add(self, logits, tok_dev, owners):
+        n_top = [-1 if self.want(int(o)) is None else int(self.want(int(o))) for o in owners]
+        if max(n_top) < 0:
+            return
+        x = logits if logits.dim() == 2 else logits[None]
+        out = _OPS.logprobs_rows(x, tok_dev.to(torch.int32), torch.tensor(n_top, dtype=torch.int32).to(self.engine.device), self.cap)
+        self.steps.append(([int(o) for o in owners], tok_dev, n_top, out))
+
+    def finish(self, res):
+        for i, r in enumerate(res):
+            if self.want(i) is not None:
+                r["logprobs"], r["cumulative_logprob"] = [], 0.0
+        if not self.steps:
+            return
+        toks = torch.cat([s[1].to(torch.int32).reshape(-1) for s in self.steps]).cpu().tolist()
+        lp, rank, tid, tlp = (torch.cat([s[3][j] for s in self.steps]).cpu().tolist() for j in range(4))
+        r0 = 0
+        for owners, _, n_top, _ in self.steps:
+            for i, (o, n) in enumerate(zip(owners, n_top)):
+                if n >= 0:
+                    k = r0 + i
+                    d = {int(tid[k][j]): Logprob(float(tlp[k][j]), j + 1) for j in range(n)}
+                    d[int(toks[k])] = Logprob(float(lp[k]), int(rank[k]))
+                    res[o]["logprobs"].append(d)
+                    res[o]["cumulative_logprob"] += float(lp[k])
+            r0 += len(owners)
 
 
 class Qwen2VLTextEngine:
@@ -199,6 +403,19 @@ class Qwen2VLTextEngine:
         st, self._sampler = getattr(self, "_sampler", None), None
         if st is not None:
             st.close()
+        ed, self._edits = getattr(self, "_edits", None), None
+        if ed is not None:
+            ed.close()
+
+    def _logit_edits(self):
+        """The edit slots behind logit_bias, allowed_token_ids, bad words and the min_tokens stop mask (td_logit_edits, one slot per cache slot),
+        created the first time a request with an edit arrives: n_slots x (2 x vocab / 8 + 8196) bytes of device memory (11.8 MB at 256 x 152 064)."""
+        ed = getattr(self, "_edits", None)
+        if ed is None or ed.n_slots != max(1, getattr(self, "n_slots", 1)):
+            if ed is not None:
+                ed.close()
+            ed = self._edits = _hip.LogitEdits(max(1, getattr(self, "n_slots", 1)), self.config.vocab_size, self.device)
+        return ed
 
     def _sampler_state(self):
         """The token history behind the penalties (td_sampler, one slot per cache slot), created the first time a request with a penalty arrives:
@@ -440,9 +657,10 @@ class Qwen2VLTextEngine:
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
         rows = None
         if by_rows and forced_output_ids is None:      # (teacher-forced decoding does not sample and keeps no history)
-            rows = _RowSampling(self, key)
+            rows = _RowSampling(self, key, eos_token_id)
             rows.admit(0, sampling, prompt_token_ids)
             rows.set_live([(sampling, 0)])
+        lplog = _LogprobLog(self, [sampling.logprobs]) if sampling.logprobs is not None else None      # (forced tokens are scored too)
         if forced_output_ids is not None:
             forced_dev = torch.tensor(list(forced_output_ids), dtype=torch.int32).to(self.device)
         for step in range(sampling.max_tokens):
@@ -452,8 +670,11 @@ class Qwen2VLTextEngine:
                 nxt = forced_dev[step:step + 1]
             elif rows is not None:
                 nxt = rows.sample(logits if logits.dim() == 2 else logits[None], step, [step])
+                rows.advance(nxt)
             else:
                 nxt = _OPS.sample_top_p(logits, float(sampling.temperature), float(sampling.top_p), int(key), int(step))     # device int32 [1], no host round trip
+            if lplog is not None:
+                lplog.add(logits, nxt, [0])
             out_tok.append(nxt)
             # one token against the cache: the decode step (fused rope + cache write, decode attention, gated-MLP weight stream)
             h1, lg = self.decode_batch(nxt, [[next_pos + step]] * 3, [n_p + step])
@@ -465,7 +686,10 @@ class Qwen2VLTextEngine:
                     break
         hs = torch.cat(out_hidden) if out_hidden else torch.empty(0, self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
         out_ids = torch.cat(out_tok).tolist() if out_tok else []
-        return {"prompt_hidden_states": prompt_hidden, "hidden_states": hs, "token_ids": out_ids}
+        res = {"prompt_hidden_states": prompt_hidden, "hidden_states": hs, "token_ids": out_ids}
+        if lplog is not None:      # "logprobs" and "cumulative_logprob": present only when asked
+            lplog.finish([res])
+        return res
 
     @staticmethod
     def _draw_sampler_key(generator: Optional[torch.Generator] = None) -> int:
@@ -563,10 +787,11 @@ class Qwen2VLTextEngine:
         stops = [set(sp.stop_token_ids or []) for sp in sps]      # per request, like max_tokens / min_tokens / ignore_eos below
         rows_s = None
         if by_rows and forced_output_ids is None:
-            rows_s = _RowSampling(self, key)
+            rows_s = _RowSampling(self, key, eos_token_id)
             for b in range(B):
                 rows_s.admit(b, sps[b], requests[b]["prompt_token_ids"])
             live_changed = True
+        lplog = _LogprobLog(self, [sp.logprobs for sp in sps]) if _LogprobLog.wanted(sps) else None
         step = 0
         # per step: the hidden rows stay ONE device tensor and the slot -> request map is remembered; the rows are handed to their requests by a
         # single gather after the loop (256 sequences x 256 steps of per-row tensor views and list appends were ~0.5 ms of host time per step,
@@ -594,10 +819,15 @@ class Qwen2VLTextEngine:
                 if live_changed:
                     rows_s.set_live([(sps[o], sl) for o, sl in zip(owner, slots)])
                     live_changed = False
-                toks = rows_s.sample(logits[:n], step, [step] * n).tolist()      # (every sequence of a batch starts at step 0)
+                tok_dev = rows_s.sample(logits[:n], step, [step] * n)      # (every sequence of a batch starts at step 0)
+                toks = tok_dev.tolist()
+                rows_s.advance(toks)
             else:
                 # one launch for all live rows (td_sample_top_p_bf16); the ids come to the host once per step for the bookkeeping below
-                toks = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(step)).tolist()
+                tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(step))
+                toks = tok_dev.tolist()
+            if lplog is not None:
+                lplog.add(logits[:n], tok_dev if forced_output_ids is None else torch.tensor(toks, dtype=torch.int32).to(self.device), owner)
             pos = torch.tensor(next_pos[:n], dtype=torch.int32).unsqueeze(0).expand(3, n)
             hid, logits = self.decode_batch(toks, pos, cache_len[:n], slots=slots)
             step_hid.append(hid)
@@ -632,6 +862,8 @@ class Qwen2VLTextEngine:
             parts = torch.split(allh.index_select(0, idx), [len(rr) for rr in rows])
         for b, r in enumerate(res):
             r["hidden_states"] = parts[b] if base and rows[b] else torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
+        if lplog is not None:
+            lplog.finish(res)
         return res
 
     @torch.no_grad()
@@ -702,7 +934,11 @@ class Qwen2VLTextEngine:
             stop_sets = [set(sp.stop_token_ids or []) for sp in sps_all]
             can_stop = forced_output_ids is None
             mint = np.zeros(max_live, dtype=np.int32)
-        rows_s = _RowSampling(self, key) if by_rows and forced_output_ids is None else None
+        rows_s = _RowSampling(self, key, eos_token_id) if by_rows and forced_output_ids is None else None
+        if sps_all is None:
+            lplog = _LogprobLog(self, sampling.logprobs) if sampling.logprobs is not None else None
+        else:
+            lplog = _LogprobLog(self, [sp.logprobs for sp in sps_all]) if _LogprobLog.wanted(sps_all) else None
         live_changed = True
         step_hid, step_owner, step_toks = [], [], []
         gstep = 0
@@ -787,6 +1023,10 @@ class Qwen2VLTextEngine:
                 else:
                     tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(gstep))
                 toks = tok_dev.cpu().numpy()      # (the host sees the ids once per step, for the stop rules below)
+                if rows_s is not None:
+                    rows_s.advance(toks)
+            if lplog is not None:
+                lplog.add(logits[:n], tok_dev, own[:n])
             pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(npos[:n], (3, n)))).to(self.device)
             hid = torch.empty(n, D, dtype=torch.bfloat16, device=self.device)
             self._decode_slots(n, slt, tok_dev, pos_dev, clen, hid, logits)      # logits of row i -> logits[i]
@@ -832,6 +1072,8 @@ class Qwen2VLTextEngine:
         else:
             for r in res:
                 r["hidden_states"] = torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
+        if lplog is not None:
+            lplog.finish(res)
         return res
 
     # the two engine calls of generate_continuous (separate methods so that the scheduler's host logic can be exercised against a stand-in engine)

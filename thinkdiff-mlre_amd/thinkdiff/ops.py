@@ -19,6 +19,9 @@ qk_norm_rope_              per-head QK-RMSNorm + rotary embedding, in place
 euler_step_                FlowMatchEulerDiscreteScheduler.step, in place
 flux_pack_latents / flux_unpack_latents, cls_avgpool2, sample_top_p
 sample_rows                per-request sampler: penalties, top-k, top-p, min-p per row (`state` = a thinkdiff._hip.Sampler handle or None)
+sample_rows_edit           sample_rows with a per-row edit of the logits in front of the penalties: bans, allowed ids and logit_bias (`edits` = a
+                           thinkdiff._hip.LogitEdits handle or None, `edit_slots` = int32 [rows], -1 = none)
+logprobs_rows              the chosen token's logprob and rank and the top-n logprobs of each row of RAW logits (vLLM's `logprobs`), no sort
 flux_forward_ / flux_denoise_ / flux_denoise_multi_   FluxTransformer2DModel.forward and the pipeline's denoising loop, on a prepared engine
                            (`engine` = the td_flux* handle thinkdiff.models.flux_transformer holds); tensors are checked against the
                            extents the prepared context expects (td_flux_prepared_shape)
@@ -74,6 +77,8 @@ SCHEMAS = {
     "cls_avgpool2": "(Tensor tokens) -> Tensor",
     "sample_top_p": "(Tensor logits, float temperature, float top_p, int seed, int offset) -> Tensor",
     "sample_rows": "(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state) -> Tensor",
+    "sample_rows_edit": "(Tensor logits, Tensor params, Tensor offsets, int? state, bool update_state, int? edits, Tensor? edit_slots) -> Tensor",
+    "logprobs_rows": "(Tensor logits, Tensor ids, Tensor n_top, int top_cap) -> (Tensor, Tensor, Tensor, Tensor)",
     "flux_forward_": "(int engine, Tensor latents, int step, Tensor(a!) velocity) -> Tensor(a!)",
     "flux_denoise_": "(int engine, Tensor(a!) latents, float[] sigmas) -> Tensor(a!)",
     "flux_denoise_multi_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, int[] streams) -> ()",
