@@ -895,6 +895,25 @@ int td_qwen2_set_fused_rope(td_qwen2* f, int on);
 int td_qwen2_slot_capacity(const td_qwen2* f);
 /* copy the first `len` cache rows of sequence src to sequence dst (compaction when a sequence finishes) */
 int td_qwen2_move_slot(td_qwen2* f, int src, int dst, int len, void* stream);
+/* KV fork (td_abi_version() >= 16; csrc/kv_fork.hip): the first n_rows rows of slot src_slot copied to the same rows of every dst_slots[i], for all
+ * planes in ONE launch; every source chunk is loaded once and stored n_dst times.  A plane is a device array of slots x slot_rows rows of row_bytes
+ * bytes: slot s starts at base + s * slot_rows * row_bytes.  Accesses are 16 bytes wide wherever the slot stride is a multiple of 16 (8, 4 or 2
+ * bytes otherwise: the width every slot's start shares), with 2-byte pieces in front of the first and behind the last aligned address.
+ * planes and dst_slots are HOST arrays, read before the call returns: they reach the device in the launches' own arguments (64 planes x 192
+ * destinations per launch), so the call allocates nothing, synchronises nothing and no host buffer has to outlive it.  The caller vouches that
+ * every named slot lies inside its plane.  TD_ERR_INVALID with a message naming the value, before any HIP call: a NULL planes / dst_slots / base,
+ * n_planes < 1, n_dst < 1, n_rows < 0 or above a plane's slot_rows, a negative slot, src_slot among the destinations, a destination given twice,
+ * row_bytes not a positive multiple of 2, a base that is not 2-byte aligned.  n_rows == 0: TD_OK, no launch. */
+typedef struct {
+  void* base;
+  int64_t row_bytes;
+  int64_t slot_rows;
+} TdKvPlane;
+int td_kv_fork_rows(const TdKvPlane* planes, int n_planes, int src_slot, const int* dst_slots, int n_dst, int n_rows, void* stream);
+/* td_kv_fork_rows over the handle's own planes (one bf16 plane per layer; the byte plane and the scale plane per layer on the e4m3 cache): the first
+ * `len` cache rows of sequence src to every sequence dst_slots[0 .. n_dst) (HOST ints) -- n sequences continuing from one prefill.  Also refused:
+ * a slot outside [0, n_slots), len above the slot capacity.  td_qwen2_move_slot is the one-destination form on hipMemcpyAsync. */
+int td_qwen2_fork_slot(td_qwen2* f, int src, const int* dst_slots, int n_dst, int len, void* stream);
 /* One new token for each of the sequences in slots 0..B-1 (B <= 64) in one pass over the weights: token_ids int32[B],
  * position_ids int32[3,B] (device); cache_pos[b] = tokens already cached for sequence b (HOST ints); hidden_out bf16[B,hidden],
  * logits bf16[B,vocab] (either may be NULL). */

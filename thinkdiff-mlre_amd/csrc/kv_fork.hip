@@ -1,0 +1,145 @@
+// KV fork: the first n_rows cache rows of one slot copied to many slots, every plane of a handle in ONE launch (td_kv_fork_rows).
+//
+// What it is for: n / best_of parallel sampling prefills a prompt once and lets k sequences continue from the same cache rows.  The slots of the
+// Qwen2 engine are a fixed partition of each layer's cache, so a fork is a copy.  td_qwen2_move_slot does that copy for ONE destination with one
+// hipMemcpyAsync per plane: 28 layers x 2 planes x 7 destinations = 392 host-enqueued copies for an e4m3 prompt forked seven ways, and the source
+// rows are read seven times.  Here every source chunk is loaded once and stored n_dst times.
+//
+// A plane is `slots x slot_rows` rows of row_bytes bytes; the rows [0, n_rows) of a slot are contiguous, so per plane the fork is one byte range of
+// n_rows x row_bytes bytes at `base + slot x slot_rows x row_bytes`.  Source and destinations differ by multiples of the slot stride, so they share
+// their alignment modulo w = the largest of 16, 8, 4, 2 that divides the stride: with that width ONE split of the range into
+//   head  (2-byte pieces up to the first w-aligned address: at most 7),  body (w-byte pieces, w-aligned on every side),  tail (2-byte pieces, at most 7)
+// holds for the source and for every destination.  w = 16 whenever the slot stride is a multiple of 16 -- every Qwen2 cache plane but the e4m3 scale
+// plane of a one-kv-head model with an odd slot_len (2 Hkv 4 = 8 bytes per row), which is copied in 8-byte pieces.
+//
+// The plane table and the destination slots travel in the launch's own arguments (td_logit_edits_set_bias's method): nothing is allocated, nothing
+// uploaded, no host buffer has to outlive the call; FORK_PLANES planes x FORK_DSTS destinations per launch, as many launches as that needs.
+#include <algorithm>
+#include <vector>
+
+#include "td_common.h"
+#include "../../include/thinkdiff_hip.h"
+
+namespace {
+
+constexpr int FORK_PLANES = 64;      // (28 layers x 2 planes of the e4m3 cache fit one launch)
+constexpr int FORK_DSTS = 192;
+constexpr int FORK_NT = 256;
+constexpr int FORK_UNROLL = 4;       // pieces a thread has in flight: 4 x 16 bytes x 256 threads = 16 KiB of source per workgroup and pass
+
+struct ForkPlane {
+  char* base;                // the plane
+  long long slot_bytes;      // slot stride
+  long long nbytes;          // bytes to copy per slot
+  int w;                     // access width of the body: 16, 8, 4 or 2
+  int head;                  // bytes before the first w-aligned address (even, < w, <= nbytes)
+};
+struct ForkArgs {            // 64 x 32 + 192 x 4 + 16 = 2832 bytes of kernel arguments
+  ForkPlane plane[FORK_PLANES];
+  int dst[FORK_DSTS];
+  int src;
+  int n_dst;
+  int pad0, pad1;
+};
+
+template <typename T>
+__device__ __forceinline__ void fork_body(const ForkArgs& a, const ForkPlane& p, long long pieces) {
+  const char* src = p.base + (long long)a.src * p.slot_bytes + p.head;
+  const long long per_pass = (long long)FORK_NT * FORK_UNROLL;
+  for (long long c0 = (long long)blockIdx.x * per_pass; c0 < pieces; c0 += (long long)gridDim.x * per_pass) {
+    T v[FORK_UNROLL];
+#pragma unroll
+    for (int u = 0; u < FORK_UNROLL; ++u) {
+      const long long c = c0 + u * FORK_NT + threadIdx.x;
+      if (c < pieces) v[u] = ((const T*)src)[c];
+    }
+    for (int d = 0; d < a.n_dst; ++d) {
+      char* dst = p.base + (long long)a.dst[d] * p.slot_bytes + p.head;
+#pragma unroll
+      for (int u = 0; u < FORK_UNROLL; ++u) {
+        const long long c = c0 + u * FORK_NT + threadIdx.x;
+        if (c < pieces) ((T*)dst)[c] = v[u];
+      }
+    }
+  }
+}
+
+// grid (passes, planes of this launch): workgroup x of plane y walks the body's pieces x, x + gridDim.x, ..; workgroup 0 of a plane also copies the
+// head (threads 0 ..) and the tail (threads 64 ..) in 2-byte pieces
+__global__ __launch_bounds__(FORK_NT) void td_kv_fork_kernel(const ForkArgs a) {
+  const ForkPlane& p = a.plane[blockIdx.y];
+  const long long body = (p.nbytes - p.head) / p.w;
+  if (blockIdx.x == 0) {
+    const int tail = (int)(p.nbytes - p.head - body * p.w);
+    const int t = threadIdx.x;
+    long long off = -1;
+    if (t < p.head / 2) off = 2 * t;
+    else if (t >= 64 && t - 64 < tail / 2) off = p.head + body * p.w + 2 * (t - 64);
+    if (off >= 0) {
+      const unsigned short v = *(const unsigned short*)(p.base + (long long)a.src * p.slot_bytes + off);
+      for (int d = 0; d < a.n_dst; ++d) *(unsigned short*)(p.base + (long long)a.dst[d] * p.slot_bytes + off) = v;
+    }
+  }
+  if (p.w == 16) fork_body<u32x4_t>(a, p, body);
+  else if (p.w == 8) fork_body<u32x2_t>(a, p, body);
+  else if (p.w == 4) fork_body<unsigned>(a, p, body);
+  else fork_body<unsigned short>(a, p, body);
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_kv_fork_rows(const TdKvPlane* planes, int n_planes, int src_slot, const int* dst_slots, int n_dst, int n_rows, void* stream) {
+  TD_CHECK_ARG(planes, "td_kv_fork_rows: null planes");
+  TD_CHECK_ARG(dst_slots, "td_kv_fork_rows: null dst_slots");
+  TD_CHECK_ARG(n_planes >= 1, "td_kv_fork_rows: n_planes=%d, at least one plane is needed", n_planes);
+  TD_CHECK_ARG(n_dst >= 1, "td_kv_fork_rows: n_dst=%d, at least one destination is needed", n_dst);
+  TD_CHECK_ARG(n_rows >= 0, "td_kv_fork_rows: n_rows=%d is negative", n_rows);
+  TD_CHECK_ARG(src_slot >= 0, "td_kv_fork_rows: src_slot=%d is negative", src_slot);
+  for (int p = 0; p < n_planes; ++p) {
+    TD_CHECK_ARG(planes[p].base, "td_kv_fork_rows: plane %d has a null base", p);
+    TD_CHECK_ARG(planes[p].row_bytes >= 2 && planes[p].row_bytes % 2 == 0, "td_kv_fork_rows: row_bytes=%lld of plane %d is not a positive multiple of 2",
+                 (long long)planes[p].row_bytes, p);
+    TD_CHECK_ARG(((uintptr_t)planes[p].base) % 2 == 0, "td_kv_fork_rows: the base %p of plane %d is not 2-byte aligned", planes[p].base, p);
+    TD_CHECK_ARG(planes[p].slot_rows >= 1, "td_kv_fork_rows: slot_rows=%lld of plane %d is not positive", (long long)planes[p].slot_rows, p);
+    TD_CHECK_ARG(n_rows <= planes[p].slot_rows, "td_kv_fork_rows: n_rows=%d exceeds slot_rows=%lld of plane %d", n_rows, (long long)planes[p].slot_rows, p);
+  }
+  std::vector<int> sorted(dst_slots, dst_slots + n_dst);
+  std::sort(sorted.begin(), sorted.end());
+  TD_CHECK_ARG(sorted[0] >= 0, "td_kv_fork_rows: destination slot %d is negative", sorted[0]);
+  for (int i = 0; i < n_dst; ++i) {
+    TD_CHECK_ARG(sorted[i] != src_slot, "td_kv_fork_rows: src_slot=%d is among the destinations", src_slot);
+    TD_CHECK_ARG(i == 0 || sorted[i] != sorted[i - 1], "td_kv_fork_rows: destination slot %d is given twice", sorted[i]);
+  }
+  if (n_rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  for (int p0 = 0; p0 < n_planes; p0 += FORK_PLANES) {
+    const int np = std::min(FORK_PLANES, n_planes - p0);
+    ForkArgs a = {};
+    a.src = src_slot;
+    long long passes = 1;
+    for (int p = 0; p < np; ++p) {
+      const TdKvPlane& q = planes[p0 + p];
+      ForkPlane& fp = a.plane[p];
+      fp.base = (char*)q.base;
+      fp.slot_bytes = (long long)q.slot_rows * q.row_bytes;
+      fp.nbytes = (long long)n_rows * q.row_bytes;
+      fp.w = fp.slot_bytes % 16 == 0 ? 16 : fp.slot_bytes % 8 == 0 ? 8 : fp.slot_bytes % 4 == 0 ? 4 : 2;
+      const long long mis = (long long)(((uintptr_t)fp.base + (uintptr_t)((long long)src_slot * fp.slot_bytes)) % (uintptr_t)fp.w);
+      fp.head = (int)std::min<long long>((fp.w - mis) % fp.w, fp.nbytes);
+      const long long per_pass = (long long)FORK_NT * FORK_UNROLL * fp.w;
+      passes = std::max(passes, (fp.nbytes - fp.head + per_pass - 1) / per_pass);
+    }
+    const unsigned gx = (unsigned)std::min<long long>(passes, 4096);      // (a longer plane is walked in strides of the grid)
+    for (int d0 = 0; d0 < n_dst; d0 += FORK_DSTS) {
+      a.n_dst = std::min(FORK_DSTS, n_dst - d0);
+      for (int d = 0; d < a.n_dst; ++d) a.dst[d] = dst_slots[d0 + d];
+      hipLaunchKernelGGL(td_kv_fork_kernel, dim3(gx, np), dim3(FORK_NT), 0, st, a);
+      TD_CHECK_LAUNCH();
+    }
+  }
+  return 0;
+}
+
+}  // extern "C"

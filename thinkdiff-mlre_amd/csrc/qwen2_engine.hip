@@ -687,6 +687,28 @@ int td_qwen2_move_slot(td_qwen2* f, int src, int dst, int len, void* stream) {
   return TD_OK;
 }
 
+// one launch for every plane and destination (td_kv_fork_rows): n sequences continuing from one prefill
+int td_qwen2_fork_slot(td_qwen2* f, int src, const int* dst_slots, int n_dst, int len, void* stream) {
+  TD_CHECK_ARG(f, "td_qwen2_fork_slot: null handle");
+  TD_CHECK_ARG(dst_slots, "td_qwen2_fork_slot: null dst_slots");
+  TD_CHECK_ARG(n_dst >= 1, "td_qwen2_fork_slot: n_dst=%d, at least one destination is needed", n_dst);
+  TD_CHECK_ARG(src >= 0 && src < f->n_slots, "td_qwen2_fork_slot: source slot %d outside the %d configured sequences", src, f->n_slots);
+  for (int i = 0; i < n_dst; ++i)
+    TD_CHECK_ARG(dst_slots[i] >= 0 && dst_slots[i] < f->n_slots, "td_qwen2_fork_slot: destination slot %d outside the %d configured sequences", dst_slots[i], f->n_slots);
+  TD_CHECK_ARG(len >= 0 && len <= f->slot_len, "td_qwen2_fork_slot: len=%d exceeds the slot capacity %d", len, f->slot_len);
+  const int64_t KVW = (int64_t)2 * f->Hkv * 128, SW = (int64_t)2 * f->Hkv;
+  std::vector<TdKvPlane> planes;
+  for (const QLayer& l : f->layers) {
+    if (f->kv_mode == TD_QWEN2_KV_E4M3) {
+      planes.push_back(TdKvPlane{l.kv8, KVW, f->slot_len});
+      planes.push_back(TdKvPlane{l.kvs, SW * 4, f->slot_len});
+    } else {
+      planes.push_back(TdKvPlane{l.kv, KVW * 2, f->slot_len});
+    }
+  }
+  return td_kv_fork_rows(planes.data(), (int)planes.size(), src, dst_slots, n_dst, len, stream);
+}
+
 }  // extern "C"
 
 // ---- batched KV-cached decode (the precompute job: many short sequences against one pass over the weights) --------------

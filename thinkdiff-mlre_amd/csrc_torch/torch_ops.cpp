@@ -878,6 +878,24 @@ void flux_lora_delete(int64_t engine, std::string adapter) {
   else ok(td_flux_lora_delete((td_flux*)(uintptr_t)engine, adapter.c_str(), current_stream()));
 }
 
+// KV fork on one plane (td_kv_fork_rows): plane [slots * slot_rows, row] of any dtype, rows [0, n_rows) of slot src_slot -> the same rows of every dst slot, in place
+void kv_fork_rows(at::Tensor plane, int64_t slot_rows, int64_t src_slot, at::IntArrayRef dst_slots, int64_t n_rows) {
+  TORCH_CHECK(plane.is_cuda(), "thinkdiff_hip: plane must live on the GPU");
+  TORCH_CHECK(plane.dim() == 2 && plane.is_contiguous(), "thinkdiff_hip::kv_fork_rows: plane [slots * slot_rows, row] contiguous");
+  TORCH_CHECK(slot_rows >= 1 && plane.size(0) % slot_rows == 0, "thinkdiff_hip::kv_fork_rows: slot_rows=", slot_rows, " does not divide the plane's ", plane.size(0), " rows");
+  const int64_t slots = plane.size(0) / slot_rows;
+  TORCH_CHECK(src_slot >= 0 && src_slot < slots, "thinkdiff_hip::kv_fork_rows: src_slot=", src_slot, " outside the plane's ", slots, " slots");
+  std::vector<int> dst;
+  for (int64_t d : dst_slots) {
+    TORCH_CHECK(d >= 0 && d < slots, "thinkdiff_hip::kv_fork_rows: destination slot ", d, " outside the plane's ", slots, " slots");
+    dst.push_back((int)d);
+  }
+  TORCH_CHECK(n_rows >= 0 && n_rows <= slot_rows, "thinkdiff_hip::kv_fork_rows: n_rows=", n_rows, " outside [0, slot_rows=", slot_rows, "]");
+  DeviceGuard guard(plane.device());
+  const TdKvPlane pl = {plane.data_ptr(), plane.size(1) * (int64_t)plane.element_size(), slot_rows};
+  ok(td_kv_fork_rows(&pl, 1, (int)src_slot, dst.data(), (int)dst.size(), (int)n_rows, stream_of(plane)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(thinkdiff_hip, m) {
@@ -933,6 +951,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("kv_dequant_rows_e4m3(Tensor q, Tensor scale) -> Tensor");
   m.def("attention_decode_kv8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor");
   m.def("linear_w8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
+  m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -984,6 +1003,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("kv_dequant_rows_e4m3", &kv_dequant_rows_e4m3);
   m.impl("attention_decode_kv8", &attention_decode_kv8);
   m.impl("linear_w8", &linear_w8);
+  m.impl("kv_fork_rows", &kv_fork_rows);
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {

@@ -198,6 +198,8 @@ def _declare(L):
         "td_qwen2_prefill_packed_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_slot_capacity": [vp],
         "td_qwen2_move_slot": [vp, i32, i32, i32, vp],
+        "td_qwen2_fork_slot": [vp, i32, vp, i32, i32, vp],
+        "td_kv_fork_rows": [vp, i32, i32, vp, i32, i32, vp],
         "td_qwen2_decode_batch": [vp, i32, vp, vp, vp, vp, vp, vp],
         "td_qwen2_decode_batch_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_quantize_weights": [vp, i32, vp],
@@ -650,6 +652,28 @@ class TdQwen2Config(ctypes.Structure):
                 ("num_kv_heads", ctypes.c_int), ("head_dim", ctypes.c_int), ("intermediate", ctypes.c_int),
                 ("vocab", ctypes.c_int), ("tie_embeddings", ctypes.c_int), ("mrope_section", ctypes.c_int * 3),
                 ("rms_eps", ctypes.c_float), ("rope_theta", ctypes.c_float)]
+
+
+class TdKvPlane(ctypes.Structure):
+    """Mirror of `struct TdKvPlane` (include/thinkdiff_hip.h): slot s of a cache plane starts at base + s * slot_rows * row_bytes."""
+    _fields_ = [("base", ctypes.c_void_p), ("row_bytes", ctypes.c_int64), ("slot_rows", ctypes.c_int64)]
+
+
+def kv_fork_rows(planes, src_slot, dst_slots, n_rows):
+    """td_kv_fork_rows: rows [0, n_rows) of slot src_slot -> the same rows of every slot of dst_slots, for every plane in one launch.
+    planes: (tensor, slot_rows) pairs, each tensor a contiguous device array of slots x slot_rows rows (any dtype); in place."""
+    arr = (TdKvPlane * max(1, len(planes)))()
+    for i, (t, slot_rows) in enumerate(planes):
+        if not t.is_contiguous() or t.dim() < 2 or t.shape[0] % int(slot_rows):
+            raise ThinkDiffHipError(f"kv_fork_rows: plane {i} must be contiguous [slots * slot_rows, ...] with slot_rows={slot_rows} dividing its {t.shape[0]} rows")
+        slots = t.shape[0] // int(slot_rows)
+        bad = [int(s) for s in [src_slot, *dst_slots] if not 0 <= int(s) < slots]
+        if bad:
+            raise ThinkDiffHipError(f"kv_fork_rows: slot {bad[0]} outside the {slots} slots of plane {i}")
+        arr[i] = TdKvPlane(t.data_ptr(), (t.numel() // t.shape[0]) * t.element_size(), int(slot_rows))
+    dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
+    check(lib().td_kv_fork_rows(ctypes.cast(arr, ctypes.c_void_p), len(planes), int(src_slot), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(n_rows),
+                                stream_ptr()))
 
 
 class TdVaeConfig(ctypes.Structure):

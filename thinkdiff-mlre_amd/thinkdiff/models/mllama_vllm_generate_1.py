@@ -47,7 +47,7 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 256),
             min_tokens=vc.get("min_tokens", 1), ignore_eos=vc.get("ignore_eos", False),
             stop_token_ids=list(vc["stop_token_ids"]) if vc.get("stop_token_ids") else None,      # (a vllm.SamplingParams field; the reference's config leaves it unset)
-            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs
+            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, None
         self.visual, self.image_processor, self.image_token_id = None, None, 151655
         self.request_builder = request_builder
@@ -92,7 +92,8 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
         # third of the chunk's decode time -- are built by a helper thread on a stream of its own while chunk k decodes (the decode loop is a chain
         # of small latency-bound launches that leaves most of the chip idle, and its host thread spends its time waiting for token ids).  vLLM's
         # engine overlaps its input processing with decoding in the same way.  TD_PRECOMPUTE_PREFETCH=0: one after the other (A/B).
-        chunks = [range(c0, min(c0 + self.decode_batch, n)) for c0 in range(0, n, self.decode_batch)]
+        per = max(1, self.decode_batch // self.mllama_sampling_params.width)      # (n / best_of: a request takes `width` cache slots; output 0 is used, as the reference does with vLLM)
+        chunks = [range(c0, min(c0 + per, n)) for c0 in range(0, n, per)]
         prefetch = len(chunks) > 1 and os.environ.get("TD_PRECOMPUTE_PREFETCH", "1") != "0"
         pool = ThreadPoolExecutor(max_workers=1) if prefetch else None
         # Continuous batching over the whole loader batch (Qwen2VLTextEngine.generate_continuous -- a finished sequence's slot goes to a waiting request

@@ -50,7 +50,7 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         self.mllama_sampling_params = SamplingParams(
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),
             min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True),
-            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs
+            **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
         self.mm_projector = HipVisionProjector(self.config.mm_hidden_size, hidden_size, mm_projector_type, device=device, fp32_norm=True)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, processor
         self.visual, self.image_token_id = visual, image_token_id
@@ -93,9 +93,10 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         reqs = self.resolve_requests(reqs)
         outs = []
         if self.decode_batch > 1 and len(reqs) > 1:
-            for c0 in range(0, len(reqs), self.decode_batch):
-                chunk = reqs[c0:c0 + self.decode_batch]
-                forced = None if forced_output_ids is None else list(forced_output_ids[c0:c0 + self.decode_batch])
+            per = max(1, self.decode_batch // sp.width)      # (n / best_of: a request takes `width` cache slots; output 0 is used, as the reference does with vLLM)
+            for c0 in range(0, len(reqs), per):
+                chunk = reqs[c0:c0 + per]
+                forced = None if forced_output_ids is None else list(forced_output_ids[c0:c0 + per])
                 outs.extend(self.mllama.generate_batch(chunk, sp, generator=generator, forced_output_ids=forced))
         else:
             for i, r in enumerate(reqs):

@@ -58,6 +58,10 @@ class SamplingParams:
     bad_words_token_ids: Optional[List[List[int]]] = None      # vLLM's bad words, already tokenised (string `bad_words` need a tokenizer: not served)
     mask_stop_below_min_tokens: bool = False      # True: vLLM's min_tokens rule (EOS and the stop ids cannot be sampled before min_tokens); False: they are sampled and only do not stop
     logprobs: Optional[int] = None
+    # parallel sampling: the request is prefilled once and runs as k = best_of or n sequences on forked cache slots (td_qwen2_fork_slot); n of them are
+    # returned, the most probable n by cumulative logprob when best_of > n
+    n: int = 1
+    best_of: Optional[int] = None
 
     def validate(self) -> "SamplingParams":
         """vLLM's ranges; a ValueError names the field and the value."""
@@ -87,6 +91,10 @@ class SamplingParams:
             for w in self.bad_words_token_ids:
                 if isinstance(w, (str, bytes)) or not hasattr(w, "__len__") or len(w) == 0 or not all(token(t) for t in w):
                     bad("bad_words_token_ids", f"every word must be a non-empty list of token ids >= 0, got {w!r}")
+        if not (isinstance(self.n, numbers.Integral) and not isinstance(self.n, bool) and self.n >= 1):
+            bad("n", "must be an integer >= 1")
+        if self.best_of is not None and not (isinstance(self.best_of, numbers.Integral) and not isinstance(self.best_of, bool) and self.best_of >= self.n):
+            bad("best_of", f"must be None or an integer >= n={self.n}")
         if not isinstance(self.mask_stop_below_min_tokens, bool):
             bad("mask_stop_below_min_tokens", "must be True or False")
         if self.logprobs is not None and not (isinstance(self.logprobs, numbers.Integral) and not isinstance(self.logprobs, bool)
@@ -124,7 +132,22 @@ class SamplingParams:
     @property
     def per_request(self) -> bool:
         """True when a field td_sample_top_p_bf16 does not serve is set."""
-        return self.top_k > 0 or self.min_p > 0.0 or self.has_penalty or self.seed is not None or self.has_edit
+        return self.top_k > 0 or self.min_p > 0.0 or self.has_penalty or self.seed is not None or self.has_edit or self.width > 1
+
+    @property
+    def width(self) -> int:
+        """k: the sequences the request runs as (best_of, or n), each on a cache slot of its own."""
+        return int(self.n if self.best_of is None else self.best_of)
+
+    def children(self) -> List["SamplingParams"]:
+        """The SamplingParams of the k sequences of a request with k > 1 ([self] otherwise).  Child i of a request with seed s draws from
+        (s + i, its own token count, 0) -- vLLM V1's child seeds -- and unseeded children draw like any other unseeded live rows.  With best_of > n every
+        child is scored (logprobs = 0: the chosen token only) unless the request asked for more."""
+        k = self.width
+        if k == 1:
+            return [self]
+        lp = self.logprobs if self.logprobs is not None else (0 if k > self.n else None)
+        return [dataclasses.replace(self, n=1, best_of=None, seed=None if self.seed is None else int(self.seed) + i, logprobs=lp) for i in range(k)]
 
     @property
     def has_edit(self) -> bool:
@@ -136,18 +159,19 @@ class SamplingParams:
 
 SAMPLER_CONFIG_KEYS = ("top_k", "min_p", "repetition_penalty", "presence_penalty", "frequency_penalty", "seed")
 LOGIT_EDIT_CONFIG_KEYS = ("logit_bias", "allowed_token_ids", "bad_words_token_ids", "mask_stop_below_min_tokens", "logprobs")
+PARALLEL_CONFIG_KEYS = ("n", "best_of")
 # vllm.SamplingParams keys the engine does not serve: a vllm_config that sets one is refused, never ignored
 UNSERVED_CONFIG_KEYS = {"prompt_logprobs": "prompt_logprobs is not served by the HIP engine (logprobs of generated or forced tokens are: `logprobs`)",
                         "bad_words": "string bad_words need a tokenizer, which the engine does not hold: pass the words as token ids in bad_words_token_ids"}
 
 
 def sampler_fields_from_vllm_config(vc) -> dict:
-    """The per-request sampler, logit-edit and logprobs fields a vllm_config sets, under SamplingParams' names; absent keys (and None) keep the
+    """The per-request sampler, logit-edit, logprobs and parallel-sampling fields a vllm_config sets, under SamplingParams' names; absent keys (and None) keep the
     defaults.  A key of UNSERVED_CONFIG_KEYS that is set raises a ValueError saying what to use instead."""
     for k, why in UNSERVED_CONFIG_KEYS.items():
         if vc.get(k) is not None:
             raise ValueError(f"vllm_config {k}={vc[k]!r}: {why}")
-    return {k: vc[k] for k in SAMPLER_CONFIG_KEYS + LOGIT_EDIT_CONFIG_KEYS if vc.get(k) is not None}
+    return {k: vc[k] for k in SAMPLER_CONFIG_KEYS + LOGIT_EDIT_CONFIG_KEYS + PARALLEL_CONFIG_KEYS if vc.get(k) is not None}
 
 
 Logprob = collections.namedtuple("Logprob", ["logprob", "rank"])      # vLLM's Logprob, without the decoded text
@@ -235,6 +259,35 @@ def _sampling_list(sampling, n, what):
             raise ValueError(f"{what}: sampling must be a SamplingParams or a sequence of them, got {type(sp).__name__}")
         sp.validate()
     return sps, True
+
+
+def _gather_outputs(seq_res, req_sps):
+    """Per-sequence results (k_i = width consecutive entries per request) -> one dict per request.  A request with k = 1 keeps its dict as it is.
+    With k > 1 the n returned children -- all of them in child order, or with best_of > n the n highest cumulative logprobs in descending order,
+    ties by child index (vLLM V0's rule) -- become "outputs": dicts with "index", "token_ids", "hidden_states", "cumulative_logprob" when the
+    children were scored or logprobs were asked, and "logprobs" only when asked; the generate()-style keys describe output 0 and
+    "prompt_hidden_states" is the one shared prefill's."""
+    out, s0 = [], 0
+    for sp in req_sps:
+        k = sp.width
+        kids, s0 = seq_res[s0:s0 + k], s0 + k
+        if k == 1:
+            out.append(kids[0])
+            continue
+        order = sorted(range(k), key=lambda j: (-kids[j]["cumulative_logprob"], j))[:sp.n] if k > sp.n else list(range(k))
+        outs = []
+        for idx, j in enumerate(order):
+            o = {"index": idx, "token_ids": kids[j]["token_ids"], "hidden_states": kids[j]["hidden_states"]}
+            if "cumulative_logprob" in kids[j]:
+                o["cumulative_logprob"] = kids[j]["cumulative_logprob"]
+            if sp.logprobs is not None:
+                o["logprobs"] = kids[j]["logprobs"]
+            outs.append(o)
+        r = {"prompt_hidden_states": kids[0]["prompt_hidden_states"]}
+        r.update({key: v for key, v in outs[0].items() if key != "index"})
+        r["outputs"] = outs
+        out.append(r)
+    return out
 
 
 class _RowSampling:
@@ -646,6 +699,15 @@ class Qwen2VLTextEngine:
         sps, by_rows = _sampling_list(sampling, 1, "generate")
         if sps is not None:
             sampling = sps[0]
+        if sampling.width > 1:      # n / best_of: one prefill, k sequences on forked slots -- the batch path runs them
+            if forced_output_ids is not None:
+                raise ValueError(f"generate: forced_output_ids with SamplingParams n={sampling.n}, best_of={sampling.best_of}: a teacher-forced "
+                                 "continuation is one sequence")
+            if getattr(self, "n_slots", 1) < sampling.width:
+                raise _hip.ThinkDiffHipError(f"generate: SamplingParams n={sampling.n}, best_of={sampling.best_of} needs {sampling.width} cache slots, "
+                                             f"n_slots={getattr(self, 'n_slots', 1)}; call set_slots first")
+            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds}], sampling,
+                                       eos_token_id=eos_token_id, generator=generator)[0]
         n_p = len(prompt_token_ids)
         pos = self.text_position_ids(n_p) if position_ids is None else position_ids
         next_pos = int(pos.max()) + 1      # M-RoPE: generation continues one past the largest prompt position
@@ -715,6 +777,12 @@ class Qwen2VLTextEngine:
             sps = [sampling] * B
         if B > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
             raise _hip.ThinkDiffHipError(f"generate_batch: {B} requests exceed min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
+        fan = any(sp.width > 1 for sp in sps)      # n / best_of: request b runs as sps[b].width sequences, each on a cache slot of its own
+        if fan and forced_output_ids is not None:
+            raise ValueError("generate_batch: forced_output_ids with SamplingParams n / best_of > 1: a teacher-forced continuation is one sequence")
+        if fan and sum(sp.width for sp in sps) > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
+            raise _hip.ThinkDiffHipError(f"generate_batch: the requests' n / best_of add up to {sum(sp.width for sp in sps)} sequences, which exceed "
+                                         f"min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
         res = [{"prompt_hidden_states": None, "hidden_states": [], "token_ids": []} for _ in range(B)]
         cache_len = [len(r["prompt_token_ids"]) for r in requests]
         poss = [self.text_position_ids(n) if r.get("position_ids") is None else r["position_ids"] for r, n in zip(requests, cache_len)]
@@ -781,15 +849,34 @@ class Qwen2VLTextEngine:
                 res[b]["prompt_hidden_states"] = hid
                 rows.append(lg)
             logits = torch.stack(rows)              # [B, vocab], row i belongs to the sequence in slot i
+        req_sps, seq_slot = sps, list(range(B))
+        if fan:
+            # Request b was prefilled once, into slot b; its other children take the slots from B up and start from a copy of its cache rows (one
+            # launch per request, td_qwen2_fork_slot) and of its row of prefill logits.  From here on the loop runs SEQUENCES: B, sps, res, cache_len
+            # and next_pos are per sequence, and _gather_outputs hands them back to their requests.
+            seq_req = [b for b in range(B) for _ in range(sps[b].width)]
+            seq_slot, free = [], B
+            for b in range(B):
+                kids = list(range(free, free + sps[b].width - 1))
+                free += len(kids)
+                seq_slot += [b] + kids
+                if kids:
+                    self._fork_slots(b, kids, cache_len[b])
+            logits = logits.index_select(0, torch.tensor(seq_req, dtype=torch.int64).to(logits.device))
+            res = [{"prompt_hidden_states": res[b]["prompt_hidden_states"], "hidden_states": [], "token_ids": []} for b in seq_req]
+            requests = [requests[b] for b in seq_req]
+            cache_len, next_pos = [cache_len[b] for b in seq_req], [next_pos[b] for b in seq_req]
+            sps = [c for sp in sps for c in sp.children()]
+            B = len(sps)
         owner = list(range(B))                      # live row -> request index
-        slots = list(range(B))                      # live row -> cache slot (a finished sequence just leaves the lists: no cache rows move)
+        slots = list(seq_slot)                      # live row -> cache slot (a finished sequence just leaves the lists: no cache rows move)
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
         stops = [set(sp.stop_token_ids or []) for sp in sps]      # per request, like max_tokens / min_tokens / ignore_eos below
         rows_s = None
         if by_rows and forced_output_ids is None:
             rows_s = _RowSampling(self, key, eos_token_id)
             for b in range(B):
-                rows_s.admit(b, sps[b], requests[b]["prompt_token_ids"])
+                rows_s.admit(seq_slot[b], sps[b], requests[b]["prompt_token_ids"])
             live_changed = True
         lplog = _LogprobLog(self, [sp.logprobs for sp in sps]) if _LogprobLog.wanted(sps) else None
         step = 0
@@ -800,7 +887,7 @@ class Qwen2VLTextEngine:
         eos_on = [(not sp.ignore_eos) and eos_token_id is not None for sp in sps]
         owner = [b for b in owner if sps[b].max_tokens > 0]
         if len(owner) < B:
-            slots = list(owner)
+            slots = [seq_slot[b] for b in owner]
             cache_len, next_pos = [cache_len[b] for b in owner], [next_pos[b] for b in owner]
             logits = logits[owner]
         while owner:
@@ -864,7 +951,7 @@ class Qwen2VLTextEngine:
             r["hidden_states"] = parts[b] if base and rows[b] else torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
         if lplog is not None:
             lplog.finish(res)
-        return res
+        return _gather_outputs(res, req_sps) if fan else res
 
     @torch.no_grad()
     def generate_continuous(self, request_chunks, sampling: SamplingParams, eos_token_id: Optional[int] = None,
@@ -892,6 +979,26 @@ class Qwen2VLTextEngine:
         else:
             n_known = None      # chunks pulled lazily: a per-request list is checked against each chunk as it arrives
         sps_all, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
+        # n / best_of: request i runs as k_of(i) SEQUENCES, numbered base_of(i) .. in arrival order of their requests (known in advance: one
+        # SamplingParams per request, or one for all).  The live rows, `res` and the logprob log are per sequence; the waiting queue and `requests`
+        # per request.  Without n / best_of a sequence IS its request and nothing below differs from the single-sequence scheduler.
+        fan = sampling.width > 1 if sps_all is None else any(sp.width > 1 for sp in sps_all)
+        if fan and forced_output_ids is not None:
+            raise ValueError("generate_continuous: forced_output_ids with SamplingParams n / best_of > 1: a teacher-forced continuation is one sequence")
+        if fan:
+            for sp in ([sampling] if sps_all is None else sps_all):
+                if sp.width > max_live:
+                    raise _hip.ThinkDiffHipError(f"generate_continuous: SamplingParams n={sp.n}, best_of={sp.best_of} needs {sp.width} cache slots at "
+                                                 f"once, max_live={max_live}")
+            if sps_all is None:
+                kids1 = sampling.children()
+                k_of, base_of, seq_sp = (lambda i: len(kids1)), (lambda i: i * len(kids1)), (lambda s: kids1[s % len(kids1)])
+            else:
+                bases = np.concatenate([[0], np.cumsum([sp.width for sp in sps_all])]).tolist()
+                seq_sps = [c for sp in sps_all for c in sp.children()]
+                k_of, base_of, seq_sp = (lambda i: bases[i + 1] - bases[i]), (lambda i: bases[i]), (lambda s: seq_sps[s])
+        else:
+            k_of, base_of = (lambda i: 1), (lambda i: i)
         chunk_it = iter(request_chunks)
         D, V = self.config.hidden_size, self.config.vocab_size
         requests, res, waiting = [], [], deque()
@@ -908,11 +1015,12 @@ class Qwen2VLTextEngine:
                 n = len(r["prompt_token_ids"])
                 if n < 1 or n > min(self.slot_len, self.prefill_rows):
                     raise _hip.ThinkDiffHipError(f"generate_continuous: a prompt of {n} tokens does not fit a slot ({self.slot_len}) / a prefill pass ({self.prefill_rows})")
-                if sps_all is not None and len(requests) >= len(sps_all):
-                    raise ValueError(f"generate_continuous: {len(sps_all)} SamplingParams for more than {len(sps_all)} requests: pass one SamplingParams, or exactly one per request")
+                if sps_req is not None and len(requests) >= len(sps_req):
+                    raise ValueError(f"generate_continuous: {len(sps_req)} SamplingParams for more than {len(sps_req)} requests: pass one SamplingParams, or exactly one per request")
                 waiting.append(len(requests))
                 requests.append(r)
-                res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
+                for _ in range(k_of(len(requests) - 1)):
+                    res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
 
         # per live row (numpy, rows [0, n)): request, cache slot, cached tokens, next position id, tokens generated, token budget.  The per-step
         # bookkeeping is vectorised and the arrays are handed to the C ABI as they are: at 256 sequences the Python-list form cost ~2 ms of host
@@ -923,8 +1031,12 @@ class Qwen2VLTextEngine:
         logits = torch.empty(max_live, V, dtype=torch.bfloat16, device=self.device)      # row i = the next-token logits of live row i
         key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
 
-        def sp_of(i):       # the SamplingParams of request i
-            return sampling if sps_all is None else sps_all[i]
+        def sp_of(i):       # the SamplingParams of sequence i
+            return seq_sp(i) if fan else sampling if sps_all is None else sps_all[i]
+
+        sps_req = sps_all      # per request
+        if fan and sps_all is not None:
+            sps_all = seq_sps      # (per sequence from here on: the stop rules and the logprob log index it by live row owner)
 
         if sps_all is None:
             stops = np.array(sorted(set(sampling.stop_token_ids or [])), dtype=np.int64)
@@ -936,7 +1048,8 @@ class Qwen2VLTextEngine:
             mint = np.zeros(max_live, dtype=np.int32)
         rows_s = _RowSampling(self, key, eos_token_id) if by_rows and forced_output_ids is None else None
         if sps_all is None:
-            lplog = _LogprobLog(self, sampling.logprobs) if sampling.logprobs is not None else None
+            lp1 = sp_of(0).logprobs      # (with best_of > n the children are scored though nobody asked)
+            lplog = _LogprobLog(self, lp1) if lp1 is not None else None
         else:
             lplog = _LogprobLog(self, [sp.logprobs for sp in sps_all]) if _LogprobLog.wanted(sps_all) else None
         live_changed = True
@@ -945,8 +1058,18 @@ class Qwen2VLTextEngine:
         slot_len, min_tok = self.slot_len, (sampling.min_tokens if sps_all is None else None)
         vp = ctypes.c_void_p
 
-        def budget(i):      # tokens request i may still produce
-            return len(forced_output_ids[i]) if forced_output_ids is not None else sp_of(i).max_tokens
+        def budget(i):      # tokens (each sequence of) request i may still produce
+            return len(forced_output_ids[i]) if forced_output_ids is not None else sp_of(base_of(i)).max_tokens
+
+        def fits(free):     # -> (requests, cache slots) of the head of the queue that `free` slots take, in arrival order: nobody overtakes a request that waits for k slots
+            if not fan:
+                return min(free, len(waiting)), min(free, len(waiting))
+            nreq = used = 0
+            for i in waiting:
+                if used + k_of(i) > free:
+                    break
+                nreq, used = nreq + 1, used + k_of(i)
+            return nreq, used
 
         while True:
             free = max_live - n
@@ -954,20 +1077,22 @@ class Qwen2VLTextEngine:
                 pull()
                 continue
             # ---- admission: one packed prefill pass into free slots ----
-            if waiting and free > 0 and (n == 0 or min(free, len(waiting)) >= admit_min or (exhausted and free >= len(waiting))):
-                new, rows = [], 0
-                while waiting and len(new) < free and rows + len(requests[waiting[0]]["prompt_token_ids"]) <= self.prefill_rows:
+            fit, fit_slots = fits(free)
+            if fit > 0 and (n == 0 or fit_slots >= admit_min or (exhausted and fit >= len(waiting))):
+                new, rows, used = [], 0, 0
+                while waiting and used + k_of(waiting[0]) <= free and rows + len(requests[waiting[0]]["prompt_token_ids"]) <= self.prefill_rows:
                     i = waiting.popleft()
                     if budget(i) <= 0:      # nothing to generate: the prompt states only, through the first free slot
                         q = requests[i]
                         m = len(q["prompt_token_ids"])
                         e = q.get("inputs_embeds")
-                        res[i]["prompt_hidden_states"], _ = self.forward(
+                        res[base_of(i)]["prompt_hidden_states"], _ = self.forward(
                             self.text_position_ids(m) if q.get("position_ids") is None else q["position_ids"],
                             torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, False, slot=free_slots[-1])
                         continue
                     new.append(i)
                     rows += len(requests[i]["prompt_token_ids"])
+                    used += k_of(i)
                 if new:
                     k = len(new)
                     emb = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
@@ -991,18 +1116,34 @@ class Qwen2VLTextEngine:
                     self._prefill_packed_slots(k, sl, emb, pos, cl, hid, logits[n:n + k])
                     r0 = 0
                     for i, m in zip(new, lens):
-                        res[i]["prompt_hidden_states"] = hid[r0:r0 + m]
+                        res[base_of(i)]["prompt_hidden_states"] = hid[r0:r0 + m]
                         r0 += m
+                    if used > k:
+                        # children: the cache rows of each prompt forked to k_of - 1 more free slots (one launch per request, td_qwen2_fork_slot) and its
+                        # row of prefill logits copied to their live rows; the rows of this admission become its sequences, in request order
+                        rep, seqs, seq_slots = [], [], []
+                        for j, i in enumerate(new):
+                            kids = [free_slots.pop() for _ in range(k_of(i) - 1)]
+                            if kids:
+                                self._fork_slots(new_slots[j], kids, lens[j])
+                            rep += [j] * k_of(i)
+                            seqs += range(base_of(i), base_of(i) + k_of(i))
+                            seq_slots += [new_slots[j]] + kids
+                        logits[n:n + used] = logits[n:n + k].index_select(0, torch.tensor(rep, dtype=torch.int64).to(logits.device))
+                        npos[n:n + used] = npos[n:n + k][rep]
+                        parents, new, new_slots, lens, k = [new[j] for j in rep], seqs, seq_slots, [lens[j] for j in rep], used
+                    else:
+                        parents, new = new, [base_of(i) for i in new]      # (a request is its sequence unless another request of the call has children)
                     own[n:n + k] = new
                     slt[n:n + k] = new_slots
                     clen[n:n + k] = lens
                     ngen[n:n + k] = 0
-                    lim[n:n + k] = [budget(i) for i in new]
+                    lim[n:n + k] = [budget(i) for i in parents]
                     if sps_all is not None:
                         mint[n:n + k] = [sps_all[i].min_tokens for i in new]
                     if rows_s is not None:      # a request admitted into a slot starts that slot's history over
-                        for i, sl in zip(new, new_slots):
-                            rows_s.admit(sl, sp_of(i), requests[i]["prompt_token_ids"])
+                        for i, p, sl in zip(new, parents, new_slots):
+                            rows_s.admit(sl, sp_of(i), requests[p]["prompt_token_ids"])
                     live_changed = True
                     n += k
                     continue      # (more may fit in another pass before the next decode step)
@@ -1057,7 +1198,7 @@ class Qwen2VLTextEngine:
                     logits[:k] = logits[:n].index_select(0, torch.from_numpy(keep).to(self.device))
                 n = k
             gstep += 1
-        N = len(requests)
+        N = len(res)
         if step_owner:
             owners_all = np.concatenate(step_owner)
             order = np.argsort(owners_all, kind="stable")      # rows grouped by request, in step order inside a request
@@ -1074,9 +1215,11 @@ class Qwen2VLTextEngine:
                 r["hidden_states"] = torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
         if lplog is not None:
             lplog.finish(res)
+        if fan:
+            res = _gather_outputs(res, [sampling] * len(requests) if sps_req is None else sps_req[:len(requests)])
         return res
 
-    # the two engine calls of generate_continuous (separate methods so that the scheduler's host logic can be exercised against a stand-in engine)
+    # the engine calls of generate_continuous (separate methods so that the scheduler's host logic can be exercised against a stand-in engine)
     def _prefill_packed_slots(self, k, slots_c, emb, pos, lens_c, hid_out, logits_out):
         _hip.check(self._L.td_qwen2_prefill_packed_slots(self._h, k, ctypes.cast(slots_c, ctypes.c_void_p), None, _hip.ptr(emb), _hip.ptr(pos),
                                                          ctypes.cast(lens_c, ctypes.c_void_p), _hip.ptr(hid_out), _hip.ptr(logits_out), _hip.stream_ptr()))
@@ -1084,6 +1227,17 @@ class Qwen2VLTextEngine:
     def _decode_slots(self, n, slots_np, tok_dev, pos_dev, cache_np, hid_out, logits_out):
         _hip.check(self._L.td_qwen2_decode_batch_slots(self._h, n, ctypes.c_void_p(slots_np.ctypes.data), _hip.ptr(tok_dev), _hip.ptr(pos_dev),
                                                        ctypes.c_void_p(cache_np.ctypes.data), _hip.ptr(hid_out), _hip.ptr(logits_out), _hip.stream_ptr()))
+
+    def _fork_slots(self, src, dst_slots, length):
+        """The fork of n / best_of admission: the `length` prompt rows of slot `src` to every slot of dst_slots (a method of its own beside the two
+        above, for the same reason)."""
+        self.fork_slot(src, dst_slots, length)
+
+    def fork_slot(self, src: int, dst_slots: Sequence[int], length: int):
+        """Copy the first `length` cache rows of slot `src` to every slot of `dst_slots` in ONE launch over all layers (td_qwen2_fork_slot: each source
+        chunk is read once and written len(dst_slots) times): the sequences in those slots then continue from the same prefill."""
+        dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
+        _hip.check(self._L.td_qwen2_fork_slot(self._h, int(src), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(length), _hip.stream_ptr()))
 
     def move_slot(self, src: int, dst: int, length: int):
         """Copy the first `length` cache rows of slot `src` to slot `dst` (td_qwen2_move_slot).  The decode steps name their slots, so nothing in this

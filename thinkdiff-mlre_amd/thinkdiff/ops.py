@@ -55,6 +55,8 @@ quant_weight_rows_e4m3 / linear_w8   weight-only fp8 of an nn.Linear (vLLM's `qu
                            output row (bytes, scales and the dequantised bf16 weight, which is exact), and the Linear of up to 64 rows that streams the bytes
 kv_quant_rows_e4m3 / kv_dequant_rows_e4m3 / attention_decode_kv8   the e4m3 KV cache of the LVLM's decode engine (vLLM's `kv_cache_dtype="fp8"`): e4m3 bytes with one
                            power-of-two scale per 128-wide head vector of a cache row, back to bf16 (exact), and the decode attention that reads bytes + scales
+kv_fork_rows               the first n_rows rows of one slot of a cache plane copied to many slots in one launch, each source chunk loaded once (what vLLM's
+                           `n` / `best_of` share through block tables is a copy here: the slots are a fixed partition); in place, any dtype
 """
 import os
 
@@ -115,6 +117,7 @@ SCHEMAS = {
     "kv_quant_rows_e4m3": "(Tensor kv, int heads) -> (Tensor, Tensor, Tensor)",
     "kv_dequant_rows_e4m3": "(Tensor q, Tensor scale) -> Tensor",
     "attention_decode_kv8": "(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor",
+    "kv_fork_rows": "(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()",
 }
 
 _loaded = False
