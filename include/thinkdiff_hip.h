@@ -113,6 +113,14 @@ int td_attention_bf16(const void* q, int64_t ldq, int64_t q_bstride, const void*
  * DEVICE int32[n_seg + 1]; max_len = the longest segment (sizes the grid).  One launch for all segments, no mask across them. */
 int td_attention_varlen_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo,
                              const int* seg_starts, int n_seg, int max_len, int Hq, int Hkv, float scale, void* stream);
+/* The packed form with a causal switch (td_abi_version() >= 17).  causal = 1: query row i of a segment sees the segment's rows j <= i -- the launch of
+ * the Qwen2-VL engine's packed prefill (td_qwen2_prefill_packed: prompts back to back, no padding rows), parameters filled as the engine fills them.
+ * causal = 0: td_attention_varlen_bf16 bit for bit.  max_len may exceed the longest segment (it only sizes the grid); max_len = 1 (every segment
+ * one row) runs the same kernel.  TD_ERR_INVALID before any HIP call for: an empty segment list, a null operand, causal outside {0, 1},
+ * Hq % Hkv != 0, a row stride shorter than its heads, ldq or ldkv not a multiple of 8 elements (16 bytes), ldo not a multiple of 4 (8 bytes),
+ * q / k / v / o not 16-byte aligned, seg_starts not 4-byte aligned. */
+int td_attention_segments_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo,
+                               const int* seg_starts, int n_seg, int max_len, int Hq, int Hkv, float scale, int causal, void* stream);
 /* The joint attention in the form the FLUX engine calls it: q already carries scale x log2(e) (folded in where RoPE rounds q to bf16), so the
  * scores arrive in the exp2 domain; one batch entry, Hq == Hkv = H, head_dim 128.  score_bound in (0, 48]: a bound of |q'.k| (log2 units) the
  * caller vouches for -- the scores are then exponentiated as they are: no reference point, no per-tile row maximum, no rescale (a bf16 probability
@@ -823,7 +831,9 @@ int td_groupnorm_nhwc_bf16(const void* x, void* y, int P, int C, int groups, flo
                            const void* beta, int silu, float* workspace, void* stream);
 int td_groupnorm_workspace_floats(void);
 /* p[rows,cols] (bf16) = softmax(scale * s[rows,cols]) (fp32 in). */
-/* (s 16-byte, p 8-byte aligned, neither NULL: the kernel's vector accesses need it; refused with TD_ERR_INVALID otherwise) */
+/* (s 16-byte, p 8-byte aligned, neither NULL: the kernel's vector accesses need it; refused with TD_ERR_INVALID otherwise)
+ * scale must be finite and > 0 (td_abi_version() >= 17: TD_ERR_INVALID otherwise): the row maximum is taken over the unscaled scores, which is the
+ * maximum of scale * s only for a positive scale. */
 int td_softmax_rows_f32_bf16(const float* s, void* p, int rows, int cols, float scale, void* stream);
 /* ... with rows `ld` elements apart in both matrices (ld >= cols, ld % 4 == 0): softmax over the first `cols` columns of each row, the pad
  * columns [cols, ld) of s never read and those of p written as exact zeros (the VAE mid-block attention's key-axis pad). */

@@ -398,6 +398,36 @@ def test_full_width_qwen2_7b_layers_wide_decode(hip, B):
     assert all(o["hidden_states"].shape == (k, 3584) and torch.isfinite(o["hidden_states"].float()).all() for o in many)
 
 
+def test_packed_prefill_of_one_token_prompts(hip):
+    """A packed pass in which EVERY prompt has one token (max_len = 1): its causal attention launch has the shape of a decode step and used to be
+    routed to the decode kernel, which knows no packed segments -- every prompt but the first got stale attention rows.  Prompt states, teacher-forced
+    decode states against one request at a time, the bar of test_packed_prefill_equals_padded_and_single.  Measured on MI355X: rel-RMSE of the
+    second prompt's states 0.53 before the routing fix in td_attn_launch, at most 0.0023 after."""
+    from thinkdiff.models.qwen2_vl import Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams
+    cfg = Q.tiny_config()
+    sd = Q.init_weights(cfg, seed=17)
+    tc = Qwen2VLTextConfig(hidden_size=cfg.hidden, num_hidden_layers=cfg.num_layers, num_attention_heads=cfg.num_heads, num_key_value_heads=cfg.num_kv_heads,
+                           intermediate_size=cfg.intermediate, vocab_size=cfg.vocab, tie_word_embeddings=cfg.tie_embeddings)
+    g = torch.Generator().manual_seed(5)
+    n = 5
+    reqs = [{"prompt_token_ids": torch.randint(0, cfg.vocab, (1,), generator=g).tolist()} for _ in range(n)]
+    forced = [torch.randint(0, cfg.vocab, (3,), generator=g).tolist() for _ in range(n)]
+    sp = SamplingParams(max_tokens=3, min_tokens=3, ignore_eos=True)
+    e = Qwen2VLTextEngine(tc, max_model_len=128, n_slots=n, prefill_rows=128)
+    e.load_state_dict(sd)
+    assert e.packed_prefill
+    packed = e.generate_batch([dict(r) for r in reqs], sp, forced_output_ids=forced)
+    packed = [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in o.items()} for o in packed]
+    e.set_slots(1)
+    for i, (r, f, c) in enumerate(zip(reqs, forced, packed)):
+        a = e.generate(r["prompt_token_ids"], sp, forced_output_ids=f)
+        torch.cuda.synchronize()
+        assert c["prompt_hidden_states"].shape == (1, cfg.hidden) and torch.isfinite(c["prompt_hidden_states"].float()).all()
+        e1, e2 = _rel(c["prompt_hidden_states"], a["prompt_hidden_states"]), _rel(c["hidden_states"], a["hidden_states"])
+        print(f"one-token prompt {i}: packed vs single rel-RMSE prompt {e1:.5f} decode {e2:.5f}")
+        assert e1 < 5e-3 and e2 < 5e-3, i
+
+
 def test_packed_prefill_equals_padded_and_single(hip):
     """td_qwen2_prefill_packed (prompts back to back, causal attention per packed segment, k|v rows scattered to their slots) against the right-padded
     batched prefill and against one request at a time: prompt states, first sampled logits (through greedy continuation) and the cache (through

@@ -310,3 +310,126 @@ def test_qwen2_preprocessing_on_device_equals_the_image_processor(hip):
     # a processor of any other kind is called as is
     f.image_processor = lambda images, return_tensors="pt": want
     assert f._preprocess_on_device(imgs) is None
+
+
+# ---- the towers' row kernels at their edges, each against a plain reference ------------------------------------------------------------------------
+
+def _bf16_ulp(r):
+    """One bf16 ulp at |r| (float64)."""
+    return torch.exp2(torch.floor(torch.log2(r.abs().clamp_min(2.0 ** -126))) - 7)
+
+
+@pytest.mark.parametrize("H", [1, 6])
+@pytest.mark.parametrize("S", [1, 37, 300])
+@pytest.mark.parametrize("hd", [64, 80, 128])
+def test_rope_half_against_float64(hip, hd, S, H):
+    """td_rope_half_bf16 on heads 128 columns apart inside rows with 64 pad columns, against float64 of the same bf16 inputs and fp32 tables.
+    Bound per element: 1 bf16 ulp of the reference (one rounding of an fp32 value that lies within a few fp32 ulps of the exact one), as it is, on
+    every element whose two products do not cancel (|ref| >= 2^-12 (|x cos| + |y sin|): more than 99.9 % of them).  On the cancelling rest the
+    fp32 evaluation error of the two-product sum, 2^-23 (|x cos| + |y sin|), is added: the result has lost 12 bits or more, and no fp32 kernel
+    can be within a bf16 ulp of a float64 result that small.  Columns [hd, 128) of every head and the pad columns keep their bits."""
+    from thinkdiff import _hip
+    g = torch.Generator().manual_seed(hd * 1000 + S * 10 + H)
+    x = torch.randn(S, H * 128 + 64, generator=g).bfloat16()
+    ang = torch.rand(S, hd // 2, generator=g) * 6.2831853
+    cos, sin = ang.cos().contiguous(), ang.sin().contiguous()
+    y = x.cuda()
+    _hip.rope_half(y, H, hd, cos.cuda(), sin.cuda())
+    torch.cuda.synchronize()
+    y = y.cpu()
+    assert torch.equal(y[:, H * 128:].view(torch.int16), x[:, H * 128:].view(torch.int16)), "pad columns changed"
+    xv, yv = x[:, :H * 128].reshape(S, H, 128), y[:, :H * 128].reshape(S, H, 128)
+    assert torch.equal(yv[..., hd:].view(torch.int16), xv[..., hd:].view(torch.int16)), "columns [hd, 128) of a head changed"
+    a, b = xv[..., :hd // 2].double(), xv[..., hd // 2:hd].double()
+    c, s = cos.double()[:, None], sin.double()[:, None]
+    ref = torch.cat([a * c - b * s, b * c + a * s], dim=-1)
+    mag = torch.cat([(a * c).abs() + (b * s).abs(), (b * c).abs() + (a * s).abs()], dim=-1)
+    err = (yv[..., :hd].double() - ref).abs()
+    plain = ref.abs() >= 2.0 ** -12 * mag                      # no cancellation to speak of: the issue's bound, 1 bf16 ulp, as it is
+    r_plain = float((err / _bf16_ulp(ref))[plain].max())
+    r_rest = float((err / (_bf16_ulp(ref) + 2.0 ** -23 * mag))[~plain].max()) if (~plain).any() else 0.0
+    print(f"rope_half hd={hd} S={S} H={H}: max error {r_plain:.3f} x 1 bf16 ulp on {int(plain.sum())} elements, {r_rest:.3f} x the widened bound on the "
+          f"{int((~plain).sum())} cancelling ones")
+    assert r_plain <= 1.0 and r_rest <= 1.0
+
+
+@pytest.mark.parametrize("hd", [64, 80])
+def test_vision_rope_table_against_float64(hip, hd):
+    """td_vision_rope_table with positions up to 255 on both axes.  Reference: float64 cos / sin of the fp32 angle pos * inv_freq, inv_freq the fp32
+    buffer of VisionRotaryEmbedding(hd / 2), 1 / theta^(arange(0, hd/2, 2) / (hd/2)), with every fp32 step of that formula correctly rounded (the
+    power through float64; a libm powf is good to an ulp or so, which would make the reference itself uncertain by the size of the bound).
+    Bound: 2^-23 max(1, |angle|) plus one fp32 ulp of the result.  Column structure: the first hd/4 columns depend on the patch row alone, the
+    last hd/4 on the patch column alone, through the same function.
+    Measured on MI355X: 0.29 (hd 64) and 0.30 (hd 80) x the bound.  The kernel used to take the power with powf: 1.22 and 1.46 x the bound, against
+    this reference and against torch's own fp32 buffer alike -- one ulp of inv_freq is one ulp of the angle, 3e-5 in cos / sin at position 255."""
+    from thinkdiff import _hip
+    g = torch.Generator().manual_seed(hd)
+    i = torch.arange(256)
+    pos = torch.cat([torch.stack([i, i], 1), torch.stack([i, 255 - i], 1), torch.randint(0, 256, (300, 2), generator=g),
+                     torch.tensor([[0, 255], [255, 0], [255, 255], [0, 0]])]).to(torch.int32)
+    cos, sin = _hip.vision_rope_table(pos.cuda().contiguous(), hd)
+    torch.cuda.synchronize()
+    cos, sin = cos.cpu(), sin.cpu()
+    half, quarter = hd // 2, hd // 4
+    expo = torch.arange(0, half, 2, dtype=torch.float32) / half               # fp32 division: correctly rounded
+    inv = 1.0 / (10000.0 ** expo.double()).float()                            # the power rounded once to fp32, then an fp32 division
+    inv_torch = 1.0 / (10000.0 ** expo)                                        # the module's own buffer: torch's fp32 pow, good to an ulp
+    n_off = int((inv_torch != inv).sum())
+    print(f"vision_rope_table hd={hd}: torch's fp32 inv_freq differs from the correctly rounded one in {n_off} of {inv.numel()} values")
+    assert ((inv_torch.double() - inv.double()).abs() <= 2.0 ** -23 * inv.double()).all()      # the two references agree to an ulp, so parity with the module holds to that
+    ang = (pos.float()[:, :, None] * inv).flatten(1)                          # fp32 [S, hd/2]: row angles | column angles
+    assert expo.dtype == inv.dtype == ang.dtype == torch.float32 and ang.shape == cos.shape
+    worst = 0.0
+    for got, ref in ((cos, ang.double().cos()), (sin, ang.double().sin())):
+        ulp = torch.exp2(torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126))) - 23)
+        tol = 2.0 ** -23 * ang.double().abs().clamp_min(1.0) + ulp
+        worst = max(worst, float(((got.double() - ref).abs() / tol).max()))
+    print(f"vision_rope_table hd={hd}: max error {worst:.3f} x the bound")
+    assert worst <= 1.0
+    for t in (cos, sin):
+        T = t[:256, :quarter]                                                   # rows 0 .. 255 are the positions (i, i)
+        assert torch.equal(t[:256, quarter:], T)
+        assert torch.equal(t[:, :quarter], T[pos[:, 0].long()]) and torch.equal(t[:, quarter:], T[pos[:, 1].long()])
+
+
+@pytest.mark.parametrize("Kpad", [588, 640])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_patchify_drops_the_remainder(hip, dtype, Kpad):
+    """A (3, 30, 45) image with p = 14: the trailing 2 rows and 3 columns are dropped as Conv2d(kernel = stride = 14) drops them; bit-exact
+    against unfold of the cropped image, both source types; the columns [588, Kpad) are zero."""
+    from thinkdiff import _hip
+    g = torch.Generator().manual_seed(45)
+    pix = torch.randn(3, 30, 45, generator=g).to(dtype)
+    out = _hip.patchify(pix.cuda(), 14, Kpad)
+    torch.cuda.synchronize()
+    ref = torch.nn.functional.unfold(pix.float()[None, :, :28, :42], 14, stride=14)[0].T.bfloat16()      # [6, 588], columns (c, iy, ix)
+    assert out.shape == (6, Kpad) and ref.shape == (6, 588)
+    assert torch.equal(out.cpu()[:, :588].view(torch.int16), ref.view(torch.int16)) and not out[:, 588:].any()
+
+
+@pytest.mark.parametrize("K,Kpad", [(1176, 1176), (1176, 1216), (37, 64)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_cast_pad_rows_both_sources(hip, dtype, K, Kpad):
+    from thinkdiff import _hip
+    g = torch.Generator().manual_seed(K + Kpad)
+    src = torch.randn(5, K, generator=g).to(dtype)
+    out = _hip.cast_pad_rows(src.cuda(), Kpad)
+    torch.cuda.synchronize()
+    assert out.shape == (5, Kpad)
+    assert torch.equal(out.cpu()[:, :K].view(torch.int16), src.bfloat16().view(torch.int16)) and not out[:, K:].any()
+
+
+@pytest.mark.parametrize("D", [8, 1408])
+@pytest.mark.parametrize("b_rows", [1, 5, 15])
+def test_add_rows_cyclic_broadcast(hip, b_rows, D):
+    """out[r] = a[r] + b[r % b_rows] for b_rows = 1 (a bias row), 5 (cyclic: 15 rows = 3 periods) and rows; bit-exact against the fp32 add
+    rounded once."""
+    from thinkdiff import _hip
+    rows = 15
+    g = torch.Generator().manual_seed(D + b_rows)
+    a = torch.randn(rows, D, generator=g).bfloat16()
+    b = torch.randn(b_rows, D, generator=g).bfloat16()
+    out = _hip.add_rows(a.cuda(), b.cuda())
+    torch.cuda.synchronize()
+    ref = (a.float() + b.float()[torch.arange(rows) % b_rows]).bfloat16()
+    assert torch.equal(out.cpu().view(torch.int16), ref.view(torch.int16))

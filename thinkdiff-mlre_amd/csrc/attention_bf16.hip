@@ -525,11 +525,14 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
                "td_attention: per-batch operand exceeds the 4 GiB buffer-descriptor range");
   TD_CHECK_ARG(((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V | (uintptr_t)p.O) % 16 == 0, "td_attention: pointers must be 16-byte aligned");
   if (p.K8) {      // an e4m3 KV cache (TdAttnParams::K8): the decode kernel's 8-bit form, there is no tile kernel that reads it
-    TD_CHECK_ARG(p.Sq == 1 && p.causal && !p.bias && (p.kv_lens || p.causal_offset == p.Skv - 1), "td_attention: an e4m3 KV cache is read by the decode form only (Sq = 1, causal, no bias)");
+    TD_CHECK_ARG(p.Sq == 1 && p.causal && !p.bias && !p.seg_starts && (p.kv_lens || p.causal_offset == p.Skv - 1),
+                 "td_attention: an e4m3 KV cache is read by the decode form only (Sq = 1, causal, no bias, no packed segments)");
     return td_attn_decode_launch(p, stream);
   }
-  // one query token per sequence against its KV cache: the dedicated decode kernel (keys split over lanes, GQA group shares K/V)
-  if (p.Sq == 1 && p.causal && !p.bias && (p.variant & 0xff) == 0 && (p.kv_lens || p.causal_offset == p.Skv - 1))
+  // one query token per sequence against its KV cache: the dedicated decode kernel (keys split over lanes, GQA group shares K/V).  Never a packed
+  // launch: the decode kernel knows no seg_starts (it steps by the batch strides, which a packed launch leaves 0), so packed one-row segments
+  // (max_len = 1: a pass of one-token prompts) stay on the tile kernel below
+  if (p.Sq == 1 && p.causal && !p.bias && !p.seg_starts && (p.variant & 0xff) == 0 && (p.kv_lens || p.causal_offset == p.Skv - 1))
     return td_attn_decode_launch(p, stream);
   TdAttnParams q = p;
   q.q_per_kv = p.Hq / p.Hkv;

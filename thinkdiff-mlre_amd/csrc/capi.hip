@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 16; }    // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 17; }   // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -36,6 +36,8 @@ int td_abi_version(void) { return 16; }    // 2: TdFluxConfig::out_channels appe
                                             // 15: logit edits in the sampler's launch (td_logit_edits_*, td_sample_rows_edit_bf16) and logprobs
                                             //     (td_logprobs_rows_bf16; csrc/logprobs_rows.hip)
                                             // 16: KV fork (td_kv_fork_rows, td_qwen2_fork_slot; csrc/kv_fork.hip)
+                                            // 17: td_attention_segments_bf16 (packed segments with a causal switch: the packed prefill's launch);
+                                            //     td_softmax_rows_* refuse a scale that is not finite and positive
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -187,6 +189,29 @@ int td_attention_varlen_bf16(const void* q, int64_t ldq, const void* k, const vo
   p.batch = n_seg; p.Sq = max_len; p.Skv = max_len; p.Hq = Hq; p.Hkv = Hkv; p.head_dim = 128;
   p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo;
   p.scale = scale; p.causal = 0; p.causal_offset = 0; p.variant = 1; p.seg_starts = seg_starts;
+  return td_attn_launch(p, (hipStream_t)stream);
+}
+
+// td_attention_varlen_bf16 with a causal switch: TdAttnParams as the Qwen2-VL engine's packed prefill fills them (prefill_attn + seg_starts in
+// csrc/qwen2_engine.hip: causal, causal_offset 0), so causal = 1 launches the engine's kernel instantiation.  Every refusal comes before the first HIP call.
+int td_attention_segments_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo,
+                               const int* seg_starts, int n_seg, int max_len, int Hq, int Hkv, float scale, int causal, void* stream) {
+  TD_CHECK_ARG(seg_starts && n_seg > 0 && max_len > 0, "td_attention_segments: empty segment list");
+  TD_CHECK_ARG(q && k && v && o, "td_attention_segments: null operand");
+  TD_CHECK_ARG(causal == 0 || causal == 1, "td_attention_segments: causal=%d must be 0 or 1", causal);
+  TD_CHECK_ARG(Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "td_attention_segments: Hq=%d not a positive multiple of Hkv=%d", Hq, Hkv);
+  TD_CHECK_ARG(ldq >= (int64_t)Hq * 128 && ldkv >= (int64_t)Hkv * 128 && ldo >= (int64_t)Hq * 128 && ldq < (1ll << 31) && ldkv < (1ll << 31) && ldo < (1ll << 31),
+               "td_attention_segments: a row stride (ldq=%lld ldkv=%lld ldo=%lld) is shorter than its heads or outside the 32-bit range", (long long)ldq, (long long)ldkv, (long long)ldo);
+  TD_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0,
+               "td_attention_segments: ldq=%lld and ldkv=%lld must be multiples of 8 elements (16 bytes), ldo=%lld of 4 (8 bytes)", (long long)ldq, (long long)ldkv, (long long)ldo);
+  TD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, "td_attention_segments: q, k, v and o must be 16-byte aligned");
+  TD_CHECK_ARG((uintptr_t)seg_starts % 4 == 0, "td_attention_segments: seg_starts must be 4-byte aligned");
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)o;
+  p.batch = n_seg; p.Sq = max_len; p.Skv = max_len; p.Hq = Hq; p.Hkv = Hkv; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo;
+  p.scale = scale; p.causal = causal; p.causal_offset = 0; p.seg_starts = seg_starts;
+  if (!causal) p.variant = 1;      // as td_attention_varlen_bf16 (the packed launch reads no variant; kept equal so that causal = 0 is that entry bit for bit)
   return td_attn_launch(p, (hipStream_t)stream);
 }
 

@@ -950,7 +950,10 @@ __global__ void td_vision_rope_table_kernel(const int* pos, int S, int hd, float
   if (idx >= S * half) return;
   const int s = idx / half, j = idx % half;
   const int axis = j >= quarter, f = j - axis * quarter;
-  const float inv = 1.0f / powf(theta, (float)(2 * f) / (float)half);
+  // inv_freq = 1 / theta^(2f / half) step by step as the module's fp32 buffer is made, every step correctly rounded: the power is taken in double and
+  // rounded once (powf is good to an ulp or so, and one ulp of inv_freq is one ulp of the ANGLE: 3e-5 in cos / sin at patch position 255)
+  const float p = (float)pow((double)theta, (double)((float)(2 * f) / (float)half));
+  const float inv = 1.0f / p;
   const float a = (float)pos[2 * s + axis] * inv;
   cs[idx] = cosf(a);
   sn[idx] = sinf(a);

@@ -172,6 +172,7 @@ int td_softmax_rows_launch(const float* s, bf16_t* p, int rows, int cols, int ld
   TD_CHECK_ARG(rows > 0 && cols > 0 && cols % 4 == 0, "td_softmax_rows: cols=%d must be a positive multiple of 4", cols);
   TD_CHECK_ARG(ld >= cols && ld % 4 == 0, "td_softmax_rows: row stride %d must be a multiple of 4 and at least cols=%d", ld, cols);
   TD_CHECK_ARG((uintptr_t)s % 16 == 0 && (uintptr_t)p % 8 == 0, "td_softmax_rows: s must be 16-byte and p 8-byte aligned");
+  TD_CHECK_ARG(scale > 0.f && scale <= 3.402823466e38f, "td_softmax_rows: scale=%g must be finite and greater than 0 (the row maximum is taken over the unscaled scores, before the scale)", (double)scale);
   TD_GRID_1D(nblk, (long long)rows * 256, 256, "td_softmax_rows");
   hipLaunchKernelGGL(td_softmax_rows_kernel, dim3(nblk), dim3(256), 0, stream, s, p, cols, ld, scale);
   TD_CHECK_LAUNCH();

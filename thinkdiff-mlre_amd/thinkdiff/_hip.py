@@ -149,6 +149,7 @@ def _declare(L):
         "td_glu_mul_bf16": [vp, vp, i32, i32, i32, vp],
         "td_attention_bias_bf16": [vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp, vp],
         "td_attention_varlen_bf16": [vp, i64, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, vp],
+        "td_attention_segments_bf16": [vp, i64, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, i32, vp],
         "td_rope_half_bf16": [vp, i64, i32, i32, i32, i32, vp, vp, vp],
         "td_vision_rope_table": [vp, i32, i32, f32, vp, vp, vp],
         "td_patchify_bf16": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
@@ -796,6 +797,22 @@ def attention_padded_varlen(qkv, H, scale, seg_starts, max_len, out=None):
     assert seg_starts.dtype == torch.int32 and seg_starts.is_cuda and seg_starts.is_contiguous() and seg_starts.numel() >= 2
     check(lib().td_attention_varlen_bf16(ptr(qkv), _rows(qkv), ptr(qkv[:, W:]), ptr(qkv[:, 2 * W:]), _rows(qkv), ptr(out), W,
                                          ptr(seg_starts), seg_starts.numel() - 1, int(max_len), H, H, float(scale), stream_ptr()))
+    return out
+
+
+def attention_segments(q, k, v, out, Hq, Hkv, seg_starts, max_len, scale=None, causal=False):
+    """td_attention_segments_bf16 on separate operand views: q, out [S, >= Hq*128], k, v [S, >= Hkv*128] (one row stride for both), each with its own
+    row stride; seg_starts device int32 [n_seg + 1] (row offsets, seg_starts[-1] == S); max_len >= the longest segment.  causal: row i of a segment
+    sees the segment's rows j <= i (the Qwen2-VL engine's packed prefill launch); otherwise full attention inside each segment."""
+    for t in (q, k, v, out):
+        assert t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    S = q.shape[0]
+    assert k.stride() == v.stride() and k.shape[0] == S and v.shape[0] == S and out.shape[0] == S
+    assert seg_starts.dtype == torch.int32 and seg_starts.is_cuda and seg_starts.is_contiguous() and seg_starts.numel() >= 2
+    if scale is None:
+        scale = 128 ** -0.5
+    check(lib().td_attention_segments_bf16(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(out), out.stride(0), ptr(seg_starts),
+                                           seg_starts.numel() - 1, int(max_len), Hq, Hkv, float(scale), int(causal), stream_ptr()))
     return out
 
 
