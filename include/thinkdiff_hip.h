@@ -924,6 +924,20 @@ int td_kv_fork_rows(const TdKvPlane* planes, int n_planes, int src_slot, const i
  * `len` cache rows of sequence src to every sequence dst_slots[0 .. n_dst) (HOST ints) -- n sequences continuing from one prefill.  Also refused:
  * a slot outside [0, n_slots), len above the slot capacity.  td_qwen2_move_slot is the one-destination form on hipMemcpyAsync. */
 int td_qwen2_fork_slot(td_qwen2* f, int src, const int* dst_slots, int n_dst, int len, void* stream);
+/* KV gather (td_abi_version() >= 18; csrc/kv_fork.hip): for every row j of 0 .. n with copy_src_dev[j] >= 0, the first n_rows[j] rows of slot
+ * slots[copy_src_dev[j]] copied to the same rows of slot slots[j], on every plane -- the reordering of cache slots behind a beam-search step, whose
+ * sources only the device knows.  slots and n_rows are HOST int arrays of n entries, read before the call returns (they travel in the launches' own
+ * arguments: 64 planes x 64 destination rows per launch, every launch with the whole slot table); copy_src_dev is a DEVICE int32[n] read by the
+ * kernel: -1 (any negative value), j itself or a value >= n copies nothing, and a workgroup of such a row returns at once.  Access widths and the
+ * head / body / tail split are td_kv_fork_rows'.  CONTRACT: the caller vouches that no destination slot (a row with copy_src >= 0) is the source of
+ * another row of the same call -- td_beam_select's placement guarantees it -- and that every slot lies inside its plane.  TD_ERR_INVALID with a
+ * message naming the value, before any HIP call: a NULL planes / slots / copy_src_dev / n_rows / base, n_planes < 1, n outside 1..256, a negative
+ * slot, a slot given twice, n_rows negative or above a plane's slot_rows, row_bytes not a positive multiple of 2, a base that is not 2-byte aligned.
+ * Every n_rows == 0: TD_OK, no launch. */
+int td_kv_gather_rows(const TdKvPlane* planes, int n_planes, int n, const int* slots, const int32_t* copy_src_dev, const int* n_rows, void* stream);
+/* td_kv_gather_rows over the handle's own planes (bf16, or bytes and scales of the e4m3 cache): sequence slots[j] takes the first lens[j] cache rows
+ * of sequence slots[copy_src_dev[j]].  Also refused: a slot outside [0, n_slots), a len above the slot capacity. */
+int td_qwen2_gather_slots(td_qwen2* f, int n, const int* slots, const int32_t* copy_src_dev, const int* lens, void* stream);
 /* One new token for each of the sequences in slots 0..B-1 (B <= 64) in one pass over the weights: token_ids int32[B],
  * position_ids int32[3,B] (device); cache_pos[b] = tokens already cached for sequence b (HOST ints); hidden_out bf16[B,hidden],
  * logits bf16[B,vocab] (either may be NULL). */
@@ -1152,6 +1166,27 @@ int td_sample_rows_edit_bf16(const td_sampler* s, const td_logit_edits* e, const
 #define TD_MAX_LOGPROBS 20
 int td_logprobs_rows_bf16(const void* logits, int64_t ld, int rows, int vocab, const int32_t* ids_dev, const int32_t* n_top_dev, int top_cap,
                           float* lp_sampled, int32_t* rank, int32_t* top_ids, float* top_lp, void* stream);
+
+/* ---- beam search: the step's choice and placement on the device (td_abi_version() >= 18; csrc/beam_search.hip), one wave per request ----
+ * A launch covers R requests of W rows each; row r*W + j is cache-slot position j of request r.  n_in (HOST) = 1 at the first step, when only row
+ * r*W of a request is live (it holds the prefill), W afterwards.  Inputs (device): top_ids int32 / top_lp fp32 [R*W, cap], cap >= 2W -- what
+ * td_logprobs_rows_bf16 returns with n_top = 2W; cum_in fp32 [R*W]; rank_in int32 [R*W], the rank of the beam living in each row; eos: a token id,
+ * or -1 for none.  The rule, per request:
+ *   a candidate is (live row j, column c < 2W) with id >= 0 and cum = cum_in[j] + top_lp[j][c] (ONE fp32 add; a NaN sum counts as -inf);
+ *   id == eos: a FINISHER of row j -- fin_flag[j] = 1, fin_cum[j] = cum (the first such column) -- and not a beam candidate; rows without one get
+ *   fin_flag 0 and fin_cum -inf;
+ *   the other candidates in the order (cum descending, rank_in ascending, c ascending[, j ascending]): the first W are the new beams, ranks 0..W-1;
+ *   with fewer than W candidates the missing beams have token -1, cum -inf and no parent.
+ * Slot-stable placement: walking the new beams in rank order, a beam whose parent's row is not yet claimed takes that row (no copy); the remaining
+ * beams, in rank order, take the unclaimed rows in ascending order and get copy_src = the absolute row index of their parent.  So every source row
+ * keeps its own beam, every destination is the row of a beam that died, and td_kv_gather_rows can do all copies of the step in one call.
+ * Outputs per row (device, [R*W]; the caller passes per-step slices of [T, R*W] logs and reads a generation back once): token, cum_out, rank_out,
+ * copy_src (-1: no copy), parent (absolute row of the parent; the own row for a missing beam), fin_flag, fin_cum.  Nothing faults and no output
+ * is NaN.  TD_ERR_INVALID with a message naming the value, before any HIP call: a NULL pointer, W outside 1..TD_MAX_BEAM_WIDTH (2W must fit
+ * TD_MAX_LOGPROBS), cap < 2W, n_in not in {1, W}, R < 1, R*W > 65535. */
+#define TD_MAX_BEAM_WIDTH 10
+int td_beam_select(const int32_t* top_ids, const float* top_lp, int cap, const float* cum_in, const int32_t* rank_in, int R, int W, int n_in, int eos,
+                   int32_t* token, float* cum_out, int32_t* rank_out, int32_t* copy_src, int32_t* parent, int32_t* fin_flag, float* fin_cum, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 17; }   // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 18; }   // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -38,6 +38,8 @@ int td_abi_version(void) { return 17; }   // 2: TdFluxConfig::out_channels appen
                                             // 16: KV fork (td_kv_fork_rows, td_qwen2_fork_slot; csrc/kv_fork.hip)
                                             // 17: td_attention_segments_bf16 (packed segments with a causal switch: the packed prefill's launch);
                                             //     td_softmax_rows_* refuse a scale that is not finite and positive
+                                            // 18: beam search (td_beam_select; csrc/beam_search.hip) and the KV gather behind it (td_kv_gather_rows,
+                                            //     td_qwen2_gather_slots; csrc/kv_fork.hip)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,

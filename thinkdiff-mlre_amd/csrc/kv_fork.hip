@@ -14,6 +14,9 @@
 //
 // The plane table and the destination slots travel in the launch's own arguments (td_logit_edits_set_bias's method): nothing is allocated, nothing
 // uploaded, no host buffer has to outlive the call; FORK_PLANES planes x FORK_DSTS destinations per launch, as many launches as that needs.
+//
+// Below the fork: the KV gather (td_kv_gather_rows), the same copy with one source per ROW, named by the device -- the reordering of cache slots
+// behind a beam-search step (csrc/beam_search.hip).
 #include <algorithm>
 #include <vector>
 
@@ -86,9 +89,134 @@ __global__ __launch_bounds__(FORK_NT) void td_kv_fork_kernel(const ForkArgs a) {
   else fork_body<unsigned short>(a, p, body);
 }
 
+// ---- KV gather (td_kv_gather_rows): row j of a launch takes the cache rows of row copy_src[j], which the DEVICE names -------------------------
+// Beam search reorders cache slots by what td_beam_select chose, and the host does not know the choice: the slot of every row and its length are
+// host values in the launch arguments (the fork's method), the source row is read from device memory.  The split of a byte range into head, body
+// and tail is the fork's -- every slot of a plane shares its alignment modulo w -- but the range's length differs per row, so it is made here.
+constexpr int GATHER_ROWS = 64;         // destination rows per launch (grid z)
+constexpr int GATHER_MAX_N = 256;       // rows of a call: every launch carries the whole slot table, a source may be any row
+constexpr int GATHER_PASSES = 32;       // workgroups per (plane, row): a row that copies nothing costs 32 x planes workgroups that return at once
+
+struct GatherPlane {
+  char* base;
+  long long slot_bytes;
+  int row_bytes;
+  int w;                     // access width of the body
+};
+struct GatherArgs {          // 64 x 24 + 256 x 4 + 64 x 4 + 16 = 2832 bytes of kernel arguments
+  GatherPlane plane[FORK_PLANES];
+  int slot[GATHER_MAX_N];
+  int n_rows[GATHER_ROWS];   // of the rows row0 .. row0 + GATHER_ROWS
+  int row0;
+  int n;
+  int pad0, pad1;
+};
+
+template <typename T>
+__device__ __forceinline__ void gather_body(const char* src, char* dst, long long pieces) {
+  const long long per_pass = (long long)FORK_NT * FORK_UNROLL;
+  for (long long c0 = (long long)blockIdx.x * per_pass; c0 < pieces; c0 += (long long)gridDim.x * per_pass) {
+    T v[FORK_UNROLL];
+#pragma unroll
+    for (int u = 0; u < FORK_UNROLL; ++u) {
+      const long long c = c0 + u * FORK_NT + threadIdx.x;
+      if (c < pieces) v[u] = ((const T*)src)[c];
+    }
+#pragma unroll
+    for (int u = 0; u < FORK_UNROLL; ++u) {
+      const long long c = c0 + u * FORK_NT + threadIdx.x;
+      if (c < pieces) ((T*)dst)[c] = v[u];
+    }
+  }
+}
+
+// grid (passes, planes of this launch, rows of this launch); a workgroup whose row copies nothing returns before it touches a plane
+__global__ __launch_bounds__(FORK_NT) void td_kv_gather_kernel(const GatherArgs a, const int* __restrict__ copy_src) {
+  const int j = a.row0 + blockIdx.z;
+  const int s = copy_src[j];
+  if (s < 0 || s >= a.n || s == j) return;      // (a source outside the call's rows names no slot: nothing is read through it)
+  const GatherPlane& p = a.plane[blockIdx.y];
+  const long long nbytes = (long long)a.n_rows[blockIdx.z] * p.row_bytes;
+  if (nbytes <= 0) return;
+  const char* src = p.base + (long long)a.slot[s] * p.slot_bytes;
+  char* dst = p.base + (long long)a.slot[j] * p.slot_bytes;
+  const int mis = (int)((uintptr_t)src % (uintptr_t)p.w);
+  const long long head = min((long long)((p.w - mis) % p.w), nbytes);
+  const long long body = (nbytes - head) / p.w;
+  if (blockIdx.x == 0) {
+    const int tail = (int)(nbytes - head - body * p.w);
+    const int t = threadIdx.x;
+    long long off = -1;
+    if (t < head / 2) off = 2 * t;
+    else if (t >= 64 && t - 64 < tail / 2) off = head + body * p.w + 2 * (t - 64);
+    if (off >= 0) *(unsigned short*)(dst + off) = *(const unsigned short*)(src + off);
+  }
+  if (p.w == 16) gather_body<u32x4_t>(src + head, dst + head, body);
+  else if (p.w == 8) gather_body<u32x2_t>(src + head, dst + head, body);
+  else if (p.w == 4) gather_body<unsigned>(src + head, dst + head, body);
+  else gather_body<unsigned short>(src + head, dst + head, body);
+}
+
 }  // namespace
 
 extern "C" {
+
+int td_kv_gather_rows(const TdKvPlane* planes, int n_planes, int n, const int* slots, const int32_t* copy_src_dev, const int* n_rows, void* stream) {
+  TD_CHECK_ARG(planes, "td_kv_gather_rows: null planes");
+  TD_CHECK_ARG(slots, "td_kv_gather_rows: null slots");
+  TD_CHECK_ARG(copy_src_dev, "td_kv_gather_rows: null copy_src_dev");
+  TD_CHECK_ARG(n_rows, "td_kv_gather_rows: null n_rows");
+  TD_CHECK_ARG(n_planes >= 1, "td_kv_gather_rows: n_planes=%d, at least one plane is needed", n_planes);
+  TD_CHECK_ARG(n >= 1 && n <= GATHER_MAX_N, "td_kv_gather_rows: n=%d rows outside 1..%d", n, GATHER_MAX_N);
+  int max_rows = 0;
+  for (int j = 0; j < n; ++j) {
+    TD_CHECK_ARG(slots[j] >= 0, "td_kv_gather_rows: slot %d of row %d is negative", slots[j], j);
+    TD_CHECK_ARG(n_rows[j] >= 0, "td_kv_gather_rows: n_rows=%d of row %d is negative", n_rows[j], j);
+    max_rows = std::max(max_rows, n_rows[j]);
+  }
+  for (int p = 0; p < n_planes; ++p) {
+    TD_CHECK_ARG(planes[p].base, "td_kv_gather_rows: plane %d has a null base", p);
+    TD_CHECK_ARG(planes[p].row_bytes >= 2 && planes[p].row_bytes % 2 == 0 && planes[p].row_bytes <= (1 << 30),
+                 "td_kv_gather_rows: row_bytes=%lld of plane %d is not a positive multiple of 2", (long long)planes[p].row_bytes, p);
+    TD_CHECK_ARG(((uintptr_t)planes[p].base) % 2 == 0, "td_kv_gather_rows: the base %p of plane %d is not 2-byte aligned", planes[p].base, p);
+    TD_CHECK_ARG(planes[p].slot_rows >= 1, "td_kv_gather_rows: slot_rows=%lld of plane %d is not positive", (long long)planes[p].slot_rows, p);
+    TD_CHECK_ARG(max_rows <= planes[p].slot_rows, "td_kv_gather_rows: n_rows=%d exceeds slot_rows=%lld of plane %d", max_rows, (long long)planes[p].slot_rows, p);
+  }
+  std::vector<int> sorted(slots, slots + n);
+  std::sort(sorted.begin(), sorted.end());
+  for (int i = 1; i < n; ++i) TD_CHECK_ARG(sorted[i] != sorted[i - 1], "td_kv_gather_rows: slot %d is given twice", sorted[i]);
+  if (max_rows == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  for (int p0 = 0; p0 < n_planes; p0 += FORK_PLANES) {
+    const int np = std::min(FORK_PLANES, n_planes - p0);
+    GatherArgs a = {};
+    a.n = n;
+    for (int j = 0; j < n; ++j) a.slot[j] = slots[j];
+    for (int p = 0; p < np; ++p) {
+      const TdKvPlane& q = planes[p0 + p];
+      GatherPlane& gp = a.plane[p];
+      gp.base = (char*)q.base;
+      gp.slot_bytes = (long long)q.slot_rows * q.row_bytes;
+      gp.row_bytes = (int)q.row_bytes;
+      gp.w = gp.slot_bytes % 16 == 0 ? 16 : gp.slot_bytes % 8 == 0 ? 8 : gp.slot_bytes % 4 == 0 ? 4 : 2;
+    }
+    for (int r0 = 0; r0 < n; r0 += GATHER_ROWS) {
+      const int nr = std::min(GATHER_ROWS, n - r0);
+      a.row0 = r0;
+      long long passes = 1;
+      for (int j = 0; j < nr; ++j) {
+        a.n_rows[j] = n_rows[r0 + j];
+        for (int p = 0; p < np; ++p) {
+          const long long per_pass = (long long)FORK_NT * FORK_UNROLL * a.plane[p].w;
+          passes = std::max(passes, ((long long)n_rows[r0 + j] * a.plane[p].row_bytes + per_pass - 1) / per_pass);
+        }
+      }
+      hipLaunchKernelGGL(td_kv_gather_kernel, dim3((unsigned)std::min<long long>(passes, GATHER_PASSES), np, nr), dim3(FORK_NT), 0, st, a, copy_src_dev);
+      TD_CHECK_LAUNCH();
+    }
+  }
+  return 0;
+}
 
 int td_kv_fork_rows(const TdKvPlane* planes, int n_planes, int src_slot, const int* dst_slots, int n_dst, int n_rows, void* stream) {
   TD_CHECK_ARG(planes, "td_kv_fork_rows: null planes");

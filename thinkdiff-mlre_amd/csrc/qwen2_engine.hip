@@ -709,6 +709,30 @@ int td_qwen2_fork_slot(td_qwen2* f, int src, const int* dst_slots, int n_dst, in
   return td_kv_fork_rows(planes.data(), (int)planes.size(), src, dst_slots, n_dst, len, stream);
 }
 
+// the reordering of a beam-search step (td_kv_gather_rows): row j takes the cache rows of row copy_src_dev[j], which only the device knows
+int td_qwen2_gather_slots(td_qwen2* f, int n, const int* slots, const int32_t* copy_src_dev, const int* lens, void* stream) {
+  TD_CHECK_ARG(f, "td_qwen2_gather_slots: null handle");
+  TD_CHECK_ARG(slots, "td_qwen2_gather_slots: null slots");
+  TD_CHECK_ARG(copy_src_dev, "td_qwen2_gather_slots: null copy_src_dev");
+  TD_CHECK_ARG(lens, "td_qwen2_gather_slots: null lens");
+  TD_CHECK_ARG(n >= 1 && n <= 256, "td_qwen2_gather_slots: n=%d rows outside 1..256", n);
+  for (int j = 0; j < n; ++j) {
+    TD_CHECK_ARG(slots[j] >= 0 && slots[j] < f->n_slots, "td_qwen2_gather_slots: slot %d of row %d outside the %d configured sequences", slots[j], j, f->n_slots);
+    TD_CHECK_ARG(lens[j] >= 0 && lens[j] <= f->slot_len, "td_qwen2_gather_slots: len=%d of row %d exceeds the slot capacity %d", lens[j], j, f->slot_len);
+  }
+  const int64_t KVW = (int64_t)2 * f->Hkv * 128, SW = (int64_t)2 * f->Hkv;
+  std::vector<TdKvPlane> planes;
+  for (const QLayer& l : f->layers) {
+    if (f->kv_mode == TD_QWEN2_KV_E4M3) {
+      planes.push_back(TdKvPlane{l.kv8, KVW, f->slot_len});
+      planes.push_back(TdKvPlane{l.kvs, SW * 4, f->slot_len});
+    } else {
+      planes.push_back(TdKvPlane{l.kv, KVW * 2, f->slot_len});
+    }
+  }
+  return td_kv_gather_rows(planes.data(), (int)planes.size(), n, slots, copy_src_dev, lens, stream);
+}
+
 }  // extern "C"
 
 // ---- batched KV-cached decode (the precompute job: many short sequences against one pass over the weights) --------------

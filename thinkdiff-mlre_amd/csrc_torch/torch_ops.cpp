@@ -896,6 +896,55 @@ void kv_fork_rows(at::Tensor plane, int64_t slot_rows, int64_t src_slot, at::Int
   ok(td_kv_fork_rows(&pl, 1, (int)src_slot, dst.data(), (int)dst.size(), (int)n_rows, stream_of(plane)));
 }
 
+// KV gather on one plane (td_kv_gather_rows): row j with copy_src[j] >= 0 takes rows [0, n_rows[j]) of slot slots[copy_src[j]] into slot slots[j], in place;
+// copy_src: int32 [len(slots)] on the plane's device, read by the kernel.  The caller vouches that no destination slot is a source of the same call.
+void kv_gather_rows(at::Tensor plane, int64_t slot_rows, at::IntArrayRef slots, const at::Tensor& copy_src, at::IntArrayRef n_rows) {
+  TORCH_CHECK(plane.is_cuda(), "thinkdiff_hip: plane must live on the GPU");
+  TORCH_CHECK(plane.dim() == 2 && plane.is_contiguous(), "thinkdiff_hip::kv_gather_rows: plane [slots * slot_rows, row] contiguous");
+  TORCH_CHECK(slot_rows >= 1 && plane.size(0) % slot_rows == 0, "thinkdiff_hip::kv_gather_rows: slot_rows=", slot_rows, " does not divide the plane's ", plane.size(0), " rows");
+  const int64_t n_slots = plane.size(0) / slot_rows, n = (int64_t)slots.size();
+  TORCH_CHECK(n >= 1 && n <= 256 && (int64_t)n_rows.size() == n, "thinkdiff_hip::kv_gather_rows: ", n, " slots (1..256) with ", n_rows.size(), " n_rows");
+  TORCH_CHECK(copy_src.is_cuda() && copy_src.device() == plane.device() && copy_src.scalar_type() == at::kInt && copy_src.is_contiguous() && copy_src.numel() == n,
+              "thinkdiff_hip::kv_gather_rows: copy_src must be a contiguous int32 tensor of ", n, " entries on the plane's device");
+  std::vector<int> sl, nr;
+  for (int64_t v : slots) {
+    TORCH_CHECK(v >= 0 && v < n_slots, "thinkdiff_hip::kv_gather_rows: slot ", v, " outside the plane's ", n_slots, " slots");
+    sl.push_back((int)v);
+  }
+  for (int64_t v : n_rows) {
+    TORCH_CHECK(v >= 0 && v <= slot_rows, "thinkdiff_hip::kv_gather_rows: n_rows=", v, " outside [0, slot_rows=", slot_rows, "]");
+    nr.push_back((int)v);
+  }
+  DeviceGuard guard(plane.device());
+  const TdKvPlane pl = {plane.data_ptr(), plane.size(1) * (int64_t)plane.element_size(), slot_rows};
+  ok(td_kv_gather_rows(&pl, 1, (int)n, sl.data(), (const int32_t*)copy_src.data_ptr(), nr.data(), stream_of(plane)));
+}
+
+// the beam-search step's choice and placement (td_beam_select): top_ids int32 / top_lp fp32 [R*W, cap] (logprobs_rows with n_top = 2W), cum_in fp32 and
+// rank_in int32 [R*W]; the seven outputs are [R*W] tensors (slices of the caller's [T, R*W] logs) written in place
+void beam_select(const at::Tensor& top_ids, const at::Tensor& top_lp, const at::Tensor& cum_in, const at::Tensor& rank_in, int64_t W, int64_t n_in, int64_t eos,
+                 at::Tensor token, at::Tensor cum_out, at::Tensor rank_out, at::Tensor copy_src, at::Tensor parent, at::Tensor fin_flag, at::Tensor fin_cum) {
+  TORCH_CHECK(top_ids.is_cuda(), "thinkdiff_hip: top_ids must live on the GPU");
+  TORCH_CHECK(W >= 1 && W <= TD_MAX_BEAM_WIDTH, "thinkdiff_hip::beam_select: W=", W, " outside 1..", TD_MAX_BEAM_WIDTH);
+  TORCH_CHECK(top_ids.dim() == 2 && top_ids.is_contiguous() && top_ids.scalar_type() == at::kInt && top_ids.size(0) >= 1 && top_ids.size(0) % W == 0,
+              "thinkdiff_hip::beam_select: top_ids must be a contiguous int32 [R*W, cap] tensor");
+  const int64_t rows = top_ids.size(0), cap = top_ids.size(1);
+  TORCH_CHECK(top_lp.device() == top_ids.device() && top_lp.scalar_type() == at::kFloat && top_lp.is_contiguous() && top_lp.sizes() == top_ids.sizes(),
+              "thinkdiff_hip::beam_select: top_lp must be a contiguous fp32 tensor of top_ids' shape on its device");
+  for (const at::Tensor* t : {&rank_in, (const at::Tensor*)&token, (const at::Tensor*)&rank_out, (const at::Tensor*)&copy_src, (const at::Tensor*)&parent,
+                              (const at::Tensor*)&fin_flag})
+    TORCH_CHECK(t->device() == top_ids.device() && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == rows,
+                "thinkdiff_hip::beam_select: rank_in, token, rank_out, copy_src, parent and fin_flag must be contiguous int32 tensors of ", rows, " entries on top_ids' device");
+  for (const at::Tensor* t : {&cum_in, (const at::Tensor*)&cum_out, (const at::Tensor*)&fin_cum})
+    TORCH_CHECK(t->device() == top_ids.device() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == rows,
+                "thinkdiff_hip::beam_select: cum_in, cum_out and fin_cum must be contiguous fp32 tensors of ", rows, " entries on top_ids' device");
+  TORCH_CHECK(eos >= -1 && eos <= std::numeric_limits<int>::max(), "thinkdiff_hip::beam_select: eos=", eos, " is neither a token id nor -1");
+  DeviceGuard guard(top_ids.device());
+  ok(td_beam_select((const int32_t*)top_ids.data_ptr(), (const float*)top_lp.data_ptr(), (int)cap, (const float*)cum_in.data_ptr(), (const int32_t*)rank_in.data_ptr(),
+                    (int)(rows / W), (int)W, (int)n_in, (int)eos, (int32_t*)token.data_ptr(), (float*)cum_out.data_ptr(), (int32_t*)rank_out.data_ptr(),
+                    (int32_t*)copy_src.data_ptr(), (int32_t*)parent.data_ptr(), (int32_t*)fin_flag.data_ptr(), (float*)fin_cum.data_ptr(), stream_of(top_ids)));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(thinkdiff_hip, m) {
@@ -952,6 +1001,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("attention_decode_kv8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor");
   m.def("linear_w8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
   m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
+  m.def("kv_gather_rows(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()");
+  m.def("beam_select(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
@@ -1004,6 +1055,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("attention_decode_kv8", &attention_decode_kv8);
   m.impl("linear_w8", &linear_w8);
   m.impl("kv_fork_rows", &kv_fork_rows);
+  m.impl("kv_gather_rows", &kv_gather_rows);
+  m.impl("beam_select", &beam_select);
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {

@@ -201,6 +201,9 @@ def _declare(L):
         "td_qwen2_move_slot": [vp, i32, i32, i32, vp],
         "td_qwen2_fork_slot": [vp, i32, vp, i32, i32, vp],
         "td_kv_fork_rows": [vp, i32, i32, vp, i32, i32, vp],
+        "td_kv_gather_rows": [vp, i32, i32, vp, vp, vp, vp],
+        "td_qwen2_gather_slots": [vp, i32, vp, vp, vp, vp],
+        "td_beam_select": [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_decode_batch": [vp, i32, vp, vp, vp, vp, vp, vp],
         "td_qwen2_decode_batch_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_quantize_weights": [vp, i32, vp],
@@ -675,6 +678,67 @@ def kv_fork_rows(planes, src_slot, dst_slots, n_rows):
     dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
     check(lib().td_kv_fork_rows(ctypes.cast(arr, ctypes.c_void_p), len(planes), int(src_slot), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(n_rows),
                                 stream_ptr()))
+
+
+def kv_gather_rows(planes, slots, copy_src, n_rows):
+    """td_kv_gather_rows: for every row j with copy_src[j] >= 0, rows [0, n_rows[j]) of slot slots[copy_src[j]] -> the same rows of slot slots[j], on every
+    plane.  planes: (tensor, slot_rows) pairs as for kv_fork_rows; slots / n_rows: host ints, one per row (n_rows may be one int for all);
+    copy_src: an int32 DEVICE tensor [len(slots)] (a list is uploaded), read by the kernel.  The caller vouches that no destination slot is a
+    source of the same call.  In place."""
+    n = len(slots)
+    if isinstance(n_rows, int):
+        n_rows = [n_rows] * n
+    if len(n_rows) != n:
+        raise ThinkDiffHipError(f"kv_gather_rows: {len(n_rows)} n_rows for {n} slots")
+    arr = (TdKvPlane * max(1, len(planes)))()
+    dev = None
+    for i, (t, slot_rows) in enumerate(planes):
+        if not t.is_contiguous() or t.dim() < 2 or t.shape[0] % int(slot_rows):
+            raise ThinkDiffHipError(f"kv_gather_rows: plane {i} must be contiguous [slots * slot_rows, ...] with slot_rows={slot_rows} dividing its {t.shape[0]} rows")
+        n_slots = t.shape[0] // int(slot_rows)
+        bad = [int(s) for s in slots if not 0 <= int(s) < n_slots]
+        if bad:
+            raise ThinkDiffHipError(f"kv_gather_rows: slot {bad[0]} outside the {n_slots} slots of plane {i}")
+        arr[i] = TdKvPlane(t.data_ptr(), (t.numel() // t.shape[0]) * t.element_size(), int(slot_rows))
+        dev = t.device
+    if not torch.is_tensor(copy_src):
+        copy_src = torch.tensor([int(c) for c in copy_src], dtype=torch.int32)
+    copy_src = copy_src.to(device=dev, dtype=torch.int32).contiguous()
+    if copy_src.numel() != n:
+        raise ThinkDiffHipError(f"kv_gather_rows: {copy_src.numel()} copy_src entries for {n} slots")
+    sl = (ctypes.c_int * max(1, n))(*[int(s) for s in slots])
+    nr = (ctypes.c_int * max(1, n))(*[int(v) for v in n_rows])
+    check(lib().td_kv_gather_rows(ctypes.cast(arr, ctypes.c_void_p), len(planes), n, ctypes.cast(sl, ctypes.c_void_p), ptr(copy_src),
+                                  ctypes.cast(nr, ctypes.c_void_p), stream_ptr()))
+
+
+MAX_BEAM_WIDTH = 10        # TD_MAX_BEAM_WIDTH (2 W candidates per row must fit TD_MAX_LOGPROBS)
+
+
+def beam_select(top_ids, top_lp, cum_in, rank_in, W, n_in, eos=-1, out=None):
+    """td_beam_select: one beam-search step for R requests of W rows.  top_ids int32 / top_lp fp32 [R*W, cap] (logprobs_rows with n_top = 2W), cum_in
+    fp32 [R*W], rank_in int32 [R*W]; n_in = 1 at the first step (only row r*W of a request is live), W afterwards; eos: a token id or -1.
+    -> (token, cum_out, rank_out, copy_src, parent, fin_flag, fin_cum), [R*W] device tensors; `out`: that tuple to write into (slices of [T, R*W] logs)."""
+    W = int(W)
+    if not (top_ids.dim() == 2 and top_ids.dtype == torch.int32 and top_ids.is_contiguous() and top_lp.dtype == torch.float32 and top_lp.is_contiguous()
+            and top_lp.shape == top_ids.shape):
+        raise ThinkDiffHipError("beam_select: top_ids int32 and top_lp fp32 must be contiguous [R*W, cap] tensors of one shape")
+    rows, cap = top_ids.shape
+    if W < 1 or rows % W:
+        raise ThinkDiffHipError(f"beam_select: W={W} does not divide the {rows} rows")
+    dev = top_ids.device
+    cum_in = cum_in.to(device=dev, dtype=torch.float32).contiguous()
+    rank_in = rank_in.to(device=dev, dtype=torch.int32).contiguous()
+    if out is None:
+        out = tuple(torch.empty(rows, dtype=torch.float32 if i in (1, 6) else torch.int32, device=dev) for i in range(7))
+    for i, t in enumerate((cum_in, rank_in) + tuple(out)):
+        want = torch.float32 if i in (0, 3, 8) else torch.int32
+        if t.dtype != want or t.numel() != rows or not t.is_contiguous() or t.device != dev:
+            raise ThinkDiffHipError(f"beam_select: tensor {i} of (cum_in, rank_in, token, cum_out, rank_out, copy_src, parent, fin_flag, fin_cum) must be a "
+                                    f"contiguous {want} tensor of {rows} entries on {dev}")
+    check(lib().td_beam_select(ptr(top_ids), ptr(top_lp), int(cap), ptr(cum_in), ptr(rank_in), rows // W, W, int(n_in), int(eos), *[ptr(t) for t in out],
+                               stream_ptr()))
+    return tuple(out)
 
 
 class TdVaeConfig(ctypes.Structure):

@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 
 from .base_model import BaseModel
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, sampler_fields_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config
 
 
 @registry.register_model("mllama-vllm-generate-1")
@@ -48,6 +48,8 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
             min_tokens=vc.get("min_tokens", 1), ignore_eos=vc.get("ignore_eos", False),
             stop_token_ids=list(vc["stop_token_ids"]) if vc.get("stop_token_ids") else None,      # (a vllm.SamplingParams field; the reference's config leaves it unset)
             **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
+        # vllm_config["beam_width"]: generation goes through Qwen2VLTextEngine.beam_search (vLLM's LLM.beam_search) and output 0, the best beam, is consumed
+        self.mllama_beam_params = beam_params_from_vllm_config(vc, max_tokens=self.mllama_sampling_params.max_tokens, ignore_eos=self.mllama_sampling_params.ignore_eos)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, None
         self.visual, self.image_processor, self.image_token_id = None, None, 151655
         self.request_builder = request_builder
@@ -93,6 +95,9 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
         # of small latency-bound launches that leaves most of the chip idle, and its host thread spends its time waiting for token ids).  vLLM's
         # engine overlaps its input processing with decoding in the same way.  TD_PRECOMPUTE_PREFETCH=0: one after the other (A/B).
         per = max(1, self.decode_batch // self.mllama_sampling_params.width)      # (n / best_of: a request takes `width` cache slots; output 0 is used, as the reference does with vLLM)
+        beam = self.mllama_beam_params
+        if beam is not None:
+            per = max(1, self.decode_batch // beam.beam_width)      # (a request takes beam_width cache slots)
         chunks = [range(c0, min(c0 + per, n)) for c0 in range(0, n, per)]
         prefetch = len(chunks) > 1 and os.environ.get("TD_PRECOMPUTE_PREFETCH", "1") != "0"
         pool = ThreadPoolExecutor(max_workers=1) if prefetch else None
@@ -105,7 +110,7 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
         # loader batch is 8192 = 32 chunks, its outputs end at EOS); TD_PRECOMPUTE_CONTINUOUS=1 / 0 forces either form.  The two sample different
         # tokens (the draw of a sequence depends on the step and the row it sits in), each reproducibly under its seed.
         env_c = os.environ.get("TD_PRECOMPUTE_CONTINUOUS", "")
-        continuous = env_c == "1" or (env_c != "0" and len(chunks) >= 8)
+        continuous = beam is None and (env_c == "1" or (env_c != "0" and len(chunks) >= 8))      # (beam search runs chunk by chunk: every beam lives to max_tokens)
         all_reqs, all_outs = [], []
         try:
             if continuous:
@@ -129,6 +134,9 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
                     else:
                         reqs = self._requests(mllama_inputs, idx)
                     all_reqs.extend(reqs)
+                    if beam is not None:
+                        all_outs.extend(self.mllama.beam_search(reqs, beam, eos_token_id=self.eos_token_id))
+                        continue
                     all_outs.extend(self.mllama.generate_batch(reqs, self.mllama_sampling_params, eos_token_id=self.eos_token_id, generator=generator))
         finally:
             if pool is not None:

@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import HipVisionProjector
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, sampler_fields_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config
 
 SYSTEM_PROMPT = "You are a helpful assistant."   # reference :1048
 NUM_SYSTEM_TOKENS = 14                            # reference :1107-1109 ("input_no_system" drops the first 14)
@@ -51,6 +51,9 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),
             min_tokens=vc.get("min_tokens", 128), ignore_eos=vc.get("ignore_eos", True),
             **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
+        # vllm_config["beam_width"]: generation goes through Qwen2VLTextEngine.beam_search (vLLM's LLM.beam_search) and output 0, the best beam, is consumed
+        self.mllama_beam_params = beam_params_from_vllm_config(vc, max_tokens=self.mllama_sampling_params.max_tokens, ignore_eos=self.mllama_sampling_params.ignore_eos)
+        self.eos_token_id = vc.get("eos_token_id", None)
         self.mm_projector = HipVisionProjector(self.config.mm_hidden_size, hidden_size, mm_projector_type, device=device, fp32_norm=True)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, processor
         self.visual, self.image_token_id = visual, image_token_id
@@ -92,7 +95,14 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         sp = self.mllama_sampling_params    # **generate_kwargs (e.g. the drivers' max_new_tokens=128) are accepted and unused, as in the reference (:1019-1118)
         reqs = self.resolve_requests(reqs)
         outs = []
-        if self.decode_batch > 1 and len(reqs) > 1:
+        beam = self.mllama_beam_params
+        if beam is not None:
+            if forced_output_ids is not None:
+                raise ValueError(f"get_embed: forced_output_ids with vllm_config beam_width={beam.beam_width}: a teacher-forced continuation is one sequence")
+            per = max(1, self.decode_batch // beam.beam_width)      # (a request takes beam_width cache slots)
+            for c0 in range(0, len(reqs), per):
+                outs.extend(self.mllama.beam_search(reqs[c0:c0 + per], beam, eos_token_id=self.eos_token_id))
+        elif self.decode_batch > 1 and len(reqs) > 1:
             per = max(1, self.decode_batch // sp.width)      # (n / best_of: a request takes `width` cache slots; output 0 is used, as the reference does with vLLM)
             for c0 in range(0, len(reqs), per):
                 chunk = reqs[c0:c0 + per]

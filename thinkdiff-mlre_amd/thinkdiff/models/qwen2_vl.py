@@ -174,6 +174,60 @@ def sampler_fields_from_vllm_config(vc) -> dict:
     return {k: vc[k] for k in SAMPLER_CONFIG_KEYS + LOGIT_EDIT_CONFIG_KEYS + PARALLEL_CONFIG_KEYS if vc.get(k) is not None}
 
 
+@dataclasses.dataclass
+class BeamSearchParams:
+    """vllm.sampling_params.BeamSearchParams under vLLM's names (`LLM.beam_search`).  The candidates of a step are RAW logprobs (td_logprobs_rows_bf16), on
+    which a temperature could not act: any value but 0 is refused, not ignored."""
+    beam_width: int
+    max_tokens: int
+    ignore_eos: bool = False
+    temperature: float = 0.0
+    length_penalty: float = 1.0
+
+    def validate(self) -> "BeamSearchParams":
+        def bad(field, why):
+            raise ValueError(f"BeamSearchParams.{field}={getattr(self, field)!r}: {why}")
+
+        def integer(v):
+            return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if not (integer(self.beam_width) and 1 <= self.beam_width <= _hip.MAX_BEAM_WIDTH):
+            bad("beam_width", f"must be an integer in [1, {_hip.MAX_BEAM_WIDTH}] (a step scores 2 x beam_width candidates per beam, at most {_hip.MAX_LOGPROBS})")
+        if not (integer(self.max_tokens) and self.max_tokens >= 1):
+            bad("max_tokens", "must be an integer >= 1")
+        if not isinstance(self.ignore_eos, bool):
+            bad("ignore_eos", "must be True or False")
+        if isinstance(self.temperature, bool) or not isinstance(self.temperature, numbers.Real) or self.temperature != 0:
+            bad("temperature", "beam search ranks raw logprobs, only temperature 0 is served")
+        lp = self.length_penalty
+        if isinstance(lp, bool) or not isinstance(lp, numbers.Real) or lp != lp or lp in (float("inf"), float("-inf")):
+            bad("length_penalty", "must be a finite number")
+        return self
+
+    def score(self, cumulative_logprob: float, seq_len: int) -> float:
+        """vLLM's get_beam_search_score: cum / seq_len ** length_penalty (seq_len = prompt + generated tokens, less a final EOS)."""
+        return float(cumulative_logprob) / (float(seq_len) ** float(self.length_penalty))
+
+
+BEAM_CONFIG_KEYS = ("beam_width", "length_penalty")
+
+
+def beam_params_from_vllm_config(vc, max_tokens: int = 128, ignore_eos: bool = False) -> Optional[BeamSearchParams]:
+    """The BeamSearchParams a vllm_config asks for with `beam_width` (None without it: generation samples as before).  max_tokens, ignore_eos and
+    temperature are the config's own keys where it sets them (a temperature other than 0 beside beam_width is refused by validate()); beam_width
+    beside n / best_of > 1 is a ValueError: the two are different ways to spend a request's cache slots."""
+    if vc.get("beam_width") is None:
+        if vc.get("length_penalty") is not None:
+            raise ValueError(f"vllm_config length_penalty={vc['length_penalty']!r} without beam_width: it only acts on a beam search")
+        return None
+    wide = {k: vc[k] for k in PARALLEL_CONFIG_KEYS if vc.get(k) is not None and vc[k] != 1}
+    if wide:
+        raise ValueError(f"vllm_config beam_width={vc['beam_width']!r} together with {wide}: beam search returns its beams, n / best_of do not apply")
+    return BeamSearchParams(beam_width=vc["beam_width"], max_tokens=vc["max_tokens"] if vc.get("max_tokens") is not None else max_tokens,
+                            ignore_eos=vc["ignore_eos"] if vc.get("ignore_eos") is not None else ignore_eos,
+                            temperature=vc["temperature"] if vc.get("temperature") is not None else 0.0,
+                            length_penalty=vc["length_penalty"] if vc.get("length_penalty") is not None else 1.0).validate()
+
+
 Logprob = collections.namedtuple("Logprob", ["logprob", "rank"])      # vLLM's Logprob, without the decoded text
 
 
@@ -1238,6 +1292,159 @@ class Qwen2VLTextEngine:
         chunk is read once and written len(dst_slots) times): the sequences in those slots then continue from the same prefill."""
         dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
         _hip.check(self._L.td_qwen2_fork_slot(self._h, int(src), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(length), _hip.stream_ptr()))
+
+    def gather_slots(self, slots: Sequence[int], copy_src, lengths: Sequence[int]):
+        """For every row j with copy_src[j] >= 0 (an int32 DEVICE tensor, read by the kernel: the host never learns it), copy the first lengths[j]
+        cache rows of slot slots[copy_src[j]] to slot slots[j], all layers and planes (td_qwen2_gather_slots).  The caller vouches that no
+        destination is a source of the same call -- beam_select's placement guarantees it."""
+        n = len(slots)
+        sl = (ctypes.c_int * max(1, n))(*[int(v) for v in slots])
+        ln = (ctypes.c_int * max(1, n))(*[int(v) for v in lengths])
+        src = copy_src.to(device=self.device, dtype=torch.int32).contiguous()
+        if src.numel() != n or len(lengths) != n:
+            raise _hip.ThinkDiffHipError(f"gather_slots: {src.numel()} copy_src entries and {len(lengths)} lengths for {n} slots")
+        _hip.check(self._L.td_qwen2_gather_slots(self._h, n, ctypes.cast(sl, ctypes.c_void_p), _hip.ptr(src), ctypes.cast(ln, ctypes.c_void_p), _hip.stream_ptr()))
+
+    # ---- beam search ([ext] vllm.LLM.beam_search) ------------------------------------------------------------------------------------------
+    def _beam_prefill(self, requests, slots, plen, poss):
+        """Each prompt once into its request's first cache slot, the way generate_batch prefills: packed passes (td_qwen2_prefill_packed_slots) where
+        several prompts fit the workspace, one forward per prompt otherwise.  -> (prompt hidden states per request, logits bf16 [R, vocab])."""
+        R, D = len(requests), self.config.hidden_size
+        logits = torch.empty(R, self.config.vocab_size, dtype=torch.bfloat16, device=self.device)
+        hidden = [None] * R
+        if R > 1 and self.packed_prefill and max(plen) <= min(self.slot_len, self.prefill_rows):
+            b0 = 0
+            while b0 < R:
+                nb, rows = 0, 0
+                while b0 + nb < R and nb < self.MAX_BATCH and rows + plen[b0 + nb] <= self.prefill_rows:
+                    rows += plen[b0 + nb]
+                    nb += 1
+                emb = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
+                pos = torch.empty(3, rows, dtype=torch.int32)
+                r = 0
+                for j in range(b0, b0 + nb):
+                    e = requests[j].get("inputs_embeds")
+                    emb[r:r + plen[j]] = self.embed_tokens(requests[j]["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
+                    pos[:, r:r + plen[j]] = poss[j].to(torch.int32)
+                    r += plen[j]
+                pos = pos.to(self.device).contiguous()
+                hid = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
+                self._prefill_packed_slots(nb, (ctypes.c_int * nb)(*slots[b0:b0 + nb]), emb, pos, (ctypes.c_int * nb)(*plen[b0:b0 + nb]), hid, logits[b0:b0 + nb])
+                r = 0
+                for j in range(b0, b0 + nb):
+                    hidden[j] = hid[r:r + plen[j]]
+                    r += plen[j]
+                b0 += nb
+        else:
+            for j, (q, p) in enumerate(zip(requests, poss)):
+                e = q.get("inputs_embeds")
+                hidden[j], lg = self.forward(p, torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, True, slot=slots[j])
+                logits[j] = lg
+        return hidden, logits
+
+    @torch.no_grad()
+    def beam_search(self, requests: Sequence[dict], params: BeamSearchParams, eos_token_id: Optional[int] = None):
+        """vLLM's `LLM.beam_search` for R requests (the dicts of generate_batch) with W = params.beam_width beams each, on R x W cache slots: request r
+        owns slots r W .. r W + W - 1 and is prefilled once, into the first.  Then T = max_tokens rounds of
+
+            logprobs_rows(2 W) -> beam_select -> gather_slots -> decode step (device tokens, fixed slots, host-known cache lengths)
+
+        are ENQUEUED without a synchronisation: the choice of the next beams, their placement and the reordering of the cache rows all happen on
+        the device (td_beam_select, td_kv_gather_rows; the first round's gather is the fork of the prompt), and the per-step logs [T, R W] are read
+        once after the loop.  The host then walks the `parent` chains.
+
+        A candidate equal to EOS (eos_token_id, unless ignore_eos) completes a sequence instead of becoming a beam: a finisher logged at round s is
+        s + 1 tokens ending in EOS, with hidden states for the s tokens before it -- the EOS is never fed to the decoder.  Per request the completed
+        sequences (in creation order) and then the live beams (by rank) are sorted stably by score = cum / seq_len ** length_penalty, descending,
+        where seq_len = prompt length + generated tokens, less one if the last token is EOS; the first W are returned.
+
+        -> per request a dict with generate()'s keys for output 0 ("prompt_hidden_states", "hidden_states", "token_ids"), "cumulative_logprob", "score"
+        and "outputs": W dicts with "index", "token_ids", "hidden_states", "cumulative_logprob", "score", "finished"."""
+        params.validate()
+        R, W, T = len(requests), int(params.beam_width), int(params.max_tokens)
+        n_slots = getattr(self, "n_slots", 1)
+        if R < 1:
+            raise ValueError("beam_search: no requests")
+        if R * W > min(self.MAX_BATCH, n_slots):
+            raise _hip.ThinkDiffHipError(f"beam_search: {R} requests x beam_width={W} need {R * W} cache slots, which exceed min({self.MAX_BATCH}, n_slots={n_slots}); "
+                                         "call set_slots first")
+        plen = [len(r["prompt_token_ids"]) for r in requests]
+        for i, n in enumerate(plen):
+            if n < 1:
+                raise ValueError(f"beam_search: request {i} has an empty prompt")
+            if n + T > self.slot_len:
+                raise _hip.ThinkDiffHipError(f"beam_search: request {i}: prompt length {n} + max_tokens={T} exceeds the slot capacity {self.slot_len}")
+        V, D = self.config.vocab_size, self.config.hidden_size
+        if V <= 2 * W:
+            raise ValueError(f"beam_search: vocab_size={V} must exceed 2 x beam_width = {2 * W}: a step takes the 2 x beam_width most probable tokens of a row")
+        if eos_token_id is not None and not 0 <= int(eos_token_id) < V:
+            raise ValueError(f"beam_search: eos_token_id={eos_token_id} outside the vocabulary of {V}")
+        import numpy as np
+        eos = -1 if (params.ignore_eos or eos_token_id is None) else int(eos_token_id)
+        N, dev = R * W, self.device
+        poss = [self.text_position_ids(n) if r.get("position_ids") is None else r["position_ids"] for r, n in zip(requests, plen)]
+        next_pos = [int(p.max()) + 1 for p in poss]
+        prompt_hidden, logits0 = self._beam_prefill(requests, [r * W for r in range(R)], plen, poss)
+        # what the loop needs from the host, uploaded before it starts: the rows' M-RoPE positions of every round and the first round's live rows
+        first = torch.arange(R, dtype=torch.int64) * W
+        logits = torch.zeros(N, V, dtype=torch.bfloat16, device=dev)
+        logits[first.to(dev)] = logits0
+        pos_all = (torch.tensor(next_pos, dtype=torch.int32).repeat_interleave(W)[None, None, :] + torch.arange(T, dtype=torch.int32)[:, None, None]) \
+            .expand(T, 3, N).contiguous().to(dev)
+        n_top0 = torch.full((N,), -1, dtype=torch.int32)
+        n_top0[first] = 2 * W
+        n_top0, n_top = n_top0.to(dev), torch.full((N,), 2 * W, dtype=torch.int32).to(dev)
+        no_ids = torch.zeros(N, dtype=torch.int32, device=dev)      # (td_logprobs_rows_bf16 also scores a chosen token per row: unused here)
+        ilog = torch.empty(5, T, N, dtype=torch.int32, device=dev)      # token, rank, copy_src, parent, fin_flag
+        flog = torch.empty(2, T, N, dtype=torch.float32, device=dev)    # cum, fin_cum
+        cum0, rank0 = torch.zeros(N, dtype=torch.float32, device=dev), torch.zeros(N, dtype=torch.int32, device=dev)
+        hid_all = torch.empty(T, N, D, dtype=torch.bfloat16, device=dev)
+        slots_np = np.arange(N, dtype=np.int32)
+        base_len = np.repeat(np.asarray(plen, dtype=np.int32), W)
+        for s in range(T):
+            _, _, top_ids, top_lp = _OPS.logprobs_rows(logits, no_ids, n_top0 if s == 0 else n_top, 2 * W)
+            _OPS.beam_select(top_ids, top_lp, cum0 if s == 0 else flog[0, s - 1], rank0 if s == 0 else ilog[1, s - 1], W, 1 if s == 0 else W, eos,
+                             ilog[0, s], flog[0, s], ilog[1, s], ilog[2, s], ilog[3, s], ilog[4, s], flog[1, s])
+            cache_np = base_len + np.int32(s)
+            self.gather_slots(slots_np, ilog[2, s], cache_np)
+            # every row decodes: vocab > 2 W leaves each live row at least 2 W - 1 >= W candidates that are not EOS, so no beam is ever missing (token -1)
+            self._decode_slots(N, slots_np, ilog[0, s], pos_all[s], cache_np, hid_all[s], logits)
+        ilog_h, flog_h = ilog.cpu().numpy(), flog.cpu().numpy()      # the one download
+        tok_l, rank_l, par_l, fin_l, cum_l, fcum_l = ilog_h[0], ilog_h[1], ilog_h[3], ilog_h[4], flog_h[0], flog_h[1]
+
+        def chain(s, row):
+            """The tokens of the beam living in `row` after round s, and where their hidden rows lie in hid_all.view(T N, D)."""
+            toks, idx = [], []
+            while s >= 0:
+                toks.append(int(tok_l[s, row]))
+                idx.append(s * N + row)
+                row, s = int(par_l[s, row]), s - 1
+            return toks[::-1], idx[::-1]
+
+        results, picks = [], []
+        for r in range(R):
+            seqs = []      # (tokens, hidden rows, cum, finished): completed sequences in creation order, then the live beams by rank
+            for s in range(T):
+                rows = [r * W] if s == 0 else sorted(range(r * W, r * W + W), key=lambda q: int(rank_l[s - 1, q]))
+                for q in rows:
+                    if fin_l[s, q]:
+                        toks, idx = chain(s - 1, q) if s else ([], [])
+                        seqs.append((toks + [eos], idx, float(fcum_l[s, q]), True))
+            for q in sorted(range(r * W, r * W + W), key=lambda q: int(rank_l[T - 1, q])):
+                toks, idx = chain(T - 1, q)
+                seqs.append((toks, idx, float(cum_l[T - 1, q]), False))
+            scored = [(params.score(c, plen[r] + len(t) - (1 if eos_token_id is not None and t[-1] == int(eos_token_id) else 0)), t, i, c, f) for t, i, c, f in seqs]
+            scored.sort(key=lambda x: -x[0])      # (stable: ties keep the order above)
+            picks.append(scored[:W])
+        flat = [i for pk in picks for _, _, idx, _, _ in pk for i in idx]
+        parts = iter(torch.split(hid_all.view(T * N, D).index_select(0, torch.tensor(flat, dtype=torch.int64).to(dev)),
+                                 [len(idx) for pk in picks for _, _, idx, _, _ in pk]))
+        for r, pk in enumerate(picks):
+            outs = [{"index": k, "token_ids": t, "hidden_states": next(parts), "cumulative_logprob": c, "score": sc, "finished": f}
+                    for k, (sc, t, _, c, f) in enumerate(pk)]
+            results.append({"prompt_hidden_states": prompt_hidden[r], "hidden_states": outs[0]["hidden_states"], "token_ids": outs[0]["token_ids"],
+                            "cumulative_logprob": outs[0]["cumulative_logprob"], "score": outs[0]["score"], "outputs": outs})
+        return results
 
     def move_slot(self, src: int, dst: int, length: int):
         """Copy the first `length` cache rows of slot `src` to slot `dst` (td_qwen2_move_slot).  The decode steps name their slots, so nothing in this

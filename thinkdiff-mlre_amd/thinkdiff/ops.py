@@ -57,6 +57,10 @@ kv_quant_rows_e4m3 / kv_dequant_rows_e4m3 / attention_decode_kv8   the e4m3 KV c
                            power-of-two scale per 128-wide head vector of a cache row, back to bf16 (exact), and the decode attention that reads bytes + scales
 kv_fork_rows               the first n_rows rows of one slot of a cache plane copied to many slots in one launch, each source chunk loaded once (what vLLM's
                            `n` / `best_of` share through block tables is a copy here: the slots are a fixed partition); in place, any dtype
+kv_gather_rows             row j of a launch takes the first n_rows[j] rows of the slot of row copy_src[j], a DEVICE int32 tensor (-1: nothing): the reordering of
+                           cache slots behind a beam-search step, with no host round trip; in place, any dtype
+beam_select                one beam-search step on the device (vLLM's `LLM.beam_search` loop): the next W beams out of W x 2W candidates (logprobs_rows with
+                           n_top = 2W), EOS candidates set aside as finishers, and a slot-stable placement whose copies kv_gather_rows does in one launch
 """
 import os
 
@@ -118,6 +122,9 @@ SCHEMAS = {
     "kv_dequant_rows_e4m3": "(Tensor q, Tensor scale) -> Tensor",
     "attention_decode_kv8": "(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor",
     "kv_fork_rows": "(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()",
+    "kv_gather_rows": "(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()",
+    "beam_select": "(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, "
+                   "Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()",
 }
 
 _loaded = False
