@@ -38,6 +38,41 @@ def expected_tokens(prompt, seed, n_tokens, temperature=1.0):
     return out
 
 
+class _History:
+    """Stands in for thinkdiff._hip.Sampler (the penalties' token history): logs the resets."""
+    handle = 0xBEEF
+
+    def __init__(self, calls):
+        self.calls = calls
+
+    def reset_slot(self, slot, prompt_ids=None):
+        self.calls.append(["history_reset", int(slot), [int(t) for t in (prompt_ids or [])]])
+
+
+class _Edits:
+    """Stands in for thinkdiff._hip.LogitEdits: keeps each slot's banned set and bias, logs the calls."""
+    handle = 0xED17
+
+    def __init__(self, calls):
+        self.calls, self.banned, self.bias = calls, {}, {}
+
+    def reset_slot(self, slot):
+        self.calls.append(["edit_reset", int(slot)])
+        self.banned[slot], self.bias[slot] = set(), {}
+
+    def set_bias(self, slot, bias):
+        self.calls.append(["edit_bias", int(slot), sorted(bias)])
+        self.bias[slot] = dict(bias)
+
+    def ban(self, slot, ids, on=True):
+        self.calls.append(["edit_ban", int(slot), [int(t) for t in ids], bool(on)])
+        self.banned[slot] = (self.banned[slot] | set(ids)) if on else (self.banned[slot] - set(ids))
+
+    def allow_only(self, slot, ids):
+        self.calls.append(["edit_allow", int(slot), [int(t) for t in ids]])
+        self.banned[slot] = set(range(V)) - set(ids)
+
+
 def fake_engine(n_slots, slot_len=64, prefill_rows=96):
     from thinkdiff import _hip
     from thinkdiff.models import qwen2_vl as Q
@@ -57,9 +92,16 @@ def fake_engine(n_slots, slot_len=64, prefill_rows=96):
             self.forks = []          # (src, dst slots, length)
             self.calls = []          # every engine call, for the comparison with the parent commit's trace
             self.tables = []         # (seed, stream, slot) per live row of every sample_rows call
+            self.history, self.edits = _History(self.calls), _Edits(self.calls)
 
         def __del__(self):
             pass
+
+        def _sampler_state(self):
+            return self.history
+
+        def _logit_edits(self):
+            return self.edits
 
         def embed_tokens(self, token_ids):
             out = torch.zeros(len(token_ids), D, dtype=torch.bfloat16)
@@ -147,6 +189,7 @@ def fake_engine(n_slots, slot_len=64, prefill_rows=96):
         return [(int(a.seed), int(a.stream), int(a.slot), float(a.temperature)) for a in arr]
 
     def sample_top_p(logits, temperature, top_p, key, step):
+        logits = logits.reshape(-1, V)      # (the op takes one row as [vocab] too)
         e.calls.append(["sample_top_p", logits.shape[0], int(step)])
         return logits.float().argmax(dim=1).to(torch.int32)
 
@@ -159,13 +202,27 @@ def fake_engine(n_slots, slot_len=64, prefill_rows=96):
         return torch.tensor([(t + (5 * seed + 3 * int(o) + stream if temp > 0 else 0)) % V
                              for t, (seed, stream, _, temp), o in zip(top, rows, offsets.tolist())], dtype=torch.int32)
 
+    def sample_rows_edit(logits, params, offsets, state, update_state, edits, edit_slots):
+        rows = rows_of(params)
+        assert edits == _Edits.handle and len(rows) == logits.shape[0] == offsets.numel() == edit_slots.numel()
+        e.calls.append(["sample_rows_edit", [list(r[:2]) for r in rows], offsets.tolist(), edit_slots.tolist()])
+        z = logits.float().clone()
+        for i, s in enumerate(edit_slots.tolist()):
+            if s >= 0:
+                for t, b in e.edits.bias[s].items():
+                    z[i, t] += b
+                if e.edits.banned[s]:
+                    z[i, sorted(e.edits.banned[s])] = float("-inf")
+        return torch.tensor([(t + (5 * seed + 3 * int(o) + stream if temp > 0 else 0)) % V
+                             for t, (seed, stream, _, temp), o in zip(z.argmax(dim=1).tolist(), rows, offsets.tolist())], dtype=torch.int32)
+
     def logprobs_rows(logits, ids, n_top, top_cap):
         n = logits.shape[0]
         e.calls.append(["logprobs_rows", n_top.tolist(), int(top_cap)])
         lp = torch.tensor([token_score(t) for t in ids.tolist()], dtype=torch.float32)
         return lp, torch.ones(n, dtype=torch.int32), torch.full((n, top_cap), -1, dtype=torch.int32), torch.full((n, top_cap), float("-inf"))
 
-    ops = SimpleNamespace(sample_top_p=sample_top_p, sample_rows=sample_rows, logprobs_rows=logprobs_rows)
+    ops = SimpleNamespace(sample_top_p=sample_top_p, sample_rows=sample_rows, sample_rows_edit=sample_rows_edit, logprobs_rows=logprobs_rows)
     return e, Q, ops
 
 
@@ -208,3 +265,110 @@ def run_n1_trace(extra):
         res = run(e, Q)
         out[name] = {"calls": e.calls, "token_ids": [r["token_ids"] for r in res]}
     return out
+
+
+# ---- the decode entries, call for call ----------------------------------------------------------------------------------------------------------
+def entry_scenarios():
+    """The calls tests/golden/decode_entries_calls.json records of the commit before the three generate loops were folded onto one token source, one
+    prompt prefill and one live-row table: (name, engine keywords, run(e, Q) -> results) on the stand-in above, and two beam searches on
+    beam_search_common.fake_engine (engine keywords with "beam": True).  Prompts of 1..8 tokens and prefill_rows = 8 throughout."""
+    reqs = prompts(11)
+    six = reqs[:6]
+    std = dict(n_slots=8, slot_len=32, prefill_rows=8)
+    p0 = six[2]["prompt_token_ids"]
+    t1 = next_token(p0[-1])
+    t2, t3 = next_token(t1), next_token(next_token(t1))
+    firsts = [next_token(r["prompt_token_ids"][-1]) for r in reqs]      # request i's first token at temperature 0
+    out = []
+
+    def add(name, run, **kw):
+        out.append((name, {**std, **kw}, run))
+
+    # generate
+    add("generate_top_p", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=0.0, max_tokens=5, min_tokens=5)))
+    add("generate_rows_seed_penalty", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=1.0, seed=3, repetition_penalty=1.2, max_tokens=4, min_tokens=1)))
+    add("generate_forced_short", lambda e, Q: e.generate(p0, Q.SamplingParams(max_tokens=5, min_tokens=5), forced_output_ids=[5, 6, 7]))
+    add("generate_forced_long", lambda e, Q: e.generate(p0, Q.SamplingParams(max_tokens=4, min_tokens=4, logprobs=0), forced_output_ids=[5, 6, 7, 8, 9, 10]))
+    add("generate_logprobs", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=0.0, max_tokens=3, min_tokens=3, logprobs=1)))
+    add("generate_stop_around_min_tokens", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=0.0, max_tokens=6, min_tokens=2, stop_token_ids=[t1, t3])))
+    add("generate_eos", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=0.0, max_tokens=6, min_tokens=1, ignore_eos=False), eos_token_id=t2))
+    add("generate_n3", lambda e, Q: e.generate(p0, Q.SamplingParams(temperature=1.0, seed=11, n=3, max_tokens=3, min_tokens=1)))
+
+    # generate_batch, 6 requests
+    add("batch_top_p_eos_stops", lambda e, Q: e.generate_batch(six, Q.SamplingParams(
+        temperature=0.0, max_tokens=6, min_tokens=2, ignore_eos=False, stop_token_ids=[next_token(firsts[1]), next_token(next_token(firsts[3])), firsts[4]]),
+        eos_token_id=next_token(next_token(next_token(firsts[0])))))
+    add("batch_list_seeds_budgets_logprobs", lambda e, Q: e.generate_batch(six, [
+        Q.SamplingParams(temperature=1.0, seed=7 * i if i % 2 else None, max_tokens=i % 5, min_tokens=1, logprobs=1 if i % 3 == 0 else None) for i in range(6)]))
+    add("batch_forced", lambda e, Q: e.generate_batch(six, Q.SamplingParams(max_tokens=3, min_tokens=3),
+                                                      forced_output_ids=[[(10 * i + j) % V for j in range(i)] for i in range(6)]))
+    add("batch_mixed_n_best_of", lambda e, Q: e.generate_batch(six, [
+        Q.SamplingParams(temperature=1.0, seed=30 + i if i != 4 else None, max_tokens=2 + i % 3, min_tokens=1, n=(1, 3, 1, 2, 1, 1)[i], best_of=4 if i == 3 else None)
+        for i in range(6)]), n_slots=12)
+    add("batch_bad_words_and_bias", lambda e, Q: e.generate_batch(six, [
+        Q.SamplingParams(temperature=0.0, max_tokens=4, min_tokens=4, bad_words_token_ids=[[firsts[0], next_token(firsts[0])]] if i == 0 else None,
+                         logit_bias={5: 100.0} if i == 1 else None) for i in range(6)]))
+    add("batch_reaches_slot_len", lambda e, Q: e.generate_batch(six, Q.SamplingParams(temperature=0.0, max_tokens=6, min_tokens=6)), slot_len=10)
+
+    # generate_continuous, 11 requests
+    for name, run in n1_scenarios({}):
+        add("n1_" + name, run)
+    add("continuous_mixed_n_chunks", lambda e, Q: e.generate_continuous(iter([reqs[:4], reqs[4:9], reqs[9:]]), [
+        Q.SamplingParams(temperature=1.0, seed=20 + i if i % 4 else None, max_tokens=2 + i % 3, min_tokens=1, n=(1, 3, 2)[i % 3] if i % 4 != 3 else 1,
+                         best_of=2 if i % 4 == 3 else None) for i in range(11)], max_live=4, admit_min=2))
+    add("continuous_forced_with_empty", lambda e, Q: e.generate_continuous(reqs, Q.SamplingParams(max_tokens=13, min_tokens=13),
+                                                                            forced_output_ids=[[(10 * i + j) % V for j in range((2 * i) % 5)] for i in range(11)],
+                                                                            max_live=3, admit_min=1))
+    add("continuous_best_of_3", lambda e, Q: e.generate_continuous(reqs, Q.SamplingParams(temperature=1.0, seed=9, n=1, best_of=3, max_tokens=4, min_tokens=1),
+                                                                    max_live=7, admit_min=1))
+    add("continuous_list_logprobs", lambda e, Q: e.generate_continuous(reqs, [
+        Q.SamplingParams(temperature=0.0 if i % 4 == 0 else 1.0, logprobs=i % 3 if i % 2 else None, max_tokens=2 + i % 4, min_tokens=1, ignore_eos=bool(i % 3),
+                         stop_token_ids=[next_token(firsts[i])] if i % 4 == 0 else None) for i in range(11)], eos_token_id=4, max_live=5, admit_min=2))
+
+    # beam_search
+    bp = [[1, 2, 3], [4, 5, 6, 7, 0, 9, 10], [8]]
+    out.append(("beam_r3_w2_eos", dict(beam=True, n_slots=6, slot_len=32, prefill_rows=8),
+                lambda e, Q: e.beam_search([{"prompt_token_ids": p} for p in bp], Q.BeamSearchParams(beam_width=2, max_tokens=4), eos_token_id=3)))
+    out.append(("beam_r1_w3_ignore_eos", dict(beam=True, n_slots=3, slot_len=32, prefill_rows=8),
+                lambda e, Q: e.beam_search([{"prompt_token_ids": bp[1]}], Q.BeamSearchParams(beam_width=3, max_tokens=5, ignore_eos=True), eos_token_id=3)))
+    return out
+
+
+def _summary(res):
+    """What a scenario's record keeps of the results: token ids, and per output the token ids and the cumulative logprob where present."""
+    out = []
+    for r in (res if isinstance(res, list) else [res]):
+        d = {"token_ids": [int(t) for t in r["token_ids"]]}
+        if "cumulative_logprob" in r:
+            d["cumulative_logprob"] = float(r["cumulative_logprob"])
+        if "outputs" in r:
+            d["outputs"] = [{k: ([int(t) for t in o[k]] if k == "token_ids" else float(o[k])) for k in ("token_ids", "cumulative_logprob") if k in o} for o in r["outputs"]]
+        out.append(d)
+    return out
+
+
+def run_entries_trace(set_ops):
+    """-> {scenario: {"calls": the stand-in's call log, "results": _summary}} on fresh stand-in engines.  set_ops(Q, ops) puts the stand-in's ops in
+    place of torch.ops.thinkdiff_hip; the sampler key is patched by the caller, as for run_n1_trace."""
+    import json
+
+    import beam_search_common as B
+    out = {}
+    for name, kw, run in entry_scenarios():
+        kw = dict(kw)
+        e, Q, ops = (B.fake_engine if kw.pop("beam", False) else fake_engine)(**kw)
+        set_ops(Q, ops)
+        out[name] = json.loads(json.dumps({"calls": e.calls, "results": _summary(run(e, Q))}))
+    return out
+
+
+if __name__ == "__main__":      # python tests/parallel_sampling_common.py OUT.json: how tests/golden/decode_entries_calls.json was written, at the parent commit
+    import json
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "thinkdiff-mlre_amd"))
+    from thinkdiff.models import qwen2_vl as _Q
+    _Q.Qwen2VLTextEngine._draw_sampler_key = staticmethod(lambda generator=None: KEY)
+    with open(sys.argv[1], "w") as fh:
+        json.dump(run_entries_trace(lambda Q, ops: setattr(Q, "_OPS", ops)), fh, separators=(",", ":"))
+        fh.write("\n")

@@ -11,8 +11,10 @@ import collections
 import ctypes
 import dataclasses
 import numbers
+from collections import deque
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from .. import _hip
@@ -460,6 +462,168 @@ class _LogprobLog:
             r0 += len(owners)
 
 
+class _TokenSource:
+    """Where the tokens of one generate call's steps come from, for all three entries: the teacher-forced ids, the per-request sampler (_RowSampling,
+    admitted per slot, its table rewritten lazily after the live set changed) or the one plain launch (td_sample_top_p_bf16) under the call's ONE
+    sampler key, and the logprobs of what was chosen (_LogprobLog).  sp_of(s): the SamplingParams of sequence s; forced[s]: its forced ids (None: the
+    call samples); want: SamplingParams.logprobs per sequence, one int for every sequence, or None when nobody asked."""
+
+    def __init__(self, engine, sampling, by_rows, sp_of, eos_token_id, generator, forced, want):
+        self.engine, self.sampling, self.sp_of, self.forced = engine, sampling, sp_of, forced
+        self.key = None if forced is not None else engine._draw_sampler_key(generator)
+        self.rows = _RowSampling(engine, self.key, eos_token_id) if by_rows and forced is None else None      # (forced decoding does not sample and keeps no history)
+        self.lplog = _LogprobLog(engine, want) if want is not None else None      # (forced tokens are scored too)
+        self.live_changed = True
+
+    def admit(self, slot, sp, prompt_ids):
+        """A sequence starts in cache slot `slot`: that slot's history and logit edits start over."""
+        if self.rows is not None:
+            self.rows.admit(slot, sp, prompt_ids)
+        self.live_changed = True
+
+    def next(self, logits, step, ngen, owners, slots):
+        """logits [n, vocab] of the live rows; step: the call's decode step; ngen[i], owners[i], slots[i]: tokens generated so far, sequence and cache
+        slot of live row i.  -> (device int32 [n] tokens, the same ids as a host array where the host already holds them -- forced ids, or a bad
+        word of several tokens had them read -- else None: a caller that needs them downloads them itself)."""
+        host = None
+        if self.forced is not None:
+            host = np.array([self.forced[o][g] for o, g in zip(owners, ngen)], dtype=np.int32)
+            tok = torch.from_numpy(host).to(self.engine.device)
+        elif self.rows is not None:
+            if self.live_changed:
+                self.rows.set_live([(self.sp_of(int(o)), int(s)) for o, s in zip(owners, slots)])
+            tok = self.rows.sample(logits, step, ngen)
+            if any(plan.needs_tokens for _, _, plan in self.rows.live_plans):
+                host = tok.cpu().numpy()
+            self.rows.advance(tok if host is None else host)
+        else:
+            tok = _OPS.sample_top_p(logits, float(self.sampling.temperature), float(self.sampling.top_p), int(self.key), int(step))
+        self.live_changed = False
+        if self.lplog is not None:
+            self.lplog.add(logits, tok, owners)
+        return tok, host
+
+    def finish(self, res):
+        """res[s]["logprobs"] and ["cumulative_logprob"] of the sequences that asked: present only then."""
+        if self.lplog is not None:
+            self.lplog.finish(res)
+
+
+class _LiveRows:
+    """The live sequences of generate_batch and generate_continuous and their one decode step.  Per live row (numpy, rows [0, n)): sequence, cache
+    slot, cached tokens, next position id, tokens generated, token budget, min_tokens and stop ids; logits[i] = the next-token logits of live row i.
+    The per-step bookkeeping is vectorised and the arrays are handed to the C ABI as they are: at 256 sequences the Python-list form cost ~2 ms of
+    host time per step, about as much as the step takes on the GPU, which idles while the host prepares the next launch.  The hidden rows of a step
+    stay ONE device tensor and are handed to their sequences by a single gather after the loop (results).
+
+    What the two entries do differently is all in what they pass to admit() and when they call it:
+      budget           generate_batch: min(max_tokens, len(forced ids)), and a sequence with budget 0 is prefilled but never live; generate_continuous:
+                       len(forced ids) alone under forced ids, and a request with budget 0 is never admitted (a prompt-only forward);
+      sampler offsets  the step counts every decode step of the call and seeded rows draw at their own token count: generate_batch admits once, so
+                       both are its loop index; generate_continuous admits between steps, so they differ;
+      slot capacity    both retire a sequence silently when its slot is full (generate, the single-sequence entry, lets the native check raise);
+      prompts          a prompt that fits no prefill pass is served by generate_batch (one forward) and refused by generate_continuous."""
+
+    def __init__(self, engine, capacity, source, eos_token_id):
+        self.engine, self.src, self.eos = engine, source, eos_token_id
+        self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint = (np.zeros(capacity, dtype=np.int32) for _ in range(7))
+        self.stops = np.empty(capacity, dtype=object)
+        self.n, self.step_no, self.any_stop = 0, 0, False
+        self.logits = torch.empty(capacity, engine.config.vocab_size, dtype=torch.bfloat16, device=engine.device)
+        self.step_hid, self.step_owner, self.step_toks = [], [], []
+
+    def admit(self, seq0, widths, slots, lens, npos, budgets, prompts, free_slots):
+        """k requests were just prefilled: request j into cache slot slots[j], lens[j] prompt tokens, generation continuing at position npos[j], its
+        prefill logits in self.logits[n + j].  It runs as the sequences seq0[j] .. seq0[j] + widths[j] - 1 with budgets[j] tokens each: the first
+        on its slot, the children (n / best_of) on the next slots popped from free_slots -- after all k parents took theirs -- which start from a copy
+        of the prompt's cache rows (one launch per request, td_qwen2_fork_slot) and of its row of logits."""
+        n, k, used = self.n, len(slots), sum(widths)
+        rep = [j for j in range(k) for _ in range(widths[j])]
+        seqs = [s for j in range(k) for s in range(seq0[j], seq0[j] + widths[j])]
+        if used > k:
+            seq_slots = []
+            for j in range(k):
+                kids = [free_slots.pop() for _ in range(widths[j] - 1)]
+                if kids:
+                    self.engine._fork_slots(slots[j], kids, lens[j])
+                seq_slots += [slots[j]] + kids
+            self.logits[n:n + used] = self.logits[n:n + k].index_select(0, torch.tensor(rep, dtype=torch.int64).to(self.logits.device))
+            slots = seq_slots
+        sps = [self.src.sp_of(s) for s in seqs]
+        for sp, sl, j in zip(sps, slots, rep):
+            self.src.admit(sl, sp, prompts[j])
+        live = [r for r, j in enumerate(rep) if budgets[j] > 0]
+        if len(live) < used:
+            self.logits[n:n + len(live)] = self.logits[n:n + used].index_select(0, torch.tensor(live, dtype=torch.int64).to(self.logits.device))
+        m = n + len(live)
+        self.own[n:m] = [seqs[r] for r in live]
+        self.slt[n:m] = [slots[r] for r in live]
+        self.clen[n:m] = [lens[rep[r]] for r in live]
+        self.npos[n:m] = [npos[rep[r]] for r in live]
+        self.ngen[n:m] = 0
+        self.lim[n:m] = [budgets[rep[r]] for r in live]
+        self.mint[n:m] = [sps[r].min_tokens for r in live]
+        for i, r in zip(range(n, m), live):      # (forced ids run to their end: no stop rule)
+            sp = sps[r]
+            self.stops[i] = set() if self.src.forced is not None else \
+                set(sp.stop_token_ids or []) | ({self.eos} if not sp.ignore_eos and self.eos is not None else set())
+            self.any_stop |= bool(self.stops[i])
+        self.n = m
+
+    def step(self):
+        """One token for every live sequence: choose it, decode it (one pass over the weights, td_qwen2_decode_batch_slots), apply the stop rule
+        and close the gaps of the finished rows (the order of the others is kept: no cache rows move).  -> the freed cache slots, highest first."""
+        n, dev = self.n, self.engine.device
+        tok_dev, toks = self.src.next(self.logits[:n], self.step_no, self.ngen[:n], self.own[:n], self.slt[:n])
+        if toks is None:
+            toks = tok_dev.cpu().numpy()      # (the host sees the ids once per step, for the stop rule and the results)
+        pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(self.npos[:n], (3, n)))).to(dev)
+        hid = torch.empty(n, self.engine.config.hidden_size, dtype=torch.bfloat16, device=dev)
+        self.engine._decode_slots(n, self.slt, tok_dev, pos_dev, self.clen, hid, self.logits)      # logits of row i -> logits[i]
+        self.step_hid.append(hid)
+        self.step_owner.append(self.own[:n].copy())
+        self.step_toks.append(toks)
+        self.clen[:n] += 1
+        self.npos[:n] += 1
+        self.ngen[:n] += 1
+        self.step_no += 1
+        done = (self.ngen[:n] >= self.lim[:n]) | (self.clen[:n] >= self.engine.slot_len)
+        if self.any_stop:
+            hit = np.fromiter((int(t) in s for t, s in zip(toks, self.stops[:n])), dtype=bool, count=n)
+            done |= hit & (self.ngen[:n] >= self.mint[:n])
+        if not done.any():
+            return []
+        keep = np.nonzero(~done)[0]
+        freed = sorted((int(x) for x in self.slt[:n][done]), reverse=True)
+        k = keep.size
+        for arr in (self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint, self.stops):
+            arr[:k] = arr[:n][keep]
+        if k:
+            self.logits[:k] = self.logits[:n].index_select(0, torch.from_numpy(keep).to(dev))
+        self.src.live_changed = True
+        self.n = k
+        return freed
+
+    def results(self, res):
+        """res[s]["hidden_states"] and ["token_ids"] of every sequence s (one gather: rows grouped by sequence, in step order inside a sequence),
+        then the logprobs of those that asked."""
+        D, dev = self.engine.config.hidden_size, self.engine.device
+        if self.step_owner:
+            owners_all = np.concatenate(self.step_owner)
+            order = np.argsort(owners_all, kind="stable")
+            counts = np.bincount(owners_all, minlength=len(res)).tolist()
+            parts = torch.split(torch.cat(self.step_hid).index_select(0, torch.from_numpy(order).to(dev)), counts)
+            toks_sorted = np.concatenate(self.step_toks)[order].tolist()
+            r0 = 0
+            for r, part, c in zip(res, parts, counts):
+                r["hidden_states"], r["token_ids"] = part, toks_sorted[r0:r0 + c]
+                r0 += c
+        else:
+            for r in res:
+                r["hidden_states"] = torch.empty(0, D, dtype=torch.bfloat16, device=dev)
+        self.src.finish(res)
+
+
 class Qwen2VLTextEngine:
     dtype = torch.bfloat16
 
@@ -518,20 +682,20 @@ class Qwen2VLTextEngine:
         """The edit slots behind logit_bias, allowed_token_ids, bad words and the min_tokens stop mask (td_logit_edits, one slot per cache slot),
         created the first time a request with an edit arrives: n_slots x (2 x vocab / 8 + 8196) bytes of device memory (11.8 MB at 256 x 152 064)."""
         ed = getattr(self, "_edits", None)
-        if ed is None or ed.n_slots != max(1, getattr(self, "n_slots", 1)):
+        if ed is None or ed.n_slots != max(1, self.n_slots):
             if ed is not None:
                 ed.close()
-            ed = self._edits = _hip.LogitEdits(max(1, getattr(self, "n_slots", 1)), self.config.vocab_size, self.device)
+            ed = self._edits = _hip.LogitEdits(max(1, self.n_slots), self.config.vocab_size, self.device)
         return ed
 
     def _sampler_state(self):
         """The token history behind the penalties (td_sampler, one slot per cache slot), created the first time a request with a penalty arrives:
         n_slots x vocab x 2.25 bytes of device memory (87.6 MB at 256 x 152 064)."""
         st = getattr(self, "_sampler", None)
-        if st is None or st.n_slots != max(1, getattr(self, "n_slots", 1)):
+        if st is None or st.n_slots != max(1, self.n_slots):
             if st is not None:
                 st.close()
-            st = self._sampler = _hip.Sampler(max(1, getattr(self, "n_slots", 1)), self.config.vocab_size, self.device)
+            st = self._sampler = _hip.Sampler(max(1, self.n_slots), self.config.vocab_size, self.device)
         return st
 
     # ---- parameters (Hugging Face names) -----------------------------------------------------------------
@@ -757,54 +921,37 @@ class Qwen2VLTextEngine:
             if forced_output_ids is not None:
                 raise ValueError(f"generate: forced_output_ids with SamplingParams n={sampling.n}, best_of={sampling.best_of}: a teacher-forced "
                                  "continuation is one sequence")
-            if getattr(self, "n_slots", 1) < sampling.width:
+            if self.n_slots < sampling.width:
                 raise _hip.ThinkDiffHipError(f"generate: SamplingParams n={sampling.n}, best_of={sampling.best_of} needs {sampling.width} cache slots, "
-                                             f"n_slots={getattr(self, 'n_slots', 1)}; call set_slots first")
+                                             f"n_slots={self.n_slots}; call set_slots first")
             return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds}], sampling,
                                        eos_token_id=eos_token_id, generator=generator)[0]
         n_p = len(prompt_token_ids)
         pos = self.text_position_ids(n_p) if position_ids is None else position_ids
         next_pos = int(pos.max()) + 1      # M-RoPE: generation continues one past the largest prompt position
         tok = torch.tensor(list(prompt_token_ids), dtype=torch.int32)
-        prompt_hidden, logits = self.forward(pos, tok if inputs_embeds is None else None, inputs_embeds, 0, True, True)
+        prompt_hidden, lg = self.forward(pos, tok if inputs_embeds is None else None, inputs_embeds, 0, True, True)
+        logits = lg[None]
         out_tok, out_hidden = [], []
-        stops = set(sampling.stop_token_ids or [])
-        can_stop = forced_output_ids is None and (bool(stops) or ((not sampling.ignore_eos) and eos_token_id is not None))
-        key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
-        rows = None
-        if by_rows and forced_output_ids is None:      # (teacher-forced decoding does not sample and keeps no history)
-            rows = _RowSampling(self, key, eos_token_id)
-            rows.admit(0, sampling, prompt_token_ids)
-            rows.set_live([(sampling, 0)])
-        lplog = _LogprobLog(self, [sampling.logprobs]) if sampling.logprobs is not None else None      # (forced tokens are scored too)
-        if forced_output_ids is not None:
-            forced_dev = torch.tensor(list(forced_output_ids), dtype=torch.int32).to(self.device)
-        for step in range(sampling.max_tokens):
-            if forced_output_ids is not None:
-                if step >= len(forced_output_ids):
-                    break
-                nxt = forced_dev[step:step + 1]
-            elif rows is not None:
-                nxt = rows.sample(logits if logits.dim() == 2 else logits[None], step, [step])
-                rows.advance(nxt)
-            else:
-                nxt = _OPS.sample_top_p(logits, float(sampling.temperature), float(sampling.top_p), int(key), int(step))     # device int32 [1], no host round trip
-            if lplog is not None:
-                lplog.add(logits, nxt, [0])
+        forced = forced_output_ids
+        stops = set(sampling.stop_token_ids or []) | ({eos_token_id} if not sampling.ignore_eos and eos_token_id is not None else set())
+        src = _TokenSource(self, sampling, by_rows, lambda s: sampling, eos_token_id, generator, None if forced is None else [forced],
+                           None if sampling.logprobs is None else [sampling.logprobs])
+        src.admit(0, sampling, prompt_token_ids)
+        for step in range(sampling.max_tokens if forced is None else min(sampling.max_tokens, len(forced))):
+            nxt, host = src.next(logits, step, [step], [0], [0])      # device int32 [1], no host round trip
             out_tok.append(nxt)
-            # one token against the cache: the decode step (fused rope + cache write, decode attention, gated-MLP weight stream)
-            h1, lg = self.decode_batch(nxt, [[next_pos + step]] * 3, [n_p + step])
-            logits = lg[0]
+            # one token against the cache: the decode step (fused rope + cache write, decode attention, gated-MLP weight stream).  Unlike the batched
+            # entries nothing here looks at the slot's capacity: a sequence that outgrows its slot raises from the native check
+            h1, logits = self.decode_batch(nxt, [[next_pos + step]] * 3, [n_p + step])
             out_hidden.append(h1)
-            if can_stop and step + 1 >= sampling.min_tokens:      # only now does the host need to see the token
-                t = int(nxt)
-                if ((not sampling.ignore_eos) and eos_token_id is not None and t == eos_token_id) or t in stops:
+            if forced is None and stops and step + 1 >= sampling.min_tokens:      # only now does the host need to see the token
+                if int(nxt if host is None else host[0]) in stops:
                     break
         hs = torch.cat(out_hidden) if out_hidden else torch.empty(0, self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
         out_ids = torch.cat(out_tok).tolist() if out_tok else []
         res = {"prompt_hidden_states": prompt_hidden, "hidden_states": hs, "token_ids": out_ids}
-        if lplog is not None:      # "logprobs" and "cumulative_logprob": present only when asked
-            lplog.finish([res])
+        src.finish([res])
         return res
 
     @staticmethod
@@ -815,8 +962,14 @@ class Qwen2VLTextEngine:
         dev = generator.device if generator is not None else "cpu"
         return int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=dev))
 
-    packed_prefill = True   # generate_batch: prompts back to back (td_qwen2_prefill_packed); False = right-padded to the longest (td_qwen2_prefill_batch_at: A/B, tests)
+    packed_prefill = True   # _prefill_prompts: prompts back to back (td_qwen2_prefill_packed_slots); False = right-padded (generate_batch) or one forward per prompt
     MAX_BATCH = 256     # td_qwen2_decode_batch: sequences sharing one decode step (vLLM's max_num_seqs of the precompute job)
+    n_slots = 1         # (until __init__ / set_slots say otherwise)
+
+    @property
+    def max_seqs(self) -> int:
+        """Sequences one call can keep live: one cache slot each, and one decode step takes at most MAX_BATCH."""
+        return min(self.MAX_BATCH, self.n_slots)
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[dict], sampling: SamplingParams, eos_token_id: Optional[int] = None,
@@ -825,187 +978,37 @@ class Qwen2VLTextEngine:
         every decode step advances all unfinished sequences in one pass over the weights (what vLLM's batching gives the
         reference's precompute job).  requests: dicts with "prompt_token_ids" and optional "position_ids" / "inputs_embeds".
         Returns one generate()-style dict per request, in order."""
-        B = len(requests)
+        B, forced = len(requests), forced_output_ids
         sps, by_rows = _sampling_list(sampling, B, "generate_batch")
         if sps is None:
             sps = [sampling] * B
-        if B > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
-            raise _hip.ThinkDiffHipError(f"generate_batch: {B} requests exceed min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
-        fan = any(sp.width > 1 for sp in sps)      # n / best_of: request b runs as sps[b].width sequences, each on a cache slot of its own
-        if fan and forced_output_ids is not None:
+        if B > self.max_seqs:
+            raise _hip.ThinkDiffHipError(f"generate_batch: {B} requests exceed min({self.MAX_BATCH}, n_slots={self.n_slots}); call set_slots first")
+        widths = [sp.width for sp in sps]      # n / best_of: request b runs as widths[b] sequences, each on a cache slot of its own
+        N, fan = sum(widths), max(widths, default=1) > 1
+        if fan and forced is not None:
             raise ValueError("generate_batch: forced_output_ids with SamplingParams n / best_of > 1: a teacher-forced continuation is one sequence")
-        if fan and sum(sp.width for sp in sps) > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
-            raise _hip.ThinkDiffHipError(f"generate_batch: the requests' n / best_of add up to {sum(sp.width for sp in sps)} sequences, which exceed "
-                                         f"min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
-        res = [{"prompt_hidden_states": None, "hidden_states": [], "token_ids": []} for _ in range(B)]
-        cache_len = [len(r["prompt_token_ids"]) for r in requests]
-        poss = [self.text_position_ids(n) if r.get("position_ids") is None else r["position_ids"] for r, n in zip(requests, cache_len)]
-        next_pos = [int(p.max()) + 1 for p in poss]
-        L = (max(cache_len) + 7) // 8 * 8
-        if B > 1 and self.packed_prefill and max(cache_len) <= min(self.slot_len, self.prefill_rows):
-            # packed prefill (td_qwen2_prefill_packed): the prompts of a pass lie back to back, no padding rows -- vLLM's batching of the
-            # reference's requests; a pass takes as many prompts as the activation workspace (max_num_batched_tokens) holds
-            D = self.config.hidden_size
-            logits = torch.empty(B, self.config.vocab_size, dtype=torch.bfloat16, device=self.device)
-            b0 = 0
-            while b0 < B:
-                nb, rows = 0, 0
-                while b0 + nb < B and nb < self.MAX_BATCH and rows + cache_len[b0 + nb] <= self.prefill_rows:
-                    rows += cache_len[b0 + nb]
-                    nb += 1
-                emb = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
-                pos = torch.empty(3, rows, dtype=torch.int32)
-                r = 0
-                for j in range(nb):
-                    q, n, pp = requests[b0 + j], cache_len[b0 + j], poss[b0 + j]
-                    e = q.get("inputs_embeds")
-                    emb[r:r + n] = self.embed_tokens(q["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
-                    pos[:, r:r + n] = pp.to(torch.int32)
-                    r += n
-                pos = pos.to(self.device).contiguous()
-                hid = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
-                lens = (ctypes.c_int * nb)(*cache_len[b0:b0 + nb])
-                _hip.check(self._L.td_qwen2_prefill_packed(self._h, b0, nb, None, _hip.ptr(emb), _hip.ptr(pos), ctypes.cast(lens, ctypes.c_void_p),
-                                                           _hip.ptr(hid), _hip.ptr(logits[b0:b0 + nb]), _hip.stream_ptr()))
-                r = 0
-                for j in range(nb):
-                    res[b0 + j]["prompt_hidden_states"] = hid[r:r + cache_len[b0 + j]]
-                    r += cache_len[b0 + j]
-                b0 += nb
-        elif B > 1 and L <= self.slot_len and 2 * L <= self.prefill_rows:
-            # one pass over the weights for as many prompts as the activation workspace holds (all of them, normally): right-padded
-            # to L rows each (causal attention keeps the padding inert); a larger request batch takes several such passes
-            D = self.config.hidden_size
-            per = min(B, self.prefill_rows // L)
-            logits = torch.empty(B, self.config.vocab_size, dtype=torch.bfloat16, device=self.device)
-            for b0 in range(0, B, per):
-                nb = min(per, B - b0)
-                emb = torch.zeros(nb * L, D, dtype=torch.bfloat16, device=self.device)
-                pos = torch.zeros(3, nb * L, dtype=torch.int32)
-                for j in range(nb):
-                    r, n, p = requests[b0 + j], cache_len[b0 + j], poss[b0 + j]
-                    e = r.get("inputs_embeds")
-                    emb[j * L:j * L + n] = self.embed_tokens(r["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
-                    pos[:, j * L:j * L + n] = p.to(torch.int32)
-                    pos[:, j * L + n:(j + 1) * L] = next_pos[b0 + j] + torch.arange(L - n, dtype=torch.int32)
-                pos = pos.to(self.device).contiguous()
-                hid = torch.empty(nb * L, D, dtype=torch.bfloat16, device=self.device)
-                lens = (ctypes.c_int * nb)(*cache_len[b0:b0 + nb])
-                _hip.check(self._L.td_qwen2_prefill_batch_at(self._h, b0, nb, L, None, _hip.ptr(emb), _hip.ptr(pos), ctypes.cast(lens, ctypes.c_void_p),
-                                                             _hip.ptr(hid), _hip.ptr(logits[b0:b0 + nb]), _hip.stream_ptr()))
-                for j in range(nb):
-                    res[b0 + j]["prompt_hidden_states"] = hid[j * L:j * L + cache_len[b0 + j]]
-        else:
-            rows = []
-            for b, (r, p) in enumerate(zip(requests, poss)):
-                e = r.get("inputs_embeds")
-                hid, lg = self.forward(p, torch.tensor(list(r["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, True, slot=b)
-                res[b]["prompt_hidden_states"] = hid
-                rows.append(lg)
-            logits = torch.stack(rows)              # [B, vocab], row i belongs to the sequence in slot i
-        req_sps, seq_slot = sps, list(range(B))
-        if fan:
-            # Request b was prefilled once, into slot b; its other children take the slots from B up and start from a copy of its cache rows (one
-            # launch per request, td_qwen2_fork_slot) and of its row of prefill logits.  From here on the loop runs SEQUENCES: B, sps, res, cache_len
-            # and next_pos are per sequence, and _gather_outputs hands them back to their requests.
-            seq_req = [b for b in range(B) for _ in range(sps[b].width)]
-            seq_slot, free = [], B
-            for b in range(B):
-                kids = list(range(free, free + sps[b].width - 1))
-                free += len(kids)
-                seq_slot += [b] + kids
-                if kids:
-                    self._fork_slots(b, kids, cache_len[b])
-            logits = logits.index_select(0, torch.tensor(seq_req, dtype=torch.int64).to(logits.device))
-            res = [{"prompt_hidden_states": res[b]["prompt_hidden_states"], "hidden_states": [], "token_ids": []} for b in seq_req]
-            requests = [requests[b] for b in seq_req]
-            cache_len, next_pos = [cache_len[b] for b in seq_req], [next_pos[b] for b in seq_req]
-            sps = [c for sp in sps for c in sp.children()]
-            B = len(sps)
-        owner = list(range(B))                      # live row -> request index
-        slots = list(seq_slot)                      # live row -> cache slot (a finished sequence just leaves the lists: no cache rows move)
-        key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
-        stops = [set(sp.stop_token_ids or []) for sp in sps]      # per request, like max_tokens / min_tokens / ignore_eos below
-        rows_s = None
-        if by_rows and forced_output_ids is None:
-            rows_s = _RowSampling(self, key, eos_token_id)
-            for b in range(B):
-                rows_s.admit(seq_slot[b], sps[b], requests[b]["prompt_token_ids"])
-            live_changed = True
-        lplog = _LogprobLog(self, [sp.logprobs for sp in sps]) if _LogprobLog.wanted(sps) else None
-        step = 0
-        # per step: the hidden rows stay ONE device tensor and the slot -> request map is remembered; the rows are handed to their requests by a
-        # single gather after the loop (256 sequences x 256 steps of per-row tensor views and list appends were ~0.5 ms of host time per step,
-        # during which the GPU idled: 15 % of a 3.3 ms step)
-        step_hid, step_owner, step_toks = [], [], []
-        eos_on = [(not sp.ignore_eos) and eos_token_id is not None for sp in sps]
-        owner = [b for b in owner if sps[b].max_tokens > 0]
-        if len(owner) < B:
-            slots = [seq_slot[b] for b in owner]
-            cache_len, next_pos = [cache_len[b] for b in owner], [next_pos[b] for b in owner]
-            logits = logits[owner]
-        while owner:
-            n = len(owner)
-            if forced_output_ids is not None:
-                live = [i for i in range(n) if step < len(forced_output_ids[owner[i]])]
-                if len(live) < n:                   # forced continuations of different lengths: retire the exhausted ones first
-                    owner, slots = [owner[i] for i in live], [slots[i] for i in live]
-                    cache_len, next_pos = [cache_len[i] for i in live], [next_pos[i] for i in live]
-                    logits = logits[live]
-                    if not owner:
-                        break
-                    n = len(owner)
-                toks = [int(forced_output_ids[owner[i]][step]) for i in range(n)]
-            elif rows_s is not None:
-                if live_changed:
-                    rows_s.set_live([(sps[o], sl) for o, sl in zip(owner, slots)])
-                    live_changed = False
-                tok_dev = rows_s.sample(logits[:n], step, [step] * n)      # (every sequence of a batch starts at step 0)
-                toks = tok_dev.tolist()
-                rows_s.advance(toks)
-            else:
-                # one launch for all live rows (td_sample_top_p_bf16); the ids come to the host once per step for the bookkeeping below
-                tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(step))
-                toks = tok_dev.tolist()
-            if lplog is not None:
-                lplog.add(logits[:n], tok_dev if forced_output_ids is None else torch.tensor(toks, dtype=torch.int32).to(self.device), owner)
-            pos = torch.tensor(next_pos[:n], dtype=torch.int32).unsqueeze(0).expand(3, n)
-            hid, logits = self.decode_batch(toks, pos, cache_len[:n], slots=slots)
-            step_hid.append(hid)
-            step_owner.append(list(owner))
-            step_toks.append(toks)
-            keep = []
-            for i in range(n):
-                cache_len[i] += 1
-                next_pos[i] += 1
-                o = owner[i]
-                may_stop = forced_output_ids is None and step + 1 >= sps[o].min_tokens
-                stop = step + 1 >= sps[o].max_tokens or (may_stop and ((eos_on[o] and toks[i] == eos_token_id) or toks[i] in stops[o]))
-                if not stop and cache_len[i] < self.slot_len:
-                    keep.append(i)
-            if len(keep) < n:
-                owner, slots = [owner[i] for i in keep], [slots[i] for i in keep]
-                cache_len, next_pos = [cache_len[i] for i in keep], [next_pos[i] for i in keep]
-                logits = logits[keep]
-                live_changed = True
-            step += 1
-        rows = [[] for _ in range(B)]
-        base = 0
-        for owners, toks in zip(step_owner, step_toks):
-            for i, o in enumerate(owners):
-                rows[o].append(base + i)
-                res[o]["token_ids"].append(toks[i])
-            base += len(owners)
-        D = self.config.hidden_size
-        if base:
-            allh = torch.cat(step_hid)
-            idx = torch.tensor([r for rr in rows for r in rr], dtype=torch.int64).to(self.device)
-            parts = torch.split(allh.index_select(0, idx), [len(rr) for rr in rows])
-        for b, r in enumerate(res):
-            r["hidden_states"] = parts[b] if base and rows[b] else torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
-        if lplog is not None:
-            lplog.finish(res)
-        return _gather_outputs(res, req_sps) if fan else res
+        if N > self.max_seqs:
+            raise _hip.ThinkDiffHipError(f"generate_batch: the requests' n / best_of add up to {N} sequences, which exceed "
+                                         f"min({self.MAX_BATCH}, n_slots={self.n_slots}); call set_slots first")
+        # sequences are numbered in request order; `res`, the live rows and the logprob log are per sequence, _gather_outputs hands them back
+        seq_sps = [c for sp in sps for c in sp.children()]
+        seq0 = np.concatenate([[0], np.cumsum(widths)]).tolist()
+        res = [{"prompt_hidden_states": None, "hidden_states": None, "token_ids": []} for _ in range(N)]
+        poss = [self._positions(r) for r in requests]
+        src = _TokenSource(self, sampling, by_rows, seq_sps.__getitem__, eos_token_id, generator, forced,
+                           [sp.logprobs for sp in seq_sps] if _LogprobLog.wanted(seq_sps) else None)
+        live = _LiveRows(self, N, src, eos_token_id)
+        # request b is prefilled once, into slot b; the children take the slots from B up
+        for b, h in enumerate(self._prefill_prompts(requests, list(range(B)), poss, live.logits[:B], padded_ok=True)):
+            res[seq0[b]]["prompt_hidden_states"] = h
+        live.admit(seq0, widths, list(range(B)), [len(r["prompt_token_ids"]) for r in requests], [int(p.max()) + 1 for p in poss],
+                   [sp.max_tokens if forced is None else min(sp.max_tokens, len(forced[b])) for b, sp in enumerate(sps)],
+                   [r["prompt_token_ids"] for r in requests], list(range(N - 1, B - 1, -1)))
+        while live.n:
+            live.step()
+        live.results(res)
+        return _gather_outputs(res, sps) if fan else res
 
     @torch.no_grad()
     def generate_continuous(self, request_chunks, sampling: SamplingParams, eos_token_id: Optional[int] = None,
@@ -1021,40 +1024,38 @@ class Qwen2VLTextEngine:
         `request_chunks`: an iterable of request lists -- pulled only when the waiting queue runs low, so a producer (the precompute model's helper
         thread) can build later chunks while earlier ones decode -- or one flat list.  Requests are numbered in arrival order; returns one
         generate()-style dict per request in that order.  forced_output_ids[i]: teacher-forced continuation of request i."""
-        from collections import deque
-        import numpy as np
-        max_live = min(self.MAX_BATCH, getattr(self, "n_slots", 1)) if max_live is None else int(max_live)
-        if max_live < 1 or max_live > min(self.MAX_BATCH, getattr(self, "n_slots", 1)):
-            raise _hip.ThinkDiffHipError(f"generate_continuous: max_live={max_live} exceeds min({self.MAX_BATCH}, n_slots={getattr(self, 'n_slots', 1)}); call set_slots first")
+        forced = forced_output_ids
+        max_live = self.max_seqs if max_live is None else int(max_live)
+        if max_live < 1 or max_live > self.max_seqs:
+            raise _hip.ThinkDiffHipError(f"generate_continuous: max_live={max_live} exceeds min({self.MAX_BATCH}, n_slots={self.n_slots}); call set_slots first")
         admit_min = max(1, max_live // 8) if admit_min is None else max(1, int(admit_min))
         if isinstance(request_chunks, (list, tuple)) and (not request_chunks or isinstance(request_chunks[0], dict)):
             request_chunks = [list(request_chunks)]
             n_known = len(request_chunks[0])
         else:
             n_known = None      # chunks pulled lazily: a per-request list is checked against each chunk as it arrives
-        sps_all, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
+        sps_req, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
         # n / best_of: request i runs as k_of(i) SEQUENCES, numbered base_of(i) .. in arrival order of their requests (known in advance: one
         # SamplingParams per request, or one for all).  The live rows, `res` and the logprob log are per sequence; the waiting queue and `requests`
-        # per request.  Without n / best_of a sequence IS its request and nothing below differs from the single-sequence scheduler.
-        fan = sampling.width > 1 if sps_all is None else any(sp.width > 1 for sp in sps_all)
-        if fan and forced_output_ids is not None:
-            raise ValueError("generate_continuous: forced_output_ids with SamplingParams n / best_of > 1: a teacher-forced continuation is one sequence")
-        if fan:
-            for sp in ([sampling] if sps_all is None else sps_all):
-                if sp.width > max_live:
-                    raise _hip.ThinkDiffHipError(f"generate_continuous: SamplingParams n={sp.n}, best_of={sp.best_of} needs {sp.width} cache slots at "
-                                                 f"once, max_live={max_live}")
-            if sps_all is None:
-                kids1 = sampling.children()
-                k_of, base_of, seq_sp = (lambda i: len(kids1)), (lambda i: i * len(kids1)), (lambda s: kids1[s % len(kids1)])
-            else:
-                bases = np.concatenate([[0], np.cumsum([sp.width for sp in sps_all])]).tolist()
-                seq_sps = [c for sp in sps_all for c in sp.children()]
-                k_of, base_of, seq_sp = (lambda i: bases[i + 1] - bases[i]), (lambda i: bases[i]), (lambda s: seq_sps[s])
+        # per request.  Without n / best_of a sequence IS its request.
+        if sps_req is None:
+            kids1 = sampling.children()
+            k_of, base_of, sp_of = (lambda i: len(kids1)), (lambda i: i * len(kids1)), (lambda s: kids1[s % len(kids1)])
+            want = kids1[0].logprobs      # (with best_of > n the children are scored though nobody asked)
         else:
-            k_of, base_of = (lambda i: 1), (lambda i: i)
+            bases = np.concatenate([[0], np.cumsum([sp.width for sp in sps_req])]).tolist()
+            seq_sps = [c for sp in sps_req for c in sp.children()]
+            k_of, base_of, sp_of = (lambda i: bases[i + 1] - bases[i]), (lambda i: bases[i]), seq_sps.__getitem__
+            want = [sp.logprobs for sp in seq_sps] if _LogprobLog.wanted(seq_sps) else None
+        wide = [sp for sp in ([sampling] if sps_req is None else sps_req) if sp.width > 1]
+        fan = bool(wide)
+        if fan and forced is not None:
+            raise ValueError("generate_continuous: forced_output_ids with SamplingParams n / best_of > 1: a teacher-forced continuation is one sequence")
+        for sp in wide:
+            if sp.width > max_live:
+                raise _hip.ThinkDiffHipError(f"generate_continuous: SamplingParams n={sp.n}, best_of={sp.best_of} needs {sp.width} cache slots at "
+                                             f"once, max_live={max_live}")
         chunk_it = iter(request_chunks)
-        D, V = self.config.hidden_size, self.config.vocab_size
         requests, res, waiting = [], [], deque()
         exhausted = False
 
@@ -1076,44 +1077,11 @@ class Qwen2VLTextEngine:
                 for _ in range(k_of(len(requests) - 1)):
                     res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
 
-        # per live row (numpy, rows [0, n)): request, cache slot, cached tokens, next position id, tokens generated, token budget.  The per-step
-        # bookkeeping is vectorised and the arrays are handed to the C ABI as they are: at 256 sequences the Python-list form cost ~2 ms of host
-        # time per step, about as much as the step itself takes on the GPU, and the GPU idles while the host prepares the next launch.
-        own, slt, clen, npos, ngen, lim = (np.zeros(max_live, dtype=np.int32) for _ in range(6))
-        n = 0
+        live = _LiveRows(self, max_live, _TokenSource(self, sampling, by_rows, sp_of, eos_token_id, generator, forced, want), eos_token_id)
         free_slots = list(range(max_live - 1, -1, -1))      # (a stack: the lowest free slot is taken first)
-        logits = torch.empty(max_live, V, dtype=torch.bfloat16, device=self.device)      # row i = the next-token logits of live row i
-        key = None if forced_output_ids is not None else self._draw_sampler_key(generator)
-
-        def sp_of(i):       # the SamplingParams of sequence i
-            return seq_sp(i) if fan else sampling if sps_all is None else sps_all[i]
-
-        sps_req = sps_all      # per request
-        if fan and sps_all is not None:
-            sps_all = seq_sps      # (per sequence from here on: the stop rules and the logprob log index it by live row owner)
-
-        if sps_all is None:
-            stops = np.array(sorted(set(sampling.stop_token_ids or [])), dtype=np.int64)
-            eos_on = (not sampling.ignore_eos) and eos_token_id is not None
-            can_stop = forced_output_ids is None and (stops.size > 0 or eos_on)
-        else:               # the stop rules per request (mint: the live rows' min_tokens)
-            stop_sets = [set(sp.stop_token_ids or []) for sp in sps_all]
-            can_stop = forced_output_ids is None
-            mint = np.zeros(max_live, dtype=np.int32)
-        rows_s = _RowSampling(self, key, eos_token_id) if by_rows and forced_output_ids is None else None
-        if sps_all is None:
-            lp1 = sp_of(0).logprobs      # (with best_of > n the children are scored though nobody asked)
-            lplog = _LogprobLog(self, lp1) if lp1 is not None else None
-        else:
-            lplog = _LogprobLog(self, [sp.logprobs for sp in sps_all]) if _LogprobLog.wanted(sps_all) else None
-        live_changed = True
-        step_hid, step_owner, step_toks = [], [], []
-        gstep = 0
-        slot_len, min_tok = self.slot_len, (sampling.min_tokens if sps_all is None else None)
-        vp = ctypes.c_void_p
 
         def budget(i):      # tokens (each sequence of) request i may still produce
-            return len(forced_output_ids[i]) if forced_output_ids is not None else sp_of(base_of(i)).max_tokens
+            return len(forced[i]) if forced is not None else sp_of(base_of(i)).max_tokens
 
         def fits(free):     # -> (requests, cache slots) of the head of the queue that `free` slots take, in arrival order: nobody overtakes a request that waits for k slots
             if not fan:
@@ -1126,152 +1094,45 @@ class Qwen2VLTextEngine:
             return nreq, used
 
         while True:
-            free = max_live - n
+            free = max_live - live.n
             if not exhausted and len(waiting) < free:      # lazily -- the producer builds the next chunk while the current sequences decode -- but enough to fill the free slots
                 pull()
                 continue
-            # ---- admission: one packed prefill pass into free slots ----
+            # ---- admission: one packed prefill pass into free slots (even for a single prompt) ----
             fit, fit_slots = fits(free)
-            if fit > 0 and (n == 0 or fit_slots >= admit_min or (exhausted and fit >= len(waiting))):
+            if fit > 0 and (live.n == 0 or fit_slots >= admit_min or (exhausted and fit >= len(waiting))):
                 new, rows, used = [], 0, 0
                 while waiting and used + k_of(waiting[0]) <= free and rows + len(requests[waiting[0]]["prompt_token_ids"]) <= self.prefill_rows:
                     i = waiting.popleft()
                     if budget(i) <= 0:      # nothing to generate: the prompt states only, through the first free slot
                         q = requests[i]
-                        m = len(q["prompt_token_ids"])
                         e = q.get("inputs_embeds")
                         res[base_of(i)]["prompt_hidden_states"], _ = self.forward(
-                            self.text_position_ids(m) if q.get("position_ids") is None else q["position_ids"],
-                            torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, False, slot=free_slots[-1])
+                            self._positions(q), torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, False,
+                            slot=free_slots[-1])
                         continue
                     new.append(i)
                     rows += len(requests[i]["prompt_token_ids"])
                     used += k_of(i)
                 if new:
-                    k = len(new)
-                    emb = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
-                    pos = torch.empty(3, rows, dtype=torch.int32)
-                    lens, r0 = [], 0
-                    for j, i in enumerate(new):
-                        q = requests[i]
-                        m = len(q["prompt_token_ids"])
-                        pp = self.text_position_ids(m) if q.get("position_ids") is None else q["position_ids"]
-                        e = q.get("inputs_embeds")
-                        emb[r0:r0 + m] = self.embed_tokens(q["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
-                        pos[:, r0:r0 + m] = pp.to(torch.int32)
-                        lens.append(m)
-                        npos[n + j] = int(pp.max()) + 1
-                        r0 += m
-                    pos = pos.to(self.device).contiguous()
-                    hid = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
+                    k, qs = len(new), [requests[i] for i in new]
+                    poss = [self._positions(q) for q in qs]
+                    emb, pos, lens = self._pack_prompts(qs, poss)
+                    hid = torch.empty(rows, self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
                     new_slots = [free_slots.pop() for _ in new]
-                    cl = (ctypes.c_int * k)(*lens)
-                    sl = (ctypes.c_int * k)(*new_slots)
-                    self._prefill_packed_slots(k, sl, emb, pos, cl, hid, logits[n:n + k])
-                    r0 = 0
-                    for i, m in zip(new, lens):
-                        res[base_of(i)]["prompt_hidden_states"] = hid[r0:r0 + m]
-                        r0 += m
-                    if used > k:
-                        # children: the cache rows of each prompt forked to k_of - 1 more free slots (one launch per request, td_qwen2_fork_slot) and its
-                        # row of prefill logits copied to their live rows; the rows of this admission become its sequences, in request order
-                        rep, seqs, seq_slots = [], [], []
-                        for j, i in enumerate(new):
-                            kids = [free_slots.pop() for _ in range(k_of(i) - 1)]
-                            if kids:
-                                self._fork_slots(new_slots[j], kids, lens[j])
-                            rep += [j] * k_of(i)
-                            seqs += range(base_of(i), base_of(i) + k_of(i))
-                            seq_slots += [new_slots[j]] + kids
-                        logits[n:n + used] = logits[n:n + k].index_select(0, torch.tensor(rep, dtype=torch.int64).to(logits.device))
-                        npos[n:n + used] = npos[n:n + k][rep]
-                        parents, new, new_slots, lens, k = [new[j] for j in rep], seqs, seq_slots, [lens[j] for j in rep], used
-                    else:
-                        parents, new = new, [base_of(i) for i in new]      # (a request is its sequence unless another request of the call has children)
-                    own[n:n + k] = new
-                    slt[n:n + k] = new_slots
-                    clen[n:n + k] = lens
-                    ngen[n:n + k] = 0
-                    lim[n:n + k] = [budget(i) for i in parents]
-                    if sps_all is not None:
-                        mint[n:n + k] = [sps_all[i].min_tokens for i in new]
-                    if rows_s is not None:      # a request admitted into a slot starts that slot's history over
-                        for i, p, sl in zip(new, parents, new_slots):
-                            rows_s.admit(sl, sp_of(i), requests[p]["prompt_token_ids"])
-                    live_changed = True
-                    n += k
+                    self._prefill_packed_slots(k, (ctypes.c_int * k)(*new_slots), emb, pos, (ctypes.c_int * k)(*lens), hid, live.logits[live.n:live.n + k])
+                    for i, h in zip(new, torch.split(hid, lens)):
+                        res[base_of(i)]["prompt_hidden_states"] = h
+                    live.admit([base_of(i) for i in new], [k_of(i) for i in new], new_slots, lens, [int(p.max()) + 1 for p in poss],
+                               [budget(i) for i in new], [q["prompt_token_ids"] for q in qs], free_slots)
                     continue      # (more may fit in another pass before the next decode step)
-            if n == 0:
+            if live.n == 0:
                 if waiting or not exhausted:
                     continue
                 break
-            # ---- one decode step for every live sequence ----
-            if forced_output_ids is not None:
-                toks = np.array([forced_output_ids[own[i]][ngen[i]] for i in range(n)], dtype=np.int32)
-                tok_dev = torch.from_numpy(toks).to(self.device)
-            else:
-                if rows_s is not None:
-                    if live_changed:
-                        rows_s.set_live([(sp_of(int(own[i])), int(slt[i])) for i in range(n)])
-                        live_changed = False
-                    tok_dev = rows_s.sample(logits[:n], gstep, ngen[:n])
-                else:
-                    tok_dev = _OPS.sample_top_p(logits[:n], float(sampling.temperature), float(sampling.top_p), int(key), int(gstep))
-                toks = tok_dev.cpu().numpy()      # (the host sees the ids once per step, for the stop rules below)
-                if rows_s is not None:
-                    rows_s.advance(toks)
-            if lplog is not None:
-                lplog.add(logits[:n], tok_dev, own[:n])
-            pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(npos[:n], (3, n)))).to(self.device)
-            hid = torch.empty(n, D, dtype=torch.bfloat16, device=self.device)
-            self._decode_slots(n, slt, tok_dev, pos_dev, clen, hid, logits)      # logits of row i -> logits[i]
-            step_hid.append(hid)
-            step_owner.append(own[:n].copy())
-            step_toks.append(toks)
-            clen[:n] += 1
-            npos[:n] += 1
-            ngen[:n] += 1
-            done = (ngen[:n] >= lim[:n]) | (clen[:n] >= slot_len)
-            if can_stop and sps_all is None:
-                hit = np.isin(toks, stops) if stops.size else np.zeros(n, dtype=bool)
-                if eos_on:
-                    hit |= toks == eos_token_id
-                done |= hit & (ngen[:n] >= min_tok)
-            elif can_stop:
-                hit = np.array([int(toks[i]) in stop_sets[own[i]] or (eos_token_id is not None and not sps_all[own[i]].ignore_eos and int(toks[i]) == eos_token_id)
-                                for i in range(n)], dtype=bool)
-                done |= hit & (ngen[:n] >= mint[:n])
-            if done.any():
-                keep = np.nonzero(~done)[0]
-                free_slots.extend(sorted((int(x) for x in slt[:n][done]), reverse=True))
-                k = keep.size
-                for arr in (own, slt, clen, npos, ngen, lim) + (() if sps_all is None else (mint,)):
-                    arr[:k] = arr[:n][keep]
-                live_changed = True
-                if k:
-                    logits[:k] = logits[:n].index_select(0, torch.from_numpy(keep).to(self.device))
-                n = k
-            gstep += 1
-        N = len(res)
-        if step_owner:
-            owners_all = np.concatenate(step_owner)
-            order = np.argsort(owners_all, kind="stable")      # rows grouped by request, in step order inside a request
-            counts = np.bincount(owners_all, minlength=N).tolist()
-            parts = torch.split(torch.cat(step_hid).index_select(0, torch.from_numpy(order).to(self.device)), counts)
-            toks_sorted = np.concatenate(step_toks)[order].tolist()
-            r0 = 0
-            for b in range(N):
-                res[b]["hidden_states"] = parts[b]
-                res[b]["token_ids"] = toks_sorted[r0:r0 + counts[b]]
-                r0 += counts[b]
-        else:
-            for r in res:
-                r["hidden_states"] = torch.empty(0, D, dtype=torch.bfloat16, device=self.device)
-        if lplog is not None:
-            lplog.finish(res)
-        if fan:
-            res = _gather_outputs(res, [sampling] * len(requests) if sps_req is None else sps_req[:len(requests)])
-        return res
+            free_slots.extend(live.step())
+        live.results(res)
+        return _gather_outputs(res, [sampling] * len(requests) if sps_req is None else sps_req[:len(requests)]) if fan else res
 
     # the engine calls of generate_continuous (separate methods so that the scheduler's host logic can be exercised against a stand-in engine)
     def _prefill_packed_slots(self, k, slots_c, emb, pos, lens_c, hid_out, logits_out):
@@ -1305,43 +1166,75 @@ class Qwen2VLTextEngine:
             raise _hip.ThinkDiffHipError(f"gather_slots: {src.numel()} copy_src entries and {len(lengths)} lengths for {n} slots")
         _hip.check(self._L.td_qwen2_gather_slots(self._h, n, ctypes.cast(sl, ctypes.c_void_p), _hip.ptr(src), ctypes.cast(ln, ctypes.c_void_p), _hip.stream_ptr()))
 
-    # ---- beam search ([ext] vllm.LLM.beam_search) ------------------------------------------------------------------------------------------
-    def _beam_prefill(self, requests, slots, plen, poss):
-        """Each prompt once into its request's first cache slot, the way generate_batch prefills: packed passes (td_qwen2_prefill_packed_slots) where
-        several prompts fit the workspace, one forward per prompt otherwise.  -> (prompt hidden states per request, logits bf16 [R, vocab])."""
-        R, D = len(requests), self.config.hidden_size
-        logits = torch.empty(R, self.config.vocab_size, dtype=torch.bfloat16, device=self.device)
-        hidden = [None] * R
-        if R > 1 and self.packed_prefill and max(plen) <= min(self.slot_len, self.prefill_rows):
+    # ---- prompt prefill of generate_batch, generate_continuous and beam_search ---------------------------------------------------------------
+    def _positions(self, request):
+        p = request.get("position_ids")
+        return self.text_position_ids(len(request["prompt_token_ids"])) if p is None else p
+
+    def _pack_prompts(self, requests, poss):
+        """The prompts back to back, no padding rows -> (emb bf16 [rows, hidden] and pos int32 [3, rows] on the device, the prompts' lengths)."""
+        lens = [len(q["prompt_token_ids"]) for q in requests]
+        emb = torch.empty(sum(lens), self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
+        pos = torch.empty(3, sum(lens), dtype=torch.int32)
+        r = 0
+        for q, pp, n in zip(requests, poss, lens):
+            e = q.get("inputs_embeds")
+            emb[r:r + n] = self.embed_tokens(q["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
+            pos[:, r:r + n] = pp.to(torch.int32)
+            r += n
+        return emb, pos.to(self.device).contiguous(), lens
+
+    def _prefill_prompts(self, requests, slots, poss, logits_out, padded_ok=False):
+        """Prompt j into cache slot slots[j], its last token's logits into logits_out[j] -> the prompts' hidden states, one tensor per request.
+        Several prompts that each fit a pass are packed (packed_prefill: td_qwen2_prefill_packed_slots -- vLLM's batching of the reference's
+        requests), a pass taking as many prompts as the activation workspace (max_num_batched_tokens) and MAX_BATCH hold; with packed_prefill off
+        and padded_ok (generate_batch alone: slots must be consecutive) they are right-padded to the longest (td_qwen2_prefill_batch_at: A/B,
+        tests); anything else is one forward per prompt."""
+        B, D = len(requests), self.config.hidden_size
+        lens = [len(q["prompt_token_ids"]) for q in requests]
+        hidden = [None] * B
+        L = (max(lens) + 7) // 8 * 8
+        if B > 1 and self.packed_prefill and max(lens) <= min(self.slot_len, self.prefill_rows):
             b0 = 0
-            while b0 < R:
+            while b0 < B:
                 nb, rows = 0, 0
-                while b0 + nb < R and nb < self.MAX_BATCH and rows + plen[b0 + nb] <= self.prefill_rows:
-                    rows += plen[b0 + nb]
+                while b0 + nb < B and nb < self.MAX_BATCH and rows + lens[b0 + nb] <= self.prefill_rows:
+                    rows += lens[b0 + nb]
                     nb += 1
-                emb = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
-                pos = torch.empty(3, rows, dtype=torch.int32)
-                r = 0
-                for j in range(b0, b0 + nb):
-                    e = requests[j].get("inputs_embeds")
-                    emb[r:r + plen[j]] = self.embed_tokens(requests[j]["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
-                    pos[:, r:r + plen[j]] = poss[j].to(torch.int32)
-                    r += plen[j]
-                pos = pos.to(self.device).contiguous()
+                emb, pos, ln = self._pack_prompts(requests[b0:b0 + nb], poss[b0:b0 + nb])
                 hid = torch.empty(rows, D, dtype=torch.bfloat16, device=self.device)
-                self._prefill_packed_slots(nb, (ctypes.c_int * nb)(*slots[b0:b0 + nb]), emb, pos, (ctypes.c_int * nb)(*plen[b0:b0 + nb]), hid, logits[b0:b0 + nb])
-                r = 0
-                for j in range(b0, b0 + nb):
-                    hidden[j] = hid[r:r + plen[j]]
-                    r += plen[j]
+                self._prefill_packed_slots(nb, (ctypes.c_int * nb)(*slots[b0:b0 + nb]), emb, pos, (ctypes.c_int * nb)(*ln), hid, logits_out[b0:b0 + nb])
+                hidden[b0:b0 + nb] = torch.split(hid, ln)
                 b0 += nb
+        elif padded_ok and B > 1 and L <= self.slot_len and 2 * L <= self.prefill_rows:
+            # one pass over the weights for as many prompts as the activation workspace holds (all of them, normally): right-padded
+            # to L rows each (causal attention keeps the padding inert); a larger request batch takes several such passes
+            per = min(B, self.prefill_rows // L)
+            for b0 in range(0, B, per):
+                nb = min(per, B - b0)
+                emb = torch.zeros(nb * L, D, dtype=torch.bfloat16, device=self.device)
+                pos = torch.zeros(3, nb * L, dtype=torch.int32)
+                for j in range(nb):
+                    q, n, p = requests[b0 + j], lens[b0 + j], poss[b0 + j]
+                    e = q.get("inputs_embeds")
+                    emb[j * L:j * L + n] = self.embed_tokens(q["prompt_token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
+                    pos[:, j * L:j * L + n] = p.to(torch.int32)
+                    pos[:, j * L + n:(j + 1) * L] = int(p.max()) + 1 + torch.arange(L - n, dtype=torch.int32)
+                pos = pos.to(self.device).contiguous()
+                hid = torch.empty(nb * L, D, dtype=torch.bfloat16, device=self.device)
+                cl = (ctypes.c_int * nb)(*lens[b0:b0 + nb])
+                _hip.check(self._L.td_qwen2_prefill_batch_at(self._h, slots[b0], nb, L, None, _hip.ptr(emb), _hip.ptr(pos), ctypes.cast(cl, ctypes.c_void_p),
+                                                             _hip.ptr(hid), _hip.ptr(logits_out[b0:b0 + nb]), _hip.stream_ptr()))
+                for j in range(nb):
+                    hidden[b0 + j] = hid[j * L:j * L + lens[b0 + j]]
         else:
             for j, (q, p) in enumerate(zip(requests, poss)):
                 e = q.get("inputs_embeds")
                 hidden[j], lg = self.forward(p, torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, True, slot=slots[j])
-                logits[j] = lg
-        return hidden, logits
+                logits_out[j] = lg
+        return hidden
 
+    # ---- beam search ([ext] vllm.LLM.beam_search) ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def beam_search(self, requests: Sequence[dict], params: BeamSearchParams, eos_token_id: Optional[int] = None):
         """vLLM's `LLM.beam_search` for R requests (the dicts of generate_batch) with W = params.beam_width beams each, on R x W cache slots: request r
@@ -1362,11 +1255,10 @@ class Qwen2VLTextEngine:
         and "outputs": W dicts with "index", "token_ids", "hidden_states", "cumulative_logprob", "score", "finished"."""
         params.validate()
         R, W, T = len(requests), int(params.beam_width), int(params.max_tokens)
-        n_slots = getattr(self, "n_slots", 1)
         if R < 1:
             raise ValueError("beam_search: no requests")
-        if R * W > min(self.MAX_BATCH, n_slots):
-            raise _hip.ThinkDiffHipError(f"beam_search: {R} requests x beam_width={W} need {R * W} cache slots, which exceed min({self.MAX_BATCH}, n_slots={n_slots}); "
+        if R * W > self.max_seqs:
+            raise _hip.ThinkDiffHipError(f"beam_search: {R} requests x beam_width={W} need {R * W} cache slots, which exceed min({self.MAX_BATCH}, n_slots={self.n_slots}); "
                                          "call set_slots first")
         plen = [len(r["prompt_token_ids"]) for r in requests]
         for i, n in enumerate(plen):
@@ -1379,12 +1271,12 @@ class Qwen2VLTextEngine:
             raise ValueError(f"beam_search: vocab_size={V} must exceed 2 x beam_width = {2 * W}: a step takes the 2 x beam_width most probable tokens of a row")
         if eos_token_id is not None and not 0 <= int(eos_token_id) < V:
             raise ValueError(f"beam_search: eos_token_id={eos_token_id} outside the vocabulary of {V}")
-        import numpy as np
         eos = -1 if (params.ignore_eos or eos_token_id is None) else int(eos_token_id)
         N, dev = R * W, self.device
-        poss = [self.text_position_ids(n) if r.get("position_ids") is None else r["position_ids"] for r, n in zip(requests, plen)]
+        poss = [self._positions(r) for r in requests]
         next_pos = [int(p.max()) + 1 for p in poss]
-        prompt_hidden, logits0 = self._beam_prefill(requests, [r * W for r in range(R)], plen, poss)
+        logits0 = torch.empty(R, V, dtype=torch.bfloat16, device=dev)
+        prompt_hidden = self._prefill_prompts(requests, [r * W for r in range(R)], poss, logits0)      # each prompt once, into its request's first slot
         # what the loop needs from the host, uploaded before it starts: the rows' M-RoPE positions of every round and the first round's live rows
         first = torch.arange(R, dtype=torch.int64) * W
         logits = torch.zeros(N, V, dtype=torch.bfloat16, device=dev)
@@ -1573,7 +1465,6 @@ class QwenChatFrontend:
         # One embedding gather and ONE scatter of the merged vision tokens for the whole batch: the placeholder positions are known on
         # the host (they are token ids), so nothing here waits for the device -- a boolean-mask assignment per request would
         # synchronise with the vision tower once per request.
-        import numpy as np
         g0 = 0
         all_ids, spans, grids = [], [], []
         for i, ims in zip(need, per_req):
@@ -1609,7 +1500,6 @@ class QwenChatFrontend:
         out = None
         try:
             if type(ip).__name__ == "Qwen2VLImageProcessorPil" and hasattr(self.visual, "padded_patch_dim"):
-                import numpy as np
                 ramp = np.arange(256, dtype=np.uint8)[None, None, :].repeat(3, 0)          # [C, 1, 256] channels first, as the backend holds images
                 x = ip.rescale(ramp, ip.rescale_factor) if ip.do_rescale else ramp
                 x = ip.normalize(x, ip.image_mean, ip.image_std) if ip.do_normalize else x
@@ -1634,7 +1524,6 @@ class QwenChatFrontend:
             return None
         if not plan["convert_rgb"] and any(im.mode != "RGB" for im in images):
             return None
-        import numpy as np
         f = plan["patch"] * plan["merge"]
         device_resize = plan["resample"] in (1, 2, 3)       # Pillow's LANCZOS, BILINEAR, BICUBIC: the filters td_resize_coeffs builds
 
