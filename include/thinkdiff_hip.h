@@ -83,6 +83,15 @@ int td_linear_drain_bf16(const void* x0, int M0, const void* w0, const void* bia
                          int64_t ldx, int64_t ldy, int64_t ldr, int N, int K, int act,
                          void* y_split, int64_t ld_split, int act_split, int n_split, int max_workgroups, void* stream);
 
+/* Which tile an automatic launch (tile_cfg = -1) of an M x N x K Linear takes (td_abi_version() >= 19): 0 256x256, 1 256x64, 2 32x256, 3 288x192.
+ * Host arithmetic only: no device is touched, no stream is needed.  M = the rows of the launch (both problems of a grouped one), K in elements of
+ * the operand type.  shared = 0: the launch has the chip to itself, and tiles are chosen by rounds of the CUs (the 288x192 tile where 256x256 leaves
+ * one ragged round and K is long).  shared != 0: several images in flight (td_flux_denoise_multi) -- other images' kernels fill the CUs a launch
+ * leaves empty, so the tile that costs the least CU time is taken, from a table of measured tile times per operand type.  operand: 0 bf16, 1 int8,
+ * 2 e4m3 (-1, with td_last_error set, for anything else or for M, N, K < 1).  The environment variable TD_GEMM_SHARED_TILES, read per call and per
+ * launch, forces the shared = 0 rule (0) or the CU-time choice (1) for every operand type under the hint.  Every tile gives the same bits. */
+int td_gemm_plan_query(int M, int N, int K, int shared, int operand);
+
 /* 3x3 convolution, stride 1, zero padding 1, over an NHWC bf16 image as an implicit GEMM (no im2col buffer):
  *   y[H*W, Cout] = conv3x3(x[Hin*Win, Cin]) + bias (+ res[H*W, Cout]);   upsample2x != 0 fuses the nearest 2x
  * upsample that precedes the conv in Upsample2D (then Hin = H/2, Win = W/2), else Hin = H, Win = W.

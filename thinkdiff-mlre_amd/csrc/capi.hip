@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 18; }   // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 19; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -40,6 +40,7 @@ int td_abi_version(void) { return 18; }   // 2: TdFluxConfig::out_channels appen
                                             //     td_softmax_rows_* refuse a scale that is not finite and positive
                                             // 18: beam search (td_beam_select; csrc/beam_search.hip) and the KV gather behind it (td_kv_gather_rows,
                                             //     td_qwen2_gather_slots; csrc/kv_fork.hip)
+                                            // 19: td_gemm_plan_query (host-only: the tile an automatic GEMM launch takes, alone or on a shared chip)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -88,6 +89,14 @@ int td_linear_grouped2_bf16(const void* x0, int M0, const void* w0, const void* 
   p.g_res = (const bf16_t*)res1; p.g_C = (bf16_t*)y1; p.g_M = M1;
   p.lda = (int)ldx; p.ldc = (int)ldy; p.ldr = (int)ldr; p.N = N; p.K = K; p.act = act; p.cfg = tile_cfg;
   return td_gemm_launch(p, (hipStream_t)stream);
+}
+
+int td_gemm_plan_query(int M, int N, int K, int shared, int operand) {
+  if (M < 1 || N < 1 || K < 1 || operand < TD_OPERAND_BF16 || operand > TD_OPERAND_E4M3) {
+    td_set_error("td_gemm_plan_query: M=%d N=%d K=%d must be positive and operand=%d one of 0 (bf16), 1 (int8), 2 (e4m3)", M, N, K, operand);
+    return -1;
+  }
+  return td_gemm_plan(M, N, operand == TD_OPERAND_BF16 ? K : K / 2, shared, operand);      // (8-bit operands: tiles are chosen by bytes, as td_gemm_launch does)
 }
 
 int td_linear_drain_bf16(const void* x0, int M0, const void* w0, const void* bias0, const void* gate0, const void* res0, void* y0,

@@ -56,10 +56,14 @@ struct TraceScope {
 
 // With several images in flight the partial last round of a GEMM is filled by the other images' kernels, and the tail split's smaller sub-tiles
 // only cost (same-box A/B, 2 in flight: bf16 0.580 with the split vs 0.583 without, int8 0.964 vs 0.968): the engine then asks for plain launches.
+// The same hint picks the tile by CU time (td_gemm_plan).  The tile is decided HERE, once, and handed to the launcher, so the trace category is the
+// kernel that runs; up to 64 rows the launcher still decides between its weight-stream and tile kernels itself (it does so only without an override).
 int gemm_p(td_flux* f, hipStream_t s, TdGemmParams p) {
   p.no_tail = f->shared_chip;
   const int rows = p.M + p.g_M;
-  const int cfg = p.cfg >= 0 ? p.cfg : td_gemm_config_id(rows, p.N, (p.fp8 || p.i8) ? p.K / 2 : p.K);      // (8-bit operands: tiles are chosen by bytes)
+  const int cfg = p.cfg >= 0 ? p.cfg : td_gemm_plan(rows, p.N, (p.fp8 || p.i8) ? p.K / 2 : p.K,      // (8-bit operands: tiles are chosen by bytes)
+                                                    p.no_tail, p.i8 ? TD_OPERAND_INT8 : p.fp8 ? TD_OPERAND_E4M3 : TD_OPERAND_BF16);
+  if (rows > 64) p.cfg = cfg;
   TraceScope ts(f, s, cfg == 0 ? TD_TRACE_GEMM_MAIN : cfg == 3 ? TD_TRACE_GEMM_288 : TD_TRACE_GEMM_OTHER, 2.0 * rows * p.N * p.K);
   return td_gemm_launch(p, s);
 }

@@ -1201,10 +1201,18 @@ WidePlan plan_wide(const TdGemmParams& p) {
 
 }  // namespace
 
-// Tile choice.  0: 256x256, 1: 256x64 (also: few-tile problems), 2: 32x256, 3: 288x192 (4: 256x128, the wide-decode planner's and by request only).  Measured on MI355X (in-process A/B,
-// tools/bench_ops.py gemmcfg): 256x256 wins whenever the grid spans several rounds of the 256 CUs; the
-// 288x192 tile wins where 256x256 leaves a single ragged round (N = 3072 at M = 4289: 204 tiles, but 240
-// tiles of the smaller shape) and K is long enough to amortise its prologue.
+// Tile choice.  0: 256x256, 1: 256x64 (also: few-tile problems), 2: 32x256, 3: 288x192 (4: 256x128, the wide-decode planner's and by request only).
+// Two regimes, two functions:
+//  * td_gemm_config_id: a launch that has the chip to itself (one image in flight, encoders, towers, prefills).  Its time is ceil(tiles / CUs)
+//    rounds of one tile's time, so the rules count rounds.  Measured on MI355X on lone launches (in-process A/B, tools/bench_ops.py gemmcfg / gemmsmall):
+//      - N <= 64 -> 1, M <= 32 -> 2: the only tiles that are not mostly padding there (both regimes);
+//      - 288x192 where 256x256 leaves a single ragged round (N = 3072 at M = 4289: 204 tiles, but 240 of the smaller shape fill the 256 CUs) and
+//        K is long enough to amortise its prologue (lone-launch regime ONLY);
+//      - below ~96 tiles of 256x256 the quarter-width tile puts 4x the workgroups on the chip, 25-30 % faster (both regimes: such launches are too
+//        short for another image's kernels to fill them);
+//      - 256x256 whenever the grid spans several rounds of the 256 CUs.
+//  * td_gemm_plan: the caller's shared-chip hint (TdGemmParams::no_tail; several images in flight).  Other images' kernels fill whatever CUs a launch
+//    leaves empty, so a launch costs the chip its workgroups x one workgroup's time (CU time), not rounds -- see below.
 int td_gemm_config_id(int M, int N, int K) {
   if (N <= 64) return 1;
   if (M <= 32) return 2;
@@ -1214,6 +1222,39 @@ int td_gemm_config_id(int M, int N, int K) {
   // few 256x256 tiles (encoders, towers, short prefills: M of 77-1024 rows, N of a few thousand): a quarter-width tile
   // puts 4x the workgroups on the chip; measured 25-30 % faster below ~96 tiles, slower above (tools/bench_ops.py gemmsmall)
   return t0 < 96 ? 1 : 0;
+}
+
+namespace {
+
+// Time of ONE workgroup of the 256x256 and the 288x192 tile on a chip it does not have to itself: c0 + c1 x k-tiles microseconds (a k-tile = 128
+// operand bytes per row), per operand type.  Least-squares lines through tools/bench_ops.py gemmtile (M = 4289, N = 3072: one round of either
+// tile, so the launch's time is the tile's; cold weights; K = 96 .. 240 k-tiles): profiles/gemm_shared_tiles_probe.log.  At the two block shapes
+// (192 / 240 k-tiles) 204 tiles of 256x256 cost 10-11 % less CU time than 240 of 288x192 in bf16, 14-15 % in int8 (96 / 120 k-tiles there).
+// `on`: whether the whole-image A/B of that operand type showed a gain from choosing by these (profiles/gemm_shared_tiles_ab.log, two images in
+// flight, arms alternated in one process): bf16 +0.85 % once the process has settled (+1.3 % on fresh processes against the parent's library),
+// the int8 policy nothing (0.9711 against 0.9715 images/s), e4m3 Linears not measured on whole images; off = the lone-launch rule.
+struct SharedTileCost { double c0_256, c1_256, c0_288, c1_288; bool on; };
+const SharedTileCost kSharedTileCost[3] = {
+    /* bf16 */ {4.03, 1.3034, 12.51, 1.2042, true},
+    /* int8 */ {8.69, 1.2866, 15.88, 1.2172, false},
+    /* e4m3 */ {2.98, 1.3049, 11.03, 1.2029, false},
+};
+
+}  // namespace
+
+// Under the shared-chip hint the 288x192 tile is taken only where it costs less CU time than 256x256: tiles(cfg) x (c0[cfg] + c1[cfg] K / 64).
+// It stays a candidate only where the lone-launch rule admits it (the range its constants were measured in); the N <= 64, M <= 32 and few-tile
+// rules are the lone launch's.  TD_GEMM_SHARED_TILES=0 / 1 forces the lone-launch rule / this choice for every operand type (A/B switch, read per
+// launch so one process can time both).  K in bf16 equivalents (operand bytes per row / 2), as td_gemm_config_id takes it.  Host arithmetic only.
+int td_gemm_plan(int M, int N, int K, int shared, int operand) {
+  const int lone = td_gemm_config_id(M, N, K);
+  if (!shared || lone != 3 || operand < 0 || operand > 2) return lone;
+  const SharedTileCost& c = kSharedTileCost[operand];
+  const char* sw = getenv("TD_GEMM_SHARED_TILES");
+  if (!(sw ? atoi(sw) != 0 : c.on)) return lone;
+  const double t0 = (double)((M + 255) / 256) * ((N + 255) / 256), t3 = (double)((M + 287) / 288) * ((N + 191) / 192);
+  const double kt = K / 64.0;
+  return t0 * (c.c0_256 + c.c1_256 * kt) < t3 * (c.c0_288 + c.c1_288 * kt) ? 0 : 3;
 }
 
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
@@ -1261,7 +1302,7 @@ int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
     return td_gemv_launch(p, stream);
   }
   if (p.g_M == 0 && !p.fp8 && !p.i8 && !p.out_f32 && p.cfg < 0 && p.split_k == 0 && p.N % 4 == 0 && (p.M <= 16 || (p.M <= 64 && td_gemv_mfma_ok(p)))) return td_gemv_launch(p, stream);      // (a caller that sets split_k wants the tile kernels)
-  int cfg = p.cfg >= 0 ? p.cfg : td_gemm_config_id(p.M + p.g_M, p.N, p.K * esz / 2);
+  int cfg = p.cfg >= 0 ? p.cfg : td_gemm_plan(p.M + p.g_M, p.N, p.K * esz / 2, p.no_tail, p.i8 ? TD_OPERAND_INT8 : p.fp8 ? TD_OPERAND_E4M3 : TD_OPERAND_BF16);
   int parts = 1;
   if (p.split_k == -1 && p.cfg < 0 && p.M > 16 && p.M <= 256 && !p.fp8 && !p.i8 && p.g_M == 0 && !p.out_f32 && !p.q8) {
     const WidePlan w = plan_wide(p);

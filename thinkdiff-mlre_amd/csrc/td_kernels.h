@@ -86,6 +86,10 @@ bool td_gemv_w8_ok(const TdGemmParams& p);     // shapes the 8-bit weight stream
 int td_quant_weight_rows_launch(const bf16_t* w, long long ldw, uint8_t* q, float* scale, bf16_t* w_hat, int N, int K, hipStream_t stream);
 // 0: 256x256 (td_gemm_bf16_nt_kernel<8,4>), 1: 256x64, 2: 32x256, 3: 288x192 (<9,3>)
 int td_gemm_config_id(int M, int N, int K);
+// The same choice under the caller's shared-chip hint (shared != 0; TdGemmParams::no_tail): the tile that costs the least CU time, per operand type
+// (csrc/gemm_bf16.hip).  shared = 0 is td_gemm_config_id.  K in bf16 equivalents (operand bytes per row / 2).  What td_gemm_launch runs when cfg < 0.
+enum { TD_OPERAND_BF16 = 0, TD_OPERAND_INT8 = 1, TD_OPERAND_E4M3 = 2 };
+int td_gemm_plan(int M, int N, int K, int shared, int operand);
 
 enum { TD_TRACE_GEMM_MAIN = 0, TD_TRACE_GEMM_OTHER = 1, TD_TRACE_ATTN = 2, TD_TRACE_NORM = 3, TD_TRACE_QKROPE = 4, TD_TRACE_GEMM_288 = 5, TD_TRACE_NCAT = 6 };
 

@@ -45,6 +45,7 @@ def _declare(L):
         "td_linear_split_bf16": [vp, i64, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
         "td_linear_splitk_bf16": [vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, vp, vp, i64, f32, vp],
         "td_linear_grouped2_bf16": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, i32, vp],
+        "td_gemm_plan_query": [i32, i32, i32, i32, i32],
         "td_linear_drain_bf16": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, i32, i32, i32, vp],
         "td_norm_rows_bf16": [vp, i64, vp, i64, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
         "td_qk_norm_rope_bf16": [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, i32, vp],
@@ -633,6 +634,18 @@ def linear_grouped2(x0, w0, b0, y0, x1, w1, b1, y1, act=ACT_NONE, gate0=None, re
                                         ptr(x1), M1, ptr(w1), ptr(b1), ptr(gate1), ptr(res1), ptr(y1),
                                         _rows(x0), _rows(y0), ldr, N, K, act, tile_cfg, stream_ptr()))
     return y0, y1
+
+
+OPERAND_BF16, OPERAND_INT8, OPERAND_E4M3 = 0, 1, 2
+
+
+def gemm_plan(M, N, K, shared=False, operand=OPERAND_BF16):
+    """td_gemm_plan_query: the tile an automatic launch of an M x N x K Linear takes (0 256x256, 1 256x64, 2 32x256, 3 288x192), alone on the
+    chip or under the shared-chip hint of several images in flight.  Host arithmetic: needs no GPU."""
+    cfg = lib().td_gemm_plan_query(int(M), int(N), int(K), int(bool(shared)), int(operand))
+    if cfg < 0:
+        raise ThinkDiffHipError(lib().td_last_error().decode())
+    return cfg
 
 
 def linear_drain(x0, w0, b0, y0, x1=None, w1=None, b1=None, y1=None, act=ACT_NONE, gate0=None, res0=None, gate1=None, res1=None,

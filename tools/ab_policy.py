@@ -1,6 +1,7 @@
 """Same-box, same-process A/B of an environment switch on whole images: config 5's shape (T = 258), 2 images in flight, a policy of
 tests/test_flux_full_depth_gpu.py::POLICIES; the switch (e.g. TD_GEMM_NO_TAIL=1) is read per launch, so both arms share weights, clocks and thermals.
-The "on" arm sets ENVVAR to $TD_AB_VALUE (default 1), the "off" arm unsets it (TD_AB_VALUE=0 with TD_GEMM_DRAIN: "on" is the one-tile launch).
+The "on" arm sets ENVVAR to $TD_AB_VALUE (default 1), the "off" arm unsets it (TD_AB_VALUE=0 with TD_GEMM_DRAIN: "on" is the one-tile launch;
+TD_AB_VALUE=0 with TD_GEMM_SHARED_TILES: "on" is the lone-launch tile rule, "off" the shipped choice by CU time).
 usage: python tools/ab_policy.py POLICY ENVVAR [rounds=3] [images in flight=2]"""
 import os
 import sys

@@ -62,6 +62,53 @@ def bench_gemmcfg():
         print(f"M={M0}+{M1} N={N} K={K}:  " + "   ".join(f"cfg{c}: {best[c]:7.3f} ms {fl/best[c]/1e9:7.1f} TF/s" for c in cfgs), flush=True)
 
 
+def bench_gemmtile():
+    """CU time of one tile of the 256x256 (cfg 0) and the 288x192 (cfg 3) shape per operand type: M = 4289, N = 3072 is ONE round of either (204 /
+    240 tiles on 256 CUs), so a launch's time is its tile's time.  Cold weights (pool cycling), interleaved rounds, K swept; the least-squares line
+    time = c0 + c1 * k-tiles (a k-tile = 128 operand bytes per row: 64 bf16 / 128 8-bit elements) gives the constants of the shared-chip tile
+    table in csrc/gemm_bf16.hip (td_gemm_plan), and tiles x time is the CU time the launch takes from a chip that other kernels keep full."""
+    M, N = 4289, 3072
+    tiles = {0: 204, 3: 240}
+    for kind in ("bf16", "int8", "fp8"):
+        esz = 2 if kind == "bf16" else 1
+        pts = {0: [], 3: []}
+        for kt in (96, 144, 192, 240):
+            K = kt * 128 // esz
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            npool = max(2, int(0.8e9 // (N * K * esz)))
+            pool = [(torch.randn(N, K, device="cuda") * 0.02).bfloat16() for _ in range(npool)]
+            b = torch.randn(N, device="cuda").bfloat16()
+            y = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            st = {"i": 0}
+            if kind == "bf16":
+                def f(cfg):
+                    st["i"] = (st["i"] + 1) % npool
+                    _hip.linear_grouped2(x, pool[st["i"]], b, y, None, None, None, None, tile_cfg=cfg)
+            else:
+                quant, lin = (_hip.quant_rows_int8, _hip.linear_int8) if kind == "int8" else (_hip.quant_rows_fp8, _hip.linear_fp8)
+                qpool = [quant(w) for w in pool]
+                xq, xs = quant(x)
+                del pool
+                def f(cfg):
+                    st["i"] = (st["i"] + 1) % npool
+                    wq, ws = qpool[st["i"]]
+                    lin(xq, xs, wq, ws, b, out=y, tile_cfg=cfg)
+            best = {0: 1e9, 3: 1e9}
+            for rnd in range(5):
+                for cfg in (0, 3):
+                    best[cfg] = min(best[cfg], timeit(lambda: f(cfg), iters=10, warmup=2))
+            for cfg in (0, 3):
+                pts[cfg].append((kt, best[cfg] * 1e3))
+            print(f"{kind} M={M} N={N} K={K} ({kt} k-tiles): " + "   ".join(
+                f"cfg{c}: {best[c]*1e3:7.1f} us x {tiles[c]} tiles = {best[c]*tiles[c]:6.2f} CU.ms" for c in (0, 3)) +
+                f"   cfg0 / cfg3 CU time {best[0]*tiles[0]/(best[3]*tiles[3]):.3f}", flush=True)
+        for cfg in (0, 3):
+            n = len(pts[cfg]); sx = sum(p[0] for p in pts[cfg]); sy = sum(p[1] for p in pts[cfg])
+            sxx = sum(p[0] * p[0] for p in pts[cfg]); sxy = sum(p[0] * p[1] for p in pts[cfg])
+            c1 = (n * sxy - sx * sy) / (n * sxx - sx * sx); c0 = (sy - c1 * sx) / n
+            print(f"{kind} cfg{cfg}: c0 = {c0:6.2f} us per tile, c1 = {c1:6.4f} us per k-tile", flush=True)
+
+
 def bench_gemmfp8():
     """fp8 (e4m3, v_mfma_scale 16x16x128) and int8 (v_mfma_i32_16x16x64_i8) vs bf16 GEMM on the FLUX shapes, cold weights (pool cycling),
     interleaved; plus the sustained FLUX-step mix per operand type (3 s windows, alternating)."""
