@@ -71,6 +71,13 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsig
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, p ? bytes : 0u, 0x00020000);
 }
 
+template <int ND>
+__device__ __forceinline__ void drain_row(const DrainState<ND>& ds, const int d) {
+  const __amdgpu_buffer_rsrc_t rs = make_rsrc(ds.C, ds.bytes);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) __builtin_amdgcn_raw_buffer_store_b128(ds.v[d][c], rs, ds.cb[c] + (unsigned)d * ds.step, 0, 0);
+}
+
 // `act` and `mode` are block-uniform run-time values: ONE body, with scalar branches around the optional stages of a row.
 // (One instantiation per activation, selected by a switch in front, made the compiler hoist the shared `acc + bias` of all
 // WM rows above the switch: 128 extra live values and a spilling kernel.)
@@ -291,9 +298,108 @@ __device__ __forceinline__ void epilogue_f32(const TdGemmParams& pp, const ProbV
 // swizzle, W ring, instruction interleave -- with the other MFMA and k-tiles of 128 elements; the int32 accumulators are exact and
 // become floats (x a_scale[m] x w_scale[n]) in front of the common epilogue.  Round 3: 8-bit operands whose quantisation noise is
 // ~4x below e4m3's on Gaussian-like operands (uniform step max/127 against a 3-bit mantissa).
-// One output tile: rows [m0, m0 + 32 WM) of problem `second_prob`, columns [n0, n0 + 64 WN).  Called once per workgroup.
-template <int WM, int WN, int CONV, bool FP8, bool I8>
-__device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0) {
+
+// One k-tile of the bf16 / int8 main loop: k-tile t is multiplied while the DMAs of A(t + 1) and W(t + 2) are issued (gemm_tile's main loop says
+// how the instruction kinds are spread).  stage_one, smem, the fragment offsets and the W ring position wcur are gemm_tile's.
+// The walk (ND > 0) also calls it with drow >= 0: the k-tile then stores deferred row drow of the previous tile, one chunk each in slots 9 and 13
+// (k-step 1: the DMAs ride on k-step 0), and with after_stores: the previous k-tile issued two stores behind its W DMAs, so the counted wait
+// leaves two more operations in flight.  Both are literals at every call, and the body is inlined at each.
+template <int WM, int WN, bool I8, int ND, class Stage, class DS>
+__device__ __forceinline__ void k_tile(const Stage& stage_one, char* smem, const int t, const int nt, int& wcur, const int foff0, const int aoff, const int woff,
+                                       f32x4_t (&acc)[WN][WM], [[maybe_unused]] DS* ds, [[maybe_unused]] const int drow, [[maybe_unused]] const bool after_stores) {
+  constexpr int A_BYTES = 32 * WM * ROW_BYTES, W_BYTES = 64 * WN * ROW_BYTES, W_REGION = 2 * A_BYTES;      // LDS: [A buf 0 | A buf 1 | W buf 0 | W buf 1 | W buf 2]
+  constexpr int SA = (4 * WM + 7) / 8, SW = (8 * WN + 7) / 8, NS = SA + SW;                                // staging instructions per wave: A, W
+  if (ND > 0 && after_stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW + 2) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
+  __builtin_amdgcn_s_barrier();
+  const char* wb = smem + W_REGION + wcur * W_BYTES + woff;
+  const char* ab = smem + (t & 1) * A_BYTES + aoff;
+  // tiles past the last are harmless re-loads of the last one (keeps the loop body branch-free)
+  const int kt_a = min(t + 1, nt - 1);
+  const int kt_w = min(t + 2, nt - 1);
+  const int abuf_next = (t + 1) & 1;
+  const int wbuf_next = wcur == 0 ? 2 : wcur - 1;   // (wcur + 2) % 3
+  wcur = wcur == 2 ? 0 : wcur + 1;
+  bf16x8_t wf[2][WN], af[2];
+#pragma unroll
+  for (int j = 0; j < WN; ++j) wf[0][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + foff0);
+  af[0] = *(const bf16x8_t*)(ab + foff0);
+  __builtin_amdgcn_sched_group_barrier(0x100, WN + 1, 0);  // the k-step-0 fragments first
+  constexpr int MASK_VMEM = 0x010, MASK_DS_READ = 0x100, MASK_MFMA = 0x008;
+  [[maybe_unused]] constexpr int MASK_VMEM_WRITE = 0x040;
+  constexpr int NIT = 2 * WM;                       // (k-step, m-tile) iterations per tile
+  constexpr int S_PER_IT = (NS + NIT - 1) / NIT;    // staging instructions per iteration
+  static_assert(ND == 0 || (NIT == 16 && NS <= 9 * S_PER_IT), "the deferred stores take slots 9 and 13, behind the last DMA");
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const int fo = foff0 ^ (ks << 6);
+#pragma unroll
+    for (int i = 0; i < WM; ++i) {
+      const int it = ks * WM + i;
+      const int cur = it & 1;
+      int nst = 0;
+#pragma unroll
+      for (int q = 0; q < S_PER_IT; ++q) {
+        const int s = it * S_PER_IT + q;
+        if (s < NS) { stage_one(s, abuf_next, wbuf_next, s < SA ? kt_a : kt_w); ++nst; }
+      }
+      const bool st = ND > 0 && drow >= 0 && (it == 9 || it == 13);
+      if constexpr (ND > 0) {
+        if (st) __builtin_amdgcn_raw_buffer_store_b128(ds->v[drow][it == 13], make_rsrc(ds->C, ds->bytes), ds->cb[it == 13] + (unsigned)drow * ds->step, 0, 0);
+      }
+      // prefetch the next A fragment (next m-tile, or m-tile 0 of the next k-step)
+      if (i + 1 < WM) af[cur ^ 1] = *(const bf16x8_t*)(ab + (i + 1) * 16 * ROW_BYTES + fo);
+      else if (ks == 0) af[cur ^ 1] = *(const bf16x8_t*)(ab + (fo ^ 64));
+      // prefetch the next k-step's W fragments behind the last m-tiles (fragment j rides on m-tile WM-1-j%WM)
+      int nwf = 0;
+      if (ks == 0) {
+#pragma unroll
+        for (int j = 0; j < WN; ++j)
+          if (WM - 1 - (j % WM) == i) {
+            wf[1][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + (fo ^ 64));
+            ++nwf;
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < WN; ++j) {
+        if constexpr (I8) {
+          typedef __attribute__((ext_vector_type(4))) int i32x4_t;
+          acc[j][i] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, wf[ks][j]), __builtin_bit_cast(i32x4_t, af[cur]),
+                                                                                         __builtin_bit_cast(i32x4_t, acc[j][i]), 0, 0, 0));
+        } else {
+          acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][j], af[cur], acc[j][i], 0, 0, 0);
+        }
+      }
+      const int nreads = ((i + 1 < WM || ks == 0) ? 1 : 0) + nwf;
+      switch (nst) {  // the builtin wants literal counts
+        case 1: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 1, 0); break;
+        case 2: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 2, 0); break;
+        case 3: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 3, 0); break;
+        default: break;
+      }
+      if (st) __builtin_amdgcn_sched_group_barrier(MASK_VMEM_WRITE, 1, 0);
+      switch (nreads) {
+        case 1: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 1, 0); break;
+        case 2: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 2, 0); break;
+        case 3: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 3, 0); break;
+        case 4: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 4, 0); break;
+        case 5: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 5, 0); break;
+        default: break;
+      }
+      __builtin_amdgcn_sched_group_barrier(MASK_MFMA, WN, 0);
+    }
+  }
+}
+
+// One output tile: rows [m0, m0 + 32 WM) of problem `second_prob`, columns [n0, n0 + 64 WN).  Called once per workgroup (ND == 0), or once per
+// tile of the persistent walk (ND > 0, ds = its DrainState<ND>; td_gemm_bf16_drain_kernel): the same body, and under `if constexpr (ND > 0)` what
+// only the walk does -- the previous tile's deferred stores inside this tile's first k-tiles with the wider counted wait behind them, the
+// wait + barrier that lets the next tile's prologue overwrite the LDS, lanes past N staying in, this tile's last ND m-tiles left in *ds.
+// *pending (workgroup-uniform): *ds holds the previous tile's rows on entry, this tile's on return.
+template <int WM, int WN, int CONV, bool FP8, bool I8, int ND = 0, class DS = void>
+__device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0, DS* ds = nullptr,
+                                          bool* pending = nullptr) {
+  static_assert(ND == 0 || (WM == 8 && WN == 4 && !CONV && !FP8 && !I8), "the walk: the 256x256 bf16 tile (no K split, no fp32 output: launch_cfg)");
   constexpr int BM = 32 * WM, BN = 64 * WN;
   constexpr int A_BYTES = BM * ROW_BYTES, W_BYTES = BN * ROW_BYTES;
   constexpr int GA = BM / 8, GW = BN / 8;           // 8-row staging groups per tile
@@ -310,18 +416,21 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
 
   const bf16_t* Aptr = second_prob ? p.g_A : p.A;
   const bf16_t* Wptr = second_prob ? p.g_W : p.W;
-  const int part = p.k_parts > 1 ? (int)blockIdx.y : 0;      // split-K launches (bf16, one problem): this workgroup contracts K-range `part`
-  if (p.k_parts > 1) { Aptr += (size_t)part * p.K; Wptr += (size_t)part * p.K; }
+  const bool k_split = ND == 0 && p.k_parts > 1;
+  const int part = k_split ? (int)blockIdx.y : 0;      // split-K launches (bf16, one problem): this workgroup contracts K-range `part`
+  if (k_split) { Aptr += (size_t)part * p.K; Wptr += (size_t)part * p.K; }
   ProbView pv;
   pv.bias = second_prob ? p.g_bias : p.bias;
   pv.gate = second_prob ? p.g_gate : p.gate;
   pv.res = second_prob ? p.g_res : p.res;
   pv.C = second_prob ? p.g_C : p.C;
   pv.M = second_prob ? p.g_M : p.M;
-  if (p.k_parts > 1) pv.C = (bf16_t*)((float*)p.C + (size_t)part * p.M * p.ldc);      // (out_f32: its slab of the fp32 partial sums)
+  if (k_split) pv.C = (bf16_t*)((float*)p.C + (size_t)part * p.M * p.ldc);      // (out_f32: its slab of the fp32 partial sums)
   pv.q8 = second_prob ? p.g_q8 : p.q8; pv.q8_inv = second_prob ? p.g_q8_inv : p.q8_inv; pv.q8_amax = second_prob ? p.g_q8_amax : p.q8_amax;
   pv.q8_smooth = second_prob ? p.g_q8_smooth : p.q8_smooth;
-  if (m0 >= pv.M) return;      // (a sub-tile of a split tail tile that lies wholly below the problem's last row; workgroup-uniform)
+  if constexpr (ND == 0) {
+    if (m0 >= pv.M) return;      // (a sub-tile of a split tail tile that lies wholly below the problem's last row; workgroup-uniform)
+  }
 
   // ---- buffer descriptors (wave-uniform; OOB rows read as zero) -----------------------------
   // (the stride-2 form reads a 2H x 2W input: its whole extent, or valid taps of the lower half would read as zero)
@@ -329,8 +438,8 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
                         : CONV ? (unsigned)((long long)(p.conv_H >> p.conv_up) * (p.conv_W >> p.conv_up) * p.conv_Cin * 2)
                                 : (unsigned)(((long long)(pv.M - 1) * p.lda + p.K) * ESZ);
   const unsigned bytesW = (unsigned)((((long long)p.N - 1) * p.ldw + p.K) * ESZ);
-  __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Aptr, 0, bytesA, 0x00020000);
-  __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)Wptr, 0, bytesW, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(Aptr, bytesA);
+  const __amdgpu_buffer_rsrc_t rsW = make_rsrc(Wptr, bytesW);
 
   // ---- per-lane staging source offsets ------------------------------------------------------
   const int srow = lane >> 3;                         // row inside the 8-row group
@@ -421,8 +530,13 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
     for (int i = 0; i < WM; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int nt = p.probe == 2 ? 1 : p.K / ((FP8 || I8) ? 2 * BK : BK);      // a k-tile is one 128-B row: 64 bf16 or 128 fp8 / int8
+  // prologue: k-tile 0 of both operands, then W of k-tile 1 (the W ring runs two k-tiles ahead; see the main loop)
 #pragma unroll
   for (int s = 0; s < NS; ++s) stage_one(s, 0, 0, 0);
+#pragma unroll
+  for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
+  int wcur = 0;
+  [[maybe_unused]] int done = 0;      // the walk: deferred rows issued inside this tile's k-loop (workgroup-uniform)
   if constexpr (FP8) {
     typedef __attribute__((ext_vector_type(4))) int i32x4_t;
     typedef __attribute__((ext_vector_type(8))) int i32x8_t;
@@ -430,9 +544,6 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
       const i32x4_t lo = *(const i32x4_t*)(base + foff0), hi = *(const i32x4_t*)(base + (foff0 ^ 64));
       return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
     };
-#pragma unroll
-    for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
-    int wcur = 0;
     constexpr int MASK_VMEM = 0x010, MASK_DS_READ = 0x100, MASK_MFMA = 0x008;
     constexpr int S_PER_IT = (NS + WM - 1) / WM;
     for (int t = 0; t < nt; ++t) {
@@ -492,11 +603,9 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
   // Ragged tile: at most 64 of the tile's rows exist (config 5's 258 text rows and 4 354 joint rows are whole 256-row tiles plus TWO rows:
   // 5.6 % of that shape's tiles).  The staging protocol is the main loop's (same DMA instructions in the same order, same counted wait --
   // every wave takes part), but only the m-tiles that hold rows are multiplied: the waves of the upper half have none, the others at most
-  // four, so the tile costs its operand traffic instead of a full tile of MFMAs on zeros.  Plain code: nothing here is matrix-bound.
+  // four, so the tile costs its operand traffic instead of a full tile of MFMAs on zeros.  Plain code: nothing here is matrix-bound (and the
+  // walk stores the previous tile's deferred rows behind it).
   const int mt_valid = wr == 0 ? (pv.M - m0 + 15) >> 4 : 0;      // wave-uniform
-#pragma unroll
-  for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
-  int wcur = 0;
   for (int t = 0; t < nt; ++t) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
     __builtin_amdgcn_s_barrier();
@@ -546,90 +655,41 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
   //    is prefetched TWO k-tiles ahead into a 3-deep W ring, the A tile (L2-resident activations) one
   //    ahead.  A DMAs are issued before the W DMAs of an iteration, so the counted `s_waitcnt vmcnt(SW)`
   //    at the barrier retires tile t+1's operands and leaves the W(t+2) transfers in flight across it.
+  // The walk: this tile's first ND k-tiles each store one deferred row of the previous tile (k_tile).
+  int t = 0;
+  if constexpr (ND > 0) {
+    if (*pending) {
 #pragma unroll
-  for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
-  int wcur = 0;
-  for (int t = 0; t < nt; ++t) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
-    __builtin_amdgcn_s_barrier();
-    const int wslot = wcur;
-    const char* wb = smem + W_REGION + wslot * W_BYTES + woff;
-    const char* ab = smem + (t & 1) * A_BYTES + aoff;
-    // tiles past the last are harmless re-loads of the last one (keeps the loop body branch-free)
-    const int kt_a = min(t + 1, nt - 1);
-    const int kt_w = min(t + 2, nt - 1);
-    const int abuf_next = (t + 1) & 1;
-    const int wbuf_next = wcur == 0 ? 2 : wcur - 1;   // (wcur + 2) % 3
-    wcur = wcur == 2 ? 0 : wcur + 1;
-    bf16x8_t wf[2][WN], af[2];
-#pragma unroll
-    for (int j = 0; j < WN; ++j) wf[0][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + foff0);
-    af[0] = *(const bf16x8_t*)(ab + foff0);
-    __builtin_amdgcn_sched_group_barrier(0x100, WN + 1, 0);  // the k-step-0 fragments first
-    constexpr int MASK_VMEM = 0x010, MASK_DS_READ = 0x100, MASK_MFMA = 0x008;
-    constexpr int NIT = 2 * WM;                       // (k-step, m-tile) iterations per tile
-    constexpr int S_PER_IT = (NS + NIT - 1) / NIT;    // staging instructions per iteration
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int fo = foff0 ^ (ks << 6);
-#pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        const int it = ks * WM + i;
-        const int cur = it & 1;
-        int nst = 0;
-#pragma unroll
-        for (int q = 0; q < S_PER_IT; ++q) {
-          const int s = it * S_PER_IT + q;
-          if (s < NS) { stage_one(s, abuf_next, wbuf_next, s < SA ? kt_a : kt_w); ++nst; }
+      for (int d = 0; d <= ND; ++d) {      // (the k-tile behind the last stores: the wider wait once more)
+        if (t < nt) {
+          k_tile<WM, WN, I8, ND>(stage_one, smem, t, nt, wcur, foff0, aoff, woff, acc, ds, d < ND ? d : -1, d > 0);
+          ++t;
+          if (d < ND) done = d + 1;
         }
-        // prefetch the next A fragment (next m-tile, or m-tile 0 of the next k-step)
-        if (i + 1 < WM) af[cur ^ 1] = *(const bf16x8_t*)(ab + (i + 1) * 16 * ROW_BYTES + fo);
-        else if (ks == 0) af[cur ^ 1] = *(const bf16x8_t*)(ab + (fo ^ 64));
-        // prefetch the next k-step's W fragments behind the last m-tiles (fragment j rides on m-tile WM-1-j%WM)
-        int nwf = 0;
-        if (ks == 0) {
-#pragma unroll
-          for (int j = 0; j < WN; ++j)
-            if (WM - 1 - (j % WM) == i) {
-              wf[1][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + (fo ^ 64));
-              ++nwf;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-          if constexpr (I8) {
-            typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-            acc[j][i] = __builtin_bit_cast(f32x4_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4_t, wf[ks][j]), __builtin_bit_cast(i32x4_t, af[cur]),
-                                                                                           __builtin_bit_cast(i32x4_t, acc[j][i]), 0, 0, 0));
-          } else {
-            acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][j], af[cur], acc[j][i], 0, 0, 0);
-          }
-        }
-        const int nreads = ((i + 1 < WM || ks == 0) ? 1 : 0) + nwf;
-        switch (nst) {  // the builtin wants literal counts
-          case 1: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 1, 0); break;
-          case 2: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 2, 0); break;
-          case 3: __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 3, 0); break;
-          default: break;
-        }
-        switch (nreads) {
-          case 1: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 1, 0); break;
-          case 2: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 2, 0); break;
-          case 3: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 3, 0); break;
-          case 4: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 4, 0); break;
-          case 5: __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 5, 0); break;
-          default: break;
-        }
-        __builtin_amdgcn_sched_group_barrier(MASK_MFMA, WN, 0);
       }
     }
   }
-
+  for (; t < nt; ++t) k_tile<WM, WN, I8, ND>(stage_one, smem, t, nt, wcur, foff0, aoff, woff, acc, ds, -1, false);
   }
 
   // ---- epilogue: lane owns NV contiguous columns of row (lane&15) of each m-tile -------------
   const int nbeg = n0 + wc * 16 * WN + (lane >> 4) * NV;
-  if (nbeg >= p.N || p.probe == 1) return;      // (probe 1: a run-time condition, so the k-loop stays; nothing else is added to the kernel)
+  if constexpr (ND > 0) {
+    // every wave has read its last fragments before anybody's next DMA may land on them (the next tile's prologue, or nothing)
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    // what a short k-loop (K = 64 ND and below) or the ragged loop could not take is stored behind it
+    if (*pending) {
+#pragma unroll
+      for (int d = 0; d < ND; ++d)
+        if (d >= done) drain_row(*ds, d);
+    }
+    *pending = false;
+    // lanes whose columns lie past N stay in (the walk goes on): their loads are range-checked, their chunks are dropped
+    if (p.probe == 1) return;
+  } else {
+    if (nbeg >= p.N || p.probe == 1) return;      // (probe 1: a run-time condition, so the k-loop stays; nothing else is added to the kernel)
+  }
   const bool second = (p.C2 != nullptr) && (n0 >= p.n_split);
   const int act = second ? p.act2 : p.act;
   const int mbeg = m0 + wr * 16 * WM + frow;
@@ -655,12 +715,15 @@ __device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, con
         }
     }
   }
-  if (p.out_f32) {
-    epilogue_f32<WM, WN>(p, pv, acc, mbeg, nbeg);
-    return;
+  if constexpr (ND == 0) {
+    if (p.out_f32) {
+      epilogue_f32<WM, WN>(p, pv, acc, mbeg, nbeg);
+      return;
+    }
   }
   const int mode = pv.gate ? 1 : (pv.res ? 2 : 0);      // after the activation, if any: bias -> act -> gate -> residual
-  epilogue<WM, WN, I8 && WN == 4>(p, pv, acc, mbeg, nbeg, second, act, mode);
+  epilogue<WM, WN, I8 && WN == 4, ND>(p, pv, acc, mbeg, nbeg, second, act, mode, ds);
+  if constexpr (ND > 0) *pending = true;
 }
 
 // XCD-aware numbering: workgroup ids go round-robin over the 8 XCDs; logical index t gives every XCD one CONTIGUOUS run of tiles (its 32 resident
@@ -670,6 +733,24 @@ __device__ __forceinline__ int xcd_contiguous(const int bid, const int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
+// Logical tile index -> tile.  Grouped M ordering: GROUP_M row tiles x all column tiles form a group that is walked column by column, so tiles
+// that follow each other share a W panel and four A panels.  Grouped launch: m-tiles [0, tiles_m0) belong to problem 0, the rest to problem 1
+// (same N, K, strides); tm counts inside its problem.
+struct TilePos { int tm, tn; bool second_prob; };
+__device__ __forceinline__ TilePos tile_pos(const int t, const TdGemmParams& p) {
+  constexpr int GROUP_M = 4;
+  const int per_group = GROUP_M * p.tiles_n;
+  const int gid = t / per_group;
+  const int first_m = gid * GROUP_M;
+  const int gsize = min(p.tiles_m - first_m, GROUP_M);
+  const int in_g = t - gid * per_group;
+  TilePos r;
+  r.tm = first_m + in_g % gsize;
+  r.tn = in_g / gsize;
+  r.second_prob = r.tm >= p.tiles_m0;
+  if (r.second_prob) r.tm -= p.tiles_m0;
+  return r;
+}
 
 // TAIL > 1 (256-row tiles, no conv): the launcher found that the tile count leaves a last, mostly empty round of the chip's CUs
 // (816 tiles on 256 CUs = 3.19 rounds: the launch takes 4 tile times), and cut the LAST `tail_tiles` tiles -- the ones dispatched
@@ -692,25 +773,14 @@ __global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmPar
   } else {
     t = xcd_contiguous((int)blockIdx.x, TAIL > 1 ? p.tail_first_wg : (int)gridDim.x);
   }
-  // grouped M ordering of the logical index
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * p.tiles_n;
-  const int gid = t / per_group;
-  const int first_m = gid * GROUP_M;
-  const int gsize = min(p.tiles_m - first_m, GROUP_M);
-  const int in_g = t - gid * per_group;
-  int tm = first_m + in_g % gsize;
-  const int tn = in_g / gsize;
-  // grouped launch: m-tiles [0, tiles_m0) belong to problem 0, the rest to problem 1 (same N, K, strides)
-  const bool second_prob = tm >= p.tiles_m0;
-  if (second_prob) tm -= p.tiles_m0;
+  const TilePos tp = tile_pos(t, p);
   if constexpr (TAIL > 1) {
     if (tail) {
-      gemm_tile<WM / TAIL, WN, CONV, FP8, I8>(p, smem, second_prob, tm * BM + sub * (BM / TAIL), tn * BN);
+      gemm_tile<WM / TAIL, WN, CONV, FP8, I8>(p, smem, tp.second_prob, tp.tm * BM + sub * (BM / TAIL), tp.tn * BN);
       return;
     }
   }
-  gemm_tile<WM, WN, CONV, FP8, I8>(p, smem, second_prob, tm * BM, tn * BN);
+  gemm_tile<WM, WN, CONV, FP8, I8>(p, smem, tp.second_prob, tp.tm * BM, tp.tn * BN);
 #endif
 }
 
@@ -723,200 +793,7 @@ __global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmPar
 // carry no DMA, and the counted waits of those k-tiles leave them in flight -- a store then has a whole k-tile of MFMAs to be acknowledged
 // under.  What a short k-loop (K = 64 ND and below) or the ragged loop cannot take is stored behind it, and the last tile's rows behind the walk.
 // Every output element is still one workgroup's whole contraction in the same k order through the same epilogue: bit-identical.
-template <int ND>
-__device__ __forceinline__ void drain_row(const DrainState<ND>& ds, const int d) {
-  const __amdgpu_buffer_rsrc_t rs = make_rsrc(ds.C, ds.bytes);
-#pragma unroll
-  for (int c = 0; c < 2; ++c) __builtin_amdgcn_raw_buffer_store_b128(ds.v[d][c], rs, ds.cb[c] + (unsigned)d * ds.step, 0, 0);
-}
-
-// One tile of the walk: gemm_tile<8, 4> for bf16 operands without its conv / 8-bit / split-K forms, plus the stores `ds` holds when `pending`.
-template <int ND>
-__device__ __forceinline__ void gemm_tile_drain(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0, DrainState<ND>& ds,
-                                                bool& pending) {
-  constexpr int WM = 8, WN = 4;
-  constexpr int BM = 32 * WM, BN = 64 * WN;
-  constexpr int A_BYTES = BM * ROW_BYTES, W_BYTES = BN * ROW_BYTES;
-  constexpr int SA = BM / 64, SW = BN / 64, NS = SA + SW;      // staging instructions per wave and k-tile
-  constexpr int NV = 4 * WN;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wid >> 2, wc = wid & 3;
-
-  ProbView pv;
-  pv.bias = second_prob ? p.g_bias : p.bias;
-  pv.gate = second_prob ? p.g_gate : p.gate;
-  pv.res = second_prob ? p.g_res : p.res;
-  pv.C = second_prob ? p.g_C : p.C;
-  pv.M = second_prob ? p.g_M : p.M;
-  pv.q8 = nullptr; pv.q8_inv = nullptr; pv.q8_amax = nullptr; pv.q8_smooth = nullptr;
-  const __amdgpu_buffer_rsrc_t rsA = make_rsrc(second_prob ? p.g_A : p.A, (unsigned)(((long long)(pv.M - 1) * p.lda + p.K) * 2));
-  const __amdgpu_buffer_rsrc_t rsW = make_rsrc(second_prob ? p.g_W : p.W, (unsigned)((((long long)p.N - 1) * p.ldw + p.K) * 2));
-
-  // staging offsets, LDS layout and fragment offsets: gemm_tile's
-  const int srow = lane >> 3;
-  const int schunk = ((lane & 7) ^ srow) << 4;
-  unsigned voffS[NS];
-  int ldsS[NS];
-#pragma unroll
-  for (int s = 0; s < SA; ++s) {
-    const int g = wid + 8 * s;
-    voffS[s] = (unsigned)(m0 + g * 8 + srow) * (unsigned)p.lda * 2u + schunk;
-    ldsS[s] = g * 1024;
-  }
-#pragma unroll
-  for (int s = 0; s < SW; ++s) {
-    const int g = wid + 8 * s;
-    const int rho = g * 8 + srow;
-    const int wcol = rho / (16 * WN);
-    const int rem = rho - wcol * (16 * WN);
-    const int j = rem >> 4, i16 = rem & 15;
-    const int n = n0 + wcol * (16 * WN) + (i16 >> 2) * NV + j * 4 + (i16 & 3);
-    voffS[SA + s] = (unsigned)n * (unsigned)p.ldw * 2u + schunk;
-    ldsS[SA + s] = g * 1024;
-  }
-  constexpr int W_REGION = 2 * A_BYTES;
-  auto stage_one = [&](int s, int abuf, int wbuf, int kt) {
-    if (s < SA) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (TD_LDS void*)(smem + abuf * A_BYTES + ldsS[s]), 16, voffS[s], kt * (BK * 2), 0, 0);
-    else __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (TD_LDS void*)(smem + W_REGION + wbuf * W_BYTES + ldsS[s]), 16, voffS[s], kt * (BK * 2), 0, 0);
-  };
-  const int frow = lane & 15;
-  const int foff0 = frow * ROW_BYTES + ((((lane >> 4)) ^ (lane & 7)) << 4);
-  const int aoff = (wr * 16 * WM) * ROW_BYTES;
-  const int woff = (wc * 16 * WN) * ROW_BYTES;
-
-  f32x4_t acc[WN][WM];
-#pragma unroll
-  for (int j = 0; j < WN; ++j)
-#pragma unroll
-    for (int i = 0; i < WM; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-  const int nt = p.probe == 2 ? 1 : p.K / BK;
-#pragma unroll
-  for (int s = 0; s < NS; ++s) stage_one(s, 0, 0, 0);
-#pragma unroll
-  for (int s = SA; s < NS; ++s) stage_one(s, 0, 1, min(1, nt - 1));
-  int wcur = 0;
-  int done = 0;      // deferred rows issued inside this tile's k-loop (workgroup-uniform)
-  if (pv.M - m0 <= p.ragged_rows) {
-    // gemm_tile's ragged loop (at most 64 rows exist): nothing is matrix-bound here, the deferred rows are stored behind it
-    const int mt_valid = wr == 0 ? (pv.M - m0 + 15) >> 4 : 0;
-    for (int t = 0; t < nt; ++t) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
-      __builtin_amdgcn_s_barrier();
-      const char* wb = smem + W_REGION + wcur * W_BYTES + woff;
-      const char* ab = smem + (t & 1) * A_BYTES + aoff;
-      const int kt_a = min(t + 1, nt - 1), kt_w = min(t + 2, nt - 1);
-      const int abuf_next = (t + 1) & 1;
-      const int wbuf_next = wcur == 0 ? 2 : wcur - 1;
-      wcur = wcur == 2 ? 0 : wcur + 1;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) stage_one(s, abuf_next, wbuf_next, s < SA ? kt_a : kt_w);
-      if (mt_valid > 0) {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-          const int fo = foff0 ^ (ks << 6);
-          bf16x8_t wf[WN];
-#pragma unroll
-          for (int j = 0; j < WN; ++j) wf[j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + fo);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            if (i < mt_valid) {
-              const bf16x8_t af = *(const bf16x8_t*)(ab + i * 16 * ROW_BYTES + fo);
-#pragma unroll
-              for (int j = 0; j < WN; ++j) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af, acc[j][i], 0, 0, 0);
-            }
-          }
-        }
-      }
-    }
-  } else {
-    // gemm_tile's main loop.  drow >= 0: this k-tile also stores deferred row drow, one chunk each in slots 9 and 13 (k-step 1: the DMAs ride on
-    // k-step 0).  after_stores: the previous k-tile issued two stores behind its W DMAs, so the counted wait leaves two more operations in flight.
-    // Both are literals at every call, and the body is inlined at each.
-    auto ktile = [&](const int t, const int drow, const bool after_stores) __attribute__((always_inline)) {
-      if (after_stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW + 2) : "memory");
-      else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(SW) : "memory");
-      __builtin_amdgcn_s_barrier();
-      const char* wb = smem + W_REGION + wcur * W_BYTES + woff;
-      const char* ab = smem + (t & 1) * A_BYTES + aoff;
-      const int kt_a = min(t + 1, nt - 1);
-      const int kt_w = min(t + 2, nt - 1);
-      const int abuf_next = (t + 1) & 1;
-      const int wbuf_next = wcur == 0 ? 2 : wcur - 1;
-      wcur = wcur == 2 ? 0 : wcur + 1;
-      bf16x8_t wf[2][WN], af[2];
-#pragma unroll
-      for (int j = 0; j < WN; ++j) wf[0][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + foff0);
-      af[0] = *(const bf16x8_t*)(ab + foff0);
-      __builtin_amdgcn_sched_group_barrier(0x100, WN + 1, 0);
-      constexpr int MASK_VMEM = 0x010, MASK_VMEM_WRITE = 0x040, MASK_DS_READ = 0x100, MASK_MFMA = 0x008;
-      const __amdgpu_buffer_rsrc_t rsD = make_rsrc(ds.C, ds.bytes);
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const int fo = foff0 ^ (ks << 6);
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-          const int it = ks * WM + i;
-          const int cur = it & 1;
-          if (it < NS) stage_one(it, abuf_next, wbuf_next, it < SA ? kt_a : kt_w);
-          const bool st = drow >= 0 && (it == 9 || it == 13);
-          if (st) __builtin_amdgcn_raw_buffer_store_b128(ds.v[drow][it == 13], rsD, ds.cb[it == 13] + (unsigned)drow * ds.step, 0, 0);
-          if (i + 1 < WM) af[cur ^ 1] = *(const bf16x8_t*)(ab + (i + 1) * 16 * ROW_BYTES + fo);
-          else if (ks == 0) af[cur ^ 1] = *(const bf16x8_t*)(ab + (fo ^ 64));
-          bool rd_w = false;
-          if (ks == 0) {
-#pragma unroll
-            for (int j = 0; j < WN; ++j)
-              if (WM - 1 - j == i) { wf[1][j] = *(const bf16x8_t*)(wb + j * 16 * ROW_BYTES + (fo ^ 64)); rd_w = true; }
-          }
-#pragma unroll
-          for (int j = 0; j < WN; ++j) acc[j][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][j], af[cur], acc[j][i], 0, 0, 0);
-          if (it < NS) __builtin_amdgcn_sched_group_barrier(MASK_VMEM, 1, 0);
-          if (st) __builtin_amdgcn_sched_group_barrier(MASK_VMEM_WRITE, 1, 0);
-          if (i + 1 < WM || ks == 0) {
-            if (rd_w) __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 2, 0);
-            else __builtin_amdgcn_sched_group_barrier(MASK_DS_READ, 1, 0);
-          }
-          __builtin_amdgcn_sched_group_barrier(MASK_MFMA, WN, 0);
-        }
-      }
-    };
-    int t = 0;
-    if (pending) {
-#pragma unroll
-      for (int d = 0; d <= ND; ++d) {      // (the k-tile behind the last stores: the wider wait once more)
-        if (t < nt) {
-          ktile(t, d < ND ? d : -1, d > 0);
-          ++t;
-          if (d < ND) done = d + 1;
-        }
-      }
-    }
-    for (; t < nt; ++t) ktile(t, -1, false);
-  }
-  // every wave has read its last fragments before anybody's next DMA may land on them (the next tile's prologue, or nothing)
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  if (pending) {
-#pragma unroll
-    for (int d = 0; d < ND; ++d)
-      if (d >= done) drain_row(ds, d);
-  }
-  pending = false;
-  if (p.probe == 1) return;
-  // epilogue.  Lanes whose columns lie past N stay in (the walk goes on): their loads are range-checked, their chunks are dropped.
-  const int nbeg = n0 + wc * 16 * WN + (lane >> 4) * NV;
-  const bool second = (p.C2 != nullptr) && (n0 >= p.n_split);
-  const int act = second ? p.act2 : p.act;
-  const int mbeg = m0 + wr * 16 * WM + frow;
-  const int mode = pv.gate ? 1 : (pv.res ? 2 : 0);
-  epilogue<WM, WN, false, ND>(p, pv, acc, mbeg, nbeg, second, act, mode, &ds);
-  pending = true;
-}
-
+// A tile of the walk is gemm_tile<8, 4> itself with ND > 0 -- one tile body, one k-tile body; what the walk adds is marked `ND > 0` there.
 constexpr int TD_DRAIN_ROWS = 4;      // m-tiles (of 8) whose stores a tile leaves to the next: see DESIGN 4
 
 template <int ND>
@@ -929,18 +806,8 @@ __global__ __launch_bounds__(512, 1) void td_gemm_bf16_drain_kernel(const TdGemm
   // virtual workgroup ids b, b + G, ...: with G a multiple of 8 they are all on this workgroup's XCD, so every tile runs where the
   // one-tile-per-workgroup launch would have put it, in the same order
   for (int v = (int)blockIdx.x; v < total; v += (int)gridDim.x) {
-    const int t = xcd_contiguous(v, total);
-    constexpr int GROUP_M = 4;
-    const int per_group = GROUP_M * p.tiles_n;
-    const int gid = t / per_group;
-    const int first_m = gid * GROUP_M;
-    const int gsize = min(p.tiles_m - first_m, GROUP_M);
-    const int in_g = t - gid * per_group;
-    int tm = first_m + in_g % gsize;
-    const int tn = in_g / gsize;
-    const bool second_prob = tm >= p.tiles_m0;
-    if (second_prob) tm -= p.tiles_m0;
-    gemm_tile_drain<ND>(p, smem, second_prob, tm * 256, tn * 256, ds, pending);
+    const TilePos tp = tile_pos(xcd_contiguous(v, total), p);
+    gemm_tile<8, 4, 0, false, false, ND>(p, smem, tp.second_prob, tp.tm * 256, tp.tn * 256, &ds, &pending);
   }
   if (pending) {
 #pragma unroll
