@@ -190,6 +190,21 @@ def test_fp8_attention_more_items_than_cus(hip, S, H):
     assert _rel(out2, out) < 2e-3        # (the merge order of a split item is fixed; which owner rounds last is not)
 
 
+def test_fp8_attention_split_items_small(hip):
+    """S = 300 with cus / 2 + 2 heads: the smallest shape at which nearly every (query tile, head) item is split over two persistent
+    workgroups and merged through the hand-off, against the restatement (and the exact softmax) by the bounds of the small cases above."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    S, H = 300, cus // 2 + 2
+    g = torch.Generator().manual_seed(S + H)
+    qkv = torch.randn(S, 3 * H * 128, generator=g).bfloat16()
+    out, _, _ = _run(hip, qkv.cuda(), H)
+    assert torch.isfinite(out.float()).all()
+    e_rest = _rel(out, _restated(qkv, H))
+    e_exact = _rel(out, _exact(qkv, H))
+    print(f"S={S} H={H}: vs restatement {e_rest:.3e}, vs exact {e_exact:.3e}")
+    assert e_rest < 5e-3 and e_exact < 8e-2
+
+
 @pytest.mark.parametrize("S,H,split", [(64, 1, 0), (300, 2, 40), (449, 4, 449), (1000, 3, 193)])
 def test_fused_qk_norm_rope_pack_is_bit_identical(hip, S, H, split):
     """td_attention_fp8_qk_rope (QK-RMSNorm + RoPE inside the pack pass, raw projections in) against td_qk_norm_rope_bf16 followed by

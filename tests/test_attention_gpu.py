@@ -88,6 +88,44 @@ def test_joint_attention_more_items_than_cus(hip, B, S, H):
     _check(outs[0], ref)
 
 
+@pytest.mark.parametrize("shape", ["split_items", "one_tile_items"])
+def test_stream_k_small_shapes(hip, shape):
+    """The stream-K form at the smallest shapes that still take its two ways through an item, sized from the device's CU count:
+    S = 300 with cus / 2 + 2 heads (two query tiles x five KV tiles per head, cus + 4 items: nearly every item is split over two
+    workgroups and merged through the hand-off) and S = 64 with cus + 4 heads (one KV tile per item: nothing can be split, some
+    workgroups run two items).  Within the module's tolerance of the fp32 reference; three launches with a foreign launch in between
+    agree bit for bit; and variant 2 (no XCD remap) equals variant 0 bit for bit -- the ranges and the merge order of a split item
+    do not depend on which physical workgroup takes a range."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    S, H = (300, cus // 2 + 2) if shape == "split_items" else (64, cus + 4)
+    W = H * 128
+    g = torch.Generator().manual_seed(S + H)
+    qkv = torch.randn(1, S, 3 * W, generator=g).bfloat16()
+    d = qkv.cuda()
+    other = torch.randn(1, S, 3 * W, generator=g).bfloat16().cuda()
+
+    def launch(x):
+        out = torch.zeros(1, S, W, dtype=torch.bfloat16, device="cuda")
+        hip.attention(x[:, :, :W], x[:, :, W:2 * W], x[:, :, 2 * W:], out, H, H)
+        torch.cuda.synchronize()
+        return out
+
+    outs = [launch(d), launch(d)]
+    launch(other)                                 # the LDS and the hand-off slots then hold foreign data
+    outs.append(launch(d))
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    _check(outs[0], _ref(qkv[:, :, :W], qkv[:, :, W:2 * W], qkv[:, :, 2 * W:], H, H, False))
+    lib = hip.lib()
+    cur = lib.td_attention_set_variant(2)
+    try:
+        if cur != 0:
+            return                                # the module's fixture runs every variant: the 0-against-2 comparison is made once, under 0
+        plain_order = launch(d)
+    finally:
+        lib.td_attention_set_variant(cur)
+    assert torch.equal(outs[0], plain_order), "stream-K with and without the XCD remap differ"
+
+
 def test_persistent_attention_concurrent_streams(hip):
     """Three persistent (stream-K) attention launches share the chip on three streams, many times over, beside an unrelated
     memory-bound kernel on a fourth: every result must equal the same launch run alone.  The split items' two owners never

@@ -20,6 +20,22 @@
 //    no head-major re-layout pass exists anywhere on the path.
 #include "attention_common.h"
 
+// Normalise and store this wave's rows of an item: lane holds O[q][db*32 + (r&3) + 8 (r>>2) + 4 h5].  The int8 form (p.q8; compiled in
+// under Q8 only: it exists for the joint attention), else 16-byte stores unless the rows are not 16-byte multiples or variant bit 0x200 asks
+// for the narrow form.  Ob: the output of this item's batch entry / segment, Sq its row count.
+template <bool Q8>
+__device__ __forceinline__ void attn_store_item(const TdAttnParams& p, const f32x16_t (&o)[4], const float inv, bf16_t* Ob, const int Sq,
+                                                const int head, const int q, const int h5) {
+  if constexpr (Q8) {
+    if (p.q8) {
+      const int qr = min(q, Sq - 1);
+      attn_store_rows_q8(o, inv, p.q8 + (size_t)qr * p.ldq8 + head * D, h5, p.q8_inv[qr], p.q8_amax + qr, q < Sq);
+      return;
+    }
+  }
+  attn_store_rows(o, inv, Ob + (size_t)min(q, Sq - 1) * p.ldo + head * D, h5, (p.ldo & 7) == 0 && !(p.variant & 0x200), q < Sq);
+}
+
 // ---------------------------------------------------------------------------------------------
 // One workgroup per (256-row query tile, head, batch).  Lean instruction stream: rocprofv3 PMC on the first form of this
 // kernel (S=4289, 24 heads) showed 7.2 VALU instructions per MFMA and the SIMD's issue slots, not the matrix pipe (50 % busy),
@@ -200,16 +216,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(c
   }
 
   const float inv = 1.0f / (RS ? lacc[0] : half_swap_sum(lacc[0]));
-  const int q = q0 + l31;
-  bool stored = false;
-  if constexpr (!CAUSAL && !BIAS && !VARLEN) {      // the int8 output form exists for the joint attention only (keeps it out of the other streams)
-    if (p.q8) {
-      const int qr = min(q, Sq - 1);
-      attn_store_rows_q8(o, inv, p.q8 + (size_t)qr * p.ldq8 + head * D, h5, p.q8_inv[qr], p.q8_amax + qr, q < Sq);
-      stored = true;
-    }
-  }
-  if (!stored) attn_store_rows(o, inv, Ob + (size_t)min(q, Sq - 1) * p.ldo + head * D, h5, (p.ldo & 7) == 0 && !(p.variant & 0x200), q < Sq);
+  // (the int8 output form exists for the joint attention only: it stays out of the other streams)
+  attn_store_item<!CAUSAL && !BIAS && !VARLEN>(p, o, inv, Ob, Sq, head, q0 + l31, h5);
 #endif
 }
 
@@ -248,20 +256,11 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kerne
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h5 = lane >> 5;
   const int l31 = lane & 31;
-  unsigned* const cnt = (unsigned*)ws + 16;
   TD_LDS unsigned* const ticket_lds = (TD_LDS unsigned*)(smem + 4 * TILE_BYTES);
 
-  // logical range of this workgroup: with XCD_REMAP, workgroups that share an XCD (equal blockIdx % 8 under round-robin
-  // placement; speed only) take neighbouring ranges = neighbouring query tiles of the same heads = the same K/V in that L2
   const int G = gridDim.x;
-  int r = blockIdx.x;
-  if constexpr (XCD_REMAP) {
-    const int q8 = G >> 3, r8 = G & 7, xcd = r & 7;
-    r = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (r >> 3);
-  }
-  const long long total = (long long)n_qblk * p.Hq * p.batch * nt;
-  long long it = total * r / G;
-  const long long it_end = total * (r + 1) / G;
+  long long it, it_end;
+  const int r = attn_sk_range<XCD_REMAP>((long long)n_qblk * p.Hq * p.batch * nt, it, it_end);
 
   const int Skv = p.Skv;
   constexpr int GROUPS = KV_TILE / 4;
@@ -390,70 +389,9 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kerne
     }
     float l_run = RS ? lacc[0] : half_swap_sum(lacc[0]);           // the complete row sum (RS: every register of lacc holds it, in both lane halves)
     // ---- what happens to the state: leave it for the other owner, combine with the other owner's, or just finish ----------
-    if (kb > 0 || ke < nt) {
-      const int j = kb > 0 ? r : r + 1;                  // boundary between ranges j-1 (head part) and j (tail part)
-      const bool tail = kb > 0;
-      const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(ws + SK_HEADER_BYTES), 0, (unsigned)(2 * G) * SK_SLOT_FLOATS * 4u, 0x00020000);
-      const unsigned lane_off = ((unsigned)wid * 17u * 64u + (unsigned)lane) * 16u;      // [wave][chunk 0..16][lane] x 16 bytes
-      const unsigned mine = (unsigned)(tail ? j : G + j) * (SK_SLOT_FLOATS * 4u) + lane_off;      // T[j] / H[j]
-      const unsigned theirs = (unsigned)(tail ? G + j : j) * (SK_SLOT_FLOATS * 4u) + lane_off;
-      // one lane asks, everyone hears the answer through LDS (block-uniform control flow below)
-      auto ask = [&](bool draw) -> unsigned {
-        __syncthreads();
-        if (tid == 0)
-          *ticket_lds = draw ? __hip_atomic_fetch_add(cnt + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        return *ticket_lds;
-      };
-      bool other_ready = !tail && ask(false) == 1u;      // head part: the tail part's owner has normally long been through
-      if (!other_ready) {
-        // leave the state for the other owner: write-through stores, drained by every wave, then the ticket
-#pragma unroll
-        for (int q4 = 0; q4 < 16; ++q4) {
-          const u32x4_t v = {as_u32(o[q4 >> 2][4 * (q4 & 3)]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 1]),
-                             as_u32(o[q4 >> 2][4 * (q4 & 3) + 2]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 3])};
-          __builtin_amdgcn_raw_buffer_store_b128(v, rsS, mine + q4 * 1024u, 0, 16);       // aux 16 = sc1
-        }
-        const u32x4_t ml = {as_u32(m_run), as_u32(l_run), 0u, 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(ml, rsS, mine + 16 * 1024u, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        other_ready = ask(true) == 1u;                   // the barrier inside orders every wave's drain before the add
-        if (!other_ready) continue;                      // first to arrive: the other owner finishes the item
-      }
-      // second to arrive: the other state is complete and published before the atomic that told us
-      if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const u32x4_t ml = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + 16 * 1024u, 0, 0);
-      const float m2 = as_f32(ml[0]), l2 = as_f32(ml[1]);
-      const float mm = fmaxf(m_run, m2);
-      const float a1 = __builtin_amdgcn_exp2f((m_run - mm) * cc), a2 = __builtin_amdgcn_exp2f((m2 - mm) * cc);
-      // One operation order whoever merges -- fma(head, a_head, tail * a_tail) -- so the result does not depend on which owner
-      // arrived second (it does under load; the sum is otherwise the same to one fp32 rounding).
-      auto comb = [&](float own, float other) {
-        return tail ? __builtin_fmaf(other, a2, own * a1) : __builtin_fmaf(own, a1, other * a2);
-      };
-      l_run = comb(l_run, l2);
-#pragma unroll
-      for (int q4 = 0; q4 < 16; ++q4) {
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + q4 * 1024u, 0, 0);
-#pragma unroll
-        for (int k4 = 0; k4 < 4; ++k4)
-          o[q4 >> 2][4 * (q4 & 3) + k4] = comb(o[q4 >> 2][4 * (q4 & 3) + k4], as_f32(v[k4]));
-      }
-      if (tid == 0) __hip_atomic_store(cnt + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // both tickets drawn: ready for the next launch
-    }
+    if ((kb > 0 || ke < nt) && !attn_sk_handoff(o, m_run, l_run, cc, r, G, kb > 0, ws, ticket_lds, tid, wid)) continue;
 
-    // ---- normalise and store: lane holds O[q][db*32 + (r&3) + 8 (r>>2) + 4 h5] ------------------------------------------
-    const float inv = 1.0f / l_run;
-    const int q = q0 + l31;
-    if (p.q8) {
-      const int qr = min(q, p.Sq - 1);
-      attn_store_rows_q8(o, inv, p.q8 + (size_t)qr * p.ldq8 + head * D, h5, p.q8_inv[qr], p.q8_amax + qr, q < p.Sq);
-    } else {
-      attn_store_rows(o, inv, p.O + (size_t)batch * p.o_bstride + (size_t)min(q, p.Sq - 1) * p.ldo + head * D, h5, (p.ldo & 7) == 0 && !(p.variant & 0x200), q < p.Sq);
-    }
+    attn_store_item<true>(p, o, 1.0f / l_run, p.O + (size_t)batch * p.o_bstride, p.Sq, head, q0 + l31, h5);
   }
 #endif
 }
@@ -494,27 +432,11 @@ int device_cus(int dev) {
   return n;
 }
 
-template <typename K>
-int set_lds_attr_once(K kernel, int bytes, std::atomic<unsigned long long>& done, int dev) {
-  if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-    TD_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-  }
-  return 0;
-}
-
 }  // namespace
 
 // shared with attention_fp8.hip
 int td_attn_device_cus(int dev) { return device_cus(dev); }
 int td_attn_pooled_workspace(int dev, int ranges, hipStream_t stream, char** out) { return sk_pooled_workspace(dev, ranges, stream, out); }
-int td_attn_set_lds_attr(const void* kernel, int bytes, std::atomic<unsigned long long>& done, int dev) {
-  if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-    TD_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    done.fetch_or(1ull << (dev & 63), std::memory_order_release);
-  }
-  return 0;
-}
 
 int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.head_dim == D, "td_attention: head_dim=%d unsupported (only 128)", p.head_dim);
@@ -547,7 +469,6 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   constexpr int lds = 4 * TILE_BYTES;
   int dev = 0;
   TD_CHECK_HIP(hipGetDevice(&dev));
-  static std::atomic<unsigned long long> a0{0}, a1{0}, a2{0}, a3{0}, a4{0}, a5{0};
   dim3 grid((p.Sq + NW * Q_WAVE - 1) / (NW * Q_WAVE), p.Hq, p.batch);
   if (p.bias) TD_CHECK_ARG(p.Skv % 4 == 0 && ((uintptr_t)p.bias) % 16 == 0 && p.batch == 1, "td_attention: bias needs Skv %% 4 == 0, 16-byte alignment, batch 1");
   if (p.kv_lens) TD_CHECK_ARG(p.causal && !p.bias, "td_attention: per-sequence kv lengths exist for the causal kernel only");
@@ -558,16 +479,9 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   if (p.seg_starts) {   // packed segments: plain grid over (query tiles of the longest segment, heads, segments)
     TD_CHECK_ARG(!p.bias && !p.kv_lens && p.Sq == p.Skv && (!p.causal || p.causal_offset == 0),
                  "td_attention(varlen): full or causal (offset 0) attention inside each segment only (no bias or cache lengths)");
-    if (p.causal) {      // packed causal prefill of the Qwen2-VL engine (prompts of different lengths back to back, no padding rows)
-      static std::atomic<unsigned long long> a12{0};
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<true, NW, false, true>, lds, a12, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<true, NW, false, true>), grid, dim3(NW * 64), lds, stream, q);
-      TD_CHECK_LAUNCH();
-      return 0;
-    }
-    static std::atomic<unsigned long long> a6{0};
-    if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<false, NW, false, true>, lds, a6, dev)) return e;
-    hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<false, NW, false, true>), grid, dim3(NW * 64), lds, stream, q);
+    // causal: the packed prefill of the Qwen2-VL engine (prompts of different lengths back to back, no padding rows)
+    if (int e = p.causal ? attn_launch<td_attn_fwd_d128_lean_kernel<true, NW, false, true>>(grid, NW * 64, lds, stream, dev, q)
+                         : attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, false, true>>(grid, NW * 64, lds, stream, dev, q)) return e;
     TD_CHECK_LAUNCH();
     return 0;
   }
@@ -577,55 +491,31 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   const int n_items = (int)(grid.x * grid.y * grid.z);
   const int cus = device_cus(dev);
   const int nt = (p.Skv + KV_TILE - 1) / KV_TILE;
+  int e;
   if (!p.causal && !p.bias && !p.kv_lens && (p.variant & 0xff) != 1 && cus > 0 && n_items > cus && cus < SK_MAX_RANGES && (long long)n_items * nt < (1ll << 31)) {
     char* ws = (char*)p.sk_ws;
     if (!ws) {
       if (int rc = sk_pooled_workspace(dev, cus, stream, &ws)) return rc;
     }
     constexpr int lds_sk = lds + 16;        // + the ticket word
-    if (p.q_prescaled && p.score_bound > 0.f) {
-      static std::atomic<unsigned long long> a10{0};
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true>, lds_sk, a10, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true>), dim3(cus), dim3(NW * 64), lds_sk, stream, q, ws, (int)grid.x, nt);
-    } else if (p.q_prescaled) {
-      static std::atomic<unsigned long long> a7{0};
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_streamk_kernel<NW, true, true>, lds_sk, a7, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_streamk_kernel<NW, true, true>), dim3(cus), dim3(NW * 64), lds_sk, stream, q, ws, (int)grid.x, nt);
-    } else if ((p.variant & 0xff) == 2) {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_streamk_kernel<NW, false>, lds_sk, a4, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_streamk_kernel<NW, false>), dim3(cus), dim3(NW * 64), lds_sk, stream, q, ws, (int)grid.x, nt);
-    } else {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_streamk_kernel<NW, true>, lds_sk, a5, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_streamk_kernel<NW, true>), dim3(cus), dim3(NW * 64), lds_sk, stream, q, ws, (int)grid.x, nt);
-    }
-    TD_CHECK_LAUNCH();
-    return 0;
-  }
-  if (p.bias) {   // separate instantiation: the score-bias loads must not touch the hot no-bias instruction stream
-    if (p.causal) {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<true, NW, true>, lds, a0, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<true, NW, true>), grid, dim3(NW * 64), lds, stream, q);
-    } else {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<false, NW, true>, lds, a1, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<false, NW, true>), grid, dim3(NW * 64), lds, stream, q);
-    }
+    const dim3 ranges(cus);
+    const int n_qblk = (int)grid.x;
+    if (p.q_prescaled && p.score_bound > 0.f) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+    else if (p.q_prescaled) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+    else if ((p.variant & 0xff) == 2) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, false>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+    else e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+  } else if (p.bias) {   // separate instantiations: the score-bias loads must not touch the hot no-bias instruction stream
+    e = p.causal ? attn_launch<td_attn_fwd_d128_lean_kernel<true, NW, true>>(grid, NW * 64, lds, stream, dev, q)
+                 : attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, true>>(grid, NW * 64, lds, stream, dev, q);
+  } else if (p.q_prescaled && p.score_bound > 0.f) {
+    e = attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, false, false, true, true, true>>(grid, NW * 64, lds, stream, dev, q);
+  } else if (p.q_prescaled) {
+    e = attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, false, false, true>>(grid, NW * 64, lds, stream, dev, q);
   } else {
-    if (p.q_prescaled && p.score_bound > 0.f) {
-      static std::atomic<unsigned long long> a11{0};
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<false, NW, false, false, true, true, true>, lds, a11, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<false, NW, false, false, true, true, true>), grid, dim3(NW * 64), lds, stream, q);
-    } else if (p.q_prescaled) {
-      static std::atomic<unsigned long long> a8{0};
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<false, NW, false, false, true>, lds, a8, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<false, NW, false, false, true>), grid, dim3(NW * 64), lds, stream, q);
-    } else if (p.causal) {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<true, NW>, lds, a2, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<true, NW>), grid, dim3(NW * 64), lds, stream, q);
-    } else {
-      if (int e = set_lds_attr_once(td_attn_fwd_d128_lean_kernel<false, NW>, lds, a3, dev)) return e;
-      hipLaunchKernelGGL((td_attn_fwd_d128_lean_kernel<false, NW>), grid, dim3(NW * 64), lds, stream, q);
-    }
+    e = p.causal ? attn_launch<td_attn_fwd_d128_lean_kernel<true, NW>>(grid, NW * 64, lds, stream, dev, q)
+                 : attn_launch<td_attn_fwd_d128_lean_kernel<false, NW>>(grid, NW * 64, lds, stream, dev, q);
   }
+  if (e) return e;
   TD_CHECK_LAUNCH();
   return 0;
 }

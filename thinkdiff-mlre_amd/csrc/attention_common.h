@@ -1,6 +1,6 @@
-// Shared pieces of the gfx950 attention kernels (attention_bf16.hip: the 8-wave forms; attention_pp.hip: the 4-wave form with two
-// row blocks per wave): tile constants, lane-exchange helpers, the tile math (reference point and row sums on the matrix pipe),
-// the 16-byte epilogue store and the layout of the stream-K hand-off workspace.  Internal; included by those two files only.
+// Shared pieces of the gfx950 attention kernels (attention_bf16.hip: the bf16 forms; attention_fp8.hip: the e4m3 form): tile constants,
+// lane-exchange helpers, the bf16 tile math (reference point and row sums on the matrix pipe), the 16-byte epilogue stores, the stream-K
+// range and split-item hand-off both persistent kernels run, and the once-per-device launch helper.  Internal; included by those two files only.
 #pragma once
 #include <atomic>
 #include <mutex>
@@ -262,13 +262,106 @@ __device__ __forceinline__ void attn_store_rows_q8(const f32x16_t (&o)[4], const
   if (live && h5 == 0) __hip_atomic_fetch_max(amax, as_u32(am), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-}  // namespace
-
-int td_attn_set_lds_attr(const void* kernel, int bytes, std::atomic<unsigned long long>& done, int dev);
-
-namespace {
+// ---- stream-K: the range of a persistent workgroup and the hand-off of an item split over two of them ---------------------------
+// (the structure and the reasons are told in front of td_attn_fwd_d128_streamk_kernel, attention_bf16.hip)
 constexpr int SK_SLOT_FLOATS = 8 * 64 * 68;          // per boundary and side: 8 waves x 64 lanes x (64 O + m + l + 2 pad) floats
 constexpr int SK_HEADER_BYTES = 4096;                 // cnt[j] at word 16 + j
 constexpr int SK_MAX_RANGES = SK_HEADER_BYTES / 4 - 16;
 // workspace = [header | T slots: ranges x SK_SLOT_FLOATS | H slots: ranges x SK_SLOT_FLOATS]
+
+// Logical range r of this workgroup and its (item, KV tile) iterations [it, it_end) out of `total`: with XCD_REMAP, workgroups that
+// share an XCD (equal blockIdx % 8 under round-robin placement; speed only) take neighbouring ranges = neighbouring query tiles of
+// the same heads = the same K/V in that L2
+template <bool XCD_REMAP>
+__device__ __forceinline__ int attn_sk_range(const long long total, long long& it, long long& it_end) {
+  const int G = gridDim.x;
+  int r = blockIdx.x;
+  if constexpr (XCD_REMAP) {
+    const int q8 = G >> 3, r8 = G & 7, xcd = r & 7;
+    r = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (r >> 3);
+  }
+  it = total * r / G;
+  it_end = total * (r + 1) / G;
+  return r;
+}
+
+// What happens to the un-normalised state (o, m_run, l_run) of a PART of an item run by range r of G: leave it for the other owner
+// (returns false: this workgroup is done with the item) or combine it with the other owner's (returns true: o and l_run are the
+// whole item's, the caller normalises and stores).  `tail`: this is the item's tail part (KV tiles kb > 0 .. nt), met first by its
+// range; otherwise the head part (0 .. ke < nt), met last.  cc: scale of the stored reference points (1 when they are log2 units).
+__device__ __forceinline__ bool attn_sk_handoff(f32x16_t (&o_io)[4], const float m_run, float& l_run, const float cc, const int r, const int G,
+                                                const bool tail, char* ws, TD_LDS unsigned* const ticket_lds, const int tid, const int wid) {
+  const int lane = tid & 63;
+  // (a copy: indexing the caller's array through the reference cost the e4m3 kernels 400-600 spilled VGPRs, profiles/attention_one_item_body.md)
+  f32x16_t o[4] = {o_io[0], o_io[1], o_io[2], o_io[3]};
+  unsigned* const cnt = (unsigned*)ws + 16;
+  const int j = tail ? r : r + 1;                    // boundary between ranges j-1 (head part) and j (tail part)
+  const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(ws + SK_HEADER_BYTES), 0, (unsigned)(2 * G) * SK_SLOT_FLOATS * 4u, 0x00020000);
+  const unsigned lane_off = ((unsigned)wid * 17u * 64u + (unsigned)lane) * 16u;      // [wave][chunk 0..16][lane] x 16 bytes
+  const unsigned mine = (unsigned)(tail ? j : G + j) * (SK_SLOT_FLOATS * 4u) + lane_off;      // T[j] / H[j]
+  const unsigned theirs = (unsigned)(tail ? G + j : j) * (SK_SLOT_FLOATS * 4u) + lane_off;
+  // one lane asks, everyone hears the answer through LDS (block-uniform control flow below)
+  auto ask = [&](bool draw) -> unsigned {
+    __syncthreads();
+    if (tid == 0)
+      *ticket_lds = draw ? __hip_atomic_fetch_add(cnt + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                         : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    return *ticket_lds;
+  };
+  bool other_ready = !tail && ask(false) == 1u;      // head part: the tail part's owner has normally long been through
+  if (!other_ready) {
+    // leave the state for the other owner: write-through stores, drained by every wave, then the ticket
+#pragma unroll
+    for (int q4 = 0; q4 < 16; ++q4) {
+      const u32x4_t v = {as_u32(o[q4 >> 2][4 * (q4 & 3)]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 1]),
+                         as_u32(o[q4 >> 2][4 * (q4 & 3) + 2]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 3])};
+      __builtin_amdgcn_raw_buffer_store_b128(v, rsS, mine + q4 * 1024u, 0, 16);       // aux 16 = sc1
+    }
+    const u32x4_t ml = {as_u32(m_run), as_u32(l_run), 0u, 0u};
+    __builtin_amdgcn_raw_buffer_store_b128(ml, rsS, mine + 16 * 1024u, 0, 16);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    other_ready = ask(true) == 1u;                   // the barrier inside orders every wave's drain before the add
+    if (!other_ready) return false;                  // first to arrive: the other owner finishes the item
+  }
+  // second to arrive: the other state is complete and published before the atomic that told us
+  if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  const u32x4_t ml = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + 16 * 1024u, 0, 0);
+  const float m2 = as_f32(ml[0]), l2 = as_f32(ml[1]);
+  const float mm = fmaxf(m_run, m2);
+  const float a1 = __builtin_amdgcn_exp2f((m_run - mm) * cc), a2 = __builtin_amdgcn_exp2f((m2 - mm) * cc);
+  // One operation order whoever merges -- fma(head, a_head, tail * a_tail) -- so the result does not depend on which owner
+  // arrived second (it does under load; the sum is otherwise the same to one fp32 rounding).
+  auto comb = [&](float own, float other) {
+    return tail ? __builtin_fmaf(other, a2, own * a1) : __builtin_fmaf(own, a1, other * a2);
+  };
+  l_run = comb(l_run, l2);
+#pragma unroll
+  for (int q4 = 0; q4 < 16; ++q4) {
+    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + q4 * 1024u, 0, 0);
+#pragma unroll
+    for (int k4 = 0; k4 < 4; ++k4)
+      o[q4 >> 2][4 * (q4 & 3) + k4] = comb(o[q4 >> 2][4 * (q4 & 3) + k4], as_f32(v[k4]));
+  }
+  if (tid == 0) __hip_atomic_store(cnt + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // both tickets drawn: ready for the next launch
+#pragma unroll
+  for (int db = 0; db < 4; ++db) o_io[db] = o[db];
+  return true;
+}
+
+// Launch KERNEL with `lds` bytes of dynamic LDS, raising its LDS limit first, once per device: every kernel instantiation has its own
+// flag word (bit d = done on device d) in its instantiation of this template.  The caller checks the launch (TD_CHECK_LAUNCH).
+template <auto KERNEL, typename... Args>
+int attn_launch(const dim3 grid, const int threads, const int lds, hipStream_t stream, const int dev, Args... args) {
+  static std::atomic<unsigned long long> done{0};
+  if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
+    TD_CHECK_HIP(hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    done.fetch_or(1ull << (dev & 63), std::memory_order_release);
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), lds, stream, args...);
+  return 0;
+}
+
 }  // namespace

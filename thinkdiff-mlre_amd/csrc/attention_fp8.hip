@@ -40,6 +40,7 @@
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;   // one 8-bit MFMA operand: 32 bytes per lane
+template <auto K> using Kernel = std::integral_constant<decltype(K), K>;      // a kernel instantiation as a value a lambda can take
 
 constexpr int TILE8 = KV_TILE * D;     // 8 KiB per K8 or V8^T tile
 // Where a new reference point puts the row maximum: in (2^4, 2^5], i.e. 3.75 ... 4.75 octaves below the limit and 11 above the smallest byte.  The
@@ -281,18 +282,11 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_fp8_kernel(co
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int h5 = lane >> 5;
   const int l31 = lane & 31;
-  unsigned* const cnt = (unsigned*)ws + 16;
   TD_LDS unsigned* const ticket_lds = (TD_LDS unsigned*)(smem + 2 * NSLOT * TILE8);
 
   const int G = gridDim.x;
-  int r = blockIdx.x;
-  if constexpr (XCD_REMAP) {
-    const int q8 = G >> 3, r8 = G & 7, xcd = r & 7;
-    r = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (r >> 3);
-  }
-  const long long total = (long long)n_qblk * p.Hq * nt;
-  long long it = total * r / G;
-  const long long it_end = total * (r + 1) / G;
+  long long it, it_end;
+  const int r = attn_sk_range<XCD_REMAP>((long long)n_qblk * p.Hq * nt, it, it_end);
   const int Skv = p.Skv, H = p.Hq;
 
   // ---- resident per-lane LDS byte addresses of slot 0 (slot, k-block and d-block parts are instruction immediates) ----
@@ -567,56 +561,8 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_fp8_kernel(co
     if (p.ref_out && h5 == 0 && q0 + l31 < p.Sq && smax_run > -INFINITY)      // this part's share of the row's largest score, as the next step's starting reference
       __hip_atomic_fetch_max(p.ref_out + (size_t)head * p.Sq + q0 + l31, (int)__builtin_ceilf(smax_run) - (int)REF_HEADROOM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     float l_run = lacc[0];
-    // ---- hand-off of a split item: attention_bf16.hip's protocol, unchanged (state = O, reference, row sum) -----------------
-    if (kb > 0 || ke < nt) {
-      const int j = kb > 0 ? r : r + 1;
-      const bool tail = kb > 0;
-      const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)(ws + SK_HEADER_BYTES), 0, (unsigned)(2 * G) * SK_SLOT_FLOATS * 4u, 0x00020000);
-      const unsigned lane_off = ((unsigned)wid * 17u * 64u + (unsigned)lane) * 16u;
-      const unsigned mine = (unsigned)(tail ? j : G + j) * (SK_SLOT_FLOATS * 4u) + lane_off;
-      const unsigned theirs = (unsigned)(tail ? G + j : j) * (SK_SLOT_FLOATS * 4u) + lane_off;
-      auto ask = [&](bool draw) -> unsigned {
-        __syncthreads();
-        if (tid == 0)
-          *ticket_lds = draw ? __hip_atomic_fetch_add(cnt + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                             : __hip_atomic_load(cnt + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        return *ticket_lds;
-      };
-      bool other_ready = !tail && ask(false) == 1u;
-      if (!other_ready) {
-#pragma unroll
-        for (int q4 = 0; q4 < 16; ++q4) {
-          const u32x4_t v = {as_u32(o[q4 >> 2][4 * (q4 & 3)]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 1]),
-                             as_u32(o[q4 >> 2][4 * (q4 & 3) + 2]), as_u32(o[q4 >> 2][4 * (q4 & 3) + 3])};
-          __builtin_amdgcn_raw_buffer_store_b128(v, rsS, mine + q4 * 1024u, 0, 16);       // aux 16 = sc1
-        }
-        const u32x4_t ml = {as_u32(m_run), as_u32(l_run), 0u, 0u};
-        __builtin_amdgcn_raw_buffer_store_b128(ml, rsS, mine + 16 * 1024u, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        other_ready = ask(true) == 1u;
-        if (!other_ready) continue;
-      }
-      if (tid == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      const u32x4_t ml = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + 16 * 1024u, 0, 0);
-      const float m2 = as_f32(ml[0]), l2 = as_f32(ml[1]);
-      const float mm = fmaxf(m_run, m2);
-      const float a1 = __builtin_amdgcn_exp2f(m_run - mm), a2 = __builtin_amdgcn_exp2f(m2 - mm);
-      auto comb = [&](float own, float other) {
-        return tail ? __builtin_fmaf(other, a2, own * a1) : __builtin_fmaf(own, a1, other * a2);
-      };
-      l_run = comb(l_run, l2);
-#pragma unroll
-      for (int q4 = 0; q4 < 16; ++q4) {
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rsS, theirs + q4 * 1024u, 0, 0);
-#pragma unroll
-        for (int k4 = 0; k4 < 4; ++k4)
-          o[q4 >> 2][4 * (q4 & 3) + k4] = comb(o[q4 >> 2][4 * (q4 & 3) + k4], as_f32(v[k4]));
-      }
-      if (tid == 0) __hip_atomic_store(cnt + j, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // ---- hand-off of a split item: the bf16 kernel's protocol (state = O, reference, row sum; references in log2 units: cc = 1) ----
+    if ((kb > 0 || ke < nt) && !attn_sk_handoff(o, m_run, l_run, 1.0f, r, G, kb > 0, ws, ticket_lds, tid, wid)) continue;
 
     const float inv = 1.0f / l_run;
     const int q = q0 + l31;
@@ -666,27 +612,23 @@ int td_attn_fp8_launch(const TdAttnParams& p, hipStream_t stream) {
   TD_CHECK_LAUNCH();
   const int G = min(cus * (8 / NW), n_items);       // a range is never shorter than an item: every item is split over at most two workgroups
   constexpr int lds = 8 * TILE8 + 16;
-  static std::atomic<unsigned long long> done[4] = {};
-  auto go = [&](auto kernel, std::atomic<unsigned long long>& once, int threads) -> int {
-    if (int e = td_attn_set_lds_attr((const void*)kernel, lds, once, dev)) return e;
-    hipLaunchKernelGGL(kernel, dim3(G), dim3(threads), lds, stream, p, (const char*)p.f8_ws, lay, ws, n_qblk, nt);
-    return 0;
+  auto go = [&](auto kernel, int threads) -> int {      // kernel: a Kernel<> tag that names the instantiation
+    return attn_launch<decltype(kernel)::value>(dim3(G), threads, lds, stream, dev, p, (const char*)p.f8_ws, lay, ws, n_qblk, nt);
   };
   int rc;
 #ifdef TD_ATTN8_PROBE
-  static std::atomic<unsigned long long> pdone[7] = {};
   switch ((p.variant >> 16) & 7) {
-    case 1: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 1>, pdone[1], 512);
-    case 2: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 2>, pdone[2], 512);
-    case 3: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 3>, pdone[3], 512);
-    case 4: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 4>, pdone[4], 512);
-    case 5: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 5>, pdone[5], 512);
-    case 6: return go(td_attn_fwd_d128_fp8_kernel<8, true, true, 6>, pdone[6], 512);
+    case 1: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 1>>{}, 512);
+    case 2: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 2>>{}, 512);
+    case 3: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 3>>{}, 512);
+    case 4: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 4>>{}, 512);
+    case 5: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 5>>{}, 512);
+    case 6: return go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true, 6>>{}, 512);
     default: break;
   }
 #endif
-  if (NW == 8) rc = lin ? go(td_attn_fwd_d128_fp8_kernel<8, true, true>, done[0], 512) : go(td_attn_fwd_d128_fp8_kernel<8, true, false>, done[1], 512);
-  else rc = lin ? go(td_attn_fwd_d128_fp8_kernel<4, true, true>, done[2], 256) : go(td_attn_fwd_d128_fp8_kernel<4, true, false>, done[3], 256);
+  if (NW == 8) rc = lin ? go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, true>>{}, 512) : go(Kernel<td_attn_fwd_d128_fp8_kernel<8, true, false>>{}, 512);
+  else rc = lin ? go(Kernel<td_attn_fwd_d128_fp8_kernel<4, true, true>>{}, 256) : go(Kernel<td_attn_fwd_d128_fp8_kernel<4, true, false>>{}, 256);
   if (rc) return rc;
   TD_CHECK_LAUNCH();
   return 0;
