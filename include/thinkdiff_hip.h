@@ -987,8 +987,34 @@ int td_linear_split_w8_bf16(const void* x, int64_t ldx, const void* wq, const fl
 int td_linear_glu_bf16(const void* x, int64_t ldx, const void* w, void* y, int64_t ldy, int M, int I, int K, void* stream);
 int td_linear_glu_w8_bf16(const void* x, int64_t ldx, const void* wq, const float* w_scale, void* y, int64_t ldy, int M, int I, int K, void* stream);
 
-enum { TD_QWEN2_WEIGHTS_BF16 = 0, TD_QWEN2_WEIGHTS_E4M3 = 1 };
-/* Called after the parameters are loaded.  mode = TD_QWEN2_WEIGHTS_E4M3 (anything else: TD_ERR_INVALID): builds the 8-bit copy and the row scales of every
+/* ---- 4-bit weight stream (td_abi_version() >= 20; vLLM's `quantization="mxfp4"`): the same weight-only scheme one format down ------------------------
+ * Format (fixed): OCP MXFP4 -- e2m1 elements under ONE e8m0 POWER-OF-TWO scale per block of 32 consecutive k of an output row of W[N, K], K % 32 == 0:
+ *   amax = max |w| over the block;  e = floor(log2(amax)) - 2 (OCP MX v1.0), clamped to [-64, 64] (0 for an all-zero block);
+ *   q = e2m1_rne(w 2^-e): round to nearest, ties to the even code, saturated at +-6 (scaled values in (6, 8) clip to 6); the grid is
+ *   {0, 0.5, 1, 1.5, 2, 3, 4, 6} with a sign bit, and -0 keeps it;  W^ = q 2^e.
+ * Storage: packed uint8 [N, K / 2], element 2j in the LOW nibble of byte j (OCP, torch's float4_e2m1fn_x2, what Quark / torchao write); scales uint8
+ * [N, K / 32] = e + 127.  W^ is a bf16 value exactly (2 significant bits), so again the quantised model is an ordinary bf16 model with weights W^, and the
+ * stream kernels rebuild those bf16 values inside the conversion instruction: only the order of the fp32 sum may differ from the bf16 kernels on W^. */
+/* w bf16 [N, ldw] -> packed [N, K / 2], scales [N, K / 32] (both dense), and w_hat bf16 [N, ldw] = W^ (NULL: not written; may alias w).
+ * K % 32 == 0, ldw % 8 == 0, ldw >= K; w / w_hat / packed 16-byte aligned.  TD_ERR_INVALID before any HIP call otherwise. */
+int td_quant_weight_rows_mxfp4(const void* w, int64_t ldw, void* packed, void* scales, void* w_hat, int N, int K, void* stream);
+/* packed, scales -> w_hat bf16 [N, ldw] = W^, exactly (any scale byte in [1, 254] whose W^ stays inside bf16: a checkpoint written under another scale
+ * rule dequantises to its own values).  The same argument rules. */
+int td_dequant_rows_mxfp4(const void* packed, const void* scales, void* w_hat, int64_t ldw, int N, int K, void* stream);
+/* td_linear_w8_bf16 / td_linear_split_w8_bf16 / td_linear_glu_w8_bf16 with W^ given as (packed, scales) in the format above: the same arguments, epilogues
+ * and rounding points.  M <= 64 ONLY.  N % 4 == 0 and K % 32 == 0; more than 16 rows (and 3 .. 16 rows on the matrix core) need K % 256 == 0 (a 128-byte
+ * line of a packed row), N % 16 == 0, ldy % 4 == 0.  x and packed 16-byte aligned, scales 8-byte, ldx % 8 == 0.  M > 64, a NULL x / packed / scales / y,
+ * misaligned operands or a K the kernels do not take: TD_ERR_INVALID with a message, before any HIP call. */
+int td_linear_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream);
+int td_linear_split_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* bias, void* y0, int64_t ldy0, int act0,
+                            void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream);
+int td_linear_glu_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, void* y, int64_t ldy, int M, int I, int K, void* stream);
+
+enum { TD_QWEN2_WEIGHTS_BF16 = 0, TD_QWEN2_WEIGHTS_E4M3 = 1, TD_QWEN2_WEIGHTS_MXFP4 = 2 };
+/* Called after the parameters are loaded.  mode = TD_QWEN2_WEIGHTS_E4M3 or TD_QWEN2_WEIGHTS_MXFP4 (anything else: TD_ERR_INVALID; below, "8-bit copy" reads
+ * "4-bit copy": packed nibbles + block scale bytes, 0.27x the Linear weights instead of half).  A handle quantised in one mode REFUSES the other
+ * (TD_ERR_INVALID naming both) until its parameters are loaded again: the original weights are gone.  Builds the 8-bit copy and the row scales of every
  * layer's q|k|v, o, gate|up and down weights and of lm_head (4 x layers + 1 Linears) and OVERWRITES the bf16 weights with W^; with tied embeddings the
  * embedding table IS the lm_head weight and becomes W^ too.  From then on the weight stream is on: every Linear launch of up to 64 rows that the
  * weight-stream kernels take (the decode step of 1 .. 64 sequences, lm_head, prefills of up to 64 rows) reads the 8-bit copy; launches of more rows
@@ -1006,8 +1032,8 @@ int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream);
  * sequences reads bf16 W^ even with the stream on (measured slower on the bytes, on the 2B shape only).  Drops the captured decode graphs.
  * Returns the previous setting (0 / 1); TD_ERR_INVALID on a NULL or unquantised handle. */
 int td_qwen2_set_weight_stream(td_qwen2* f, int on);
-/* mode (TD_QWEN2_WEIGHTS_*), whether the stream is on, bytes of the 8-bit copy (weight bytes + row scales), number of quantised Linears; any output
- * may be NULL */
+/* mode (TD_QWEN2_WEIGHTS_*), whether the stream is on, bytes of the 8-bit copy (weight bytes + row scales; MXFP4: N K / 2 + N K / 32 per Linear), number
+ * of quantised Linears; any output may be NULL */
 int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* bytes_8bit, int* n_linears);
 /* How many Linear launches the handle has enqueued so far that read the 8-bit copy (a captured decode step counts once, when it is captured;
  * its replays launch nothing from the host and do not count).  The test handle that tells "the 8-bit kernels ran" from "the bf16 kernels ran on

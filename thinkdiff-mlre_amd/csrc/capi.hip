@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 19; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 20; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -41,6 +41,8 @@ int td_abi_version(void) { return 19; }  // 2: TdFluxConfig::out_channels append
                                             // 18: beam search (td_beam_select; csrc/beam_search.hip) and the KV gather behind it (td_kv_gather_rows,
                                             //     td_qwen2_gather_slots; csrc/kv_fork.hip)
                                             // 19: td_gemm_plan_query (host-only: the tile an automatic GEMM launch takes, alone or on a shared chip)
+                                            // 20: MXFP4 weight stream (td_quant_weight_rows_mxfp4, td_dequant_rows_mxfp4, td_linear*_w4_bf16,
+                                            //     TD_QWEN2_WEIGHTS_MXFP4)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -672,6 +674,54 @@ int td_linear_glu_w8_bf16(const void* x, int64_t ldx, const void* wq, const floa
   if (int rc = w8_linear_check("td_linear_glu_w8_bf16", x, ldx, wq, w_scale, y, ldy, M, I, K)) return rc;
   TdGemmParams p;
   p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W8 = (const uint8_t*)wq; p.w8_scale = w_scale; p.C = (bf16_t*)y; p.ldc = (int)ldy; p.M = M; p.N = I; p.K = K; p.glu_I = I;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+// ---- 4-bit weight stream (td_abi_version() >= 20): as above, every refusal comes before the first HIP call
+int td_quant_weight_rows_mxfp4(const void* w, int64_t ldw, void* packed, void* scales, void* w_hat, int N, int K, void* stream) {
+  return td_quant_weight_rows_mxfp4_launch((const bf16_t*)w, (long long)ldw, (uint8_t*)packed, (uint8_t*)scales, (bf16_t*)w_hat, N, K, (hipStream_t)stream);
+}
+
+int td_dequant_rows_mxfp4(const void* packed, const void* scales, void* w_hat, int64_t ldw, int N, int K, void* stream) {
+  return td_dequant_rows_mxfp4_launch((const uint8_t*)packed, (const uint8_t*)scales, (bf16_t*)w_hat, (long long)ldw, N, K, (hipStream_t)stream);
+}
+
+namespace {
+int w4_linear_check(const char* me, const void* x, int64_t ldx, const void* packed, const void* scales, const void* y, int64_t ldy, int M, int N, int K) {
+  TD_CHECK_ARG(x && packed && scales && y, "%s: x, the packed 4-bit weights, their block scales and the output are required", me);
+  TD_CHECK_ARG(M >= 1 && M <= 64, "%s: M=%d: the 4-bit weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", me, M);
+  TD_CHECK_ARG(N > 0 && K > 0 && ld32(ldx) && ld32(ldy), "%s: N=%d, K=%d, ldx=%lld, ldy=%lld", me, N, K, (long long)ldx, (long long)ldy);
+  return 0;
+}
+}  // namespace
+
+int td_linear_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream) {
+  if (int rc = w4_linear_check("td_linear_w4_bf16", x, ldx, packed, scales, y, ldy, M, N, K)) return rc;
+  TD_CHECK_ARG(ld32(ldr) && (!res || ldr >= N), "td_linear_w4_bf16: ldr=%lld must cover the N=%d columns of the residual", (long long)ldr, N);
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W4 = (const uint8_t*)packed; p.w4_scale = (const uint8_t*)scales; p.bias = (const bf16_t*)bias;
+  p.C = (bf16_t*)y; p.ldc = (int)ldy; p.gate = (const bf16_t*)gate; p.res = (const bf16_t*)res; p.ldr = (int)ldr;
+  p.M = M; p.N = N; p.K = K; p.act = act;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_split_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* bias, void* y0, int64_t ldy0, int act0,
+                            void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream) {
+  if (int rc = w4_linear_check("td_linear_split_w4_bf16", x, ldx, packed, scales, y0, ldy0, M, N, K)) return rc;
+  TD_CHECK_ARG(y1 && ld32(ldy1), "td_linear_split_w4_bf16: the second output y1 is required");
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W4 = (const uint8_t*)packed; p.w4_scale = (const uint8_t*)scales; p.bias = (const bf16_t*)bias;
+  p.C = (bf16_t*)y0; p.ldc = (int)ldy0; p.act = act0; p.C2 = (bf16_t*)y1; p.ldc2 = (int)ldy1; p.act2 = act1; p.n_split = n_split;
+  p.M = M; p.N = N; p.K = K;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_glu_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, void* y, int64_t ldy, int M, int I, int K, void* stream) {
+  if (int rc = w4_linear_check("td_linear_glu_w4_bf16", x, ldx, packed, scales, y, ldy, M, I, K)) return rc;
+  TdGemmParams p;
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W4 = (const uint8_t*)packed; p.w4_scale = (const uint8_t*)scales; p.C = (bf16_t*)y; p.ldc = (int)ldy;
+  p.M = M; p.N = I; p.K = K; p.glu_I = I;
   return td_gemv_launch(p, (hipStream_t)stream);
 }
 

@@ -1127,8 +1127,8 @@ int td_gemm_plan(int M, int N, int K, int shared, int operand) {
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "td_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemm: unknown activation code act=%d act2=%d (0 .. 4: TD_ACT_NONE .. TD_ACT_QUICK_GELU)", p.act, p.act2);
-  if (p.W8) {      // 8-bit weight stream: skinny-M kernels only, with checks of their own (a chunk is 16 weights)
-    TD_CHECK_ARG(p.g_M == 0 && !p.fp8 && !p.i8 && !p.out_f32 && p.conv_H == 0 && p.split_k == 0 && !p.q8, "td_gemm: 8-bit weights (W8) exist for the plain skinny-M Linear only");
+  if (p.W8 || p.W4) {      // 8-bit / 4-bit weight stream: skinny-M kernels only, with checks of their own (a chunk is 16 / 32 weights)
+    TD_CHECK_ARG(p.g_M == 0 && !p.fp8 && !p.i8 && !p.out_f32 && p.conv_H == 0 && p.split_k == 0 && !p.q8, "td_gemm: 8-bit and 4-bit weights (W8, W4) exist for the plain skinny-M Linear only");
     return td_gemv_launch(p, stream);
   }
   const int esz = (p.fp8 || p.i8) ? 1 : 2;

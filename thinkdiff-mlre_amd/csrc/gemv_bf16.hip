@@ -5,7 +5,8 @@
 //   * a workgroup (4 waves) owns 4 consecutive output columns = 4 weight rows; its 256 threads stride the rows' 16-byte
 //     chunks, so every wave-level load is a fully coalesced 1 KiB line run; loads are non-temporal (weights are read once);
 //   * two chunk-columns are in flight per thread (8 weight loads + the matching x chunks, which hit L2);
-//   * bf16 pairs go straight into v_dot2c_f32_bf16 (fp32 accumulate, no unpacking);
+//   * bf16 pairs go straight into v_dot2c_f32_bf16 (fp32 accumulate, no unpacking); the W8 / W4 forms stream e4m3 bytes / MXFP4 nibbles and convert them
+//     to those pairs in one instruction per pair (csrc/e4m3_pow2.h, csrc/mxfp4_pow2.h);
 //   * wave shuffle + LDS cross-wave reduction, then the same epilogue semantics and bf16 rounding points as the tile kernel
 //     (bias, activation, gate, residual, split output).
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include "td_common.h"
 #include "td_kernels.h"
 #include "e4m3_pow2.h"
+#include "mxfp4_pow2.h"
 
 namespace {
 
@@ -39,21 +41,34 @@ __device__ __forceinline__ void cvt16(const u32x4_t& w, float scale, u32x4_t& lo
 constexpr int R = 4;          // weight rows (output columns) per workgroup
 constexpr int THREADS = 256;
 
+// what the weight rows of a stream kernel hold (the WF template parameter): bf16 values, e4m3 bytes under a row scale (TdGemmParams::W8), or MXFP4
+// nibbles under a scale byte per 32 weights (TdGemmParams::W4)
+constexpr int WF_BF16 = 0, WF_W8 = 1, WF_W4 = 2;
+
 // W8: the weight rows are e4m3 bytes (p.W8, p.w8_scale); a 16-byte chunk then holds 16 weights and meets two chunks of x.  Everything behind the
 // accumulators is shared with the bf16 form.
-template <int MR, bool W8 = false>
+// W4: the weight rows are MXFP4 nibbles (p.W4, p.w4_scale; the format of csrc/mxfp4_pow2.h); a 16-byte chunk is then exactly one MX block: 32 weights
+// under one scale byte, which the thread loads beside the chunk, and meets four chunks of x.  The chunk is converted a dword (8 weights) at a time.
+template <int MR, int WF = WF_BF16>
 __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParams p) {
+  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4;
   __shared__ float red[THREADS / 64][R][MR];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int n0 = blockIdx.x * R;
-  const int nchunk = W8 ? p.K >> 4 : p.K >> 3;
+  const int nchunk = W4 ? p.K >> 5 : W8 ? p.K >> 4 : p.K >> 3;
   const u32x4_t* wp[R];
+  const uint8_t* sp[R];      // W4: the row's scale bytes, one per chunk
   float wsc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     // gated mode: rows 0,1 = gate rows 2b, 2b+1; rows 2,3 = the matching up rows (glu_I further down the matrix)
     const int row = p.glu_I ? (blockIdx.x * 2 + (r & 1) + (r >> 1) * p.glu_I) : min(n0 + r, p.N - 1);
-    if constexpr (W8) {
+    sp[r] = nullptr;
+    if constexpr (W4) {
+      wp[r] = (const u32x4_t*)(p.W4 + (size_t)row * (p.K >> 1));
+      sp[r] = p.w4_scale + (size_t)row * (p.K >> 5);
+      wsc[r] = 1.f;
+    } else if constexpr (W8) {
       wp[r] = (const u32x4_t*)(p.W8 + (size_t)row * p.K);
       wsc[r] = p.w8_scale[row];
     } else {
@@ -71,6 +86,22 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
 #pragma unroll
     for (int m = 0; m < MR; ++m) acc[r][m] = 0.f;
 
+  // W4: one chunk (= one block) of the R rows, at chunk index cc, against its four chunks of x
+  auto eat4 = [&](const u32x4_t (&w)[R], const unsigned (&sb)[R], int cc) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      u32x4_t a[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) a[r] = mx4_to_bf16(w[r][i], mx4_scale_f32(sb[r]));
+#pragma unroll
+      for (int m = 0; m < MR; ++m) {
+        const u32x4_t x = xp[m][4 * cc + i];
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r][m] = dot8(a[r], x, acc[r][m]);
+      }
+    }
+  };
+
   int c = tid;
   for (; c + THREADS < nchunk; c += 2 * THREADS) {
     u32x4_t w0[R], w1[R];
@@ -79,7 +110,13 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
       w0[r] = __builtin_nontemporal_load(wp[r] + c);
       w1[r] = __builtin_nontemporal_load(wp[r] + c + THREADS);
     }
-    if constexpr (W8) {
+    if constexpr (W4) {
+      unsigned s0[R], s1[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) { s0[r] = sp[r][c]; s1[r] = sp[r][c + THREADS]; }
+      eat4(w0, s0, c);
+      eat4(w1, s1, c + THREADS);
+    } else if constexpr (W8) {
       u32x4_t a0[R], b0[R], a1[R], b1[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) { cvt16(w0[r], wsc[r], a0[r], b0[r]); cvt16(w1[r], wsc[r], a1[r], b1[r]); }
@@ -102,7 +139,12 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
     u32x4_t w0[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) w0[r] = __builtin_nontemporal_load(wp[r] + c);
-    if constexpr (W8) {
+    if constexpr (W4) {
+      unsigned s0[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) s0[r] = sp[r][c];
+      eat4(w0, s0, c);
+    } else if constexpr (W8) {
       u32x4_t a0[R], b0[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) cvt16(w0[r], wsc[r], a0[r], b0[r]);
@@ -188,8 +230,13 @@ template <int MB, int NR> constexpr int gemv_lds_bytes() { return MW * (2 * NR +
 // in turn.  The weight lines go through the slab AS BYTES (same writes, same XOR placement of the 16-byte chunks); a lane reads the 8 bytes of its operand
 // fragment back (ds_read_b64) and converts them with its row's scale (e4m3p2_to_bf16) into the very bf16 fragment the bf16
 // form would have read.  Accumulators, reduction, split-K hand-off and epilogue are shared.
-template <int MB, int NR, bool DEEP, bool W8 = false>
+// W4 (TdGemmParams::W4): the weight rows are MXFP4 nibbles.  A 128-byte line of a row is 256 weights = 8 MX blocks, so a step covers 256 elements of K: the
+// same two weight loads per block, four times the activation loads, four 64-element quarters in turn.  A lane's 8-element operand fragment is 4 bytes
+// (ds_read_b32) inside ONE 16-byte chunk = one block, so one scale per fragment: the 8 scale bytes of the lane's row and step arrive in one 8-byte load
+// in operand layout (lane = row r) beside the weight lines, and mx4_to_bf16 rebuilds the bf16 fragment.
+template <int MB, int NR, bool DEEP, int WF = WF_BF16>
 __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParams p, char* ws) {
+  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int XB = gemv_xb<MB>();
   constexpr int SLAB = (2 * NR + 2 * XB) * 1024;
@@ -210,14 +257,18 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   // LDS pass (a workgroup streams only 16 rows x K, its lifetime is a handful of memory round trips); otherwise hipcc threads
   // the loads between the steps at low register count, which keeps several workgroups per CU for short K.
   const unsigned w_rows = p.glu_I ? 2u * (unsigned)p.glu_I : (unsigned)p.N;
-  const __amdgpu_buffer_rsrc_t rsW = W8 ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W8, 0, (unsigned)((size_t)w_rows * p.K), 0x00020000)
-                                        : __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (unsigned)((size_t)w_rows * p.K * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = W4   ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W4, 0, (unsigned)((size_t)w_rows * (p.K >> 1)), 0x00020000)
+                                     : W8 ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W8, 0, (unsigned)((size_t)w_rows * p.K), 0x00020000)
+                                          : __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (unsigned)((size_t)w_rows * p.K * 2), 0x00020000);
+  // W4: the scale bytes [w_rows, K / 32]; a lane reads the 8 of its operand row and step (K % 256 == 0: 8-byte aligned)
+  const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scale, 0, W4 ? (unsigned)((size_t)w_rows * (p.K >> 5)) : 0u, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (unsigned)((((size_t)p.M - 1) * p.lda + p.K) * 2), 0x00020000);
   constexpr unsigned OOB = 0xFFFFFF00u;
   const int lrow = lane >> 3;                                  // row of the 8-row half this lane fetches
   const int lchunk = (lane & 7) ^ (lrow & 7);                  // ... and which 16-byte chunk of the row's 128-byte line
   unsigned woff[NR][2], xoff[MB][2];
   float wsc[NR];                                               // W8: scale of the weight row this lane holds in operand layout (row r of the block)
+  unsigned soff[NR];                                           // W4: where that row's scale bytes begin
 #pragma unroll
   for (int nr = 0; nr < NR; ++nr) {
     const int bid = min((int)blockIdx.x * NR + nr, nblk - 1);
@@ -225,10 +276,14 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
     for (int h = 0; h < 2; ++h) {
       // gated mode: rows 0-7 = gate rows 8b..8b+7, rows 8-15 = the matching up rows
       const int wr_ = p.glu_I ? (bid * 8 + lrow + h * p.glu_I) : bid * 16 + 8 * h + lrow;
-      woff[nr][h] = W8 ? (unsigned)((size_t)wr_ * p.K + 16 * lchunk) : (unsigned)(((size_t)wr_ * p.K + 8 * lchunk) * 2);
+      woff[nr][h] = W4   ? (unsigned)((size_t)wr_ * (p.K >> 1) + 16 * lchunk)
+                    : W8 ? (unsigned)((size_t)wr_ * p.K + 16 * lchunk)
+                         : (unsigned)(((size_t)wr_ * p.K + 8 * lchunk) * 2);
     }
-    if constexpr (W8) wsc[nr] = p.w8_scale[p.glu_I ? (bid * 8 + (r & 7) + (r >> 3) * p.glu_I) : bid * 16 + r];
+    const int orow = p.glu_I ? (bid * 8 + (r & 7) + (r >> 3) * p.glu_I) : bid * 16 + r;      // the weight row this lane holds in operand layout
+    if constexpr (W8) wsc[nr] = p.w8_scale[orow];
     else wsc[nr] = 1.f;
+    soff[nr] = W4 ? (unsigned)((size_t)orow * (p.K >> 5)) : 0u;
   }
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -247,8 +302,16 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
 #pragma unroll
       for (int h = 0; h < 2; ++h) rd8_ptr[j][h] = slab + r * 128 + (((4 * j + 2 * h + (g >> 1)) ^ (r & 7)) << 4) + 8 * (g & 1);
   }
-  constexpr int KH = W8 ? 2 : 1;                // 64-element halves of a step
-  const int nk_all = W8 ? p.K >> 7 : p.K >> 6;  // steps (64 elements; W8: 128)
+  // W4: the 4 fragment bytes of (quarter j of the step, h): k = 64 j + 32 h + 8 g .. + 7 = chunk (= block) 2 j + h of the row's line, its bytes 4 g .. 4 g + 3
+  const char* rd4_ptr[4][2];
+  if constexpr (W4) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) rd4_ptr[j][h] = slab + r * 128 + (((2 * j + h) ^ (r & 7)) << 4) + 4 * g;
+  }
+  constexpr int KH = W4 ? 4 : W8 ? 2 : 1;       // 64-element parts of a step
+  const int nk_all = W4 ? p.K >> 8 : W8 ? p.K >> 7 : p.K >> 6;  // steps (64 elements; W8: 128; W4: 256)
   const int s_beg = (int)((long long)nk_all * ky / KS), nk = (int)((long long)nk_all * (ky + 1) / KS);   // this workgroup's steps
   f32x4_t acc[NR][MB];
 #pragma unroll
@@ -258,6 +321,7 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   constexpr int SF = DEEP ? (32 / (2 * NR + 2 * KH * MB) > 0 ? 32 / (2 * NR + 2 * KH * MB) : 1) : (MB * NR == 1 ? 2 : 1);    // k-steps per wave and iteration
   for (int s = s_beg + wid; s < nk; s += SF * MW) {
     u32x4_t w[SF][NR][2], x[SF][KH][MB][2];
+    u32x2_t sc4[SF][NR];      // W4: the step's 8 scale bytes of the lane's operand row
 #pragma unroll
     for (int f = 0; f < SF; ++f) {
       const int st = s + f * MW;
@@ -267,6 +331,10 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
       for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
         for (int h = 0; h < 2; ++h) w[f][nr][h] = __builtin_amdgcn_raw_buffer_load_b128(rsW, ok ? woff[nr][h] + k0 : OOB, 0, 0);
+      if constexpr (W4) {
+#pragma unroll
+        for (int nr = 0; nr < NR; ++nr) sc4[f][nr] = __builtin_amdgcn_raw_buffer_load_b64(rsS, ok ? soff[nr] + (unsigned)st * 8u : OOB, 0, 0);
+      }
 #pragma unroll
       for (int j = 0; j < KH; ++j)
 #pragma unroll
@@ -298,7 +366,10 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
           if (m0 == 0) {
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
-              if constexpr (W8) {
+              if constexpr (W4) {
+                const unsigned sb = (sc4[f][nr][(2 * kh + h) >> 2] >> (8 * ((2 * kh + h) & 3))) & 0xffu;      // block 2 kh + h of the line
+                wf[nr][h] = __builtin_bit_cast(bf16x8_t, mx4_to_bf16(*(const unsigned*)(rd4_ptr[kh][h] + nr * 2048), mx4_scale_f32(sb)));
+              } else if constexpr (W8) {
                 wf[nr][h] = __builtin_bit_cast(bf16x8_t, e4m3p2_to_bf16(*(const u32x2_t*)(rd8_ptr[kh][h] + nr * 2048), wsc[nr]));
               } else {
                 wf[nr][h] = *(const bf16x8_t*)(rd_ptr[h] + nr * 2048);
@@ -422,7 +493,12 @@ int splitk_workspace(hipStream_t stream, char** out) {
   return 0;
 }
 
-template <int MB, int NR, bool DEEP, bool W8>
+// The weight forms of the stream kernels, as far as the host's shape rules go
+struct WeightForm { int chunk, step, bits; };      // weights per 16-byte chunk (dot form), per MFMA k-step, and bits per weight
+constexpr WeightForm FORM_BF16{8, 64, 16}, FORM_W8{16, 128, 8}, FORM_W4{32, 256, 4};
+template <int WF> constexpr WeightForm form_of() { return WF == WF_W4 ? FORM_W4 : WF == WF_W8 ? FORM_W8 : FORM_BF16; }
+
+template <int MB, int NR, bool DEEP, int WF>
 int launch_one(const TdGemmParams& p, dim3 grid, char* ws, hipStream_t stream) {
   constexpr int lds = gemv_lds_bytes<MB, NR>();
   if (lds + 64 >= 64 * 1024) {  // dynamic + the static ticket word reach the default 64 KiB limit: raise it once per device
@@ -430,22 +506,22 @@ int launch_one(const TdGemmParams& p, dim3 grid, char* ws, hipStream_t stream) {
     int dev = 0;
     TD_CHECK_HIP(hipGetDevice(&dev));
     if (!((done.load(std::memory_order_acquire) >> (dev & 63)) & 1ull)) {
-      TD_CHECK_HIP(hipFuncSetAttribute((const void*)td_gemv_mfma_kernel<MB, NR, DEEP, W8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+      TD_CHECK_HIP(hipFuncSetAttribute((const void*)td_gemv_mfma_kernel<MB, NR, DEEP, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       done.fetch_or(1ull << (dev & 63), std::memory_order_release);
     }
   }
-  hipLaunchKernelGGL((td_gemv_mfma_kernel<MB, NR, DEEP, W8>), grid, dim3(MW * 64), lds, stream, p, ws);
+  hipLaunchKernelGGL((td_gemv_mfma_kernel<MB, NR, DEEP, WF>), grid, dim3(MW * 64), lds, stream, p, ws);
   return 0;
 }
 
-template <int MB, bool W8>
+template <int MB, int WF>
 int launch_mfma(const TdGemmParams& p, hipStream_t stream) {
   const int nblk = p.glu_I ? p.glu_I / 8 : p.N / 16;
-  const int steps = W8 ? p.K >> 7 : p.K >> 6;      // k-steps of the kernel (64 elements; W8: 128, one line of weight bytes)
+  const int steps = p.K / form_of<WF>().step;      // k-steps of the kernel (64 elements; W8: 128, W4: 256 -- one line of weight bytes)
   // two weight blocks per workgroup halve the x re-reads from L2; only where the grid still oversubscribes the chip
   if (MB > 1 && nblk >= 1024) {
     const dim3 grid((nblk + 1) / 2);
-    return steps >= 4 * MW ? launch_one<MB, 2, true, W8>(p, grid, nullptr, stream) : launch_one<MB, 2, false, W8>(p, grid, nullptr, stream);
+    return steps >= 4 * MW ? launch_one<MB, 2, true, WF>(p, grid, nullptr, stream) : launch_one<MB, 2, false, WF>(p, grid, nullptr, stream);
   }
   // few block columns: split K over workgroups too, as long as every wave of a workgroup keeps at least one step
   int ks = 1;
@@ -455,51 +531,51 @@ int launch_mfma(const TdGemmParams& p, hipStream_t stream) {
     if (int rc = splitk_workspace(stream, &ws)) return rc;
   }
   const dim3 grid(nblk, ks);
-  return steps / ks >= 4 * MW ? launch_one<MB, 1, true, W8>(p, grid, ws, stream) : launch_one<MB, 1, false, W8>(p, grid, ws, stream);
+  return steps / ks >= 4 * MW ? launch_one<MB, 1, true, WF>(p, grid, ws, stream) : launch_one<MB, 1, false, WF>(p, grid, ws, stream);
 }
 
-template <bool W8>
+template <int WF>
 int launch_mfma_rows(const TdGemmParams& p, hipStream_t stream) {
-  if (p.M <= 16) return launch_mfma<1, W8>(p, stream);
-  if (p.M <= 32) return launch_mfma<2, W8>(p, stream);
-  if (p.M <= 48) return launch_mfma<3, W8>(p, stream);
-  return launch_mfma<4, W8>(p, stream);
+  if (p.M <= 16) return launch_mfma<1, WF>(p, stream);
+  if (p.M <= 32) return launch_mfma<2, WF>(p, stream);
+  if (p.M <= 48) return launch_mfma<3, WF>(p, stream);
+  return launch_mfma<4, WF>(p, stream);
 }
 
 // the dot-product form's launch for M <= 16 rows
-template <bool W8>
+template <int WF>
 void launch_dot(const TdGemmParams& p, dim3 grid, hipStream_t stream) {
   const dim3 block(THREADS);
-  if (p.M == 1) hipLaunchKernelGGL((td_gemv_bf16_kernel<1, W8>), grid, block, 0, stream, p);
-  else if (p.M == 2) hipLaunchKernelGGL((td_gemv_bf16_kernel<2, W8>), grid, block, 0, stream, p);
-  else if (p.M <= 4) hipLaunchKernelGGL((td_gemv_bf16_kernel<4, W8>), grid, block, 0, stream, p);
-  else if (p.M <= 8) hipLaunchKernelGGL((td_gemv_bf16_kernel<8, W8>), grid, block, 0, stream, p);
-  else hipLaunchKernelGGL((td_gemv_bf16_kernel<16, W8>), grid, block, 0, stream, p);
+  if (p.M == 1) hipLaunchKernelGGL((td_gemv_bf16_kernel<1, WF>), grid, block, 0, stream, p);
+  else if (p.M == 2) hipLaunchKernelGGL((td_gemv_bf16_kernel<2, WF>), grid, block, 0, stream, p);
+  else if (p.M <= 4) hipLaunchKernelGGL((td_gemv_bf16_kernel<4, WF>), grid, block, 0, stream, p);
+  else if (p.M <= 8) hipLaunchKernelGGL((td_gemv_bf16_kernel<8, WF>), grid, block, 0, stream, p);
+  else hipLaunchKernelGGL((td_gemv_bf16_kernel<16, WF>), grid, block, 0, stream, p);
 }
-
-// The two weight forms of the stream kernels, as far as the host's shape rules go
-struct WeightForm { int chunk, step, bytes; };      // weights per 16-byte chunk (dot form), per MFMA k-step, and bytes per weight
-constexpr WeightForm FORM_BF16{8, 64, 2}, FORM_W8{16, 128, 1};
 
 // Shapes the matrix-core form takes.  Its operands sit behind 32-bit buffer descriptors, a k-step is whole, and the epilogue stores 4 columns (8 bytes) at
 // a time.  `gated_checked`: the caller has already put a gated problem (glu_I) through the gated argument check (N == glu_I, a multiple of 8, ldc % 4, lda % 8,
 // no split), which is all a gated launch needs -- its blocks are 8 gate + 8 up rows, so N % 16 is NOT asked.  td_gemv_mfma_ok asks it all the same.
 bool mfma_ok(const TdGemmParams& p, WeightForm f, bool gated_checked) {
   const long long w_rows = p.glu_I ? 2ll * p.glu_I : p.N;
-  if (w_rows * p.K * f.bytes >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
+  if (w_rows * p.K * f.bits / 8 >= 0xFFFFFF00ll || ((long long)(p.M - 1) * p.lda + p.K) * 2 >= 0xFFFFFF00ll) return false;
   if (p.K % f.step != 0) return false;
   if (p.glu_I && gated_checked) return true;
   return p.N % 16 == 0 && p.ldc % 4 == 0 && p.lda % 8 == 0 && (!p.C2 || (p.ldc2 % 4 == 0 && p.n_split % 4 == 0));
 }
 
-// The routing tail of both forms: more than 4 rows and a shape the matrix core takes -> MFMA form, else the dot form (the caller has refused more than
-// 16 rows without the MFMA form, in its own words)
-template <bool W8>
+// The routing tail of all forms: more than 4 rows and a shape the matrix core takes -> MFMA form, else the dot form (the caller has refused more than
+// 16 rows without the MFMA form, in its own words).  W4 draws the line at 2 rows: a 4-bit weight byte meets four times the bytes of x a bf16 weight byte
+// meets, every activation row reads them from L2 again, and at 3 .. 4 rows the dot form measured SLOWER than the bf16 kernels on W^ on the 2B decoder shape
+// (2.19 vs 2.01 ms per step of 4 sequences) and level with them on the 7B one (3.78 vs 3.80), while the matrix-core form at 8 sequences took 1.48 / 2.54 ms
+// (tools/bench_qwen2_w4.py)
+template <int WF>
 int route(const TdGemmParams& p, bool mfma, hipStream_t stream) {
-  if (p.M > 4 && mfma) {
-    if (int rc = launch_mfma_rows<W8>(p, stream)) return rc;
+  constexpr int DOT_ROWS = WF == WF_W4 ? 2 : 4;
+  if (p.M > DOT_ROWS && mfma) {
+    if (int rc = launch_mfma_rows<WF>(p, stream)) return rc;
   } else {
-    launch_dot<W8>(p, dim3(p.glu_I ? p.glu_I / 2 : p.N / R), stream);
+    launch_dot<WF>(p, dim3(p.glu_I ? p.glu_I / 2 : p.N / R), stream);
   }
   TD_CHECK_LAUNCH();
   return 0;
@@ -521,10 +597,36 @@ int gemv_w8_launch(const TdGemmParams& p, hipStream_t stream) {
   }
   const bool mfma = mfma_ok(p, FORM_W8, true);
   TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(w8): more than 16 rows need the matrix-core form (K=%d %% 128, N=%d %% 16, ldc %% 4 == 0, operands under 4 GiB)", p.K, p.N);
-  return route<true>(p, mfma, stream);
+  return route<WF_W8>(p, mfma, stream);
+}
+
+// td_gemv_launch for TdGemmParams::W4, with the same duties as the 8-bit one above: the C ABI's 4-bit entries come straight here
+int gemv_w4_launch(const TdGemmParams& p, hipStream_t stream) {
+  TD_CHECK_ARG(!p.W8, "td_gemv(w4): W8 and W4 are exclusive");
+  TD_CHECK_ARG(p.W4 && p.w4_scale && p.A && p.C, "td_gemv(w4): x, the packed 4-bit weights, their block scales and the output are required");
+  TD_CHECK_ARG(p.M >= 1 && p.M <= 64, "td_gemv(w4): M=%d: the 4-bit weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", p.M);
+  TD_CHECK_ARG(p.N > 0 && p.N % R == 0 && p.K > 0 && p.K % 32 == 0, "td_gemv(w4): N=%d must be a multiple of 4 and K=%d a multiple of 32 (one MX block = one 16-byte chunk of a packed row)", p.N, p.K);
+  TD_CHECK_ARG(p.lda >= p.K && p.lda % 8 == 0 && p.ldc >= (p.C2 ? p.n_split : p.N), "td_gemv(w4): bad leading dimensions lda=%d ldc=%d", p.lda, p.ldc);
+  TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W4) % 16 == 0 && (uintptr_t)p.w4_scale % 8 == 0 && (uintptr_t)p.C % 8 == 0 && (uintptr_t)p.C2 % 8 == 0,
+               "td_gemv(w4): misaligned operands: x and the packed weights must be 16-byte aligned, the outputs and the scale bytes 8-byte");
+  if (p.C2) TD_CHECK_ARG(p.n_split > 0 && p.n_split < p.N && p.n_split % 4 == 0 && p.ldc2 >= p.N - p.n_split, "td_gemv(w4): bad split-output arguments");
+  if (p.glu_I) {
+    TD_CHECK_ARG(p.N == p.glu_I && p.glu_I % 8 == 0 && !p.bias && !p.gate && !p.res && !p.C2 && p.act == TD_ACT_NONE && p.ldc % 4 == 0,
+                 "td_gemv(w4, glu): N must equal glu_I (multiple of 8), no bias / gate / residual / split");
+  }
+  const bool mfma = mfma_ok(p, FORM_W4, true);
+  TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(w4): more than 16 rows need the matrix-core form (K=%d %% 256, N=%d %% 16, ldc %% 4 == 0, operands under 4 GiB)", p.K, p.N);
+  return route<WF_W4>(p, mfma, stream);
 }
 
 }  // namespace
+
+// shapes the 4-bit weight stream takes (csrc/qwen2_engine.hip asks before it routes a Linear to its MXFP4 copy)
+bool td_gemv_w4_ok(const TdGemmParams& p) {
+  if (p.M < 1 || p.M > 64 || p.N % R != 0 || p.K % FORM_W4.chunk != 0 || p.lda % 8 != 0) return false;
+  if (p.glu_I && (p.N != p.glu_I || p.glu_I % 8 != 0 || p.ldc % 4 != 0)) return false;
+  return p.M <= 16 || mfma_ok(p, FORM_W4, true);
+}
 
 // shapes the 8-bit weight stream takes (csrc/qwen2_engine.hip asks before it routes a Linear to its e4m3 copy)
 bool td_gemv_w8_ok(const TdGemmParams& p) {
@@ -538,6 +640,7 @@ bool td_gemv_mfma_ok(const TdGemmParams& p) { return mfma_ok(p, FORM_BF16, false
 
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemv: unknown activation code act=%d act2=%d", p.act, p.act2);
+  if (p.W4) return gemv_w4_launch(p, stream);
   if (p.W8) return gemv_w8_launch(p, stream);
   TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % FORM_BF16.chunk == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");
   TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.W) % 16 == 0, "td_gemv: operands must be 16-byte aligned");
@@ -548,5 +651,5 @@ int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
   const bool mfma = mfma_ok(p, FORM_BF16, true);
   if (p.glu_I) TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(glu): more than 16 rows need K %% 64 == 0 and operands under 4 GiB");
   else TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv: more than 16 rows need the matrix-core form (K %% 64, N %% 16, ldc %% 4 == 0)");
-  return route<false>(p, mfma, stream);
+  return route<WF_BF16>(p, mfma, stream);
 }

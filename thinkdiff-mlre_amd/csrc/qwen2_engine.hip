@@ -34,8 +34,9 @@ namespace {
 
 struct QSlot { std::string name; bf16_t* ptr; int64_t count; };
 
-// the 8-bit copy of one Linear weight (td_qwen2_quantize_weights): e4m3 bytes [N, K] and the row scales 2^e_n; null on an unquantised handle
-struct W8Ref { uint8_t* q = nullptr; float* s = nullptr; };
+// the quantised copy of one Linear weight (td_qwen2_quantize_weights): e4m3 bytes [N, K] and the fp32 row scales 2^e_n, or -- TD_QWEN2_WEIGHTS_MXFP4 --
+// packed nibbles [N, K / 2] and the e8m0 block scale bytes [N, K / 32]; null on an unquantised handle
+struct W8Ref { uint8_t* q = nullptr; void* s = nullptr; };
 
 struct QLayer {
   W8Ref qkv_8, o_8, gu_8, down_8;
@@ -82,7 +83,7 @@ struct td_qwen2 {
   bf16_t* logits_buf = nullptr;                 // [MAX_BATCH, vocab]
   int* row_map = nullptr;                       // [ws_rows] packed prefill: cache row of every packed prompt row
   std::vector<int> row_map_host;                // ... its host image (kept alive across the asynchronous upload)
-  // 8-bit weight stream (td_qwen2_quantize_weights): the e4m3 copy of every Linear weight beside the bf16 arena, which then holds the dequantised values
+  // 8-bit / 4-bit weight stream (td_qwen2_quantize_weights): the e4m3 or MXFP4 copy (w_mode) of every Linear weight beside the bf16 arena, which then holds the dequantised values
   int w_mode = TD_QWEN2_WEIGHTS_BF16;
   bool w8_on = false;                           // launches of up to 64 rows read the 8-bit copy (td_qwen2_set_weight_stream)
   bool w8_stale = false;                        // parameters were loaded after quantising: every run is refused until td_qwen2_quantize_weights is called again
@@ -199,12 +200,17 @@ TdGemmParams linear(const bf16_t* x, int ldx, const bf16_t* W, const bf16_t* bia
 }
 
 // Launches a Linear of the decoder.  With the weight stream on, a launch of up to 64 rows that would reach the skinny-M kernels anyway (no tile override,
-// no K split) and has a shape their 8-bit forms take reads the e4m3 copy `w8` instead of the bf16 weight; everything else reads the bf16 arena, which
-// holds the same (dequantised) values -- the model does not depend on the route.
+// no K split) and has a shape their 8-bit (4-bit) forms take reads the quantised copy `w8` instead of the bf16 weight; everything else reads the bf16 arena,
+// which holds the same (dequantised) values -- the model does not depend on the route.
 int run_linear(td_qwen2* f, TdGemmParams g, const W8Ref& w8, hipStream_t s, bool allow8 = true) {
-  if (allow8 && f->w8_on && w8.q && g.M <= STREAM_ROWS_MAX && g.cfg < 0 && g.split_k == 0 && td_gemv_w8_ok(g)) {
-    g.W8 = w8.q; g.w8_scale = w8.s;
-    ++f->w8_launches;
+  if (allow8 && f->w8_on && w8.q && g.M <= STREAM_ROWS_MAX && g.cfg < 0 && g.split_k == 0) {
+    if (f->w_mode == TD_QWEN2_WEIGHTS_MXFP4 && td_gemv_w4_ok(g)) {
+      g.W4 = w8.q; g.w4_scale = (const uint8_t*)w8.s;
+      ++f->w8_launches;
+    } else if (f->w_mode == TD_QWEN2_WEIGHTS_E4M3 && td_gemv_w8_ok(g)) {
+      g.W8 = w8.q; g.w8_scale = (const float*)w8.s;
+      ++f->w8_launches;
+    }
   }
   return td_gemm_launch(g, s);
 }
@@ -507,7 +513,14 @@ int td_qwen2_read_kv(td_qwen2* f, int layer, int slot, int row0, int n, void* ou
 
 int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream) {
   TD_CHECK_ARG(f, "td_qwen2_quantize_weights: null handle");
-  TD_CHECK_ARG(mode == TD_QWEN2_WEIGHTS_E4M3, "td_qwen2_quantize_weights: unknown mode %d (TD_QWEN2_WEIGHTS_E4M3 = %d is the one served)", mode, TD_QWEN2_WEIGHTS_E4M3);
+  TD_CHECK_ARG(mode == TD_QWEN2_WEIGHTS_E4M3 || mode == TD_QWEN2_WEIGHTS_MXFP4,
+               "td_qwen2_quantize_weights: unknown mode %d (TD_QWEN2_WEIGHTS_E4M3 = %d and TD_QWEN2_WEIGHTS_MXFP4 = %d are the ones served)", mode, TD_QWEN2_WEIGHTS_E4M3,
+               TD_QWEN2_WEIGHTS_MXFP4);
+  const bool mx4 = mode == TD_QWEN2_WEIGHTS_MXFP4;
+  // the arena holds W^ of the mode it was quantised in, not the weights it was loaded with: another format would quantise the wrong model
+  TD_CHECK_ARG(f->w_mode == TD_QWEN2_WEIGHTS_BF16 || f->w_mode == mode || f->w8_stale,
+               "td_qwen2_quantize_weights: the handle was quantised as %s and its original weights are gone; load its parameters again before quantising as %s",
+               f->w_mode == TD_QWEN2_WEIGHTS_MXFP4 ? "TD_QWEN2_WEIGHTS_MXFP4" : "TD_QWEN2_WEIGHTS_E4M3", mx4 ? "TD_QWEN2_WEIGHTS_MXFP4" : "TD_QWEN2_WEIGHTS_E4M3");
   const int D = f->D, I = f->I, QW = f->Hq * 128, NQKV = (f->Hq + 2 * f->Hkv) * 128;
   struct Lin { bf16_t* w; W8Ref* ref; int N, K; };
   std::vector<Lin> lins;
@@ -518,28 +531,40 @@ int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream) {
     lins.push_back({l.down_w, &l.down_8, D, I});
   }
   lins.push_back({f->lm_w, &f->lm_8, f->cfg.vocab, D});      // (tied embeddings: this is the embedding table)
+  if (mx4)
+    for (const Lin& x : lins) TD_CHECK_ARG(x.K % 32 == 0, "td_qwen2_quantize_weights: TD_QWEN2_WEIGHTS_MXFP4 needs every Linear's K=%d to be a multiple of 32 (one MX block)", x.K);
+  if (f->w8_arena && f->w_mode != mode) {      // reloaded and quantised in the other format: its copy has other sizes
+    (void)hipFree(f->w8_arena);
+    f->w8_arena = nullptr;
+  }
+  // bytes of a Linear's weight piece and of its scale piece
+  auto wbytes = [&](const Lin& x) { return mx4 ? (int64_t)x.N * x.K / 2 : (int64_t)x.N * x.K; };
+  auto sbytes = [&](const Lin& x) { return mx4 ? (int64_t)x.N * x.K / 32 : (int64_t)x.N * 4; };
   if (!f->w8_arena) {
     int64_t total = 0;
-    for (const Lin& x : lins) total += (((int64_t)x.N * x.K + 255) & ~int64_t(255)) + (((int64_t)x.N * 4 + 255) & ~int64_t(255));
+    for (const Lin& x : lins) total += ((wbytes(x) + 255) & ~int64_t(255)) + ((sbytes(x) + 255) & ~int64_t(255));
     hipError_t e = hipMalloc((void**)&f->w8_arena, (size_t)total);
     if (e != hipSuccess) {
       f->w8_arena = nullptr;
-      td_set_error("td_qwen2_quantize_weights: hipMalloc of %.2f GiB for the 8-bit copy failed: %s", total / double(1 << 30), hipGetErrorString(e));
+      td_set_error("td_qwen2_quantize_weights: hipMalloc of %.2f GiB for the quantised copy failed: %s", total / double(1 << 30), hipGetErrorString(e));
       return TD_ERR_HIP;
     }
     int64_t o = 0;
     for (const Lin& x : lins) {
-      x.ref->q = (uint8_t*)(f->w8_arena + o); o += ((int64_t)x.N * x.K + 255) & ~int64_t(255);
-      x.ref->s = (float*)(f->w8_arena + o); o += ((int64_t)x.N * 4 + 255) & ~int64_t(255);
+      x.ref->q = (uint8_t*)(f->w8_arena + o); o += (wbytes(x) + 255) & ~int64_t(255);
+      x.ref->s = f->w8_arena + o; o += (sbytes(x) + 255) & ~int64_t(255);
     }
     f->w8_bytes = 0;
-    for (const Lin& x : lins) f->w8_bytes += (int64_t)x.N * x.K + (int64_t)x.N * 4;      // (reported without the padding between the pieces)
+    for (const Lin& x : lins) f->w8_bytes += wbytes(x) + sbytes(x);      // (reported without the padding between the pieces)
     f->w8_linears = (int)lins.size();
   }
   drop_step_graphs(f);      // the captured steps carry the bf16 launch list
   f->w8_stale = true;       // (a failing launch below must not leave a half-quantised handle runnable)
   f->w_mode = mode;
-  for (const Lin& x : lins) TD_TRY(td_quant_weight_rows_launch(x.w, x.K, x.ref->q, x.ref->s, x.w, x.N, x.K, (hipStream_t)stream));
+  for (const Lin& x : lins) {
+    if (mx4) TD_TRY(td_quant_weight_rows_mxfp4_launch(x.w, x.K, x.ref->q, (uint8_t*)x.ref->s, x.w, x.N, x.K, (hipStream_t)stream));
+    else TD_TRY(td_quant_weight_rows_launch(x.w, x.K, x.ref->q, (float*)x.ref->s, x.w, x.N, x.K, (hipStream_t)stream));
+  }
   f->w8_stale = false;
   f->w8_on = true;
   return TD_OK;
@@ -751,12 +776,13 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
   // 18 % ahead on the tiles at 64 (5.44 vs 6.63 ms).  TD_QWEN2_STREAM_BATCH (>= 16): A/B.
   static const int env_stream_batch = getenv("TD_QWEN2_STREAM_BATCH") ? atoi(getenv("TD_QWEN2_STREAM_BATCH")) : 0;
   const int stream_batch = env_stream_batch > 0 ? (env_stream_batch < 16 ? 16 : env_stream_batch) : (D >= 3072 ? 32 : STREAM_BATCH);
-  // With the 8-bit stream on, a step of up to 64 sequences moves half the bytes, so it stays on the stream kernels on both shapes
-  // (tools/bench_qwen2_w8.py measures every batch bucket against the bf16 routing of the same handle)
+  // With the 8-bit (or 4-bit) stream on, a step of up to 64 sequences moves half (a quarter of) the bytes, so it stays on the stream kernels on both shapes
+  // (tools/bench_qwen2_w8.py and tools/bench_qwen2_w4.py measure every batch bucket against the bf16 routing of the same handle)
   const bool wide = B > (f->w8_on ? STREAM_BATCH : stream_batch);
   // ... every bucket but one: two sequences measured 3 % SLOWER on the bytes than on bf16 W^ (1.503 vs 1.461 ms per step, profiles/qwen2_w8_bench.json),
   // so that step reads bf16 W^ -- the same model, no cost in numerics.  Measured on the 2B shape (hidden 1536) ONLY; the rule is drawn at the width
-  // that already separates the two measured shapes (hidden < 3072), other narrow widths have not been timed
+  // that already separates the two measured shapes (hidden < 3072), other narrow widths have not been timed.  The MXFP4 mode keeps the rule as it found it
+  // (its own 2-sequence cell on the 2B shape was not timed); every other bucket measured faster on the nibbles than on bf16 W^ on both shapes
   const bool a8 = !(B == 2 && D < 3072);
 
   TD_TRY(td_embed_gather_launch(f->tok_buf, f->embed_w, f->h, B, D, f->cfg.vocab, s));

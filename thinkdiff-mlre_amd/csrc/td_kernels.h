@@ -74,6 +74,10 @@ struct TdGemmParams {
   int no_tail = 0;                             // caller's hint: other kernels share the chip (several images in flight) -- an empty last round gets filled anyway, do not split it
   int probe = 0;                               // filled by the launcher from TD_GEMM_PROBE (timing experiments, results WRONG): 1 = no epilogue, 2 = no k-loop
   int drain_cap = 0;                           // 256x256 bf16 tile: at most this many persistent workgroups walk the tiles (0: one per CU); see td_gemm_bf16_drain_kernel
+  // 4-bit weight stream (skinny-M kernels only, M <= 64; W and W8 are then unused): W4 = MXFP4 nibbles [N, K / 2] (gated form: [2 glu_I, K / 2]), element 2j in
+  // the low nibble of byte j, w4_scale = e8m0 bytes [N, K / 32], the format td_quant_weight_rows_mxfp4_launch writes (csrc/mxfp4_pow2.h).  As with W8 the
+  // kernels see the bf16 values q * 2^e exactly.  (At the end: the fields in front keep their places in the kernels' argument block.)
+  const uint8_t* W4 = nullptr; const uint8_t* w4_scale = nullptr;
 };
 
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream);
@@ -84,6 +88,11 @@ bool td_gemv_w8_ok(const TdGemmParams& p);     // shapes the 8-bit weight stream
 // Weight-only e4m3 quantisation with one power-of-two scale per row (csrc/quant_weight.hip; the format: csrc/e4m3_pow2.h): q = the row's bytes,
 // scale[n] = 2^e_n; w_hat (may be null, may alias w) = q 2^e_n as bf16, exactly
 int td_quant_weight_rows_launch(const bf16_t* w, long long ldw, uint8_t* q, float* scale, bf16_t* w_hat, int N, int K, hipStream_t stream);
+bool td_gemv_w4_ok(const TdGemmParams& p);     // shapes the 4-bit weight stream takes (p.W4 need not be set yet): what td_gemv_launch would accept with W4
+// Weight-only MXFP4 quantisation, one e8m0 scale per 32 consecutive k of a row (csrc/quant_weight.hip; the format: csrc/mxfp4_pow2.h): packed [N, K / 2],
+// scales [N, K / 32]; w_hat (may be null, may alias w) = q 2^e as bf16, exactly.  The second entry rebuilds w_hat from the bytes.
+int td_quant_weight_rows_mxfp4_launch(const bf16_t* w, long long ldw, uint8_t* packed, uint8_t* scales, bf16_t* w_hat, int N, int K, hipStream_t stream);
+int td_dequant_rows_mxfp4_launch(const uint8_t* packed, const uint8_t* scales, bf16_t* w_hat, long long ldw, int N, int K, hipStream_t stream);
 // 0: 256x256 (td_gemm_bf16_nt_kernel<8,4>), 1: 256x64, 2: 32x256, 3: 288x192 (<9,3>)
 int td_gemm_config_id(int M, int N, int K);
 // The same choice under the caller's shared-chip hint (shared != 0; TdGemmParams::no_tail): the tile that costs the least CU time, per operand type

@@ -139,6 +139,56 @@ at::Tensor linear_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor
   return y;
 }
 
+// Weight-only MXFP4 quantisation (td_quant_weight_rows_mxfp4): w [N,K] -> (packed uint8 [N,K/2], scales uint8 [N,K/32], w_hat bf16 [N,K])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> quant_weight_rows_mxfp4(const at::Tensor& w) {
+  check_rows(w, "w");
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous() && w.size(1) % 32 == 0, "thinkdiff_hip::quant_weight_rows_mxfp4: w [N,K] contiguous, K a multiple of 32");
+  DeviceGuard guard(w.device());
+  at::Tensor packed = at::empty({w.size(0), w.size(1) / 2}, w.options().dtype(at::kByte));
+  at::Tensor scales = at::empty({w.size(0), w.size(1) / 32}, w.options().dtype(at::kByte));
+  at::Tensor w_hat = at::empty_like(w);
+  ok(td_quant_weight_rows_mxfp4(w.data_ptr(), w.stride(0), packed.data_ptr(), scales.data_ptr(), w_hat.data_ptr(), (int)w.size(0), (int)w.size(1), stream_of(w)));
+  return std::make_tuple(packed, scales, w_hat);
+}
+
+namespace {
+// packed uint8 [N,K/2] contiguous with scales uint8 [N,K/32] contiguous on its device
+void check_mxfp4(const at::Tensor& packed, const at::Tensor& scales, const char* op) {
+  check_rows(packed, "packed", at::kByte); check_rows(scales, "scales", at::kByte); same_device(scales, "scales", packed);
+  TORCH_CHECK(packed.dim() == 2 && packed.is_contiguous() && scales.dim() == 2 && scales.is_contiguous() && packed.size(0) > 0 && packed.size(1) % 16 == 0 &&
+                  scales.size(0) == packed.size(0) && scales.size(1) * 16 == packed.size(1),
+              "thinkdiff_hip::", op, ": packed uint8 [N,K/2] and scales uint8 [N,K/32], both contiguous, K a multiple of 32");
+}
+}  // namespace
+
+// ... and back (td_dequant_rows_mxfp4): packed, scales -> bf16 [N,K]
+at::Tensor dequant_rows_mxfp4(const at::Tensor& packed, const at::Tensor& scales) {
+  check_mxfp4(packed, scales, "dequant_rows_mxfp4");
+  DeviceGuard guard(packed.device());
+  at::Tensor w_hat = at::empty({packed.size(0), packed.size(1) * 2}, packed.options().dtype(at::kBFloat16));
+  ok(td_dequant_rows_mxfp4(packed.data_ptr(), scales.data_ptr(), w_hat.data_ptr(), w_hat.stride(0), (int)packed.size(0), (int)packed.size(1) * 2, stream_of(packed)));
+  return w_hat;
+}
+
+// linear with the weight given as MXFP4 nibbles + block scale bytes (the 4-bit weight stream, M <= 64)
+at::Tensor linear_w4(const at::Tensor& x, const at::Tensor& packed, const at::Tensor& scales, const c10::optional<at::Tensor>& bias, int64_t act,
+                     const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& res) {
+  check_rows(x, "x"); same_device(packed, "packed", x);
+  check_mxfp4(packed, scales, "linear_w4");
+  TORCH_CHECK(x.dim() == 2 && packed.size(1) * 2 == x.size(1), "thinkdiff_hip::linear_w4: x [M,K], packed uint8 [N,K/2]");
+  check_vec(bias, "bias", x, packed.size(0)); check_vec(gate, "gate", x, packed.size(0));
+  if (res.has_value() && res->defined()) {
+    check_rows(*res, "res"); same_device(*res, "res", x);
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == x.size(0) && res->size(1) == packed.size(0), "thinkdiff_hip::linear_w4: res must be [M,N]");
+  }
+  DeviceGuard guard(x.device());
+  at::Tensor y = at::empty({x.size(0), packed.size(0)}, x.options());
+  const int64_t ldr = res.has_value() && res->defined() ? res->stride(0) : 0;
+  ok(td_linear_w4_bf16(x.data_ptr(), x.stride(0), packed.data_ptr(), scales.data_ptr(), P(bias), y.data_ptr(), y.stride(0), (int)x.size(0),
+                       (int)packed.size(0), (int)x.size(1), (int)act, P(gate), P(res), ldr, stream_of(x)));
+  return y;
+}
+
 // ThinkDiff aligner mm_projector "mlp2x_gelu_t5_norm": T5LayerNorm(Linear2(GELU_erf(Linear0(x))))
 at::Tensor aligner_mlp2x(const at::Tensor& x, const at::Tensor& w0, const at::Tensor& b0, const at::Tensor& w2, const at::Tensor& b2,
                          const at::Tensor& norm_w, double eps, bool fp32_norm) {
@@ -1000,6 +1050,9 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("kv_dequant_rows_e4m3(Tensor q, Tensor scale) -> Tensor");
   m.def("attention_decode_kv8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor");
   m.def("linear_w8(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
+  m.def("quant_weight_rows_mxfp4(Tensor w) -> (Tensor, Tensor, Tensor)");
+  m.def("dequant_rows_mxfp4(Tensor packed, Tensor scales) -> Tensor");
+  m.def("linear_w4(Tensor x, Tensor packed, Tensor scales, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
   m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
   m.def("kv_gather_rows(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()");
   m.def("beam_select(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()");
@@ -1054,6 +1107,9 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("kv_dequant_rows_e4m3", &kv_dequant_rows_e4m3);
   m.impl("attention_decode_kv8", &attention_decode_kv8);
   m.impl("linear_w8", &linear_w8);
+  m.impl("quant_weight_rows_mxfp4", &quant_weight_rows_mxfp4);
+  m.impl("dequant_rows_mxfp4", &dequant_rows_mxfp4);
+  m.impl("linear_w4", &linear_w4);
   m.impl("kv_fork_rows", &kv_fork_rows);
   m.impl("kv_gather_rows", &kv_gather_rows);
   m.impl("beam_select", &beam_select);

@@ -221,6 +221,11 @@ def _declare(L):
         "td_linear_split_w8_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
         "td_linear_glu_bf16": [vp, i64, vp, vp, i64, i32, i32, i32, vp],
         "td_linear_glu_w8_bf16": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
+        "td_quant_weight_rows_mxfp4": [vp, i64, vp, vp, vp, i32, i32, vp],
+        "td_dequant_rows_mxfp4": [vp, vp, vp, i64, i32, i32, vp],
+        "td_linear_w4_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp],
+        "td_linear_split_w4_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
+        "td_linear_glu_w4_bf16": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
         "td_embed_gather_bf16": [vp, vp, vp, i32, i32, i32, vp],
         "td_silu_mul_bf16": [vp, vp, i32, i32, vp],
         "td_mrope_table": [vp, i32, vp, f32, i32, vp, vp, vp],
@@ -311,7 +316,7 @@ def linear(x, w, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
     return out
 
 
-QWEN2_WEIGHTS_BF16, QWEN2_WEIGHTS_E4M3 = 0, 1
+QWEN2_WEIGHTS_BF16, QWEN2_WEIGHTS_E4M3, QWEN2_WEIGHTS_MXFP4 = 0, 1, 2
 
 
 def quant_weight_rows_e4m3(w, want_w_hat=True, inplace=False):
@@ -404,6 +409,63 @@ def linear_split_w8(x, wq, w_scale, bias, out0, act0, out1, act1, n_split):
     check(lib().td_linear_split_w8_bf16(ptr(x), _rows(x), ptr(wq), ptr(w_scale), ptr(bias), ptr(out0), _rows(out0), act0,
                                         ptr(out1), _rows(out1), act1, M, N, K, n_split, stream_ptr()))
     return out0, out1
+
+
+def quant_weight_rows_mxfp4(w, want_w_hat=True, inplace=False):
+    """Weight-only OCP MXFP4 quantisation (td_quant_weight_rows_mxfp4): w bf16 [N, K] (K % 32 == 0; row stride may exceed K) -> (packed uint8 [N, K / 2],
+    element 2j in the low nibble of byte j; scales uint8 [N, K / 32] = e + 127; w_hat bf16 = q 2^e exactly, or None).  inplace: w_hat is written over w."""
+    N, K = w.shape
+    packed = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    scales = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    w_hat = w if inplace else (torch.empty_strided(w.shape, w.stride(), dtype=w.dtype, device=w.device) if want_w_hat else None)
+    check(lib().td_quant_weight_rows_mxfp4(ptr(w), _rows(w), ptr(packed), ptr(scales), ptr(w_hat), N, K, stream_ptr()))
+    return packed, scales, w_hat
+
+
+def _w4(x, packed, scales):
+    M, K = x.shape
+    assert packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous() and packed.shape[1] * 2 == K, (packed.shape, packed.dtype, K)
+    assert scales.dtype == torch.uint8 and scales.is_contiguous() and scales.shape == (packed.shape[0], K // 32), (scales.shape, scales.dtype, K)
+    return M, packed.shape[0], K
+
+
+def dequant_rows_mxfp4(packed, scales, out=None):
+    """packed [N, K / 2] + scales [N, K / 32] -> bf16 [N, K] = q 2^e, exactly (td_dequant_rows_mxfp4)."""
+    assert packed.dtype == torch.uint8 and scales.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous() and scales.is_contiguous()
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert scales.shape == (N, K // 32), (scales.shape, N, K)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=packed.device)
+    assert out.dtype == torch.bfloat16 and out.stride(1) == 1
+    check(lib().td_dequant_rows_mxfp4(ptr(packed), ptr(scales), ptr(out), out.stride(0), N, K, stream_ptr()))
+    return out
+
+
+def linear_w4(x, packed, scales, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
+    """linear() with the weight as MXFP4 nibbles + block scale bytes (the 4-bit weight stream; M <= 64)."""
+    M, N, K = _w4(x, packed, scales)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_w4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(bias), ptr(out), _rows(out), M, N, K, act,
+                                  ptr(gate), ptr(res), _rows(res) if res is not None else 0, stream_ptr()))
+    return out
+
+
+def linear_split_w4(x, packed, scales, bias, out0, act0, out1, act1, n_split):
+    M, N, K = _w4(x, packed, scales)
+    check(lib().td_linear_split_w4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(bias), ptr(out0), _rows(out0), act0,
+                                        ptr(out1), _rows(out1), act1, M, N, K, n_split, stream_ptr()))
+    return out0, out1
+
+
+def linear_glu_w4(x, packed, scales, out=None):
+    """linear_glu() with the weight as MXFP4 nibbles + block scale bytes."""
+    M, N2, K = _w4(x, packed, scales)
+    assert N2 % 2 == 0
+    if out is None:
+        out = torch.empty((M, N2 // 2), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_glu_w4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(out), _rows(out), M, N2 // 2, K, stream_ptr()))
+    return out
 
 
 def linear_glu(x, w, out=None):

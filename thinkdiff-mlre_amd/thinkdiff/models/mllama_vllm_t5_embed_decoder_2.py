@@ -45,7 +45,7 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         self.mllama = Qwen2VLTextEngine(text_config, max_model_len=vc.get("max_model_len", 8192), device=device, n_slots=self.decode_batch,
                                         kv_cache_dtype=kv_cache_dtype,
                                         prefill_rows=min(int(vc.get("max_num_batched_tokens", 16384)), 16384) if self.decode_batch > 1 else None)
-        # vLLM's `quantization="fp8"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
+        # vLLM's `quantization="fp8"` / `"mxfp4"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
         self.mllama.weight_quantization = quantization
         self.mllama_sampling_params = SamplingParams(
             temperature=vc.get("temperature", 0.6), top_p=vc.get("top_p", 0.9), max_tokens=vc.get("max_tokens", 128),

@@ -706,8 +706,41 @@ class Qwen2VLTextEngine:
             out[buf.value.decode()] = cnt.value
         return out
 
+    def _dequantize_packed(self, sd: Dict[str, torch.Tensor], table: Dict[str, int]) -> Dict[str, torch.Tensor]:
+        """A pre-quantised MXFP4 checkpoint (Quark / torchao layout): a decoder Linear or lm_head given as `<name>.weight` uint8 [N, K / 2] plus
+        `<name>.weight_scale` uint8 [N, K / 32] is dequantised EXACTLY to bf16 here and loaded like any weight; the quantisation that closes the load
+        rebuilds the engine's copy from those values, which it reproduces bit for bit whatever scale rule wrote the checkpoint (every e2m1 value times
+        2, 4 or 8 is on the grid again).  Anything malformed is a ValueError naming the key."""
+        packed = [k for k, t in sd.items() if k in table and k.endswith(".weight") and t.dtype == torch.uint8]
+        for k in sd:
+            if k.endswith(".weight_scale") and k[:-len("_scale")] not in packed:
+                raise ValueError(f"Qwen2VLTextEngine.load_state_dict: {k!r} has no packed uint8 tensor {k[:-len('_scale')]!r} beside it")
+        if not packed:
+            return sd
+        out = {k: t for k, t in sd.items() if not k.endswith(".weight_scale")}
+        for k in packed:
+            if self.weight_quantization != "mxfp4":
+                raise ValueError(f"Qwen2VLTextEngine.load_state_dict: {k!r} is a packed MXFP4 tensor but the engine's quantization is "
+                                 f"{self.weight_quantization!r}: packed weights load only with quantization='mxfp4'")
+            if k + "_scale" not in sd:
+                raise ValueError(f"Qwen2VLTextEngine.load_state_dict: packed MXFP4 tensor {k!r} lacks its scales {k + '_scale'!r}")
+            q, sc = sd[k], sd[k + "_scale"]
+            K = 2 * q.shape[-1] if q.dim() == 2 else 0
+            if q.dim() != 2 or K % 32 != 0 or q.numel() * 2 != table[k] or k.split(".")[-2] not in self.PACKED_LINEARS:
+                raise ValueError(f"Qwen2VLTextEngine.load_state_dict: packed MXFP4 tensor {k!r} has shape {tuple(q.shape)}: expected uint8 [N, K / 2] "
+                                 f"with N K = {table[k]} and K a multiple of 32, on a decoder Linear or lm_head")
+            if sc.dtype != torch.uint8 or tuple(sc.shape) != (q.shape[0], K // 32):
+                raise ValueError(f"Qwen2VLTextEngine.load_state_dict: {k + '_scale'!r} is {sc.dtype} {tuple(sc.shape)}: expected uint8 "
+                                 f"{(q.shape[0], K // 32)} (one e8m0 byte per 32 weights of a row)")
+            out[k] = _hip.dequant_rows_mxfp4(q.to(self.device).contiguous(), sc.to(self.device).contiguous())
+        return out
+
+    # the Linears a packed checkpoint may carry: the ones quantize_weights("mxfp4") quantises
+    PACKED_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj", "lm_head")
+
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         table = self.param_table()
+        sd = self._dequantize_packed(sd, table)
         missing = [k for k in table if k not in sd]
         if strict and missing:
             raise KeyError(f"Qwen2VLTextEngine.load_state_dict: missing {missing[:4]}..")
@@ -759,22 +792,25 @@ class Qwen2VLTextEngine:
         return self
 
     # ---- 8-bit weight stream --------------------------------------------------------------------------------
-    WEIGHT_QUANTIZATIONS = {"fp8": _hip.QWEN2_WEIGHTS_E4M3}
+    WEIGHT_QUANTIZATIONS = {"fp8": _hip.QWEN2_WEIGHTS_E4M3, "mxfp4": _hip.QWEN2_WEIGHTS_MXFP4}
 
     @classmethod
     def check_quantization(cls, value):
-        """vllm_config["quantization"] as the models take it: None (bf16) or "fp8"; anything else is an error, never ignored."""
+        """vllm_config["quantization"] as the models take it: None (bf16), "fp8" or "mxfp4"; anything else is an error, never ignored."""
         if value is not None and value not in cls.WEIGHT_QUANTIZATIONS:
-            raise ValueError(f"vllm_config quantization={value!r} is not served by the HIP engine: only 'fp8' (weight-only e4m3), or None for bf16")
+            raise ValueError(f"vllm_config quantization={value!r} is not served by the HIP engine: only 'fp8' (weight-only e4m3) and 'mxfp4' "
+                             "(weight-only OCP MXFP4), or None for bf16")
         return value
 
     def quantize_weights(self, quantization: str = "fp8"):
         """Weight-only fp8 of every decoder Linear and lm_head (vLLM's `quantization="fp8"`): e4m3 bytes with one power-of-two scale per output row
         beside the bf16 weights, which are OVERWRITTEN with the dequantised values (exactly representable; with tied embeddings the embedding table too).
         Decode steps of up to 64 sequences then stream the bytes; prefill and wider steps run the same model in bf16.  Call after the weights
-        are loaded, and again after any later load_state_dict / init_random (runs are refused until then)."""
+        are loaded, and again after any later load_state_dict / init_random (runs are refused until then).
+        "mxfp4" (vLLM's `quantization="mxfp4"`) is the same scheme in OCP MXFP4: e2m1 nibbles under one e8m0 scale per 32 weights of a row, 0.27x the
+        bf16 bytes, its dequantised values exact in bf16 too.  An engine quantised in one format refuses the other until its weights are loaded again."""
         if quantization not in Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS:
-            raise ValueError(f"Qwen2VLTextEngine.quantize_weights: quantization={quantization!r} is not served (only 'fp8')")
+            raise ValueError(f"Qwen2VLTextEngine.quantize_weights: quantization={quantization!r} is not served (only 'fp8' and 'mxfp4')")
         _hip.check(self._L.td_qwen2_quantize_weights(self._h, Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS[quantization], _hip.stream_ptr()))
         return self
 

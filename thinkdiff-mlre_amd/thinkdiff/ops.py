@@ -53,6 +53,9 @@ image_resize_u8            PIL's `Image.resize` (LANCZOS / BILINEAR / BICUBIC, w
                            fixed-point horizontal and vertical passes as two kernels over host-made coefficient tables, the same bytes
 quant_weight_rows_e4m3 / linear_w8   weight-only fp8 of an nn.Linear (vLLM's `quantization="fp8"` on the LVLM): e4m3 bytes with one power-of-two scale per
                            output row (bytes, scales and the dequantised bf16 weight, which is exact), and the Linear of up to 64 rows that streams the bytes
+quant_weight_rows_mxfp4 / dequant_rows_mxfp4 / linear_w4   weight-only OCP MXFP4 of an nn.Linear (vLLM's `quantization="mxfp4"` on the LVLM): e2m1 nibbles (element 2j
+                           in the low nibble of byte j) with one e8m0 scale byte per 32 weights of a row, back to bf16 (exact), and the Linear of up to 64 rows
+                           that streams the nibbles
 kv_quant_rows_e4m3 / kv_dequant_rows_e4m3 / attention_decode_kv8   the e4m3 KV cache of the LVLM's decode engine (vLLM's `kv_cache_dtype="fp8"`): e4m3 bytes with one
                            power-of-two scale per 128-wide head vector of a cache row, back to bf16 (exact), and the decode attention that reads bytes + scales
 kv_fork_rows               the first n_rows rows of one slot of a cache plane copied to many slots in one launch, each source chunk loaded once (what vLLM's
@@ -118,6 +121,9 @@ SCHEMAS = {
     "image_resize_u8": "(Tensor img, int out_h, int out_w, int resample, int? out_channels) -> Tensor",
     "quant_weight_rows_e4m3": "(Tensor w) -> (Tensor, Tensor, Tensor)",
     "linear_w8": "(Tensor x, Tensor wq, Tensor w_scale, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor",
+    "quant_weight_rows_mxfp4": "(Tensor w) -> (Tensor, Tensor, Tensor)",
+    "dequant_rows_mxfp4": "(Tensor packed, Tensor scales) -> Tensor",
+    "linear_w4": "(Tensor x, Tensor packed, Tensor scales, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor",
     "kv_quant_rows_e4m3": "(Tensor kv, int heads) -> (Tensor, Tensor, Tensor)",
     "kv_dequant_rows_e4m3": "(Tensor q, Tensor scale) -> Tensor",
     "attention_decode_kv8": "(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor",
