@@ -1223,6 +1223,59 @@ int td_logprobs_rows_bf16(const void* logits, int64_t ld, int rows, int vocab, c
 int td_beam_select(const int32_t* top_ids, const float* top_lp, int cap, const float* cum_in, const int32_t* rank_in, int R, int W, int n_in, int eos,
                    int32_t* token, float* cum_out, int32_t* rank_out, int32_t* copy_src, int32_t* parent, int32_t* fin_flag, float* fin_cum, void* stream);
 
+/* ---- speculative decoding: a multi-row verify step and the accept rule (td_abi_version() >= 21) ----
+ * Multi-row decode attention (csrc/attention_decode.hip).  Sequence b of n_seq (1..256) owns the query rows [seq_row0[b], seq_row0[b] + seq_rows[b]) of
+ * q / o (row strides ldq / ldo, elements), 1 <= seq_rows[b] <= TD_MAX_VERIFY_ROWS; row j of it sees keys [0, seq_len0[b] + j) of cache slot seq_slot[b]
+ * (slot stride kv_bstride; s_bstride for the scales).  seq_len0[b] counts the keys visible to the first row, that row's own key included; the new rows'
+ * k | v are in the cache when the launch starts.  bf16 cache: k, v set (ldkv, kv_bstride in elements), k8 / v8 / k_scale / v_scale NULL; e4m3 cache
+ * (the format of td_kv_quant_rows_e4m3): k8, v8, k_scale, v_scale set (ldkv, kv_bstride in bytes; lds, s_bstride in floats), k / v NULL.
+ * Two forms.  Form 1, one workgroup per (q-head group, row): the single-row kernel's own body, K/V read once per row; row (b, j) receives the BITS
+ * td_attention_bf16 (Sq = 1, causal) / td_attention_decode_kv8 give one query with kv_lens = seq_len0[b] + j on the same cache under the same q-head group.
+ * Form 2, one workgroup per (q-head group, sequence, chunk of T rows): K/V read once for the G x T <= 8 (row, head) states of a workgroup; its softmax
+ * update is written out as fmas, so its result is the same under every G and T but differs from form 1 in the last bf16 bit of a fraction of a per cent of
+ * the rows: it is held to one bf16 ulp + 2^-12 max |v| of the float64 result, not to bit equality.  The automatic routing (td_attention_verify_set_form:
+ * 0 = automatic, 1, 2; returns the previous value; tests and A/B) takes form 2 only where it measured faster -- 2 .. 4 rows per sequence with
+ * Hq x n_seq below the CU count, on the e4m3 cache or from 4096 keys on -- which it can only know through td_attention_verify_ex: this entry always runs
+ * form 1 unless forced.  td_attention_decode_set_group forces G in both forms.
+ * The four per-sequence arrays are DEVICE int32, so their values cannot be checked on the host: the kernels clamp seq_rows[b] to 1..TD_MAX_VERIFY_ROWS and
+ * never read a key at or past seq_len0[b] + seq_rows[b] - 1.
+ * TD_ERR_INVALID with a message naming the value, before any HIP call: a NULL operand, both or neither cache form, n_seq outside 1..256, Hq % Hkv != 0,
+ * ldq / ldo / ldkv / kv_bstride not multiples of 8 or narrower than their heads, q / o / k / v not 16-byte, k8 / v8 not 8-byte, scales or arrays not
+ * 4-byte aligned. */
+#define TD_MAX_VERIFY_ROWS 8
+int td_attention_verify(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, int64_t kv_bstride, const void* k8, const void* v8,
+                        const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int n_seq,
+                        const int32_t* seq_row0_dev, const int32_t* seq_rows_dev, const int32_t* seq_len0_dev, const int32_t* seq_slot_dev, int Hq, int Hkv,
+                        float scale, void* stream);
+int td_attention_verify_set_form(int form);
+/* ... for a caller that knows on the HOST what the device arrays hold: t_max = the largest seq_rows[b] (1..8; seq_rows[b] is clamped to it, and the grid
+ * is laid out for it), max_len = the longest visible length seq_len0[b] + seq_rows[b] - 1 (0 = unknown; it only feeds the automatic routing).
+ * td_attention_verify is this entry with t_max = 8 and max_len = 0.  Stateless: nothing a call passes here outlives it. */
+int td_attention_verify_ex(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, int64_t kv_bstride, const void* k8, const void* v8,
+                           const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int n_seq,
+                           const int32_t* seq_row0_dev, const int32_t* seq_rows_dev, const int32_t* seq_len0_dev, const int32_t* seq_slot_dev, int Hq, int Hkv,
+                           float scale, int t_max, int max_len, void* stream);
+
+/* The verify step of the Qwen2-VL engine: sequence b (cache slot slots[b], HOST ints, distinct; NULL = 0 .. B-1) feeds n_new[b] tokens (HOST, 1..8) at
+ * cache rows cache_pos[b] .. (HOST).  R = sum n_new <= 256 rows, sequence after sequence: token_ids int32[R], position_ids int32[3, R] (device);
+ * hidden_out bf16[R, hidden], logits bf16[R, vocab] (either may be NULL).  Row (b, j) is what td_qwen2_decode_batch_slots returns for that token had the
+ * j tokens before it been decoded one step at a time (the same launches under the routing a step of R sequences takes; always the separate rotary +
+ * cache-write launch, then td_attention_verify's kernels).  The call runs eagerly; with every n_new == 1 it IS td_qwen2_decode_batch_slots.
+ * No rollback: all R new k | v rows are written; a caller that rejects tokens advances cache_pos by what it keeps and the next step overwrites the rest.
+ * TD_ERR_INVALID before any launch: what td_qwen2_decode_batch_slots refuses, n_new[b] outside 1..8, cache_pos[b] + n_new[b] > the slot capacity,
+ * R above 256 or above the workspace rows. */
+int td_qwen2_verify_batch_slots(td_qwen2* f, int B, const int* slots, const int* n_new, const int* token_ids, const int* position_ids, const int* cache_pos,
+                                void* hidden_out, void* logits, void* stream);
+
+/* The accept rule (csrc/spec_decode.hip).  sampled[r] = the token SAMPLED from row r's logits, input[r] = the token that was fed as row r (device
+ * int32[R]); sequence b owns rows [seq_row0[b], seq_row0[b] + seq_rows[b]) (device int32[B], seq_rows clamped to 1..TD_MAX_VERIFY_ROWS).
+ *   a[b] = the number of leading j < seq_rows[b] - 1 with input[row0 + j + 1] == sampled[row0 + j];
+ *   n_emit[b] = a[b] + 1;  emit[b, 0 .. a[b]] = sampled[row0 .. row0 + a[b]], the other columns of emit int32[B, TD_MAX_VERIFY_ROWS] hold -1.
+ * Every emitted token is a draw from the target distribution on a true prefix; the guesses decide only how many rows were.
+ * TD_ERR_INVALID before any HIP call: a NULL or misaligned pointer, B outside 1..256. */
+int td_spec_accept(const int32_t* sampled_dev, const int32_t* input_dev, const int32_t* seq_row0_dev, const int32_t* seq_rows_dev, int B,
+                   int32_t* n_emit_dev, int32_t* emit_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

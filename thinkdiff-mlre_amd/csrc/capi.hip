@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 20; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 21; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -43,6 +43,8 @@ int td_abi_version(void) { return 20; }  // 2: TdFluxConfig::out_channels append
                                             // 19: td_gemm_plan_query (host-only: the tile an automatic GEMM launch takes, alone or on a shared chip)
                                             // 20: MXFP4 weight stream (td_quant_weight_rows_mxfp4, td_dequant_rows_mxfp4, td_linear*_w4_bf16,
                                             //     TD_QWEN2_WEIGHTS_MXFP4)
+                                            // 21: speculative decoding (td_attention_verify, td_attention_verify_ex, td_attention_verify_set_form,
+                                            //     td_qwen2_verify_batch_slots, td_spec_accept; csrc/spec_decode.hip)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -753,6 +755,32 @@ int td_attention_decode_kv8(const void* q, int64_t ldq, int64_t q_bstride, const
   p.q_bstride = q_bstride; p.kv_bstride = kv_bstride; p.o_bstride = o_bstride; p.s_bstride = s_bstride;
   p.scale = scale; p.causal = 1; p.causal_offset = Skv - 1; p.kv_lens = kv_lens;
   return td_attn_launch(p, (hipStream_t)stream);
+}
+
+// ---- speculative decoding (td_abi_version() >= 21): the launcher refuses before its first HIP call
+int td_attention_verify_ex(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, int64_t kv_bstride, const void* k8, const void* v8,
+                           const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int n_seq,
+                           const int32_t* seq_row0_dev, const int32_t* seq_rows_dev, const int32_t* seq_len0_dev, const int32_t* seq_slot_dev, int Hq, int Hkv,
+                           float scale, int t_max, int max_len, void* stream) {
+  TD_CHECK_ARG(max_len >= 0, "td_attention_verify: max_len=%d is negative (0 = unknown)", max_len);
+  TD_CHECK_ARG(ld32(ldq) && ld32(ldkv) && ld32(ldo) && ld32(lds), "td_attention_verify: ldq=%lld, ldkv=%lld, ldo=%lld, lds=%lld must fit 32 bits", (long long)ldq,
+               (long long)ldkv, (long long)ldo, (long long)lds);
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.O = (bf16_t*)o; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v;
+  p.K8 = (const uint8_t*)k8; p.V8 = (const uint8_t*)v8; p.k_scale = k_scale; p.v_scale = v_scale;
+  p.batch = n_seq; p.Sq = 1; p.Skv = max_len; p.Hq = Hq; p.Hkv = Hkv; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo; p.lds = (int)lds;
+  p.kv_bstride = kv_bstride; p.s_bstride = s_bstride; p.scale = scale; p.causal = 1;
+  p.vr_row0 = seq_row0_dev; p.vr_rows = seq_rows_dev; p.vr_len0 = seq_len0_dev; p.vr_slot = seq_slot_dev;
+  return td_attn_verify_launch(p, t_max, (hipStream_t)stream);
+}
+
+int td_attention_verify(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, int64_t kv_bstride, const void* k8, const void* v8,
+                        const float* k_scale, const float* v_scale, int64_t lds, int64_t s_bstride, void* o, int64_t ldo, int n_seq,
+                        const int32_t* seq_row0_dev, const int32_t* seq_rows_dev, const int32_t* seq_len0_dev, const int32_t* seq_slot_dev, int Hq, int Hkv,
+                        float scale, void* stream) {
+  return td_attention_verify_ex(q, ldq, k, v, ldkv, kv_bstride, k8, v8, k_scale, v_scale, lds, s_bstride, o, ldo, n_seq, seq_row0_dev, seq_rows_dev, seq_len0_dev,
+                                seq_slot_dev, Hq, Hkv, scale, TD_MAX_VERIFY_ROWS, 0, stream);
 }
 
 int td_sample_top_p_bf16(const void* logits, int64_t ld, int rows, int vocab, float temperature, float top_p,

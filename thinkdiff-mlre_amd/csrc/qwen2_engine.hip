@@ -765,12 +765,18 @@ namespace {
 // The launches of one decode step for the sequences in slots 0 .. B-1: ids from tok_buf / pos_buf, lengths and cache rows from ibuf, the final
 // hidden states left in xn and the logits in logits_buf.  Captured into a graph by td_qwen2_decode_batch (nothing here may depend on a host value
 // other than B and the engine's own pointers; max_len only sizes the generic attention entry's bookkeeping, the decode kernel reads kv_lens).
-int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s) {
+// vr_seqs > 0: the verify step of td_qwen2_verify_batch_slots.  The B rows are then the new tokens of vr_seqs sequences, up to vr_tmax each, sequence after
+// sequence: ibuf holds row_off per ROW where it always does and the four per-SEQUENCE arrays of td_attn_verify_launch around it (first row | - | rows |
+// keys visible to the first row | cache slot).  Everything but the attention is the step of B sequences; the rotary embedding and the cache write take
+// their separate launch, so that every new k | v row is in the cache before the attention, which serves all rows of a sequence from one pass over it.
+int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s, int vr_seqs = 0, int vr_tmax = 0) {
   const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv;
   const int QW = Hq * 128, KVW = 2 * Hkv * 128;
   const int* kv_lens = f->ibuf;
   const int* row_off = f->ibuf + MAX_BATCH;
   const int* slot_ids = f->ibuf + 2 * MAX_BATCH;      // cache slot of each sequence of the step
+  const bool verify = vr_seqs > 0;
+  const bool fused_rope = f->fused_rope && !verify;
   // Cross-over between the weight-stream kernels and the tile kernels, measured on both decoder shapes (profiles/r4z_decode_crossover.log): the 2B
   // shape (hidden 1536) stays ahead on the stream through 64 sequences (2.68 vs 2.79 ms per step), the 7B shape (hidden 3584) is level at 24 and
   // 18 % ahead on the tiles at 64 (5.44 vs 6.63 ms).  TD_QWEN2_STREAM_BATCH (>= 16): A/B.
@@ -805,12 +811,12 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     // rotary embedding of the new q / k rows and the cache write ride inside the attention launch (TdAttnParams::dec_kv_new);
     // td_qwen2_set_fused_rope(f, 0): the separate launch (A/B and the bit-identity test)
     const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
-    if (!f->fused_rope) {
+    if (!fused_rope) {
       if (kv8) hipLaunchKernelGGL(td_decode_rope_scatter_kernel<true>, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, (bf16_t*)nullptr, l.kv8, l.kvs, row_off, f->cosT, f->sinT, Hq, Hkv);
       else hipLaunchKernelGGL(td_decode_rope_scatter_kernel<false>, dim3(B), dim3(256), 0, s, f->q, f->kvtmp, l.kv, (uint8_t*)nullptr, (float*)nullptr, row_off, f->cosT, f->sinT, Hq, Hkv);
     }
     TdAttnParams ap;
-    if (f->fused_rope) { ap.dec_kv_new = f->kvtmp; ap.dec_cos = f->cosT; ap.dec_sin = f->sinT; ap.dec_row_off = row_off; }
+    if (fused_rope) { ap.dec_kv_new = f->kvtmp; ap.dec_cos = f->cosT; ap.dec_sin = f->sinT; ap.dec_row_off = row_off; }
     ap.Q = f->q; ap.ldq = QW; ap.q_bstride = QW; ap.ldkv = KVW;
     ap.kv_bstride = (long long)f->slot_len * KVW; ap.O = f->attn; ap.ldo = QW; ap.o_bstride = QW;
     ap.batch = B; ap.Sq = 1; ap.Skv = max_len; ap.Hq = Hq; ap.Hkv = Hkv; ap.scale = 0.08838834764831845f;
@@ -820,7 +826,13 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     } else {      // the same launch, its descriptor carrying bytes + scales (ldkv / kv_bstride then count bytes)
       ap.K8 = l.kv8; ap.V8 = l.kv8 + Hkv * 128; ap.k_scale = l.kvs; ap.v_scale = l.kvs + Hkv; ap.lds = 2 * Hkv; ap.s_bstride = (long long)f->slot_len * 2 * Hkv;
     }
-    TD_TRY(td_attn_launch(ap, s));
+    if (verify) {
+      ap.batch = vr_seqs; ap.kv_lens = nullptr; ap.dec_slots = nullptr;
+      ap.vr_row0 = f->ibuf; ap.vr_rows = f->ibuf + 2 * MAX_BATCH; ap.vr_len0 = f->ibuf + 3 * MAX_BATCH; ap.vr_slot = f->ibuf + 4 * MAX_BATCH;
+      TD_TRY(td_attn_verify_launch(ap, vr_tmax, s));
+    } else {
+      TD_TRY(td_attn_launch(ap, s));
+    }
     {
       TdGemmParams g = linear(f->attn, QW, l.o_w, nullptr, f->h, D, B, D, QW, true);
       if (wide) {
@@ -930,6 +942,46 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
   }
   if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)B * D * 2, hipMemcpyDeviceToDevice, s));
   if (logits) TD_CHECK_HIP(hipMemcpyAsync(logits, f->logits_buf, (size_t)B * f->cfg.vocab * 2, hipMemcpyDeviceToDevice, s));
+  return TD_OK;
+}
+
+// The verify step of speculative decoding (include/thinkdiff_hip.h): sequence b feeds n_new[b] tokens at cache rows cache_pos[b] .., R = sum n_new rows in
+// all.  decode_step over R rows with the multi-row attention; eager.  Every n_new == 1: the plain step itself.
+int td_qwen2_verify_batch_slots(td_qwen2* f, int B, const int* slots, const int* n_new, const int* token_ids, const int* position_ids, const int* cache_pos,
+                                void* hidden_out, void* logits, void* stream) {
+  TD_CHECK_ARG(f && n_new && token_ids && position_ids && cache_pos, "td_qwen2_verify_batch: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_verify_batch");
+  TD_CHECK_ARG(B >= 1 && B <= MAX_BATCH && B <= f->n_slots && B <= f->ws_rows, "td_qwen2_verify_batch: batch %d exceeds min(%d, %d slots, %d workspace rows)", B, MAX_BATCH, f->n_slots, f->ws_rows);
+  if (slots) TD_TRY(check_distinct_slots("td_qwen2_verify_batch", "sequence", slots, B));
+  IntPack rows_pack, seq_pack;      // ibuf [0, 3 MAX_BATCH): first row per sequence | cache row per ROW | rows per sequence; [3 MAX_BATCH, 5 MAX_BATCH): len0 | slot
+  int R = 0, max_len = 0, t_max = 1;
+  for (int b = 0; b < B; ++b) {
+    const int slot = slots ? slots[b] : b;
+    TD_CHECK_ARG(slot >= 0 && slot < f->n_slots, "td_qwen2_verify_batch: sequence %d names cache slot %d of %d", b, slot, f->n_slots);
+    TD_CHECK_ARG(n_new[b] >= 1 && n_new[b] <= TD_MAX_VERIFY_ROWS, "td_qwen2_verify_batch: n_new[%d]=%d outside 1..%d", b, n_new[b], TD_MAX_VERIFY_ROWS);
+    TD_CHECK_ARG(cache_pos[b] >= 0 && cache_pos[b] + n_new[b] <= f->slot_len, "td_qwen2_verify_batch: sequence %d: cache_pos %d + n_new %d exceeds the slot capacity %d", b,
+                 cache_pos[b], n_new[b], f->slot_len);
+    TD_CHECK_ARG(R + n_new[b] <= MAX_BATCH && R + n_new[b] <= f->ws_rows, "td_qwen2_verify_batch: R=%d rows exceed min(%d, %d workspace rows)", R + n_new[b], MAX_BATCH, f->ws_rows);
+    rows_pack.v[b] = R;
+    rows_pack.v[2 * MAX_BATCH + b] = n_new[b];
+    seq_pack.v[b] = cache_pos[b] + 1;
+    seq_pack.v[MAX_BATCH + b] = slot;
+    for (int j = 0; j < n_new[b]; ++j) rows_pack.v[MAX_BATCH + R + j] = slot * f->slot_len + cache_pos[b] + j;
+    R += n_new[b];
+    t_max = n_new[b] > t_max ? n_new[b] : t_max;
+    max_len = cache_pos[b] + n_new[b] > max_len ? cache_pos[b] + n_new[b] : max_len;
+  }
+  if (t_max == 1) return td_qwen2_decode_batch_slots(f, B, slots, token_ids, position_ids, cache_pos, hidden_out, logits, stream);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, f->ibuf, rows_pack, 3 * MAX_BATCH);
+  hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, f->ibuf + 3 * MAX_BATCH, seq_pack, 2 * MAX_BATCH);
+  TD_CHECK_LAUNCH();
+  TD_CHECK_HIP(hipMemcpyAsync(f->tok_buf, token_ids, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
+  // (pos_buf is [3, R] here: the table launch reads stream k of row r at k R + r)
+  TD_CHECK_HIP(hipMemcpyAsync(f->pos_buf, position_ids, (size_t)3 * R * 4, hipMemcpyDeviceToDevice, s));
+  TD_TRY(decode_step(f, R, max_len, logits != nullptr, s, B, t_max));
+  if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)R * f->D * 2, hipMemcpyDeviceToDevice, s));
+  if (logits) TD_CHECK_HIP(hipMemcpyAsync(logits, f->logits_buf, (size_t)R * f->cfg.vocab * 2, hipMemcpyDeviceToDevice, s));
   return TD_OK;
 }
 

@@ -128,6 +128,10 @@ struct TdAttnParams {
   // decode kernel only: sequence b's cache is slot dec_slots[b] (K / V + dec_slots[b] kv_bstride) instead of slot b -- the sequences of a step need not
   // sit in the first slots, so a finished sequence frees its slot without anybody's cache rows being moved (continuous batching); q / o stay row b
   const int* dec_slots = nullptr;
+  // td_attn_verify_launch only (device int[batch] each; batch = sequences): sequence b owns the q / o ROWS [vr_row0[b], vr_row0[b] + vr_rows[b]) (row stride
+  // ldq / ldo), 1 <= vr_rows[b] <= TD_MAX_VERIFY_ROWS (clamped by the kernels), row j sees keys [0, vr_len0[b] + j) of cache slot vr_slot[b]
+  const int* vr_row0 = nullptr; const int* vr_rows = nullptr; const int* vr_len0 = nullptr; const int* vr_slot = nullptr;
+  int vr_tmax = 8;      // rows per sequence the launch is laid out for (filled by the launcher from its t_max): vr_rows[b] is clamped to 1..vr_tmax
   // decode kernel only: an e4m3 KV cache (K8 != null; K / V are then unused).  K8 / V8 [batch][Skv, ldkv] hold OCP e4m3 BYTES -- ldkv and kv_bstride count
   // bytes in this form -- and k_scale / v_scale [batch][Skv, lds] the power-of-two scale 2^e of every (row, kv head) (s_bstride floats between sequences):
   // the format td_kv_quant_rows_launch writes.  The kernel converts with the scale inside the conversion, so q.k and p.v see the bf16 values q 2^e exactly:
@@ -177,6 +181,14 @@ int td_attn_fp8_launch(const TdAttnParams& p, hipStream_t stream);
 int td_attn_launch(const TdAttnParams& p, hipStream_t stream);
 // Sq = 1 (KV-cached decode) form, csrc/attention_decode.hip; td_attn_launch routes to it
 int td_attn_decode_launch(const TdAttnParams& p, hipStream_t stream);
+// Multi-row decode attention (a speculative step's verify pass; csrc/attention_decode.hip): the vr_* layout of TdAttnParams, both cache forms.  t_max: the
+// largest vr_rows[b] the caller vouches for (TD_MAX_VERIFY_ROWS when it cannot: the arrays are device memory); vr_rows[b] is clamped to 1..t_max, so a
+// sequence never gets more rows than the grid was laid out for.  p.Skv: the longest visible length where the caller knows it (0 otherwise): routing only.
+// td_attention_verify_set_form: 0 automatic, 1 one workgroup per row, 2 the multi-row kernel.
+#ifndef TD_MAX_VERIFY_ROWS
+#define TD_MAX_VERIFY_ROWS 8
+#endif
+int td_attn_verify_launch(const TdAttnParams& p, int t_max, hipStream_t stream);
 // e4m3 KV-cache rows (csrc/attention_decode.hip; the layout of TdAttnParams::K8, the format of csrc/e4m3_pow2.h): every 128-wide head vector x of the
 // `rows` bf16 rows kv [rows, ld] (`heads` vectors per row) becomes its 128 bytes at q[dst, h 128 ..] and its scale 2^e at scale[dst, h],
 // dst = dst_rows[r] (device ints) or r.  kv_hat (may be null, may alias kv; row stride ld): x^ = q 2^e as bf16, exactly, at row r.  ldq in bytes, lds in floats.

@@ -995,6 +995,55 @@ void beam_select(const at::Tensor& top_ids, const at::Tensor& top_lp, const at::
                     (int32_t*)copy_src.data_ptr(), (int32_t*)parent.data_ptr(), (int32_t*)fin_flag.data_ptr(), (float*)fin_cum.data_ptr(), stream_of(top_ids)));
 }
 
+// multi-row decode attention (td_attention_verify): q bf16 [R, Hq 128] (row stride free), the cache as k / v bf16 [slots, S, >= Hkv 128] views, or -- k_scale
+// given -- k / v uint8 planes with k_scale / v_scale fp32 [slots, S, >= Hkv]; the four per-sequence int32 device tensors [n_seq] -> o bf16 [R, Hq 128]
+at::Tensor attention_verify(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const c10::optional<at::Tensor>& k_scale,
+                            const c10::optional<at::Tensor>& v_scale, const at::Tensor& seq_row0, const at::Tensor& seq_rows, const at::Tensor& seq_len0,
+                            const at::Tensor& seq_slot, int64_t Hq, int64_t Hkv, double scale) {
+  TORCH_CHECK(q.is_cuda(), "thinkdiff_hip: q must live on the GPU");
+  const bool kv8 = k_scale.has_value();
+  TORCH_CHECK(kv8 == v_scale.has_value(), "thinkdiff_hip::attention_verify: k_scale and v_scale come together (the e4m3 cache) or not at all (bf16)");
+  TORCH_CHECK(q.dim() == 2 && q.scalar_type() == at::kBFloat16 && q.stride(1) == 1, "thinkdiff_hip::attention_verify: q must be bf16 [R, Hq x 128] with unit column stride");
+  const auto kvt = kv8 ? at::kByte : at::kBFloat16;
+  TORCH_CHECK(k.dim() == 3 && v.dim() == 3 && k.scalar_type() == kvt && v.scalar_type() == kvt && k.stride(2) == 1 && k.strides() == v.strides() && k.sizes() == v.sizes() &&
+                  k.device() == q.device() && v.device() == q.device(),
+              "thinkdiff_hip::attention_verify: k and v must be [slots, S, Hkv x 128] views of one shape and stride on q's device, bf16, or uint8 with scales");
+  const int64_t n = seq_row0.numel();
+  for (const at::Tensor* t : {&seq_row0, &seq_rows, &seq_len0, &seq_slot})
+    TORCH_CHECK(t->device() == q.device() && t->scalar_type() == at::kInt && t->is_contiguous() && t->numel() == n,
+                "thinkdiff_hip::attention_verify: seq_row0, seq_rows, seq_len0 and seq_slot must be contiguous int32 tensors of one length on q's device");
+  const float *ks = nullptr, *vs = nullptr;
+  int64_t lds = 0, sb = 0;
+  if (kv8) {
+    TORCH_CHECK(k_scale->dim() == 3 && k_scale->scalar_type() == at::kFloat && v_scale->scalar_type() == at::kFloat && k_scale->stride(2) == 1 &&
+                    k_scale->strides() == v_scale->strides() && k_scale->device() == q.device() && v_scale->device() == q.device(),
+                "thinkdiff_hip::attention_verify: k_scale and v_scale must be fp32 [slots, S, Hkv] views of one stride on q's device");
+    ks = (const float*)k_scale->data_ptr(); vs = (const float*)v_scale->data_ptr(); lds = k_scale->stride(1); sb = k_scale->stride(0);
+  }
+  DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({q.size(0), Hq * 128}, q.options());
+  ok(td_attention_verify(q.data_ptr(), q.stride(0), kv8 ? nullptr : k.data_ptr(), kv8 ? nullptr : v.data_ptr(), k.stride(1), k.stride(0), kv8 ? k.data_ptr() : nullptr,
+                         kv8 ? v.data_ptr() : nullptr, ks, vs, lds, sb, o.data_ptr(), o.stride(0), (int)n, (const int32_t*)seq_row0.data_ptr(),
+                         (const int32_t*)seq_rows.data_ptr(), (const int32_t*)seq_len0.data_ptr(), (const int32_t*)seq_slot.data_ptr(), (int)Hq, (int)Hkv, (float)scale,
+                         stream_of(q)));
+  return o;
+}
+
+// the accept rule of speculative decoding (td_spec_accept): sampled / fed int32 [R], seq_row0 / seq_rows int32 [B] -> (n_emit int32 [B], emit int32 [B, 8])
+std::tuple<at::Tensor, at::Tensor> spec_accept(const at::Tensor& sampled, const at::Tensor& fed, const at::Tensor& seq_row0, const at::Tensor& seq_rows) {
+  TORCH_CHECK(sampled.is_cuda(), "thinkdiff_hip: sampled must live on the GPU");
+  const int64_t B = seq_row0.numel();
+  for (const at::Tensor* t : {&sampled, &fed, &seq_row0, &seq_rows})
+    TORCH_CHECK(t->device() == sampled.device() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                "thinkdiff_hip::spec_accept: sampled, fed, seq_row0 and seq_rows must be contiguous int32 tensors on one device");
+  TORCH_CHECK(fed.numel() == sampled.numel() && seq_rows.numel() == B, "thinkdiff_hip::spec_accept: sampled / fed and seq_row0 / seq_rows must pair up in length");
+  DeviceGuard guard(sampled.device());
+  at::Tensor n_emit = at::empty({B}, sampled.options()), emit = at::empty({B, TD_MAX_VERIFY_ROWS}, sampled.options());
+  ok(td_spec_accept((const int32_t*)sampled.data_ptr(), (const int32_t*)fed.data_ptr(), (const int32_t*)seq_row0.data_ptr(), (const int32_t*)seq_rows.data_ptr(), (int)B,
+                    (int32_t*)n_emit.data_ptr(), (int32_t*)emit.data_ptr(), stream_of(sampled)));
+  return {n_emit, emit};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(thinkdiff_hip, m) {
@@ -1055,6 +1104,8 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("linear_w4(Tensor x, Tensor packed, Tensor scales, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
   m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
   m.def("kv_gather_rows(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()");
+  m.def("attention_verify(Tensor q, Tensor k, Tensor v, Tensor? k_scale, Tensor? v_scale, Tensor seq_row0, Tensor seq_rows, Tensor seq_len0, Tensor seq_slot, int Hq, int Hkv, float scale) -> Tensor");
+  m.def("spec_accept(Tensor sampled, Tensor fed, Tensor seq_row0, Tensor seq_rows) -> (Tensor, Tensor)");
   m.def("beam_select(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()");
 }
 
@@ -1113,6 +1164,8 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("kv_fork_rows", &kv_fork_rows);
   m.impl("kv_gather_rows", &kv_gather_rows);
   m.impl("beam_select", &beam_select);
+  m.impl("attention_verify", &attention_verify);
+  m.impl("spec_accept", &spec_accept);
 }
 
 TORCH_LIBRARY_IMPL(thinkdiff_hip, CompositeExplicitAutograd, m) {

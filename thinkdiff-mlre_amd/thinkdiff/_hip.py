@@ -205,6 +205,11 @@ def _declare(L):
         "td_kv_gather_rows": [vp, i32, i32, vp, vp, vp, vp],
         "td_qwen2_gather_slots": [vp, i32, vp, vp, vp, vp],
         "td_beam_select": [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "td_attention_verify": [vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, i32, i32, f32, vp],
+        "td_attention_verify_set_form": [i32],
+        "td_attention_verify_ex": [vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp, i64, i32, vp, vp, vp, vp, i32, i32, f32, i32, i32, vp],
+        "td_qwen2_verify_batch_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "td_spec_accept": [vp, vp, vp, vp, i32, vp, vp, vp],
         "td_qwen2_decode_batch": [vp, i32, vp, vp, vp, vp, vp, vp],
         "td_qwen2_decode_batch_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_quantize_weights": [vp, i32, vp],
@@ -814,6 +819,64 @@ def beam_select(top_ids, top_lp, cum_in, rank_in, W, n_in, eos=-1, out=None):
     check(lib().td_beam_select(ptr(top_ids), ptr(top_lp), int(cap), ptr(cum_in), ptr(rank_in), rows // W, W, int(n_in), int(eos), *[ptr(t) for t in out],
                                stream_ptr()))
     return tuple(out)
+
+
+MAX_VERIFY_ROWS = 8        # TD_MAX_VERIFY_ROWS
+
+
+def _seq_ints(t, n, what, dev):
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != n or t.device != dev:
+        raise ThinkDiffHipError(f"{what} must be a contiguous int32 tensor of {n} entries on {dev}")
+    return t
+
+
+def attention_verify(q, cache, seq_row0, seq_rows, seq_len0, seq_slot, Hq, Hkv, scale=None, out=None, t_max=None, max_len=None):
+    """td_attention_verify: multi-row decode attention.  q bf16 [R, >= Hq*128]; `cache` = (k, v) bf16 [slots, S, >= Hkv*128] views of one cache, or
+    (k8, v8, k_scale, v_scale) for the e4m3 form (uint8 [slots, S, >= Hkv*128], fp32 [slots, S, >= Hkv]); the four per-sequence int32 device tensors
+    [n_seq]: first q row, rows (1..8), keys visible to the first row, cache slot.  -> out bf16 [R, Hq*128]; rows no sequence owns are left alone.
+    t_max / max_len: what the host knows of seq_rows' maximum and of the longest visible length (td_attention_verify_ex; None: 8 rows, length unknown)."""
+    dev, n = q.device, seq_row0.numel()
+    if not (q.dim() == 2 and q.dtype == torch.bfloat16 and q.stride(1) == 1):
+        raise ThinkDiffHipError("attention_verify: q must be a bf16 [R, Hq*128] tensor with unit column stride")
+    for name, t in (("seq_row0", seq_row0), ("seq_rows", seq_rows), ("seq_len0", seq_len0), ("seq_slot", seq_slot)):
+        _seq_ints(t, n, f"attention_verify: {name}", dev)
+    if len(cache) not in (2, 4):
+        raise ThinkDiffHipError(f"attention_verify: cache holds {len(cache)} tensors: (k, v) or (k8, v8, k_scale, v_scale)")
+    k, v = cache[0], cache[1]
+    want = torch.bfloat16 if len(cache) == 2 else torch.uint8
+    if not (k.dim() == 3 and k.dtype == want and v.dtype == want and k.stride(2) == 1 and k.stride() == v.stride() and k.shape == v.shape):
+        raise ThinkDiffHipError(f"attention_verify: the k and v planes must be {want} [slots, S, Hkv*128] views that share shape and strides")
+    if out is None:
+        out = torch.empty((q.shape[0], Hq * 128), dtype=torch.bfloat16, device=dev)
+    if scale is None:
+        scale = 128 ** -0.5
+    if len(cache) == 2:
+        args = (ptr(k), ptr(v), k.stride(1), k.stride(0), None, None, None, None, 0, 0)
+    else:
+        ks, vs = cache[2], cache[3]
+        if not (ks.dim() == 3 and ks.dtype == torch.float32 and vs.dtype == torch.float32 and ks.stride(2) == 1 and ks.stride() == vs.stride()):
+            raise ThinkDiffHipError("attention_verify: k_scale and v_scale must be fp32 [slots, S, Hkv] views that share their strides")
+        args = (None, None, k.stride(1), k.stride(0), ptr(k), ptr(v), ptr(ks), ptr(vs), ks.stride(1), ks.stride(0))
+    check(lib().td_attention_verify_ex(ptr(q), q.stride(0), *args, ptr(out), out.stride(0), n, ptr(seq_row0), ptr(seq_rows), ptr(seq_len0), ptr(seq_slot),
+                                       int(Hq), int(Hkv), float(scale), MAX_VERIFY_ROWS if t_max is None else int(t_max), 0 if max_len is None else int(max_len),
+                                       stream_ptr()))
+    return out
+
+
+def spec_accept(sampled, fed, seq_row0, seq_rows, out=None):
+    """td_spec_accept: sampled / fed int32 [R] (the token sampled from each row's logits, the token fed as that row), seq_row0 / seq_rows int32 [B]
+    -> (n_emit int32 [B], emit int32 [B, 8]): per sequence the sampled tokens up to and including the first whose guess behind it was wrong; -1 beyond."""
+    dev, B = sampled.device, seq_row0.numel()
+    _seq_ints(sampled, sampled.numel(), "spec_accept: sampled", dev)
+    _seq_ints(fed, sampled.numel(), "spec_accept: fed", dev)
+    _seq_ints(seq_row0, B, "spec_accept: seq_row0", dev)
+    _seq_ints(seq_rows, B, "spec_accept: seq_rows", dev)
+    if out is None:
+        out = (torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, MAX_VERIFY_ROWS, dtype=torch.int32, device=dev))
+    _seq_ints(out[0], B, "spec_accept: n_emit", dev)
+    _seq_ints(out[1], B * MAX_VERIFY_ROWS, "spec_accept: emit", dev)
+    check(lib().td_spec_accept(ptr(sampled), ptr(fed), ptr(seq_row0), ptr(seq_rows), B, ptr(out[0]), ptr(out[1]), stream_ptr()))
+    return out
 
 
 class TdVaeConfig(ctypes.Structure):

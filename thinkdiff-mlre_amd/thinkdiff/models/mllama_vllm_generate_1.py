@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 
 from .base_model import BaseModel
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
 
 
 @registry.register_model("mllama-vllm-generate-1")
@@ -50,6 +50,11 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
             **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
         # vllm_config["beam_width"]: generation goes through Qwen2VLTextEngine.beam_search (vLLM's LLM.beam_search) and output 0, the best beam, is consumed
         self.mllama_beam_params = beam_params_from_vllm_config(vc, max_tokens=self.mllama_sampling_params.max_tokens, ignore_eos=self.mllama_sampling_params.ignore_eos)
+        # vllm_config["speculative_config"] (method "ngram"): the generate calls run under speculative decoding; refused beside beam search
+        self.mllama_speculative = speculative_params_from_vllm_config(vc)
+        if self.mllama_speculative is not None and self.mllama_beam_params is not None:
+            raise ValueError(f"vllm_config speculative_config together with beam_width={self.mllama_beam_params.beam_width}: speculation under beam search is not built")
+        self._spec_kw = {} if self.mllama_speculative is None else {"speculative": self.mllama_speculative}
         self.mllama_tokenizer, self.mllama_processor = tokenizer, None
         self.visual, self.image_processor, self.image_token_id = None, None, 151655
         self.request_builder = request_builder
@@ -124,7 +129,7 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
                         yield reqs
                 all_outs = self.mllama.generate_continuous(chunk_source(), self.mllama_sampling_params, eos_token_id=self.eos_token_id, generator=generator,
                                                            max_live=self.decode_batch,
-                                                           admit_min=int(os.environ["TD_CONTINUOUS_ADMIT_MIN"]) if os.environ.get("TD_CONTINUOUS_ADMIT_MIN") else None)
+                                                           admit_min=int(os.environ["TD_CONTINUOUS_ADMIT_MIN"]) if os.environ.get("TD_CONTINUOUS_ADMIT_MIN") else None, **self._spec_kw)
             else:
                 fut = pool.submit(self._requests_on_side_stream, mllama_inputs, chunks[0]) if prefetch else None
                 for k, idx in enumerate(chunks):
@@ -137,7 +142,7 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
                     if beam is not None:
                         all_outs.extend(self.mllama.beam_search(reqs, beam, eos_token_id=self.eos_token_id))
                         continue
-                    all_outs.extend(self.mllama.generate_batch(reqs, self.mllama_sampling_params, eos_token_id=self.eos_token_id, generator=generator))
+                    all_outs.extend(self.mllama.generate_batch(reqs, self.mllama_sampling_params, eos_token_id=self.eos_token_id, generator=generator, **self._spec_kw))
         finally:
             if pool is not None:
                 pool.shutdown(wait=True)      # (also when a chunk raised: the helper thread does not outlive the call)

@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import HipVisionProjector
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
 
 SYSTEM_PROMPT = "You are a helpful assistant."   # reference :1048
 NUM_SYSTEM_TOKENS = 14                            # reference :1107-1109 ("input_no_system" drops the first 14)
@@ -53,6 +53,11 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
             **sampler_fields_from_vllm_config(vc)).validate()      # top_k, min_p, the penalties, seed (td_sample_rows_bf16); logit_bias, allowed_token_ids, bad_words_token_ids, mask_stop_below_min_tokens (its edit form), logprobs; n, best_of (forked cache slots)
         # vllm_config["beam_width"]: generation goes through Qwen2VLTextEngine.beam_search (vLLM's LLM.beam_search) and output 0, the best beam, is consumed
         self.mllama_beam_params = beam_params_from_vllm_config(vc, max_tokens=self.mllama_sampling_params.max_tokens, ignore_eos=self.mllama_sampling_params.ignore_eos)
+        # vllm_config["speculative_config"] (method "ngram"): the generate calls run under speculative decoding; refused beside beam search
+        self.mllama_speculative = speculative_params_from_vllm_config(vc)
+        if self.mllama_speculative is not None and self.mllama_beam_params is not None:
+            raise ValueError(f"vllm_config speculative_config together with beam_width={self.mllama_beam_params.beam_width}: speculation under beam search is not built")
+        self._spec_kw = {} if self.mllama_speculative is None else {"speculative": self.mllama_speculative}
         self.eos_token_id = vc.get("eos_token_id", None)
         self.mm_projector = HipVisionProjector(self.config.mm_hidden_size, hidden_size, mm_projector_type, device=device, fp32_norm=True)
         self.mllama_tokenizer, self.mllama_processor = tokenizer, processor
@@ -107,12 +112,12 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
             for c0 in range(0, len(reqs), per):
                 chunk = reqs[c0:c0 + per]
                 forced = None if forced_output_ids is None else list(forced_output_ids[c0:c0 + per])
-                outs.extend(self.mllama.generate_batch(chunk, sp, generator=generator, forced_output_ids=forced))
+                outs.extend(self.mllama.generate_batch(chunk, sp, generator=generator, forced_output_ids=forced, **self._spec_kw))
         else:
             for i, r in enumerate(reqs):
                 forced = None if forced_output_ids is None else forced_output_ids[i]
                 outs.append(self.mllama.generate(list(r["prompt_token_ids"]), sp, position_ids=r.get("position_ids"),
-                                                 inputs_embeds=r.get("inputs_embeds"), generator=generator, forced_output_ids=forced))
+                                                 inputs_embeds=r.get("inputs_embeds"), generator=generator, forced_output_ids=forced, **self._spec_kw))
         inp = [o["prompt_hidden_states"] for o in outs]
         out = [o["hidden_states"] for o in outs]
         if embedding_type == "both":

@@ -230,6 +230,113 @@ def beam_params_from_vllm_config(vc, max_tokens: int = 128, ignore_eos: bool = F
                             length_penalty=vc["length_penalty"] if vc.get("length_penalty") is not None else 1.0).validate()
 
 
+SPECULATIVE_CONFIG_KEYS = ("method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min")
+
+
+@dataclasses.dataclass
+class SpeculativeConfig:
+    """vLLM's `speculative_config` for the one method served, "ngram" (prompt lookup): up to num_speculative_tokens guessed tokens per sequence and step,
+    found by matching the last prompt_lookup_min .. prompt_lookup_max tokens against the sequence's own past (ngram_propose).  A step then verifies the
+    guesses of every live sequence in ONE pass over the weights (td_qwen2_verify_batch_slots) and keeps the sampled tokens up to the first wrong guess
+    (td_spec_accept): the tokens are the target model's own draws, a guess only saves passes."""
+    method: str = "ngram"
+    num_speculative_tokens: int = 3
+    prompt_lookup_max: int = 4
+    prompt_lookup_min: int = 1
+
+    def validate(self) -> "SpeculativeConfig":
+        def bad(field, why):
+            raise ValueError(f"SpeculativeConfig.{field}={getattr(self, field)!r}: {why}")
+
+        def integer(v):
+            return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+        if self.method != "ngram":
+            bad("method", 'only "ngram" (prompt lookup) is served: a draft model, EAGLE and Medusa are not built')
+        if not (integer(self.num_speculative_tokens) and 1 <= self.num_speculative_tokens <= _hip.MAX_VERIFY_ROWS - 1):
+            bad("num_speculative_tokens", f"must be an integer in [1, {_hip.MAX_VERIFY_ROWS - 1}] (a verify step takes {_hip.MAX_VERIFY_ROWS} rows per sequence)")
+        if not (integer(self.prompt_lookup_min) and self.prompt_lookup_min >= 1):
+            bad("prompt_lookup_min", "must be an integer >= 1")
+        if not (integer(self.prompt_lookup_max) and self.prompt_lookup_max >= self.prompt_lookup_min):
+            bad("prompt_lookup_max", f"must be an integer >= prompt_lookup_min={self.prompt_lookup_min}")
+        return self
+
+
+def speculative_params_from_vllm_config(vc) -> Optional[SpeculativeConfig]:
+    """The SpeculativeConfig a vllm_config asks for with `speculative_config` (None without it).  Any method but "ngram" and any key but
+    SPECULATIVE_CONFIG_KEYS is a ValueError naming it: a setting is refused, never ignored."""
+    sc = vc.get("speculative_config")
+    if sc is None:
+        return None
+    if not hasattr(sc, "items"):
+        raise ValueError(f"vllm_config speculative_config={sc!r}: must be a dict with the keys {SPECULATIVE_CONFIG_KEYS}")
+    if sc.get("method", "ngram") != "ngram":
+        raise ValueError(f"vllm_config speculative_config method={sc.get('method')!r}: only \"ngram\" is served")
+    unknown = sorted(set(sc) - set(SPECULATIVE_CONFIG_KEYS))
+    if unknown:
+        raise ValueError(f"vllm_config speculative_config sets {unknown}: only {SPECULATIVE_CONFIG_KEYS} are served")
+    return SpeculativeConfig(**{k: v for k, v in sc.items() if v is not None}).validate()
+
+
+def ngram_propose(tokens, n_min: int, n_max: int, k: int) -> np.ndarray:
+    """Prompt lookup, the project's statement of the rule (it restates what vLLM's `NgramProposer` computes in `_find_longest_matched_ngram_and_propose_tokens`;
+    vLLM itself is not a dependency): take the LONGEST suffix of `tokens`, of length n_max down to n_min, that also occurs earlier in `tokens` (an
+    occurrence may overlap the suffix but not be it); of that length use the EARLIEST occurrence; return the up to k tokens that followed it.  Nothing
+    matches, or n_min > len(tokens) - 1: an empty array."""
+    t = np.asarray(tokens, dtype=np.int64).reshape(-1)
+    L = t.size
+    if k <= 0:
+        return np.empty(0, dtype=np.int32)
+    for n in range(min(int(n_max), L - 1), int(n_min) - 1, -1):
+        if n < 1:
+            break
+        suffix = t[L - n:]
+        win = np.lib.stride_tricks.sliding_window_view(t[:L - 1], n)      # windows starting at 0 .. L-1-n: every occurrence but the suffix itself
+        hit = np.nonzero((win == suffix).all(axis=1))[0]
+        if hit.size:
+            s0 = int(hit[0]) + n
+            return t[s0:s0 + int(k)].astype(np.int32)
+    return np.empty(0, dtype=np.int32)
+
+
+class NgramDraftSource:
+    """The draft source of SpeculativeConfig(method="ngram").  A draft source is anything with `propose(token_ids, k) -> ids`: token_ids is a sequence's
+    prompt and everything chosen so far (the token about to be fed included), ids up to k guesses for what follows."""
+
+    def __init__(self, config: SpeculativeConfig):
+        self.config = config.validate()
+        self.k = int(config.num_speculative_tokens)
+
+    def propose(self, token_ids, k):
+        return ngram_propose(token_ids, self.config.prompt_lookup_min, self.config.prompt_lookup_max, min(int(k), self.k))
+
+
+def _draft_source(speculative, what):
+    if speculative is None:
+        return None
+    if isinstance(speculative, SpeculativeConfig):
+        return NgramDraftSource(speculative)
+    if callable(getattr(speculative, "propose", None)):
+        return speculative
+    raise ValueError(f"{what}: speculative={speculative!r} must be a SpeculativeConfig or a draft source with propose(token_ids, k)")
+
+
+def _check_speculative(what, sps, forced):
+    """Speculation serves plain sampling only; everything else is refused by name before any GPU work."""
+    if forced is not None:
+        raise ValueError(f"{what}: speculative= together with forced_output_ids: a teacher-forced continuation has nothing to guess")
+    for sp in sps:
+        if sp.has_penalty:
+            raise ValueError(f"{what}: speculative= together with a penalty (repetition_penalty / presence_penalty / frequency_penalty): the history "
+                             "would have to hold the guessed tokens; not built")
+        if sp.has_edit:
+            raise ValueError(f"{what}: speculative= together with a logit edit (logit_bias / allowed_token_ids / bad_words_token_ids / "
+                             "mask_stop_below_min_tokens): not built")
+        if sp.logprobs is not None:
+            raise ValueError(f"{what}: speculative= together with logprobs={sp.logprobs}: not built")
+        if sp.width > 1:
+            raise ValueError(f"{what}: speculative= together with n={sp.n}, best_of={sp.best_of}: not built")
+
+
 Logprob = collections.namedtuple("Logprob", ["logprob", "rank"])      # vLLM's Logprob, without the decoded text
 
 
@@ -468,8 +575,12 @@ class _TokenSource:
     sampler key, and the logprobs of what was chosen (_LogprobLog).  sp_of(s): the SamplingParams of sequence s; forced[s]: its forced ids (None: the
     call samples); want: SamplingParams.logprobs per sequence, one int for every sequence, or None when nobody asked."""
 
-    def __init__(self, engine, sampling, by_rows, sp_of, eos_token_id, generator, forced, want):
+    def __init__(self, engine, sampling, by_rows, sp_of, eos_token_id, generator, forced, want, draft=None):
         self.engine, self.sampling, self.sp_of, self.forced = engine, sampling, sp_of, forced
+        self.draft = draft      # speculative decoding: the draft source (None: every step is one token per sequence, exactly as before)
+        self.spec_table = None
+        if draft is not None:
+            engine._spec_stats = dict(steps=0, drafted=0, accepted=0, emitted=0)
         self.key = None if forced is not None else engine._draw_sampler_key(generator)
         self.rows = _RowSampling(engine, self.key, eos_token_id) if by_rows and forced is None else None      # (forced decoding does not sample and keeps no history)
         self.lplog = _LogprobLog(engine, want) if want is not None else None      # (forced tokens are scored too)
@@ -503,6 +614,22 @@ class _TokenSource:
             self.lplog.add(logits, tok, owners)
         return tok, host
 
+    def spec_sample(self, logits, owners, live_of_row, offsets):
+        """Speculative decoding: one sampler launch (td_sample_rows_bf16) over rows that belong to live sequences live_of_row[r] (several rows per
+        sequence in a verify step).  A seeded sequence draws token number g at (seed, g, 0), as on the plain path; the others at (the call's key, g,
+        sequence index) -- NOT the plain path's (key, step, live row): a step no longer emits one token per sequence, so the step does not name a
+        token.  offsets[r]: the number g of the token row r's logits choose."""
+        if self.live_changed or self.spec_table is None:
+            recs = []
+            for o in owners:
+                sp = self.sp_of(int(o))
+                recs.append(dict(temperature=sp.temperature, top_p=sp.top_p, min_p=sp.min_p, top_k=sp.top_k, slot=-1,
+                                 stream=0 if sp.seed is not None else int(o), seed=sp.seed if sp.seed is not None else self.key))
+            self.spec_table = _hip.pack_sample_rows(recs)
+            self.live_changed = False
+        table = self.spec_table if len(live_of_row) == len(owners) else self.spec_table.index_select(0, torch.from_numpy(np.asarray(live_of_row, dtype=np.int64)))
+        return _OPS.sample_rows(logits, table.to(self.engine.device), torch.from_numpy(np.asarray(offsets, dtype=np.int64)).to(self.engine.device), None, False)
+
     def finish(self, res):
         """res[s]["logprobs"] and ["cumulative_logprob"] of the sequences that asked: present only then."""
         if self.lplog is not None:
@@ -528,6 +655,10 @@ class _LiveRows:
         self.engine, self.src, self.eos = engine, source, eos_token_id
         self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint = (np.zeros(capacity, dtype=np.int32) for _ in range(7))
         self.stops = np.empty(capacity, dtype=object)
+        # speculative decoding (source.draft): per live row the token chosen but not yet fed (-1: none, its next-token logits are in self.logits) and
+        # the prompt + every token chosen so far, which the draft source reads
+        self.pend = np.full(capacity, -1, dtype=np.int32)
+        self.hist = np.empty(capacity, dtype=object)
         self.n, self.step_no, self.any_stop = 0, 0, False
         self.logits = torch.empty(capacity, engine.config.vocab_size, dtype=torch.bfloat16, device=engine.device)
         self.step_hid, self.step_owner, self.step_toks = [], [], []
@@ -563,8 +694,11 @@ class _LiveRows:
         self.ngen[n:m] = 0
         self.lim[n:m] = [budgets[rep[r]] for r in live]
         self.mint[n:m] = [sps[r].min_tokens for r in live]
+        self.pend[n:m] = -1
         for i, r in zip(range(n, m), live):      # (forced ids run to their end: no stop rule)
             sp = sps[r]
+            if self.src.draft is not None:
+                self.hist[i] = [int(t) for t in prompts[rep[r]]]
             self.stops[i] = set() if self.src.forced is not None else \
                 set(sp.stop_token_ids or []) | ({self.eos} if not sp.ignore_eos and self.eos is not None else set())
             self.any_stop |= bool(self.stops[i])
@@ -573,10 +707,17 @@ class _LiveRows:
     def step(self):
         """One token for every live sequence: choose it, decode it (one pass over the weights, td_qwen2_decode_batch_slots), apply the stop rule
         and close the gaps of the finished rows (the order of the others is kept: no cache rows move).  -> the freed cache slots, highest first."""
+        if self.src.draft is not None:
+            return self._spec_step()
         n, dev = self.n, self.engine.device
         tok_dev, toks = self.src.next(self.logits[:n], self.step_no, self.ngen[:n], self.own[:n], self.slt[:n])
         if toks is None:
             toks = tok_dev.cpu().numpy()      # (the host sees the ids once per step, for the stop rule and the results)
+        return self._feed_one(tok_dev, toks)
+
+    def _feed_one(self, tok_dev, toks):
+        """The plain step behind the choice of its tokens: decode one token per live sequence, stop rule, retire."""
+        n, dev = self.n, self.engine.device
         pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(self.npos[:n], (3, n)))).to(dev)
         hid = torch.empty(n, self.engine.config.hidden_size, dtype=torch.bfloat16, device=dev)
         self.engine._decode_slots(n, self.slt, tok_dev, pos_dev, self.clen, hid, self.logits)      # logits of row i -> logits[i]
@@ -591,18 +732,99 @@ class _LiveRows:
         if self.any_stop:
             hit = np.fromiter((int(t) in s for t, s in zip(toks, self.stops[:n])), dtype=bool, count=n)
             done |= hit & (self.ngen[:n] >= self.mint[:n])
+        return self._retire(done)
+
+    def _retire(self, done):
+        """Close the gaps of the finished rows.  -> the freed cache slots, highest first."""
+        n, dev = self.n, self.engine.device
         if not done.any():
             return []
         keep = np.nonzero(~done)[0]
         freed = sorted((int(x) for x in self.slt[:n][done]), reverse=True)
         k = keep.size
-        for arr in (self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint, self.stops):
+        for arr in (self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint, self.stops, self.pend, self.hist):
             arr[:k] = arr[:n][keep]
         if k:
             self.logits[:k] = self.logits[:n].index_select(0, torch.from_numpy(keep).to(dev))
         self.src.live_changed = True
         self.n = k
         return freed
+
+    def _spec_step(self):
+        """The step under speculative decoding.  Every live sequence holds one chosen-but-unfed token (drawn here from its next-token logits where it
+        has none), the draft source guesses what follows, and ONE pass over the weights feeds [that token | guesses] of every sequence
+        (td_qwen2_verify_batch_slots).  All rows are sampled in one launch, td_spec_accept keeps the samples up to the first wrong guess, the host reads
+        (n_emit, emit) once.  Row 0 and the rows of the accepted guesses were computed on a true prefix: their hidden states and tokens are the
+        sequence's, token by token under the stop rule; the last emitted sample is the next step's unfed token.  Rejected rows stay in the cache and
+        are overwritten by the next step.  A step in which nobody has a guess is the plain step."""
+        n, dev, eng, src = self.n, self.engine.device, self.engine, self.src
+        stats = eng._spec_stats
+        need = self.pend[:n] < 0
+        if need.any():
+            t0 = src.spec_sample(self.logits[:n], self.own[:n], np.arange(n), self.ngen[:n]).cpu().numpy()
+            self.pend[:n] = np.where(need, t0, self.pend[:n])
+        # guesses: at most the token budget less the unfed token, the slot's free rows less one, 7, and what keeps the step inside 256 rows
+        row_cap = eng.MAX_BATCH // n - 1
+        drafts = []
+        for i in range(n):
+            room = min(int(self.lim[i] - self.ngen[i]) - 1, eng.slot_len - int(self.clen[i]) - 1, _hip.MAX_VERIFY_ROWS - 1, row_cap)
+            d = []
+            if room > 0:
+                self.hist[i].append(int(self.pend[i]))
+                d = [int(t) for t in np.asarray(src.draft.propose(self.hist[i], room)).reshape(-1)[:room]]
+                self.hist[i].pop()
+            drafts.append(d)
+        stats["steps"] += 1
+        if not any(drafts):
+            toks = self.pend[:n].copy()
+            self.pend[:n] = -1
+            for i in range(n):
+                self.hist[i].append(int(toks[i]))
+            stats["emitted"] += n
+            return self._feed_one(torch.from_numpy(toks).to(dev), toks)
+        n_new = np.array([1 + len(d) for d in drafts], dtype=np.int32)
+        row0 = np.concatenate([[0], np.cumsum(n_new)[:-1]]).astype(np.int32)
+        R = int(n_new.sum())
+        fed = np.concatenate([[self.pend[i]] + drafts[i] for i in range(n)]).astype(np.int32)
+        live_of_row = np.repeat(np.arange(n), n_new)
+        within = np.arange(R) - row0[live_of_row]
+        pos = (self.npos[:n][live_of_row] + within).astype(np.int32)
+        fed_dev = torch.from_numpy(fed).to(dev)
+        pos_dev = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(pos, (3, R)))).to(dev)
+        hid = torch.empty(R, eng.config.hidden_size, dtype=torch.bfloat16, device=dev)
+        lg = torch.empty(R, eng.config.vocab_size, dtype=torch.bfloat16, device=dev)
+        eng._verify_slots(n, self.slt, n_new, fed_dev, pos_dev, self.clen, hid, lg)
+        sampled = src.spec_sample(lg, self.own[:n], live_of_row, self.ngen[:n][live_of_row] + 1 + within)
+        n_emit, emit = _OPS.spec_accept(sampled, fed_dev, torch.from_numpy(row0).to(dev), torch.from_numpy(n_new).to(dev))
+        got = torch.cat([n_emit.reshape(n, 1), emit.reshape(n, -1)], dim=1).cpu().numpy()      # (the step's one download)
+        done = np.zeros(n, dtype=bool)
+        rows_kept, owners_kept, toks_kept = [], [], []
+        for i in range(n):
+            a = int(got[i, 0]) - 1
+            stats["drafted"] += len(drafts[i])
+            stats["accepted"] += a
+            keep = 0
+            for j in range(a + 1):      # the fed tokens on a true prefix, one at a time as the plain loop would have met them
+                tok = int(fed[row0[i] + j])
+                keep += 1
+                g = int(self.ngen[i]) + keep
+                if g >= self.lim[i] or int(self.clen[i]) + keep >= eng.slot_len or (tok in self.stops[i] and g >= self.mint[i]):
+                    done[i] = True
+                    break
+            rows_kept.extend(range(int(row0[i]), int(row0[i]) + keep))
+            owners_kept.extend([int(self.own[i])] * keep)
+            toks_kept.extend(fed[row0[i]:row0[i] + keep].tolist())
+            self.hist[i].extend(fed[row0[i]:row0[i] + keep].tolist())
+            self.clen[i] += keep
+            self.npos[i] += keep
+            self.ngen[i] += keep
+            self.pend[i] = int(got[i, 1 + a])
+            stats["emitted"] += keep
+        self.step_hid.append(hid if len(rows_kept) == R else hid.index_select(0, torch.tensor(rows_kept, dtype=torch.int64).to(dev)))
+        self.step_owner.append(np.array(owners_kept, dtype=np.int32))
+        self.step_toks.append(np.array(toks_kept, dtype=np.int32))
+        self.step_no += 1
+        return self._retire(done)
 
     def results(self, res):
         """res[s]["hidden_states"] and ["token_ids"] of every sequence s (one gather: rows grouped by sequence, in step order inside a sequence),
@@ -886,6 +1108,25 @@ class Qwen2VLTextEngine:
                                                        _hip.ptr(hid), _hip.ptr(lg), _hip.stream_ptr()))
         return hid, lg
 
+    def verify_batch(self, token_ids, position_ids, cache_pos: Sequence[int], n_new: Sequence[int], slots: Optional[Sequence[int]] = None, want_logits=True):
+        """The verify step of speculative decoding (td_qwen2_verify_batch_slots): sequence b feeds n_new[b] tokens (1..8) at cache rows cache_pos[b] ..,
+        R = sum(n_new) rows, sequence after sequence.  token_ids [R], position_ids [3, R].  -> (hidden [R, hidden], logits [R, vocab] | None): row
+        (b, j) is what decode_batch returns for that token after the j tokens before it.  All R cache rows are written; the caller advances by what it
+        keeps."""
+        B, R = len(cache_pos), int(sum(int(v) for v in n_new))
+        tok = torch.as_tensor(token_ids, dtype=torch.int32).to(self.device).contiguous()
+        pos = torch.as_tensor(position_ids, dtype=torch.int32).to(self.device).contiguous()
+        if len(n_new) != B or tok.shape != (R,) or pos.shape != (3, R):
+            raise _hip.ThinkDiffHipError(f"verify_batch: {len(n_new)} n_new for {B} sequences, token_ids {tuple(tok.shape)} and position_ids {tuple(pos.shape)} for R={R} rows")
+        hid = torch.empty(R, self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
+        lg = torch.empty(R, self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if want_logits else None
+        cp = (ctypes.c_int * B)(*[int(c) for c in cache_pos])
+        nn = (ctypes.c_int * B)(*[int(c) for c in n_new])
+        sl = ctypes.cast((ctypes.c_int * B)(*[int(c) for c in slots]), ctypes.c_void_p) if slots is not None else None
+        _hip.check(self._L.td_qwen2_verify_batch_slots(self._h, B, sl, ctypes.cast(nn, ctypes.c_void_p), _hip.ptr(tok), _hip.ptr(pos),
+                                                       ctypes.cast(cp, ctypes.c_void_p), _hip.ptr(hid), _hip.ptr(lg), _hip.stream_ptr()))
+        return hid, lg
+
     # ---- multimodal prompt assembly ([ext] vLLM Qwen2-VL input processor + transformers Qwen2VLModel.get_rope_index) ----
     def embed_tokens(self, token_ids) -> torch.Tensor:
         """[n] ids -> bf16 [n, hidden] rows of model.embed_tokens."""
@@ -945,14 +1186,20 @@ class Qwen2VLTextEngine:
     @torch.no_grad()
     def generate(self, prompt_token_ids: Sequence[int], sampling: SamplingParams, position_ids=None, inputs_embeds=None,
                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 forced_output_ids: Optional[Sequence[int]] = None):
+                 forced_output_ids: Optional[Sequence[int]] = None, speculative=None):
         """Returns dict(prompt_hidden_states [n_prompt,D], hidden_states [n_gen,D], token_ids [n_gen]).
+        speculative: a SpeculativeConfig or a draft source -- the batch path then runs the one sequence (generate_batch).
 
         Sampling is temperature / top-p on the device.  `forced_output_ids` teacher-forces the continuation
         (the reference samples at T=0.6, so parity of the hidden states is checked on forced ids)."""
         sps, by_rows = _sampling_list(sampling, 1, "generate")
         if sps is not None:
             sampling = sps[0]
+        if speculative is not None:
+            _draft_source(speculative, "generate")
+            _check_speculative("generate", [sampling], forced_output_ids)
+            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds}], sampling,
+                                       eos_token_id=eos_token_id, generator=generator, speculative=speculative)[0]
         if sampling.width > 1:      # n / best_of: one prefill, k sequences on forked slots -- the batch path runs them
             if forced_output_ids is not None:
                 raise ValueError(f"generate: forced_output_ids with SamplingParams n={sampling.n}, best_of={sampling.best_of}: a teacher-forced "
@@ -1009,7 +1256,7 @@ class Qwen2VLTextEngine:
 
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[dict], sampling: SamplingParams, eos_token_id: Optional[int] = None,
-                       generator: Optional[torch.Generator] = None, forced_output_ids: Optional[Sequence[Sequence[int]]] = None):
+                       generator: Optional[torch.Generator] = None, forced_output_ids: Optional[Sequence[Sequence[int]]] = None, speculative=None):
         """`generate` for up to min(256, n_slots) requests together: each prompt is prefilled into its own cache slot, then
         every decode step advances all unfinished sequences in one pass over the weights (what vLLM's batching gives the
         reference's precompute job).  requests: dicts with "prompt_token_ids" and optional "position_ids" / "inputs_embeds".
@@ -1018,6 +1265,9 @@ class Qwen2VLTextEngine:
         sps, by_rows = _sampling_list(sampling, B, "generate_batch")
         if sps is None:
             sps = [sampling] * B
+        draft = _draft_source(speculative, "generate_batch")
+        if draft is not None:
+            _check_speculative("generate_batch", sps, forced)
         if B > self.max_seqs:
             raise _hip.ThinkDiffHipError(f"generate_batch: {B} requests exceed min({self.MAX_BATCH}, n_slots={self.n_slots}); call set_slots first")
         widths = [sp.width for sp in sps]      # n / best_of: request b runs as widths[b] sequences, each on a cache slot of its own
@@ -1033,7 +1283,7 @@ class Qwen2VLTextEngine:
         res = [{"prompt_hidden_states": None, "hidden_states": None, "token_ids": []} for _ in range(N)]
         poss = [self._positions(r) for r in requests]
         src = _TokenSource(self, sampling, by_rows, seq_sps.__getitem__, eos_token_id, generator, forced,
-                           [sp.logprobs for sp in seq_sps] if _LogprobLog.wanted(seq_sps) else None)
+                           [sp.logprobs for sp in seq_sps] if _LogprobLog.wanted(seq_sps) else None, draft)
         live = _LiveRows(self, N, src, eos_token_id)
         # request b is prefilled once, into slot b; the children take the slots from B up
         for b, h in enumerate(self._prefill_prompts(requests, list(range(B)), poss, live.logits[:B], padded_ok=True)):
@@ -1049,7 +1299,7 @@ class Qwen2VLTextEngine:
     @torch.no_grad()
     def generate_continuous(self, request_chunks, sampling: SamplingParams, eos_token_id: Optional[int] = None,
                             generator: Optional[torch.Generator] = None, forced_output_ids: Optional[Sequence[Sequence[int]]] = None,
-                            max_live: Optional[int] = None, admit_min: Optional[int] = None):
+                            max_live: Optional[int] = None, admit_min: Optional[int] = None, speculative=None):
         """Continuous batching ([ext] vLLM's scheduler behind the reference's `LLM.generate` of a whole loader batch, thinkdiff/models/
         mllama_vllm_generate_1.py:585 with `max_num_seqs: 256`): any number of requests against `max_live` (default min(256, n_slots)) cache slots.
         A sequence that finishes frees its slot at once -- nothing moves: a decode step names the slot of each of its rows
@@ -1071,6 +1321,9 @@ class Qwen2VLTextEngine:
         else:
             n_known = None      # chunks pulled lazily: a per-request list is checked against each chunk as it arrives
         sps_req, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
+        draft = _draft_source(speculative, "generate_continuous")
+        if draft is not None:
+            _check_speculative("generate_continuous", [sampling] if sps_req is None else sps_req, forced)
         # n / best_of: request i runs as k_of(i) SEQUENCES, numbered base_of(i) .. in arrival order of their requests (known in advance: one
         # SamplingParams per request, or one for all).  The live rows, `res` and the logprob log are per sequence; the waiting queue and `requests`
         # per request.  Without n / best_of a sequence IS its request.
@@ -1113,7 +1366,7 @@ class Qwen2VLTextEngine:
                 for _ in range(k_of(len(requests) - 1)):
                     res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
 
-        live = _LiveRows(self, max_live, _TokenSource(self, sampling, by_rows, sp_of, eos_token_id, generator, forced, want), eos_token_id)
+        live = _LiveRows(self, max_live, _TokenSource(self, sampling, by_rows, sp_of, eos_token_id, generator, forced, want, draft), eos_token_id)
         free_slots = list(range(max_live - 1, -1, -1))      # (a stack: the lowest free slot is taken first)
 
         def budget(i):      # tokens (each sequence of) request i may still produce
@@ -1178,6 +1431,17 @@ class Qwen2VLTextEngine:
     def _decode_slots(self, n, slots_np, tok_dev, pos_dev, cache_np, hid_out, logits_out):
         _hip.check(self._L.td_qwen2_decode_batch_slots(self._h, n, ctypes.c_void_p(slots_np.ctypes.data), _hip.ptr(tok_dev), _hip.ptr(pos_dev),
                                                        ctypes.c_void_p(cache_np.ctypes.data), _hip.ptr(hid_out), _hip.ptr(logits_out), _hip.stream_ptr()))
+
+    def _verify_slots(self, n, slots_np, n_new_np, tok_dev, pos_dev, cache_np, hid_out, logits_out):
+        """The verify step of speculative decoding: live row i feeds n_new_np[i] tokens (td_qwen2_verify_batch_slots)."""
+        _hip.check(self._L.td_qwen2_verify_batch_slots(self._h, n, ctypes.c_void_p(slots_np.ctypes.data), ctypes.c_void_p(n_new_np.ctypes.data), _hip.ptr(tok_dev),
+                                                       _hip.ptr(pos_dev), ctypes.c_void_p(cache_np.ctypes.data), _hip.ptr(hid_out), _hip.ptr(logits_out),
+                                                       _hip.stream_ptr()))
+
+    def spec_stats(self) -> dict:
+        """Of the last call with speculative=: steps (passes over the weights), drafted (guesses fed), accepted (guesses that matched the sampled
+        token), emitted (tokens the sequences advanced by).  Empty before the first such call."""
+        return dict(getattr(self, "_spec_stats", {}))
 
     def _fork_slots(self, src, dst_slots, length):
         """The fork of n / best_of admission: the `length` prompt rows of slot `src` to every slot of dst_slots (a method of its own beside the two

@@ -64,6 +64,9 @@ kv_gather_rows             row j of a launch takes the first n_rows[j] rows of t
                            cache slots behind a beam-search step, with no host round trip; in place, any dtype
 beam_select                one beam-search step on the device (vLLM's `LLM.beam_search` loop): the next W beams out of W x 2W candidates (logprobs_rows with
                            n_top = 2W), EOS candidates set aside as finishers, and a slot-stable placement whose copies kv_gather_rows does in one launch
+attention_verify / spec_accept   speculative decoding (vLLM's `speculative_config`, method "ngram"): the decode attention of a verify step -- up to 8 query rows per
+                           sequence, bf16 or e4m3 cache; through this op one workgroup per row, bit-equal to the single-row kernel (the multi-row kernel is
+                           routed by td_attention_verify_ex) -- and the accept rule: the sampled tokens up to the first wrong guess
 """
 import os
 
@@ -131,6 +134,9 @@ SCHEMAS = {
     "kv_gather_rows": "(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()",
     "beam_select": "(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, "
                    "Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()",
+    "attention_verify": "(Tensor q, Tensor k, Tensor v, Tensor? k_scale, Tensor? v_scale, Tensor seq_row0, Tensor seq_rows, Tensor seq_len0, Tensor seq_slot, int Hq, int Hkv, "
+                        "float scale) -> Tensor",
+    "spec_accept": "(Tensor sampled, Tensor fed, Tensor seq_row0, Tensor seq_rows) -> (Tensor, Tensor)",
 }
 
 _loaded = False
