@@ -1011,7 +1011,58 @@ int td_linear_split_w4_bf16(const void* x, int64_t ldx, const void* packed, cons
                             void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream);
 int td_linear_glu_w4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, void* y, int64_t ldy, int M, int I, int K, void* stream);
 
-enum { TD_QWEN2_WEIGHTS_BF16 = 0, TD_QWEN2_WEIGHTS_E4M3 = 1, TD_QWEN2_WEIGHTS_MXFP4 = 2 };
+/* ---- grouped int4 weight stream (td_abi_version() >= 22): AWQ / GPTQ checkpoints, loaded as they are --------------------------------------------------
+ * Format (fixed): asymmetric uint4 under ONE fp16 scale and ONE 4-bit zero point per group of G consecutive k of an output row of W[N, K]; G is 32, 64 or
+ * 128, K % G == 0 and K % 32 == 0:   q, z in 0 .. 15, s a finite fp16;   W^ = bf16_rne(fp32(q - z) * fp32(s)).
+ * q - z has at most 5 significant bits and s has 11: the product is exact in fp32, the rounding to bf16 is the ONLY rounding, and |W^| <= 15 * 65504 is
+ * finite in bf16 (an fp16 subnormal scale gives a normal bf16 magnitude).  So once more the quantised model is an ordinary bf16 model with weights W^:
+ * td_dequant_rows_int4 and the stream kernels apply the same rounding and agree bit for bit WITH EACH OTHER; against the formula they differ in one
+ * case that no value can show: a zero weight (q == z) under a negative scale is +0 here where the formula's product is -0.
+ * Storage: packed uint8 [N, K / 2], scales fp16 [N, K / G], zeros uint8 [N, K / G] (values 0 .. 15; only the low nibble is read), all dense.  The order of
+ * the nibbles inside `packed` belongs to the library (csrc/int4_group.h): packed bytes are made by td_repack_int4 and by nothing else. */
+enum { TD_INT4_AWQ = 0, TD_INT4_GPTQ = 1, TD_INT4_GPTQ_V2 = 2 /* flag, with TD_INT4_GPTQ: checkpoint_format "gptq_v2", zero points stored as they are */ };
+/* One checkpoint Linear -> the device layout, in one launch (all pointers device memory).
+ *   TD_INT4_AWQ, AutoAWQ version "GEMM": qweight int32 [K, N / 8], nibble p of column c = q[k, 8c + o[p]], o = {0, 2, 4, 6, 1, 3, 5, 7}; qzeros int32
+ *     [K / G, N / 8] packed the same way; scales_in fp16 [K / G, N].  The Linear is x @ w with w[k, n] = (q - z) s, so row n of W is w[:, n].
+ *   TD_INT4_GPTQ, AutoGPTQ 4-bit: qweight int32 [K / 8, N], nibble p of row r = q[8r + p, n]; qzeros int32 [K / G, N / 8], nibble p of column c =
+ *     z[g, 8c + p] - 1 (z = (stored + 1) & 15, AutoGPTQ's own unpack) -- with TD_INT4_GPTQ | TD_INT4_GPTQ_V2: z = stored; scales_in fp16 [K / G, N].
+ * g_idx (int32 [K], may be NULL) is NOT read: only the trivial map g_idx[k] = k / G is served (no act-order), and the caller vouches for it.
+ * N % 8 == 0; qweight / qzeros / packed 4-byte aligned.  TD_ERR_INVALID with a message, before any HIP call, otherwise. */
+int td_repack_int4(int layout, const void* qweight, const void* qzeros, const void* scales_in, const void* g_idx, int N, int K, int G,
+                   void* packed, void* scales, void* zeros, void* stream);
+/* packed, scales, zeros -> w_hat bf16 [N, ldw] = W^.  ldw % 8 == 0, ldw >= K; w_hat 16-byte aligned, packed 4-byte. */
+int td_dequant_rows_int4(const void* packed, const void* scales, const void* zeros, int G, void* w_hat, int64_t ldw, int N, int K, void* stream);
+/* td_linear_w4_bf16 / td_linear_split_w4_bf16 / td_linear_glu_w4_bf16 with W^ given as (packed, scales, zeros, G) in the format above: the same arguments,
+ * epilogues, rounding points and refusals.  M <= 64 ONLY.  N % 4 == 0, K % G == 0 and K % 32 == 0; more than 16 rows (and 3 .. 16 rows on the matrix core)
+ * need K % 256 == 0, N % 16 == 0, ldy % 4 == 0.  x, packed and scales 16-byte aligned, zeros 8-byte, ldx % 8 == 0. */
+int td_linear_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream);
+int td_linear_split_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, const void* bias, void* y0,
+                            int64_t ldy0, int act0, void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream);
+int td_linear_glu_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, void* y, int64_t ldy, int M, int I,
+                          int K, void* stream);
+
+enum { TD_QWEN2_WEIGHTS_BF16 = 0, TD_QWEN2_WEIGHTS_E4M3 = 1, TD_QWEN2_WEIGHTS_MXFP4 = 2, TD_QWEN2_WEIGHTS_INT4 = 3 };
+/* TD_QWEN2_WEIGHTS_INT4 is not a mode td_qwen2_quantize_weights takes (there is no round-to-nearest int4 quantiser): a handle enters it by being LOADED
+ * with int4 Linears.  `name` is a decoder Linear's "...weight" name from td_qwen2_param_info (q / k / v / o / gate / up / down_proj); packed / scales / zeros
+ * are that Linear's device layout from td_repack_int4 (device memory).  The call writes W^ into the rows of the bf16 arena td_qwen2_load_param would write
+ * for that name, and the nibbles, scales and zeros into the same rows of the handle's int4 copy (allocated on the first call from the shapes of all
+ * 7 x layers Linears: N K / 2 + 3 N K / G bytes each, 0.26x the bf16 Linear weights at G = 128, beside the arena).  Until every one of the 7 x layers
+ * Linears has int4 data the handle is stale: every run is refused.  Then the mode is TD_QWEN2_WEIGHTS_INT4 and the weight stream is on, with
+ * td_qwen2_set_weight_stream, td_qwen2_weight_info (n_linears = 7 x layers) and td_qwen2_weight_stream_launches as in the other modes.  With the stream
+ * on, only the row counts at which the int4 forms measured faster than the bf16 kernels read the copy (the table int4_rows_routed in
+ * csrc/qwen2_engine.hip, from profiles/qwen2_int4_bench.json; td_qwen2_set_int4_routing below lifts it); every other launch reads W^ from the bf16
+ * arena -- the same model.  lm_head and the
+ * embedding table are not quantised in these checkpoints: they load through td_qwen2_load_param and always run as bf16.
+ * Mixing is refused with TD_ERR_INVALID, the message naming the rule: this call on an E4M3 / MXFP4 handle; a second G on one handle;
+ * td_qwen2_quantize_weights, td_qwen2_init_random, or td_qwen2_load_param of a decoder Linear weight on an INT4 handle (biases, norms, embeddings and
+ * lm_head load as ever). */
+int td_qwen2_load_param_int4(td_qwen2* f, const char* name, const void* packed, const void* scales, const void* zeros, int G, void* stream);
+/* Measurement and test switch on an INT4 handle (as td_attention_verify_set_form is for the verify kernels): all = 1 sends EVERY launch of up to 64 rows
+ * that the int4 forms take to the int4 copy while the stream is on, all = 0 (the default) only the row counts of the table above.  The model is the same
+ * either way.  tools/bench_qwen2_int4.py times both settings, which is where the table comes from.  Drops the captured decode graphs.  Returns the
+ * previous setting (0 / 1); TD_ERR_INVALID for another value, a NULL handle or a handle that is not in INT4 mode. */
+int td_qwen2_set_int4_routing(td_qwen2* f, int all);
 /* Called after the parameters are loaded.  mode = TD_QWEN2_WEIGHTS_E4M3 or TD_QWEN2_WEIGHTS_MXFP4 (anything else: TD_ERR_INVALID; below, "8-bit copy" reads
  * "4-bit copy": packed nibbles + block scale bytes, 0.27x the Linear weights instead of half).  A handle quantised in one mode REFUSES the other
  * (TD_ERR_INVALID naming both) until its parameters are loaded again: the original weights are gone.  Builds the 8-bit copy and the row scales of every

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 21; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 22; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -45,6 +45,8 @@ int td_abi_version(void) { return 21; }  // 2: TdFluxConfig::out_channels append
                                             //     TD_QWEN2_WEIGHTS_MXFP4)
                                             // 21: speculative decoding (td_attention_verify, td_attention_verify_ex, td_attention_verify_set_form,
                                             //     td_qwen2_verify_batch_slots, td_spec_accept; csrc/spec_decode.hip)
+                                            // 22: grouped int4 weight stream for AWQ / GPTQ checkpoints (td_repack_int4, td_dequant_rows_int4,
+                                            //     td_linear*_i4_bf16, td_qwen2_load_param_int4, td_qwen2_set_int4_routing, TD_QWEN2_WEIGHTS_INT4)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -724,6 +726,57 @@ int td_linear_glu_w4_bf16(const void* x, int64_t ldx, const void* packed, const 
   TdGemmParams p;
   p.A = (const bf16_t*)x; p.lda = (int)ldx; p.W4 = (const uint8_t*)packed; p.w4_scale = (const uint8_t*)scales; p.C = (bf16_t*)y; p.ldc = (int)ldy;
   p.M = M; p.N = I; p.K = K; p.glu_I = I;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+// ---- grouped int4 weight stream (td_abi_version() >= 22): as above, every refusal comes before the first HIP call
+int td_repack_int4(int layout, const void* qweight, const void* qzeros, const void* scales_in, const void* g_idx, int N, int K, int G,
+                   void* packed, void* scales, void* zeros, void* stream) {
+  return td_repack_int4_launch(layout, (const int*)qweight, (const int*)qzeros, (const uint16_t*)scales_in, (const int*)g_idx, N, K, G, (uint8_t*)packed,
+                               (uint16_t*)scales, (uint8_t*)zeros, (hipStream_t)stream);
+}
+
+int td_dequant_rows_int4(const void* packed, const void* scales, const void* zeros, int G, void* w_hat, int64_t ldw, int N, int K, void* stream) {
+  return td_dequant_rows_int4_launch((const uint8_t*)packed, (const uint16_t*)scales, (const uint8_t*)zeros, G, (bf16_t*)w_hat, (long long)ldw, N, K, (hipStream_t)stream);
+}
+
+namespace {
+// the checks the three int4 Linear entries share, and the weight operands into p
+int i4_linear_args(const char* me, TdGemmParams& p, const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, const void* y,
+                   int64_t ldy, int M, int N, int K) {
+  TD_CHECK_ARG(x && packed && scales && zeros && y, "%s: x, the packed int4 weights, their group scales and zeros and the output are required", me);
+  TD_CHECK_ARG(G == 32 || G == 64 || G == 128, "%s: G=%d: the group sizes served are 32, 64 and 128", me, G);
+  TD_CHECK_ARG(M >= 1 && M <= 64, "%s: M=%d: the int4 weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", me, M);
+  TD_CHECK_ARG(N > 0 && K > 0 && ld32(ldx) && ld32(ldy), "%s: N=%d, K=%d, ldx=%lld, ldy=%lld", me, N, K, (long long)ldx, (long long)ldy);
+  p.A = (const bf16_t*)x; p.lda = (int)ldx; p.C = (bf16_t*)y; p.ldc = (int)ldy; p.M = M; p.N = N; p.K = K;
+  p.I4 = (const uint8_t*)packed; p.i4_scale = (const uint16_t*)scales; p.i4_zero = (const uint8_t*)zeros; p.i4_gshift = G == 32 ? 5 : G == 64 ? 6 : 7;
+  return 0;
+}
+}  // namespace
+
+int td_linear_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, const void* bias, void* y, int64_t ldy,
+                      int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr, void* stream) {
+  TdGemmParams p;
+  if (int rc = i4_linear_args("td_linear_i4_bf16", p, x, ldx, packed, scales, zeros, G, y, ldy, M, N, K)) return rc;
+  TD_CHECK_ARG(ld32(ldr) && (!res || ldr >= N), "td_linear_i4_bf16: ldr=%lld must cover the N=%d columns of the residual", (long long)ldr, N);
+  p.bias = (const bf16_t*)bias; p.gate = (const bf16_t*)gate; p.res = (const bf16_t*)res; p.ldr = (int)ldr; p.act = act;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_split_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, const void* bias, void* y0,
+                            int64_t ldy0, int act0, void* y1, int64_t ldy1, int act1, int M, int N, int K, int n_split, void* stream) {
+  TdGemmParams p;
+  if (int rc = i4_linear_args("td_linear_split_i4_bf16", p, x, ldx, packed, scales, zeros, G, y0, ldy0, M, N, K)) return rc;
+  TD_CHECK_ARG(y1 && ld32(ldy1), "td_linear_split_i4_bf16: the second output y1 is required");
+  p.bias = (const bf16_t*)bias; p.act = act0; p.C2 = (bf16_t*)y1; p.ldc2 = (int)ldy1; p.act2 = act1; p.n_split = n_split;
+  return td_gemv_launch(p, (hipStream_t)stream);
+}
+
+int td_linear_glu_i4_bf16(const void* x, int64_t ldx, const void* packed, const void* scales, const void* zeros, int G, void* y, int64_t ldy, int M, int I,
+                          int K, void* stream) {
+  TdGemmParams p;
+  if (int rc = i4_linear_args("td_linear_glu_i4_bf16", p, x, ldx, packed, scales, zeros, G, y, ldy, M, I, K)) return rc;
+  p.glu_I = I;
   return td_gemv_launch(p, (hipStream_t)stream);
 }
 

@@ -83,7 +83,7 @@ __device__ __forceinline__ void drain_row(const DrainState<ND>& ds, const int d)
 // WM rows above the switch: 128 extra live values and a spilling kernel.)
 // ND > 0 (persistent walk): the last ND m-tiles are packed into *ds instead of being stored; the others are stored here, i.e. ahead of them.
 template <int WM, int WN, bool Q8 = false, int ND = 0, class DS = void>   // mode 0: bias(+act); 1: bias(+act), gate, (+res); 2: bias(+act), res
-__device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg, bool second,
+__device__ __forceinline__ void epilogue(const TdGemmArgs& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg, bool second,
                                          const int act, const int mode, DS* ds = nullptr) {
   constexpr int NV = 4 * WN;
   constexpr int CH = (NV % 8 == 0) ? 8 : 4;          // columns per access: 16-byte accesses when the lane's span allows
@@ -269,7 +269,7 @@ __device__ __forceinline__ void epilogue(const TdGemmParams& pp, const ProbView&
 
 // raw fp32 rows (attention scores of the VAE mid block): acc + bias, no bf16 rounding, no activation / gate / residual
 template <int WM, int WN>
-__device__ __forceinline__ void epilogue_f32(const TdGemmParams& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg) {
+__device__ __forceinline__ void epilogue_f32(const TdGemmArgs& pp, const ProbView& p, f32x4_t (&acc)[WN][WM], int mbeg, int nbeg) {
   const __amdgpu_buffer_rsrc_t rsC = make_rsrc(p.C, (unsigned)(((long long)(p.M - 1) * pp.ldc + pp.N) * 4));
   const __amdgpu_buffer_rsrc_t rsB = make_rsrc(p.bias, (unsigned)pp.N * 2u);
 #pragma unroll
@@ -397,7 +397,7 @@ __device__ __forceinline__ void k_tile(const Stage& stage_one, char* smem, const
 // wait + barrier that lets the next tile's prologue overwrite the LDS, lanes past N staying in, this tile's last ND m-tiles left in *ds.
 // *pending (workgroup-uniform): *ds holds the previous tile's rows on entry, this tile's on return.
 template <int WM, int WN, int CONV, bool FP8, bool I8, int ND = 0, class DS = void>
-__device__ __forceinline__ void gemm_tile(const TdGemmParams& p, char* smem, const bool second_prob, const int m0, const int n0, DS* ds = nullptr,
+__device__ __forceinline__ void gemm_tile(const TdGemmArgs& p, char* smem, const bool second_prob, const int m0, const int n0, DS* ds = nullptr,
                                           bool* pending = nullptr) {
   static_assert(ND == 0 || (WM == 8 && WN == 4 && !CONV && !FP8 && !I8), "the walk: the 256x256 bf16 tile (no K split, no fp32 output: launch_cfg)");
   constexpr int BM = 32 * WM, BN = 64 * WN;
@@ -737,7 +737,7 @@ __device__ __forceinline__ int xcd_contiguous(const int bid, const int nwg) {
 // that follow each other share a W panel and four A panels.  Grouped launch: m-tiles [0, tiles_m0) belong to problem 0, the rest to problem 1
 // (same N, K, strides); tm counts inside its problem.
 struct TilePos { int tm, tn; bool second_prob; };
-__device__ __forceinline__ TilePos tile_pos(const int t, const TdGemmParams& p) {
+__device__ __forceinline__ TilePos tile_pos(const int t, const TdGemmArgs& p) {
   constexpr int GROUP_M = 4;
   const int per_group = GROUP_M * p.tiles_n;
   const int gid = t / per_group;
@@ -758,7 +758,7 @@ __device__ __forceinline__ TilePos tile_pos(const int t, const TdGemmParams& p) 
 // last round costs 1 / TAIL of a tile time (x the smaller tile's lower efficiency) instead of a whole one.  No split along K, no
 // fix-up pass: every output element is still produced by one workgroup with the full contraction, bit-identical to the unsplit launch.
 template <int WM, int WN, int CONV = 0, bool FP8 = false, bool I8 = false, int TAIL = 1>
-__global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmParams p) {
+__global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)  // body uses gfx950-only types (__amdgpu_buffer_rsrc_t): the host pass only needs the stub
   static_assert(TAIL == 1 || (WM % TAIL == 0 && !CONV), "tail sub-tiles cut the m extent of the tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -797,7 +797,7 @@ __global__ __launch_bounds__(512, 1) void td_gemm_bf16_nt_kernel(const TdGemmPar
 constexpr int TD_DRAIN_ROWS = 4;      // m-tiles (of 8) whose stores a tile leaves to the next: see DESIGN 4
 
 template <int ND>
-__global__ __launch_bounds__(512, 1) void td_gemm_bf16_drain_kernel(const TdGemmParams p) {
+__global__ __launch_bounds__(512, 1) void td_gemm_bf16_drain_kernel(const TdGemmArgs p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int total = p.tiles_m * p.tiles_n;
@@ -1127,8 +1127,8 @@ int td_gemm_plan(int M, int N, int K, int shared, int operand) {
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.M > 0 && p.N > 0 && p.K > 0, "td_gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemm: unknown activation code act=%d act2=%d (0 .. 4: TD_ACT_NONE .. TD_ACT_QUICK_GELU)", p.act, p.act2);
-  if (p.W8 || p.W4) {      // 8-bit / 4-bit weight stream: skinny-M kernels only, with checks of their own (a chunk is 16 / 32 weights)
-    TD_CHECK_ARG(p.g_M == 0 && !p.fp8 && !p.i8 && !p.out_f32 && p.conv_H == 0 && p.split_k == 0 && !p.q8, "td_gemm: 8-bit and 4-bit weights (W8, W4) exist for the plain skinny-M Linear only");
+  if (p.W8 || p.W4 || p.I4) {      // 8-bit / 4-bit weight stream: skinny-M kernels only, with checks of their own (a chunk is 16 / 32 weights)
+    TD_CHECK_ARG(p.g_M == 0 && !p.fp8 && !p.i8 && !p.out_f32 && p.conv_H == 0 && p.split_k == 0 && !p.q8, "td_gemm: 8-bit and 4-bit weights (W8, W4, I4) exist for the plain skinny-M Linear only");
     return td_gemv_launch(p, stream);
   }
   const int esz = (p.fp8 || p.i8) ? 1 : 2;

@@ -6,18 +6,21 @@
 //     chunks, so every wave-level load is a fully coalesced 1 KiB line run; loads are non-temporal (weights are read once);
 //   * two chunk-columns are in flight per thread (8 weight loads + the matching x chunks, which hit L2);
 //   * bf16 pairs go straight into v_dot2c_f32_bf16 (fp32 accumulate, no unpacking); the W8 / W4 forms stream e4m3 bytes / MXFP4 nibbles and convert them
-//     to those pairs in one instruction per pair (csrc/e4m3_pow2.h, csrc/mxfp4_pow2.h);
+//     to those pairs in one instruction per pair (csrc/e4m3_pow2.h, csrc/mxfp4_pow2.h); the I4 form streams the uint4 nibbles of AWQ / GPTQ checkpoints and
+//     rebuilds the pairs with one fp32 fma per weight and one rounding (csrc/int4_group.h);
 //   * wave shuffle + LDS cross-wave reduction, then the same epilogue semantics and bf16 rounding points as the tile kernel
 //     (bias, activation, gate, residual, split output).
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "td_common.h"
 #include "td_kernels.h"
 #include "e4m3_pow2.h"
 #include "mxfp4_pow2.h"
+#include "int4_group.h"
 
 namespace {
 
@@ -42,29 +45,42 @@ constexpr int R = 4;          // weight rows (output columns) per workgroup
 constexpr int THREADS = 256;
 
 // what the weight rows of a stream kernel hold (the WF template parameter): bf16 values, e4m3 bytes under a row scale (TdGemmParams::W8), or MXFP4
-// nibbles under a scale byte per 32 weights (TdGemmParams::W4)
-constexpr int WF_BF16 = 0, WF_W8 = 1, WF_W4 = 2;
+// nibbles under a scale byte per 32 weights (TdGemmParams::W4), or uint4 nibbles under an fp16 scale and a zero point per group (TdGemmParams::I4)
+constexpr int WF_BF16 = 0, WF_W8 = 1, WF_W4 = 2, WF_I4 = 3;
+// the argument block of a form's kernels: only I4 reads (and carries) the int4 fields of TdGemmParams
+template <int WF> using GemvArgs = std::conditional_t<WF == WF_I4, TdGemmParams, TdGemmArgs>;
 
 // W8: the weight rows are e4m3 bytes (p.W8, p.w8_scale); a 16-byte chunk then holds 16 weights and meets two chunks of x.  Everything behind the
 // accumulators is shared with the bf16 form.
 // W4: the weight rows are MXFP4 nibbles (p.W4, p.w4_scale; the format of csrc/mxfp4_pow2.h); a 16-byte chunk is then exactly one MX block: 32 weights
 // under one scale byte, which the thread loads beside the chunk, and meets four chunks of x.  The chunk is converted a dword (8 weights) at a time.
+// I4: the weight rows are grouped int4 nibbles (p.I4, p.i4_scale, p.i4_zero, p.i4_gshift; the format of csrc/int4_group.h).  The loop is the W4 loop: a 16-byte
+// chunk is 32 weights inside ONE group, whose fp16 scale and zero point the thread loads beside the chunk and combines once (i4_group).
 template <int MR, int WF = WF_BF16>
-__global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParams p) {
-  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4;
+__global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const GemvArgs<WF> p) {
+  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4, I4 = WF == WF_I4;
   __shared__ float red[THREADS / 64][R][MR];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int n0 = blockIdx.x * R;
-  const int nchunk = W4 ? p.K >> 5 : W8 ? p.K >> 4 : p.K >> 3;
+  const int nchunk = (W4 || I4) ? p.K >> 5 : W8 ? p.K >> 4 : p.K >> 3;
   const u32x4_t* wp[R];
   const uint8_t* sp[R];      // W4: the row's scale bytes, one per chunk
+  const uint16_t* isp[R];    // I4: the row's group scales and zero points, one per (chunk >> gsh)
+  const uint8_t* izp[R];
+  int gsh = 0;
+  if constexpr (I4) gsh = p.i4_gshift - 5;
   float wsc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     // gated mode: rows 0,1 = gate rows 2b, 2b+1; rows 2,3 = the matching up rows (glu_I further down the matrix)
     const int row = p.glu_I ? (blockIdx.x * 2 + (r & 1) + (r >> 1) * p.glu_I) : min(n0 + r, p.N - 1);
-    sp[r] = nullptr;
-    if constexpr (W4) {
+    sp[r] = nullptr; isp[r] = nullptr; izp[r] = nullptr;
+    if constexpr (I4) {
+      wp[r] = (const u32x4_t*)(p.I4 + (size_t)row * (p.K >> 1));
+      isp[r] = p.i4_scale + (size_t)row * (p.K >> p.i4_gshift);
+      izp[r] = p.i4_zero + (size_t)row * (p.K >> p.i4_gshift);
+      wsc[r] = 1.f;
+    } else if constexpr (W4) {
       wp[r] = (const u32x4_t*)(p.W4 + (size_t)row * (p.K >> 1));
       sp[r] = p.w4_scale + (size_t)row * (p.K >> 5);
       wsc[r] = 1.f;
@@ -86,13 +102,16 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
 #pragma unroll
     for (int m = 0; m < MR; ++m) acc[r][m] = 0.f;
 
-  // W4: one chunk (= one block) of the R rows, at chunk index cc, against its four chunks of x
-  auto eat4 = [&](const u32x4_t (&w)[R], const unsigned (&sb)[R], int cc) {
+  // W4 / I4: one chunk (= one block; inside one group) of the R rows, at chunk index cc, against its four chunks of x; sb: the scale byte / the group
+  auto eat4 = [&](const u32x4_t (&w)[R], const auto (&sb)[R], int cc) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       u32x4_t a[R];
 #pragma unroll
-      for (int r = 0; r < R; ++r) a[r] = mx4_to_bf16(w[r][i], mx4_scale_f32(sb[r]));
+      for (int r = 0; r < R; ++r) {
+        if constexpr (I4) a[r] = i4_to_bf16(w[r][i], sb[r]);
+        else a[r] = mx4_to_bf16(w[r][i], mx4_scale_f32(sb[r]));
+      }
 #pragma unroll
       for (int m = 0; m < MR; ++m) {
         const u32x4_t x = xp[m][4 * cc + i];
@@ -110,7 +129,17 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
       w0[r] = __builtin_nontemporal_load(wp[r] + c);
       w1[r] = __builtin_nontemporal_load(wp[r] + c + THREADS);
     }
-    if constexpr (W4) {
+    if constexpr (I4) {
+      I4Group g0[R], g1[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const int e0 = c >> gsh, e1 = (c + THREADS) >> gsh;
+        g0[r] = i4_group(isp[r][e0], izp[r][e0]);
+        g1[r] = i4_group(isp[r][e1], izp[r][e1]);
+      }
+      eat4(w0, g0, c);
+      eat4(w1, g1, c + THREADS);
+    } else if constexpr (W4) {
       unsigned s0[R], s1[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) { s0[r] = sp[r][c]; s1[r] = sp[r][c + THREADS]; }
@@ -139,7 +168,12 @@ __global__ __launch_bounds__(THREADS) void td_gemv_bf16_kernel(const TdGemmParam
     u32x4_t w0[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) w0[r] = __builtin_nontemporal_load(wp[r] + c);
-    if constexpr (W4) {
+    if constexpr (I4) {
+      I4Group g0[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) g0[r] = i4_group(isp[r][c >> gsh], izp[r][c >> gsh]);
+      eat4(w0, g0, c);
+    } else if constexpr (W4) {
       unsigned s0[R];
 #pragma unroll
       for (int r = 0; r < R; ++r) s0[r] = sp[r][c];
@@ -234,9 +268,13 @@ template <int MB, int NR> constexpr int gemv_lds_bytes() { return MW * (2 * NR +
 // same two weight loads per block, four times the activation loads, four 64-element quarters in turn.  A lane's 8-element operand fragment is 4 bytes
 // (ds_read_b32) inside ONE 16-byte chunk = one block, so one scale per fragment: the 8 scale bytes of the lane's row and step arrive in one 8-byte load
 // in operand layout (lane = row r) beside the weight lines, and mx4_to_bf16 rebuilds the bf16 fragment.
+// I4 (TdGemmParams::I4): the weight rows are grouped int4 nibbles; lines, steps, slab and fragments are those of W4.  A fragment lies in one 16-byte chunk and
+// therefore in one group: the 256 / G groups of the lane's row and step -- their fp16 scales in one load of 4 .. 16 bytes, their zero points in one of
+// 2 .. 8 -- arrive beside the weight lines, and i4_to_bf16 rebuilds the bf16 fragment with the single rounding of csrc/int4_group.h.  The group size is a
+// kernel argument: the loads and a byte permute that spreads the groups over the line's 8 chunks run under a uniform branch, everything behind is one code.
 template <int MB, int NR, bool DEEP, int WF = WF_BF16>
-__global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParams p, char* ws) {
-  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4;
+__global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const GemvArgs<WF> p, char* ws) {
+  constexpr bool W8 = WF == WF_W8, W4 = WF == WF_W4, I4 = WF == WF_I4, N4 = W4 || I4;      // N4: nibble rows
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int XB = gemv_xb<MB>();
   constexpr int SLAB = (2 * NR + 2 * XB) * 1024;
@@ -257,18 +295,28 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   // LDS pass (a workgroup streams only 16 rows x K, its lifetime is a handful of memory round trips); otherwise hipcc threads
   // the loads between the steps at low register count, which keeps several workgroups per CU for short K.
   const unsigned w_rows = p.glu_I ? 2u * (unsigned)p.glu_I : (unsigned)p.N;
-  const __amdgpu_buffer_rsrc_t rsW = W4   ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W4, 0, (unsigned)((size_t)w_rows * (p.K >> 1)), 0x00020000)
+  const void* nib = p.W4;      // the nibble rows of either 4-bit form
+  if constexpr (I4) nib = p.I4;
+  const __amdgpu_buffer_rsrc_t rsW = N4   ? __builtin_amdgcn_make_buffer_rsrc((void*)nib, 0, (unsigned)((size_t)w_rows * (p.K >> 1)), 0x00020000)
                                      : W8 ? __builtin_amdgcn_make_buffer_rsrc((void*)p.W8, 0, (unsigned)((size_t)w_rows * p.K), 0x00020000)
                                           : __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (unsigned)((size_t)w_rows * p.K * 2), 0x00020000);
   // W4: the scale bytes [w_rows, K / 32]; a lane reads the 8 of its operand row and step (K % 256 == 0: 8-byte aligned)
   const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)p.w4_scale, 0, W4 ? (unsigned)((size_t)w_rows * (p.K >> 5)) : 0u, 0x00020000);
+  // I4: the fp16 scales and the zero points [w_rows, K / G]; a lane reads the 256 / G of its operand row and step (K % 256 == 0: naturally aligned)
+  int gsh = 0;      // chunks per group, as a shift
+  __amdgpu_buffer_rsrc_t rsIS = rsS, rsIZ = rsS;
+  if constexpr (I4) {
+    gsh = p.i4_gshift - 5;
+    rsIS = __builtin_amdgcn_make_buffer_rsrc((void*)p.i4_scale, 0, (unsigned)((size_t)w_rows * (p.K >> p.i4_gshift) * 2), 0x00020000);
+    rsIZ = __builtin_amdgcn_make_buffer_rsrc((void*)p.i4_zero, 0, (unsigned)((size_t)w_rows * (p.K >> p.i4_gshift)), 0x00020000);
+  }
   const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (unsigned)((((size_t)p.M - 1) * p.lda + p.K) * 2), 0x00020000);
   constexpr unsigned OOB = 0xFFFFFF00u;
   const int lrow = lane >> 3;                                  // row of the 8-row half this lane fetches
   const int lchunk = (lane & 7) ^ (lrow & 7);                  // ... and which 16-byte chunk of the row's 128-byte line
   unsigned woff[NR][2], xoff[MB][2];
   float wsc[NR];                                               // W8: scale of the weight row this lane holds in operand layout (row r of the block)
-  unsigned soff[NR];                                           // W4: where that row's scale bytes begin
+  unsigned soff[NR];                                           // W4: where that row's scale bytes begin; I4: its first group
 #pragma unroll
   for (int nr = 0; nr < NR; ++nr) {
     const int bid = min((int)blockIdx.x * NR + nr, nblk - 1);
@@ -276,7 +324,7 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
     for (int h = 0; h < 2; ++h) {
       // gated mode: rows 0-7 = gate rows 8b..8b+7, rows 8-15 = the matching up rows
       const int wr_ = p.glu_I ? (bid * 8 + lrow + h * p.glu_I) : bid * 16 + 8 * h + lrow;
-      woff[nr][h] = W4   ? (unsigned)((size_t)wr_ * (p.K >> 1) + 16 * lchunk)
+      woff[nr][h] = N4   ? (unsigned)((size_t)wr_ * (p.K >> 1) + 16 * lchunk)
                     : W8 ? (unsigned)((size_t)wr_ * p.K + 16 * lchunk)
                          : (unsigned)(((size_t)wr_ * p.K + 8 * lchunk) * 2);
     }
@@ -284,6 +332,7 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
     if constexpr (W8) wsc[nr] = p.w8_scale[orow];
     else wsc[nr] = 1.f;
     soff[nr] = W4 ? (unsigned)((size_t)orow * (p.K >> 5)) : 0u;
+    if constexpr (I4) soff[nr] = (unsigned)((size_t)orow * (p.K >> p.i4_gshift));
   }
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -304,14 +353,14 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   }
   // W4: the 4 fragment bytes of (quarter j of the step, h): k = 64 j + 32 h + 8 g .. + 7 = chunk (= block) 2 j + h of the row's line, its bytes 4 g .. 4 g + 3
   const char* rd4_ptr[4][2];
-  if constexpr (W4) {
+  if constexpr (N4) {
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int h = 0; h < 2; ++h) rd4_ptr[j][h] = slab + r * 128 + (((2 * j + h) ^ (r & 7)) << 4) + 4 * g;
   }
-  constexpr int KH = W4 ? 4 : W8 ? 2 : 1;       // 64-element parts of a step
-  const int nk_all = W4 ? p.K >> 8 : W8 ? p.K >> 7 : p.K >> 6;  // steps (64 elements; W8: 128; W4: 256)
+  constexpr int KH = N4 ? 4 : W8 ? 2 : 1;       // 64-element parts of a step
+  const int nk_all = N4 ? p.K >> 8 : W8 ? p.K >> 7 : p.K >> 6;  // steps (64 elements; W8: 128; W4: 256)
   const int s_beg = (int)((long long)nk_all * ky / KS), nk = (int)((long long)nk_all * (ky + 1) / KS);   // this workgroup's steps
   f32x4_t acc[NR][MB];
 #pragma unroll
@@ -322,6 +371,8 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
   for (int s = s_beg + wid; s < nk; s += SF * MW) {
     u32x4_t w[SF][NR][2], x[SF][KH][MB][2];
     u32x2_t sc4[SF][NR];      // W4: the step's 8 scale bytes of the lane's operand row
+    u32x4_t si4[SF][NR];      // I4: the step's 8 >> gsh group scales of that row (fp16 bits, two to a word) ...
+    u32x2_t zi4[SF][NR];      // ... and zero points (four to a word)
 #pragma unroll
     for (int f = 0; f < SF; ++f) {
       const int st = s + f * MW;
@@ -334,6 +385,25 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
       if constexpr (W4) {
 #pragma unroll
         for (int nr = 0; nr < NR; ++nr) sc4[f][nr] = __builtin_amdgcn_raw_buffer_load_b64(rsS, ok ? soff[nr] + (unsigned)st * 8u : OOB, 0, 0);
+      }
+      if constexpr (I4) {
+#pragma unroll
+        for (int nr = 0; nr < NR; ++nr) {
+          const unsigned e0 = soff[nr] + ((unsigned)st << (3 - gsh));      // the step's first group of the row
+          si4[f][nr] = u32x4_t{0u, 0u, 0u, 0u};
+          zi4[f][nr] = u32x2_t{0u, 0u};
+          if (gsh == 2) {
+            si4[f][nr][0] = __builtin_amdgcn_raw_buffer_load_b32(rsIS, ok ? e0 * 2u : OOB, 0, 0);
+            zi4[f][nr][0] = __builtin_amdgcn_raw_buffer_load_b16(rsIZ, ok ? e0 : OOB, 0, 0);
+          } else if (gsh == 1) {
+            const u32x2_t t = __builtin_amdgcn_raw_buffer_load_b64(rsIS, ok ? e0 * 2u : OOB, 0, 0);
+            si4[f][nr][0] = t[0]; si4[f][nr][1] = t[1];
+            zi4[f][nr][0] = __builtin_amdgcn_raw_buffer_load_b32(rsIZ, ok ? e0 : OOB, 0, 0);
+          } else {
+            si4[f][nr] = __builtin_amdgcn_raw_buffer_load_b128(rsIS, ok ? e0 * 2u : OOB, 0, 0);
+            zi4[f][nr] = __builtin_amdgcn_raw_buffer_load_b64(rsIZ, ok ? e0 : OOB, 0, 0);
+          }
+        }
       }
 #pragma unroll
       for (int j = 0; j < KH; ++j)
@@ -350,6 +420,21 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
       for (int nr = 0; nr < NR; ++nr)
 #pragma unroll
         for (int h = 0; h < 2; ++h) wr_ptr[(2 * nr + h) * 64] = w[f][nr][h];
+      if constexpr (I4) {      // spread the step's 8 >> gsh groups over the 8 chunks of the line: from here on chunk j reads half j / byte j, whatever G is
+#pragma unroll
+        for (int nr = 0; nr < NR; ++nr) {
+          const unsigned s0 = si4[f][nr][0], s1 = si4[f][nr][1], z = zi4[f][nr][0];
+          if (gsh == 2) {
+            const unsigned a = __builtin_amdgcn_perm(s0, s0, 0x01000100u), b = __builtin_amdgcn_perm(s0, s0, 0x03020302u);
+            si4[f][nr] = u32x4_t{a, a, b, b};
+            zi4[f][nr] = u32x2_t{__builtin_amdgcn_perm(z, z, 0x00000000u), __builtin_amdgcn_perm(z, z, 0x01010101u)};
+          } else if (gsh == 1) {
+            si4[f][nr] = u32x4_t{__builtin_amdgcn_perm(s0, s0, 0x01000100u), __builtin_amdgcn_perm(s0, s0, 0x03020302u),
+                                 __builtin_amdgcn_perm(s1, s1, 0x01000100u), __builtin_amdgcn_perm(s1, s1, 0x03020302u)};
+            zi4[f][nr] = u32x2_t{__builtin_amdgcn_perm(z, z, 0x01010000u), __builtin_amdgcn_perm(z, z, 0x03030202u)};
+          }
+        }
+      }
 #pragma unroll
       for (int kh = 0; kh < KH; ++kh) {
       bf16x8_t wf[NR][2];
@@ -366,7 +451,11 @@ __global__ __launch_bounds__(MW * 64) void td_gemv_mfma_kernel(const TdGemmParam
           if (m0 == 0) {
 #pragma unroll
             for (int nr = 0; nr < NR; ++nr) {
-              if constexpr (W4) {
+              if constexpr (I4) {
+                const int j = 2 * kh + h;                                                          // chunk of the line
+                const unsigned sb = (si4[f][nr][j >> 1] >> (16 * (j & 1))) & 0xffffu, zb = (zi4[f][nr][j >> 2] >> (8 * (j & 3))) & 0xffu;
+                wf[nr][h] = __builtin_bit_cast(bf16x8_t, i4_to_bf16(*(const unsigned*)(rd4_ptr[kh][h] + nr * 2048), i4_group(sb, zb)));
+              } else if constexpr (W4) {
                 const unsigned sb = (sc4[f][nr][(2 * kh + h) >> 2] >> (8 * ((2 * kh + h) & 3))) & 0xffu;      // block 2 kh + h of the line
                 wf[nr][h] = __builtin_bit_cast(bf16x8_t, mx4_to_bf16(*(const unsigned*)(rd4_ptr[kh][h] + nr * 2048), mx4_scale_f32(sb)));
               } else if constexpr (W8) {
@@ -495,8 +584,8 @@ int splitk_workspace(hipStream_t stream, char** out) {
 
 // The weight forms of the stream kernels, as far as the host's shape rules go
 struct WeightForm { int chunk, step, bits; };      // weights per 16-byte chunk (dot form), per MFMA k-step, and bits per weight
-constexpr WeightForm FORM_BF16{8, 64, 16}, FORM_W8{16, 128, 8}, FORM_W4{32, 256, 4};
-template <int WF> constexpr WeightForm form_of() { return WF == WF_W4 ? FORM_W4 : WF == WF_W8 ? FORM_W8 : FORM_BF16; }
+constexpr WeightForm FORM_BF16{8, 64, 16}, FORM_W8{16, 128, 8}, FORM_W4{32, 256, 4}, FORM_I4{32, 256, 4};
+template <int WF> constexpr WeightForm form_of() { return WF == WF_I4 ? FORM_I4 : WF == WF_W4 ? FORM_W4 : WF == WF_W8 ? FORM_W8 : FORM_BF16; }
 
 template <int MB, int NR, bool DEEP, int WF>
 int launch_one(const TdGemmParams& p, dim3 grid, char* ws, hipStream_t stream) {
@@ -571,7 +660,7 @@ bool mfma_ok(const TdGemmParams& p, WeightForm f, bool gated_checked) {
 // (tools/bench_qwen2_w4.py)
 template <int WF>
 int route(const TdGemmParams& p, bool mfma, hipStream_t stream) {
-  constexpr int DOT_ROWS = WF == WF_W4 ? 2 : 4;
+  constexpr int DOT_ROWS = (WF == WF_W4 || WF == WF_I4) ? 2 : 4;      // (I4 streams the same bytes per weight and unpacks with more VALU work per row)
   if (p.M > DOT_ROWS && mfma) {
     if (int rc = launch_mfma_rows<WF>(p, stream)) return rc;
   } else {
@@ -619,7 +708,36 @@ int gemv_w4_launch(const TdGemmParams& p, hipStream_t stream) {
   return route<WF_W4>(p, mfma, stream);
 }
 
+// td_gemv_launch for TdGemmParams::I4, with the same duties and the same refusals as the two above: the C ABI's grouped-int4 entries come straight here
+int gemv_i4_launch(const TdGemmParams& p, hipStream_t stream) {
+  TD_CHECK_ARG(!p.W8 && !p.W4, "td_gemv(i4): W8, W4 and I4 are exclusive");
+  TD_CHECK_ARG(p.I4 && p.i4_scale && p.i4_zero && p.A && p.C, "td_gemv(i4): x, the packed int4 weights, their group scales and zeros and the output are required");
+  TD_CHECK_ARG(p.i4_gshift >= 5 && p.i4_gshift <= 7, "td_gemv(i4): G=%d: the group sizes served are 32, 64 and 128", p.i4_gshift >= 0 && p.i4_gshift < 31 ? 1 << p.i4_gshift : -1);
+  TD_CHECK_ARG(p.M >= 1 && p.M <= 64, "td_gemv(i4): M=%d: the int4 weight stream takes 1 .. 64 rows (more rows read the bf16 weights through td_linear_bf16)", p.M);
+  TD_CHECK_ARG(p.N > 0 && p.N % R == 0 && p.K > 0 && p.K % 32 == 0 && p.K % (1 << p.i4_gshift) == 0,
+               "td_gemv(i4): N=%d must be a multiple of 4 and K=%d a multiple of G=%d and of 32 (one 16-byte chunk of a packed row)", p.N, p.K, 1 << p.i4_gshift);
+  TD_CHECK_ARG(p.lda >= p.K && p.lda % 8 == 0 && p.ldc >= (p.C2 ? p.n_split : p.N), "td_gemv(i4): bad leading dimensions lda=%d ldc=%d", p.lda, p.ldc);
+  TD_CHECK_ARG(((uintptr_t)p.A | (uintptr_t)p.I4 | (uintptr_t)p.i4_scale) % 16 == 0 && (uintptr_t)p.i4_zero % 8 == 0 && (uintptr_t)p.C % 8 == 0 && (uintptr_t)p.C2 % 8 == 0,
+               "td_gemv(i4): misaligned operands: x, the packed weights and the scales must be 16-byte aligned, the outputs and the zeros 8-byte");
+  if (p.C2) TD_CHECK_ARG(p.n_split > 0 && p.n_split < p.N && p.n_split % 4 == 0 && p.ldc2 >= p.N - p.n_split, "td_gemv(i4): bad split-output arguments");
+  if (p.glu_I) {
+    TD_CHECK_ARG(p.N == p.glu_I && p.glu_I % 8 == 0 && !p.bias && !p.gate && !p.res && !p.C2 && p.act == TD_ACT_NONE && p.ldc % 4 == 0,
+                 "td_gemv(i4, glu): N must equal glu_I (multiple of 8), no bias / gate / residual / split");
+  }
+  const bool mfma = mfma_ok(p, FORM_I4, true);
+  TD_CHECK_ARG(p.M <= 16 || mfma, "td_gemv(i4): more than 16 rows need the matrix-core form (K=%d %% 256, N=%d %% 16, ldc %% 4 == 0, operands under 4 GiB)", p.K, p.N);
+  return route<WF_I4>(p, mfma, stream);
+}
+
 }  // namespace
+
+// shapes the grouped int4 weight stream takes (csrc/qwen2_engine.hip asks before it routes a Linear to its int4 copy)
+bool td_gemv_i4_ok(const TdGemmParams& p) {
+  if (p.i4_gshift < 5 || p.i4_gshift > 7 || p.K % (1 << p.i4_gshift) != 0) return false;
+  if (p.M < 1 || p.M > 64 || p.N % R != 0 || p.K % FORM_I4.chunk != 0 || p.lda % 8 != 0) return false;
+  if (p.glu_I && (p.N != p.glu_I || p.glu_I % 8 != 0 || p.ldc % 4 != 0)) return false;
+  return p.M <= 16 || mfma_ok(p, FORM_I4, true);
+}
 
 // shapes the 4-bit weight stream takes (csrc/qwen2_engine.hip asks before it routes a Linear to its MXFP4 copy)
 bool td_gemv_w4_ok(const TdGemmParams& p) {
@@ -640,6 +758,7 @@ bool td_gemv_mfma_ok(const TdGemmParams& p) { return mfma_ok(p, FORM_BF16, false
 
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream) {
   TD_CHECK_ARG(td_act_valid(p.act) && td_act_valid(p.act2), "td_gemv: unknown activation code act=%d act2=%d", p.act, p.act2);
+  if (p.I4) return gemv_i4_launch(p, stream);
   if (p.W4) return gemv_w4_launch(p, stream);
   if (p.W8) return gemv_w8_launch(p, stream);
   TD_CHECK_ARG(p.M >= 1 && p.M <= 64 && p.N % R == 0 && p.K % FORM_BF16.chunk == 0 && p.lda % 8 == 0, "td_gemv: needs M <= 64, N %% 4 == 0, K %% 8 == 0");

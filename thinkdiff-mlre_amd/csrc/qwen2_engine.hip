@@ -35,8 +35,9 @@ namespace {
 struct QSlot { std::string name; bf16_t* ptr; int64_t count; };
 
 // the quantised copy of one Linear weight (td_qwen2_quantize_weights): e4m3 bytes [N, K] and the fp32 row scales 2^e_n, or -- TD_QWEN2_WEIGHTS_MXFP4 --
-// packed nibbles [N, K / 2] and the e8m0 block scale bytes [N, K / 32]; null on an unquantised handle
-struct W8Ref { uint8_t* q = nullptr; void* s = nullptr; };
+// packed nibbles [N, K / 2] and the e8m0 block scale bytes [N, K / 32], or -- TD_QWEN2_WEIGHTS_INT4 (td_qwen2_load_param_int4) -- packed nibbles [N, K / 2],
+// fp16 group scales [N, K / G] and zero points [N, K / G]; null on an unquantised handle (and for lm_head on an INT4 one)
+struct W8Ref { uint8_t* q = nullptr; void* s = nullptr; uint8_t* z = nullptr; };
 
 struct QLayer {
   W8Ref qkv_8, o_8, gu_8, down_8;
@@ -92,6 +93,11 @@ struct td_qwen2 {
   int w8_linears = 0;
   long long w8_launches = 0;                    // Linear launches enqueued (or captured) so far that read the 8-bit copy (td_qwen2_weight_stream_launches)
   W8Ref lm_8;
+  // INT4: the group size of the copy (0: none yet) and which of the 7 x layers checkpoint Linears have int4 data (layer * 7 + q, k, v, o, gate, up, down)
+  int i4_G = 0;
+  std::vector<char> i4_have;
+  int i4_loaded = 0;
+  bool i4_route_all = false;                    // every row count the int4 forms take reads the copy, not only the measured-faster ones (td_qwen2_set_int4_routing)
   // e4m3 KV cache (td_qwen2_create_kv): fixed at creation, it sizes the allocation.  The parameter arena then lacks the cache rows; `segs` maps its pieces
   // (arena offset, offset in the bf16-mode layout, elements) so that td_qwen2_init_random draws the weights a bf16-mode handle draws from the same seed
   int kv_mode = TD_QWEN2_KV_BF16;
@@ -199,12 +205,26 @@ TdGemmParams linear(const bf16_t* x, int ldx, const bf16_t* W, const bf16_t* bia
   return g;
 }
 
+// INT4: the row counts at which the int4 forms measured FASTER than the bf16 kernels on W^ in both run orders (tools/bench_qwen2_int4.py with every
+// bucket forced onto them, the int4_all column of profiles/qwen2_int4_bench.json): the unpack is VALU work the MXFP4 conversion instruction
+// does not have, and at the other row counts it costs more than the bytes save.  Measured on the two decoder shapes at 1, 2, 4, 8, 16, 32 and 64 rows; the
+// line between the shapes is drawn at the width that already separates them (hidden 3072), a row count between two buckets goes with the one above it.
+// 7B shape: every bucket (x1.001 at 2 rows, x1.03 .. 1.31 elsewhere); 2B shape: 32 and 64 rows only (x1.07, x1.03; x0.81 .. 0.92 below).  Every other row
+// count reads the bf16 arena.
+bool int4_rows_routed(int M, int D) { return D >= 3072 ? M <= 64 : (M >= 17 && M <= 64); }
+
 // Launches a Linear of the decoder.  With the weight stream on, a launch of up to 64 rows that would reach the skinny-M kernels anyway (no tile override,
 // no K split) and has a shape their 8-bit (4-bit) forms take reads the quantised copy `w8` instead of the bf16 weight; everything else reads the bf16 arena,
 // which holds the same (dequantised) values -- the model does not depend on the route.
 int run_linear(td_qwen2* f, TdGemmParams g, const W8Ref& w8, hipStream_t s, bool allow8 = true) {
   if (allow8 && f->w8_on && w8.q && g.M <= STREAM_ROWS_MAX && g.cfg < 0 && g.split_k == 0) {
-    if (f->w_mode == TD_QWEN2_WEIGHTS_MXFP4 && td_gemv_w4_ok(g)) {
+    if (f->w_mode == TD_QWEN2_WEIGHTS_INT4) {
+      g.i4_gshift = f->i4_G == 32 ? 5 : f->i4_G == 64 ? 6 : 7;
+      if ((f->i4_route_all || int4_rows_routed(g.M, f->D)) && td_gemv_i4_ok(g)) {
+        g.I4 = w8.q; g.i4_scale = (const uint16_t*)w8.s; g.i4_zero = w8.z;
+        ++f->w8_launches;
+      }
+    } else if (f->w_mode == TD_QWEN2_WEIGHTS_MXFP4 && td_gemv_w4_ok(g)) {
       g.W4 = w8.q; g.w4_scale = (const uint8_t*)w8.s;
       ++f->w8_launches;
     } else if (f->w_mode == TD_QWEN2_WEIGHTS_E4M3 && td_gemv_w8_ok(g)) {
@@ -221,8 +241,13 @@ int lm_head(td_qwen2* f, const bf16_t* rows, int M, void* logits, hipStream_t s,
 }
 
 // every entry that runs the model: a handle whose parameters changed after quantising is refused, never run half-quantised
-#define TD_QWEN2_FRESH(f, fn) \
-  TD_CHECK_ARG(!(f)->w8_stale, "%s: parameters were loaded after the weights were quantised; call td_qwen2_quantize_weights again first", fn)
+#define TD_QWEN2_FRESH(f, fn)                                                                                                                                  \
+  do {                                                                                                                                                         \
+    TD_CHECK_ARG(!((f)->w8_stale && (f)->w_mode == TD_QWEN2_WEIGHTS_INT4),                                                                                     \
+                 "%s: the handle holds int4 data for %d of its %d decoder Linears; give td_qwen2_load_param_int4 the rest first", fn, (f)->i4_loaded,         \
+                 (int)(f)->i4_have.size());                                                                                                                    \
+    TD_CHECK_ARG(!(f)->w8_stale, "%s: parameters were loaded after the weights were quantised; call td_qwen2_quantize_weights again first", fn);              \
+  } while (0)
 
 // two rows on one slot would write the same cache row: refused, not left to corrupt a sequence
 int check_distinct_slots(const char* fn, const char* unit, const int* slots, int B) {
@@ -517,6 +542,9 @@ int td_qwen2_quantize_weights(td_qwen2* f, int mode, void* stream) {
                "td_qwen2_quantize_weights: unknown mode %d (TD_QWEN2_WEIGHTS_E4M3 = %d and TD_QWEN2_WEIGHTS_MXFP4 = %d are the ones served)", mode, TD_QWEN2_WEIGHTS_E4M3,
                TD_QWEN2_WEIGHTS_MXFP4);
   const bool mx4 = mode == TD_QWEN2_WEIGHTS_MXFP4;
+  TD_CHECK_ARG(f->w_mode != TD_QWEN2_WEIGHTS_INT4,
+               "td_qwen2_quantize_weights: the handle holds AWQ / GPTQ int4 weights (TD_QWEN2_WEIGHTS_INT4), and one handle holds one weight format: its decoder "
+               "Linears came quantised and are not quantised again");
   // the arena holds W^ of the mode it was quantised in, not the weights it was loaded with: another format would quantise the wrong model
   TD_CHECK_ARG(f->w_mode == TD_QWEN2_WEIGHTS_BF16 || f->w_mode == mode || f->w8_stale,
                "td_qwen2_quantize_weights: the handle was quantised as %s and its original weights are gone; load its parameters again before quantising as %s",
@@ -579,6 +607,16 @@ int td_qwen2_set_weight_stream(td_qwen2* f, int on) {
   return prev;
 }
 
+int td_qwen2_set_int4_routing(td_qwen2* f, int all) {
+  TD_CHECK_ARG(all == 0 || all == 1, "td_qwen2_set_int4_routing: all=%d: 0 (the measured row counts) or 1 (every row count the int4 forms take)", all);
+  TD_CHECK_ARG(f, "td_qwen2_set_int4_routing: null handle");
+  TD_CHECK_ARG(f->w_mode == TD_QWEN2_WEIGHTS_INT4, "td_qwen2_set_int4_routing: the handle holds no int4 weights (td_qwen2_load_param_int4 first)");
+  const int prev = f->i4_route_all ? 1 : 0;
+  f->i4_route_all = all != 0;
+  drop_step_graphs(f);      // the captured steps carry the old launch list
+  return prev;
+}
+
 int64_t td_qwen2_weight_stream_launches(const td_qwen2* f) { return f ? (int64_t)f->w8_launches : -1; }
 
 int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* bytes_8bit, int* n_linears) {
@@ -602,12 +640,116 @@ int td_qwen2_param_info(const td_qwen2* f, int idx, char* name_buf, int buf_len,
   return TD_OK;
 }
 
+namespace {
+// Is slot `s` one of the 7 x layers decoder Linear weights a checkpoint quantises?  Then: its layer, which of q, k, v, o, gate, up, down it is, its extents,
+// its first row in the fused Linear the engine runs (q|k|v and gate|up are row concatenations) and that Linear's copy.
+bool int4_linear_of(td_qwen2* f, const QSlot& s, int* layer, int* which, int* N, int* K, int* row0, W8Ref** ref) {
+  const int D = f->D, I = f->I, QW = f->Hq * 128, KVW = f->Hkv * 128;
+  for (int i = 0; i < (int)f->layers.size(); ++i) {
+    QLayer& l = f->layers[i];
+    struct Cand { bf16_t* p; int N, K, row0; W8Ref* ref; };
+    const Cand c[7] = {{l.qkv_w, QW, D, 0, &l.qkv_8}, {l.qkv_w + (int64_t)QW * D, KVW, D, QW, &l.qkv_8}, {l.qkv_w + (int64_t)(QW + KVW) * D, KVW, D, QW + KVW, &l.qkv_8},
+                       {l.o_w, D, QW, 0, &l.o_8}, {l.gu_w, I, D, 0, &l.gu_8}, {l.gu_w + (int64_t)I * D, I, D, I, &l.gu_8}, {l.down_w, D, I, 0, &l.down_8}};
+    for (int w = 0; w < 7; ++w)
+      if (s.ptr == c[w].p && s.count == (int64_t)c[w].N * c[w].K) {
+        *layer = i; *which = w; *N = c[w].N; *K = c[w].K; *row0 = c[w].row0; *ref = c[w].ref;
+        return true;
+      }
+  }
+  return false;
+}
+}  // namespace
+
+int td_qwen2_load_param_int4(td_qwen2* f, const char* name, const void* packed, const void* scales, const void* zeros, int G, void* stream) {
+  TD_CHECK_ARG(G == 32 || G == 64 || G == 128, "td_qwen2_load_param_int4: G=%d: the group sizes served are 32, 64 and 128", G);
+  TD_CHECK_ARG(f && name && packed && scales && zeros, "td_qwen2_load_param_int4: the handle, name, packed, scales and zeros are required");
+  TD_CHECK_ARG((uintptr_t)packed % 4 == 0 && (uintptr_t)scales % 2 == 0, "td_qwen2_load_param_int4: misaligned operands: packed must be 4-byte aligned, scales 2-byte");
+  TD_CHECK_ARG(f->w_mode == TD_QWEN2_WEIGHTS_BF16 || f->w_mode == TD_QWEN2_WEIGHTS_INT4,
+               "td_qwen2_load_param_int4: the handle was quantised as %s, and one handle holds one weight format: create another handle for an AWQ / GPTQ checkpoint",
+               f->w_mode == TD_QWEN2_WEIGHTS_MXFP4 ? "TD_QWEN2_WEIGHTS_MXFP4" : "TD_QWEN2_WEIGHTS_E4M3");
+  TD_CHECK_ARG(f->i4_G == 0 || f->i4_G == G, "td_qwen2_load_param_int4: G=%d, but the handle holds int4 weights of group size %d: one handle, one group size", G, f->i4_G);
+  auto it = f->index.find(name);
+  TD_CHECK_ARG(it != f->index.end(), "td_qwen2_load_param_int4: unknown parameter '%s'", name);
+  const QSlot& s = f->slots[it->second];
+  int layer, which, N, K, row0;
+  W8Ref* ref;
+  TD_CHECK_ARG(int4_linear_of(f, s, &layer, &which, &N, &K, &row0, &ref),
+               "td_qwen2_load_param_int4: '%s' is not a decoder Linear weight (q / k / v / o / gate / up / down_proj.weight); everything else loads as bf16", name);
+  const int D = f->D, I = f->I, QW = f->Hq * 128, NQKV = (f->Hq + 2 * f->Hkv) * 128;
+  TD_CHECK_ARG(D % G == 0 && I % G == 0 && D % 32 == 0 && I % 32 == 0,
+               "td_qwen2_load_param_int4: G=%d must divide hidden=%d and intermediate=%d (and both must be multiples of 32, one 16-byte chunk of a packed row)", G, D, I);
+  if (!f->w8_arena) {      // the copy of all 4 x layers fused Linears, from their shapes
+    struct Lin { W8Ref* ref; int N, K; };
+    std::vector<Lin> lins;
+    for (QLayer& l : f->layers) {
+      lins.push_back({&l.qkv_8, NQKV, D});
+      lins.push_back({&l.o_8, D, QW});
+      lins.push_back({&l.gu_8, 2 * I, D});
+      lins.push_back({&l.down_8, D, I});
+    }
+    auto pad = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+    int64_t total = 0, bytes = 0;
+    for (const Lin& x : lins) {
+      const int64_t w = (int64_t)x.N * x.K / 2, g = (int64_t)x.N * (x.K / G);
+      total += pad(w) + pad(2 * g) + pad(g);
+      bytes += w + 3 * g;
+    }
+    hipError_t e = hipMalloc((void**)&f->w8_arena, (size_t)total);
+    if (e != hipSuccess) {
+      f->w8_arena = nullptr;
+      td_set_error("td_qwen2_load_param_int4: hipMalloc of %.2f GiB for the int4 copy failed: %s", total / double(1 << 30), hipGetErrorString(e));
+      return TD_ERR_HIP;
+    }
+    int64_t o = 0;
+    for (const Lin& x : lins) {
+      const int64_t w = (int64_t)x.N * x.K / 2, g = (int64_t)x.N * (x.K / G);
+      x.ref->q = (uint8_t*)(f->w8_arena + o); o += pad(w);
+      x.ref->s = f->w8_arena + o; o += pad(2 * g);
+      x.ref->z = (uint8_t*)(f->w8_arena + o); o += pad(g);
+    }
+    f->w8_bytes = bytes;      // (reported without the padding between the pieces)
+    f->w8_linears = 7 * (int)f->layers.size();
+    f->i4_have.assign((size_t)f->w8_linears, 0);
+    f->i4_loaded = 0;
+    f->i4_G = G;
+    f->w8_on = false;
+  }
+  drop_step_graphs(f);
+  f->w_mode = TD_QWEN2_WEIGHTS_INT4;
+  const bool was_whole = f->i4_loaded == (int)f->i4_have.size();
+  f->w8_stale = true;      // (a failing call below must not leave a half-loaded handle runnable)
+  const int ng = K / G;
+  uint8_t* dq = ref->q + (size_t)row0 * (K / 2);
+  uint16_t* ds = (uint16_t*)ref->s + (size_t)row0 * ng;
+  uint8_t* dz = ref->z + (size_t)row0 * ng;
+  TD_CHECK_HIP(hipMemcpyAsync(dq, packed, (size_t)N * (K / 2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  TD_CHECK_HIP(hipMemcpyAsync(ds, scales, (size_t)N * ng * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  TD_CHECK_HIP(hipMemcpyAsync(dz, zeros, (size_t)N * ng, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  TD_TRY(td_dequant_rows_int4_launch(dq, ds, dz, G, s.ptr, K, N, K, (hipStream_t)stream));      // W^ from the copy itself: the arena is what the stream reads
+  char& have = f->i4_have[(size_t)layer * 7 + which];
+  if (!have) { have = 1; ++f->i4_loaded; }
+  if (f->i4_loaded == (int)f->i4_have.size()) {
+    f->w8_stale = false;
+    if (!was_whole) f->w8_on = true;
+  }
+  return TD_OK;
+}
+
 int td_qwen2_load_param(td_qwen2* f, const char* name, const void* src, int64_t count, void* stream) {
   TD_CHECK_ARG(f && name && src, "td_qwen2_load_param: null argument");
   auto it = f->index.find(name);
   TD_CHECK_ARG(it != f->index.end(), "td_qwen2_load_param: unknown parameter '%s'", name);
   const QSlot& s = f->slots[it->second];
   TD_CHECK_ARG(s.count == count, "td_qwen2_load_param: '%s' expects %lld elements, got %lld", name, (long long)s.count, (long long)count);
+  if (f->w_mode == TD_QWEN2_WEIGHTS_INT4) {      // biases, norms, embeddings and lm_head have no int4 copy: they load as ever and leave the handle as it is
+    int layer, which, N, K, row0;
+    W8Ref* ref;
+    TD_CHECK_ARG(!int4_linear_of(f, s, &layer, &which, &N, &K, &row0, &ref),
+                 "td_qwen2_load_param: '%s' is a decoder Linear of a handle that holds int4 weights (TD_QWEN2_WEIGHTS_INT4), and one handle holds one weight format: "
+                 "load it through td_qwen2_load_param_int4, or create another handle for bf16 weights", name);
+    TD_CHECK_HIP(hipMemcpyAsync(s.ptr, src, (size_t)count * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return TD_OK;
+  }
   TD_CHECK_HIP(hipMemcpyAsync(s.ptr, src, (size_t)count * 2, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (f->w_mode != TD_QWEN2_WEIGHTS_BF16) f->w8_stale = true;      // the 8-bit copy no longer matches: td_qwen2_quantize_weights again
   return TD_OK;
@@ -615,6 +757,8 @@ int td_qwen2_load_param(td_qwen2* f, const char* name, const void* src, int64_t 
 
 int td_qwen2_init_random(td_qwen2* f, uint64_t seed, float std, void* stream) {
   TD_CHECK_ARG(f, "td_qwen2_init_random: null handle");
+  TD_CHECK_ARG(f->w_mode != TD_QWEN2_WEIGHTS_INT4, "td_qwen2_init_random: the handle holds int4 weights (TD_QWEN2_WEIGHTS_INT4), and one handle holds one weight "
+               "format: random bf16 weights over its decoder Linears would leave the int4 copy behind");
   if (f->w_mode != TD_QWEN2_WEIGHTS_BF16) f->w8_stale = true;
   if (f->kv_mode == TD_QWEN2_KV_BF16) {
     TD_TRY(td_fill_normal_bf16(f->arena, f->arena_elems, seed, std, 0.f, stream));
@@ -789,7 +933,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
   // so that step reads bf16 W^ -- the same model, no cost in numerics.  Measured on the 2B shape (hidden 1536) ONLY; the rule is drawn at the width
   // that already separates the two measured shapes (hidden < 3072), other narrow widths have not been timed.  The MXFP4 mode keeps the rule as it found it
   // (its own 2-sequence cell on the 2B shape was not timed); every other bucket measured faster on the nibbles than on bf16 W^ on both shapes
-  const bool a8 = !(B == 2 && D < 3072);
+  const bool a8 = f->w_mode == TD_QWEN2_WEIGHTS_INT4 || !(B == 2 && D < 3072);      // (INT4 has a table of its own for every row count: int4_rows_routed)
 
   TD_TRY(td_embed_gather_launch(f->tok_buf, f->embed_w, f->h, B, D, f->cfg.vocab, s));
   TD_TRY(td_mrope_table_launch(f->pos_buf, B, f->cfg.mrope_section, f->cfg.rope_theta, 1, f->cosT, f->sinT, s));

@@ -7,7 +7,8 @@ enum TdAct { TD_ACT_NONE = 0, TD_ACT_GELU_TANH = 1, TD_ACT_GELU_ERF = 2, TD_ACT_
 // every launcher that takes an activation code refuses one outside this range (no route has a fallback for it)
 inline bool td_act_valid(int act) { return act >= TD_ACT_NONE && act <= TD_ACT_QUICK_GELU; }
 
-struct TdGemmParams {
+// (TdGemmArgs: what every GEMM / skinny-M kernel takes as its argument block; TdGemmParams below is what the launchers take)
+struct TdGemmArgs {
   const bf16_t* A = nullptr;     // [M, lda]  activations, K-contiguous
   const bf16_t* W = nullptr;     // [N, K]    torch Linear weight layout
   const bf16_t* bias = nullptr;  // [N] or null
@@ -80,6 +81,15 @@ struct TdGemmParams {
   const uint8_t* W4 = nullptr; const uint8_t* w4_scale = nullptr;
 };
 
+// ... plus the grouped int4 weight stream.  A part of its own: only the I4 forms of the skinny-M kernels take the whole struct, every other kernel takes the
+// TdGemmArgs part, so its argument block -- and the code hipcc makes around it -- is what it was before this form existed.
+struct TdGemmParams : TdGemmArgs {
+  // grouped int4 weight stream (AWQ / GPTQ checkpoints; skinny-M kernels only, M <= 64; W, W8 and W4 are then unused): I4 = uint4 nibbles [N, K / 2] (gated
+  // form: [2 glu_I, K / 2]), i4_scale = fp16 bits [N, K / G], i4_zero = zero points 0 .. 15 [N, K / G], i4_gshift = log2(G), G in {32, 64, 128}: the format
+  // td_repack_int4_launch writes (csrc/int4_group.h).  The kernels see the bf16 values bf16_rne((q - z) s) exactly.
+  const uint8_t* I4 = nullptr; const uint16_t* i4_scale = nullptr; const uint8_t* i4_zero = nullptr; int i4_gshift = 0;
+};
+
 int td_gemm_launch(const TdGemmParams& p, hipStream_t stream);
 // weight-streaming form for M <= 8 (td_gemm_launch routes to it; csrc/gemv_bf16.hip)
 int td_gemv_launch(const TdGemmParams& p, hipStream_t stream);
@@ -93,6 +103,15 @@ bool td_gemv_w4_ok(const TdGemmParams& p);     // shapes the 4-bit weight stream
 // scales [N, K / 32]; w_hat (may be null, may alias w) = q 2^e as bf16, exactly.  The second entry rebuilds w_hat from the bytes.
 int td_quant_weight_rows_mxfp4_launch(const bf16_t* w, long long ldw, uint8_t* packed, uint8_t* scales, bf16_t* w_hat, int N, int K, hipStream_t stream);
 int td_dequant_rows_mxfp4_launch(const uint8_t* packed, const uint8_t* scales, bf16_t* w_hat, long long ldw, int N, int K, hipStream_t stream);
+bool td_gemv_i4_ok(const TdGemmParams& p);     // shapes the grouped int4 weight stream takes (p.I4 need not be set yet; p.i4_gshift must be)
+// Grouped int4 (csrc/quant_weight.hip; the format: csrc/int4_group.h).  td_repack_int4_launch turns one checkpoint Linear -- layout 0: AutoAWQ "GEMM"
+// (qweight int32 [K, N / 8], qzeros int32 [K / G, N / 8], scales fp16 [K / G, N]), 1: AutoGPTQ 4-bit (qweight int32 [K / 8, N], qzeros int32 [K / G, N / 8]
+// stored as z - 1, scales fp16 [K / G, N]), 1 | 2: the same with checkpoint_format "gptq_v2" (zeros stored as they are) -- into packed [N, K / 2],
+// scales fp16 [N, K / G], zeros uint8 [N, K / G] in one launch.  g_idx (may be null) is not read: only the trivial map k / G is served and the caller vouches
+// for it.  td_dequant_rows_int4_launch yields w^ = bf16_rne((q - z) s) as bf16 [N, ldw].
+int td_repack_int4_launch(int layout, const int* qweight, const int* qzeros, const uint16_t* scales_in, const int* g_idx, int N, int K, int G, uint8_t* packed,
+                          uint16_t* scales, uint8_t* zeros, hipStream_t stream);
+int td_dequant_rows_int4_launch(const uint8_t* packed, const uint16_t* scales, const uint8_t* zeros, int G, bf16_t* w_hat, long long ldw, int N, int K, hipStream_t stream);
 // 0: 256x256 (td_gemm_bf16_nt_kernel<8,4>), 1: 256x64, 2: 32x256, 3: 288x192 (<9,3>)
 int td_gemm_config_id(int M, int N, int K);
 // The same choice under the caller's shared-chip hint (shared != 0; TdGemmParams::no_tail): the tile that costs the least CU time, per operand type

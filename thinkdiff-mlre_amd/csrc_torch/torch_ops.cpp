@@ -189,6 +189,69 @@ at::Tensor linear_w4(const at::Tensor& x, const at::Tensor& packed, const at::Te
   return y;
 }
 
+namespace {
+// packed uint8 [N,K/2], scales fp16 [N,K/G], zeros uint8 [N,K/G], all contiguous on one device, G one of 32 / 64 / 128
+void check_int4(const at::Tensor& packed, const at::Tensor& scales, const at::Tensor& zeros, int64_t G, const char* op) {
+  check_rows(packed, "packed", at::kByte); check_rows(scales, "scales", at::kHalf); check_rows(zeros, "zeros", at::kByte);
+  same_device(scales, "scales", packed); same_device(zeros, "zeros", packed);
+  TORCH_CHECK(G == 32 || G == 64 || G == 128, "thinkdiff_hip::", op, ": group_size ", G, " is not one of 32, 64, 128");
+  const int64_t K = packed.dim() == 2 ? packed.size(1) * 2 : 0;
+  TORCH_CHECK(packed.dim() == 2 && packed.is_contiguous() && scales.dim() == 2 && scales.is_contiguous() && zeros.dim() == 2 && zeros.is_contiguous() &&
+                  packed.size(0) > 0 && K > 0 && K % G == 0 && K % 32 == 0 && scales.size(0) == packed.size(0) && scales.size(1) == K / G &&
+                  zeros.size(0) == packed.size(0) && zeros.size(1) == K / G,
+              "thinkdiff_hip::", op, ": packed uint8 [N,K/2], scales float16 [N,K/G] and zeros uint8 [N,K/G], all contiguous, K a multiple of G and of 32");
+}
+}  // namespace
+
+// One AWQ (layout 0) / GPTQ (1; 3 = gptq_v2) checkpoint Linear -> (packed uint8 [N,K/2], scales float16 [N,K/G], zeros uint8 [N,K/G]) (td_repack_int4)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> repack_int4(int64_t layout, const at::Tensor& qweight, const at::Tensor& qzeros, const at::Tensor& scales, int64_t G) {
+  check_rows(qweight, "qweight", at::kInt); check_rows(qzeros, "qzeros", at::kInt); check_rows(scales, "scales", at::kHalf);
+  same_device(qzeros, "qzeros", qweight); same_device(scales, "scales", qweight);
+  TORCH_CHECK(layout == 0 || layout == 1 || layout == 3, "thinkdiff_hip::repack_int4: layout ", layout, " is not 0 (AWQ), 1 (GPTQ) or 3 (GPTQ v2)");
+  TORCH_CHECK(G == 32 || G == 64 || G == 128, "thinkdiff_hip::repack_int4: group_size ", G, " is not one of 32, 64, 128");
+  TORCH_CHECK(qweight.dim() == 2 && qweight.is_contiguous() && qzeros.dim() == 2 && qzeros.is_contiguous() && scales.dim() == 2 && scales.is_contiguous(),
+              "thinkdiff_hip::repack_int4: qweight, qzeros and scales must be contiguous matrices");
+  const int64_t K = layout == 0 ? qweight.size(0) : qweight.size(0) * 8, N = layout == 0 ? qweight.size(1) * 8 : qweight.size(1);
+  TORCH_CHECK(N > 0 && K > 0 && N % 8 == 0 && K % G == 0 && K % 32 == 0 && qzeros.size(0) == K / G && qzeros.size(1) == N / 8 && scales.size(0) == K / G && scales.size(1) == N,
+              "thinkdiff_hip::repack_int4: qzeros must be int32 [K/G,N/8] and scales float16 [K/G,N] for the N=", N, ", K=", K, " of qweight");
+  DeviceGuard guard(qweight.device());
+  at::Tensor packed = at::empty({N, K / 2}, qweight.options().dtype(at::kByte));
+  at::Tensor s_out = at::empty({N, K / G}, qweight.options().dtype(at::kHalf));
+  at::Tensor z_out = at::empty({N, K / G}, qweight.options().dtype(at::kByte));
+  ok(td_repack_int4((int)layout, qweight.data_ptr(), qzeros.data_ptr(), scales.data_ptr(), nullptr, (int)N, (int)K, (int)G, packed.data_ptr(), s_out.data_ptr(),
+                    z_out.data_ptr(), stream_of(qweight)));
+  return std::make_tuple(packed, s_out, z_out);
+}
+
+// packed, scales, zeros -> bf16 [N,K] = bf16_rne((q - z) s) (td_dequant_rows_int4)
+at::Tensor dequant_rows_int4(const at::Tensor& packed, const at::Tensor& scales, const at::Tensor& zeros, int64_t G) {
+  check_int4(packed, scales, zeros, G, "dequant_rows_int4");
+  DeviceGuard guard(packed.device());
+  at::Tensor w_hat = at::empty({packed.size(0), packed.size(1) * 2}, packed.options().dtype(at::kBFloat16));
+  ok(td_dequant_rows_int4(packed.data_ptr(), scales.data_ptr(), zeros.data_ptr(), (int)G, w_hat.data_ptr(), w_hat.stride(0), (int)packed.size(0),
+                          (int)packed.size(1) * 2, stream_of(packed)));
+  return w_hat;
+}
+
+// linear with the weight given as grouped int4 nibbles + fp16 group scales + zero points (the AWQ / GPTQ weight stream, M <= 64)
+at::Tensor linear_i4(const at::Tensor& x, const at::Tensor& packed, const at::Tensor& scales, const at::Tensor& zeros, int64_t G,
+                     const c10::optional<at::Tensor>& bias, int64_t act, const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& res) {
+  check_rows(x, "x"); same_device(packed, "packed", x);
+  check_int4(packed, scales, zeros, G, "linear_i4");
+  TORCH_CHECK(x.dim() == 2 && packed.size(1) * 2 == x.size(1), "thinkdiff_hip::linear_i4: x [M,K], packed uint8 [N,K/2]");
+  check_vec(bias, "bias", x, packed.size(0)); check_vec(gate, "gate", x, packed.size(0));
+  if (res.has_value() && res->defined()) {
+    check_rows(*res, "res"); same_device(*res, "res", x);
+    TORCH_CHECK(res->dim() == 2 && res->size(0) == x.size(0) && res->size(1) == packed.size(0), "thinkdiff_hip::linear_i4: res must be [M,N]");
+  }
+  DeviceGuard guard(x.device());
+  at::Tensor y = at::empty({x.size(0), packed.size(0)}, x.options());
+  const int64_t ldr = res.has_value() && res->defined() ? res->stride(0) : 0;
+  ok(td_linear_i4_bf16(x.data_ptr(), x.stride(0), packed.data_ptr(), scales.data_ptr(), zeros.data_ptr(), (int)G, P(bias), y.data_ptr(), y.stride(0),
+                       (int)x.size(0), (int)packed.size(0), (int)x.size(1), (int)act, P(gate), P(res), ldr, stream_of(x)));
+  return y;
+}
+
 // ThinkDiff aligner mm_projector "mlp2x_gelu_t5_norm": T5LayerNorm(Linear2(GELU_erf(Linear0(x))))
 at::Tensor aligner_mlp2x(const at::Tensor& x, const at::Tensor& w0, const at::Tensor& b0, const at::Tensor& w2, const at::Tensor& b2,
                          const at::Tensor& norm_w, double eps, bool fp32_norm) {
@@ -1102,6 +1165,9 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("quant_weight_rows_mxfp4(Tensor w) -> (Tensor, Tensor, Tensor)");
   m.def("dequant_rows_mxfp4(Tensor packed, Tensor scales) -> Tensor");
   m.def("linear_w4(Tensor x, Tensor packed, Tensor scales, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
+  m.def("repack_int4(int layout, Tensor qweight, Tensor qzeros, Tensor scales, int group_size) -> (Tensor, Tensor, Tensor)");
+  m.def("dequant_rows_int4(Tensor packed, Tensor scales, Tensor zeros, int group_size) -> Tensor");
+  m.def("linear_i4(Tensor x, Tensor packed, Tensor scales, Tensor zeros, int group_size, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor");
   m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
   m.def("kv_gather_rows(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()");
   m.def("attention_verify(Tensor q, Tensor k, Tensor v, Tensor? k_scale, Tensor? v_scale, Tensor seq_row0, Tensor seq_rows, Tensor seq_len0, Tensor seq_slot, int Hq, int Hkv, float scale) -> Tensor");
@@ -1161,6 +1227,9 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("quant_weight_rows_mxfp4", &quant_weight_rows_mxfp4);
   m.impl("dequant_rows_mxfp4", &dequant_rows_mxfp4);
   m.impl("linear_w4", &linear_w4);
+  m.impl("repack_int4", &repack_int4);
+  m.impl("dequant_rows_int4", &dequant_rows_int4);
+  m.impl("linear_i4", &linear_i4);
   m.impl("kv_fork_rows", &kv_fork_rows);
   m.impl("kv_gather_rows", &kv_gather_rows);
   m.impl("beam_select", &beam_select);

@@ -231,6 +231,13 @@ def _declare(L):
         "td_linear_w4_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp],
         "td_linear_split_w4_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
         "td_linear_glu_w4_bf16": [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp],
+        "td_repack_int4": [i32, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp],
+        "td_dequant_rows_int4": [vp, vp, vp, i32, vp, i64, i32, i32, vp],
+        "td_linear_i4_bf16": [vp, i64, vp, vp, vp, i32, vp, vp, i64, i32, i32, i32, i32, vp, vp, i64, vp],
+        "td_linear_split_i4_bf16": [vp, i64, vp, vp, vp, i32, vp, vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, vp],
+        "td_linear_glu_i4_bf16": [vp, i64, vp, vp, vp, i32, vp, i64, i32, i32, i32, vp],
+        "td_qwen2_load_param_int4": [vp, ctypes.c_char_p, vp, vp, vp, i32, vp],
+        "td_qwen2_set_int4_routing": [vp, i32],
         "td_embed_gather_bf16": [vp, vp, vp, i32, i32, i32, vp],
         "td_silu_mul_bf16": [vp, vp, i32, i32, vp],
         "td_mrope_table": [vp, i32, vp, f32, i32, vp, vp, vp],
@@ -321,7 +328,9 @@ def linear(x, w, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
     return out
 
 
-QWEN2_WEIGHTS_BF16, QWEN2_WEIGHTS_E4M3, QWEN2_WEIGHTS_MXFP4 = 0, 1, 2
+QWEN2_WEIGHTS_BF16, QWEN2_WEIGHTS_E4M3, QWEN2_WEIGHTS_MXFP4, QWEN2_WEIGHTS_INT4 = 0, 1, 2, 3
+INT4_AWQ, INT4_GPTQ, INT4_GPTQ_V2 = 0, 1, 2      # td_repack_int4 layouts; INT4_GPTQ_V2 is a flag on INT4_GPTQ (zero points stored as they are)
+INT4_GROUP_SIZES = (32, 64, 128)
 
 
 def quant_weight_rows_e4m3(w, want_w_hat=True, inplace=False):
@@ -470,6 +479,76 @@ def linear_glu_w4(x, packed, scales, out=None):
     if out is None:
         out = torch.empty((M, N2 // 2), dtype=torch.bfloat16, device=x.device)
     check(lib().td_linear_glu_w4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(out), _rows(out), M, N2 // 2, K, stream_ptr()))
+    return out
+
+
+def repack_int4(layout, qweight, qzeros, scales, G, g_idx=None):
+    """One AWQ / GPTQ checkpoint Linear -> the device layout of the grouped int4 weight stream (td_repack_int4), in one launch.
+    layout INT4_AWQ: qweight int32 [K, N / 8], qzeros int32 [K / G, N / 8], scales fp16 [K / G, N] (AutoAWQ "GEMM");
+    layout INT4_GPTQ (| INT4_GPTQ_V2): qweight int32 [K / 8, N], qzeros int32 [K / G, N / 8], scales fp16 [K / G, N]; g_idx is not read (only k // G is served).
+    -> (packed uint8 [N, K / 2], scales fp16 [N, K / G], zeros uint8 [N, K / G]).  The nibble order inside `packed` is the library's own."""
+    assert qweight.dtype == torch.int32 and qzeros.dtype == torch.int32 and scales.dtype == torch.float16, (qweight.dtype, qzeros.dtype, scales.dtype)
+    assert qweight.dim() == 2 and qweight.is_contiguous() and qzeros.is_contiguous() and scales.is_contiguous()
+    if layout == INT4_AWQ:
+        K, N = qweight.shape[0], qweight.shape[1] * 8
+    else:
+        K, N = qweight.shape[0] * 8, qweight.shape[1]
+    assert G in INT4_GROUP_SIZES and K % G == 0, (K, G)
+    assert qzeros.shape == (K // G, N // 8) and scales.shape == (K // G, N), (qzeros.shape, scales.shape, N, K, G)
+    dev = qweight.device
+    packed = torch.empty((N, K // 2), dtype=torch.uint8, device=dev)
+    s_out = torch.empty((N, K // G), dtype=torch.float16, device=dev)
+    z_out = torch.empty((N, K // G), dtype=torch.uint8, device=dev)
+    check(lib().td_repack_int4(layout, ptr(qweight), ptr(qzeros), ptr(scales), ptr(g_idx), N, K, G, ptr(packed), ptr(s_out), ptr(z_out), stream_ptr()))
+    return packed, s_out, z_out
+
+
+def _i4(x, packed, scales, zeros, G):
+    M, K = x.shape
+    N = packed.shape[0]
+    assert packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous() and packed.shape[1] * 2 == K, (packed.shape, packed.dtype, K)
+    assert scales.dtype == torch.float16 and scales.is_contiguous() and scales.shape == (N, K // G), (scales.shape, scales.dtype, K, G)
+    assert zeros.dtype == torch.uint8 and zeros.is_contiguous() and zeros.shape == (N, K // G), (zeros.shape, zeros.dtype, K, G)
+    return M, N, K
+
+
+def dequant_rows_int4(packed, scales, zeros, G, out=None):
+    """packed [N, K / 2] + scales fp16 [N, K / G] + zeros uint8 [N, K / G] -> bf16 [N, K] = bf16_rne((q - z) s): one rounding (td_dequant_rows_int4)."""
+    assert packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous()
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert scales.dtype == torch.float16 and zeros.dtype == torch.uint8 and scales.is_contiguous() and zeros.is_contiguous()
+    assert scales.shape == (N, K // G) and zeros.shape == (N, K // G), (scales.shape, zeros.shape, N, K, G)
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.bfloat16, device=packed.device)
+    assert out.dtype == torch.bfloat16 and out.stride(1) == 1
+    check(lib().td_dequant_rows_int4(ptr(packed), ptr(scales), ptr(zeros), G, ptr(out), out.stride(0), N, K, stream_ptr()))
+    return out
+
+
+def linear_i4(x, packed, scales, zeros, G, bias=None, act=ACT_NONE, gate=None, res=None, out=None):
+    """linear() with the weight as grouped int4 nibbles + fp16 group scales + zero points (the AWQ / GPTQ weight stream; M <= 64)."""
+    M, N, K = _i4(x, packed, scales, zeros, G)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_i4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(zeros), G, ptr(bias), ptr(out), _rows(out), M, N, K, act,
+                                  ptr(gate), ptr(res), _rows(res) if res is not None else 0, stream_ptr()))
+    return out
+
+
+def linear_split_i4(x, packed, scales, zeros, G, bias, out0, act0, out1, act1, n_split):
+    M, N, K = _i4(x, packed, scales, zeros, G)
+    check(lib().td_linear_split_i4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(zeros), G, ptr(bias), ptr(out0), _rows(out0), act0,
+                                        ptr(out1), _rows(out1), act1, M, N, K, n_split, stream_ptr()))
+    return out0, out1
+
+
+def linear_glu_i4(x, packed, scales, zeros, G, out=None):
+    """linear_glu() with the weight as grouped int4 nibbles + fp16 group scales + zero points."""
+    M, N2, K = _i4(x, packed, scales, zeros, G)
+    assert N2 % 2 == 0
+    if out is None:
+        out = torch.empty((M, N2 // 2), dtype=torch.bfloat16, device=x.device)
+    check(lib().td_linear_glu_i4_bf16(ptr(x), _rows(x), ptr(packed), ptr(scales), ptr(zeros), G, ptr(out), _rows(out), M, N2 // 2, K, stream_ptr()))
     return out
 
 

@@ -885,6 +885,7 @@ class Qwen2VLTextEngine:
         self._h = h
         # set by the models from vllm_config["quantization"]: every load below then ends with quantize_weights (None: the bf16 engine, untouched)
         self.weight_quantization: Optional[str] = None
+        self.int4_config: Optional[dict] = None      # an AWQ / GPTQ checkpoint's own `quantization_config` (load_pretrained reads it from config.json)
         self._defer_quantize = False
         self.n_slots, self.slot_len = int(n_slots), max_model_len
         self.max_model_len = max_model_len
@@ -960,12 +961,110 @@ class Qwen2VLTextEngine:
     # the Linears a packed checkpoint may carry: the ones quantize_weights("mxfp4") quantises
     PACKED_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj", "lm_head")
 
+    # the Linears an AWQ / GPTQ checkpoint quantises (lm_head and the embedding table stay bf16 there), and the tensors such a Linear comes as
+    INT4_LINEARS = ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj")
+    INT4_TENSORS = ("qweight", "qzeros", "scales", "g_idx")
+
+    @staticmethod
+    def check_int4_config(cfg) -> dict:
+        """An AWQ / GPTQ checkpoint's `quantization_config` as the engine serves it -> {"layout": td_repack_int4's, "group_size": G}; anything else is a
+        ValueError naming the field.  Served: 4 bits, group_size 32 / 64 / 128; AWQ version "gemm" with zero points; GPTQ without act-order
+        (checkpoint_format "gptq" or "gptq_v2")."""
+        def bad(field, why):
+            return ValueError(f"Qwen2VLTextEngine: int4_config[{field!r}]={cfg.get(field)!r} is not served by the HIP engine: {why}")
+        if not isinstance(cfg, dict):
+            raise ValueError(f"Qwen2VLTextEngine: int4_config must be the checkpoint's quantization_config dict, got {type(cfg).__name__}")
+        method = cfg.get("quant_method")
+        if method not in ("awq", "gptq"):
+            raise bad("quant_method", "'awq' and 'gptq' are the int4 checkpoint formats it loads")
+        if cfg.get("bits") != 4:
+            raise bad("bits", "only 4-bit checkpoints (3- and 8-bit GPTQ are not built)")
+        G = cfg.get("group_size")
+        if G not in _hip.INT4_GROUP_SIZES:
+            raise bad("group_size", f"the group sizes served are {_hip.INT4_GROUP_SIZES} (no per-channel -1)")
+        if method == "awq":
+            if str(cfg.get("version", "gemm")).lower() != "gemm":
+                raise bad("version", "only AutoAWQ's 'gemm' layout (no 'gemv' / Marlin)")
+            if cfg.get("zero_point", True) is not True:
+                raise bad("zero_point", "the AWQ layout it reads carries zero points")
+            return {"layout": _hip.INT4_AWQ, "group_size": G}
+        if cfg.get("desc_act", False):
+            raise bad("desc_act", "act-order (a g_idx other than k // group_size) is not built")
+        fmt = cfg.get("checkpoint_format", "gptq")
+        if fmt not in ("gptq", "gptq_v2"):
+            raise bad("checkpoint_format", "'gptq' and 'gptq_v2' are the ones read (no Marlin)")
+        return {"layout": _hip.INT4_GPTQ | (_hip.INT4_GPTQ_V2 if fmt == "gptq_v2" else 0), "group_size": G}
+
+    def _split_int4(self, sd: Dict[str, torch.Tensor], table: Dict[str, int]):
+        """An AWQ / GPTQ state dict: a decoder Linear given as `<linear>.qweight` + `.qzeros` + `.scales` (+ `.g_idx`) instead of `.weight`.
+        -> (the dict without those tensors, [(weight name, layout, G, qweight, qzeros, scales)]).  Everything is checked here, on the host, before any
+        device work; anything malformed or unserved is a ValueError naming the key or the config field."""
+        me = "Qwen2VLTextEngine.load_state_dict"
+        bases = []
+        for k in sd:
+            base, _, suffix = k.rpartition(".")
+            if suffix in self.INT4_TENSORS and (base + ".weight" in table or base == "lm_head") and base not in bases:
+                bases.append(base)
+        if not bases:
+            return sd, []
+        if "lm_head" in bases:
+            key = next(k for k in sd if k.startswith("lm_head.") and k.rpartition(".")[2] in self.INT4_TENSORS)
+            raise ValueError(f"{me}: {key!r}: a quantised lm_head is not served (AWQ / GPTQ Qwen2-VL checkpoints keep lm_head and the embeddings in bf16)")
+        if self.int4_config is None:
+            raise ValueError(f"{me}: {bases[0] + '.qweight'!r} is an AWQ / GPTQ int4 tensor, but the engine has no int4_config (the checkpoint's "
+                             "quantization_config; load_pretrained reads it from config.json)")
+        if self.weight_quantization is not None:
+            raise ValueError(f"{me}: int4 tensors ({bases[0] + '.qweight'!r}) cannot be combined with weight_quantization={self.weight_quantization!r}: "
+                             "the checkpoint is quantised already, and one engine holds one weight format")
+        spec = self.check_int4_config(self.int4_config)
+        layout, G = spec["layout"], spec["group_size"]
+        awq = layout == _hip.INT4_AWQ
+        jobs = []
+        for base in bases:
+            name = base + ".weight"
+            if base.split(".")[-1] not in self.INT4_LINEARS:
+                raise ValueError(f"{me}: {base + '.qweight'!r}: only the decoder Linears {self.INT4_LINEARS} load as int4")
+            if name in sd:
+                raise ValueError(f"{me}: {name!r} is given both as bf16 and as int4 tensors")
+            for suffix in ("qweight", "qzeros", "scales"):
+                if base + "." + suffix not in sd:
+                    raise ValueError(f"{me}: int4 Linear {base!r} lacks {base + '.' + suffix!r}")
+            qw, qz, sc = sd[base + ".qweight"], sd[base + ".qzeros"], sd[base + ".scales"]
+            if qw.dtype != torch.int32 or qw.dim() != 2:
+                raise ValueError(f"{me}: {base + '.qweight'!r} is {qw.dtype} {tuple(qw.shape)}: expected a 2-D int32 tensor")
+            K, N = (qw.shape[0], qw.shape[1] * 8) if awq else (qw.shape[0] * 8, qw.shape[1])
+            if N * K != table[name] or K % G != 0 or K % 32 != 0 or N % 8 != 0:
+                raise ValueError(f"{me}: {base + '.qweight'!r} has shape {tuple(qw.shape)}: expected int32 "
+                                 f"{'[K, N / 8]' if awq else '[K / 8, N]'} with N K = {table[name]}, K a multiple of group_size {G} and of 32, N of 8")
+            if qz.dtype != torch.int32 or tuple(qz.shape) != (K // G, N // 8):
+                raise ValueError(f"{me}: {base + '.qzeros'!r} is {qz.dtype} {tuple(qz.shape)}: expected int32 {(K // G, N // 8)}")
+            if sc.dtype != torch.float16:
+                raise ValueError(f"{me}: {base + '.scales'!r} is {sc.dtype}: the scales must be float16 (bf16 scales are not served)")
+            if tuple(sc.shape) != (K // G, N):
+                raise ValueError(f"{me}: {base + '.scales'!r} has shape {tuple(sc.shape)}: expected float16 {(K // G, N)}")
+            if not bool(torch.isfinite(sc).all()):
+                raise ValueError(f"{me}: {base + '.scales'!r} holds a non-finite scale")
+            if base + ".g_idx" in sd:
+                gi = sd[base + ".g_idx"]
+                if awq or tuple(gi.shape) != (K,) or not torch.equal(gi.to("cpu", torch.int64), torch.arange(K) // G):
+                    raise ValueError(f"{me}: {base + '.g_idx'!r} is not the map k // group_size of a GPTQ checkpoint without act-order (desc_act is not built)")
+            jobs.append((name, layout, G, qw, qz, sc))
+        drop = {b + "." + t for b in bases for t in self.INT4_TENSORS}
+        return {k: t for k, t in sd.items() if k not in drop}, jobs
+
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         table = self.param_table()
+        sd, int4_jobs = self._split_int4(sd, table)
         sd = self._dequantize_packed(sd, table)
-        missing = [k for k in table if k not in sd]
+        as_int4 = {job[0] for job in int4_jobs}
+        missing = [k for k in table if k not in sd and k not in as_int4]
         if strict and missing:
             raise KeyError(f"Qwen2VLTextEngine.load_state_dict: missing {missing[:4]}..")
+        for name, layout, G, qw, qz, sc in int4_jobs:      # repacked into the device layout, then into the arena (as W^) and the handle's int4 copy
+            dev = [t.to(self.device).contiguous() for t in (qw, qz, sc)]
+            packed, scales, zeros = _hip.repack_int4(layout, dev[0], dev[1], dev[2], G)
+            _hip.check(self._L.td_qwen2_load_param_int4(self._h, name.encode(), _hip.ptr(packed), _hip.ptr(scales), _hip.ptr(zeros), G, _hip.stream_ptr()))
+            torch.cuda.current_stream().synchronize()
         for name, t in sd.items():
             if name in table:
                 d = t.to(device=self.device, dtype=torch.bfloat16).contiguous()
@@ -980,13 +1079,34 @@ class Qwen2VLTextEngine:
             self.quantize_weights(self.weight_quantization)
 
     def load_pretrained(self, path: str):
-        """Text-decoder tensors of a LOCAL Hugging Face Qwen2-VL checkpoint directory (*.safetensors; `visual.*` skipped)."""
+        """Text-decoder tensors of a LOCAL Hugging Face Qwen2-VL checkpoint directory (*.safetensors; `visual.*` skipped).  A config.json beside the
+        shards whose `quantization_config` says quant_method "awq" or "gptq" (the published Qwen2-VL-*-Instruct-AWQ / -GPTQ-Int4) becomes `int4_config`
+        and the decoder Linears load as int4 -- what vLLM does with `quantization` left unset."""
         import glob
+        import json
         import os
         from safetensors import safe_open
         files = sorted(glob.glob(os.path.join(path, "*.safetensors")))
         if not files:
             raise FileNotFoundError(f"no *.safetensors under {path}")
+        cfg_path = os.path.join(path, "config.json")
+        if os.path.exists(cfg_path):
+            with open(cfg_path) as fh:
+                qc = json.load(fh).get("quantization_config")
+            if isinstance(qc, dict) and qc.get("quant_method") in ("awq", "gptq"):
+                self.check_int4_config(qc)
+                self.int4_config = qc
+        if self.int4_config is not None:      # one dict for all shards: the three tensors of a Linear need not share a shard
+            sd = {}
+            for fn in files:
+                with safe_open(fn, framework="pt") as fh:
+                    for k in fh.keys():
+                        if "visual." not in k:
+                            sd[k.replace("model.language_model.", "model.")] = fh.get_tensor(k)
+            missing = [k for k in self.load_state_dict(sd, strict=False) if not (k == "lm_head.weight" and self.config.tie_word_embeddings)]
+            if missing:
+                raise KeyError(f"checkpoint at {path} lacks {len(missing)} decoder tensors, e.g. {missing[:3]}")
+            return self
         seen = set()
         self._defer_quantize = True      # (one quantisation behind the last shard, not one per shard)
         try:
@@ -1021,7 +1141,8 @@ class Qwen2VLTextEngine:
         """vllm_config["quantization"] as the models take it: None (bf16), "fp8" or "mxfp4"; anything else is an error, never ignored."""
         if value is not None and value not in cls.WEIGHT_QUANTIZATIONS:
             raise ValueError(f"vllm_config quantization={value!r} is not served by the HIP engine: only 'fp8' (weight-only e4m3) and 'mxfp4' "
-                             "(weight-only OCP MXFP4), or None for bf16")
+                             "(weight-only OCP MXFP4), or None for bf16.  AWQ / GPTQ int4 checkpoints are recognised from their own quantization_config "
+                             "(config.json beside the shards) with quantization left unset")
         return value
 
     def quantize_weights(self, quantization: str = "fp8"):
@@ -1044,6 +1165,15 @@ class Qwen2VLTextEngine:
             _hip.check(rc)
         return bool(rc)
 
+    def set_int4_routing(self, all_rows: bool) -> bool:
+        """Measurement and test switch of an int4 engine: with the stream on, every launch of up to 64 rows reads the int4 copy (True) or only the row
+        counts at which the int4 forms measured faster than the bf16 kernels (False, the default) -- the same model either way.  Returns the previous
+        setting."""
+        rc = self._L.td_qwen2_set_int4_routing(self._h, 1 if all_rows else 0)
+        if rc not in (0, 1):
+            _hip.check(rc)
+        return bool(rc)
+
     def weight_stream_launches(self) -> int:
         """Linear launches enqueued so far that read the 8-bit copy (a captured decode step counts when captured, not per replay)."""
         return int(self._L.td_qwen2_weight_stream_launches(self._h))
@@ -1051,7 +1181,8 @@ class Qwen2VLTextEngine:
     def weight_info(self) -> dict:
         mode, on, nbytes, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int()
         _hip.check(self._L.td_qwen2_weight_info(self._h, ctypes.byref(mode), ctypes.byref(on), ctypes.byref(nbytes), ctypes.byref(n)))
-        return {"mode": {v: k for k, v in self.WEIGHT_QUANTIZATIONS.items()}.get(mode.value, "bf16"), "stream_on": bool(on.value),
+        names = {**{v: k for k, v in self.WEIGHT_QUANTIZATIONS.items()}, _hip.QWEN2_WEIGHTS_INT4: "int4"}      # (int4: loaded, never quantised here)
+        return {"mode": names.get(mode.value, "bf16"), "stream_on": bool(on.value),
                 "bytes_8bit": int(nbytes.value), "n_linears": int(n.value)}
 
     # ---- e4m3 KV cache ----------------------------------------------------------------------------------------

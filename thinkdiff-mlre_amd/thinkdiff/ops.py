@@ -56,6 +56,9 @@ quant_weight_rows_e4m3 / linear_w8   weight-only fp8 of an nn.Linear (vLLM's `qu
 quant_weight_rows_mxfp4 / dequant_rows_mxfp4 / linear_w4   weight-only OCP MXFP4 of an nn.Linear (vLLM's `quantization="mxfp4"` on the LVLM): e2m1 nibbles (element 2j
                            in the low nibble of byte j) with one e8m0 scale byte per 32 weights of a row, back to bf16 (exact), and the Linear of up to 64 rows
                            that streams the nibbles
+repack_int4 / dequant_rows_int4 / linear_i4   the grouped int4 of AWQ / GPTQ checkpoints (asymmetric uint4, one fp16 scale and one 4-bit zero point per group of
+                           32 / 64 / 128 weights of a row): one checkpoint Linear (layout 0 = AutoAWQ "GEMM", 1 = AutoGPTQ, 3 = AutoGPTQ "gptq_v2") repacked into the
+                           device layout, that layout back to bf16 (bf16_rne((q - z) s): one rounding), and the Linear of up to 64 rows that streams the nibbles
 kv_quant_rows_e4m3 / kv_dequant_rows_e4m3 / attention_decode_kv8   the e4m3 KV cache of the LVLM's decode engine (vLLM's `kv_cache_dtype="fp8"`): e4m3 bytes with one
                            power-of-two scale per 128-wide head vector of a cache row, back to bf16 (exact), and the decode attention that reads bytes + scales
 kv_fork_rows               the first n_rows rows of one slot of a cache plane copied to many slots in one launch, each source chunk loaded once (what vLLM's
@@ -127,6 +130,9 @@ SCHEMAS = {
     "quant_weight_rows_mxfp4": "(Tensor w) -> (Tensor, Tensor, Tensor)",
     "dequant_rows_mxfp4": "(Tensor packed, Tensor scales) -> Tensor",
     "linear_w4": "(Tensor x, Tensor packed, Tensor scales, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor",
+    "repack_int4": "(int layout, Tensor qweight, Tensor qzeros, Tensor scales, int group_size) -> (Tensor, Tensor, Tensor)",
+    "dequant_rows_int4": "(Tensor packed, Tensor scales, Tensor zeros, int group_size) -> Tensor",
+    "linear_i4": "(Tensor x, Tensor packed, Tensor scales, Tensor zeros, int group_size, Tensor? bias, int act, Tensor? gate, Tensor? res) -> Tensor",
     "kv_quant_rows_e4m3": "(Tensor kv, int heads) -> (Tensor, Tensor, Tensor)",
     "kv_dequant_rows_e4m3": "(Tensor q, Tensor scale) -> Tensor",
     "attention_decode_kv8": "(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor? kv_lens, int Hq, int Hkv, float scale) -> Tensor",
