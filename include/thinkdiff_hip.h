@@ -130,6 +130,18 @@ int td_attention_varlen_bf16(const void* q, int64_t ldq, const void* k, const vo
  * q / k / v / o not 16-byte aligned, seg_starts not 4-byte aligned. */
 int td_attention_segments_bf16(const void* q, int64_t ldq, const void* k, const void* v, int64_t ldkv, void* o, int64_t ldo,
                                const int* seg_starts, int n_seg, int max_len, int Hq, int Hkv, float scale, int causal, void* stream);
+/* Context attention (td_abi_version() >= 23): the packed causal form over key ranges of their own -- prompts continued behind cached prefixes, what vLLM
+ * calls context attention.  Segment b owns q / o rows [seg_starts[b], seg_starts[b+1]) (Sq_b rows); its keys are rows [kv_row0[b], kv_row0[b] + kv_lens[b])
+ * of k / v, counted in rows of ldkv (a KV cache seen as rows: kv_row0[b] = slot x slot rows).  Query row i of the segment sees keys
+ * 0 .. kv_lens[b] - Sq_b + i: the last Sq_b keys are the segment's own tokens, the ones in front its prefix.  seg_starts int32[n_seg + 1], kv_row0 and
+ * kv_lens int32[n_seg], all DEVICE arrays.  max_q_len >= the longest query segment (it sizes the grid), max_kv_len >= the longest key range (it sizes the
+ * 4 GiB range check); either may exceed the longest.  The buffer descriptors cover the segment's own keys only, so rows of a neighbouring slot are never
+ * read; kv_lens[b] < Sq_b counts as Sq_b.  With every prefix empty and k / v the packed rows this is td_attention_segments_bf16(causal = 1).
+ * TD_ERR_INVALID before any HIP call for: an empty segment list, kv_row0 or kv_lens null, max_kv_len < max_q_len, a null operand, Hq % Hkv != 0, a row
+ * stride shorter than its heads, ldq or ldkv not a multiple of 8 elements, ldo not a multiple of 4, q / k / v / o not 16-byte aligned, an int array not
+ * 4-byte aligned. */
+int td_attention_prefix_segments_bf16(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldkv, int64_t ldo, const int* seg_starts,
+                                      const int* kv_row0, const int* kv_lens, int n_seg, int max_q_len, int max_kv_len, int Hq, int Hkv, float scale, void* stream);
 /* The joint attention in the form the FLUX engine calls it: q already carries scale x log2(e) (folded in where RoPE rounds q to bf16), so the
  * scores arrive in the exp2 domain; one batch entry, Hq == Hkv = H, head_dim 128.  score_bound in (0, 48]: a bound of |q'.k| (log2 units) the
  * caller vouches for -- the scores are then exponentiated as they are: no reference point, no per-tile row maximum, no rescale (a bf16 probability
@@ -906,6 +918,16 @@ int td_qwen2_prefill_packed(td_qwen2* f, int slot0, int B, const int* token_ids,
 /* ... sequence b into cache slot slots[b] (HOST ints, distinct, any order): the free slots of a running batch (continuous batching). */
 int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const int* token_ids, const void* inputs_embeds, const int* position_ids,
                                   const int* lens, void* hidden_out, void* logits_last, void* stream);
+/* ... behind cached prefixes (td_abi_version() >= 23; vLLM's automatic prefix caching needs it): sequence b feeds lens[b] >= 1 NEW rows, which go to cache
+ * rows [prefix_lens[b], prefix_lens[b] + lens[b]) of slot slots[b].  The caller vouches that the first prefix_lens[b] rows of that slot hold the keys and
+ * values of the tokens in front (same tokens, same position ids: the cached keys are rotated).  token_ids / inputs_embeds / position_ids / hidden_out /
+ * logits_last cover the new rows only, laid out as in td_qwen2_prefill_packed_slots; lens and prefix_lens are HOST ints.  Every prefix_lens[b] == 0: that
+ * entry itself, launch for launch.  bf16 cache: the attention reads K / V straight from the cache (td_attention_prefix_segments_bf16's form).  e4m3 cache:
+ * staged -- rows [0, prefix + len) of every sequence are dequantised into a buffer of ws_rows rows (allocated at the first such call), so a pass with
+ * sum(prefix_lens + lens) > ws_rows is refused.  TD_ERR_INVALID naming the value: a null argument, B outside 1 .. 256, a slot out of range or given twice,
+ * lens[b] < 1, prefix_lens[b] < 0, prefix_lens[b] + lens[b] above the slot capacity, sum(lens) > ws_rows. */
+int td_qwen2_prefill_packed_prefix_slots(td_qwen2* f, int B, const int* slots, const int* token_ids, const void* inputs_embeds, const int* position_ids,
+                                         const int* lens, const int* prefix_lens, void* hidden_out, void* logits_last, void* stream);
 int td_qwen2_set_slots(td_qwen2* f, int n_slots);   /* re-partition the cache rows of an existing handle */
 /* Decode step: the rotary embedding of the new q / k rows and the write of the new k | v rows into the cache happen inside the decode-attention
  * launch (default, one launch per layer fewer) or in a launch of their own (on = 0: A/B and the bit-identity test).  Same arithmetic either way

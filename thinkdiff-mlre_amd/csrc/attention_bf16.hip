@@ -43,7 +43,9 @@ __device__ __forceinline__ void attn_store_item(const TdAttnParams& p, const f32
 // accumulator zeroing.  Here every per-lane LDS address lives in a register for the whole kernel (8 for the K row reads,
 // 8 for the V transposed reads; k-block / k-step / tile-slot parts are instruction immediates).
 // ---------------------------------------------------------------------------------------------
-template <bool CAUSAL, int NWAVES, bool BIAS = false, bool VARLEN = false, bool PRE = false, bool RS = true, bool FIXED = false>
+// KVSEG (with CAUSAL and VARLEN): the packed query segments run over key ranges of their own (TdAttnParams::kv_seg_row0 / kv_seg_lens) -- context
+// attention, prompts continued behind cached prefixes.  Everything it changes sits behind `if constexpr (KVSEG)`.
+template <bool CAUSAL, int NWAVES, bool BIAS = false, bool VARLEN = false, bool PRE = false, bool RS = true, bool FIXED = false, bool KVSEG = false>
 __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(const TdAttnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [K slot 0 | K slot 1 | V slot 0 | V slot 1]
@@ -71,7 +73,16 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(c
     const int r0 = p.seg_starts[batch];
     Sq = Skv = p.seg_starts[batch + 1] - r0;
     if (qblk * (NWAVES * Q_WAVE) >= Sq) return;
-    Qb += (size_t)r0 * p.ldq; Kb += (size_t)r0 * p.ldkv; Vb += (size_t)r0 * p.ldkv; Ob += (size_t)r0 * p.ldo;
+    if constexpr (KVSEG) {
+      // ... its keys are rows [kv_seg_row0[b], + kv_seg_lens[b]) of K / V: the base pointers and, below, the descriptors are the segment's own, so a
+      // neighbouring slot's rows are out of range, not merely masked.  Device values are clamped, never trusted: fewer keys than queries count as Sq
+      const int k0 = max(p.kv_seg_row0[batch], 0);
+      Skv = max(p.kv_seg_lens[batch], Sq);
+      c_off = Skv - Sq;
+      Qb += (size_t)r0 * p.ldq; Kb += (size_t)k0 * p.ldkv; Vb += (size_t)k0 * p.ldkv; Ob += (size_t)r0 * p.ldo;
+    } else {
+      Qb += (size_t)r0 * p.ldq; Kb += (size_t)r0 * p.ldkv; Vb += (size_t)r0 * p.ldkv; Ob += (size_t)r0 * p.ldo;
+    }
   }
 
   const unsigned q_bytes = (unsigned)(((long long)(Sq - 1) * p.ldq + p.Hq * D) * 2);
@@ -446,6 +457,14 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   TD_CHECK_ARG(((long long)(p.Sq + 256) * p.ldq) * 2 < (1ll << 32) && ((long long)(p.Skv + 64) * p.ldkv) * 2 < (1ll << 32),
                "td_attention: per-batch operand exceeds the 4 GiB buffer-descriptor range");
   TD_CHECK_ARG(((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V | (uintptr_t)p.O) % 16 == 0, "td_attention: pointers must be 16-byte aligned");
+  if (p.kv_seg_row0 || p.kv_seg_lens) {   // packed query segments over key ranges of their own: one form, refused here, before the first HIP call
+    TD_CHECK_ARG(p.kv_seg_row0 && p.kv_seg_lens && p.seg_starts,
+                 "td_attention(prefix segments): kv_seg_row0 and kv_seg_lens are given together, and with seg_starts (kv_seg_row0 %s, kv_seg_lens %s, seg_starts %s)",
+                 p.kv_seg_row0 ? "set" : "null", p.kv_seg_lens ? "set" : "null", p.seg_starts ? "set" : "null");
+    TD_CHECK_ARG(p.causal && !p.bias && !p.kv_lens && !p.q_prescaled && !p.q8 && !p.K8,
+                 "td_attention(prefix segments): causal bf16 attention only (causal=%d; no bias%s, kv_lens%s, pre-scaled q%s, int8 output%s or e4m3 cache%s)", p.causal,
+                 p.bias ? " [given]" : "", p.kv_lens ? " [given]" : "", p.q_prescaled ? " [given]" : "", p.q8 ? " [given]" : "", p.K8 ? " [given]" : "");
+  }
   if (p.K8) {      // an e4m3 KV cache (TdAttnParams::K8): the decode kernel's 8-bit form, there is no tile kernel that reads it
     TD_CHECK_ARG(p.Sq == 1 && p.causal && !p.bias && !p.seg_starts && (p.kv_lens || p.causal_offset == p.Skv - 1),
                  "td_attention: an e4m3 KV cache is read by the decode form only (Sq = 1, causal, no bias, no packed segments)");
@@ -476,6 +495,11 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   TD_CHECK_ARG(p.score_bound >= 0.f && p.score_bound <= 48.f && (p.score_bound == 0.f || p.q_prescaled), "td_attention: a score bound goes with pre-scaled q (joint attention) and lies in (0, 48] octaves (0 = none)");
   if (p.q8) TD_CHECK_ARG(!p.causal && !p.bias && !p.kv_lens && !p.seg_starts && p.batch == 1 && p.q8_inv && p.q8_amax && p.ldq8 % 8 == 0 && ((uintptr_t)p.q8) % 8 == 0,
                          "td_attention: the int8 output form is for the joint attention of one batch entry, with 8-byte aligned rows");
+  if (p.seg_starts && p.kv_seg_row0) {   // ... with their own key ranges (checked on entry): Sq sizes the grid, Skv only the descriptor check above
+    if (int e = attn_launch<td_attn_fwd_d128_lean_kernel<true, NW, false, true, false, true, false, true>>(grid, NW * 64, lds, stream, dev, q)) return e;
+    TD_CHECK_LAUNCH();
+    return 0;
+  }
   if (p.seg_starts) {   // packed segments: plain grid over (query tiles of the longest segment, heads, segments)
     TD_CHECK_ARG(!p.bias && !p.kv_lens && p.Sq == p.Skv && (!p.causal || p.causal_offset == 0),
                  "td_attention(varlen): full or causal (offset 0) attention inside each segment only (no bias or cache lengths)");

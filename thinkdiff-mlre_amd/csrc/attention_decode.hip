@@ -599,6 +599,18 @@ __global__ __launch_bounds__(256) void td_kv_dequant_rows_kernel(const uint8_t* 
   *(u32x4_t*)(out + (size_t)r * ld + (size_t)h * 128 + 8 * j) = e4m3p2_to_bf16(b, scale[(size_t)r * lds + h]);
 }
 
+// ... row-mapped: out row r = cache row src_rows[r] (device ints): the rows of several sequences gathered into one packed staging buffer in one launch
+__global__ __launch_bounds__(256) void td_kv_dequant_rows_from_kernel(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld,
+                                                                      long long total, int heads, const int* src_rows) {
+  const long long unit = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (unit >= total) return;
+  const long long r = unit / heads;
+  const int h = (int)(unit - r * heads), j = threadIdx.x & 15;
+  const size_t sr = (size_t)max(src_rows[r], 0);
+  const u32x2_t b = *(const u32x2_t*)(q + sr * ldq + (size_t)h * 128 + 8 * j);
+  *(u32x4_t*)(out + (size_t)r * ld + (size_t)h * 128 + 8 * j) = e4m3p2_to_bf16(b, scale[sr * lds + h]);
+}
+
 }  // namespace
 
 int td_kv_quant_rows_launch(const bf16_t* kv, long long ld, uint8_t* q, long long ldq, float* scale, long long lds, bf16_t* kv_hat, int rows, int heads,
@@ -624,6 +636,21 @@ int td_kv_dequant_rows_launch(const uint8_t* q, long long ldq, const float* scal
                "td_kv_dequant_rows_e4m3: misaligned rows: out must be 16-byte aligned, q 8-byte, scale 4-byte");
   const long long total = (long long)rows * heads;
   hipLaunchKernelGGL(td_kv_dequant_rows_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, q, ldq, scale, lds, out, ld, total, heads);
+  TD_CHECK_LAUNCH();
+  return 0;
+}
+
+// out row r = the dequantised cache row src_rows[r] (device ints, the caller vouches that they name rows of q / scale; a negative one counts as 0)
+int td_kv_dequant_rows_from_launch(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld, int rows, int heads,
+                                   const int* src_rows, hipStream_t stream) {
+  TD_CHECK_ARG(q && scale && out && src_rows, "td_kv_dequant_rows_from: q, scale, out and src_rows are required");
+  TD_CHECK_ARG(heads > 0 && rows > 0, "td_kv_dequant_rows_from: rows=%d, heads=%d must be positive", rows, heads);
+  TD_CHECK_ARG(ld >= (long long)heads * 128 && ld % 8 == 0 && ldq >= (long long)heads * 128 && ldq % 8 == 0 && lds >= heads,
+               "td_kv_dequant_rows_from: ld=%lld, ldq=%lld must be multiples of 8 and at least heads x 128 = %lld, lds=%lld at least heads", ld, ldq, (long long)heads * 128, lds);
+  TD_CHECK_ARG((uintptr_t)out % 16 == 0 && (uintptr_t)q % 8 == 0 && (uintptr_t)scale % 4 == 0 && (uintptr_t)src_rows % 4 == 0,
+               "td_kv_dequant_rows_from: misaligned rows: out must be 16-byte aligned, q 8-byte, scale and src_rows 4-byte");
+  const long long total = (long long)rows * heads;
+  hipLaunchKernelGGL(td_kv_dequant_rows_from_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, stream, q, ldq, scale, lds, out, ld, total, heads, src_rows);
   TD_CHECK_LAUNCH();
   return 0;
 }

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 22; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 23; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -47,6 +47,8 @@ int td_abi_version(void) { return 22; }  // 2: TdFluxConfig::out_channels append
                                             //     td_qwen2_verify_batch_slots, td_spec_accept; csrc/spec_decode.hip)
                                             // 22: grouped int4 weight stream for AWQ / GPTQ checkpoints (td_repack_int4, td_dequant_rows_int4,
                                             //     td_linear*_i4_bf16, td_qwen2_load_param_int4, td_qwen2_set_int4_routing, TD_QWEN2_WEIGHTS_INT4)
+                                            // 23: prefix caching (td_attention_prefix_segments_bf16: packed query segments over key ranges of their own;
+                                            //     td_qwen2_prefill_packed_prefix_slots: the packed prefill behind cached prefixes)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -229,6 +231,30 @@ int td_attention_segments_bf16(const void* q, int64_t ldq, const void* k, const 
   p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo;
   p.scale = scale; p.causal = causal; p.causal_offset = 0; p.seg_starts = seg_starts;
   if (!causal) p.variant = 1;      // as td_attention_varlen_bf16 (the packed launch reads no variant; kept equal so that causal = 0 is that entry bit for bit)
+  return td_attn_launch(p, (hipStream_t)stream);
+}
+
+// Packed causal query segments over key ranges of their own (context attention; TdAttnParams::kv_seg_row0 / kv_seg_lens as the Qwen2-VL engine's prefill
+// behind cached prefixes fills them).  The refusals of td_attention_segments_bf16, before the first HIP call.
+int td_attention_prefix_segments_bf16(const void* q, const void* k, const void* v, void* o, int64_t ldq, int64_t ldkv, int64_t ldo, const int* seg_starts,
+                                      const int* kv_row0, const int* kv_lens, int n_seg, int max_q_len, int max_kv_len, int Hq, int Hkv, float scale, void* stream) {
+  TD_CHECK_ARG(seg_starts && n_seg > 0 && max_q_len > 0, "td_attention_prefix_segments: empty segment list (n_seg=%d, max_q_len=%d)", n_seg, max_q_len);
+  TD_CHECK_ARG(kv_row0 && kv_lens, "td_attention_prefix_segments: kv_row0 and kv_lens are both required (kv_row0 %s, kv_lens %s)", kv_row0 ? "set" : "null",
+               kv_lens ? "set" : "null");
+  TD_CHECK_ARG(max_kv_len >= max_q_len, "td_attention_prefix_segments: max_kv_len=%d is below max_q_len=%d (a segment has at least as many keys as queries)", max_kv_len, max_q_len);
+  TD_CHECK_ARG(q && k && v && o, "td_attention_prefix_segments: null operand");
+  TD_CHECK_ARG(Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "td_attention_prefix_segments: Hq=%d not a positive multiple of Hkv=%d", Hq, Hkv);
+  TD_CHECK_ARG(ldq >= (int64_t)Hq * 128 && ldkv >= (int64_t)Hkv * 128 && ldo >= (int64_t)Hq * 128 && ldq < (1ll << 31) && ldkv < (1ll << 31) && ldo < (1ll << 31),
+               "td_attention_prefix_segments: a row stride (ldq=%lld ldkv=%lld ldo=%lld) is shorter than its heads or outside the 32-bit range", (long long)ldq, (long long)ldkv, (long long)ldo);
+  TD_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 4 == 0,
+               "td_attention_prefix_segments: ldq=%lld and ldkv=%lld must be multiples of 8 elements (16 bytes), ldo=%lld of 4 (8 bytes)", (long long)ldq, (long long)ldkv, (long long)ldo);
+  TD_CHECK_ARG(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, "td_attention_prefix_segments: q, k, v and o must be 16-byte aligned");
+  TD_CHECK_ARG(((uintptr_t)seg_starts | (uintptr_t)kv_row0 | (uintptr_t)kv_lens) % 4 == 0, "td_attention_prefix_segments: seg_starts, kv_row0 and kv_lens must be 4-byte aligned");
+  TdAttnParams p;
+  p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)o;
+  p.batch = n_seg; p.Sq = max_q_len; p.Skv = max_kv_len; p.Hq = Hq; p.Hkv = Hkv; p.head_dim = 128;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo;
+  p.scale = scale; p.causal = 1; p.seg_starts = seg_starts; p.kv_seg_row0 = kv_row0; p.kv_seg_lens = kv_lens;
   return td_attn_launch(p, (hipStream_t)stream);
 }
 

@@ -11,10 +11,10 @@
 //
 // Layout: one fused [q | k | v] projection per layer (dual-output GEMM epilogue: q to scratch, k | v to their own rows) and a KV
 // cache of n_slots sequences x slot_len rows per layer.  Two layer loops:
-//   prefill_pass -- many rows at once, in three forms that differ only in where a layer's k|v rows are written, what carries them
+//   prefill_pass -- many rows at once, in four forms that differ only in where a layer's k|v rows are written, what carries them
 //     to the cache and what the attention reads (PrefillForm): one sequence at positions [pos0, pos0 + n) written straight into its
 //     cache rows (td_qwen2_forward_slot), a right-padded batch (td_qwen2_prefill_batch_at), prompts back to back
-//     (td_qwen2_prefill_packed_slots);
+//     (td_qwen2_prefill_packed_slots), prompts back to back behind cached prefixes (td_qwen2_prefill_packed_prefix_slots);
 //   decode_step -- one new token for each of up to 256 sequences, with a launch list of its own (weight-stream or split-K Linears,
 //     rotary embedding and cache write inside the attention launch), captured into a graph per batch size and replayed.
 // Parameters are addressed by their Hugging Face names (model.layers.N.self_attn.q_proj.weight, ...).
@@ -109,6 +109,10 @@ struct td_qwen2 {
     for (const Seg& g : segs) if (o >= g.off && o < g.off + g.n) return g.voff + (o - g.off);
     return o;
   }
+  // e4m3 cache, packed prefill behind cached prefixes (td_qwen2_prefill_packed_prefix_slots): the dequantised rows [0, prefix + len) of every sequence of a
+  // pass, packed per segment, and the cache row of every staged row.  ws_rows rows each, allocated at the first such pass.
+  bf16_t* kvstage = nullptr;
+  int* stage_map = nullptr;
   float* sk_ws = nullptr;                       // partial sums of the decode step's split-K Linears (65-256 sequences): the engine's own buffer, so a captured step allocates nothing
 };
 
@@ -279,6 +283,9 @@ struct PrefillForm {
   // to_rows[r], or (to_rows null) q8_cache_row0 + q8_tmp_row0 + r, and puts x^ back into kvtmp, which the attention reads (attn_kv = KV_TMP).  A continuation
   // (q8_tmp_row0 > 0) first dequantises cache rows [q8_cache_row0, q8_cache_row0 + q8_tmp_row0) into kvtmp rows [0, q8_tmp_row0): exact, x^ is a bf16 value.
   int q8_tmp_row0 = 0; long long q8_cache_row0 = 0;
+  // e4m3 cache behind cached prefixes (q8_stage_n > 0; to_rows given): once the new rows are in the cache, cache row q8_stage_rows[r] (device ints) is
+  // dequantised into row r of f->kvstage for r < q8_stage_n -- every sequence's rows [0, prefix + len), packed per segment -- and the attention reads kvstage
+  const int* q8_stage_rows = nullptr; int q8_stage_n = 0;
 };
 
 // Runs form.n rows through the decoder: embed (or take inputs_embeds), M-RoPE table, every layer, model.norm -- left in f->xn and copied to
@@ -328,11 +335,13 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
     if (kv8) {      // the quantising scatter runs BEFORE the attention, which then reads K^ | V^: no result depends on where a key came from
       const long long r0 = form.to_rows ? 0 : form.q8_cache_row0 + form.q8_tmp_row0;
       TD_TRY(td_kv_quant_rows_launch(kv_new, KVW, l.kv8 + (size_t)r0 * KVW, KVW, l.kvs + (size_t)r0 * 2 * Hkv, 2 * Hkv, kv_new, n, 2 * Hkv, form.to_rows, s));
+      if (form.q8_stage_n > 0)
+        TD_TRY(td_kv_dequant_rows_from_launch(l.kv8, KVW, l.kvs, 2 * Hkv, f->kvstage, KVW, form.q8_stage_n, 2 * Hkv, form.q8_stage_rows, s));
     } else if (form.to_rows)
       hipLaunchKernelGGL(td_kv_rows_to_rows_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv, form.to_rows, KVW);
     else if (form.to_slots >= 0)
       hipLaunchKernelGGL(td_kv_rows_to_slots_kernel, dim3((KVW / 8 + 255) / 256, n), dim3(256), 0, s, kv_new, l.kv + form.to_slots, form.slots_L, f->slot_len, KVW);
-    ap.K = kv8 ? f->kvtmp : form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
+    ap.K = kv8 ? (form.q8_stage_n > 0 ? f->kvstage : f->kvtmp) : form.attn_kv.of(f, l); ap.V = ap.K + Hkv * 128;
     TD_TRY(td_attn_launch(ap, s));
     // h += o_proj(attn)
     TD_TRY(run_linear(f, linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), l.o_8, s));
@@ -473,7 +482,7 @@ int td_qwen2_create_kv(const TdQwen2Config* cfg, int slot_len, int n_slots, int 
       {(void**)&f->h, n * D * 2}, {(void**)&f->xn, n * D * 2}, {(void**)&f->q, n * Hq * 128 * 2},
       {(void**)&f->attn, n * Hq * 128 * 2}, {(void**)&f->gu, n * 2 * I * 2}, {(void**)&f->act, n * I * 2},
       {(void**)&f->cosT, n * 128 * 4}, {(void**)&f->sinT, n * 128 * 4},
-      {(void**)&f->kvtmp, n * 2 * Hkv * 128 * 2}, {(void**)&f->ibuf, (5 * MAX_BATCH + 16) * 4}, {(void**)&f->lastrows, (int64_t)MAX_BATCH * D * 2},
+      {(void**)&f->kvtmp, n * 2 * Hkv * 128 * 2}, {(void**)&f->ibuf, (7 * MAX_BATCH + 16) * 4}, {(void**)&f->lastrows, (int64_t)MAX_BATCH * D * 2},
       {(void**)&f->tok_buf, MAX_BATCH * 4}, {(void**)&f->pos_buf, 3 * MAX_BATCH * 4}, {(void**)&f->logits_buf, (int64_t)MAX_BATCH * cfg->vocab * 2},
       {(void**)&f->sk_ws, SK_WS_BYTES}, {(void**)&f->row_map, n * 4},
   };
@@ -509,6 +518,7 @@ void td_qwen2_destroy(td_qwen2* f) {
   (void)hipFree(f->ws);
   if (f->w8_arena) (void)hipFree(f->w8_arena);
   if (f->kv8_arena) (void)hipFree(f->kv8_arena);
+  if (f->kvstage) (void)hipFree(f->kvstage);
   delete f;
 }
 
@@ -1225,6 +1235,87 @@ int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const in
   form.to_rows = f->row_map;
   form.attn = prefill_attn(f, B, L, L, 0);      // causal attention inside each packed prompt, straight from the projection rows (a prefill starts at position 0)
   form.attn.seg_starts = seg_starts;
+  TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
+  if (logits_last) {
+    hipLaunchKernelGGL(td_gather_last_rows_kernel, dim3((D / 8 + 255) / 256, B), dim3(256), 0, s, f->xn, f->lastrows, seg_starts, D);
+    TD_TRY(lm_head(f, f->lastrows, B, logits_last, s));
+  }
+  TD_CHECK_LAUNCH();
+  return TD_OK;
+}
+
+// Packed prefill behind cached prefixes (automatic prefix caching): sequence b feeds lens[b] >= 1 NEW rows, which go to cache rows [prefix_lens[b],
+// prefix_lens[b] + lens[b]) of slot slots[b]; the caller vouches that the first prefix_lens[b] rows of that slot are valid.  The packed operands and outputs
+// cover the new rows only, laid out as in td_qwen2_prefill_packed_slots, which every prefix_lens[b] == 0 delegates to.  bf16 cache: the new k | v rows are
+// scattered to their cache rows in front of the attention, which reads K / V straight from the layer's cache, every query segment over its own slot's rows
+// [0, prefix + len) (TdAttnParams::kv_seg_row0 / kv_seg_lens).  e4m3 cache: staged -- the new rows are quantised into the cache, rows [0, prefix + len) of every
+// sequence are dequantised into f->kvstage, packed per segment, by ONE row-mapped launch per layer, and the attention runs over that buffer.
+int td_qwen2_prefill_packed_prefix_slots(td_qwen2* f, int B, const int* slots, const int* token_ids, const void* inputs_embeds, const int* position_ids,
+                                         const int* lens, const int* prefix_lens, void* hidden_out, void* logits_last, void* stream) {
+  TD_CHECK_ARG(f && slots && position_ids && lens && prefix_lens && (token_ids || inputs_embeds), "td_qwen2_prefill_packed_prefix: null argument");
+  TD_QWEN2_FRESH(f, "td_qwen2_prefill_packed_prefix");
+  TD_CHECK_ARG(B >= 1 && B <= MAX_BATCH, "td_qwen2_prefill_packed_prefix: %d sequences (1 .. %d)", B, MAX_BATCH);
+  for (int b = 0; b < B; ++b) TD_CHECK_ARG(slots[b] >= 0 && slots[b] < f->n_slots, "td_qwen2_prefill_packed_prefix: sequence %d names cache slot %d of %d", b, slots[b], f->n_slots);
+  TD_TRY(check_distinct_slots("td_qwen2_prefill_packed_prefix", "sequence", slots, B));
+  long long total = 0, staged = 0;
+  int L = 0, Lkv = 0;
+  bool any_prefix = false;
+  for (int b = 0; b < B; ++b) {
+    TD_CHECK_ARG(lens[b] >= 1, "td_qwen2_prefill_packed_prefix: sequence %d feeds lens=%d rows (at least 1)", b, lens[b]);
+    TD_CHECK_ARG(prefix_lens[b] >= 0, "td_qwen2_prefill_packed_prefix: sequence %d has prefix_lens=%d (at least 0)", b, prefix_lens[b]);
+    TD_CHECK_ARG((long long)prefix_lens[b] + lens[b] <= f->slot_len, "td_qwen2_prefill_packed_prefix: sequence %d: prefix %d + %d new rows exceed the slot capacity %d", b,
+                 prefix_lens[b], lens[b], f->slot_len);
+    total += lens[b];
+    staged += prefix_lens[b] + lens[b];
+    L = lens[b] > L ? lens[b] : L;
+    Lkv = prefix_lens[b] + lens[b] > Lkv ? prefix_lens[b] + lens[b] : Lkv;
+    any_prefix = any_prefix || prefix_lens[b] > 0;
+  }
+  TD_CHECK_ARG(total <= f->ws_rows, "td_qwen2_prefill_packed_prefix: %lld packed rows exceed the %d workspace rows", total, f->ws_rows);
+  if (!any_prefix) return td_qwen2_prefill_packed_slots(f, B, slots, token_ids, inputs_embeds, position_ids, lens, hidden_out, logits_last, stream);
+  const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
+  if (kv8) TD_CHECK_ARG(staged <= f->ws_rows, "td_qwen2_prefill_packed_prefix: the e4m3 cache stages prefix + new rows: %lld staged rows exceed the %d workspace rows", staged, f->ws_rows);
+  hipStream_t s = (hipStream_t)stream;
+  const int D = f->D, n = (int)total, KVW = 2 * f->Hkv * 128;
+  if (kv8 && !f->kvstage) {      // the staging buffer and its row map, at the first pass that needs them
+    const size_t rows_bytes = ((size_t)f->ws_rows * KVW * 2 + 255) & ~(size_t)255;
+    TD_CHECK_HIP(hipMalloc((void**)&f->kvstage, rows_bytes + (size_t)f->ws_rows * 4));
+    f->stage_map = (int*)((char*)f->kvstage + rows_bytes);
+  }
+  // device ints: seg_starts [B + 1] where the packed prefill keeps them, the first key row and the key count of every segment behind the verify step's arrays;
+  // the cache row of every packed new row, and (e4m3) of every staged row
+  IntPack ip, kp;
+  int* seg_starts = f->ibuf + 3 * MAX_BATCH;
+  int* kv_row0 = f->ibuf + 5 * MAX_BATCH;
+  int* kv_lens = f->ibuf + 6 * MAX_BATCH;
+  f->row_map_host.resize((size_t)n + (kv8 ? (size_t)staged : 0));
+  int r = 0, sr = 0;
+  for (int b = 0; b < B; ++b) {
+    const int row0 = slots[b] * f->slot_len, klen = prefix_lens[b] + lens[b];
+    ip.v[b] = r;
+    kp.v[b] = kv8 ? sr : row0;
+    kp.v[MAX_BATCH + b] = klen;
+    for (int t = 0; t < lens[b]; ++t) f->row_map_host[(size_t)r + t] = row0 + prefix_lens[b] + t;
+    if (kv8)
+      for (int t = 0; t < klen; ++t) f->row_map_host[(size_t)n + sr + t] = row0 + t;
+    r += lens[b];
+    sr += klen;
+  }
+  ip.v[B] = r;
+  hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, seg_starts, ip, B + 1);
+  hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, kv_row0, kp, 2 * MAX_BATCH);
+  TD_CHECK_LAUNCH();
+  TD_CHECK_HIP(hipMemcpyAsync(f->row_map, f->row_map_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s));
+  if (kv8) TD_CHECK_HIP(hipMemcpyAsync(f->stage_map, f->row_map_host.data() + n, (size_t)staged * 4, hipMemcpyHostToDevice, s));
+  PrefillForm form;
+  form.n = n;
+  form.to_rows = f->row_map;
+  form.attn = prefill_attn(f, B, L, Lkv, 0);      // (the segments' causal offsets are prefix_lens: the kernel takes them from kv_seg_lens)
+  form.attn.seg_starts = seg_starts;
+  form.attn.kv_seg_row0 = kv_row0;
+  form.attn.kv_seg_lens = kv_lens;
+  if (kv8) { form.q8_stage_rows = f->stage_map; form.q8_stage_n = (int)staged; }
+  else form.attn_kv = KvRows{0};                  // K / V = the layer's cache, seen as rows
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     hipLaunchKernelGGL(td_gather_last_rows_kernel, dim3((D / 8 + 255) / 256, B), dim3(256), 0, s, f->xn, f->lastrows, seg_starts, D);

@@ -189,6 +189,11 @@ struct TdAttnParams {
   const bf16_t* rope_wqA = nullptr; const bf16_t* rope_wkA = nullptr; const bf16_t* rope_wqB = nullptr; const bf16_t* rope_wkB = nullptr;
   int rope_split = 0; float rope_eps = 1e-6f;
   float rope_q_premul = 1.0f;   // as TdQkRopeParams::q_premul (then q_prescaled = 1)
+  // causal kernel, with seg_starts, both or neither (device int[batch] each): the packed query segments run over K / V ranges of their own -- prompts
+  // continued behind cached prefixes.  Segment b's keys are rows [kv_seg_row0[b], kv_seg_row0[b] + kv_seg_lens[b]) of K / V (rows of ldkv), query row i of its
+  // Sq_b rows sees keys 0 .. kv_seg_lens[b] - Sq_b + i.  Sq = the longest query segment (the grid), Skv = the longest key range (the descriptor check); the
+  // kernel counts kv_seg_lens[b] < Sq_b as Sq_b.  (At the end: the fields in front keep their places in the kernels' argument block.)
+  const int* kv_seg_row0 = nullptr; const int* kv_seg_lens = nullptr;
 };
 size_t td_attn_streamk_ws_bytes();
 int td_attn_device_cus(int dev);
@@ -215,6 +220,10 @@ int td_kv_quant_rows_launch(const bf16_t* kv, long long ld, uint8_t* q, long lon
                             const int* dst_rows, hipStream_t stream);
 // ... and back: out[r, h 128 + d] = q[r, h 128 + d] scale[r, h] as bf16 (exact)
 int td_kv_dequant_rows_launch(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld, int rows, int heads, hipStream_t stream);
+// ... row-mapped: out[r, :] = the dequantised row src_rows[r] (device ints) of q / scale -- the rows of several cache slots packed into one staging buffer in
+// one launch (the packed prefill behind cached prefixes on an e4m3 cache)
+int td_kv_dequant_rows_from_launch(const uint8_t* q, long long ldq, const float* scale, long long lds, bf16_t* out, long long ld, int rows, int heads,
+                                   const int* src_rows, hipStream_t stream);
 // csrc/flux_model.hip: td_fill_normal_bf16 whose element i draws what element 2 pair0 + i of a fill from pair 0 draws (a piece of a larger buffer).
 // It exists for ONE caller: td_qwen2_init_random on a handle with the e4m3 cache, whose arena lacks the cache rows (td_qwen2::segs), so that the same seed
 // gives the weights of a bf16-cache handle -- what tools/bench_qwen2_kv8.py's two-handle comparison needs.  Every other fill passes pair0 = 0.

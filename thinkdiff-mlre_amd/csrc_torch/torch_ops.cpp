@@ -1092,6 +1092,28 @@ at::Tensor attention_verify(const at::Tensor& q, const at::Tensor& k, const at::
   return o;
 }
 
+// context attention (td_attention_prefix_segments_bf16): packed causal query segments q [R, >= Hq x 128] over key ranges of their own in k / v [rows, >= Hkv x 128]
+// (views of one stride: a KV cache seen as rows); seg_starts int32 [n + 1], kv_row0 / kv_lens int32 [n] on q's device -> o [R, Hq x 128]
+at::Tensor attention_prefix_segments(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& seg_starts, const at::Tensor& kv_row0,
+                                     const at::Tensor& kv_lens, int64_t max_q_len, int64_t max_kv_len, int64_t Hq, int64_t Hkv, double scale) {
+  TORCH_CHECK(q.is_cuda(), "thinkdiff_hip: q must live on the GPU");
+  TORCH_CHECK(q.dim() == 2 && q.scalar_type() == at::kBFloat16 && q.stride(1) == 1, "thinkdiff_hip::attention_prefix_segments: q must be bf16 [R, Hq x 128] with unit column stride");
+  TORCH_CHECK(k.dim() == 2 && v.dim() == 2 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16 && k.stride(1) == 1 && k.strides() == v.strides() &&
+                  k.sizes() == v.sizes() && k.device() == q.device() && v.device() == q.device(),
+              "thinkdiff_hip::attention_prefix_segments: k and v must be bf16 [rows, Hkv x 128] views of one shape and stride on q's device");
+  const int64_t n = kv_row0.numel();
+  for (const at::Tensor* t : {&seg_starts, &kv_row0, &kv_lens})
+    TORCH_CHECK(t->device() == q.device() && t->scalar_type() == at::kInt && t->is_contiguous(),
+                "thinkdiff_hip::attention_prefix_segments: seg_starts, kv_row0 and kv_lens must be contiguous int32 tensors on q's device");
+  TORCH_CHECK(n >= 1 && kv_lens.numel() == n && seg_starts.numel() == n + 1, "thinkdiff_hip::attention_prefix_segments: seg_starts [n + 1], kv_row0 [n] and kv_lens [n] must pair up in length");
+  DeviceGuard guard(q.device());
+  at::Tensor o = at::empty({q.size(0), Hq * 128}, q.options());
+  ok(td_attention_prefix_segments_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), q.stride(0), k.stride(0), o.stride(0), (const int*)seg_starts.data_ptr(),
+                                       (const int*)kv_row0.data_ptr(), (const int*)kv_lens.data_ptr(), (int)n, (int)max_q_len, (int)max_kv_len, (int)Hq, (int)Hkv, (float)scale,
+                                       stream_of(q)));
+  return o;
+}
+
 // the accept rule of speculative decoding (td_spec_accept): sampled / fed int32 [R], seq_row0 / seq_rows int32 [B] -> (n_emit int32 [B], emit int32 [B, 8])
 std::tuple<at::Tensor, at::Tensor> spec_accept(const at::Tensor& sampled, const at::Tensor& fed, const at::Tensor& seq_row0, const at::Tensor& seq_rows) {
   TORCH_CHECK(sampled.is_cuda(), "thinkdiff_hip: sampled must live on the GPU");
@@ -1171,6 +1193,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("kv_fork_rows(Tensor(a!) plane, int slot_rows, int src_slot, int[] dst_slots, int n_rows) -> ()");
   m.def("kv_gather_rows(Tensor(a!) plane, int slot_rows, int[] slots, Tensor copy_src, int[] n_rows) -> ()");
   m.def("attention_verify(Tensor q, Tensor k, Tensor v, Tensor? k_scale, Tensor? v_scale, Tensor seq_row0, Tensor seq_rows, Tensor seq_len0, Tensor seq_slot, int Hq, int Hkv, float scale) -> Tensor");
+  m.def("attention_prefix_segments(Tensor q, Tensor k, Tensor v, Tensor seg_starts, Tensor kv_row0, Tensor kv_lens, int max_q_len, int max_kv_len, int Hq, int Hkv, float scale) -> Tensor");
   m.def("spec_accept(Tensor sampled, Tensor fed, Tensor seq_row0, Tensor seq_rows) -> (Tensor, Tensor)");
   m.def("beam_select(Tensor top_ids, Tensor top_lp, Tensor cum_in, Tensor rank_in, int W, int n_in, int eos, Tensor(a!) token, Tensor(b!) cum_out, Tensor(c!) rank_out, Tensor(d!) copy_src, Tensor(e!) parent, Tensor(f!) fin_flag, Tensor(g!) fin_cum) -> ()");
 }
@@ -1234,6 +1257,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("kv_gather_rows", &kv_gather_rows);
   m.impl("beam_select", &beam_select);
   m.impl("attention_verify", &attention_verify);
+  m.impl("attention_prefix_segments", &attention_prefix_segments);
   m.impl("spec_accept", &spec_accept);
 }
 

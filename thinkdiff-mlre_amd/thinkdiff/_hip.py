@@ -151,6 +151,7 @@ def _declare(L):
         "td_attention_bias_bf16": [vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, f32, i32, vp, vp],
         "td_attention_varlen_bf16": [vp, i64, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, vp],
         "td_attention_segments_bf16": [vp, i64, vp, vp, i64, vp, i64, vp, i32, i32, i32, i32, f32, i32, vp],
+        "td_attention_prefix_segments_bf16": [vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp],
         "td_rope_half_bf16": [vp, i64, i32, i32, i32, i32, vp, vp, vp],
         "td_vision_rope_table": [vp, i32, i32, f32, vp, vp, vp],
         "td_patchify_bf16": [vp, i32, i32, i32, i32, i32, vp, i32, vp],
@@ -198,6 +199,7 @@ def _declare(L):
         "td_qwen2_prefill_batch_at": [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_prefill_packed": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_prefill_packed_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        "td_qwen2_prefill_packed_prefix_slots": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "td_qwen2_slot_capacity": [vp],
         "td_qwen2_move_slot": [vp, i32, i32, i32, vp],
         "td_qwen2_fork_slot": [vp, i32, vp, i32, i32, vp],
@@ -1094,6 +1096,25 @@ def attention_segments(q, k, v, out, Hq, Hkv, seg_starts, max_len, scale=None, c
         scale = 128 ** -0.5
     check(lib().td_attention_segments_bf16(ptr(q), q.stride(0), ptr(k), ptr(v), k.stride(0), ptr(out), out.stride(0), ptr(seg_starts),
                                            seg_starts.numel() - 1, int(max_len), Hq, Hkv, float(scale), int(causal), stream_ptr()))
+    return out
+
+
+def attention_prefix_segments(q, k, v, out, Hq, Hkv, seg_starts, kv_row0, kv_lens, max_q_len, max_kv_len, scale=None):
+    """td_attention_prefix_segments_bf16 (context attention): packed causal query segments q, out [R, >= Hq*128] over key ranges of their own in k, v
+    [rows, >= Hkv*128] (one row stride for both: a KV cache seen as rows).  Segment b = q rows [seg_starts[b], seg_starts[b+1]) against key rows
+    [kv_row0[b], kv_row0[b] + kv_lens[b]); its last rows are the segment's own tokens, the ones in front its cached prefix.  seg_starts device int32
+    [n + 1], kv_row0 / kv_lens device int32 [n]; max_q_len / max_kv_len >= the longest query segment / key range."""
+    for t in (q, k, v, out):
+        assert t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+    assert k.stride() == v.stride() and k.shape[0] == v.shape[0] and out.shape[0] == q.shape[0]
+    for t in (seg_starts, kv_row0, kv_lens):
+        assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous()
+    n = kv_row0.numel()
+    assert n >= 1 and kv_lens.numel() == n and seg_starts.numel() == n + 1
+    if scale is None:
+        scale = 128 ** -0.5
+    check(lib().td_attention_prefix_segments_bf16(ptr(q), ptr(k), ptr(v), ptr(out), q.stride(0), k.stride(0), out.stride(0), ptr(seg_starts), ptr(kv_row0),
+                                                  ptr(kv_lens), n, int(max_q_len), int(max_kv_len), Hq, Hkv, float(scale), stream_ptr()))
     return out
 
 

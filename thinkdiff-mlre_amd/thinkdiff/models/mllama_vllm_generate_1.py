@@ -37,9 +37,10 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
         # vLLM decodes `max_num_seqs` requests together (256 in configs/qwen2_vl_embed_ccsbu.yaml); the engine takes up to 256 per decode step
         quantization = Qwen2VLTextEngine.check_quantization(vc.get("quantization"))      # (before the engine allocates anything)
         kv_cache_dtype = Qwen2VLTextEngine.check_kv_cache_dtype(vc.get("kv_cache_dtype", "auto"))      # vLLM's `kv_cache_dtype`: "auto" (bf16) or "fp8" / "fp8_e4m3"
+        prefix_caching = Qwen2VLTextEngine.check_prefix_caching(vc.get("enable_prefix_caching", False))      # vLLM's `enable_prefix_caching` (off by default here)
         self.decode_batch = max(1, min(Qwen2VLTextEngine.MAX_BATCH, int(vc.get("max_num_seqs", Qwen2VLTextEngine.MAX_BATCH))))
         self.mllama = Qwen2VLTextEngine(text_config, max_model_len=vc.get("max_model_len", 8192), device=device, n_slots=self.decode_batch,
-                                        kv_cache_dtype=kv_cache_dtype,
+                                        kv_cache_dtype=kv_cache_dtype, **({"enable_prefix_caching": True} if prefix_caching else {}),
                                         prefill_rows=min(int(vc.get("max_num_batched_tokens", 16384)), 65536) if self.decode_batch > 1 else None)      # (60 000 in the reference config: rows of one packed prefill pass)
         # vLLM's `quantization="fp8"` / `"mxfp4"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
         self.mllama.weight_quantization = quantization

@@ -19,7 +19,53 @@ import torch
 
 from .. import _hip
 from ..ops import register as _register_ops
+from . import prefix_cache as _pfx
 _OPS = _register_ops()      # torch.ops.thinkdiff_hip: the custom-op layer over the C ABI (GPU kernels only, no fallback)
+
+
+def _prefix_entry(fn):
+    """A generate entry under automatic prefix caching: while it runs, the low-level writers it calls (forward, fork_slot, gather_slots, ..) do not drop the
+    cache's entries -- the entry keeps the books itself -- and whatever it leaves live is retained when it returns or raises.  With the feature off: fn."""
+    import functools
+
+    @functools.wraps(fn)
+    def run(self, *a, **kw):
+        pc = getattr(self, "_prefix_cache", None)
+        if pc is None:
+            return fn(self, *a, **kw)
+        self._pc_depth = getattr(self, "_pc_depth", 0) + 1
+        if self._pc_depth == 1:
+            pc.release_all()
+        try:
+            return fn(self, *a, **kw)
+        finally:
+            self._pc_depth -= 1
+            if self._pc_depth == 0:
+                pc.release_all()
+    return run
+
+
+class _CacheSlots:
+    """The free-slot stack of generate_batch / generate_continuous while prefix caching is on: slots come from the cache's allocator (free ones first,
+    then retained ones, least recently used first) and a finished sequence's slot goes back retained."""
+
+    def __init__(self, pc):
+        self.pc = pc
+
+    def pop(self):
+        s = self.pc.take(1)
+        if s is None:
+            raise _hip.ThinkDiffHipError("prefix cache: no cache slot left for a new sequence")
+        return s[0]
+
+    def extend(self, slots):
+        for s in slots:
+            self.pc.release(int(s))
+
+    def __getitem__(self, i):      # ([-1]: a slot to run a prompt-only forward through -- it holds nothing afterwards)
+        s = self.pop()
+        self.pc.drop(s)
+        return s
 
 
 @dataclasses.dataclass
@@ -864,8 +910,9 @@ class Qwen2VLTextEngine:
         return "auto" if cls.KV_CACHE_DTYPES[value] == _hip.QWEN2_KV_BF16 else "fp8"
 
     def __init__(self, config: Optional[Qwen2VLTextConfig] = None, max_model_len: int = 8192, device="cuda", n_slots: int = 1,
-                 prefill_rows: Optional[int] = None, kv_cache_dtype: Optional[str] = "auto", **kw):
+                 prefill_rows: Optional[int] = None, kv_cache_dtype: Optional[str] = "auto", enable_prefix_caching: bool = False, **kw):
         self.kv_cache_dtype = self.check_kv_cache_dtype(kv_cache_dtype)      # (before anything is allocated)
+        self.check_prefix_caching(enable_prefix_caching)
         self.config = config or Qwen2VLTextConfig(**kw)
         c = self.config
         self.device = torch.device(device)
@@ -889,6 +936,45 @@ class Qwen2VLTextEngine:
         self._defer_quantize = False
         self.n_slots, self.slot_len = int(n_slots), max_model_len
         self.max_model_len = max_model_len
+        self.set_prefix_caching(enable_prefix_caching)
+
+    # ---- automatic prefix caching (vLLM's enable_prefix_caching; thinkdiff/models/prefix_cache.py) ----------------------------------------------
+    @staticmethod
+    def check_prefix_caching(value) -> bool:
+        """vllm_config["enable_prefix_caching"] as the models take it: a bool; anything else is an error naming the value."""
+        if not isinstance(value, bool):
+            raise ValueError(f"vllm_config enable_prefix_caching={value!r} must be True or False")
+        return value
+
+    def set_prefix_caching(self, on: bool):
+        """Turn automatic prefix caching on or off (off by default; turning it off forgets everything).  On: generate_batch, generate_continuous, beam_search
+        and the n / best_of parents serve the longest cached run of whole 16-token blocks of a prompt from a donor cache slot and prefill the rest."""
+        on = self.check_prefix_caching(on)
+        if on and getattr(self, "_prefix_cache", None) is None:
+            self._prefix_cache = _pfx.PrefixCache(self.n_slots)
+        elif not on:
+            self._prefix_cache = None
+        return self
+
+    def reset_prefix_cache(self):
+        """vLLM's LLM.reset_prefix_cache: every slot forgets its prompt (the statistics keep counting)."""
+        pc = getattr(self, "_prefix_cache", None)
+        if pc is not None:
+            pc.resize(self.n_slots)
+        return self
+
+    def prefix_cache_stats(self) -> dict:
+        """queries / hits in tokens (vLLM's metrics), passes, copies (launches) and copied_rows, in_place take-overs, deferred requests, evictions, and
+        hidden_bytes: the prompts' hidden rows the entries hold on the device.  All zero while the feature is off."""
+        pc = getattr(self, "_prefix_cache", None)
+        return _pfx.zero_stats() if pc is None else pc.get_stats()
+
+    def _pc_wrote(self, slots):
+        """A low-level writer called from outside the generate entries wrote these slots: their cached prompts are gone."""
+        pc = getattr(self, "_prefix_cache", None)
+        if pc is not None and not getattr(self, "_pc_depth", 0):
+            for s in slots:
+                pc.drop(int(s))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -1053,6 +1139,7 @@ class Qwen2VLTextEngine:
         return {k: t for k, t in sd.items() if k not in drop}, jobs
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
+        self.reset_prefix_cache()      # (the cached keys and hidden rows belong to the old weights)
         table = self.param_table()
         sd, int4_jobs = self._split_int4(sd, table)
         sd = self._dequantize_packed(sd, table)
@@ -1129,6 +1216,7 @@ class Qwen2VLTextEngine:
         return self
 
     def init_random(self, seed: int = 0, std: float = 0.02):
+        self.reset_prefix_cache()
         _hip.check(self._L.td_qwen2_init_random(self._h, seed, std, _hip.stream_ptr()))
         self._requantize()
         return self
@@ -1154,12 +1242,14 @@ class Qwen2VLTextEngine:
         bf16 bytes, its dequantised values exact in bf16 too.  An engine quantised in one format refuses the other until its weights are loaded again."""
         if quantization not in Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS:
             raise ValueError(f"Qwen2VLTextEngine.quantize_weights: quantization={quantization!r} is not served (only 'fp8' and 'mxfp4')")
+        self.reset_prefix_cache()
         _hip.check(self._L.td_qwen2_quantize_weights(self._h, Qwen2VLTextEngine.WEIGHT_QUANTIZATIONS[quantization], _hip.stream_ptr()))
         return self
 
     def set_weight_stream(self, on: bool) -> bool:
         """A/B switch of a quantised engine: launches of up to 64 rows read the 8-bit copy (default) or the dequantised bf16 weights -- the same
         model either way.  Returns the previous setting."""
+        self.reset_prefix_cache()
         rc = self._L.td_qwen2_set_weight_stream(self._h, 1 if on else 0)
         if rc not in (0, 1):
             _hip.check(rc)
@@ -1204,6 +1294,7 @@ class Qwen2VLTextEngine:
         """Split the KV cache into `n_slots` sequences (each max_model_len // n_slots tokens) for batched decode."""
         _hip.check(self._L.td_qwen2_set_slots(self._h, int(n_slots)))
         self.n_slots, self.slot_len = int(n_slots), int(self._L.td_qwen2_slot_capacity(self._h))
+        self.reset_prefix_cache()      # (the slots' rows moved)
         return self
 
     def set_fused_rope(self, on: bool) -> bool:
@@ -1220,6 +1311,7 @@ class Qwen2VLTextEngine:
         emb = None if inputs_embeds is None else inputs_embeds.to(self.device, torch.bfloat16).contiguous()
         hid = torch.empty(n, self.config.hidden_size, dtype=torch.bfloat16, device=self.device) if want_hidden else None
         lg = torch.empty(self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if want_logits else None
+        self._pc_wrote([slot])
         _hip.check(self._L.td_qwen2_forward_slot(self._h, slot, _hip.ptr(tok), _hip.ptr(emb), _hip.ptr(pos), n, pos0,
                                                  _hip.ptr(hid), _hip.ptr(lg), _hip.stream_ptr()))
         return hid, lg
@@ -1235,6 +1327,7 @@ class Qwen2VLTextEngine:
         lg = torch.empty(B, self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if want_logits else None
         cp = (ctypes.c_int * B)(*[int(c) for c in cache_pos])
         sl = ctypes.cast((ctypes.c_int * B)(*[int(c) for c in slots]), ctypes.c_void_p) if slots is not None else None
+        self._pc_wrote(slots if slots is not None else range(B))
         _hip.check(self._L.td_qwen2_decode_batch_slots(self._h, B, sl, _hip.ptr(tok), _hip.ptr(pos), ctypes.cast(cp, ctypes.c_void_p),
                                                        _hip.ptr(hid), _hip.ptr(lg), _hip.stream_ptr()))
         return hid, lg
@@ -1254,6 +1347,7 @@ class Qwen2VLTextEngine:
         cp = (ctypes.c_int * B)(*[int(c) for c in cache_pos])
         nn = (ctypes.c_int * B)(*[int(c) for c in n_new])
         sl = ctypes.cast((ctypes.c_int * B)(*[int(c) for c in slots]), ctypes.c_void_p) if slots is not None else None
+        self._pc_wrote(slots if slots is not None else range(B))
         _hip.check(self._L.td_qwen2_verify_batch_slots(self._h, B, sl, ctypes.cast(nn, ctypes.c_void_p), _hip.ptr(tok), _hip.ptr(pos),
                                                        ctypes.cast(cp, ctypes.c_void_p), _hip.ptr(hid), _hip.ptr(lg), _hip.stream_ptr()))
         return hid, lg
@@ -1385,6 +1479,7 @@ class Qwen2VLTextEngine:
         """Sequences one call can keep live: one cache slot each, and one decode step takes at most MAX_BATCH."""
         return min(self.MAX_BATCH, self.n_slots)
 
+    @_prefix_entry
     @torch.no_grad()
     def generate_batch(self, requests: Sequence[dict], sampling: SamplingParams, eos_token_id: Optional[int] = None,
                        generator: Optional[torch.Generator] = None, forced_output_ids: Optional[Sequence[Sequence[int]]] = None, speculative=None):
@@ -1416,17 +1511,27 @@ class Qwen2VLTextEngine:
         src = _TokenSource(self, sampling, by_rows, seq_sps.__getitem__, eos_token_id, generator, forced,
                            [sp.logprobs for sp in seq_sps] if _LogprobLog.wanted(seq_sps) else None, draft)
         live = _LiveRows(self, N, src, eos_token_id)
-        # request b is prefilled once, into slot b; the children take the slots from B up
-        for b, h in enumerate(self._prefill_prompts(requests, list(range(B)), poss, live.logits[:B], padded_ok=True)):
+        pc = getattr(self, "_prefix_cache", None)
+        if pc is None:
+            # request b is prefilled once, into slot b; the children take the slots from B up
+            parents, free_slots = list(range(B)), list(range(N - 1, B - 1, -1))
+            hidden = self._prefill_prompts(requests, parents, poss, live.logits[:B], padded_ok=True)
+        else:      # prefix caching: the cache places the prompts and hands out the children's slots; a finished sequence's slot is retained
+            free_slots = _CacheSlots(pc)
+            hidden, parents = self._prefill_prompts_cached(pc, requests, poss, live.logits[:B])
+        for b, h in enumerate(hidden):
             res[seq0[b]]["prompt_hidden_states"] = h
-        live.admit(seq0, widths, list(range(B)), [len(r["prompt_token_ids"]) for r in requests], [int(p.max()) + 1 for p in poss],
+        live.admit(seq0, widths, parents, [len(r["prompt_token_ids"]) for r in requests], [int(p.max()) + 1 for p in poss],
                    [sp.max_tokens if forced is None else min(sp.max_tokens, len(forced[b])) for b, sp in enumerate(sps)],
-                   [r["prompt_token_ids"] for r in requests], list(range(N - 1, B - 1, -1)))
+                   [r["prompt_token_ids"] for r in requests], free_slots)
         while live.n:
-            live.step()
+            freed = live.step()
+            if pc is not None:
+                free_slots.extend(freed)
         live.results(res)
         return _gather_outputs(res, sps) if fan else res
 
+    @_prefix_entry
     @torch.no_grad()
     def generate_continuous(self, request_chunks, sampling: SamplingParams, eos_token_id: Optional[int] = None,
                             generator: Optional[torch.Generator] = None, forced_output_ids: Optional[Sequence[Sequence[int]]] = None,
@@ -1498,7 +1603,10 @@ class Qwen2VLTextEngine:
                     res.append({"prompt_hidden_states": None, "hidden_states": None, "token_ids": []})
 
         live = _LiveRows(self, max_live, _TokenSource(self, sampling, by_rows, sp_of, eos_token_id, generator, forced, want, draft), eos_token_id)
-        free_slots = list(range(max_live - 1, -1, -1))      # (a stack: the lowest free slot is taken first)
+        pc = getattr(self, "_prefix_cache", None)
+        # (a stack: the lowest free slot is taken first; under prefix caching the cache's allocator, over all n_slots, with max_live bounding the live ones)
+        free_slots = list(range(max_live - 1, -1, -1)) if pc is None else _CacheSlots(pc)
+        hashes_of = {}      # prefix caching: request -> its block hashes, computed once
 
         def budget(i):      # tokens (each sequence of) request i may still produce
             return len(forced[i]) if forced is not None else sp_of(base_of(i)).max_tokens
@@ -1522,7 +1630,9 @@ class Qwen2VLTextEngine:
             fit, fit_slots = fits(free)
             if fit > 0 and (live.n == 0 or fit_slots >= admit_min or (exhausted and fit >= len(waiting))):
                 new, rows, used = [], 0, 0
-                while waiting and used + k_of(waiting[0]) <= free and rows + len(requests[waiting[0]]["prompt_token_ids"]) <= self.prefill_rows:
+                # (under prefix caching the pass's rows are counted where it is planned: only the rows behind the cached prefixes are fed)
+                while waiting and used + k_of(waiting[0]) <= free and (rows + len(requests[waiting[0]]["prompt_token_ids"]) <= self.prefill_rows
+                                                                        or (pc is not None and len(new) < self.MAX_BATCH)):
                     i = waiting.popleft()
                     if budget(i) <= 0:      # nothing to generate: the prompt states only, through the first free slot
                         q = requests[i]
@@ -1534,6 +1644,23 @@ class Qwen2VLTextEngine:
                     new.append(i)
                     rows += len(requests[i]["prompt_token_ids"])
                     used += k_of(i)
+                if new and pc is not None:      # one pass over as many of them as the cache's plan takes; the rest wait, in order, at the head of the queue
+                    qs = [requests[i] for i in new]
+                    poss = [self._positions(q) for q in qs]
+                    for i, q, p in zip(new, qs, poss):
+                        if i not in hashes_of:
+                            hashes_of[i] = self._prefix_hashes(q, p)
+                    hids, new_slots = self._prefill_pass_cached(pc, qs, poss, [hashes_of[i] for i in new], live.logits[live.n:live.n + len(new)])
+                    k = len(new_slots)
+                    for i in reversed(new[k:]):
+                        waiting.appendleft(i)
+                    new, qs, poss = new[:k], qs[:k], poss[:k]
+                    for i, h in zip(new, hids):
+                        res[base_of(i)]["prompt_hidden_states"] = h
+                        hashes_of.pop(i, None)
+                    live.admit([base_of(i) for i in new], [k_of(i) for i in new], new_slots, [len(q["prompt_token_ids"]) for q in qs],
+                               [int(p.max()) + 1 for p in poss], [budget(i) for i in new], [q["prompt_token_ids"] for q in qs], free_slots)
+                    continue
                 if new:
                     k, qs = len(new), [requests[i] for i in new]
                     poss = [self._positions(q) for q in qs]
@@ -1559,6 +1686,99 @@ class Qwen2VLTextEngine:
         _hip.check(self._L.td_qwen2_prefill_packed_slots(self._h, k, ctypes.cast(slots_c, ctypes.c_void_p), None, _hip.ptr(emb), _hip.ptr(pos),
                                                          ctypes.cast(lens_c, ctypes.c_void_p), _hip.ptr(hid_out), _hip.ptr(logits_out), _hip.stream_ptr()))
 
+    def _prefill_packed_prefix_slots(self, k, slots_c, emb, pos, lens_c, prefix_c, hid_out, logits_out):
+        """The packed prefill behind cached prefixes (td_qwen2_prefill_packed_prefix_slots): emb, pos, hid_out cover the lens_c[b] NEW rows of every
+        sequence, which go behind the prefix_c[b] rows its slot already holds."""
+        _hip.check(self._L.td_qwen2_prefill_packed_prefix_slots(self._h, k, ctypes.cast(slots_c, ctypes.c_void_p), None, _hip.ptr(emb), _hip.ptr(pos),
+                                                                ctypes.cast(lens_c, ctypes.c_void_p), ctypes.cast(prefix_c, ctypes.c_void_p), _hip.ptr(hid_out),
+                                                                _hip.ptr(logits_out), _hip.stream_ptr()))
+
+    def _prefix_copy(self, src, dst_slots, length):
+        """The copy of a cache hit: rows [0, length) of the donor slot to every destination, one launch over all layers (td_qwen2_fork_slot)."""
+        dst = (ctypes.c_int * len(dst_slots))(*[int(d) for d in dst_slots])
+        _hip.check(self._L.td_qwen2_fork_slot(self._h, int(src), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(length), _hip.stream_ptr()))
+
+    def prefill_packed(self, requests_rows, slots: Sequence[int], prefix_lens: Sequence[int], want_logits=True):
+        """The packed prefill behind cached prefixes as a call of its own (tests, callers that keep their own books): requests_rows[b] = dict with
+        "position_ids" [3, n_b] and "token_ids" [n_b] or "inputs_embeds" [n_b, hidden] for the n_b NEW rows of sequence b, which go to cache rows
+        [prefix_lens[b], prefix_lens[b] + n_b) of slot slots[b]; the caller vouches for the rows in front.  -> ([hidden [n_b, hidden]], logits of each
+        sequence's last row [B, vocab] | None).  Drops the prefix cache's entries of the slots it writes."""
+        B, D = len(requests_rows), self.config.hidden_size
+        if len(slots) != B or len(prefix_lens) != B or B < 1:
+            raise _hip.ThinkDiffHipError(f"prefill_packed: {len(slots)} slots and {len(prefix_lens)} prefix_lens for {B} sequences")
+        lens = [int(r["position_ids"].shape[1]) for r in requests_rows]
+        emb = torch.empty(sum(lens), D, dtype=torch.bfloat16, device=self.device)
+        pos = torch.empty(3, sum(lens), dtype=torch.int32)
+        r0 = 0
+        for r, n in zip(requests_rows, lens):
+            e = r.get("inputs_embeds")
+            emb[r0:r0 + n] = self.embed_tokens(r["token_ids"]) if e is None else e.to(self.device, torch.bfloat16)
+            pos[:, r0:r0 + n] = r["position_ids"].to(torch.int32)
+            r0 += n
+        hid = torch.empty(sum(lens), D, dtype=torch.bfloat16, device=self.device)
+        lg = torch.empty(B, self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if want_logits else None
+        self._pc_wrote(slots)
+        self._prefill_packed_prefix_slots(B, (ctypes.c_int * B)(*[int(s) for s in slots]), emb, pos.to(self.device).contiguous(), (ctypes.c_int * B)(*lens),
+                                          (ctypes.c_int * B)(*[int(p) for p in prefix_lens]), hid, lg)
+        return list(torch.split(hid, lens)), lg
+
+    # ---- prompt prefill under prefix caching ---------------------------------------------------------------------------------------------------
+    def _prefix_hashes(self, request, pos):
+        return _pfx.block_hashes(request["prompt_token_ids"], pos, request.get("inputs_embeds"), request.get("mm_hash"))
+
+    def _prefill_pass_cached(self, pc, requests, poss, hashes, logits_out):
+        """ONE prefill pass over the head of `requests` as the cache plans it (PrefixCache.plan_pass) -> (the prompts' complete hidden states, their cache
+        slots) for the first t requests, t >= 1; logits_out[j] receives the last-token logits of request j < t.  All copies of the pass are enqueued in
+        front of its prefill; a prompt's hidden states are cat(the donor's first m rows, the new rows)."""
+        D = self.config.hidden_size
+        lens = [len(q["prompt_token_ids"]) for q in requests]
+        stage = self.prefill_rows if getattr(self, "kv_cache_dtype", "auto") == "fp8" else None      # (the e4m3 cache stages prefix + new rows)
+        plan = pc.plan_pass(list(zip(hashes, lens)), self.MAX_BATCH, self.prefill_rows, stage)
+        t = len(plan)
+        if t == 0:
+            raise _hip.ThinkDiffHipError("prefix cache: no cache slot left for a waiting request")
+        donor_hidden = [None if p.m == 0 else pc.hidden_of(p.donor)[:p.m] for p in plan]      # (before the entries of this pass replace anything)
+        for donor, m, dsts in pc.copies(plan):
+            self._prefix_copy(donor, dsts, m)
+        new = [n - p.m for n, p in zip(lens, plan)]
+        emb = torch.empty(sum(new), D, dtype=torch.bfloat16, device=self.device)
+        pos = torch.empty(3, sum(new), dtype=torch.int32)
+        r = 0
+        for q, pp, p, k in zip(requests, poss, plan, new):
+            e = q.get("inputs_embeds")
+            emb[r:r + k] = self.embed_tokens(q["prompt_token_ids"][p.m:]) if e is None else e[p.m:].to(self.device, torch.bfloat16)
+            pos[:, r:r + k] = pp[:, p.m:].to(torch.int32)
+            r += k
+        hid = torch.empty(sum(new), D, dtype=torch.bfloat16, device=self.device)
+        slots = [p.slot for p in plan]
+        self._prefill_packed_prefix_slots(t, (ctypes.c_int * t)(*slots), emb, pos.to(self.device).contiguous(), (ctypes.c_int * t)(*new),
+                                          (ctypes.c_int * t)(*[p.m for p in plan]), hid, logits_out[:t])
+        hidden = []
+        for h_new, h_old, p, hs in zip(torch.split(hid, new), donor_hidden, plan, hashes):
+            h = h_new if h_old is None else torch.cat([h_old, h_new])
+            pc.insert(p.slot, hs, h)
+            hidden.append(h)
+        return hidden, slots
+
+    def _prefill_prompts_cached(self, pc, requests, poss, logits_out):
+        """_prefill_prompts under prefix caching -> (the prompts' hidden states, the cache slots the cache chose for them).  Prompts that fit no packed
+        pass (or packed_prefill off) go the uncached way into slots from the cache's allocator and leave no entry."""
+        B = len(requests)
+        lens = [len(q["prompt_token_ids"]) for q in requests]
+        if not self.packed_prefill or max(lens) > min(self.slot_len, self.prefill_rows):
+            slots = pc.take(B)
+            if slots is None:
+                raise _hip.ThinkDiffHipError(f"prefix cache: no {B} cache slots left")
+            return self._prefill_prompts(requests, slots, poss, logits_out), slots
+        hashes = [self._prefix_hashes(q, p) for q, p in zip(requests, poss)]
+        hidden, slots, b0 = [], [], 0
+        while b0 < B:
+            h, s = self._prefill_pass_cached(pc, requests[b0:], poss[b0:], hashes[b0:], logits_out[b0:])
+            hidden += h
+            slots += s
+            b0 += len(s)
+        return hidden, slots
+
     def _decode_slots(self, n, slots_np, tok_dev, pos_dev, cache_np, hid_out, logits_out):
         _hip.check(self._L.td_qwen2_decode_batch_slots(self._h, n, ctypes.c_void_p(slots_np.ctypes.data), _hip.ptr(tok_dev), _hip.ptr(pos_dev),
                                                        ctypes.c_void_p(cache_np.ctypes.data), _hip.ptr(hid_out), _hip.ptr(logits_out), _hip.stream_ptr()))
@@ -1583,6 +1803,7 @@ class Qwen2VLTextEngine:
         """Copy the first `length` cache rows of slot `src` to every slot of `dst_slots` in ONE launch over all layers (td_qwen2_fork_slot: each source
         chunk is read once and written len(dst_slots) times): the sequences in those slots then continue from the same prefill."""
         dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
+        self._pc_wrote(dst_slots)
         _hip.check(self._L.td_qwen2_fork_slot(self._h, int(src), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(length), _hip.stream_ptr()))
 
     def gather_slots(self, slots: Sequence[int], copy_src, lengths: Sequence[int]):
@@ -1595,6 +1816,7 @@ class Qwen2VLTextEngine:
         src = copy_src.to(device=self.device, dtype=torch.int32).contiguous()
         if src.numel() != n or len(lengths) != n:
             raise _hip.ThinkDiffHipError(f"gather_slots: {src.numel()} copy_src entries and {len(lengths)} lengths for {n} slots")
+        self._pc_wrote(slots)
         _hip.check(self._L.td_qwen2_gather_slots(self._h, n, ctypes.cast(sl, ctypes.c_void_p), _hip.ptr(src), ctypes.cast(ln, ctypes.c_void_p), _hip.stream_ptr()))
 
     # ---- prompt prefill of generate_batch, generate_continuous and beam_search ---------------------------------------------------------------
@@ -1666,6 +1888,7 @@ class Qwen2VLTextEngine:
         return hidden
 
     # ---- beam search ([ext] vllm.LLM.beam_search) ------------------------------------------------------------------------------------------
+    @_prefix_entry
     @torch.no_grad()
     def beam_search(self, requests: Sequence[dict], params: BeamSearchParams, eos_token_id: Optional[int] = None):
         """vLLM's `LLM.beam_search` for R requests (the dicts of generate_batch) with W = params.beam_width beams each, on R x W cache slots: request r
@@ -1707,7 +1930,17 @@ class Qwen2VLTextEngine:
         poss = [self._positions(r) for r in requests]
         next_pos = [int(p.max()) + 1 for p in poss]
         logits0 = torch.empty(R, V, dtype=torch.bfloat16, device=dev)
-        prompt_hidden = self._prefill_prompts(requests, [r * W for r in range(R)], poss, logits0)      # each prompt once, into its request's first slot
+        pc = getattr(self, "_prefix_cache", None)
+        slots_np = np.arange(N, dtype=np.int32)
+        if pc is None:
+            prompt_hidden = self._prefill_prompts(requests, [r * W for r in range(R)], poss, logits0)      # each prompt once, into its request's first slot
+        else:      # prefix caching: the cache places the prompts; the other beams of a request take slots from its allocator
+            prompt_hidden, parents = self._prefill_prompts_cached(pc, requests, poss, logits0)
+            kids = pc.take(N - R) if N > R else []
+            if kids is None:
+                raise _hip.ThinkDiffHipError(f"beam_search: the prefix cache has no {N - R} cache slots left for the beams")
+            for r in range(R):
+                slots_np[r * W:(r + 1) * W] = [parents[r]] + kids[r * (W - 1):(r + 1) * (W - 1)]
         # what the loop needs from the host, uploaded before it starts: the rows' M-RoPE positions of every round and the first round's live rows
         first = torch.arange(R, dtype=torch.int64) * W
         logits = torch.zeros(N, V, dtype=torch.bfloat16, device=dev)
@@ -1722,7 +1955,6 @@ class Qwen2VLTextEngine:
         flog = torch.empty(2, T, N, dtype=torch.float32, device=dev)    # cum, fin_cum
         cum0, rank0 = torch.zeros(N, dtype=torch.float32, device=dev), torch.zeros(N, dtype=torch.int32, device=dev)
         hid_all = torch.empty(T, N, D, dtype=torch.bfloat16, device=dev)
-        slots_np = np.arange(N, dtype=np.int32)
         base_len = np.repeat(np.asarray(plen, dtype=np.int32), W)
         for s in range(T):
             _, _, top_ids, top_lp = _OPS.logprobs_rows(logits, no_ids, n_top0 if s == 0 else n_top, 2 * W)
@@ -1772,6 +2004,7 @@ class Qwen2VLTextEngine:
     def move_slot(self, src: int, dst: int, length: int):
         """Copy the first `length` cache rows of slot `src` to slot `dst` (td_qwen2_move_slot).  The decode steps name their slots, so nothing in this
         class needs it any more; it stays for callers that want to defragment a handle before re-partitioning it (set_slots)."""
+        self._pc_wrote([dst])
         _hip.check(self._L.td_qwen2_move_slot(self._h, int(src), int(dst), int(length), _hip.stream_ptr()))
 
 
@@ -1916,6 +2149,8 @@ class QwenChatFrontend:
             ids = all_ids[a0:a1]
             r["prompt_token_ids"], r["inputs_embeds"] = ids, emb_all[a0:a1]
             r["position_ids"] = Qwen2VLTextEngine.mrope_position_ids(ids, g, merge, self.image_token_id)
+        for i, ims in zip(need, per_req):
+            self._fill_mm_hash(out[i], ims)
         return out
 
     def _device_preprocess_plan(self):
@@ -2009,4 +2244,11 @@ class QwenChatFrontend:
         mm = r.get("multi_modal_data") or {}
         if mm.get("image") is not None and "inputs_embeds" not in r:
             r["prompt_token_ids"], r["inputs_embeds"], r["position_ids"] = self.splice_images(list(r["prompt_token_ids"]), mm["image"])
+            self._fill_mm_hash(r, mm["image"])
         return r
+
+    def _fill_mm_hash(self, r: dict, images):
+        """While prefix caching is on, an image request carries "mm_hash" (vLLM's multimodal hash), here a digest of the image bytes on the host: the identity
+        of its embedding rows in the cache's keys, so that a lookup costs no device read-back.  A hash the request brought is kept."""
+        if getattr(getattr(self, "mllama", None), "_prefix_cache", None) is not None and r.get("mm_hash") is None:
+            r["mm_hash"] = _pfx.image_digest(images)

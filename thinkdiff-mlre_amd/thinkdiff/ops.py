@@ -70,6 +70,8 @@ beam_select                one beam-search step on the device (vLLM's `LLM.beam_
 attention_verify / spec_accept   speculative decoding (vLLM's `speculative_config`, method "ngram"): the decode attention of a verify step -- up to 8 query rows per
                            sequence, bf16 or e4m3 cache; through this op one workgroup per row, bit-equal to the single-row kernel (the multi-row kernel is
                            routed by td_attention_verify_ex) -- and the accept rule: the sampled tokens up to the first wrong guess
+attention_prefix_segments  context attention (vLLM's automatic prefix caching needs it): packed causal query segments, each over the key range of its own cache
+                           slot -- the rows of its cached prefix and its own -- in one launch of the tile kernel
 """
 import os
 
@@ -143,6 +145,8 @@ SCHEMAS = {
     "attention_verify": "(Tensor q, Tensor k, Tensor v, Tensor? k_scale, Tensor? v_scale, Tensor seq_row0, Tensor seq_rows, Tensor seq_len0, Tensor seq_slot, int Hq, int Hkv, "
                         "float scale) -> Tensor",
     "spec_accept": "(Tensor sampled, Tensor fed, Tensor seq_row0, Tensor seq_rows) -> (Tensor, Tensor)",
+    "attention_prefix_segments": "(Tensor q, Tensor k, Tensor v, Tensor seg_starts, Tensor kv_row0, Tensor kv_lens, int max_q_len, int max_kv_len, int Hq, int Hkv, "
+                                 "float scale) -> Tensor",
 }
 
 _loaded = False
