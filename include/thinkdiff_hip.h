@@ -596,6 +596,30 @@ int td_lora_pack_bf16(const void* A, const void* B, int rank, int N, int K, void
  * none left w_out receives the base bits.  TD_ERR_INVALID before any launch for anything else. */
 int td_lora_merge_bf16(const void* w_base, void* w_out, int N, int K, int n_adapters, const void* const* packed, const int* ranks,
                        const float* scales, void* stream);
+/* ---- Row-indexed low-rank add (td_abi_version() >= 24; csrc/lora_rows.hip): the UNMERGED form, every row under an adapter of its own, behind a base
+ * Linear that has already written y.  For a row whose adapter has A [r, K], B [N, r] and scale s:
+ *   t_j = bf16_rne( sum_k x_k A_jk )                                 fp32 accumulation; products are exact
+ *   y_n = bf16_rne( float(y_n) + s * sum_j float(t_j) B_nj )         fp32 accumulation; ONE rounding
+ * Rows with row_adapter[row] = -1 (or outside 0 .. n_adapters - 1) are not written, nor are rows whose adapter has a null operand for the segment.  No
+ * float atomics: K is split into slabs by a rule of K alone and the slabs are added in order, so a call is bit-reproducible and a row's result does not
+ * depend on the rows beside it.  What vLLM's punica shrink / expand pair does behind `enable_lora` ([ext] vllm/lora/ops), restated.
+ *   x            bf16 [rows, K], leading dimension ldx (>= K, % 8 == 0), 16-byte aligned; K % 64 == 0
+ *   row_adapter  DEVICE int32 [rows], read by the kernels: a captured launch stays valid when the assignment changes
+ *   packed       HOST array [n_adapters * n_segs] of device pointers, entry a * n_segs + s = the td_lora_rows_pack_bf16 form of adapter a's pair for
+ *                segment s (N = widths[s], the same K), or NULL: adapter a does not touch segment s
+ *   ranks/scales HOST [n_adapters]: rank 1 .. TD_LORA_ROWS_MAX_RANK, finite scale (looked at only for adapters with a non-null operand)
+ *   y/ldy/widths HOST [n_segs], 1 .. TD_LORA_ROWS_MAX_SEGS output segments: device bf16 pointer (8-byte aligned), leading dimension (>= width, % 4 == 0),
+ *                width (% 16 == 0).  A fused Linear is one call: [q | k | v] is three segments on one x, q into one buffer and k, v into another
+ *   ws/ws_bytes  device workspace of at least td_lora_rows_workspace_bytes(rows, K, n_segs, largest rank) bytes, 16-byte aligned; nothing is allocated
+ * TD_ERR_INVALID, naming the argument, before any HIP call for anything else.  With no non-null operand nothing is launched. */
+#define TD_LORA_ROWS_MAX_SEGS 3
+#define TD_LORA_ROWS_MAX_RANK 64
+/* Ap [r_pad, K] = lora_A.weight, then Bp [N, r_pad] = lora_B.weight, the rank zero-padded to r_pad = 16 ceil(rank / 16); N % 16 == 0, K % 64 == 0 */
+size_t td_lora_rows_packed_bytes(int rank, int N, int K);
+int td_lora_rows_pack_bf16(const void* A, const void* B, int rank, int N, int K, void* packed, void* stream);
+size_t td_lora_rows_workspace_bytes(int rows, int K, int n_segs, int max_rank);
+int td_lora_rows_bf16(const void* x, int64_t ldx, int rows, int K, const int32_t* row_adapter, int n_adapters, const void* const* packed, const int* ranks,
+                      const float* scales, int n_segs, void* const* y, const int64_t* ldy, const int* widths, void* ws, size_t ws_bytes, void* stream);
 /* The parameter AS THE FORWARD SEES IT NOW (the effective weight: base + merged adapters) -> dst (device bf16, `count` elements): the inverse of
  * td_flux_load_param; what `transformer.state_dict()[name]` is after fuse_lora. */
 int td_flux_read_param(td_flux* f, const char* name, void* dst, int64_t count, void* stream);
@@ -1112,6 +1136,31 @@ int td_qwen2_weight_info(const td_qwen2* f, int* mode, int* stream_on, int64_t* 
  * its replays launch nothing from the host and do not count).  The test handle that tells "the 8-bit kernels ran" from "the bf16 kernels ran on
  * W^", which the outputs alone cannot (the model is the same).  -1 on a NULL handle. */
 int64_t td_qwen2_weight_stream_launches(const td_qwen2* f);
+
+/* ---- per-request LoRA (td_abi_version() >= 24; vLLM's `enable_lora` with a LoRARequest per request) ------------------------------------------------
+ * UNMERGED adapters: every row of a prefill or a decode step names its own adapter (or none), and td_lora_rows_bf16 adds that adapter's low-rank update
+ * behind each base Linear of a layer (q | k | v in front of RoPE, o_proj, gate | up in front of SiLU * up, down_proj).  The base Linears are the launches
+ * they were, so every weight-stream mode and both cache formats work underneath; lm_head and the embeddings are never adapted.  A pass in which no row names
+ * an adapter -- and every pass of a handle on which LoRA is not enabled -- issues exactly the launches it issued before and returns the same bits.
+ * A decode step with an adapted row takes a launch list of its own (gate | up into the [B, 2 I] buffer, SiLU * up in its own launch, the wide path's RMSNorm
+ * out of the split-K reduction), captured under a graph key of its own; the row -> adapter array is device data, so the captured step replays under a
+ * changed assignment.  The rows' adapters come from a host map cache slot -> adapter:
+ *   td_qwen2_lora_set_slot sets it (index -1: none); td_qwen2_fork_slot and td_qwen2_move_slot give the destination the source's adapter;
+ *   td_qwen2_set_slots clears it; td_qwen2_gather_slots cannot know its sources: the caller sets all beams of a request to the request's adapter first. */
+/* Allocates the pool (max_loras <= TD_LORA_MAX_ADAPTERS adapters x layers x 7 Linears, each place sized for max_rank <= TD_LORA_ROWS_MAX_RANK) and the
+ * kernels' workspace for the handle's workspace rows.  Once per handle; not capturable; drops the step graphs. */
+int td_qwen2_lora_enable(td_qwen2* f, int max_loras, int max_rank);
+/* One pair of adapter `index` (0 .. max_loras - 1): `module` is the Hugging Face name of one of the 7 Linears of a layer ("model.layers.3.self_attn.q_proj",
+ * ..., "model.layers.3.mlp.down_proj"), A = lora_A.weight [rank, K], B = lora_B.weight [N, rank], device bf16 (the caller vouches for the extents: N, K are
+ * the module's), scale = lora_alpha / rank (or / sqrt(rank)).  One rank and scale per adapter.  A module an adapter never loads stays untouched for its rows.
+ * Packs into the pool on `stream`; drops the step graphs. */
+int td_qwen2_lora_load(td_qwen2* f, int index, const char* module, const void* A, const void* B, int rank, float scale, void* stream);
+/* Forgets every pair of adapter `index`; slots that named it name none.  Drops the step graphs. */
+int td_qwen2_lora_remove(td_qwen2* f, int index);
+int td_qwen2_lora_set_slot(td_qwen2* f, int slot, int index);
+/* max_loras (0: not enabled), adapters holding at least one pair, bytes held (pool + workspace), and the low-rank launches enqueued or captured so far
+ * (two per adapted Linear: the count td_qwen2_weight_stream_launches keeps for the 8-bit stream; an adapter-less pass adds none); any output may be NULL */
+int td_qwen2_lora_info(const td_qwen2* f, int* max_loras, int* resident, int64_t* bytes, int64_t* launches);
 
 /* ---- e4m3 KV cache (td_abi_version() >= 13; vLLM's `kv_cache_dtype="fp8"`) --------------------------------------------------------------------
  * Format (fixed): the weight format above applied to every 128-wide head vector x of a cache row (one token of one sequence, one layer; the rotated

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 23; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 24; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -49,6 +49,8 @@ int td_abi_version(void) { return 23; }  // 2: TdFluxConfig::out_channels append
                                             //     td_linear*_i4_bf16, td_qwen2_load_param_int4, td_qwen2_set_int4_routing, TD_QWEN2_WEIGHTS_INT4)
                                             // 23: prefix caching (td_attention_prefix_segments_bf16: packed query segments over key ranges of their own;
                                             //     td_qwen2_prefill_packed_prefix_slots: the packed prefill behind cached prefixes)
+                                            // 24: per-request LoRA (td_lora_rows_bf16, td_lora_rows_pack_bf16: the row-indexed low-rank add,
+                                            //     csrc/lora_rows.hip; td_qwen2_lora_*: the adapter pool of the Qwen2-VL decode engine)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,

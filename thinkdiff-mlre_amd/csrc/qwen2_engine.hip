@@ -114,6 +114,23 @@ struct td_qwen2 {
   bf16_t* kvstage = nullptr;
   int* stage_map = nullptr;
   float* sk_ws = nullptr;                       // partial sums of the decode step's split-K Linears (65-256 sequences): the engine's own buffer, so a captured step allocates nothing
+  // Per-request LoRA (td_qwen2_lora_enable; csrc/lora_rows.hip): a pool of lora_max adapters x layers x 7 Linears of packed pairs, each place sized for
+  // lora_max_rank; the row -> adapter array of a pass at a fixed device address (written before the pass, as ibuf is) and the kernels' workspace for ws_rows rows
+  int lora_max = 0, lora_max_rank = 0;
+  char* lora_arena = nullptr;
+  int64_t lora_pool_bytes = 0;
+  int64_t lora_place[7] = {0, 0, 0, 0, 0, 0, 0};   // byte offset of a Linear's place inside one (adapter, layer) block, and the block's size
+  int64_t lora_block = 0;
+  int* lora_rows = nullptr;                     // device int32 [ws_rows]
+  char* lora_ws = nullptr;
+  size_t lora_ws_bytes = 0;
+  std::vector<char> lora_have;                  // [lora_max][layers][7]
+  std::vector<int> lora_rank, lora_count;       // per adapter: its rank (one per adapter: rank_pattern is not served) and the pairs it holds
+  std::vector<float> lora_scale;
+  std::vector<int> slot_lora;                   // host map cache slot -> adapter (td_qwen2_lora_set_slot); slots past its end are -1
+  std::vector<int> lora_rows_host;              // host image of lora_rows (kept alive across the asynchronous upload)
+  long long lora_launches = 0;                  // low-rank launches enqueued (or captured) so far (td_qwen2_lora_info)
+  int slot_adapter(int slot) const { return slot >= 0 && slot < (int)slot_lora.size() ? slot_lora[(size_t)slot] : -1; }
 };
 
 namespace {
@@ -286,7 +303,67 @@ struct PrefillForm {
   // e4m3 cache behind cached prefixes (q8_stage_n > 0; to_rows given): once the new rows are in the cache, cache row q8_stage_rows[r] (device ints) is
   // dequantised into row r of f->kvstage for r < q8_stage_n -- every sequence's rows [0, prefix + len), packed per segment -- and the attention reads kvstage
   const int* q8_stage_rows = nullptr; int q8_stage_n = 0;
+  bool lora = false;           // some row names an adapter (f->lora_rows is written): the low-rank add follows each of the four Linears
 };
+
+// The low-rank add behind one fused Linear of layer `layer` (td_lora_rows_bf16): segments m0 .. m0 + n_segs - 1 of the 7 Linears (q, k, v, o, gate, up, down)
+// on one input x [rows, K], segment i into y[i].  The rows' adapters are in f->lora_rows already.  Nothing is launched where no resident adapter holds a
+// pair for one of the segments.
+int lora_add(td_qwen2* f, int layer, int m0, int n_segs, const bf16_t* x, int ldx, int rows, int K, bf16_t* const* y, const int64_t* ldy, const int* widths,
+             hipStream_t s) {
+  const void* packed[TD_LORA_MAX_ADAPTERS * TD_LORA_ROWS_MAX_SEGS];
+  bool any = false;
+  for (int a = 0; a < f->lora_max; ++a)
+    for (int i = 0; i < n_segs; ++i) {
+      const bool have = f->lora_have[((size_t)a * f->layers.size() + layer) * 7 + m0 + i] != 0;
+      packed[a * n_segs + i] = have ? f->lora_arena + ((size_t)a * f->layers.size() + layer) * f->lora_block + f->lora_place[m0 + i] : nullptr;
+      any = any || have;
+    }
+  if (!any) return TD_OK;
+  f->lora_launches += 2;      // shrink + expand
+  return td_lora_rows_bf16(x, ldx, rows, K, f->lora_rows, f->lora_max, packed, f->lora_rank.data(), f->lora_scale.data(), n_segs, (void* const*)y, ldy, widths,
+                           f->lora_ws, f->lora_ws_bytes, s);
+}
+int lora_add_qkv(td_qwen2* f, int layer, bf16_t* kv_new, int rows, hipStream_t s) {
+  const int QW = f->Hq * 128, HW = f->Hkv * 128;
+  bf16_t* y[3] = {f->q, kv_new, kv_new + HW};
+  const int64_t ldy[3] = {QW, 2 * HW, 2 * HW};
+  const int widths[3] = {QW, HW, HW};
+  return lora_add(f, layer, 0, 3, f->xn, f->D, rows, f->D, y, ldy, widths, s);
+}
+int lora_add_o(td_qwen2* f, int layer, int rows, hipStream_t s) {
+  bf16_t* y[1] = {f->h};
+  const int64_t ldy[1] = {f->D};
+  const int widths[1] = {f->D};
+  return lora_add(f, layer, 3, 1, f->attn, f->Hq * 128, rows, f->Hq * 128, y, ldy, widths, s);
+}
+int lora_add_gu(td_qwen2* f, int layer, int rows, hipStream_t s) {
+  bf16_t* y[2] = {f->gu, f->gu + f->I};
+  const int64_t ldy[2] = {2 * f->I, 2 * f->I};
+  const int widths[2] = {f->I, f->I};
+  return lora_add(f, layer, 4, 2, f->xn, f->D, rows, f->D, y, ldy, widths, s);
+}
+int lora_add_down(td_qwen2* f, int layer, int rows, hipStream_t s) {
+  bf16_t* y[1] = {f->h};
+  const int64_t ldy[1] = {f->D};
+  const int widths[1] = {f->D};
+  return lora_add(f, layer, 6, 1, f->act, f->I, rows, f->I, y, ldy, widths, s);
+}
+
+// The rows' adapters of a pass -> f->lora_rows, from the host image the entry filled; false (nothing uploaded: the pass is the adapter-less one) where LoRA is
+// off or no row names an adapter.  rc: the upload's status.
+bool lora_upload_rows(td_qwen2* f, int n, hipStream_t s, int* rc) {
+  *rc = TD_OK;
+  if (f->lora_max == 0) return false;
+  bool any = false;
+  for (int r = 0; r < n; ++r) any = any || f->lora_rows_host[(size_t)r] >= 0;
+  if (!any) return false;
+  if (hipMemcpyAsync(f->lora_rows, f->lora_rows_host.data(), (size_t)n * 4, hipMemcpyHostToDevice, s) != hipSuccess) {
+    td_set_error("td_qwen2: the upload of the row -> adapter array failed");
+    *rc = TD_ERR_HIP;
+  }
+  return true;
+}
 
 // Runs form.n rows through the decoder: embed (or take inputs_embeds), M-RoPE table, every layer, model.norm -- left in f->xn and copied to
 // hidden_out if given.  The caller has checked its arguments; which rows feed lm_head is its business too.
@@ -309,7 +386,8 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
   TdAttnParams ap = form.attn;
   const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
 
-  for (const QLayer& l : f->layers) {
+  for (int li = 0; li < (int)f->layers.size(); ++li) {
+    const QLayer& l = f->layers[(size_t)li];
     bf16_t* kv_new = kv8 ? f->kvtmp + (size_t)form.q8_tmp_row0 * KVW : form.kv_new.of(f, l);
     if (kv8 && form.q8_tmp_row0 > 0)
       TD_TRY(td_kv_dequant_rows_launch(l.kv8 + (size_t)form.q8_cache_row0 * KVW, KVW, l.kvs + (size_t)form.q8_cache_row0 * 2 * Hkv, 2 * Hkv, f->kvtmp, KVW,
@@ -330,6 +408,7 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
         TD_TRY(td_gemm_launch(b, s));
       }
     }
+    if (form.lora) TD_TRY(lora_add_qkv(f, li, kv_new, n, s));      // in front of RoPE
     TD_TRY(td_qk_norm_rope_launch(rq, s));
     rk.qkv = kv_new; TD_TRY(td_qk_norm_rope_launch(rk, s));
     if (kv8) {      // the quantising scatter runs BEFORE the attention, which then reads K^ | V^: no result depends on where a key came from
@@ -345,12 +424,15 @@ int prefill_pass(td_qwen2* f, const PrefillForm& form, const int* token_ids, con
     TD_TRY(td_attn_launch(ap, s));
     // h += o_proj(attn)
     TD_TRY(run_linear(f, linear(f->attn, QW, l.o_w, nullptr, f->h, D, n, D, QW, true), l.o_8, s));
+    if (form.lora) TD_TRY(lora_add_o(f, li, n, s));
     np.w = l.ln2_w;
     TD_TRY(td_norm_rows_launch(np, s));
     // gate | up, SwiGLU, down (+ residual)
     TD_TRY(run_linear(f, linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, n, 2 * I, D), l.gu_8, s));
+    if (form.lora) TD_TRY(lora_add_gu(f, li, n, s));               // in front of SiLU * up
     TD_TRY(td_silu_mul_launch(f->gu, f->act, n, I, s));
     TD_TRY(run_linear(f, linear(f->act, I, l.down_w, nullptr, f->h, D, n, D, I, true), l.down_8, s));
+    if (form.lora) TD_TRY(lora_add_down(f, li, n, s));
   }
   // model.norm -> captured embedding
   np.w = f->norm_w;
@@ -519,6 +601,7 @@ void td_qwen2_destroy(td_qwen2* f) {
   if (f->w8_arena) (void)hipFree(f->w8_arena);
   if (f->kv8_arena) (void)hipFree(f->kv8_arena);
   if (f->kvstage) (void)hipFree(f->kvstage);
+  if (f->lora_arena) (void)hipFree(f->lora_arena);
   delete f;
 }
 
@@ -815,6 +898,12 @@ int td_qwen2_forward_slot(td_qwen2* f, int slot, const int* token_ids, const voi
     form.kv_new = KvRows{seq + pos0 * KVW};      // k | v -> straight into the layer's cache rows
     form.attn_kv = KvRows{seq};
   }
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.assign((size_t)n, f->slot_adapter(slot));
+    form.lora = lora_upload_rows(f, n, s, &rc);
+    TD_TRY(rc);
+  }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) TD_TRY(lm_head(f, f->xn + (size_t)(n - 1) * f->D, 1, logits_last, s));
   return TD_OK;
@@ -834,6 +923,7 @@ int td_qwen2_set_slots(td_qwen2* f, int n_slots) {
   TD_CHECK_ARG(f && n_slots >= 1 && n_slots <= f->max_tokens, "td_qwen2_set_slots: bad slot count %d", n_slots);
   f->n_slots = n_slots;
   f->slot_len = f->max_tokens / n_slots < f->ws_rows ? f->max_tokens / n_slots : f->ws_rows;
+  f->slot_lora.clear();     // the slots are other cache rows now: none carries an adapter
   drop_step_graphs(f);      // the captured steps carry the old slot stride
   return TD_OK;
 }
@@ -850,6 +940,10 @@ int td_qwen2_slot_capacity(const td_qwen2* f) { return f ? f->slot_len : 0; }
 
 int td_qwen2_move_slot(td_qwen2* f, int src, int dst, int len, void* stream) {
   TD_CHECK_ARG(f && src >= 0 && src < f->n_slots && dst >= 0 && dst < f->n_slots && len >= 0 && len <= f->slot_len, "td_qwen2_move_slot: bad arguments");
+  if (src != dst && f->lora_max > 0) {      // the destination continues the source's sequence: under its adapter
+    if ((int)f->slot_lora.size() <= dst) f->slot_lora.resize((size_t)dst + 1, -1);
+    f->slot_lora[(size_t)dst] = f->slot_adapter(src);
+  }
   if (src == dst || len == 0) return TD_OK;
   const size_t KVW = (size_t)2 * f->Hkv * 128;
   if (f->kv_mode == TD_QWEN2_KV_E4M3) {      // both planes
@@ -875,6 +969,11 @@ int td_qwen2_fork_slot(td_qwen2* f, int src, const int* dst_slots, int n_dst, in
   for (int i = 0; i < n_dst; ++i)
     TD_CHECK_ARG(dst_slots[i] >= 0 && dst_slots[i] < f->n_slots, "td_qwen2_fork_slot: destination slot %d outside the %d configured sequences", dst_slots[i], f->n_slots);
   TD_CHECK_ARG(len >= 0 && len <= f->slot_len, "td_qwen2_fork_slot: len=%d exceeds the slot capacity %d", len, f->slot_len);
+  if (f->lora_max > 0)
+    for (int i = 0; i < n_dst; ++i) {      // every destination continues the source's sequence: under its adapter
+      if ((int)f->slot_lora.size() <= dst_slots[i]) f->slot_lora.resize((size_t)dst_slots[i] + 1, -1);
+      f->slot_lora[(size_t)dst_slots[i]] = f->slot_adapter(src);
+    }
   const int64_t KVW = (int64_t)2 * f->Hkv * 128, SW = (int64_t)2 * f->Hkv;
   std::vector<TdKvPlane> planes;
   for (const QLayer& l : f->layers) {
@@ -923,7 +1022,10 @@ namespace {
 // sequence: ibuf holds row_off per ROW where it always does and the four per-SEQUENCE arrays of td_attn_verify_launch around it (first row | - | rows |
 // keys visible to the first row | cache slot).  Everything but the attention is the step of B sequences; the rotary embedding and the cache write take
 // their separate launch, so that every new k | v row is in the cache before the attention, which serves all rows of a sequence from one pass over it.
-int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s, int vr_seqs = 0, int vr_tmax = 0) {
+// lora: some row names an adapter (f->lora_rows is written).  The step then takes a launch list of its own: the low-rank add behind each of the four Linears,
+// gate | up into the [B, 2 I] buffer with SiLU * up in a launch of its own (the fused GLU stream applies the activation before an update could be added), and on
+// the wide path the RMSNorm out of the split-K reduction and into td_norm_rows_launch (the fused norm would read h before the update reaches it).
+int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s, int vr_seqs = 0, int vr_tmax = 0, bool lora = false) {
   const int D = f->D, I = f->I, Hq = f->Hq, Hkv = f->Hkv;
   const int QW = Hq * 128, KVW = 2 * Hkv * 128;
   const int* kv_lens = f->ibuf;
@@ -952,7 +1054,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
   for (int i = 0; i < f->cfg.num_layers; ++i) {
     const QLayer& l = f->layers[i];
     // (wide steps: the reduction launch of the Linear in front normalises the rows it finishes -- TdGemmParams::sk_norm_w -- so only layer 0 has a norm launch)
-    if (!wide || i == 0) {
+    if (!wide || lora || i == 0) {
       np.w = l.ln1_w;
       TD_TRY(td_norm_rows_launch(np, s));
     }
@@ -962,6 +1064,7 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
       if (wide) { g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES; }      // (tile width and parts by the wide planner: n_split = Hq 128 fits its 64- / 128-column tiles)
       TD_TRY(run_linear(f, g, l.qkv_8, s, a8));
     }
+    if (lora) TD_TRY(lora_add_qkv(f, i, f->kvtmp, B, s));
     // rotary embedding of the new q / k rows and the cache write ride inside the attention launch (TdAttnParams::dec_kv_new);
     // td_qwen2_set_fused_rope(f, 0): the separate launch (A/B and the bit-identity test)
     const bool kv8 = f->kv_mode == TD_QWEN2_KV_E4M3;
@@ -991,15 +1094,23 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
       TdGemmParams g = linear(f->attn, QW, l.o_w, nullptr, f->h, D, B, D, QW, true);
       if (wide) {
         g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES;
-        g.sk_norm_w = l.ln2_w; g.sk_norm_out = f->xn; g.sk_norm_ld = D; g.sk_norm_eps = f->cfg.rms_eps;
+        if (!lora) { g.sk_norm_w = l.ln2_w; g.sk_norm_out = f->xn; g.sk_norm_ld = D; g.sk_norm_eps = f->cfg.rms_eps; }
       }
       TD_TRY(run_linear(f, g, l.o_8, s, a8));
     }
-    if (!wide) {
+    if (lora) TD_TRY(lora_add_o(f, i, B, s));
+    if (!wide || lora) {
       np.w = l.ln2_w;
       TD_TRY(td_norm_rows_launch(np, s));
     }
-    if (!wide) {
+    if (lora) {      // gate | up as one Linear, the add, then SiLU and product in a pass of their own (the prefill's rounding points)
+      TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->gu, 2 * I, B, 2 * I, D);
+      if (wide) { g.split_k = -1; g.sk_ws = f->sk_ws; g.sk_ws_bytes = SK_WS_BYTES; }
+      if (wide) TD_TRY(td_gemm_launch(g, s));
+      else TD_TRY(run_linear(f, g, l.gu_8, s, a8));
+      TD_TRY(lora_add_gu(f, i, B, s));
+      TD_TRY(td_silu_mul_launch(f->gu, f->act, B, I, s));
+    } else if (!wide) {
       TdGemmParams g = linear(f->xn, D, l.gu_w, nullptr, f->act, I, B, I, D);
       g.glu_I = I;   // gate | up, SiLU and product in one pass
       TD_TRY(run_linear(f, g, l.gu_8, s, a8));
@@ -1012,12 +1123,15 @@ int decode_step(td_qwen2* f, int B, int max_len, bool want_logits, hipStream_t s
     TdGemmParams d = linear(f->act, I, l.down_w, nullptr, f->h, D, B, D, I, true);
     if (wide) {
       d.split_k = -1; d.sk_ws = f->sk_ws; d.sk_ws_bytes = SK_WS_BYTES;
-      d.sk_norm_w = i + 1 < f->cfg.num_layers ? f->layers[i + 1].ln1_w : f->norm_w;      // the next layer's input norm, or model.norm
-      d.sk_norm_out = f->xn; d.sk_norm_ld = D; d.sk_norm_eps = f->cfg.rms_eps;
+      if (!lora) {
+        d.sk_norm_w = i + 1 < f->cfg.num_layers ? f->layers[i + 1].ln1_w : f->norm_w;      // the next layer's input norm, or model.norm
+        d.sk_norm_out = f->xn; d.sk_norm_ld = D; d.sk_norm_eps = f->cfg.rms_eps;
+      }
     }
     TD_TRY(run_linear(f, d, l.down_8, s, a8));
+    if (lora) TD_TRY(lora_add_down(f, i, B, s));
   }
-  if (!wide) {
+  if (!wide || lora) {
     np.w = f->norm_w; np.y = f->xn;
     TD_TRY(td_norm_rows_launch(np, s));
   }
@@ -1060,17 +1174,25 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
   }
   hipLaunchKernelGGL(td_set_ints_kernel, dim3(1), dim3(3 * MAX_BATCH), 0, s, f->ibuf, ip, 3 * MAX_BATCH);
   TD_CHECK_LAUNCH();
+  bool lora = false;      // the rows' adapters from the slot map: device data, so a captured LoRA step replays under a changed assignment
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.resize((size_t)B);
+    for (int b = 0; b < B; ++b) f->lora_rows_host[(size_t)b] = f->slot_adapter(slots ? slots[b] : b);
+    lora = lora_upload_rows(f, B, s, &rc);
+    TD_TRY(rc);
+  }
   // the step reads its ids from fixed buffers and leaves its outputs in fixed buffers (the captured form needs stable addresses)
   TD_CHECK_HIP(hipMemcpyAsync(f->tok_buf, token_ids, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   TD_CHECK_HIP(hipMemcpyAsync(f->pos_buf, position_ids, (size_t)3 * B * 4, hipMemcpyDeviceToDevice, s));
   const bool want_logits = logits != nullptr;
-  const int key = 2 * B + (want_logits ? 1 : 0);
+  const int key = 2 * B + (want_logits ? 1 : 0) + (lora ? 1 << 20 : 0);      // (a LoRA step is another launch list)
   static const bool no_graph = getenv("TD_QWEN2_NO_GRAPH") != nullptr;
   auto it = f->step_graphs.find(key);
   if (it != f->step_graphs.end()) {
     TD_CHECK_HIP(hipGraphLaunch(it->second, s));
   } else if (no_graph || !f->graphs_ok || f->step_calls[key]++ == 0) {
-    TD_TRY(decode_step(f, B, max_len, want_logits, s));
+    TD_TRY(decode_step(f, B, max_len, want_logits, s, 0, 0, lora));
   } else {
     // capture on the engine's own stream (the caller's may be the legacy default stream, which cannot capture), after everything the caller
     // queued so far: nothing runs during a capture, but the eager fallback below must see the ids copied above
@@ -1079,7 +1201,7 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
     hipGraphExec_t exec = nullptr;
     bool ok = hipStreamBeginCapture(f->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess;
     if (ok) {
-      const int rc = decode_step(f, B, max_len, want_logits, f->capture_stream);
+      const int rc = decode_step(f, B, max_len, want_logits, f->capture_stream, 0, 0, lora);
       ok = hipStreamEndCapture(f->capture_stream, &graph) == hipSuccess && rc == TD_OK && graph != nullptr;
     }
     if (ok) ok = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess;
@@ -1091,7 +1213,7 @@ int td_qwen2_decode_batch_slots(td_qwen2* f, int B, const int* slots, const int*
     } else {
       (void)hipGetLastError();
       f->graphs_ok = false;      // this runtime cannot capture the step: stay on the eager path for good
-      TD_TRY(decode_step(f, B, max_len, want_logits, s));
+      TD_TRY(decode_step(f, B, max_len, want_logits, s, 0, 0, lora));
     }
   }
   if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)B * D * 2, hipMemcpyDeviceToDevice, s));
@@ -1133,7 +1255,16 @@ int td_qwen2_verify_batch_slots(td_qwen2* f, int B, const int* slots, const int*
   TD_CHECK_HIP(hipMemcpyAsync(f->tok_buf, token_ids, (size_t)R * 4, hipMemcpyDeviceToDevice, s));
   // (pos_buf is [3, R] here: the table launch reads stream k of row r at k R + r)
   TD_CHECK_HIP(hipMemcpyAsync(f->pos_buf, position_ids, (size_t)3 * R * 4, hipMemcpyDeviceToDevice, s));
-  TD_TRY(decode_step(f, R, max_len, logits != nullptr, s, B, t_max));
+  bool lora = false;      // a sequence's adapter on all of its rows
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.resize((size_t)R);
+    for (int b = 0, r = 0; b < B; ++b)
+      for (int j = 0; j < n_new[b]; ++j) f->lora_rows_host[(size_t)r++] = f->slot_adapter(slots ? slots[b] : b);
+    lora = lora_upload_rows(f, R, s, &rc);
+    TD_TRY(rc);
+  }
+  TD_TRY(decode_step(f, R, max_len, logits != nullptr, s, B, t_max, lora));
   if (hidden_out) TD_CHECK_HIP(hipMemcpyAsync(hidden_out, f->xn, (size_t)R * f->D * 2, hipMemcpyDeviceToDevice, s));
   if (logits) TD_CHECK_HIP(hipMemcpyAsync(logits, f->logits_buf, (size_t)R * f->cfg.vocab * 2, hipMemcpyDeviceToDevice, s));
   return TD_OK;
@@ -1174,6 +1305,14 @@ int td_qwen2_prefill_batch_at(td_qwen2* f, int slot0, int B, int L, const int* t
     form.to_slots = kv0; form.slots_L = L;
     form.attn.kv_bstride = f->slot_len * KVW;
     form.attn_kv = KvRows{kv0};
+  }
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.resize((size_t)B * L);
+    for (int b = 0; b < B; ++b)
+      for (int t = 0; t < L; ++t) f->lora_rows_host[(size_t)b * L + t] = f->slot_adapter(slot0 + b);
+    form.lora = lora_upload_rows(f, B * L, s, &rc);
+    TD_TRY(rc);
   }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
@@ -1235,6 +1374,14 @@ int td_qwen2_prefill_packed_slots(td_qwen2* f, int B, const int* slots, const in
   form.to_rows = f->row_map;
   form.attn = prefill_attn(f, B, L, L, 0);      // causal attention inside each packed prompt, straight from the projection rows (a prefill starts at position 0)
   form.attn.seg_starts = seg_starts;
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.resize((size_t)n);
+    for (int b = 0, q = 0; b < B; ++b)
+      for (int t = 0; t < lens[b]; ++t) f->lora_rows_host[(size_t)q++] = f->slot_adapter(slots[b]);
+    form.lora = lora_upload_rows(f, n, s, &rc);
+    TD_TRY(rc);
+  }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     hipLaunchKernelGGL(td_gather_last_rows_kernel, dim3((D / 8 + 255) / 256, B), dim3(256), 0, s, f->xn, f->lastrows, seg_starts, D);
@@ -1316,12 +1463,132 @@ int td_qwen2_prefill_packed_prefix_slots(td_qwen2* f, int B, const int* slots, c
   form.attn.kv_seg_lens = kv_lens;
   if (kv8) { form.q8_stage_rows = f->stage_map; form.q8_stage_n = (int)staged; }
   else form.attn_kv = KvRows{0};                  // K / V = the layer's cache, seen as rows
+  if (f->lora_max > 0) {
+    int rc;
+    f->lora_rows_host.resize((size_t)n);
+    for (int b = 0, q = 0; b < B; ++b)
+      for (int t = 0; t < lens[b]; ++t) f->lora_rows_host[(size_t)q++] = f->slot_adapter(slots[b]);
+    form.lora = lora_upload_rows(f, n, s, &rc);
+    TD_TRY(rc);
+  }
   TD_TRY(prefill_pass(f, form, token_ids, inputs_embeds, position_ids, hidden_out, s));
   if (logits_last) {
     hipLaunchKernelGGL(td_gather_last_rows_kernel, dim3((D / 8 + 255) / 256, B), dim3(256), 0, s, f->xn, f->lastrows, seg_starts, D);
     TD_TRY(lm_head(f, f->lastrows, B, logits_last, s));
   }
   TD_CHECK_LAUNCH();
+  return TD_OK;
+}
+
+// ---- per-request LoRA: the adapter pool, the slot map and what the passes above read ------------------------------------------------------------------------
+
+int td_qwen2_lora_enable(td_qwen2* f, int max_loras, int max_rank) {
+  TD_CHECK_ARG(f, "td_qwen2_lora_enable: null handle");
+  TD_CHECK_ARG(max_loras >= 1 && max_loras <= TD_LORA_MAX_ADAPTERS, "td_qwen2_lora_enable: max_loras=%d outside 1..%d", max_loras, TD_LORA_MAX_ADAPTERS);
+  TD_CHECK_ARG(max_rank >= 1 && max_rank <= TD_LORA_ROWS_MAX_RANK, "td_qwen2_lora_enable: max_rank=%d outside 1..%d", max_rank, TD_LORA_ROWS_MAX_RANK);
+  TD_CHECK_ARG(f->lora_max == 0, "td_qwen2_lora_enable: LoRA is enabled on this handle already (max_loras=%d, max_rank=%d)", f->lora_max, f->lora_max_rank);
+  const int D = f->D, I = f->I, QW = f->Hq * 128, HW = f->Hkv * 128;
+  const int N[7] = {QW, HW, HW, D, I, I, D}, K[7] = {D, D, D, QW, D, D, I};
+  auto pad = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+  int64_t block = 0, place[7];
+  for (int m = 0; m < 7; ++m) {
+    TD_CHECK_ARG(N[m] % 16 == 0 && K[m] % 64 == 0, "td_qwen2_lora_enable: the low-rank kernels need every Linear's N=%d %% 16 == 0 and K=%d %% 64 == 0", N[m], K[m]);
+    place[m] = block;
+    block += pad((int64_t)td_lora_rows_packed_bytes(max_rank, N[m], K[m]));
+  }
+  const int64_t pool = block * max_loras * (int64_t)f->layers.size();
+  size_t ws = 0;
+  const int wsK[4] = {D, QW, D, I}, wsS[4] = {3, 1, 2, 1};
+  for (int i = 0; i < 4; ++i) ws = std::max(ws, td_lora_rows_workspace_bytes(f->ws_rows, wsK[i], wsS[i], max_rank));
+  const int64_t rows_bytes = pad((int64_t)f->ws_rows * 4);
+  hipError_t e = hipMalloc((void**)&f->lora_arena, (size_t)(pool + rows_bytes + pad((int64_t)ws)));
+  if (e != hipSuccess) {
+    f->lora_arena = nullptr;
+    td_set_error("td_qwen2_lora_enable: hipMalloc of %.2f GiB for %d adapters of rank %d failed: %s", (pool + rows_bytes + ws) / double(1 << 30), max_loras, max_rank,
+                 hipGetErrorString(e));
+    return TD_ERR_HIP;
+  }
+  f->lora_max = max_loras; f->lora_max_rank = max_rank;
+  f->lora_pool_bytes = pool; f->lora_block = block;
+  for (int m = 0; m < 7; ++m) f->lora_place[m] = place[m];
+  f->lora_rows = (int*)(f->lora_arena + pool);
+  f->lora_ws = f->lora_arena + pool + rows_bytes;
+  f->lora_ws_bytes = ws;
+  f->lora_have.assign((size_t)max_loras * f->layers.size() * 7, 0);
+  f->lora_rank.assign((size_t)TD_LORA_MAX_ADAPTERS, 0);
+  f->lora_count.assign((size_t)TD_LORA_MAX_ADAPTERS, 0);
+  f->lora_scale.assign((size_t)TD_LORA_MAX_ADAPTERS, 0.f);
+  f->slot_lora.clear();
+  drop_step_graphs(f);
+  return TD_OK;
+}
+
+int td_qwen2_lora_load(td_qwen2* f, int index, const char* module, const void* A, const void* B, int rank, float scale, void* stream) {
+  TD_CHECK_ARG(f && module && A && B, "td_qwen2_lora_load: the handle, module, A and B are required");
+  TD_CHECK_ARG(f->lora_max > 0, "td_qwen2_lora_load: LoRA is not enabled on this handle (td_qwen2_lora_enable first)");
+  TD_CHECK_ARG(index >= 0 && index < f->lora_max, "td_qwen2_lora_load: index=%d outside the %d adapters of the pool", index, f->lora_max);
+  TD_CHECK_ARG(rank >= 1 && rank <= f->lora_max_rank, "td_qwen2_lora_load: rank=%d outside 1..%d (max_rank of td_qwen2_lora_enable)", rank, f->lora_max_rank);
+  TD_CHECK_ARG(scale == scale && scale - scale == 0.f, "td_qwen2_lora_load: scale is not finite");
+  int layer = -1, used = 0;
+  char sub[16] = {0}, name[16] = {0};
+  const bool parsed = sscanf(module, "model.layers.%d.%15[a-z_].%15[a-z_]%n", &layer, sub, name, &used) == 3 && module[used] == 0;
+  static const char* const names[7] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
+  int m = -1;
+  if (parsed)
+    for (int i = 0; i < 7; ++i)
+      if ((std::string(sub) + "." + name) == names[i]) m = i;
+  TD_CHECK_ARG(m >= 0 && layer >= 0 && layer < (int)f->layers.size(),
+               "td_qwen2_lora_load: module '%s' is not one of the 7 Linears of a decoder layer (model.layers.N.self_attn.{q,k,v,o}_proj, model.layers.N.mlp.{gate,up,down}_proj, "
+               "N < %d)", module, (int)f->layers.size());
+  TD_CHECK_ARG(f->lora_count[(size_t)index] == 0 || (f->lora_rank[(size_t)index] == rank && f->lora_scale[(size_t)index] == scale),
+               "td_qwen2_lora_load: adapter %d holds pairs of rank=%d, scale=%g; '%s' comes with rank=%d, scale=%g (one rank and scale per adapter: rank_pattern / "
+               "alpha_pattern are not served)", index, f->lora_rank[(size_t)index], f->lora_scale[(size_t)index], module, rank, scale);
+  const int D = f->D, I = f->I, QW = f->Hq * 128, HW = f->Hkv * 128;
+  const int N[7] = {QW, HW, HW, D, I, I, D}, K[7] = {D, D, D, QW, D, D, I};
+  drop_step_graphs(f);      // the captured LoRA steps carry which pairs exist, their ranks and scales
+  char* dst = f->lora_arena + ((size_t)index * f->layers.size() + layer) * f->lora_block + f->lora_place[m];
+  TD_TRY(td_lora_rows_pack_bf16(A, B, rank, N[m], K[m], dst, stream));
+  char& have = f->lora_have[((size_t)index * f->layers.size() + layer) * 7 + m];
+  if (!have) { have = 1; ++f->lora_count[(size_t)index]; }
+  f->lora_rank[(size_t)index] = rank;
+  f->lora_scale[(size_t)index] = scale;
+  return TD_OK;
+}
+
+int td_qwen2_lora_remove(td_qwen2* f, int index) {
+  TD_CHECK_ARG(f, "td_qwen2_lora_remove: null handle");
+  TD_CHECK_ARG(f->lora_max > 0, "td_qwen2_lora_remove: LoRA is not enabled on this handle (td_qwen2_lora_enable first)");
+  TD_CHECK_ARG(index >= 0 && index < f->lora_max, "td_qwen2_lora_remove: index=%d outside the %d adapters of the pool", index, f->lora_max);
+  const size_t per = f->layers.size() * 7;
+  std::fill(f->lora_have.begin() + (size_t)index * per, f->lora_have.begin() + (size_t)(index + 1) * per, 0);
+  f->lora_count[(size_t)index] = 0;
+  f->lora_rank[(size_t)index] = 0;
+  f->lora_scale[(size_t)index] = 0.f;
+  for (int& a : f->slot_lora)
+    if (a == index) a = -1;      // no slot keeps naming a place that another adapter may take
+  drop_step_graphs(f);
+  return TD_OK;
+}
+
+int td_qwen2_lora_set_slot(td_qwen2* f, int slot, int index) {
+  TD_CHECK_ARG(f, "td_qwen2_lora_set_slot: null handle");
+  TD_CHECK_ARG(slot >= 0 && slot < f->n_slots, "td_qwen2_lora_set_slot: slot %d outside the %d configured sequences", slot, f->n_slots);
+  TD_CHECK_ARG(index == -1 || f->lora_max > 0, "td_qwen2_lora_set_slot: LoRA is not enabled on this handle (td_qwen2_lora_enable first)");
+  TD_CHECK_ARG(index >= -1 && index < f->lora_max, "td_qwen2_lora_set_slot: index=%d outside -1 (no adapter) .. %d", index, f->lora_max - 1);
+  if (index < 0 && slot >= (int)f->slot_lora.size()) return TD_OK;
+  if ((int)f->slot_lora.size() <= slot) f->slot_lora.resize((size_t)slot + 1, -1);
+  f->slot_lora[(size_t)slot] = index;
+  return TD_OK;
+}
+
+int td_qwen2_lora_info(const td_qwen2* f, int* max_loras, int* resident, int64_t* bytes, int64_t* launches) {
+  TD_CHECK_ARG(f, "td_qwen2_lora_info: null handle");
+  int n = 0;
+  for (int c : f->lora_count) n += c > 0 ? 1 : 0;
+  if (max_loras) *max_loras = f->lora_max;
+  if (resident) *resident = n;
+  if (bytes) *bytes = f->lora_max > 0 ? f->lora_pool_bytes + (int64_t)f->lora_ws_bytes + (int64_t)f->ws_rows * 4 : 0;
+  if (launches) *launches = f->lora_launches;
   return TD_OK;
 }
 

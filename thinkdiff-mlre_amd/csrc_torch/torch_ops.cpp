@@ -939,6 +939,61 @@ at::Tensor& lora_merge_(at::Tensor& w, at::TensorList A, at::TensorList B, at::A
   ok(td_lora_merge_bf16(w.data_ptr(), w.data_ptr(), (int)N, (int)K, (int)ptrs.size(), ptrs.data(), ranks.data(), sc.data(), stream_of(w)));
   return w;
 }
+// the row-indexed low-rank add (td_lora_rows_bf16; csrc/lora_rows.hip), in place on the output segments ys: ys[s][row] += scales[a] * B (bf16(A x[row])) for
+// a = row_adapter[row] >= 0, one rounding.  A / B hold the pairs that exist, pair[a * len(ys) + s] the index of adapter a's pair for segment s in them or -1
+// (the adapter does not touch the segment).  The kernels' operand form of every pair is made here, per call (the engine makes it once).
+void lora_rows_(const at::Tensor& x, const at::Tensor& row_adapter, at::TensorList A, at::TensorList B, at::IntArrayRef pair, at::ArrayRef<double> scales,
+                at::TensorList ys) {
+  check_rows(x, "x");
+  TORCH_CHECK(x.dim() == 2, "thinkdiff_hip::lora_rows_: x must be [rows, K]");
+  const int64_t rows = x.size(0), K = x.size(1);
+  const size_t n_ad = scales.size(), n_segs = ys.size();
+  TORCH_CHECK(n_ad <= TD_LORA_MAX_ADAPTERS, "thinkdiff_hip::lora_rows_: ", n_ad, " adapters, one call takes at most ", TD_LORA_MAX_ADAPTERS);
+  TORCH_CHECK(n_segs >= 1 && n_segs <= TD_LORA_ROWS_MAX_SEGS, "thinkdiff_hip::lora_rows_: ", n_segs, " output segments outside 1..", TD_LORA_ROWS_MAX_SEGS);
+  TORCH_CHECK(A.size() == B.size() && pair.size() == n_ad * n_segs, "thinkdiff_hip::lora_rows_: ", A.size(), " A, ", B.size(), " B, ", pair.size(), " pair entries for ", n_ad,
+              " adapters x ", n_segs, " segments");
+  check_vec(row_adapter, "row_adapter", x, rows, at::kInt);
+  TORCH_CHECK(rows >= 1 && rows < (1ll << 24) && K < (1ll << 31), "thinkdiff_hip::lora_rows_: x is empty or too large");
+  std::vector<void*> yp; std::vector<int64_t> ld; std::vector<int> wd;
+  for (size_t s = 0; s < n_segs; ++s) {
+    check_rows(ys[s], "ys");
+    TORCH_CHECK(ys[s].dim() == 2 && ys[s].size(0) == rows && ys[s].device() == x.device() && ys[s].size(1) < (1ll << 31), "thinkdiff_hip::lora_rows_: segment ", s, " must be [", rows,
+                ", width] on ", x.device());
+    yp.push_back(ys[s].data_ptr()); ld.push_back(ys[s].stride(0)); wd.push_back((int)ys[s].size(1));
+  }
+  DeviceGuard guard(x.device());
+  std::vector<at::Tensor> packed(A.size());
+  std::vector<const void*> ptrs(std::max<size_t>(1, n_ad * n_segs), nullptr);
+  std::vector<int> ranks(std::max<size_t>(1, n_ad), 1);
+  std::vector<float> sc(std::max<size_t>(1, n_ad), 0.f);
+  int max_rank = 1;
+  for (size_t a = 0; a < n_ad; ++a) {
+    sc[a] = (float)scales[a];
+    for (size_t s = 0; s < n_segs; ++s) {
+      const int64_t i = pair[a * n_segs + s];
+      if (i < 0) continue;
+      TORCH_CHECK((size_t)i < A.size(), "thinkdiff_hip::lora_rows_: pair index ", i, " outside the ", A.size(), " pairs given");
+      const int64_t N = wd[s];
+      TORCH_CHECK(A[i].dim() == 2 && B[i].dim() == 2 && A[i].size(0) >= 1 && A[i].size(0) <= TD_LORA_ROWS_MAX_RANK, "thinkdiff_hip::lora_rows_: pair ", i,
+                  ": A [r, K], B [N, r] with r in 1..", TD_LORA_ROWS_MAX_RANK);
+      const int64_t r = A[i].size(0);
+      TORCH_CHECK(A[i].size(1) == K && B[i].size(0) == N && B[i].size(1) == r, "thinkdiff_hip::lora_rows_: pair ", i, ": A ", A[i].sizes(), " / B ", B[i].sizes(),
+                  " do not fit x ", x.sizes(), " and a segment of width ", N);
+      check_vec(A[i], "A", x, r * K); check_vec(B[i], "B", x, N * r);
+      if (!packed[i].defined()) {
+        packed[i] = at::empty({(int64_t)td_lora_rows_packed_bytes((int)r, (int)N, (int)K)}, x.options().dtype(at::kByte));
+        ok(td_lora_rows_pack_bf16(A[i].data_ptr(), B[i].data_ptr(), (int)r, (int)N, (int)K, packed[i].data_ptr(), stream_of(x)));
+      }
+      ptrs[a * n_segs + s] = packed[i].data_ptr();
+      ranks[a] = (int)r;
+      max_rank = std::max(max_rank, (int)r);
+    }
+  }
+  const size_t wsb = td_lora_rows_workspace_bytes((int)rows, (int)K, (int)n_segs, max_rank);
+  at::Tensor ws = at::empty({(int64_t)std::max<size_t>(16, wsb)}, x.options().dtype(at::kByte));
+  ok(td_lora_rows_bf16(x.data_ptr(), x.stride(0), (int)rows, (int)K, (const int32_t*)row_adapter.data_ptr(), (int)n_ad, ptrs.data(), ranks.data(), sc.data(), (int)n_segs,
+                       yp.data(), ld.data(), wd.data(), ws.data_ptr(), (size_t)ws.numel(), stream_of(x)));
+}
 // attach one pair to a Linear of the engine (td_flux_lora_load): A [r, K], B [N, r] against the [N, K] td_flux_param_shape reports
 void flux_lora_load(int64_t engine, std::string adapter, std::string param, const at::Tensor& A, const at::Tensor& B, double scale) {
   TORCH_CHECK(engine != 0, "thinkdiff_hip: null engine handle");
@@ -1168,6 +1223,7 @@ TORCH_LIBRARY(thinkdiff_hip, m) {
   m.def("flux_denoise_multi_inpaint_(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()");
   m.def("lora_merge(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor");
   m.def("lora_merge_(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)");
+  m.def("lora_rows_(Tensor x, Tensor row_adapter, Tensor[] A, Tensor[] B, int[] pair, float[] scales, Tensor(a!)[] ys) -> ()");
   m.def("redux_compose(Tensor? text, Tensor? image, float[] scales, int text_rows) -> Tensor");
   m.def("image_resize_u8(Tensor img, int out_h, int out_w, int resample, int? out_channels) -> Tensor");
   m.def("ip_attention(Tensor q, Tensor k, Tensor v, int H, Tensor? norm_w, float eps, float out_scale) -> Tensor");
@@ -1235,6 +1291,7 @@ TORCH_LIBRARY_IMPL(thinkdiff_hip, CUDA, m) {
   m.impl("flux_fill_condition", &flux_fill_condition);
   m.impl("lora_merge", &lora_merge);
   m.impl("lora_merge_", &lora_merge_);
+  m.impl("lora_rows_", &lora_rows_);
   m.impl("flux_lora_load", &flux_lora_load);
   m.impl("redux_compose", &redux_compose);
   m.impl("image_resize_u8", &image_resize_u8);

@@ -262,6 +262,13 @@ def _declare(L):
         "td_logit_edits_read": [vp, i32, vp, vp, vp],
         "td_sample_rows_edit_bf16": [vp, vp, vp, vp, i64, i32, i32, vp, vp, i32, vp, vp],
         "td_logprobs_rows_bf16": [vp, i64, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp],
+        "td_lora_rows_pack_bf16": [vp, vp, i32, i32, i32, vp, vp],
+        "td_lora_rows_bf16": [vp, i64, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "td_qwen2_lora_enable": [vp, i32, i32],
+        "td_qwen2_lora_load": [vp, i32, ctypes.c_char_p, vp, vp, i32, f32, vp],
+        "td_qwen2_lora_remove": [vp, i32],
+        "td_qwen2_lora_set_slot": [vp, i32, i32],
+        "td_qwen2_lora_info": [vp, vp, vp, vp, vp],
     }
     for name, args in sig.items():
         if os.environ.get("TD_HIP_LIB") and not hasattr(L, name):
@@ -291,6 +298,11 @@ def _declare(L):
     L.td_flux_param_elems.restype = ctypes.c_int64
     L.td_lora_packed_bytes.argtypes = [i32, i32, i32]
     L.td_lora_packed_bytes.restype = ctypes.c_size_t
+    if hasattr(L, "td_lora_rows_packed_bytes"):
+        L.td_lora_rows_packed_bytes.argtypes = [i32, i32, i32]
+        L.td_lora_rows_packed_bytes.restype = ctypes.c_size_t
+        L.td_lora_rows_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        L.td_lora_rows_workspace_bytes.restype = ctypes.c_size_t
     L.td_attention_fp8_workspace_bytes.argtypes = [i32, i32, i32]
     L.td_attention_fp8_workspace_bytes.restype = ctypes.c_size_t
     return sig
@@ -871,6 +883,56 @@ def kv_gather_rows(planes, slots, copy_src, n_rows):
     nr = (ctypes.c_int * max(1, n))(*[int(v) for v in n_rows])
     check(lib().td_kv_gather_rows(ctypes.cast(arr, ctypes.c_void_p), len(planes), n, ctypes.cast(sl, ctypes.c_void_p), ptr(copy_src),
                                   ctypes.cast(nr, ctypes.c_void_p), stream_ptr()))
+
+
+LORA_ROWS_MAX_ADAPTERS = 8     # TD_LORA_MAX_ADAPTERS
+LORA_ROWS_MAX_SEGS = 3         # TD_LORA_ROWS_MAX_SEGS
+LORA_ROWS_MAX_RANK = 64        # TD_LORA_ROWS_MAX_RANK
+
+
+def lora_rows_pack(A, B):
+    """td_lora_rows_pack_bf16: the kernels' operand form of one (lora_A.weight [r, K], lora_B.weight [N, r]) bf16 pair: Ap [r_pad, K] then Bp [N, r_pad], the
+    rank zero-padded to a multiple of 16.  Returns a uint8 device tensor."""
+    assert A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.dim() == 2 and B.dim() == 2 and A.shape[0] == B.shape[1], (A.shape, B.shape)
+    A, B = A.contiguous(), B.contiguous()
+    r, K = A.shape
+    N = B.shape[0]
+    packed = torch.empty(max(16, lib().td_lora_rows_packed_bytes(int(r), int(N), int(K))), dtype=torch.uint8, device=A.device)
+    check(lib().td_lora_rows_pack_bf16(ptr(A), ptr(B), int(r), int(N), int(K), ptr(packed), stream_ptr()))
+    return packed
+
+
+def lora_rows_workspace_bytes(rows, K, n_segs, max_rank):
+    return int(lib().td_lora_rows_workspace_bytes(int(rows), int(K), int(n_segs), int(max_rank)))
+
+
+def lora_rows(x, row_adapter, packed, ranks, scales, ys, workspace=None):
+    """td_lora_rows_bf16: ys[s][row] += scales[a] * B_as (bf16(A_as x[row])) for a = row_adapter[row] >= 0, in place, one rounding (csrc/lora_rows.hip).
+    x bf16 [rows, K] (row stride free); row_adapter int32 device [rows]; packed[a][s]: lora_rows_pack of adapter a's pair for segment s, or None;
+    ranks / scales: one per adapter; ys: 1 to 3 bf16 [rows, width_s] views (row stride free), the output segments.  Returns ys."""
+    ldx = _rows(x)
+    rows, K = x.shape
+    n_ad, n_segs = len(packed), len(ys)
+    ptrs = (ctypes.c_void_p * max(1, n_ad * n_segs))()
+    for a, per in enumerate(packed):
+        if len(per) != n_segs:
+            raise ThinkDiffHipError(f"lora_rows: adapter {a} gives {len(per)} operands for {n_segs} segments")
+        for s, p in enumerate(per):
+            ptrs[a * n_segs + s] = None if p is None else p.data_ptr()
+    rk = (ctypes.c_int * max(1, n_ad))(*[int(r) for r in ranks])
+    sc = (ctypes.c_float * max(1, n_ad))(*[float(v) for v in scales])
+    yp = (ctypes.c_void_p * n_segs)(*[y.data_ptr() for y in ys])
+    ld = (ctypes.c_int64 * n_segs)(*[_rows(y) for y in ys])
+    wd = (ctypes.c_int * n_segs)(*[int(y.shape[1]) for y in ys])
+    if any(y.shape[0] != rows for y in ys) or row_adapter.numel() != rows or row_adapter.dtype != torch.int32:
+        raise ThinkDiffHipError(f"lora_rows: every output and the int32 row_adapter need {rows} rows")
+    if workspace is None:
+        max_rank = max([int(r) for r, per in zip(ranks, packed) if any(p is not None for p in per)] or [1])
+        workspace = torch.empty(max(16, lora_rows_workspace_bytes(rows, K, n_segs, max_rank)), dtype=torch.uint8, device=x.device)
+    check(lib().td_lora_rows_bf16(ptr(x), ldx, int(rows), int(K), ptr(row_adapter), n_ad, ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(rk, ctypes.c_void_p),
+                                  ctypes.cast(sc, ctypes.c_void_p), n_segs, ctypes.cast(yp, ctypes.c_void_p), ctypes.cast(ld, ctypes.c_void_p),
+                                  ctypes.cast(wd, ctypes.c_void_p), ptr(workspace), workspace.numel(), stream_ptr()))
+    return ys
 
 
 MAX_BEAM_WIDTH = 10        # TD_MAX_BEAM_WIDTH (2 W candidates per row must fit TD_MAX_LOGPROBS)

@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 
 from .base_model import BaseModel
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, lora_engine_kwargs_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
 
 
 @registry.register_model("mllama-vllm-generate-1")
@@ -38,9 +38,11 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
         quantization = Qwen2VLTextEngine.check_quantization(vc.get("quantization"))      # (before the engine allocates anything)
         kv_cache_dtype = Qwen2VLTextEngine.check_kv_cache_dtype(vc.get("kv_cache_dtype", "auto"))      # vLLM's `kv_cache_dtype`: "auto" (bf16) or "fp8" / "fp8_e4m3"
         prefix_caching = Qwen2VLTextEngine.check_prefix_caching(vc.get("enable_prefix_caching", False))      # vLLM's `enable_prefix_caching` (off by default here)
+        lora = lora_engine_kwargs_from_vllm_config(vc)      # vLLM's `enable_lora`, `max_loras`, `max_lora_rank`; "lora_request": one adapter for every request
+        self.mllama_lora_request = lora["lora_request"]
         self.decode_batch = max(1, min(Qwen2VLTextEngine.MAX_BATCH, int(vc.get("max_num_seqs", Qwen2VLTextEngine.MAX_BATCH))))
         self.mllama = Qwen2VLTextEngine(text_config, max_model_len=vc.get("max_model_len", 8192), device=device, n_slots=self.decode_batch,
-                                        kv_cache_dtype=kv_cache_dtype, **({"enable_prefix_caching": True} if prefix_caching else {}),
+                                        kv_cache_dtype=kv_cache_dtype, **({"enable_prefix_caching": True} if prefix_caching else {}), **lora["engine"],
                                         prefill_rows=min(int(vc.get("max_num_batched_tokens", 16384)), 65536) if self.decode_batch > 1 else None)      # (60 000 in the reference config: rows of one packed prefill pass)
         # vLLM's `quantization="fp8"` / `"mxfp4"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
         self.mllama.weight_quantization = quantization
@@ -84,11 +86,11 @@ class MllamaVllmGenerate_1(QwenChatFrontend, BaseModel):
     def _requests(self, samples: dict, idx) -> List[dict]:
         """The requests of one decode chunk; with the chat front end loaded, their images share one vision-tower call."""
         if self.request_builder is not None or self.mllama_processor is None or self.mllama_tokenizer is None:
-            return [self._request(samples, i) for i in idx]
+            return self.with_lora_request([self._request(samples, i) for i in idx])
         texts = samples["answers"] if self.config.text_input_key is None else samples[self.config.text_input_key]
         images = samples.get("images", None)
         idx = list(idx)
-        return self.resolve_requests(self.chat_requests([texts[i] for i in idx], [images[i] if images is not None else None for i in idx]))
+        return self.with_lora_request(self.resolve_requests(self.chat_requests([texts[i] for i in idx], [images[i] if images is not None else None for i in idx])))
 
     @torch.no_grad()
     def forward_inner(self, mllama_inputs: dict, generator=None) -> Dict:

@@ -21,7 +21,7 @@ from .. import _hip
 from ..common.registry import registry
 from .base_model import BaseModel
 from .blip_vision_t5_decoder import HipVisionProjector
-from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
+from .qwen2_vl import QwenChatFrontend, Qwen2VLTextConfig, Qwen2VLTextEngine, SamplingParams, beam_params_from_vllm_config, lora_engine_kwargs_from_vllm_config, sampler_fields_from_vllm_config, speculative_params_from_vllm_config
 
 SYSTEM_PROMPT = "You are a helpful assistant."   # reference :1048
 NUM_SYSTEM_TOKENS = 14                            # reference :1107-1109 ("input_no_system" drops the first 14)
@@ -42,9 +42,11 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         quantization = Qwen2VLTextEngine.check_quantization(vc.get("quantization"))      # (before the engine allocates anything)
         kv_cache_dtype = Qwen2VLTextEngine.check_kv_cache_dtype(vc.get("kv_cache_dtype", "auto"))      # vLLM's `kv_cache_dtype`: "auto" (bf16) or "fp8" / "fp8_e4m3"
         prefix_caching = Qwen2VLTextEngine.check_prefix_caching(vc.get("enable_prefix_caching", False))      # vLLM's `enable_prefix_caching` (off by default here)
+        lora = lora_engine_kwargs_from_vllm_config(vc)      # vLLM's `enable_lora`, `max_loras`, `max_lora_rank`; "lora_request": one adapter for every request
+        self.mllama_lora_request = lora["lora_request"]
         self.decode_batch = max(1, min(Qwen2VLTextEngine.MAX_BATCH, int(vc.get("max_num_seqs", 1))))
         self.mllama = Qwen2VLTextEngine(text_config, max_model_len=vc.get("max_model_len", 8192), device=device, n_slots=self.decode_batch,
-                                        kv_cache_dtype=kv_cache_dtype, **({"enable_prefix_caching": True} if prefix_caching else {}),
+                                        kv_cache_dtype=kv_cache_dtype, **({"enable_prefix_caching": True} if prefix_caching else {}), **lora["engine"],
                                         prefill_rows=min(int(vc.get("max_num_batched_tokens", 16384)), 16384) if self.decode_batch > 1 else None)
         # vLLM's `quantization="fp8"` / `"mxfp4"`: the engine quantises behind every weight load (load_pretrained / load_state_dict / init_random)
         self.mllama.weight_quantization = quantization
@@ -99,7 +101,7 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
         decoded text when a tokenizer is loaded, else the generated token ids as a space-separated string."""
         reqs = self._to_requests(mllama_inputs, need_process)
         sp = self.mllama_sampling_params    # **generate_kwargs (e.g. the drivers' max_new_tokens=128) are accepted and unused, as in the reference (:1019-1118)
-        reqs = self.resolve_requests(reqs)
+        reqs = self.with_lora_request(self.resolve_requests(reqs))
         outs = []
         beam = self.mllama_beam_params
         if beam is not None:
@@ -118,7 +120,8 @@ class MllamaVllmT5EmbedDecoderForConditionalGeneration_5(QwenChatFrontend, BaseM
             for i, r in enumerate(reqs):
                 forced = None if forced_output_ids is None else forced_output_ids[i]
                 outs.append(self.mllama.generate(list(r["prompt_token_ids"]), sp, position_ids=r.get("position_ids"),
-                                                 inputs_embeds=r.get("inputs_embeds"), generator=generator, forced_output_ids=forced, **self._spec_kw))
+                                                 inputs_embeds=r.get("inputs_embeds"), generator=generator, forced_output_ids=forced, lora_request=r.get("lora_request"),
+                                                 **self._spec_kw))
         inp = [o["prompt_hidden_states"] for o in outs]
         out = [o["hidden_states"] for o in outs]
         if embedding_type == "both":

@@ -33,9 +33,12 @@ def _as_bytes(x) -> bytes:
     return x if isinstance(x, (bytes, bytearray)) else str(x).encode("utf-8")
 
 
-def block_hashes(token_ids: Sequence[int], position_ids, inputs_embeds=None, mm_hash=None) -> List[bytes]:
+def block_hashes(token_ids: Sequence[int], position_ids, inputs_embeds=None, mm_hash=None, adapter=None) -> List[bytes]:
     """The chained hashes of the FULL blocks of a prompt (len(token_ids) // 16 of them).  position_ids: [3, n] ints.  inputs_embeds: the request's
-    embedding rows [n, D] or None; mm_hash: their identity (str / bytes) -- without one the rows' bytes are read back to the host and hashed."""
+    embedding rows [n, D] or None; mm_hash: their identity (str / bytes) -- without one the rows' bytes are read back to the host and hashed.
+    adapter: the identity of the request's LoRA adapter (an int id, str or bytes; vLLM hashes the LoRA id into a block's extra keys): it salts the root, so
+    the same prompt under two adapters shares no block -- the cached keys and values came through the adapter's k_proj / v_proj.  None: the hashes of the
+    base model, bit for bit what they were before adapters existed."""
     n = len(token_ids)
     nb = n // BLOCK
     if nb == 0:
@@ -50,7 +53,7 @@ def block_hashes(token_ids: Sequence[int], position_ids, inputs_embeds=None, mm_
             ident = b"mm:" + _as_bytes(mm_hash)
         else:      # one read-back of the rows the full blocks cover
             rows = inputs_embeds[:nb * BLOCK].detach().contiguous().view(torch.int16 if inputs_embeds.element_size() == 2 else torch.int32).cpu().numpy()
-    out, parent = [], hashlib.blake2b(_ROOT, digest_size=16).digest()
+    out, parent = [], hashlib.blake2b(_ROOT if adapter is None else _ROOT + b"/lora:" + _as_bytes(adapter), digest_size=16).digest()
     for j in range(nb):
         a, b = j * BLOCK, (j + 1) * BLOCK
         h = hashlib.blake2b(parent, digest_size=16)

@@ -20,7 +20,10 @@ import torch
 from .. import _hip
 from ..ops import register as _register_ops
 from . import prefix_cache as _pfx
+from . import qwen2_lora as _lora
+from .qwen2_lora import LoRARequest      # noqa: F401  (vLLM's name, importable from here as SamplingParams is)
 _OPS = _register_ops()      # torch.ops.thinkdiff_hip: the custom-op layer over the C ABI (GPU kernels only, no fallback)
+_KEEP = object()            # forward(lora_request=...): leave the slot's adapter as it is
 
 
 def _prefix_entry(fn):
@@ -30,6 +33,17 @@ def _prefix_entry(fn):
 
     @functools.wraps(fn)
     def run(self, *a, **kw):
+        if getattr(self, "_lora", None) is None:
+            return cached(self, *a, **kw)
+        self._lora_depth = getattr(self, "_lora_depth", 0) + 1
+        try:
+            return cached(self, *a, **kw)
+        finally:      # per-request LoRA: when the outermost entry returns or raises, no cache slot names an adapter any more
+            self._lora_depth -= 1
+            if self._lora_depth == 0:
+                self._lora.release_all()
+
+    def cached(self, *a, **kw):
         pc = getattr(self, "_prefix_cache", None)
         if pc is None:
             return fn(self, *a, **kw)
@@ -211,6 +225,14 @@ PARALLEL_CONFIG_KEYS = ("n", "best_of")
 # vllm.SamplingParams keys the engine does not serve: a vllm_config that sets one is refused, never ignored
 UNSERVED_CONFIG_KEYS = {"prompt_logprobs": "prompt_logprobs is not served by the HIP engine (logprobs of generated or forced tokens are: `logprobs`)",
                         "bad_words": "string bad_words need a tokenizer, which the engine does not hold: pass the words as token ids in bad_words_token_ids"}
+
+
+def lora_engine_kwargs_from_vllm_config(vc) -> dict:
+    """vllm_config's enable_lora / max_loras / max_lora_rank as Qwen2VLTextEngine keyword arguments ({} with LoRA off) plus "lora_request" (a LoRARequest or
+    None); the keys vLLM has and the engine does not serve are a ValueError naming the key (thinkdiff/models/qwen2_lora.py)."""
+    f = _lora.lora_fields_from_vllm_config(vc)
+    kw = {"enable_lora": True, "max_loras": f["max_loras"], "max_lora_rank": f["max_lora_rank"]} if f["enable_lora"] else {}
+    return {"engine": kw, "lora_request": f["lora_request"]}
 
 
 def sampler_fields_from_vllm_config(vc) -> dict:
@@ -723,6 +745,7 @@ class _LiveRows:
                 kids = [free_slots.pop() for _ in range(widths[j] - 1)]
                 if kids:
                     self.engine._fork_slots(slots[j], kids, lens[j])
+                    self.engine._lora_inherit(slots[j], kids)
                 seq_slots += [slots[j]] + kids
             self.logits[n:n + used] = self.logits[n:n + k].index_select(0, torch.tensor(rep, dtype=torch.int64).to(self.logits.device))
             slots = seq_slots
@@ -787,6 +810,7 @@ class _LiveRows:
             return []
         keep = np.nonzero(~done)[0]
         freed = sorted((int(x) for x in self.slt[:n][done]), reverse=True)
+        self.engine._lora_release(freed)
         k = keep.size
         for arr in (self.own, self.slt, self.clen, self.npos, self.ngen, self.lim, self.mint, self.stops, self.pend, self.hist):
             arr[:k] = arr[:n][keep]
@@ -910,9 +934,14 @@ class Qwen2VLTextEngine:
         return "auto" if cls.KV_CACHE_DTYPES[value] == _hip.QWEN2_KV_BF16 else "fp8"
 
     def __init__(self, config: Optional[Qwen2VLTextConfig] = None, max_model_len: int = 8192, device="cuda", n_slots: int = 1,
-                 prefill_rows: Optional[int] = None, kv_cache_dtype: Optional[str] = "auto", enable_prefix_caching: bool = False, **kw):
+                 prefill_rows: Optional[int] = None, kv_cache_dtype: Optional[str] = "auto", enable_prefix_caching: bool = False,
+                 enable_lora: bool = False, max_loras: int = 1, max_lora_rank: int = 16, **kw):
         self.kv_cache_dtype = self.check_kv_cache_dtype(kv_cache_dtype)      # (before anything is allocated)
         self.check_prefix_caching(enable_prefix_caching)
+        if not isinstance(enable_lora, bool):
+            raise ValueError(f"enable_lora={enable_lora!r} must be True or False")
+        if enable_lora:
+            _lora.check_pool_size(max_loras, max_lora_rank)
         self.config = config or Qwen2VLTextConfig(**kw)
         c = self.config
         self.device = torch.device(device)
@@ -937,6 +966,107 @@ class Qwen2VLTextEngine:
         self.n_slots, self.slot_len = int(n_slots), max_model_len
         self.max_model_len = max_model_len
         self.set_prefix_caching(enable_prefix_caching)
+        self._lora = None
+        if enable_lora:      # vLLM's enable_lora: the adapter pool and the low-rank kernels' workspace (td_qwen2_lora_enable), once, here
+            with torch.cuda.device(self.device):
+                _hip.check(self._L.td_qwen2_lora_enable(self._h, int(max_loras), int(max_lora_rank)))
+            self._lora = _lora.LoraPool(int(max_loras), int(max_lora_rank), self._lora_dev_load, self._lora_dev_remove, self._lora_dev_set_slot)
+
+    # ---- per-request LoRA (vLLM's enable_lora / LoRARequest; thinkdiff/models/qwen2_lora.py) ------------------------------------------------------
+    def _lora_dev_load(self, place: int, adapter):
+        for (layer, module), (A, B) in adapter.pairs.items():
+            a, b = A.to(self.device), B.to(self.device)
+            _hip.check(self._L.td_qwen2_lora_load(self._h, int(place), f"model.layers.{layer}.{module}".encode(), _hip.ptr(a), _hip.ptr(b), int(adapter.rank),
+                                                  float(adapter.scale), _hip.stream_ptr()))
+
+    def _lora_dev_remove(self, place: int):
+        _hip.check(self._L.td_qwen2_lora_remove(self._h, int(place)))
+
+    def _lora_dev_set_slot(self, slot: int, place: int):
+        _hip.check(self._L.td_qwen2_lora_set_slot(self._h, int(slot), int(place)))
+
+    def _lora_pool(self, what):
+        pool = getattr(self, "_lora", None)
+        if pool is None:
+            raise ValueError(f"{what}: LoRA was requested on an engine created without enable_lora=True")
+        return pool
+
+    def add_lora(self, request_or_name, state_dict=None, config=None) -> bool:
+        """vLLM's `LLM.add_lora`: register an adapter.  request_or_name: a LoRARequest (or a dict of its fields), or a name -- the adapter then gets the next
+        free lora_int_id.  state_dict + config: the adapter in peft's published layout and its adapter_config.json as a dict; without them the adapter is read
+        from the request's lora_path (a peft directory).  Tensors of another float dtype are rounded to bf16 once, here.  It reaches the device at its first
+        use (or now, while the pool has a free place).  Returns True; see thinkdiff/models/qwen2_lora.py for what is refused."""
+        pool = self._lora_pool("add_lora")
+        if isinstance(request_or_name, str):
+            req = LoRARequest(request_or_name, max(list(pool.known) + [0]) + 1)
+        else:
+            req = LoRARequest.of(request_or_name)
+        if req is None:
+            raise ValueError("add_lora: a LoRARequest or a name is required")
+        if state_dict is None:
+            if req.lora_path is None:
+                raise ValueError(f"add_lora: adapter {req.lora_int_id} ('{req.lora_name}') comes with neither a state_dict nor a lora_path")
+            state_dict, config = _lora.load_adapter_dir(req.lora_path)
+        elif config is None:
+            raise ValueError("add_lora: a state_dict needs its config dict (peft's adapter_config.json: r, lora_alpha, ...)")
+        adapter = _lora.parse_adapter(state_dict, config, _lora.module_shapes(self.config), self.config.num_hidden_layers, pool.max_lora_rank)
+        pool.register(req, adapter)
+        if len(pool.resident) < pool.max_loras:
+            pool.place([req.lora_int_id])
+        return True
+
+    def remove_lora(self, lora_int_id: int) -> bool:
+        """vLLM's `LLM.remove_lora`: forget the adapter (device and host).  A later request naming it must bring a lora_path.  -> whether it was known."""
+        return self._lora_pool("remove_lora").forget(int(lora_int_id))
+
+    def list_loras(self) -> List[int]:
+        """vLLM's `LLM.list_loras`: the ids of the registered adapters."""
+        pool = getattr(self, "_lora", None)
+        return [] if pool is None else sorted(pool.known)
+
+    def lora_info(self) -> dict:
+        """max_loras (0: not enabled), resident adapters, bytes the pool and the kernels' workspace hold, low-rank launches enqueued or captured so far
+        (td_qwen2_lora_info), and the pool's loads / evictions."""
+        m, r, b, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        _hip.check(self._L.td_qwen2_lora_info(self._h, ctypes.byref(m), ctypes.byref(r), ctypes.byref(b), ctypes.byref(n)))
+        pool = getattr(self, "_lora", None)
+        return {"max_loras": m.value, "resident": r.value, "bytes": b.value, "launches": n.value, **({} if pool is None else pool.stats)}
+
+    def _lora_req_of(self, request) -> Optional[LoRARequest]:
+        """The adapter a request dict names (key "lora_request": a LoRARequest or a dict of its fields), known to the pool: one that was never added is read
+        from its lora_path now."""
+        req = LoRARequest.of(request.get("lora_request"))
+        if req is None:
+            return None
+        pool = self._lora_pool("lora_request")
+        if req.lora_int_id not in pool.known:
+            if req.lora_path is None:
+                raise ValueError(f"lora_request: adapter {req.lora_int_id} ('{req.lora_name}') is not loaded (add_lora) and names no lora_path")
+            self.add_lora(req)
+        return req
+
+    def _lora_check_call(self, requests):
+        """A call whose requests name more distinct adapters than max_loras is refused before anything runs."""
+        reqs = [self._lora_req_of(r) for r in requests]
+        if any(r is not None for r in reqs):
+            self._lora_pool("lora_request").check_call(reqs)
+
+    def _lora_bind(self, requests, slots):
+        """In front of a prefill: cache slot slots[j] runs under request j's adapter (none: under none), the adapter resident."""
+        reqs = [self._lora_req_of(r) for r in requests]
+        pool = getattr(self, "_lora", None)
+        if pool is not None:
+            pool.bind([int(x) for x in slots], reqs)
+
+    def _lora_inherit(self, src, dst_slots):
+        pool = getattr(self, "_lora", None)
+        if pool is not None:
+            pool.inherit(src, dst_slots)
+
+    def _lora_release(self, slots):
+        pool = getattr(self, "_lora", None)
+        if pool is not None:
+            pool.release(slots)
 
     # ---- automatic prefix caching (vLLM's enable_prefix_caching; thinkdiff/models/prefix_cache.py) ----------------------------------------------
     @staticmethod
@@ -1295,6 +1425,8 @@ class Qwen2VLTextEngine:
         _hip.check(self._L.td_qwen2_set_slots(self._h, int(n_slots)))
         self.n_slots, self.slot_len = int(n_slots), int(self._L.td_qwen2_slot_capacity(self._h))
         self.reset_prefix_cache()      # (the slots' rows moved)
+        if getattr(self, "_lora", None) is not None:
+            self._lora.clear_slots()
         return self
 
     def set_fused_rope(self, on: bool) -> bool:
@@ -1302,9 +1434,12 @@ class Qwen2VLTextEngine:
         previous setting."""
         return bool(self._L.td_qwen2_set_fused_rope(self._h, 1 if on else 0))
 
-    def forward(self, position_ids, token_ids=None, inputs_embeds=None, pos0: int = 0, want_hidden=True, want_logits=False, slot: int = 0):
+    def forward(self, position_ids, token_ids=None, inputs_embeds=None, pos0: int = 0, want_hidden=True, want_logits=False, slot: int = 0, lora_request=_KEEP):
         """position_ids int32 [3,n]; token_ids int32 [n] or inputs_embeds bf16 [n,hidden].  Returns
-        (hidden [n,hidden] | None, logits_last [vocab] | None)."""
+        (hidden [n,hidden] | None, logits_last [vocab] | None).  lora_request: a LoRARequest -- the slot runs under that adapter from here on (this call,
+        decode_batch and verify_batch rows naming the slot) -- or None: under none; not given: as the slot stands."""
+        if lora_request is not _KEEP:
+            self._lora_bind([{"lora_request": lora_request}], [slot])
         pos = position_ids.to(self.device, torch.int32).contiguous()
         n = pos.shape[1]
         tok = None if token_ids is None else token_ids.to(self.device, torch.int32).contiguous()
@@ -1411,9 +1546,10 @@ class Qwen2VLTextEngine:
     @torch.no_grad()
     def generate(self, prompt_token_ids: Sequence[int], sampling: SamplingParams, position_ids=None, inputs_embeds=None,
                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
-                 forced_output_ids: Optional[Sequence[int]] = None, speculative=None):
+                 forced_output_ids: Optional[Sequence[int]] = None, speculative=None, lora_request=None):
         """Returns dict(prompt_hidden_states [n_prompt,D], hidden_states [n_gen,D], token_ids [n_gen]).
         speculative: a SpeculativeConfig or a draft source -- the batch path then runs the one sequence (generate_batch).
+        lora_request: the LoRARequest the sequence runs under (vLLM's `generate(..., lora_request=)`).
 
         Sampling is temperature / top-p on the device.  `forced_output_ids` teacher-forces the continuation
         (the reference samples at T=0.6, so parity of the hidden states is checked on forced ids)."""
@@ -1423,8 +1559,8 @@ class Qwen2VLTextEngine:
         if speculative is not None:
             _draft_source(speculative, "generate")
             _check_speculative("generate", [sampling], forced_output_ids)
-            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds}], sampling,
-                                       eos_token_id=eos_token_id, generator=generator, speculative=speculative)[0]
+            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds,
+                                         "lora_request": lora_request}], sampling, eos_token_id=eos_token_id, generator=generator, speculative=speculative)[0]
         if sampling.width > 1:      # n / best_of: one prefill, k sequences on forked slots -- the batch path runs them
             if forced_output_ids is not None:
                 raise ValueError(f"generate: forced_output_ids with SamplingParams n={sampling.n}, best_of={sampling.best_of}: a teacher-forced "
@@ -1432,12 +1568,14 @@ class Qwen2VLTextEngine:
             if self.n_slots < sampling.width:
                 raise _hip.ThinkDiffHipError(f"generate: SamplingParams n={sampling.n}, best_of={sampling.best_of} needs {sampling.width} cache slots, "
                                              f"n_slots={self.n_slots}; call set_slots first")
-            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds}], sampling,
-                                       eos_token_id=eos_token_id, generator=generator)[0]
+            return self.generate_batch([{"prompt_token_ids": prompt_token_ids, "position_ids": position_ids, "inputs_embeds": inputs_embeds,
+                                         "lora_request": lora_request}], sampling, eos_token_id=eos_token_id, generator=generator)[0]
         n_p = len(prompt_token_ids)
         pos = self.text_position_ids(n_p) if position_ids is None else position_ids
         next_pos = int(pos.max()) + 1      # M-RoPE: generation continues one past the largest prompt position
         tok = torch.tensor(list(prompt_token_ids), dtype=torch.int32)
+        if lora_request is not None or getattr(self, "_lora", None) is not None:
+            self._lora_bind([{"lora_request": lora_request}], [0])
         prompt_hidden, lg = self.forward(pos, tok if inputs_embeds is None else None, inputs_embeds, 0, True, True)
         logits = lg[None]
         out_tok, out_hidden = [], []
@@ -1460,6 +1598,8 @@ class Qwen2VLTextEngine:
         out_ids = torch.cat(out_tok).tolist() if out_tok else []
         res = {"prompt_hidden_states": prompt_hidden, "hidden_states": hs, "token_ids": out_ids}
         src.finish([res])
+        if not getattr(self, "_lora_depth", 0):
+            self._lora_release([0])
         return res
 
     @staticmethod
@@ -1486,8 +1626,9 @@ class Qwen2VLTextEngine:
         """`generate` for up to min(256, n_slots) requests together: each prompt is prefilled into its own cache slot, then
         every decode step advances all unfinished sequences in one pass over the weights (what vLLM's batching gives the
         reference's precompute job).  requests: dicts with "prompt_token_ids" and optional "position_ids" / "inputs_embeds".
-        Returns one generate()-style dict per request, in order."""
+        A request's "lora_request" (a LoRARequest) names the adapter its sequences run under.  Returns one generate()-style dict per request, in order."""
         B, forced = len(requests), forced_output_ids
+        self._lora_check_call(requests)
         sps, by_rows = _sampling_list(sampling, B, "generate_batch")
         if sps is None:
             sps = [sampling] * B
@@ -1556,6 +1697,8 @@ class Qwen2VLTextEngine:
             n_known = len(request_chunks[0])
         else:
             n_known = None      # chunks pulled lazily: a per-request list is checked against each chunk as it arrives
+        if n_known is not None:
+            self._lora_check_call(request_chunks[0])
         sps_req, by_rows = _sampling_list(sampling, n_known, "generate_continuous")
         draft = _draft_source(speculative, "generate_continuous")
         if draft is not None:
@@ -1637,9 +1780,12 @@ class Qwen2VLTextEngine:
                     if budget(i) <= 0:      # nothing to generate: the prompt states only, through the first free slot
                         q = requests[i]
                         e = q.get("inputs_embeds")
+                        slot0 = free_slots[-1]
+                        self._lora_bind([q], [slot0])
                         res[base_of(i)]["prompt_hidden_states"], _ = self.forward(
                             self._positions(q), torch.tensor(list(q["prompt_token_ids"]), dtype=torch.int32) if e is None else None, e, 0, True, False,
-                            slot=free_slots[-1])
+                            slot=slot0)
+                        self._lora_release([slot0])
                         continue
                     new.append(i)
                     rows += len(requests[i]["prompt_token_ids"])
@@ -1667,6 +1813,7 @@ class Qwen2VLTextEngine:
                     emb, pos, lens = self._pack_prompts(qs, poss)
                     hid = torch.empty(rows, self.config.hidden_size, dtype=torch.bfloat16, device=self.device)
                     new_slots = [free_slots.pop() for _ in new]
+                    self._lora_bind(qs, new_slots)
                     self._prefill_packed_slots(k, (ctypes.c_int * k)(*new_slots), emb, pos, (ctypes.c_int * k)(*lens), hid, live.logits[live.n:live.n + k])
                     for i, h in zip(new, torch.split(hid, lens)):
                         res[base_of(i)]["prompt_hidden_states"] = h
@@ -1718,13 +1865,16 @@ class Qwen2VLTextEngine:
         hid = torch.empty(sum(lens), D, dtype=torch.bfloat16, device=self.device)
         lg = torch.empty(B, self.config.vocab_size, dtype=torch.bfloat16, device=self.device) if want_logits else None
         self._pc_wrote(slots)
+        if getattr(self, "_lora", None) is not None or any(r.get("lora_request") is not None for r in requests_rows):
+            self._lora_bind(requests_rows, slots)      # (each dict's "lora_request": the adapter its sequence runs under from here on; none: under none)
         self._prefill_packed_prefix_slots(B, (ctypes.c_int * B)(*[int(s) for s in slots]), emb, pos.to(self.device).contiguous(), (ctypes.c_int * B)(*lens),
                                           (ctypes.c_int * B)(*[int(p) for p in prefix_lens]), hid, lg)
         return list(torch.split(hid, lens)), lg
 
     # ---- prompt prefill under prefix caching ---------------------------------------------------------------------------------------------------
     def _prefix_hashes(self, request, pos):
-        return _pfx.block_hashes(request["prompt_token_ids"], pos, request.get("inputs_embeds"), request.get("mm_hash"))
+        lr = LoRARequest.of(request.get("lora_request"))      # (the same prompt under two adapters shares no block)
+        return _pfx.block_hashes(request["prompt_token_ids"], pos, request.get("inputs_embeds"), request.get("mm_hash"), None if lr is None else lr.lora_int_id)
 
     def _prefill_pass_cached(self, pc, requests, poss, hashes, logits_out):
         """ONE prefill pass over the head of `requests` as the cache plans it (PrefixCache.plan_pass) -> (the prompts' complete hidden states, their cache
@@ -1751,6 +1901,7 @@ class Qwen2VLTextEngine:
             r += k
         hid = torch.empty(sum(new), D, dtype=torch.bfloat16, device=self.device)
         slots = [p.slot for p in plan]
+        self._lora_bind(requests[:t], slots)      # (behind the copies: a destination took its donor's adapter, which is the request's own -- the hashes are salted)
         self._prefill_packed_prefix_slots(t, (ctypes.c_int * t)(*slots), emb, pos.to(self.device).contiguous(), (ctypes.c_int * t)(*new),
                                           (ctypes.c_int * t)(*[p.m for p in plan]), hid, logits_out[:t])
         hidden = []
@@ -1805,6 +1956,7 @@ class Qwen2VLTextEngine:
         dst = (ctypes.c_int * max(1, len(dst_slots)))(*[int(d) for d in dst_slots])
         self._pc_wrote(dst_slots)
         _hip.check(self._L.td_qwen2_fork_slot(self._h, int(src), ctypes.cast(dst, ctypes.c_void_p), len(dst_slots), int(length), _hip.stream_ptr()))
+        self._lora_inherit(src, dst_slots)      # (the device map did the same inside the call)
 
     def gather_slots(self, slots: Sequence[int], copy_src, lengths: Sequence[int]):
         """For every row j with copy_src[j] >= 0 (an int32 DEVICE tensor, read by the kernel: the host never learns it), copy the first lengths[j]
@@ -1847,6 +1999,7 @@ class Qwen2VLTextEngine:
         lens = [len(q["prompt_token_ids"]) for q in requests]
         hidden = [None] * B
         L = (max(lens) + 7) // 8 * 8
+        self._lora_bind(requests, slots)
         if B > 1 and self.packed_prefill and max(lens) <= min(self.slot_len, self.prefill_rows):
             b0 = 0
             while b0 < B:
@@ -1911,6 +2064,7 @@ class Qwen2VLTextEngine:
         R, W, T = len(requests), int(params.beam_width), int(params.max_tokens)
         if R < 1:
             raise ValueError("beam_search: no requests")
+        self._lora_check_call(requests)
         if R * W > self.max_seqs:
             raise _hip.ThinkDiffHipError(f"beam_search: {R} requests x beam_width={W} need {R * W} cache slots, which exceed min({self.MAX_BATCH}, n_slots={self.n_slots}); "
                                          "call set_slots first")
@@ -1941,6 +2095,9 @@ class Qwen2VLTextEngine:
                 raise _hip.ThinkDiffHipError(f"beam_search: the prefix cache has no {N - R} cache slots left for the beams")
             for r in range(R):
                 slots_np[r * W:(r + 1) * W] = [parents[r]] + kids[r * (W - 1):(r + 1) * (W - 1)]
+        # per-request LoRA: the gather cannot know its source rows, so every beam slot of a request is set to the request's adapter once, here
+        if getattr(self, "_lora", None) is not None:
+            self._lora_bind([requests[r] for r in range(R) for _ in range(W)], slots_np)
         # what the loop needs from the host, uploaded before it starts: the rows' M-RoPE positions of every round and the first round's live rows
         first = torch.arange(R, dtype=torch.int64) * W
         logits = torch.zeros(N, V, dtype=torch.bfloat16, device=dev)
@@ -2006,6 +2163,7 @@ class Qwen2VLTextEngine:
         class needs it any more; it stays for callers that want to defragment a handle before re-partitioning it (set_slots)."""
         self._pc_wrote([dst])
         _hip.check(self._L.td_qwen2_move_slot(self._h, int(src), int(dst), int(length), _hip.stream_ptr()))
+        self._lora_inherit(src, [dst])
 
 
 def smart_resize(height: int, width: int, factor: int = 28, min_pixels: int = 4 * 28 * 28, max_pixels: int = 16384 * 28 * 28):
@@ -2064,6 +2222,14 @@ class QwenChatFrontend:
     """What vLLM's Qwen2-VL input pipeline does around the decoder, shared by the two LVLM model mirrors: ChatML request
     building, tokenisation, the vision tower, placeholder expansion / embedding splice and M-RoPE positions.
     Expects on `self`: mllama (Qwen2VLTextEngine), mllama_processor, mllama_tokenizer, image_processor, visual, image_token_id."""
+
+    mllama_lora_request = None      # vllm_config["lora_request"]: the one adapter every request of the model class runs under
+
+    def with_lora_request(self, reqs: Sequence[dict]) -> List[dict]:
+        """The requests under the model's adapter (a request that names one of its own keeps it); with none configured: the requests as they are."""
+        if self.mllama_lora_request is None:
+            return list(reqs)
+        return [r if r.get("lora_request") is not None else dict(r, lora_request=self.mllama_lora_request) for r in reqs]
 
     def chat_requests(self, texts, images) -> List[dict]:
         """(instruction, [image]) pairs -> [{"prompt", "multi_modal_data": {"image": ...}}] exactly as the reference builds

@@ -40,6 +40,8 @@ flux_residual_inject_multi_   the same under FluxMultiControlNetModel: the scale
 block_cache_head / block_cache_tail   diffusers' First Block Cache arithmetic: the first block's residual with the two sums of its
                            `(r - r_prev).abs().mean() / r_prev.abs().mean()` test taken deterministically (no atomics), and the tail difference
 lora_merge / lora_merge_   peft's `weight + scaling * (lora_B @ lora_A)` for up to 8 pairs at once, fp32 accumulation, one rounding
+lora_rows_                 the UNMERGED form (vLLM's `enable_lora` with a LoRARequest per request): every row under an adapter of its own, that adapter's
+                           `scale * lora_B(lora_A(x))` added behind a base Linear's output in place, 1 to 3 output segments per call, one rounding
 flux_lora_load / flux_lora_set_adapters / flux_lora_delete / flux_read_param   diffusers' load_lora_weights / set_adapters / delete_adapters
                            (empty name: unload_lora_weights) on the engine's merged weights, and the effective parameter read back; the last
                            three take no tensor, so they alone are registered for every backend (they only reach the engine handle)
@@ -116,6 +118,7 @@ SCHEMAS = {
     "flux_denoise_multi_inpaint_": "(int[] engines, Tensor(a!)[] latents, float[] sigmas, Tensor[] image_latents, Tensor[] noise, Tensor[] mask, int[] streams) -> ()",
     "lora_merge": "(Tensor w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor",
     "lora_merge_": "(Tensor(a!) w, Tensor[] A, Tensor[] B, float[] scales) -> Tensor(a!)",
+    "lora_rows_": "(Tensor x, Tensor row_adapter, Tensor[] A, Tensor[] B, int[] pair, float[] scales, Tensor(a!)[] ys) -> ()",
     "flux_read_param": "(int engine, str name) -> Tensor",
     "flux_lora_load": "(int engine, str adapter, str param, Tensor A, Tensor B, float scale) -> ()",
     "flux_lora_set_adapters": "(int engine, str[] names, float[] weights) -> ()",
