@@ -18,6 +18,8 @@
 //    (off(row,ch) = 256 row + 16 (ch ^ ((row&3)<<2 | (row>>2)&3))), applied on the DMA source side.
 //  * q/k/v are read in place from the projection output ([S, ld] rows, head h at column h*128):
 //    no head-major re-layout pass exists anywhere on the path.
+//  * the score-bound joint form (pre-scaled q, TdAttnParams::score_bound) has no row maximum to keep on a lane, and runs the same
+//    structure on v_mfma_f32_16x16x32_bf16 (template switch M16; the tile body, its layouts and V's own LDS image: attention_common.h).
 #include "attention_common.h"
 
 // Normalise and store this wave's rows of an item: lane holds O[q][db*32 + (r&3) + 8 (r>>2) + 4 h5].  The int8 form (p.q8; compiled in
@@ -45,7 +47,8 @@ __device__ __forceinline__ void attn_store_item(const TdAttnParams& p, const f32
 // ---------------------------------------------------------------------------------------------
 // KVSEG (with CAUSAL and VARLEN): the packed query segments run over key ranges of their own (TdAttnParams::kv_seg_row0 / kv_seg_lens) -- context
 // attention, prompts continued behind cached prefixes.  Everything it changes sits behind `if constexpr (KVSEG)`.
-template <bool CAUSAL, int NWAVES, bool BIAS = false, bool VARLEN = false, bool PRE = false, bool RS = true, bool FIXED = false, bool KVSEG = false>
+// M16 (with PRE, RS and FIXED, joint attention only): the tile body on the 16x16x32 MFMA (attention_common.h); V's LDS image then has its own XOR.
+template <bool CAUSAL, int NWAVES, bool BIAS = false, bool VARLEN = false, bool PRE = false, bool RS = true, bool FIXED = false, bool KVSEG = false, bool M16 = false>
 __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(const TdAttnParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [K slot 0 | K slot 1 | V slot 0 | V slot 1]
@@ -105,13 +108,14 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(c
   constexpr int GROUPS = KV_TILE / 4;
   constexpr int SG = (GROUPS + NWAVES - 1) / NWAVES;
   const int srow = lane >> 4;
-  unsigned voffK[SG];
+  unsigned voffK[SG], voffV[SG];
 #pragma unroll
   for (int s = 0; s < SG; ++s) {
     const int g = wid + NWAVES * s;
     const int swz = (srow << 2) | (g & 3);
     const int chunk = (lane & 15) ^ swz;
     voffK[s] = (unsigned)(g * 4 + srow) * (unsigned)p.ldkv * 2u + (unsigned)(kvhead * D + chunk * 8) * 2u;
+    voffV[s] = M16 ? (unsigned)(g * 4 + srow) * (unsigned)p.ldkv * 2u + (unsigned)(kvhead * D + attn16_v_src_chunk(g, lane) * 8) * 2u : voffK[s];
   }
   auto stage = [&](int slot, int t) {
     const unsigned tile_off = (unsigned)t * KV_TILE * (unsigned)p.ldkv * 2u;
@@ -120,11 +124,30 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(c
       const int g = wid + NWAVES * s;
       if (GROUPS % NWAVES == 0 || g < GROUPS) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (TD_LDS void*)(smem + slot * TILE_BYTES + g * 1024), 16, voffK[s] + tile_off, 0, 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (TD_LDS void*)(smem + (2 + slot) * TILE_BYTES + g * 1024), 16, voffK[s] + tile_off, 0, 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (TD_LDS void*)(smem + (2 + slot) * TILE_BYTES + g * 1024), 16, voffV[s] + tile_off, 0, 0, 0);
       }
     }
   };
   stage(0, 0);
+
+  if constexpr (M16) {      // the whole item on the 16x16x32 body
+    static_assert(!CAUSAL && !BIAS && !VARLEN && PRE && RS && FIXED, "the 16x16x32 body serves the score-bound joint form only");
+    bf16x8_t qf[2][4];
+    attn16_load_q(qf, rsQ, q0, head, p.ldq, lane);
+    unsigned ka[4], va[8];
+    attn16_lds_addrs((unsigned)(uintptr_t)(TD_LDS char*)smem, lane, ka, va);
+    f32x4_t o[8][2], ls[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) o[dt][0][i] = o[dt][1][i] = 0.f;
+      ls[0][i] = ls[1][i] = 0.f;
+    }
+    attn16_run_tiles(o, ls, qf, ka, va, 0, nt, Skv, lane, stage);
+    const float l[2] = {ls[0][0], ls[1][0]};
+    attn16_store_rows(o, l, Ob + head * D, p.ldo, q0, Sq, lane, (p.ldo & 7) == 0 && !(p.variant & 0x200));
+    return;
+  }
 
   bf16x8_t qf[8];
   {
@@ -257,7 +280,7 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_lean_kernel(c
 // workspace (one per engine context / stream: concurrent launches must not share it) is zeroed when it is created.
 // ---------------------------------------------------------------------------------------------
 
-template <int NWAVES, bool XCD_REMAP, bool PRE = false, bool RS = true, bool FIXED = false>
+template <int NWAVES, bool XCD_REMAP, bool PRE = false, bool RS = true, bool FIXED = false, bool M16 = false>
 __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kernel(const TdAttnParams p, char* __restrict__ ws,
                                                                                   const int n_qblk, const int nt) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -302,6 +325,9 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kerne
     }
   }
 
+  unsigned ka16[4], va16[8];      // M16: the 16x16x32 body's addresses (attention_common.h)
+  if constexpr (M16) attn16_lds_addrs(lds0, lane, ka16, va16);
+
   if ((p.variant & 0x100) && wid >= 4) __builtin_amdgcn_s_setprio(1);   // static priority for the younger half (A/B switch)
   while (it < it_end) {
     // ---- the part of an item this workgroup runs now: KV tiles [kb, ke) of item `item` -------------------------------
@@ -325,13 +351,14 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kerne
     __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc((void*)Kb, 0, kv_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc((void*)Vb, 0, kv_bytes, 0x00020000);
 
-    unsigned voffK[SG];
+    unsigned voffK[SG], voffV[SG];
 #pragma unroll
     for (int s = 0; s < SG; ++s) {
       const int g = wid + NWAVES * s;
       const int swz = (srow << 2) | (g & 3);
       const int chunk = (lane & 15) ^ swz;
       voffK[s] = (unsigned)(g * 4 + srow) * (unsigned)p.ldkv * 2u + (unsigned)(kvhead * D + chunk * 8) * 2u;
+      voffV[s] = M16 ? (unsigned)(g * 4 + srow) * (unsigned)p.ldkv * 2u + (unsigned)(kvhead * D + attn16_v_src_chunk(g, lane) * 8) * 2u : voffK[s];
     }
     auto stage = [&](int slot, int t) {
       const unsigned tile_off = (unsigned)t * KV_TILE * (unsigned)p.ldkv * 2u;
@@ -340,12 +367,37 @@ __global__ __launch_bounds__(NWAVES * 64, 2) void td_attn_fwd_d128_streamk_kerne
         const int g = wid + NWAVES * s;
         if (GROUPS % NWAVES == 0 || g < GROUPS) {
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, (TD_LDS void*)(smem + slot * TILE_BYTES + g * 1024), 16, voffK[s] + tile_off, 0, 0, 0);
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (TD_LDS void*)(smem + (2 + slot) * TILE_BYTES + g * 1024), 16, voffK[s] + tile_off, 0, 0, 0);
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsV, (TD_LDS void*)(smem + (2 + slot) * TILE_BYTES + g * 1024), 16, voffV[s] + tile_off, 0, 0, 0);
         }
       }
     };
     __syncthreads();          // the previous part's last tile is no longer read by any wave
     stage(0, kb);
+
+    if constexpr (M16) {      // this part of the item on the 16x16x32 body
+      static_assert(PRE && RS && FIXED, "the 16x16x32 body serves the score-bound form only");
+      bf16x8_t qf[2][4];
+      attn16_load_q(qf, rsQ, q0, head, p.ldq, lane);
+      f32x4_t o[8][2], ls[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) o[dt][0][i] = o[dt][1][i] = 0.f;
+        ls[0][i] = ls[1][i] = 0.f;
+      }
+      attn16_run_tiles(o, ls, qf, ka16, va16, kb, ke, Skv, lane, stage);
+      float l[2] = {ls[0][0], ls[1][0]};
+      if (kb > 0 || ke < nt) {      // the hand-off state: the 64 accumulator registers in the order n = 8 dt + 4 qb + i, and the two row sums
+        f32x16_t o16[4];
+#pragma unroll
+        for (int n = 0; n < 64; ++n) o16[n >> 4][n & 15] = o[n >> 3][(n >> 2) & 1][n & 3];
+        if (!attn_sk_handoff<true>(o16, l[1], l[0], 1.0f, r, G, kb > 0, ws, ticket_lds, tid, wid)) continue;
+#pragma unroll
+        for (int n = 0; n < 64; ++n) o[n >> 3][(n >> 2) & 1][n & 3] = o16[n >> 4][n & 15];
+      }
+      attn16_store_rows(o, l, p.O + (size_t)batch * p.o_bstride + head * D, p.ldo, q0, p.Sq, lane, (p.ldo & 7) == 0 && !(p.variant & 0x200));
+      continue;
+    }
 
     bf16x8_t qf[8];
     {
@@ -515,6 +567,9 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
   const int n_items = (int)(grid.x * grid.y * grid.z);
   const int cus = device_cus(dev);
   const int nt = (p.Skv + KV_TILE - 1) / KV_TILE;
+  // The score-bound form runs its tile body on the 16x16x32 MFMA (attention_common.h).  Not with the int8 output: that store form is written for the
+  // 32x32 register layout only; variant bit M16_FORCE_32 keeps the 32x32 body for the in-process A/B.
+  const bool m16 = !p.q8 && !(p.variant & M16_FORCE_32);
   int e;
   if (!p.causal && !p.bias && !p.kv_lens && (p.variant & 0xff) != 1 && cus > 0 && n_items > cus && cus < SK_MAX_RANGES && (long long)n_items * nt < (1ll << 31)) {
     char* ws = (char*)p.sk_ws;
@@ -524,13 +579,16 @@ int td_attn_launch(const TdAttnParams& p, hipStream_t stream) {
     constexpr int lds_sk = lds + 16;        // + the ticket word
     const dim3 ranges(cus);
     const int n_qblk = (int)grid.x;
-    if (p.q_prescaled && p.score_bound > 0.f) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+    if (p.q_prescaled && p.score_bound > 0.f && m16) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
+    else if (p.q_prescaled && p.score_bound > 0.f) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
     else if (p.q_prescaled) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
     else if ((p.variant & 0xff) == 2) e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, false>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
     else e = attn_launch<td_attn_fwd_d128_streamk_kernel<NW, true>>(ranges, NW * 64, lds_sk, stream, dev, q, ws, n_qblk, nt);
   } else if (p.bias) {   // separate instantiations: the score-bias loads must not touch the hot no-bias instruction stream
     e = p.causal ? attn_launch<td_attn_fwd_d128_lean_kernel<true, NW, true>>(grid, NW * 64, lds, stream, dev, q)
                  : attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, true>>(grid, NW * 64, lds, stream, dev, q);
+  } else if (p.q_prescaled && p.score_bound > 0.f && m16) {
+    e = attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, false, false, true, true, true, false, true>>(grid, NW * 64, lds, stream, dev, q);
   } else if (p.q_prescaled && p.score_bound > 0.f) {
     e = attn_launch<td_attn_fwd_d128_lean_kernel<false, NW, false, false, true, true, true>>(grid, NW * 64, lds, stream, dev, q);
   } else if (p.q_prescaled) {

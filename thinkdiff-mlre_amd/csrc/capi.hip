@@ -169,7 +169,7 @@ int td_attention_joint_prescaled_bf16(const void* q, int64_t ldq, const void* k,
   TdAttnParams p;
   p.Q = (const bf16_t*)q; p.K = (const bf16_t*)k; p.V = (const bf16_t*)v; p.O = (bf16_t*)o;
   p.batch = 1; p.Sq = S; p.Skv = S; p.Hq = H; p.Hkv = H; p.head_dim = 128;
-  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo; p.scale = 1.0f; p.causal = 0; p.causal_offset = 0; p.variant = g_attn_variant & 0xff;
+  p.ldq = (int)ldq; p.ldkv = (int)ldkv; p.ldo = (int)ldo; p.scale = 1.0f; p.causal = 0; p.causal_offset = 0; p.variant = g_attn_variant & 0x4ff;      // (bit 0x400: the 32x32x16 body, A/B)
   p.q_prescaled = 1; p.score_bound = score_bound;
   return td_attn_launch(p, (hipStream_t)stream);
 }

@@ -195,15 +195,16 @@ int attn(td_flux* f, hipStream_t s, const TdAttnParams& p, const TdQkRopeParams*
   return td_attn_launch(p, s);
 }
 
-// A/B switches of the forward (experiments, and the bit-identity tests).  Tests flip several of them inside one process, so all but TD_ATTN_TUNE
+// A/B switches of the forward (experiments, and the bit-identity tests).  Tests and tools/ab_policy.py flip them inside one process, so all
 // are read per call; a few getenv per forward are noise next to ~600 launches.
 struct Switches {
-  int attn_tune;             // TD_ATTN_TUNE: variant bits of the attention kernel, read once
+  int attn_tune;             // TD_ATTN_TUNE: variant bits of the attention kernel (0x400: the score-bound form on its 32x32x16 body)
   bool attn8_no_fuse;        // TD_ATTN8_NO_FUSE: the 8-bit attention takes q / k from td_qk_norm_rope instead of its own pack pass
   bool attn8_no_href;        // TD_ATTN8_NO_HREF: no history reference points
   bool attn_no_bound;        // TD_ATTN_NO_BOUND: the running-maximum form of the bf16 attention
   static Switches read() {
-    static const int tune = getenv("TD_ATTN_TUNE") ? (int)strtol(getenv("TD_ATTN_TUNE"), nullptr, 0) & ~0xff : 0;
+    const char* const at = getenv("TD_ATTN_TUNE");
+    const int tune = at ? (int)strtol(at, nullptr, 0) & ~0xff : 0;
     return {tune, getenv("TD_ATTN8_NO_FUSE") != nullptr, getenv("TD_ATTN8_NO_HREF") != nullptr, getenv("TD_ATTN_NO_BOUND") != nullptr};
   }
 };

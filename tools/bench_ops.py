@@ -365,6 +365,36 @@ def bench_attn():
         print(f"attn S={S} H={H}: " + "   ".join(f"{names[v]} {best[v]*1e3:6.1f} us {fl/best[v]/1e9:6.0f} TF/s" for v in names), flush=True)
 
 
+def bench_attn_m16():
+    """The score-bound joint attention (td_attention_joint_prescaled_bf16, the form the FLUX engine runs): its 16x16x32 MFMA body against the 32x32x16
+    body (variant bit 0x400), persistent form and one workgroup per item (variant 1), arms alternated in one process on cold random inputs (pool
+    cycling; q and k uniform in +-0.25 so that the bound of 8 octaves holds).  Median and minimum per arm over the alternations."""
+    import statistics
+    arms = {"streamk m32": 0x400, "streamk m16": 0, "per-item m32": 0x401, "per-item m16": 1}
+    S, H = 4289, 24
+    W = H * 128
+    pool = []
+    for _ in range(6):
+        t = torch.randn(S, 3 * W, device="cuda")
+        t[:, :2 * W] = torch.rand(S, 2 * W, device="cuda") * 0.5 - 0.25
+        pool.append(t.bfloat16())
+    out = torch.empty(S, W, device="cuda", dtype=torch.bfloat16)
+    st = {"i": 0}
+    def f():
+        st["i"] = (st["i"] + 1) % len(pool)
+        q = pool[st["i"]]
+        _hip.attention_joint_prescaled(q[:, :W], q[:, W:2 * W], q[:, 2 * W:], out, H, 8.0)
+    res = {a: [] for a in arms}
+    for _ in range(9):
+        for a, var in arms.items():
+            _hip.lib().td_attention_set_variant(var)
+            res[a].append(timeit(f, iters=10, warmup=2))
+    _hip.lib().td_attention_set_variant(0)
+    fl = 4.0 * S * S * H * 128
+    for a, v in res.items():
+        print(f"attn_m16 S={S} H={H} {a}: median {statistics.median(v)*1e3:6.1f} us min {min(v)*1e3:6.1f} us max {max(v)*1e3:6.1f} us  {fl/min(v)/1e9:6.0f} TF/s", flush=True)
+
+
 def bench_attn8():
     """The 8-bit joint attention (pack + attention kernels together) against the shipped bf16 kernel, interleaved, cold inputs."""
     for S, H in [(4289, 24), (4354, 24)]:
