@@ -198,6 +198,22 @@ int td_qk_norm_rope_bf16(void* qkv, int64_t ld, int rows, int Hq, int Hk, int q_
                          const float* cos, const float* sin, int split, const void* wqA, const void* wkA,
                          const void* wqB, const void* wkB, float eps, int rotate_half, void* stream);
 
+/* td_qk_norm_rope_bf16 with the factor the FLUX engine folds into q (td_abi_version() >= 25): q, not k, is multiplied by q_premul in fp32 behind the
+ * rotation and in front of its one rounding to bf16 -- the engine passes attention scale * log2(e), so that the attention kernel needs no per-score
+ * multiply.  q_premul = 1 gives td_qk_norm_rope_bf16's bits. */
+int td_qk_norm_rope_premul_bf16(void* qkv, int64_t ld, int rows, int Hq, int Hk, int q_col, int k_col,
+                                const float* cos, const float* sin, int split, const void* wqA, const void* wkA,
+                                const void* wqB, const void* wkB, float eps, int rotate_half, float q_premul, void* stream);
+/* The FLUX engine's conditioning vector (td_abi_version() >= 25; [ext] diffusers CombinedTimestepGuidanceTextProjEmbeddings.forward, then the nn.SiLU
+ * in front of every AdaLayerNorm*'s Linear):  temb[r, c] = bf16(bf16(te[r, c] + ge[c]) + pe[c]);  silu_out[r, c] = bf16(silu(temb[r, c])).
+ * te, temb, silu_out bf16 [n, D] contiguous; ge, pe bf16 [D].  ge NULL: temb = bf16(te + pe) (no guidance embedding).  temb NULL: only silu_out is
+ * written.  te, pe or silu_out NULL, n <= 0 or D <= 0: TD_ERR_INVALID, nothing launched. */
+int td_temb_combine_silu_bf16(const void* te, const void* ge, const void* pe, int n, int D, void* temb, void* silu_out, void* stream);
+/* dst[r, 0 .. cols) = src[r, 0 .. cols) between two bf16 matrices of row strides lds, ldd (td_abi_version() >= 25; the channel-conditioned engine's
+ * gather of the latents into cat(latents, cond)).  cols, lds, ldd multiples of 8, cols <= lds and cols <= ldd, both pointers 16-byte aligned; columns
+ * of dst beyond cols are untouched.  Anything else: TD_ERR_INVALID, nothing launched. */
+int td_copy_cols_bf16(const void* src, int64_t lds, void* dst, int64_t ldd, int rows, int cols, void* stream);
+
 /* FluxPosEmbed tables: ids fp32 [S,3] -> cos,sin fp32 [S,128]. */
 int td_flux_rope_table(const float* ids, int S, const int* axes_dims3, double theta, float* cos, float* sin, void* stream);
 /* Timesteps(256) sinusoid: t fp32 [n] (device) -> bf16 [n,256] = [cos | sin]. */
@@ -311,6 +327,10 @@ int td_flux_pack_latents(const void* src, void* dst, int C, int H, int W, int un
 int td_cls_avgpool2_bf16(const void* x, void* y, int G, int C, void* stream);
 /* counter-based N(mean,std) fill (synthetic checkpoints for throughput runs). */
 int td_fill_normal_bf16(void* dst, int64_t n, uint64_t seed, float std, float mean, void* stream);
+/* ... of a piece of a larger buffer (td_abi_version() >= 25): element i of dst draws what element 2 * pair0 + i of td_fill_normal_bf16 with the same seed
+ * draws.  Elements come in pairs: pair p = splitmix64(seed + 0x9E3779B97F4A7C15 * (p + 1)) gives u1 from its top 24 bits and u2 from the next 24, and
+ * Box-Muller in fp32 gives elements 2p (cosine) and 2p + 1 (sine).  pair0 < 0: TD_ERR_INVALID, nothing launched. */
+int td_fill_normal_from_bf16(void* dst, int64_t n, uint64_t seed, float std, float mean, int64_t pair0, void* stream);
 
 /* ThinkDiff aligner `mm_projector` of type "mlp2x_gelu_t5_norm" (every shipped config):
  *   y = T5LayerNorm(Linear2(GELU_erf(Linear0(x))))        x:[M,K] -> y:[M,hidden]

@@ -87,6 +87,40 @@ def test_oversize_element_counts_are_refused_not_truncated():
         assert b"2^32" in msg or b"32-bit index" in msg, (what, msg)
 
 
+def test_flux_row_kernel_entries_refuse_bad_arguments_without_a_gpu():
+    """td_abi_version() >= 25: td_qk_norm_rope_premul_bf16, td_temb_combine_silu_bf16, td_copy_cols_bf16 and td_fill_normal_from_bf16 (the FLUX
+    step's row kernels, launched alone by tests/test_flux_row*_gpu.py) are declared by the Python binding and refuse bad arguments with
+    TD_ERR_INVALID before any HIP call; so does td_norm_rows_bf16 for a D without an instantiation."""
+    import importlib
+    hip = importlib.import_module("thinkdiff._hip")
+    lib = hip.lib()
+    assert lib.td_abi_version() >= 25
+    one = ctypes.c_void_p(256)                          # 16-byte aligned, never dereferenced
+    odd = ctypes.c_void_p(264)                          # 8-byte aligned only
+    cases = {
+        "rotate_half=3": (b"rotation mode", lambda: lib.td_qk_norm_rope_premul_bf16(one, 512, 2, 1, 1, 0, 128, one, one, 0, None, None, None, None, 1e-6, 3, 1.0, None)),
+        "ld % 8": (b"16-byte", lambda: lib.td_qk_norm_rope_premul_bf16(one, 516, 2, 1, 1, 0, 128, one, one, 0, None, None, None, None, 1e-6, 0, 0.1275, None)),
+        "te null": (b"required", lambda: lib.td_temb_combine_silu_bf16(None, None, one, 1, 8, None, one, None)),
+        "silu_out null": (b"required", lambda: lib.td_temb_combine_silu_bf16(one, one, one, 1, 8, one, None, None)),
+        "n = 0": (b"empty", lambda: lib.td_temb_combine_silu_bf16(one, None, one, 0, 8, None, one, None)),
+        "n * D beyond int32": (b"32-bit index", lambda: lib.td_temb_combine_silu_bf16(one, None, one, 2 ** 20, 2 ** 11, None, one, None)),
+        "cols % 8": (b"multiples of 8", lambda: lib.td_copy_cols_bf16(one, 64, one, 64, 4, 12, None)),
+        "cols > ldd": (b"within both", lambda: lib.td_copy_cols_bf16(one, 64, one, 32, 4, 40, None)),
+        "src misaligned": (b"16-byte aligned", lambda: lib.td_copy_cols_bf16(odd, 64, one, 64, 4, 8, None)),
+        "ldd beyond int32": (b"32-bit range", lambda: lib.td_copy_cols_bf16(one, 64, one, 2 ** 31 + 64, 4, 8, None)),
+        "pair0 < 0": (b"pair0", lambda: lib.td_fill_normal_from_bf16(one, 8, 1, 1.0, 0.0, -1, None)),
+        "fill n = 0": (b"empty", lambda: lib.td_fill_normal_from_bf16(one, 0, 1, 1.0, 0.0, 0, None)),
+        "norm D=520": (b"multiple of 512", lambda: lib.td_norm_rows_bf16(one, 520, one, 520, 4, 520, 0, 1e-6, None, 0, None, None, None, None, None)),
+        "norm D=4608": (b"multiple of 512", lambda: lib.td_norm_rows_bf16(one, 4608, one, 4608, 4, 4608, 0, 1e-6, None, 0, None, None, None, None, None)),
+        "norm ld % 8": (b"multiples of 8", lambda: lib.td_norm_rows_bf16(one, 516, one, 512, 4, 512, 0, 1e-6, None, 0, None, None, None, None, None)),
+        "norm scale without shift": (b"come together", lambda: lib.td_norm_rows_bf16(one, 512, one, 512, 4, 512, 0, 1e-6, None, 0, None, one, None, None, None)),
+    }
+    for what, (needle, call) in cases.items():
+        rc = call()
+        msg = lib.td_last_error()
+        assert rc == 2 and needle in msg, (what, rc, msg)
+
+
 def test_unknown_activation_codes_are_refused_without_a_gpu():
     """Activation codes outside 0 .. 4 (TD_ACT_NONE .. TD_ACT_QUICK_GELU) are an argument error on every entry that takes one -- the
     tile GEMM and the skinny-M weight stream (both behind td_gemm_launch) and td_glu_mul -- before any HIP call."""

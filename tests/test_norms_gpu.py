@@ -16,43 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 
-def _ulp(r):
-    a = r.abs().clamp_min(2.0 ** -126)
-    return torch.exp2(torch.floor(torch.log2(a)) - 7)
-
-
-def _ref(x, w, b, eps, rms):
-    """float64 reference and its per-element tolerance."""
-    x = x.double()
-    D = x.shape[1]
-    wd = w.double() if w is not None else torch.ones(D, dtype=torch.float64)
-    if rms:
-        rstd = 1.0 / torch.sqrt((x * x).mean(dim=1, keepdim=True) + eps)
-        t = (x * rstd).bfloat16().double()
-        y = (t * wd).bfloat16().double() if w is not None else t
-        tol = _ulp(y) + (wd.abs() * _ulp(t) if w is not None else 0.0)
-        return y, tol
-    mean = x.mean(dim=1, keepdim=True)
-    var = ((x - mean) ** 2).mean(dim=1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(var + eps)
-    y = (x - mean) * rstd * wd
-    if b is not None:
-        y = y + b.double()
-    y = y.bfloat16().double()
-    return y, _ulp(y) + (D / 64 + 8) * 2.0 ** -24 * x.abs().mean(dim=1, keepdim=True) * rstd * wd.abs()
-
-
-def _check(got, ref, tol, what):
-    got = got.double().cpu()
-    assert torch.isfinite(got).all(), what
-    err = (got - ref).abs()
-    bad = err > tol
-    print(f"{what}: max error {float((err / tol).max()):.3f} x the bound")
-    if bad.any():
-        i = int(torch.argmax(err / tol))
-        r, c = divmod(i, ref.shape[1])
-        raise AssertionError(f"{what}: {int(bad.sum())} / {bad.numel()} elements beyond the bound; worst row {r} col {c}: got "
-                             f"{float(got[r, c]):.6g} ref {float(ref[r, c]):.6g} ({float(err[r, c] / tol[r, c]):.3g} x the bound)")
+from flux_rowops_common import _check, _ref, _ulp  # noqa: F401  (the float64 reference, ulp and check, shared with the FLUX row-kernel tests)
 
 
 @pytest.mark.parametrize("D", [8, 520, 768, 1024, 1280, 1408, 4096])

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 24; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 25; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -51,6 +51,8 @@ int td_abi_version(void) { return 24; }  // 2: TdFluxConfig::out_channels append
                                             //     td_qwen2_prefill_packed_prefix_slots: the packed prefill behind cached prefixes)
                                             // 24: per-request LoRA (td_lora_rows_bf16, td_lora_rows_pack_bf16: the row-indexed low-rank add,
                                             //     csrc/lora_rows.hip; td_qwen2_lora_*: the adapter pool of the Qwen2-VL decode engine)
+                                            // 25: the FLUX step's row kernels alone (td_qk_norm_rope_premul_bf16, td_temb_combine_silu_bf16,
+                                            //     td_copy_cols_bf16, td_fill_normal_from_bf16: test entries of launches only the engines made)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -281,6 +283,34 @@ int td_qk_norm_rope_bf16(void* qkv, int64_t ld, int rows, int Hq, int Hk, int q_
   p.wqA = (const bf16_t*)wqA; p.wkA = (const bf16_t*)wkA; p.wqB = (const bf16_t*)wqB; p.wkB = (const bf16_t*)wkB;
   p.eps = eps; p.rotate_half = rotate_half;
   return td_qk_norm_rope_launch(p, (hipStream_t)stream);
+}
+
+// td_qk_norm_rope_bf16 with the factor the FLUX engine folds into q (TdQkRopeParams::q_premul), filled as the engine fills it
+int td_qk_norm_rope_premul_bf16(void* qkv, int64_t ld, int rows, int Hq, int Hk, int q_col, int k_col,
+                                const float* cos, const float* sin, int split, const void* wqA, const void* wkA,
+                                const void* wqB, const void* wkB, float eps, int rotate_half, float q_premul, void* stream) {
+  TdQkRopeParams p;
+  p.qkv = (bf16_t*)qkv; p.ld = (int)ld; p.rows = rows; p.Hq = Hq; p.Hk = Hk; p.q_col = q_col; p.k_col = k_col;
+  p.cos = cos; p.sin = sin; p.split = split;
+  p.wqA = (const bf16_t*)wqA; p.wkA = (const bf16_t*)wkA; p.wqB = (const bf16_t*)wqB; p.wkB = (const bf16_t*)wkB;
+  p.eps = eps; p.rotate_half = rotate_half;
+  p.q_premul = q_premul;
+  return td_qk_norm_rope_launch(p, (hipStream_t)stream);
+}
+
+int td_temb_combine_silu_bf16(const void* te, const void* ge, const void* pe, int n, int D, void* temb, void* silu_out, void* stream) {
+  TD_CHECK_ARG(te && pe && silu_out, "td_temb_combine_silu: te, pe and silu_out are required (ge and temb may be null)");
+  return td_temb_combine_silu_launch((const bf16_t*)te, (const bf16_t*)ge, (const bf16_t*)pe, n, D, (bf16_t*)temb, (bf16_t*)silu_out, (hipStream_t)stream);
+}
+
+int td_copy_cols_bf16(const void* src, int64_t lds, void* dst, int64_t ldd, int rows, int cols, void* stream) {
+  TD_CHECK_ARG(lds >= 0 && lds < (1ll << 31) && ldd >= 0 && ldd < (1ll << 31), "td_copy_cols: lds=%lld / ldd=%lld outside the 32-bit range", (long long)lds, (long long)ldd);
+  return td_copy_cols_launch((const bf16_t*)src, (int)lds, (bf16_t*)dst, (int)ldd, rows, cols, (hipStream_t)stream);
+}
+
+int td_fill_normal_from_bf16(void* dst, int64_t n, uint64_t seed, float std, float mean, int64_t pair0, void* stream) {
+  TD_CHECK_ARG(pair0 >= 0, "td_fill_normal_from: pair0=%lld must not be negative", (long long)pair0);
+  return td_fill_normal_from_launch((bf16_t*)dst, (long long)n, (unsigned long long)seed, std, mean, (long long)pair0, (hipStream_t)stream);
 }
 
 int td_flux_rope_table(const float* ids, int S, const int* axes_dims3, double theta, float* cos, float* sin, void* stream) {

@@ -49,6 +49,9 @@ def _declare(L):
         "td_linear_drain_bf16": [vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, i32, i32, i32, vp],
         "td_norm_rows_bf16": [vp, i64, vp, i64, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp],
         "td_qk_norm_rope_bf16": [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, i32, vp],
+        "td_qk_norm_rope_premul_bf16": [vp, i64, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, f32, i32, f32, vp],
+        "td_temb_combine_silu_bf16": [vp, vp, vp, i32, i32, vp, vp, vp],
+        "td_copy_cols_bf16": [vp, i64, vp, i64, i32, i32, vp],
         "td_flux_rope_table": [vp, i32, vp, ctypes.c_double, vp, vp, vp],
         "td_timestep_sincos": [vp, i32, vp, vp],
         "td_euler_step_bf16": [vp, vp, f32, i64, vp],
@@ -78,6 +81,7 @@ def _declare(L):
         "td_flux_pack_latents": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
         "td_cls_avgpool2_bf16": [vp, vp, i32, i32, vp],
         "td_fill_normal_bf16": [vp, i64, ctypes.c_uint64, f32, f32, vp],
+        "td_fill_normal_from_bf16": [vp, i64, ctypes.c_uint64, f32, f32, i64, vp],
         "td_aligner_mlp2x_bf16": [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, f32, i32, vp, vp, i64, vp],
         "td_flux_create": [vp, i32, i32, i32, vp],
         "td_flux_num_params": [vp],
@@ -697,6 +701,35 @@ def qk_norm_rope(qkv, Hq, Hk, q_col, k_col, cos, sin, split=0, wqA=None, wkA=Non
     return qkv
 
 
+def qk_norm_rope_premul(qkv, Hq, Hk, q_col, k_col, cos, sin, split=0, wqA=None, wkA=None, wqB=None, wkB=None, eps=1e-6,
+                        rotate_half=False, q_premul=1.0):
+    """td_qk_norm_rope_premul_bf16: qk_norm_rope with q (not k) multiplied by q_premul in front of its one bf16 rounding, as the FLUX engine runs it."""
+    assert cos.dtype == torch.float32 and cos.shape == (qkv.shape[0], 128) and cos.is_contiguous() and sin.is_contiguous()
+    check(lib().td_qk_norm_rope_premul_bf16(ptr(qkv), _rows(qkv), qkv.shape[0], Hq, Hk, q_col, k_col, ptr(cos), ptr(sin), split,
+                                            ptr(wqA), ptr(wkA), ptr(wqB if wqB is not None else wqA),
+                                            ptr(wkB if wkB is not None else wkA), float(eps), int(rotate_half), float(q_premul), stream_ptr()))
+    return qkv
+
+
+def temb_combine_silu(te, ge, pe, want_temb=True):
+    """td_temb_combine_silu_bf16: te bf16 [n, D], ge bf16 [D] or None, pe bf16 [D] -> (temb or None, silu(temb)), both bf16 [n, D]."""
+    assert te.dim() == 2 and te.is_contiguous() and te.dtype == torch.bfloat16
+    n, D = te.shape
+    for t in (ge, pe):
+        assert t is None or (t.dtype == torch.bfloat16 and t.shape == (D,) and t.is_contiguous())
+    temb = torch.empty_like(te) if want_temb else None
+    silu_out = torch.empty_like(te)
+    check(lib().td_temb_combine_silu_bf16(ptr(te), ptr(ge), ptr(pe), n, D, ptr(temb), ptr(silu_out), stream_ptr()))
+    return temb, silu_out
+
+
+def copy_cols(src, dst, cols):
+    """td_copy_cols_bf16: dst[:, :cols] = src[:, :cols] for two bf16 matrices of the same row count (row strides may exceed the widths)."""
+    assert src.shape[0] == dst.shape[0]
+    check(lib().td_copy_cols_bf16(ptr(src), _rows(src), ptr(dst), _rows(dst), src.shape[0], cols, stream_ptr()))
+    return dst
+
+
 def flux_rope_table(ids, axes_dims=(16, 56, 56), theta=10000.0):
     assert ids.dtype == torch.float32 and ids.is_contiguous() and ids.shape[1] == 3
     S = ids.shape[0]
@@ -770,6 +803,13 @@ def cls_avgpool2(x):
 def fill_normal(t, seed, std=1.0, mean=0.0):
     assert t.is_contiguous() and t.dtype == torch.bfloat16
     check(lib().td_fill_normal_bf16(ptr(t), t.numel(), seed, float(std), float(mean), stream_ptr()))
+    return t
+
+
+def fill_normal_from(t, seed, pair0, std=1.0, mean=0.0):
+    """td_fill_normal_from_bf16: t is a piece of a larger buffer; element i draws what element 2 * pair0 + i of fill_normal with this seed draws."""
+    assert t.is_contiguous() and t.dtype == torch.bfloat16
+    check(lib().td_fill_normal_from_bf16(ptr(t), t.numel(), seed, float(std), float(mean), int(pair0), stream_ptr()))
     return t
 
 
