@@ -102,6 +102,15 @@ int td_conv3x3_nhwc_bf16(const void* x, const void* w, const void* bias, const v
                          int H, int W, int Cin, int Cout, int upsample2x, void* stream);
 /* [Cout, Cin, 3, 3] (torch) -> [Cout_pad, 9*Cin_pad] (k = tap*Cin_pad + c), zero filled padding. */
 int td_conv3x3_pack_weight(const void* w_oihw, void* w_packed, int Cout, int Cin, int Cout_pad, int Cin_pad, void* stream);
+/* The two launches at the ends of td_vae_decode, alone (td_abi_version() >= 26; test entries: the engine runs the same kernels on its own buffers).
+ * td_vae_latents_to_nhwc_bf16: packed FLUX latents [(h/2)(w/2), 4C] bf16 -> NHWC [h*w, Cpad] bf16, the statement
+ * `(unpack_latents(packed) / scaling_factor) + shift_factor` on bf16 tensors ([ext] diffusers pipeline_flux.py): the quotient by the fp32 divisor
+ * rounds to bf16, then the sum with bf16(shift_factor) rounds; channels C .. Cpad-1 are zero.  h, w even, Cpad >= C, no null pointer.
+ * td_vae_image_finalize: x [P, Cpad] bf16 NHWC, its first three channels -> image_u8 [P, 3] = round(clamp(x / 2 + 0.5, 0, 1) * 255) with the
+ * quotient, the sum and the clamp in bf16 and the product in fp32 ([ext] diffusers VaeImageProcessor.postprocess), and / or image_chw [3, P] bf16,
+ * the same bits transposed.  Either output may be NULL, not both; Cpad >= 3; channels >= 3 of x are never read. */
+int td_vae_latents_to_nhwc_bf16(const void* packed, void* out, int C, int h, int w, int Cpad, float scaling_factor, float shift_factor, void* stream);
+int td_vae_image_finalize(const void* x, int P, int Cpad, void* image_u8, void* image_chw, void* stream);
 /* y[M,N] (fp32) = x[M,K] . w[N,K]^T (+ bias): unrounded rows, e.g. attention scores. */
 int td_linear_f32out_bf16(const void* x, int64_t ldx, const void* w, const void* bias, float* y, int64_t ldy,
                           int M, int N, int K, void* stream);

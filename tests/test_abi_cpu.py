@@ -61,6 +61,11 @@ def test_round3_entry_points_refuse_bad_arguments_without_a_gpu():
     assert lib.td_attention_fp8_workspace_bytes(0, 64, 24) == 0 and lib.td_attention_fp8_workspace_bytes(4289, 4289, 24) > 3 * 4289 * 24 * 128
     assert lib.td_flux_prepared_shape(None, None, None, None, None) == 2
     assert lib.td_vae_output_shape(None, 8, 8, None, None, None) == 2
+    # the decoder's boundary kernels alone: null pointers are refused by the entry, shapes by the launcher behind it
+    assert lib.td_vae_latents_to_nhwc_bf16(one, None, 16, 4, 4, 64, f32(0.3611), f32(0.1159), None) == 2 and b"null" in lib.td_last_error()
+    assert lib.td_vae_latents_to_nhwc_bf16(one, one, 16, 4, 3, 64, f32(0.3611), f32(0.1159), None) == 2 and b"bad shape" in lib.td_last_error()
+    assert lib.td_vae_image_finalize(None, 16, 8, one, one, None) == 2 and b"null input" in lib.td_last_error()
+    assert lib.td_vae_image_finalize(one, 16, 8, None, None, None) == 2 and b"no output" in lib.td_last_error()
 
 
 def test_oversize_element_counts_are_refused_not_truncated():

@@ -46,6 +46,7 @@ def _close(got, ref, tol):
 @pytest.mark.parametrize("H,W,Cin,Cout,up,res", [(16, 16, 64, 64, False, False), (24, 40, 128, 256, False, True),
                                                  (32, 32, 64, 128, True, False), (18, 22, 64, 8, False, False)])
 def test_conv3x3_implicit_gemm(hip, H, W, Cin, Cout, up, res):
+    """One number against the output scale; the per-element bounds and the edge shapes are in tests/test_vae_conv_fp64_gpu.py."""
     g = torch.Generator().manual_seed(H * W + Cin)
     Hin, Win = (H // 2, W // 2) if up else (H, W)
     x = torch.randn(1, Cin, Hin, Win, generator=g).bfloat16()

@@ -17,7 +17,7 @@ void td_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* td_last_error(void) { return g_err; }
-int td_abi_version(void) { return 25; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
+int td_abi_version(void) { return 26; }  // 2: TdFluxConfig::out_channels appended (channel-conditioned FLUX); 3: LoRA adapters, td_flux_read_param;
                                             // 4: FLUX ControlNet (td_flux_controlnet_*, td_flux_attach_controlnet, td_flux_residual_inject_bf16)
                                             // 5: FLUX IP-Adapter (td_ip_attention_bf16, td_flux_ip_adapter_*, td_flux_set_ip_image_embeds)
                                             // 6: first-block cache (td_block_cache_*_bf16, td_flux_set_block_cache*, td_flux_block_cache_*)
@@ -53,6 +53,8 @@ int td_abi_version(void) { return 25; }  // 2: TdFluxConfig::out_channels append
                                             //     csrc/lora_rows.hip; td_qwen2_lora_*: the adapter pool of the Qwen2-VL decode engine)
                                             // 25: the FLUX step's row kernels alone (td_qk_norm_rope_premul_bf16, td_temb_combine_silu_bf16,
                                             //     td_copy_cols_bf16, td_fill_normal_from_bf16: test entries of launches only the engines made)
+                                            // 26: the VAE decoder's boundary kernels alone (td_vae_latents_to_nhwc_bf16, td_vae_image_finalize: test
+                                            //     entries of the two launches only td_vae_decode made)
 
 int td_linear_bf16(const void* x, int64_t ldx, const void* w, const void* bias, void* y, int64_t ldy,
                    int M, int N, int K, int act, const void* gate, const void* res, int64_t ldr,
@@ -408,6 +410,17 @@ int td_mrope_table(const int* pos3n, int n, const int* sections3, float theta, i
 
 int td_conv3x3_pack_weight(const void* w_oihw, void* w_packed, int Cout, int Cin, int Cout_pad, int Cin_pad, void* stream) {
   return td_conv_pack_launch((const bf16_t*)w_oihw, (bf16_t*)w_packed, Cout, Cin, Cout_pad, Cin_pad, (hipStream_t)stream);
+}
+// the two launches at the ends of td_vae_decode, alone (the engine calls the launchers with its own buffers: the null checks live here)
+int td_vae_latents_to_nhwc_bf16(const void* packed, void* out, int C, int h, int w, int Cpad, float scaling_factor, float shift_factor, void* stream) {
+  TD_CHECK_ARG(packed && out, "td_vae_latents_to_nhwc_bf16: null argument");
+  TD_CHECK_ARG(h > 0 && w > 0, "td_vae_latents_to_nhwc_bf16: h=%d, w=%d must be positive (and even)", h, w);
+  return td_latents_to_nhwc_launch((const bf16_t*)packed, (bf16_t*)out, C, h, w, Cpad, scaling_factor, shift_factor, (hipStream_t)stream);
+}
+int td_vae_image_finalize(const void* x, int P, int Cpad, void* image_u8, void* image_chw, void* stream) {
+  TD_CHECK_ARG(x, "td_vae_image_finalize: null input");
+  TD_CHECK_ARG(image_u8 || image_chw, "td_vae_image_finalize: no output asked for (image_u8 and image_chw are both null)");
+  return td_image_finalize_launch((const bf16_t*)x, P, Cpad, (unsigned char*)image_u8, (bf16_t*)image_chw, (hipStream_t)stream);
 }
 int td_groupnorm_nhwc_bf16(const void* x, void* y, int P, int C, int groups, float eps, const void* gamma,
                            const void* beta, int silu, float* workspace, void* stream) {

@@ -173,6 +173,8 @@ def _declare(L):
         "td_conv3x3_nhwc_bf16": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
         "td_conv3x3_pack_weight": [vp, vp, i32, i32, i32, i32, vp],
         "td_conv3x3_s2_nhwc_bf16": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "td_vae_latents_to_nhwc_bf16": [vp, vp, i32, i32, i32, i32, f32, f32, vp],
+        "td_vae_image_finalize": [vp, i32, i32, vp, vp, vp],
         "td_vae_enc_create": [vp, i32, i32, vp],
         "td_vae_enc_num_params": [vp],
         "td_vae_enc_param_info": [vp, i32, ctypes.c_char_p, i32, vp],
@@ -1068,10 +1070,15 @@ class TdVaeConfig(ctypes.Structure):
                 ("block_out_channels", ctypes.c_int * 4), ("layers_per_block", ctypes.c_int), ("norm_groups", ctypes.c_int)]
 
 
-def conv3x3_nhwc(x, w_packed, bias, H, W, Cout, res=None, upsample2x=False):
-    """x [Hin*Win, Cin] bf16 NHWC, w_packed [Cout, 9*Cin] -> [H*W, Cout]"""
+def conv3x3_nhwc(x, w_packed, bias, H, W, Cout, res=None, upsample2x=False, out=None):
+    """x [Hin*Win, Cin] bf16 NHWC, w_packed [Cout, 9*Cin] -> [H*W, Cout].  out: the output buffer, which may be `res` itself (the VAE's
+    resnet adds its input in place)."""
     Cin = x.shape[1]
-    y = torch.empty(H * W, Cout, dtype=torch.bfloat16, device=x.device)
+    if out is None:
+        y = torch.empty(H * W, Cout, dtype=torch.bfloat16, device=x.device)
+    else:
+        assert out.shape == (H * W, Cout) and out.dtype == torch.bfloat16 and out.is_contiguous() and out.device == x.device
+        y = out
     check(lib().td_conv3x3_nhwc_bf16(ptr(x), ptr(w_packed), ptr(bias), ptr(res), ptr(y), H, W, Cin, Cout, int(upsample2x), stream_ptr()))
     return y
 
@@ -1112,6 +1119,26 @@ def conv3x3_pack_weight(w_oihw, Cout_pad=None, Cin_pad=None):
     out = torch.empty(Cout_pad, 9 * Cin_pad, dtype=torch.bfloat16, device=w_oihw.device)
     check(lib().td_conv3x3_pack_weight(ptr(w_oihw.contiguous()), ptr(out), Cout, Cin, Cout_pad, Cin_pad, stream_ptr()))
     return out
+
+
+def vae_latents_to_nhwc(packed, h, w, Cpad, scaling_factor, shift_factor):
+    """The first launch of td_vae_decode alone: packed FLUX latents [(h/2)(w/2), 4C] bf16 -> NHWC [h*w, Cpad] bf16,
+    `(unpack_latents(packed) / scaling_factor) + shift_factor` with the bf16 rounding points of the torch statement; channels >= C zero."""
+    assert packed.dtype == torch.bfloat16 and packed.is_contiguous() and packed.shape[0] == (h // 2) * (w // 2) and packed.shape[1] % 4 == 0
+    C = packed.shape[1] // 4
+    out = torch.empty(h * w, Cpad, dtype=torch.bfloat16, device=packed.device)
+    check(lib().td_vae_latents_to_nhwc_bf16(ptr(packed), ptr(out), C, h, w, Cpad, float(scaling_factor), float(shift_factor), stream_ptr()))
+    return out
+
+
+def vae_image_finalize(x, u8=True, chw=True):
+    """The last launch of td_vae_decode alone: x [P, Cpad] bf16 NHWC (three live channels) -> (uint8 [P, 3] or None, bf16 [3, P] or None)."""
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and x.dim() == 2
+    P, Cpad = x.shape
+    o8 = torch.empty(P, 3, dtype=torch.uint8, device=x.device) if u8 else None
+    oc = torch.empty(3, P, dtype=torch.bfloat16, device=x.device) if chw else None
+    check(lib().td_vae_image_finalize(ptr(x), P, Cpad, ptr(o8), ptr(oc), stream_ptr()))
+    return o8, oc
 
 
 def groupnorm_nhwc(x, gamma, beta, groups=32, eps=1e-6, silu=False):
